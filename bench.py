@@ -17,6 +17,11 @@ predict (RCCL over xGMI).  Rank 0 prints one JSON line.
 
     python bench.py --mode train [--steps 5]     one train! iteration (src/optimisers.jl:40-80) per step: setparams!,
                                                  fit!, mll, updategradients!, grad of the tree mll, stateless-ADAM step
+
+    --dump-outputs DIR   after the run, rank 0 writes what the LAST TIMED step returned as DIR/<name>.npy (float64):
+                         fit_predict: mu, var (predictive moments of the n_t test rows), root_mll, leaf_mll;
+                         train: hyperparameters (after the step's ADAM update), mll, gradient.
+                         The inputs come from fixed seeds: two builds run with the same arguments compare file for file.
 """
 import argparse
 import json
@@ -376,6 +381,7 @@ def bench_train(args, model, X, y, rank, world, td, torch):
     ctx.set_profile(1)
     opt = dsm.ADAM()
     hyp = dsm.getparams(model).copy()
+    last_grad = [None]
 
     def iteration(h):
         t = {}
@@ -387,6 +393,7 @@ def bench_train(args, model, X, y, rank, world, td, torch):
         dsm.updategradients(model)
         c_ = time.perf_counter()
         g = dsm.grad_mll(model)
+        last_grad[0] = g
         h = h + opt.apply(h, g)
         d = time.perf_counter()
         t.update(fit_wall=b - a, grad_wall=c_ - b, tree_wall=d - c_, mll=ell)
@@ -449,10 +456,27 @@ def bench_train(args, model, X, y, rank, world, td, torch):
                                                  "tile_reduce_kernel launches of dsmgp_gradients, n^3/3 flops per factor"}
             out["roofline_fit_update"] = {"achieved": fl_upd / dev["chol_update"] / 1e12 if dev.get("chol_update") else None,
                                           "unit": "TFLOP/s", "kernel": "update launches of fit! inside the iteration"}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"hyperparameters": hyp, "mll": hist[-1], "gradient": last_grad[0]})
         print(json.dumps(out))
     if td is not None:
         td.barrier()
         td.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64.  The inputs come from fixed seeds, so two builds run with the same
+    arguments can be compared file for file."""
+    arrays = {k: np.array(v, dtype=np.float64, ndmin=1) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the limit of {DUMP_LIMIT_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def spread(v):
@@ -556,7 +580,12 @@ def main():
     ap.add_argument("--simulate-shard", default=None, metavar="R/W",
                     help="diagnostic: run only rank R's leaf shard of a W-rank job on this one GPU (no exchange; "
                          "not a valid bench line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64; rank 0), "
+                         "to compare two builds output for output on the same seeded inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ and not args.simulate_shard:
         self_launch(args)                       # does not return
@@ -713,6 +742,9 @@ def main():
             step_clock.append(ctx.clock_sample_read()[0])
     sync_all()
     elapsed = time.perf_counter() - t0
+    # copies of the last timed step's results: the untimed steps below overwrite them
+    outputs = ({"mu": np.copy(mu), "var": np.copy(var), "root_mll": root[0], "leaf_mll": np.copy(model.leaf_mll)}
+               if args.dump_outputs else None)
     probe_after = ctx.probe_f64_mfma_detail(8) if can_probe else None
     xs1, xn1 = model.shard.exchange_seconds, model.shard.exchanges
     if not args.no_profile:   # one more, untimed, step with every category timed: the breakdown printed below
@@ -956,6 +988,8 @@ def main():
                 out["speedup_vs_cpu_baseline"] = out["cpu_baseline"]["value"] / per_step
             except Exception as e:      # noqa: BLE001
                 out["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
     if td is not None:
         td.barrier()

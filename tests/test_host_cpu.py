@@ -544,25 +544,18 @@ def test_julia_binding_matches_the_header():
     assert "kind(::IsoSE) = Int32(0)" in src and "kind(::ArdSE) = Int32(1)" in src and "kind(::IsoLinear) = Int32(2)" in src
 
 
-def test_julia_binding_names_exist_in_the_reference():
-    """Build container only (the reference does not travel): every name the binding imports from DeepStructuredMixtures is
-    defined there, every method it extends exists with that many positional arguments, and every field it reads off a
-    reference struct is declared in one (`src/fit.jl:71,294,306`, `src/gaussianprocess.jl:82,131,163,185`,
-    `src/common.jl:304-307`)."""
-    import glob
+def test_julia_binding_names_exist_in_the_reference(golden_dir):
+    """Every name the binding imports from DeepStructuredMixtures is defined there, every method it extends exists with that
+    many positional arguments, and every field it reads off a reference struct is declared in one (`src/fit.jl:71,294,306`,
+    `src/gaussianprocess.jl:82,131,163,185`, `src/common.jl:304-307`).  The reference's side is the name index
+    tests/golden/reference_api.json (tests/golden/make_reference_api.py)."""
+    import json
     import re
-    refdir = "/root/reference/src"
-    if not os.path.isdir(refdir):
-        pytest.skip("reference sources are not on this machine")
-    ref = "\n".join(open(f, encoding="utf-8").read() for f in sorted(glob.glob(os.path.join(refdir, "*.jl"))))
+    api = json.load(open(os.path.join(golden_dir, "reference_api.json"), encoding="utf-8"))
+    assert len(api["defined"]) >= 100 and len(api["arities"]) >= 100 and len(api["struct_fields"]) >= 30
     src = open(os.path.join(ROOT, "julia", "DSMGPHip.jl"), encoding="utf-8").read()
     ident = r"[A-Za-z_∇∂ℓσϵμ][\w!∇∂ℓσϵμ²]*"
-
-    def defined(name):
-        n = re.escape(name)
-        return bool(re.search(rf"(?m)^\s*(?:@inline\s+)?function\s+(?:\w+\.)?{n}\s*[({{]", ref) or re.search(rf"(?m)^\s*(?:@inline\s+)?(?:\w+\.)?{n}\([^)\n]*\)\s*(?:where[^=\n]*)?=", ref)
-                    or re.search(rf"(?m)^\s*(?:mutable\s+)?struct\s+{n}\b", ref) or re.search(rf"(?m)^\s*abstract\s+type\s+{n}\b", ref)
-                    or re.search(rf"(?m)^\s*const\s+{n}\b", ref))
+    names = set(api["defined"])
 
     imported = []
     for m in re.finditer(r"(?m)^(?:import|using) DeepStructuredMixtures: ((?:[^\n]*,\s*\n)*[^\n]*)", src):
@@ -570,26 +563,15 @@ def test_julia_binding_names_exist_in_the_reference():
     assert len(imported) >= 20
     third_party = {"children", "logweights", "BiDict"}        # SumProductNetworks.jl / the package's own re-exports
     for name in imported:
-        assert defined(name) or name in third_party, f"{name} is imported from DeepStructuredMixtures but not defined in /root/reference/src"
-    assert re.search(r"BiDict", ref) and re.search(r"\bchildren\(", ref) and re.search(r"\blogweights\b", ref)
+        assert name in names or name in third_party, f"{name} is imported from DeepStructuredMixtures but not defined in its src/"
+    assert api["mentions"]["BiDict"] and api["mentions"]["children("] and api["mentions"]["logweights"]
 
     def positional_arity(sig):
         args = sig.split(";")[0]
         return len([a for a in _split_top(args) if a])
 
     def ref_arities(name):
-        out = set()
-        for m in re.finditer(rf"(?m)^\s*(?:@inline\s+)?function\s+(?:\w+\.)?{re.escape(name)}\s*\(", ref):
-            i = m.end()
-            depth, j = 1, i
-            while depth:
-                depth += ref[j] == "("
-                depth -= ref[j] == ")"
-                j += 1
-            out.add(positional_arity(ref[i:j - 1]))
-        for m in re.finditer(rf"(?m)^\s*(?:@inline\s+)?(?:\w+\.)?{re.escape(name)}\(([^)\n]*)\)\s*(?:where[^=\n]*)?=", ref):
-            out.add(positional_arity(m.group(1)))
-        return out
+        return set(api["arities"].get(name, []))
 
     extended = re.search(r"(?m)^import DeepStructuredMixtures: ([^\n]*)", src).group(1)
     extended = [t.strip() for t in extended.split(",")]
@@ -609,19 +591,14 @@ def test_julia_binding_names_exist_in_the_reference():
         assert mine <= theirs, f"{name}: the binding defines methods of {sorted(mine)} positional arguments, the reference has {sorted(theirs)}"
 
     # fields read off reference structs: declared as a field of some struct of the reference
-    fields = set()
-    for m in re.finditer(r"(?ms)^\s*(?:mutable\s+)?struct\s+[^\n]*\n(.*?)^\s*end", ref):
-        for line in m.group(1).splitlines():
-            mm = re.match(rf"\s*({ident})\s*(?:::|$)", line)
-            if mm:
-                fields.add(mm.group(1))
+    fields = set(api["struct_fields"])
     own = set(re.findall(r"(?m)^\s+(\w+)::", src[src.index("mutable struct Session"):src.index("const SESSIONS")]))
     base = {"jl", "so", "py", "md", "e", "c", "attach!", "DSMGPHip", "value"}     # file suffixes / doc text / Ref().value-like wrappers
     qualified = set(re.findall(rf"\bDeepStructuredMixtures\.({ident})", src))      # module-qualified calls: functions, not fields
     for name in qualified:
-        assert defined(name), f"DeepStructuredMixtures.{name} is called but not defined in /root/reference/src"
+        assert name in names, f"DeepStructuredMixtures.{name} is called but not defined in its src/"
     used = set(re.findall(rf"(?<![\w)])(?:{ident})\.({ident})", src)) - qualified
-    assert {"value"} <= fields or re.search(r"\.value\b", ref)                     # the reference's own parameter wrapper
+    assert {"value"} <= fields or api["mentions"][".value"]                        # the reference's own parameter wrapper
     unknown = sorted(f for f in used if f not in fields and f not in own and f not in base)
     assert not unknown, f"fields the binding reads that no struct of the reference declares: {unknown}"
 
@@ -1255,3 +1232,19 @@ def test_tree_builders_reproduce_the_committed_tables(golden_dir):
         for r, i in enumerate(reg):
             o = z[f"{name}/obs"][z[f"{name}/obs_ptr"][i]:z[f"{name}/obs_ptr"][i + 1]]
             assert np.array_equal(leaves[r * max(1, nk)].obs, o)
+
+
+def test_bench_dump_outputs_and_step_count_arguments(tmp_path):
+    """bench.py --dump-outputs writes one float64 DIR/<name>.npy per array and refuses more than 64 MB in all; --steps 0 is
+    refused before anything is run (the result line's ms_per_step divides by the step count)."""
+    import bench
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), {"mu": np.arange(5, dtype=np.float32), "root_mll": -3.5})
+    assert sorted(os.listdir(out)) == ["mu.npy", "root_mll.npy"]
+    mu, root = np.load(out / "mu.npy"), np.load(out / "root_mll.npy")
+    assert mu.dtype == np.float64 and np.array_equal(mu, np.arange(5)) and root.shape == (1,) and root[0] == -3.5
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not (tmp_path / "big").exists()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
