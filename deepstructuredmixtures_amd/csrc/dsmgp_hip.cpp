@@ -551,10 +551,12 @@ struct dsmgp_ctx {
     std::vector<int> gfrob_leaf;    // owner leaf of each frob task
     DevBuf<GradTask> gdot;
     std::vector<int> gdot_leaf;     // leaf of each graddot task
+    DevBuf<ArdLinTask> gardlin;     // ArdLinear leaves: column groups of L^-T (ardlin_quad_kernel)
+    std::vector<int> gardlin_leaf;  // leaf of each of them
     bool ard_true_gradient = false; // DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT
     int gstride = 2;                // doubles per contraction task in d_gpart
     std::vector<int> grad_src;      // per leaf: the leaf whose contraction it shares (COPY leaf with the same mean), or -1
-    double* d_gpart = nullptr;      // partial results: frob | graddot pairs | per-leaf dots
+    double* d_gpart = nullptr;      // partial results: frob | graddot pairs | per-leaf dots | ArdLinear quadratic forms (2 D per task)
     size_t gpart_count = 0, gpart_cap = 0;
 
     // multi-GPU exchange over RCCL (dsmgp_comm_*, dsmgp_allgather): librccl.so is loaded on first use
@@ -736,6 +738,7 @@ void free_grad_lists(dsmgp_ctx* c) {
     dev_drop(c->gred, true);
     dev_drop(c->gfrob, true);
     dev_drop(c->gdot, true);
+    dev_drop(c->gardlin, true);
     c->grad_ready = false;
 }
 
@@ -749,6 +752,7 @@ void free_grad(dsmgp_ctx* c) {
     dev_free(c->gred);
     dev_free(c->gfrob);
     dev_free(c->gdot);
+    dev_free(c->gardlin);
     dev_free(c->d_gpart);
     c->gpart_cap = 0;
     c->grad_ready = false;
@@ -889,12 +893,18 @@ int upload_hyper(dsmgp_ctx* c) {
         kp[k].nl = nl;
         const double logs = h.loghyp[nl];
         const double logn = h.loghyp[nl + 1];
-        kp[k].sigma2 = (h.kind == DSMGP_KIND_ISO_LINEAR) ? 1.0 : std::exp(2.0 * logs);
-        kp[k].sigma = (h.kind == DSMGP_KIND_ISO_LINEAR) ? 1.0 : std::exp(logs);
+        const bool linear = h.kind == DSMGP_KIND_ISO_LINEAR || h.kind == DSMGP_KIND_ARD_LINEAR;   // no signal variance
+        kp[k].sigma2 = linear ? 1.0 : std::exp(2.0 * logs);
+        kp[k].sigma = linear ? 1.0 : std::exp(logs);
         kp[k].noise = std::exp(2.0 * logn);
     }
     const size_t nslots = l2pool.size();
-    for (size_t i = 0; i < nslots; ++i) l2pool.push_back(-0.5 / l2pool[i]);   // second half: the exponent's factor
+    // second half (KParam.nh): the per-dimension factor -- of the exponent, -0.5 / l^2, or of ArdLinear's product, 1 / l_d^2
+    std::vector<char> slot_ard_linear(nslots, 0);
+    for (int k = 0; k < nk; ++k)
+        if (c->hyper[k].kind == DSMGP_KIND_ARD_LINEAR)
+            for (size_t i = off[k]; i < off[k] + c->hyper[k].loghyp.size() - 2; ++i) slot_ard_linear[i] = 1;
+    for (size_t i = 0; i < nslots; ++i) l2pool.push_back(slot_ard_linear[i] ? 1.0 / l2pool[i] : -0.5 / l2pool[i]);
     if (l2pool.size() > c->l2_cap || !c->d_l2) {   // (re)allocate only when the table grows: fit is called in loops
         drop_graphs(c);
         dev_free(c->d_l2);
@@ -921,6 +931,12 @@ int upload_hyper(dsmgp_ctx* c) {
     return 0;
 }
 
+// an ArdLinear kernel id reads D per-dimension factors wherever its kernel function is evaluated
+bool ard_linear_short(const dsmgp_ctx* c, int kid) {
+    const HyperHost& h = c->hyper[kid];
+    return h.kind == DSMGP_KIND_ARD_LINEAR && (int)h.loghyp.size() - 2 != c->D;
+}
+
 int check_hyper(dsmgp_ctx* c) {
     for (int l = 0; l < c->L; ++l) {
         const int kid = c->leaves[l].kid;
@@ -929,9 +945,11 @@ int check_hyper(dsmgp_ctx* c) {
                                               " without hyper-parameters");
         const HyperHost& h = c->hyper[kid];
         const int nl = (int)h.loghyp.size() - 2;
-        if (h.kind == DSMGP_KIND_ARD_SE && nl != c->D)
-            return fail(c, DSMGP_E_ARG, "ArdSE needs one lengthscale per input dimension");
-        if (h.kind != DSMGP_KIND_ARD_SE && nl != 1) return fail(c, DSMGP_E_ARG, "Iso kernels take one lengthscale");
+        const bool ard = h.kind == DSMGP_KIND_ARD_SE || h.kind == DSMGP_KIND_ARD_LINEAR;
+        if (ard && nl != c->D)
+            return fail(c, DSMGP_E_ARG, std::string(h.kind == DSMGP_KIND_ARD_SE ? "ArdSE" : "ArdLinear") +
+                                            " needs one lengthscale per input dimension");
+        if (!ard && nl != 1) return fail(c, DSMGP_E_ARG, "Iso kernels take one lengthscale");
     }
     return 0;
 }
@@ -2247,11 +2265,11 @@ int dsmgp_set_sharing(dsmgp_ctx* c, const int32_t* op, const int32_t* src, const
 int dsmgp_set_hyper(dsmgp_ctx* c, int32_t kernel_id, int32_t kind, const double* loghyp, int32_t n) {
     if (!c) return DSMGP_E_ARG;
     if (kernel_id < 0 || kernel_id >= DSMGP_MAX_KERNEL_IDS || !loghyp || n < 3) return fail(c, DSMGP_E_ARG, "set_hyper: bad arguments");
-    if (kind < 0 || kind > 2) return fail(c, DSMGP_E_ARG, "set_hyper: unknown kernel kind");
+    if (kind < 0 || kind > DSMGP_KIND_ARD_LINEAR) return fail(c, DSMGP_E_ARG, "set_hyper: unknown kernel kind");
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(loghyp[i])) return fail(c, DSMGP_E_ARG, "set_hyper: non-finite hyper-parameter");
     if ((int)c->hyper.size() <= kernel_id) c->hyper.resize(kernel_id + 1);
-    if (c->hyper[kernel_id].kind != kind) free_grad(c);   // the contraction tiles depend on the kernel kind
+    if (c->hyper[kernel_id].kind != kind) free_grad(c);   // the contraction tiles / ArdLinear tasks depend on the kernel kind
     c->hyper[kernel_id].kind = kind;
     c->hyper[kernel_id].loghyp.assign(loghyp, loghyp + n);
     c->fitted = false;
@@ -3108,6 +3126,8 @@ int dsmgp_aggregate_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain
     if (c->agg_family == AGG_RBCM &&
         (prior_kernel_id < 0 || prior_kernel_id >= (int)c->hyper.size() || c->hyper[prior_kernel_id].kind < 0))
         return fail(c, DSMGP_E_ARG, "aggregate_finish: rBCM needs the kernel id of the model's first leaf");
+    if (c->agg_family == AGG_RBCM && ard_linear_short(c, prior_kernel_id))
+        return fail(c, DSMGP_E_ARG, "aggregate_finish: ArdLinear needs one lengthscale per input dimension");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nt = (size_t)c->n_t;
     const size_t nblk = (nt + 255) / 256;
@@ -3395,7 +3415,43 @@ int build_grad_plan(dsmgp_ctx* c) {
     if (any_ard && c->D > GRADDOT_STAGE_D)
         return fail(c, DSMGP_E_ARG, "ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
     c->gstride = any_ard ? 2 + c->D : 2;
-    c->gpart_count = frob.size() + (size_t)c->gstride * gd.size() + 2 * (size_t)L;
+
+    // ArdLinear leaves: ARDLIN_COLS columns of L^-T per task (a COPY leaf with its source's mean takes the source's sums,
+    // as for the contraction), the tasks of the longest columns first
+    std::vector<ArdLinTask> al;
+    c->gardlin_leaf.clear();
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR || c->grad_src[l] >= 0 || !needC[l]) continue;
+        const LeafDev& d = c->h_leaves[l];
+        for (int c0 = 0; c0 < lf.n; c0 += ARDLIN_COLS) {
+            ArdLinTask a{};
+            a.Xt = Xt(l);
+            a.x = d.Xg;
+            a.alpha = d.alpha;
+            a.ldt = c->leaves[lf.owner].npad;
+            a.ldx = lf.npad;
+            a.c0 = c0;
+            a.n = lf.n;
+            al.push_back(a);
+            c->gardlin_leaf.push_back(l);
+        }
+    }
+    {
+        std::vector<size_t> ord(al.size());
+        for (size_t i = 0; i < ord.size(); ++i) ord[i] = i;
+        std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return al[a].c0 > al[b].c0; });
+        std::vector<ArdLinTask> al2(al.size());
+        std::vector<int> leaf2(al.size());
+        for (size_t i = 0; i < ord.size(); ++i) {
+            al2[i] = al[ord[i]];
+            leaf2[i] = c->gardlin_leaf[ord[i]];
+        }
+        al.swap(al2);
+        c->gardlin_leaf.swap(leaf2);
+    }
+    if (int rc = dev_upload(c, c->gardlin, al)) return rc;
+    c->gpart_count = frob.size() + (size_t)c->gstride * gd.size() + 2 * (size_t)L + 2 * (size_t)c->D * al.size();
     if (int rc = dev_grow(c, c->d_gpart, c->gpart_cap, c->gpart_count)) return rc;
     c->grad_ready = true;
     return 0;
@@ -3480,6 +3536,10 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     HIPCHK(c, hipEventRecord(e_dot.a, c->stream));
     if (c->gfrob.count) frob_kernel<<<(int)c->gfrob.count, 256, 0, c->stream>>>(c->gfrob.p, pfrob);
     dots_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves, pleaf);
+    double* pardlin = pleaf + 2 * (size_t)L;
+    if (c->gardlin.count)
+        ardlin_quad_kernel<<<dim3((unsigned)c->gardlin.count, (unsigned)((c->D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
+            c->gardlin.p, c->D, pardlin);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(t1, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3518,6 +3578,24 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
                 for (int d = 0; d < c->D; ++d) Sd[(size_t)l * c->D + d] = Sd[(size_t)c->grad_src[l] * c->D + d];
         }
     const double* pl = pd + gs * c->gdot.count;
+    // ArdLinear: S_d = (alpha . x_d)^2 - |L^-1 x_d|^2 per leaf, the task sums added in list order
+    std::vector<double> Sl((size_t)L * c->D, 0.0);
+    if (c->gardlin.count) {
+        const size_t D = (size_t)c->D;
+        std::vector<double> A((size_t)L * D, 0.0), Q((size_t)L * D, 0.0);
+        const double* pq = pl + 2 * (size_t)L;
+        for (size_t i = 0; i < c->gardlin.count; ++i) {
+            const size_t l = (size_t)c->gardlin_leaf[i];
+            for (size_t d = 0; d < D; ++d) {
+                A[l * D + d] += pq[2 * D * i + d];
+                Q[l * D + d] += pq[2 * D * i + D + d];
+            }
+        }
+        for (int l = 0; l < L; ++l) {
+            const int s = c->grad_src[l] >= 0 ? c->grad_src[l] : l;      // copygradients (src/fit.jl:352-356)
+            for (size_t d = 0; d < D; ++d) Sl[l * D + d] = A[s * D + d] * A[s * D + d] - Q[s * D + d];
+        }
+    }
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
         const HyperHost& h = c->hyper[lf.kid];
@@ -3541,9 +3619,14 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
             for (int d = 0; d < nl; ++d)                      // src/kernels.jl:161: identically zero unless the
                 g[d] = (c->ard_true_gradient && gs > 2) ? 0.5 * Sd[(size_t)l * c->D + d] : 0.0;   // true gradient is asked for
             g[nl] = sigma * trPK;                             // src/kernels.jl:157
-        } else {
+        } else if (h.kind == DSMGP_KIND_ISO_LINEAR) {
             g[0] = -trPK;                                     // src/kernels.jl:198
             g[1] = 0.0;                                       // src/kernels.jl:201
+        } else if (h.kind == DSMGP_KIND_ARD_LINEAR) {
+            // the true derivative -S_d / l_d^2 (src/kernels.jl:234-246 is the same trace with kappa = z / l_d and does not run;
+            // DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT is about ArdSE only); no variance gradient (the slot is a dummy, :216-218)
+            for (int d = 0; d < nl; ++d) g[d] = -Sl[(size_t)l * c->D + d] / std::exp(2.0 * h.loghyp[d]);
+            g[nl] = 0.0;
         }
         g[nl + 1] = noise * (aa - trK[l]);                    // src/gaussianprocess.jl:176
     }
@@ -3557,6 +3640,7 @@ int dsmgp_kernel_matrix(dsmgp_ctx* c, int32_t kernel_id, const double* x1, int64
     if (!x1 || !x2 || !K_out || n1 <= 0 || n2 <= 0 || c->D <= 0) return fail(c, DSMGP_E_ARG, "kernel_matrix: bad arguments");
     if (kernel_id < 0 || kernel_id >= (int)c->hyper.size() || c->hyper[kernel_id].kind < 0)
         return fail(c, DSMGP_E_STATE, "kernel_matrix: kernel id without hyper-parameters");
+    if (ard_linear_short(c, kernel_id)) return fail(c, DSMGP_E_ARG, "kernel_matrix: ArdLinear needs one lengthscale per input dimension");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = upload_hyper(c)) return rc;
     const int D = c->D;

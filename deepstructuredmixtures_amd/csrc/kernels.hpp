@@ -45,11 +45,12 @@ typedef const double __attribute__((address_space(4)))* cf64_ptr;
 struct KParam {
     int kind;           // DSMGP_KIND_*
     int nl;             // number of lengthscales (1 for Iso, D for Ard)
-    double sigma2;      // exp(2 logs)  (1.0 for IsoLinear, src/kernels.jl:181)
+    double sigma2;      // exp(2 logs)  (1.0 for IsoLinear and ArdLinear, src/kernels.jl:181,216)
     double sigma;       // exp(logs)
     double noise;       // exp(2 logNoise)
     const double* l2;   // device: lengthscale^2 per slot
-    const double* nh;   // device: -0.5 / lengthscale^2 per slot (the factor of the exponent)
+    const double* nh;   // device: the per-dimension factor of the kernel function per slot: -0.5 / lengthscale^2 (the factor of
+                        //   the exponent; IsoSE, ArdSE), 1 / lengthscale^2 (ArdLinear)
     double nh0;         // nh[0]
     double il2;         // 1 / l2[0]
 };
@@ -99,7 +100,9 @@ struct GramTask {
 // one rounding of the exponent's argument apart: <= 4e-15 relative on the kernel value), with z accumulated
 // from direct differences (the reference's Distances.pairwise uses |a|^2+|b|^2-2a.b; same value up to
 // rounding).  ArdSE is the additive form sigma^2 * sum_d exp(-0.5 (a_d-b_d)^2 / l_d^2)
-// (src/kernels.jl:39-49).  IsoLinear is a.b / l^2 (src/kernels.jl:189-194).
+// (src/kernels.jl:39-49).  IsoLinear is a.b / l^2 (src/kernels.jl:189-194).  ArdLinear is sum_d (a_d b_d) / l_d^2, the
+// generic ArdKernel loop of src/kernels.jl:39-49 with kappa = z / l_d^2 (:228-229): per dimension the product a_d b_d, scaled
+// by 1 / l_d^2 and added in ascending d (one fma: bit-symmetric in a and b).
 template <int KIND>
 __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam& p, int D, int half,
                                                double (*sa)[TB], double (*sb)[TB / 2]) {
@@ -132,7 +135,7 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
         if (!rows_live) continue;
         for (int d = 0; d < dn; ++d) {
             const double a0 = sa[d][r0], a1 = sa[d][r0 + 1], a2 = sa[d][r0 + 2], a3 = sa[d][r0 + 3];
-            const double nhd = (KIND == 1) ? p.nh[d0 + d] : 0.0;   // -0.5 / l_d^2
+            const double nhd = (KIND == 1 || KIND == 3) ? p.nh[d0 + d] : 0.0;   // -0.5 / l_d^2, resp. 1 / l_d^2
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const double b = sb[d][cb + 8 * q];
@@ -148,11 +151,16 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
                     u = a1 - b; acc[q][1] += exp_nonpos((u * u) * nhd);
                     u = a2 - b; acc[q][2] += exp_nonpos((u * u) * nhd);
                     u = a3 - b; acc[q][3] += exp_nonpos((u * u) * nhd);
-                } else {
+                } else if (KIND == 2) {
                     acc[q][0] = fma(a0, b, acc[q][0]);
                     acc[q][1] = fma(a1, b, acc[q][1]);
                     acc[q][2] = fma(a2, b, acc[q][2]);
                     acc[q][3] = fma(a3, b, acc[q][3]);
+                } else {
+                    acc[q][0] = fma(a0 * b, nhd, acc[q][0]);
+                    acc[q][1] = fma(a1 * b, nhd, acc[q][1]);
+                    acc[q][2] = fma(a2 * b, nhd, acc[q][2]);
+                    acc[q][3] = fma(a3 * b, nhd, acc[q][3]);
                 }
             }
         }
@@ -169,7 +177,8 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
             double kv;
             if (KIND == 0) kv = p.sigma2 * exp_nonpos(acc[q][j] * nh);
             else if (KIND == 1) kv = p.sigma2 * acc[q][j];
-            else kv = acc[q][j] * il2;
+            else if (KIND == 2) kv = acc[q][j] * il2;
+            else kv = acc[q][j];
             const bool valid = (r < tk.na) && (c < tk.nb);
             if (!valid) kv = 0.0;
             if (tk.sym && tk.diag && r == c) kv = valid ? kv + (p.noise + 1e-8) : 1.0;
@@ -188,7 +197,8 @@ __global__ __launch_bounds__(256) void gram_tile_kernel(const GramTask* __restri
     const int half = blockIdx.x & 1;
     if (p.kind == 0) gram_half_tile<0>(tk, p, D, half, sa, sb);
     else if (p.kind == 1) gram_half_tile<1>(tk, p, D, half, sa, sb);
-    else gram_half_tile<2>(tk, p, D, half, sa, sb);
+    else if (p.kind == 2) gram_half_tile<2>(tk, p, D, half, sa, sb);
+    else if (p.kind == 3) gram_half_tile<3>(tk, p, D, half, sa, sb);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -305,8 +315,10 @@ __device__ __forceinline__ void gram_accumulate(double (&z)[NA][NB], const doubl
             } else if (KIND == 1) {
                 const double u = a[i] - b[j];
                 z[i][j] += exp_nonpos((u * u) * nhd);
-            } else {
+            } else if (KIND == 2) {
                 z[i][j] = fma(a[i], b[j], z[i][j]);
+            } else {
+                z[i][j] = fma(a[i] * b[j], nhd, z[i][j]);
             }
         }
 }
@@ -318,7 +330,8 @@ __device__ __forceinline__ double gram_finish(double z, const KParam& p, int row
     double kv;
     if (KIND == 0) kv = p.sigma2 * exp_nonpos(z * p.nh0);
     else if (KIND == 1) kv = p.sigma2 * z;
-    else kv = z * p.il2;
+    else if (KIND == 2) kv = z * p.il2;
+    else kv = z;
     if (!EDGE) return kv;
     const bool valid = (row < na) && (col < nb);
     if (!valid) kv = 0.0;
@@ -353,7 +366,7 @@ __device__ __forceinline__ void gram_tile_epilogue(const TileTask& tk, const KPa
                 a[i] = pa[d * TB + 16 * i];
                 b[i] = pb[d * TB + 4 * i];
             }
-            gram_accumulate<KIND, 4, 4>(z, a, b, (KIND == 1) ? p.nh[d] : 0.0);
+            gram_accumulate<KIND, 4, 4>(z, a, b, (KIND == 1 || KIND == 3) ? p.nh[d] : 0.0);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -382,9 +395,12 @@ __device__ __forceinline__ void tile_epilogue(const TileTask& tk, d4 (&acc)[4][4
         } else if (p.kind == 1) {
             if (edge) gram_tile_epilogue<1, true>(tk, p, D, acc, red, sb);
             else gram_tile_epilogue<1, false>(tk, p, D, acc, red, sb);
-        } else {
+        } else if (p.kind == 2) {
             if (edge) gram_tile_epilogue<2, true>(tk, p, D, acc, red, sb);
             else gram_tile_epilogue<2, false>(tk, p, D, acc, red, sb);
+        } else if (p.kind == 3) {
+            if (edge) gram_tile_epilogue<3, true>(tk, p, D, acc, red, sb);
+            else gram_tile_epilogue<3, false>(tk, p, D, acc, red, sb);
         }
         return;
     }
@@ -800,7 +816,7 @@ __device__ __forceinline__ void syrk_gram_epilogue(const TileTask& tk, const KPa
 #pragma unroll
             for (int r = 0; r < 4; ++r) z[j][0][r] = 0.0;
         for (int d = 0; d < D; ++d) {
-            const double nhd = (KIND == 1) ? p.nh[d] : 0.0;
+            const double nhd = (KIND == 1 || KIND == 3) ? p.nh[d] : 0.0;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 double a[1], b[4];
@@ -830,7 +846,8 @@ __device__ __forceinline__ void syrk_finish(const TileTask& tk, d4 (&acc)[9], co
         gram_stage_coords(tk, D, sa, nullptr, false);
         if (p.kind == 0) syrk_gram_epilogue<SHAPE, 0>(tk, p, D, acc, blk, sa);
         else if (p.kind == 1) syrk_gram_epilogue<SHAPE, 1>(tk, p, D, acc, blk, sa);
-        else syrk_gram_epilogue<SHAPE, 2>(tk, p, D, acc, blk, sa);
+        else if (p.kind == 2) syrk_gram_epilogue<SHAPE, 2>(tk, p, D, acc, blk, sa);
+        else if (p.kind == 3) syrk_gram_epilogue<SHAPE, 3>(tk, p, D, acc, blk, sa);
     } else {
         syrk_epilogue<SHAPE>(tk, acc, blk);
     }
@@ -998,7 +1015,7 @@ __device__ __forceinline__ void rows_gram_epilogue(const TileTask& tk, const KPa
             for (int i = 0; i < NR; ++i) a[i] = pa[d * TB + 16 * i];
 #pragma unroll
             for (int i = 0; i < 4; ++i) b[i] = pb[d * TB + 4 * i];
-            gram_accumulate<KIND, NR, 4>(z, a, b, (KIND == 1) ? p.nh[d] : 0.0);
+            gram_accumulate<KIND, NR, 4>(z, a, b, (KIND == 1 || KIND == 3) ? p.nh[d] : 0.0);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1030,7 +1047,8 @@ __device__ __forceinline__ void tile_rows_body(const TileTask& tk, double (*sA)[
         gram_stage_coords(tk, D, &sA[0][0], &sB[0][0], true);
         if (p.kind == 0) rows_gram_epilogue<NR, 0>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
         else if (p.kind == 1) rows_gram_epilogue<NR, 1>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
-        else rows_gram_epilogue<NR, 2>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
+        else if (p.kind == 2) rows_gram_epilogue<NR, 2>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
+        else if (p.kind == 3) rows_gram_epilogue<NR, 3>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -2364,13 +2382,19 @@ __global__ __launch_bounds__(128) void pred_finish_kernel(const LeafDev* __restr
     double kss;
     if (p.kind == 0) kss = p.sigma2;
     else if (p.kind == 1) kss = p.sigma2 * (double)D;
-    else {
+    else if (p.kind == 2) {
         double q = 0.0;
         for (int d = 0; d < D; ++d) {
             const double x = lf.Xtg[r + (size_t)d * lf.ntpad];
             q = fma(x, x, q);
         }
         kss = q / p.l2[0];
+    } else {
+        kss = 0.0;          // ArdLinear: k(x*, x*) with the operations of gram_accumulate<3>
+        for (int d = 0; d < D; ++d) {
+            const double x = lf.Xtg[r + (size_t)d * lf.ntpad];
+            kss = fma(x * x, p.nh[d], kss);
+        }
     }
     lf.mu[r] = lf.mean + lf.macc[r];
     lf.var[r] = (kss - lf.sacc[r]) + p.noise;
@@ -2396,13 +2420,19 @@ __global__ __launch_bounds__(256) void pred_var_kernel(const LeafDev* __restrict
         double kss;
         if (p.kind == 0) kss = p.sigma2;
         else if (p.kind == 1) kss = p.sigma2 * (double)D;
-        else {
+        else if (p.kind == 2) {
             double q = 0.0;
             for (int d = 0; d < D; ++d) {
                 const double x = lf.Xtg[tk.row0 + t + (size_t)d * lf.ntpad];
                 q = fma(x, x, q);
             }
             kss = q / p.l2[0];
+        } else {
+            kss = 0.0;      // ArdLinear (gram_accumulate<3>)
+            for (int d = 0; d < D; ++d) {
+                const double x = lf.Xtg[tk.row0 + t + (size_t)d * lf.ntpad];
+                kss = fma(x * x, p.nh[d], kss);
+            }
         }
         lf.var[tk.row0 + t] = (kss - red[t]) + p.noise;
     }
@@ -2431,6 +2461,71 @@ __global__ __launch_bounds__(256) void dots_kernel(const LeafDev* __restrict__ l
     if (t == 0) {
         out[2 * blockIdx.x] = r1[0];
         out[2 * blockIdx.x + 1] = r2[0];
+    }
+}
+
+// ArdLinear length-scale gradients (dsmgp_gradients).  dK / dlog l_d = -2 x_d x_d^T / l_d^2 for k(a, b) = sum_d a_d b_d / l_d^2,
+// so 0.5 tr((alpha alpha^T - K_y^-1) dK / dlog l_d) = -((alpha . x_d)^2 - |L^-1 x_d|^2) / l_d^2: two quadratic forms per
+// dimension, the second one a skinny product of the L^-T arena (filled for tr K_y^-1) with the leaf's n x D inputs --
+// n^2 D flops per leaf, each stored entry of L^-T read once per group of ARDLIN_DC dimensions, no n^3 contraction.
+// One task = ARDLIN_COLS consecutive columns c of L^-T (rows i <= c: what the inversion wrote), blockIdx.y = a group of
+// ARDLIN_DC dimensions.  out[task * 2 D + d] = sum_c alpha_c x_cd, out[task * 2 D + D + d] = sum_c (sum_{i<=c} Xt(i, c) x_id)^2
+// over the task's columns; the host adds the tasks of a leaf in list order (fixed: bit-reproducible).
+struct ArdLinTask {
+    const double* Xt;       // L^-T of the leaf's factor owner, column-major (ld = ldt)
+    const double* x;        // the leaf's inputs, npad x D (ld = ldx)
+    const double* alpha;
+    int ldt, ldx;
+    int c0;                 // first column of the task
+    int n;                  // leaf size (columns c0 .. min(c0 + ARDLIN_COLS, n) - 1)
+};
+constexpr int ARDLIN_COLS = 8;
+constexpr int ARDLIN_DC = 8;
+__global__ __launch_bounds__(256) void ardlin_quad_kernel(const ArdLinTask* __restrict__ tasks, int D, double* __restrict__ out) {
+    __shared__ double red[4][ARDLIN_COLS * ARDLIN_DC];
+    const ArdLinTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int d0 = blockIdx.y * ARDLIN_DC;
+    const int dn = min(ARDLIN_DC, D - d0);
+    const int nc = min(ARDLIN_COLS, tk.n - tk.c0);
+    const int rend = tk.c0 + nc;                // rows 0 .. rend - 1: row i enters column c for i <= c only
+    double acc[ARDLIN_COLS][ARDLIN_DC];
+#pragma unroll
+    for (int j = 0; j < ARDLIN_COLS; ++j)
+#pragma unroll
+        for (int k = 0; k < ARDLIN_DC; ++k) acc[j][k] = 0.0;
+    for (int i = t; i < rend; i += 256) {
+        double xv[ARDLIN_DC], v[ARDLIN_COLS];
+#pragma unroll
+        for (int k = 0; k < ARDLIN_DC; ++k) xv[k] = (k < dn) ? tk.x[i + (size_t)(d0 + k) * tk.ldx] : 0.0;
+#pragma unroll
+        for (int j = 0; j < ARDLIN_COLS; ++j) v[j] = (j < nc && i <= tk.c0 + j) ? tk.Xt[i + (size_t)(tk.c0 + j) * tk.ldt] : 0.0;
+#pragma unroll
+        for (int j = 0; j < ARDLIN_COLS; ++j)
+#pragma unroll
+            for (int k = 0; k < ARDLIN_DC; ++k) acc[j][k] = fma(v[j], xv[k], acc[j][k]);
+    }
+    // (L^-1 x_d)_c: over the lanes of each wave (fixed butterfly), then over the four waves in order
+#pragma unroll
+    for (int j = 0; j < ARDLIN_COLS; ++j)
+#pragma unroll
+        for (int k = 0; k < ARDLIN_DC; ++k) {
+            double s = acc[j][k];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (lane == 0) red[w][j * ARDLIN_DC + k] = s;
+        }
+    __syncthreads();
+    if (t < dn) {
+        double q = 0.0, a = 0.0;
+        for (int j = 0; j < nc; ++j) {
+            const int e = j * ARDLIN_DC + t;
+            const double s = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+            q = fma(s, s, q);
+            a = fma(tk.alpha[tk.c0 + j], tk.x[tk.c0 + j + (size_t)(d0 + t) * tk.ldx], a);
+        }
+        out[(size_t)blockIdx.x * 2 * D + d0 + t] = a;
+        out[(size_t)blockIdx.x * 2 * D + D + d0 + t] = q;
     }
 }
 
@@ -2524,13 +2619,19 @@ __global__ __launch_bounds__(256) void agg_finish_kernel(const double* __restric
         double kss;
         if (p.kind == 0) kss = p.sigma2;
         else if (p.kind == 1) kss = p.sigma2 * (double)D;
-        else {
+        else if (p.kind == 2) {
             double q = 0.0;
             for (int d = 0; d < D; ++d) {
                 const double x = Xt[r + (size_t)d * n_t];
                 q = fma(x, x, q);
             }
             kss = q / p.l2[0];
+        } else {
+            kss = 0.0;      // ArdLinear (gram_accumulate<3>)
+            for (int d = 0; d < D; ++d) {
+                const double x = Xt[r + (size_t)d * n_t];
+                kss = fma(x * x, p.nh[d], kss);
+            }
         }
         const double s = kss + p.noise;
         double C = 1.0 / s, m = 0.0;

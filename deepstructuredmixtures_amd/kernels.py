@@ -14,6 +14,7 @@ import numpy as np
 KIND_ISO_SE = 0
 KIND_ARD_SE = 1
 KIND_ISO_LINEAR = 2
+KIND_ARD_LINEAR = 3
 
 
 class KernelFunction:
@@ -100,6 +101,30 @@ class IsoLinear(KernelFunction):
 
     def __repr__(self):
         return f"IsoLinear({self.logl})"
+
+
+class ArdLinear(KernelFunction):
+    """k(a,b) = sum_d a_d b_d / exp(logl_d)^2 over the D input dimensions; the variance slot is a dummy
+    (`src/kernels.jl:209-230` through the generic ArdKernel loop `:39-49`).  The reference's own ArdLinear cannot be fitted
+    (`:232,247`); this is the kernel its generic code states.  Length-scale gradients are the true derivatives of the
+    log-marginal (include/dsmgp_hip.h, dsmgp_gradients)."""
+    kind = KIND_ARD_LINEAR
+
+    def __init__(self, logl):
+        self.logl = np.array(logl, dtype=np.float64).reshape(-1)
+        self.dl = np.zeros_like(self.logl)
+
+    def loghyp(self):
+        return np.concatenate([self.logl, [0.0]])
+
+    def set_loghyp(self, v):
+        self.logl = np.array(v[:-1], dtype=np.float64)  # setvariance! is a no-op (`src/kernels.jl:218`)
+
+    def copy(self):
+        return ArdLinear(self.logl.copy())
+
+    def __repr__(self):
+        return f"ArdLinear({self.logl.tolist()})"
 
 
 class ConstMean:

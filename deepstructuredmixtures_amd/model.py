@@ -17,7 +17,7 @@ except ImportError:          # pragma: no cover
     _xxhash = None
 
 from . import hipabi
-from .kernels import IsoSE, ConstMean, KIND_ISO_SE, KIND_ARD_SE, KIND_ISO_LINEAR
+from .kernels import IsoSE, ConstMean, KIND_ISO_SE, KIND_ARD_SE, KIND_ISO_LINEAR, KIND_ARD_LINEAR
 from .tree import (DSMGPConfig, GPSumNode, build_tree, get_leaves, get_overlap, obs_table, share_schedule, share_decisions,
                    share_census, route, route_all, route_index, get_child, ordered_nodes, SHARE_COPY, SHARE_FULL, SHARE_PREFIX)
 from . import dist as _dist
@@ -588,6 +588,8 @@ def updategradients(model, active=None):
         n = lf.kernel.nparams()
         if lf.kernel.kind == KIND_ISO_LINEAR:
             lf.kernel.dl = float(row[0])
+        elif lf.kernel.kind == KIND_ARD_LINEAR:       # [dl_1..dl_D, 0, dnoise]: no variance gradient
+            lf.kernel.dl = row[: n - 1].copy()
         else:
             lf.kernel.dl = row[: n - 1].copy() if lf.kernel.kind == KIND_ARD_SE else float(row[0])
             lf.kernel.ds = float(row[n - 1])
@@ -1159,6 +1161,8 @@ def _prior_diag(lf, xt):
         return np.full(xt.shape[0], np.exp(2 * k.logs))
     if k.kind == KIND_ARD_SE:
         return np.full(xt.shape[0], np.exp(2 * k.logs) * xt.shape[1])
+    if k.kind == KIND_ARD_LINEAR:
+        return (xt * xt) @ np.exp(-2.0 * k.logl)
     return np.sum(xt * xt, axis=1) / np.exp(k.logl) ** 2
 
 

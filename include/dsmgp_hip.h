@@ -28,10 +28,17 @@ extern "C" {
 
 typedef struct dsmgp_ctx dsmgp_ctx;
 
-/* kernel kinds (src/kernels.jl:59,109,174) */
+/* kernel kinds (src/kernels.jl:59,109,174,209) */
 #define DSMGP_KIND_ISO_SE     0
 #define DSMGP_KIND_ARD_SE     1   /* additive form, src/kernels.jl:39-49 */
 #define DSMGP_KIND_ISO_LINEAR 2
+/* ArdLinear: k(a, b) = sum_d a_d b_d / l_d^2, l_d = exp(logl_d), d = 1..D -- the generic ArdKernel loop of src/kernels.jl:39-49
+ * with getlengthscales(k).^2 and kappa = z -> z / l (:228-229), per entry the product a_d b_d scaled by 1 / l_d^2 and added in
+ * ascending d (k(a, b) == k(b, a) to the bit).  Exactly D length-scales; no signal variance: the variance slot of the
+ * hyper-vector [logl_1..logl_D, 0, logNoise] is a dummy (getvariance = 1, setvariance! a no-op, :216-218).  A repair: the
+ * reference's ArdLinear cannot be fitted (getdistancematrix returns a Vector{Matrix} no kernelmatrix method takes, :232;
+ * getgradients reads an undefined name, :247). */
+#define DSMGP_KIND_ARD_LINEAR 3
 
 /* per-leaf sharing decisions of the shared-Cholesky fit! (src/fit.jl:107-117) */
 #define DSMGP_SHARE_FULL   0      /* update_cholesky!               src/gaussianprocess.jl:82-108 */
@@ -151,7 +158,11 @@ int dsmgp_scores(dsmgp_ctx* ctx, const double* y_test /* n_t */, double* out /* 
 
 /* ---- updategradients!(gp) + grad vector of src/gaussianprocess.jl:165-178,185-217 per leaf.
  *      grad_out[l*stride + j], j over [dl..., ds, dnoise] (reference order, src/gaussianprocess.jl:212-214),
- *      reproducing the reference's scaling and ArdSE dl == 0. */
+ *      reproducing the reference's scaling and ArdSE dl == 0.
+ *      ArdLinear: [dl_1..dl_D, 0, dnoise] with the true derivative dl_d = 0.5 tr((alpha alpha^T - K_y^-1) dK/dlog l_d)
+ *      = -((alpha . x_d)^2 - x_d^T K_y^-1 x_d) / l_d^2 (x_d = column d of the leaf's inputs; n^2 D flops per leaf on the L^-T
+ *      of the trace term, any D; DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT does not apply).  With all l_d equal their sum is
+ *      IsoLinear's dl (src/kernels.jl:196-200). */
 int dsmgp_gradients(dsmgp_ctx* ctx, double* grad_out, int32_t stride);
 /* Restricts dsmgp_gradients to the leaves with active[l] != 0 (NULL: every leaf again; a new leaf table resets it): the rows
  * of the others come back as zeros, and neither L^-T nor the contraction tiles of leaves nobody asked for are computed (a

@@ -33,7 +33,7 @@ using Libdl
 using DeepStructuredMixtures
 import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, mll, predict, updategradients!, ∇mll
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
-                              IsoSE, ArdSE, IsoLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
+                              IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
 export attach!, detach!, census
 
@@ -53,10 +53,12 @@ const AGG_MIXTURE, AGG_POE, AGG_GPOE, AGG_RBCM = Int32(0), Int32(1), Int32(2), I
 kind(::IsoSE) = Int32(0)
 kind(::ArdSE) = Int32(1)
 kind(::IsoLinear) = Int32(2)
+kind(::ArdLinear) = Int32(3)     # DSMGP_KIND_ARD_LINEAR: sum_d a_d b_d / ℓ_d² (the reference's own methods cannot fit it, src/kernels.jl:232,247)
 # hyper-vector of one kernel id on the reference's log scale, [logℓ..., logσ, logNoise] (src/gaussianprocess.jl:141-161)
 loghyp(k::IsoSE, ln) = Float64[k.logℓ, k.logσ, ln]
 loghyp(k::ArdSE, ln) = Float64[k.logℓ..., k.logσ, ln]
 loghyp(k::IsoLinear, ln) = Float64[k.logℓ, 0.0, ln]             # the variance slot is a dummy (src/kernels.jl:181-183)
+loghyp(k::ArdLinear, ln) = Float64[k.logℓ..., 0.0, ln]          # ... here too (src/kernels.jl:216-218)
 
 # ---------------------------------------------------------------------------------------------- session
 "One device context + the leaf table of one model (or of one stand-alone GaussianProcess)."
@@ -473,13 +475,13 @@ function fetchgradients!(s::Session)
     GC.@preserve g chk(s, ccall(sym(:dsmgp_gradients), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32), s.h, g, Int32(s.stride)))
     for (l, gp) in enumerate(s.gps)
         k = gp.kernel
-        nl = k isa ArdSE ? length(k.logℓ) : 1
-        if k isa ArdSE
-            k.∂ℓ[:] = g[1:nl, l]
+        nl = k isa Union{ArdSE,ArdLinear} ? length(k.logℓ) : 1
+        if k isa Union{ArdSE,ArdLinear}
+            k.∂ℓ[:] = g[1:nl, l]        # ArdLinear: written in place, never through getgradients (src/kernels.jl:247 cannot run)
         else
             k.∂ℓ = g[1, l]
         end
-        k isa IsoLinear || (k.∂σ = g[nl + 1, l])
+        k isa Union{IsoLinear,ArdLinear} || (k.∂σ = g[nl + 1, l])
         gp.∂ϵ.value = g[nl + 2, l]
     end
     return nothing

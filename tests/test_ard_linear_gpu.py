@@ -1,0 +1,304 @@
+"""GPU suite for the ArdLinear kernel (DSMGP_KIND_ARD_LINEAR): Gram tiles of every path, single leaves, gradients by the new
+quadratic-form kernel, and whole models -- against the dense restatement of tests/ard_linear_dense.py and through the
+oracle-checked IsoLinear path (equal length-scales, rescaled inputs)."""
+import itertools
+
+import numpy as np
+import pytest
+
+import deepstructuredmixtures_amd as dsm
+from deepstructuredmixtures_amd import hipabi, tree as ptree
+from deepstructuredmixtures_amd.datagen import uniform, normal, regression_data
+from oracle import spn as ospn
+from ard_linear_dense import DenseGP, kernelmatrix as dense_K
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-8
+KIND = 3
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = hipabi.Context(0)
+    yield c
+    c.close()
+
+
+def _data(seed, n, D, nt=150):
+    X = uniform(seed, 0, n * D).reshape((n, D), order="F") - 0.5
+    w = np.linspace(-1.0, 1.5, D)
+    y = X @ w + np.sin(3 * X[:, 0]) + 0.1 * normal(seed + 1, 0, n)
+    Xt = uniform(seed + 2, 0, nt * D).reshape((nt, D), order="F") - 0.5
+    return X, y, Xt
+
+
+def _logl(D):
+    return np.log(np.linspace(0.6, 1.4, D))
+
+
+def _single(ctx, X, y, mean, kind, loghyp, logNoise):
+    n = X.shape[0]
+    ctx.set_train(X, y)
+    ctx.set_leaves([0, n], np.arange(n), [0], [mean])
+    ctx.set_hyper(0, kind, np.concatenate([loghyp, [logNoise]]))
+    return ctx.fit()
+
+
+@pytest.mark.parametrize("D", [1, 3, 8, 32, 33, 48])
+def test_kernel_matrix_against_the_dense_formula(ctx, D):
+    n1, n2 = 300, 131
+    x1 = uniform(500 + D, 0, n1 * D).reshape((n1, D), order="F") - 0.3
+    x2 = uniform(600 + D, 0, n2 * D).reshape((n2, D), order="F") - 0.3
+    ll = _logl(D)
+    ctx.set_train(x1, np.zeros(n1))
+    ctx.set_hyper(0, KIND, list(ll) + [0.0, 0.0])
+    K = ctx.kernel_matrix(0, x1, x2)
+    s = 1.0 / np.exp(ll) ** 2
+    scale = np.abs(x1) @ np.diag(s) @ np.abs(x2).T              # sum_d |a_d b_d| / l_d^2 per entry
+    assert np.all(np.abs(K - dense_K(ll, x1, x2)) <= 1e-14 * scale)
+    Ks = ctx.kernel_matrix(0, x1, x1)
+    assert np.array_equal(Ks, Ks.T)                            # bit-symmetric
+
+
+@pytest.mark.parametrize("n,D", [(127, 3), (128, 33), (129, 8), (515, 40), (700, 5), (1500, 32)])
+def test_single_leaf_against_the_dense_restatement_under_every_schedule(ctx, n, D):
+    X, y, Xt = _data(700 + n, n, D)
+    ll, ln, mean = _logl(D), np.log(0.2), float(np.mean(y))
+    g = DenseGP(X, y, mean, ll, ln)
+    assert g.info == 0
+    ref = None
+    try:
+        for fg, fs, du in itertools.product([1, 0], [1, 0], [1, 0]):
+            ctx.set_option(hipabi.OPT_FUSED_GRAM, fg)
+            ctx.set_option(hipabi.OPT_FUSED_STEPS, fs)
+            ctx.set_option(hipabi.OPT_DIAG_IN_UPDATE, du)
+            mll, info, _ = _single(ctx, X, y, mean, KIND, np.append(ll, 0.0), ln)
+            assert info[0] == 0
+            assert abs(mll[0] - g.mll()) <= RTOL * max(1.0, abs(g.mll())), (fg, fs, du)
+            F, alpha = ctx.download_factor(0, n)
+            assert np.max(np.abs(F - g.L())) <= 1e-9 * np.max(np.abs(g.L())), (fg, fs, du)
+            assert np.max(np.abs(alpha - g.alpha)) <= 1e-7 * np.max(np.abs(g.alpha))
+            mu, var = ctx.predict_leaves(Xt, [0, Xt.shape[0]], np.arange(Xt.shape[0]))
+            mo, vo = g.prediction(Xt)
+            assert np.allclose(mu, mo, rtol=RTOL, atol=1e-9), (fg, fs, du)
+            assert np.allclose(var, vo, rtol=RTOL, atol=1e-10), (fg, fs, du)
+            if ref is None:
+                ref = mll[0]
+    finally:
+        ctx.set_option(hipabi.OPT_FUSED_GRAM, 1)
+        ctx.set_option(hipabi.OPT_FUSED_STEPS, 1)
+        ctx.set_option(hipabi.OPT_DIAG_IN_UPDATE, 1)
+
+
+@pytest.mark.parametrize("n,D", [(515, 3), (1300, 8), (400, 36)])
+def test_equal_lengthscales_are_iso_linear_and_scaled_inputs_are_unit_lengthscales(ctx, n, D):
+    """Witnesses through the oracle-checked IsoLinear path: ArdLinear(l, ..., l) = IsoLinear(l) in mll, moments and
+    sum_d dl_d = dl; ArdLinear(logl) on X = IsoLinear(0) on X diag(1 / l) at the leaf level."""
+    X, y, Xt = _data(900 + n, n, D)
+    ln, mean, l0 = np.log(0.3), float(np.mean(y)), np.log(0.8)
+    ma = _single(ctx, X, y, mean, KIND, np.full(D + 1, l0) * np.append(np.ones(D), 0.0), ln)[0][0]
+    mua, vara = ctx.predict_leaves(Xt, [0, Xt.shape[0]], np.arange(Xt.shape[0]))
+    ga = ctx.gradients(D + 2)[0]
+    mi = _single(ctx, X, y, mean, 2, np.array([l0, 0.0]), ln)[0][0]
+    mui, vari = ctx.predict_leaves(Xt, [0, Xt.shape[0]], np.arange(Xt.shape[0]))
+    gi = ctx.gradients(3)[0]
+    assert abs(ma - mi) <= 1e-11 * abs(mi)
+    assert np.allclose(mua, mui, rtol=1e-11, atol=0) and np.allclose(vara, vari, rtol=1e-11, atol=0)
+    A, Q = DenseGP(X, y, mean, np.full(D, l0), ln).quad_terms()
+    scale = max(abs(gi[0]), np.sum(A + Q) / np.exp(2 * l0))      # magnitude of the terms whose difference dl is
+    assert abs(np.sum(ga[:D]) - gi[0]) <= 1e-11 * scale, (np.sum(ga[:D]), gi[0])
+    assert ga[D] == 0.0 and abs(ga[D + 1] - gi[2]) <= 1e-11 * abs(gi[2])
+    # rescaled inputs
+    ll = _logl(D)
+    ma = _single(ctx, X, y, mean, KIND, np.append(ll, 0.0), ln)[0][0]
+    mua, vara = ctx.predict_leaves(Xt, [0, Xt.shape[0]], np.arange(Xt.shape[0]))
+    Xs, Xts = X / np.exp(ll), Xt / np.exp(ll)
+    mi = _single(ctx, Xs, y, mean, 2, np.array([0.0, 0.0]), ln)[0][0]
+    mui, vari = ctx.predict_leaves(Xts, [0, Xt.shape[0]], np.arange(Xt.shape[0]))
+    assert abs(ma - mi) <= 1e-10 * abs(mi)
+    assert np.allclose(mua, mui, rtol=1e-10, atol=1e-12) and np.allclose(vara, vari, rtol=1e-10, atol=0)
+
+
+@pytest.mark.parametrize("n,D", [(333, 2), (700, 8), (1111, 40)])
+def test_gradients_closed_form_finite_differences_and_the_ardse_option(ctx, n, D):
+    X, y, _ = _data(1100 + n, n, D, nt=4)
+    ll, ln, mean = _logl(D), np.log(0.25), float(np.mean(y))
+    h = np.append(ll, 0.0)
+    _single(ctx, X, y, mean, KIND, h, ln)
+    g = ctx.gradients(D + 2)[0]
+    go = DenseGP(X, y, mean, ll, ln).grad()
+    assert np.max(np.abs(g - go)) <= 1e-8 * np.max(np.abs(go)), (g, go)
+    assert g[D] == 0.0
+    ctx.set_option(hipabi.OPT_ARD_LENGTHSCALE_GRADIENT, 1)
+    try:
+        _single(ctx, X, y, mean, KIND, h, ln)
+        assert np.array_equal(ctx.gradients(D + 2)[0], g)       # the ArdSE option does not touch ArdLinear
+    finally:
+        ctx.set_option(hipabi.OPT_ARD_LENGTHSCALE_GRADIENT, 0)
+    eps = 1e-5
+    for d in range(0, D, max(1, D // 4)):
+        hp, hm = h.copy(), h.copy()
+        hp[d] += eps
+        hm[d] -= eps
+        fd = (_single(ctx, X, y, mean, KIND, hp, ln)[0][0] - _single(ctx, X, y, mean, KIND, hm, ln)[0][0]) / (2 * eps)
+        assert abs(g[d] - fd) <= 1e-5 * max(abs(fd), 1e-3 * np.max(np.abs(g[:D]))), (d, g[d], fd)
+
+
+def test_gradients_on_copy_and_prefix_leaves_and_under_a_leaf_mask(ctx):
+    """Leaf 0 (300 rows), leaf 1 = COPY of it (same mean: shares its sums), leaf 2 = COPY with a mean of its own (own sums on
+    the shared L^-T), leaf 3 = PREFIX: 600 rows whose first 300 are leaf 0's (factor continued from column 300)."""
+    n, D = 600, 5
+    X, y, _ = _data(1400, n, D, nt=4)
+    ll, ln = _logl(D), np.log(0.3)
+    means = [0.1, 0.1, -0.4, 0.2]
+    rows = [np.arange(300), np.arange(300), np.arange(300), np.arange(n)]
+    ptr = np.cumsum([0] + [r.size for r in rows])
+    ctx.set_train(X, y)
+    ctx.set_leaves(ptr, np.concatenate(rows), [0, 0, 0, 0], means)
+    ctx.set_hyper(0, KIND, np.concatenate([ll, [0.0, ln]]))
+    ctx.set_sharing([0, 1, 1, 2], [-1, 0, 0, 0], [0, 0, 0, 300])
+    mll, info, _ = ctx.fit()
+    assert np.all(info == 0)
+    g = ctx.gradients(D + 2)
+    for l in range(4):
+        r = DenseGP(X[rows[l]], y[rows[l]], means[l], ll, ln)
+        assert abs(mll[l] - r.mll()) <= RTOL * abs(r.mll())
+        go = r.grad()
+        assert np.max(np.abs(g[l] - go)) <= 1e-8 * np.max(np.abs(go)), (l, g[l], go)
+    assert np.array_equal(g[0], g[1])                          # copygradients
+    ctx.set_sharing(None, None, None)
+    ctx.fit()
+    assert np.allclose(ctx.gradients(D + 2), g, rtol=1e-9, atol=1e-11)
+    ctx.set_sharing([0, 1, 1, 2], [-1, 0, 0, 0], [0, 0, 0, 300])
+    ctx.fit()
+    for mask in ([0, 1, 0, 1], [0, 0, 1, 0], [1, 0, 0, 0]):
+        ctx.set_gradient_leaves(mask)
+        gm = ctx.gradients(D + 2)
+        for l in range(4):
+            if mask[l]:
+                assert np.allclose(gm[l], g[l], rtol=1e-12, atol=1e-14), (mask, l)
+            else:
+                assert np.all(gm[l] == 0.0)
+    ctx.set_gradient_leaves(None)
+
+
+def test_lengthscale_count_and_unknown_kinds_are_refused(ctx):
+    n, D = 200, 3
+    X, y, _ = _data(1500, n, D, nt=4)
+    ctx.set_train(X, y)
+    ctx.set_leaves([0, n], np.arange(n), [0], [0.0])
+    ctx.set_hyper(0, KIND, [0.1, 0.2, 0.0, np.log(0.3)])          # two length-scales for D = 3
+    with pytest.raises(hipabi.DsmgpError) as e:
+        ctx.fit()
+    assert e.value.code == -1                                   # DSMGP_E_ARG
+    with pytest.raises(hipabi.DsmgpError) as e:
+        ctx.kernel_matrix(0, X, X)
+    assert e.value.code == -1
+    with pytest.raises(hipabi.DsmgpError) as e:
+        ctx.set_hyper(0, 4, [0.1, 0.0, 0.0])
+    assert e.value.code == -1
+    ctx.set_hyper(0, KIND, [0.1, 0.2, 0.3, 0.0, np.log(0.3)])
+    assert ctx.fit()[1][0] == 0
+
+
+def _dense_leaves(m, X, y):
+    return [DenseGP(X[lf.obs], y[lf.obs], lf.mean.m, lf.kernel.logl, lf.logNoise) for lf in ptree.get_leaves(m.root)]
+
+
+def test_model_fit_predict_scores_gradients_and_the_iso_linear_identity():
+    N, D = 3000, 4
+    X, y, Xt = regression_data(N, D, n_test=200, seed=910)
+    ll = np.log([0.7, 0.9, 1.2, 1.5])
+    kw = dict(M=60, logNoise=np.log(0.2), seed=4)
+    m = dsm.buildDSMGP(X, y, 3, 4, kernel=dsm.ArdLinear(ll), **kw)
+    gps = _dense_leaves(m, X, y)
+    assert np.allclose(m.leaf_mll, [g.mll() for g in gps], rtol=RTOL, atol=1e-8)
+    z, zo = dsm.update(m), ospn.update(m.root, gps)
+    assert abs(z - zo) <= RTOL * max(1.0, abs(zo))
+    mu, var = dsm.predict(m, Xt)
+    mo, vo = ospn.predict(m.root, gps, Xt)
+    assert np.allclose(mu, mo, rtol=RTOL, atol=1e-9) and np.allclose(var, vo, rtol=RTOL, atol=1e-10)
+    yt = Xt @ np.array([1.0, -0.5, 0.3, 0.0])
+    sd, so = dsm.scores(m, yt), dsm.scores(m, yt, mo, vo)           # on the device's aggregated prediction / the dense one
+    for k in so:
+        assert abs(sd[k] - so[k]) <= 1e-8 * max(1.0, abs(so[k])), k
+    g = dsm.updategradients(m).copy()
+    for l, r in enumerate(gps):
+        go = r.grad()
+        assert np.max(np.abs(g[l] - go)) <= 1e-7 * max(1e-3, np.max(np.abs(go))), l
+    assert m.leaves[0].kernel.dl.shape == (D,) and not hasattr(m.leaves[0].kernel, "ds")
+    gm = dsm.grad_mll(m)
+    assert gm.shape == (D + 2,) and gm[D] == 0.0
+    # equal length-scales: the IsoLinear model on the same tree
+    l0 = np.log(0.9)
+    ma = dsm.buildDSMGP(X, y, 3, 4, kernel=dsm.ArdLinear(np.full(D, l0)), **kw)
+    mi = dsm.buildDSMGP(X, y, 3, 4, kernel=dsm.IsoLinear(l0), **kw)
+    assert np.allclose(ma.leaf_mll, mi.leaf_mll, rtol=1e-11, atol=0)
+    assert abs(dsm.update(ma) - dsm.update(mi)) <= 1e-11 * abs(dsm.update(mi))
+    mua, vara = dsm.predict(ma, Xt)
+    mui, vari = dsm.predict(mi, Xt)
+    assert np.allclose(mua, mui, rtol=1e-10, atol=1e-13) and np.allclose(vara, vari, rtol=1e-10, atol=0)
+    dsm.updategradients(ma)
+    dsm.updategradients(mi)
+    ga, gi = dsm.grad_mll(ma), dsm.grad_mll(mi)
+    assert abs(np.sum(ga[:D]) - gi[0]) <= 1e-8 * max(1.0, np.sum(np.abs(ga[:D])))
+    assert abs(ga[D + 1] - gi[2]) <= 1e-9 * max(1.0, abs(gi[2]))
+
+
+def test_deep_tree_runs_the_fused_small_leaf_kernels_on_ard_linear():
+    """depth 4, thousands of leaves of a few blocks (more leaves than CUs: the fused small-leaf kernels take the steps)."""
+    N, D = 12000, 3
+    X, y, Xt = regression_data(N, D, n_test=300, seed=78)
+    kw = dict(M=8, D=4, logNoise=np.log(0.1), seed=9)
+    ll = np.log([0.5, 0.8, 1.3])
+    m = dsm.buildDSMGP(X, y, 2, 5, kernel=dsm.ArdLinear(ll), **kw)
+    assert m.L > 256
+    sample = np.linspace(0, m.L - 1, 40).astype(int)
+    leaves = ptree.get_leaves(m.root)
+    for l in sample:
+        lf = leaves[l]
+        r = DenseGP(X[lf.obs], y[lf.obs], lf.mean.m, ll, lf.logNoise)
+        assert abs(m.leaf_mll[l] - r.mll()) <= RTOL * max(1.0, abs(r.mll())), l
+    gps = _dense_leaves(m, X, y)
+    mu, var = dsm.predict(m, Xt)
+    mo, vo = ospn.predict(m.root, gps, Xt)
+    assert np.allclose(mu, mo, rtol=RTOL, atol=1e-9) and np.allclose(var, vo, rtol=RTOL, atol=1e-10)
+    l0 = np.log(0.7)
+    ma = dsm.buildDSMGP(X, y, 2, 5, kernel=dsm.ArdLinear(np.full(D, l0)), **kw)
+    mi = dsm.buildDSMGP(X, y, 2, 5, kernel=dsm.IsoLinear(l0), **kw)
+    # (leaves of a few points with three input dimensions can be ill-conditioned: the two kernels round each entry differently)
+    assert np.max(np.abs(ma.leaf_mll - mi.leaf_mll) / np.maximum(1.0, np.abs(mi.leaf_mll))) <= 1e-9
+
+
+def test_mixed_kernel_vector_n_sub_and_training():
+    N, D = 2000, 3
+    X, y, Xt = regression_data(N, D, n_test=100, seed=930)
+    ll = np.log([0.6, 1.0, 1.4])
+    kern = [dsm.IsoSE(np.log(0.4), 0.0), dsm.ArdLinear(ll)]
+    kw = dict(M=60, logNoise=np.log(0.2), seed=5)
+    m = dsm.buildDSMGP(X, y, 2, 4, kernel=kern, **kw)
+    kinds = [lf.kernel.kind for lf in m.leaves]
+    assert 0 in kinds and 3 in kinds
+    c = hipabi.Context(0)
+    try:
+        for l in np.linspace(0, m.L - 1, 12).astype(int):
+            lf = m.leaves[l]
+            mll = _single(c, X[lf.obs], y[lf.obs], lf.mean.m, lf.kernel.kind, lf.kernel.loghyp(), lf.logNoise)[0][0]
+            assert abs(m.leaf_mll[l] - mll) <= 1e-12 * max(1.0, abs(mll)), l
+    finally:
+        c.close()
+    m2 = dsm.buildDSMGP(X, y, 2, 4, kernel=kern, n_sub=2, **kw)
+    assert np.allclose(m2.leaf_mll, m.leaf_mll, rtol=1e-12, atol=0)
+    assert np.allclose(dsm.predict(m2, Xt)[0], dsm.predict(m, Xt)[0], rtol=1e-11, atol=1e-13)
+    dsm.updategradients(m)
+    dsm.updategradients(m2)
+    g1, g2 = dsm.grad_mll(m), dsm.grad_mll(m2)
+    assert np.allclose(g1, g2, rtol=1e-10, atol=1e-12)
+    # three train! iterations move every length-scale of the ArdLinear kernel and raise the log-marginal
+    ma = dsm.buildDSMGP(X, y, 2, 4, kernel=dsm.ArdLinear(ll), **kw)
+    before = dsm.getparams(ma).copy()
+    _, hist = dsm.train(ma, dsm.ADAM(eta=0.05), iterations=3, randinit=False)
+    after = dsm.getparams(ma)
+    assert np.all(after[:D] != before[:D]) and after[D] == 0.0
+    assert hist[-1] > hist[0]

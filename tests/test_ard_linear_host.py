@@ -1,0 +1,100 @@
+"""ArdLinear without a GPU: the parameter object, the kind number shared with the C header, and the Julia glue's methods
+for it (julia/DSMGPHip.jl cannot be executed here: its text is checked)."""
+import os
+import re
+
+import numpy as np
+
+import deepstructuredmixtures_amd as dsm
+from deepstructuredmixtures_amd import kernels
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_ard_linear_hyper_vector_layout_and_round_trip():
+    k = dsm.ArdLinear(np.log([0.5, 1.5, 2.0]))
+    assert k.kind == kernels.KIND_ARD_LINEAR == 3
+    h = k.loghyp()
+    assert h.tolist() == list(np.log([0.5, 1.5, 2.0])) + [0.0]      # [logl_1..logl_D, dummy variance slot]
+    assert k.nparams() == 4 and k.dl.shape == (3,)
+    k.set_loghyp(np.array([0.1, 0.2, 0.3, 7.0]))                     # the variance slot is ignored (setvariance! is a no-op)
+    assert k.logl.tolist() == [0.1, 0.2, 0.3] and k.loghyp()[-1] == 0.0
+    c = k.copy()
+    c.logl[0] = 9.0
+    assert k.logl[0] == 0.1                                          # copy owns its vector
+    assert repr(k) == "ArdLinear([0.1, 0.2, 0.3])"
+    assert isinstance(k, dsm.KernelFunction)
+
+
+def test_ard_linear_parameters_through_getparams_setparams():
+    """getparams / setparams on a hand-made model table with an ArdLinear kernel next to an IsoSE one: the concatenated
+    vector is [logl..., 0, logNoise] per kernel id, and setparams writes it back unchanged."""
+    from deepstructuredmixtures_amd import model as M
+
+    class Leaf:
+        def __init__(self, kid, kern, ln):
+            self.kernelid, self.kernel, self.logNoise = kid, kern, ln
+
+    class Table:
+        def __init__(self, leaves):
+            self.leaves = leaves
+
+        def kernel_table(self):
+            return self.leaves
+
+    t = Table([Leaf(0, dsm.IsoSE(0.1, 0.2), -1.0), Leaf(1, dsm.ArdLinear([0.3, 0.4]), -2.0)])
+    v = M.getparams(t)
+    assert v.tolist() == [0.1, 0.2, -1.0, 0.3, 0.4, 0.0, -2.0]
+    M.setparams(t, np.array([1.0, 2.0, 3.0, 4.0, 5.0, 6.0, 7.0]))
+    assert t.leaves[1].kernel.logl.tolist() == [4.0, 5.0] and t.leaves[1].logNoise == 7.0
+    assert M.getparams(t).tolist() == [1.0, 2.0, 3.0, 4.0, 5.0, 0.0, 7.0]
+
+
+def test_ard_linear_kind_matches_the_header():
+    hdr = open(os.path.join(ROOT, "include", "dsmgp_hip.h"), encoding="utf-8").read()
+    m = re.search(r"#define\s+DSMGP_KIND_ARD_LINEAR\s+(\d+)", hdr)
+    assert m and int(m.group(1)) == kernels.KIND_ARD_LINEAR
+    for name, val in (("ISO_SE", kernels.KIND_ISO_SE), ("ARD_SE", kernels.KIND_ARD_SE), ("ISO_LINEAR", kernels.KIND_ISO_LINEAR)):
+        assert int(re.search(rf"#define\s+DSMGP_KIND_{name}\s+(\d+)", hdr).group(1)) == val
+
+
+def test_julia_glue_maps_ard_linear():
+    """kind(::ArdLinear) carries the header's number, loghyp has a method for it with the dummy variance slot, the type is
+    imported from the reference, and its gradients are written in place into k.∂ℓ (never through the reference's
+    getgradients(::ArdLinear), which reads an undefined name)."""
+    src = open(os.path.join(ROOT, "julia", "DSMGPHip.jl"), encoding="utf-8").read()
+    m = re.search(r"(?m)^kind\(::ArdLinear\) = Int32\((\d+)\)", src)
+    assert m and int(m.group(1)) == kernels.KIND_ARD_LINEAR
+    assert re.search(r"(?m)^loghyp\(k::ArdLinear, ln\) = Float64\[k\.logℓ\.\.\., 0\.0, ln\]", src)
+    imported = re.search(r"(?m)^using DeepStructuredMixtures: ((?:[^\n]*,\s*\n)*[^\n]*)", src).group(1)
+    assert "ArdLinear" in [t.strip() for t in imported.replace("\n", " ").split(",")]
+    body = src[src.index("function fetchgradients!"):]
+    body = body[:body.index("\nend\n")]
+    assert "Union{ArdSE,ArdLinear}" in body and "k.∂ℓ[:] = g[1:nl, l]" in body
+    assert not re.search(r"getgradients\(", src)
+
+
+def test_dense_restatement_with_equal_lengthscales_is_the_oracle_iso_linear():
+    """The dense ArdLinear restatement the GPU tests compare against (tests/ard_linear_dense.py), tied to the reviewed oracle:
+    with every l_d = l it is oracle.gp's IsoLinear(l) in K, log-marginal, predictive moments and sum_d dl_d = dl."""
+    from ard_linear_dense import DenseGP, kernelmatrix
+    from oracle import gp as ogp
+    from deepstructuredmixtures_amd.datagen import uniform, normal
+    n, D = 300, 3
+    X = uniform(7, 0, n * D).reshape((n, D), order="F")
+    y = X @ np.array([0.5, -1.0, 2.0]) + 0.1 * normal(8, 0, n)
+    Xt = uniform(9, 0, 40 * D).reshape((40, D), order="F")
+    ll, ln, m = np.log(0.7), np.log(0.3), float(np.mean(y))
+    g = DenseGP(X, y, m, np.full(D, ll), ln)
+    o = ogp.GaussianProcess(X, y, m, ogp.IsoLinear(ll), ln).update_cholesky()
+    Ko = ogp.kernelmatrix(ogp.IsoLinear(ll), X, Xt)
+    assert np.max(np.abs(kernelmatrix(np.full(D, ll), X, Xt) - Ko)) <= 1e-14 * np.max(np.abs(Ko))
+    assert abs(g.mll() - o.mll()) <= 1e-11 * abs(o.mll())
+    mu, var = g.prediction(Xt)
+    mo, vo = o.prediction(Xt)
+    assert np.allclose(mu, mo, rtol=1e-11, atol=0) and np.allclose(var, vo, rtol=1e-9, atol=0)
+    gd, go = g.grad(), o.grad()
+    A, Q = g.quad_terms()
+    scale = np.sum(A + Q) / np.exp(2 * ll)                       # magnitude of the terms whose difference dl is
+    assert abs(np.sum(gd[:D]) - go[0]) <= 1e-11 * scale, (np.sum(gd[:D]), go[0])
+    assert gd[D] == 0.0 and abs(gd[D + 1] - go[2]) <= 1e-9 * abs(go[2])
