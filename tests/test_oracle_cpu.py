@@ -228,3 +228,33 @@ def test_chol_continue_on_the_reference_self_check_construction(golden_dir):
     C, info = sla.lapack.dpotrf(A[np.ix_(idx, idx)], lower=1, clean=1)
     assert info == 0 and np.allclose(np.diag(C), z["lr_B/diag"], rtol=1e-13)
     assert abs(2 * np.sum(np.log(np.diag(C))) - float(z["lr_B/logdet"])) < 1e-10
+
+
+def test_oracle_gradients_match_the_50_digit_references(golden_dir):
+    """tests/golden/gp_grad.npz (make_grad_golden.py): gradients contracted directly at 50 digits, in the library's
+    convention.  oracle.gp (DenseGP for ArdLinear) within 16 cond_2(K_y) eps max(1, |g|_inf) of every component; the ArdSE
+    length-scale slots are the reference's zeros.  Leaf sizes 1, 2, 127..129, 160; D up to 48; the weak-signal cases too."""
+    from ard_linear_dense import DenseGP
+
+    z = np.load(os.path.join(golden_dir, "gp_grad.npz"))
+    cases = {}
+    for key in z.files:
+        name, field = key.split("/")
+        cases.setdefault(name, {})[field] = z[key]
+    assert sorted(set(int(c["kind"]) for c in cases.values())) == [0, 1, 2, 3]
+    eps = np.finfo(np.float64).eps
+    for name, c in cases.items():
+        kind, h, ln = int(c["kind"]), c["loghyp"], float(c["logNoise"])
+        if kind == 3:
+            g = DenseGP(c["X"], c["y"], float(c["mean"]), h[:-1], ln)
+        else:
+            g = ogp.GaussianProcess(c["X"], c["y"], float(c["mean"]), ogp.make_kernel(kind, h), ln, True).update_cholesky()
+        assert g.info == 0
+        v = g.grad()
+        ref = c["grad"]
+        assert v.shape == ref.shape, name
+        tol = 16 * float(c["cond"]) * eps * max(1.0, float(np.max(np.abs(ref))))
+        assert np.max(np.abs(v - ref)) <= tol, (name, v, ref, tol)
+        assert abs(g.mll() - float(c["mll"])) <= 16 * float(c["cond"]) * eps * max(1.0, abs(float(c["mll"]))), name
+        if kind == 1:
+            assert np.all(ref[:c["X"].shape[1]] == 0.0) and c["grad_true"].shape == (c["X"].shape[1],)
