@@ -48,11 +48,44 @@ struct LeafHost {
     int64_t route_off = 0;
 };
 
+// The one owner of a device array: every device allocation of the library outside the pool's arenas lives in one of these
+// and is freed by it.  `cap` is assigned in one place only, after a successful allocation (grow).
 template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t count = 0;       // entries in use (what a launch may cover)
     size_t cap = 0;         // entries allocated: a list that is replaced keeps its allocation while the new one fits (dev_upload)
+
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), count(o.count), cap(o.cap) {
+        o.p = nullptr;
+        o.count = o.cap = 0;
+    }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            std::swap(p, o.p);
+            std::swap(count, o.count);
+            std::swap(cap, o.cap);
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+
+    // room for `need` entries, `count` = need: the allocation stays while it holds them, else the old one is freed BEFORE
+    // `want` entries are asked for (peak memory).  On failure the owner is empty (p null, count and cap 0).
+    int grow(dsmgp_ctx* c, size_t need, size_t want);
+    int grow(dsmgp_ctx* c, size_t need) { return grow(c, need, std::max<size_t>(1, need + need / 8)); }
+    int alloc(dsmgp_ctx* c, size_t n) { return grow(c, n, n); }      // exactly n entries when there is no room for n yet
+    void clear() { count = 0; }             // an empty list; the allocation stays for the list that replaces it
+    void release() {                        // a freed list is an EMPTY list: nobody may launch over its old count
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        count = cap = 0;
+    }
+    void drop(bool keep) { keep ? clear() : release(); }
 };
 
 // DSMGP_HOSTLOG=1: wall time of the host-side phases of plan building to stderr (diagnostic)
@@ -140,6 +173,16 @@ struct StepLists {
     std::vector<int> dpos, dfin_off;                         // size nsteps / nsteps+1
     DevBuf<DiagFinishTask> dfin;
     int nsteps = 0;
+
+    void drop(bool keep) {
+        upd.drop(keep);
+        trsm.drop(keep);
+        red.drop(keep);
+        diag.drop(keep);
+        fdiag.drop(keep);
+        ftile8.drop(keep);
+        dfin.drop(keep);
+    }
 };
 
 // Collects the update tiles of one block step and splits their K range over several workgroups when
@@ -385,29 +428,26 @@ struct dsmgp_ctx {
 
     int64_t N = 0;
     int D = 0;
-    double* dX = nullptr;
-    double* dy = nullptr;
+    DevBuf<double> dX, dy;
 
     int L = 0;
     std::vector<LeafHost> leaves;
     std::vector<int64_t> obs_ptr, obs_idx;
-    int64_t* d_obs_ptr = nullptr;
-    int64_t* d_obs_idx = nullptr;
+    DevBuf<int64_t> d_obs_ptr, d_obs_idx;
     bool plan_ready = false;
 
     std::vector<HyperHost> hyper;
-    KParam* d_kp = nullptr;
-    double* d_l2 = nullptr;
-    size_t kp_cap = 0, l2_cap = 0;   // capacities of d_kp / d_l2 (elements)
+    DevBuf<KParam> d_kp;
+    DevBuf<double> d_l2;
 
     double* arenaF = nullptr;
     double* arenaDinv = nullptr;
     double* arenaVec = nullptr;     // per leaf: yc, w, z, alpha (4 x npad)
     double* arenaXg = nullptr;
-    int* d_info = nullptr;
-    int* d_owner = nullptr;         // per leaf: the leaf whose factor (and info slot) it uses (dsmgp_fit_exchange packs info per owner)
-    double* d_mll = nullptr;
-    LeafDev* d_leaves = nullptr;
+    DevBuf<int> d_info;
+    DevBuf<int> d_owner;            // per leaf: the leaf whose factor (and info slot) it uses (dsmgp_fit_exchange packs info per owner)
+    DevBuf<double> d_mll;
+    DevBuf<LeafDev> d_leaves;
     std::vector<LeafDev> h_leaves;
     size_t bytes_needed = 0;
 
@@ -487,17 +527,15 @@ struct dsmgp_ctx {
                                     // rows riding along, and must outlive a test set that is replaced between a fit and its first use
 
     // prediction
-    double* dXt = nullptr;
+    DevBuf<double> dXt;
     int64_t n_t = 0;
-    int64_t* d_route_ptr = nullptr;
-    int64_t* d_route_idx = nullptr;
+    DevBuf<int64_t> d_route_ptr, d_route_idx;
     std::vector<int64_t> route_ptr;
     double* arenaVt = nullptr;
     size_t arenaVt_count = 0;       // doubles allocated for the K_tn arena: a test set that replaces another takes it over while it
                                     // fits (releasing ~10 GB and asking the driver for them again took up to 0.6 s of a 0.06 s predict)
-    // capacities of the test set's other buffers (dev_grow: kept across registrations, freed with the context / the plan)
-    size_t cap_dXt = 0, cap_route_ptr = 0, cap_route_idx = 0, cap_row_ptr = 0, cap_row_ent = 0, cap_ent_leaf = 0, cap_agg_coef = 0,
-           cap_agg_group = 0, cap_agg_out = 0, cap_Xt = 0, cap_PV = 0, cap_slabP = 0;
+    // capacities of the test set's pool-carved arenas (arena_fit: kept across registrations, freed with the plan)
+    size_t cap_Xt = 0, cap_PV = 0, cap_slabP = 0;
     // pinned host staging for the uploads of a registration (stage_upload): the lists of a test set are ~10 MB at the headline
     // model; through hipMemcpy from pageable vectors they took 9 ms of a 25 ms registration and left the runtime busy behind them
     char* stage = nullptr;
@@ -522,14 +560,13 @@ struct dsmgp_ctx {
     int64_t route_total = 0;
 
     // aggregation of the leaf moments per test row + scores (dsmgp_aggregate*, dsmgp_scores)
-    int64_t* d_row_ptr = nullptr;   // n_t + 1: entries of every test row (built by set_test)
-    int32_t* d_row_ent = nullptr;   // entry positions, ascending per row
-    int32_t* d_ent_leaf = nullptr;  // leaf of every entry position
-    double* d_agg_part = nullptr;   // W x n_t partial sums
-    size_t agg_part_cap = 0;
-    double* d_agg_coef = nullptr;   // L
-    int32_t* d_agg_group = nullptr; // L
-    double* d_agg_out = nullptr;    // mu | var (n_t each) | y_test (n_t) | score block sums
+    DevBuf<int64_t> d_row_ptr;      // n_t + 1: entries of every test row (built by set_test)
+    DevBuf<int32_t> d_row_ent;      // entry positions, ascending per row
+    DevBuf<int32_t> d_ent_leaf;     // leaf of every entry position
+    DevBuf<double> d_agg_part;      // W x n_t partial sums
+    DevBuf<double> d_agg_coef;      // L
+    DevBuf<int32_t> d_agg_group;    // L
+    DevBuf<double> d_agg_out;       // mu | var (n_t each) | y_test (n_t) | score block sums
     int agg_family = -1, agg_G = 0, agg_W = 0;
     bool agg_partial_ready = false, agg_done = false;
     bool agg_total = false;         // d_agg_part holds the sum over ranks (dsmgp_aggregate_exchange ran on these partial sums)
@@ -556,26 +593,26 @@ struct dsmgp_ctx {
     bool ard_true_gradient = false; // DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT
     int gstride = 2;                // doubles per contraction task in d_gpart
     std::vector<int> grad_src;      // per leaf: the leaf whose contraction it shares (COPY leaf with the same mean), or -1
-    double* d_gpart = nullptr;      // partial results: frob | graddot pairs | per-leaf dots | ArdLinear quadratic forms (2 D per task)
-    size_t gpart_count = 0, gpart_cap = 0;
+    DevBuf<double> d_gpart;         // partial results: frob | graddot pairs | per-leaf dots | ArdLinear quadratic forms (2 D per task)
+    size_t gpart_count = 0;
 
     // multi-GPU exchange over RCCL (dsmgp_comm_*, dsmgp_allgather): librccl.so is loaded on first use
     void* comm = nullptr;           // ncclComm_t
     int comm_rank = 0, comm_world = 1;
-    double* d_xchg = nullptr;       // send | recv staging
-    size_t xchg_cap = 0;
+    DevBuf<double> d_xchg;          // send | recv staging
     // the model's tree as flat arrays in HBM (dsmgp_set_tree): the routing of predict runs on the device (dsmgp_set_test_routed)
-    RouteTree rtree{};
+    RouteTree rtree{};              // the kernel's by-value view of the arrays below
+    DevBuf<int8_t> rt_kind;
+    DevBuf<int32_t> rt_first, rt_nchild, rt_sdim, rt_leaf;
+    DevBuf<double> rt_thr;
     int64_t rtree_nodes = 0;
     int rtree_max_leaf = -1;        // largest local leaf index a region names (checked against the leaf table at routing time)
     bool rtree_ready = false;
     // routing workspace, kept across registrations: row counts | leaf counts | outside flag, bitmap, word prefixes
-    int32_t* rws_counts = nullptr;
-    size_t rws_counts_cap = 0;
-    uint32_t* rws_bits = nullptr;
-    size_t rws_bits_cap = 0;
+    DevBuf<int32_t> rws_counts;
+    DevBuf<uint32_t> rws_bits;
     hipStream_t side = nullptr;     // clock sampler (dsmgp_clock_sample_*): a one-wave kernel beside the context's own launches
-    unsigned long long* d_clock = nullptr;
+    DevBuf<unsigned long long> d_clock;
     bool clock_pending = false;
     double timings[DSMGP_N_TIMINGS] = {0};
     std::vector<hipEvent_t> event_pool;   // PhaseTimer's events, reused across calls
@@ -603,23 +640,26 @@ int fail(dsmgp_ctx* ctx, int code, const std::string& msg) {
     return code;
 }
 
+template <class T>
+int DevBuf<T>::grow(dsmgp_ctx* c, size_t need, size_t want) {
+    count = 0;
+    if (!p || need > cap) {
+        const hipError_t e = p ? hipFree(p) : hipSuccess;
+        p = nullptr;
+        cap = 0;
+        HIPCHK(c, e);
+        HIPCHK(c, hipMalloc(&p, want * sizeof(T)));
+        cap = want;
+    }
+    count = need;
+    return 0;
+}
 // `count` entries for a task list: the allocation is kept while the new list fits (a test set that replaces another, a
 // gradient mask that changes: hipFree + hipMalloc per list and registration were 3-4 ms of a 16 ms predict at depth 4)
 template <class T>
 int dev_reserve(dsmgp_ctx* ctx, DevBuf<T>& buf, size_t count) {
-    buf.count = 0;
-    if (count > buf.cap || (count && !buf.p)) {
-        if (buf.p) {
-            HIPCHK(ctx, hipFree(buf.p));
-            buf.p = nullptr;
-        }
-        buf.cap = 0;
-        const size_t want = count + count / 8;
-        HIPCHK(ctx, hipMalloc(&buf.p, want * sizeof(T)));
-        buf.cap = want;
-    }
-    buf.count = count;
-    return 0;
+    buf.clear();
+    return count ? buf.grow(ctx, count) : 0;
 }
 template <class T>
 int dev_upload(dsmgp_ctx* ctx, DevBuf<T>& buf, const std::vector<T>& host) {
@@ -627,41 +667,6 @@ int dev_upload(dsmgp_ctx* ctx, DevBuf<T>& buf, const std::vector<T>& host) {
     if (host.empty()) return 0;
     HIPCHK(ctx, hipMemcpy(buf.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     return 0;
-}
-
-template <class T>
-void dev_free(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-template <class T>
-void dev_free(DevBuf<T>& b) {      // a freed list is an EMPTY list: nobody may launch over its old count
-    dev_free(b.p);
-    b.count = 0;
-    b.cap = 0;
-}
-template <class T>
-void dev_drop(DevBuf<T>& b, bool keep) {    // keep: the list is emptied, its allocation stays for the list that replaces it
-    if (keep) b.count = 0;
-    else dev_free(b);
-}
-// a plain device array that grows on demand and otherwise stays (the buffers of a registered test set)
-template <class T>
-int dev_grow(dsmgp_ctx* ctx, T*& p, size_t& cap, size_t need) {
-    if (p && need <= cap) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(1, need + need / 8);
-    HIPCHK(ctx, hipMalloc(&p, want * sizeof(T)));
-    cap = want;
-    return 0;
-}
-template <class T>
-void dev_drop(T*& p, size_t& cap, bool keep) {
-    if (keep) return;
-    dev_free(p);
-    cap = 0;
 }
 
 bool in_pool(const dsmgp_ctx* c, const void* p) {
@@ -732,13 +737,13 @@ void drop_graphs(dsmgp_ctx* c) {
 // stay -- finetune! changes the mask L times per iteration (src/finetuning.jl:34-57), and the lists that replace these fit into
 // the same buffers (dev_upload) instead of a hipFree + hipMalloc per list and pass
 void free_grad_lists(dsmgp_ctx* c) {
-    dev_drop(c->gtrans, true);
-    dev_drop(c->gupd, true);
-    dev_drop(c->gtrsm, true);
-    dev_drop(c->gred, true);
-    dev_drop(c->gfrob, true);
-    dev_drop(c->gdot, true);
-    dev_drop(c->gardlin, true);
+    c->gtrans.clear();
+    c->gupd.clear();
+    c->gtrsm.clear();
+    c->gred.clear();
+    c->gfrob.clear();
+    c->gdot.clear();
+    c->gardlin.clear();
     c->grad_ready = false;
 }
 
@@ -746,25 +751,25 @@ void free_grad(dsmgp_ctx* c) {
     arena_put(c, c->slabG);
     c->slabG_count = 0;
     arena_put(c, c->arenaX);
-    dev_free(c->gtrans);
-    dev_free(c->gupd);
-    dev_free(c->gtrsm);
-    dev_free(c->gred);
-    dev_free(c->gfrob);
-    dev_free(c->gdot);
-    dev_free(c->gardlin);
-    dev_free(c->d_gpart);
-    c->gpart_cap = 0;
+    c->gtrans.release();
+    c->gupd.release();
+    c->gtrsm.release();
+    c->gred.release();
+    c->gfrob.release();
+    c->gdot.release();
+    c->gardlin.release();
+    c->d_gpart.release();
     c->grad_ready = false;
 }
 
 void free_tree(dsmgp_ctx* c) {
-    dev_free(const_cast<int8_t*&>(c->rtree.kind));
-    dev_free(const_cast<int32_t*&>(c->rtree.first));
-    dev_free(const_cast<int32_t*&>(c->rtree.nchild));
-    dev_free(const_cast<int32_t*&>(c->rtree.sdim));
-    dev_free(const_cast<int32_t*&>(c->rtree.leaf));
-    dev_free(const_cast<double*&>(c->rtree.thr));
+    c->rtree = RouteTree{};
+    c->rt_kind.release();
+    c->rt_first.release();
+    c->rt_nchild.release();
+    c->rt_sdim.release();
+    c->rt_leaf.release();
+    c->rt_thr.release();
     c->rtree_ready = false;
     c->rtree_nodes = 0;
     c->rtree_max_leaf = -1;
@@ -782,27 +787,19 @@ void free_plan(dsmgp_ctx* c) {
     arena_put(c, c->arenaDinv);
     arena_put(c, c->arenaVec);
     arena_put(c, c->arenaXg);
-    dev_free(c->d_info);
-    dev_free(c->d_owner);
-    dev_free(c->d_mll);
-    dev_free(c->d_leaves);
-    dev_free(c->gram);
+    c->d_info.release();
+    c->d_owner.release();
+    c->d_mll.release();
+    c->d_leaves.release();
+    c->gram.release();
     for (auto& lane : c->phase)
-        for (auto& ph : lane) {
-            dev_free(ph.upd);
-            dev_free(ph.trsm);
-            dev_free(ph.red);
-            dev_free(ph.diag);
-            dev_free(ph.fdiag);
-            dev_free(ph.ftile8);
-            dev_free(ph.dfin);
-        }
+        for (auto& ph : lane) ph.drop(false);
     for (auto& sl : c->slabF) arena_put(c, sl);
-    dev_free(c->fwd);
-    dev_free(c->bwd);
-    dev_free(c->dinvc_prefix);
-    dev_free(c->dinvc_fwd);
-    dev_free(c->dinvc_all);
+    c->fwd.release();
+    c->bwd.release();
+    c->dinvc_prefix.release();
+    c->dinvc_fwd.release();
+    c->dinvc_all.release();
     free_grad(c);
     c->plan_ready = false;
     c->phase_ready = false;
@@ -818,16 +815,16 @@ void free_test(dsmgp_ctx* c, bool keep) {
         c->pool_top = c->pool_mark_plan;
         keep = false;
     }
-    dev_drop(c->dXt, c->cap_dXt, keep);
-    dev_drop(c->d_route_ptr, c->cap_route_ptr, keep);
-    dev_drop(c->d_route_idx, c->cap_route_idx, keep);
-    dev_drop(c->d_row_ptr, c->cap_row_ptr, keep);
-    dev_drop(c->d_row_ent, c->cap_row_ent, keep);
-    dev_drop(c->d_ent_leaf, c->cap_ent_leaf, keep);
-    dev_drop(c->d_agg_part, c->agg_part_cap, keep);
-    dev_drop(c->d_agg_coef, c->cap_agg_coef, keep);
-    dev_drop(c->d_agg_group, c->cap_agg_group, keep);
-    dev_drop(c->d_agg_out, c->cap_agg_out, keep);
+    c->dXt.drop(keep);
+    c->d_route_ptr.drop(keep);
+    c->d_route_idx.drop(keep);
+    c->d_row_ptr.drop(keep);
+    c->d_row_ent.drop(keep);
+    c->d_ent_leaf.drop(keep);
+    c->d_agg_part.drop(keep);
+    c->d_agg_coef.drop(keep);
+    c->d_agg_group.drop(keep);
+    c->d_agg_out.drop(keep);
     c->agg_partial_ready = c->agg_done = c->agg_total = false;
     if (!keep) {
         arena_put(c, c->arenaVt);
@@ -837,25 +834,17 @@ void free_test(dsmgp_ctx* c, bool keep) {
         arena_put(c, c->slabP);
         c->cap_Xt = c->cap_PV = c->cap_slabP = 0;
     }
-    dev_drop(c->pgram, keep);
-    dev_drop(c->pgram0, keep);
-    dev_drop(c->ptasks, keep);
-    dev_drop(c->ptasks_slow, keep);
-    dev_drop(c->pupd, keep);
-    dev_drop(c->ptrsm, keep);
-    dev_drop(c->pred, keep);
-    dev_drop(c->psweep8, keep);
-    dev_drop(c->psegs, keep);
+    c->pgram.drop(keep);
+    c->pgram0.drop(keep);
+    c->ptasks.drop(keep);
+    c->ptasks_slow.drop(keep);
+    c->pupd.drop(keep);
+    c->ptrsm.drop(keep);
+    c->pred.drop(keep);
+    c->psweep8.drop(keep);
+    c->psegs.drop(keep);
     for (auto& lane : c->phaseJ)
-        for (auto& ph : lane) {
-            dev_drop(ph.upd, keep);
-            dev_drop(ph.trsm, keep);
-            dev_drop(ph.red, keep);
-            dev_drop(ph.diag, keep);
-            dev_drop(ph.fdiag, keep);
-            dev_drop(ph.ftile8, keep);
-            dev_drop(ph.dfin, keep);
-        }
+        for (auto& ph : lane) ph.drop(keep);
     for (auto& sl : c->slabJ) arena_put(c, sl);
     c->joint_ready = false;
     c->vt_valid = false;
@@ -905,28 +894,24 @@ int upload_hyper(dsmgp_ctx* c) {
         if (c->hyper[k].kind == DSMGP_KIND_ARD_LINEAR)
             for (size_t i = off[k]; i < off[k] + c->hyper[k].loghyp.size() - 2; ++i) slot_ard_linear[i] = 1;
     for (size_t i = 0; i < nslots; ++i) l2pool.push_back(slot_ard_linear[i] ? 1.0 / l2pool[i] : -0.5 / l2pool[i]);
-    if (l2pool.size() > c->l2_cap || !c->d_l2) {   // (re)allocate only when the table grows: fit is called in loops
+    if (l2pool.size() > c->d_l2.cap || !c->d_l2.p) {   // (re)allocate only when the table grows: fit is called in loops
         drop_graphs(c);
-        dev_free(c->d_l2);
-        c->l2_cap = std::max<size_t>(16, 2 * l2pool.size());
-        HIPCHK(c, hipMalloc(&c->d_l2, c->l2_cap * sizeof(double)));
+        if (int rc = c->d_l2.grow(c, l2pool.size(), std::max<size_t>(16, 2 * l2pool.size()))) return rc;
     }
-    if ((size_t)nk > c->kp_cap || !c->d_kp) {
+    if ((size_t)nk > c->d_kp.cap || !c->d_kp.p) {
         drop_graphs(c);
-        dev_free(c->d_kp);
-        c->kp_cap = std::max<size_t>(4, 2 * (size_t)nk);
-        HIPCHK(c, hipMalloc(&c->d_kp, c->kp_cap * sizeof(KParam)));
+        if (int rc = c->d_kp.grow(c, (size_t)nk, std::max<size_t>(4, 2 * (size_t)nk))) return rc;
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_l2, l2pool.data(), l2pool.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_l2.p, l2pool.data(), l2pool.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     for (int k = 0; k < nk; ++k) {
-        kp[k].l2 = c->d_l2 + off[k];
-        kp[k].nh = c->d_l2 + nslots + off[k];
+        kp[k].l2 = c->d_l2.p + off[k];
+        kp[k].nh = c->d_l2.p + nslots + off[k];
         if (c->hyper[k].kind >= 0) {
             kp[k].nh0 = l2pool[nslots + off[k]];
             kp[k].il2 = 1.0 / l2pool[off[k]];
         }
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_kp, kp.data(), nk * sizeof(KParam), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_kp.p, kp.data(), nk * sizeof(KParam), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // l2pool / kp are stack storage
     return 0;
 }
@@ -1429,15 +1414,15 @@ int build_plan(dsmgp_ctx* c) {
         if (int rc = arena_get(c, c->arenaVec, vTot)) return rc;
         if (int rc = arena_get(c, c->arenaXg, xTot)) return rc;
     }
-    HIPCHK(c, hipMalloc(&c->d_info, L * sizeof(int)));
-    HIPCHK(c, hipMalloc(&c->d_owner, L * sizeof(int)));
+    if (int rc = c->d_info.alloc(c, L)) return rc;
+    if (int rc = c->d_owner.alloc(c, L)) return rc;
     {   // the owner table changes with the leaf table / sharing schedule only: uploaded here, once
         std::vector<int> owner(L);
         for (int l = 0; l < L; ++l) owner[l] = c->leaves[l].owner;
-        HIPCHK(c, hipMemcpy(c->d_owner, owner.data(), (size_t)L * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_owner.p, owner.data(), (size_t)L * sizeof(int), hipMemcpyHostToDevice));
     }
-    HIPCHK(c, hipMalloc(&c->d_mll, L * sizeof(double)));
-    HIPCHK(c, hipMalloc(&c->d_leaves, L * sizeof(LeafDev)));
+    if (int rc = c->d_mll.alloc(c, L)) return rc;
+    if (int rc = c->d_leaves.alloc(c, L)) return rc;
 
     c->h_leaves.assign(L, LeafDev{});
     for (int l = 0; l < L; ++l) {
@@ -1450,14 +1435,14 @@ int build_plan(dsmgp_ctx* c) {
         d.w = d.yc + lf.npad;
         d.z = d.w + lf.npad;
         d.alpha = d.z + lf.npad;
-        d.info = c->d_info + lf.owner;
+        d.info = c->d_info.p + lf.owner;
         d.mean = lf.mean;
         d.n = lf.n;
         d.npad = lf.npad;
         d.nb = lf.nb;
         d.kid = lf.kid;
     }
-    HIPCHK(c, hipMemcpy(c->d_leaves, c->h_leaves.data(), L * sizeof(LeafDev), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_leaves.p, c->h_leaves.data(), L * sizeof(LeafDev), hipMemcpyHostToDevice));
 
     // gather X rows and centred y of every leaf (replaces the per-leaf views + apply_subtract!,
     // src/gaussianprocess.jl:72-74, src/treeStructure.jl:271-273)
@@ -1467,7 +1452,7 @@ int build_plan(dsmgp_ctx* c) {
         for (int l0 = 0; l0 < L; l0 += 32768) {
             const int cnt = std::min(32768, L - l0);
             dim3 grid((maxpad + 255) / 256, cnt);
-            gather_leaf_kernel<<<grid, 256, 0, c->stream>>>(c->d_leaves, c->d_obs_ptr, c->d_obs_idx, c->dX, c->dy,
+            gather_leaf_kernel<<<grid, 256, 0, c->stream>>>(c->d_leaves.p, c->d_obs_ptr.p, c->d_obs_idx.p, c->dX.p, c->dy.p,
                                                             c->N, c->D, l0);
         }
         HIPCHK(c, hipGetLastError());
@@ -1475,9 +1460,8 @@ int build_plan(dsmgp_ctx* c) {
     // The eight-wave fused tile tasks write the 16-row blocks of a factor that hold data and nothing else: the rows below them
     // in a leaf's last row tile -- padding, which the classic steps and every sweep over the factor expect to be zero -- are
     // zeroed here, once per plan (nothing writes anything else there afterwards)
-    DevBuf<ZeroRowsTask> zrows;
+    std::vector<ZeroRowsTask> zr;
     if (gram_fused(c)) {
-        std::vector<ZeroRowsTask> zr;
         for (int l = 0; l < L; ++l) {
             const LeafHost& lf = c->leaves[l];
             const int last = lf.n - (lf.nb - 1) * TB;
@@ -1489,28 +1473,27 @@ int build_plan(dsmgp_ctx* c) {
             z.ncols = (lf.nb - 1) * TB;
             if (z.r0 < TB) zr.push_back(z);
         }
-        if (int rc = dev_upload(c, zrows, zr)) return rc;
-        if (!zr.empty()) zero_pad_rows_kernel<<<(int)zr.size(), 256, 0, c->stream>>>(zrows.p);
     }
     // the upper 16x16 blocks of every diagonal tile: zero once per plan, written by nobody afterwards (zero_upper_blocks_kernel)
-    DevBuf<ZeroUpperTask> zupper;
-    {
-        std::vector<ZeroUpperTask> zu;
-        int maxnb = 1;
-        for (int l = 0; l < L; ++l) {
-            const LeafHost& lf = c->leaves[l];
-            if (lf.owner != l) continue;
-            zu.push_back(ZeroUpperTask{c->h_leaves[l].F, lf.npad, lf.nb});
-            maxnb = std::max(maxnb, lf.nb);
-        }
+    std::vector<ZeroUpperTask> zu;
+    int maxnb = 1;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.owner != l) continue;
+        zu.push_back(ZeroUpperTask{c->h_leaves[l].F, lf.npad, lf.nb});
+        maxnb = std::max(maxnb, lf.nb);
+    }
+    {   // both lists are on the device before the first launch: nothing returns between a launch and its synchronise
+        DevBuf<ZeroRowsTask> zrows;
+        DevBuf<ZeroUpperTask> zupper;
+        if (int rc = dev_upload(c, zrows, zr)) return rc;
         if (int rc = dev_upload(c, zupper, zu)) return rc;
+        if (!zr.empty()) zero_pad_rows_kernel<<<(int)zr.size(), 256, 0, c->stream>>>(zrows.p);
         for (size_t b0 = 0; b0 < zu.size(); b0 += 32768) {
             const size_t cnt = std::min<size_t>(32768, zu.size() - b0);
             zero_upper_blocks_kernel<<<dim3((unsigned)cnt, (unsigned)std::min(maxnb, 64)), 256, 0, c->stream>>>(zupper.p + b0);
         }
         const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
-        dev_free(zrows);          // before anything below can return
-        dev_free(zupper);
         HIPCHK(c, e1);
         HIPCHK(c, e2);
     }
@@ -1783,15 +1766,15 @@ void launch_tiles(dsmgp_ctx* c, const TileTask* tasks, int n, int role = 0 /* 0 
     if (!st) st = c->stream;
     if (pad) {   // launches with many padding-row tiles (small leaves): waves without data rows stay off the matrix pipe
         if (role == 1) tile_trsm_kernel<true><<<n, 256, 0, st>>>(tasks);
-        else if (c->profile == 0 || c->alt_names) tile_gemm_kernel_v2<false, 2, true><<<g, 256, 0, st>>>(tasks, nullptr, c->d_kp, c->D, dpos, dfin, ndfin);
-        else tile_gemm_kernel_v2<false, 0, true><<<g, 256, 0, st>>>(tasks, nullptr, c->d_kp, c->D, dpos, dfin, ndfin);
+        else if (c->profile == 0 || c->alt_names) tile_gemm_kernel_v2<false, 2, true><<<g, 256, 0, st>>>(tasks, nullptr, c->d_kp.p, c->D, dpos, dfin, ndfin);
+        else tile_gemm_kernel_v2<false, 0, true><<<g, 256, 0, st>>>(tasks, nullptr, c->d_kp.p, c->D, dpos, dfin, ndfin);
         return;
     }
     // ROLE only names the instantiation: with per-launch timing switched off (dsmgp_set_profile(ctx, 0)) the same code
     // runs as <false, 2>, so that a profiler's per-kernel average of <false, 0> covers exactly the launches bench.py times
     if (role == 1) tile_trsm_kernel<false><<<n, 256, 0, st>>>(tasks);   // B = inverse of a diagonal block, K = 128
-    else if (c->profile == 0 || c->alt_names) tile_gemm_kernel_v2<false, 2><<<g, 256, 0, st>>>(tasks, nullptr, c->d_kp, c->D, dpos, dfin, ndfin);
-    else tile_gemm_kernel_v2<false, 0><<<g, 256, 0, st>>>(tasks, nullptr, c->d_kp, c->D, dpos, dfin, ndfin);
+    else if (c->profile == 0 || c->alt_names) tile_gemm_kernel_v2<false, 2><<<g, 256, 0, st>>>(tasks, nullptr, c->d_kp.p, c->D, dpos, dfin, ndfin);
+    else tile_gemm_kernel_v2<false, 0><<<g, 256, 0, st>>>(tasks, nullptr, c->d_kp.p, c->D, dpos, dfin, ndfin);
 }
 
 // Two events bracketing a call on the context's stream; destroyed on every exit path.
@@ -1892,14 +1875,14 @@ void run_step(dsmgp_ctx* c, StepLists& S, int k, PhaseTimer& pt, hipStream_t st,
     if (nfd > 0 || nft8 > 0) {     // fused step: diagonal blocks (their tile's update included), then the tiles below them
         if (nfd > 0) {
             pt.begin(2, st);
-            diag_fused_reg_kernel<<<nfd, 256, DIAGR_LDS_BYTES, st>>>(S.fdiag.p + S.fdiag_off[k], c->d_kp, c->D);
+            diag_fused_reg_kernel<<<nfd, 256, DIAGR_LDS_BYTES, st>>>(S.fdiag.p + S.fdiag_off[k], c->d_kp.p, c->D);
             pt.note(k, nfd, 0);
             pt.end(st);
         }
         if (nft8 > 0) {
             pt.begin(18, st);
-            if (c->profile == 0 || c->alt_names) tile_fused8_kernel<2><<<nft8, 512, 0, st>>>(S.ftile8.p + S.ftile8_off[k], c->d_kp, c->D);
-            else tile_fused8_kernel<0><<<nft8, 512, 0, st>>>(S.ftile8.p + S.ftile8_off[k], c->d_kp, c->D);
+            if (c->profile == 0 || c->alt_names) tile_fused8_kernel<2><<<nft8, 512, 0, st>>>(S.ftile8.p + S.ftile8_off[k], c->d_kp.p, c->D);
+            else tile_fused8_kernel<0><<<nft8, 512, 0, st>>>(S.ftile8.p + S.ftile8_off[k], c->d_kp.p, c->D);
             pt.note(k, nft8, nft8);
             pt.end(st);
             if (count_launches) c->n_fused_launches++;
@@ -1980,7 +1963,7 @@ int ensure_alpha(dsmgp_ctx* c) {
     HIPCHK(c, hipEventRecord(ev.a, c->stream));
     int maxpad = 0;
     for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
-    copy_z_kernel<<<dim3((maxpad + 255) / 256, c->L), 256, 0, c->stream>>>(c->d_leaves);
+    copy_z_kernel<<<dim3((maxpad + 255) / 256, c->L), 256, 0, c->stream>>>(c->d_leaves.p);
     for (int s = 0; s < c->solve_steps; ++s) {
         const int n = c->bwd_off[s + 1] - c->bwd_off[s];
         if (n > 0) solve_bwd_kernel<<<n, 256, 0, c->stream>>>(c->bwd.p + c->bwd_off[s]);
@@ -2052,22 +2035,12 @@ int dsmgp_destroy(dsmgp_ctx* c) {
     free_test(c);
     if (c->pool_base) (void)hipFree(c->pool_base);
     c->pool_base = nullptr;
-    dev_free(c->dX);
-    dev_free(c->dy);
-    dev_free(c->d_obs_ptr);
-    dev_free(c->d_obs_idx);
-    dev_free(c->d_kp);
-    dev_free(c->d_l2);
     (void)dsmgp_comm_destroy(c);
     drop_graphs(c);
     if (c->side) {
         (void)hipStreamSynchronize(c->side);
         (void)hipStreamDestroy(c->side);
     }
-    dev_free(c->d_clock);
-    free_tree(c);
-    dev_free(c->rws_counts);
-    dev_free(c->rws_bits);
     if (c->stage) (void)hipHostFree(c->stage);
     c->stage = nullptr;
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
@@ -2077,7 +2050,7 @@ int dsmgp_destroy(dsmgp_ctx* c) {
         if (c->lane_stream[lane]) (void)hipStreamDestroy(c->lane_stream[lane]);
     }
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;               // the context's device arrays go with their owners
     return 0;
 }
 
@@ -2166,14 +2139,14 @@ int dsmgp_set_train(dsmgp_ctx* c, const double* X, const double* y, int64_t N, i
     free_plan(c);
     free_test(c);
     free_tree(c);
-    dev_free(c->dX);
-    dev_free(c->dy);
+    c->dX.release();
+    c->dy.release();
     c->N = N;
     c->D = D;
-    HIPCHK(c, hipMalloc(&c->dX, (size_t)N * D * sizeof(double)));
-    HIPCHK(c, hipMalloc(&c->dy, (size_t)N * sizeof(double)));
-    HIPCHK(c, hipMemcpy(c->dX, X, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->dy, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = c->dX.alloc(c, (size_t)N * D)) return rc;
+    if (int rc = c->dy.alloc(c, (size_t)N)) return rc;
+    HIPCHK(c, hipMemcpy(c->dX.p, X, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->dy.p, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice));
     c->L = 0;
     c->leaves.clear();
     return 0;
@@ -2182,7 +2155,7 @@ int dsmgp_set_train(dsmgp_ctx* c, const double* X, const double* y, int64_t N, i
 int dsmgp_set_leaves(dsmgp_ctx* c, int32_t L, const int64_t* obs_ptr, const int64_t* obs_idx,
                      const int32_t* kernel_id, const double* mean) {
     if (!c) return DSMGP_E_ARG;
-    if (!c->dX) return fail(c, DSMGP_E_STATE, "set_leaves before set_train");
+    if (!c->dX.p) return fail(c, DSMGP_E_STATE, "set_leaves before set_train");
     if (L <= 0 || !obs_ptr || !obs_idx || !kernel_id || !mean) return fail(c, DSMGP_E_ARG, "set_leaves: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     free_plan(c);
@@ -2211,12 +2184,12 @@ int dsmgp_set_leaves(dsmgp_ctx* c, int32_t L, const int64_t* obs_ptr, const int6
     c->L = L;
     c->obs_ptr.assign(obs_ptr, obs_ptr + L + 1);
     c->obs_idx.assign(obs_idx, obs_idx + obs_ptr[L]);
-    dev_free(c->d_obs_ptr);
-    dev_free(c->d_obs_idx);
-    HIPCHK(c, hipMalloc(&c->d_obs_ptr, (L + 1) * sizeof(int64_t)));
-    HIPCHK(c, hipMalloc(&c->d_obs_idx, std::max<size_t>(1, c->obs_idx.size()) * sizeof(int64_t)));
-    HIPCHK(c, hipMemcpy(c->d_obs_ptr, obs_ptr, (L + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_obs_idx, obs_idx, c->obs_idx.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    c->d_obs_ptr.release();
+    c->d_obs_idx.release();
+    if (int rc = c->d_obs_ptr.alloc(c, (size_t)L + 1)) return rc;
+    if (int rc = c->d_obs_idx.grow(c, c->obs_idx.size(), std::max<size_t>(1, c->obs_idx.size()))) return rc;
+    HIPCHK(c, hipMemcpy(c->d_obs_ptr.p, obs_ptr, (L + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_obs_idx.p, obs_idx, c->obs_idx.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -2309,22 +2282,22 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
 
     StepLists (*phases)[2] = joint ? c->phaseJ : c->phase;
     auto enqueue = [&]() -> int {
-        HIPCHK(c, hipMemsetAsync(c->d_info, 0, L * sizeof(int), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_info.p, 0, L * sizeof(int), c->stream));
         if (joint && c->acc_count) HIPCHK(c, hipMemsetAsync(c->arenaPV + c->acc_off, 0, c->acc_count * sizeof(double), c->stream));
         // 1. kernel matrices K + (noise + eps) I, lower tiles   (src/gaussianprocess.jl:83-98) [+ K_tn tiles]
         //    (fused into the update tasks: only the tiles of block column 0 are written here)
         {
             const DevBuf<GramTask>& tg = (joint && gram_fused(c)) ? c->pgram0 : c->pgram;
             pt.begin(0);
-            if (c->gram.count) gram_tile_kernel<<<2 * (int)c->gram.count, 256, 0, c->stream>>>(c->gram.p, c->d_kp, c->D);
-            if (joint && tg.count) gram_tile_kernel<<<2 * (int)tg.count, 256, 0, c->stream>>>(tg.p, c->d_kp, c->D);
+            if (c->gram.count) gram_tile_kernel<<<2 * (int)c->gram.count, 256, 0, c->stream>>>(c->gram.p, c->d_kp.p, c->D);
+            if (joint && tg.count) gram_tile_kernel<<<2 * (int)tg.count, 256, 0, c->stream>>>(tg.p, c->d_kp.p, c->D);
             pt.end();
         }
         // 2. factorisation, full leaves first                    (src/gaussianprocess.jl:101); w = y - m rides along
         {
             int maxpad = 0;
             for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
-            copy_vec_kernel<<<dim3((maxpad + 255) / 256, L), 256, 0, c->stream>>>(c->d_leaves);
+            copy_vec_kernel<<<dim3((maxpad + 255) / 256, L), 256, 0, c->stream>>>(c->d_leaves.p);
         }
         if (int rc = run_lanes(c, phases, 0, pt, true)) return rc;
         // 3. prefix leaves: copy the leading blocks of the source factor, continue (src/fit.jl:276-278)
@@ -2361,7 +2334,7 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
         }
         // 5. log marginal likelihood                              (src/gaussianprocess.jl:163)
         pt.begin(5);
-        mll_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves, c->d_mll);
+        mll_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->d_mll.p);
         pt.end();
         return 0;
     };
@@ -2410,11 +2383,11 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
     pt.collect(t0);
     c->timings[11] = ms * 1e-3;
     if (seconds) *seconds = ms * 1e-3;
-    if (mll_out) HIPCHK(c, hipMemcpy(mll_out, c->d_mll, L * sizeof(double), hipMemcpyDeviceToHost));
+    if (mll_out) HIPCHK(c, hipMemcpy(mll_out, c->d_mll.p, L * sizeof(double), hipMemcpyDeviceToHost));
     if (info_out) {
         // info lives per factor owner
         std::vector<int> owner_info(L);
-        HIPCHK(c, hipMemcpy(owner_info.data(), c->d_info, L * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(owner_info.data(), c->d_info.p, L * sizeof(int), hipMemcpyDeviceToHost));
         for (int l = 0; l < L; ++l) info_out[l] = owner_info[c->leaves[l].owner];
     }
     c->fitted = true;
@@ -2495,12 +2468,12 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
         d.ntpad = lf.ntpad;
         maxpad = std::max(maxpad, lf.ntpad);
     }
-    if (int rc = stage_upload(c, c->d_leaves, c->h_leaves.data(), (size_t)L * sizeof(LeafDev))) return rc;
+    if (int rc = stage_upload(c, c->d_leaves.p, c->h_leaves.data(), (size_t)L * sizeof(LeafDev))) return rc;
     if (maxpad > 0) {
         for (int l0 = 0; l0 < L; l0 += 32768) {
             const int cnt = std::min(32768, L - l0);
             gather_test_kernel<<<dim3((maxpad + 255) / 256, cnt), 256, 0, c->stream>>>(
-                c->d_leaves, c->d_route_ptr, c->d_route_idx, c->dXt, n_t, c->D, l0);
+                c->d_leaves.p, c->d_route_ptr.p, c->d_route_idx.p, c->dXt.p, n_t, c->D, l0);
         }
         HIPCHK(c, hipGetLastError());
     }
@@ -2704,7 +2677,7 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
     if (int rc = stage_upload_list(c, c->psegs, segs)) return rc;
     if (int rc = dev_reserve(c, c->psweep8, (size_t)c->psweep8_off[(size_t)nv])) return rc;
     if (!segs.empty())
-        build_sweep8_kernel<<<(unsigned)((segs.size() + 127) / 128), 128, 0, c->stream>>>(c->psegs.p, (int)segs.size(), c->d_leaves, c->psweep8.p,
+        build_sweep8_kernel<<<(unsigned)((segs.size() + 127) / 128), 128, 0, c->stream>>>(c->psegs.p, (int)segs.size(), c->d_leaves.p, c->psweep8.p,
                                                                                         c->xcd_order ? 1 : 0);
     HIPCHK(c, hipGetLastError());
     if (slab_tot) {
@@ -2794,12 +2767,12 @@ int dsmgp_set_test(dsmgp_ctx* c, const double* Xt, int64_t n_t, int32_t D, const
     c->route_total = total;
     c->route_ptr.assign(route_ptr, route_ptr + L + 1);
     hl.lap("set_test: uploads + row index");
-    if (int rc = dev_grow(c, c->dXt, c->cap_dXt, (size_t)n_t * c->D)) return rc;
-    HIPCHK(c, hipMemcpy(c->dXt, Xt, (size_t)n_t * c->D * sizeof(double), hipMemcpyHostToDevice));
-    if (int rc = dev_grow(c, c->d_route_ptr, c->cap_route_ptr, (size_t)L + 1)) return rc;
-    HIPCHK(c, hipMemcpy(c->d_route_ptr, route_ptr, (L + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (int rc = dev_grow(c, c->d_route_idx, c->cap_route_idx, (size_t)total)) return rc;
-    if (total) HIPCHK(c, hipMemcpy(c->d_route_idx, route_idx, total * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (int rc = c->dXt.grow(c, (size_t)n_t * c->D)) return rc;
+    HIPCHK(c, hipMemcpy(c->dXt.p, Xt, (size_t)n_t * c->D * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = c->d_route_ptr.grow(c, (size_t)L + 1)) return rc;
+    HIPCHK(c, hipMemcpy(c->d_route_ptr.p, route_ptr, (L + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (int rc = c->d_route_idx.grow(c, (size_t)total)) return rc;
+    if (total) HIPCHK(c, hipMemcpy(c->d_route_idx.p, route_idx, total * sizeof(int64_t), hipMemcpyHostToDevice));
     {
         // per test row, the (leaf, row) entries that carry its moments, in ascending entry order (= leaf order):
         // the index agg_partial_kernel walks
@@ -2814,12 +2787,12 @@ int dsmgp_set_test(dsmgp_ctx* c, const double* Xt, int64_t n_t, int32_t D, const
                 rent[fill[route_idx[i]]++] = (int32_t)i;
                 eleaf[i] = l;
             }
-        if (int rc = dev_grow(c, c->d_row_ptr, c->cap_row_ptr, (size_t)n_t + 1)) return rc;
-        if (int rc = dev_grow(c, c->d_row_ent, c->cap_row_ent, rent.size())) return rc;
-        if (int rc = dev_grow(c, c->d_ent_leaf, c->cap_ent_leaf, eleaf.size())) return rc;
-        HIPCHK(c, hipMemcpy(c->d_row_ptr, rptr.data(), rptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_row_ent, rent.data(), rent.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_ent_leaf, eleaf.data(), eleaf.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (int rc = c->d_row_ptr.grow(c, (size_t)n_t + 1)) return rc;
+        if (int rc = c->d_row_ent.grow(c, rent.size())) return rc;
+        if (int rc = c->d_ent_leaf.grow(c, eleaf.size())) return rc;
+        HIPCHK(c, hipMemcpy(c->d_row_ptr.p, rptr.data(), rptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_row_ent.p, rent.data(), rent.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_ent_leaf.p, eleaf.data(), eleaf.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     return register_test(c, hl);
 }
@@ -2856,21 +2829,18 @@ int dsmgp_set_tree(dsmgp_ctx* c, int64_t n_nodes, const int8_t* kind, const int6
                                         std::to_string(ROUTE_STACK));
     HIPCHK(c, hipSetDevice(c->device));
     free_tree(c);
-    auto up = [&](auto*& dst, const auto* src, size_t n) -> int {
-        using T = std::remove_cv_t<std::remove_pointer_t<std::remove_reference_t<decltype(dst)>>>;
-        T* p = nullptr;
-        HIPCHK(c, hipMalloc(&p, std::max<size_t>(1, n) * sizeof(T)));
-        dst = p;
-        HIPCHK(c, hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    auto up = [&](auto& buf, const auto* src, size_t n) -> int {
+        if (int rc = buf.alloc(c, n)) return rc;
+        HIPCHK(c, hipMemcpy(buf.p, src, n * sizeof(*src), hipMemcpyHostToDevice));
         return 0;
     };
-    if (int rc = up(c->rtree.kind, kind, (size_t)n_nodes)) return rc;
-    if (int rc = up(c->rtree.first, first.data(), (size_t)n_nodes)) return rc;
-    if (int rc = up(c->rtree.nchild, nch.data(), (size_t)n_nodes)) return rc;
-    if (int rc = up(c->rtree.sdim, sdim.data(), (size_t)n_nodes)) return rc;
-    if (int rc = up(c->rtree.leaf, leaf.data(), (size_t)n_nodes)) return rc;
-    if (int rc = up(c->rtree.thr, thr, (size_t)n_nodes * (size_t)thr_ld)) return rc;
-    c->rtree.thr_ld = (int)thr_ld;
+    if (int rc = up(c->rt_kind, kind, (size_t)n_nodes)) return rc;
+    if (int rc = up(c->rt_first, first.data(), (size_t)n_nodes)) return rc;
+    if (int rc = up(c->rt_nchild, nch.data(), (size_t)n_nodes)) return rc;
+    if (int rc = up(c->rt_sdim, sdim.data(), (size_t)n_nodes)) return rc;
+    if (int rc = up(c->rt_leaf, leaf.data(), (size_t)n_nodes)) return rc;
+    if (int rc = up(c->rt_thr, thr, (size_t)n_nodes * (size_t)thr_ld)) return rc;
+    c->rtree = RouteTree{c->rt_kind.p, c->rt_first.p, c->rt_nchild.p, c->rt_sdim.p, c->rt_leaf.p, c->rt_thr.p, (int)thr_ld};
     c->rtree_nodes = n_nodes;
     c->rtree_max_leaf = max_leaf;
     c->rtree_ready = true;
@@ -2896,36 +2866,28 @@ int dsmgp_set_test_routed(dsmgp_ctx* c, const double* Xt, int64_t n_t, int32_t D
     const size_t nbits = (size_t)L * (size_t)wpl;
     if (nbits * 8 > (size_t(8) << 30)) return fail(c, DSMGP_E_NOMEM, "set_test_routed: routing bitmap above 8 GiB; route on the host (dsmgp_set_test)");
     const size_t ncounts = (size_t)n_t + (size_t)L + 1;
-    if (ncounts > c->rws_counts_cap) {
-        dev_free(c->rws_counts);
-        c->rws_counts_cap = ncounts + ncounts / 4;
-        HIPCHK(c, hipMalloc(&c->rws_counts, c->rws_counts_cap * sizeof(int32_t)));
-    }
-    if (2 * nbits > c->rws_bits_cap) {
-        dev_free(c->rws_bits);
-        c->rws_bits_cap = 2 * nbits + nbits / 2;
-        HIPCHK(c, hipMalloc(&c->rws_bits, c->rws_bits_cap * sizeof(uint32_t)));
-    }
-    int32_t* row_cnt = c->rws_counts;
+    if (int rc = c->rws_counts.grow(c, ncounts, ncounts + ncounts / 4)) return rc;
+    if (int rc = c->rws_bits.grow(c, 2 * nbits, 2 * nbits + nbits / 2)) return rc;
+    int32_t* row_cnt = c->rws_counts.p;
     int32_t* leaf_cnt = row_cnt + n_t;
     int* outside = reinterpret_cast<int*>(leaf_cnt + L);
-    uint32_t* bitmap = c->rws_bits;
+    uint32_t* bitmap = c->rws_bits.p;
     uint32_t* wprefix = bitmap + nbits;
-    if (int rc = dev_grow(c, c->dXt, c->cap_dXt, (size_t)n_t * c->D)) return rc;
-    if (int rc = stage_upload(c, c->dXt, Xt, (size_t)n_t * c->D * sizeof(double))) return rc;
-    if (int rc = dev_grow(c, c->d_route_ptr, c->cap_route_ptr, (size_t)L + 1)) return rc;
-    if (int rc = dev_grow(c, c->d_row_ptr, c->cap_row_ptr, (size_t)n_t + 1)) return rc;
+    if (int rc = c->dXt.grow(c, (size_t)n_t * c->D)) return rc;
+    if (int rc = stage_upload(c, c->dXt.p, Xt, (size_t)n_t * c->D * sizeof(double))) return rc;
+    if (int rc = c->d_route_ptr.grow(c, (size_t)L + 1)) return rc;
+    if (int rc = c->d_row_ptr.grow(c, (size_t)n_t + 1)) return rc;
     HIPCHK(c, hipMemsetAsync(bitmap, 0, nbits * sizeof(uint32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(outside, 0, sizeof(int), c->stream));
     const unsigned gr = (unsigned)((n_t + 255) / 256);
-    route_walk_kernel<false><<<gr, 256, 0, c->stream>>>(c->rtree, c->dXt, n_t, row_cnt, bitmap, wpl, outside, nullptr, nullptr, nullptr, nullptr);
-    scan_counts_kernel<<<1, 1024, 0, c->stream>>>(row_cnt, n_t, c->d_row_ptr);
+    route_walk_kernel<false><<<gr, 256, 0, c->stream>>>(c->rtree, c->dXt.p, n_t, row_cnt, bitmap, wpl, outside, nullptr, nullptr, nullptr, nullptr);
+    scan_counts_kernel<<<1, 1024, 0, c->stream>>>(row_cnt, n_t, c->d_row_ptr.p);
     route_rank_kernel<<<L, 256, 0, c->stream>>>(bitmap, wpl, wprefix, leaf_cnt);
-    scan_counts_kernel<<<1, 1024, 0, c->stream>>>(leaf_cnt, (int64_t)L, c->d_route_ptr);
+    scan_counts_kernel<<<1, 1024, 0, c->stream>>>(leaf_cnt, (int64_t)L, c->d_route_ptr.p);
     HIPCHK(c, hipGetLastError());
     c->route_ptr.assign((size_t)L + 1, 0);
     int flag = 0;
-    HIPCHK(c, hipMemcpyAsync(c->route_ptr.data(), c->d_route_ptr, ((size_t)L + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->route_ptr.data(), c->d_route_ptr.p, ((size_t)L + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&flag, outside, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (flag != 0) {
@@ -2939,12 +2901,12 @@ int dsmgp_set_test_routed(dsmgp_ctx* c, const double* Xt, int64_t n_t, int32_t D
     }
     c->n_t = n_t;
     c->route_total = total;
-    if (int rc = dev_grow(c, c->d_route_idx, c->cap_route_idx, (size_t)total)) return rc;
-    if (int rc = dev_grow(c, c->d_row_ent, c->cap_row_ent, (size_t)total)) return rc;
-    if (int rc = dev_grow(c, c->d_ent_leaf, c->cap_ent_leaf, (size_t)total)) return rc;
-    route_fill_kernel<<<L, 256, 0, c->stream>>>(bitmap, wpl, wprefix, c->d_route_ptr, c->d_route_idx, c->d_ent_leaf);
-    route_walk_kernel<true><<<gr, 256, 0, c->stream>>>(c->rtree, c->dXt, n_t, nullptr, bitmap, wpl, nullptr, c->d_row_ptr, c->d_route_ptr, wprefix,
-                                                       c->d_row_ent);
+    if (int rc = c->d_route_idx.grow(c, (size_t)total)) return rc;
+    if (int rc = c->d_row_ent.grow(c, (size_t)total)) return rc;
+    if (int rc = c->d_ent_leaf.grow(c, (size_t)total)) return rc;
+    route_fill_kernel<<<L, 256, 0, c->stream>>>(bitmap, wpl, wprefix, c->d_route_ptr.p, c->d_route_idx.p, c->d_ent_leaf.p);
+    route_walk_kernel<true><<<gr, 256, 0, c->stream>>>(c->rtree, c->dXt.p, n_t, nullptr, bitmap, wpl, nullptr, c->d_row_ptr.p, c->d_route_ptr.p, wprefix,
+                                                       c->d_row_ent.p);
     HIPCHK(c, hipGetLastError());
     return register_test(c, hl);
 }
@@ -2955,7 +2917,7 @@ int dsmgp_routes(dsmgp_ctx* c, int64_t* route_ptr, int64_t* route_idx) {
     HIPCHK(c, hipSetDevice(c->device));
     if (route_ptr) std::memcpy(route_ptr, c->route_ptr.data(), ((size_t)c->L + 1) * sizeof(int64_t));
     if (route_idx && c->route_total)
-        HIPCHK(c, hipMemcpy(route_idx, c->d_route_idx, (size_t)c->route_total * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(route_idx, c->d_route_idx.p, (size_t)c->route_total * sizeof(int64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2981,7 +2943,7 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
             // K_tn tiles of the classic steps                (src/gaussianprocess.jl:133)
             if (c->pgram.count) {
                 pt.begin(6);
-                gram_tile_kernel<<<2 * (int)c->pgram.count, 256, 0, c->stream>>>(c->pgram.p, c->d_kp, c->D);
+                gram_tile_kernel<<<2 * (int)c->pgram.count, 256, 0, c->stream>>>(c->pgram.p, c->d_kp.p, c->D);
                 pt.end();
             }
             // V^T = K_tn L^-T, block column by block column (src/gaussianprocess.jl:120), lane by lane on the lanes' streams
@@ -2997,7 +2959,7 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
                     const int n8 = c->psweep8_off[v + 1] - c->psweep8_off[v];
                     if (n8 > 0) {
                         pt.begin(7, st);
-                        tile_fused8_kernel<1><<<n8, 512, 0, st>>>(c->psweep8.p + c->psweep8_off[v], c->d_kp, c->D);
+                        tile_fused8_kernel<1><<<n8, 512, 0, st>>>(c->psweep8.p + c->psweep8_off[v], c->d_kp.p, c->D);
                         pt.end(st);
                     }
                     const int nu = c->pupd_off[v + 1] - c->pupd_off[v];
@@ -3025,10 +2987,10 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
         // both sums were accumulated by the panel-solve epilogues of the sweep; leaves whose z did not exist yet
         // while their rows rode through the factorisation (COPY / PREFIX) are finished from the stored rows
         pt.begin(9);
-        pred_finish_kernel<<<(int)c->ptasks.count, 128, 0, c->stream>>>(c->d_leaves, c->ptasks.p, c->d_kp, c->D);
+        pred_finish_kernel<<<(int)c->ptasks.count, 128, 0, c->stream>>>(c->d_leaves.p, c->ptasks.p, c->d_kp.p, c->D);
         if (!standalone && c->ptasks_slow.count) {
-            pred_mu_kernel<<<(int)c->ptasks_slow.count, 256, 0, c->stream>>>(c->d_leaves, c->ptasks_slow.p);
-            pred_var_kernel<<<(int)c->ptasks_slow.count, 256, 0, c->stream>>>(c->d_leaves, c->ptasks_slow.p, c->d_kp, c->D);
+            pred_mu_kernel<<<(int)c->ptasks_slow.count, 256, 0, c->stream>>>(c->d_leaves.p, c->ptasks_slow.p);
+            pred_var_kernel<<<(int)c->ptasks_slow.count, 256, 0, c->stream>>>(c->d_leaves.p, c->ptasks_slow.p, c->d_kp.p, c->D);
         }
         pt.end();
     }
@@ -3088,27 +3050,27 @@ int dsmgp_aggregate_partial(dsmgp_ctx* c, int32_t family, const double* leaf_coe
     const int G = family == AGG_RBCM ? n_groups : 0;
     const int W = agg_width(family, G);
     const size_t need = (size_t)W * (size_t)c->n_t;
-    if (int rc = dev_grow(c, c->d_agg_part, c->agg_part_cap, need)) return rc;
-    if (int rc = dev_grow(c, c->d_agg_coef, c->cap_agg_coef, (size_t)L)) return rc;
-    if (int rc = dev_grow(c, c->d_agg_group, c->cap_agg_group, (size_t)L)) return rc;
-    if (leaf_coef) HIPCHK(c, hipMemcpyAsync(c->d_agg_coef, leaf_coef, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = c->d_agg_part.grow(c, need)) return rc;
+    if (int rc = c->d_agg_coef.grow(c, (size_t)L)) return rc;
+    if (int rc = c->d_agg_group.grow(c, (size_t)L)) return rc;
+    if (leaf_coef) HIPCHK(c, hipMemcpyAsync(c->d_agg_coef.p, leaf_coef, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (family == AGG_RBCM)
-        HIPCHK(c, hipMemcpyAsync(c->d_agg_group, leaf_group, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_agg_group.p, leaf_group, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     AggArgs a{};
-    a.row_ptr = c->d_row_ptr;
-    a.row_ent = c->d_row_ent;
-    a.ent_leaf = c->d_ent_leaf;
+    a.row_ptr = c->d_row_ptr.p;
+    a.row_ent = c->d_row_ent.p;
+    a.ent_leaf = c->d_ent_leaf.p;
     a.mu = c->arenaPV;
     a.var = c->arenaPV + (size_t)c->route_total;
-    a.coef = c->d_agg_coef;
-    a.group = c->d_agg_group;
-    a.part = c->d_agg_part;
+    a.coef = c->d_agg_coef.p;
+    a.group = c->d_agg_group.p;
+    a.part = c->d_agg_part.p;
     a.n_t = c->n_t;
     a.family = family;
     a.G = G;
     agg_partial_kernel<<<(unsigned)((c->n_t + 255) / 256), 256, 0, c->stream>>>(a);
     HIPCHK(c, hipGetLastError());
-    if (partial_out) HIPCHK(c, hipMemcpyAsync(partial_out, c->d_agg_part, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (partial_out) HIPCHK(c, hipMemcpyAsync(partial_out, c->d_agg_part.p, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // leaf_coef / leaf_group are the caller's
     c->agg_family = family;
     c->agg_G = G;
@@ -3131,15 +3093,15 @@ int dsmgp_aggregate_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nt = (size_t)c->n_t;
     const size_t nblk = (nt + 255) / 256;
-    if (int rc = dev_grow(c, c->d_agg_out, c->cap_agg_out, 3 * nt + 3 * nblk + 8)) return rc;
+    if (int rc = c->d_agg_out.grow(c, 3 * nt + 3 * nblk + 8)) return rc;
     if (partial_in)   // sums over all ranks / contexts, added by the caller
-        HIPCHK(c, hipMemcpyAsync(c->d_agg_part, partial_in, (size_t)c->agg_W * nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    agg_finish_kernel<<<(unsigned)nblk, 256, 0, c->stream>>>(c->d_agg_part, c->n_t, c->agg_family, c->agg_G, plain ? 1 : 0,
-                                                           c->d_kp, c->agg_family == AGG_RBCM ? prior_kernel_id : 0, c->dXt,
-                                                           c->D, c->d_agg_out, c->d_agg_out + nt);
+        HIPCHK(c, hipMemcpyAsync(c->d_agg_part.p, partial_in, (size_t)c->agg_W * nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    agg_finish_kernel<<<(unsigned)nblk, 256, 0, c->stream>>>(c->d_agg_part.p, c->n_t, c->agg_family, c->agg_G, plain ? 1 : 0,
+                                                           c->d_kp.p, c->agg_family == AGG_RBCM ? prior_kernel_id : 0, c->dXt.p,
+                                                           c->D, c->d_agg_out.p, c->d_agg_out.p + nt);
     HIPCHK(c, hipGetLastError());
-    if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->d_agg_out, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->d_agg_out + nt, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->d_agg_out.p, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->d_agg_out.p + nt, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->agg_done = true;
     return 0;
@@ -3158,12 +3120,12 @@ int dsmgp_scores(dsmgp_ctx* c, const double* y_test, double* out) {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nt = (size_t)c->n_t;
     const size_t nblk = (nt + 255) / 256;
-    double* dy = c->d_agg_out + 2 * nt;
+    double* dy = c->d_agg_out.p + 2 * nt;
     double* dsum = dy + nt;
     HIPCHK(c, hipMemcpyAsync(dy, y_test, nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
     std::vector<double> blk(3 * nblk);
     auto pass = [&](int which, double mse, double mae, double (&tot)[3]) -> int {
-        agg_scores_kernel<<<(unsigned)nblk, 256, 0, c->stream>>>(dy, c->d_agg_out, c->d_agg_out + nt, c->n_t, which, mse, mae, dsum);
+        agg_scores_kernel<<<(unsigned)nblk, 256, 0, c->stream>>>(dy, c->d_agg_out.p, c->d_agg_out.p + nt, c->n_t, which, mse, mae, dsum);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(blk.data(), dsum, blk.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3452,7 +3414,7 @@ int build_grad_plan(dsmgp_ctx* c) {
     }
     if (int rc = dev_upload(c, c->gardlin, al)) return rc;
     c->gpart_count = frob.size() + (size_t)c->gstride * gd.size() + 2 * (size_t)L + 2 * (size_t)c->D * al.size();
-    if (int rc = dev_grow(c, c->d_gpart, c->gpart_cap, c->gpart_count)) return rc;
+    if (int rc = c->d_gpart.grow(c, c->gpart_count)) return rc;
     c->grad_ready = true;
     return 0;
 }
@@ -3528,14 +3490,14 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[q], 0));
     }
     HIPCHK(c, hipEventRecord(e_inv.a, c->stream));
-    double* pfrob = c->d_gpart;
+    double* pfrob = c->d_gpart.p;
     double* pdot = pfrob + c->gfrob.count;
     double* pleaf = pdot + (size_t)c->gstride * c->gdot.count;
     if (c->gdot.count)
-        tile_graddot_kernel<<<(int)c->gdot.count, 256, 0, c->stream>>>(c->gdot.p, c->d_kp, c->D, pdot, c->gstride);
+        tile_graddot_kernel<<<(int)c->gdot.count, 256, 0, c->stream>>>(c->gdot.p, c->d_kp.p, c->D, pdot, c->gstride);
     HIPCHK(c, hipEventRecord(e_dot.a, c->stream));
     if (c->gfrob.count) frob_kernel<<<(int)c->gfrob.count, 256, 0, c->stream>>>(c->gfrob.p, pfrob);
-    dots_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves, pleaf);
+    dots_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, pleaf);
     double* pardlin = pleaf + 2 * (size_t)L;
     if (c->gardlin.count)
         ardlin_quad_kernel<<<dim3((unsigned)c->gardlin.count, (unsigned)((c->D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
@@ -3553,7 +3515,7 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     HIPCHK(c, hipEventElapsedTime(&ms, e_dot.a, t1));
     c->timings[17] = ms * 1e-3;
     std::vector<double> part(c->gpart_count);
-    HIPCHK(c, hipMemcpy(part.data(), c->d_gpart, c->gpart_count * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(part.data(), c->d_gpart.p, c->gpart_count * sizeof(double), hipMemcpyDeviceToHost));
     // host assembly (fixed summation order -> reproducible)
     std::vector<double> trK(L, 0.0), S1(L, 0.0);
     for (size_t i = 0; i < c->gfrob.count; ++i) trK[c->gfrob_leaf[i]] += part[i];
@@ -3645,19 +3607,19 @@ int dsmgp_kernel_matrix(dsmgp_ctx* c, int32_t kernel_id, const double* x1, int64
     if (int rc = upload_hyper(c)) return rc;
     const int D = c->D;
     const int p1 = round_up((int)n1, TB), p2 = round_up((int)n2, TB);
-    double *dx1 = nullptr, *dx2 = nullptr, *dK = nullptr;
-    HIPCHK(c, hipMalloc(&dx1, (size_t)n1 * D * sizeof(double)));
-    HIPCHK(c, hipMalloc(&dx2, (size_t)n2 * D * sizeof(double)));
-    HIPCHK(c, hipMalloc(&dK, (size_t)p1 * p2 * sizeof(double)));
-    HIPCHK(c, hipMemcpy(dx1, x1, (size_t)n1 * D * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dx2, x2, (size_t)n2 * D * sizeof(double), hipMemcpyHostToDevice));
+    DevBuf<double> dx1, dx2, dK;
+    if (int rc = dx1.alloc(c, (size_t)n1 * D)) return rc;
+    if (int rc = dx2.alloc(c, (size_t)n2 * D)) return rc;
+    if (int rc = dK.alloc(c, (size_t)p1 * p2)) return rc;
+    HIPCHK(c, hipMemcpy(dx1.p, x1, (size_t)n1 * D * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dx2.p, x2, (size_t)n2 * D * sizeof(double), hipMemcpyHostToDevice));
     std::vector<GramTask> g;
     for (int j = 0; j < p2 / TB; ++j)
         for (int i = 0; i < p1 / TB; ++i) {
             GramTask t{};
-            t.xa = dx1 + (size_t)i * TB;
-            t.xb = dx2 + (size_t)j * TB;
-            t.out = dK + (size_t)i * TB + (size_t)j * TB * p1;
+            t.xa = dx1.p + (size_t)i * TB;
+            t.xb = dx2.p + (size_t)j * TB;
+            t.out = dK.p + (size_t)i * TB + (size_t)j * TB * p1;
             t.lda = (int)n1;
             t.ldb = (int)n2;
             t.ldo = p1;
@@ -3668,15 +3630,11 @@ int dsmgp_kernel_matrix(dsmgp_ctx* c, int32_t kernel_id, const double* x1, int64
         }
     DevBuf<GramTask> dg;
     if (int rc = dev_upload(c, dg, g)) return rc;
-    gram_tile_kernel<<<2 * (int)g.size(), 256, 0, c->stream>>>(dg.p, c->d_kp, D);
+    gram_tile_kernel<<<2 * (int)g.size(), 256, 0, c->stream>>>(dg.p, c->d_kp.p, D);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy2D(K_out, (size_t)n1 * sizeof(double), dK, (size_t)p1 * sizeof(double), (size_t)n1 * sizeof(double),
+    HIPCHK(c, hipMemcpy2D(K_out, (size_t)n1 * sizeof(double), dK.p, (size_t)p1 * sizeof(double), (size_t)n1 * sizeof(double),
                           (size_t)n2, hipMemcpyDeviceToHost));
-    dev_free(dg);
-    dev_free(dx1);
-    dev_free(dx2);
-    dev_free(dK);
     return 0;
 }
 
@@ -3814,24 +3772,22 @@ int dsmgp_probe_f64_mfma_detail(dsmgp_ctx* c, int32_t blocks_per_cu, double* out
     const int blocks = c->ncu * blocks_per_cu;
     const int iters = 6000 / blocks_per_cu;
     const int nwaves = blocks * 4;
-    double* sink = nullptr;
-    unsigned long long* stamps = nullptr;
-    HIPCHK(c, hipMalloc(&sink, (size_t)blocks * 256 * sizeof(double)));
-    HIPCHK(c, hipMalloc(&stamps, (size_t)nwaves * 2 * sizeof(unsigned long long)));
+    DevBuf<double> sink;
+    DevBuf<unsigned long long> stamps;
+    if (int rc = sink.alloc(c, (size_t)blocks * 256)) return rc;
+    if (int rc = stamps.alloc(c, (size_t)nwaves * 2)) return rc;
     EventPair ev;
     HIPCHK(c, ev.init());
     const hipEvent_t t0 = ev.a, t1 = ev.b;
-    for (int rep = 0; rep < 3; ++rep) mfma_probe_kernel<<<blocks, 256, 0, c->stream>>>(sink, stamps, iters);
+    for (int rep = 0; rep < 3; ++rep) mfma_probe_kernel<<<blocks, 256, 0, c->stream>>>(sink.p, stamps.p, iters);
     HIPCHK(c, hipEventRecord(t0, c->stream));
-    mfma_probe_kernel<<<blocks, 256, 0, c->stream>>>(sink, stamps, iters);
+    mfma_probe_kernel<<<blocks, 256, 0, c->stream>>>(sink.p, stamps.p, iters);
     HIPCHK(c, hipEventRecord(t1, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, t0, t1));
     std::vector<unsigned long long> hs((size_t)nwaves * 2);
-    HIPCHK(c, hipMemcpy(hs.data(), stamps, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    dev_free(sink);
-    dev_free(stamps);
+    HIPCHK(c, hipMemcpy(hs.data(), stamps.p, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     std::vector<double> cyc(nwaves), clk(nwaves);
     for (int i = 0; i < nwaves; ++i) {
         cyc[i] = (double)hs[2 * i] / ((double)iters * 16.0);
@@ -3855,8 +3811,8 @@ int dsmgp_clock_sample_start(dsmgp_ctx* c, double milliseconds) {
     if (c->clock_pending) return fail(c, DSMGP_E_STATE, "clock_sample_start: a sample is already running (read it first)");
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->side) HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-    if (!c->d_clock) HIPCHK(c, hipMalloc(&c->d_clock, 2 * sizeof(unsigned long long)));
-    clock_sample_kernel<<<1, 64, 0, c->side>>>(c->d_clock, (unsigned long long)(milliseconds * 1e5));   // 100 MHz ticks
+    if (int rc = c->d_clock.alloc(c, 2)) return rc;
+    clock_sample_kernel<<<1, 64, 0, c->side>>>(c->d_clock.p, (unsigned long long)(milliseconds * 1e5));   // 100 MHz ticks
     HIPCHK(c, hipGetLastError());
     c->clock_pending = true;
     return 0;
@@ -3869,7 +3825,7 @@ int dsmgp_clock_sample_read(dsmgp_ctx* c, double* ghz, double* milliseconds) {
     HIPCHK(c, hipStreamSynchronize(c->side));
     c->clock_pending = false;
     unsigned long long h[2] = {0, 0};
-    HIPCHK(c, hipMemcpy(h, c->d_clock, sizeof(h), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(h, c->d_clock.p, sizeof(h), hipMemcpyDeviceToHost));
     if (ghz) *ghz = h[1] ? (double)h[0] / ((double)h[1] * 10.0) : 0.0;      // cycles per 10 ns tick / 10 = GHz
     if (milliseconds) *milliseconds = (double)h[1] * 1e-5;
     return 0;
@@ -3883,23 +3839,20 @@ int dsmgp_probe_coissue(dsmgp_ctx* c, double* out) {
     if (!c || !out) return DSMGP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     const int blocks = c->ncu, iters = 2000;
-    double* sink = nullptr;
-    unsigned long long* st = nullptr;
-    HIPCHK(c, hipMalloc(&sink, (size_t)blocks * 512 * sizeof(double)));
-    HIPCHK(c, hipMalloc(&st, (size_t)blocks * 8 * 2 * sizeof(unsigned long long)));
+    DevBuf<double> sink;
+    DevBuf<unsigned long long> st;
+    if (int rc = sink.alloc(c, (size_t)blocks * 512)) return rc;
+    if (int rc = st.alloc(c, (size_t)blocks * 8 * 2)) return rc;
     for (int mode = 0; mode < 3; ++mode) {
-        hipEvent_t t0, t1;
-        HIPCHK(c, hipEventCreate(&t0));
-        HIPCHK(c, hipEventCreate(&t1));
-        coissue_probe_kernel<<<blocks, 512, 0, c->stream>>>(sink, st, iters, mode);
-        HIPCHK(c, hipEventRecord(t0, c->stream));
-        coissue_probe_kernel<<<blocks, 512, 0, c->stream>>>(sink, st, iters, mode);
-        HIPCHK(c, hipEventRecord(t1, c->stream));
+        EventPair ev;
+        HIPCHK(c, ev.init());
+        coissue_probe_kernel<<<blocks, 512, 0, c->stream>>>(sink.p, st.p, iters, mode);
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        coissue_probe_kernel<<<blocks, 512, 0, c->stream>>>(sink.p, st.p, iters, mode);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, t0, t1));
-        (void)hipEventDestroy(t0);
-        (void)hipEventDestroy(t1);
+        HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
         const double waves_mfma = (mode == 0) ? 8.0 : (mode == 2 ? 4.0 : 0.0);
         const double waves_valu = (mode == 1) ? 8.0 : (mode == 2 ? 4.0 : 0.0);
         const double fl_m = (double)blocks * waves_mfma * iters * 16.0 * 2048.0;
@@ -3908,8 +3861,6 @@ int dsmgp_probe_coissue(dsmgp_ctx* c, double* out) {
         out[3 * mode + 1] = fl_v / (ms * 1e-3) / 1e12;
         out[3 * mode + 2] = ms;
     }
-    dev_free(sink);
-    dev_free(st);
     return 0;
 }
 
@@ -3924,35 +3875,35 @@ int dsmgp_bench_tile(dsmgp_ctx* c, int32_t ntiles, int32_t K, int32_t mode, int3
     const int nA = mode == 1 ? 1 : ((mode == 3 || mode == 5) ? (ntiles + group - 1) / group * group : ntiles);
     const int nB = mode == 1 ? 1 : (ntiles + group - 1) / group;
     if (mode == 2 && std::getenv("DSMGP_STAMPS")) return fail(c, DSMGP_E_ARG, "no stamps in mode 2");
-    double *A = nullptr, *B = nullptr, *C = nullptr;
-    HIPCHK(c, hipMalloc(&A, nA * panel * sizeof(double)));
-    HIPCHK(c, hipMalloc(&B, nB * panel * sizeof(double)));
-    HIPCHK(c, hipMalloc(&C, (size_t)ntiles * TB * TB * sizeof(double)));
-    HIPCHK(c, hipMemset(A, 0, nA * panel * sizeof(double)));
-    HIPCHK(c, hipMemset(B, 0, nB * panel * sizeof(double)));
-    HIPCHK(c, hipMemset(C, 0, (size_t)ntiles * TB * TB * sizeof(double)));
+    DevBuf<double> A, B, C;
+    if (int rc = A.alloc(c, nA * panel)) return rc;
+    if (int rc = B.alloc(c, nB * panel)) return rc;
+    if (int rc = C.alloc(c, (size_t)ntiles * TB * TB)) return rc;
+    HIPCHK(c, hipMemset(A.p, 0, nA * panel * sizeof(double)));
+    HIPCHK(c, hipMemset(B.p, 0, nB * panel * sizeof(double)));
+    HIPCHK(c, hipMemset(C.p, 0, (size_t)ntiles * TB * TB * sizeof(double)));
     {   // non-trivial operand values (random-ish, bounded)
         std::vector<double> hv(panel);
         for (size_t i = 0; i < panel; ++i) hv[i] = 1e-3 * (double)((i * 2654435761u) % 2001) - 1.0;
-        for (int i = 0; i < nA; ++i) HIPCHK(c, hipMemcpy(A + i * panel, hv.data(), panel * sizeof(double), hipMemcpyHostToDevice));
-        for (int i = 0; i < nB; ++i) HIPCHK(c, hipMemcpy(B + i * panel, hv.data(), panel * sizeof(double), hipMemcpyHostToDevice));
+        for (int i = 0; i < nA; ++i) HIPCHK(c, hipMemcpy(A.p + i * panel, hv.data(), panel * sizeof(double), hipMemcpyHostToDevice));
+        for (int i = 0; i < nB; ++i) HIPCHK(c, hipMemcpy(B.p + i * panel, hv.data(), panel * sizeof(double), hipMemcpyHostToDevice));
     }
     std::vector<TileTask> tasks(ntiles);
     for (int i = 0; i < ntiles; ++i) {
         TileTask t{};
-        t.A = A + (mode == 1 ? 0 : (size_t)i * panel);
-        t.B = B + (mode == 1 ? 0 : (size_t)(i / group) * panel);
-        t.C = C + (size_t)i * TB * TB;
+        t.A = A.p + (mode == 1 ? 0 : (size_t)i * panel);
+        t.B = B.p + (mode == 1 ? 0 : (size_t)(i / group) * panel);
+        t.C = C.p + (size_t)i * TB * TB;
         t.lda = t.ldb = TB;
-        if (mode == 3 || mode == 5) {   // A tiles are row tiles of a (group*128) x K column-major matrix, like the rows of Vt
-            t.A = A + (size_t)(i / group) * group * panel + (size_t)(i % group) * TB;
+        if (mode == 3 || mode == 5) {   // A.p tiles are row tiles of a (group*128) x K column-major matrix, like the rows of Vt
+            t.A = A.p + (size_t)(i / group) * group * panel + (size_t)(i % group) * TB;
             t.lda = group * TB;
         }
         t.ldc = TB;
         t.k0 = 0;
         t.k1 = K;
         t.update = 1;
-        if (mode == 4 || mode == 5) {   // diagonal tiles of the factorisation: C -= A A^T, lower blocks only
+        if (mode == 4 || mode == 5) {   // diagonal tiles of the factorisation: C.p -= A.p A.p^T, lower blocks only
             t.B = t.A;
             t.ldb = t.lda;
             t.sym = 1;
@@ -3965,11 +3916,12 @@ int dsmgp_bench_tile(dsmgp_ctx* c, int32_t ntiles, int32_t K, int32_t mode, int3
     U.xcd = c->xcd_order;
     U.tail_split = c->tail_split;
     U.tail_rounds = c->tail_rounds;
-    double* slabs = nullptr;
+    DevBuf<double> slabs;
     if (mode == 2) {
         U.add_step(tasks, K);
-        if (U.max_slabs) HIPCHK(c, hipMalloc(&slabs, U.max_slabs * TB * TB * sizeof(double)));
-        U.bind(slabs);
+        if (U.max_slabs)
+            if (int rc = slabs.alloc(c, U.max_slabs * TB * TB)) return rc;
+        U.bind(slabs.p);
         tasks = U.upd;
         std::fprintf(stderr, "  splitter: %zu tiles -> %zu tasks, %zu reduces\n", (size_t)ntiles, tasks.size(), U.red.size());
     } else {
@@ -3989,29 +3941,23 @@ int dsmgp_bench_tile(dsmgp_ctx* c, int32_t ntiles, int32_t K, int32_t mode, int3
         launch_tiles(c, dt.p, nt_);
         if (dr.count) tile_reduce_kernel<<<(int)dr.count * REDUCE_WGS, 256, 0, c->stream>>>(dr.p);
     };
-    hipEvent_t t0, t1;
-    HIPCHK(c, hipEventCreate(&t0));
-    HIPCHK(c, hipEventCreate(&t1));
+    EventPair ev;
+    HIPCHK(c, ev.init());
     run();
-    HIPCHK(c, hipEventRecord(t0, c->stream));
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
     for (int r = 0; r < reps; ++r) run();
-    HIPCHK(c, hipEventRecord(t1, c->stream));
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, t0, t1));
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    dev_free(dr);
-    dev_free(slabs);
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     *seconds_per_launch = ms * 1e-3 / reps;
     if (std::getenv("DSMGP_STAMPS")) {
-        unsigned long long* st = nullptr;
-        HIPCHK(c, hipMalloc(&st, (size_t)ntiles * 32 * sizeof(unsigned long long)));
-        tile_gemm_kernel_v2<true><<<ntiles, 256, 0, c->stream>>>(dt.p, st, nullptr, 0, 0, nullptr, 0);
+        DevBuf<unsigned long long> st;
+        if (int rc = st.alloc(c, (size_t)ntiles * 32)) return rc;
+        tile_gemm_kernel_v2<true><<<ntiles, 256, 0, c->stream>>>(dt.p, st.p, nullptr, 0, 0, nullptr, 0);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         std::vector<unsigned long long> hs((size_t)ntiles * 32);
-        HIPCHK(c, hipMemcpy(hs.data(), st, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        dev_free(st);
+        HIPCHK(c, hipMemcpy(hs.data(), st.p, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         double tot = 0, mf = 0, bd = 0, nchs = 0, pro = 0, loop = 0, epi = 0;
         unsigned long long first = ~0ull, last = 0;
         for (size_t i = 0; i < (size_t)ntiles * 4; ++i) {
@@ -4035,10 +3981,6 @@ int dsmgp_bench_tile(dsmgp_ctx* c, int32_t ntiles, int32_t K, int32_t mode, int3
                      tot / loop / 10.0, (double)(last - first) * 0.01,
                      (pro + loop + epi) / ((double)(last - first) * std::min<double>(2.0 * c->ncu * 4.0, nw)));
     }
-    dev_free(dt);
-    dev_free(A);
-    dev_free(B);
-    dev_free(C);
     return 0;
 }
 // Diagnostic: the eight-wave fused tile task (tile_fused8_kernel) on a uniform batch of `ntasks` tasks of depth K -- eight full
@@ -4052,45 +3994,45 @@ int dsmgp_bench_fused8(dsmgp_ctx* c, int32_t ntasks, int32_t K, int32_t group, i
     const int D = 8;
     const size_t apanel = (size_t)TB * K, bpanel = (size_t)TB * (K + TB);
     const int nB = (ntasks + group - 1) / group;
-    double *A = nullptr, *B = nullptr, *Cc = nullptr, *Dv = nullptr, *gx = nullptr, *l2 = nullptr;
-    KParam* kp = nullptr;
-    HIPCHK(c, hipMalloc(&A, std::max<size_t>(1, (size_t)ntasks * apanel) * sizeof(double)));
-    HIPCHK(c, hipMalloc(&B, (size_t)nB * bpanel * sizeof(double)));
-    HIPCHK(c, hipMalloc(&Cc, (size_t)ntasks * TB * TB * sizeof(double)));
-    HIPCHK(c, hipMalloc(&Dv, (size_t)TB * TB * sizeof(double)));
-    HIPCHK(c, hipMalloc(&gx, (size_t)TB * D * sizeof(double)));
-    HIPCHK(c, hipMalloc(&l2, 2 * sizeof(double)));
-    HIPCHK(c, hipMalloc(&kp, sizeof(KParam)));
+    DevBuf<double> A, B, Cc, Dv, gx, l2;
+    DevBuf<KParam> kp;
+    if (int rc = A.alloc(c, std::max<size_t>(1, (size_t)ntasks * apanel))) return rc;
+    if (int rc = B.alloc(c, (size_t)nB * bpanel)) return rc;
+    if (int rc = Cc.alloc(c, (size_t)ntasks * TB * TB)) return rc;
+    if (int rc = Dv.alloc(c, (size_t)TB * TB)) return rc;
+    if (int rc = gx.alloc(c, (size_t)TB * D)) return rc;
+    if (int rc = l2.alloc(c, 2)) return rc;
+    if (int rc = kp.alloc(c, 1)) return rc;
     {
         std::vector<double> hv(std::max(apanel, bpanel));
         for (size_t i = 0; i < hv.size(); ++i) hv[i] = 1e-3 * (double)((i * 2654435761u) % 2001) - 1.0;
-        for (int i = 0; i < ntasks && apanel; ++i) HIPCHK(c, hipMemcpy(A + i * apanel, hv.data(), apanel * sizeof(double), hipMemcpyHostToDevice));
-        for (int i = 0; i < nB; ++i) HIPCHK(c, hipMemcpy(B + i * bpanel, hv.data(), bpanel * sizeof(double), hipMemcpyHostToDevice));
+        for (int i = 0; i < ntasks && apanel; ++i) HIPCHK(c, hipMemcpy(A.p + i * apanel, hv.data(), apanel * sizeof(double), hipMemcpyHostToDevice));
+        for (int i = 0; i < nB; ++i) HIPCHK(c, hipMemcpy(B.p + i * bpanel, hv.data(), bpanel * sizeof(double), hipMemcpyHostToDevice));
         std::vector<double> id((size_t)TB * TB, 0.0), xs((size_t)TB * D);
         for (int i = 0; i < TB; ++i) id[i + (size_t)i * TB] = 1.0;
         for (size_t i = 0; i < xs.size(); ++i) xs[i] = 1e-3 * (double)((i * 40503u) % 1000);
-        HIPCHK(c, hipMemcpy(Dv, id.data(), id.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(gx, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(Dv.p, id.data(), id.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(gx.p, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice));
         const double hl2[2] = {1.0, -0.5};
-        HIPCHK(c, hipMemcpy(l2, hl2, sizeof(hl2), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(l2.p, hl2, sizeof(hl2), hipMemcpyHostToDevice));
         KParam h{};
         h.kind = 0;
         h.nl = 1;
         h.sigma2 = h.sigma = 1.0;
         h.noise = 0.01;
-        h.l2 = l2;
-        h.nh = l2 + 1;
+        h.l2 = l2.p;
+        h.nh = l2.p + 1;
         h.nh0 = -0.5;
         h.il2 = 1.0;
-        HIPCHK(c, hipMemcpy(kp, &h, sizeof(h), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(kp.p, &h, sizeof(h), hipMemcpyHostToDevice));
     }
     std::vector<FusedTask8> tasks(ntasks);
     for (int i = 0; i < ntasks; ++i) {
         FusedTask8 t{};
-        t.B = B + (size_t)(i / group) * bpanel;
-        t.Dinv = Dv;
+        t.B = B.p + (size_t)(i / group) * bpanel;
+        t.Dinv = Dv.p;
         t.zk = nullptr;
-        t.gxb = gx;
+        t.gxb = gx.p;
         t.ldb = TB;
         t.gldb = TB;
         t.gnb = TB;
@@ -4099,9 +4041,9 @@ int dsmgp_bench_fused8(dsmgp_ctx* c, int32_t ntasks, int32_t K, int32_t group, i
         t.nblk = 8;
         for (int w = 0; w < 8; ++w) {
             RowBlock& r = t.rb[w];
-            r.A = (K ? A + (size_t)i * apanel : B) + 16 * w;
-            r.C = Cc + (size_t)i * TB * TB + 16 * w;
-            r.gx = gx + 16 * w;
+            r.A = (K ? A.p + (size_t)i * apanel : B.p) + 16 * w;
+            r.C = Cc.p + (size_t)i * TB * TB + 16 * w;
+            r.gx = gx.p + 16 * w;
             r.wi = nullptr;
             r.sq = nullptr;
             r.lda = TB;
@@ -4117,7 +4059,7 @@ int dsmgp_bench_fused8(dsmgp_ctx* c, int32_t ntasks, int32_t K, int32_t group, i
     }
     DevBuf<FusedTask8> dt;
     if (int rc = dev_upload(c, dt, tasks)) return rc;
-    auto run = [&]() { tile_fused8_kernel<2><<<ntasks, 512, 0, c->stream>>>(dt.p, kp, D); };
+    auto run = [&]() { tile_fused8_kernel<2><<<ntasks, 512, 0, c->stream>>>(dt.p, kp.p, D); };
     EventPair ev;
     HIPCHK(c, ev.init());
     run();
@@ -4128,14 +4070,6 @@ int dsmgp_bench_fused8(dsmgp_ctx* c, int32_t ntasks, int32_t K, int32_t group, i
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     *seconds_per_launch = ms * 1e-3 / reps;
-    dev_free(dt);
-    dev_free(A);
-    dev_free(B);
-    dev_free(Cc);
-    dev_free(Dv);
-    dev_free(gx);
-    dev_free(l2);
-    dev_free(kp);
     return 0;
 }
 // Diagnostic: the diagonal-block kernel alone on `ntiles` well-conditioned blocks (microseconds per launch over `reps`
@@ -4155,72 +4089,67 @@ int dsmgp_probe_diag(dsmgp_ctx* c, int32_t ntiles, int32_t ld, int32_t reps, dou
     };
     for (int cidx = 0; cidx < TB; ++cidx)
         for (int r = cidx; r < TB; ++r) h[r + (size_t)cidx * ld] = (r == cidx) ? 64.0 + rnd() : rnd();
-    double *T0 = nullptr, *T = nullptr, *Dinv = nullptr, *wz = nullptr;
-    int* info = nullptr;
-    unsigned long long* stamps = nullptr;
-    DiagTask* dt = nullptr;
-    HIPCHK(c, hipMalloc(&T0, tile * sizeof(double)));
-    HIPCHK(c, hipMalloc(&T, ntiles * tile * sizeof(double)));
-    HIPCHK(c, hipMalloc(&Dinv, (size_t)ntiles * TB * TB * sizeof(double)));
-    HIPCHK(c, hipMalloc(&wz, (size_t)ntiles * 2 * TB * sizeof(double)));
-    HIPCHK(c, hipMalloc(&info, ntiles * sizeof(int)));
-    HIPCHK(c, hipMalloc(&stamps, (size_t)ntiles * 24 * sizeof(unsigned long long)));
-    HIPCHK(c, hipMalloc(&dt, ntiles * sizeof(DiagTask)));
-    HIPCHK(c, hipMemcpy(T0, h.data(), tile * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemset(wz, 0, (size_t)ntiles * 2 * TB * sizeof(double)));
-    HIPCHK(c, hipMemset(Dinv, 0, (size_t)ntiles * TB * TB * sizeof(double)));
-    HIPCHK(c, hipMemset(info, 0, ntiles * sizeof(int)));
+    DevBuf<double> T0, T, Dinv, wz;
+    DevBuf<int> info;
+    DevBuf<unsigned long long> stamps;
+    DevBuf<DiagTask> dt;
+    if (int rc = T0.alloc(c, tile)) return rc;
+    if (int rc = T.alloc(c, ntiles * tile)) return rc;
+    if (int rc = Dinv.alloc(c, (size_t)ntiles * TB * TB)) return rc;
+    if (int rc = wz.alloc(c, (size_t)ntiles * 2 * TB)) return rc;
+    if (int rc = info.alloc(c, ntiles)) return rc;
+    if (int rc = stamps.alloc(c, (size_t)ntiles * 24)) return rc;
+    if (int rc = dt.alloc(c, ntiles)) return rc;
+    HIPCHK(c, hipMemcpy(T0.p, h.data(), tile * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(wz.p, 0, (size_t)ntiles * 2 * TB * sizeof(double)));
+    HIPCHK(c, hipMemset(Dinv.p, 0, (size_t)ntiles * TB * TB * sizeof(double)));
+    HIPCHK(c, hipMemset(info.p, 0, ntiles * sizeof(int)));
     std::vector<DiagTask> tasks(ntiles);
     for (int i = 0; i < ntiles; ++i) {
         DiagTask g{};
-        g.T = T + i * tile;
-        g.Dinv = Dinv + (size_t)i * TB * TB;
-        g.wk = wz + (size_t)i * 2 * TB;
-        g.zk = wz + (size_t)i * 2 * TB + TB;
-        g.info = info + i;
+        g.T = T.p + i * tile;
+        g.Dinv = Dinv.p + (size_t)i * TB * TB;
+        g.wk = wz.p + (size_t)i * 2 * TB;
+        g.zk = wz.p + (size_t)i * 2 * TB + TB;
+        g.info = info.p + i;
         g.ld = ld;
         g.nvalid = TB;
         g.row0 = 0;
         tasks[i] = g;
     }
-    HIPCHK(c, hipMemcpy(dt, tasks.data(), ntiles * sizeof(DiagTask), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dt.p, tasks.data(), ntiles * sizeof(DiagTask), hipMemcpyHostToDevice));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(chol_diag_packed_stamp_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, DIAGP_LDS_BYTES);
     const size_t lds = DIAGP_LDS_BYTES;
-    hipEvent_t e0, e1;
-    HIPCHK(c, hipEventCreate(&e0));
-    HIPCHK(c, hipEventCreate(&e1));
+    EventPair ev;
+    HIPCHK(c, ev.init());
     auto refill = [&]() {
         for (int i = 0; i < ntiles; ++i)
-            (void)hipMemcpyAsync(T + i * tile, T0, tile * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+            (void)hipMemcpyAsync(T.p + i * tile, T0.p, tile * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
     };
     double total = 0.0;
     for (int r = 0; r < reps + 1; ++r) {
         refill();
-        HIPCHK(c, hipEventRecord(e0, c->stream));
-        chol_diag_packed_kernel<<<ntiles, 256, lds, c->stream>>>(dt);
-        HIPCHK(c, hipEventRecord(e1, c->stream));
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        chol_diag_packed_kernel<<<ntiles, 256, lds, c->stream>>>(dt.p);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
+        HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
         if (r > 0) total += ms;
     }
     *kernel_us = total / reps * 1e3;
     refill();
-    chol_diag_packed_stamp_kernel<<<ntiles, 256, lds, c->stream>>>(dt, stamps);
+    chol_diag_packed_stamp_kernel<<<ntiles, 256, lds, c->stream>>>(dt.p, stamps.p);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     unsigned long long hs[24];
-    HIPCHK(c, hipMemcpy(hs, stamps, sizeof(hs), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hs, stamps.p, sizeof(hs), hipMemcpyDeviceToHost));
     for (int i = 0; i < 20; ++i) phases_us[i] = (double)(hs[i + 1] - hs[i]) * 0.01;   // 100 MHz
     phases_us[20] = (double)(hs[21] - hs[9]) * 0.01;
     phases_us[21] = (double)(hs[22] - hs[21]) * 0.01;
     phases_us[22] = (double)hs[23];                       // shader cycles of the interval of [21]
     int bad = 0;
-    HIPCHK(c, hipMemcpy(&bad, info, sizeof(int), hipMemcpyDeviceToHost));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(T0); (void)hipFree(T); (void)hipFree(Dinv); (void)hipFree(wz);
-    (void)hipFree(info); (void)hipFree(stamps); (void)hipFree(dt);
+    HIPCHK(c, hipMemcpy(&bad, info.p, sizeof(int), hipMemcpyDeviceToHost));
     if (bad != 0) return fail(c, DSMGP_E_STATE, "probe block was not positive definite");
     return 0;
 }
@@ -4241,77 +4170,72 @@ int dsmgp_probe_diag_fused(dsmgp_ctx* c, int32_t ntiles, int32_t K, int32_t reps
     std::vector<double> hx((size_t)TB * D), ha((size_t)TB * std::max(K, 1));
     for (double& v : hx) v = rnd();
     for (double& v : ha) v = (rnd() - 0.5) * 2e-3;
-    double *F = nullptr, *X = nullptr, *Dinv = nullptr, *wz = nullptr, *nh = nullptr;
-    int* info = nullptr;
-    DiagFusedTask* dt = nullptr;
-    KParam* kp = nullptr;
-    HIPCHK(c, hipMalloc(&F, (size_t)ntiles * leaf * sizeof(double)));
-    HIPCHK(c, hipMalloc(&X, (size_t)TB * D * sizeof(double)));
-    HIPCHK(c, hipMalloc(&Dinv, (size_t)ntiles * TB * TB * sizeof(double)));
-    HIPCHK(c, hipMalloc(&wz, (size_t)ntiles * 2 * TB * sizeof(double)));
-    HIPCHK(c, hipMalloc(&info, ntiles * sizeof(int)));
-    HIPCHK(c, hipMalloc(&dt, ntiles * sizeof(DiagFusedTask)));
-    HIPCHK(c, hipMalloc(&kp, sizeof(KParam)));
-    HIPCHK(c, hipMalloc(&nh, 2 * sizeof(double)));
-    HIPCHK(c, hipMemset(F, 0, (size_t)ntiles * leaf * sizeof(double)));
-    HIPCHK(c, hipMemset(Dinv, 0, (size_t)ntiles * TB * TB * sizeof(double)));
-    HIPCHK(c, hipMemset(wz, 0, (size_t)ntiles * 2 * TB * sizeof(double)));
-    HIPCHK(c, hipMemset(info, 0, ntiles * sizeof(int)));
-    HIPCHK(c, hipMemcpy(X, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
+    DevBuf<double> F, X, Dinv, wz, nh;
+    DevBuf<int> info;
+    DevBuf<DiagFusedTask> dt;
+    DevBuf<KParam> kp;
+    if (int rc = F.alloc(c, (size_t)ntiles * leaf)) return rc;
+    if (int rc = X.alloc(c, (size_t)TB * D)) return rc;
+    if (int rc = Dinv.alloc(c, (size_t)ntiles * TB * TB)) return rc;
+    if (int rc = wz.alloc(c, (size_t)ntiles * 2 * TB)) return rc;
+    if (int rc = info.alloc(c, ntiles)) return rc;
+    if (int rc = dt.alloc(c, ntiles)) return rc;
+    if (int rc = kp.alloc(c, 1)) return rc;
+    if (int rc = nh.alloc(c, 2)) return rc;
+    HIPCHK(c, hipMemset(F.p, 0, (size_t)ntiles * leaf * sizeof(double)));
+    HIPCHK(c, hipMemset(Dinv.p, 0, (size_t)ntiles * TB * TB * sizeof(double)));
+    HIPCHK(c, hipMemset(wz.p, 0, (size_t)ntiles * 2 * TB * sizeof(double)));
+    HIPCHK(c, hipMemset(info.p, 0, ntiles * sizeof(int)));
+    HIPCHK(c, hipMemcpy(X.p, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
     if (K > 0)
         for (int i = 0; i < ntiles; ++i)
-            HIPCHK(c, hipMemcpyAsync(F + (size_t)i * leaf, ha.data(), (size_t)TB * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(F.p + (size_t)i * leaf, ha.data(), (size_t)TB * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const double l2 = 0.09, hnh[2] = {-0.5 / l2, l2};
-    HIPCHK(c, hipMemcpy(nh, hnh, sizeof(hnh), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(nh.p, hnh, sizeof(hnh), hipMemcpyHostToDevice));
     KParam p{};
     p.kind = DSMGP_KIND_ISO_SE;
     p.nl = 1;
     p.sigma2 = p.sigma = 1.0;
     p.noise = 0.01;
-    p.l2 = nh + 1;
-    p.nh = nh;
+    p.l2 = nh.p + 1;
+    p.nh = nh.p;
     p.nh0 = hnh[0];
     p.il2 = 1.0 / l2;
-    HIPCHK(c, hipMemcpy(kp, &p, sizeof(p), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(kp.p, &p, sizeof(p), hipMemcpyHostToDevice));
     std::vector<DiagFusedTask> tasks(ntiles);
     for (int i = 0; i < ntiles; ++i) {
         DiagFusedTask f{};
-        f.d.T = F + (size_t)i * leaf + (size_t)K * TB;
-        f.d.Dinv = Dinv + (size_t)i * TB * TB;
-        f.d.wk = wz + (size_t)i * 2 * TB;
-        f.d.zk = wz + (size_t)i * 2 * TB + TB;
-        f.d.info = info + i;
+        f.d.T = F.p + (size_t)i * leaf + (size_t)K * TB;
+        f.d.Dinv = Dinv.p + (size_t)i * TB * TB;
+        f.d.wk = wz.p + (size_t)i * 2 * TB;
+        f.d.zk = wz.p + (size_t)i * 2 * TB + TB;
+        f.d.info = info.p + i;
         f.d.ld = TB;
         f.d.nvalid = TB;
         f.d.row0 = 0;
-        f.A = F + (size_t)i * leaf;
-        f.gx = X;
+        f.A = F.p + (size_t)i * leaf;
+        f.gx = X.p;
         f.k1 = K;
         f.glda = TB;
         f.kid = 0;
         tasks[i] = f;
     }
-    HIPCHK(c, hipMemcpy(dt, tasks.data(), ntiles * sizeof(DiagFusedTask), hipMemcpyHostToDevice));
-    hipEvent_t e0, e1;
-    HIPCHK(c, hipEventCreate(&e0));
-    HIPCHK(c, hipEventCreate(&e1));
+    HIPCHK(c, hipMemcpy(dt.p, tasks.data(), ntiles * sizeof(DiagFusedTask), hipMemcpyHostToDevice));
+    EventPair ev;
+    HIPCHK(c, ev.init());
     double total = 0.0;
     for (int r = 0; r < reps + 1; ++r) {
-        HIPCHK(c, hipEventRecord(e0, c->stream));
-        diag_fused_reg_kernel<<<ntiles, 256, DIAGR_LDS_BYTES, c->stream>>>(dt, kp, D);
-        HIPCHK(c, hipEventRecord(e1, c->stream));
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        diag_fused_reg_kernel<<<ntiles, 256, DIAGR_LDS_BYTES, c->stream>>>(dt.p, kp.p, D);
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
+        HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
         if (r > 0) total += ms;
     }
     *kernel_us = total / reps * 1e3;
     int bad = 0;
-    HIPCHK(c, hipMemcpy(&bad, info, sizeof(int), hipMemcpyDeviceToHost));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(F); (void)hipFree(X); (void)hipFree(Dinv); (void)hipFree(wz); (void)hipFree(nh);
-    (void)hipFree(info); (void)hipFree(dt); (void)hipFree(kp);
+    HIPCHK(c, hipMemcpy(&bad, info.p, sizeof(int), hipMemcpyDeviceToHost));
     if (bad != 0) return fail(c, DSMGP_E_STATE, "probe block was not positive definite");
     return 0;
 }
@@ -4406,42 +4330,32 @@ int dsmgp_comm_init(dsmgp_ctx* c, int32_t rank, int32_t world, const char* id) {
     return 0;
 }
 
+namespace {
+// all-gather of `n` doubles per rank, device to device on the context's stream: d_xchg = [send n | recv world * n]
+int xchg_reserve(dsmgp_ctx* c, size_t n) {
+    const size_t need = n * (size_t)(c->comm_world + 1);
+    return need > c->d_xchg.cap ? c->d_xchg.alloc(c, need) : 0;
+}
+int xchg_gather(dsmgp_ctx* c, size_t n) {
+    const int rc = g_rccl.AllGather(c->d_xchg.p, c->d_xchg.p + n, n, NCCL_FLOAT64, c->comm, c->stream);
+    if (rc != 0) return fail(c, DSMGP_E_HIP, "ncclAllGather: " + g_rccl.what(rc));
+    return 0;
+}
+}  // namespace
+
 int dsmgp_allgather(dsmgp_ctx* c, const double* send, int64_t count, double* recv) {
     if (!c) return DSMGP_E_ARG;
     if (!c->comm) return fail(c, DSMGP_E_STATE, "allgather before comm_init");
     if (!send || !recv || count <= 0) return fail(c, DSMGP_E_ARG, "allgather: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)count, need = n * (size_t)(c->comm_world + 1);
-    if (need > c->xchg_cap) {
-        dev_free(c->d_xchg);
-        HIPCHK(c, hipMalloc(&c->d_xchg, need * sizeof(double)));
-        c->xchg_cap = need;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_xchg, send, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const int rc = g_rccl.AllGather(c->d_xchg, c->d_xchg + n, n, NCCL_FLOAT64, c->comm, c->stream);
-    if (rc != 0) return fail(c, DSMGP_E_HIP, "ncclAllGather: " + g_rccl.what(rc));
-    HIPCHK(c, hipMemcpyAsync(recv, c->d_xchg + n, n * (size_t)c->comm_world * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    const size_t n = (size_t)count;
+    if (int rc = xchg_reserve(c, n)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_xchg.p, send, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = xchg_gather(c, n)) return rc;
+    HIPCHK(c, hipMemcpyAsync(recv, c->d_xchg.p + n, n * (size_t)c->comm_world * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
-
-namespace {
-// all-gather of `n` doubles per rank, device to device on the context's stream: d_xchg = [send n | recv world * n]
-int xchg_reserve(dsmgp_ctx* c, size_t n) {
-    const size_t need = n * (size_t)(c->comm_world + 1);
-    if (need > c->xchg_cap) {
-        dev_free(c->d_xchg);
-        HIPCHK(c, hipMalloc(&c->d_xchg, need * sizeof(double)));
-        c->xchg_cap = need;
-    }
-    return 0;
-}
-int xchg_gather(dsmgp_ctx* c, size_t n) {
-    const int rc = g_rccl.AllGather(c->d_xchg, c->d_xchg + n, n, NCCL_FLOAT64, c->comm, c->stream);
-    if (rc != 0) return fail(c, DSMGP_E_HIP, "ncclAllGather: " + g_rccl.what(rc));
-    return 0;
-}
-}  // namespace
 
 int dsmgp_fit_exchange(dsmgp_ctx* c, int64_t count, double* out) {
     if (!c) return DSMGP_E_ARG;
@@ -4453,13 +4367,13 @@ int dsmgp_fit_exchange(dsmgp_ctx* c, int64_t count, double* out) {
     if (int rc = xchg_reserve(c, n)) return rc;
     if (c->L > 0) {
         // info lives per factor owner (the table is the plan's: build_plan)
-        pack_mll_info_kernel<<<(unsigned)((count + 255) / 256), 256, 0, c->stream>>>(c->d_mll, c->d_info, c->d_owner, c->L, count, c->d_xchg);
+        pack_mll_info_kernel<<<(unsigned)((count + 255) / 256), 256, 0, c->stream>>>(c->d_mll.p, c->d_info.p, c->d_owner.p, c->L, count, c->d_xchg.p);
         HIPCHK(c, hipGetLastError());
     } else {
-        HIPCHK(c, hipMemsetAsync(c->d_xchg, 0, n * sizeof(double), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_xchg.p, 0, n * sizeof(double), c->stream));
     }
     if (int rc = xchg_gather(c, n)) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->d_xchg + n, n * (size_t)c->comm_world * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_xchg.p + n, n * (size_t)c->comm_world * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -4472,11 +4386,11 @@ int dsmgp_aggregate_exchange(dsmgp_ctx* c, double* total_out) {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->agg_W * (size_t)c->n_t;
     if (int rc = xchg_reserve(c, n)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_xchg, c->d_agg_part, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_xchg.p, c->d_agg_part.p, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     if (int rc = xchg_gather(c, n)) return rc;
-    sum_ranks_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->d_xchg + n, c->comm_world, (int64_t)n, c->d_agg_part);
+    sum_ranks_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->d_xchg.p + n, c->comm_world, (int64_t)n, c->d_agg_part.p);
     HIPCHK(c, hipGetLastError());
-    if (total_out) HIPCHK(c, hipMemcpyAsync(total_out, c->d_agg_part, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (total_out) HIPCHK(c, hipMemcpyAsync(total_out, c->d_agg_part.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->agg_total = true;
     return 0;
@@ -4489,12 +4403,12 @@ int dsmgp_aggregate_exchange_empty(dsmgp_ctx* c, int32_t W, int64_t n_t, double*
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)W * (size_t)n_t;
     if (int rc = xchg_reserve(c, n)) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_xchg, 0, n * sizeof(double), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_xchg.p, 0, n * sizeof(double), c->stream));
     if (int rc = xchg_gather(c, n)) return rc;
     if (total_out) {
-        sum_ranks_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->d_xchg + n, c->comm_world, (int64_t)n, c->d_xchg);
+        sum_ranks_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->d_xchg.p + n, c->comm_world, (int64_t)n, c->d_xchg.p);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(total_out, c->d_xchg, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(total_out, c->d_xchg.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -4508,8 +4422,7 @@ int dsmgp_comm_destroy(dsmgp_ctx* c) {
         (void)g_rccl.CommDestroy(c->comm);
         c->comm = nullptr;
     }
-    dev_free(c->d_xchg);
-    c->xchg_cap = 0;
+    c->d_xchg.release();
     c->comm_world = 1;
     c->comm_rank = 0;
     return 0;
