@@ -209,3 +209,48 @@ def table(root):
     return dict(kind=np.array(kind, dtype=np.int32), parent=np.array(parent, dtype=np.int32), split_dim=np.array(sdim, dtype=np.int32),
                 lb=np.array(lb), ub=np.array(ub), thr_ptr=np.array(thr_ptr, dtype=np.int64), thr=np.array(thr, dtype=np.float64),
                 obs_ptr=np.array(obs_ptr, dtype=np.int64), obs=np.array(obs, dtype=np.int64), mean=mean, weights=weights)
+
+
+class _Node:
+    pass
+
+
+class _Kernel:
+    def __init__(self, kind, loghyp):
+        self.kind = int(kind)
+        self._h = np.asarray(loghyp, dtype=np.float64)
+
+    def loghyp(self):
+        return self._h.copy()
+
+
+def spn_nodes(root, kind, loghyp, logNoise):
+    """The tree of `build_tree` as the duck-typed nodes oracle/spn.py walks (one kernel for every region): "gp" leaves
+    numbered in pre-order with their observations, mean and kernel; "split" nodes with `.split` = [(dim, upper bound)] of
+    each child (src/common.jl:101-122 reads them in that form); "sum" nodes with their log-weights."""
+    count = [0]
+
+    def conv(node):
+        n = _Node()
+        if node["kind"] == "region":
+            n.kind = "gp"
+            n.leaf = count[0]
+            count[0] += 1
+            n.obs = np.asarray(node["obs"], dtype=np.int64)
+            n.kernelid = 0
+            n.mean = _Node()
+            n.mean.m = float(node["mean"])
+            n.kernel = _Kernel(kind, loghyp)
+            n.logNoise = float(logNoise)
+            return n
+        n.children = [conv(c) for c in node["children"]]
+        if node["kind"] == "split":
+            n.kind = "split"
+            n.split = [(int(node["dim"]), float(t)) for t in node["thr"]]
+        else:
+            n.kind = "sum"
+            n.logweights = np.array(node["logweights"], dtype=np.float64)
+            n.of_gps = all(c.kind == "gp" for c in n.children)
+        return n
+
+    return conv(root)

@@ -1,0 +1,637 @@
+"""Generate tests/golden/gp_pred.npz: 50-digit predictive moments, aggregations and scores.
+
+Everything is evaluated in mpmath at 50 digits from the float64 inputs the device reads: the kernel matrix, K_y = K +
+(noise + 1e-8) I, its Cholesky factor (rows, mp.fdot), alpha = K_y^-1 (y - mean), the log-marginal, and per test row
+mu = mean + k*.alpha and sigma^2 = k(x*, x*) - |L^-1 k*|^2 + noise (src/gaussianprocess.jl:110-137,163).  Three groups:
+
+  single/<case>   single leaves of every kernel kind at the shapes where the device changes behaviour: n and routed rows on
+                  both sides of 128 (row tiles, test tiles, split-K), D > 32 (K_tn from the Gram launch), a target offset
+                  by 1000.  Test rows AT training inputs on both sides of a 128 edge, 1e-7 away, far from the data (for the
+                  linear kernels: the origin, where k* = 0, and a large row), and one row listed twice.
+  table/...       a leaf table of 41 leaves for the low-level ABI: 8 observation sets (n = 130 .. 512) repeated over 5
+                  replicas, a COPY and a PREFIX leaf among them and one leaf without routed rows; four kernel ids.  Every
+                  replica's leaves partition the 600 test rows, so each row has one entry per replica.  Per-entry moments,
+                  per-leaf mll, and the aggregations agg_partial_kernel / agg_finish_kernel evaluate (kernels.hpp, the
+                  comment above AggArgs) for mixture (plain off / on), PoE, gPoE and rBCM (a row-dependent prior kernel,
+                  rows that no leaf of group 2 sees), each with its five scores; the same table with the targets offset by
+                  1000 for the mixture, where S1 - S0^2 cancels.
+  config1/...     the README example (make_golden.config1) on the tree of oracle/tree.py: leaf mlls, update! (the
+                  level-order log-sum-exp) and predict through the reference's literal log-domain recursion
+                  (src/common.jl:134-143,275-302), both at 50 digits, and the scores.
+
+Before anything is stored, every value is checked against the float64 oracle (oracle.gp, oracle.spn, oracle.scores;
+tests/ard_linear_dense.DenseGP for ArdLinear) and the n = 1 cases against their closed forms.  Imports: oracle/, datagen,
+tests/ard_linear_dense.py and tests/pred_tolerance.py (the aggregation formula, run here at 50 digits) only.  Run from the repo root:  python tests/golden/make_pred_golden.py  (a few minutes;
+the output is byte-reproducible)
+"""
+import importlib.util
+import io
+import os
+import sys
+import zipfile
+
+import mpmath as mp
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from oracle import gp as ogp, spn as ospn, scores as oscores, tree as otree  # noqa: E402
+from ard_linear_dense import DenseGP  # noqa: E402
+from pred_tolerance import Prop, aggregate, row_entries  # noqa: E402
+
+# the data generator alone, loaded from its file: importing it through the package would run the product's model and tree code
+_spec = importlib.util.spec_from_file_location("datagen", os.path.join(ROOT, "deepstructuredmixtures_amd", "datagen.py"))
+datagen = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(datagen)
+uniform, normal = datagen.uniform, datagen.normal
+
+OUT = os.path.dirname(os.path.abspath(__file__))
+mp.mp.dps = 50
+EPS = np.finfo(np.float64).eps
+
+
+# ------------------------------------------------------------------------------------------ one leaf at 50 digits
+
+class MPLeaf:
+    """One GP leaf at 50 digits.  kind: 0 IsoSE, 1 ArdSE, 2 IsoLinear, 3 ArdLinear; loghyp = the library hyper-vector without
+    the noise.  `targets` = list of (y, mean) pairs sharing the factor (the offset variants); predict() is memoised per row."""
+
+    def __init__(self, kind, loghyp, logNoise, X, targets):
+        self.kind = kind
+        self.X = np.asarray(X, dtype=np.float64)
+        n, D = self.X.shape
+        self.n, self.D = n, D
+        h = [mp.mpf(float(v)) for v in loghyp]
+        self.noise = mp.e ** (2 * mp.mpf(float(logNoise)))
+        if kind == 0:
+            self.il2 = 1 / mp.e ** (2 * h[0])
+            self.s2 = mp.e ** (2 * h[1])
+        elif kind == 1:
+            self.il2 = [1 / mp.e ** (2 * v) for v in h[:D]]
+            self.s2 = mp.e ** (2 * h[D])
+        elif kind == 2:
+            self.il2 = 1 / mp.e ** (2 * h[0])
+        else:
+            self.il2 = [1 / mp.e ** (2 * v) for v in h[:D]]
+        self.x = [self._mprow(r) for r in self.X]
+        c = self.noise + mp.mpf("1e-8")
+        K = [[self.k(self.x[i], self.x[j]) for j in range(i + 1)] for i in range(n)]
+        L = []
+        for i in range(n):
+            row = []
+            for j in range(i):
+                row.append((K[i][j] - mp.fdot(row[:j], L[j][:j])) / L[j][j])
+            row.append(mp.sqrt(K[i][i] + c - mp.fdot(row, row)))
+            L.append(row)
+        self.L = L
+        self.alpha, self.mll, self.means = [], [], []
+        logdet = 2 * mp.fsum(mp.log(L[i][i]) for i in range(n))
+        for y, mean in targets:
+            yc = [mp.mpf(float(v)) - mp.mpf(float(mean)) for v in y]
+            z = self.fwd(yc)
+            a = [mp.mpf(0)] * n                                       # L^T alpha = z
+            for i in range(n - 1, -1, -1):
+                a[i] = (z[i] - mp.fsum(L[j][i] * a[j] for j in range(i + 1, n))) / L[i][i]
+            self.alpha.append(a)
+            self.mll.append(-(mp.fdot(z, z) + logdet + n * mp.log(2 * mp.pi)) / 2)
+            self.means.append(mp.mpf(float(mean)))
+        self.memo = {}
+        Ky = np.array([[float(K[max(i, j)][min(i, j)] + (c if i == j else 0)) for j in range(n)] for i in range(n)])
+        ev = np.linalg.eigvalsh(Ky)
+        self.cond = float(f"{ev[-1] / ev[0]:.4g}")            # tolerance metadata: 4 digits, stable across LAPACK builds
+
+    @staticmethod
+    def _mprow(r):
+        return [mp.mpf(float(v)) for v in r]
+
+    def k(self, a, b):
+        if self.kind == 0:
+            u = [p - q for p, q in zip(a, b)]
+            return self.s2 * mp.e ** (-mp.fdot(u, u) * self.il2 / 2)
+        if self.kind == 1:
+            return self.s2 * mp.fsum(mp.e ** (-((p - q) ** 2) * il / 2) for p, q, il in zip(a, b, self.il2))
+        if self.kind == 2:
+            return mp.fdot(a, b) * self.il2
+        return mp.fdot([p * q for p, q in zip(a, b)], self.il2)
+
+    def fwd(self, b):
+        v = []
+        for i in range(self.n):
+            v.append((b[i] - mp.fdot(self.L[i][:i], v)) / self.L[i][i])
+        return v
+
+    def predict(self, xrow):
+        """([mu per target], sigma^2, k(x*, x*)) of one test row, 50 digits."""
+        key = np.asarray(xrow, dtype=np.float64).tobytes()
+        if key not in self.memo:
+            xs = self._mprow(xrow)
+            ks = [self.k(xi, xs) for xi in self.x]
+            kss = self.k(xs, xs)
+            v = self.fwd(ks)
+            mus = [m + mp.fdot(ks, a) for m, a in zip(self.means, self.alpha)]
+            self.memo[key] = (mus, kss - mp.fdot(v, v) + self.noise, kss)
+        return self.memo[key]
+
+
+def oracle_leaf(kind, loghyp, logNoise, X, y, mean):
+    """The float64 oracle of one leaf (DenseGP for ArdLinear)."""
+    if kind == 3:
+        return DenseGP(X, y, mean, loghyp[:-1], logNoise)
+    return ogp.GaussianProcess(X, y, mean, ogp.make_kernel(kind, loghyp), logNoise, exact_dist=True).update_cholesky()
+
+
+def oracle_kss(kind, loghyp, Xt):
+    if kind == 3:
+        return (Xt * Xt) @ (1.0 / np.exp(np.asarray(loghyp[:-1])) ** 2)
+    return ogp.prior_diag(ogp.make_kernel(kind, loghyp), Xt)
+
+
+def check_moments(tag, cond, mu_mp, var_mp, mu_o, var_o, yscale):
+    """The oracle's moments against the 50-digit values: 16 cond_2(K_y) eps relative to the target's and the variance's
+    scale (the forward error of a backward-stable Cholesky solve)."""
+    tol = 16 * cond * EPS
+    emu = np.max(np.abs(mu_o - mu_mp)) / yscale
+    evar = np.max(np.abs(var_o - var_mp) / np.maximum(var_mp, 1.0))
+    assert emu <= tol and evar <= tol, (tag, emu, evar, tol)
+    return emu, evar
+
+
+def f(v):
+    return np.array([float(a) for a in v])
+
+
+# ------------------------------------------------------------------------------------------ (a) single leaves
+
+SQ = np.sqrt
+# name, kind, n, routed rows, D, loghyp (library hyper-vector without the noise), logNoise, target offset
+SINGLE = [
+    ("isose_n1", 0, 1, 3, 1, [np.log(0.5), 0.1], np.log(0.2), 0.0),
+    ("ardlinear_n1", 3, 1, 3, 2, [np.log(0.7), np.log(1.3), 0.0], np.log(0.2), 0.0),
+    ("isose_n129", 0, 129, 129, 2, [np.log(0.35), 0.0], np.log(0.1), 0.0),
+    ("isose_n257", 0, 257, 257, 3, [np.log(0.4), 0.1], np.log(0.1), 0.0),
+    ("ardse_n200", 1, 200, 128, 4, list(np.log([0.4, 0.6, 0.8, 1.1])) + [-0.2], np.log(0.1), 0.0),
+    ("isolinear_n160", 2, 160, 200, 3, [np.log(0.9), 0.0], np.log(0.1), 0.0),
+    ("ardlinear_n150", 3, 150, 130, 5, list(np.log([0.5, 0.8, 1.1, 1.6, 2.4])) + [0.0], np.log(0.1), 0.0),
+    ("ardlinear_d33", 3, 129, 129, 33, list(np.log(SQ(33) * np.linspace(0.6, 1.8, 33))) + [0.0], np.log(0.1), 0.0),
+    ("isose_d33", 0, 200, 129, 33, [np.log(0.3 * SQ(33)), 0.0], np.log(0.1), 0.0),
+    ("isose_d48", 0, 200, 129, 48, [np.log(0.3 * SQ(48)), 0.0], np.log(0.1), 0.0),
+    ("isose_offset", 0, 200, 150, 2, [np.log(0.35), 0.0], np.log(0.1), 1000.0),
+]
+FAR = 1e3      # SE kinds: exp(-|x* - x|^2 / 2 l^2) underflows to 0 in float64, so mu = mean and sigma^2 = kss + noise exactly
+
+
+def single_rows(si, kind, X, R):
+    """The routed rows of one case (R of them, R + 1 for n = 1) and the positions of the special rows: `at` (training inputs on
+    both sides of the 128 edge, placed at test positions 127 / 128 when R > 128), `near` (1e-7 away), `far`, `dup` (a pair)."""
+    n, D = X.shape
+    Xt = uniform(1100 + si, 0, R * D).reshape((R, D), order="F") * 1.2 - 0.1
+    pos = dict(at=[], near=[], far=[], dup=[])
+    at_src = [127, 128] if n > 128 else [0]
+    at_pos = [127, 128] if R > 128 else [0, 1][:len(at_src)]
+    for p, s in zip(at_pos, at_src):
+        Xt[p] = X[s]
+        pos["at"].append(p)
+    near_src = [126, n - 1] if n > 128 else [0]
+    for j, s in enumerate(near_src):
+        p = 2 + j if R > 128 else len(at_src) + j
+        Xt[p] = X[s] + 1e-7 * (1 if j % 2 == 0 else -1)
+        pos["near"].append(p)
+    p = pos["near"][-1] + 1
+    if kind in (0, 1):
+        Xt[p] = FAR
+        pos["far"].append(p)
+        if R > 4:
+            Xt[p + 1] = -FAR
+            pos["far"].append(p + 1)
+    else:
+        Xt[p] = 0.0                   # the linear kernels' far row: k* = 0, so mu = mean and sigma^2 = 0 + noise exactly
+        pos["far"].append(p)
+        if R > 4:
+            Xt[p + 1] = 50.0          # large extrapolation
+    if n == 1:                        # n = 1: the listed rows plus the duplicate of the first
+        Xt = np.concatenate([Xt, Xt[:1]])
+        pos["dup"] = [0, R]
+    elif R > 128:                     # the row AT a training input in the second test tile, listed again in the first
+        Xt[6] = Xt[128]
+        pos["dup"] = [6, 128]
+    else:
+        Xt[R - 1] = Xt[6]
+        pos["dup"] = [6, R - 1]
+    return Xt, pos
+
+
+def closed_form_n1(kind, loghyp, logNoise, x, y, mean, xs):
+    """n = 1 written out by hand at 50 digits: K_y = k(x, x) + c, alpha = (y - m) / K_y, mu = m + k* alpha,
+    sigma^2 = k** - k*^2 / K_y + noise, mll = -((y - m) alpha + log K_y + log 2pi) / 2."""
+    noise = mp.e ** (2 * mp.mpf(float(logNoise)))
+    c = noise + mp.mpf("1e-8")
+    a = [mp.mpf(float(v)) for v in x]
+    if kind == 0:
+        s2, l2 = mp.e ** (2 * mp.mpf(float(loghyp[1]))), mp.e ** (2 * mp.mpf(float(loghyp[0])))
+        kf = lambda p, q: s2 * mp.e ** (-sum((u - v) ** 2 for u, v in zip(p, q)) / (2 * l2))     # noqa: E731
+    else:
+        il2 = [1 / mp.e ** (2 * mp.mpf(float(v))) for v in loghyp[:len(x)]]
+        kf = lambda p, q: sum(u * v * w for u, v, w in zip(p, q, il2))                        # noqa: E731
+    Ky = kf(a, a) + c
+    yc = mp.mpf(float(y)) - mp.mpf(float(mean))
+    al = yc / Ky
+    mll = -(yc * al + mp.log(Ky) + mp.log(2 * mp.pi)) / 2
+    mus, vs = [], []
+    for r in xs:
+        b = [mp.mpf(float(v)) for v in r]
+        ks = kf(a, b)
+        mus.append(mp.mpf(float(mean)) + ks * al)
+        vs.append(kf(b, b) - ks * ks / Ky + noise)
+    return al, mll, mus, vs
+
+
+def single_cases(flat, log):
+    for si, (name, kind, n, R, D, loghyp, logNoise, off) in enumerate(SINGLE):
+        X = uniform(1000 + si, 0, n * D).reshape((n, D), order="F")
+        y = np.sin(3.0 * X[:, 0]) * np.cos(2.0 * X[:, -1]) + 0.1 * normal(1050 + si, 0, n) + off
+        mean = float(np.mean(y)) if n > 1 else 0.0           # n = 1: y - mean(y) would be zero
+        loghyp = np.array(loghyp, dtype=np.float64)
+        Xt, pos = single_rows(si, kind, X, R)
+        g = MPLeaf(kind, loghyp, logNoise, X, [(y, mean)])
+        res = [g.predict(r) for r in Xt]
+        mu_mp = [r[0][0] for r in res]
+        var_mp = [r[1] for r in res]
+        kss = f([r[2] for r in res])
+        mu, var = f(mu_mp), f(var_mp)
+        if n == 1:
+            al, mll, mus, vs = closed_form_n1(kind, loghyp, logNoise, X[0], y[0], mean, Xt)
+            assert abs(al - g.alpha[0][0]) <= mp.mpf("1e-40") * abs(al) and abs(mll - g.mll[0]) <= mp.mpf("1e-40") * abs(mll), name
+            for a, b in zip(mu_mp + var_mp, mus + vs):
+                assert abs(a - b) <= mp.mpf("1e-40") * max(1, abs(b)), (name, a, b)
+        go = oracle_leaf(kind, loghyp, logNoise, X, y, mean)
+        assert go.info == 0, name
+        mo, vo = go.prediction(Xt)
+        yscale = max(1.0, float(np.max(np.abs(y))))
+        emu, evar = check_moments(name, g.cond, mu, var, mo, vo, yscale)
+        assert abs(go.mll() - float(g.mll[0])) <= 16 * g.cond * EPS * max(1.0, abs(float(g.mll[0]))), name
+        assert np.allclose(oracle_kss(kind, loghyp, Xt), kss, rtol=4 * D * EPS, atol=0), name
+        assert np.array_equal(mu[pos["dup"][0]], mu[pos["dup"][1]]) and var[pos["dup"][0]] == var[pos["dup"][1]]
+        for p in pos["far"]:          # k* = 0 in float64: mu = mean, sigma^2 = kss + noise up to the rounding of the sum
+            assert mu[p] == mean and abs(var[p] - (kss[p] + float(g.noise))) <= EPS * var[p], (name, p, mu[p], var[p])
+        rec = dict(kind=kind, X=X, y=y, mean=mean, loghyp=loghyp, logNoise=logNoise, Xt=Xt, alpha=f(g.alpha[0]),
+                   mll=float(g.mll[0]), mu=mu, var=var, kss=kss, cond=g.cond, at=pos["at"], near=pos["near"], far=pos["far"],
+                   dup=pos["dup"])
+        for k, v in rec.items():
+            flat[f"single/{name}/{k}"] = np.asarray(v)
+        log(f"single {name:15s} kind {kind} n {n:3d} rows {Xt.shape[0]:3d} D {D:2d}  cond {g.cond:9.4g}  "
+            f"oracle err mu {emu:8.2g} var {evar:8.2g}")
+
+
+# ------------------------------------------------------------------------------------------ (b) the leaf table
+
+SETS = [130, 160, 192, 224, 256, 300, 384, 512]
+SET_KID = [0, 3, 1, 0, 2, 3, 0, 1]            # kernel id of each observation set
+HYP = {0: (0, [np.log(0.3), 0.0, np.log(0.1)]),
+       1: (3, [np.log(0.8), np.log(1.2), np.log(1.7), 0.0, np.log(0.1)]),
+       2: (1, [np.log(0.3), np.log(0.5), np.log(0.7), -0.5 * np.log(3.0), np.log(0.1)]),
+       3: (2, [np.log(1.3), 0.0, np.log(0.1)])}        # kernel id -> (kind, library hyper-vector incl. logNoise)
+NT, NB, REP = 600, 8, 5                       # test rows, blocks of 75 rows, replicas
+W_REP = [0.3, 0.25, 0.2, 0.15, 0.1]           # mixture weight of every leaf of a replica: each row's weights sum to 1
+PRIOR_KID = 1                                 # rBCM prior kernel: ArdLinear, k(x*, x*) depends on the row
+OFFSET = 1000.0
+COPY_LEAF, COPY_SRC = 32, 0                   # replica 4, set 0: a declared COPY of replica 0's leaf of set 0
+PREFIX_LEAF, PREFIX_SRC, PREFIX_TAIL = 26, 2, 40   # replica 3, set 2 (ArdLinear): set 2's observations plus 40 more rows
+
+
+def table_layout():
+    """Training data, the observation sets and the routing.  Test rows are split into 8 blocks of 75; set j's leaves may see
+    rows of blocks j and j + 1 (its pool).  In replica c, k[c][j] rows of block j go to set j and the rest to set j - 1, so
+    every replica's leaves partition the test rows and leaf (c, j) sees k[c][j] + 75 - k[c][j + 1] rows (10 .. 150)."""
+    N0, D = 3000, 3
+    N = N0 + PREFIX_TAIL          # the last rows: the PREFIX leaf's tail, after every row of its source (lists ascend)
+    X = uniform(1200, 0, N * D).reshape((N, D), order="F")
+    y = np.sin(3.0 * X[:, 0]) * np.cos(2.0 * X[:, 1]) + X[:, 2] + 0.1 * normal(1201, 0, N)
+    perm = np.argsort(uniform(1202, 0, N0), kind="stable")
+    obs, pos = [], 0
+    for n in SETS:
+        obs.append(np.sort(perm[pos:pos + n]))
+        pos += n
+    tail = np.arange(N0, N)
+    Xt = uniform(1203, 0, NT * D).reshape((NT, D), order="F")
+    yt = np.sin(3.0 * Xt[:, 0]) * np.cos(2.0 * Xt[:, 1]) + Xt[:, 2]
+    rows = np.argsort(uniform(1204, 0, NT), kind="stable").reshape(NB, NT // NB)
+    k = np.floor(5 + 61 * uniform(1205, 0, REP * NB)).astype(int).reshape(REP, NB)   # 5 .. 65
+    k[0, 0], k[0, 1] = 75, 0          # leaf (0, 0): 150 rows
+    k[0, 2], k[0, 3] = 60, 6          # leaf (0, 2): 129 rows
+    k[1, 4], k[1, 5] = 10, 75         # leaf (1, 4): 10 rows
+    routes = []
+    for c in range(REP):
+        for j in range(NB):
+            mine = rows[j][:k[c, j]]
+            nxt = rows[(j + 1) % NB][k[c, (j + 1) % NB]:]
+            routes.append(np.concatenate([mine, nxt]))
+    routes.append(np.zeros(0, dtype=np.int64))               # leaf 40: no routed rows
+    leaf_obs = [obs[l % NB] for l in range(REP * NB)] + [obs[2]]
+    leaf_obs[PREFIX_LEAF] = np.concatenate([obs[PREFIX_SRC], tail])
+    leaf_set = [l % NB for l in range(REP * NB)] + [2]
+    assert all(np.all(np.diff(o) > 0) for o in leaf_obs)                  # dsmgp_set_leaves: strictly ascending lists
+    assert np.array_equal(leaf_obs[PREFIX_LEAF][:obs[PREFIX_SRC].size], obs[PREFIX_SRC])
+    return X, y, obs, tail, Xt, yt, routes, leaf_obs, leaf_set
+
+
+def scores_mp(y, mu, var):
+    """src/scorefunctions.jl:6-16 at 50 digits: mse, sse, mae, sae, nlpd."""
+    n = len(y)
+    yy = [mp.mpf(float(v)) for v in y]
+    d = [a - b for a, b in zip(yy, mu)]
+    se = [a * a for a in d]
+    ae = [abs(a) for a in d]
+    mse, mae = mp.fsum(se) / n, mp.fsum(ae) / n
+    sse = mp.sqrt(mp.fsum((a - mse) ** 2 for a in se) / (n - 1)) / mp.sqrt(n)
+    sae = mp.sqrt(mp.fsum((a - mae) ** 2 for a in ae) / (n - 1)) / mp.sqrt(n)
+    nlpd = mp.fsum((a * a / v + mp.log(2 * mp.pi)) / 2 + mp.log(mp.sqrt(v)) for a, v in zip(d, var)) / n
+    return [mse, sse, mae, sae, nlpd]
+
+
+def check_scores(tag, y, mu, var, ref):
+    o = [oscores.mse(y, mu), oscores.sse(y, mu), oscores.mae(y, mu), oscores.sae(y, mu), oscores.nlpd(y, mu, var)]
+    for name, a, b in zip(("mse", "sse", "mae", "sae", "nlpd"), o, ref):
+        assert abs(a - float(b)) <= 1e-12 * max(1.0, abs(float(b))), (tag, name, a, float(b))
+
+
+def table(flat, log_):
+    X, y, obs, tail, Xt, yt, routes, leaf_obs, leaf_set = table_layout()
+    L = len(routes)
+    D = X.shape[1]
+    yo = y + OFFSET
+    # one 50-digit leaf per observation set (and the PREFIX leaf's own set), both target variants
+    sets = {}
+    for s in range(NB):
+        kind, hyp = HYP[SET_KID[s]]
+        o = obs[s]
+        sets[s] = MPLeaf(kind, hyp[:-1], hyp[-1], X[o], [(y[o], np.mean(y[o])), (yo[o], np.mean(yo[o]))])
+        log_(f"table set {s}: n {o.size} kind {kind} cond {sets[s].cond:.4g}")
+    kind, hyp = HYP[SET_KID[PREFIX_SRC]]
+    po = leaf_obs[PREFIX_LEAF]
+    sets["prefix"] = MPLeaf(kind, hyp[:-1], hyp[-1], X[po], [(y[po], np.mean(y[po])), (yo[po], np.mean(yo[po]))])
+    leaf_key = [leaf_set[l] for l in range(L)]
+    leaf_key[PREFIX_LEAF] = "prefix"
+    route_ptr = np.concatenate([[0], np.cumsum([r.size for r in routes])]).astype(np.int64)
+    route_idx = np.concatenate(routes).astype(np.int64)
+    mu, mu_off, var, kss = [], [], [], []
+    for l in range(L):
+        g = sets[leaf_key[l]]
+        for r in routes[l]:
+            mus, v, k = g.predict(Xt[r])
+            mu.append(mus[0])
+            mu_off.append(mus[1])
+            var.append(v)
+            kss.append(k)
+    mu_f, mu_off_f, var_f = f(mu), f(mu_off), f(var)
+    means = np.array([float(sets[leaf_key[l]].means[0]) for l in range(L)])
+    means_off = np.array([float(sets[leaf_key[l]].means[1]) for l in range(L)])
+    mll = np.array([float(sets[leaf_key[l]].mll[0]) for l in range(L)])
+    mll_off = np.array([float(sets[leaf_key[l]].mll[1]) for l in range(L)])
+    cond = np.array([sets[leaf_key[l]].cond for l in range(L)])
+    kid = np.array([SET_KID[leaf_set[l]] for l in range(L)], dtype=np.int32)
+    # the float64 oracle per leaf
+    worst = 0.0
+    for l in range(L):
+        if routes[l].size == 0:
+            continue
+        kd, hp = HYP[kid[l]]
+        o = leaf_obs[l]
+        e0, e1 = route_ptr[l], route_ptr[l + 1]
+        for yv, m, mref, mllref in ((y, means[l], mu_f, mll), (yo, means_off[l], mu_off_f, mll_off)):
+            go = oracle_leaf(kd, hp[:-1], hp[-1], X[o], yv[o], m)
+            mo, vo = go.prediction(Xt[routes[l]])
+            e = check_moments(f"table leaf {l}", cond[l], mref[e0:e1], var_f[e0:e1], mo, vo, max(1.0, float(np.max(np.abs(yv[o])))))
+            worst = max(worst, *e)
+            assert abs(go.mll() - mllref[l]) <= 16 * cond[l] * EPS * max(1.0, abs(mllref[l])), l
+    log_(f"table: {L} leaves, {route_idx.size} entries, oracle worst {worst:.2g}")
+    # sharing: a declared COPY and a PREFIX leaf
+    op = np.zeros(L, dtype=np.int32)
+    src = np.full(L, -1, dtype=np.int32)
+    plen = np.zeros(L, dtype=np.int64)
+    assert np.array_equal(leaf_obs[COPY_LEAF], leaf_obs[COPY_SRC]) and means[COPY_LEAF] == means[COPY_SRC]
+    op[COPY_LEAF], src[COPY_LEAF] = 1, COPY_SRC
+    op[PREFIX_LEAF], src[PREFIX_LEAF], plen[PREFIX_LEAF] = 2, PREFIX_SRC, obs[PREFIX_SRC].size
+    # coefficients
+    rep = np.array([l // NB for l in range(REP * NB)] + [0])
+    w_mix = np.array([W_REP[c] for c in rep])
+    beta = np.array([0.15 + 0.05 * (l % 3) for l in range(L)])
+    group = np.array([2 if (c == 4 and leaf_set[l] < 4) else c % 2 for l, c in enumerate(rep)], dtype=np.int32)
+    group[L - 1] = 2
+    G = 3
+    seen2 = np.zeros(NT, dtype=bool)
+    for l in range(L):
+        if group[l] == 2:
+            seen2[routes[l]] = True
+    assert 0 < np.count_nonzero(~seen2) < NT
+    kh = HYP[PRIOR_KID]
+    kss_prior = [mp.fdot([mp.mpf(float(v)) ** 2 for v in Xt[r]], [1 / mp.e ** (2 * mp.mpf(float(h))) for h in kh[1][:D]])
+                 for r in range(NT)]
+    noise_prior = mp.e ** (2 * mp.mpf(float(kh[1][-1])))
+    ones = np.ones(L)
+    fams = dict(mixture=(0, w_mix, False), mixture_plain=(0, w_mix, True), poe=(1, ones, False), gpoe=(2, beta, False),
+                rbcm=(3, None, False))
+    out = dict(Xt=Xt, yt=yt, X=X, y=y, obs_ptr=np.concatenate([[0], np.cumsum([o.size for o in leaf_obs])]).astype(np.int64),
+               obs_idx=np.concatenate(leaf_obs).astype(np.int64), kid=kid, mean=means, mean_off=means_off,
+               route_ptr=route_ptr, route_idx=route_idx, op=op, src=src, plen=plen, mu=mu_f, mu_off=mu_off_f, var=var_f,
+               kss=f(kss), mll=mll, mll_off=mll_off, cond=cond, w_mix=w_mix, beta=beta, group=group, G=G,
+               prior_kid=PRIOR_KID, kinds=np.array([HYP[k][0] for k in range(4)]),
+               hyp=np.array([np.pad(HYP[k][1], (0, 5 - len(HYP[k][1])), constant_values=np.nan) for k in range(4)]),
+               hyp_len=np.array([len(HYP[k][1]) for k in range(4)]))
+    ent = row_entries(route_ptr, route_idx, NT)
+    for fam_name, (fam, coef, plain) in list(fams.items()) + [("mixture_off", (0, w_mix, False))]:
+        m_in = mu_off if fam_name == "mixture_off" else mu
+        kw = dict(coef=coef, group=group, G=G, plain=plain, noise_prior=noise_prior)
+        am, av = aggregate(fam, m_in, var, ent, kss_prior=kss_prior, log=mp.log, **kw)
+        amf, avf = f(am), f(av)
+        # float64 evaluation of the same formula from the oracle-checked moments, against the 50-digit values
+        kw["noise_prior"] = float(noise_prior)
+        pm, pv = aggregate(fam, [Prop(v) for v in f(m_in)], [Prop(v) for v in var_f], ent,
+                           kss_prior=[Prop(float(v)) for v in kss_prior], log=Prop.log, **kw)
+        fm = np.array([float(Prop.of(p).v) for p in pm])
+        fv = np.array([float(Prop.of(p).v) for p in pv])
+        if fam == 0:      # S1 = sum W mu^2 per row: the scale of the mixture variance's cancellation
+            s1 = f([mp.fsum(float(w_mix[l]) * m_in[e] ** 2 for l, e in er) for er in ent])
+            out[f"agg/{fam_name}/S1"] = s1
+            assert np.all(np.abs(fv - avf) <= 1e-12 * avf + 8 * EPS * s1), fam_name
+        else:
+            assert np.all(np.abs(fv - avf) <= 1e-12 * avf), fam_name
+        assert np.all(np.abs(fm - amf) <= 1e-12 * np.maximum(1.0, np.abs(amf))), fam_name
+        out[f"agg/{fam_name}/mu"] = amf
+        out[f"agg/{fam_name}/var"] = avf
+        yy = yt + (OFFSET if fam_name == "mixture_off" else 0.0)
+        sc = scores_mp(yy, am, av)
+        check_scores(fam_name, yy, amf, avf, sc)
+        out[f"agg/{fam_name}/scores"] = f(sc)
+        log_(f"table {fam_name:13s} var [{avf.min():.3g}, {avf.max():.3g}]  scores {', '.join(f'{float(v):.6g}' for v in sc)}")
+    for k, v in out.items():
+        flat[f"table/{k}"] = np.asarray(v)
+
+
+# ------------------------------------------------------------------------------------------ (c) config 1 end to end
+
+def config1(flat, log_):
+    """The README example of make_golden.config1 on the tree of oracle/tree.py (the reference's builder restated)."""
+    N = 100
+    x = np.linspace(0.0, 1.0, N)
+    y = np.sin(x * 4 * np.pi + normal(42, 0, N) * 0.2)
+    xt = np.linspace(0.5, 1.5, 100).reshape(-1, 1)[:50] * 0.98
+    xt = np.concatenate([xt[:25], np.linspace(0.05, 0.95, 25).reshape(-1, 1)])
+    yt = np.sin(xt[:, 0] * 4 * np.pi)
+    X = x.reshape(-1, 1)
+    loghyp, logNoise = np.array([1.0, 1.0]), 1.0
+    root = otree.build_tree(X, y, 10, 4, 3, 2, 0.5, True, meanFun=float(np.mean(x)), seed=11)
+    tab = otree.table(root)
+    z = np.load(os.path.join(OUT, "config1.npz"))
+    reg = np.flatnonzero(tab["kind"] == 0)
+    leaf_ptr = np.concatenate([[0], np.cumsum([tab["obs_ptr"][i + 1] - tab["obs_ptr"][i] for i in reg])])
+    assert np.array_equal(leaf_ptr, z["obs_ptr"]) and np.array_equal(tab["obs"], z["obs_idx"])   # the model's leaf table
+    sroot = otree.spn_nodes(root, 0, loghyp, logNoise)
+    leaves = ospn.get_leaves(sroot)
+    mps = [MPLeaf(0, loghyp, logNoise, X[lf.obs], [(y[lf.obs], lf.mean.m)]) for lf in leaves]
+    leaf_mll = [g.mll[0] for g in mps]
+
+    # update!: z and the normalised log-weights of every sum node, at 50 digits (src/common.jl:323-334)
+    def update(node):
+        if node.kind == "gp":
+            return leaf_mll[node.leaf]
+        if node.kind == "split":
+            return mp.fsum(update(c) for c in node.children)
+        K = len(node.children)
+        lw = [-mp.log(K) + update(c) for c in node.children]
+        zz = mp.log(mp.fsum(mp.e ** v for v in lw))
+        node.mp_logweights = [v - zz for v in lw]
+        return zz
+
+    zroot = update(sroot)
+
+    def getchild(node, xv):
+        for k, (d, s) in enumerate(node.split):
+            if xv[d] <= s and (k == 0 or xv[d] > node.split[k - 1][1]):
+                return k
+        raise AssertionError("row outside every child")
+
+    def minpredict(node, xv):
+        if node.kind == "gp":
+            return mps[node.leaf].predict(xv)[0][0]
+        if node.kind == "split":
+            return minpredict(node.children[getchild(node, xv)], xv)
+        return min(minpredict(c, xv) for c in node.children)
+
+    def lse(v):
+        v = [a for a in v if a != -mp.inf]
+        m = max(v)
+        return m + mp.log(mp.fsum(mp.e ** (a - m) for a in v))
+
+    def lpredict(node, xv, mumin):          # src/common.jl:134-143 (leaf), :181-196 (split), :275-292 (sum)
+        if node.kind == "gp":
+            (mus, s2, _) = mps[node.leaf].predict(xv)
+            mu = mus[0]
+            s2 = s2 if s2 > 0 else mp.mpf("1e-8")
+            return mp.log(mu - mumin), mp.log(mu * mu), mp.log(s2)
+        if node.kind == "split":
+            return lpredict(node.children[getchild(node, xv)], xv, mumin)
+        parts = [lpredict(c, xv, mumin) for c in node.children]
+        return tuple(lse([p[i] + w for p, w in zip(parts, node.mp_logweights)]) for i in range(3))
+
+    def flat_mixture(node, xv, w):          # the same mixture unrolled: sum over visited leaves of W mu, W mu^2, W sigma^2
+        if node.kind == "gp":
+            (mus, s2, _) = mps[node.leaf].predict(xv)
+            return [w * mus[0], w * mus[0] ** 2, w * (s2 if s2 > 0 else mp.mpf("1e-8"))]
+        if node.kind == "split":
+            return flat_mixture(node.children[getchild(node, xv)], xv, w)
+        acc = [mp.mpf(0)] * 3
+        for c, lw in zip(node.children, node.mp_logweights):
+            acc = [a + b for a, b in zip(acc, flat_mixture(c, xv, w * mp.e ** lw))]
+        return acc
+
+    mu, var, s1 = [], [], []
+    for r in xt:
+        mumin = minpredict(sroot, r) - 1
+        lm, lm2, ls = lpredict(sroot, r, mumin)
+        m = mp.e ** lm + mumin                                   # :299
+        v = mp.e ** ls + (mp.e ** lm2 - m * m)                   # :300
+        S0, S1, S2 = flat_mixture(sroot, r, mp.mpf(1))
+        assert abs(m - S0) <= mp.mpf("1e-40") and abs(v - (S2 + S1 - S0 * S0)) <= mp.mpf("1e-40"), (m, S0, v)
+        mu.append(m)
+        var.append(v)
+        s1.append(S1)
+    muf, varf, s1f = f(mu), f(var), f(s1)
+    # the float64 oracle: leaf GPs, update!, the literal recursion
+    gps = ospn.make_leaf_gps(sroot, X, y, exact_dist=True)
+    for g in gps:
+        g.update_cholesky()
+    zo = ospn.update(sroot, gps)
+    mo, vo = ospn.predict(sroot, gps, xt)
+    lm_o = np.array([g.mll() for g in gps])
+    cond = max(g.cond for g in mps)
+    assert np.all(np.abs(lm_o - f(leaf_mll)) <= 16 * cond * EPS * np.maximum(1.0, np.abs(f(leaf_mll))))
+    assert abs(zo - float(zroot)) <= 16 * cond * EPS * len(gps) * max(1.0, abs(float(zroot)))
+    assert np.all(np.abs(mo - muf) <= 16 * cond * EPS), float(np.max(np.abs(mo - muf)))
+    assert np.all(np.abs(vo - varf) <= 16 * cond * EPS * varf + 8 * EPS * s1f), float(np.max(np.abs(vo - varf) / varf))
+    sc = scores_mp(yt, mu, var)
+    check_scores("config1", yt, muf, varf, sc)
+    # per-leaf moments for the device's leaf table (route order of the model's routing = leaf order, rows ascending)
+    rows = [[] for _ in leaves]
+
+    def route(node, i, xv):
+        if node.kind == "gp":
+            rows[node.leaf].append(i)
+        elif node.kind == "split":
+            route(node.children[getchild(node, xv)], i, xv)
+        else:
+            for c in node.children:
+                route(c, i, xv)
+
+    for i, r in enumerate(xt):
+        route(sroot, i, r)
+    W = [None] * len(leaves)             # the flat mixture weight of every leaf: product of the sum-node weights on its path
+
+    def weights(node, w):
+        if node.kind == "gp":
+            W[node.leaf] = w
+        elif node.kind == "split":
+            for c in node.children:
+                weights(c, w)
+        else:
+            for c, lw in zip(node.children, node.mp_logweights):
+                weights(c, w * mp.e ** lw)
+
+    weights(sroot, mp.mpf(1))
+    lmu = [mps[l].predict(xt[i])[0][0] for l in range(len(leaves)) for i in rows[l]]
+    lvar = [mps[l].predict(xt[i])[1] for l in range(len(leaves)) for i in rows[l]]
+    rec = dict(x=x, y=y, xt=xt, yt=yt, leaf_mll=f(leaf_mll), root_mll=float(zroot), mu=muf, var=varf, S1=s1f, scores=f(sc),
+               cond=np.array([g.cond for g in mps]), route_ptr=np.concatenate([[0], np.cumsum([len(r) for r in rows])]),
+               route_idx=np.array([i for r in rows for i in r], dtype=np.int64), leaf_mu=f(lmu), leaf_var=f(lvar), leaf_w=f(W))
+    for k, v in rec.items():
+        flat[f"config1/{k}"] = np.asarray(v)
+    log_(f"config1: {len(leaves)} leaves, root mll {float(zroot):.12g}, oracle err mu {np.max(np.abs(mo - muf)):.2g} "
+         f"var {np.max(np.abs(vo - varf)):.2g}")
+
+
+def savez_reproducible(path, arrays):
+    """np.savez_compressed with fixed member timestamps, so that a rerun writes the same bytes."""
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for key in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asarray(arrays[key]), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o600 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def main():
+    def log_(s):
+        print(s, flush=True)
+
+    flat = {}
+    single_cases(flat, log_)
+    table(flat, log_)
+    config1(flat, log_)
+    savez_reproducible(os.path.join(OUT, "gp_pred.npz"), flat)
+
+
+if __name__ == "__main__":
+    main()

@@ -258,3 +258,108 @@ def test_oracle_gradients_match_the_50_digit_references(golden_dir):
         assert abs(g.mll() - float(c["mll"])) <= 16 * float(c["cond"]) * eps * max(1.0, abs(float(c["mll"]))), name
         if kind == 1:
             assert np.all(ref[:c["X"].shape[1]] == 0.0) and c["grad_true"].shape == (c["X"].shape[1],)
+
+
+def test_oracle_prediction_aggregation_and_scores_match_the_50_digit_references(golden_dir):
+    """tests/golden/gp_pred.npz (make_pred_golden.py): the float64 oracle within 16 cond_2(K_y) eps of the 50-digit moments --
+    relative to max(1, max|y|) for mu and to max(1, k** + noise) for sigma^2 -- and its mll as for the gradients.  The
+    leaf table's aggregations (the formula of tests/pred_tolerance.py in float64) and the scores (oracle.scores), and config 1
+    through oracle/spn.py's update! and literal predict recursion on the tree of oracle/tree.py, within those per-entry bounds
+    carried through the formula (pred_tolerance.agg_tol / score_tol)."""
+    import math
+    from ard_linear_dense import DenseGP, prior_diag as ardlin_diag
+    from oracle import scores as oscores, tree as otree
+    from pred_tolerance import agg_tol, aggregate, row_entries, score_tol
+
+    eps = np.finfo(np.float64).eps
+    z = np.load(os.path.join(golden_dir, "gp_pred.npz"))
+    single, T, C = {}, {}, {}
+    for key in z.files:
+        head, rest = key.split("/", 1)
+        if head == "single":
+            name, field = rest.split("/")
+            single.setdefault(name, {})[field] = z[key]
+        else:
+            (T if head == "table" else C)[rest] = z[key]
+
+    def leaf(kind, hyp, X, y, mean):
+        if kind == 3:
+            return DenseGP(X, y, mean, hyp[:-2], hyp[-1])
+        return ogp.GaussianProcess(X, y, mean, ogp.make_kernel(kind, hyp[:-1]), hyp[-1], True).update_cholesky()
+
+    def moments_tol(cond, kss, noise, yscale):
+        b = 16 * np.asarray(cond) * eps
+        return b * yscale, b * np.maximum(1.0, np.asarray(kss) + noise)
+
+    assert sorted(set(int(c["kind"]) for c in single.values())) == [0, 1, 2, 3]
+    for name, c in single.items():
+        kind = int(c["kind"])
+        hyp = np.concatenate([c["loghyp"], [float(c["logNoise"])]])
+        g = leaf(kind, hyp, c["X"], c["y"], float(c["mean"]))
+        assert g.info == 0
+        mu, var = g.prediction(c["Xt"])
+        tm, tv = moments_tol(float(c["cond"]), c["kss"], np.exp(2 * hyp[-1]), max(1.0, float(np.max(np.abs(c["y"])))))
+        assert np.all(np.abs(mu - c["mu"]) <= tm) and np.all(np.abs(var - c["var"]) <= tv), name
+        assert abs(g.mll() - float(c["mll"])) <= 16 * float(c["cond"]) * eps * max(1.0, abs(float(c["mll"]))), name
+    # the leaf table: per entry, both target variants
+    L = T["kid"].size
+    rp, op_ = T["route_ptr"], T["obs_ptr"]
+    nt = T["Xt"].shape[0]
+    mu_o, mu_off_o, var_o = np.zeros(rp[-1]), np.zeros(rp[-1]), np.zeros(rp[-1])
+    tmu, tmu_off, tvar = np.zeros(rp[-1]), np.zeros(rp[-1]), np.zeros(rp[-1])
+    for l in range(L):
+        k = int(T["kid"][l])
+        kind, hyp = int(T["kinds"][k]), T["hyp"][k][:T["hyp_len"][k]]
+        o = T["obs_idx"][op_[l]:op_[l + 1]]
+        rows = T["route_idx"][rp[l]:rp[l + 1]]
+        sl = slice(rp[l], rp[l + 1])
+        for off, mean, mll, mref, mo, tmo in ((0.0, T["mean"], T["mll"], T["mu"], mu_o, tmu),
+                                              (1000.0, T["mean_off"], T["mll_off"], T["mu_off"], mu_off_o, tmu_off)):
+            y = T["y"] + off
+            g = leaf(kind, hyp, T["X"][o], y[o], float(mean[l]))
+            assert g.info == 0 and abs(g.mll() - mll[l]) <= 16 * T["cond"][l] * eps * max(1.0, abs(mll[l])), l
+            if rows.size:
+                mo[sl], var_o[sl] = g.prediction(T["Xt"][rows])
+                tmo[sl], tvar[sl] = moments_tol(T["cond"][l], T["kss"][sl], np.exp(2 * hyp[-1]), max(1.0, float(np.max(np.abs(y)))))
+                assert np.all(np.abs(mo[sl] - mref[sl]) <= tmo[sl]) and np.all(np.abs(var_o[sl] - T["var"][sl]) <= tvar[sl]), l
+    # aggregations in float64 from the oracle's moments, and the oracle's scores of them
+    ent = row_entries(rp, T["route_idx"], nt)
+    pk = int(T["prior_kid"])
+    kss_prior = ardlin_diag(T["hyp"][pk][:T["Xt"].shape[1]], T["Xt"])
+    noise_prior = float(np.exp(2.0 * T["hyp"][pk][T["hyp_len"][pk] - 1]))
+    fams = dict(mixture=(0, T["w_mix"], False), mixture_plain=(0, T["w_mix"], True), poe=(1, np.ones(L), False),
+                gpoe=(2, T["beta"], False), rbcm=(3, None, False), mixture_off=(0, T["w_mix"], False))
+    for fam_name, (fam, coef, plain) in fams.items():
+        off = fam_name == "mixture_off"
+        m_in, tm_in = (mu_off_o, tmu_off) if off else (mu_o, tmu)
+        kw = dict(coef=coef, group=T["group"], G=int(T["G"]), plain=plain, noise_prior=noise_prior)
+        am, av = aggregate(fam, list(m_in), list(var_o), ent, kss_prior=list(kss_prior), log=math.log, **kw)
+        am, av = np.array(am, dtype=np.float64), np.array(av, dtype=np.float64)
+        tm, tv = agg_tol(fam, m_in, var_o, tm_in, tvar, ent, S1=T.get(f"agg/{fam_name}/S1"), kss_prior=kss_prior, **kw)
+        assert np.all(np.abs(am - T[f"agg/{fam_name}/mu"]) <= tm) and np.all(np.abs(av - T[f"agg/{fam_name}/var"]) <= tv), fam_name
+        yt = T["yt"] + (1000.0 if off else 0.0)
+        sc = [oscores.mse(yt, am), oscores.sse(yt, am), oscores.mae(yt, am), oscores.sae(yt, am), oscores.nlpd(yt, am, av)]
+        ts = score_tol(yt, T[f"agg/{fam_name}/mu"], T[f"agg/{fam_name}/var"], tm, tv)
+        assert np.all(np.abs(np.array(sc) - T[f"agg/{fam_name}/scores"]) <= ts), fam_name
+    # config 1: the reference's tree builder, update! and literal predict recursion, all in the oracle
+    x, y, xt = C["x"], C["y"], C["xt"]
+    X = x.reshape(-1, 1)
+    root = otree.spn_nodes(otree.build_tree(X, y, 10, 4, 3, 2, 0.5, True, meanFun=float(np.mean(x)), seed=11), 0, [1.0, 1.0], 1.0)
+    gps = ospn.make_leaf_gps(root, X, y, exact_dist=True)
+    for g in gps:
+        g.update_cholesky()
+    lm = np.array([g.mll() for g in gps])
+    ltol = 16 * C["cond"] * eps * np.maximum(1.0, np.abs(C["leaf_mll"]))
+    assert np.all(np.abs(lm - C["leaf_mll"]) <= ltol)
+    zr = ospn.update(root, gps)
+    assert abs(zr - float(C["root_mll"])) <= np.sum(ltol) + 16 * eps * abs(float(C["root_mll"]))
+    mu, var = ospn.predict(root, gps, xt)
+    noise = np.exp(2.0)
+    tm_e, tv_e = moments_tol(np.repeat(C["cond"], np.diff(C["route_ptr"])), np.full(C["leaf_var"].size, noise), noise,
+                             max(1.0, float(np.max(np.abs(y)))))
+    ent = row_entries(C["route_ptr"], C["route_idx"], xt.shape[0])
+    tm, tv = agg_tol(0, C["leaf_mu"], C["leaf_var"], tm_e, tv_e, ent, S1=C["S1"], coef=C["leaf_w"])
+    assert np.all(np.abs(mu - C["mu"]) <= tm) and np.all(np.abs(var - C["var"]) <= tv)
+    sc = [oscores.mse(C["yt"], mu), oscores.sse(C["yt"], mu), oscores.mae(C["yt"], mu), oscores.sae(C["yt"], mu),
+          oscores.nlpd(C["yt"], mu, var)]
+    assert np.all(np.abs(np.array(sc) - C["scores"]) <= score_tol(C["yt"], C["mu"], C["var"], tm, tv))
