@@ -185,6 +185,31 @@ struct StepLists {
     }
 };
 
+// A blocked triangular sweep after a fit -- the prediction sweep V^T = K_tn L^-T, the L^-T inversion of the gradient pass -- run
+// lane by lane like the factorisation (dsmgp_ctx::nlanes): one device list of each kind for all lanes, lane q's tasks behind those
+// of the lanes before it and its split-K slabs behind theirs; the tasks of lane q's block step k are entry q * nsteps + k of the
+// offset tables.  One lane's panel solves and reduces run under the other's update launches.
+struct SweepLists {
+    int nsteps = 0, nlanes = 1;
+    std::vector<int> upd_off, red_off, trsm_off;   // size nlanes * nsteps + 1
+    DevBuf<TileTask> upd, trsm;
+    DevBuf<ReduceTask> red;
+    std::vector<int> f8_off;                       // fused 8-block tasks per (lane, step), made on the device (build_sweep8_kernel);
+    DevBuf<FusedTask8> f8;                         // empty where the sweep has none (the gradient pass)
+    double* slab = nullptr;                        // split-K workspace of all lanes (slab_grow)
+    size_t slab_cap = 0;                           // doubles
+
+    void clear() {           // empty lists; the allocations and the slab stay for the lists that replace them
+        nsteps = 0;
+        upd.clear();
+        trsm.clear();
+        red.clear();
+        f8.clear();
+    }
+    void release(dsmgp_ctx* c);
+    void drop(dsmgp_ctx* c, bool keep) { keep ? clear() : release(c); }
+};
+
 // Collects the update tiles of one block step and splits their K range over several workgroups when
 // the step has too few tiles to fill the chip (tail of the factorisation, prediction sweeps).
 // Cost model in units of one K column on one CU: a workgroup costs (K/S + C0), rounds = ceil(T*S / CUs).
@@ -417,6 +442,19 @@ struct UpdateSplitter {
     }
 };
 
+// One lane's part of a SweepLists while the host builds it: the update tiles through the lane's splitter, the panel solves, and
+// per block step where its tasks begin in the two (the gradient pass's step 0 has no tasks and is not marked: it begins at 0)
+struct SweepLane {
+    UpdateSplitter U;
+    std::vector<TileTask> trsm;
+    std::vector<int> upd_at, red_at, trsm_at;     // size nsteps
+    void mark(int k) {
+        upd_at[(size_t)k] = (int)U.upd.size();
+        red_at[(size_t)k] = (int)U.red.size();
+        trsm_at[(size_t)k] = (int)trsm.size();
+    }
+};
+
 }  // namespace
 
 struct dsmgp_ctx {
@@ -496,7 +534,6 @@ struct dsmgp_ctx {
     bool joint_ready = false;
     bool vt_valid = false;          // Vt holds K_tn L^-T for the current factor
     bool last_fit_joint = false;
-    double* slabP = nullptr;        // ... of the prediction sweep
     int ncu = 256;
     bool xcd_order = true;          // XCD-aware task order (speed only)
     int tail_split = DSMGP_TAIL_SPLIT_DEFAULT, tail_rounds = DSMGP_TAIL_ROUNDS_DEFAULT;          // plans with one lane
@@ -535,7 +572,7 @@ struct dsmgp_ctx {
     size_t arenaVt_count = 0;       // doubles allocated for the K_tn arena: a test set that replaces another takes it over while it
                                     // fits (releasing ~10 GB and asking the driver for them again took up to 0.6 s of a 0.06 s predict)
     // capacities of the test set's pool-carved arenas (arena_fit: kept across registrations, freed with the plan)
-    size_t cap_Xt = 0, cap_PV = 0, cap_slabP = 0;
+    size_t cap_Xt = 0, cap_PV = 0;
     // pinned host staging for the uploads of a registration (stage_upload): the lists of a test set are ~10 MB at the headline
     // model; through hipMemcpy from pageable vectors they took 9 ms of a 25 ms registration and left the runtime busy behind them
     char* stage = nullptr;
@@ -548,13 +585,7 @@ struct dsmgp_ctx {
     DevBuf<GramTask> pgram;         // K_tn tiles the standalone sweep reads from memory (all of them only when D > 32)
     DevBuf<GramTask> pgram0;        // ... of the joint fit when the Gram is fused: block column 0 only
     DevBuf<PredTask> ptasks;
-    std::vector<int> pupd_off, pred_off, ptrsm_off;
-    DevBuf<FusedTask8> psweep8;     // the sweep's tasks in the block steps that run fused: update + solve of eight 16-row blocks each
-    std::vector<int> psweep8_off;
-    DevBuf<TileTask> pupd, ptrsm;
-    DevBuf<ReduceTask> pred;
-    int psteps = 0;
-    int plan_lanes_test = 1;        // lanes the registered test set's sweep lists were built for
+    SweepLists psweep;              // V^T = K_tn L^-T; in the block steps that run fused: update + solve of eight 16-row blocks per task
     bool test_ready = false;
     bool predicted = false;
     int64_t route_total = 0;
@@ -576,14 +607,8 @@ struct dsmgp_ctx {
     std::vector<char> grad_active;  // dsmgp_set_gradient_leaves: leaves whose gradients are wanted (empty = all)
     double* arenaX = nullptr;       // Xt = L^-T per factor owner, npad x npad
     size_t arenaX_count = 0;
-    double* slabG = nullptr;
-    size_t slabG_count = 0;
     DevBuf<TransTask> gtrans;
-    std::vector<int> gupd_off, gred_off, gtrsm_off;   // entry q * gsteps + k: block step k of lane q
-    int glanes = 1;                                    // lanes of the gradient plan (= nlanes of the plan it was built on)
-    DevBuf<TileTask> gupd, gtrsm;
-    DevBuf<ReduceTask> gred;
-    int gsteps = 0;
+    SweepLists ginv;                // Xt = L^-T (no fused tasks)
     DevBuf<FrobTask> gfrob;
     std::vector<int> gfrob_leaf;    // owner leaf of each frob task
     DevBuf<GradTask> gdot;
@@ -661,12 +686,14 @@ int dev_reserve(dsmgp_ctx* ctx, DevBuf<T>& buf, size_t count) {
     buf.clear();
     return count ? buf.grow(ctx, count) : 0;
 }
+int copy_upload(dsmgp_ctx* ctx, void* dst, const void* src, size_t bytes) {     // synchronous, from pageable memory
+    if (bytes) HIPCHK(ctx, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
 template <class T>
 int dev_upload(dsmgp_ctx* ctx, DevBuf<T>& buf, const std::vector<T>& host) {
     if (int rc = dev_reserve(ctx, buf, host.size())) return rc;
-    if (host.empty()) return 0;
-    HIPCHK(ctx, hipMemcpy(buf.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
+    return copy_upload(ctx, buf.p, host.data(), host.size() * sizeof(T));
 }
 
 bool in_pool(const dsmgp_ctx* c, const void* p) {
@@ -724,6 +751,94 @@ void arena_put(dsmgp_ctx* c, double*& p) {
     if (p && !in_pool(c, p)) (void)hipFree(p);
     p = nullptr;
 }
+// A grow-only workspace of `count` doubles: kept while it holds them, else put back before the new one is asked for.  `cap` is
+// set only once the new one is there: on failure the workspace is empty (p null, cap 0).
+int slab_grow(dsmgp_ctx* c, double*& p, size_t& cap, size_t count) {
+    if (count == 0 || (p && cap >= count)) return 0;
+    arena_put(c, p);
+    cap = 0;
+    if (int rc = arena_get(c, p, count)) return rc;
+    cap = count;
+    return 0;
+}
+
+void SweepLists::release(dsmgp_ctx* c) {
+    nsteps = 0;
+    upd.release();
+    trsm.release();
+    red.release();
+    f8.release();
+    arena_put(c, slab);
+    slab_cap = 0;
+}
+
+// An UpdateSplitter with the context's scheduling settings for a plan of `nl` lanes
+UpdateSplitter make_splitter(const dsmgp_ctx* c, int nl) {
+    UpdateSplitter U;
+    U.ncu = c->ncu;
+    U.xcd = c->xcd_order;
+    U.tail_split = nl > 1 ? c->tail_split_lanes : c->tail_split;
+    U.tail_rounds = nl > 1 ? c->tail_rounds_lanes : c->tail_rounds;
+    U.ragged_rounds = c->ragged_rounds;      // (0 / 1 / 2 rounds cut under lanes: no difference, profiles/r05_grad_lanes_ab.log)
+    U.ragged_div = c->ragged_div;
+    return U;
+}
+
+std::vector<SweepLane> sweep_lanes(const dsmgp_ctx* c, int nl, int nsteps) {
+    std::vector<SweepLane> lanes((size_t)nl);
+    for (SweepLane& q : lanes) {
+        q.U = make_splitter(c, nl);
+        q.upd_at.assign((size_t)nsteps, 0);
+        q.red_at.assign((size_t)nsteps, 0);
+        q.trsm_at.assign((size_t)nsteps, 0);
+    }
+    return lanes;
+}
+
+// The lanes' lists into S, lane after lane through `put` (stage_upload, or copy_upload): the split-K workspace grows to hold the
+// slabs of every lane, each lane's splitter is bound to its part of it, and the offset tables are filled
+int pack_sweep(dsmgp_ctx* c, SweepLists& S, std::vector<SweepLane>& lanes, int (*put)(dsmgp_ctx*, void*, const void*, size_t)) {
+    const int nl = (int)lanes.size(), nsteps = (int)lanes[0].upd_at.size(), nv = nl * nsteps;
+    size_t slabs = 0, nu = 0, nr = 0, nt = 0;
+    for (const SweepLane& q : lanes) {
+        slabs += q.U.max_slabs;
+        nu += q.U.upd.size();
+        nr += q.U.red.size();
+        nt += q.trsm.size();
+    }
+    if (int rc = slab_grow(c, S.slab, S.slab_cap, slabs * TB * TB)) return rc;
+    if (int rc = dev_reserve(c, S.upd, nu)) return rc;
+    if (int rc = dev_reserve(c, S.red, nr)) return rc;
+    if (int rc = dev_reserve(c, S.trsm, nt)) return rc;
+    S.nsteps = nsteps;
+    S.nlanes = nl;
+    S.upd_off.assign((size_t)nv + 1, 0);
+    S.red_off.assign((size_t)nv + 1, 0);
+    S.trsm_off.assign((size_t)nv + 1, 0);
+    size_t bs = 0;
+    int bu = 0, br = 0, bt = 0;
+    for (int q = 0; q < nl; ++q) {
+        SweepLane& ln = lanes[(size_t)q];
+        ln.U.bind(S.slab + bs * TB * TB);
+        for (int k = 0; k < nsteps; ++k) {
+            const size_t v = (size_t)q * (size_t)nsteps + (size_t)k;
+            S.upd_off[v] = bu + ln.upd_at[(size_t)k];
+            S.red_off[v] = br + ln.red_at[(size_t)k];
+            S.trsm_off[v] = bt + ln.trsm_at[(size_t)k];
+        }
+        if (int rc = put(c, S.upd.p + bu, ln.U.upd.data(), ln.U.upd.size() * sizeof(TileTask))) return rc;
+        if (int rc = put(c, S.red.p + br, ln.U.red.data(), ln.U.red.size() * sizeof(ReduceTask))) return rc;
+        if (int rc = put(c, S.trsm.p + bt, ln.trsm.data(), ln.trsm.size() * sizeof(TileTask))) return rc;
+        bs += ln.U.max_slabs;
+        bu += (int)ln.U.upd.size();
+        br += (int)ln.U.red.size();
+        bt += (int)ln.trsm.size();
+    }
+    S.upd_off[(size_t)nv] = bu;
+    S.red_off[(size_t)nv] = br;
+    S.trsm_off[(size_t)nv] = bt;
+    return 0;
+}
 
 void drop_graphs(dsmgp_ctx* c) {
     for (auto& g : c->fit_graph)
@@ -738,9 +853,7 @@ void drop_graphs(dsmgp_ctx* c) {
 // the same buffers (dev_upload) instead of a hipFree + hipMalloc per list and pass
 void free_grad_lists(dsmgp_ctx* c) {
     c->gtrans.clear();
-    c->gupd.clear();
-    c->gtrsm.clear();
-    c->gred.clear();
+    c->ginv.clear();
     c->gfrob.clear();
     c->gdot.clear();
     c->gardlin.clear();
@@ -748,13 +861,9 @@ void free_grad_lists(dsmgp_ctx* c) {
 }
 
 void free_grad(dsmgp_ctx* c) {
-    arena_put(c, c->slabG);
-    c->slabG_count = 0;
+    c->ginv.release(c);
     arena_put(c, c->arenaX);
     c->gtrans.release();
-    c->gupd.release();
-    c->gtrsm.release();
-    c->gred.release();
     c->gfrob.release();
     c->gdot.release();
     c->gardlin.release();
@@ -831,17 +940,13 @@ void free_test(dsmgp_ctx* c, bool keep) {
         c->arenaVt_count = 0;
         arena_put(c, c->arenaXt);
         arena_put(c, c->arenaPV);
-        arena_put(c, c->slabP);
-        c->cap_Xt = c->cap_PV = c->cap_slabP = 0;
+        c->cap_Xt = c->cap_PV = 0;
     }
     c->pgram.drop(keep);
     c->pgram0.drop(keep);
     c->ptasks.drop(keep);
     c->ptasks_slow.drop(keep);
-    c->pupd.drop(keep);
-    c->ptrsm.drop(keep);
-    c->pred.drop(keep);
-    c->psweep8.drop(keep);
+    c->psweep.drop(c, keep);
     c->psegs.drop(keep);
     for (auto& lane : c->phaseJ)
         for (auto& ph : lane) ph.drop(keep);
@@ -1001,14 +1106,10 @@ int build_factor_steps(dsmgp_ctx* c, int lane, bool with_test, StepLists (&phase
     const int L = c->L;
     alg_flops = 0.0;
     const bool fused = gram_fused(c);
-    UpdateSplitter split[2];
+    UpdateSplitter split[2] = {make_splitter(c, c->nlanes), make_splitter(c, c->nlanes)};
     for (int ph = 0; ph < 2; ++ph) {
         StepLists& S = phase[ph];
         UpdateSplitter& U = split[ph];
-        U.ncu = c->ncu;
-        U.xcd = c->xcd_order;
-        U.tail_split = c->nlanes > 1 ? c->tail_split_lanes : c->tail_split;
-        U.tail_rounds = c->nlanes > 1 ? c->tail_rounds_lanes : c->tail_rounds;
         auto in_phase = [&](const LeafHost& lf) {
             const size_t l = (size_t)(&lf - c->leaves.data());
             return c->leaf_group[l] == ph && c->leaf_lane[l] == lane;
@@ -1919,16 +2020,30 @@ void run_step(dsmgp_ctx* c, StepLists& S, int k, PhaseTimer& pt, hipStream_t st,
     }
 }
 
-// Phase `ph` of every lane: the lanes' streams wait for what the context's stream has queued so far (fork), take their block
-// steps -- enqueued step by step, lane after lane, so that both queues stay fed -- and the context's stream waits for them (join).
+// Lanes 1 .. nl-1 wait for what the context's stream has queued so far (fork); the context's stream waits for them (join).
+// Lane 0 is the context's stream.
+int fork_lanes(dsmgp_ctx* c, int nl) {
+    if (nl > 1) {
+        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+        for (int lane = 1; lane < nl; ++lane) HIPCHK(c, hipStreamWaitEvent(c->lane_stream[lane], c->ev_fork, 0));
+    }
+    return 0;
+}
+int join_lanes(dsmgp_ctx* c, int nl) {
+    for (int lane = 1; lane < nl; ++lane) {
+        HIPCHK(c, hipEventRecord(c->ev_join[lane], c->lane_stream[lane]));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[lane], 0));
+    }
+    return 0;
+}
+
+// Phase `ph` of every lane: the lanes fork, take their block steps -- enqueued step by step, lane after lane, so that both queues
+// stay fed -- and join.
 int run_lanes(dsmgp_ctx* c, StepLists (*lists)[2], int ph, PhaseTimer& pt, bool count_launches) {
     int nsteps = 0;
     for (int lane = 0; lane < c->nlanes; ++lane) nsteps = std::max(nsteps, lists[lane][ph].nsteps);
     if (nsteps == 0) return 0;
-    if (c->nlanes > 1) {
-        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-        for (int lane = 1; lane < c->nlanes; ++lane) HIPCHK(c, hipStreamWaitEvent(c->lane_stream[lane], c->ev_fork, 0));
-    }
+    if (int rc = fork_lanes(c, c->nlanes)) return rc;
     // (Starting the second lane half a step late -- after the first launch of the first lane's step 0, so that the latency-bound
     // launches of one lane meet the pipe-bound ones of the other from the start -- measured nothing: headline 0.3870 / 0.3865 /
     // 0.3928 plain, 0.3870 / 0.3878 / 0.3922 staggered; depth 4 0.0495 / 0.0500 / 0.0495 against 0.0501 / 0.0498 / 0.0500
@@ -1936,11 +2051,7 @@ int run_lanes(dsmgp_ctx* c, StepLists (*lists)[2], int ph, PhaseTimer& pt, bool 
     for (int k = 0; k < nsteps; ++k)
         for (int lane = 0; lane < c->nlanes; ++lane) run_step(c, lists[lane][ph], k, pt, c->lane_stream[lane], count_launches);
     HIPCHK(c, hipGetLastError());
-    for (int lane = 1; lane < c->nlanes; ++lane) {
-        HIPCHK(c, hipEventRecord(c->ev_join[lane], c->lane_stream[lane]));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[lane], 0));
-    }
-    return 0;
+    return join_lanes(c, c->nlanes);
 }
 
 // The whole inverse of every diagonal block (the fused steps of a fit leave L_kk and its 16x16 diagonal inverses only): what the
@@ -2519,24 +2630,11 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
             }
         }
     }
-    c->psteps = nsteps;
-    // The sweep runs lane by lane like the factorisation (dsmgp_ctx::nlanes): the lists of lane q's block step k are entry
-    // q * nsteps + k of the offset tables, one lane's panel solves and reduces run under the other's update launches.
+    // the sweep runs lane by lane like the factorisation (SweepLists)
     const int nl = c->nlanes, nv = nl * nsteps;
-    c->plan_lanes_test = nl;
-    std::vector<UpdateSplitter> U((size_t)nl);
-    for (UpdateSplitter& u : U) {
-        u.ncu = c->ncu;
-        u.xcd = c->xcd_order;
-        u.tail_split = c->nlanes > 1 ? c->tail_split_lanes : c->tail_split;
-        u.tail_rounds = c->nlanes > 1 ? c->tail_rounds_lanes : c->tail_rounds;
-    }
-    std::vector<std::vector<TileTask>> trsm_l((size_t)nl);
-    std::vector<int> upd_loc((size_t)nv + 1, 0), red_loc((size_t)nv + 1, 0), trsm_loc((size_t)nv + 1, 0);   // offsets inside the lane's own lists
-    c->pupd_off.assign(nv + 1, 0);
-    c->pred_off.assign(nv + 1, 0);
-    c->ptrsm_off.assign(nv + 1, 0);
-    c->psweep8_off.assign(nv + 1, 0);
+    std::vector<SweepLane> lanes = sweep_lanes(c, nl, nsteps);
+    std::vector<int>& f8_off = c->psweep.f8_off;
+    f8_off.assign((size_t)nv + 1, 0);
     // Fused steps: the tasks are made on the device (build_sweep8_kernel) from one SweepSeg per (leaf, step); the host counts them
     // per step -- a leaf of nt routed rows has ceil(ceil(nt / 16) / 8) tasks in each of its fused steps -- and says where each
     // pair's tasks start.  Classic steps: the leaves that have them, per step (few: the largest leaves of a many-leaf model,
@@ -2560,7 +2658,7 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
         // product depends on its own row of the first operand alone, every rider sums per row, and nothing reads a row beyond a
         // leaf's routed ones (pred_finish / pred_mu / pred_var stop at nt): what sits in the padding rows never reaches a result.
         // Clearing cost more than its own time: 9.6 GB per registration at depth 4.)
-        for (int v = 0; v < nv; ++v) c->psweep8_off[(size_t)v + 1] = c->psweep8_off[(size_t)v] + cnt8[(size_t)v];
+        for (int v = 0; v < nv; ++v) f8_off[(size_t)v + 1] = f8_off[(size_t)v] + cnt8[(size_t)v];
         std::vector<int> cursor((size_t)nv, 0);
         segs.reserve((size_t)L * 4);
         for (int l = 0; l < L; ++l) {
@@ -2574,7 +2672,7 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
                     sg.leaf = l;
                     sg.k = k;
                     sg.src0 = cursor[v0 + (size_t)k];
-                    sg.begin = c->psweep8_off[v0 + (size_t)k];
+                    sg.begin = f8_off[v0 + (size_t)k];
                     sg.n = cnt8[v0 + (size_t)k];
                     segs.push_back(sg);
                     cursor[v0 + (size_t)k] += nt8;
@@ -2585,11 +2683,8 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
     auto build_lane = [&](int lane) {
       for (int k = 0; k < nsteps; ++k) {
         const int v = lane * nsteps + k;
-        UpdateSplitter& Ul = U[(size_t)lane];
-        std::vector<TileTask>& trsm = trsm_l[(size_t)lane];
-        upd_loc[(size_t)v] = (int)Ul.upd.size();
-        red_loc[(size_t)v] = (int)Ul.red.size();
-        trsm_loc[(size_t)v] = (int)trsm.size();
+        SweepLane& ln = lanes[(size_t)lane];
+        ln.mark(k);
         std::vector<TileTask> tiles;
         for (int l : classic[(size_t)v]) {
             const LeafHost& lf = c->leaves[l];
@@ -2634,10 +2729,10 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
                 s.zk = d.z + (size_t)k * TB;           // predictive mean and variance ride along
                 s.wi = d.macc + (size_t)ti * TB;
                 s.sq = d.sacc + (size_t)ti * TB;
-                trsm.push_back(s);
+                ln.trsm.push_back(s);
             }
         }
-        Ul.add_step(tiles, k * TB);
+        ln.U.add_step(tiles, k * TB);
       }
     };
     {
@@ -2666,60 +2761,14 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
         for (int q = started; q < nl; ++q) build_lane_safe(q);
         if (lane_failed.load()) return fail(c, DSMGP_E_NOMEM, "set_test: out of host memory while building the sweep's task lists");
     }
-    // one split-K workspace per lane, one list of each kind for all lanes (lane after lane)
-    size_t slab_tot = 0;
-    std::vector<size_t> slab_base((size_t)nl, 0);
-    for (int q = 0; q < nl; ++q) {
-        slab_base[(size_t)q] = slab_tot;
-        slab_tot += U[(size_t)q].max_slabs;
-    }
     hl.lap("set_test: task uploads");
     if (int rc = stage_upload_list(c, c->psegs, segs)) return rc;
-    if (int rc = dev_reserve(c, c->psweep8, (size_t)c->psweep8_off[(size_t)nv])) return rc;
+    if (int rc = dev_reserve(c, c->psweep.f8, (size_t)f8_off[(size_t)nv])) return rc;
     if (!segs.empty())
-        build_sweep8_kernel<<<(unsigned)((segs.size() + 127) / 128), 128, 0, c->stream>>>(c->psegs.p, (int)segs.size(), c->d_leaves.p, c->psweep8.p,
+        build_sweep8_kernel<<<(unsigned)((segs.size() + 127) / 128), 128, 0, c->stream>>>(c->psegs.p, (int)segs.size(), c->d_leaves.p, c->psweep.f8.p,
                                                                                         c->xcd_order ? 1 : 0);
     HIPCHK(c, hipGetLastError());
-    if (slab_tot) {
-        if (c->pool_base) {
-            if (int rc = arena_get(c, c->slabP, slab_tot * TB * TB)) return rc;
-        } else if (!c->slabP || c->cap_slabP < slab_tot * TB * TB) {
-            arena_put(c, c->slabP);
-            if (int rc = arena_get(c, c->slabP, slab_tot * TB * TB)) return rc;
-            c->cap_slabP = slab_tot * TB * TB;
-        }
-    }
-    {   // the lanes' lists one behind the other in one device list of each kind, uploaded lane by lane
-        size_t nu = 0, nr = 0, nt_ = 0;
-        for (int q = 0; q < nl; ++q) {
-            nu += U[(size_t)q].upd.size();
-            nr += U[(size_t)q].red.size();
-            nt_ += trsm_l[(size_t)q].size();
-        }
-        if (int rc = dev_reserve(c, c->pupd, nu)) return rc;
-        if (int rc = dev_reserve(c, c->pred, nr)) return rc;
-        if (int rc = dev_reserve(c, c->ptrsm, nt_)) return rc;
-        int bu = 0, br = 0, bt = 0;
-        for (int q = 0; q < nl; ++q) {
-            UpdateSplitter& Uq = U[(size_t)q];
-            Uq.bind(c->slabP + slab_base[(size_t)q] * TB * TB);
-            for (int k = 0; k < nsteps; ++k) {
-                const size_t v = (size_t)q * (size_t)nsteps + (size_t)k;
-                c->pupd_off[v] = bu + upd_loc[v];
-                c->pred_off[v] = br + red_loc[v];
-                c->ptrsm_off[v] = bt + trsm_loc[v];
-            }
-            if (int rc = stage_upload(c, c->pupd.p + bu, Uq.upd.data(), Uq.upd.size() * sizeof(TileTask))) return rc;
-            if (int rc = stage_upload(c, c->pred.p + br, Uq.red.data(), Uq.red.size() * sizeof(ReduceTask))) return rc;
-            if (int rc = stage_upload(c, c->ptrsm.p + bt, trsm_l[(size_t)q].data(), trsm_l[(size_t)q].size() * sizeof(TileTask))) return rc;
-            bu += (int)Uq.upd.size();
-            br += (int)Uq.red.size();
-            bt += (int)trsm_l[(size_t)q].size();
-        }
-        c->pupd_off[(size_t)nv] = bu;
-        c->pred_off[(size_t)nv] = br;
-        c->ptrsm_off[(size_t)nv] = bt;
-    }
+    if (int rc = pack_sweep(c, c->psweep, lanes, stage_upload)) return rc;
     if (int rc = stage_upload_list(c, c->pgram, pg)) return rc;
     if (int rc = stage_upload_list(c, c->pgram0, pg0)) return rc;
     if (int rc = stage_upload_list(c, c->ptasks, ptk)) return rc;
@@ -2921,6 +2970,44 @@ int dsmgp_routes(dsmgp_ctx* c, int64_t* route_ptr, int64_t* route_idx) {
     return 0;
 }
 
+}  // extern "C"
+
+namespace {
+// A sweep (SweepLists) on the lanes' streams, step by step, lanes inner: per (lane, step) the fused 8-block tasks, the update
+// launch with its split-K reduce, the panel solves.  pt: spans in slots 7 (fused tasks, updates) and 8 (panel solves), or none.
+int run_sweep(dsmgp_ctx* c, const SweepLists& S, PhaseTimer* pt) {
+    if (int rc = fork_lanes(c, S.nlanes)) return rc;
+    for (int k = 0; k < S.nsteps; ++k)
+        for (int lane = 0; lane < S.nlanes; ++lane) {
+            const int v = lane * S.nsteps + k;
+            const hipStream_t st = c->lane_stream[lane];
+            const int n8 = S.f8_off.empty() ? 0 : S.f8_off[v + 1] - S.f8_off[v];
+            if (n8 > 0) {
+                if (pt) pt->begin(7, st);
+                tile_fused8_kernel<1><<<n8, 512, 0, st>>>(S.f8.p + S.f8_off[v], c->d_kp.p, c->D);
+                if (pt) pt->end(st);
+            }
+            const int nu = S.upd_off[v + 1] - S.upd_off[v];
+            if (nu > 0) {
+                if (pt) pt->begin(7, st);
+                launch_tiles(c, S.upd.p + S.upd_off[v], nu, 0, false, 0, nullptr, 0, st);
+                const int nr = S.red_off[v + 1] - S.red_off[v];
+                if (nr > 0) tile_reduce_kernel<<<nr * REDUCE_WGS, 256, 0, st>>>(S.red.p + S.red_off[v]);
+                if (pt) pt->end(st);
+            }
+            const int ns = S.trsm_off[v + 1] - S.trsm_off[v];
+            if (ns > 0) {
+                if (pt) pt->begin(8, st);
+                launch_tiles(c, S.trsm.p + S.trsm_off[v], ns, 1, false, 0, nullptr, 0, st);
+                if (pt) pt->end(st);
+            }
+        }
+    return join_lanes(c, S.nlanes);
+}
+}  // namespace
+
+extern "C" {
+
 int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
     if (!c) return DSMGP_E_ARG;
     if (!c->fitted) return fail(c, DSMGP_E_STATE, "predict before fit");
@@ -2947,40 +3034,7 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
                 pt.end();
             }
             // V^T = K_tn L^-T, block column by block column (src/gaussianprocess.jl:120), lane by lane on the lanes' streams
-            const int nl = c->plan_lanes_test;
-            if (nl > 1) {
-                HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-                for (int lane = 1; lane < nl; ++lane) HIPCHK(c, hipStreamWaitEvent(c->lane_stream[lane], c->ev_fork, 0));
-            }
-            for (int k = 0; k < c->psteps; ++k)
-                for (int lane = 0; lane < nl; ++lane) {
-                    const int v = lane * c->psteps + k;
-                    hipStream_t st = c->lane_stream[lane];
-                    const int n8 = c->psweep8_off[v + 1] - c->psweep8_off[v];
-                    if (n8 > 0) {
-                        pt.begin(7, st);
-                        tile_fused8_kernel<1><<<n8, 512, 0, st>>>(c->psweep8.p + c->psweep8_off[v], c->d_kp.p, c->D);
-                        pt.end(st);
-                    }
-                    const int nu = c->pupd_off[v + 1] - c->pupd_off[v];
-                    if (nu > 0) {
-                        pt.begin(7, st);
-                        launch_tiles(c, c->pupd.p + c->pupd_off[v], nu, 0, false, 0, nullptr, 0, st);
-                        const int nr = c->pred_off[v + 1] - c->pred_off[v];
-                        if (nr > 0) tile_reduce_kernel<<<nr * REDUCE_WGS, 256, 0, st>>>(c->pred.p + c->pred_off[v]);
-                        pt.end(st);
-                    }
-                    const int ns = c->ptrsm_off[v + 1] - c->ptrsm_off[v];
-                    if (ns > 0) {
-                        pt.begin(8, st);
-                        launch_tiles(c, c->ptrsm.p + c->ptrsm_off[v], ns, 1, false, 0, nullptr, 0, st);
-                        pt.end(st);
-                    }
-                }
-            for (int lane = 1; lane < nl; ++lane) {
-                HIPCHK(c, hipEventRecord(c->ev_join[lane], c->lane_stream[lane]));
-                HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[lane], 0));
-            }
+            if (int rc = run_sweep(c, c->psweep, &pt)) return rc;
             c->vt_valid = true;
         }
         // mu = m + V^T z (= m + K_tn alpha), var = diag(Ktt - V'V) + noise   (src/gaussianprocess.jl:117-126):
@@ -3216,31 +3270,13 @@ int build_grad_plan(dsmgp_ctx* c) {
             c->gfrob_leaf.push_back(l);
         }
     }
-    c->gsteps = nsteps;
-    // The inversion runs lane by lane like the factorisation (dsmgp_ctx::nlanes; a leaf inverts in the lane that factorised it):
-    // the lists of lane q's block step k are entry q * nsteps + k of the offset tables, one lane's panel solves and reduces run
-    // under the other's update launches.
-    const int nl = std::max(1, c->nlanes);
-    c->glanes = nl;
-    const int nv = nl * nsteps;
-    std::vector<UpdateSplitter> U((size_t)nl);
-    for (UpdateSplitter& u : U) {
-        u.ncu = c->ncu;
-        u.xcd = c->xcd_order;
-        u.tail_split = nl > 1 ? c->tail_split_lanes : c->tail_split;
-        u.tail_rounds = nl > 1 ? c->tail_rounds_lanes : c->tail_rounds;
-        u.ragged_rounds = c->ragged_rounds;      // (0 / 1 / 2 rounds cut under lanes: no difference, profiles/r05_grad_lanes_ab.log)
-        u.ragged_div = c->ragged_div;
-    }
-    std::vector<std::vector<TileTask>> trsm_l((size_t)nl);
-    std::vector<int> upd_loc((size_t)nv + 1, 0), red_loc((size_t)nv + 1, 0), trsm_loc((size_t)nv + 1, 0);   // inside the lane's own lists
+    // the inversion runs lane by lane like the factorisation (SweepLists; a leaf inverts in the lane that factorised it)
+    const int nl = c->nlanes;
+    std::vector<SweepLane> lanes = sweep_lanes(c, nl, nsteps);
     for (int q = 0; q < nl; ++q) {
-        std::vector<TileTask>& trsm = trsm_l[q];
+        SweepLane& ln = lanes[(size_t)q];
         for (int k = 1; k < nsteps; ++k) {
-            const int v = q * nsteps + k;
-            upd_loc[v] = (int)U[q].upd.size();
-            red_loc[v] = (int)U[q].red.size();
-            trsm_loc[v] = (int)trsm.size();
+            ln.mark(k);
             std::vector<TileTask> tiles;
             double depth = 0.0;
             for (int l = 0; l < L; ++l) {
@@ -3270,46 +3306,13 @@ int build_grad_plan(dsmgp_ctx* c) {
                     s.k0 = 0;
                     s.k1 = TB;
                     s.update = 0;
-                    trsm.push_back(s);
+                    ln.trsm.push_back(s);
                 }
             }
             const int Kavg = tiles.empty() ? 0 : (int)(depth / tiles.size()) / TB * TB;
-            U[q].add_step_ragged(tiles, std::max(TB, Kavg), k);
+            ln.U.add_step_ragged(tiles, std::max(TB, Kavg), k);
         }
     }
-    // one list of each kind for all lanes: lane q's tasks behind those of the lanes before it, its slabs behind theirs
-    c->gupd_off.assign((size_t)nv + 1, 0);
-    c->gred_off.assign((size_t)nv + 1, 0);
-    c->gtrsm_off.assign((size_t)nv + 1, 0);
-    std::vector<TileTask> upd_all, trsm_all;
-    std::vector<ReduceTask> red_all;
-    size_t slabs_total = 0;
-    std::vector<size_t> slab_base((size_t)nl, 0);
-    for (int q = 0; q < nl; ++q) {
-        slab_base[q] = slabs_total;
-        slabs_total += U[q].max_slabs;
-    }
-    if (slabs_total * TB * TB > c->slabG_count) {
-        arena_put(c, c->slabG);
-        if (int rc = arena_get(c, c->slabG, slabs_total * TB * TB)) return rc;
-        c->slabG_count = slabs_total * TB * TB;
-    }
-    for (int q = 0; q < nl; ++q) {
-        U[q].bind(c->slabG + slab_base[q] * TB * TB);
-        const int ub = (int)upd_all.size(), rb = (int)red_all.size(), tb = (int)trsm_all.size();
-        for (int k = 0; k < nsteps; ++k) {
-            const int v = q * nsteps + k;
-            c->gupd_off[v] = ub + (k >= 1 ? upd_loc[v] : 0);
-            c->gred_off[v] = rb + (k >= 1 ? red_loc[v] : 0);
-            c->gtrsm_off[v] = tb + (k >= 1 ? trsm_loc[v] : 0);
-        }
-        upd_all.insert(upd_all.end(), U[q].upd.begin(), U[q].upd.end());
-        red_all.insert(red_all.end(), U[q].red.begin(), U[q].red.end());
-        trsm_all.insert(trsm_all.end(), trsm_l[q].begin(), trsm_l[q].end());
-    }
-    c->gupd_off[nv] = (int)upd_all.size();
-    c->gred_off[nv] = (int)red_all.size();
-    c->gtrsm_off[nv] = (int)trsm_all.size();
 
     // contraction tiles: every IsoSE leaf (COPY leaves too: their alpha is their own)
     // Order.  A 128x128 tile task moves 2 x 128 x K operand doubles for 2 x 128^2 x K flops: 8 flop/B, below the
@@ -3370,9 +3373,7 @@ int build_grad_plan(dsmgp_ctx* c) {
     }
     if (int rc = dev_upload(c, c->gtrans, trans)) return rc;
     if (int rc = dev_upload(c, c->gfrob, frob)) return rc;
-    if (int rc = dev_upload(c, c->gupd, upd_all)) return rc;
-    if (int rc = dev_upload(c, c->gred, red_all)) return rc;
-    if (int rc = dev_upload(c, c->gtrsm, trsm_all)) return rc;
+    if (int rc = pack_sweep(c, c->ginv, lanes, copy_upload)) return rc;
     if (int rc = dev_upload(c, c->gdot, gd)) return rc;
     if (any_ard && c->D > GRADDOT_STAGE_D)
         return fail(c, DSMGP_E_ARG, "ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
@@ -3467,28 +3468,7 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     HIPCHK(c, e_dot.init());
     // Xt = L^-T (blocks left of the diagonal are never written and never read)
     if (c->gtrans.count) transpose_tile_kernel<<<(int)c->gtrans.count * 16, 256, 0, c->stream>>>(c->gtrans.p);
-    const int gl = c->glanes;
-    if (gl > 1) {       // fork: the lanes' streams wait for the transposes
-        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-        for (int q = 1; q < gl; ++q) HIPCHK(c, hipStreamWaitEvent(c->lane_stream[q], c->ev_fork, 0));
-    }
-    for (int k = 1; k < c->gsteps; ++k)
-        for (int q = 0; q < gl; ++q) {
-            const int v = q * c->gsteps + k;
-            const hipStream_t st = gl > 1 ? c->lane_stream[q] : c->stream;
-            const int nu = c->gupd_off[v + 1] - c->gupd_off[v];
-            if (nu > 0) {
-                launch_tiles(c, c->gupd.p + c->gupd_off[v], nu, 0, false, 0, nullptr, 0, st);
-                const int nr = c->gred_off[v + 1] - c->gred_off[v];
-                if (nr > 0) tile_reduce_kernel<<<nr * REDUCE_WGS, 256, 0, st>>>(c->gred.p + c->gred_off[v]);
-            }
-            const int ns = c->gtrsm_off[v + 1] - c->gtrsm_off[v];
-            if (ns > 0) launch_tiles(c, c->gtrsm.p + c->gtrsm_off[v], ns, 1, false, 0, nullptr, 0, st);
-        }
-    for (int q = 1; q < gl; ++q) {      // join
-        HIPCHK(c, hipEventRecord(c->ev_join[q], c->lane_stream[q]));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[q], 0));
-    }
+    if (int rc = run_sweep(c, c->ginv, nullptr)) return rc;     // the lanes' streams wait for the transposes
     HIPCHK(c, hipEventRecord(e_inv.a, c->stream));
     double* pfrob = c->d_gpart.p;
     double* pdot = pfrob + c->gfrob.count;
@@ -3911,11 +3891,7 @@ int dsmgp_bench_tile(dsmgp_ctx* c, int32_t ntiles, int32_t K, int32_t mode, int3
         tasks[i] = t;
     }
     // mode 0/1: the raw batch; mode 2: the batch as UpdateSplitter would schedule it (split-K + reduce)
-    UpdateSplitter U;
-    U.ncu = c->ncu;
-    U.xcd = c->xcd_order;
-    U.tail_split = c->tail_split;
-    U.tail_rounds = c->tail_rounds;
+    UpdateSplitter U = make_splitter(c, 1);
     DevBuf<double> slabs;
     if (mode == 2) {
         U.add_step(tasks, K);

@@ -170,7 +170,7 @@ def _agg_args(fam_name):
 def test_leaf_table_prediction_aggregation_and_scores(ctx, path, fused_steps, lanes):
     """41 leaves through the low-level ABI: 8 observation sets (n = 130 .. 512) over 5 replicas -- >= 32 leaves in the
     shallow block steps, so with DSMGP_OPT_FUSED_STEPS = 1 they run fused (tile_fused8_kernel, and in the standalone sweep
-    psweep8) -- a declared COPY and a PREFIX leaf (joint: the pred_mu / pred_var slow path), one leaf without routed rows,
+    psweep.f8) -- a declared COPY and a PREFIX leaf (joint: the pred_mu / pred_var slow path), one leaf without routed rows,
     10 .. 150 routed rows per leaf (second test tile), four kernel ids (IsoSE, ArdSE, IsoLinear, ArdLinear), one or two
     leaf lanes.  Per entry mu / sigma^2 and per leaf the mll against the fixture; every family through dsmgp_aggregate and
     through aggregate_partial + aggregate_finish, and the scores; then the targets offset by 1000 for the mixture."""
