@@ -612,6 +612,7 @@ struct dsmgp_ctx {
     DevBuf<FrobTask> gfrob;
     std::vector<int> gfrob_leaf;    // owner leaf of each frob task
     DevBuf<GradTask> gdot;
+    size_t gdot_prod0 = 0;          // first task of an ArdSEProduct leaf in gdot (they form its tail)
     std::vector<int> gdot_leaf;     // leaf of each graddot task
     DevBuf<ArdLinTask> gardlin;     // ArdLinear leaves: column groups of L^-T (ardlin_quad_kernel)
     std::vector<int> gardlin_leaf;  // leaf of each of them
@@ -1021,10 +1022,20 @@ int upload_hyper(dsmgp_ctx* c) {
     return 0;
 }
 
-// an ArdLinear kernel id reads D per-dimension factors wherever its kernel function is evaluated
+// an ArdLinear or ArdSEProduct kernel id reads D per-dimension factors wherever its kernel function is evaluated
 bool ard_linear_short(const dsmgp_ctx* c, int kid) {
     const HyperHost& h = c->hyper[kid];
-    return h.kind == DSMGP_KIND_ARD_LINEAR && (int)h.loghyp.size() - 2 != c->D;
+    return (h.kind == DSMGP_KIND_ARD_LINEAR || h.kind == DSMGP_KIND_ARD_SE_PRODUCT) && (int)h.loghyp.size() - 2 != c->D;
+}
+
+const char* kind_name(int kind) {
+    switch (kind) {
+        case DSMGP_KIND_ISO_SE: return "IsoSE";
+        case DSMGP_KIND_ARD_SE: return "ArdSE";
+        case DSMGP_KIND_ISO_LINEAR: return "IsoLinear";
+        case DSMGP_KIND_ARD_LINEAR: return "ArdLinear";
+        default: return "ArdSEProduct";
+    }
 }
 
 int check_hyper(dsmgp_ctx* c) {
@@ -1035,10 +1046,9 @@ int check_hyper(dsmgp_ctx* c) {
                                               " without hyper-parameters");
         const HyperHost& h = c->hyper[kid];
         const int nl = (int)h.loghyp.size() - 2;
-        const bool ard = h.kind == DSMGP_KIND_ARD_SE || h.kind == DSMGP_KIND_ARD_LINEAR;
+        const bool ard = h.kind == DSMGP_KIND_ARD_SE || h.kind == DSMGP_KIND_ARD_LINEAR || h.kind == DSMGP_KIND_ARD_SE_PRODUCT;
         if (ard && nl != c->D)
-            return fail(c, DSMGP_E_ARG, std::string(h.kind == DSMGP_KIND_ARD_SE ? "ArdSE" : "ArdLinear") +
-                                            " needs one lengthscale per input dimension");
+            return fail(c, DSMGP_E_ARG, std::string(kind_name(h.kind)) + " needs one lengthscale per input dimension");
         if (!ard && nl != 1) return fail(c, DSMGP_E_ARG, "Iso kernels take one lengthscale");
     }
     return 0;
@@ -2349,7 +2359,9 @@ int dsmgp_set_sharing(dsmgp_ctx* c, const int32_t* op, const int32_t* src, const
 int dsmgp_set_hyper(dsmgp_ctx* c, int32_t kernel_id, int32_t kind, const double* loghyp, int32_t n) {
     if (!c) return DSMGP_E_ARG;
     if (kernel_id < 0 || kernel_id >= DSMGP_MAX_KERNEL_IDS || !loghyp || n < 3) return fail(c, DSMGP_E_ARG, "set_hyper: bad arguments");
-    if (kind < 0 || kind > DSMGP_KIND_ARD_LINEAR) return fail(c, DSMGP_E_ARG, "set_hyper: unknown kernel kind");
+    if (kind < 0 || kind > DSMGP_KIND_ARD_SE_PRODUCT) return fail(c, DSMGP_E_ARG, "set_hyper: unknown kernel kind");
+    if (kind == DSMGP_KIND_ARD_SE_PRODUCT && c->D > 0 && n != c->D + 2)
+        return fail(c, DSMGP_E_ARG, "set_hyper: ArdSEProduct needs one lengthscale per input dimension");
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(loghyp[i])) return fail(c, DSMGP_E_ARG, "set_hyper: non-finite hyper-parameter");
     if ((int)c->hyper.size() <= kernel_id) c->hyper.resize(kernel_id + 1);
@@ -3143,7 +3155,8 @@ int dsmgp_aggregate_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain
         (prior_kernel_id < 0 || prior_kernel_id >= (int)c->hyper.size() || c->hyper[prior_kernel_id].kind < 0))
         return fail(c, DSMGP_E_ARG, "aggregate_finish: rBCM needs the kernel id of the model's first leaf");
     if (c->agg_family == AGG_RBCM && ard_linear_short(c, prior_kernel_id))
-        return fail(c, DSMGP_E_ARG, "aggregate_finish: ArdLinear needs one lengthscale per input dimension");
+        return fail(c, DSMGP_E_ARG, std::string("aggregate_finish: ") + kind_name(c->hyper[prior_kernel_id].kind) +
+                                        " needs one lengthscale per input dimension");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nt = (size_t)c->n_t;
     const size_t nblk = (nt + 255) / 256;
@@ -3314,7 +3327,7 @@ int build_grad_plan(dsmgp_ctx* c) {
         }
     }
 
-    // contraction tiles: every IsoSE leaf (COPY leaves too: their alpha is their own)
+    // contraction tiles: every IsoSE and ArdSEProduct leaf (COPY leaves too: their alpha is their own)
     // Order.  A 128x128 tile task moves 2 x 128 x K operand doubles for 2 x 128^2 x K flops: 8 flop/B, below the
     // ridge of the chip unless operands are shared through L2.  Tasks that are adjacent in this list run at the same
     // time on one XCD (xcd_permute below), so the lower tiles of a leaf are listed in super-tiles of GS x GS tiles:
@@ -3324,52 +3337,61 @@ int build_grad_plan(dsmgp_ctx* c) {
     std::vector<GradTask> gd;
     std::vector<size_t> gblock;
     c->gdot_leaf.clear();
-    bool any_ard = false;
-    for (int l = 0; l < L; ++l) {
-        const LeafHost& lf = c->leaves[l];
-        const int kind_l = c->hyper[lf.kid].kind;
-        const bool ard = kind_l == DSMGP_KIND_ARD_SE && c->ard_true_gradient;
-        if (kind_l != DSMGP_KIND_ISO_SE && !ard) continue;
-        any_ard = any_ard || ard;
-        // Shared gradients (the idea of src/fit.jl:313-395: a leaf whose observation set equals its main leaf's takes
-        // that leaf's gradients, `copygradients`): a COPY leaf has its source's factor and kernel id; with the same
-        // ConstMean its alpha is the source's too, so its contraction is the source's and is not computed again.
-        if (c->grad_src[l] >= 0 || !needC[l]) continue;
-        const LeafDev& d = c->h_leaves[l];
-        for (int ib = 0; ib < lf.nb; ib += GS) {
-            gblock.push_back(gd.size());           // one block per (leaf, GS tile rows): these tasks share their A panels
-            for (int jb = 0; jb <= ib; jb += GS)
-                for (int i = ib; i < std::min(ib + GS, lf.nb); ++i)
-                    for (int j = jb; j < std::min(jb + GS, i + 1); ++j) {
-                        GradTask g{};
-                        g.gemm.A = Xt(l) + (size_t)i * TB;
-                        g.gemm.B = Xt(l) + (size_t)j * TB;
-                        g.gemm.C = nullptr;
-                        g.gemm.lda = g.gemm.ldb = lf.npad;
-                        g.gemm.ldc = TB;
-                        g.gemm.k0 = i * TB;
-                        g.gemm.k1 = lf.npad;
-                        g.gemm.update = 0;
-                        g.xa = d.Xg + (size_t)i * TB;
-                        g.xb = d.Xg + (size_t)j * TB;
-                        g.alpha_a = d.alpha + (size_t)i * TB;
-                        g.alpha_b = d.alpha + (size_t)j * TB;
-                        g.ldx = lf.npad;
-                        g.na = std::max(0, std::min(TB, lf.n - i * TB));
-                        g.nb = std::max(0, std::min(TB, lf.n - j * TB));
-                        g.diag = (i == j);
-                        g.kid = lf.kid;
-                        gd.push_back(g);
-                        c->gdot_leaf.push_back(l);
-                    }
+    // The tasks of ArdSEProduct leaves form the tail of the list (pass 1), run by tile_graddot_prod_kernel.
+    bool any_ard = false, any_prod = false;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1) c->gdot_prod0 = gd.size();
+        const size_t begin = gd.size();
+        gblock.clear();
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            const int kind_l = c->hyper[lf.kid].kind;
+            const bool ard = kind_l == DSMGP_KIND_ARD_SE && c->ard_true_gradient;
+            const bool prod = kind_l == DSMGP_KIND_ARD_SE_PRODUCT;
+            if (kind_l != DSMGP_KIND_ISO_SE && !ard && !prod) continue;
+            if (prod != (pass == 1)) continue;
+            any_ard = any_ard || ard;
+            any_prod = any_prod || prod;
+            // Shared gradients (the idea of src/fit.jl:313-395: a leaf whose observation set equals its main leaf's takes
+            // that leaf's gradients, `copygradients`): a COPY leaf has its source's factor and kernel id; with the same
+            // ConstMean its alpha is the source's too, so its contraction is the source's and is not computed again.
+            if (c->grad_src[l] >= 0 || !needC[l]) continue;
+            const LeafDev& d = c->h_leaves[l];
+            for (int ib = 0; ib < lf.nb; ib += GS) {
+                gblock.push_back(gd.size() - begin);   // one block per (leaf, GS tile rows): these tasks share their A panels
+                for (int jb = 0; jb <= ib; jb += GS)
+                    for (int i = ib; i < std::min(ib + GS, lf.nb); ++i)
+                        for (int j = jb; j < std::min(jb + GS, i + 1); ++j) {
+                            GradTask g{};
+                            g.gemm.A = Xt(l) + (size_t)i * TB;
+                            g.gemm.B = Xt(l) + (size_t)j * TB;
+                            g.gemm.C = nullptr;
+                            g.gemm.lda = g.gemm.ldb = lf.npad;
+                            g.gemm.ldc = TB;
+                            g.gemm.k0 = i * TB;
+                            g.gemm.k1 = lf.npad;
+                            g.gemm.update = 0;
+                            g.xa = d.Xg + (size_t)i * TB;
+                            g.xb = d.Xg + (size_t)j * TB;
+                            g.alpha_a = d.alpha + (size_t)i * TB;
+                            g.alpha_b = d.alpha + (size_t)j * TB;
+                            g.ldx = lf.npad;
+                            g.na = std::max(0, std::min(TB, lf.n - i * TB));
+                            g.nb = std::max(0, std::min(TB, lf.n - j * TB));
+                            g.diag = (i == j);
+                            g.kid = lf.kid;
+                            gd.push_back(g);
+                            c->gdot_leaf.push_back(l);
+                        }
+            }
         }
-    }
-    // neighbours in the list sit 8 apart in the launch: they run on one XCD and share its L2; the XCD slots get equal work
-    {
-        gblock.push_back(gd.size());
-        std::vector<double> work(gd.size());
-        for (size_t i = 0; i < gd.size(); ++i) work[i] = (double)(gd[i].gemm.k1 - gd[i].gemm.k0) + 64.0;   // + per-task overhead
-        xcd_deal_by_work(gd, c->gdot_leaf, 0, gd.size(), gblock, work, c->xcd_order);
+        // neighbours in the list sit 8 apart in the launch: they run on one XCD and share its L2; the XCD slots get equal work
+        {
+            gblock.push_back(gd.size() - begin);
+            std::vector<double> work(gd.size() - begin);
+            for (size_t i = 0; i < work.size(); ++i) work[i] = (double)(gd[begin + i].gemm.k1 - gd[begin + i].gemm.k0) + 64.0;   // + per-task overhead
+            xcd_deal_by_work(gd, c->gdot_leaf, begin, gd.size(), gblock, work, c->xcd_order);
+        }
     }
     if (int rc = dev_upload(c, c->gtrans, trans)) return rc;
     if (int rc = dev_upload(c, c->gfrob, frob)) return rc;
@@ -3377,7 +3399,7 @@ int build_grad_plan(dsmgp_ctx* c) {
     if (int rc = dev_upload(c, c->gdot, gd)) return rc;
     if (any_ard && c->D > GRADDOT_STAGE_D)
         return fail(c, DSMGP_E_ARG, "ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
-    c->gstride = any_ard ? 2 + c->D : 2;
+    c->gstride = (any_ard || any_prod) ? 2 + c->D : 2;     // ArdSEProduct: any D (staged in chunks)
 
     // ArdLinear leaves: ARDLIN_COLS columns of L^-T per task (a COPY leaf with its source's mean takes the source's sums,
     // as for the contraction), the tasks of the longest columns first
@@ -3473,8 +3495,12 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     double* pfrob = c->d_gpart.p;
     double* pdot = pfrob + c->gfrob.count;
     double* pleaf = pdot + (size_t)c->gstride * c->gdot.count;
-    if (c->gdot.count)
-        tile_graddot_kernel<<<(int)c->gdot.count, 256, 0, c->stream>>>(c->gdot.p, c->d_kp.p, c->D, pdot, c->gstride);
+    const size_t np0 = c->gdot_prod0;     // tasks [np0, count): ArdSEProduct leaves
+    if (np0)
+        tile_graddot_kernel<<<(int)np0, 256, 0, c->stream>>>(c->gdot.p, c->d_kp.p, c->D, pdot, c->gstride);
+    if (c->gdot.count > np0)
+        tile_graddot_prod_kernel<<<(int)(c->gdot.count - np0), 256, 0, c->stream>>>(c->gdot.p + np0, c->d_kp.p, c->D,
+                                                                                      pdot + (size_t)c->gstride * np0, c->gstride);
     HIPCHK(c, hipEventRecord(e_dot.a, c->stream));
     if (c->gfrob.count) frob_kernel<<<(int)c->gfrob.count, 256, 0, c->stream>>>(c->gfrob.p, pfrob);
     dots_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, pleaf);
@@ -3503,11 +3529,12 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
         if (c->leaves[l].owner != l) trK[l] = trK[c->leaves[l].owner];
     const double* pd = part.data() + c->gfrob.count;
     const size_t gs = (size_t)c->gstride;
-    std::vector<double> Sd;           // per leaf and dimension: contraction with dK / dlog l_d (ArdSE option)
+    std::vector<double> Sd;           // per leaf and dimension: contraction with dK / dlog l_d (ArdSE option, ArdSEProduct)
     if (gs > 2) Sd.assign((size_t)L * c->D, 0.0);
     for (size_t i = 0; i < c->gdot.count; ++i) {
         const int l = c->gdot_leaf[i];
-        if (c->hyper[c->leaves[l].kid].kind == DSMGP_KIND_ARD_SE) {
+        const int kind_l = c->hyper[c->leaves[l].kid].kind;
+        if (kind_l == DSMGP_KIND_ARD_SE || kind_l == DSMGP_KIND_ARD_SE_PRODUCT) {
             for (int d = 0; d < c->D; ++d) Sd[(size_t)l * c->D + d] += pd[gs * i + 2 + d];
         } else {
             S1[l] += pd[gs * i];
@@ -3569,6 +3596,10 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
             // DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT is about ArdSE only); no variance gradient (the slot is a dummy, :216-218)
             for (int d = 0; d < nl; ++d) g[d] = -Sl[(size_t)l * c->D + d] / std::exp(2.0 * h.loghyp[d]);
             g[nl] = 0.0;
+        } else if (h.kind == DSMGP_KIND_ARD_SE_PRODUCT) {
+            // the true derivatives: 0.5 tr(W dK / dlog l_d) from the per-dimension sums, 0.5 tr(W 2K) = tr(W K) (no SURVEY F7 factor)
+            for (int d = 0; d < nl; ++d) g[d] = 0.5 * Sd[(size_t)l * c->D + d];
+            g[nl] = trPK;
         }
         g[nl + 1] = noise * (aa - trK[l]);                    // src/gaussianprocess.jl:176
     }
@@ -3582,7 +3613,9 @@ int dsmgp_kernel_matrix(dsmgp_ctx* c, int32_t kernel_id, const double* x1, int64
     if (!x1 || !x2 || !K_out || n1 <= 0 || n2 <= 0 || c->D <= 0) return fail(c, DSMGP_E_ARG, "kernel_matrix: bad arguments");
     if (kernel_id < 0 || kernel_id >= (int)c->hyper.size() || c->hyper[kernel_id].kind < 0)
         return fail(c, DSMGP_E_STATE, "kernel_matrix: kernel id without hyper-parameters");
-    if (ard_linear_short(c, kernel_id)) return fail(c, DSMGP_E_ARG, "kernel_matrix: ArdLinear needs one lengthscale per input dimension");
+    if (ard_linear_short(c, kernel_id))
+        return fail(c, DSMGP_E_ARG, std::string("kernel_matrix: ") + kind_name(c->hyper[kernel_id].kind) +
+                                        " needs one lengthscale per input dimension");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = upload_hyper(c)) return rc;
     const int D = c->D;
@@ -3646,14 +3679,16 @@ int dsmgp_timings(dsmgp_ctx* c, double* out) {
 
 int dsmgp_work_gradients(dsmgp_ctx* c, double* alg_flops_inverse, double* alg_flops_contraction, int32_t* n_contraction_tiles) {
     if (!c) return DSMGP_E_ARG;
-    // L^-T of every factor owner: n^3/3; contraction (alpha alpha^T - K_y^-1) o K o P of every IsoSE leaf: the lower
+    // L^-T of every factor owner: n^3/3; contraction (alpha alpha^T - K_y^-1) o K o P of every IsoSE / ArdSEProduct leaf: the lower
     // tiles of L^-T L^-1, n^3/3 again (2 x 128 x 128 x K per tile with K = n - 128 i)
     double fi = 0.0, fc = 0.0;
     for (int l = 0; l < c->L; ++l) {
         const LeafHost& lf = c->leaves[l];
         const double n = (double)lf.n;
         if (lf.owner == l) fi += n * n * n / 3.0;
-        if (lf.kid < (int)c->hyper.size() && c->hyper[lf.kid].kind == DSMGP_KIND_ISO_SE) fc += n * n * n / 3.0;
+        if (lf.kid < (int)c->hyper.size() &&
+            (c->hyper[lf.kid].kind == DSMGP_KIND_ISO_SE || c->hyper[lf.kid].kind == DSMGP_KIND_ARD_SE_PRODUCT))
+            fc += n * n * n / 3.0;
     }
     if (alg_flops_inverse) *alg_flops_inverse = fi;
     if (alg_flops_contraction) *alg_flops_contraction = fc;

@@ -102,7 +102,8 @@ struct GramTask {
 // rounding).  ArdSE is the additive form sigma^2 * sum_d exp(-0.5 (a_d-b_d)^2 / l_d^2)
 // (src/kernels.jl:39-49).  IsoLinear is a.b / l^2 (src/kernels.jl:189-194).  ArdLinear is sum_d (a_d b_d) / l_d^2, the
 // generic ArdKernel loop of src/kernels.jl:39-49 with kappa = z / l_d^2 (:228-229): per dimension the product a_d b_d, scaled
-// by 1 / l_d^2 and added in ascending d (one fma: bit-symmetric in a and b).
+// by 1 / l_d^2 and added in ascending d (one fma: bit-symmetric in a and b).  ArdSEProduct (KIND 4, not a reference kernel) is
+// sigma^2 exp(z), z = sum_d (a_d-b_d)^2 * (-0.5 / l_d^2) in one fma per dimension, ascending d (bit-symmetric as well).
 template <int KIND>
 __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam& p, int D, int half,
                                                double (*sa)[TB], double (*sb)[TB / 2]) {
@@ -135,7 +136,7 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
         if (!rows_live) continue;
         for (int d = 0; d < dn; ++d) {
             const double a0 = sa[d][r0], a1 = sa[d][r0 + 1], a2 = sa[d][r0 + 2], a3 = sa[d][r0 + 3];
-            const double nhd = (KIND == 1 || KIND == 3) ? p.nh[d0 + d] : 0.0;   // -0.5 / l_d^2, resp. 1 / l_d^2
+            const double nhd = (KIND == 1 || KIND == 3 || KIND == 4) ? p.nh[d0 + d] : 0.0;   // -0.5 / l_d^2, resp. 1 / l_d^2
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const double b = sb[d][cb + 8 * q];
@@ -156,11 +157,17 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
                     acc[q][1] = fma(a1, b, acc[q][1]);
                     acc[q][2] = fma(a2, b, acc[q][2]);
                     acc[q][3] = fma(a3, b, acc[q][3]);
-                } else {
+                } else if (KIND == 3) {
                     acc[q][0] = fma(a0 * b, nhd, acc[q][0]);
                     acc[q][1] = fma(a1 * b, nhd, acc[q][1]);
                     acc[q][2] = fma(a2 * b, nhd, acc[q][2]);
                     acc[q][3] = fma(a3 * b, nhd, acc[q][3]);
+                } else {
+                    double u;
+                    u = a0 - b; acc[q][0] = fma(u * u, nhd, acc[q][0]);
+                    u = a1 - b; acc[q][1] = fma(u * u, nhd, acc[q][1]);
+                    u = a2 - b; acc[q][2] = fma(u * u, nhd, acc[q][2]);
+                    u = a3 - b; acc[q][3] = fma(u * u, nhd, acc[q][3]);
                 }
             }
         }
@@ -178,7 +185,8 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
             if (KIND == 0) kv = p.sigma2 * exp_nonpos(acc[q][j] * nh);
             else if (KIND == 1) kv = p.sigma2 * acc[q][j];
             else if (KIND == 2) kv = acc[q][j] * il2;
-            else kv = acc[q][j];
+            else if (KIND == 3) kv = acc[q][j];
+            else kv = p.sigma2 * exp_nonpos(acc[q][j]);
             const bool valid = (r < tk.na) && (c < tk.nb);
             if (!valid) kv = 0.0;
             if (tk.sym && tk.diag && r == c) kv = valid ? kv + (p.noise + 1e-8) : 1.0;
@@ -199,6 +207,7 @@ __global__ __launch_bounds__(256) void gram_tile_kernel(const GramTask* __restri
     else if (p.kind == 1) gram_half_tile<1>(tk, p, D, half, sa, sb);
     else if (p.kind == 2) gram_half_tile<2>(tk, p, D, half, sa, sb);
     else if (p.kind == 3) gram_half_tile<3>(tk, p, D, half, sa, sb);
+    else if (p.kind == 4) gram_half_tile<4>(tk, p, D, half, sa, sb);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -317,8 +326,11 @@ __device__ __forceinline__ void gram_accumulate(double (&z)[NA][NB], const doubl
                 z[i][j] += exp_nonpos((u * u) * nhd);
             } else if (KIND == 2) {
                 z[i][j] = fma(a[i], b[j], z[i][j]);
-            } else {
+            } else if (KIND == 3) {
                 z[i][j] = fma(a[i] * b[j], nhd, z[i][j]);
+            } else {
+                const double u = a[i] - b[j];
+                z[i][j] = fma(u * u, nhd, z[i][j]);
             }
         }
 }
@@ -331,7 +343,8 @@ __device__ __forceinline__ double gram_finish(double z, const KParam& p, int row
     if (KIND == 0) kv = p.sigma2 * exp_nonpos(z * p.nh0);
     else if (KIND == 1) kv = p.sigma2 * z;
     else if (KIND == 2) kv = z * p.il2;
-    else kv = z;
+    else if (KIND == 3) kv = z;
+    else kv = p.sigma2 * exp_nonpos(z);
     if (!EDGE) return kv;
     const bool valid = (row < na) && (col < nb);
     if (!valid) kv = 0.0;
@@ -366,7 +379,7 @@ __device__ __forceinline__ void gram_tile_epilogue(const TileTask& tk, const KPa
                 a[i] = pa[d * TB + 16 * i];
                 b[i] = pb[d * TB + 4 * i];
             }
-            gram_accumulate<KIND, 4, 4>(z, a, b, (KIND == 1 || KIND == 3) ? p.nh[d] : 0.0);
+            gram_accumulate<KIND, 4, 4>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4) ? p.nh[d] : 0.0);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -401,6 +414,9 @@ __device__ __forceinline__ void tile_epilogue(const TileTask& tk, d4 (&acc)[4][4
         } else if (p.kind == 3) {
             if (edge) gram_tile_epilogue<3, true>(tk, p, D, acc, red, sb);
             else gram_tile_epilogue<3, false>(tk, p, D, acc, red, sb);
+        } else if (p.kind == 4) {
+            if (edge) gram_tile_epilogue<4, true>(tk, p, D, acc, red, sb);
+            else gram_tile_epilogue<4, false>(tk, p, D, acc, red, sb);
         }
         return;
     }
@@ -816,7 +832,7 @@ __device__ __forceinline__ void syrk_gram_epilogue(const TileTask& tk, const KPa
 #pragma unroll
             for (int r = 0; r < 4; ++r) z[j][0][r] = 0.0;
         for (int d = 0; d < D; ++d) {
-            const double nhd = (KIND == 1 || KIND == 3) ? p.nh[d] : 0.0;
+            const double nhd = (KIND == 1 || KIND == 3 || KIND == 4) ? p.nh[d] : 0.0;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 double a[1], b[4];
@@ -848,6 +864,7 @@ __device__ __forceinline__ void syrk_finish(const TileTask& tk, d4 (&acc)[9], co
         else if (p.kind == 1) syrk_gram_epilogue<SHAPE, 1>(tk, p, D, acc, blk, sa);
         else if (p.kind == 2) syrk_gram_epilogue<SHAPE, 2>(tk, p, D, acc, blk, sa);
         else if (p.kind == 3) syrk_gram_epilogue<SHAPE, 3>(tk, p, D, acc, blk, sa);
+        else if (p.kind == 4) syrk_gram_epilogue<SHAPE, 4>(tk, p, D, acc, blk, sa);
     } else {
         syrk_epilogue<SHAPE>(tk, acc, blk);
     }
@@ -1015,7 +1032,7 @@ __device__ __forceinline__ void rows_gram_epilogue(const TileTask& tk, const KPa
             for (int i = 0; i < NR; ++i) a[i] = pa[d * TB + 16 * i];
 #pragma unroll
             for (int i = 0; i < 4; ++i) b[i] = pb[d * TB + 4 * i];
-            gram_accumulate<KIND, NR, 4>(z, a, b, (KIND == 1 || KIND == 3) ? p.nh[d] : 0.0);
+            gram_accumulate<KIND, NR, 4>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4) ? p.nh[d] : 0.0);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1049,6 +1066,7 @@ __device__ __forceinline__ void tile_rows_body(const TileTask& tk, double (*sA)[
         else if (p.kind == 1) rows_gram_epilogue<NR, 1>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
         else if (p.kind == 2) rows_gram_epilogue<NR, 2>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
         else if (p.kind == 3) rows_gram_epilogue<NR, 3>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
+        else if (p.kind == 4) rows_gram_epilogue<NR, 4>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -1227,7 +1245,8 @@ struct GradTask {
 constexpr int GRADDOT_STAGE_D = 35;
 // ostride = doubles per task in `out`: 2, or 2 + D when the per-dimension sums of the additive ArdSE kernel are
 // asked for (dsmgp_set_option DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT): out[2 + d] = sum_rc (alpha_r alpha_c - G_rc) *
-// sigma^2 exp(-u_d^2 / 2 l_d^2) * u_d^2 / l_d^2, u_d = x_rd - x_cd -- the contraction with dK / dlog l_d.
+// sigma^2 exp(-u_d^2 / 2 l_d^2) * u_d^2 / l_d^2, u_d = x_rd - x_cd -- the contraction with dK / dlog l_d.  2 + D too when an
+// ArdSEProduct leaf has tasks: out[2 + d] = sum_rc (alpha_r alpha_c - G_rc) K_rc u_d^2 / l_d^2, its dK / dlog l_d.
 __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __restrict__ tasks,
                                                               const KParam* __restrict__ kp, int D,
                                                               double* __restrict__ out, int ostride) {
@@ -1367,6 +1386,123 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
     if (threadIdx.x == 0) {
         const double wgt = g.diag ? 1.0 : 2.0;
         out[(size_t)ostride * blockIdx.x] = wgt * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+        out[(size_t)ostride * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    }
+}
+
+// ArdSEProduct leaves (DSMGP_KIND_ARD_SE_PRODUCT), any D: the contraction of tile_graddot_kernel with out[2 + d] =
+// sum_rc (alpha_r alpha_c - G_rc) K_rc u_d^2 / l_d^2 and out[0] = 0 (the host takes tr(W K) from its trace identity).  A kernel
+// of its own, launched over the tail of the task list: as an arm of tile_graddot_kernel it cost that kernel 304 bytes of
+// scratch per lane.  K_rc = sigma^2 exp(sum_d u_d^2 nh_d) once per entry from all dimensions (the operations of
+// gram_accumulate<4>), with the coordinates staged GRADDOT_STAGE_D dimensions at a time (one stage for all four row groups
+// when D fits at once); the trace is taken from acc first, then acc <- (alpha_r alpha_c - G_rc) K_rc, and each dimension
+// costs one fma per entry.
+__global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTask* __restrict__ tasks,
+                                                                   const KParam* __restrict__ kp, int D,
+                                                                   double* __restrict__ out, int ostride) {
+    __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
+    __shared__ double red[2][4];
+    static_assert((GRADDOT_STAGE_D + 1) * 256 <= 2 * NRING * KC2 * LDP, "a chunk of coordinates and the alphas fit the ring");
+    double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
+    double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
+    const GradTask g = tasks[blockIdx.x];
+    const KParam p = kp[g.kid];
+    d4 acc[4][4];
+    gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);      // ends on a barrier: the ring is free
+    const int t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+    double tr = 0.0;
+    constexpr int CH = GRADDOT_STAGE_D;
+    double* xs = smem;
+    double* al = smem + (size_t)CH * 256;
+    const int nch = (D + CH - 1) / CH;
+    const double wgt = g.diag ? 1.0 : 2.0;
+#pragma unroll
+    for (int rn = 0; rn < 4; ++rn) {
+        const int r = wr * 64 + 16 * rn + l15;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+            if (g.diag && r == c && r < g.na) tr += acc[i >> 2][rn][i & 3];
+        }
+    }
+    al[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[t - TB] : 0.0);
+#pragma unroll
+    for (int rn = 0; rn < 4; ++rn) {
+        const int r = wr * 64 + 16 * rn + l15;
+        const bool rv = r < g.na;
+        double z[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) z[i] = 0.0;
+        for (int ch = 0; ch < nch; ++ch) {
+            const int d0 = ch * CH, dn = min(CH, D - d0);
+            if (nch > 1 || rn == 0) {
+                __syncthreads();
+                for (int e = t; e < dn * 256; e += 256) {
+                    const int d = e >> 8, rc = e & 255;
+                    xs[e] = (rc < TB) ? ((rc < g.na) ? g.xa[rc + (size_t)(d0 + d) * g.ldx] : 0.0)
+                                      : ((rc - TB < g.nb) ? g.xb[rc - TB + (size_t)(d0 + d) * g.ldx] : 0.0);
+                }
+                __syncthreads();
+            }
+            for (int d = 0; d < dn; ++d) {
+                const double nhd = p.nh[d0 + d];
+                const double a = xs[d * 256 + r];
+                const double* xb = xs + d * 256 + TB + wc * 64 + l4;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const double u = a - xb[16 * (i >> 2) + 4 * (i & 3)];
+                    z[i] = fma(u * u, nhd, z[i]);
+                }
+            }
+        }
+        const double ar = al[r];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+            const double pre = ar * al[TB + c] - acc[i >> 2][rn][i & 3];
+            acc[i >> 2][rn][i & 3] = (rv && c < g.nb) ? pre * (p.sigma2 * exp_nonpos(z[i])) : 0.0;
+        }
+    }
+    for (int ch = 0; ch < nch; ++ch) {
+        const int d0 = ch * CH, dn = min(CH, D - d0);
+        if (nch > 1) {
+            __syncthreads();
+            for (int e = t; e < dn * 256; e += 256) {
+                const int d = e >> 8, rc = e & 255;
+                xs[e] = (rc < TB) ? ((rc < g.na) ? g.xa[rc + (size_t)(d0 + d) * g.ldx] : 0.0)
+                                  : ((rc - TB < g.nb) ? g.xb[rc - TB + (size_t)(d0 + d) * g.ldx] : 0.0);
+            }
+            __syncthreads();
+        }
+        for (int d = 0; d < dn; ++d) {
+            double sd = 0.0;
+#pragma unroll
+            for (int rn = 0; rn < 4; ++rn) {
+                const double a = xs[d * 256 + wr * 64 + 16 * rn + l15];
+                const double* xb = xs + d * 256 + TB + wc * 64 + l4;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const double u = a - xb[16 * (i >> 2) + 4 * (i & 3)];
+                    sd = fma(acc[i >> 2][rn][i & 3], u * u, sd);
+                }
+            }
+            for (int o = 32; o > 0; o >>= 1) sd += __shfl_down(sd, o);
+            __syncthreads();
+            if (lane == 0) red[0][w] = sd;
+            __syncthreads();
+            if (t == 0)   // u^2 / l_d^2 = -2 nh_d u^2
+                out[(size_t)ostride * blockIdx.x + 2 + d0 + d] =
+                    wgt * (-2.0 * p.nh[d0 + d]) * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+        }
+    }
+    __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) tr += __shfl_down(tr, o);
+    if (lane == 0) red[1][w] = tr;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[(size_t)ostride * blockIdx.x] = 0.0;
         out[(size_t)ostride * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
     }
 }
@@ -2380,7 +2516,7 @@ __global__ __launch_bounds__(128) void pred_finish_kernel(const LeafDev* __restr
     const int r = tk.row0 + threadIdx.x;
     if (r >= lf.nt) return;
     double kss;
-    if (p.kind == 0) kss = p.sigma2;
+    if (p.kind == 0 || p.kind == 4) kss = p.sigma2;
     else if (p.kind == 1) kss = p.sigma2 * (double)D;
     else if (p.kind == 2) {
         double q = 0.0;
@@ -2418,7 +2554,7 @@ __global__ __launch_bounds__(256) void pred_var_kernel(const LeafDev* __restrict
     block_reduce_store(s, red, t);
     if (t < TB && tk.row0 + t < lf.nt) {
         double kss;
-        if (p.kind == 0) kss = p.sigma2;
+        if (p.kind == 0 || p.kind == 4) kss = p.sigma2;      // IsoSE, ArdSEProduct: k(x, x) = sigma^2
         else if (p.kind == 1) kss = p.sigma2 * (double)D;
         else if (p.kind == 2) {
             double q = 0.0;
@@ -2617,7 +2753,7 @@ __global__ __launch_bounds__(256) void agg_finish_kernel(const double* __restric
     } else if (family == AGG_RBCM) {
         const KParam p = kp[prior_kid];
         double kss;
-        if (p.kind == 0) kss = p.sigma2;
+        if (p.kind == 0 || p.kind == 4) kss = p.sigma2;      // IsoSE, ArdSEProduct: k(x, x) = sigma^2
         else if (p.kind == 1) kss = p.sigma2 * (double)D;
         else if (p.kind == 2) {
             double q = 0.0;

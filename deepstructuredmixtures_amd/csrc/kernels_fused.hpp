@@ -123,7 +123,7 @@ __device__ __forceinline__ void rowsplit_gram_init(int gna, int gnb, const KPara
             for (int i = 0; i < NRW; ++i) a[i] = pa[d * TB + 16 * i];
 #pragma unroll
             for (int j = 0; j < NJ; ++j) b[j] = pb[d * TB + 16 * (j >> 2) + 4 * (j & 3)];
-            gram_accumulate<KIND, NRW, NJ>(z, a, b, (KIND == 1 || KIND == 3) ? AS_CONST_F64(p.nh)[d] : 0.0);
+            gram_accumulate<KIND, NRW, NJ>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4) ? AS_CONST_F64(p.nh)[d] : 0.0);
         }
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -247,11 +247,13 @@ __device__ __forceinline__ void tile_fused8_body(const FusedTask8* __restrict__ 
                 else if (p.kind == 1) rowsplit_gram_init<1, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 2) rowsplit_gram_init<2, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 3) rowsplit_gram_init<3, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
+                else if (p.kind == 4) rowsplit_gram_init<4, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
             } else {
                 if (p.kind == 0) rowsplit_gram_init<0, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 1) rowsplit_gram_init<1, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 2) rowsplit_gram_init<2, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 3) rowsplit_gram_init<3, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
+                else if (p.kind == 4) rowsplit_gram_init<4, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
             }
         }
         __syncthreads();    // the coordinates are no longer read: the ring takes the operand chunks
@@ -536,7 +538,7 @@ __device__ __forceinline__ void syrk_gram_inplace(const TileTask& tk, const KPar
         cbk[i] = (SHAPE == 0) ? blk[3 + j] : blk[2 * g3 + (j > 1 ? 1 : 0)];
     }
     if constexpr (KIND != 0) {
-        // ArdSE / IsoLinear / ArdLinear: one block, two of its entries at a time (the exp per dimension of the additive kernel and the
+        // ArdSE / IsoLinear / ArdLinear / ArdSEProduct: one block, two of its entries at a time (the exp per dimension of the additive kernel and the
         // unrolled dot product each wanted one register more than the task has at four)
 #pragma unroll
         for (int i = 0; i < 9; ++i)
@@ -545,7 +547,7 @@ __device__ __forceinline__ void syrk_gram_inplace(const TileTask& tk, const KPar
                 double z[1][2] = {{0.0, 0.0}};
 #pragma unroll 1
                 for (int d = 0; d < D; ++d) {
-                    const double nhd = (KIND == 1 || KIND == 3) ? AS_CONST_F64(p.nh)[d] : 0.0;
+                    const double nhd = (KIND == 1 || KIND == 3 || KIND == 4) ? AS_CONST_F64(p.nh)[d] : 0.0;
                     double a[1], b[2];
                     a[0] = sa[d * TB + 16 * rbk[i] + l15];
 #pragma unroll
@@ -864,6 +866,7 @@ __device__ __forceinline__ void diag_fused_reg(const TileTask& tt, const DiagTas
     else if (p.kind == 1) syrk_gram_inplace<SHAPE, 1>(tt, p, D, acc, blk, S);
     else if (p.kind == 2) syrk_gram_inplace<SHAPE, 2>(tt, p, D, acc, blk, S);
     else if (p.kind == 3) syrk_gram_inplace<SHAPE, 3>(tt, p, D, acc, blk, S);
+    else if (p.kind == 4) syrk_gram_inplace<SHAPE, 4>(tt, p, D, acc, blk, S);
     __syncthreads();                                        // the coordinates are no longer read: panel and rhs take their place
     diag_reg_body<W>(d, acc, S);
 }

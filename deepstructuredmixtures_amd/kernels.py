@@ -15,6 +15,7 @@ KIND_ISO_SE = 0
 KIND_ARD_SE = 1
 KIND_ISO_LINEAR = 2
 KIND_ARD_LINEAR = 3
+KIND_ARD_SE_PRODUCT = 4
 
 
 class KernelFunction:
@@ -125,6 +126,32 @@ class ArdLinear(KernelFunction):
 
     def __repr__(self):
         return f"ArdLinear({self.logl.tolist()})"
+
+
+class ArdSEProduct(KernelFunction):
+    """Product-form ARD squared exponential exp(2 logs) * exp(-0.5 sum_d (a_d-b_d)^2 / exp(logl_d)^2) over the D input
+    dimensions (GPML's covSEard).  Not a kernel of the reference, whose ArdSE is additive.  Same hyper-vector
+    layout as ArdSE; all gradients are the true derivatives of the log-marginal (include/dsmgp_hip.h, dsmgp_gradients)."""
+    kind = KIND_ARD_SE_PRODUCT
+
+    def __init__(self, logl, logs):
+        self.logl = np.array(logl, dtype=np.float64).reshape(-1)
+        self.logs = float(logs)
+        self.dl = np.zeros_like(self.logl)
+        self.ds = 0.0
+
+    def loghyp(self):
+        return np.concatenate([self.logl, [self.logs]])
+
+    def set_loghyp(self, v):
+        self.logl = np.array(v[:-1], dtype=np.float64)
+        self.logs = float(v[-1])
+
+    def copy(self):
+        return ArdSEProduct(self.logl.copy(), self.logs)
+
+    def __repr__(self):
+        return f"ArdSEProduct({self.logl.tolist()}, {self.logs})"
 
 
 class ConstMean:

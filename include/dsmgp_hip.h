@@ -39,6 +39,11 @@ typedef struct dsmgp_ctx dsmgp_ctx;
  * reference's ArdLinear cannot be fitted (getdistancematrix returns a Vector{Matrix} no kernelmatrix method takes, :232;
  * getgradients reads an undefined name, :247). */
 #define DSMGP_KIND_ARD_LINEAR 3
+/* ArdSEProduct: the product-form squared exponential with one length-scale per input dimension (GPML covSEard),
+ * k(a, b) = sigma^2 exp(z), z = sum_d (a_d - b_d)^2 * (-0.5 / l_d^2) added in ascending d (each term depends on (a_d - b_d)^2
+ * only: k(a, b) == k(b, a) to the bit).  Hyper-vector [logl_1..logl_D, logs, logNoise] as ArdSE; exactly D length-scales
+ * (set_hyper refuses another length once set_train has fixed D).  Not a kernel of the reference, whose ArdSE is additive. */
+#define DSMGP_KIND_ARD_SE_PRODUCT 4
 
 /* per-leaf sharing decisions of the shared-Cholesky fit! (src/fit.jl:107-117) */
 #define DSMGP_SHARE_FULL   0      /* update_cholesky!               src/gaussianprocess.jl:82-108 */
@@ -162,7 +167,9 @@ int dsmgp_scores(dsmgp_ctx* ctx, const double* y_test /* n_t */, double* out /* 
  *      ArdLinear: [dl_1..dl_D, 0, dnoise] with the true derivative dl_d = 0.5 tr((alpha alpha^T - K_y^-1) dK/dlog l_d)
  *      = -((alpha . x_d)^2 - x_d^T K_y^-1 x_d) / l_d^2 (x_d = column d of the leaf's inputs; n^2 D flops per leaf on the L^-T
  *      of the trace term, any D; DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT does not apply).  With all l_d equal their sum is
- *      IsoLinear's dl (src/kernels.jl:196-200). */
+ *      IsoLinear's dl (src/kernels.jl:196-200).
+ *      ArdSEProduct: [dl_1..dl_D, ds, dnoise], all true derivatives (no SURVEY F7 factor): dl_d = 0.5 sum_rc W_rc K_rc
+ *      (x_rd - x_cd)^2 / l_d^2 and ds = tr(W K), W = alpha alpha^T - K_y^-1, K without noise; any D. */
 int dsmgp_gradients(dsmgp_ctx* ctx, double* grad_out, int32_t stride);
 /* Restricts dsmgp_gradients to the leaves with active[l] != 0 (NULL: every leaf again; a new leaf table resets it): the rows
  * of the others come back as zeros, and neither L^-T nor the contraction tiles of leaves nobody asked for are computed (a

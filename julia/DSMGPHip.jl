@@ -35,7 +35,32 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census
+export attach!, detach!, census, ArdSEProduct
+
+# ---------------------------------------------------------------------------------------------- ArdSEProduct
+"""
+    ArdSEProduct(logℓ, logσ)
+
+The product-form ARD squared exponential σ² exp(-½ Σ_d (a_d - b_d)² / ℓ_d²) (GPML's covSEard), with ArdSE's fields.  The
+reference's ArdSE is the additive form (src/kernels.jl:39-49); this kernel lives on the device only (kind 4), so of the
+reference's kernel methods it has just what GaussianProcess (src/gaussianprocess.jl:50-58) and params / setparams!
+(:139-161) call on a kernel.  Its gradients are the true derivatives, written into ∂ℓ and ∂σ by updategradients!.
+"""
+mutable struct ArdSEProduct{T<:AbstractFloat} <: DeepStructuredMixtures.ArdKernel
+    logℓ::Vector{T}
+    logσ::T
+    ∂ℓ::Vector{T}
+    ∂σ::T
+end
+ArdSEProduct(logℓ, logσ) = ArdSEProduct(logℓ, logσ, zero(logℓ), zero(logσ))
+DeepStructuredMixtures.getvariance(k::ArdSEProduct; logscale=false) = logscale ? k.logσ : exp(2 * k.logσ)
+DeepStructuredMixtures.getstd(k::ArdSEProduct) = exp(k.logσ)
+DeepStructuredMixtures.setvariance!(k::ArdSEProduct, v::AbstractFloat) = (k.logσ = v)
+DeepStructuredMixtures.getlengthscales(k::ArdSEProduct; logscale=false) = logscale ? k.logℓ : exp.(k.logℓ)
+DeepStructuredMixtures.setlengthscale!(k::ArdSEProduct{T}, l::AbstractVector{T}) where {T} = (k.logℓ[:] = l)
+# the per-dimension squared distances GaussianProcess stores in gp.P (the array ArdSE builds; the device never reads it)
+DeepStructuredMixtures.getdistancematrix(k::ArdSEProduct{T}, x1::AbstractMatrix{T}, x2::AbstractMatrix{T}) where {T} =
+    DeepStructuredMixtures.getdistancematrix(ArdSE(k.logℓ, k.logσ), x1, x2)
 
 # ---------------------------------------------------------------------------------------------- library
 const LIB = Ref{Ptr{Cvoid}}(C_NULL)
@@ -54,11 +79,13 @@ kind(::IsoSE) = Int32(0)
 kind(::ArdSE) = Int32(1)
 kind(::IsoLinear) = Int32(2)
 kind(::ArdLinear) = Int32(3)     # DSMGP_KIND_ARD_LINEAR: sum_d a_d b_d / ℓ_d² (the reference's own methods cannot fit it, src/kernels.jl:232,247)
+kind(::ArdSEProduct) = Int32(4)  # DSMGP_KIND_ARD_SE_PRODUCT: σ² exp(-½ Σ_d (a_d - b_d)² / ℓ_d²), not a kernel of the reference
 # hyper-vector of one kernel id on the reference's log scale, [logℓ..., logσ, logNoise] (src/gaussianprocess.jl:141-161)
 loghyp(k::IsoSE, ln) = Float64[k.logℓ, k.logσ, ln]
 loghyp(k::ArdSE, ln) = Float64[k.logℓ..., k.logσ, ln]
 loghyp(k::IsoLinear, ln) = Float64[k.logℓ, 0.0, ln]             # the variance slot is a dummy (src/kernels.jl:181-183)
 loghyp(k::ArdLinear, ln) = Float64[k.logℓ..., 0.0, ln]          # ... here too (src/kernels.jl:216-218)
+loghyp(k::ArdSEProduct, ln) = Float64[k.logℓ..., k.logσ, ln]    # the layout of ArdSE
 
 # ---------------------------------------------------------------------------------------------- session
 "One device context + the leaf table of one model (or of one stand-alone GaussianProcess)."
@@ -475,8 +502,8 @@ function fetchgradients!(s::Session)
     GC.@preserve g chk(s, ccall(sym(:dsmgp_gradients), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32), s.h, g, Int32(s.stride)))
     for (l, gp) in enumerate(s.gps)
         k = gp.kernel
-        nl = k isa Union{ArdSE,ArdLinear} ? length(k.logℓ) : 1
-        if k isa Union{ArdSE,ArdLinear}
+        nl = k isa Union{ArdSE,ArdLinear} || k isa ArdSEProduct ? length(k.logℓ) : 1
+        if k isa Union{ArdSE,ArdLinear} || k isa ArdSEProduct
             k.∂ℓ[:] = g[1:nl, l]        # ArdLinear: written in place, never through getgradients (src/kernels.jl:247 cannot run)
         else
             k.∂ℓ = g[1, l]
