@@ -22,6 +22,15 @@ predict (RCCL over xGMI).  Rank 0 prints one JSON line.
                          fit_predict: mu, var (predictive moments of the n_t test rows), root_mll, leaf_mll;
                          train: hyperparameters (after the step's ADAM update), mll, gradient.
                          The inputs come from fixed seeds: two builds run with the same arguments compare file for file.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line (with
+the per-step spread, the device seconds of the timed region, the roofline from the timed launches and, N > 1, the per-rank
+report).  Everything that takes device or host time of its own beside the warm-up and timed steps runs with --full only:
+
+    --full               the f64-MFMA probe before warm-up and after the timed loop, an untimed step with every kernel
+                         category timed (device_seconds_per_step), the drop-in series (predict running its own sweep, and on
+                         new rows), the one-lane step of the roofline, BASELINE configs 2, 3 and depth 4 (`configs`), the CPU
+                         baseline, and with N > 1 the second series over the library's own RCCL exchange
 """
 import argparse
 import json
@@ -251,7 +260,7 @@ def blas_threads():
 
 
 def short_series(ctx, step, flops_step, steps, warmup, torch):
-    """A short timed series of one of the other single-GPU BASELINE configs (run by the default bench after the headline series,
+    """A short timed series of one of the other single-GPU BASELINE configs (run by bench --full after the headline series,
     outside its timed region): `steps` calls of step() on wall clock with totals-only timing, then the same number with HIP events
     around the launches of the dominant kernel -> {step_s, roofline}.  flops_step = sum n^3/3 + n^2 n_t over the leaves."""
     ctx.set_profile(0)
@@ -563,9 +572,13 @@ def main():
     ap.add_argument("--hyper", default="survey", choices=sorted(HYPER),
                     help="hyper-parameters of the run: survey (default: IsoSE(log 0.3, 0), logNoise log 0.1) or the "
                          "reference's own defaults IsoSE(1, 1), logNoise 1 (src/treeStructure.jl:332-334), SURVEY 8(d)'s secondary point")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: f64-MFMA probe, per-category step, drop-in series, "
+                         "one-lane roofline step, BASELINE configs 2, 3 and depth 4, CPU baseline, N > 1 device-exchange series")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short series of BASELINE configs 2, 3 and depth 4 that follow the headline series (N = 1, default config)")
+                    help="with --full: skip the short series of BASELINE configs 2, 3 and depth 4 that follow the headline series "
+                         "(N = 1, default config)")
     ap.add_argument("--no-profile", action="store_true", help="do not time kernel categories with hipEvents")
     ap.add_argument("--unfused-gram", action="store_true",
                     help="diagnostic: every Gram tile through memory first (DSMGP_OPT_FUSED_GRAM = 0), for A/B runs")
@@ -669,8 +682,9 @@ def main():
     # N > 1 over RCCL: the library's own communicator (dsmgp_fit_exchange / dsmgp_aggregate_exchange: payload in HBM, collective
     # on the context's stream) is built and PROVEN now, before the first series, and left on standby: the timed series below
     # travels over torch.distributed (the path every world-2 test covers), a second series of the same steps then over the
-    # communicator -- so the first hardware run with more than one rank shows both paths in one line
-    if td is not None and exchange_backend == "nccl" and n_sub == 1 and isinstance(ctx, dsm.hipabi.Context) and not args.simulate_shard:
+    # communicator -- so the first hardware run with more than one rank shows both paths in one line.  --full only
+    if (args.full and td is not None and exchange_backend == "nccl" and n_sub == 1 and isinstance(ctx, dsm.hipabi.Context)
+            and not args.simulate_shard):
         model.shard.device_comm(ctx, force=True, standby=True)
     if args.unfused_gram:
         ctx.set_option(dsm.hipabi.OPT_FUSED_GRAM, 0)
@@ -703,8 +717,8 @@ def main():
         return dsm.predict(model, Xt)
 
     # f64-MFMA probe (register-only loop over the whole chip; also reports the shader clock it held) BEFORE warm-up and
-    # IMMEDIATELY AFTER the timed loop: with the clock sampled inside the steps it tells box from code when two runs differ
-    can_probe = hasattr(ctx, "probe_f64_mfma_detail") and not args.simulate_shard
+    # IMMEDIATELY AFTER the timed loop: with the clock sampled inside the steps it tells box from code when two runs differ (--full)
+    can_probe = args.full and hasattr(ctx, "probe_f64_mfma_detail") and not args.simulate_shard
     probe_before = ctx.probe_f64_mfma_detail(8) if can_probe else None
     t_warm = 0.1
     for _ in range(args.warmup):
@@ -747,7 +761,8 @@ def main():
                if args.dump_outputs else None)
     probe_after = ctx.probe_f64_mfma_detail(8) if can_probe else None
     xs1, xn1 = model.shard.exchange_seconds, model.shard.exchanges
-    if not args.no_profile:   # one more, untimed, step with every category timed: the breakdown printed below
+    if args.full and not args.no_profile:   # one more, untimed, step with every category timed: the breakdown printed below
+                                            # (a plain run prints the categories of the timed region itself)
         timed = dict(cats)
         ctx.set_profile(2)
         step()
@@ -773,9 +788,10 @@ def main():
         td.all_gather_object(ranks_info, mine)
 
     # The same steps once more with the exchanges inside the library (RCCL on the context's stream, payload in HBM): every rank
-    # holds the standby communicator or none does (its set-up MIN-reduces every verdict), so every rank enters this block or none
+    # holds the standby communicator or none does (its set-up MIN-reduces every verdict), so every rank enters this block or none;
+    # without --full no rank has set one up
     device_series = None
-    if td is not None and model.shard.standby_ctx is not None:
+    if args.full and td is not None and model.shard.standby_ctx is not None:
         mu_t, var_t = mu.copy(), var.copy()
         model.shard.activate_device_exchange()
         step()                                   # its fit_exchange is cross-checked against torch.distributed (dist.Shard.fit_exchange)
@@ -847,23 +863,23 @@ def main():
                 "frac": achieved / F64_MATRIX_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
                 "kernel": kname, "avg_launch_ms": avg_launch * 1e3, "launches_per_step": n_l // args.steps,
                 "alg_flops_per_step": fl_step, "lanes": lanes, "launch_seconds_per_step": {"sum": t_cat / args.steps, "union": t_union / args.steps}}
+        # the same kernel against what THIS chip's matrix pipe delivered right after the timed loop (register-only f64 MFMA
+        # loop, 8 waves per SIMD; --full), and the peak rescaled to the shader clock held inside the steps: 78.6 TFLOP/s is
+        # 256 CUs x 4 SIMDs x 32 flop per cycle at 2.4 GHz
         if probe_after is not None:
-            # the same kernel against what THIS chip's matrix pipe delivered right after the timed loop (register-only f64 MFMA
-            # loop, 8 waves per SIMD), and the peak rescaled to the shader clock held inside the steps: 78.6 TFLOP/s is
-            # 256 CUs x 4 SIMDs x 32 flop per cycle at 2.4 GHz
             roof["frac_of_probe"] = achieved / probe_after["tflops"]
-            if step_clock:
-                ghz = float(np.median(step_clock))
-                roof["clock_ghz_in_steps"] = ghz
-                roof["frac_at_held_clock"] = achieved / (F64_MATRIX_PEAK_TFLOPS * ghz / 2.4)
+        if step_clock:
+            ghz = float(np.median(step_clock))
+            roof["clock_ghz_in_steps"] = ghz
+            roof["frac_at_held_clock"] = achieved / (F64_MATRIX_PEAK_TFLOPS * ghz / 2.4)
     nobs = np.array([lf.nobs for lf in model.leaves], dtype=np.float64)
     matrix_flops_total = float(np.sum(nobs ** 3) / 3 + np.sum(nobs ** 2 * np.diff(ptr)))   # Cholesky + predict solves
 
     # The drop-in call pattern of src/common.jl:304 -- fit!(model) + update!(model) on a model whose fit does not know the test
     # set, then predict(model, x) running its own sweep -- as a second TIMED SERIES of the same --steps (one GPU only; the
-    # step above registers its test set before the first fit, dsm.resident_test, which has no reference counterpart).
+    # step above registers its test set before the first fit, dsm.resident_test, which has no reference counterpart).  --full only
     standalone = None
-    if world == 1 and not args.simulate_shard and not CONFIGS[args.config].get("stream"):
+    if args.full and world == 1 and not args.simulate_shard and not CONFIGS[args.config].get("stream"):
         ctx.set_profile(0)      # also renames the update kernel's instantiation: these launches stay out of the profiler's
                                 # average of tile_gemm_kernel_v2<false, 0, *> (the kernel of the roofline block)
         ctx.set_joint(False)
@@ -975,14 +991,14 @@ def main():
             out["drop_in"] = standalone
         if roof is not None:
             out["roofline"] = roof
-        if (world == 1 and args.config == "dsmgp_n100k_d8" and not args.simulate_shard and not args.no_other_configs
+        if (args.full and world == 1 and args.config == "dsmgp_n100k_d8" and not args.simulate_shard and not args.no_other_configs
                 and args.hyper == "survey"):
-            # BASELINE configs 2, 3 and depth 4 on the same GPU, each a short series of its own (after every headline series)
+            # BASELINE configs 2, 3 and depth 4 on the same GPU, each a short series of its own (after the headline series)
             try:
                 out["configs"] = other_configs(local_rank, torch)
             except Exception as e:      # noqa: BLE001 -- the headline line must be printed whatever happens to the extras
                 out["configs"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(model, X, y, Xt, ptr, idx)
                 out["speedup_vs_cpu_baseline"] = out["cpu_baseline"]["value"] / per_step

@@ -1081,8 +1081,9 @@ def test_bench_two_ranks_on_one_gpu_matches_one_rank(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ["--config", "dsmgp_n20k_d8", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dump-outputs", str(tmp_path / "one")] + common,
-                         env=env, capture_output=True, text=True, timeout=600)
+    # --full: the one-rank line below also carries the probe, the drop-in series and the probe-relative roofline
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--full", "--dump-outputs", str(tmp_path / "one")]
+                         + common, env=env, capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     j1 = json.loads(one.stdout.strip().splitlines()[-1])
     # --dump-outputs: what the last timed step returned (predictive moments, root and leaf log-marginals), float64
@@ -2169,7 +2170,7 @@ def test_bench_two_ranks_over_gloo_prints_one_json_line():
     """bench.py --gpus 2 without a launcher (it starts its own two ranks under torch.distributed.run), exchange over gloo with both
     ranks on this one GPU: the rehearsal of the N > 1 bench path the driver runs on a multi-GPU node.  Rank 0's stdout must carry
     ONE JSON line and nothing else (gloo announces its connections on stdout: bench.py points fd 1 at stderr while the groups come
-    up), with both ranks' shares, the exchange seconds, and no device-exchange series (that needs RCCL)."""
+    up), with both ranks' shares, the exchange seconds, and no device-exchange series (that needs RCCL and --full)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -2186,3 +2187,25 @@ def test_bench_two_ranks_over_gloo_prints_one_json_line():
     assert [x["rank"] for x in ranks] == [0, 1] and sum(x["n_leaves"] for x in ranks) == 144
     assert abs(sum(x["cholesky_flop_share"] for x in ranks) - 1.0) < 1e-12
     assert all(x["exchanges_per_step"] == 2 and x["exchange_s_per_step"] > 0 for x in ranks)
+
+
+def test_bench_plain_line_leaves_the_extras_to_full(tmp_path):
+    """A plain `bench.py --gpus 1` run does only what its headline figure needs: the line carries the headline keys, the per-step
+    spread and the roofline of the timed launches, and none of what --full adds (probe, drop-in series, one-lane step, other
+    configs, CPU baseline); --dump-outputs still writes the last timed step, whose root log-marginal is the line's."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--config", "dsmgp_n20k_d8", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[:500]
+    j = json.loads(lines[0])
+    assert j["unit"] == "s" and j["higher_is_better"] is False and j["dtype"] == "f64" and j["steps"] == 2 and j["warmup"] == 1
+    assert j["value"] > 0 and abs(j["ms_per_step"] - 1e3 * j["value"]) <= 1e-9 * j["ms_per_step"]
+    assert j["step_s"]["min"] <= j["step_s"]["median"] <= j["step_s"]["max"] and j["roofline"]["bound"] == "mfma"
+    assert not {"f64_mfma_probe", "drop_in", "drop_in_s", "configs", "cpu_baseline"} & set(j)
+    assert not {"frac_of_probe", "single_lane"} & set(j["roofline"]) and 1.0 < j["roofline"]["clock_ghz_in_steps"] < 3.0
+    d = {k: np.load(tmp_path / f"{k}.npy") for k in ("mu", "var", "root_mll", "leaf_mll")}
+    assert d["root_mll"][0] == j["root_mll"] and d["mu"].shape == d["var"].shape == (2000,) and np.all(d["var"] > 0)

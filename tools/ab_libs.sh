@@ -19,11 +19,11 @@ for round in $(seq 1 ${ROUNDS:-2}); do
     cp "$lib" /tmp/lib_cur.so && cp /tmp/lib_cur.so $pk/libdsmgp_hip.so
     for w in $WHAT; do
       case $w in
-        h) python bench.py --steps 3 --warmup 2 --no-cpu-baseline $xa > $o/h_${tag}_$round.json 2> $o/err.txt; line $o/h_${tag}_$round.json "$tag headline";;
-        s8) for sh in 0/8 5/8; do python bench.py --steps 3 --warmup 2 --no-cpu-baseline $xa --simulate-shard $sh > $o/s_${tag}_$round.json 2> $o/err.txt; line $o/s_${tag}_$round.json "$tag shard $sh"; done;;
-        s4) python bench.py --steps 3 --warmup 2 --no-cpu-baseline $xa --simulate-shard 0/4 > $o/s_${tag}_$round.json 2> $o/err.txt; line $o/s_${tag}_$round.json "$tag shard 0/4";;
-        d4) python bench.py --config dsmgp_n100k_d8_depth4 --steps 3 --warmup 2 --no-cpu-baseline $xa > $o/d4_${tag}_$round.json 2> $o/err.txt; line $o/d4_${tag}_$round.json "$tag depth4";;
-        d3) python bench.py --config dsmgp_n100k_d8_depth3 --steps 3 --warmup 2 --no-cpu-baseline $xa > $o/d3_${tag}_$round.json 2> $o/err.txt; line $o/d3_${tag}_$round.json "$tag depth3";;
+        h) python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline $xa > $o/h_${tag}_$round.json 2> $o/err.txt; line $o/h_${tag}_$round.json "$tag headline";;
+        s8) for sh in 0/8 5/8; do python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline $xa --simulate-shard $sh > $o/s_${tag}_$round.json 2> $o/err.txt; line $o/s_${tag}_$round.json "$tag shard $sh"; done;;
+        s4) python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline $xa --simulate-shard 0/4 > $o/s_${tag}_$round.json 2> $o/err.txt; line $o/s_${tag}_$round.json "$tag shard 0/4";;
+        d4) python bench.py --full --config dsmgp_n100k_d8_depth4 --steps 3 --warmup 2 --no-cpu-baseline $xa > $o/d4_${tag}_$round.json 2> $o/err.txt; line $o/d4_${tag}_$round.json "$tag depth4";;
+        d3) python bench.py --full --config dsmgp_n100k_d8_depth3 --steps 3 --warmup 2 --no-cpu-baseline $xa > $o/d3_${tag}_$round.json 2> $o/err.txt; line $o/d3_${tag}_$round.json "$tag depth3";;
         tr) python bench.py --mode train --steps 2 --warmup 1 $xa > $o/tr_${tag}_$round.json 2> $o/err.txt; line $o/tr_${tag}_$round.json "$tag train";;
         c23) DSMGP_RUN_ARGS="$xa" python tools/run_config3.py 2>&1 | sed "s/^/$tag /";;
       esac

@@ -11,9 +11,10 @@ o=gpurun_out/ab_rounds; mkdir -p $o
 for r in $(seq 1 $rounds); do
   for tree in "$old" .; do
     tag=$(basename "$tree"); [ "$tree" = . ] && tag=current
-    python $tree/bench.py --steps 3 --warmup 2 --no-cpu-baseline > $o/h_$tag.json 2> $o/err.txt; line $o/h_$tag.json "$tag headline"
-    python $tree/bench.py --config dsmgp_n100k_d8_depth4 --steps 5 --warmup 2 --no-cpu-baseline > $o/d4_$tag.json 2> $o/err.txt; line $o/d4_$tag.json "$tag depth4"
-    for sh in 0/8 5/8; do python $tree/bench.py --steps 3 --warmup 2 --no-cpu-baseline --simulate-shard $sh > $o/s_$tag.json 2> $o/err.txt; line $o/s_$tag.json "$tag shard $sh"; done
+    full=""; grep -q -e '"--full"' $tree/bench.py && full=--full     # a tree from before --full prints the per-category split by default
+    python $tree/bench.py $full --steps 3 --warmup 2 --no-cpu-baseline > $o/h_$tag.json 2> $o/err.txt; line $o/h_$tag.json "$tag headline"
+    python $tree/bench.py $full --config dsmgp_n100k_d8_depth4 --steps 5 --warmup 2 --no-cpu-baseline > $o/d4_$tag.json 2> $o/err.txt; line $o/d4_$tag.json "$tag depth4"
+    for sh in 0/8 5/8; do python $tree/bench.py $full --steps 3 --warmup 2 --no-cpu-baseline --simulate-shard $sh > $o/s_$tag.json 2> $o/err.txt; line $o/s_$tag.json "$tag shard $sh"; done
     (cd $tree && python tools/run_config3.py 2>&1 | grep "^config" | sed "s/^/$tag /")
   done
 done

@@ -3,7 +3,7 @@ each fused launch carries (where are the small-leaf kernels below
 
     python tools/fit_timeline.py gpurun_out/prof_round/depth4_stats r06          -> profiles/r06_bench_depth4_fit_timeline.json
 
-The fit taken is a ONE-lane fit of the run (bench.py's `single_lane` extra: launches named tile_fused8_kernel<2>, one stream), whose
+The fit taken is a ONE-lane fit of the run (the `single_lane` extra of bench.py --full: launches named tile_fused8_kernel<2>, one stream), whose
 launches do not overlap: per launch {kernel, workgroups, start, duration}, and per fit {span, union of all launches, gap = span - union}.
 Two-lane fits of the same trace are summarised beside it (span, union, sums per kernel).
 

@@ -24,8 +24,8 @@ run() {   # run <name> <bench args...>: the three PMC passes FIRST; for the head
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/${name}_stats -- python3 bench.py "$@" > $out/${name}_stats/bench.log 2>&1
   echo "$name stats done"
 }
-run n100k --steps 2 --warmup 2 --no-cpu-baseline --no-other-configs
-run depth4 --config dsmgp_n100k_d8_depth4 --steps 2 --warmup 2 --no-cpu-baseline
+run n100k --full --steps 2 --warmup 2 --no-cpu-baseline --no-other-configs
+run depth4 --full --config dsmgp_n100k_d8_depth4 --steps 2 --warmup 2 --no-cpu-baseline
 run train --mode train --steps 2 --warmup 1
 # BASELINE configs 2 and 3 (tools/run_config3.py: single GP n = 4096, then the PoE of 128 ArdSE experts): kernel stats, the SQ / GRBM
 # pass, and the vector-instruction counters that say whether the ArdSE kernel function (8 exp per entry) is what its launches do
