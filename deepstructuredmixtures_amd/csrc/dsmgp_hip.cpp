@@ -612,7 +612,8 @@ struct dsmgp_ctx {
     DevBuf<FrobTask> gfrob;
     std::vector<int> gfrob_leaf;    // owner leaf of each frob task
     DevBuf<GradTask> gdot;
-    size_t gdot_prod0 = 0;          // first task of an ArdSEProduct leaf in gdot (they form its tail)
+    size_t gdot_prod0 = 0;          // first task of an ArdSEProduct leaf in gdot (they and the Matern leaves form its tail)
+    size_t gdot_mat0 = 0;           // first task of a Matern leaf in gdot (the end of the list)
     std::vector<int> gdot_leaf;     // leaf of each graddot task
     DevBuf<ArdLinTask> gardlin;     // ArdLinear leaves: column groups of L^-T (ardlin_quad_kernel)
     std::vector<int> gardlin_leaf;  // leaf of each of them
@@ -965,6 +966,19 @@ inline int tile_mrows(int valid) {
     return m >= TB ? 0 : std::max(16, m);
 }
 
+inline bool is_matern(int kind) { return kind >= DSMGP_KIND_ISO_MATERN32 && kind <= DSMGP_KIND_ARD_MATERN52; }
+inline bool is_iso_matern(int kind) { return kind == DSMGP_KIND_ISO_MATERN32 || kind == DSMGP_KIND_ISO_MATERN52; }
+// some kernel id has a Matern kind: the fused steps launch diag_fused_reg_matern_kernel as well
+inline bool any_matern(const dsmgp_ctx* c) {
+    for (const HyperHost& h : c->hyper)
+        if (is_matern(h.kind)) return true;
+    return false;
+}
+// 2 nu of a Matern kind
+inline double matern_2nu(int kind) {
+    return (kind == DSMGP_KIND_ISO_MATERN32 || kind == DSMGP_KIND_ARD_MATERN32) ? 3.0 : 5.0;
+}
+
 // Upload the KParam table from the host hyper-parameters.
 int upload_hyper(dsmgp_ctx* c) {
     const int nk = (int)c->hyper.size();
@@ -984,6 +998,9 @@ int upload_hyper(dsmgp_ctx* c) {
             const double l = std::exp(h.loghyp[i]);
             l2pool.push_back(l * l);
         }
+        // an iso Matern id reads D per-dimension factors like its ARD kind: D slots of its one length-scale
+        if (is_iso_matern(h.kind))
+            for (int i = 1; i < c->D; ++i) l2pool.push_back(l2pool[off[k]]);
         kp[k].kind = h.kind;
         kp[k].nl = nl;
         const double logs = h.loghyp[nl];
@@ -994,12 +1011,16 @@ int upload_hyper(dsmgp_ctx* c) {
         kp[k].noise = std::exp(2.0 * logn);
     }
     const size_t nslots = l2pool.size();
-    // second half (KParam.nh): the per-dimension factor -- of the exponent, -0.5 / l^2, or of ArdLinear's product, 1 / l_d^2
-    std::vector<char> slot_ard_linear(nslots, 0);
-    for (int k = 0; k < nk; ++k)
-        if (c->hyper[k].kind == DSMGP_KIND_ARD_LINEAR)
-            for (size_t i = off[k]; i < off[k] + c->hyper[k].loghyp.size() - 2; ++i) slot_ard_linear[i] = 1;
-    for (size_t i = 0; i < nslots; ++i) l2pool.push_back(slot_ard_linear[i] ? 1.0 / l2pool[i] : -0.5 / l2pool[i]);
+    // second half (KParam.nh): the per-dimension factor -- of the exponent, -0.5 / l^2, of ArdLinear's product, 1 / l_d^2, or
+    // of a Matern kernel's s^2, 2 nu / l_d^2
+    std::vector<double> slot_num(nslots, -0.5);
+    for (int k = 0; k < nk; ++k) {
+        const int kind = c->hyper[k].kind;
+        if (kind != DSMGP_KIND_ARD_LINEAR && !is_matern(kind)) continue;
+        const size_t ns = is_iso_matern(kind) ? (size_t)std::max(1, c->D) : c->hyper[k].loghyp.size() - 2;
+        for (size_t i = off[k]; i < off[k] + ns; ++i) slot_num[i] = kind == DSMGP_KIND_ARD_LINEAR ? 1.0 : matern_2nu(kind);
+    }
+    for (size_t i = 0; i < nslots; ++i) l2pool.push_back(slot_num[i] / l2pool[i]);
     if (l2pool.size() > c->d_l2.cap || !c->d_l2.p) {   // (re)allocate only when the table grows: fit is called in loops
         drop_graphs(c);
         if (int rc = c->d_l2.grow(c, l2pool.size(), std::max<size_t>(16, 2 * l2pool.size()))) return rc;
@@ -1022,10 +1043,12 @@ int upload_hyper(dsmgp_ctx* c) {
     return 0;
 }
 
-// an ArdLinear or ArdSEProduct kernel id reads D per-dimension factors wherever its kernel function is evaluated
+// an ArdLinear, ArdSEProduct or ARD Matern kernel id reads D per-dimension factors wherever its kernel function is evaluated
 bool ard_linear_short(const dsmgp_ctx* c, int kid) {
     const HyperHost& h = c->hyper[kid];
-    return (h.kind == DSMGP_KIND_ARD_LINEAR || h.kind == DSMGP_KIND_ARD_SE_PRODUCT) && (int)h.loghyp.size() - 2 != c->D;
+    return (h.kind == DSMGP_KIND_ARD_LINEAR || h.kind == DSMGP_KIND_ARD_SE_PRODUCT || h.kind == DSMGP_KIND_ARD_MATERN32 ||
+            h.kind == DSMGP_KIND_ARD_MATERN52) &&
+           (int)h.loghyp.size() - 2 != c->D;
 }
 
 const char* kind_name(int kind) {
@@ -1034,6 +1057,10 @@ const char* kind_name(int kind) {
         case DSMGP_KIND_ARD_SE: return "ArdSE";
         case DSMGP_KIND_ISO_LINEAR: return "IsoLinear";
         case DSMGP_KIND_ARD_LINEAR: return "ArdLinear";
+        case DSMGP_KIND_ISO_MATERN32: return "IsoMatern32";
+        case DSMGP_KIND_ISO_MATERN52: return "IsoMatern52";
+        case DSMGP_KIND_ARD_MATERN32: return "ArdMatern32";
+        case DSMGP_KIND_ARD_MATERN52: return "ArdMatern52";
         default: return "ArdSEProduct";
     }
 }
@@ -1046,7 +1073,8 @@ int check_hyper(dsmgp_ctx* c) {
                                               " without hyper-parameters");
         const HyperHost& h = c->hyper[kid];
         const int nl = (int)h.loghyp.size() - 2;
-        const bool ard = h.kind == DSMGP_KIND_ARD_SE || h.kind == DSMGP_KIND_ARD_LINEAR || h.kind == DSMGP_KIND_ARD_SE_PRODUCT;
+        const bool ard = h.kind == DSMGP_KIND_ARD_SE || h.kind == DSMGP_KIND_ARD_LINEAR || h.kind == DSMGP_KIND_ARD_SE_PRODUCT ||
+                         h.kind == DSMGP_KIND_ARD_MATERN32 || h.kind == DSMGP_KIND_ARD_MATERN52;
         if (ard && nl != c->D)
             return fail(c, DSMGP_E_ARG, std::string(kind_name(h.kind)) + " needs one lengthscale per input dimension");
         if (!ard && nl != 1) return fail(c, DSMGP_E_ARG, "Iso kernels take one lengthscale");
@@ -1987,6 +2015,9 @@ void run_step(dsmgp_ctx* c, StepLists& S, int k, PhaseTimer& pt, hipStream_t st,
         if (nfd > 0) {
             pt.begin(2, st);
             diag_fused_reg_kernel<<<nfd, 256, DIAGR_LDS_BYTES, st>>>(S.fdiag.p + S.fdiag_off[k], c->d_kp.p, c->D);
+            // Matern leaves: their diagonal blocks in a launch of their own over the same list (each kernel skips the other's)
+            if (any_matern(c))
+                diag_fused_reg_matern_kernel<<<nfd, 256, DIAGR_LDS_BYTES, st>>>(S.fdiag.p + S.fdiag_off[k], c->d_kp.p, c->D);
             pt.note(k, nfd, 0);
             pt.end(st);
         }
@@ -2359,15 +2390,20 @@ int dsmgp_set_sharing(dsmgp_ctx* c, const int32_t* op, const int32_t* src, const
 int dsmgp_set_hyper(dsmgp_ctx* c, int32_t kernel_id, int32_t kind, const double* loghyp, int32_t n) {
     if (!c) return DSMGP_E_ARG;
     if (kernel_id < 0 || kernel_id >= DSMGP_MAX_KERNEL_IDS || !loghyp || n < 3) return fail(c, DSMGP_E_ARG, "set_hyper: bad arguments");
-    if (kind < 0 || kind > DSMGP_KIND_ARD_SE_PRODUCT) return fail(c, DSMGP_E_ARG, "set_hyper: unknown kernel kind");
-    if (kind == DSMGP_KIND_ARD_SE_PRODUCT && c->D > 0 && n != c->D + 2)
-        return fail(c, DSMGP_E_ARG, "set_hyper: ArdSEProduct needs one lengthscale per input dimension");
+    if (kind < 0 || kind > DSMGP_KIND_ARD_MATERN52) return fail(c, DSMGP_E_ARG, "set_hyper: unknown kernel kind");
+    if ((kind == DSMGP_KIND_ARD_SE_PRODUCT || kind == DSMGP_KIND_ARD_MATERN32 || kind == DSMGP_KIND_ARD_MATERN52) && c->D > 0 &&
+        n != c->D + 2)
+        return fail(c, DSMGP_E_ARG, std::string("set_hyper: ") + kind_name(kind) + " needs one lengthscale per input dimension");
+    if (is_iso_matern(kind) && n != 3)
+        return fail(c, DSMGP_E_ARG, std::string("set_hyper: ") + kind_name(kind) + " takes [logl, logs, logNoise]");
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(loghyp[i])) return fail(c, DSMGP_E_ARG, "set_hyper: non-finite hyper-parameter");
     if ((int)c->hyper.size() <= kernel_id) c->hyper.resize(kernel_id + 1);
+    const bool had_matern = any_matern(c);
     if (c->hyper[kernel_id].kind != kind) free_grad(c);   // the contraction tiles / ArdLinear tasks depend on the kernel kind
     c->hyper[kernel_id].kind = kind;
     c->hyper[kernel_id].loghyp.assign(loghyp, loghyp + n);
+    if (any_matern(c) != had_matern) drop_graphs(c);       // a captured fit launches diag_fused_reg_matern_kernel or not
     c->fitted = false;
     c->predicted = false;
     c->vt_valid = false;
@@ -3327,7 +3363,7 @@ int build_grad_plan(dsmgp_ctx* c) {
         }
     }
 
-    // contraction tiles: every IsoSE and ArdSEProduct leaf (COPY leaves too: their alpha is their own)
+    // contraction tiles: every IsoSE, ArdSEProduct and Matern leaf (COPY leaves too: their alpha is their own)
     // Order.  A 128x128 tile task moves 2 x 128 x K operand doubles for 2 x 128^2 x K flops: 8 flop/B, below the
     // ridge of the chip unless operands are shared through L2.  Tasks that are adjacent in this list run at the same
     // time on one XCD (xcd_permute below), so the lower tiles of a leaf are listed in super-tiles of GS x GS tiles:
@@ -3337,10 +3373,12 @@ int build_grad_plan(dsmgp_ctx* c) {
     std::vector<GradTask> gd;
     std::vector<size_t> gblock;
     c->gdot_leaf.clear();
-    // The tasks of ArdSEProduct leaves form the tail of the list (pass 1), run by tile_graddot_prod_kernel.
+    // The tasks of ArdSEProduct leaves (pass 1), then those of Matern leaves (pass 2) form the tail of the list, run by
+    // tile_graddot_prod_kernel and tile_graddot_matern_kernel.
     bool any_ard = false, any_prod = false;
-    for (int pass = 0; pass < 2; ++pass) {
+    for (int pass = 0; pass < 3; ++pass) {
         if (pass == 1) c->gdot_prod0 = gd.size();
+        if (pass == 2) c->gdot_mat0 = gd.size();
         const size_t begin = gd.size();
         gblock.clear();
         for (int l = 0; l < L; ++l) {
@@ -3348,10 +3386,11 @@ int build_grad_plan(dsmgp_ctx* c) {
             const int kind_l = c->hyper[lf.kid].kind;
             const bool ard = kind_l == DSMGP_KIND_ARD_SE && c->ard_true_gradient;
             const bool prod = kind_l == DSMGP_KIND_ARD_SE_PRODUCT;
-            if (kind_l != DSMGP_KIND_ISO_SE && !ard && !prod) continue;
-            if (prod != (pass == 1)) continue;
+            const bool mat = is_matern(kind_l);
+            if (kind_l != DSMGP_KIND_ISO_SE && !ard && !prod && !mat) continue;
+            if ((prod ? 1 : mat ? 2 : 0) != pass) continue;
             any_ard = any_ard || ard;
-            any_prod = any_prod || prod;
+            any_prod = any_prod || prod || mat;
             // Shared gradients (the idea of src/fit.jl:313-395: a leaf whose observation set equals its main leaf's takes
             // that leaf's gradients, `copygradients`): a COPY leaf has its source's factor and kernel id; with the same
             // ConstMean its alpha is the source's too, so its contraction is the source's and is not computed again.
@@ -3399,7 +3438,7 @@ int build_grad_plan(dsmgp_ctx* c) {
     if (int rc = dev_upload(c, c->gdot, gd)) return rc;
     if (any_ard && c->D > GRADDOT_STAGE_D)
         return fail(c, DSMGP_E_ARG, "ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
-    c->gstride = (any_ard || any_prod) ? 2 + c->D : 2;     // ArdSEProduct: any D (staged in chunks)
+    c->gstride = (any_ard || any_prod) ? 2 + c->D : 2;     // ArdSEProduct, Matern: any D (staged in chunks)
 
     // ArdLinear leaves: ARDLIN_COLS columns of L^-T per task (a COPY leaf with its source's mean takes the source's sums,
     // as for the contraction), the tasks of the longest columns first
@@ -3495,12 +3534,16 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     double* pfrob = c->d_gpart.p;
     double* pdot = pfrob + c->gfrob.count;
     double* pleaf = pdot + (size_t)c->gstride * c->gdot.count;
-    const size_t np0 = c->gdot_prod0;     // tasks [np0, count): ArdSEProduct leaves
+    const size_t np0 = c->gdot_prod0;     // tasks [np0, nm0): ArdSEProduct leaves
+    const size_t nm0 = c->gdot_mat0;      // tasks [nm0, count): Matern leaves
     if (np0)
         tile_graddot_kernel<<<(int)np0, 256, 0, c->stream>>>(c->gdot.p, c->d_kp.p, c->D, pdot, c->gstride);
-    if (c->gdot.count > np0)
-        tile_graddot_prod_kernel<<<(int)(c->gdot.count - np0), 256, 0, c->stream>>>(c->gdot.p + np0, c->d_kp.p, c->D,
-                                                                                      pdot + (size_t)c->gstride * np0, c->gstride);
+    if (nm0 > np0)
+        tile_graddot_prod_kernel<<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->gdot.p + np0, c->d_kp.p, c->D,
+                                                                               pdot + (size_t)c->gstride * np0, c->gstride);
+    if (c->gdot.count > nm0)
+        tile_graddot_matern_kernel<<<(int)(c->gdot.count - nm0), 256, 0, c->stream>>>(c->gdot.p + nm0, c->d_kp.p, c->D,
+                                                                                         pdot + (size_t)c->gstride * nm0, c->gstride);
     HIPCHK(c, hipEventRecord(e_dot.a, c->stream));
     if (c->gfrob.count) frob_kernel<<<(int)c->gfrob.count, 256, 0, c->stream>>>(c->gfrob.p, pfrob);
     dots_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, pleaf);
@@ -3529,12 +3572,12 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
         if (c->leaves[l].owner != l) trK[l] = trK[c->leaves[l].owner];
     const double* pd = part.data() + c->gfrob.count;
     const size_t gs = (size_t)c->gstride;
-    std::vector<double> Sd;           // per leaf and dimension: contraction with dK / dlog l_d (ArdSE option, ArdSEProduct)
+    std::vector<double> Sd;           // per leaf and dimension: contraction with dK / dlog l_d (ArdSE option, ArdSEProduct, Matern)
     if (gs > 2) Sd.assign((size_t)L * c->D, 0.0);
     for (size_t i = 0; i < c->gdot.count; ++i) {
         const int l = c->gdot_leaf[i];
         const int kind_l = c->hyper[c->leaves[l].kid].kind;
-        if (kind_l == DSMGP_KIND_ARD_SE || kind_l == DSMGP_KIND_ARD_SE_PRODUCT) {
+        if (kind_l == DSMGP_KIND_ARD_SE || kind_l == DSMGP_KIND_ARD_SE_PRODUCT || is_matern(kind_l)) {
             for (int d = 0; d < c->D; ++d) Sd[(size_t)l * c->D + d] += pd[gs * i + 2 + d];
         } else {
             S1[l] += pd[gs * i];
@@ -3599,6 +3642,16 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
         } else if (h.kind == DSMGP_KIND_ARD_SE_PRODUCT) {
             // the true derivatives: 0.5 tr(W dK / dlog l_d) from the per-dimension sums, 0.5 tr(W 2K) = tr(W K) (no SURVEY F7 factor)
             for (int d = 0; d < nl; ++d) g[d] = 0.5 * Sd[(size_t)l * c->D + d];
+            g[nl] = trPK;
+        } else if (is_matern(h.kind)) {
+            // the true derivatives as for ArdSEProduct; an iso kind's dl is the sum over the dimensions, added in ascending d
+            if (is_iso_matern(h.kind)) {
+                double sl = 0.0;
+                for (int d = 0; d < c->D; ++d) sl += Sd[(size_t)l * c->D + d];
+                g[0] = 0.5 * sl;
+            } else {
+                for (int d = 0; d < nl; ++d) g[d] = 0.5 * Sd[(size_t)l * c->D + d];
+            }
             g[nl] = trPK;
         }
         g[nl + 1] = noise * (aa - trK[l]);                    // src/gaussianprocess.jl:176
@@ -3679,7 +3732,7 @@ int dsmgp_timings(dsmgp_ctx* c, double* out) {
 
 int dsmgp_work_gradients(dsmgp_ctx* c, double* alg_flops_inverse, double* alg_flops_contraction, int32_t* n_contraction_tiles) {
     if (!c) return DSMGP_E_ARG;
-    // L^-T of every factor owner: n^3/3; contraction (alpha alpha^T - K_y^-1) o K o P of every IsoSE / ArdSEProduct leaf: the lower
+    // L^-T of every factor owner: n^3/3; contraction (alpha alpha^T - K_y^-1) o K o P of every IsoSE / ArdSEProduct / Matern leaf: the lower
     // tiles of L^-T L^-1, n^3/3 again (2 x 128 x 128 x K per tile with K = n - 128 i)
     double fi = 0.0, fc = 0.0;
     for (int l = 0; l < c->L; ++l) {
@@ -3687,7 +3740,8 @@ int dsmgp_work_gradients(dsmgp_ctx* c, double* alg_flops_inverse, double* alg_fl
         const double n = (double)lf.n;
         if (lf.owner == l) fi += n * n * n / 3.0;
         if (lf.kid < (int)c->hyper.size() &&
-            (c->hyper[lf.kid].kind == DSMGP_KIND_ISO_SE || c->hyper[lf.kid].kind == DSMGP_KIND_ARD_SE_PRODUCT))
+            (c->hyper[lf.kid].kind == DSMGP_KIND_ISO_SE || c->hyper[lf.kid].kind == DSMGP_KIND_ARD_SE_PRODUCT ||
+             is_matern(c->hyper[lf.kid].kind)))
             fc += n * n * n / 3.0;
     }
     if (alg_flops_inverse) *alg_flops_inverse = fi;

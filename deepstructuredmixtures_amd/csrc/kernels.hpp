@@ -50,7 +50,8 @@ struct KParam {
     double noise;       // exp(2 logNoise)
     const double* l2;   // device: lengthscale^2 per slot
     const double* nh;   // device: the per-dimension factor of the kernel function per slot: -0.5 / lengthscale^2 (the factor of
-                        //   the exponent; IsoSE, ArdSE), 1 / lengthscale^2 (ArdLinear)
+                        //   the exponent; IsoSE, ArdSE), 1 / lengthscale^2 (ArdLinear), 2 nu / lengthscale^2 (Matern: D slots for
+                        //   the iso kinds too, all equal)
     double nh0;         // nh[0]
     double il2;         // 1 / l2[0]
 };
@@ -75,6 +76,17 @@ __device__ __forceinline__ double exp_nonpos(double x) {
     p = fma(r, p, 1.0);
     p = fma(r, p, 1.0);
     return ldexp(p, (int)n);
+}
+
+// Matern (DSMGP kinds 5-8, device KIND 5): the s^2 coefficient of the polynomial, 0 (nu = 3/2, kinds 5 and 7) or 1/3 (nu = 5/2,
+// kinds 6 and 8) -- taken from the kind, so that KParam keeps its size
+__device__ __forceinline__ double matern_c2(const KParam& p) {
+    return (p.kind == 6 || p.kind == 8) ? 1.0 / 3.0 : 0.0;
+}
+// kernel value from z = s^2 = sum_d (a_d-b_d)^2 * 2 nu / l_d^2: sigma^2 exp(-s) (1 + s + c2 s^2), with the correctly rounded sqrt
+__device__ __forceinline__ double matern_value(double z, const KParam& p) {
+    const double s = sqrt(z);
+    return p.sigma2 * exp_nonpos(-s) * fma(fma(matern_c2(p), s, 1.0), s, 1.0);
 }
 
 
@@ -104,6 +116,8 @@ struct GramTask {
 // generic ArdKernel loop of src/kernels.jl:39-49 with kappa = z / l_d^2 (:228-229): per dimension the product a_d b_d, scaled
 // by 1 / l_d^2 and added in ascending d (one fma: bit-symmetric in a and b).  ArdSEProduct (KIND 4, not a reference kernel) is
 // sigma^2 exp(z), z = sum_d (a_d-b_d)^2 * (-0.5 / l_d^2) in one fma per dimension, ascending d (bit-symmetric as well).
+// KIND 5 is every Matern kind (DSMGP kinds 5-8, not reference kernels): z = s^2 accumulated as for KIND 4 with the factors
+// 2 nu / l_d^2, then matern_value.
 template <int KIND>
 __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam& p, int D, int half,
                                                double (*sa)[TB], double (*sb)[TB / 2]) {
@@ -136,7 +150,7 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
         if (!rows_live) continue;
         for (int d = 0; d < dn; ++d) {
             const double a0 = sa[d][r0], a1 = sa[d][r0 + 1], a2 = sa[d][r0 + 2], a3 = sa[d][r0 + 3];
-            const double nhd = (KIND == 1 || KIND == 3 || KIND == 4) ? p.nh[d0 + d] : 0.0;   // -0.5 / l_d^2, resp. 1 / l_d^2
+            const double nhd = (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? p.nh[d0 + d] : 0.0;   // -0.5 / l_d^2, 1 / l_d^2, 2 nu / l_d^2
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const double b = sb[d][cb + 8 * q];
@@ -186,7 +200,8 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
             else if (KIND == 1) kv = p.sigma2 * acc[q][j];
             else if (KIND == 2) kv = acc[q][j] * il2;
             else if (KIND == 3) kv = acc[q][j];
-            else kv = p.sigma2 * exp_nonpos(acc[q][j]);
+            else if (KIND == 4) kv = p.sigma2 * exp_nonpos(acc[q][j]);
+            else kv = matern_value(acc[q][j], p);
             const bool valid = (r < tk.na) && (c < tk.nb);
             if (!valid) kv = 0.0;
             if (tk.sym && tk.diag && r == c) kv = valid ? kv + (p.noise + 1e-8) : 1.0;
@@ -208,6 +223,7 @@ __global__ __launch_bounds__(256) void gram_tile_kernel(const GramTask* __restri
     else if (p.kind == 2) gram_half_tile<2>(tk, p, D, half, sa, sb);
     else if (p.kind == 3) gram_half_tile<3>(tk, p, D, half, sa, sb);
     else if (p.kind == 4) gram_half_tile<4>(tk, p, D, half, sa, sb);
+    else if (p.kind >= 5) gram_half_tile<5>(tk, p, D, half, sa, sb);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -328,7 +344,7 @@ __device__ __forceinline__ void gram_accumulate(double (&z)[NA][NB], const doubl
                 z[i][j] = fma(a[i], b[j], z[i][j]);
             } else if (KIND == 3) {
                 z[i][j] = fma(a[i] * b[j], nhd, z[i][j]);
-            } else {
+            } else {    // KIND 4, 5
                 const double u = a[i] - b[j];
                 z[i][j] = fma(u * u, nhd, z[i][j]);
             }
@@ -344,7 +360,8 @@ __device__ __forceinline__ double gram_finish(double z, const KParam& p, int row
     else if (KIND == 1) kv = p.sigma2 * z;
     else if (KIND == 2) kv = z * p.il2;
     else if (KIND == 3) kv = z;
-    else kv = p.sigma2 * exp_nonpos(z);
+    else if (KIND == 4) kv = p.sigma2 * exp_nonpos(z);
+    else kv = matern_value(z, p);
     if (!EDGE) return kv;
     const bool valid = (row < na) && (col < nb);
     if (!valid) kv = 0.0;
@@ -379,7 +396,7 @@ __device__ __forceinline__ void gram_tile_epilogue(const TileTask& tk, const KPa
                 a[i] = pa[d * TB + 16 * i];
                 b[i] = pb[d * TB + 4 * i];
             }
-            gram_accumulate<KIND, 4, 4>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4) ? p.nh[d] : 0.0);
+            gram_accumulate<KIND, 4, 4>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? p.nh[d] : 0.0);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -417,6 +434,9 @@ __device__ __forceinline__ void tile_epilogue(const TileTask& tk, d4 (&acc)[4][4
         } else if (p.kind == 4) {
             if (edge) gram_tile_epilogue<4, true>(tk, p, D, acc, red, sb);
             else gram_tile_epilogue<4, false>(tk, p, D, acc, red, sb);
+        } else if (p.kind >= 5) {
+            if (edge) gram_tile_epilogue<5, true>(tk, p, D, acc, red, sb);
+            else gram_tile_epilogue<5, false>(tk, p, D, acc, red, sb);
         }
         return;
     }
@@ -832,7 +852,7 @@ __device__ __forceinline__ void syrk_gram_epilogue(const TileTask& tk, const KPa
 #pragma unroll
             for (int r = 0; r < 4; ++r) z[j][0][r] = 0.0;
         for (int d = 0; d < D; ++d) {
-            const double nhd = (KIND == 1 || KIND == 3 || KIND == 4) ? p.nh[d] : 0.0;
+            const double nhd = (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? p.nh[d] : 0.0;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 double a[1], b[4];
@@ -865,6 +885,7 @@ __device__ __forceinline__ void syrk_finish(const TileTask& tk, d4 (&acc)[9], co
         else if (p.kind == 2) syrk_gram_epilogue<SHAPE, 2>(tk, p, D, acc, blk, sa);
         else if (p.kind == 3) syrk_gram_epilogue<SHAPE, 3>(tk, p, D, acc, blk, sa);
         else if (p.kind == 4) syrk_gram_epilogue<SHAPE, 4>(tk, p, D, acc, blk, sa);
+        else if (p.kind >= 5) syrk_gram_epilogue<SHAPE, 5>(tk, p, D, acc, blk, sa);
     } else {
         syrk_epilogue<SHAPE>(tk, acc, blk);
     }
@@ -1032,7 +1053,7 @@ __device__ __forceinline__ void rows_gram_epilogue(const TileTask& tk, const KPa
             for (int i = 0; i < NR; ++i) a[i] = pa[d * TB + 16 * i];
 #pragma unroll
             for (int i = 0; i < 4; ++i) b[i] = pb[d * TB + 4 * i];
-            gram_accumulate<KIND, NR, 4>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4) ? p.nh[d] : 0.0);
+            gram_accumulate<KIND, NR, 4>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? p.nh[d] : 0.0);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1067,6 +1088,7 @@ __device__ __forceinline__ void tile_rows_body(const TileTask& tk, double (*sA)[
         else if (p.kind == 2) rows_gram_epilogue<NR, 2>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
         else if (p.kind == 3) rows_gram_epilogue<NR, 3>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
         else if (p.kind == 4) rows_gram_epilogue<NR, 4>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
+        else if (p.kind >= 5) rows_gram_epilogue<NR, 5>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -1246,7 +1268,7 @@ constexpr int GRADDOT_STAGE_D = 35;
 // ostride = doubles per task in `out`: 2, or 2 + D when the per-dimension sums of the additive ArdSE kernel are
 // asked for (dsmgp_set_option DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT): out[2 + d] = sum_rc (alpha_r alpha_c - G_rc) *
 // sigma^2 exp(-u_d^2 / 2 l_d^2) * u_d^2 / l_d^2, u_d = x_rd - x_cd -- the contraction with dK / dlog l_d.  2 + D too when an
-// ArdSEProduct leaf has tasks: out[2 + d] = sum_rc (alpha_r alpha_c - G_rc) K_rc u_d^2 / l_d^2, its dK / dlog l_d.
+// ArdSEProduct or Matern leaf has tasks: out[2 + d] = sum_rc (alpha_r alpha_c - G_rc) dK_rc / dlog l_d.
 __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __restrict__ tasks,
                                                               const KParam* __restrict__ kp, int D,
                                                               double* __restrict__ out, int ostride) {
@@ -1495,6 +1517,126 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTas
             if (t == 0)   // u^2 / l_d^2 = -2 nh_d u^2
                 out[(size_t)ostride * blockIdx.x + 2 + d0 + d] =
                     wgt * (-2.0 * p.nh[d0 + d]) * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+        }
+    }
+    __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) tr += __shfl_down(tr, o);
+    if (lane == 0) red[1][w] = tr;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[(size_t)ostride * blockIdx.x] = 0.0;
+        out[(size_t)ostride * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    }
+}
+
+// Matern leaves (DSMGP kinds 5-8), any D: tile_graddot_prod_kernel with z = s^2 (factors nh_d = 2 nu / l_d^2), the per-entry
+// weight sigma^2 exp(-s) c(s), c(s) = 1 (nu = 3/2) or (1 + s) / 3 (nu = 5/2), and the per-dimension factor nh_d: dK / dlog l_d =
+// sigma^2 exp(-s) c(s) u_d^2 nh_d, finite at s = 0.  Launched over the last part of the tail.  A copy, not a template of that
+// kernel: as a template instantiation, or with the body shared through a template <bool> device function, the ArdSEProduct
+// kernel went from 240 VGPRs to 256 and 684 bytes of scratch per lane.
+__global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradTask* __restrict__ tasks,
+                                                                     const KParam* __restrict__ kp, int D,
+                                                                     double* __restrict__ out, int ostride) {
+    __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
+    __shared__ double red[2][4];
+    static_assert((GRADDOT_STAGE_D + 1) * 256 <= 2 * NRING * KC2 * LDP, "a chunk of coordinates and the alphas fit the ring");
+    double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
+    double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
+    const GradTask g = tasks[blockIdx.x];
+    const KParam p = kp[g.kid];
+    d4 acc[4][4];
+    gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);      // ends on a barrier: the ring is free
+    const int t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+    double tr = 0.0;
+    constexpr int CH = GRADDOT_STAGE_D;
+    double* xs = smem;
+    double* al = smem + (size_t)CH * 256;
+    const int nch = (D + CH - 1) / CH;
+    const double wgt = g.diag ? 1.0 : 2.0;
+    // c(s) = c1 + c2 s: (1, 0) for nu = 3/2, (1/3, 1/3) for nu = 5/2
+    const double c2 = matern_c2(p);
+    const double c1 = (c2 != 0.0) ? c2 : 1.0;
+#pragma unroll
+    for (int rn = 0; rn < 4; ++rn) {
+        const int r = wr * 64 + 16 * rn + l15;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+            if (g.diag && r == c && r < g.na) tr += acc[i >> 2][rn][i & 3];
+        }
+    }
+    al[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[t - TB] : 0.0);
+#pragma unroll
+    for (int rn = 0; rn < 4; ++rn) {
+        const int r = wr * 64 + 16 * rn + l15;
+        const bool rv = r < g.na;
+        double z[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) z[i] = 0.0;
+        for (int ch = 0; ch < nch; ++ch) {
+            const int d0 = ch * CH, dn = min(CH, D - d0);
+            if (nch > 1 || rn == 0) {
+                __syncthreads();
+                for (int e = t; e < dn * 256; e += 256) {
+                    const int d = e >> 8, rc = e & 255;
+                    xs[e] = (rc < TB) ? ((rc < g.na) ? g.xa[rc + (size_t)(d0 + d) * g.ldx] : 0.0)
+                                      : ((rc - TB < g.nb) ? g.xb[rc - TB + (size_t)(d0 + d) * g.ldx] : 0.0);
+                }
+                __syncthreads();
+            }
+            for (int d = 0; d < dn; ++d) {
+                const double nhd = p.nh[d0 + d];
+                const double a = xs[d * 256 + r];
+                const double* xb = xs + d * 256 + TB + wc * 64 + l4;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const double u = a - xb[16 * (i >> 2) + 4 * (i & 3)];
+                    z[i] = fma(u * u, nhd, z[i]);
+                }
+            }
+        }
+        const double ar = al[r];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+            const double pre = ar * al[TB + c] - acc[i >> 2][rn][i & 3];
+            const double s = sqrt(z[i]);
+            const double wk = p.sigma2 * exp_nonpos(-s) * fma(c2, s, c1);
+            acc[i >> 2][rn][i & 3] = (rv && c < g.nb) ? pre * wk : 0.0;
+        }
+    }
+    for (int ch = 0; ch < nch; ++ch) {
+        const int d0 = ch * CH, dn = min(CH, D - d0);
+        if (nch > 1) {
+            __syncthreads();
+            for (int e = t; e < dn * 256; e += 256) {
+                const int d = e >> 8, rc = e & 255;
+                xs[e] = (rc < TB) ? ((rc < g.na) ? g.xa[rc + (size_t)(d0 + d) * g.ldx] : 0.0)
+                                  : ((rc - TB < g.nb) ? g.xb[rc - TB + (size_t)(d0 + d) * g.ldx] : 0.0);
+            }
+            __syncthreads();
+        }
+        for (int d = 0; d < dn; ++d) {
+            double sd = 0.0;
+#pragma unroll
+            for (int rn = 0; rn < 4; ++rn) {
+                const double a = xs[d * 256 + wr * 64 + 16 * rn + l15];
+                const double* xb = xs + d * 256 + TB + wc * 64 + l4;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const double u = a - xb[16 * (i >> 2) + 4 * (i & 3)];
+                    sd = fma(acc[i >> 2][rn][i & 3], u * u, sd);
+                }
+            }
+            for (int o = 32; o > 0; o >>= 1) sd += __shfl_down(sd, o);
+            __syncthreads();
+            if (lane == 0) red[0][w] = sd;
+            __syncthreads();
+            if (t == 0)   // s_d^2 = nh_d u^2
+                out[(size_t)ostride * blockIdx.x + 2 + d0 + d] =
+                    wgt * p.nh[d0 + d] * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
         }
     }
     __syncthreads();
@@ -2516,7 +2658,7 @@ __global__ __launch_bounds__(128) void pred_finish_kernel(const LeafDev* __restr
     const int r = tk.row0 + threadIdx.x;
     if (r >= lf.nt) return;
     double kss;
-    if (p.kind == 0 || p.kind == 4) kss = p.sigma2;
+    if (p.kind == 0 || p.kind >= 4) kss = p.sigma2;      // IsoSE, ArdSEProduct, Matern: k(x, x) = sigma^2
     else if (p.kind == 1) kss = p.sigma2 * (double)D;
     else if (p.kind == 2) {
         double q = 0.0;
@@ -2554,7 +2696,7 @@ __global__ __launch_bounds__(256) void pred_var_kernel(const LeafDev* __restrict
     block_reduce_store(s, red, t);
     if (t < TB && tk.row0 + t < lf.nt) {
         double kss;
-        if (p.kind == 0 || p.kind == 4) kss = p.sigma2;      // IsoSE, ArdSEProduct: k(x, x) = sigma^2
+        if (p.kind == 0 || p.kind >= 4) kss = p.sigma2;      // IsoSE, ArdSEProduct, Matern: k(x, x) = sigma^2
         else if (p.kind == 1) kss = p.sigma2 * (double)D;
         else if (p.kind == 2) {
             double q = 0.0;
@@ -2753,7 +2895,7 @@ __global__ __launch_bounds__(256) void agg_finish_kernel(const double* __restric
     } else if (family == AGG_RBCM) {
         const KParam p = kp[prior_kid];
         double kss;
-        if (p.kind == 0 || p.kind == 4) kss = p.sigma2;      // IsoSE, ArdSEProduct: k(x, x) = sigma^2
+        if (p.kind == 0 || p.kind >= 4) kss = p.sigma2;      // IsoSE, ArdSEProduct, Matern: k(x, x) = sigma^2
         else if (p.kind == 1) kss = p.sigma2 * (double)D;
         else if (p.kind == 2) {
             double q = 0.0;

@@ -123,7 +123,7 @@ __device__ __forceinline__ void rowsplit_gram_init(int gna, int gnb, const KPara
             for (int i = 0; i < NRW; ++i) a[i] = pa[d * TB + 16 * i];
 #pragma unroll
             for (int j = 0; j < NJ; ++j) b[j] = pb[d * TB + 16 * (j >> 2) + 4 * (j & 3)];
-            gram_accumulate<KIND, NRW, NJ>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4) ? AS_CONST_F64(p.nh)[d] : 0.0);
+            gram_accumulate<KIND, NRW, NJ>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? AS_CONST_F64(p.nh)[d] : 0.0);
         }
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -248,12 +248,14 @@ __device__ __forceinline__ void tile_fused8_body(const FusedTask8* __restrict__ 
                 else if (p.kind == 2) rowsplit_gram_init<2, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 3) rowsplit_gram_init<3, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 4) rowsplit_gram_init<4, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
+                else if (p.kind >= 5) rowsplit_gram_init<5, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
             } else {
                 if (p.kind == 0) rowsplit_gram_init<0, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 1) rowsplit_gram_init<1, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 2) rowsplit_gram_init<2, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 3) rowsplit_gram_init<3, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
                 else if (p.kind == 4) rowsplit_gram_init<4, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
+                else if (p.kind >= 5) rowsplit_gram_init<5, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
             }
         }
         __syncthreads();    // the coordinates are no longer read: the ring takes the operand chunks
@@ -538,24 +540,26 @@ __device__ __forceinline__ void syrk_gram_inplace(const TileTask& tk, const KPar
         cbk[i] = (SHAPE == 0) ? blk[3 + j] : blk[2 * g3 + (j > 1 ? 1 : 0)];
     }
     if constexpr (KIND != 0) {
-        // ArdSE / IsoLinear / ArdLinear / ArdSEProduct: one block, two of its entries at a time (the exp per dimension of the additive kernel and the
-        // unrolled dot product each wanted one register more than the task has at four)
+        // ArdSE / IsoLinear / ArdLinear / ArdSEProduct: one block, two of its entries at a time (the exp per dimension of the
+        // additive kernel and the unrolled dot product each wanted one register more than the task has at four); Matern: one
+        // entry at a time (a sqrt and an exp per entry)
+        constexpr int NE = (KIND == 5) ? 1 : 2;
 #pragma unroll
         for (int i = 0; i < 9; ++i)
 #pragma unroll
-            for (int r0 = 0; r0 < 4; r0 += 2) {
-                double z[1][2] = {{0.0, 0.0}};
+            for (int r0 = 0; r0 < 4; r0 += NE) {
+                double z[1][NE] = {};
 #pragma unroll 1
                 for (int d = 0; d < D; ++d) {
-                    const double nhd = (KIND == 1 || KIND == 3 || KIND == 4) ? AS_CONST_F64(p.nh)[d] : 0.0;
-                    double a[1], b[2];
+                    const double nhd = (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? AS_CONST_F64(p.nh)[d] : 0.0;
+                    double a[1], b[NE];
                     a[0] = sa[d * TB + 16 * rbk[i] + l15];
 #pragma unroll
-                    for (int r = 0; r < 2; ++r) b[r] = sa[d * TB + 16 * cbk[i] + l4 + 4 * (r0 + r)];
-                    gram_accumulate<KIND, 1, 2>(z, a, b, nhd);
+                    for (int r = 0; r < NE; ++r) b[r] = sa[d * TB + 16 * cbk[i] + l4 + 4 * (r0 + r)];
+                    gram_accumulate<KIND, 1, NE>(z, a, b, nhd);
                 }
 #pragma unroll
-                for (int r = 0; r < 2; ++r) {
+                for (int r = 0; r < NE; ++r) {
                     const int row = 16 * rbk[i] + l15, col = 16 * cbk[i] + l4 + 4 * (r0 + r);
                     const double kv = gram_finish<KIND>(z[0][r], p, row, col, tk.gna, tk.gnb, true);
                     acc[i][r0 + r] = kv - acc[i][r0 + r];
@@ -845,7 +849,9 @@ __device__ __forceinline__ void diag_reg_body(const DiagTask& tk, d4 (&acc)[9], 
     }
 }
 
-template <int W>
+// MATERN: the diagonal blocks of Matern leaves (DSMGP kinds 5-8), in a launch of their own (diag_fused_reg_matern_kernel).  As a
+// sixth arm of the other kinds' kernel the sqrt + exp epilogue cost diag_fused_reg_kernel 104 bytes of scratch per lane.
+template <int W, bool MATERN>
 __device__ __forceinline__ void diag_fused_reg(const TileTask& tt, const DiagTask& d, const KParam* __restrict__ kp, int D, double* S) {
     constexpr int SHAPE = W == 3 ? 1 : 0;
     constexpr int rbase = (W == 2) ? 2 : 5, cbase = (W == 1) ? 3 : 0;
@@ -862,7 +868,8 @@ __device__ __forceinline__ void diag_fused_reg(const TileTask& tt, const DiagTas
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 acc[i][r] = (diagr_rb(W, i) == diagr_cb(W, i) && (int)(threadIdx.x & 15) == (int)((threadIdx.x & 63) >> 4) + 4 * r) ? 4.0 : 0.0;
-    } else if (p.kind == 0) syrk_gram_inplace<SHAPE, 0>(tt, p, D, acc, blk, S);
+    } else if constexpr (MATERN) syrk_gram_inplace<SHAPE, 5>(tt, p, D, acc, blk, S);
+    else if (p.kind == 0) syrk_gram_inplace<SHAPE, 0>(tt, p, D, acc, blk, S);
     else if (p.kind == 1) syrk_gram_inplace<SHAPE, 1>(tt, p, D, acc, blk, S);
     else if (p.kind == 2) syrk_gram_inplace<SHAPE, 2>(tt, p, D, acc, blk, S);
     else if (p.kind == 3) syrk_gram_inplace<SHAPE, 3>(tt, p, D, acc, blk, S);
@@ -871,11 +878,14 @@ __device__ __forceinline__ void diag_fused_reg(const TileTask& tt, const DiagTas
     diag_reg_body<W>(d, acc, S);
 }
 
-__global__ __launch_bounds__(256, DSMGP_DIAGR_WGS) void diag_fused_reg_kernel(const DiagFusedTask* __restrict__ tasks,
-                                                                              const KParam* __restrict__ kp, int D) {
-    extern __shared__ __attribute__((aligned(16))) double S[];   // DIAGR_LDS_BYTES: ring / coordinates / panel share the space
-    static_assert(GRAM_FUSE_MAX_D * TB * (int)sizeof(double) <= DIAGR_LDS_BYTES, "coordinates must fit");
+// One diagonal-block task of a FUSED step.  Both kernels below run over the whole diagonal-block list of the step and take the
+// tasks of their own kinds: which kinds a leaf has is read here, at the launch, from the hyper-parameters of that fit -- the task
+// lists themselves do not depend on them (they can be built before set_hyper, e.g. by set_test under a device pool).
+template <bool MATERN>
+__device__ __forceinline__ void diag_fused_task(const DiagFusedTask* __restrict__ tasks, const KParam* __restrict__ kp, int D,
+                                                double* S) {
     const DiagFusedTask ft = tasks[blockIdx.x];
+    if ((kp[ft.kid].kind >= 5) != MATERN) return;          // another kernel's task (uniform over the workgroup)
     TileTask tt{};
     tt.A = ft.A;
     tt.lda = ft.d.ld;
@@ -891,10 +901,25 @@ __global__ __launch_bounds__(256, DSMGP_DIAGR_WGS) void diag_fused_reg_kernel(co
     // workgroup, so that the chains of co-resident tasks sit on different SIMDs, measured nothing: depth 4 0.0516-0.0522 s with
     // the role shifted by blockIdx, blockIdx / 8 or blockIdx / 256 as without.)
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (w == 0) diag_fused_reg<0>(tt, ft.d, kp, D, S);
-    else if (w == 1) diag_fused_reg<1>(tt, ft.d, kp, D, S);
-    else if (w == 2) diag_fused_reg<2>(tt, ft.d, kp, D, S);
-    else diag_fused_reg<3>(tt, ft.d, kp, D, S);
+    if (w == 0) diag_fused_reg<0, MATERN>(tt, ft.d, kp, D, S);
+    else if (w == 1) diag_fused_reg<1, MATERN>(tt, ft.d, kp, D, S);
+    else if (w == 2) diag_fused_reg<2, MATERN>(tt, ft.d, kp, D, S);
+    else diag_fused_reg<3, MATERN>(tt, ft.d, kp, D, S);
+}
+
+// the diagonal blocks of IsoSE / ArdSE / IsoLinear / ArdLinear / ArdSEProduct leaves
+__global__ __launch_bounds__(256, DSMGP_DIAGR_WGS) void diag_fused_reg_kernel(const DiagFusedTask* __restrict__ tasks,
+                                                                              const KParam* __restrict__ kp, int D) {
+    extern __shared__ __attribute__((aligned(16))) double S[];   // DIAGR_LDS_BYTES: ring / coordinates / panel share the space
+    static_assert(GRAM_FUSE_MAX_D * TB * (int)sizeof(double) <= DIAGR_LDS_BYTES, "coordinates must fit");
+    diag_fused_task<false>(tasks, kp, D, S);
+}
+
+// the diagonal blocks of Matern leaves (launched only while a kernel id has a Matern kind)
+__global__ __launch_bounds__(256, DSMGP_DIAGR_WGS) void diag_fused_reg_matern_kernel(const DiagFusedTask* __restrict__ tasks,
+                                                                                     const KParam* __restrict__ kp, int D) {
+    extern __shared__ __attribute__((aligned(16))) double S[];
+    diag_fused_task<true>(tasks, kp, D, S);
 }
 
 // ---------------------------------------------------------------------------------------------

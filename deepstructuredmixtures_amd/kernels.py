@@ -16,6 +16,10 @@ KIND_ARD_SE = 1
 KIND_ISO_LINEAR = 2
 KIND_ARD_LINEAR = 3
 KIND_ARD_SE_PRODUCT = 4
+KIND_ISO_MATERN32 = 5
+KIND_ISO_MATERN52 = 6
+KIND_ARD_MATERN32 = 7
+KIND_ARD_MATERN52 = 8
 
 
 class KernelFunction:
@@ -152,6 +156,75 @@ class ArdSEProduct(KernelFunction):
 
     def __repr__(self):
         return f"ArdSEProduct({self.logl.tolist()}, {self.logs})"
+
+
+class _IsoMatern(KernelFunction):
+    """Matern kernel with one length-scale: exp(2 logs) (1 + s [+ s^2/3]) exp(-s), s = sqrt(2 nu) |a-b| / exp(logl)
+    (GPML's covMaterniso).  Not a kernel of the reference.  Hyper-vector [logl, logs] as IsoSE; the gradients are the true
+    derivatives of the log-marginal (no SURVEY F7 factor sigma; include/dsmgp_hip.h, dsmgp_gradients)."""
+
+    def __init__(self, logl, logs):
+        self.logl = float(logl)
+        self.logs = float(logs)
+        self.dl = 0.0
+        self.ds = 0.0
+
+    def loghyp(self):
+        return np.array([self.logl, self.logs])
+
+    def set_loghyp(self, v):
+        self.logl, self.logs = float(v[0]), float(v[1])
+
+    def copy(self):
+        return type(self)(self.logl, self.logs)
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.logl}, {self.logs})"
+
+
+class _ArdMatern(KernelFunction):
+    """Matern kernel with one length-scale per input dimension: r^2 = sum_d (a_d-b_d)^2 / exp(logl_d)^2 in the formula of
+    the iso kind (GPML's covMaternard, the distance form).  Not a kernel of the reference.  Hyper-vector [logl_1..logl_D,
+    logs] as ArdSEProduct; all gradients are the true derivatives of the log-marginal."""
+
+    def __init__(self, logl, logs):
+        self.logl = np.array(logl, dtype=np.float64).reshape(-1)
+        self.logs = float(logs)
+        self.dl = np.zeros_like(self.logl)
+        self.ds = 0.0
+
+    def loghyp(self):
+        return np.concatenate([self.logl, [self.logs]])
+
+    def set_loghyp(self, v):
+        self.logl = np.array(v[:-1], dtype=np.float64)
+        self.logs = float(v[-1])
+
+    def copy(self):
+        return type(self)(self.logl.copy(), self.logs)
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.logl.tolist()}, {self.logs})"
+
+
+class IsoMatern32(_IsoMatern):
+    """Matern nu = 3/2: exp(2 logs) (1 + s) exp(-s), s = sqrt(3) |a-b| / exp(logl)."""
+    kind = KIND_ISO_MATERN32
+
+
+class IsoMatern52(_IsoMatern):
+    """Matern nu = 5/2: exp(2 logs) (1 + s + s^2/3) exp(-s), s = sqrt(5) |a-b| / exp(logl)."""
+    kind = KIND_ISO_MATERN52
+
+
+class ArdMatern32(_ArdMatern):
+    """Matern nu = 3/2 with per-dimension length-scales: s = sqrt(3 sum_d (a_d-b_d)^2 / exp(logl_d)^2)."""
+    kind = KIND_ARD_MATERN32
+
+
+class ArdMatern52(_ArdMatern):
+    """Matern nu = 5/2 with per-dimension length-scales: s = sqrt(5 sum_d (a_d-b_d)^2 / exp(logl_d)^2)."""
+    kind = KIND_ARD_MATERN52
 
 
 class ConstMean:

@@ -17,7 +17,8 @@ except ImportError:          # pragma: no cover
     _xxhash = None
 
 from . import hipabi
-from .kernels import IsoSE, ConstMean, KIND_ISO_SE, KIND_ARD_SE, KIND_ISO_LINEAR, KIND_ARD_LINEAR, KIND_ARD_SE_PRODUCT
+from .kernels import (IsoSE, ConstMean, KIND_ISO_SE, KIND_ARD_SE, KIND_ISO_LINEAR, KIND_ARD_LINEAR, KIND_ARD_SE_PRODUCT,
+                      KIND_ISO_MATERN32, KIND_ISO_MATERN52, KIND_ARD_MATERN32, KIND_ARD_MATERN52)
 from .tree import (DSMGPConfig, GPSumNode, build_tree, get_leaves, get_overlap, obs_table, share_schedule, share_decisions,
                    share_census, route, route_all, route_index, get_child, ordered_nodes, SHARE_COPY, SHARE_FULL, SHARE_PREFIX)
 from . import dist as _dist
@@ -591,7 +592,8 @@ def updategradients(model, active=None):
         elif lf.kernel.kind == KIND_ARD_LINEAR:       # [dl_1..dl_D, 0, dnoise]: no variance gradient
             lf.kernel.dl = row[: n - 1].copy()
         else:
-            lf.kernel.dl = row[: n - 1].copy() if lf.kernel.kind in (KIND_ARD_SE, KIND_ARD_SE_PRODUCT) else float(row[0])
+            ard = lf.kernel.kind in (KIND_ARD_SE, KIND_ARD_SE_PRODUCT, KIND_ARD_MATERN32, KIND_ARD_MATERN52)
+            lf.kernel.dl = row[: n - 1].copy() if ard else float(row[0])
             lf.kernel.ds = float(row[n - 1])
         lf.dnoise = float(row[n])
     target.leaf_grad = g
@@ -1157,7 +1159,7 @@ def _aggregate_dsmgp(model, xt, ptr, mu, var, sel_cache=None):
 
 def _prior_diag(lf, xt):
     k = lf.kernel
-    if k.kind in (KIND_ISO_SE, KIND_ARD_SE_PRODUCT):
+    if k.kind in (KIND_ISO_SE, KIND_ARD_SE_PRODUCT, KIND_ISO_MATERN32, KIND_ISO_MATERN52, KIND_ARD_MATERN32, KIND_ARD_MATERN52):
         return np.full(xt.shape[0], np.exp(2 * k.logs))
     if k.kind == KIND_ARD_SE:
         return np.full(xt.shape[0], np.exp(2 * k.logs) * xt.shape[1])

@@ -44,6 +44,15 @@ typedef struct dsmgp_ctx dsmgp_ctx;
  * only: k(a, b) == k(b, a) to the bit).  Hyper-vector [logl_1..logl_D, logs, logNoise] as ArdSE; exactly D length-scales
  * (set_hyper refuses another length once set_train has fixed D).  Not a kernel of the reference, whose ArdSE is additive. */
 #define DSMGP_KIND_ARD_SE_PRODUCT 4
+/* Matern kernels, distance form (GPML covMaterniso / covMaternard): r^2 = sum_d (a_d - b_d)^2 / l_d^2, s = sqrt(2 nu) r,
+ * k(a, b) = sigma^2 (1 + s) exp(-s) for nu = 3/2 and sigma^2 (1 + s + s^2 / 3) exp(-s) for nu = 5/2; k(x, x) = sigma^2.  s^2 is
+ * added in ascending d from (a_d - b_d)^2 * (2 nu / l_d^2) (k(a, b) == k(b, a) to the bit; an iso kind is its ARD kind with all
+ * l_d equal, to the bit).  Iso hyper-vector [logl, logs, logNoise] (exactly 3 values); ARD [logl_1..logl_D, logs, logNoise]
+ * (exactly D length-scales once set_train has fixed D): set_hyper refuses other lengths.  Not kernels of the reference. */
+#define DSMGP_KIND_ISO_MATERN32 5   /* nu = 3/2, one length-scale */
+#define DSMGP_KIND_ISO_MATERN52 6   /* nu = 5/2, one length-scale */
+#define DSMGP_KIND_ARD_MATERN32 7   /* nu = 3/2, one length-scale per input dimension */
+#define DSMGP_KIND_ARD_MATERN52 8   /* nu = 5/2, one length-scale per input dimension */
 
 /* per-leaf sharing decisions of the shared-Cholesky fit! (src/fit.jl:107-117) */
 #define DSMGP_SHARE_FULL   0      /* update_cholesky!               src/gaussianprocess.jl:82-108 */
@@ -169,7 +178,10 @@ int dsmgp_scores(dsmgp_ctx* ctx, const double* y_test /* n_t */, double* out /* 
  *      of the trace term, any D; DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT does not apply).  With all l_d equal their sum is
  *      IsoLinear's dl (src/kernels.jl:196-200).
  *      ArdSEProduct: [dl_1..dl_D, ds, dnoise], all true derivatives (no SURVEY F7 factor): dl_d = 0.5 sum_rc W_rc K_rc
- *      (x_rd - x_cd)^2 / l_d^2 and ds = tr(W K), W = alpha alpha^T - K_y^-1, K without noise; any D. */
+ *      (x_rd - x_cd)^2 / l_d^2 and ds = tr(W K), W = alpha alpha^T - K_y^-1, K without noise; any D.
+ *      Matern (kinds 5-8): iso [dl, ds, dnoise], ARD [dl_1..dl_D, ds, dnoise], all true derivatives (no SURVEY F7 factor):
+ *      dl_d = 0.5 sum_rc W_rc sigma^2 exp(-s) c(s) s_d^2 with s_d^2 = 2 nu (x_rd - x_cd)^2 / l_d^2, c(s) = 1 (nu = 3/2) or
+ *      (1 + s) / 3 (nu = 5/2) -- finite at s = 0, nothing divides by r; the iso dl is the sum over d; ds = tr(W K); any D. */
 int dsmgp_gradients(dsmgp_ctx* ctx, double* grad_out, int32_t stride);
 /* Restricts dsmgp_gradients to the leaves with active[l] != 0 (NULL: every leaf again; a new leaf table resets it): the rows
  * of the others come back as zeros, and neither L^-T nor the contraction tiles of leaves nobody asked for are computed (a

@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, ArdSEProduct
+export attach!, detach!, census, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -62,6 +62,59 @@ DeepStructuredMixtures.setlengthscale!(k::ArdSEProduct{T}, l::AbstractVector{T})
 DeepStructuredMixtures.getdistancematrix(k::ArdSEProduct{T}, x1::AbstractMatrix{T}, x2::AbstractMatrix{T}) where {T} =
     DeepStructuredMixtures.getdistancematrix(ArdSE(k.logℓ, k.logσ), x1, x2)
 
+# ---------------------------------------------------------------------------------------------- Matérn 3/2 and 5/2
+"""
+    IsoMatern32(logℓ, logσ), IsoMatern52(logℓ, logσ), ArdMatern32(logℓ, logσ), ArdMatern52(logℓ, logσ)
+
+Matérn kernels in the distance form (GPML's covMaterniso / covMaternard): r² = Σ_d (a_d - b_d)² / ℓ_d², s = √(2ν) r,
+k = σ² (1 + s) e^(-s) for ν = 3/2 and σ² (1 + s + s²/3) e^(-s) for ν = 5/2.  The iso types have IsoSE's fields, the ARD types
+ArdSE's.  Not kernels of the reference: they live on the device only (kinds 5-8), with just the methods GaussianProcess
+(src/gaussianprocess.jl:50-58) and params / setparams! (:139-161) call on a kernel.  Their gradients are the true derivatives,
+written into ∂ℓ and ∂σ by updategradients!.
+"""
+mutable struct IsoMatern32{T<:AbstractFloat} <: DeepStructuredMixtures.IsoKernel
+    logℓ::T
+    logσ::T
+    ∂ℓ::T
+    ∂σ::T
+end
+mutable struct IsoMatern52{T<:AbstractFloat} <: DeepStructuredMixtures.IsoKernel
+    logℓ::T
+    logσ::T
+    ∂ℓ::T
+    ∂σ::T
+end
+mutable struct ArdMatern32{T<:AbstractFloat} <: DeepStructuredMixtures.ArdKernel
+    logℓ::Vector{T}
+    logσ::T
+    ∂ℓ::Vector{T}
+    ∂σ::T
+end
+mutable struct ArdMatern52{T<:AbstractFloat} <: DeepStructuredMixtures.ArdKernel
+    logℓ::Vector{T}
+    logσ::T
+    ∂ℓ::Vector{T}
+    ∂σ::T
+end
+IsoMatern32(logℓ, logσ) = IsoMatern32(logℓ, logσ, zero(logℓ), zero(logσ))
+IsoMatern52(logℓ, logσ) = IsoMatern52(logℓ, logσ, zero(logℓ), zero(logσ))
+ArdMatern32(logℓ, logσ) = ArdMatern32(logℓ, logσ, zero(logℓ), zero(logσ))
+ArdMatern52(logℓ, logσ) = ArdMatern52(logℓ, logσ, zero(logℓ), zero(logσ))
+const IsoMatern = Union{IsoMatern32,IsoMatern52}
+const ArdMatern = Union{ArdMatern32,ArdMatern52}
+DeepStructuredMixtures.getvariance(k::Union{IsoMatern,ArdMatern}; logscale=false) = logscale ? k.logσ : exp(2 * k.logσ)
+DeepStructuredMixtures.getstd(k::Union{IsoMatern,ArdMatern}) = exp(k.logσ)
+DeepStructuredMixtures.setvariance!(k::Union{IsoMatern,ArdMatern}, v::AbstractFloat) = (k.logσ = v)
+DeepStructuredMixtures.getlengthscales(k::IsoMatern; logscale=false) = logscale ? k.logℓ : exp(k.logℓ)
+DeepStructuredMixtures.getlengthscales(k::ArdMatern; logscale=false) = logscale ? k.logℓ : exp.(k.logℓ)
+DeepStructuredMixtures.setlengthscale!(k::IsoMatern, l::AbstractFloat) = (k.logℓ = l)
+DeepStructuredMixtures.setlengthscale!(k::ArdMatern, l::AbstractVector) = (k.logℓ[:] = l)
+# the distance arrays GaussianProcess stores in gp.P (those IsoSE and ArdSE build; the device never reads them)
+DeepStructuredMixtures.getdistancematrix(k::IsoMatern, x1::AbstractMatrix, x2::AbstractMatrix) =
+    DeepStructuredMixtures.getdistancematrix(IsoSE(k.logℓ, k.logσ), x1, x2)
+DeepStructuredMixtures.getdistancematrix(k::ArdMatern, x1::AbstractMatrix, x2::AbstractMatrix) =
+    DeepStructuredMixtures.getdistancematrix(ArdSE(k.logℓ, k.logσ), x1, x2)
+
 # ---------------------------------------------------------------------------------------------- library
 const LIB = Ref{Ptr{Cvoid}}(C_NULL)
 function lib()
@@ -80,12 +133,18 @@ kind(::ArdSE) = Int32(1)
 kind(::IsoLinear) = Int32(2)
 kind(::ArdLinear) = Int32(3)     # DSMGP_KIND_ARD_LINEAR: sum_d a_d b_d / ℓ_d² (the reference's own methods cannot fit it, src/kernels.jl:232,247)
 kind(::ArdSEProduct) = Int32(4)  # DSMGP_KIND_ARD_SE_PRODUCT: σ² exp(-½ Σ_d (a_d - b_d)² / ℓ_d²), not a kernel of the reference
+kind(::IsoMatern32) = Int32(5)   # DSMGP_KIND_ISO_MATERN32: σ² (1 + s) e^(-s), s = √3 r; not kernels of the reference
+kind(::IsoMatern52) = Int32(6)   # DSMGP_KIND_ISO_MATERN52: σ² (1 + s + s²/3) e^(-s), s = √5 r
+kind(::ArdMatern32) = Int32(7)   # DSMGP_KIND_ARD_MATERN32: as 5 with one ℓ_d per dimension
+kind(::ArdMatern52) = Int32(8)   # DSMGP_KIND_ARD_MATERN52: as 6 with one ℓ_d per dimension
 # hyper-vector of one kernel id on the reference's log scale, [logℓ..., logσ, logNoise] (src/gaussianprocess.jl:141-161)
 loghyp(k::IsoSE, ln) = Float64[k.logℓ, k.logσ, ln]
 loghyp(k::ArdSE, ln) = Float64[k.logℓ..., k.logσ, ln]
 loghyp(k::IsoLinear, ln) = Float64[k.logℓ, 0.0, ln]             # the variance slot is a dummy (src/kernels.jl:181-183)
 loghyp(k::ArdLinear, ln) = Float64[k.logℓ..., 0.0, ln]          # ... here too (src/kernels.jl:216-218)
 loghyp(k::ArdSEProduct, ln) = Float64[k.logℓ..., k.logσ, ln]    # the layout of ArdSE
+loghyp(k::IsoMatern, ln) = Float64[k.logℓ, k.logσ, ln]          # the layout of IsoSE
+loghyp(k::ArdMatern, ln) = Float64[k.logℓ..., k.logσ, ln]       # the layout of ArdSE
 
 # ---------------------------------------------------------------------------------------------- session
 "One device context + the leaf table of one model (or of one stand-alone GaussianProcess)."
@@ -502,8 +561,8 @@ function fetchgradients!(s::Session)
     GC.@preserve g chk(s, ccall(sym(:dsmgp_gradients), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32), s.h, g, Int32(s.stride)))
     for (l, gp) in enumerate(s.gps)
         k = gp.kernel
-        nl = k isa Union{ArdSE,ArdLinear} || k isa ArdSEProduct ? length(k.logℓ) : 1
-        if k isa Union{ArdSE,ArdLinear} || k isa ArdSEProduct
+        nl = k isa Union{ArdSE,ArdLinear} || k isa ArdSEProduct || k isa ArdMatern ? length(k.logℓ) : 1
+        if k isa Union{ArdSE,ArdLinear} || k isa ArdSEProduct || k isa ArdMatern
             k.∂ℓ[:] = g[1:nl, l]        # ArdLinear: written in place, never through getgradients (src/kernels.jl:247 cannot run)
         else
             k.∂ℓ = g[1, l]
