@@ -966,23 +966,45 @@ inline int tile_mrows(int valid) {
     return m >= TB ? 0 : std::max(16, m);
 }
 
-inline bool is_matern(int kind) { return kind >= DSMGP_KIND_ISO_MATERN32 && kind <= DSMGP_KIND_ARD_MATERN52; }
-inline bool is_iso_matern(int kind) { return kind == DSMGP_KIND_ISO_MATERN32 || kind == DSMGP_KIND_ISO_MATERN52; }
+// What the host needs to know about a kernel kind: one row per DSMGP_KIND_*, indexed by the kind (dsmgp_set_hyper admits no
+// other value; a kernel id never set has kind -1 and no row).
+struct KindInfo {
+    const char* name;
+    bool ard;           // one length-scale per input dimension (else one)
+    bool iso_matern;    // Matern with one length-scale: D equal per-dimension slots of it
+    bool matern;        // device KIND 5
+    bool linear;        // no signal variance: KParam.sigma2 = sigma = 1
+    double nh_num;      // numerator of the per-dimension factor KParam.nh = nh_num / l^2: -0.5, 1 (ArdLinear) or 2 nu (Matern)
+    bool per_dim_grad;  // length-scale gradients from the per-dimension contraction sums Sd (ArdSE: with ard_true_gradient only)
+    bool contraction;   // the gradient always contracts (alpha alpha^T - K_y^-1) with dK on the device (tile_graddot*); ArdSE
+                        //   with ard_true_gradient only
+    bool set_checked;   // dsmgp_set_hyper refuses a wrong number of length-scales itself (the reference kinds: check_hyper, at fit)
+};
+constexpr KindInfo KINDS[] = {
+    //  name           ard    iso_m  matern linear nh_num per_dim contr. set_checked
+    {"IsoSE",          false, false, false, false, -0.5,  false,  true,  false},
+    {"ArdSE",          true,  false, false, false, -0.5,  true,   false, false},
+    {"IsoLinear",      false, false, false, true,  -0.5,  false,  false, false},
+    {"ArdLinear",      true,  false, false, true,  1.0,   false,  false, false},
+    {"ArdSEProduct",   true,  false, false, false, -0.5,  true,   true,  true},
+    {"IsoMatern32",    false, true,  true,  false, 3.0,   true,   true,  true},
+    {"IsoMatern52",    false, true,  true,  false, 5.0,   true,   true,  true},
+    {"ArdMatern32",    true,  false, true,  false, 3.0,   true,   true,  true},
+    {"ArdMatern52",    true,  false, true,  false, 5.0,   true,   true,  true},
+};
+static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == DSMGP_KIND_ARD_MATERN52 + 1, "one row per DSMGP_KIND_*");
+
 // some kernel id has a Matern kind: the fused steps launch diag_fused_reg_matern_kernel as well
 inline bool any_matern(const dsmgp_ctx* c) {
     for (const HyperHost& h : c->hyper)
-        if (is_matern(h.kind)) return true;
+        if (h.kind >= 0 && KINDS[h.kind].matern) return true;
     return false;
-}
-// 2 nu of a Matern kind
-inline double matern_2nu(int kind) {
-    return (kind == DSMGP_KIND_ISO_MATERN32 || kind == DSMGP_KIND_ARD_MATERN32) ? 3.0 : 5.0;
 }
 
 // Upload the KParam table from the host hyper-parameters.
 int upload_hyper(dsmgp_ctx* c) {
     const int nk = (int)c->hyper.size();
-    std::vector<double> l2pool;
+    std::vector<double> l2pool, slot_num;
     std::vector<KParam> kp(nk);
     std::vector<size_t> off(nk);
     for (int k = 0; k < nk; ++k) {
@@ -998,28 +1020,22 @@ int upload_hyper(dsmgp_ctx* c) {
             const double l = std::exp(h.loghyp[i]);
             l2pool.push_back(l * l);
         }
+        const KindInfo& ki = KINDS[h.kind];
         // an iso Matern id reads D per-dimension factors like its ARD kind: D slots of its one length-scale
-        if (is_iso_matern(h.kind))
+        if (ki.iso_matern)
             for (int i = 1; i < c->D; ++i) l2pool.push_back(l2pool[off[k]]);
+        slot_num.resize(l2pool.size(), ki.nh_num);
         kp[k].kind = h.kind;
         kp[k].nl = nl;
         const double logs = h.loghyp[nl];
         const double logn = h.loghyp[nl + 1];
-        const bool linear = h.kind == DSMGP_KIND_ISO_LINEAR || h.kind == DSMGP_KIND_ARD_LINEAR;   // no signal variance
-        kp[k].sigma2 = linear ? 1.0 : std::exp(2.0 * logs);
-        kp[k].sigma = linear ? 1.0 : std::exp(logs);
+        kp[k].sigma2 = ki.linear ? 1.0 : std::exp(2.0 * logs);
+        kp[k].sigma = ki.linear ? 1.0 : std::exp(logs);
         kp[k].noise = std::exp(2.0 * logn);
     }
     const size_t nslots = l2pool.size();
     // second half (KParam.nh): the per-dimension factor -- of the exponent, -0.5 / l^2, of ArdLinear's product, 1 / l_d^2, or
     // of a Matern kernel's s^2, 2 nu / l_d^2
-    std::vector<double> slot_num(nslots, -0.5);
-    for (int k = 0; k < nk; ++k) {
-        const int kind = c->hyper[k].kind;
-        if (kind != DSMGP_KIND_ARD_LINEAR && !is_matern(kind)) continue;
-        const size_t ns = is_iso_matern(kind) ? (size_t)std::max(1, c->D) : c->hyper[k].loghyp.size() - 2;
-        for (size_t i = off[k]; i < off[k] + ns; ++i) slot_num[i] = kind == DSMGP_KIND_ARD_LINEAR ? 1.0 : matern_2nu(kind);
-    }
     for (size_t i = 0; i < nslots; ++i) l2pool.push_back(slot_num[i] / l2pool[i]);
     if (l2pool.size() > c->d_l2.cap || !c->d_l2.p) {   // (re)allocate only when the table grows: fit is called in loops
         drop_graphs(c);
@@ -1043,26 +1059,11 @@ int upload_hyper(dsmgp_ctx* c) {
     return 0;
 }
 
-// an ArdLinear, ArdSEProduct or ARD Matern kernel id reads D per-dimension factors wherever its kernel function is evaluated
+// an ARD kernel id reads D per-dimension factors wherever its kernel function is evaluated (the additive ArdSE is left to
+// check_hyper here, as it has been since this check came in with ArdLinear)
 bool ard_linear_short(const dsmgp_ctx* c, int kid) {
     const HyperHost& h = c->hyper[kid];
-    return (h.kind == DSMGP_KIND_ARD_LINEAR || h.kind == DSMGP_KIND_ARD_SE_PRODUCT || h.kind == DSMGP_KIND_ARD_MATERN32 ||
-            h.kind == DSMGP_KIND_ARD_MATERN52) &&
-           (int)h.loghyp.size() - 2 != c->D;
-}
-
-const char* kind_name(int kind) {
-    switch (kind) {
-        case DSMGP_KIND_ISO_SE: return "IsoSE";
-        case DSMGP_KIND_ARD_SE: return "ArdSE";
-        case DSMGP_KIND_ISO_LINEAR: return "IsoLinear";
-        case DSMGP_KIND_ARD_LINEAR: return "ArdLinear";
-        case DSMGP_KIND_ISO_MATERN32: return "IsoMatern32";
-        case DSMGP_KIND_ISO_MATERN52: return "IsoMatern52";
-        case DSMGP_KIND_ARD_MATERN32: return "ArdMatern32";
-        case DSMGP_KIND_ARD_MATERN52: return "ArdMatern52";
-        default: return "ArdSEProduct";
-    }
+    return KINDS[h.kind].ard && h.kind != DSMGP_KIND_ARD_SE && (int)h.loghyp.size() - 2 != c->D;
 }
 
 int check_hyper(dsmgp_ctx* c) {
@@ -1073,10 +1074,9 @@ int check_hyper(dsmgp_ctx* c) {
                                               " without hyper-parameters");
         const HyperHost& h = c->hyper[kid];
         const int nl = (int)h.loghyp.size() - 2;
-        const bool ard = h.kind == DSMGP_KIND_ARD_SE || h.kind == DSMGP_KIND_ARD_LINEAR || h.kind == DSMGP_KIND_ARD_SE_PRODUCT ||
-                         h.kind == DSMGP_KIND_ARD_MATERN32 || h.kind == DSMGP_KIND_ARD_MATERN52;
+        const bool ard = KINDS[h.kind].ard;
         if (ard && nl != c->D)
-            return fail(c, DSMGP_E_ARG, std::string(kind_name(h.kind)) + " needs one lengthscale per input dimension");
+            return fail(c, DSMGP_E_ARG, std::string(KINDS[h.kind].name) + " needs one lengthscale per input dimension");
         if (!ard && nl != 1) return fail(c, DSMGP_E_ARG, "Iso kernels take one lengthscale");
     }
     return 0;
@@ -2391,11 +2391,11 @@ int dsmgp_set_hyper(dsmgp_ctx* c, int32_t kernel_id, int32_t kind, const double*
     if (!c) return DSMGP_E_ARG;
     if (kernel_id < 0 || kernel_id >= DSMGP_MAX_KERNEL_IDS || !loghyp || n < 3) return fail(c, DSMGP_E_ARG, "set_hyper: bad arguments");
     if (kind < 0 || kind > DSMGP_KIND_ARD_MATERN52) return fail(c, DSMGP_E_ARG, "set_hyper: unknown kernel kind");
-    if ((kind == DSMGP_KIND_ARD_SE_PRODUCT || kind == DSMGP_KIND_ARD_MATERN32 || kind == DSMGP_KIND_ARD_MATERN52) && c->D > 0 &&
-        n != c->D + 2)
-        return fail(c, DSMGP_E_ARG, std::string("set_hyper: ") + kind_name(kind) + " needs one lengthscale per input dimension");
-    if (is_iso_matern(kind) && n != 3)
-        return fail(c, DSMGP_E_ARG, std::string("set_hyper: ") + kind_name(kind) + " takes [logl, logs, logNoise]");
+    const KindInfo& ki = KINDS[kind];
+    if (ki.set_checked && ki.ard && c->D > 0 && n != c->D + 2)
+        return fail(c, DSMGP_E_ARG, std::string("set_hyper: ") + ki.name + " needs one lengthscale per input dimension");
+    if (ki.set_checked && !ki.ard && n != 3)
+        return fail(c, DSMGP_E_ARG, std::string("set_hyper: ") + ki.name + " takes [logl, logs, logNoise]");
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(loghyp[i])) return fail(c, DSMGP_E_ARG, "set_hyper: non-finite hyper-parameter");
     if ((int)c->hyper.size() <= kernel_id) c->hyper.resize(kernel_id + 1);
@@ -3191,7 +3191,7 @@ int dsmgp_aggregate_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain
         (prior_kernel_id < 0 || prior_kernel_id >= (int)c->hyper.size() || c->hyper[prior_kernel_id].kind < 0))
         return fail(c, DSMGP_E_ARG, "aggregate_finish: rBCM needs the kernel id of the model's first leaf");
     if (c->agg_family == AGG_RBCM && ard_linear_short(c, prior_kernel_id))
-        return fail(c, DSMGP_E_ARG, std::string("aggregate_finish: ") + kind_name(c->hyper[prior_kernel_id].kind) +
+        return fail(c, DSMGP_E_ARG, std::string("aggregate_finish: ") + KINDS[c->hyper[prior_kernel_id].kind].name +
                                         " needs one lengthscale per input dimension");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nt = (size_t)c->n_t;
@@ -3386,8 +3386,8 @@ int build_grad_plan(dsmgp_ctx* c) {
             const int kind_l = c->hyper[lf.kid].kind;
             const bool ard = kind_l == DSMGP_KIND_ARD_SE && c->ard_true_gradient;
             const bool prod = kind_l == DSMGP_KIND_ARD_SE_PRODUCT;
-            const bool mat = is_matern(kind_l);
-            if (kind_l != DSMGP_KIND_ISO_SE && !ard && !prod && !mat) continue;
+            const bool mat = KINDS[kind_l].matern;
+            if (!KINDS[kind_l].contraction && !ard) continue;
             if ((prod ? 1 : mat ? 2 : 0) != pass) continue;
             any_ard = any_ard || ard;
             any_prod = any_prod || prod || mat;
@@ -3446,7 +3446,8 @@ int build_grad_plan(dsmgp_ctx* c) {
     c->gardlin_leaf.clear();
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
-        if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR || c->grad_src[l] >= 0 || !needC[l]) continue;
+        if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR) continue;
+        if (c->grad_src[l] >= 0 || !needC[l]) continue;
         const LeafDev& d = c->h_leaves[l];
         for (int c0 = 0; c0 < lf.n; c0 += ARDLIN_COLS) {
             ArdLinTask a{};
@@ -3576,8 +3577,7 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     if (gs > 2) Sd.assign((size_t)L * c->D, 0.0);
     for (size_t i = 0; i < c->gdot.count; ++i) {
         const int l = c->gdot_leaf[i];
-        const int kind_l = c->hyper[c->leaves[l].kid].kind;
-        if (kind_l == DSMGP_KIND_ARD_SE || kind_l == DSMGP_KIND_ARD_SE_PRODUCT || is_matern(kind_l)) {
+        if (KINDS[c->hyper[c->leaves[l].kid].kind].per_dim_grad) {
             for (int d = 0; d < c->D; ++d) Sd[(size_t)l * c->D + d] += pd[gs * i + 2 + d];
         } else {
             S1[l] += pd[gs * i];
@@ -3643,9 +3643,9 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
             // the true derivatives: 0.5 tr(W dK / dlog l_d) from the per-dimension sums, 0.5 tr(W 2K) = tr(W K) (no SURVEY F7 factor)
             for (int d = 0; d < nl; ++d) g[d] = 0.5 * Sd[(size_t)l * c->D + d];
             g[nl] = trPK;
-        } else if (is_matern(h.kind)) {
+        } else if (KINDS[h.kind].matern) {
             // the true derivatives as for ArdSEProduct; an iso kind's dl is the sum over the dimensions, added in ascending d
-            if (is_iso_matern(h.kind)) {
+            if (KINDS[h.kind].iso_matern) {
                 double sl = 0.0;
                 for (int d = 0; d < c->D; ++d) sl += Sd[(size_t)l * c->D + d];
                 g[0] = 0.5 * sl;
@@ -3667,7 +3667,7 @@ int dsmgp_kernel_matrix(dsmgp_ctx* c, int32_t kernel_id, const double* x1, int64
     if (kernel_id < 0 || kernel_id >= (int)c->hyper.size() || c->hyper[kernel_id].kind < 0)
         return fail(c, DSMGP_E_STATE, "kernel_matrix: kernel id without hyper-parameters");
     if (ard_linear_short(c, kernel_id))
-        return fail(c, DSMGP_E_ARG, std::string("kernel_matrix: ") + kind_name(c->hyper[kernel_id].kind) +
+        return fail(c, DSMGP_E_ARG, std::string("kernel_matrix: ") + KINDS[c->hyper[kernel_id].kind].name +
                                         " needs one lengthscale per input dimension");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = upload_hyper(c)) return rc;
@@ -3739,9 +3739,7 @@ int dsmgp_work_gradients(dsmgp_ctx* c, double* alg_flops_inverse, double* alg_fl
         const LeafHost& lf = c->leaves[l];
         const double n = (double)lf.n;
         if (lf.owner == l) fi += n * n * n / 3.0;
-        if (lf.kid < (int)c->hyper.size() &&
-            (c->hyper[lf.kid].kind == DSMGP_KIND_ISO_SE || c->hyper[lf.kid].kind == DSMGP_KIND_ARD_SE_PRODUCT ||
-             is_matern(c->hyper[lf.kid].kind)))
+        if (lf.kid < (int)c->hyper.size() && c->hyper[lf.kid].kind >= 0 && KINDS[c->hyper[lf.kid].kind].contraction)
             fc += n * n * n / 3.0;
     }
     if (alg_flops_inverse) *alg_flops_inverse = fi;

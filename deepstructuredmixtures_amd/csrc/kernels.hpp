@@ -56,6 +56,23 @@ struct KParam {
     double il2;         // 1 / l2[0]
 };
 
+// DSMGP_KIND_DISPATCH(kind, K, stmt...): runs stmt once, with `constexpr int K` the device kind of `kind` -- DSMGP kinds 0-4 as
+// they are, 5 for every Matern kind (5-8).  The _NON_MATERN form has the arms 0-4 only (diag_fused_reg_kernel, whose Matern
+// tasks run in a kernel of their own).  A macro and not a generic lambda: dispatching through `[&](auto k)` changed the ISA of
+// nine kernels (diag_fused_reg_matern_kernel: scratch 200 -> 292 bytes per lane); this if / else chain is the one it replaces.
+#define DSMGP_KIND_ARMS_0_4(kind, K, ...)                      \
+    if ((kind) == 0) { constexpr int K = 0; __VA_ARGS__; }      \
+    else if ((kind) == 1) { constexpr int K = 1; __VA_ARGS__; } \
+    else if ((kind) == 2) { constexpr int K = 2; __VA_ARGS__; } \
+    else if ((kind) == 3) { constexpr int K = 3; __VA_ARGS__; } \
+    else if ((kind) == 4) { constexpr int K = 4; __VA_ARGS__; }
+#define DSMGP_KIND_DISPATCH(kind, K, ...) \
+    do { DSMGP_KIND_ARMS_0_4(kind, K, __VA_ARGS__) else if ((kind) >= 5) { constexpr int K = 5; __VA_ARGS__; } } while (0)
+#define DSMGP_KIND_DISPATCH_NON_MATERN(kind, K, ...) do { DSMGP_KIND_ARMS_0_4(kind, K, __VA_ARGS__) } while (0)
+
+// device kind K reads the per-dimension factors KParam.nh in its sum over the dimensions (ArdSE, ArdLinear, ArdSEProduct, Matern)
+constexpr bool kind_reads_nh(int K) { return K == 1 || K == 3 || K == 4 || K == 5; }
+
 // exp(x) for finite x <= 0: the argument reduction and degree-12 polynomial of the device library's exp
 // (n = rint(x log2 e), r = x - n ln2 in two pieces, Horner, ldexp) without its overflow / underflow selects --
 // the argument of a squared-exponential kernel is never positive, and ldexp underflows to 0 by itself.
@@ -105,6 +122,48 @@ struct GramTask {
     int kid;
 };
 
+// sum over the dimensions for one entry pair list: z[i][j] over rows a[i], columns b[j]
+template <int KIND, int NA, int NB>
+__device__ __forceinline__ void gram_accumulate(double (&z)[NA][NB], const double (&a)[NA], const double (&b)[NB], double nhd) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            if (KIND == 0) {
+                const double u = a[i] - b[j];
+                z[i][j] = fma(u, u, z[i][j]);
+            } else if (KIND == 1) {
+                const double u = a[i] - b[j];
+                z[i][j] += exp_nonpos((u * u) * nhd);
+            } else if (KIND == 2) {
+                z[i][j] = fma(a[i], b[j], z[i][j]);
+            } else if (KIND == 3) {
+                z[i][j] = fma(a[i] * b[j], nhd, z[i][j]);
+            } else {    // KIND 4, 5
+                const double u = a[i] - b[j];
+                z[i][j] = fma(u * u, nhd, z[i][j]);
+            }
+        }
+}
+
+// kernel value from the accumulated sum, with the padding / diagonal rules of the Gram tiles above (EDGE = false: a tile of
+// 128 valid rows and columns off the block diagonal -- the value as it is)
+template <int KIND, bool EDGE = true>
+__device__ __forceinline__ double gram_finish(double z, const KParam& p, int row, int col, int na, int nb, bool diag_tile) {
+    double kv;
+    if (KIND == 0) kv = p.sigma2 * exp_nonpos(z * p.nh0);
+    else if (KIND == 1) kv = p.sigma2 * z;
+    else if (KIND == 2) kv = z * p.il2;
+    else if (KIND == 3) kv = z;
+    else if (KIND == 4) kv = p.sigma2 * exp_nonpos(z);
+    else kv = matern_value(z, p);
+    if (!EDGE) return kv;
+    const bool valid = (row < na) && (col < nb);
+    if (!valid) kv = 0.0;
+    if (diag_tile && row == col) kv = valid ? kv + (p.noise + 1e-8) : 1.0;
+    return kv;
+}
+
 // One 256-thread workgroup per 128x64 half tile (blockIdx = 2*task + half): thread t owns rows
 // 4*(t&31)..+3 and columns 64*half + (t>>5) + 8q, q<8, so every column is written as 32 threads x 32 B =
 // 1 KiB contiguous, and the 32 accumulators keep the kernel at 4 waves per SIMD.
@@ -129,11 +188,11 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
     // of the K_tn arena hold never reaches a result (a row of a tile product depends on its own operand row only, the riders sum
     // per row, nothing reads beyond a leaf's routed rows): since round 5 the arena is not even cleared (register_test)
     const bool rows_live = tk.sym != 0 || r0 < tk.na;
-    double acc[8][4];
+    double acc[8][4][1];    // acc[q]: the 4 x 1 block of rows r0..r0 + 3, column c0 + cb + 8 q (gram_accumulate<KIND, 4, 1>)
 #pragma unroll
     for (int q = 0; q < 8; ++q)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[q][j] = 0.0;
+        for (int j = 0; j < 4; ++j) acc[q][j][0] = 0.0;
 
     for (int d0 = 0; d0 < D; d0 += DCH) {
         const int dn = min(DCH, D - d0);
@@ -149,40 +208,12 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
         __syncthreads();
         if (!rows_live) continue;
         for (int d = 0; d < dn; ++d) {
-            const double a0 = sa[d][r0], a1 = sa[d][r0 + 1], a2 = sa[d][r0 + 2], a3 = sa[d][r0 + 3];
-            const double nhd = (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? p.nh[d0 + d] : 0.0;   // -0.5 / l_d^2, 1 / l_d^2, 2 nu / l_d^2
+            const double a[4] = {sa[d][r0], sa[d][r0 + 1], sa[d][r0 + 2], sa[d][r0 + 3]};
+            const double nhd = kind_reads_nh(KIND) ? p.nh[d0 + d] : 0.0;   // -0.5 / l_d^2, 1 / l_d^2, 2 nu / l_d^2
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                const double b = sb[d][cb + 8 * q];
-                if (KIND == 0) {
-                    double u;
-                    u = a0 - b; acc[q][0] = fma(u, u, acc[q][0]);
-                    u = a1 - b; acc[q][1] = fma(u, u, acc[q][1]);
-                    u = a2 - b; acc[q][2] = fma(u, u, acc[q][2]);
-                    u = a3 - b; acc[q][3] = fma(u, u, acc[q][3]);
-                } else if (KIND == 1) {
-                    double u;
-                    u = a0 - b; acc[q][0] += exp_nonpos((u * u) * nhd);
-                    u = a1 - b; acc[q][1] += exp_nonpos((u * u) * nhd);
-                    u = a2 - b; acc[q][2] += exp_nonpos((u * u) * nhd);
-                    u = a3 - b; acc[q][3] += exp_nonpos((u * u) * nhd);
-                } else if (KIND == 2) {
-                    acc[q][0] = fma(a0, b, acc[q][0]);
-                    acc[q][1] = fma(a1, b, acc[q][1]);
-                    acc[q][2] = fma(a2, b, acc[q][2]);
-                    acc[q][3] = fma(a3, b, acc[q][3]);
-                } else if (KIND == 3) {
-                    acc[q][0] = fma(a0 * b, nhd, acc[q][0]);
-                    acc[q][1] = fma(a1 * b, nhd, acc[q][1]);
-                    acc[q][2] = fma(a2 * b, nhd, acc[q][2]);
-                    acc[q][3] = fma(a3 * b, nhd, acc[q][3]);
-                } else {
-                    double u;
-                    u = a0 - b; acc[q][0] = fma(u * u, nhd, acc[q][0]);
-                    u = a1 - b; acc[q][1] = fma(u * u, nhd, acc[q][1]);
-                    u = a2 - b; acc[q][2] = fma(u * u, nhd, acc[q][2]);
-                    u = a3 - b; acc[q][3] = fma(u * u, nhd, acc[q][3]);
-                }
+                const double b[1] = {sb[d][cb + 8 * q]};
+                gram_accumulate<KIND, 4, 1>(acc[q], a, b, nhd);
             }
         }
     }
@@ -196,12 +227,12 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
         for (int j = 0; j < 4; ++j) {
             const int r = r0 + j;
             double kv;
-            if (KIND == 0) kv = p.sigma2 * exp_nonpos(acc[q][j] * nh);
-            else if (KIND == 1) kv = p.sigma2 * acc[q][j];
-            else if (KIND == 2) kv = acc[q][j] * il2;
-            else if (KIND == 3) kv = acc[q][j];
-            else if (KIND == 4) kv = p.sigma2 * exp_nonpos(acc[q][j]);
-            else kv = matern_value(acc[q][j], p);
+            if (KIND == 0) kv = p.sigma2 * exp_nonpos(acc[q][j][0] * nh);
+            else if (KIND == 1) kv = p.sigma2 * acc[q][j][0];
+            else if (KIND == 2) kv = acc[q][j][0] * il2;
+            else if (KIND == 3) kv = acc[q][j][0];
+            else if (KIND == 4) kv = p.sigma2 * exp_nonpos(acc[q][j][0]);
+            else kv = matern_value(acc[q][j][0], p);
             const bool valid = (r < tk.na) && (c < tk.nb);
             if (!valid) kv = 0.0;
             if (tk.sym && tk.diag && r == c) kv = valid ? kv + (p.noise + 1e-8) : 1.0;
@@ -218,12 +249,7 @@ __global__ __launch_bounds__(256) void gram_tile_kernel(const GramTask* __restri
     const GramTask tk = tasks[blockIdx.x >> 1];
     const KParam p = kp[tk.kid];
     const int half = blockIdx.x & 1;
-    if (p.kind == 0) gram_half_tile<0>(tk, p, D, half, sa, sb);
-    else if (p.kind == 1) gram_half_tile<1>(tk, p, D, half, sa, sb);
-    else if (p.kind == 2) gram_half_tile<2>(tk, p, D, half, sa, sb);
-    else if (p.kind == 3) gram_half_tile<3>(tk, p, D, half, sa, sb);
-    else if (p.kind == 4) gram_half_tile<4>(tk, p, D, half, sa, sb);
-    else if (p.kind >= 5) gram_half_tile<5>(tk, p, D, half, sa, sb);
+    DSMGP_KIND_DISPATCH(p.kind, K, gram_half_tile<K>(tk, p, D, half, sa, sb));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -327,48 +353,6 @@ __device__ __forceinline__ void gram_stage_coords(const TileTask& tk, int D, dou
     __syncthreads();
 }
 
-// sum over the dimensions for one entry pair list: z[i][j] over rows a[i], columns b[j] (gram_half_tile's inner loop)
-template <int KIND, int NA, int NB>
-__device__ __forceinline__ void gram_accumulate(double (&z)[NA][NB], const double (&a)[NA], const double (&b)[NB], double nhd) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            if (KIND == 0) {
-                const double u = a[i] - b[j];
-                z[i][j] = fma(u, u, z[i][j]);
-            } else if (KIND == 1) {
-                const double u = a[i] - b[j];
-                z[i][j] += exp_nonpos((u * u) * nhd);
-            } else if (KIND == 2) {
-                z[i][j] = fma(a[i], b[j], z[i][j]);
-            } else if (KIND == 3) {
-                z[i][j] = fma(a[i] * b[j], nhd, z[i][j]);
-            } else {    // KIND 4, 5
-                const double u = a[i] - b[j];
-                z[i][j] = fma(u * u, nhd, z[i][j]);
-            }
-        }
-}
-
-// kernel value from the accumulated sum, with the padding / diagonal rules of gram_half_tile (EDGE = false: a tile of
-// 128 valid rows and columns off the block diagonal -- the value as it is)
-template <int KIND, bool EDGE = true>
-__device__ __forceinline__ double gram_finish(double z, const KParam& p, int row, int col, int na, int nb, bool diag_tile) {
-    double kv;
-    if (KIND == 0) kv = p.sigma2 * exp_nonpos(z * p.nh0);
-    else if (KIND == 1) kv = p.sigma2 * z;
-    else if (KIND == 2) kv = z * p.il2;
-    else if (KIND == 3) kv = z;
-    else if (KIND == 4) kv = p.sigma2 * exp_nonpos(z);
-    else kv = matern_value(z, p);
-    if (!EDGE) return kv;
-    const bool valid = (row < na) && (col < nb);
-    if (!valid) kv = 0.0;
-    if (diag_tile && row == col) kv = valid ? kv + (p.noise + 1e-8) : 1.0;
-    return kv;
-}
-
 // Full tile, accumulator layout of gemm_mainloop_v2: lane rows wr*64 + 16 rn + l15 (4), columns wc*64 + 16 cm + l4 + 4 r
 // (16), one cm (16 entries) at a time.
 template <int KIND, bool EDGE>
@@ -396,7 +380,7 @@ __device__ __forceinline__ void gram_tile_epilogue(const TileTask& tk, const KPa
                 a[i] = pa[d * TB + 16 * i];
                 b[i] = pb[d * TB + 4 * i];
             }
-            gram_accumulate<KIND, 4, 4>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? p.nh[d] : 0.0);
+            gram_accumulate<KIND, 4, 4>(z, a, b, kind_reads_nh(KIND) ? p.nh[d] : 0.0);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -419,25 +403,9 @@ __device__ __forceinline__ void tile_epilogue(const TileTask& tk, d4 (&acc)[4][4
     if (tk.gram != 0 && kp != nullptr) {      // Gram values instead of the tile read (update launches of fit!; no rider there)
         const KParam p = kp[tk.kid];
         const bool edge = tk.gna < TB || tk.gnb < TB || (tk.gram & 2) != 0;
-        if (p.kind == 0) {
-            if (edge) gram_tile_epilogue<0, true>(tk, p, D, acc, red, sb);
-            else gram_tile_epilogue<0, false>(tk, p, D, acc, red, sb);
-        } else if (p.kind == 1) {
-            if (edge) gram_tile_epilogue<1, true>(tk, p, D, acc, red, sb);
-            else gram_tile_epilogue<1, false>(tk, p, D, acc, red, sb);
-        } else if (p.kind == 2) {
-            if (edge) gram_tile_epilogue<2, true>(tk, p, D, acc, red, sb);
-            else gram_tile_epilogue<2, false>(tk, p, D, acc, red, sb);
-        } else if (p.kind == 3) {
-            if (edge) gram_tile_epilogue<3, true>(tk, p, D, acc, red, sb);
-            else gram_tile_epilogue<3, false>(tk, p, D, acc, red, sb);
-        } else if (p.kind == 4) {
-            if (edge) gram_tile_epilogue<4, true>(tk, p, D, acc, red, sb);
-            else gram_tile_epilogue<4, false>(tk, p, D, acc, red, sb);
-        } else if (p.kind >= 5) {
-            if (edge) gram_tile_epilogue<5, true>(tk, p, D, acc, red, sb);
-            else gram_tile_epilogue<5, false>(tk, p, D, acc, red, sb);
-        }
+        DSMGP_KIND_DISPATCH(p.kind, K,
+                            if (edge) gram_tile_epilogue<K, true>(tk, p, D, acc, red, sb);
+                            else gram_tile_epilogue<K, false>(tk, p, D, acc, red, sb));
         return;
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -852,7 +820,7 @@ __device__ __forceinline__ void syrk_gram_epilogue(const TileTask& tk, const KPa
 #pragma unroll
             for (int r = 0; r < 4; ++r) z[j][0][r] = 0.0;
         for (int d = 0; d < D; ++d) {
-            const double nhd = (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? p.nh[d] : 0.0;
+            const double nhd = kind_reads_nh(KIND) ? p.nh[d] : 0.0;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 double a[1], b[4];
@@ -880,12 +848,7 @@ __device__ __forceinline__ void syrk_finish(const TileTask& tk, d4 (&acc)[9], co
     if (tk.gram != 0 && kp != nullptr) {
         const KParam p = kp[tk.kid];
         gram_stage_coords(tk, D, sa, nullptr, false);
-        if (p.kind == 0) syrk_gram_epilogue<SHAPE, 0>(tk, p, D, acc, blk, sa);
-        else if (p.kind == 1) syrk_gram_epilogue<SHAPE, 1>(tk, p, D, acc, blk, sa);
-        else if (p.kind == 2) syrk_gram_epilogue<SHAPE, 2>(tk, p, D, acc, blk, sa);
-        else if (p.kind == 3) syrk_gram_epilogue<SHAPE, 3>(tk, p, D, acc, blk, sa);
-        else if (p.kind == 4) syrk_gram_epilogue<SHAPE, 4>(tk, p, D, acc, blk, sa);
-        else if (p.kind >= 5) syrk_gram_epilogue<SHAPE, 5>(tk, p, D, acc, blk, sa);
+        DSMGP_KIND_DISPATCH(p.kind, K, syrk_gram_epilogue<SHAPE, K>(tk, p, D, acc, blk, sa));
     } else {
         syrk_epilogue<SHAPE>(tk, acc, blk);
     }
@@ -1053,7 +1016,7 @@ __device__ __forceinline__ void rows_gram_epilogue(const TileTask& tk, const KPa
             for (int i = 0; i < NR; ++i) a[i] = pa[d * TB + 16 * i];
 #pragma unroll
             for (int i = 0; i < 4; ++i) b[i] = pb[d * TB + 4 * i];
-            gram_accumulate<KIND, NR, 4>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? p.nh[d] : 0.0);
+            gram_accumulate<KIND, NR, 4>(z, a, b, kind_reads_nh(KIND) ? p.nh[d] : 0.0);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1083,12 +1046,7 @@ __device__ __forceinline__ void tile_rows_body(const TileTask& tk, double (*sA)[
     if (tk.gram != 0 && kp != nullptr) {
         const KParam p = kp[tk.kid];
         gram_stage_coords(tk, D, &sA[0][0], &sB[0][0], true);
-        if (p.kind == 0) rows_gram_epilogue<NR, 0>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
-        else if (p.kind == 1) rows_gram_epilogue<NR, 1>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
-        else if (p.kind == 2) rows_gram_epilogue<NR, 2>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
-        else if (p.kind == 3) rows_gram_epilogue<NR, 3>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
-        else if (p.kind == 4) rows_gram_epilogue<NR, 4>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
-        else if (p.kind >= 5) rows_gram_epilogue<NR, 5>(tk, p, D, acc, &sA[0][0], &sB[0][0]);
+        DSMGP_KIND_DISPATCH(p.kind, K, rows_gram_epilogue<NR, K>(tk, p, D, acc, &sA[0][0], &sB[0][0]));
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -2649,6 +2607,30 @@ __global__ __launch_bounds__(256) void pred_mu_kernel(const LeafDev* __restrict_
     if (t < TB && tk.row0 + t < lf.nt) lf.mu[tk.row0 + t] = lf.mean + red[t];
 }
 
+// prior variance k(x*, x*) of the point X[r + d ld], d < D: IsoSE / ArdSEProduct / Matern sigma^2, ArdSE sigma^2 D, IsoLinear
+// sum_d x_d^2 / l^2, ArdLinear sum_d x_d^2 nh_d with the operations of gram_accumulate<3> (ascending d)
+template <class Int>      // index type of the caller (int or int64_t), so that the address arithmetic is the one it had inline
+__device__ __forceinline__ double prior_var(const KParam& p, const double* X, Int r, Int ld, int D) {
+    double kss;
+    if (p.kind == 0 || p.kind >= 4) kss = p.sigma2;
+    else if (p.kind == 1) kss = p.sigma2 * (double)D;
+    else if (p.kind == 2) {
+        double q = 0.0;
+        for (int d = 0; d < D; ++d) {
+            const double x = X[r + (size_t)d * ld];
+            q = fma(x, x, q);
+        }
+        kss = q / p.l2[0];
+    } else {
+        kss = 0.0;
+        for (int d = 0; d < D; ++d) {
+            const double x = X[r + (size_t)d * ld];
+            kss = fma(x * x, p.nh[d], kss);
+        }
+    }
+    return kss;
+}
+
 // mu = m + macc, var = k(x*,x*) + noise - sacc for the rows whose moments were accumulated by the sweep
 __global__ __launch_bounds__(128) void pred_finish_kernel(const LeafDev* __restrict__ leaves, const PredTask* __restrict__ tasks,
                                                           const KParam* __restrict__ kp, int D) {
@@ -2657,23 +2639,7 @@ __global__ __launch_bounds__(128) void pred_finish_kernel(const LeafDev* __restr
     const KParam p = kp[lf.kid];
     const int r = tk.row0 + threadIdx.x;
     if (r >= lf.nt) return;
-    double kss;
-    if (p.kind == 0 || p.kind >= 4) kss = p.sigma2;      // IsoSE, ArdSEProduct, Matern: k(x, x) = sigma^2
-    else if (p.kind == 1) kss = p.sigma2 * (double)D;
-    else if (p.kind == 2) {
-        double q = 0.0;
-        for (int d = 0; d < D; ++d) {
-            const double x = lf.Xtg[r + (size_t)d * lf.ntpad];
-            q = fma(x, x, q);
-        }
-        kss = q / p.l2[0];
-    } else {
-        kss = 0.0;          // ArdLinear: k(x*, x*) with the operations of gram_accumulate<3>
-        for (int d = 0; d < D; ++d) {
-            const double x = lf.Xtg[r + (size_t)d * lf.ntpad];
-            kss = fma(x * x, p.nh[d], kss);
-        }
-    }
+    const double kss = prior_var(p, lf.Xtg, r, lf.ntpad, D);
     lf.mu[r] = lf.mean + lf.macc[r];
     lf.var[r] = (kss - lf.sacc[r]) + p.noise;
 }
@@ -2695,23 +2661,7 @@ __global__ __launch_bounds__(256) void pred_var_kernel(const LeafDev* __restrict
     }
     block_reduce_store(s, red, t);
     if (t < TB && tk.row0 + t < lf.nt) {
-        double kss;
-        if (p.kind == 0 || p.kind >= 4) kss = p.sigma2;      // IsoSE, ArdSEProduct, Matern: k(x, x) = sigma^2
-        else if (p.kind == 1) kss = p.sigma2 * (double)D;
-        else if (p.kind == 2) {
-            double q = 0.0;
-            for (int d = 0; d < D; ++d) {
-                const double x = lf.Xtg[tk.row0 + t + (size_t)d * lf.ntpad];
-                q = fma(x, x, q);
-            }
-            kss = q / p.l2[0];
-        } else {
-            kss = 0.0;      // ArdLinear (gram_accumulate<3>)
-            for (int d = 0; d < D; ++d) {
-                const double x = lf.Xtg[tk.row0 + t + (size_t)d * lf.ntpad];
-                kss = fma(x * x, p.nh[d], kss);
-            }
-        }
+        const double kss = prior_var(p, lf.Xtg, tk.row0 + t, lf.ntpad, D);
         lf.var[tk.row0 + t] = (kss - red[t]) + p.noise;
     }
 }
@@ -2894,24 +2844,7 @@ __global__ __launch_bounds__(256) void agg_finish_kernel(const double* __restric
         var_out[r] = plain ? sv : sv + (m2 - m * m);              // src/common.jl:299-300
     } else if (family == AGG_RBCM) {
         const KParam p = kp[prior_kid];
-        double kss;
-        if (p.kind == 0 || p.kind >= 4) kss = p.sigma2;      // IsoSE, ArdSEProduct, Matern: k(x, x) = sigma^2
-        else if (p.kind == 1) kss = p.sigma2 * (double)D;
-        else if (p.kind == 2) {
-            double q = 0.0;
-            for (int d = 0; d < D; ++d) {
-                const double x = Xt[r + (size_t)d * n_t];
-                q = fma(x, x, q);
-            }
-            kss = q / p.l2[0];
-        } else {
-            kss = 0.0;      // ArdLinear (gram_accumulate<3>)
-            for (int d = 0; d < D; ++d) {
-                const double x = Xt[r + (size_t)d * n_t];
-                kss = fma(x * x, p.nh[d], kss);
-            }
-        }
-        const double s = kss + p.noise;
+        const double s = prior_var(p, Xt, r, n_t, D) + p.noise;
         double C = 1.0 / s, m = 0.0;
         for (int g = 0; g < G; ++g) {
             const double T = part[(size_t)(2 * g + 1) * n_t + r];

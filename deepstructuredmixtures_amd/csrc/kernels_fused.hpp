@@ -123,7 +123,7 @@ __device__ __forceinline__ void rowsplit_gram_init(int gna, int gnb, const KPara
             for (int i = 0; i < NRW; ++i) a[i] = pa[d * TB + 16 * i];
 #pragma unroll
             for (int j = 0; j < NJ; ++j) b[j] = pb[d * TB + 16 * (j >> 2) + 4 * (j & 3)];
-            gram_accumulate<KIND, NRW, NJ>(z, a, b, (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? AS_CONST_F64(p.nh)[d] : 0.0);
+            gram_accumulate<KIND, NRW, NJ>(z, a, b, kind_reads_nh(KIND) ? AS_CONST_F64(p.nh)[d] : 0.0);
         }
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -243,19 +243,9 @@ __device__ __forceinline__ void tile_fused8_body(const FusedTask8* __restrict__ 
         if (active) {
             const int gna = 16 * w + rb.nvalid;     // rowsplit_gram_init counts rows from the top of the 128-row image
             if (rb.nvalid == 16 && gnb >= 16 * NCB) {       // no padding rows or columns in this wave's blocks (wave-uniform)
-                if (p.kind == 0) rowsplit_gram_init<0, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
-                else if (p.kind == 1) rowsplit_gram_init<1, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
-                else if (p.kind == 2) rowsplit_gram_init<2, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
-                else if (p.kind == 3) rowsplit_gram_init<3, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
-                else if (p.kind == 4) rowsplit_gram_init<4, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
-                else if (p.kind >= 5) rowsplit_gram_init<5, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb);
+                DSMGP_KIND_DISPATCH(p.kind, K, rowsplit_gram_init<K, 1, NCB, false>(gna, gnb, p, D, acc, sa, sb));
             } else {
-                if (p.kind == 0) rowsplit_gram_init<0, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
-                else if (p.kind == 1) rowsplit_gram_init<1, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
-                else if (p.kind == 2) rowsplit_gram_init<2, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
-                else if (p.kind == 3) rowsplit_gram_init<3, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
-                else if (p.kind == 4) rowsplit_gram_init<4, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
-                else if (p.kind >= 5) rowsplit_gram_init<5, 1, NCB>(gna, gnb, p, D, acc, sa, sb);
+                DSMGP_KIND_DISPATCH(p.kind, K, rowsplit_gram_init<K, 1, NCB>(gna, gnb, p, D, acc, sa, sb));
             }
         }
         __syncthreads();    // the coordinates are no longer read: the ring takes the operand chunks
@@ -551,7 +541,7 @@ __device__ __forceinline__ void syrk_gram_inplace(const TileTask& tk, const KPar
                 double z[1][NE] = {};
 #pragma unroll 1
                 for (int d = 0; d < D; ++d) {
-                    const double nhd = (KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5) ? AS_CONST_F64(p.nh)[d] : 0.0;
+                    const double nhd = kind_reads_nh(KIND) ? AS_CONST_F64(p.nh)[d] : 0.0;
                     double a[1], b[NE];
                     a[0] = sa[d * TB + 16 * rbk[i] + l15];
 #pragma unroll
@@ -869,11 +859,7 @@ __device__ __forceinline__ void diag_fused_reg(const TileTask& tt, const DiagTas
             for (int r = 0; r < 4; ++r)
                 acc[i][r] = (diagr_rb(W, i) == diagr_cb(W, i) && (int)(threadIdx.x & 15) == (int)((threadIdx.x & 63) >> 4) + 4 * r) ? 4.0 : 0.0;
     } else if constexpr (MATERN) syrk_gram_inplace<SHAPE, 5>(tt, p, D, acc, blk, S);
-    else if (p.kind == 0) syrk_gram_inplace<SHAPE, 0>(tt, p, D, acc, blk, S);
-    else if (p.kind == 1) syrk_gram_inplace<SHAPE, 1>(tt, p, D, acc, blk, S);
-    else if (p.kind == 2) syrk_gram_inplace<SHAPE, 2>(tt, p, D, acc, blk, S);
-    else if (p.kind == 3) syrk_gram_inplace<SHAPE, 3>(tt, p, D, acc, blk, S);
-    else if (p.kind == 4) syrk_gram_inplace<SHAPE, 4>(tt, p, D, acc, blk, S);
+    else DSMGP_KIND_DISPATCH_NON_MATERN(p.kind, K, syrk_gram_inplace<SHAPE, K>(tt, p, D, acc, blk, S));
     __syncthreads();                                        // the coordinates are no longer read: panel and rhs take their place
     diag_reg_body<W>(d, acc, S);
 }
