@@ -586,6 +586,9 @@ struct dsmgp_ctx {
     DevBuf<GramTask> pgram0;        // ... of the joint fit when the Gram is fused: block column 0 only
     DevBuf<PredTask> ptasks;
     SweepLists psweep;              // V^T = K_tn L^-T; in the block steps that run fused: update + solve of eight 16-row blocks per task
+    double* arenaCov = nullptr;     // ntpad x ntpad of the leaf dsmgp_predict_cov was last asked for (grow-only, allocated on first use,
+    size_t cap_Cov = 0;             //   from the pool when there is one; goes with the test set: free_test).  Not part of bytes_needed.
+    DevBuf<PredCovTask> pcov;       // its lower tiles, rebuilt per call
     bool test_ready = false;
     bool predicted = false;
     int64_t route_total = 0;
@@ -950,6 +953,9 @@ void free_test(dsmgp_ctx* c, bool keep) {
     c->ptasks_slow.drop(keep);
     c->psweep.drop(c, keep);
     c->psegs.drop(keep);
+    arena_put(c, c->arenaCov);
+    c->cap_Cov = 0;
+    c->pcov.drop(keep);
     for (auto& lane : c->phaseJ)
         for (auto& ph : lane) ph.drop(keep);
     for (auto& sl : c->slabJ) arena_put(c, sl);
@@ -3127,6 +3133,64 @@ int dsmgp_predict_leaves(dsmgp_ctx* c, const double* Xt, int64_t n_t, int32_t D,
     if (int rc = dsmgp_set_test(c, Xt, n_t, D, route_ptr, route_idx)) return rc;
     if (int rc = dsmgp_predict_run(c, nullptr)) return rc;
     return dsmgp_predict_fetch(c, mu_out, var_out);
+}
+
+// Sigma = K_tt - V^T V (+ noise I) of one leaf over its routed rows: the lower tiles of Vt Vt^T on the matrix cores with the
+// kernel function in the epilogue (tile_predcov_kernel), mirrored by the same kernel.  Reads Vt only: after dsmgp_predict_run
+// it holds K_tn L^-T for every leaf and every real column, whether the rows went through the standalone sweep or rode through
+// the factorisation -- each block step of either reads all earlier block columns of Vt as its operand, and the leaves whose
+// moments are finished late (pred_mu_kernel / pred_var_kernel) are finished from those stored rows.
+int dsmgp_predict_cov(dsmgp_ctx* c, int32_t leaf, int32_t with_noise, double* Sigma_out, int64_t ld, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->predicted || !c->vt_valid) return fail(c, DSMGP_E_STATE, "predict_cov before predict_run on the current fit");
+    if (leaf < 0 || leaf >= c->L) return fail(c, DSMGP_E_ARG, "predict_cov: leaf out of range");
+    const LeafHost& lf = c->leaves[leaf];
+    if (lf.nt == 0) return 0;
+    if (!Sigma_out || ld < lf.nt) return fail(c, DSMGP_E_ARG, "predict_cov: Sigma_out is NULL or ld < nt");
+    HIPCHK(c, hipSetDevice(c->device));
+    const LeafDev& d = c->h_leaves[leaf];
+    const int ntp = lf.ntpad, nbt = ntp / TB;
+    if (int rc = slab_grow(c, c->arenaCov, c->cap_Cov, (size_t)ntp * ntp)) return rc;
+    std::vector<PredCovTask> tasks;
+    tasks.reserve((size_t)nbt * (nbt + 1) / 2);
+    // row tile by row tile, the tiles of one row next to each other: they share their A panel
+    for (int i = 0; i < nbt; ++i)
+        for (int j = 0; j <= i; ++j) {
+            PredCovTask g{};
+            g.gemm.A = d.Vt + (size_t)i * TB;
+            g.gemm.B = d.Vt + (size_t)j * TB;
+            g.gemm.C = c->arenaCov + (size_t)i * TB + (size_t)j * TB * ntp;
+            g.gemm.lda = g.gemm.ldb = g.gemm.ldc = ntp;
+            g.gemm.k0 = 0;
+            g.gemm.k1 = lf.n - lf.n % KC2;
+            g.Ct = c->arenaCov + (size_t)j * TB + (size_t)i * TB * ntp;
+            g.xa = d.Xtg + (size_t)i * TB;
+            g.xb = d.Xtg + (size_t)j * TB;
+            g.ldx = ntp;
+            g.na = std::min(TB, lf.nt - i * TB);
+            g.nb = std::min(TB, lf.nt - j * TB);
+            g.diag = (i == j);
+            g.kid = lf.kid;
+            g.n = lf.n;
+            g.with_noise = with_noise ? 1 : 0;
+            tasks.push_back(g);
+        }
+    c->stage_top = 0;       // (the stream is idle: every entry point synchronises before it returns)
+    if (int rc = stage_upload_list(c, c->pcov, tasks)) return rc;
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    tile_predcov_kernel<<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->pcov.p, c->d_kp.p, c->D);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(Sigma_out, (size_t)ld * sizeof(double), c->arenaCov, (size_t)ntp * sizeof(double),
+                               (size_t)lf.nt * sizeof(double), (size_t)lf.nt, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = stage_done(c)) return rc;
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = ms * 1e-3;
+    return 0;
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -1607,6 +1607,112 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Full predictive covariance of one leaf (prediction(gp, xtest), src/gaussianprocess.jl:110-137):
+//   Sigma = K_tt - V^T V (+ noise I),  V^T = K_tn L^-T = LeafDev::Vt (ntpad x npad, ld = ntpad) after the sweep.
+// One workgroup per lower 128 x 128 tile (i, j), i >= j: the product of row tile i with row tile j of the one column-major
+// matrix Vt through gemm_mainloop_v2, as the contraction of the gradient pass runs it on L^-T, then k(x*_r, x*_c) per
+// accumulator element with the arithmetic of the Gram tiles (gram_accumulate / gram_finish) from the gathered test inputs.
+//   * The sum runs over the n real columns of Vt only: the main loop takes [0, n - n % 8) (its chunks are 8 columns), the
+//     epilogue adds the last n % 8 columns with plain fmas.  What columns n..npad of Vt hold never enters.
+//   * The padding rows of Vt (nt..ntpad) are not cleared by the sweep: an accumulator element depends on its own two rows
+//     only, and rows / columns >= nt are not stored.
+//   * Only entries r >= c are computed-and-stored; every entry below the diagonal is also stored at its mirror position, so
+//     Sigma[r, c] and Sigma[c, r] are the same bits by construction.
+struct PredCovTask {
+    TileTask gemm;          // A = Vt row tile i, B = Vt row tile j, K range [0, n - n % 8); C = tile (i, j) of Sigma, ldc
+    double* Ct;             // tile (j, i) of Sigma: the mirror (== gemm.C on the block diagonal)
+    const double* xa;       // gathered test inputs of the rows (tile i), ld = ldx
+    const double* xb;       // ... of the columns (tile j)
+    int ldx;
+    int na, nb;             // valid rows / columns
+    int diag;               // tile on the block diagonal
+    int kid;
+    int n;                  // real columns of Vt: the epilogue sums columns [gemm.k1, n)
+    int with_noise;         // + noise on the diagonal
+    int pad;
+};
+
+template <int KIND>
+__device__ __forceinline__ void predcov_epilogue(const PredCovTask& g, const KParam& p, int D, d4 (&acc)[4][4], double* xs) {
+    const int t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+    constexpr int CH = GRADDOT_STAGE_D;
+    const int nch = (D + CH - 1) / CH;
+    const size_t ldc = (size_t)g.gemm.ldc;
+    const double dadd = g.with_noise ? p.noise : 0.0;
+#pragma unroll
+    for (int rn = 0; rn < 4; ++rn) {
+        const int r = wr * 64 + 16 * rn + l15;
+        double z[1][16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) z[0][i] = 0.0;
+        // coordinates in rounds of CH dimensions through the ring (one round for all four row groups when D fits at once)
+        for (int ch = 0; ch < nch; ++ch) {
+            const int d0 = ch * CH, dn = min(CH, D - d0);
+            if (nch > 1 || rn == 0) {
+                __syncthreads();
+                for (int e = t; e < dn * 256; e += 256) {
+                    const int d = e >> 8, rc = e & 255;
+                    xs[e] = (rc < TB) ? ((rc < g.na) ? g.xa[rc + (size_t)(d0 + d) * g.ldx] : 0.0)
+                                      : ((rc - TB < g.nb) ? g.xb[rc - TB + (size_t)(d0 + d) * g.ldx] : 0.0);
+                }
+                __syncthreads();
+            }
+            for (int d = 0; d < dn; ++d) {
+                const double a[1] = {xs[d * 256 + r]};
+                const double* xb = xs + d * 256 + TB + wc * 64 + l4;
+                double b[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) b[i] = xb[16 * (i >> 2) + 4 * (i & 3)];
+                gram_accumulate<KIND, 1, 16>(z, a, b, kind_reads_nh(KIND) ? p.nh[d0 + d] : 0.0);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+            const bool low = g.diag ? (r >= c) : true;
+            if (r < g.na && c < g.nb && low) {
+                double v = gram_finish<KIND, false>(z[0][i], p, r, c, g.na, g.nb, false) - acc[i >> 2][rn][i & 3];
+                if (g.diag && r == c) v += dadd;
+                AS_GLOBAL_F64(g.gemm.C)[r + (size_t)c * ldc] = v;
+                if (!g.diag || r != c) AS_GLOBAL_F64(g.Ct)[c + (size_t)r * ldc] = v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void tile_predcov_kernel(const PredCovTask* __restrict__ tasks,
+                                                              const KParam* __restrict__ kp, int D) {
+    __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
+    static_assert(GRADDOT_STAGE_D * 256 <= 2 * NRING * KC2 * LDP, "a round of coordinates fits the ring");
+    double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
+    double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
+    const PredCovTask g = tasks[blockIdx.x];
+    const KParam p = kp[g.kid];
+    d4 acc[4][4];
+    gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);      // ends on a barrier: the ring is free
+    if (g.gemm.k1 < g.n) {      // the last n % 8 columns (the main loop's chunks are whole)
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+        for (int k = g.gemm.k1; k < g.n; ++k) {
+            const double* ca = g.gemm.A + (size_t)k * g.gemm.lda + wr * 64 + l15;
+            const double* cb = g.gemm.B + (size_t)k * g.gemm.ldb + wc * 64 + l4;
+            double a[4], b[16];
+#pragma unroll
+            for (int rn = 0; rn < 4; ++rn) a[rn] = ca[16 * rn];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) b[i] = cb[16 * (i >> 2) + 4 * (i & 3)];
+#pragma unroll
+            for (int rn = 0; rn < 4; ++rn)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i >> 2][rn][i & 3] = fma(a[rn], b[i], acc[i >> 2][rn][i & 3]);
+        }
+    }
+    DSMGP_KIND_DISPATCH(p.kind, K, predcov_epilogue<K>(g, p, D, acc, smem));
+}
+
 // trace(K_y^-1) = |L^-1|_F^2 without forming K_y^-1: sum of squares of one row tile of Xt (columns >= its block)
 struct FrobTask {
     const double* X;   // Xt + row0

@@ -51,6 +51,7 @@ SIGNATURES = {
     "dsmgp_predict_run": (C.c_int, [_ctx, _dp]),
     "dsmgp_predict_fetch": (C.c_int, [_ctx, _dp, _dp]),
     "dsmgp_predict_leaves": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, _lp, _lp, _dp, _dp]),
+    "dsmgp_predict_cov": (C.c_int, [_ctx, C.c_int32, C.c_int32, _dp, C.c_int64, _dp]),
     "dsmgp_gradients": (C.c_int, [_ctx, _dp, C.c_int32]),
     "dsmgp_set_gradient_leaves": (C.c_int, [_ctx, _ip]),
     "dsmgp_set_option": (C.c_int, [_ctx, C.c_int32, C.c_int32]),
@@ -307,6 +308,18 @@ class Context:
         self.set_test(Xt, route_ptr, route_idx)
         self.predict_run()
         return self.predict_fetch()
+
+    def predict_cov(self, leaf, nt, with_noise=True):
+        """Full predictive covariance of leaf `leaf` over its `nt` routed test rows, in route order (needs `predict_run` on the
+        current fit): Sigma = K_tt - V'V (+ noise I), an (nt, nt) float64 array in Fortran order, symmetric to the bit.  `nt` is
+        the leaf's routed row count (`route_ptr[leaf + 1] - route_ptr[leaf]`); a smaller one is refused (E_ARG).  The device time
+        of the call is left in `self.cov_seconds`."""
+        nt = int(nt)
+        S = np.empty((nt, nt), dtype=np.float64, order="F")
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_predict_cov(self.h, int(leaf), 1 if with_noise else 0, S.ctypes.data_as(_dp), nt, C.byref(sec)))
+        self.cov_seconds = sec.value
+        return S
 
     def set_option(self, option, value):
         """include/dsmgp_hip.h DSMGP_OPT_*: OPT_ARD_LENGTHSCALE_GRADIENT = 1, OPT_FUSED_GRAM = 2, OPT_FUSED_STEPS = 3."""
@@ -699,6 +712,10 @@ class MultiContext:
         self.predict_run()
         return self.predict_fetch()
 
+    def predict_cov(self, leaf, nt, with_noise=True):
+        raise DsmgpError(E_STATE, "predict_cov: the full covariance of a leaf is served by a single Context only "
+                                  "(MultiContext spreads the leaf table over several devices)")
+
     def aggregate_partial(self, family, leaf_coef=None, leaf_group=None, n_groups=0):
         """Partial sums of all sub-contexts added in context order (the sums are linear in the leaves)."""
         coef = None if leaf_coef is None else np.asarray(leaf_coef, dtype=np.float64)
@@ -1044,6 +1061,10 @@ class StreamingContext:
 
     def predict_fetch(self):
         return self._res["mu"], self._res["var"]
+
+    def predict_cov(self, leaf, nt, with_noise=True):
+        raise DsmgpError(E_STATE, "predict_cov: a streaming pass discards K_tn L^-T with its leaf group; "
+                                  "use a resident Context for the full covariance of a leaf")
 
     def predict_leaves(self, Xt, route_ptr, route_idx):
         self.set_test(Xt, route_ptr, route_idx)

@@ -22,6 +22,7 @@ from .kernels import (IsoSE, ConstMean, KIND_ISO_SE, KIND_ARD_SE, KIND_ISO_LINEA
 from .tree import (DSMGPConfig, GPSumNode, build_tree, get_leaves, get_overlap, obs_table, share_schedule, share_decisions,
                    share_census, route, route_all, route_index, get_child, ordered_nodes, SHARE_COPY, SHARE_FULL, SHARE_PREFIX)
 from . import dist as _dist
+from . import datagen as _datagen
 
 EPS = 1e-8  # `const ϵ` of src/DeepStructuredMixtures.jl:27
 
@@ -383,17 +384,68 @@ def update_cholesky(gp):
     return gp
 
 
-def prediction(gp, xtest):
+def prediction(gp, xtest, full_cov=False):
     """`prediction(gp, xtest)` -> (mu, diag of Sigma) (`src/gaussianprocess.jl:110-137`; only the
-    diagonal of Sigma is ever consumed, `src/common.jl:136,147`)."""
+    diagonal of Sigma is ever consumed, `src/common.jl:136,147`).  `full_cov=True` -> (mu, Sigma) as the reference returns
+    them: the full n_t x n_t matrix K_tt - V'V + noise I from the device (`Context.predict_cov`), symmetric to the bit."""
     xt = _test_matrix(gp.model, xtest)
     if xt.shape[0] == 0:
-        return np.zeros(0), np.zeros(0)
+        return np.zeros(0), (np.zeros((0, 0)) if full_cov else np.zeros(0))
     # registered like the test set of a tree model (cached by content): a loop of update_cholesky! + prediction on the same
     # rows carries them through the factorisation launches from its second pass on, and prediction only finishes the moments
     rc = _routing(gp.model, xt)
     mu, var = _leaf_moments(gp.model, xt, rc)
+    if full_cov:
+        return mu, gp.model.ctx.predict_cov(0, xt.shape[0], True)
     return mu, var
+
+
+def leaf_covariance(model, xtest, leaf, with_noise=True):
+    """(rows, Sigma) of one leaf of a tree model: the rows of `xtest` routed to leaf `leaf` (ascending) and their joint
+    predictive covariance under that leaf's GP, K_tt - V'V (+ noise I), from the device.  Leaf level only: the joint law of
+    a mixture over several leaves is not Gaussian and is not what the reference computes.  Single rank, or the owning rank of
+    the leaf: with `shard.world > 1` a leaf another rank holds raises NotImplementedError."""
+    if isinstance(model, GaussianProcess):
+        model = model.model
+    leaf = int(leaf)
+    if not 0 <= leaf < model.L:
+        raise ValueError(f"leaf {leaf}: the model has {model.L} leaves")
+    local = [int(g) for g in model.shard.local]
+    if model.shard.world > 1 and leaf not in local:
+        raise NotImplementedError(f"leaf {leaf} is held by another rank: leaf_covariance serves this rank's leaves only")
+    xt = _test_matrix(model, xtest)
+    rc = _routing(model, xt)
+    rows = np.asarray(rc["idx"][rc["ptr"][leaf]:rc["ptr"][leaf + 1]], dtype=np.int64)
+    if rows.size == 0:
+        return rows, np.zeros((0, 0))
+    if not rc["uploaded"]:
+        model.ctx.set_test(xt, rc["lptr"], rc["lidx"])      # (host lists: the rows come back in THIS order)
+        rc["uploaded"] = True
+    model.last_predict_seconds = model.ctx.predict_run()
+    return rows, model.ctx.predict_cov(local.index(leaf), rows.size, with_noise)
+
+
+def posterior_sample(gp, xtest, n_samples, seed=0, with_noise=False):
+    """`n_samples` joint draws of a GaussianProcess at the rows of `xtest`: mu + chol(Sigma) eps, an (n_samples, n_t) array.
+    Sigma comes from the device (`Context.predict_cov`), the factorisation and the draws run on the host; eps is the
+    project's counter stream (`datagen.normal(seed, 0, n_t * n_samples)`, one column of n_t per sample).  Without noise the
+    module's EPS is added to the diagonal; np.linalg.LinAlgError if the Cholesky still fails."""
+    if not isinstance(gp, GaussianProcess):
+        raise TypeError("posterior_sample takes a GaussianProcess (the joint law of a mixture is not Gaussian)")
+    n_samples = int(n_samples)
+    if n_samples < 0:
+        raise ValueError("n_samples must not be negative")
+    mu, _ = prediction(gp, xtest)
+    nt = mu.size
+    if nt == 0:
+        return np.zeros((n_samples, 0))
+    S = gp.model.ctx.predict_cov(0, nt, with_noise)
+    if not with_noise:
+        d = np.arange(nt)
+        S[d, d] += EPS
+    Lc = np.linalg.cholesky(S)
+    eps = _datagen.normal(int(seed), 0, nt * n_samples).reshape((nt, n_samples), order="F")
+    return (mu[:, None] + Lc @ eps).T
 
 
 # ------------------------------------------------------------------------------------ fit

@@ -142,6 +142,15 @@ int dsmgp_predict_run(dsmgp_ctx* ctx, double* seconds);   /* device work only, i
 int dsmgp_predict_fetch(dsmgp_ctx* ctx, double* mu_out, double* var_out);
 int dsmgp_predict_leaves(dsmgp_ctx* ctx, const double* Xt, int64_t n_t, int32_t D, const int64_t* route_ptr,
                          const int64_t* route_idx, double* mu_out, double* var_out);
+/* prediction(gp, xtest) as the reference writes it (src/gaussianprocess.jl:110-137): the full covariance of leaf
+ * `leaf` over ITS routed test rows, in route order (the order of its segment of dsmgp_predict_fetch):
+ * Sigma = K_tt - V'V (+ exp(2 logNoise) I when with_noise != 0), nt x nt column-major with leading dimension ld >= nt.
+ * Needs dsmgp_predict_run on the current fit (DSMGP_E_STATE otherwise); leaf out of range or ld < nt: DSMGP_E_ARG;
+ * a leaf without routed rows: success, nothing written.  Symmetric to the bit.  seconds (may be NULL): device time.
+ * Its ntpad x ntpad device scratch (nt rounded up to 128) is allocated on first use -- from the reserved pool when there is
+ * one -- and is NOT counted by dsmgp_estimate_bytes / dsmgp_memory; it is dropped with the test set, the leaf table and
+ * dsmgp_release. */
+int dsmgp_predict_cov(dsmgp_ctx* ctx, int32_t leaf, int32_t with_noise, double* Sigma_out, int64_t ld, double* seconds);
 
 /* ---- predict(model, x): sum/product aggregation of the leaf moments over the leaves every test row visits, on the
  *      moments the last dsmgp_predict_run left in HBM (replaces the host recursions of src/common.jl:134-149,198-302).

@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52
+export attach!, detach!, census, predict_cov, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -424,6 +424,22 @@ function prediction(gp::GaussianProcess, xtest::AbstractMatrix)
         s.h, xt, nt, size(xt, 2), ptr, idx, μ, σ²))
     s.testkey = UInt(0)
     return μ, Diagonal(σ²)
+end
+
+"predict_cov(s, leaf; with_noise=true): the full Σ of prediction(gp, xtest) as the reference writes it (src/gaussianprocess.jl:110-137)
+for leaf `leaf` (1-based, the order of `s.leaves`) over ITS routed rows of the registered test set, in route order:
+K_tt − VᵀV (+ exp(2 logNoise) I), from dsmgp_predict_cov.  Needs a prediction on the current fit (dsmgp_predict_run); symmetric to
+the bit.  A leaf without routed rows gives a 0×0 matrix."
+function predict_cov(s::Session, leaf::Integer; with_noise::Bool=true)
+    ptr = Vector{Int64}(undef, length(s.leaves) + 1)
+    GC.@preserve ptr chk(s, ccall(sym(:dsmgp_routes), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), s.h, ptr, C_NULL))
+    nt = Int(ptr[leaf + 1] - ptr[leaf])
+    Σ = Matrix{Float64}(undef, nt, nt)
+    nt == 0 && return Σ
+    sec = Ref{Float64}(0.0)
+    GC.@preserve Σ chk(s, ccall(sym(:dsmgp_predict_cov), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int64, Ref{Float64}),
+                           s.h, Int32(leaf - 1), Int32(with_noise), Σ, nt, sec))
+    return Σ
 end
 
 # ---------------------------------------------------------------------------------------------- predict
