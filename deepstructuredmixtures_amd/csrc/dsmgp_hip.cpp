@@ -625,6 +625,18 @@ struct dsmgp_ctx {
     std::vector<int> grad_src;      // per leaf: the leaf whose contraction it shares (COPY leaf with the same mean), or -1
     DevBuf<double> d_gpart;         // partial results: frob | graddot pairs | per-leaf dots | ArdLinear quadratic forms (2 D per task)
     size_t gpart_count = 0;
+    // leave-one-out (dsmgp_loo): reads the same L^-T arena
+    bool xinv_all = false;          // arenaX holds L^-T of the CURRENT fit for EVERY factor owner: set by a sweep over lists that invert
+                                    // every owner (dsmgp_loo's; dsmgp_gradients' when no mask leaves an owner out), cleared by a fit, by
+                                    // a sweep over fewer owners, a new leaf table and dsmgp_release.  The arena outlives the lists.
+    bool grad_lists_all = false;    // the current lists invert every factor owner (build_grad_plan)
+    bool grad_all_owners = false;   // build_grad_plan: invert every owner whatever the mask says (set by dsmgp_loo around its own build)
+    std::vector<size_t> gxoff;      // per owner leaf: its offset in arenaX (build_grad_plan)
+    bool loo_ready = false;         // the two lists below point into the current arenaX / scratch (they depend on the leaf table only)
+    DevBuf<RowNormTask> lrow;
+    DevBuf<LooTask> lleaf;
+    DevBuf<double> d_loo;           // row-sum planes of every owner | mu | var (obs_ptr[L] each) | lpd (L).  Allocated on first use,
+                                    // dropped with the leaf table (free_grad); not part of bytes_needed
 
     // multi-GPU exchange over RCCL (dsmgp_comm_*, dsmgp_allgather): librccl.so is loaded on first use
     void* comm = nullptr;           // ncclComm_t
@@ -874,6 +886,11 @@ void free_grad(dsmgp_ctx* c) {
     c->gardlin.release();
     c->d_gpart.release();
     c->grad_ready = false;
+    c->xinv_all = false;
+    c->loo_ready = false;
+    c->lrow.release();
+    c->lleaf.release();
+    c->d_loo.release();
 }
 
 void free_tree(dsmgp_ctx* c) {
@@ -2505,6 +2522,7 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
     };
     c->vt_valid = false;
     c->alpha_valid = false;
+    c->xinv_all = false;
     // Replay the sequence as a graph while nothing inside it records events (profile 0); capture it on first use
     const int gk = joint ? 1 : 0;
     if (c->use_graph && c->profile == 0) {
@@ -3338,6 +3356,7 @@ int build_grad_plan(dsmgp_ctx* c) {
         if (int rc = arena_get(c, c->arenaX, xTot)) return rc;
         c->arenaX_count = xTot;
     }
+    c->gxoff = xoff;
     auto Xt = [&](int l) { return c->arenaX + xoff[c->leaves[l].owner]; };
     // Active leaves (dsmgp_set_gradient_leaves; default all).  A leaf's gradient needs tr K_y^-1 = |L^-1|_F^2 of its factor
     // owner and, for the kernels with a length-scale term, the contraction tiles -- its own, or its source's where a COPY leaf
@@ -3355,7 +3374,11 @@ int build_grad_plan(dsmgp_ctx* c) {
             needX[c->leaves[l].owner] = 1;
         }
     for (int l = 0; l < L; ++l)
-        if (needC[l]) needX[c->leaves[l].owner] = 1;
+        if (needC[l] || c->grad_all_owners) needX[c->leaves[l].owner] = 1;     // (dsmgp_loo reads L^-T of every owner)
+
+    c->grad_lists_all = true;
+    for (int l = 0; l < L; ++l)
+        if (c->leaves[l].owner == l && !needX[l]) c->grad_lists_all = false;
 
     std::vector<TransTask> trans;
     std::vector<FrobTask> frob;
@@ -3593,6 +3616,7 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     HIPCHK(c, e_inv.init());
     HIPCHK(c, e_dot.init());
     // Xt = L^-T (blocks left of the diagonal are never written and never read)
+    c->xinv_all = false;
     if (c->gtrans.count) transpose_tile_kernel<<<(int)c->gtrans.count * 16, 256, 0, c->stream>>>(c->gtrans.p);
     if (int rc = run_sweep(c, c->ginv, nullptr)) return rc;     // the lanes' streams wait for the transposes
     HIPCHK(c, hipEventRecord(e_inv.a, c->stream));
@@ -3619,6 +3643,8 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(t1, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->xinv_all = c->grad_lists_all;    // dsmgp_loo on this fit reads the arena as it is (this pass itself inverts on every call, as it
+                                        // always did); under a mask that leaves owners out, theirs is stale or rewritten by other lists
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, t0, t1));
     c->timings[10] = ms * 1e-3;
@@ -3720,6 +3746,107 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
         }
         g[nl + 1] = noise * (aa - trK[l]);                    // src/gaussianprocess.jl:176
     }
+    return 0;
+}
+
+// Leave-one-out moments of every leaf from the diagonal of K_y^-1 and alpha (GPML 5.4.2): d = rowsumsq of L^-T per factor
+// owner (rownorm_kernel: one task per 128-row tile and ROWNORM_COLS columns), then loo_moments_kernel per leaf.  L^-T comes from
+// the gradient pass's lists; it is built here unless the arena holds it for the current fit and for every owner.
+namespace {
+int build_loo_plan(dsmgp_ctx* c) {
+    const int L = c->L;
+    std::vector<size_t> poff(L, 0);
+    size_t pTot = 0;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.owner != l) continue;
+        poff[l] = pTot;
+        pTot += (size_t)lf.npad * ((lf.n + ROWNORM_COLS - 1) / ROWNORM_COLS);
+    }
+    const size_t nobs = (size_t)c->obs_ptr[L];
+    if (int rc = c->d_loo.alloc(c, pTot + 2 * nobs + (size_t)L)) return rc;
+    std::vector<RowNormTask> rows;
+    std::vector<LooTask> lt((size_t)L);
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        const LeafHost& ow = c->leaves[lf.owner];
+        lt[l].P = c->d_loo.p + poff[lf.owner];
+        lt[l].alpha = c->h_leaves[c->grad_src[l] >= 0 ? c->grad_src[l] : l].alpha;
+        lt[l].off = (long long)c->obs_ptr[l];
+        lt[l].ldp = ow.npad;
+        if (lf.owner != l) continue;
+        for (int t = 0; t * TB < lf.n; ++t)
+            for (int c0 = t * TB, k = 0; c0 < lf.n; c0 += ROWNORM_COLS, ++k) {
+                RowNormTask r{};
+                r.X = c->arenaX + c->gxoff[l] + (size_t)t * TB;
+                r.out = c->d_loo.p + poff[l] + (size_t)k * lf.npad + (size_t)t * TB;
+                r.ld = lf.npad;
+                r.col0 = c0;
+                r.col1 = std::min(c0 + ROWNORM_COLS, lf.n);
+                r.nrows = std::min(TB, lf.n - t * TB);
+                rows.push_back(r);
+            }
+    }
+    if (int rc = dev_upload(c, c->lrow, rows)) return rc;
+    if (int rc = dev_upload(c, c->lleaf, lt)) return rc;
+    c->loo_ready = true;
+    return 0;
+}
+}  // namespace
+
+int dsmgp_loo(dsmgp_ctx* c, double* mu_out, double* var_out, double* lpd_out, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->fitted) return fail(c, DSMGP_E_STATE, "loo before fit");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int L = c->L;
+    // L^-T of every factor owner.  Lists made under a mask (dsmgp_set_gradient_leaves) leave out the owners no active leaf needs:
+    // then the sweep runs over lists of this call's own, built for every owner and dropped again below, so that the next
+    // dsmgp_gradients builds the mask's lists as it would have without this call -- same launches, same bits.
+    struct OwnLists {       // (dropped on every way out, the failing ones too)
+        dsmgp_ctx* c;
+        bool on = false;
+        ~OwnLists() {
+            if (on) free_grad_lists(c);
+        }
+    } own_lists{c};
+    if (!c->xinv_all) {
+        if (c->grad_ready && !c->grad_lists_all) free_grad_lists(c);
+        if (!c->grad_ready) {
+            own_lists.on = !c->grad_active.empty();
+            c->grad_all_owners = true;
+            const int rc = build_grad_plan(c);
+            c->grad_all_owners = false;
+            if (rc) return rc;
+        }
+    }
+    if (!c->loo_ready)
+        if (int rc = build_loo_plan(c)) return rc;
+    EventPair ev;           // the device work of the call: what is left to complete of Dinv and alpha after this fit, the sweep, the two kernels
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    if (int rc = ensure_dinv(c)) return rc;
+    if (int rc = ensure_alpha(c)) return rc;
+    if (!c->xinv_all) {
+        if (c->gtrans.count) transpose_tile_kernel<<<(int)c->gtrans.count * 16, 256, 0, c->stream>>>(c->gtrans.p);
+        if (int rc = run_sweep(c, c->ginv, nullptr)) return rc;
+    }
+    const size_t nobs = (size_t)c->obs_ptr[L];
+    double* dmu = c->d_loo.p + (c->d_loo.count - 2 * nobs - (size_t)L);
+    double* dvar = dmu + nobs;
+    double* dlpd = dvar + nobs;
+    if (c->lrow.count) rownorm_kernel<<<(unsigned)c->lrow.count, 256, 0, c->stream>>>(c->lrow.p);
+    loo_moments_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->lleaf.p, c->d_obs_idx.p, c->dy.p, dmu, dvar, dlpd);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->xinv_all = true;
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = ms * 1e-3;
+    if (mu_out) HIPCHK(c, hipMemcpy(mu_out, dmu, nobs * sizeof(double), hipMemcpyDeviceToHost));
+    if (var_out) HIPCHK(c, hipMemcpy(var_out, dvar, nobs * sizeof(double), hipMemcpyDeviceToHost));
+    if (lpd_out) HIPCHK(c, hipMemcpy(lpd_out, dlpd, (size_t)L * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

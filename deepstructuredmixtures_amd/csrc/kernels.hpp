@@ -1741,6 +1741,52 @@ __global__ __launch_bounds__(256) void frob_kernel(const FrobTask* __restrict__ 
     if (t == 0) out[blockIdx.x] = red[0];
 }
 
+// Leave-one-out (dsmgp_loo): d_r = [K_y^-1]_rr = |column r of L^-1|^2 = the squares of ROW r of Xt from its block on --
+// frob_kernel's sums kept per row.  One task = one 128-row tile of Xt x ROWNORM_COLS columns, so that a single large leaf
+// (n = 4096: 32 row tiles) still fills the chip (272 tasks); out holds one 128-row slice per task, which loo_moments_kernel
+// adds in ascending column order.  A wave covers the 128 rows of a column with one 16 B load per lane (two rows each), the four
+// waves take the columns c = col0 + w (mod 4), four of them in flight per lane; partial sums meet in a fixed order.
+struct RowNormTask {
+    const double* X;   // Xt + row0 (16 B aligned: row0 and ld are multiples of 128)
+    double* out;       // 128 sums (rows >= nrows: 0)
+    int ld;
+    int col0, col1;    // column range (elements), col1 <= n: padding columns never enter
+    int nrows;         // valid rows in this tile
+};
+constexpr int ROWNORM_COLS = 256;
+
+__global__ __launch_bounds__(256) void rownorm_kernel(const RowNormTask* __restrict__ tasks) {
+    __shared__ double red[4][TB];
+    const RowNormTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const double* X = tk.X + 2 * lane;
+    double2 s[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] = make_double2(0.0, 0.0);
+    int c = tk.col0 + w;
+    for (; c + 12 < tk.col1; c += 16) {
+        double2 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const double2*>(X + (size_t)(c + 4 * j) * tk.ld);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            s[j].x = fma(v[j].x, v[j].x, s[j].x);
+            s[j].y = fma(v[j].y, v[j].y, s[j].y);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (c + 4 * j < tk.col1) {
+            const double2 v = *reinterpret_cast<const double2*>(X + (size_t)(c + 4 * j) * tk.ld);
+            s[j].x = fma(v.x, v.x, s[j].x);
+            s[j].y = fma(v.y, v.y, s[j].y);
+        }
+    red[w][2 * lane] = (s[0].x + s[1].x) + (s[2].x + s[3].x);
+    red[w][2 * lane + 1] = (s[0].y + s[1].y) + (s[2].y + s[3].y);
+    __syncthreads();
+    if (t < TB) tk.out[t] = t < tk.nrows ? (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]) : 0.0;
+}
+
 // Xt diagonal tiles: Xt[t,t] = Dinv_t^T
 struct TransTask {
     const double* src;   // 128x128, ld 128
@@ -2796,6 +2842,52 @@ __global__ __launch_bounds__(256) void dots_kernel(const LeafDev* __restrict__ l
         out[2 * blockIdx.x] = r1[0];
         out[2 * blockIdx.x + 1] = r2[0];
     }
+}
+
+// Leave-one-out moments of every leaf (GPML eqs. 5.10-5.12 with the mean and the hyper-parameters held fixed), one workgroup
+// per leaf:  d_i = [K_y^-1]_ii from the owner's row sums (rownorm_kernel, the slices of a row added in ascending column order),
+//   mu_i = y_i - alpha_i / d_i,  var_i = 1 / d_i,  lpd_i = -(log 2pi - log d_i + alpha_i^2 / d_i) / 2
+// (y_i - mu_i = alpha_i / d_i enters the density as it is: no difference of two rounded numbers).  lpd[leaf] = sum_i lpd_i:
+// thread t adds the rows t, t + 256, ..., then the tree of mll_kernel -- a fixed order.  A COPY leaf reads its source's sums and
+// its own alpha and y -- with its source's mean its alpha IS the source's (the rule of the gradients' grad_src), and that one
+// is read, so that the two leaves agree to the bit (a COPY leaf's own alpha comes from the forward sweep, its source's z from
+// the factorisation).  A leaf whose factorisation failed (info != 0) gets NaN throughout.
+struct LooTask {
+    const double* P;      // row sums of the factor owner: plane k (stride ldp) holds, for row tile t, the columns from 128 t + 256 k on
+    const double* alpha;  // the leaf's alpha, or its source's (COPY leaf with the same mean)
+    long long off;        // the leaf's first entry in obs_idx = its first slot in mu / var
+    int ldp;
+    int pad;
+};
+
+__global__ __launch_bounds__(256) void loo_moments_kernel(const LeafDev* __restrict__ leaves, const LooTask* __restrict__ tasks,
+                                                          const int64_t* __restrict__ obs_idx, const double* __restrict__ y,
+                                                          double* __restrict__ mu, double* __restrict__ var, double* __restrict__ lpd) {
+    __shared__ double red[256];
+    const LeafDev lf = leaves[blockIdx.x];
+    const LooTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x;
+    const bool bad = *lf.info != 0;
+    const double log2pi = 1.8378770664093454835606594728112;
+    const double qnan = __builtin_nan("");
+    double s = 0.0;
+    for (int i = t; i < lf.n; i += 256) {
+        const int nparts = (lf.n - (i & ~(TB - 1)) + ROWNORM_COLS - 1) / ROWNORM_COLS;
+        double d = 0.0;
+        for (int k = 0; k < nparts; ++k) d += tk.P[(size_t)k * tk.ldp + i];
+        const double a = tk.alpha[i];
+        const double q = a / d;
+        mu[tk.off + i] = bad ? qnan : y[obs_idx[tk.off + i]] - q;
+        var[tk.off + i] = bad ? qnan : 1.0 / d;
+        s += -0.5 * ((log2pi - log(d)) + a * q);
+    }
+    red[t] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+    if (t == 0) lpd[blockIdx.x] = bad ? qnan : red[0];
 }
 
 // ArdLinear length-scale gradients (dsmgp_gradients).  dK / dlog l_d = -2 x_d x_d^T / l_d^2 for k(a, b) = sum_d a_d b_d / l_d^2,

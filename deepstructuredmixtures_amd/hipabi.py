@@ -53,6 +53,7 @@ SIGNATURES = {
     "dsmgp_predict_leaves": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, _lp, _lp, _dp, _dp]),
     "dsmgp_predict_cov": (C.c_int, [_ctx, C.c_int32, C.c_int32, _dp, C.c_int64, _dp]),
     "dsmgp_gradients": (C.c_int, [_ctx, _dp, C.c_int32]),
+    "dsmgp_loo": (C.c_int, [_ctx, _dp, _dp, _dp, _dp]),
     "dsmgp_set_gradient_leaves": (C.c_int, [_ctx, _ip]),
     "dsmgp_set_option": (C.c_int, [_ctx, C.c_int32, C.c_int32]),
     "dsmgp_lanes": (C.c_int, [_ctx, _ip]),
@@ -186,6 +187,7 @@ class Context:
             self.h = None
             raise DsmgpError(rc, msg)
         self.L = 0
+        self.n_obs = 0          # obs_ptr[L] of the leaf table (set_leaves): the length of loo's outputs
         self.D = 0
         self.route_total = 0
         self.n_t = 0
@@ -225,6 +227,7 @@ class Context:
         L = len(obs_ptr) - 1
         self._chk(self.lib.dsmgp_set_leaves(self.h, L, p0, p1, p2, p3))
         self.L = L
+        self.n_obs = int(obs_ptr[-1])
 
     def set_sharing(self, op, src, plen):
         if op is None:
@@ -344,6 +347,20 @@ class Context:
         g = np.zeros((self.L, stride))
         self._chk(self.lib.dsmgp_gradients(self.h, g.ctypes.data_as(_dp), int(stride)))
         return g
+
+    def loo(self):
+        """Leave-one-out moments of every leaf on the current fit (dsmgp_loo; GPML eqs. 5.10-5.12, mean and hyper-parameters
+        held fixed): `(mu, var, lpd)` with `mu`, `var` of length `obs_ptr[L]` in the order of `obs_idx` (leaf l's rows at
+        `obs_ptr[l]:obs_ptr[l + 1]`) and `lpd[l]` the leaf's summed LOO log predictive density.  `var` carries the fit's 1e-8
+        jitter.  Leaves with `info != 0` come back as NaN.  Reuses L^-T when `gradients` or `loo` built it for this fit; the
+        device time of the call is left in `self.loo_seconds`."""
+        mu = np.empty(self.n_obs)
+        var = np.empty_like(mu)
+        lpd = np.empty(self.L)
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_loo(self.h, mu.ctypes.data_as(_dp), var.ctypes.data_as(_dp), lpd.ctypes.data_as(_dp), C.byref(sec)))
+        self.loo_seconds = sec.value
+        return mu, var, lpd
 
     # ---- predict(model, x) aggregation + scores on the device (src/common.jl:134-302, src/scorefunctions.jl) ----
     def _agg_args(self, family, leaf_coef, leaf_group):
@@ -740,6 +757,26 @@ class MultiContext:
             g[loc] = r
         return g
 
+    def loo(self):
+        """`Context.loo` per sub-context, put back into the order of the whole leaf table (leaves are independent);
+        `self.loo_seconds` is the longest of the sub-contexts' device times."""
+        self._upload()
+        res = self._each(lambda s: s.loo())
+        ptr = self._leaves[0]
+        mu = np.empty(int(ptr[-1]))
+        var = np.empty_like(mu)
+        lpd = np.empty(self.L)
+        for (m, v, d), loc in zip(res, self.part):
+            pos = 0
+            for g in loc:
+                c = int(ptr[g + 1] - ptr[g])
+                mu[ptr[g]:ptr[g + 1]] = m[pos:pos + c]
+                var[ptr[g]:ptr[g + 1]] = v[pos:pos + c]
+                pos += c
+            lpd[loc] = d
+        self.loo_seconds = max(s.loo_seconds for s in self.act)
+        return mu, var, lpd
+
     def timings(self):
         ts = [s.timings() for s in self.act]
         return {k: max(t[k] for t in ts) for k in ts[0]}
@@ -1081,6 +1118,10 @@ class StreamingContext:
             self.groups = None              # L^-1 doubles the footprint of a group
             self._pass()
         return self._res["grads"][:, :stride].copy()
+
+    def loo(self):
+        raise DsmgpError(E_STATE, "loo: a streaming pass discards the factors and L^-T with their leaf group; "
+                                  "use a resident Context for leave-one-out moments")
 
     def timings(self):
         return dict(self._res["timings"]) if self._res else {k: 0.0 for k in TIMING_NAMES}

@@ -1113,6 +1113,71 @@ def scores(model, y_test, mu=None, var=None):
     return dict(mse=mse(y_test, mu), sse=sse(y_test, mu), mae=mae(y_test, mu), sae=sae(y_test, mu), nlpd=nlpd(y_test, mu, var))
 
 
+# ------------------------------------------------------------------------------------ leave-one-out
+
+def loo(model):
+    """Leave-one-out cross-validation of every leaf GP on the current fit (GPML 5.4.2, eqs. 5.10-5.12; `dsmgp_loo`), the mean
+    and the hyper-parameters held fixed.  dict(obs, mu, var, lpd): per leaf, in the model's leaf order, `obs[l]` the leaf's
+    training rows, `mu[l]` / `var[l]` the moments at those rows of the leaf's GP fitted without the row (`var` with noise and
+    the fit's 1e-8 jitter), and `lpd[l]` the leaf's summed LOO log predictive density (an array of length L).  Works on a
+    `GaussianProcess` too (one leaf).  Needs a fit.  Single rank only: with `shard.world > 1` it raises NotImplementedError
+    (nothing is gathered)."""
+    target = model.model if isinstance(model, GaussianProcess) else model
+    if target.shard.world > 1:
+        raise NotImplementedError("loo: leave-one-out moments are served on a single rank only")
+    mu, var, lpd = target.ctx.loo()
+    ptr, idx = obs_table(target.leaves)
+    return dict(obs=[np.asarray(idx[ptr[l]:ptr[l + 1]], dtype=np.int64) for l in range(target.L)],
+                mu=[mu[ptr[l]:ptr[l + 1]] for l in range(target.L)],
+                var=[var[ptr[l]:ptr[l + 1]] for l in range(target.L)], lpd=lpd)
+
+
+def _loo_substitute(ptr, idx, mu, var, obs, mu_loo, var_loo):
+    """The per-(leaf, row) moments (CSR lists `ptr`, `idx` over the leaves; `mu`, `var` aligned with `idx`) with every entry
+    whose row is one of its leaf's observations `obs[l]` replaced by that observation's leave-one-out moments
+    (`mu_loo[l]`, `var_loo[l]`, aligned with `obs[l]`).  Entries of leaves that never saw the row are kept.  Returns copies."""
+    mu = np.array(mu, dtype=np.float64)
+    var = np.array(var, dtype=np.float64)
+    for l in range(len(ptr) - 1):
+        o = np.asarray(obs[l], dtype=np.int64)
+        if o.size == 0 or ptr[l + 1] == ptr[l]:
+            continue
+        rows = np.asarray(idx[ptr[l]:ptr[l + 1]], dtype=np.int64)
+        order = np.argsort(o, kind="stable")
+        pos = np.minimum(np.searchsorted(o[order], rows), o.size - 1)
+        hit = o[order][pos] == rows
+        src = order[pos[hit]]
+        mu[ptr[l]:ptr[l + 1]][hit] = np.asarray(mu_loo[l])[src]
+        var[ptr[l]:ptr[l + 1]][hit] = np.asarray(var_loo[l])[src]
+    return mu, var
+
+
+def loo_predict(model):
+    """(mu, var) per training row: `predict(model, model.x)` with, for every leaf that holds the row among its observations,
+    that leaf's leave-one-out moments in place of its ordinary ones; leaves that never saw the row keep their prediction.
+    The entries are aggregated by the model's own family rule on the host (the rules `predict` falls back to); tree weights
+    and hyper-parameters stay as they are.  Single rank only (NotImplementedError with `shard.world > 1`, as `loo`)."""
+    res = loo(model)
+    if isinstance(model, GaussianProcess):
+        model = model.model
+    xt = model.x
+    rc = _routing(model, xt)
+    mu, var = _leaf_moments(model, xt, rc)
+    mu, var = _loo_substitute(rc["ptr"], rc["idx"], mu, var, res["obs"], res["mu"], res["var"])
+    if model.family == "dsmgp":
+        if model.root.kind != "gp" and not model.tindex.weights_normalised():
+            return _aggregate_dsmgp(model, xt, rc["ptr"], mu, var)
+        return _aggregate_dsmgp_flat(model, xt.shape[0], rc, mu, var)
+    return _aggregate_poe(model, xt, rc["ptr"], mu, var)
+
+
+def loo_scores(model):
+    """dict(mse, sse, mae, sae, nlpd) of the training targets against `loo_predict(model)`."""
+    mu, var = loo_predict(model)
+    y = (model.model if isinstance(model, GaussianProcess) else model).y
+    return dict(mse=mse(y, mu), sse=sse(y, mu), mae=mae(y, mu), sae=sae(y, mu), nlpd=nlpd(y, mu, var))
+
+
 def _aggregate_dsmgp_flat(model, n_t, rc, mu, var):
     """The nested log-domain recursion of `_predict` (`src/common.jl:275-302`) is linear in the leaf quantities
     (mu - c, mu^2, sigma^2): unrolled, a test row's prediction is the flat mixture over the leaves it visits with

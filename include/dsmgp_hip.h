@@ -198,6 +198,31 @@ int dsmgp_gradients(dsmgp_ctx* ctx, double* grad_out, int32_t stride);
  * the overlap D[j, l] while it moves leaf j's vector (src/optimize.jl:101, src/finetuning.jl:34-57): all but the overlapping
  * leaves are multiplied by zero there.  Changing the set rebuilds the task lists of the gradient pass (the L^-T arena stays). */
 int dsmgp_set_gradient_leaves(dsmgp_ctx* ctx, const int32_t* active /* L flags, or NULL */);
+/* Leave-one-out cross-validation of every leaf GP (Rasmussen & Williams, GPML 5.4.2, eqs. 5.10-5.12), the mean and the
+ * hyper-parameters held fixed.  With K_y = K + (exp(2 logNoise) + 1e-8) I the matrix the fit factorises, d_i = [K_y^-1]_ii
+ * and alpha = K_y^-1 (y - m), for observation i of a leaf (the order of its segment of obs_idx):
+ *   mu_out[obs_ptr[l] + i]  = y_i - alpha_i / d_i   -- the mean at x_i of the same GP fitted without row i,
+ *   var_out[obs_ptr[l] + i] = 1 / d_i               -- its predictive variance there with noise, plus the 1e-8 jitter,
+ *   lpd_out[l] = sum_i -(log 2pi + log var_i + (y_i - mu_i)^2 / var_i) / 2   -- the leaf's LOO log predictive density,
+ * added in a fixed order: results are the same to the bit from call to call.  Any of the three may be NULL.
+ * Needs a fit (DSMGP_E_STATE otherwise).  d comes from L^-T of every factor owner, the arena dsmgp_gradients fills (same size,
+ * same DSMGP_E_NOMEM when it does not fit): it is read as it is when dsmgp_loo, or a dsmgp_gradients pass that inverted every
+ * owner, already filled it for the current fit, else filled here with the gradient pass's task lists.  dsmgp_gradients itself
+ * inverts on every call, as before, and this call changes nothing about it: under a mask of dsmgp_set_gradient_leaves that
+ * leaves owners out, the sweep runs over lists of this call's own (every owner) which are dropped before it returns, so the
+ * next dsmgp_gradients builds and runs the mask's lists exactly as without this call (same work, same bits; the price is one
+ * more build of those lists on the host).  The mask does not change the LOO results.  Because the lists are the gradient
+ * pass's, the call fails like dsmgp_gradients (DSMGP_E_ARG) where that cannot build them: ArdSE leaves with
+ * DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT = 1 and more input dimensions than the contraction stages.
+ * A COPY leaf takes its source's d and its own alpha, y and mean.  Leaves whose fit reported info != 0 get NaN in all three
+ * outputs; the others are unaffected.  seconds (may be NULL): device time of the call -- what is left to complete after this
+ * fit of the diagonal-block inverses and of alpha, the inversion when it runs, and the two LOO kernels (there is no
+ * dsmgp_timings slot for it).
+ * Its device scratch (the row sums of L^-T in slices, about 1/256 of the L^-T arena, and 2 obs_ptr[L] + L doubles) is
+ * allocated on first use and is NOT counted by dsmgp_estimate_bytes(with_gradients = 1) / dsmgp_memory, which cover the L^-T
+ * arena only; it is dropped with the leaf table and dsmgp_release. */
+int dsmgp_loo(dsmgp_ctx* ctx, double* mu_out, double* var_out /* obs_ptr[L] each, in obs_idx order; may be NULL */,
+              double* lpd_out /* L; may be NULL */, double* seconds /* may be NULL */);
 /* Options.  DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT: 0 (default) = ArdSE length-scale gradients exactly as the reference
  * computes them, i.e. identically zero (`precomp * K .* (p/ls[d])` parses as `(precomp*K) .* (p/ls[d])` and p has a zero
  * diagonal, src/kernels.jl:161: train!/finetune! never move ARD length-scales); 1 = the true derivative of the

@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, predict_cov, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52
+export attach!, detach!, census, predict_cov, loo, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -440,6 +440,25 @@ function predict_cov(s::Session, leaf::Integer; with_noise::Bool=true)
     GC.@preserve Σ chk(s, ccall(sym(:dsmgp_predict_cov), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int64, Ref{Float64}),
                            s.h, Int32(leaf - 1), Int32(with_noise), Σ, nt, sec))
     return Σ
+end
+
+"loo(s): leave-one-out cross-validation of every leaf GP on the current fit (GPML §5.4.2, eqs. 5.10–5.12; dsmgp_loo), mean and
+hyper-parameters held fixed.  Returns (μ, σ², lpd): per leaf, in the order of `s.leaves`, the moments at its own observations (in
+the order of its observation list) of the leaf's GP fitted without that observation — σ² with noise and the fit's 1e-8 jitter —
+and the leaf's summed LOO log predictive density.  Leaves whose fit reported info ≠ 0 come back as NaN.  L⁻ᵀ is reused when
+updategradients! or loo already built it for this fit."
+function loo(s::Session)
+    L = length(s.leaves)
+    cnt = [length(lf.obs) for lf in s.leaves]
+    tot = sum(cnt)
+    μ = Vector{Float64}(undef, tot)
+    σ² = Vector{Float64}(undef, tot)
+    lpd = Vector{Float64}(undef, L)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve μ σ² lpd chk(s, ccall(sym(:dsmgp_loo), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                                       s.h, μ, σ², lpd, sec))
+    off = cumsum(vcat(0, cnt))
+    return [μ[off[l]+1:off[l+1]] for l in 1:L], [σ²[off[l]+1:off[l+1]] for l in 1:L], lpd
 end
 
 # ---------------------------------------------------------------------------------------------- predict
