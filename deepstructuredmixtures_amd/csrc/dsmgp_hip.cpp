@@ -637,6 +637,21 @@ struct dsmgp_ctx {
     DevBuf<LooTask> lleaf;
     DevBuf<double> d_loo;           // row-sum planes of every owner | mu | var (obs_ptr[L] each) | lpd (L).  Allocated on first use,
                                     // dropped with the leaf table (free_grad); not part of bytes_needed
+    // gradients of the LOO density (dsmgp_loo_gradients): lists and arena built on first use, dropped with the leaf table (free_grad)
+    bool lg_ready = false;
+    std::vector<int> lg_kinds;      // kind of every kernel id the lists were built for (a change of kind rebuilds them)
+    double* arenaH = nullptr;       // H = K_y^-1 diag(sqrt w) per computing leaf, npad x npad
+    DevBuf<double> d_lgvec;         // [alpha | u | sqrt w | alpha / (d sqrt w)] per computing leaf, npad each
+    DevBuf<LooVecTask> lgvec;
+    DevBuf<GinvTask> lginv;
+    DevBuf<LooHvecTask> lghvec;
+    std::vector<int> lghvec_leaf;
+    DevBuf<GradTask> lgdot;         // as gdot: IsoSE / ArdSE | ArdSEProduct | Matern
+    size_t lgdot_prod0 = 0, lgdot_mat0 = 0;
+    std::vector<int> lgdot_leaf;
+    DevBuf<ArdLinTask> lgardlin;
+    std::vector<int> lgardlin_leaf;
+    DevBuf<double> d_lgpart;        // weights 2 L | hvec pairs | graddot x (2 + D) | ArdLinear 3 D per task
 
     // multi-GPU exchange over RCCL (dsmgp_comm_*, dsmgp_allgather): librccl.so is loaded on first use
     void* comm = nullptr;           // ncclComm_t
@@ -891,6 +906,15 @@ void free_grad(dsmgp_ctx* c) {
     c->lrow.release();
     c->lleaf.release();
     c->d_loo.release();
+    c->lg_ready = false;
+    arena_put(c, c->arenaH);
+    c->d_lgvec.release();
+    c->lgvec.release();
+    c->lginv.release();
+    c->lghvec.release();
+    c->lgdot.release();
+    c->lgardlin.release();
+    c->d_lgpart.release();
 }
 
 void free_tree(dsmgp_ctx* c) {
@@ -3626,19 +3650,19 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     const size_t np0 = c->gdot_prod0;     // tasks [np0, nm0): ArdSEProduct leaves
     const size_t nm0 = c->gdot_mat0;      // tasks [nm0, count): Matern leaves
     if (np0)
-        tile_graddot_kernel<<<(int)np0, 256, 0, c->stream>>>(c->gdot.p, c->d_kp.p, c->D, pdot, c->gstride);
+        tile_graddot_kernel<false><<<(int)np0, 256, 0, c->stream>>>(c->gdot.p, c->d_kp.p, c->D, pdot, c->gstride);
     if (nm0 > np0)
-        tile_graddot_prod_kernel<<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->gdot.p + np0, c->d_kp.p, c->D,
+        tile_graddot_prod_kernel<false><<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->gdot.p + np0, c->d_kp.p, c->D,
                                                                                pdot + (size_t)c->gstride * np0, c->gstride);
     if (c->gdot.count > nm0)
-        tile_graddot_matern_kernel<<<(int)(c->gdot.count - nm0), 256, 0, c->stream>>>(c->gdot.p + nm0, c->d_kp.p, c->D,
+        tile_graddot_matern_kernel<false><<<(int)(c->gdot.count - nm0), 256, 0, c->stream>>>(c->gdot.p + nm0, c->d_kp.p, c->D,
                                                                                          pdot + (size_t)c->gstride * nm0, c->gstride);
     HIPCHK(c, hipEventRecord(e_dot.a, c->stream));
     if (c->gfrob.count) frob_kernel<<<(int)c->gfrob.count, 256, 0, c->stream>>>(c->gfrob.p, pfrob);
     dots_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, pleaf);
     double* pardlin = pleaf + 2 * (size_t)L;
     if (c->gardlin.count)
-        ardlin_quad_kernel<<<dim3((unsigned)c->gardlin.count, (unsigned)((c->D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
+        ardlin_quad_kernel<false><<<dim3((unsigned)c->gardlin.count, (unsigned)((c->D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
             c->gardlin.p, c->D, pardlin);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(t1, c->stream));
@@ -3847,6 +3871,296 @@ int dsmgp_loo(dsmgp_ctx* c, double* mu_out, double* var_out, double* lpd_out, do
     if (mu_out) HIPCHK(c, hipMemcpy(mu_out, dmu, nobs * sizeof(double), hipMemcpyDeviceToHost));
     if (var_out) HIPCHK(c, hipMemcpy(var_out, dvar, nobs * sizeof(double), hipMemcpyDeviceToHost));
     if (lpd_out) HIPCHK(c, hipMemcpy(lpd_out, dlpd, (size_t)L * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Hyper-parameter gradients of the LOO log predictive density (GPML eq. 5.13; the kernels and the formulas: kernels.hpp at
+// loo_weights_kernel).  dsmgp_loo itself runs first -- L^-T of every owner, the row sums, lpd -- so lpd_out is its lpd_out to
+// the bit and everything that call promises about dsmgp_gradients and the mask holds here too; then the passes of this call's
+// own lists over an arena of their own.  Nothing the gradient pass or dsmgp_loo reads is written.
+namespace {
+int build_loo_grad_plan(dsmgp_ctx* c) {
+    const int L = c->L;
+    const int D = c->D;
+    std::vector<size_t> hoff(L, 0), voff(L, 0);
+    size_t hTot = 0, vTot = 0;
+    bool any_ardse = false;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        any_ardse = any_ardse || c->hyper[lf.kid].kind == DSMGP_KIND_ARD_SE;
+        if (c->grad_src[l] >= 0) continue;
+        hoff[l] = hTot;
+        voff[l] = vTot;
+        hTot += (size_t)lf.npad * lf.npad;
+        vTot += 4 * (size_t)lf.npad;
+    }
+    if (any_ardse && D > GRADDOT_STAGE_D)
+        return fail(c, DSMGP_E_ARG, "loo_gradients: ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
+    if (!c->arenaH) {
+        size_t freeB = 0, totalB = 0;
+        HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
+        if (!c->pool_base && hTot * sizeof(double) + (size_t(2) << 30) > freeB)
+            return fail(c, DSMGP_E_NOMEM, "loo_gradients need " + std::to_string((hTot * 8) >> 20) + " MiB for K_y^-1, device has " +
+                                              std::to_string(freeB >> 20) + " MiB free");
+        if (int rc = arena_get(c, c->arenaH, hTot)) return rc;
+    }
+    if (int rc = c->d_lgvec.alloc(c, vTot)) return rc;
+    auto H = [&](int l) { return c->arenaH + hoff[l]; };
+    auto V = [&](int l) { return c->d_lgvec.p + voff[l]; };
+    auto Xt = [&](int l) { return c->arenaX + c->gxoff[c->leaves[l].owner]; };
+
+    std::vector<LooVecTask> vt((size_t)L);
+    std::vector<LooHvecTask> hv;
+    c->lghvec_leaf.clear();
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        vt[l].npad = lf.npad;
+        vt[l].vec = c->grad_src[l] >= 0 ? nullptr : V(l);
+        if (c->grad_src[l] >= 0) continue;
+        for (int t = 0; t * TB < lf.n; ++t) {
+            LooHvecTask h{};
+            h.H = H(l);
+            h.vec = V(l);
+            h.ld = lf.npad;
+            h.n = lf.n;
+            h.row0 = t * TB;
+            h.nrows = std::min(TB, lf.n - t * TB);
+            hv.push_back(h);
+            c->lghvec_leaf.push_back(l);
+        }
+    }
+    // tiles of G, then of the contraction: the super-tile order and the XCD dealing of build_grad_plan.  `each_tile` lists the
+    // lower tiles (i, j) of a leaf in that order and marks the start of every block of GS tile rows.
+    constexpr int GS = 4;
+    auto each_tile = [&](const LeafHost& lf, std::vector<size_t>& gblock, size_t begin, auto&& size_now, auto&& emit) {
+        for (int ib = 0; ib < lf.nb; ib += GS) {
+            gblock.push_back(size_now() - begin);
+            for (int jb = 0; jb <= ib; jb += GS)
+                for (int i = ib; i < std::min(ib + GS, lf.nb); ++i)
+                    for (int j = jb; j < std::min(jb + GS, i + 1); ++j)
+                        emit(i, j, std::max(0, std::min(TB, lf.n - i * TB)), std::max(0, std::min(TB, lf.n - j * TB)));
+        }
+    };
+    auto deal = [&](auto& tasks, std::vector<int>& leaf_of, size_t begin, std::vector<size_t>& gblock) {
+        gblock.push_back(tasks.size() - begin);
+        std::vector<double> work(tasks.size() - begin);
+        for (size_t i = 0; i < work.size(); ++i) work[i] = (double)(tasks[begin + i].gemm.k1 - tasks[begin + i].gemm.k0) + 64.0;
+        xcd_deal_by_work(tasks, leaf_of, begin, tasks.size(), gblock, work, c->xcd_order);
+    };
+    std::vector<size_t> gblock;
+    std::vector<GinvTask> gi;
+    std::vector<int> gi_leaf;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (c->grad_src[l] >= 0) continue;
+        each_tile(lf, gblock, 0, [&] { return gi.size(); }, [&](int i, int j, int na, int nb) {
+            GinvTask g{};
+            g.gemm.A = Xt(l) + (size_t)i * TB;
+            g.gemm.B = Xt(l) + (size_t)j * TB;
+            g.gemm.C = H(l) + (size_t)i * TB + (size_t)j * TB * lf.npad;
+            g.Ct = H(l) + (size_t)j * TB + (size_t)i * TB * lf.npad;
+            g.gemm.lda = g.gemm.ldb = g.gemm.ldc = lf.npad;
+            g.gemm.k0 = i * TB;
+            g.gemm.k1 = lf.npad;
+            g.sw_a = V(l) + 2 * (size_t)lf.npad + (size_t)i * TB;
+            g.sw_b = V(l) + 2 * (size_t)lf.npad + (size_t)j * TB;
+            g.na = na;
+            g.nb = nb;
+            g.diag = (i == j);
+            gi.push_back(g);
+            gi_leaf.push_back(l);
+        });
+    }
+    deal(gi, gi_leaf, 0, gblock);
+    // the contraction, as gdot: IsoSE and ArdSE leaves (pass 0), ArdSEProduct (1), Matern (2), each run by its own kernel
+    std::vector<GradTask> gd;
+    c->lgdot_leaf.clear();
+    for (int pass = 0; pass < 3; ++pass) {
+        if (pass == 1) c->lgdot_prod0 = gd.size();
+        if (pass == 2) c->lgdot_mat0 = gd.size();
+        const size_t begin = gd.size();
+        gblock.clear();
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            if (c->grad_src[l] >= 0) continue;
+            const int kind_l = c->hyper[lf.kid].kind;
+            if (!KINDS[kind_l].contraction && kind_l != DSMGP_KIND_ARD_SE) continue;
+            if ((kind_l == DSMGP_KIND_ARD_SE_PRODUCT ? 1 : KINDS[kind_l].matern ? 2 : 0) != pass) continue;
+            const LeafDev& d = c->h_leaves[l];
+            each_tile(lf, gblock, begin, [&] { return gd.size(); }, [&](int i, int j, int na, int nb) {
+                GradTask g{};
+                g.gemm.A = H(l) + (size_t)i * TB;
+                g.gemm.B = H(l) + (size_t)j * TB;
+                g.gemm.C = nullptr;
+                g.gemm.lda = g.gemm.ldb = lf.npad;
+                g.gemm.ldc = TB;
+                g.gemm.k0 = 0;
+                g.gemm.k1 = lf.npad;
+                g.xa = d.Xg + (size_t)i * TB;
+                g.xb = d.Xg + (size_t)j * TB;
+                g.alpha_a = V(l) + (size_t)i * TB;
+                g.alpha_b = V(l) + (size_t)j * TB;
+                g.uoff = lf.npad;
+                g.ldx = lf.npad;
+                g.na = na;
+                g.nb = nb;
+                g.diag = (i == j);
+                g.kid = lf.kid;
+                gd.push_back(g);
+                c->lgdot_leaf.push_back(l);
+            });
+        }
+        deal(gd, c->lgdot_leaf, begin, gblock);
+    }
+    std::vector<ArdLinTask> al;
+    c->lgardlin_leaf.clear();
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR || c->grad_src[l] >= 0) continue;
+        for (int c0 = 0; c0 < lf.n; c0 += ARDLIN_COLS) {
+            ArdLinTask a{};
+            a.Xt = H(l);
+            a.x = c->h_leaves[l].Xg;
+            a.alpha = V(l);
+            a.ldt = lf.npad;
+            a.ldx = lf.npad;      // also the distance from alpha to u in the vector block (ardlin_quad_kernel<true>)
+            a.c0 = c0;
+            a.n = lf.n;
+            al.push_back(a);
+            c->lgardlin_leaf.push_back(l);
+        }
+    }
+    if (int rc = dev_upload(c, c->lgvec, vt)) return rc;
+    if (int rc = dev_upload(c, c->lghvec, hv)) return rc;
+    if (int rc = dev_upload(c, c->lginv, gi)) return rc;
+    if (int rc = dev_upload(c, c->lgdot, gd)) return rc;
+    if (int rc = dev_upload(c, c->lgardlin, al)) return rc;
+    if (int rc = c->d_lgpart.grow(c, 2 * (size_t)L + 2 * hv.size() + (size_t)(2 + D) * gd.size() + 3 * (size_t)D * al.size())) return rc;
+    c->lg_kinds.clear();
+    for (const HyperHost& h : c->hyper) c->lg_kinds.push_back(h.kind);
+    c->lg_ready = true;
+    return 0;
+}
+}  // namespace
+
+int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* lpd_out, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->fitted) return fail(c, DSMGP_E_STATE, "loo_gradients before fit");
+    if (!grad_out) return fail(c, DSMGP_E_ARG, "grad_out is NULL");
+    const int L = c->L;
+    const int D = c->D;
+    for (int l = 0; l < L; ++l)
+        if ((int)c->hyper[c->leaves[l].kid].loghyp.size() > stride)
+            return fail(c, DSMGP_E_ARG, "loo_gradients: stride smaller than the hyper-vector");
+    std::vector<double> lpd((size_t)L);
+    double sec_loo = 0.0;
+    if (int rc = dsmgp_loo(c, nullptr, nullptr, lpd.data(), &sec_loo)) return rc;
+    if (c->lg_ready) {
+        bool same = c->lg_kinds.size() == c->hyper.size();
+        for (size_t k = 0; same && k < c->hyper.size(); ++k) same = c->lg_kinds[k] == c->hyper[k].kind;
+        c->lg_ready = same;
+    }
+    if (!c->lg_ready)
+        if (int rc = build_loo_grad_plan(c)) return rc;
+    const int gs = 2 + D;
+    double* pw = c->d_lgpart.p;
+    double* ph = pw + 2 * (size_t)L;
+    double* pdot = ph + 2 * c->lghvec.count;
+    double* pal = pdot + (size_t)gs * c->lgdot.count;
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    loo_weights_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->lleaf.p, c->lgvec.p, pw);
+    if (c->lginv.count) tile_ginv_kernel<<<(unsigned)c->lginv.count, 256, 0, c->stream>>>(c->lginv.p);
+    if (c->lghvec.count) loo_hvec_kernel<<<(unsigned)c->lghvec.count, 256, 0, c->stream>>>(c->lghvec.p, ph);
+    const size_t np0 = c->lgdot_prod0, nm0 = c->lgdot_mat0, nd = c->lgdot.count;
+    if (np0) tile_graddot_kernel<true><<<(int)np0, 256, 0, c->stream>>>(c->lgdot.p, c->d_kp.p, D, pdot, gs);
+    if (nm0 > np0)
+        tile_graddot_prod_kernel<true><<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->lgdot.p + np0, c->d_kp.p, D, pdot + (size_t)gs * np0, gs);
+    if (nd > nm0)
+        tile_graddot_matern_kernel<true><<<(int)(nd - nm0), 256, 0, c->stream>>>(c->lgdot.p + nm0, c->d_kp.p, D, pdot + (size_t)gs * nm0, gs);
+    if (c->lgardlin.count)
+        ardlin_quad_kernel<true><<<dim3((unsigned)c->lgardlin.count, (unsigned)((D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
+            c->lgardlin.p, D, pal);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = sec_loo + ms * 1e-3;
+    std::vector<double> part(c->d_lgpart.count);
+    HIPCHK(c, hipMemcpy(part.data(), c->d_lgpart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    // host assembly: the task sums of a leaf are added in list order (fixed: bit-reproducible)
+    const double* hw = part.data();
+    const double* hh = hw + 2 * (size_t)L;
+    const double* hd = hh + 2 * c->lghvec.count;
+    const double* ha = hd + (size_t)gs * nd;
+    std::vector<double> frob(L, 0.0), ua(L, 0.0), S1(L, 0.0), SK(L, 0.0), Sd((size_t)L * D, 0.0);
+    for (size_t i = 0; i < c->lghvec.count; ++i) {
+        frob[c->lghvec_leaf[i]] += hh[2 * i];
+        ua[c->lghvec_leaf[i]] += hh[2 * i + 1];
+    }
+    for (size_t i = 0; i < nd; ++i) {
+        const size_t l = (size_t)c->lgdot_leaf[i];
+        S1[l] += hd[gs * i];
+        SK[l] += hd[gs * i + 1];
+        const int kind_l = c->hyper[c->leaves[l].kid].kind;      // IsoSE tasks write no per-dimension sums
+        if (kind_l == DSMGP_KIND_ARD_SE || KINDS[kind_l].per_dim_grad)
+            for (int d = 0; d < D; ++d) Sd[l * D + d] += hd[gs * i + 2 + d];
+    }
+    std::vector<double> A, U, Q;
+    if (c->lgardlin.count) {
+        A.assign((size_t)L * D, 0.0);
+        U = A;
+        Q = A;
+        for (size_t i = 0; i < c->lgardlin.count; ++i) {
+            const size_t l = (size_t)c->lgardlin_leaf[i];
+            for (int d = 0; d < D; ++d) {
+                A[l * D + d] += ha[3 * (size_t)D * i + d];
+                Q[l * D + d] += ha[3 * (size_t)D * i + D + d];
+                U[l * D + d] += ha[3 * (size_t)D * i + 2 * D + d];
+            }
+        }
+    }
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        const HyperHost& h = c->hyper[lf.kid];
+        const size_t s = (size_t)(c->grad_src[l] >= 0 ? c->grad_src[l] : l);      // a COPY leaf with its source's mean: the source's
+        const int nl = (int)h.loghyp.size() - 2;
+        const double noise = std::exp(2.0 * h.loghyp[nl + 1]);
+        const double cc = noise + 1e-8;
+        double* g = grad_out + (size_t)l * stride;
+        for (int j = 0; j < stride; ++j) g[j] = 0.0;
+        if (std::isnan(lpd[l])) {       // the fit of this leaf failed (info != 0)
+            for (int j = 0; j < nl + 2; ++j) g[j] = std::nan("");
+            continue;
+        }
+        const double trM = ua[s] - frob[s];                       // tr M = u . alpha - |H|_F^2
+        const double trMKy = hw[2 * s] - hw[2 * s + 1];           // tr(M K_y) = sum alpha_i^2 / d_i - sum w_i d_i
+        if (h.kind == DSMGP_KIND_ISO_SE) {
+            g[0] = S1[s] / std::exp(2.0 * h.loghyp[0]);           // dK / dlog l = K r^2 / l^2
+            g[1] = 2.0 * SK[s];                                   // dK / dlog sigma = 2 K, contracted directly
+        } else if (h.kind == DSMGP_KIND_ISO_LINEAR) {
+            g[0] = -2.0 * (trMKy - cc * trM);                     // dK / dlog l = -2 K; sum M K = tr(M K_y) - c tr M
+            g[1] = 0.0;
+        } else if (h.kind == DSMGP_KIND_ARD_LINEAR) {
+            for (int d = 0; d < nl; ++d)                          // x_d^T M x_d = (x_d . u)(x_d . alpha) - |H^T x_d|^2
+                g[d] = -2.0 * (U[s * D + d] * A[s * D + d] - Q[s * D + d]) / std::exp(2.0 * h.loghyp[d]);
+            g[nl] = 0.0;
+        } else {                                                  // ArdSE, ArdSEProduct, Matern: per-dimension sums
+            if (KINDS[h.kind].iso_matern) {
+                double sl = 0.0;
+                for (int d = 0; d < D; ++d) sl += Sd[s * D + d];
+                g[0] = sl;
+            } else {
+                for (int d = 0; d < nl; ++d) g[d] = Sd[s * D + d];
+            }
+            g[nl] = 2.0 * SK[s];
+        }
+        g[nl + 1] = 2.0 * noise * trM;
+    }
+    if (lpd_out) std::memcpy(lpd_out, lpd.data(), (size_t)L * sizeof(double));
     return 0;
 }
 

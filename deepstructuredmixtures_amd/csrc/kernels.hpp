@@ -1216,8 +1216,16 @@ struct GradTask {
     int na, nb;             // valid rows / cols
     int diag;               // tile on the block diagonal
     int kid;
-    int pad;
+    int uoff;               // LOO contraction (template argument LOO): u of the rows / columns = alpha_a / alpha_b + uoff; else unused
 };
+
+// The weight an accumulator element G_rc is contracted with.  Marginal likelihood: alpha_r alpha_c - G_rc with G = K_y^-1.
+// Leave-one-out density (dsmgp_loo_gradients, GPML eq. 5.13): (u_r alpha_c + alpha_r u_c) / 2 - G_rc with G = H H^T.
+template <bool LOO>
+__device__ __forceinline__ double graddot_weight(double ar, double ac, double ur, double uc, double acc) {
+    if constexpr (LOO) return 0.5 * fma(ur, ac, ar * uc) - acc;
+    else return ar * ac - acc;
+}
 
 // The epilogue is a Gram tile of its own (squared distance + exp per element): the coordinates of the tile's 128 rows
 // and 128 columns and the two alpha blocks are staged once through the LDS the main loop no longer needs (D <= 35;
@@ -1227,6 +1235,9 @@ constexpr int GRADDOT_STAGE_D = 35;
 // asked for (dsmgp_set_option DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT): out[2 + d] = sum_rc (alpha_r alpha_c - G_rc) *
 // sigma^2 exp(-u_d^2 / 2 l_d^2) * u_d^2 / l_d^2, u_d = x_rd - x_cd -- the contraction with dK / dlog l_d.  2 + D too when an
 // ArdSEProduct or Matern leaf has tasks: out[2 + d] = sum_rc (alpha_r alpha_c - G_rc) dK_rc / dlog l_d.
+// LOO (all three kernels): the weight is graddot_weight<true>, u staged next to alpha in 256 doubles of LDS of its own, and
+// out[1] = sum_rc weight_rc K_rc (counted like out[0]) in place of the trace, which that pass does not need.
+template <bool LOO>
 __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __restrict__ tasks,
                                                               const KParam* __restrict__ kp, int D,
                                                               double* __restrict__ out, int ostride) {
@@ -1241,6 +1252,13 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
     const int t = threadIdx.x;
     const int lane = t & 63, w = t >> 6;
     const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+    double* ul = nullptr;
+    if constexpr (LOO) {
+        __shared__ double ul_s[2 * TB];
+        ul = ul_s;
+        ul[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[g.uoff + t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[g.uoff + t - TB] : 0.0);
+        __syncthreads();
+    }
     const double nh = p.nh0;
     double s = 0.0, tr = 0.0;
     if (p.kind == 1) {
@@ -1263,14 +1281,23 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
                 const int r = wr * 64 + 16 * rn + l15;
                 const bool rv = r < g.na;
                 const double ar = al[r], a = xs[d * 256 + r];
+                const double ur = LOO ? ul[r] : 0.0;
                 const double* xb = xs + d * 256 + TB + wc * 64 + l4;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
                     const double u = a - xb[16 * (i >> 2) + 4 * (i & 3)];
                     const double q = u * u;
-                    const double pre = ar * al[TB + c] - acc[i >> 2][rn][i & 3];
-                    if (rv && c < g.nb) sd = fma(pre * exp_nonpos(q * nhd), q, sd);
+                    const double pre = graddot_weight<LOO>(ar, al[TB + c], ur, LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
+                    if constexpr (LOO) {
+                        if (rv && c < g.nb) {
+                            const double pe = pre * exp_nonpos(q * nhd);
+                            sd = fma(pe, q, sd);
+                            tr += pe;
+                        }
+                    } else {
+                        if (rv && c < g.nb) sd = fma(pre * exp_nonpos(q * nhd), q, sd);
+                    }
                 }
             }
             for (int o = 32; o > 0; o >>= 1) sd += __shfl_down(sd, o);
@@ -1280,13 +1307,17 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
             if (t == 0)   // u^2 / l_d^2 = -2 nh_d u^2
                 out[(size_t)ostride * blockIdx.x + 2 + d] = wgt * p.sigma2 * (-2.0 * nhd) * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
         }
+        if constexpr (LOO) {
+            tr *= p.sigma2;      // sum_rc weight_rc K_rc, K = sigma^2 sum_d exp(...)
+        } else {
 #pragma unroll
-        for (int rn = 0; rn < 4; ++rn) {
-            const int r = wr * 64 + 16 * rn + l15;
+            for (int rn = 0; rn < 4; ++rn) {
+                const int r = wr * 64 + 16 * rn + l15;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
-                if (g.diag && r == c && r < g.na) tr += acc[i >> 2][rn][i & 3];
+                for (int i = 0; i < 16; ++i) {
+                    const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+                    if (g.diag && r == c && r < g.na) tr += acc[i >> 2][rn][i & 3];
+                }
             }
         }
         __syncthreads();
@@ -1306,6 +1337,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
             const int r = wr * 64 + 16 * rn + l15;
             const bool rv = r < g.na;
             const double ar = al[r];
+            const double ur = LOO ? ul[r] : 0.0;
             double z[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) z[i] = 0.0;
@@ -1323,9 +1355,10 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
                 const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
                 if (rv && c < g.nb) {
                     const double kv = p.sigma2 * exp_nonpos(z[i] * nh);
-                    const double pre = ar * al[TB + c] - acc[i >> 2][rn][i & 3];
+                    const double pre = graddot_weight<LOO>(ar, al[TB + c], ur, LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
                     s = fma(pre * kv, z[i], s);
-                    if (g.diag && r == c) tr += acc[i >> 2][rn][i & 3];
+                    if constexpr (LOO) tr += pre * kv;
+                    else if (g.diag && r == c) tr += acc[i >> 2][rn][i & 3];
                 }
             }
         }
@@ -1347,9 +1380,10 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
                             z = fma(u, u, z);
                         }
                         const double kv = p.sigma2 * exp_nonpos(z * nh);
-                        const double pre = ar * g.alpha_b[c] - acc[cm][rn][q];
+                        const double pre = graddot_weight<LOO>(ar, g.alpha_b[c], LOO ? ul[r] : 0.0, LOO ? ul[TB + c] : 0.0, acc[cm][rn][q]);
                         s = fma(pre * kv, z, s);
-                        if (g.diag && r == c) tr += acc[cm][rn][q];
+                        if constexpr (LOO) tr += pre * kv;
+                        else if (g.diag && r == c) tr += acc[cm][rn][q];
                     }
                 }
         }
@@ -1366,7 +1400,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
     if (threadIdx.x == 0) {
         const double wgt = g.diag ? 1.0 : 2.0;
         out[(size_t)ostride * blockIdx.x] = wgt * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
-        out[(size_t)ostride * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        out[(size_t)ostride * blockIdx.x + 1] = (LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 
@@ -1377,6 +1411,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
 // gram_accumulate<4>), with the coordinates staged GRADDOT_STAGE_D dimensions at a time (one stage for all four row groups
 // when D fits at once); the trace is taken from acc first, then acc <- (alpha_r alpha_c - G_rc) K_rc, and each dimension
 // costs one fma per entry.
+template <bool LOO>
 __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTask* __restrict__ tasks,
                                                                    const KParam* __restrict__ kp, int D,
                                                                    double* __restrict__ out, int ostride) {
@@ -1392,19 +1427,28 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTas
     const int t = threadIdx.x;
     const int lane = t & 63, w = t >> 6;
     const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+    double* ul = nullptr;
+    if constexpr (LOO) {
+        __shared__ double ul_s[2 * TB];
+        ul = ul_s;
+        ul[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[g.uoff + t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[g.uoff + t - TB] : 0.0);
+        __syncthreads();
+    }
     double tr = 0.0;
     constexpr int CH = GRADDOT_STAGE_D;
     double* xs = smem;
     double* al = smem + (size_t)CH * 256;
     const int nch = (D + CH - 1) / CH;
     const double wgt = g.diag ? 1.0 : 2.0;
+    if constexpr (!LOO) {
 #pragma unroll
-    for (int rn = 0; rn < 4; ++rn) {
-        const int r = wr * 64 + 16 * rn + l15;
+        for (int rn = 0; rn < 4; ++rn) {
+            const int r = wr * 64 + 16 * rn + l15;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
-            if (g.diag && r == c && r < g.na) tr += acc[i >> 2][rn][i & 3];
+            for (int i = 0; i < 16; ++i) {
+                const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+                if (g.diag && r == c && r < g.na) tr += acc[i >> 2][rn][i & 3];
+            }
         }
     }
     al[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[t - TB] : 0.0);
@@ -1438,11 +1482,13 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTas
             }
         }
         const double ar = al[r];
+        const double ur = LOO ? ul[r] : 0.0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
-            const double pre = ar * al[TB + c] - acc[i >> 2][rn][i & 3];
+            const double pre = graddot_weight<LOO>(ar, al[TB + c], ur, LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
             acc[i >> 2][rn][i & 3] = (rv && c < g.nb) ? pre * (p.sigma2 * exp_nonpos(z[i])) : 0.0;
+            if constexpr (LOO) tr += acc[i >> 2][rn][i & 3];
         }
     }
     for (int ch = 0; ch < nch; ++ch) {
@@ -1483,7 +1529,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTas
     __syncthreads();
     if (threadIdx.x == 0) {
         out[(size_t)ostride * blockIdx.x] = 0.0;
-        out[(size_t)ostride * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        out[(size_t)ostride * blockIdx.x + 1] = (LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 
@@ -1492,6 +1538,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTas
 // sigma^2 exp(-s) c(s) u_d^2 nh_d, finite at s = 0.  Launched over the last part of the tail.  A copy, not a template of that
 // kernel: as a template instantiation, or with the body shared through a template <bool> device function, the ArdSEProduct
 // kernel went from 240 VGPRs to 256 and 684 bytes of scratch per lane.
+template <bool LOO>
 __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradTask* __restrict__ tasks,
                                                                      const KParam* __restrict__ kp, int D,
                                                                      double* __restrict__ out, int ostride) {
@@ -1507,6 +1554,13 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
     const int t = threadIdx.x;
     const int lane = t & 63, w = t >> 6;
     const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+    double* ul = nullptr;
+    if constexpr (LOO) {
+        __shared__ double ul_s[2 * TB];
+        ul = ul_s;
+        ul[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[g.uoff + t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[g.uoff + t - TB] : 0.0);
+        __syncthreads();
+    }
     double tr = 0.0;
     constexpr int CH = GRADDOT_STAGE_D;
     double* xs = smem;
@@ -1516,13 +1570,15 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
     // c(s) = c1 + c2 s: (1, 0) for nu = 3/2, (1/3, 1/3) for nu = 5/2
     const double c2 = matern_c2(p);
     const double c1 = (c2 != 0.0) ? c2 : 1.0;
+    if constexpr (!LOO) {
 #pragma unroll
-    for (int rn = 0; rn < 4; ++rn) {
-        const int r = wr * 64 + 16 * rn + l15;
+        for (int rn = 0; rn < 4; ++rn) {
+            const int r = wr * 64 + 16 * rn + l15;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
-            if (g.diag && r == c && r < g.na) tr += acc[i >> 2][rn][i & 3];
+            for (int i = 0; i < 16; ++i) {
+                const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+                if (g.diag && r == c && r < g.na) tr += acc[i >> 2][rn][i & 3];
+            }
         }
     }
     al[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[t - TB] : 0.0);
@@ -1556,13 +1612,16 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
             }
         }
         const double ar = al[r];
+        const double ur = LOO ? ul[r] : 0.0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
-            const double pre = ar * al[TB + c] - acc[i >> 2][rn][i & 3];
+            const double pre = graddot_weight<LOO>(ar, al[TB + c], ur, LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
             const double s = sqrt(z[i]);
             const double wk = p.sigma2 * exp_nonpos(-s) * fma(c2, s, c1);
             acc[i >> 2][rn][i & 3] = (rv && c < g.nb) ? pre * wk : 0.0;
+            if constexpr (LOO)        // the kernel value from the weight: K = wk (1 + s + c2 s^2) / c(s), c(s) >= 1/3
+                tr = fma(acc[i >> 2][rn][i & 3], fma(fma(c2, s, 1.0), s, 1.0) / fma(c2, s, c1), tr);
         }
     }
     for (int ch = 0; ch < nch; ++ch) {
@@ -1603,7 +1662,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
     __syncthreads();
     if (threadIdx.x == 0) {
         out[(size_t)ostride * blockIdx.x] = 0.0;
-        out[(size_t)ostride * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        out[(size_t)ostride * blockIdx.x + 1] = (LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 
@@ -2907,6 +2966,10 @@ struct ArdLinTask {
 };
 constexpr int ARDLIN_COLS = 8;
 constexpr int ARDLIN_DC = 8;
+// FULL (dsmgp_loo_gradients): Xt is the leaf's H = K_y^-1 diag(sqrt w), a full square, so every row i < n enters every column:
+// the second sum is |H^T x_d|^2 over the task's columns; the task's alpha points at the leaf's [alpha | u] block (u = alpha + ldx:
+// both are npad long) and a third sum out[task * 3 D + 2 D + d] = sum_c u_c x_cd is written (3 D doubles per task).
+template <bool FULL>
 __global__ __launch_bounds__(256) void ardlin_quad_kernel(const ArdLinTask* __restrict__ tasks, int D, double* __restrict__ out) {
     __shared__ double red[4][ARDLIN_COLS * ARDLIN_DC];
     const ArdLinTask tk = tasks[blockIdx.x];
@@ -2914,7 +2977,7 @@ __global__ __launch_bounds__(256) void ardlin_quad_kernel(const ArdLinTask* __re
     const int d0 = blockIdx.y * ARDLIN_DC;
     const int dn = min(ARDLIN_DC, D - d0);
     const int nc = min(ARDLIN_COLS, tk.n - tk.c0);
-    const int rend = tk.c0 + nc;                // rows 0 .. rend - 1: row i enters column c for i <= c only
+    const int rend = FULL ? tk.n : tk.c0 + nc;  // rows 0 .. rend - 1: row i enters column c for i <= c only
     double acc[ARDLIN_COLS][ARDLIN_DC];
 #pragma unroll
     for (int j = 0; j < ARDLIN_COLS; ++j)
@@ -2925,7 +2988,7 @@ __global__ __launch_bounds__(256) void ardlin_quad_kernel(const ArdLinTask* __re
 #pragma unroll
         for (int k = 0; k < ARDLIN_DC; ++k) xv[k] = (k < dn) ? tk.x[i + (size_t)(d0 + k) * tk.ldx] : 0.0;
 #pragma unroll
-        for (int j = 0; j < ARDLIN_COLS; ++j) v[j] = (j < nc && i <= tk.c0 + j) ? tk.Xt[i + (size_t)(tk.c0 + j) * tk.ldt] : 0.0;
+        for (int j = 0; j < ARDLIN_COLS; ++j) v[j] = (j < nc && (FULL || i <= tk.c0 + j)) ? tk.Xt[i + (size_t)(tk.c0 + j) * tk.ldt] : 0.0;
 #pragma unroll
         for (int j = 0; j < ARDLIN_COLS; ++j)
 #pragma unroll
@@ -2943,15 +3006,181 @@ __global__ __launch_bounds__(256) void ardlin_quad_kernel(const ArdLinTask* __re
         }
     __syncthreads();
     if (t < dn) {
-        double q = 0.0, a = 0.0;
+        constexpr int OS = FULL ? 3 : 2;
+        double q = 0.0, a = 0.0, b = 0.0;
         for (int j = 0; j < nc; ++j) {
             const int e = j * ARDLIN_DC + t;
             const double s = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
             q = fma(s, s, q);
             a = fma(tk.alpha[tk.c0 + j], tk.x[tk.c0 + j + (size_t)(d0 + t) * tk.ldx], a);
+            if constexpr (FULL) b = fma(tk.alpha[tk.ldx + tk.c0 + j], tk.x[tk.c0 + j + (size_t)(d0 + t) * tk.ldx], b);
         }
-        out[(size_t)blockIdx.x * 2 * D + d0 + t] = a;
-        out[(size_t)blockIdx.x * 2 * D + D + d0 + t] = q;
+        out[(size_t)blockIdx.x * OS * D + d0 + t] = a;
+        out[(size_t)blockIdx.x * OS * D + D + d0 + t] = q;
+        if constexpr (FULL) out[(size_t)blockIdx.x * OS * D + 2 * D + d0 + t] = b;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Hyper-parameter gradients of the leave-one-out log predictive density (dsmgp_loo_gradients, GPML eq. 5.13).  With
+// G = K_y^-1, d = diag G, alpha = G (y - m):   dlpd / dtheta = sum_rc M_rc (dK_y / dtheta)_rc,
+//     M = (u alpha^T + alpha u^T) / 2 - H H^T,   H = G diag(sqrt w),   u = G (alpha / d),   w_i = (1 + alpha_i^2 / d_i) / (2 d_i).
+// Per leaf that computes (every leaf but a COPY leaf with its source's mean) a block of four vectors of npad doubles,
+// [alpha | u | sqrt w | alpha / (d sqrt w)], zero from row n on, and an npad x npad arena for H.
+//   loo_weights_kernel   d from the row sums of dsmgp_loo (LooTask), the vectors but u, and the two sums of tr(M K_y)
+//   tile_ginv_kernel     tiles of G on the f64-MFMA main loop (the product tile_graddot_kernel forms), stored as H
+//   loo_hvec_kernel      u = H (alpha / (d sqrt w)) = G (alpha / d), |H|_F^2 and u . alpha per row tile
+//   tile_graddot_*<true> the contraction of M with dK, H H^T over the full K range never stored
+//   ardlin_quad_kernel<true>   ArdLinear: |H^T x_d|^2, x_d . alpha, x_d . u
+struct LooVecTask {
+    double* vec;          // the leaf's vector block, or NULL: the leaf takes its source's results
+    int npad;
+    int pad;
+};
+
+// out[2 l] = sum_i alpha_i^2 / d_i, out[2 l + 1] = sum_i w_i d_i: thread t adds rows t, t + 256, ..., then a fixed tree
+__global__ __launch_bounds__(256) void loo_weights_kernel(const LeafDev* __restrict__ leaves, const LooTask* __restrict__ tasks,
+                                                          const LooVecTask* __restrict__ vt, double* __restrict__ out) {
+    __shared__ double r1[256], r2[256];
+    const LooVecTask v = vt[blockIdx.x];
+    if (!v.vec) return;
+    const LeafDev lf = leaves[blockIdx.x];
+    const LooTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x;
+    const size_t np = (size_t)v.npad;
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = t; i < v.npad; i += 256) {
+        double a = 0.0, sw = 0.0, tq = 0.0;
+        if (i < lf.n) {
+            const int nparts = (lf.n - (i & ~(TB - 1)) + ROWNORM_COLS - 1) / ROWNORM_COLS;
+            double d = 0.0;
+            for (int k = 0; k < nparts; ++k) d += tk.P[(size_t)k * tk.ldp + i];
+            a = tk.alpha[i];
+            const double q = a / d;
+            const double w = fma(a, q, 1.0) / (2.0 * d);
+            sw = sqrt(w);
+            tq = q / sw;
+            s1 = fma(a, q, s1);
+            s2 = fma(w, d, s2);
+        }
+        v.vec[i] = a;
+        v.vec[np + i] = 0.0;
+        v.vec[2 * np + i] = sw;
+        v.vec[3 * np + i] = tq;
+    }
+    r1[t] = s1;
+    r2[t] = s2;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            r1[t] += r1[t + o];
+            r2[t] += r2[t + o];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[2 * blockIdx.x] = r1[0];
+        out[2 * blockIdx.x + 1] = r2[0];
+    }
+}
+
+// One lower tile (i, j) of G = K_y^-1 = Xt Xt^T (row tile i times row tile j of Xt = L^-T over the columns [128 i, npad)),
+// stored scaled: H(r, c) = G(r, c) sqrt(w_c) into tile (i, j), and H(c, r) = G(r, c) sqrt(w_r) into the mirror tile (j, i).
+// Every entry of both tiles is written, zero outside the leaf's n rows / columns: the contraction reads whole tiles.
+struct GinvTask {
+    TileTask gemm;          // A = Xt row tile i, B = Xt row tile j, K range [128 i, npad); C = tile (i, j) of H, ldc
+    double* Ct;             // tile (j, i) of H
+    const double* sw_a;     // sqrt w of the rows (tile i)
+    const double* sw_b;     // ... of the columns (tile j)
+    int na, nb;             // valid rows / columns
+    int diag;
+    int pad;
+};
+
+__global__ __launch_bounds__(256, 2) void tile_ginv_kernel(const GinvTask* __restrict__ tasks) {
+    __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
+    double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
+    double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
+    const GinvTask g = tasks[blockIdx.x];
+    d4 acc[4][4];
+    gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);      // ends on a barrier: the ring is free
+    const int t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+    double* sw = smem;
+    sw[t] = (t < TB) ? ((t < g.na) ? g.sw_a[t] : 0.0) : ((t - TB < g.nb) ? g.sw_b[t - TB] : 0.0);
+    __syncthreads();
+    const size_t ldc = (size_t)g.gemm.ldc;
+#pragma unroll
+    for (int rn = 0; rn < 4; ++rn) {
+        const int r = wr * 64 + 16 * rn + l15;
+        const double swr = sw[r];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+            const double v = (r < g.na && c < g.nb) ? acc[i >> 2][rn][i & 3] : 0.0;
+            AS_GLOBAL_F64(g.gemm.C)[r + (size_t)c * ldc] = v * sw[TB + c];
+            if (!g.diag) AS_GLOBAL_F64(g.Ct)[c + (size_t)r * ldc] = v * swr;
+        }
+    }
+}
+
+// One 128-row tile of H: u_r = sum_c H(r, c) tq_c over the leaf's n columns (two halves of the columns in two half workgroups,
+// four partial sums each, joined in a fixed order), then sum_r sum_c H(r, c)^2 and sum_r u_r alpha_r of the tile (fixed tree).
+struct LooHvecTask {
+    const double* H;      // the leaf's H
+    double* vec;          // the leaf's vector block
+    int ld;               // npad: leading dimension of H and the stride between the vectors
+    int n;                // columns
+    int row0;             // first row of the tile
+    int nrows;            // valid rows of this tile
+};
+
+__global__ __launch_bounds__(256) void loo_hvec_kernel(const LooHvecTask* __restrict__ tasks, double* __restrict__ out) {
+    __shared__ double ru[256], rf[256];
+    const LooHvecTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x, r = t & 127, h = t >> 7;
+    const double* tq = tk.vec + 3 * (size_t)tk.ld;
+    double su[4] = {0.0, 0.0, 0.0, 0.0}, sf[4] = {0.0, 0.0, 0.0, 0.0};
+    if (r < tk.nrows) {
+        const double* Hr = tk.H + tk.row0 + r;
+        int c = h;
+        for (; c + 6 < tk.n; c += 8) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double v = Hr[(size_t)(c + 2 * j) * tk.ld];
+                su[j] = fma(v, tq[c + 2 * j], su[j]);
+                sf[j] = fma(v, v, sf[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (c + 2 * j < tk.n) {
+                const double v = Hr[(size_t)(c + 2 * j) * tk.ld];
+                su[j] = fma(v, tq[c + 2 * j], su[j]);
+                sf[j] = fma(v, v, sf[j]);
+            }
+    }
+    ru[t] = (su[0] + su[1]) + (su[2] + su[3]);
+    rf[t] = (sf[0] + sf[1]) + (sf[2] + sf[3]);
+    __syncthreads();
+    if (t < TB) {
+        const double u = ru[t] + ru[t + TB];
+        rf[t] = rf[t] + rf[t + TB];
+        tk.vec[(size_t)tk.ld + tk.row0 + t] = u;         // rows >= nrows: 0
+        ru[t] = u * tk.vec[tk.row0 + t];
+    }
+    __syncthreads();
+    for (int o = 64; o > 0; o >>= 1) {
+        if (t < o) {
+            ru[t] += ru[t + o];
+            rf[t] += rf[t + o];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[2 * blockIdx.x] = rf[0];
+        out[2 * blockIdx.x + 1] = ru[0];
     }
 }
 

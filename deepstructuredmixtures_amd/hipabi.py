@@ -54,6 +54,7 @@ SIGNATURES = {
     "dsmgp_predict_cov": (C.c_int, [_ctx, C.c_int32, C.c_int32, _dp, C.c_int64, _dp]),
     "dsmgp_gradients": (C.c_int, [_ctx, _dp, C.c_int32]),
     "dsmgp_loo": (C.c_int, [_ctx, _dp, _dp, _dp, _dp]),
+    "dsmgp_loo_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp]),
     "dsmgp_set_gradient_leaves": (C.c_int, [_ctx, _ip]),
     "dsmgp_set_option": (C.c_int, [_ctx, C.c_int32, C.c_int32]),
     "dsmgp_lanes": (C.c_int, [_ctx, _ip]),
@@ -361,6 +362,18 @@ class Context:
         self._chk(self.lib.dsmgp_loo(self.h, mu.ctypes.data_as(_dp), var.ctypes.data_as(_dp), lpd.ctypes.data_as(_dp), C.byref(sec)))
         self.loo_seconds = sec.value
         return mu, var, lpd
+
+    def loo_gradients(self, stride):
+        """`(grad, lpd)`: the true derivatives of every leaf's LOO log predictive density `lpd[l]` (the `lpd` of `loo()`, same
+        bits) with respect to its log-scale hyper-vector, `grad[l, j]` in the layout of `gradients` (dsmgp_loo_gradients; GPML
+        eq. 5.13, mean held fixed).  Leaves with `info != 0` come back as NaN.  The mask of `set_gradient_leaves` does not
+        apply.  The device time of the call is left in `self.loo_gradients_seconds`."""
+        g = np.zeros((self.L, stride))
+        lpd = np.empty(self.L)
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_loo_gradients(self.h, g.ctypes.data_as(_dp), int(stride), lpd.ctypes.data_as(_dp), C.byref(sec)))
+        self.loo_gradients_seconds = sec.value
+        return g, lpd
 
     # ---- predict(model, x) aggregation + scores on the device (src/common.jl:134-302, src/scorefunctions.jl) ----
     def _agg_args(self, family, leaf_coef, leaf_group):
@@ -757,6 +770,19 @@ class MultiContext:
             g[loc] = r
         return g
 
+    def loo_gradients(self, stride):
+        """`Context.loo_gradients` per sub-context, put back into the order of the whole leaf table;
+        `self.loo_gradients_seconds` is the longest of the sub-contexts' device times."""
+        self._upload()
+        res = self._each(lambda s: s.loo_gradients(stride))
+        g = np.zeros((self.L, stride))
+        lpd = np.empty(self.L)
+        for (r, d), loc in zip(res, self.part):
+            g[loc] = r
+            lpd[loc] = d
+        self.loo_gradients_seconds = max(s.loo_gradients_seconds for s in self.act)
+        return g, lpd
+
     def loo(self):
         """`Context.loo` per sub-context, put back into the order of the whole leaf table (leaves are independent);
         `self.loo_seconds` is the longest of the sub-contexts' device times."""
@@ -1122,6 +1148,10 @@ class StreamingContext:
     def loo(self):
         raise DsmgpError(E_STATE, "loo: a streaming pass discards the factors and L^-T with their leaf group; "
                                   "use a resident Context for leave-one-out moments")
+
+    def loo_gradients(self, stride):
+        raise DsmgpError(E_STATE, "loo_gradients: a streaming pass discards the factors and L^-T with their leaf group; "
+                                  "use a resident Context for the gradients of the leave-one-out density")
 
     def timings(self):
         return dict(self._res["timings"]) if self._res else {k: 0.0 for k in TIMING_NAMES}

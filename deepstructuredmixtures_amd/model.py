@@ -543,11 +543,16 @@ def _mll_recursive(model):
 
 def mll_table(model):
     """`mll!(spn, L)`: value per node id (`src/optimize.jl:27-39`)."""
+    return _value_table(model, model.leaf_mll)
+
+
+def _value_table(model, leaf_values):
+    """The recursion of `mll!(spn, L)` over any per-leaf values (log marginals, LOO densities): value per node id."""
     tab = {}
 
     def rec(node):
         if node.kind == "gp":
-            v = float(model.leaf_mll[node.leaf])
+            v = float(leaf_values[node.leaf])
         elif node.kind == "split":
             v = sum(rec(c) for c in node.children)
         else:
@@ -621,7 +626,12 @@ def setparams(model, hyp):
 
 # ------------------------------------------------------------------------------------ gradients / training
 
-def updategradients(model, active=None):
+def _check_objective(objective):
+    if objective not in ("mll", "loo"):
+        raise ValueError(f"objective must be 'mll' or 'loo', not {objective!r}")
+
+
+def updategradients(model, active=None, objective="mll"):
     """`updategradients!(spn)` (`src/fit.jl:306-311`): per-leaf gradient vectors in the reference's order
     [dl..., ds, dnoise] (`src/gaussianprocess.jl:212-214`), computed on the device for the local leaves and
     gathered.  Also stored on the leaves (kernel.dl / kernel.ds / dnoise) like the reference does.
@@ -629,14 +639,28 @@ def updategradients(model, active=None):
     what `finetune!` needs, whose pass for leaf j weights leaf l's gradient by the overlap D[j, l] (`src/optimize.jl:101`).
     The gradients stored on the leaves (kernel.dl / kernel.ds / dnoise) are ZERO outside the active set, where the reference
     stores every leaf's gradient on every pass (they are multiplied by D[j, l] = 0 there and never read otherwise); the
-    streaming context ignores the mask and computes all of them."""
+    streaming context ignores the mask and computes all of them.
+    `objective="loo"`: the rows are the true derivatives of each leaf's LOO log predictive density (`dsmgp_loo_gradients`, GPML
+    eq. 5.13) instead, and the densities themselves are stored in `leaf_lpd` (what `loo_objective` and `grad_loo` read); no mask
+    (`active` must be None), no streaming context."""
+    _check_objective(objective)
     target = model.model if isinstance(model, GaussianProcess) else model
     stride = max(lf.kernel.nparams() + 1 for lf in target.leaves)
-    if len(target.shard.local) and (active is not None or getattr(target, "_grad_masked", False)):
-        target.ctx.set_gradient_leaves(None if active is None else np.asarray(active)[target.shard.local])
-        target._grad_masked = active is not None
-    g_loc = target.ctx.gradients(stride) if len(target.shard.local) else np.zeros((0, stride))
-    g = target.shard.gather_leaf_columns(g_loc[:, :stride])
+    if objective == "loo":
+        if active is not None:
+            raise ValueError("updategradients: the LOO gradients take no mask")
+        if len(target.shard.local):
+            g_loc, lpd_loc = target.ctx.loo_gradients(stride)
+        else:
+            g_loc, lpd_loc = np.zeros((0, stride)), np.zeros(0)
+        g = target.shard.gather_leaf_columns(g_loc[:, :stride])
+        target.leaf_lpd = target.shard.gather_leaf_columns(lpd_loc[:, None])[:, 0]
+    else:
+        if len(target.shard.local) and (active is not None or getattr(target, "_grad_masked", False)):
+            target.ctx.set_gradient_leaves(None if active is None else np.asarray(active)[target.shard.local])
+            target._grad_masked = active is not None
+        g_loc = target.ctx.gradients(stride) if len(target.shard.local) else np.zeros((0, stride))
+        g = target.shard.gather_leaf_columns(g_loc[:, :stride])
     for lf, row in zip(target.leaves, g):
         n = lf.kernel.nparams()
         if lf.kernel.kind == KIND_ISO_LINEAR:
@@ -658,7 +682,38 @@ def grad_mll(model, leaf_weights=None):
     per leaf: a row of the overlap matrix) it is the `finetune!` variant, `src/optimize.jl:91-150`."""
     if isinstance(model, GaussianProcess):
         return model.model.leaf_grad[0][: model.node.kernel.nparams() + 1].copy()
-    tab = mll_table(model)
+    return _grad_tree(model, mll_table(model), leaf_weights)
+
+
+def loo_objective(model, lpd=None):
+    """The tree recursion of `mll(model)` with each leaf's LOO log predictive density in place of its log marginal (sum nodes:
+    log-sum-exp with their uniform weights; split nodes: sum); for a `GaussianProcess` its density.  `lpd` (one value per leaf):
+    default the densities of the current fit from the device (`ctx.loo()`), which are also stored in `leaf_lpd`."""
+    target = model.model if isinstance(model, GaussianProcess) else model
+    if lpd is None:
+        lpd_loc = target.ctx.loo()[2] if len(target.shard.local) else np.zeros(0)
+        lpd = target.leaf_lpd = target.shard.gather_leaf_columns(lpd_loc[:, None])[:, 0]
+    if isinstance(model, GaussianProcess):
+        return float(lpd[0])
+    return _value_table(model, lpd)[model.root.id]
+
+
+def grad_loo(model):
+    """Gradient of `loo_objective(model)` w.r.t. the shared hyper-vector: the recursion of `grad_mll` on the table of the LOO
+    densities `leaf_lpd` and the leaf gradients `leaf_grad`, both left by `updategradients(model, objective="loo")`.  It is the
+    true gradient of that objective (`_grad_tree(rho=False)`): a sum node of K children weighs child c by
+    exp(-log K + value_c - value_node), where `∇mll!` multiplies by K again under a sum over split nodes and leaves the 1 / K
+    out under a sum over GPs."""
+    if isinstance(model, GaussianProcess):
+        return model.model.leaf_grad[0][: model.node.kernel.nparams() + 1].copy()
+    return _grad_tree(model, _value_table(model, model.leaf_lpd), None, rho=False)
+
+
+def _grad_tree(model, tab, leaf_weights, rho=True):
+    """`∇mll!` over a table of node values `tab` and the per-leaf gradients `model.leaf_grad` (shared by grad_mll and grad_loo).
+    `rho=False`: every sum node of K children weighs a child by exp(-log K + child - node) and nothing else -- without the
+    reference's `+ log K` (`src/optimize.jl:70-73`) and with the `-log K` it leaves out under a sum over GPs (`:76-89`): the true
+    derivative of the root value."""
     logS = tab[model.root.id]
     n_hyp = getparams(model).size
     grad = np.zeros(n_hyp)
@@ -676,12 +731,12 @@ def grad_mll(model, leaf_weights=None):
             c0 = 0
             for c in node.children:                                           # :76-89
                 nn = c.kernel.nparams() + 1
-                rec(c, dparent, lrho, g[c0:c0 + nn])
+                rec(c, dparent if rho else dparent - np.log(len(node.children)), lrho, g[c0:c0 + nn])
                 c0 += nn
         else:
             K = len(node.children)
             for c in node.children:
-                rec(c, -np.log(K) + dparent, np.log(K) + lrho, g)             # :70-73
+                rec(c, -np.log(K) + dparent, np.log(K) + lrho if rho else lrho, g)   # :70-73
 
     rec(model.root, 0.0, 0.0, grad)
     return grad
@@ -726,7 +781,7 @@ class RMSProp:
         return g * (self.eta / (np.sqrt(self.acc) + self.eps))
 
 
-def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose):
+def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="mll"):
     """`train!(gp::GaussianProcess; iterations, optim, λ)` (`src/optimisers.jl:89-145`): ascent on one GP's log
     marginal; a NaN log marginal (or a factorisation that fails: LAPACK info > 0, which the reference's potrf! call
     ignores and which then shows up as NaN) rolls back to the previous hyper-vector and returns; early stop when the
@@ -744,6 +799,9 @@ def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose):
             ell = mll(gp)
         except (np.linalg.LinAlgError, ValueError, hipabi.DsmgpError):   # failed potrf / non-finite hyper-parameters
             ell = float("nan")
+        if objective == "loo" and not np.isnan(ell):      # value and gradient from one call, outside the try: an error of the
+            updategradients(gp, objective="loo")          # LOO pass itself (memory, ArdSE with D > 35) is an error, as for the
+            ell = loo_objective(gp, lpd=gp.model.leaf_lpd)    # marginal-likelihood gradients below
         hist.append(ell)
         if np.isnan(ell):                                                     # :115-119
             setparams(target, old)
@@ -751,11 +809,14 @@ def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose):
             return gp, np.array(hist)
         delta = abs(ell - np.mean(hist[-10:-1])) if it > 10 else np.inf        # :121
         if verbose:
-            print(f"iter {it}: mll {ell:.6f} delta {delta:.3g}")
+            print(f"iter {it}: {objective} {ell:.6f} delta {delta:.3g}")
         if delta < lam:                                                       # :125-128
             return gp, np.array(hist)
-        updategradients(gp)
-        g = grad_mll(gp)
+        if objective == "loo":
+            g = grad_loo(gp)
+        else:
+            updategradients(gp)
+            g = grad_mll(gp)
         old = hyp.copy()
         hyp = hyp + optim.apply(hyp, g)                                       # :135-137 (ascent)
     setparams(target, hyp)
@@ -763,32 +824,39 @@ def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose):
     return gp, np.array(hist)
 
 
-def train(model, optim=None, *, iterations=10_000, lam=None, randinit=True, earlystop=10, seed=0, tau=0.05, verbose=False):
+def train(model, optim=None, *, iterations=10_000, lam=None, randinit=True, earlystop=10, seed=0, tau=0.05, verbose=False,
+          objective="mll"):
     """`train!(model, optim; iterations, λ, randinit, earlystop)` (`src/optimisers.jl:4-87`): gradient ASCENT
     on the tree log marginal over one shared hyper-vector.  Returns (model, history of root mll).
     For a single `GaussianProcess` it is `train!(gp; iterations, optim, λ)` (`src/optimisers.jl:89-145`:
-    RMSProp, λ = 0.1, rollback on a NaN log marginal)."""
+    RMSProp, λ = 0.1, rollback on a NaN log marginal).
+    `objective="loo"`: the same loops on `loo_objective(model)` -- history and early stop on it, ascent on `grad_loo` (no
+    counterpart in the reference); a streaming model refuses (`DsmgpError`, E_STATE)."""
     from .datagen import normal
+    _check_objective(objective)
     if isinstance(model, GaussianProcess):
         return _train_gp(model, RMSProp() if optim is None else optim, iterations, 0.1 if lam is None else lam, randinit, seed,
-                         verbose)
+                         verbose, objective)
+    has_leaves = len(model.shard.local) > 0
+    # factor-and-discard context: a pass over the leaf groups cannot be revisited, so the loop's fit! asks for the
+    # gradients of the same pass up front (one pass per iteration instead of a fit pass plus a fit + gradient pass)
+    streaming = has_leaves and hasattr(model.ctx, "want_gradients")
+    if streaming and objective == "loo":
+        raise hipabi.DsmgpError(hipabi.E_STATE, "train: the LOO objective needs the factors of a resident Context; a streaming "
+                                                "pass discards them with their leaf group")
     lam = 0.05 if lam is None else lam
     optim = ADAM() if optim is None else optim
     n = getparams(model).size
     hyp = normal(seed, 0, n) if randinit else getparams(model)
     hist = []
     c = 0
-    has_leaves = len(model.shard.local) > 0
     if has_leaves:
         model.ctx.set_joint(False)     # fit is not followed by predict inside the loop: keep resident test rows out of it
-    # factor-and-discard context: a pass over the leaf groups cannot be revisited, so the loop's fit! asks for the
-    # gradients of the same pass up front (one pass per iteration instead of a fit pass plus a fit + gradient pass)
-    streaming = has_leaves and hasattr(model.ctx, "want_gradients")
     if streaming:
         model.ctx.want_gradients = max(lf.kernel.nparams() + 1 for lf in model.leaves)
         model.ctx.groups = None
     try:
-        return _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming)
+        return _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming, objective)
     finally:
         if streaming:                  # also after an error inside the loop: later passes must not collect gradients
             model.ctx.want_gradients = 0
@@ -797,7 +865,7 @@ def train(model, optim=None, *, iterations=10_000, lam=None, randinit=True, earl
             model.ctx.set_joint(True)
 
 
-def _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming=False):
+def _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming=False, objective="mll"):
     def plain_fits():
         if streaming:                  # the fits after the loop need no gradients: smaller groups, fewer passes
             model.ctx.want_gradients = 0
@@ -806,17 +874,24 @@ def _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, ver
     for it in range(1, iterations + 1):
         setparams(model, hyp)
         fit(model, tau=tau)
-        ell = mll(model)
+        if objective == "loo":          # value and gradient from one call
+            updategradients(model, objective="loo")
+            ell = loo_objective(model, lpd=model.leaf_lpd)
+        else:
+            ell = mll(model)
         hist.append(ell)
         delta = abs(ell - np.mean(hist[-10:-1])) if it > 10 else np.inf       # :53
         c = c + 1 if delta < lam else 0
         if verbose:
-            print(f"iter {it}: mll {ell:.6f} delta {delta:.3g}")
+            print(f"iter {it}: {objective} {ell:.6f} delta {delta:.3g}")
         if c >= earlystop:
             plain_fits()
             return model, np.array(hist)
-        updategradients(model)
-        g = grad_mll(model)
+        if objective == "loo":
+            g = grad_loo(model)
+        else:
+            updategradients(model)
+            g = grad_mll(model)
         hyp = hyp + optim.apply(hyp, g)                                       # :78-79 (ascent)
     plain_fits()
     setparams(model, hyp)

@@ -223,6 +223,31 @@ int dsmgp_set_gradient_leaves(dsmgp_ctx* ctx, const int32_t* active /* L flags, 
  * arena only; it is dropped with the leaf table and dsmgp_release. */
 int dsmgp_loo(dsmgp_ctx* ctx, double* mu_out, double* var_out /* obs_ptr[L] each, in obs_idx order; may be NULL */,
               double* lpd_out /* L; may be NULL */, double* seconds /* may be NULL */);
+/* Gradients of the leaf's LOO log predictive density lpd_l (dsmgp_loo's lpd_out[l]) with respect to its log-scale
+ * hyper-parameters (GPML 5.4.2, eq. 5.13), the mean held fixed: what makes leave-one-out a training objective.  With G = K_y^-1,
+ * d = diag G, alpha = G (y - m):
+ *   dlpd / dtheta = sum_rc M_rc (dK_y / dtheta)_rc,   M = (u alpha^T + alpha u^T) / 2 - H H^T,
+ *   u = G (alpha / d),   H = G diag(sqrt w),   w_i = (1 + alpha_i^2 / d_i) / (2 d_i).
+ * grad_out[l * stride + j], j over [dl..., ds, dnoise] -- the layout of dsmgp_gradients -- and EVERY component is the true
+ * derivative, for all kinds: no factor sigma for IsoSE, true per-dimension length-scale derivatives for the additive ArdSE
+ * whatever DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT says (ArdSE leaves with more input dimensions than the contraction stages, 35:
+ * DSMGP_E_ARG), the sum over the dimensions in ascending order for an iso Matern kind, 0 in the dummy variance slot of the
+ * linear kinds, zeros past the hyper-vector.  Signal variances and the SE / Matern length-scales are contracted with M
+ * directly on the device; IsoLinear's dl = -2 (tr(M K_y) - c tr M) comes from the trace identity (it cancels when the signal
+ * is weak against c = exp(2 logNoise) + 1e-8), dnoise = 2 exp(2 logNoise) tr M.
+ * lpd_out (L, may be NULL): dsmgp_loo's lpd_out, the same bits -- this call runs dsmgp_loo first and inherits what it says
+ * about L^-T, the mask of dsmgp_set_gradient_leaves (it does not apply) and dsmgp_gradients (left exactly as it is).
+ * Needs a fit (DSMGP_E_STATE); stride smaller than a hyper-vector: DSMGP_E_ARG.  Leaves whose fit reported info != 0 get a
+ * NaN row and NaN lpd, the others are unaffected.  A COPY leaf with its source's mean takes its source's row.  Results are
+ * the same to the bit from call to call.  seconds (may be NULL): device time of the call, dsmgp_loo's included (there is no
+ * dsmgp_timings slot for it).
+ * Memory: one more arena for H, npad^2 doubles for every leaf but the COPY leaves with their source's mean -- the size of the
+ * L^-T arena (npad^2 per factor owner) plus npad^2 for every COPY leaf with a mean of its own, which owns no L^-T --, plus
+ * 4 npad doubles per leaf and the partial sums, allocated on first use (the arena from the reserved pool when there is one;
+ * DSMGP_E_NOMEM with a usable context when it does not fit), dropped with the leaf table and dsmgp_release, and NOT counted
+ * by dsmgp_estimate_bytes / dsmgp_memory.  Cost per leaf: n^3 / 3 flops for the tiles of G and n^3 for H H^T. */
+int dsmgp_loo_gradients(dsmgp_ctx* ctx, double* grad_out /* L x stride */, int32_t stride,
+                        double* lpd_out /* L; may be NULL */, double* seconds /* may be NULL */);
 /* Options.  DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT: 0 (default) = ArdSE length-scale gradients exactly as the reference
  * computes them, i.e. identically zero (`precomp * K .* (p/ls[d])` parses as `(precomp*K) .* (p/ls[d])` and p has a zero
  * diagonal, src/kernels.jl:161: train!/finetune! never move ARD length-scales); 1 = the true derivative of the

@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, predict_cov, loo, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52
+export attach!, detach!, census, predict_cov, loo, loo_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -459,6 +459,21 @@ function loo(s::Session)
                                        s.h, μ, σ², lpd, sec))
     off = cumsum(vcat(0, cnt))
     return [μ[off[l]+1:off[l+1]] for l in 1:L], [σ²[off[l]+1:off[l+1]] for l in 1:L], lpd
+end
+
+"loo_gradients(s): the true derivatives of every leaf's LOO log predictive density with respect to its log-scale hyper-vector
+(GPML §5.4.2, eq. 5.13; dsmgp_loo_gradients), mean held fixed.  Returns (g, lpd): `g[:, l]` in the order [∂ℓ…, ∂σ, ∂ϵ] of
+updategradients! for leaf `l` of `s.leaves` (every component the true derivative: no factor σ for IsoSE, true length-scale
+derivatives for ArdSE; zeros past the leaf's hyper-vector) and `lpd`, the densities of `loo(s)`, same bits.  Leaves whose fit
+reported info ≠ 0 come back as NaN.  Nothing is written to the kernels' gradient fields."
+function loo_gradients(s::Session)
+    L = length(s.leaves)
+    g = Matrix{Float64}(undef, s.stride, L)
+    lpd = Vector{Float64}(undef, L)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve g lpd chk(s, ccall(sym(:dsmgp_loo_gradients), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ref{Float64}),
+                                    s.h, g, Int32(s.stride), lpd, sec))
+    return g, lpd
 end
 
 # ---------------------------------------------------------------------------------------------- predict
