@@ -8,7 +8,8 @@ from .kernels import (IsoSE, ArdSE, IsoLinear, ArdLinear, ArdSEProduct, IsoMater
 from .model import (DSMGP, PoE, gPoE, rBCM, GaussianProcess, build, buildDSMGP, buildPoE, buildBCM, fit,
                     fit_naive, predict, prediction, update_cholesky, update, infer, mll, mll_table,
                     reset_weights, getparams, setparams, mse, sse, mae, sae, nlpd, scores, updategradients, grad_mll, train, ADAM, RMSProp,
-                    resident_test, finetune, leaf_covariance, posterior_sample, loo, loo_predict, loo_scores, loo_objective, grad_loo)
+                    resident_test, finetune, leaf_covariance, posterior_sample, loo, loo_predict, loo_scores, loo_objective, grad_loo,
+                    predict_gradients, aggregate_input_gradients)
 from .tree import get_leaves, get_overlap, share_schedule, route
 from .datagen import regression_data
 

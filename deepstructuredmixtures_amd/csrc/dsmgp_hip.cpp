@@ -589,6 +589,14 @@ struct dsmgp_ctx {
     double* arenaCov = nullptr;     // ntpad x ntpad of the leaf dsmgp_predict_cov was last asked for (grow-only, allocated on first use,
     size_t cap_Cov = 0;             //   from the pool when there is one; goes with the test set: free_test).  Not part of bytes_needed.
     DevBuf<PredCovTask> pcov;       // its lower tiles, rebuilt per call
+    // input gradients of the predictive moments (dsmgp_predict_gradients): lists rebuilt per call, buffers allocated on first use
+    double* arenaB = nullptr;       // B = Vt L^-1 (rows K_y^-1 k_t), ntpad x npad per leaf with routed rows, laid out like arenaVt (grow-only,
+    size_t cap_B = 0;               //   from the pool when there is one; goes with the test set: free_test).  Not part of bytes_needed.
+    DevBuf<PredBetaTask> pgbeta;    // the tiles of B
+    DevBuf<PredGradTask> pgtasks;   // (test tile, slab of training rows) pairs
+    DevBuf<PredGradFinTask> pgfin;  // test tiles
+    DevBuf<double> d_pgpart;        // the slabs' sums
+    DevBuf<double> d_pgout;         // dmu | dvar (absent in a mean-only call), route_total x D each (ld = route_total)
     bool test_ready = false;
     bool predicted = false;
     int64_t route_total = 0;
@@ -997,6 +1005,13 @@ void free_test(dsmgp_ctx* c, bool keep) {
     arena_put(c, c->arenaCov);
     c->cap_Cov = 0;
     c->pcov.drop(keep);
+    arena_put(c, c->arenaB);
+    c->cap_B = 0;
+    c->pgbeta.drop(keep);
+    c->pgtasks.drop(keep);
+    c->pgfin.drop(keep);
+    c->d_pgpart.drop(keep);
+    c->d_pgout.drop(keep);
     for (auto& lane : c->phaseJ)
         for (auto& ph : lane) ph.drop(keep);
     for (auto& sl : c->slabJ) arena_put(c, sl);
@@ -3777,6 +3792,37 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
 // owner (rownorm_kernel: one task per 128-row tile and ROWNORM_COLS columns), then loo_moments_kernel per leaf.  L^-T comes from
 // the gradient pass's lists; it is built here unless the arena holds it for the current fit and for every owner.
 namespace {
+// L^-T of every factor owner in arenaX for whoever reads it after a fit (dsmgp_loo, dsmgp_predict_gradients), in two halves.
+// xinv_lists: the task lists of the inversion, unless the arena already holds the current fit's L^-T.  Lists made under a mask
+// (dsmgp_set_gradient_leaves) leave out the owners no active leaf needs: then the sweep runs over lists of the call's own, built
+// for every owner and dropped again when `own` goes out of scope (on every way out, the failing ones too), so that the next
+// dsmgp_gradients builds the mask's lists as it would have without the call -- same launches, same bits.
+// xinv_fill: queues the transposes and the sweep when they are needed; the caller sets xinv_all once the stream is through.
+struct OwnGradLists {
+    dsmgp_ctx* c;
+    bool on = false;
+    ~OwnGradLists() {
+        if (on) free_grad_lists(c);
+    }
+};
+int xinv_lists(dsmgp_ctx* c, OwnGradLists& own) {
+    if (c->xinv_all) return 0;
+    if (c->grad_ready && !c->grad_lists_all) free_grad_lists(c);
+    if (!c->grad_ready) {
+        own.on = !c->grad_active.empty();
+        c->grad_all_owners = true;
+        const int rc = build_grad_plan(c);
+        c->grad_all_owners = false;
+        if (rc) return rc;
+    }
+    return 0;
+}
+int xinv_fill(dsmgp_ctx* c) {
+    if (c->xinv_all) return 0;
+    if (c->gtrans.count) transpose_tile_kernel<<<(int)c->gtrans.count * 16, 256, 0, c->stream>>>(c->gtrans.p);
+    return run_sweep(c, c->ginv, nullptr);
+}
+
 int build_loo_plan(dsmgp_ctx* c) {
     const int L = c->L;
     std::vector<size_t> poff(L, 0);
@@ -3824,26 +3870,9 @@ int dsmgp_loo(dsmgp_ctx* c, double* mu_out, double* var_out, double* lpd_out, do
     if (!c->fitted) return fail(c, DSMGP_E_STATE, "loo before fit");
     HIPCHK(c, hipSetDevice(c->device));
     const int L = c->L;
-    // L^-T of every factor owner.  Lists made under a mask (dsmgp_set_gradient_leaves) leave out the owners no active leaf needs:
-    // then the sweep runs over lists of this call's own, built for every owner and dropped again below, so that the next
-    // dsmgp_gradients builds the mask's lists as it would have without this call -- same launches, same bits.
-    struct OwnLists {       // (dropped on every way out, the failing ones too)
-        dsmgp_ctx* c;
-        bool on = false;
-        ~OwnLists() {
-            if (on) free_grad_lists(c);
-        }
-    } own_lists{c};
-    if (!c->xinv_all) {
-        if (c->grad_ready && !c->grad_lists_all) free_grad_lists(c);
-        if (!c->grad_ready) {
-            own_lists.on = !c->grad_active.empty();
-            c->grad_all_owners = true;
-            const int rc = build_grad_plan(c);
-            c->grad_all_owners = false;
-            if (rc) return rc;
-        }
-    }
+    // L^-T of every factor owner (xinv_lists / xinv_fill)
+    OwnGradLists own_lists{c};
+    if (int rc = xinv_lists(c, own_lists)) return rc;
     if (!c->loo_ready)
         if (int rc = build_loo_plan(c)) return rc;
     EventPair ev;           // the device work of the call: what is left to complete of Dinv and alpha after this fit, the sweep, the two kernels
@@ -3851,10 +3880,7 @@ int dsmgp_loo(dsmgp_ctx* c, double* mu_out, double* var_out, double* lpd_out, do
     HIPCHK(c, hipEventRecord(ev.a, c->stream));
     if (int rc = ensure_dinv(c)) return rc;
     if (int rc = ensure_alpha(c)) return rc;
-    if (!c->xinv_all) {
-        if (c->gtrans.count) transpose_tile_kernel<<<(int)c->gtrans.count * 16, 256, 0, c->stream>>>(c->gtrans.p);
-        if (int rc = run_sweep(c, c->ginv, nullptr)) return rc;
-    }
+    if (int rc = xinv_fill(c)) return rc;
     const size_t nobs = (size_t)c->obs_ptr[L];
     double* dmu = c->d_loo.p + (c->d_loo.count - 2 * nobs - (size_t)L);
     double* dvar = dmu + nobs;
@@ -3871,6 +3897,135 @@ int dsmgp_loo(dsmgp_ctx* c, double* mu_out, double* var_out, double* lpd_out, do
     if (mu_out) HIPCHK(c, hipMemcpy(mu_out, dmu, nobs * sizeof(double), hipMemcpyDeviceToHost));
     if (var_out) HIPCHK(c, hipMemcpy(var_out, dvar, nobs * sizeof(double), hipMemcpyDeviceToHost));
     if (lpd_out) HIPCHK(c, hipMemcpy(lpd_out, dlpd, (size_t)L * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Input gradients of the predictive moments (the kernels and the formulas: kernels.hpp at tile_predbeta_kernel).  The mean half
+// reads alpha and the gathered inputs only.  The variance half needs beta_t = K_y^-1 k_t for every routed row: B = Vt L^-1 by a
+// tile GEMM against the L^-T arena (dsmgp_loo's rule for filling it), into an arena of its own -- Vt stays for dsmgp_predict_cov.
+// Nothing any other entry point reads is written.
+int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int64_t ld, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->predicted || !c->vt_valid) return fail(c, DSMGP_E_STATE, "predict_gradients before predict_run on the current fit");
+    const size_t nr = (size_t)c->route_total;
+    if (nr == 0) return 0;
+    if (ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_gradients: ld < route_total");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int L = c->L, D = c->D;
+    const bool var = dvar_out != nullptr;
+    OwnGradLists own_lists{c};
+    std::vector<size_t> boff((size_t)L, 0);
+    if (var) {
+        if (int rc = xinv_lists(c, own_lists)) return rc;
+        size_t bTot = 0;
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            if (lf.nt == 0) continue;
+            boff[l] = bTot;
+            bTot += (size_t)lf.ntpad * lf.npad;
+        }
+        if (int rc = slab_grow(c, c->arenaB, c->cap_B, bTot)) return rc;
+    }
+    // task lists: the tiles of B; per test tile its slabs of training rows, next to each other in the list and in d_pgpart
+    const size_t planes = (var ? 2 : 1) * (size_t)D * TB;
+    std::vector<PredBetaTask> beta;
+    std::vector<PredGradTask> tasks;
+    std::vector<PredGradFinTask> fin;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.nt == 0) continue;
+        const int nslab = (lf.n + PGRAD_SLAB - 1) / PGRAD_SLAB;
+        for (int i = 0; i < lf.ntpad / TB; ++i) {
+            PredGradFinTask f{};
+            f.nslab = nslab;
+            f.nrows = std::min(TB, lf.nt - i * TB);
+            fin.push_back(f);
+            for (int s = 0; s < nslab; ++s) tasks.push_back(PredGradTask{});
+        }
+    }
+    if (int rc = c->d_pgpart.grow(c, tasks.size() * planes)) return rc;
+    if (int rc = c->d_pgout.grow(c, (var ? 2 : 1) * nr * (size_t)D)) return rc;
+    size_t ti = 0, fi = 0;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.nt == 0) continue;
+        const LeafDev& d = c->h_leaves[l];
+        const int nslab = (lf.n + PGRAD_SLAB - 1) / PGRAD_SLAB;
+        double* Bl = var ? c->arenaB + boff[l] : nullptr;
+        for (int i = 0; i < lf.ntpad / TB; ++i) {
+            PredGradFinTask& f = fin[fi++];
+            f.part = c->d_pgpart.p + ti * planes;
+            f.xt = d.Xtg + (size_t)i * TB;
+            f.dmu = c->d_pgout.p + (size_t)lf.route_off + (size_t)i * TB;
+            f.dvar = var ? f.dmu + nr * (size_t)D : nullptr;
+            f.info = d.info;
+            f.pstride = (long long)planes;
+            f.ldo = (long long)nr;
+            f.ldt = lf.ntpad;
+            f.kid = lf.kid;
+            for (int s = 0; s < nslab; ++s) {
+                PredGradTask& g = tasks[ti];
+                g.xt = f.xt;
+                g.xg = d.Xg;
+                g.alpha = d.alpha;
+                g.B = var ? Bl + (size_t)i * TB : nullptr;
+                g.part = c->d_pgpart.p + ti * planes;
+                g.ldt = lf.ntpad;
+                g.ldg = lf.npad;
+                g.nrows = f.nrows;
+                g.c0 = s * PGRAD_SLAB;
+                g.c1 = std::min(lf.n, g.c0 + PGRAD_SLAB);
+                g.kid = lf.kid;
+                ++ti;
+            }
+            if (!var) continue;
+            const LeafHost& ow = c->leaves[lf.owner];       // a COPY leaf: its source's L^-T, its own Vt
+            for (int j = 0; j * TB < lf.n; ++j) {
+                PredBetaTask b{};
+                b.gemm.A = d.Vt + (size_t)i * TB;
+                b.gemm.B = c->arenaX + c->gxoff[lf.owner] + (size_t)j * TB;
+                b.gemm.C = Bl + (size_t)i * TB + (size_t)j * TB * lf.ntpad;
+                b.gemm.lda = b.gemm.ldc = lf.ntpad;
+                b.gemm.ldb = ow.npad;
+                b.gemm.k0 = j * TB;
+                b.gemm.k1 = lf.n - lf.n % KC2;
+                b.n = lf.n;
+                beta.push_back(b);
+            }
+        }
+    }
+    c->stage_top = 0;       // (the stream is idle: every entry point synchronises before it returns)
+    if (int rc = stage_upload_list(c, c->pgbeta, beta)) return rc;
+    if (int rc = stage_upload_list(c, c->pgtasks, tasks)) return rc;
+    if (int rc = stage_upload_list(c, c->pgfin, fin)) return rc;
+    if (int rc = stage_done(c)) return rc;
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    if (int rc = ensure_dinv(c)) return rc;
+    if (int rc = ensure_alpha(c)) return rc;
+    if (var) {
+        if (int rc = xinv_fill(c)) return rc;
+        tile_predbeta_kernel<<<(unsigned)beta.size(), 256, 0, c->stream>>>(c->pgbeta.p);
+        pred_inputgrad_kernel<true><<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->pgtasks.p, c->d_kp.p, D);
+    } else {
+        pred_inputgrad_kernel<false><<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->pgtasks.p, c->d_kp.p, D);
+    }
+    pred_inputgrad_finish_kernel<<<(unsigned)fin.size(), 128, 0, c->stream>>>(c->pgfin.p, c->d_kp.p, D);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (var) c->xinv_all = true;
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = ms * 1e-3;
+    if (dmu_out)
+        HIPCHK(c, hipMemcpy2D(dmu_out, (size_t)ld * sizeof(double), c->d_pgout.p, nr * sizeof(double), nr * sizeof(double), (size_t)D,
+                              hipMemcpyDeviceToHost));
+    if (dvar_out)
+        HIPCHK(c, hipMemcpy2D(dvar_out, (size_t)ld * sizeof(double), c->d_pgout.p + nr * (size_t)D, nr * sizeof(double),
+                              nr * sizeof(double), (size_t)D, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1772,6 +1772,249 @@ __global__ __launch_bounds__(256, 2) void tile_predcov_kernel(const PredCovTask*
     DSMGP_KIND_DISPATCH(p.kind, K, predcov_epilogue<K>(g, p, D, acc, smem));
 }
 
+// ---------------------------------------------------------------------------------------------
+// Input gradients of the predictive moments (dsmgp_predict_gradients).  Per leaf, routed test row t and dimension d, with
+// g_d(t, i) = dk(x_t, x_i) / dx_{t,d}:
+//   dmu[t, d]  = sum_i alpha_i g_d(t, i)
+//   dvar[t, d] = dk(x_t, x_t) / dx_{t,d} - 2 sum_i beta_{t,i} g_d(t, i),   beta_t = K_y^-1 k_t = L^-T v_t  (v_t = row t of Vt)
+// (noise and jitter are constants: dvar is the derivative of dsmgp_predict_fetch's var as it stands).
+//
+// Step 1, tile_predbeta_kernel: B = Vt L^-1 (ntpad x npad per leaf, rows beta_t^T) on the f64 matrix cores.  The L^-T arena of
+// the gradient pass holds Xt(i, c) = L^-1(c, i) -- the (column, k) layout the main loop reads as its B operand -- and row tile
+// j of Xt is defined from column 128 j on only (L^-1 is lower triangular), so tile (i, j) of B sums the K range [128 j, n):
+// whole chunks in the main loop, the last n % 8 columns with plain fmas (tile_predcov_kernel's rule: what columns n..npad of
+// Vt hold never enters).  One task per tile, no split-K: the order of the sum is fixed.  The whole tile is stored; its rows
+// >= nt and columns >= n are never read.
+struct PredBetaTask {
+    TileTask gemm;          // A = Vt row tile i, B = Xt row tile j, K range [128 j, n - n % 8), C = tile (i, j) of B
+    int n;                  // real columns of Vt: the epilogue sums columns [gemm.k1, n)
+    int pad;
+};
+
+__global__ __launch_bounds__(256, 2) void tile_predbeta_kernel(const PredBetaTask* __restrict__ tasks) {
+    __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
+    double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
+    double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
+    const PredBetaTask g = tasks[blockIdx.x];
+    d4 acc[4][4];
+    gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+    for (int k = g.gemm.k1; k < g.n; ++k) {
+        const double* ca = g.gemm.A + (size_t)k * g.gemm.lda + wr * 64 + l15;
+        const double* cb = g.gemm.B + (size_t)k * g.gemm.ldb + wc * 64 + l4;
+        double a[4], b[16];
+#pragma unroll
+        for (int rn = 0; rn < 4; ++rn) a[rn] = ca[16 * rn];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) b[i] = cb[16 * (i >> 2) + 4 * (i & 3)];
+#pragma unroll
+        for (int rn = 0; rn < 4; ++rn)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i >> 2][rn][i & 3] = fma(a[rn], b[i], acc[i >> 2][rn][i & 3]);
+    }
+    const size_t ldc = (size_t)g.gemm.ldc;
+#pragma unroll
+    for (int rn = 0; rn < 4; ++rn) {
+        const int r = wr * 64 + 16 * rn + l15;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+            AS_GLOBAL_F64(g.gemm.C)[r + (size_t)c * ldc] = acc[i >> 2][rn][i & 3];
+        }
+    }
+}
+
+// Step 2, pred_inputgrad_kernel: one task = a 128-row test tile of one leaf x a slab of PGRAD_SLAB training rows.  Thread
+// (r = t & 127, h = t >> 7) owns test row r and the slab's training rows of parity h, PGRAD_SUB of them at a time: their
+// coordinates go through LDS in rounds of PGRAD_DC dimensions (a broadcast read per wave), the test row's own coordinates and
+// B[r, i] come straight from memory (consecutive lanes, consecutive addresses).  The 2 x PGRAD_DC sums of a chunk of dimensions
+// live in registers whatever D is; the kinds whose derivative carries the kernel value (IsoSE, ArdSEProduct, Matern) first sum
+// the exponent over ALL dimensions and evaluate the factor once per pair and chunk -- once per pair up to D = PGRAD_DC.
+//   IsoSE         g_d = -k D_d / l^2                      ArdSEProduct  g_d = -k D_d / l_d^2        (D_d = x_{t,d} - x_{i,d})
+//   ArdSE         g_d = -sigma^2 exp(-D_d^2 / 2 l_d^2) D_d / l_d^2      (term d only)
+//   IsoLinear     g_d = x_{i,d} / l^2                     ArdLinear     g_d = x_{i,d} / l_d^2
+//   Matern        g_d = -sigma^2 exp(-s) c(s) (2 nu / l_d^2) D_d,  c(s) of tile_graddot_matern_kernel: nothing divides by r
+// The two parities meet through LDS (h = 0 + h = 1), the slabs are added in ascending order by pred_inputgrad_finish_kernel:
+// no atomics, the same bits from call to call.  Rows >= nrows and training rows >= n are neither read nor written.
+constexpr int PGRAD_DC = 8;       // dimensions per chunk (the accumulators of a thread)
+constexpr int PGRAD_SUB = 32;     // training rows per staging round (16 pair factors per thread)
+constexpr int PGRAD_SLAB = 128;   // training rows per task
+
+struct PredGradTask {
+    const double* xt;       // gathered test inputs, offset to the tile's first row (ld = ldt)
+    const double* xg;       // gathered training inputs of the leaf (ld = ldg)
+    const double* alpha;    // the leaf's alpha
+    const double* B;        // the leaf's B = Vt L^-1, offset to the tile's first row (ld = ldt); unused by the mean-only kernel
+    double* part;           // this task's sums: plane d (mean), plane D + d (variance; absent in the mean-only form), 128 rows each
+    int ldt, ldg;
+    int nrows;              // valid test rows of the tile
+    int c0, c1;             // training rows [c0, c1), c1 <= n
+    int kid;
+};
+
+template <int KIND, bool VAR>
+__device__ __forceinline__ void pred_inputgrad_body(const PredGradTask& tk, const KParam& p, int D, double (*sc)[PGRAD_SUB],
+                                                    double* sal, double* red) {
+    constexpr int DC = PGRAD_DC, SUB = PGRAD_SUB, NP = PGRAD_SUB / 2;
+    constexpr bool PAIR = (KIND == 0 || KIND == 4 || KIND == 5);   // the derivative carries the kernel value of the pair
+    const int t = threadIdx.x, r = t & (TB - 1), h = t >> 7;
+    const bool live = r < tk.nrows;
+    const int nround = (D + DC - 1) / DC;
+    const double c2 = (KIND == 5) ? matern_c2(p) : 0.0;
+    const double c1 = (c2 != 0.0) ? c2 : 1.0;
+    // coordinates of training rows s0 .. s0 + sn - 1, dimensions of round rd, and their alpha -> LDS
+    auto stage = [&](int rd, int s0, int sn) {
+        const int d0 = rd * DC, dn = min(DC, D - d0);
+        __syncthreads();
+        if (t < DC * SUB) {
+            const int d = t / SUB, i = t % SUB;
+            sc[d][i] = (d < dn && i < sn) ? tk.xg[s0 + i + (size_t)(d0 + d) * tk.ldg] : 0.0;
+        }
+        if (t < SUB) sal[t] = (t < sn) ? tk.alpha[s0 + t] : 0.0;
+        __syncthreads();
+    };
+    for (int ch = 0; ch < nround; ++ch) {
+        const int e0 = ch * DC, en = min(DC, D - e0);
+        double xa[DC], am[DC], av[DC];
+#pragma unroll
+        for (int d = 0; d < DC; ++d) {
+            xa[d] = (live && d < en) ? tk.xt[r + (size_t)(e0 + d) * tk.ldt] : 0.0;
+            am[d] = 0.0;
+            av[d] = 0.0;
+        }
+        for (int s0 = tk.c0; s0 < tk.c1; s0 += SUB) {
+            const int sn = min(SUB, tk.c1 - s0);
+            double f[NP];
+            if (PAIR) {
+#pragma unroll
+                for (int j = 0; j < NP; ++j) f[j] = 0.0;
+                for (int rd = 0; rd < nround; ++rd) {
+                    const int d0 = rd * DC, dn = min(DC, D - d0);
+                    stage(rd, s0, sn);
+                    if (live) {
+#pragma unroll
+                        for (int d = 0; d < DC; ++d)
+                            if (d < dn) {
+                                const double a = (rd == ch) ? xa[d] : tk.xt[r + (size_t)(d0 + d) * tk.ldt];
+                                const double nhd = (KIND == 0) ? 0.0 : p.nh[d0 + d];
+#pragma unroll
+                                for (int j = 0; j < NP; ++j) {
+                                    const double u = a - sc[d][h + 2 * j];
+                                    f[j] = (KIND == 0) ? fma(u, u, f[j]) : fma(u * u, nhd, f[j]);
+                                }
+                            }
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < NP; ++j) {
+                    if (KIND == 0) f[j] = -(p.sigma2 * exp_nonpos(f[j] * p.nh0)) * p.il2;
+                    else if (KIND == 4) f[j] = p.sigma2 * exp_nonpos(f[j]);
+                    else {
+                        const double s = sqrt(f[j]);
+                        f[j] = -(p.sigma2 * exp_nonpos(-s) * fma(c2, s, c1));
+                    }
+                }
+            }
+            if (!PAIR || nround > 1) stage(ch, s0, sn);      // (one round: the coordinates of the chunk are still there)
+            if (live) {
+#pragma unroll
+                for (int j = 0; j < NP; ++j) {
+                    const int i = h + 2 * j;
+                    if (i < sn) {
+                        const double al = sal[i];
+                        const double be = VAR ? tk.B[r + (size_t)(s0 + i) * tk.ldt] : 0.0;
+                        const double wa = PAIR ? al * f[j] : al;
+                        const double wb = PAIR ? be * f[j] : be;
+#pragma unroll
+                        for (int d = 0; d < DC; ++d)
+                            if (d < en) {
+                                const double xc = sc[d][i];
+                                double g;
+                                if (KIND == 0) g = xa[d] - xc;
+                                else if (KIND == 4) g = (xa[d] - xc) * (2.0 * p.nh[e0 + d]);
+                                else if (KIND == 5) g = (xa[d] - xc) * p.nh[e0 + d];
+                                else if (KIND == 1) {
+                                    const double u = xa[d] - xc, nhd = p.nh[e0 + d];
+                                    g = (p.sigma2 * exp_nonpos((u * u) * nhd)) * (u * (2.0 * nhd));
+                                } else if (KIND == 2) g = xc * p.il2;
+                                else g = xc * p.nh[e0 + d];
+                                am[d] = fma(wa, g, am[d]);
+                                if (VAR) av[d] = fma(wb, g, av[d]);
+                            }
+                    }
+                }
+            }
+        }
+        // the two parities of the slab: h = 0 + h = 1
+        __syncthreads();
+        if (h == 1) {
+#pragma unroll
+            for (int d = 0; d < DC; ++d) {
+                red[d * TB + r] = am[d];
+                if (VAR) red[(DC + d) * TB + r] = av[d];
+            }
+        }
+        __syncthreads();
+        if (h == 0 && live) {
+#pragma unroll
+            for (int d = 0; d < DC; ++d)
+                if (d < en) {
+                    tk.part[(size_t)(e0 + d) * TB + r] = am[d] + red[d * TB + r];
+                    if (VAR) tk.part[(size_t)(D + e0 + d) * TB + r] = av[d] + red[(DC + d) * TB + r];
+                }
+        }
+    }
+}
+
+template <bool VAR>
+__global__ __launch_bounds__(256) void pred_inputgrad_kernel(const PredGradTask* __restrict__ tasks,
+                                                             const KParam* __restrict__ kp, int D) {
+    __shared__ double sc[PGRAD_DC][PGRAD_SUB];
+    __shared__ double sal[PGRAD_SUB];
+    __shared__ double red[(VAR ? 2 : 1) * PGRAD_DC * TB];     // the sums of parity h = 1: mean planes, then variance planes
+    const PredGradTask tk = tasks[blockIdx.x];
+    const KParam p = kp[tk.kid];
+    DSMGP_KIND_DISPATCH(p.kind, K, pred_inputgrad_body<K, VAR>(tk, p, D, sc, sal, red));
+}
+
+// Step 3: the slabs of a test tile in ascending order, the self term dk(x_t, x_t) / dx_{t,d} (2 x_{t,d} / l_d^2 for the linear
+// kinds, 0 for the stationary ones) and the factor -2; NaN rows for a leaf whose factorisation failed.  One workgroup per tile.
+struct PredGradFinTask {
+    const double* part;     // the tile's first slab; slab s at part + s * pstride
+    const double* xt;       // gathered test inputs of the tile's rows (ld = ldt)
+    double* dmu;            // column d at dmu + d * ldo, offset to the tile's first entry
+    double* dvar;           // likewise, or NULL (mean only)
+    const int* info;
+    long long pstride, ldo;
+    int nslab, nrows, ldt, kid;
+};
+
+__global__ __launch_bounds__(128) void pred_inputgrad_finish_kernel(const PredGradFinTask* __restrict__ tasks,
+                                                                    const KParam* __restrict__ kp, int D) {
+    const PredGradFinTask tk = tasks[blockIdx.x];
+    const KParam p = kp[tk.kid];
+    const int r = threadIdx.x;
+    if (r >= tk.nrows) return;
+    const bool bad = *tk.info != 0;
+    const double qnan = __builtin_nan("");
+    for (int d = 0; d < D; ++d) {
+        double sm = 0.0, sv = 0.0;
+        for (int s = 0; s < tk.nslab; ++s) {
+            const double* ps = tk.part + (size_t)s * tk.pstride + r;
+            sm += ps[(size_t)d * TB];
+            if (tk.dvar) sv += ps[(size_t)(D + d) * TB];
+        }
+        tk.dmu[r + (size_t)d * tk.ldo] = bad ? qnan : sm;
+        if (tk.dvar) {
+            double self = 0.0;
+            if (p.kind == 2) self = 2.0 * tk.xt[r + (size_t)d * tk.ldt] * p.il2;
+            else if (p.kind == 3) self = 2.0 * tk.xt[r + (size_t)d * tk.ldt] * p.nh[d];
+            tk.dvar[r + (size_t)d * tk.ldo] = bad ? qnan : fma(-2.0, sv, self);
+        }
+    }
+}
+
 // trace(K_y^-1) = |L^-1|_F^2 without forming K_y^-1: sum of squares of one row tile of Xt (columns >= its block)
 struct FrobTask {
     const double* X;   // Xt + row0

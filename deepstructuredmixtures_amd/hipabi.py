@@ -52,6 +52,7 @@ SIGNATURES = {
     "dsmgp_predict_fetch": (C.c_int, [_ctx, _dp, _dp]),
     "dsmgp_predict_leaves": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, _lp, _lp, _dp, _dp]),
     "dsmgp_predict_cov": (C.c_int, [_ctx, C.c_int32, C.c_int32, _dp, C.c_int64, _dp]),
+    "dsmgp_predict_gradients": (C.c_int, [_ctx, _dp, _dp, C.c_int64, _dp]),
     "dsmgp_gradients": (C.c_int, [_ctx, _dp, C.c_int32]),
     "dsmgp_loo": (C.c_int, [_ctx, _dp, _dp, _dp, _dp]),
     "dsmgp_loo_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp]),
@@ -324,6 +325,21 @@ class Context:
         self._chk(self.lib.dsmgp_predict_cov(self.h, int(leaf), 1 if with_noise else 0, S.ctypes.data_as(_dp), nt, C.byref(sec)))
         self.cov_seconds = sec.value
         return S
+
+    def predict_gradients(self, want_var=True):
+        """`(dmu, dvar)`: the gradients of the predictive mean and variance of every (leaf, routed test row) entry of
+        `predict_fetch` with respect to the test point (dsmgp_predict_gradients; needs `predict_run` on the current fit), both
+        `(route_total, D)` float64 arrays in Fortran order.  `want_var=False` returns `(dmu, None)` and computes neither L^-T
+        nor K_tn K_y^-1; `dmu` is the same bits either way.  Entries of leaves with `info != 0` come back as NaN.  The device
+        time of the call is left in `self.grad_seconds`."""
+        n = int(self.route_total)
+        dmu = np.empty((n, self.D), dtype=np.float64, order="F")
+        dvar = np.empty((n, self.D), dtype=np.float64, order="F") if want_var else None
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_predict_gradients(self.h, dmu.ctypes.data_as(_dp),
+                                                   dvar.ctypes.data_as(_dp) if want_var else None, max(1, n), C.byref(sec)))
+        self.grad_seconds = sec.value
+        return dmu, dvar
 
     def set_option(self, option, value):
         """include/dsmgp_hip.h DSMGP_OPT_*: OPT_ARD_LENGTHSCALE_GRADIENT = 1, OPT_FUSED_GRAM = 2, OPT_FUSED_STEPS = 3."""
@@ -746,6 +762,25 @@ class MultiContext:
         raise DsmgpError(E_STATE, "predict_cov: the full covariance of a leaf is served by a single Context only "
                                   "(MultiContext spreads the leaf table over several devices)")
 
+    def predict_gradients(self, want_var=True):
+        """`Context.predict_gradients` per sub-context, put back into the entry order of the whole leaf table;
+        `self.grad_seconds` is the longest of the sub-contexts' device times."""
+        _, rptr, _ = self._test
+        res = self._each(lambda s: s.predict_gradients(want_var))
+        D = self.act[0].D
+        dmu = np.empty((self.route_total, D), dtype=np.float64, order="F")
+        dvar = np.empty((self.route_total, D), dtype=np.float64, order="F") if want_var else None
+        for (m, v), loc in zip(res, self.part):
+            pos = 0
+            for g in loc:
+                c = int(rptr[g + 1] - rptr[g])
+                dmu[rptr[g]:rptr[g + 1]] = m[pos:pos + c]
+                if want_var:
+                    dvar[rptr[g]:rptr[g + 1]] = v[pos:pos + c]
+                pos += c
+        self.grad_seconds = max(s.grad_seconds for s in self.act)
+        return dmu, dvar
+
     def aggregate_partial(self, family, leaf_coef=None, leaf_group=None, n_groups=0):
         """Partial sums of all sub-contexts added in context order (the sums are linear in the leaves)."""
         coef = None if leaf_coef is None else np.asarray(leaf_coef, dtype=np.float64)
@@ -1128,6 +1163,10 @@ class StreamingContext:
     def predict_cov(self, leaf, nt, with_noise=True):
         raise DsmgpError(E_STATE, "predict_cov: a streaming pass discards K_tn L^-T with its leaf group; "
                                   "use a resident Context for the full covariance of a leaf")
+
+    def predict_gradients(self, want_var=True):
+        raise DsmgpError(E_STATE, "predict_gradients: a streaming pass discards alpha, K_tn L^-T and L^-T with their leaf group; "
+                                  "use a resident Context for the input gradients of the prediction")
 
     def predict_leaves(self, Xt, route_ptr, route_idx):
         self.set_test(Xt, route_ptr, route_idx)

@@ -384,12 +384,18 @@ def update_cholesky(gp):
     return gp
 
 
-def prediction(gp, xtest, full_cov=False):
+def prediction(gp, xtest, full_cov=False, input_gradients=False):
     """`prediction(gp, xtest)` -> (mu, diag of Sigma) (`src/gaussianprocess.jl:110-137`; only the
     diagonal of Sigma is ever consumed, `src/common.jl:136,147`).  `full_cov=True` -> (mu, Sigma) as the reference returns
-    them: the full n_t x n_t matrix K_tt - V'V + noise I from the device (`Context.predict_cov`), symmetric to the bit."""
+    them: the full n_t x n_t matrix K_tt - V'V + noise I from the device (`Context.predict_cov`), symmetric to the bit.
+    `input_gradients=True` -> (mu, var, dmu, dvar) with the (n_t, D) gradients of both moments with respect to the test
+    point, from the device (`Context.predict_gradients`; no reference counterpart)."""
     xt = _test_matrix(gp.model, xtest)
+    if input_gradients and full_cov:
+        raise ValueError("prediction: full_cov and input_gradients are separate calls")
     if xt.shape[0] == 0:
+        if input_gradients:
+            return np.zeros(0), np.zeros(0), np.zeros((0, xt.shape[1])), np.zeros((0, xt.shape[1]))
         return np.zeros(0), (np.zeros((0, 0)) if full_cov else np.zeros(0))
     # registered like the test set of a tree model (cached by content): a loop of update_cholesky! + prediction on the same
     # rows carries them through the factorisation launches from its second pass on, and prediction only finishes the moments
@@ -397,6 +403,9 @@ def prediction(gp, xtest, full_cov=False):
     mu, var = _leaf_moments(gp.model, xt, rc)
     if full_cov:
         return mu, gp.model.ctx.predict_cov(0, xt.shape[0], True)
+    if input_gradients:
+        dmu, dvar = gp.model.ctx.predict_gradients()
+        return mu, var, dmu, dvar
     return mu, var
 
 
@@ -1096,6 +1105,136 @@ def predict(model, xtest):
     if model.family == "dsmgp":
         return _aggregate_dsmgp_flat(model, xt.shape[0], rc, mu, var)
     return _aggregate_poe(model, xt, rc["ptr"], mu, var)
+
+
+def aggregate_input_gradients(family, mu, var, dmu, dvar, ent, coef=None, group=None, G=0, plain=False, kss_prior=None,
+                              noise_prior=None, dkss_prior=None):
+    """(dmu, dvar), each (n_t, D): the gradients of the aggregated prediction of one family with respect to the test point,
+    from the per-entry moments `mu`, `var` (length E) and their input gradients `dmu`, `dvar` (E x D).  `ent[r]` lists the
+    (leaf, entry) pairs of test row r in ascending entry order; the other arguments are those of the aggregation itself
+    (`dsmgp_aggregate`: family 0 mixture, 1 PoE, 2 gPoE, 3 rBCM; `coef[l]` = W_l or beta_l, `group[l]` and `G` for rBCM, whose
+    prior term is s = `kss_prior[r]` + `noise_prior` with ds/dx = `dkss_prior[r]`, zero for a stationary kernel).  Pure
+    NumPy on the host; nothing is modified.
+      mixture   dmu = sum W dmu_l,  dvar = sum W [dvar_l + 2 (mu_l - mu) dmu_l]  (plain: sum W dvar_l); a leaf variance the
+                aggregation clamps (sigma2_l <= 0 -> 1e-8) is a constant: dvar_l = 0
+      PoE/gPoE  T = sum beta / sigma2_l, P = sum beta mu_l / sigma2_l, mu = P / T, var = 1 / T:
+                dT = -sum beta dvar_l / sigma2_l^2, dP = sum beta (dmu_l / sigma2_l - mu_l dvar_l / sigma2_l^2),
+                dmu = (dP - mu dT) / T, dvar = -dT / T^2
+      rBCM      per group g that saw the row T_g, P_g, dT_g, dP_g as above with beta = 1; beta_g = (log s + log T_g) / 2,
+                dbeta_g = (ds / s + dT_g / T_g) / 2; C = 1 / s + sum_g beta_g (T_g - 1 / s), m = sum_g beta_g P_g,
+                dC = -ds / s^2 + sum_g [dbeta_g (T_g - 1 / s) + beta_g (dT_g + ds / s^2)], dm = sum_g (dbeta_g P_g + beta_g dP_g),
+                mu = m / C, var = 1 / C: dmu = (dm - mu dC) / C, dvar = -dC / C^2
+    The tree is piecewise constant in x (which leaves see a row does not change inside a region): this is the gradient
+    inside the row's region."""
+    mu = np.asarray(mu, dtype=np.float64)
+    var = np.asarray(var, dtype=np.float64)
+    dmu = np.asarray(dmu, dtype=np.float64)
+    dvar = np.asarray(dvar, dtype=np.float64)
+    n_t = len(ent)
+    D = dmu.shape[1]
+    rows = np.array([r for r, er in enumerate(ent) for _ in er], dtype=np.int64)
+    leaf = np.array([l for er in ent for l, _ in er], dtype=np.int64)
+    e = np.array([k for er in ent for _, k in er], dtype=np.int64)
+    m, v, dm, dv = mu[e], var[e], dmu[e], dvar[e]
+
+    def rowsum(a, idx=rows, n=n_t):
+        out = np.zeros((n,) + a.shape[1:])
+        np.add.at(out, idx, a)
+        return out
+
+    if family == 0:
+        w = np.asarray(coef, dtype=np.float64)[leaf]
+        clamped = ~(v > 0)
+        dv = np.where(clamped[:, None], 0.0, dv)
+        s0 = rowsum(w * m)
+        out_dmu = rowsum(w[:, None] * dm)
+        if plain:
+            return out_dmu, rowsum(w[:, None] * dv)
+        return out_dmu, rowsum(w[:, None] * (dv + 2.0 * (m - s0[rows])[:, None] * dm))
+    if family != 3:
+        b = np.asarray(coef, dtype=np.float64)[leaf]
+        t = b / v
+        T = rowsum(t)
+        P = rowsum(t * m)
+        dT = rowsum(-(t / v)[:, None] * dv)
+        dP = rowsum(t[:, None] * dm - (t * m / v)[:, None] * dv)
+        mu_a = P / T
+        return (dP - mu_a[:, None] * dT) / T[:, None], -dT / (T * T)[:, None]
+    grp = np.asarray(group, dtype=np.int64)[leaf]
+    key = rows * G + grp
+    t = 1.0 / v
+    T = rowsum(t, key, n_t * G).reshape(n_t, G)
+    P = rowsum(t * m, key, n_t * G).reshape(n_t, G)
+    dT = rowsum(-(t / v)[:, None] * dv, key, n_t * G).reshape(n_t, G, D)
+    dP = rowsum(t[:, None] * dm - (t * m / v)[:, None] * dv, key, n_t * G).reshape(n_t, G, D)
+    seen = np.zeros(n_t * G, dtype=bool)
+    seen[key] = True
+    seen = seen.reshape(n_t, G)
+    s = np.asarray(kss_prior, dtype=np.float64) + float(noise_prior)
+    ds = np.zeros((n_t, D)) if dkss_prior is None else np.asarray(dkss_prior, dtype=np.float64)
+    Ts = np.where(seen, T, 1.0)
+    beta = np.where(seen, 0.5 * (np.log(s)[:, None] + np.log(Ts)), 0.0)
+    dbeta = np.where(seen[:, :, None], 0.5 * ((ds / s[:, None])[:, None, :] + dT / Ts[:, :, None]), 0.0)
+    ds_s2 = ds / (s * s)[:, None]
+    C = 1.0 / s + np.sum(beta * (np.where(seen, T, 0.0) - np.where(seen, 1.0, 0.0) / s[:, None]), axis=1)
+    mm = np.sum(beta * P, axis=1)
+    dC = -ds_s2 + np.sum(dbeta * (Ts - 1.0 / s[:, None])[:, :, None] + beta[:, :, None] * (dT + ds_s2[:, None, :]), axis=1)
+    dmm = np.sum(dbeta * P[:, :, None] + beta[:, :, None] * dP, axis=1)
+    mu_a = mm / C
+    return (dmm - mu_a[:, None] * dC) / C[:, None], -dC / (C * C)[:, None]
+
+
+def _prior_diag_grad(lf, xt):
+    """d k(x, x) / dx of the leaf's kernel at the rows of `xt`: 2 x_d / l_d^2 for the linear kinds, 0 for the stationary ones."""
+    k = lf.kernel
+    if k.kind == KIND_ARD_LINEAR:
+        return 2.0 * xt * np.exp(-2.0 * k.logl)[None, :]
+    if k.kind == KIND_ISO_LINEAR:
+        return 2.0 * xt / np.exp(k.logl) ** 2
+    return np.zeros(xt.shape)
+
+
+def predict_gradients(model, xtest):
+    """(mu, var, dmu, dvar): `predict(model, xtest)` -- the same bits -- and the gradients of both moments with respect to
+    the test point, `dmu`, `dvar` of shape (n_t, D), for a DSMGP, PoE, gPoE, rBCM or a single GaussianProcess (no reference
+    counterpart).  The per-(leaf, row) gradients come from the device (`Context.predict_gradients`), the aggregation runs on
+    the host (`aggregate_input_gradients`).  The tree is piecewise constant in x -- which leaves a row reaches changes only
+    at a split threshold, where the prediction itself jumps -- so the result is the gradient inside the row's region.
+    Refused: a DSMGP whose sum weights are not normalised (ValueError: `predict` then shifts the means by mu_min - 1, which
+    is not differentiable), a model sharded over several ranks (NotImplementedError), and contexts that do not keep what the
+    device call reads (the streaming context: DsmgpError)."""
+    if isinstance(model, GaussianProcess):
+        mu, var, dmu, dvar = prediction(model, xtest, input_gradients=True)
+        return mu, np.where(var <= 0, EPS, var), np.ascontiguousarray(dmu), np.ascontiguousarray(dvar)
+    if model.shard.world > 1:
+        raise NotImplementedError("predict_gradients: the model is sharded over several ranks; the gradients are aggregated on "
+                                  "the host of a single rank only")
+    if model.family == "dsmgp" and model.root.kind != "gp" and not model.tindex.weights_normalised():
+        raise ValueError("predict_gradients: the sum weights are not normalised; predict then shifts the means by mu_min - 1, "
+                         "which is not differentiable")
+    if not hasattr(_ctx_type(model), "predict_gradients"):
+        raise NotImplementedError(f"predict_gradients: {_ctx_type(model).__name__} has no predict_gradients")
+    if issubclass(_ctx_type(model), hipabi.StreamingContext):
+        raise hipabi.DsmgpError(hipabi.E_STATE, "predict_gradients: a streaming context discards what the input gradients read")
+    xt = _test_matrix(model, xtest)
+    n_t, D = xt.shape
+    if n_t == 0:
+        return np.zeros(0), np.zeros(0), np.zeros((0, D)), np.zeros((0, D))
+    mu, var = predict(model, xt)            # routes, registers and runs as predict does; the moments stay on the device
+    rc = _routing(model, xt)                # the host's lists: entry by entry those of a context that routed the rows itself
+    ptr, idx = rc["lptr"], rc["lidx"]
+    mu_l, var_l = model.ctx.predict_fetch()
+    dmu_l, dvar_l = model.ctx.predict_gradients()
+    ent = [[] for _ in range(n_t)]
+    for l in range(len(ptr) - 1):
+        for k in range(int(ptr[l]), int(ptr[l + 1])):
+            ent[int(idx[k])].append((l, k))
+    family, coef, group, G, plain, prior = _aggregation_spec(model)
+    kw = {}
+    if family == hipabi.AGG_RBCM:
+        kw = dict(kss_prior=_prior_diag(prior, xt), noise_prior=np.exp(2 * prior.logNoise), dkss_prior=_prior_diag_grad(prior, xt))
+    dmu, dvar = aggregate_input_gradients(family, mu_l, var_l, dmu_l, dvar_l, ent, coef=coef, group=group, G=G, plain=plain, **kw)
+    return mu, var, dmu, dvar
 
 
 def _ctx_type(model):

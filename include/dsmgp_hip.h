@@ -151,6 +151,33 @@ int dsmgp_predict_leaves(dsmgp_ctx* ctx, const double* Xt, int64_t n_t, int32_t 
  * one -- and is NOT counted by dsmgp_estimate_bytes / dsmgp_memory; it is dropped with the test set, the leaf table and
  * dsmgp_release. */
 int dsmgp_predict_cov(dsmgp_ctx* ctx, int32_t leaf, int32_t with_noise, double* Sigma_out, int64_t ld, double* seconds);
+/* Gradients of the predictive mean and variance with respect to the test point (not a call of the reference): for every
+ * (leaf, routed test row t) -- the entries of dsmgp_predict_fetch, in its order -- and every input dimension d,
+ *   dmu_out[e + d * ld]  = d mu / d x_{t,d}  = sum_i alpha_i dk(x_t, x_i) / dx_{t,d},
+ *   dvar_out[e + d * ld] = d var / d x_{t,d} = dk(x_t, x_t) / dx_{t,d} - 2 sum_i beta_{t,i} dk(x_t, x_i) / dx_{t,d},
+ * beta_t = K_y^-1 k_t: the derivative of var as dsmgp_predict_fetch returns it (noise and jitter are constants).  Both outputs
+ * are route_total x D, column-major with leading dimension ld >= route_total (DSMGP_E_ARG otherwise); either may be NULL.
+ * The kernel derivatives are true derivatives, finite at x_t = x_i (nothing divides by a distance): with D_d = x_{t,d} - x_{i,d},
+ * -k D_d / l_d^2 (IsoSE, ArdSEProduct), -sigma^2 exp(-D_d^2 / 2 l_d^2) D_d / l_d^2 (ArdSE: term d only), x_{i,d} / l_d^2 (the
+ * linear kinds, whose dk(x_t, x_t) / dx_{t,d} = 2 x_{t,d} / l_d^2; it is 0 for the stationary kinds), and
+ * -sigma^2 exp(-s) c(s) (2 nu / l_d^2) D_d for the Matern kinds, c(s) as in dsmgp_gradients.  Any D.
+ * Needs dsmgp_predict_run on the current fit (DSMGP_E_STATE otherwise), on either route to K_tn L^-T: rows that rode through the
+ * fit, or the standalone sweep; one lane or two.  No routed rows at all: success, nothing written.  Leaves whose fit reported
+ * info != 0 get NaN rows, the others are unaffected.  Sums are added in a fixed order: the same bits from call to call, and
+ * dmu_out is the same bits with and without dvar_out.  seconds (may be NULL): device time of the call.
+ * dmu reads alpha (materialised here on first use after a fit) and the inputs only.  dvar needs B = K_tn K_y^-1 = (K_tn L^-T) L^-1:
+ * a tile product on the matrix cores against L^-T of every factor owner (a COPY leaf: its source's), the arena dsmgp_gradients
+ * fills -- read as it is, or filled here, by the rule of dsmgp_loo, and what that call says about dsmgp_gradients and the mask
+ * of dsmgp_set_gradient_leaves holds here too (both are left exactly as they are; the mask does not apply; DSMGP_E_NOMEM /
+ * DSMGP_E_ARG where the lists of the inversion cannot be built).  With dvar_out = NULL none of that is computed or allocated.
+ * dsmgp_predict_fetch, dsmgp_predict_cov, dsmgp_gradients and dsmgp_loo* return the same bits before and after this call.
+ * Memory: B gets an arena of its own, the size of the K_tn arena (ntpad x npad per leaf with routed rows; K_tn L^-T must
+ * survive for dsmgp_predict_cov), plus 2 D doubles per routed row and per 128 training rows of its leaf for the partial sums:
+ * allocated on first use (the arena from the reserved pool when there is one; DSMGP_E_NOMEM with a usable context when it
+ * does not fit), NOT counted by dsmgp_estimate_bytes / dsmgp_memory, dropped with the test set, the leaf table and
+ * dsmgp_release.  Cost: n^2 n_t flops per leaf for B, the order of the standalone sweep, and n n_t D kernel derivatives. */
+int dsmgp_predict_gradients(dsmgp_ctx* ctx, double* dmu_out, double* dvar_out /* route_total x D, column-major, ld */,
+                            int64_t ld, double* seconds);
 
 /* ---- predict(model, x): sum/product aggregation of the leaf moments over the leaves every test row visits, on the
  *      moments the last dsmgp_predict_run left in HBM (replaces the host recursions of src/common.jl:134-149,198-302).

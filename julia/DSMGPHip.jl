@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, predict_cov, loo, loo_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52
+export attach!, detach!, census, predict_cov, predict_gradients, loo, loo_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -459,6 +459,23 @@ function loo(s::Session)
                                        s.h, μ, σ², lpd, sec))
     off = cumsum(vcat(0, cnt))
     return [μ[off[l]+1:off[l+1]] for l in 1:L], [σ²[off[l]+1:off[l+1]] for l in 1:L], lpd
+end
+
+"predict_gradients(s; want_var=true): the gradients of the predictive mean and variance of every (leaf, routed test row) entry of
+the last prediction with respect to the test point (dsmgp_predict_gradients; needs the prediction of the registered rows on the
+current fit).  Returns (dmu, dvar), both `route_total × D` in the entry order of the per-leaf moments; `dvar === nothing` with
+`want_var=false`, which computes neither L⁻ᵀ nor K_tn K_y⁻¹.  Entries of leaves whose fit reported info ≠ 0 come back as NaN."
+function predict_gradients(s::Session; want_var::Bool=true)
+    ptr = Vector{Int64}(undef, length(s.leaves) + 1)
+    GC.@preserve ptr chk(s, ccall(sym(:dsmgp_routes), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), s.h, ptr, C_NULL))
+    nr = Int(ptr[end])
+    D = size(s.gps[1].x, 2)
+    dmu = Matrix{Float64}(undef, nr, D)
+    dvar = want_var ? Matrix{Float64}(undef, nr, D) : nothing
+    sec = Ref{Float64}(0.0)
+    GC.@preserve dmu dvar chk(s, ccall(sym(:dsmgp_predict_gradients), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Float64}),
+                                       s.h, dmu, want_var ? pointer(dvar) : Ptr{Float64}(C_NULL), Int64(max(nr, 1)), sec))
+    return dmu, dvar
 end
 
 "loo_gradients(s): the true derivatives of every leaf's LOO log predictive density with respect to its log-scale hyper-vector

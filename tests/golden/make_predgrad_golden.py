@@ -1,0 +1,292 @@
+"""Generate tests/golden/gp_predgrad.npz: 50-digit input gradients of the predictive mean and variance.
+
+Single leaves.  Everything is evaluated in mpmath at 50 digits from the float64 inputs the device reads, literally as
+include/dsmgp_hip.h states it (dsmgp_predict_gradients): K_y = K + (noise + 1e-8) I, its Cholesky factor, alpha = K_y^-1 (y - m),
+per test row k_t, v_t = L^-1 k_t, beta_t = L^-T v_t,
+    dmu[t, d] = sum_i alpha_i dk(x_t, x_i) / dx_{t,d},   dvar[t, d] = dk(x_t, x_t) / dx_{t,d} - 2 sum_i beta_{t,i} dk(x_t, x_i) / dx_{t,d}.
+Cases: every kernel kind (0-8) at the shapes (n, n_t) = (1, 1), (5, 3), (127, 128), (130, 129), (300, 260) with D = 1 and D = 3,
+and IsoSE / ArdSEProduct with D = 40 at (130, 9).  The cases of one (n, n_t, D) share their inputs (stored once: `in_<n>_<nt>_<D>`);
+every case has a non-zero mean that is not the mean of y, a test row AT a training row (row 0), one row listed twice inside one
+128-row tile (the sweep that forms K_tn L^-T may cut the sums of different row tiles differently: rows of two tiles are equal
+to rounding only), and -- stationary kinds, n_t > 4 -- rows 2 and 3 at +-1e3, where k* underflows in float64 (the 50-digit
+values there are below 1e-300 and stored as the 0.0 they round to).  The targets of (130, 129, 3) are scaled to |y| > 500.
+Every case is checked here against mp.diff of the 50-digit mu(x), sigma^2(x) at three rows, and the float64 dense helper
+(tests/predgrad_dense.py) must stay within predgrad_dense.tolerances of the 50 digits; cond_2(K_y) <= 1e6 is stored.
+
+Aggregates.  On the first 120 test rows of the 41-leaf table of gp_pred.npz (loaded, not modified): per-entry gradients from the
+dense helper in float64 (stored: they are the INPUT of the aggregation, beside the table's own per-entry mu, var) and the
+aggregated (dmu, dvar) of mixture, plain, PoE, gPoE and rBCM at 50 digits from exactly those inputs
+(predgrad_dense.aggregate_gradients over mpmath), each checked against mp.diff of pred_tolerance.aggregate along the direction
+the per-entry gradients define.
+Run from the repo root:  python tests/golden/make_predgrad_golden.py   (minutes on 8 cores; the output is byte-reproducible)
+"""
+import multiprocessing
+import os
+import sys
+
+import mpmath as mp
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, HERE)
+
+from deepstructuredmixtures_amd import datagen  # noqa: E402
+import predgrad_dense as pgd  # noqa: E402
+from pred_tolerance import aggregate, row_entries  # noqa: E402
+from make_predcov_golden import savez_reproducible  # noqa: E402
+
+mp.mp.dps = 50
+SHAPES = [(1, 1), (5, 3), (127, 128), (130, 129), (300, 260)]
+NAMES = ["isose", "ardse", "isolinear", "ardlinear", "ardseproduct", "isomatern32", "isomatern52", "ardmatern32", "ardmatern52"]
+AGG_ROWS = 120
+
+
+def loghyp_of(kind, D):
+    """Hyper-vector without the noise; length-scales grow with sqrt(D) so that cond(K_y) stays below 1e6."""
+    ls = np.array([0.35, 0.5, 0.42])[:D] * np.sqrt(D) if D <= 3 else np.full(D, 0.3 * np.sqrt(D))
+    if kind in pgd.LINEAR:
+        ls = ls + 0.5
+    nl = D if kind in pgd.ARD else 1
+    return np.concatenate([np.log(ls[:nl]), [0.0 if kind in pgd.LINEAR else 0.1]])
+
+
+def inputs(n, nt, D):
+    seed = 9000 + 7 * n + 3 * nt + D
+    X = datagen.uniform(seed, 0, n * D).reshape((n, D), order="F")
+    yscale = 400.0 if (n, nt, D) == (130, 129, 3) else 1.0
+    y = yscale * (np.sin(3.0 * X[:, 0]) * np.cos(2.0 * X[:, -1]) + 0.1 * datagen.normal(seed + 1, 0, n) + 0.7)
+    Xt = datagen.uniform(seed + 2, 0, nt * D).reshape((nt, D), order="F") * 1.2 - 0.1
+    Xt[0] = X[n - 1]
+    if nt > 4:
+        Xt[4] = Xt[1]
+        dup = (1, 4)
+    elif nt > 1:
+        Xt[nt - 1] = Xt[1]
+        dup = (1, nt - 1)
+    else:
+        dup = (0, 0)
+    return X, y, Xt, dup
+
+
+class MPGrad:
+    def __init__(self, kind, loghyp, logNoise, X, y, mean):
+        self.kind = kind
+        n, D = X.shape
+        h = [mp.mpf(float(v)) for v in loghyp]
+        self.noise = mp.e ** (2 * mp.mpf(float(logNoise)))
+        nl = D if kind in pgd.ARD else 1
+        il2 = [1 / mp.e ** (2 * v) for v in h[:nl]]
+        self.il2 = il2 if kind in pgd.ARD else il2 * D
+        self.s2 = mp.mpf(1) if kind in pgd.LINEAR else mp.e ** (2 * h[nl])
+        self.nu2 = 3 if kind in (5, 7) else 5
+        self.x = [[mp.mpf(float(v)) for v in r] for r in X]
+        self.mean = mp.mpf(float(mean))
+        c = self.noise + mp.mpf("1e-8")
+        K = [[self.k(self.x[i], self.x[j]) for j in range(i + 1)] for i in range(n)]
+        L = []
+        for i in range(n):
+            row = []
+            for j in range(i):
+                row.append((K[i][j] - mp.fdot(row[:j], L[j][:j])) / L[j][j])
+            row.append(mp.sqrt(K[i][i] + c - mp.fdot(row, row)))
+            L.append(row)
+        self.L = L
+        self.LT = [[L[j][i] for j in range(i + 1, n)] for i in range(n)]
+        yc = [mp.mpf(float(v)) - self.mean for v in y]
+        self.alpha = self.bwd(self.fwd(yc))
+        Ky = np.array([[float(K[max(i, j)][min(i, j)] + (c if i == j else 0)) for j in range(n)] for i in range(n)])
+        ev = np.linalg.eigvalsh(Ky)
+        self.cond = float(f"{ev[-1] / ev[0]:.4g}")
+
+    def fwd(self, b):
+        v = []
+        for i in range(len(b)):
+            v.append((b[i] - mp.fdot(self.L[i][:i], v)) / self.L[i][i])
+        return v
+
+    def bwd(self, v):
+        n = len(v)
+        b = [None] * n
+        for i in range(n - 1, -1, -1):
+            b[i] = (v[i] - mp.fdot(self.LT[i], b[i + 1:])) / self.L[i][i]
+        return b
+
+    def k(self, a, b):
+        kind = self.kind
+        if kind == 1:
+            return self.s2 * mp.fsum(mp.e ** (-((p - q) ** 2) * il / 2) for p, q, il in zip(a, b, self.il2))
+        if kind in pgd.LINEAR:
+            return mp.fsum(p * q * il for p, q, il in zip(a, b, self.il2))
+        r2 = mp.fsum((p - q) ** 2 * il for p, q, il in zip(a, b, self.il2))
+        if kind in (0, 4):
+            return self.s2 * mp.e ** (-r2 / 2)
+        s = mp.sqrt(self.nu2 * r2)
+        return self.s2 * mp.e ** (-s) * (1 + s + (s * s / 3 if self.nu2 == 5 else 0))
+
+    def dk(self, t, xi):
+        """[dk(t, xi) / dt_d for d]: the formulas of the issue, literally."""
+        kind = self.kind
+        if kind in pgd.LINEAR:
+            return [q * il for q, il in zip(xi, self.il2)]
+        if kind == 1:
+            return [-self.s2 * mp.e ** (-((p - q) ** 2) * il / 2) * (p - q) * il for p, q, il in zip(t, xi, self.il2)]
+        if kind in (0, 4):
+            kv = self.k(t, xi)
+            return [-kv * (p - q) * il for p, q, il in zip(t, xi, self.il2)]
+        r2 = mp.fsum((p - q) ** 2 * il for p, q, il in zip(t, xi, self.il2))
+        s = mp.sqrt(self.nu2 * r2)
+        c = 1 if self.nu2 == 3 else (1 + s) / 3
+        f = self.s2 * mp.e ** (-s) * c
+        return [-f * (self.nu2 * il) * (p - q) for p, q, il in zip(t, xi, self.il2)]
+
+    def mu(self, t):
+        return self.mean + mp.fdot([self.k(xi, t) for xi in self.x], self.alpha)
+
+    def var(self, t):
+        v = self.fwd([self.k(xi, t) for xi in self.x])
+        return self.k(t, t) - mp.fdot(v, v) + self.noise
+
+    def grads(self, t):
+        D = len(t)
+        beta = self.bwd(self.fwd([self.k(xi, t) for xi in self.x]))
+        G = [self.dk(t, xi) for xi in self.x]
+        self_term = [2 * p * il for p, il in zip(t, self.il2)] if self.kind in pgd.LINEAR else [mp.mpf(0)] * D
+        dmu = [mp.fdot(self.alpha, [g[d] for g in G]) for d in range(D)]
+        dvar = [self_term[d] - 2 * mp.fdot(beta, [g[d] for g in G]) for d in range(D)]
+        return dmu, dvar
+
+
+def run_case(spec):
+    mp.mp.dps = 50
+    name, kind, n, nt, D = spec
+    X, y, Xt, dup = inputs(n, nt, D)
+    Xt = Xt.copy()
+    if kind not in pgd.LINEAR and nt > 4:
+        Xt[2], Xt[3] = 1e3, -1e3
+    loghyp = loghyp_of(kind, D)
+    logNoise = float(np.log(0.1))
+    mean = float(np.mean(y)) + 0.25
+    g = MPGrad(kind, loghyp, logNoise, X, y, mean)
+    assert g.cond <= 1e6, (name, g.cond)
+    cache = {}
+    out = np.zeros((nt, 2 * D))
+    rows_mp = {}
+    for r in range(nt):
+        key = Xt[r].tobytes()
+        if key not in cache:
+            t = [mp.mpf(float(v)) for v in Xt[r]]
+            cache[key] = g.grads(t)
+        rows_mp[r] = cache[key]
+        out[r, :D] = [float(v) for v in cache[key][0]]
+        out[r, D:] = [float(v) for v in cache[key][1]]
+    # mp.diff of the 50-digit moments at three rows: the row AT a training row, the row listed twice, one in the last tile
+    worst_diff = 0.0
+    for r in sorted({0, dup[0], nt - 1}):
+        t = [mp.mpf(float(v)) for v in Xt[r]]
+        for d in range(D if D <= 3 else 2):
+            def at(u, d=d, t=t):
+                return t[:d] + [u] + t[d + 1:]
+            dm = mp.diff(lambda u: g.mu(at(u)), t[d])
+            dv = mp.diff(lambda u: g.var(at(u)), t[d])
+            for got, ref in ((rows_mp[r][0][d], dm), (rows_mp[r][1][d], dv)):
+                e = float(abs(got - ref) / (1 + abs(ref)))
+                worst_diff = max(worst_diff, e)
+                assert e <= 1e-12, (name, r, d, e)
+    # the float64 dense helper alone
+    _, _, hm, hv = pgd.moments(kind, loghyp, logNoise, X, y, mean, Xt)
+    tm, tv = pgd.tolerances(kind, loghyp, logNoise, X, y, Xt, out[:, :D], out[:, D:])
+    ratio = max(float(np.max(np.abs(hm - out[:, :D]) / tm)), float(np.max(np.abs(hv - out[:, D:]) / tv)))
+    assert ratio <= 1.0, (name, ratio)
+    meta = np.concatenate([[kind, n, nt, D, mean, logNoise, g.cond, dup[0], dup[1]], loghyp])
+    print(f"{name:24s} cond {g.cond:9.4g}  mp.diff {worst_diff:8.2g}  dense err/tol {ratio:8.2g}", flush=True)
+    return name, out, meta
+
+
+def aggregates(flat):
+    z = np.load(os.path.join(HERE, "gp_pred.npz"))
+    T = {k.split("/", 1)[1]: v for k, v in z.items() if k.startswith("table/")}
+    rp, ri, op_, ob = T["route_ptr"], T["route_idx"], T["obs_ptr"], T["obs_idx"]
+    Xt = T["Xt"][:AGG_ROWS]
+    D = Xt.shape[1]
+    sel = np.flatnonzero(ri < AGG_ROWS)                     # entries of the first rows, in entry order
+    dmu = np.zeros((sel.size, D))
+    dvar = np.zeros((sel.size, D))
+    leaf_of = np.searchsorted(rp, sel, side="right") - 1
+    for l in np.unique(leaf_of):
+        kid = int(T["kid"][l])
+        hyp = T["hyp"][kid][:T["hyp_len"][kid]]
+        obs = ob[op_[l]:op_[l + 1]]
+        pos = np.flatnonzero(leaf_of == l)
+        _, _, a, b = pgd.moments(int(T["kinds"][kid]), hyp[:-1], float(hyp[-1]), T["X"][obs], T["y"][obs], float(T["mean"][l]),
+                                 T["Xt"][ri[sel[pos]]])
+        dmu[pos], dvar[pos] = a, b
+    ent = [[] for _ in range(AGG_ROWS)]
+    for k, e in enumerate(sel):
+        ent[int(ri[e])].append((int(leaf_of[k]), k))
+    M = lambda a: [mp.mpf(float(v)) for v in a]                                         # noqa: E731
+    mu_e, var_e = M(T["mu"][sel]), M(T["var"][sel])
+    dmu_e, dvar_e = [M(r) for r in dmu], [M(r) for r in dvar]
+    pk = int(T["prior_kid"])
+    phyp = T["hyp"][pk][:T["hyp_len"][pk]]
+    pkind = int(T["kinds"][pk])
+    kss = M(pgd.prior_diag(pkind, phyp[:-1], Xt))
+    dkss = [M(r) for r in pgd.prior_dx(pkind, phyp[:-1], Xt)]
+    pnoise = mp.e ** (2 * mp.mpf(float(phyp[-1])))
+    fams = dict(mixture=(0, dict(coef=T["w_mix"])), plain=(0, dict(coef=T["w_mix"], plain=True)), poe=(1, dict(coef=np.ones(41))),
+                gpoe=(2, dict(coef=T["beta"])),
+                rbcm=(3, dict(group=T["group"], G=int(T["G"]), kss_prior=kss, noise_prior=pnoise)))
+    for fname, (fam, kw) in fams.items():
+        extra = dict(dkss_prior=dkss) if fam == 3 else {}
+        gm, gv = pgd.aggregate_gradients(fam, mu_e, var_e, dmu_e, dvar_e, ent, log=mp.log, **kw, **extra)
+        worst = 0.0
+        for r in (0, 57, AGG_ROWS - 1):
+            for d in range(D):
+                def f(t, which, r=r, d=d):
+                    kw2 = dict(kw)
+                    if fam == 3:
+                        kw2["kss_prior"] = [kss[r] + t * dkss[r][d]]
+                    m, v = aggregate(fam, [a + t * b[d] for a, b in zip(mu_e, dmu_e)], [a + t * b[d] for a, b in zip(var_e, dvar_e)],
+                                     [ent[r]], log=mp.log, **kw2)
+                    return (m, v)[which][0]
+                for which, got in ((0, gm[r][d]), (1, gv[r][d])):
+                    ref = mp.diff(lambda t: f(t, which), 0)
+                    e = float(abs(got - ref) / (1 + abs(ref)))
+                    worst = max(worst, e)
+                    assert e <= 1e-12, (fname, r, d, e)
+        flat[f"agg/{fname}"] = np.array([[float(v) for v in a] + [float(v) for v in b] for a, b in zip(gm, gv)])
+        print(f"aggregate {fname:8s} mp.diff {worst:8.2g}", flush=True)
+    flat["agg/entries"] = sel.astype(np.int32)
+    flat["agg/dleaf"] = np.concatenate([dmu, dvar], axis=1)
+
+
+def main():
+    flat = {}
+    aggregates(flat)
+    specs, groups = [], set()
+    for kind in range(9):
+        for n, nt in SHAPES:
+            for D in (1, 3):
+                specs.append((f"{NAMES[kind]}_{n}_{nt}_{D}", kind, n, nt, D))
+                groups.add((n, nt, D))
+    for kind in (0, 4):
+        specs.append((f"{NAMES[kind]}_130_9_40", kind, 130, 9, 40))
+    groups.add((130, 9, 40))
+    for n, nt, D in sorted(groups):
+        X, y, Xt, _ = inputs(n, nt, D)
+        flat[f"in_{n}_{nt}_{D}/X"], flat[f"in_{n}_{nt}_{D}/y"], flat[f"in_{n}_{nt}_{D}/Xt"] = X, y, Xt
+    specs.sort(key=lambda s: -(s[2] ** 2) * (s[2] + 6 * s[3]))
+    with multiprocessing.Pool(min(8, os.cpu_count() or 1)) as pool:
+        for name, out, meta in pool.imap_unordered(run_case, specs):
+            flat[name + "/out"], flat[name + "/meta"] = out, meta
+    path = os.path.join(HERE, "gp_predgrad.npz")
+    savez_reproducible(path, flat)
+    size, limit = os.path.getsize(path), os.path.getsize(os.path.join(HERE, "gp_pred.npz"))
+    print(f"{path}: {size} bytes (gp_pred.npz: {limit})")
+    assert size <= limit
+
+
+if __name__ == "__main__":
+    main()
