@@ -4,7 +4,7 @@ Host API mirrors the Julia package (buildDSMGP / fit / predict / update / train 
 numerics run in libdsmgp_hip.so (hand-written HIP for gfx950) behind the C ABI of include/dsmgp_hip.h.
 """
 from .kernels import (IsoSE, ArdSE, IsoLinear, ArdLinear, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52,
-                      ConstMean, KernelFunction)
+                      IsoRQ, ArdRQ, ConstMean, KernelFunction)
 from .model import (DSMGP, PoE, gPoE, rBCM, GaussianProcess, build, buildDSMGP, buildPoE, buildBCM, fit,
                     fit_naive, predict, prediction, update_cholesky, update, infer, mll, mll_table,
                     reset_weights, getparams, setparams, mse, sse, mae, sae, nlpd, scores, updategradients, grad_mll, train, ADAM, RMSProp,

@@ -624,7 +624,8 @@ struct dsmgp_ctx {
     std::vector<int> gfrob_leaf;    // owner leaf of each frob task
     DevBuf<GradTask> gdot;
     size_t gdot_prod0 = 0;          // first task of an ArdSEProduct leaf in gdot (they and the Matern leaves form its tail)
-    size_t gdot_mat0 = 0;           // first task of a Matern leaf in gdot (the end of the list)
+    size_t gdot_mat0 = 0;           // first task of a Matern leaf in gdot
+    size_t gdot_rq0 = 0;            // first task of a rational quadratic leaf in gdot (the end of the list)
     std::vector<int> gdot_leaf;     // leaf of each graddot task
     DevBuf<ArdLinTask> gardlin;     // ArdLinear leaves: column groups of L^-T (ardlin_quad_kernel)
     std::vector<int> gardlin_leaf;  // leaf of each of them
@@ -655,7 +656,8 @@ struct dsmgp_ctx {
     DevBuf<LooHvecTask> lghvec;
     std::vector<int> lghvec_leaf;
     DevBuf<GradTask> lgdot;         // as gdot: IsoSE / ArdSE | ArdSEProduct | Matern
-    size_t lgdot_prod0 = 0, lgdot_mat0 = 0;
+    size_t lgdot_prod0 = 0, lgdot_mat0 = 0, lgdot_rq0 = 0;
+    int lgstride = 2;               // doubles per contraction task in d_lgpart: 2 + D, one more with a rational quadratic id
     std::vector<int> lgdot_leaf;
     DevBuf<ArdLinTask> lgardlin;
     std::vector<int> lgardlin_leaf;
@@ -1035,6 +1037,8 @@ struct KindInfo {
     bool ard;           // one length-scale per input dimension (else one)
     bool iso_matern;    // Matern with one length-scale: D equal per-dimension slots of it
     bool matern;        // device KIND 5
+    bool rq;            // device KIND 6 (rational quadratic): per-dimension factors 1 / (2 alpha l_d^2), D slots for the iso kind too
+    int n_shape;        // shape parameters between the length-scales and logs in the hyper-vector (rational quadratic: loga)
     bool linear;        // no signal variance: KParam.sigma2 = sigma = 1
     double nh_num;      // numerator of the per-dimension factor KParam.nh = nh_num / l^2: -0.5, 1 (ArdLinear) or 2 nu (Matern)
     bool per_dim_grad;  // length-scale gradients from the per-dimension contraction sums Sd (ArdSE: with ard_true_gradient only)
@@ -1043,23 +1047,35 @@ struct KindInfo {
     bool set_checked;   // dsmgp_set_hyper refuses a wrong number of length-scales itself (the reference kinds: check_hyper, at fit)
 };
 constexpr KindInfo KINDS[] = {
-    //  name           ard    iso_m  matern linear nh_num per_dim contr. set_checked
-    {"IsoSE",          false, false, false, false, -0.5,  false,  true,  false},
-    {"ArdSE",          true,  false, false, false, -0.5,  true,   false, false},
-    {"IsoLinear",      false, false, false, true,  -0.5,  false,  false, false},
-    {"ArdLinear",      true,  false, false, true,  1.0,   false,  false, false},
-    {"ArdSEProduct",   true,  false, false, false, -0.5,  true,   true,  true},
-    {"IsoMatern32",    false, true,  true,  false, 3.0,   true,   true,  true},
-    {"IsoMatern52",    false, true,  true,  false, 5.0,   true,   true,  true},
-    {"ArdMatern32",    true,  false, true,  false, 3.0,   true,   true,  true},
-    {"ArdMatern52",    true,  false, true,  false, 5.0,   true,   true,  true},
+    //  name           ard    iso_m  matern rq     n_shape linear nh_num per_dim contr. set_checked
+    {"IsoSE",          false, false, false, false, 0,      false, -0.5,  false,  true,  false},
+    {"ArdSE",          true,  false, false, false, 0,      false, -0.5,  true,   false, false},
+    {"IsoLinear",      false, false, false, false, 0,      true,  -0.5,  false,  false, false},
+    {"ArdLinear",      true,  false, false, false, 0,      true,  1.0,   false,  false, false},
+    {"ArdSEProduct",   true,  false, false, false, 0,      false, -0.5,  true,   true,  true},
+    {"IsoMatern32",    false, true,  true,  false, 0,      false, 3.0,   true,   true,  true},
+    {"IsoMatern52",    false, true,  true,  false, 0,      false, 5.0,   true,   true,  true},
+    {"ArdMatern32",    true,  false, true,  false, 0,      false, 3.0,   true,   true,  true},
+    {"ArdMatern52",    true,  false, true,  false, 0,      false, 5.0,   true,   true,  true},
+    // rational quadratic: iso_m = D equal slots for the iso kind; nh_num is 0.5 / alpha, made in upload_hyper
+    {"IsoRQ",          false, true,  false, true,  1,      false, 0.0,   true,   true,  true},
+    {"ArdRQ",          true,  false, false, true,  1,      false, 0.0,   true,   true,  true},
 };
-static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == DSMGP_KIND_ARD_MATERN52 + 1, "one row per DSMGP_KIND_*");
+static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == DSMGP_KIND_ARD_RQ + 1, "one row per DSMGP_KIND_*");
+// length-scales of a hyper-vector of n values: [logl..., shape..., logs, logNoise]
+inline int n_lengthscales(int kind, size_t n) { return (int)n - 2 - KINDS[kind].n_shape; }
 
 // some kernel id has a Matern kind: the fused steps launch diag_fused_reg_matern_kernel as well
 inline bool any_matern(const dsmgp_ctx* c) {
     for (const HyperHost& h : c->hyper)
         if (h.kind >= 0 && KINDS[h.kind].matern) return true;
+    return false;
+}
+// some kernel id has a rational quadratic kind: the fused steps launch diag_fused_reg_rq_kernel as well, and a contraction task
+// has one more sum (dK / dlog alpha)
+inline bool any_rq(const dsmgp_ctx* c) {
+    for (const HyperHost& h : c->hyper)
+        if (h.kind >= 0 && KINDS[h.kind].rq) return true;
     return false;
 }
 
@@ -1076,28 +1092,31 @@ int upload_hyper(dsmgp_ctx* c) {
             kp[k] = KParam{0, 0, 1.0, 1.0, 1.0, nullptr, nullptr, 0.0, 1.0};
             continue;
         }
-        const int nl = (int)h.loghyp.size() - 2;
+        const int nl = n_lengthscales(h.kind, h.loghyp.size());
         off[k] = l2pool.size();
         for (int i = 0; i < nl; ++i) {
             const double l = std::exp(h.loghyp[i]);
             l2pool.push_back(l * l);
         }
         const KindInfo& ki = KINDS[h.kind];
-        // an iso Matern id reads D per-dimension factors like its ARD kind: D slots of its one length-scale
+        // an iso Matern / rational quadratic id reads D per-dimension factors like its ARD kind: D slots of its one length-scale
         if (ki.iso_matern)
             for (int i = 1; i < c->D; ++i) l2pool.push_back(l2pool[off[k]]);
-        slot_num.resize(l2pool.size(), ki.nh_num);
+        // rational quadratic: nh = 1 / (2 alpha l^2), alpha = exp(loga) from the shape slot behind the length-scales
+        const double alpha = ki.rq ? std::exp(h.loghyp[nl]) : 0.0;
+        slot_num.resize(l2pool.size(), ki.rq ? 0.5 / alpha : ki.nh_num);
         kp[k].kind = h.kind;
         kp[k].nl = nl;
-        const double logs = h.loghyp[nl];
-        const double logn = h.loghyp[nl + 1];
+        kp[k].il2 = alpha;      // (every other kind: 1 / l2[0], below)
+        const double logs = h.loghyp[nl + ki.n_shape];
+        const double logn = h.loghyp[nl + ki.n_shape + 1];
         kp[k].sigma2 = ki.linear ? 1.0 : std::exp(2.0 * logs);
         kp[k].sigma = ki.linear ? 1.0 : std::exp(logs);
         kp[k].noise = std::exp(2.0 * logn);
     }
     const size_t nslots = l2pool.size();
     // second half (KParam.nh): the per-dimension factor -- of the exponent, -0.5 / l^2, of ArdLinear's product, 1 / l_d^2, or
-    // of a Matern kernel's s^2, 2 nu / l_d^2
+    // of a Matern kernel's s^2, 2 nu / l_d^2, or of a rational quadratic kernel's w, 1 / (2 alpha l_d^2)
     for (size_t i = 0; i < nslots; ++i) l2pool.push_back(slot_num[i] / l2pool[i]);
     if (l2pool.size() > c->d_l2.cap || !c->d_l2.p) {   // (re)allocate only when the table grows: fit is called in loops
         drop_graphs(c);
@@ -1113,7 +1132,7 @@ int upload_hyper(dsmgp_ctx* c) {
         kp[k].nh = c->d_l2.p + nslots + off[k];
         if (c->hyper[k].kind >= 0) {
             kp[k].nh0 = l2pool[nslots + off[k]];
-            kp[k].il2 = 1.0 / l2pool[off[k]];
+            if (!KINDS[c->hyper[k].kind].rq) kp[k].il2 = 1.0 / l2pool[off[k]];
         }
     }
     HIPCHK(c, hipMemcpyAsync(c->d_kp.p, kp.data(), nk * sizeof(KParam), hipMemcpyHostToDevice, c->stream));
@@ -1125,7 +1144,7 @@ int upload_hyper(dsmgp_ctx* c) {
 // check_hyper here, as it has been since this check came in with ArdLinear)
 bool ard_linear_short(const dsmgp_ctx* c, int kid) {
     const HyperHost& h = c->hyper[kid];
-    return KINDS[h.kind].ard && h.kind != DSMGP_KIND_ARD_SE && (int)h.loghyp.size() - 2 != c->D;
+    return KINDS[h.kind].ard && h.kind != DSMGP_KIND_ARD_SE && n_lengthscales(h.kind, h.loghyp.size()) != c->D;
 }
 
 int check_hyper(dsmgp_ctx* c) {
@@ -1135,7 +1154,7 @@ int check_hyper(dsmgp_ctx* c) {
             return fail(c, DSMGP_E_STATE, "leaf " + std::to_string(l) + " uses kernel id " + std::to_string(kid) +
                                               " without hyper-parameters");
         const HyperHost& h = c->hyper[kid];
-        const int nl = (int)h.loghyp.size() - 2;
+        const int nl = n_lengthscales(h.kind, h.loghyp.size());
         const bool ard = KINDS[h.kind].ard;
         if (ard && nl != c->D)
             return fail(c, DSMGP_E_ARG, std::string(KINDS[h.kind].name) + " needs one lengthscale per input dimension");
@@ -2080,6 +2099,8 @@ void run_step(dsmgp_ctx* c, StepLists& S, int k, PhaseTimer& pt, hipStream_t st,
             // Matern leaves: their diagonal blocks in a launch of their own over the same list (each kernel skips the other's)
             if (any_matern(c))
                 diag_fused_reg_matern_kernel<<<nfd, 256, DIAGR_LDS_BYTES, st>>>(S.fdiag.p + S.fdiag_off[k], c->d_kp.p, c->D);
+            if (any_rq(c))      // rational quadratic leaves likewise
+                diag_fused_reg_rq_kernel<<<nfd, 256, DIAGR_LDS_BYTES, st>>>(S.fdiag.p + S.fdiag_off[k], c->d_kp.p, c->D);
             pt.note(k, nfd, 0);
             pt.end(st);
         }
@@ -2452,20 +2473,24 @@ int dsmgp_set_sharing(dsmgp_ctx* c, const int32_t* op, const int32_t* src, const
 int dsmgp_set_hyper(dsmgp_ctx* c, int32_t kernel_id, int32_t kind, const double* loghyp, int32_t n) {
     if (!c) return DSMGP_E_ARG;
     if (kernel_id < 0 || kernel_id >= DSMGP_MAX_KERNEL_IDS || !loghyp || n < 3) return fail(c, DSMGP_E_ARG, "set_hyper: bad arguments");
-    if (kind < 0 || kind > DSMGP_KIND_ARD_MATERN52) return fail(c, DSMGP_E_ARG, "set_hyper: unknown kernel kind");
+    if (kind < 0 || kind > DSMGP_KIND_ARD_RQ) return fail(c, DSMGP_E_ARG, "set_hyper: unknown kernel kind");
     const KindInfo& ki = KINDS[kind];
-    if (ki.set_checked && ki.ard && c->D > 0 && n != c->D + 2)
+    if (ki.set_checked && ki.ard && c->D > 0 && n != c->D + 2 + ki.n_shape)
         return fail(c, DSMGP_E_ARG, std::string("set_hyper: ") + ki.name + " needs one lengthscale per input dimension");
-    if (ki.set_checked && !ki.ard && n != 3)
-        return fail(c, DSMGP_E_ARG, std::string("set_hyper: ") + ki.name + " takes [logl, logs, logNoise]");
+    if (ki.set_checked && ki.ard && n < 3 + ki.n_shape)      // before set_train has fixed D: at least one length-scale
+        return fail(c, DSMGP_E_ARG, std::string("set_hyper: ") + ki.name + " needs one lengthscale per input dimension");
+    if (ki.set_checked && !ki.ard && n != 3 + ki.n_shape)
+        return fail(c, DSMGP_E_ARG, std::string("set_hyper: ") + ki.name +
+                                        (ki.n_shape ? " takes [logl, loga, logs, logNoise]" : " takes [logl, logs, logNoise]"));
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(loghyp[i])) return fail(c, DSMGP_E_ARG, "set_hyper: non-finite hyper-parameter");
     if ((int)c->hyper.size() <= kernel_id) c->hyper.resize(kernel_id + 1);
-    const bool had_matern = any_matern(c);
+    const bool had_matern = any_matern(c), had_rq = any_rq(c);
     if (c->hyper[kernel_id].kind != kind) free_grad(c);   // the contraction tiles / ArdLinear tasks depend on the kernel kind
     c->hyper[kernel_id].kind = kind;
     c->hyper[kernel_id].loghyp.assign(loghyp, loghyp + n);
-    if (any_matern(c) != had_matern) drop_graphs(c);       // a captured fit launches diag_fused_reg_matern_kernel or not
+    // a captured fit launches diag_fused_reg_matern_kernel / diag_fused_reg_rq_kernel or not
+    if (any_matern(c) != had_matern || any_rq(c) != had_rq) drop_graphs(c);
     c->fitted = false;
     c->predicted = false;
     c->vt_valid = false;
@@ -3499,12 +3524,13 @@ int build_grad_plan(dsmgp_ctx* c) {
     std::vector<GradTask> gd;
     std::vector<size_t> gblock;
     c->gdot_leaf.clear();
-    // The tasks of ArdSEProduct leaves (pass 1), then those of Matern leaves (pass 2) form the tail of the list, run by
-    // tile_graddot_prod_kernel and tile_graddot_matern_kernel.
+    // The tasks of ArdSEProduct leaves (pass 1), then those of Matern leaves (pass 2), then those of rational quadratic leaves
+    // (pass 3) form the tail of the list, run by tile_graddot_prod_kernel, tile_graddot_matern_kernel and tile_graddot_rq_kernel.
     bool any_ard = false, any_prod = false;
-    for (int pass = 0; pass < 3; ++pass) {
+    for (int pass = 0; pass < 4; ++pass) {
         if (pass == 1) c->gdot_prod0 = gd.size();
         if (pass == 2) c->gdot_mat0 = gd.size();
+        if (pass == 3) c->gdot_rq0 = gd.size();
         const size_t begin = gd.size();
         gblock.clear();
         for (int l = 0; l < L; ++l) {
@@ -3512,11 +3538,11 @@ int build_grad_plan(dsmgp_ctx* c) {
             const int kind_l = c->hyper[lf.kid].kind;
             const bool ard = kind_l == DSMGP_KIND_ARD_SE && c->ard_true_gradient;
             const bool prod = kind_l == DSMGP_KIND_ARD_SE_PRODUCT;
-            const bool mat = KINDS[kind_l].matern;
+            const bool mat = KINDS[kind_l].matern, rq = KINDS[kind_l].rq;
             if (!KINDS[kind_l].contraction && !ard) continue;
-            if ((prod ? 1 : mat ? 2 : 0) != pass) continue;
+            if ((prod ? 1 : mat ? 2 : rq ? 3 : 0) != pass) continue;
             any_ard = any_ard || ard;
-            any_prod = any_prod || prod || mat;
+            any_prod = any_prod || prod || mat || rq;
             // Shared gradients (the idea of src/fit.jl:313-395: a leaf whose observation set equals its main leaf's takes
             // that leaf's gradients, `copygradients`): a COPY leaf has its source's factor and kernel id; with the same
             // ConstMean its alpha is the source's too, so its contraction is the source's and is not computed again.
@@ -3564,7 +3590,8 @@ int build_grad_plan(dsmgp_ctx* c) {
     if (int rc = dev_upload(c, c->gdot, gd)) return rc;
     if (any_ard && c->D > GRADDOT_STAGE_D)
         return fail(c, DSMGP_E_ARG, "ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
-    c->gstride = (any_ard || any_prod) ? 2 + c->D : 2;     // ArdSEProduct, Matern: any D (staged in chunks)
+    c->gstride = (any_ard || any_prod) ? 2 + c->D : 2;     // ArdSEProduct, Matern, rational quadratic: any D (staged in chunks)
+    if (any_rq(c)) c->gstride = 3 + c->D;                  // one more slot behind the dimensions: the sum for dK / dlog alpha
 
     // ArdLinear leaves: ARDLIN_COLS columns of L^-T per task (a COPY leaf with its source's mean takes the source's sums,
     // as for the contraction), the tasks of the longest columns first
@@ -3663,15 +3690,19 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     double* pdot = pfrob + c->gfrob.count;
     double* pleaf = pdot + (size_t)c->gstride * c->gdot.count;
     const size_t np0 = c->gdot_prod0;     // tasks [np0, nm0): ArdSEProduct leaves
-    const size_t nm0 = c->gdot_mat0;      // tasks [nm0, count): Matern leaves
+    const size_t nm0 = c->gdot_mat0;      // tasks [nm0, nr0): Matern leaves
+    const size_t nr0 = c->gdot_rq0;       // tasks [nr0, count): rational quadratic leaves
     if (np0)
         tile_graddot_kernel<false><<<(int)np0, 256, 0, c->stream>>>(c->gdot.p, c->d_kp.p, c->D, pdot, c->gstride);
     if (nm0 > np0)
         tile_graddot_prod_kernel<false><<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->gdot.p + np0, c->d_kp.p, c->D,
                                                                                pdot + (size_t)c->gstride * np0, c->gstride);
-    if (c->gdot.count > nm0)
-        tile_graddot_matern_kernel<false><<<(int)(c->gdot.count - nm0), 256, 0, c->stream>>>(c->gdot.p + nm0, c->d_kp.p, c->D,
-                                                                                         pdot + (size_t)c->gstride * nm0, c->gstride);
+    if (nr0 > nm0)
+        tile_graddot_matern_kernel<false><<<(int)(nr0 - nm0), 256, 0, c->stream>>>(c->gdot.p + nm0, c->d_kp.p, c->D,
+                                                                                 pdot + (size_t)c->gstride * nm0, c->gstride);
+    if (c->gdot.count > nr0)
+        tile_graddot_rq_kernel<false><<<(int)(c->gdot.count - nr0), 256, 0, c->stream>>>(c->gdot.p + nr0, c->d_kp.p, c->D,
+                                                                                       pdot + (size_t)c->gstride * nr0, c->gstride);
     HIPCHK(c, hipEventRecord(e_dot.a, c->stream));
     if (c->gfrob.count) frob_kernel<<<(int)c->gfrob.count, 256, 0, c->stream>>>(c->gfrob.p, pfrob);
     dots_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, pleaf);
@@ -3704,10 +3735,12 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     const size_t gs = (size_t)c->gstride;
     std::vector<double> Sd;           // per leaf and dimension: contraction with dK / dlog l_d (ArdSE option, ArdSEProduct, Matern)
     if (gs > 2) Sd.assign((size_t)L * c->D, 0.0);
+    std::vector<double> Sa(L, 0.0);   // per leaf: contraction with dK / dlog alpha (rational quadratic)
     for (size_t i = 0; i < c->gdot.count; ++i) {
         const int l = c->gdot_leaf[i];
         if (KINDS[c->hyper[c->leaves[l].kid].kind].per_dim_grad) {
             for (int d = 0; d < c->D; ++d) Sd[(size_t)l * c->D + d] += pd[gs * i + 2 + d];
+            if (KINDS[c->hyper[c->leaves[l].kid].kind].rq) Sa[l] += pd[gs * i + 2 + c->D];
         } else {
             S1[l] += pd[gs * i];
         }
@@ -3715,6 +3748,7 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     for (int l = 0; l < L; ++l)
         if (c->grad_src[l] >= 0) {   // copygradients (src/fit.jl:352-356)
             S1[l] = S1[c->grad_src[l]];
+            Sa[l] = Sa[c->grad_src[l]];
             if (gs > 2)
                 for (int d = 0; d < c->D; ++d) Sd[(size_t)l * c->D + d] = Sd[(size_t)c->grad_src[l] * c->D + d];
         }
@@ -3740,8 +3774,9 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
         const HyperHost& h = c->hyper[lf.kid];
-        const int nl = (int)h.loghyp.size() - 2;
-        const double noise = std::exp(2.0 * h.loghyp[nl + 1]);
+        const int nl = n_lengthscales(h.kind, h.loghyp.size());
+        const int ns = nl + KINDS[h.kind].n_shape;               // the slot of logs; logNoise behind it
+        const double noise = std::exp(2.0 * h.loghyp[ns + 1]);
         const double cc = noise + 1e-8;
         const double ya = pl[2 * l], aa = pl[2 * l + 1];
         const double n = (double)lf.n;
@@ -3772,7 +3807,7 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
             // the true derivatives: 0.5 tr(W dK / dlog l_d) from the per-dimension sums, 0.5 tr(W 2K) = tr(W K) (no SURVEY F7 factor)
             for (int d = 0; d < nl; ++d) g[d] = 0.5 * Sd[(size_t)l * c->D + d];
             g[nl] = trPK;
-        } else if (KINDS[h.kind].matern) {
+        } else if (KINDS[h.kind].matern || KINDS[h.kind].rq) {
             // the true derivatives as for ArdSEProduct; an iso kind's dl is the sum over the dimensions, added in ascending d
             if (KINDS[h.kind].iso_matern) {
                 double sl = 0.0;
@@ -3781,9 +3816,10 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
             } else {
                 for (int d = 0; d < nl; ++d) g[d] = 0.5 * Sd[(size_t)l * c->D + d];
             }
-            g[nl] = trPK;
+            if (KINDS[h.kind].rq) g[nl] = 0.5 * Sa[l];        // da = 0.5 tr(W dK / dlog alpha)
+            g[ns] = trPK;
         }
-        g[nl + 1] = noise * (aa - trK[l]);                    // src/gaussianprocess.jl:176
+        g[ns + 1] = noise * (aa - trK[l]);                    // src/gaussianprocess.jl:176
     }
     return 0;
 }
@@ -4009,8 +4045,10 @@ int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int
         if (int rc = xinv_fill(c)) return rc;
         tile_predbeta_kernel<<<(unsigned)beta.size(), 256, 0, c->stream>>>(c->pgbeta.p);
         pred_inputgrad_kernel<true><<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->pgtasks.p, c->d_kp.p, D);
+        if (any_rq(c)) pred_inputgrad_rq_kernel<true><<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->pgtasks.p, c->d_kp.p, D);
     } else {
         pred_inputgrad_kernel<false><<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->pgtasks.p, c->d_kp.p, D);
+        if (any_rq(c)) pred_inputgrad_rq_kernel<false><<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->pgtasks.p, c->d_kp.p, D);
     }
     pred_inputgrad_finish_kernel<<<(unsigned)fin.size(), 128, 0, c->stream>>>(c->pgfin.p, c->d_kp.p, D);
     HIPCHK(c, hipGetLastError());
@@ -4127,12 +4165,14 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
         });
     }
     deal(gi, gi_leaf, 0, gblock);
-    // the contraction, as gdot: IsoSE and ArdSE leaves (pass 0), ArdSEProduct (1), Matern (2), each run by its own kernel
+    // the contraction, as gdot: IsoSE and ArdSE leaves (pass 0), ArdSEProduct (1), Matern (2), rational quadratic (3), each run
+    // by its own kernel
     std::vector<GradTask> gd;
     c->lgdot_leaf.clear();
-    for (int pass = 0; pass < 3; ++pass) {
+    for (int pass = 0; pass < 4; ++pass) {
         if (pass == 1) c->lgdot_prod0 = gd.size();
         if (pass == 2) c->lgdot_mat0 = gd.size();
+        if (pass == 3) c->lgdot_rq0 = gd.size();
         const size_t begin = gd.size();
         gblock.clear();
         for (int l = 0; l < L; ++l) {
@@ -4140,7 +4180,7 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
             if (c->grad_src[l] >= 0) continue;
             const int kind_l = c->hyper[lf.kid].kind;
             if (!KINDS[kind_l].contraction && kind_l != DSMGP_KIND_ARD_SE) continue;
-            if ((kind_l == DSMGP_KIND_ARD_SE_PRODUCT ? 1 : KINDS[kind_l].matern ? 2 : 0) != pass) continue;
+            if ((kind_l == DSMGP_KIND_ARD_SE_PRODUCT ? 1 : KINDS[kind_l].matern ? 2 : KINDS[kind_l].rq ? 3 : 0) != pass) continue;
             const LeafDev& d = c->h_leaves[l];
             each_tile(lf, gblock, begin, [&] { return gd.size(); }, [&](int i, int j, int na, int nb) {
                 GradTask g{};
@@ -4190,7 +4230,8 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
     if (int rc = dev_upload(c, c->lginv, gi)) return rc;
     if (int rc = dev_upload(c, c->lgdot, gd)) return rc;
     if (int rc = dev_upload(c, c->lgardlin, al)) return rc;
-    if (int rc = c->d_lgpart.grow(c, 2 * (size_t)L + 2 * hv.size() + (size_t)(2 + D) * gd.size() + 3 * (size_t)D * al.size())) return rc;
+    c->lgstride = 2 + D + (any_rq(c) ? 1 : 0);      // one more slot behind the dimensions: the sum for dK / dlog alpha
+    if (int rc = c->d_lgpart.grow(c, 2 * (size_t)L + 2 * hv.size() + (size_t)c->lgstride * gd.size() + 3 * (size_t)D * al.size())) return rc;
     c->lg_kinds.clear();
     for (const HyperHost& h : c->hyper) c->lg_kinds.push_back(h.kind);
     c->lg_ready = true;
@@ -4218,7 +4259,7 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
     }
     if (!c->lg_ready)
         if (int rc = build_loo_grad_plan(c)) return rc;
-    const int gs = 2 + D;
+    const int gs = c->lgstride;
     double* pw = c->d_lgpart.p;
     double* ph = pw + 2 * (size_t)L;
     double* pdot = ph + 2 * c->lghvec.count;
@@ -4229,12 +4270,14 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
     loo_weights_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->lleaf.p, c->lgvec.p, pw);
     if (c->lginv.count) tile_ginv_kernel<<<(unsigned)c->lginv.count, 256, 0, c->stream>>>(c->lginv.p);
     if (c->lghvec.count) loo_hvec_kernel<<<(unsigned)c->lghvec.count, 256, 0, c->stream>>>(c->lghvec.p, ph);
-    const size_t np0 = c->lgdot_prod0, nm0 = c->lgdot_mat0, nd = c->lgdot.count;
+    const size_t np0 = c->lgdot_prod0, nm0 = c->lgdot_mat0, nr0 = c->lgdot_rq0, nd = c->lgdot.count;
     if (np0) tile_graddot_kernel<true><<<(int)np0, 256, 0, c->stream>>>(c->lgdot.p, c->d_kp.p, D, pdot, gs);
     if (nm0 > np0)
         tile_graddot_prod_kernel<true><<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->lgdot.p + np0, c->d_kp.p, D, pdot + (size_t)gs * np0, gs);
-    if (nd > nm0)
-        tile_graddot_matern_kernel<true><<<(int)(nd - nm0), 256, 0, c->stream>>>(c->lgdot.p + nm0, c->d_kp.p, D, pdot + (size_t)gs * nm0, gs);
+    if (nr0 > nm0)
+        tile_graddot_matern_kernel<true><<<(int)(nr0 - nm0), 256, 0, c->stream>>>(c->lgdot.p + nm0, c->d_kp.p, D, pdot + (size_t)gs * nm0, gs);
+    if (nd > nr0)
+        tile_graddot_rq_kernel<true><<<(int)(nd - nr0), 256, 0, c->stream>>>(c->lgdot.p + nr0, c->d_kp.p, D, pdot + (size_t)gs * nr0, gs);
     if (c->lgardlin.count)
         ardlin_quad_kernel<true><<<dim3((unsigned)c->lgardlin.count, (unsigned)((D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
             c->lgardlin.p, D, pal);
@@ -4251,7 +4294,7 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
     const double* hh = hw + 2 * (size_t)L;
     const double* hd = hh + 2 * c->lghvec.count;
     const double* ha = hd + (size_t)gs * nd;
-    std::vector<double> frob(L, 0.0), ua(L, 0.0), S1(L, 0.0), SK(L, 0.0), Sd((size_t)L * D, 0.0);
+    std::vector<double> frob(L, 0.0), ua(L, 0.0), S1(L, 0.0), SK(L, 0.0), Sd((size_t)L * D, 0.0), Sa(L, 0.0);
     for (size_t i = 0; i < c->lghvec.count; ++i) {
         frob[c->lghvec_leaf[i]] += hh[2 * i];
         ua[c->lghvec_leaf[i]] += hh[2 * i + 1];
@@ -4263,6 +4306,7 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
         const int kind_l = c->hyper[c->leaves[l].kid].kind;      // IsoSE tasks write no per-dimension sums
         if (kind_l == DSMGP_KIND_ARD_SE || KINDS[kind_l].per_dim_grad)
             for (int d = 0; d < D; ++d) Sd[l * D + d] += hd[gs * i + 2 + d];
+        if (KINDS[kind_l].rq) Sa[l] += hd[gs * i + 2 + D];
     }
     std::vector<double> A, U, Q;
     if (c->lgardlin.count) {
@@ -4282,13 +4326,14 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
         const LeafHost& lf = c->leaves[l];
         const HyperHost& h = c->hyper[lf.kid];
         const size_t s = (size_t)(c->grad_src[l] >= 0 ? c->grad_src[l] : l);      // a COPY leaf with its source's mean: the source's
-        const int nl = (int)h.loghyp.size() - 2;
-        const double noise = std::exp(2.0 * h.loghyp[nl + 1]);
+        const int nl = n_lengthscales(h.kind, h.loghyp.size());
+        const int ns = nl + KINDS[h.kind].n_shape;                // the slot of logs; logNoise behind it
+        const double noise = std::exp(2.0 * h.loghyp[ns + 1]);
         const double cc = noise + 1e-8;
         double* g = grad_out + (size_t)l * stride;
         for (int j = 0; j < stride; ++j) g[j] = 0.0;
         if (std::isnan(lpd[l])) {       // the fit of this leaf failed (info != 0)
-            for (int j = 0; j < nl + 2; ++j) g[j] = std::nan("");
+            for (int j = 0; j < ns + 2; ++j) g[j] = std::nan("");
             continue;
         }
         const double trM = ua[s] - frob[s];                       // tr M = u . alpha - |H|_F^2
@@ -4303,7 +4348,7 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
             for (int d = 0; d < nl; ++d)                          // x_d^T M x_d = (x_d . u)(x_d . alpha) - |H^T x_d|^2
                 g[d] = -2.0 * (U[s * D + d] * A[s * D + d] - Q[s * D + d]) / std::exp(2.0 * h.loghyp[d]);
             g[nl] = 0.0;
-        } else {                                                  // ArdSE, ArdSEProduct, Matern: per-dimension sums
+        } else {                                                  // ArdSE, ArdSEProduct, Matern, rational quadratic: per-dimension sums
             if (KINDS[h.kind].iso_matern) {
                 double sl = 0.0;
                 for (int d = 0; d < D; ++d) sl += Sd[s * D + d];
@@ -4311,9 +4356,10 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
             } else {
                 for (int d = 0; d < nl; ++d) g[d] = Sd[s * D + d];
             }
-            g[nl] = 2.0 * SK[s];
+            if (KINDS[h.kind].rq) g[nl] = Sa[s];                  // sum M dK / dlog alpha
+            g[ns] = 2.0 * SK[s];
         }
-        g[nl + 1] = 2.0 * noise * trM;
+        g[ns + 1] = 2.0 * noise * trM;
     }
     if (lpd_out) std::memcpy(lpd_out, lpd.data(), (size_t)L * sizeof(double));
     return 0;

@@ -53,12 +53,13 @@ struct KParam {
                         //   the exponent; IsoSE, ArdSE), 1 / lengthscale^2 (ArdLinear), 2 nu / lengthscale^2 (Matern: D slots for
                         //   the iso kinds too, all equal)
     double nh0;         // nh[0]
-    double il2;         // 1 / l2[0]
+    double il2;         // 1 / l2[0]; the rational quadratic kinds (9, 10), which never read 1 / l2[0], keep alpha here (rq_alpha),
+                        //   so that KParam keeps its size
 };
 
 // DSMGP_KIND_DISPATCH(kind, K, stmt...): runs stmt once, with `constexpr int K` the device kind of `kind` -- DSMGP kinds 0-4 as
-// they are, 5 for every Matern kind (5-8).  The _NON_MATERN form has the arms 0-4 only (diag_fused_reg_kernel, whose Matern
-// tasks run in a kernel of their own).  A macro and not a generic lambda: dispatching through `[&](auto k)` changed the ISA of
+// they are, 5 for every Matern kind (5-8), 6 for the rational quadratic kinds (9, 10).  The _NON_MATERN form has the arms 0-4
+// only (diag_fused_reg_kernel, whose Matern and rational quadratic tasks run in kernels of their own).  A macro and not a generic lambda: dispatching through `[&](auto k)` changed the ISA of
 // nine kernels (diag_fused_reg_matern_kernel: scratch 200 -> 292 bytes per lane); this if / else chain is the one it replaces.
 #define DSMGP_KIND_ARMS_0_4(kind, K, ...)                      \
     if ((kind) == 0) { constexpr int K = 0; __VA_ARGS__; }      \
@@ -67,11 +68,20 @@ struct KParam {
     else if ((kind) == 3) { constexpr int K = 3; __VA_ARGS__; } \
     else if ((kind) == 4) { constexpr int K = 4; __VA_ARGS__; }
 #define DSMGP_KIND_DISPATCH(kind, K, ...) \
-    do { DSMGP_KIND_ARMS_0_4(kind, K, __VA_ARGS__) else if ((kind) >= 5) { constexpr int K = 5; __VA_ARGS__; } } while (0)
+    do { DSMGP_KIND_ARMS_0_4(kind, K, __VA_ARGS__) else if ((kind) >= 9) { constexpr int K = 6; __VA_ARGS__; } \
+         else if ((kind) >= 5) { constexpr int K = 5; __VA_ARGS__; } } while (0)
 #define DSMGP_KIND_DISPATCH_NON_MATERN(kind, K, ...) do { DSMGP_KIND_ARMS_0_4(kind, K, __VA_ARGS__) } while (0)
+// the arms 0-5 only: kernels whose rational quadratic tasks run in a kernel of their own (pred_inputgrad_kernel, where the log1p
+// of a seventh arm cost the mean-only form 14 VGPRs and a wave per SIMD)
+#define DSMGP_KIND_DISPATCH_NON_RQ(kind, K, ...) \
+    do { DSMGP_KIND_ARMS_0_4(kind, K, __VA_ARGS__) else if ((kind) >= 5 && (kind) <= 8) { constexpr int K = 5; __VA_ARGS__; } } while (0)
 
-// device kind K reads the per-dimension factors KParam.nh in its sum over the dimensions (ArdSE, ArdLinear, ArdSEProduct, Matern)
-constexpr bool kind_reads_nh(int K) { return K == 1 || K == 3 || K == 4 || K == 5; }
+// device kind K reads the per-dimension factors KParam.nh in its sum over the dimensions (ArdSE, ArdLinear, ArdSEProduct, Matern,
+// rational quadratic)
+constexpr bool kind_reads_nh(int K) { return K == 1 || K == 3 || K == 4 || K == 5 || K == 6; }
+// which diagonal-block kernel of a fused step takes a leaf of DSMGP kind `kind`: 0 diag_fused_reg_kernel (kinds 0-4), 5 the Matern
+// one, 6 the rational quadratic one
+__device__ __forceinline__ int diag_kernel_class(int kind) { return kind >= 9 ? 6 : kind >= 5 ? 5 : 0; }
 
 // exp(x) for finite x <= 0: the argument reduction and degree-12 polynomial of the device library's exp
 // (n = rint(x log2 e), r = x - n ln2 in two pieces, Horner, ldexp) without its overflow / underflow selects --
@@ -106,6 +116,13 @@ __device__ __forceinline__ double matern_value(double z, const KParam& p) {
     return p.sigma2 * exp_nonpos(-s) * fma(fma(matern_c2(p), s, 1.0), s, 1.0);
 }
 
+// Rational quadratic (DSMGP kinds 9 and 10, device KIND 6): sigma^2 (1 + w)^-alpha from w = sum_d (a_d-b_d)^2 / (2 alpha l_d^2)
+// (factors nh_d = 1 / (2 alpha l_d^2)), evaluated as sigma^2 exp(-alpha log1p(w)): w >= 0, so the argument is never positive, and
+// w = 0 gives sigma^2 exactly
+__device__ __forceinline__ double rq_alpha(const KParam& p) { return p.il2; }
+__device__ __forceinline__ double rq_value(double z, const KParam& p) {
+    return p.sigma2 * exp_nonpos(-rq_alpha(p) * log1p(z));
+}
 
 // ---------------------------------------------------------------------------------------------
 // Gram tiles.  out(r,c) = k(a_r, b_c); rows/cols beyond the valid counts are 0, and with `sym` the
@@ -139,7 +156,7 @@ __device__ __forceinline__ void gram_accumulate(double (&z)[NA][NB], const doubl
                 z[i][j] = fma(a[i], b[j], z[i][j]);
             } else if (KIND == 3) {
                 z[i][j] = fma(a[i] * b[j], nhd, z[i][j]);
-            } else {    // KIND 4, 5
+            } else {    // KIND 4, 5, 6
                 const double u = a[i] - b[j];
                 z[i][j] = fma(u * u, nhd, z[i][j]);
             }
@@ -156,7 +173,8 @@ __device__ __forceinline__ double gram_finish(double z, const KParam& p, int row
     else if (KIND == 2) kv = z * p.il2;
     else if (KIND == 3) kv = z;
     else if (KIND == 4) kv = p.sigma2 * exp_nonpos(z);
-    else kv = matern_value(z, p);
+    else if (KIND == 5) kv = matern_value(z, p);
+    else kv = rq_value(z, p);
     if (!EDGE) return kv;
     const bool valid = (row < na) && (col < nb);
     if (!valid) kv = 0.0;
@@ -176,7 +194,8 @@ __device__ __forceinline__ double gram_finish(double z, const KParam& p, int row
 // by 1 / l_d^2 and added in ascending d (one fma: bit-symmetric in a and b).  ArdSEProduct (KIND 4, not a reference kernel) is
 // sigma^2 exp(z), z = sum_d (a_d-b_d)^2 * (-0.5 / l_d^2) in one fma per dimension, ascending d (bit-symmetric as well).
 // KIND 5 is every Matern kind (DSMGP kinds 5-8, not reference kernels): z = s^2 accumulated as for KIND 4 with the factors
-// 2 nu / l_d^2, then matern_value.
+// 2 nu / l_d^2, then matern_value.  KIND 6 is the rational quadratic kinds (9, 10): w accumulated the same way with the factors
+// 1 / (2 alpha l_d^2), then rq_value.
 template <int KIND>
 __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam& p, int D, int half,
                                                double (*sa)[TB], double (*sb)[TB / 2]) {
@@ -232,7 +251,8 @@ __device__ __forceinline__ void gram_half_tile(const GramTask& tk, const KParam&
             else if (KIND == 2) kv = acc[q][j][0] * il2;
             else if (KIND == 3) kv = acc[q][j][0];
             else if (KIND == 4) kv = p.sigma2 * exp_nonpos(acc[q][j][0]);
-            else kv = matern_value(acc[q][j][0], p);
+            else if (KIND == 5) kv = matern_value(acc[q][j][0], p);
+            else kv = rq_value(acc[q][j][0], p);
             const bool valid = (r < tk.na) && (c < tk.nb);
             if (!valid) kv = 0.0;
             if (tk.sym && tk.diag && r == c) kv = valid ? kv + (p.noise + 1e-8) : 1.0;
@@ -1666,6 +1686,143 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
     }
 }
 
+// Rational quadratic leaves (DSMGP kinds 9 and 10), any D: tile_graddot_matern_kernel with z = w (factors nh_d = 1 / (2 alpha
+// l_d^2)), k = sigma^2 exp(-alpha log1p(w)), the per-entry length-scale weight k / (1 + w) and the per-dimension factor
+// 2 alpha nh_d = 1 / l_d^2: dK / dlog l_d = k / (1 + w) u_d^2 / l_d^2.  One more output, out[2 + D] (ostride >= 3 + D): the
+// contraction with dK / dlog alpha = k alpha (w / (1 + w) - log1p(w)), evaluated as written (<= 0; the cancellation at small w
+// costs absolute error of order eps k alpha w).  A copy for the reason given there.
+template <bool LOO>
+__global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const GradTask* __restrict__ tasks,
+                                                                     const KParam* __restrict__ kp, int D,
+                                                                     double* __restrict__ out, int ostride) {
+    __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
+    __shared__ double red[2][4];
+    static_assert((GRADDOT_STAGE_D + 1) * 256 <= 2 * NRING * KC2 * LDP, "a chunk of coordinates and the alphas fit the ring");
+    double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
+    double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
+    const GradTask g = tasks[blockIdx.x];
+    const KParam p = kp[g.kid];
+    d4 acc[4][4];
+    gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);      // ends on a barrier: the ring is free
+    const int t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+    double* ul = nullptr;
+    if constexpr (LOO) {
+        __shared__ double ul_s[2 * TB];
+        ul = ul_s;
+        ul[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[g.uoff + t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[g.uoff + t - TB] : 0.0);
+        __syncthreads();
+    }
+    double tr = 0.0;
+    constexpr int CH = GRADDOT_STAGE_D;
+    double* xs = smem;
+    double* al = smem + (size_t)CH * 256;
+    const int nch = (D + CH - 1) / CH;
+    const double wgt = g.diag ? 1.0 : 2.0;
+    const double alpha = rq_alpha(p);
+    double sa = 0.0;            // sum_rc weight_rc k_rc (w / (1 + w) - log1p(w)): the contraction with dK / dlog alpha, over alpha
+    if constexpr (!LOO) {
+#pragma unroll
+        for (int rn = 0; rn < 4; ++rn) {
+            const int r = wr * 64 + 16 * rn + l15;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+                if (g.diag && r == c && r < g.na) tr += acc[i >> 2][rn][i & 3];
+            }
+        }
+    }
+    al[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[t - TB] : 0.0);
+#pragma unroll
+    for (int rn = 0; rn < 4; ++rn) {
+        const int r = wr * 64 + 16 * rn + l15;
+        const bool rv = r < g.na;
+        double z[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) z[i] = 0.0;
+        for (int ch = 0; ch < nch; ++ch) {
+            const int d0 = ch * CH, dn = min(CH, D - d0);
+            if (nch > 1 || rn == 0) {
+                __syncthreads();
+                for (int e = t; e < dn * 256; e += 256) {
+                    const int d = e >> 8, rc = e & 255;
+                    xs[e] = (rc < TB) ? ((rc < g.na) ? g.xa[rc + (size_t)(d0 + d) * g.ldx] : 0.0)
+                                      : ((rc - TB < g.nb) ? g.xb[rc - TB + (size_t)(d0 + d) * g.ldx] : 0.0);
+                }
+                __syncthreads();
+            }
+            for (int d = 0; d < dn; ++d) {
+                const double nhd = p.nh[d0 + d];
+                const double a = xs[d * 256 + r];
+                const double* xb = xs + d * 256 + TB + wc * 64 + l4;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const double u = a - xb[16 * (i >> 2) + 4 * (i & 3)];
+                    z[i] = fma(u * u, nhd, z[i]);
+                }
+            }
+        }
+        const double ar = al[r];
+        const double ur = LOO ? ul[r] : 0.0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+            const double pre = graddot_weight<LOO>(ar, al[TB + c], ur, LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
+            const double lw = log1p(z[i]);
+            const double q = 1.0 / (1.0 + z[i]);
+            const double pk = (rv && c < g.nb) ? pre * (p.sigma2 * exp_nonpos(-alpha * lw)) : 0.0;
+            sa = fma(pk, z[i] * q - lw, sa);
+            acc[i >> 2][rn][i & 3] = pk * q;
+            if constexpr (LOO) tr += pk;
+        }
+    }
+    for (int ch = 0; ch < nch; ++ch) {
+        const int d0 = ch * CH, dn = min(CH, D - d0);
+        if (nch > 1) {
+            __syncthreads();
+            for (int e = t; e < dn * 256; e += 256) {
+                const int d = e >> 8, rc = e & 255;
+                xs[e] = (rc < TB) ? ((rc < g.na) ? g.xa[rc + (size_t)(d0 + d) * g.ldx] : 0.0)
+                                  : ((rc - TB < g.nb) ? g.xb[rc - TB + (size_t)(d0 + d) * g.ldx] : 0.0);
+            }
+            __syncthreads();
+        }
+        for (int d = 0; d < dn; ++d) {
+            double sd = 0.0;
+#pragma unroll
+            for (int rn = 0; rn < 4; ++rn) {
+                const double a = xs[d * 256 + wr * 64 + 16 * rn + l15];
+                const double* xb = xs + d * 256 + TB + wc * 64 + l4;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const double u = a - xb[16 * (i >> 2) + 4 * (i & 3)];
+                    sd = fma(acc[i >> 2][rn][i & 3], u * u, sd);
+                }
+            }
+            for (int o = 32; o > 0; o >>= 1) sd += __shfl_down(sd, o);
+            __syncthreads();
+            if (lane == 0) red[0][w] = sd;
+            __syncthreads();
+            if (t == 0)   // u^2 / l_d^2 = 2 alpha nh_d u^2
+                out[(size_t)ostride * blockIdx.x + 2 + d0 + d] =
+                    wgt * (2.0 * alpha * p.nh[d0 + d]) * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) sa += __shfl_down(sa, o);
+    __syncthreads();
+    if (lane == 0) red[0][w] = sa;
+    __syncthreads();
+    if (t == 0) out[(size_t)ostride * blockIdx.x + 2 + D] = wgt * alpha * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+    for (int o = 32; o > 0; o >>= 1) tr += __shfl_down(tr, o);
+    if (lane == 0) red[1][w] = tr;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[(size_t)ostride * blockIdx.x] = 0.0;
+        out[(size_t)ostride * blockIdx.x + 1] = (LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Full predictive covariance of one leaf (prediction(gp, xtest), src/gaussianprocess.jl:110-137):
 //   Sigma = K_tt - V^T V (+ noise I),  V^T = K_tn L^-T = LeafDev::Vt (ntpad x npad, ld = ntpad) after the sweep.
@@ -1829,12 +1986,13 @@ __global__ __launch_bounds__(256, 2) void tile_predbeta_kernel(const PredBetaTas
 // (r = t & 127, h = t >> 7) owns test row r and the slab's training rows of parity h, PGRAD_SUB of them at a time: their
 // coordinates go through LDS in rounds of PGRAD_DC dimensions (a broadcast read per wave), the test row's own coordinates and
 // B[r, i] come straight from memory (consecutive lanes, consecutive addresses).  The 2 x PGRAD_DC sums of a chunk of dimensions
-// live in registers whatever D is; the kinds whose derivative carries the kernel value (IsoSE, ArdSEProduct, Matern) first sum
+// live in registers whatever D is; the kinds whose derivative carries the kernel value (IsoSE, ArdSEProduct, Matern, RQ) first sum
 // the exponent over ALL dimensions and evaluate the factor once per pair and chunk -- once per pair up to D = PGRAD_DC.
 //   IsoSE         g_d = -k D_d / l^2                      ArdSEProduct  g_d = -k D_d / l_d^2        (D_d = x_{t,d} - x_{i,d})
 //   ArdSE         g_d = -sigma^2 exp(-D_d^2 / 2 l_d^2) D_d / l_d^2      (term d only)
 //   IsoLinear     g_d = x_{i,d} / l^2                     ArdLinear     g_d = x_{i,d} / l_d^2
 //   Matern        g_d = -sigma^2 exp(-s) c(s) (2 nu / l_d^2) D_d,  c(s) of tile_graddot_matern_kernel: nothing divides by r
+//   RQ            g_d = -k / (1 + w) D_d / l_d^2,  1 / l_d^2 = 2 alpha nh_d
 // The two parities meet through LDS (h = 0 + h = 1), the slabs are added in ascending order by pred_inputgrad_finish_kernel:
 // no atomics, the same bits from call to call.  Rows >= nrows and training rows >= n are neither read nor written.
 constexpr int PGRAD_DC = 8;       // dimensions per chunk (the accumulators of a thread)
@@ -1857,7 +2015,7 @@ template <int KIND, bool VAR>
 __device__ __forceinline__ void pred_inputgrad_body(const PredGradTask& tk, const KParam& p, int D, double (*sc)[PGRAD_SUB],
                                                     double* sal, double* red) {
     constexpr int DC = PGRAD_DC, SUB = PGRAD_SUB, NP = PGRAD_SUB / 2;
-    constexpr bool PAIR = (KIND == 0 || KIND == 4 || KIND == 5);   // the derivative carries the kernel value of the pair
+    constexpr bool PAIR = (KIND == 0 || KIND == 4 || KIND == 5 || KIND == 6);   // the derivative carries the kernel value of the pair
     const int t = threadIdx.x, r = t & (TB - 1), h = t >> 7;
     const bool live = r < tk.nrows;
     const int nround = (D + DC - 1) / DC;
@@ -1910,6 +2068,7 @@ __device__ __forceinline__ void pred_inputgrad_body(const PredGradTask& tk, cons
                 for (int j = 0; j < NP; ++j) {
                     if (KIND == 0) f[j] = -(p.sigma2 * exp_nonpos(f[j] * p.nh0)) * p.il2;
                     else if (KIND == 4) f[j] = p.sigma2 * exp_nonpos(f[j]);
+                    else if (KIND == 6) f[j] = -(rq_value(f[j], p) / (1.0 + f[j])) * (2.0 * rq_alpha(p));
                     else {
                         const double s = sqrt(f[j]);
                         f[j] = -(p.sigma2 * exp_nonpos(-s) * fma(c2, s, c1));
@@ -1933,7 +2092,7 @@ __device__ __forceinline__ void pred_inputgrad_body(const PredGradTask& tk, cons
                                 double g;
                                 if (KIND == 0) g = xa[d] - xc;
                                 else if (KIND == 4) g = (xa[d] - xc) * (2.0 * p.nh[e0 + d]);
-                                else if (KIND == 5) g = (xa[d] - xc) * p.nh[e0 + d];
+                                else if (KIND == 5 || KIND == 6) g = (xa[d] - xc) * p.nh[e0 + d];
                                 else if (KIND == 1) {
                                     const double u = xa[d] - xc, nhd = p.nh[e0 + d];
                                     g = (p.sigma2 * exp_nonpos((u * u) * nhd)) * (u * (2.0 * nhd));
@@ -1975,7 +2134,21 @@ __global__ __launch_bounds__(256) void pred_inputgrad_kernel(const PredGradTask*
     __shared__ double red[(VAR ? 2 : 1) * PGRAD_DC * TB];     // the sums of parity h = 1: mean planes, then variance planes
     const PredGradTask tk = tasks[blockIdx.x];
     const KParam p = kp[tk.kid];
-    DSMGP_KIND_DISPATCH(p.kind, K, pred_inputgrad_body<K, VAR>(tk, p, D, sc, sal, red));
+    DSMGP_KIND_DISPATCH_NON_RQ(p.kind, K, pred_inputgrad_body<K, VAR>(tk, p, D, sc, sal, red));
+}
+
+// the tasks of rational quadratic leaves (kinds 9, 10), over the same list: launched only while a kernel id has such a kind;
+// each of the two kernels leaves the other's tasks alone
+template <bool VAR>
+__global__ __launch_bounds__(256) void pred_inputgrad_rq_kernel(const PredGradTask* __restrict__ tasks,
+                                                                const KParam* __restrict__ kp, int D) {
+    __shared__ double sc[PGRAD_DC][PGRAD_SUB];
+    __shared__ double sal[PGRAD_SUB];
+    __shared__ double red[(VAR ? 2 : 1) * PGRAD_DC * TB];
+    const PredGradTask tk = tasks[blockIdx.x];
+    const KParam p = kp[tk.kid];
+    if (p.kind < 9) return;
+    pred_inputgrad_body<6, VAR>(tk, p, D, sc, sal, red);
 }
 
 // Step 3: the slabs of a test tile in ascending order, the self term dk(x_t, x_t) / dx_{t,d} (2 x_{t,d} / l_d^2 for the linear

@@ -531,9 +531,9 @@ __device__ __forceinline__ void syrk_gram_inplace(const TileTask& tk, const KPar
     }
     if constexpr (KIND != 0) {
         // ArdSE / IsoLinear / ArdLinear / ArdSEProduct: one block, two of its entries at a time (the exp per dimension of the
-        // additive kernel and the unrolled dot product each wanted one register more than the task has at four); Matern: one
-        // entry at a time (a sqrt and an exp per entry)
-        constexpr int NE = (KIND == 5) ? 1 : 2;
+        // additive kernel and the unrolled dot product each wanted one register more than the task has at four); Matern and
+        // rational quadratic: one entry at a time (a sqrt, resp. a log1p, and an exp per entry)
+        constexpr int NE = (KIND >= 5) ? 1 : 2;
 #pragma unroll
         for (int i = 0; i < 9; ++i)
 #pragma unroll
@@ -839,9 +839,10 @@ __device__ __forceinline__ void diag_reg_body(const DiagTask& tk, d4 (&acc)[9], 
     }
 }
 
-// MATERN: the diagonal blocks of Matern leaves (DSMGP kinds 5-8), in a launch of their own (diag_fused_reg_matern_kernel).  As a
+// DK = 5: the diagonal blocks of Matern leaves (DSMGP kinds 5-8), in a launch of their own (diag_fused_reg_matern_kernel).  As a
 // sixth arm of the other kinds' kernel the sqrt + exp epilogue cost diag_fused_reg_kernel 104 bytes of scratch per lane.
-template <int W, bool MATERN>
+// DK = 6: those of rational quadratic leaves (kinds 9, 10), likewise (diag_fused_reg_rq_kernel).  DK = 0: every other kind.
+template <int W, int DK>
 __device__ __forceinline__ void diag_fused_reg(const TileTask& tt, const DiagTask& d, const KParam* __restrict__ kp, int D, double* S) {
     constexpr int SHAPE = W == 3 ? 1 : 0;
     constexpr int rbase = (W == 2) ? 2 : 5, cbase = (W == 1) ? 3 : 0;
@@ -858,20 +859,20 @@ __device__ __forceinline__ void diag_fused_reg(const TileTask& tt, const DiagTas
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 acc[i][r] = (diagr_rb(W, i) == diagr_cb(W, i) && (int)(threadIdx.x & 15) == (int)((threadIdx.x & 63) >> 4) + 4 * r) ? 4.0 : 0.0;
-    } else if constexpr (MATERN) syrk_gram_inplace<SHAPE, 5>(tt, p, D, acc, blk, S);
+    } else if constexpr (DK != 0) syrk_gram_inplace<SHAPE, DK>(tt, p, D, acc, blk, S);
     else DSMGP_KIND_DISPATCH_NON_MATERN(p.kind, K, syrk_gram_inplace<SHAPE, K>(tt, p, D, acc, blk, S));
     __syncthreads();                                        // the coordinates are no longer read: panel and rhs take their place
     diag_reg_body<W>(d, acc, S);
 }
 
-// One diagonal-block task of a FUSED step.  Both kernels below run over the whole diagonal-block list of the step and take the
+// One diagonal-block task of a FUSED step.  The kernels below run over the whole diagonal-block list of the step and take the
 // tasks of their own kinds: which kinds a leaf has is read here, at the launch, from the hyper-parameters of that fit -- the task
 // lists themselves do not depend on them (they can be built before set_hyper, e.g. by set_test under a device pool).
-template <bool MATERN>
+template <int DK>
 __device__ __forceinline__ void diag_fused_task(const DiagFusedTask* __restrict__ tasks, const KParam* __restrict__ kp, int D,
                                                 double* S) {
     const DiagFusedTask ft = tasks[blockIdx.x];
-    if ((kp[ft.kid].kind >= 5) != MATERN) return;          // another kernel's task (uniform over the workgroup)
+    if (diag_kernel_class(kp[ft.kid].kind) != DK) return;  // another kernel's task (uniform over the workgroup)
     TileTask tt{};
     tt.A = ft.A;
     tt.lda = ft.d.ld;
@@ -887,10 +888,10 @@ __device__ __forceinline__ void diag_fused_task(const DiagFusedTask* __restrict_
     // workgroup, so that the chains of co-resident tasks sit on different SIMDs, measured nothing: depth 4 0.0516-0.0522 s with
     // the role shifted by blockIdx, blockIdx / 8 or blockIdx / 256 as without.)
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (w == 0) diag_fused_reg<0, MATERN>(tt, ft.d, kp, D, S);
-    else if (w == 1) diag_fused_reg<1, MATERN>(tt, ft.d, kp, D, S);
-    else if (w == 2) diag_fused_reg<2, MATERN>(tt, ft.d, kp, D, S);
-    else diag_fused_reg<3, MATERN>(tt, ft.d, kp, D, S);
+    if (w == 0) diag_fused_reg<0, DK>(tt, ft.d, kp, D, S);
+    else if (w == 1) diag_fused_reg<1, DK>(tt, ft.d, kp, D, S);
+    else if (w == 2) diag_fused_reg<2, DK>(tt, ft.d, kp, D, S);
+    else diag_fused_reg<3, DK>(tt, ft.d, kp, D, S);
 }
 
 // the diagonal blocks of IsoSE / ArdSE / IsoLinear / ArdLinear / ArdSEProduct leaves
@@ -898,14 +899,21 @@ __global__ __launch_bounds__(256, DSMGP_DIAGR_WGS) void diag_fused_reg_kernel(co
                                                                               const KParam* __restrict__ kp, int D) {
     extern __shared__ __attribute__((aligned(16))) double S[];   // DIAGR_LDS_BYTES: ring / coordinates / panel share the space
     static_assert(GRAM_FUSE_MAX_D * TB * (int)sizeof(double) <= DIAGR_LDS_BYTES, "coordinates must fit");
-    diag_fused_task<false>(tasks, kp, D, S);
+    diag_fused_task<0>(tasks, kp, D, S);
 }
 
 // the diagonal blocks of Matern leaves (launched only while a kernel id has a Matern kind)
 __global__ __launch_bounds__(256, DSMGP_DIAGR_WGS) void diag_fused_reg_matern_kernel(const DiagFusedTask* __restrict__ tasks,
                                                                                      const KParam* __restrict__ kp, int D) {
     extern __shared__ __attribute__((aligned(16))) double S[];
-    diag_fused_task<true>(tasks, kp, D, S);
+    diag_fused_task<5>(tasks, kp, D, S);
+}
+
+// the diagonal blocks of rational quadratic leaves (launched only while a kernel id has such a kind)
+__global__ __launch_bounds__(256, DSMGP_DIAGR_WGS) void diag_fused_reg_rq_kernel(const DiagFusedTask* __restrict__ tasks,
+                                                                                 const KParam* __restrict__ kp, int D) {
+    extern __shared__ __attribute__((aligned(16))) double S[];
+    diag_fused_task<6>(tasks, kp, D, S);
 }
 
 // ---------------------------------------------------------------------------------------------

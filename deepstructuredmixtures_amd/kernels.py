@@ -20,6 +20,8 @@ KIND_ISO_MATERN32 = 5
 KIND_ISO_MATERN52 = 6
 KIND_ARD_MATERN32 = 7
 KIND_ARD_MATERN52 = 8
+KIND_ISO_RQ = 9
+KIND_ARD_RQ = 10
 
 
 class KernelFunction:
@@ -225,6 +227,63 @@ class ArdMatern32(_ArdMatern):
 class ArdMatern52(_ArdMatern):
     """Matern nu = 5/2 with per-dimension length-scales: s = sqrt(5 sum_d (a_d-b_d)^2 / exp(logl_d)^2)."""
     kind = KIND_ARD_MATERN52
+
+
+class IsoRQ(KernelFunction):
+    """Rational quadratic kernel with one length-scale (GPML's covRQiso): exp(2 logs) (1 + w)^(-alpha), w = |a-b|^2 /
+    (2 alpha exp(logl)^2), alpha = exp(loga) -- a scale mixture of squared exponentials whose shape alpha is trained with the
+    rest.  Not a kernel of the reference.  Hyper-vector [logl, loga, logs]; the gradients dl, da, ds are the true derivatives
+    (include/dsmgp_hip.h, dsmgp_gradients)."""
+    kind = KIND_ISO_RQ
+
+    def __init__(self, logl, loga, logs):
+        self.logl = float(logl)
+        self.loga = float(loga)
+        self.logs = float(logs)
+        self.dl = 0.0
+        self.da = 0.0
+        self.ds = 0.0
+
+    def loghyp(self):
+        return np.array([self.logl, self.loga, self.logs])
+
+    def set_loghyp(self, v):
+        self.logl, self.loga, self.logs = float(v[0]), float(v[1]), float(v[2])
+
+    def copy(self):
+        return IsoRQ(self.logl, self.loga, self.logs)
+
+    def __repr__(self):
+        return f"IsoRQ({self.logl}, {self.loga}, {self.logs})"
+
+
+class ArdRQ(KernelFunction):
+    """Rational quadratic kernel with one length-scale per input dimension (GPML's covRQard): w = sum_d (a_d-b_d)^2 /
+    (2 alpha exp(logl_d)^2) in the formula of IsoRQ.  Not a kernel of the reference.  Hyper-vector [logl_1..logl_D, loga, logs];
+    all gradients are the true derivatives."""
+    kind = KIND_ARD_RQ
+
+    def __init__(self, logl, loga, logs):
+        self.logl = np.array(logl, dtype=np.float64).reshape(-1)
+        self.loga = float(loga)
+        self.logs = float(logs)
+        self.dl = np.zeros_like(self.logl)
+        self.da = 0.0
+        self.ds = 0.0
+
+    def loghyp(self):
+        return np.concatenate([self.logl, [self.loga, self.logs]])
+
+    def set_loghyp(self, v):
+        self.logl = np.array(v[:-2], dtype=np.float64)
+        self.loga = float(v[-2])
+        self.logs = float(v[-1])
+
+    def copy(self):
+        return ArdRQ(self.logl.copy(), self.loga, self.logs)
+
+    def __repr__(self):
+        return f"ArdRQ({self.logl.tolist()}, {self.loga}, {self.logs})"
 
 
 class ConstMean:

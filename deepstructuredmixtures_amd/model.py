@@ -18,7 +18,7 @@ except ImportError:          # pragma: no cover
 
 from . import hipabi
 from .kernels import (IsoSE, ConstMean, KIND_ISO_SE, KIND_ARD_SE, KIND_ISO_LINEAR, KIND_ARD_LINEAR, KIND_ARD_SE_PRODUCT,
-                      KIND_ISO_MATERN32, KIND_ISO_MATERN52, KIND_ARD_MATERN32, KIND_ARD_MATERN52)
+                      KIND_ISO_MATERN32, KIND_ISO_MATERN52, KIND_ARD_MATERN32, KIND_ARD_MATERN52, KIND_ISO_RQ, KIND_ARD_RQ)
 from .tree import (DSMGPConfig, GPSumNode, build_tree, get_leaves, get_overlap, obs_table, share_schedule, share_decisions,
                    share_census, route, route_all, route_index, get_child, ordered_nodes, SHARE_COPY, SHARE_FULL, SHARE_PREFIX)
 from . import dist as _dist
@@ -642,7 +642,7 @@ def _check_objective(objective):
 
 def updategradients(model, active=None, objective="mll"):
     """`updategradients!(spn)` (`src/fit.jl:306-311`): per-leaf gradient vectors in the reference's order
-    [dl..., ds, dnoise] (`src/gaussianprocess.jl:212-214`), computed on the device for the local leaves and
+    [dl..., ds, dnoise] (`src/gaussianprocess.jl:212-214`; [dl..., da, ds, dnoise] for the rational quadratic kernels), computed on the device for the local leaves and
     gathered.  Also stored on the leaves (kernel.dl / kernel.ds / dnoise) like the reference does.
     `active` (one flag per leaf, default all): only those leaves' gradients are computed, the other rows are zero --
     what `finetune!` needs, whose pass for leaf j weights leaf l's gradient by the overlap D[j, l] (`src/optimize.jl:101`).
@@ -676,6 +676,10 @@ def updategradients(model, active=None, objective="mll"):
             lf.kernel.dl = float(row[0])
         elif lf.kernel.kind == KIND_ARD_LINEAR:       # [dl_1..dl_D, 0, dnoise]: no variance gradient
             lf.kernel.dl = row[: n - 1].copy()
+        elif lf.kernel.kind in (KIND_ISO_RQ, KIND_ARD_RQ):       # [dl..., da, ds, dnoise]: the shape sits before the variance
+            lf.kernel.dl = row[: n - 2].copy() if lf.kernel.kind == KIND_ARD_RQ else float(row[0])
+            lf.kernel.da = float(row[n - 2])
+            lf.kernel.ds = float(row[n - 1])
         else:
             ard = lf.kernel.kind in (KIND_ARD_SE, KIND_ARD_SE_PRODUCT, KIND_ARD_MATERN32, KIND_ARD_MATERN52)
             lf.kernel.dl = row[: n - 1].copy() if ard else float(row[0])
@@ -1490,7 +1494,8 @@ def _aggregate_dsmgp(model, xt, ptr, mu, var, sel_cache=None):
 
 def _prior_diag(lf, xt):
     k = lf.kernel
-    if k.kind in (KIND_ISO_SE, KIND_ARD_SE_PRODUCT, KIND_ISO_MATERN32, KIND_ISO_MATERN52, KIND_ARD_MATERN32, KIND_ARD_MATERN52):
+    if k.kind in (KIND_ISO_SE, KIND_ARD_SE_PRODUCT, KIND_ISO_MATERN32, KIND_ISO_MATERN52, KIND_ARD_MATERN32, KIND_ARD_MATERN52,
+                  KIND_ISO_RQ, KIND_ARD_RQ):
         return np.full(xt.shape[0], np.exp(2 * k.logs))
     if k.kind == KIND_ARD_SE:
         return np.full(xt.shape[0], np.exp(2 * k.logs) * xt.shape[1])

@@ -53,6 +53,15 @@ typedef struct dsmgp_ctx dsmgp_ctx;
 #define DSMGP_KIND_ISO_MATERN52 6   /* nu = 5/2, one length-scale */
 #define DSMGP_KIND_ARD_MATERN32 7   /* nu = 3/2, one length-scale per input dimension */
 #define DSMGP_KIND_ARD_MATERN52 8   /* nu = 5/2, one length-scale per input dimension */
+/* Rational quadratic kernels (GPML covRQiso / covRQard), a scale mixture of squared exponentials with a trainable shape:
+ * k(a, b) = sigma^2 (1 + w)^(-alpha), w = sum_d (a_d - b_d)^2 / (2 alpha l_d^2), alpha = exp(loga); k(x, x) = sigma^2 exactly.  w is
+ * added in ascending d from (a_d - b_d)^2 * (1 / (2 alpha l_d^2)), one fma per dimension, and the value is sigma^2 exp(-alpha
+ * log1p(w)) (k(a, b) == k(b, a) to the bit; the iso kind is its ARD kind with all l_d equal, to the bit).  The first kinds with a
+ * shape parameter: it sits between the length-scales and logs.  Iso hyper-vector [logl, loga, logs, logNoise] (exactly 4 values);
+ * ARD [logl_1..logl_D, loga, logs, logNoise] (exactly D + 3 values once set_train has fixed D): set_hyper refuses other lengths.
+ * Not kernels of the reference. */
+#define DSMGP_KIND_ISO_RQ 9         /* one length-scale */
+#define DSMGP_KIND_ARD_RQ 10        /* one length-scale per input dimension */
 
 /* per-leaf sharing decisions of the shared-Cholesky fit! (src/fit.jl:107-117) */
 #define DSMGP_SHARE_FULL   0      /* update_cholesky!               src/gaussianprocess.jl:82-108 */
@@ -103,7 +112,9 @@ int dsmgp_set_sharing(dsmgp_ctx* ctx, const int32_t* op /* L */, const int32_t* 
                       const int64_t* prefix_len /* L */);
 
 /* replaces setparams!(gp, hyper) (src/gaussianprocess.jl:153-161, src/optimize.jl:188-198) for all
- * leaves of one kernel id; n = (#lengthscales) + 2 */
+ * leaves of one kernel id; n = (#lengthscales) + 2, one more for the rational quadratic kinds (their shape loga).  DSMGP_E_ARG:
+ * an unknown kind, a non-finite value, or a length the kind does not take (checked here for kinds 4-10, at the fit for the
+ * reference's kinds) */
 int dsmgp_set_hyper(dsmgp_ctx* ctx, int32_t kernel_id, int32_t kind, const double* loghyp, int32_t n);
 
 /* ---- fit!: Gram assembly + Cholesky + alpha for every leaf
@@ -160,7 +171,8 @@ int dsmgp_predict_cov(dsmgp_ctx* ctx, int32_t leaf, int32_t with_noise, double* 
  * The kernel derivatives are true derivatives, finite at x_t = x_i (nothing divides by a distance): with D_d = x_{t,d} - x_{i,d},
  * -k D_d / l_d^2 (IsoSE, ArdSEProduct), -sigma^2 exp(-D_d^2 / 2 l_d^2) D_d / l_d^2 (ArdSE: term d only), x_{i,d} / l_d^2 (the
  * linear kinds, whose dk(x_t, x_t) / dx_{t,d} = 2 x_{t,d} / l_d^2; it is 0 for the stationary kinds), and
- * -sigma^2 exp(-s) c(s) (2 nu / l_d^2) D_d for the Matern kinds, c(s) as in dsmgp_gradients.  Any D.
+ * -sigma^2 exp(-s) c(s) (2 nu / l_d^2) D_d for the Matern kinds, c(s) as in dsmgp_gradients, and -k / (1 + w) D_d / l_d^2 for the
+ * rational quadratic kinds.  Any D.
  * Needs dsmgp_predict_run on the current fit (DSMGP_E_STATE otherwise), on either route to K_tn L^-T: rows that rode through the
  * fit, or the standalone sweep; one lane or two.  No routed rows at all: success, nothing written.  Leaves whose fit reported
  * info != 0 get NaN rows, the others are unaffected.  Sums are added in a fixed order: the same bits from call to call, and
@@ -217,7 +229,10 @@ int dsmgp_scores(dsmgp_ctx* ctx, const double* y_test /* n_t */, double* out /* 
  *      (x_rd - x_cd)^2 / l_d^2 and ds = tr(W K), W = alpha alpha^T - K_y^-1, K without noise; any D.
  *      Matern (kinds 5-8): iso [dl, ds, dnoise], ARD [dl_1..dl_D, ds, dnoise], all true derivatives (no SURVEY F7 factor):
  *      dl_d = 0.5 sum_rc W_rc sigma^2 exp(-s) c(s) s_d^2 with s_d^2 = 2 nu (x_rd - x_cd)^2 / l_d^2, c(s) = 1 (nu = 3/2) or
- *      (1 + s) / 3 (nu = 5/2) -- finite at s = 0, nothing divides by r; the iso dl is the sum over d; ds = tr(W K); any D. */
+ *      (1 + s) / 3 (nu = 5/2) -- finite at s = 0, nothing divides by r; the iso dl is the sum over d; ds = tr(W K); any D.
+ *      Rational quadratic (kinds 9, 10): iso [dl, da, ds, dnoise], ARD [dl_1..dl_D, da, ds, dnoise], all true derivatives:
+ *      dl_d = 0.5 sum_rc W_rc K_rc / (1 + w) (x_rd - x_cd)^2 / l_d^2 (the iso dl is the sum over d),
+ *      da = 0.5 sum_rc W_rc K_rc alpha (w / (1 + w) - log1p(w)), ds = tr(W K); any D.  Zeros past the hyper-vector. */
 int dsmgp_gradients(dsmgp_ctx* ctx, double* grad_out, int32_t stride);
 /* Restricts dsmgp_gradients to the leaves with active[l] != 0 (NULL: every leaf again; a new leaf table resets it): the rows
  * of the others come back as zeros, and neither L^-T nor the contraction tiles of leaves nobody asked for are computed (a
@@ -255,7 +270,8 @@ int dsmgp_loo(dsmgp_ctx* ctx, double* mu_out, double* var_out /* obs_ptr[L] each
  * d = diag G, alpha = G (y - m):
  *   dlpd / dtheta = sum_rc M_rc (dK_y / dtheta)_rc,   M = (u alpha^T + alpha u^T) / 2 - H H^T,
  *   u = G (alpha / d),   H = G diag(sqrt w),   w_i = (1 + alpha_i^2 / d_i) / (2 d_i).
- * grad_out[l * stride + j], j over [dl..., ds, dnoise] -- the layout of dsmgp_gradients -- and EVERY component is the true
+ * grad_out[l * stride + j], j over [dl..., ds, dnoise] ([dl..., da, ds, dnoise] for the rational quadratic kinds) -- the layout
+ * of dsmgp_gradients -- and EVERY component is the true
  * derivative, for all kinds: no factor sigma for IsoSE, true per-dimension length-scale derivatives for the additive ArdSE
  * whatever DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT says (ArdSE leaves with more input dimensions than the contraction stages, 35:
  * DSMGP_E_ARG), the sum over the dimensions in ascending order for an iso Matern kind, 0 in the dummy variance slot of the

@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, predict_cov, predict_gradients, loo, loo_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52
+export attach!, detach!, census, predict_cov, predict_gradients, loo, loo_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -115,6 +115,45 @@ DeepStructuredMixtures.getdistancematrix(k::IsoMatern, x1::AbstractMatrix, x2::A
 DeepStructuredMixtures.getdistancematrix(k::ArdMatern, x1::AbstractMatrix, x2::AbstractMatrix) =
     DeepStructuredMixtures.getdistancematrix(ArdSE(k.logℓ, k.logσ), x1, x2)
 
+# ---------------------------------------------------------------------------------------------- rational quadratic
+"""
+    IsoRQ(logℓ, logα, logσ), ArdRQ(logℓ, logα, logσ)
+
+Rational quadratic kernels (GPML's covRQiso / covRQard): k = σ² (1 + w)^(-α), w = Σ_d (a_d - b_d)² / (2 α ℓ_d²), α = exp(logα).
+IsoSE's / ArdSE's fields plus the shape logα and its gradient ∂α.  Not kernels of the reference: they live on the device only
+(kinds 9 and 10); hyper-vector [logℓ..., logα, logσ, logNoise], gradient row [∂ℓ..., ∂α, ∂σ, ∂ϵ], all true derivatives.
+"""
+mutable struct IsoRQ{T<:AbstractFloat} <: DeepStructuredMixtures.IsoKernel
+    logℓ::T
+    logα::T
+    logσ::T
+    ∂ℓ::T
+    ∂α::T
+    ∂σ::T
+end
+mutable struct ArdRQ{T<:AbstractFloat} <: DeepStructuredMixtures.ArdKernel
+    logℓ::Vector{T}
+    logα::T
+    logσ::T
+    ∂ℓ::Vector{T}
+    ∂α::T
+    ∂σ::T
+end
+IsoRQ(logℓ, logα, logσ) = IsoRQ(logℓ, logα, logσ, zero(logℓ), zero(logα), zero(logσ))
+ArdRQ(logℓ, logα, logσ) = ArdRQ(logℓ, logα, logσ, zero(logℓ), zero(logα), zero(logσ))
+const RQ = Union{IsoRQ,ArdRQ}
+DeepStructuredMixtures.getvariance(k::RQ; logscale=false) = logscale ? k.logσ : exp(2 * k.logσ)
+DeepStructuredMixtures.getstd(k::RQ) = exp(k.logσ)
+DeepStructuredMixtures.setvariance!(k::RQ, v::AbstractFloat) = (k.logσ = v)
+DeepStructuredMixtures.getlengthscales(k::IsoRQ; logscale=false) = logscale ? k.logℓ : exp(k.logℓ)
+DeepStructuredMixtures.getlengthscales(k::ArdRQ; logscale=false) = logscale ? k.logℓ : exp.(k.logℓ)
+DeepStructuredMixtures.setlengthscale!(k::IsoRQ, l::AbstractFloat) = (k.logℓ = l)
+DeepStructuredMixtures.setlengthscale!(k::ArdRQ, l::AbstractVector) = (k.logℓ[:] = l)
+DeepStructuredMixtures.getdistancematrix(k::IsoRQ, x1::AbstractMatrix, x2::AbstractMatrix) =
+    DeepStructuredMixtures.getdistancematrix(IsoSE(k.logℓ, k.logσ), x1, x2)
+DeepStructuredMixtures.getdistancematrix(k::ArdRQ, x1::AbstractMatrix, x2::AbstractMatrix) =
+    DeepStructuredMixtures.getdistancematrix(ArdSE(k.logℓ, k.logσ), x1, x2)
+
 # ---------------------------------------------------------------------------------------------- library
 const LIB = Ref{Ptr{Cvoid}}(C_NULL)
 function lib()
@@ -137,6 +176,8 @@ kind(::IsoMatern32) = Int32(5)   # DSMGP_KIND_ISO_MATERN32: σ² (1 + s) e^(-s),
 kind(::IsoMatern52) = Int32(6)   # DSMGP_KIND_ISO_MATERN52: σ² (1 + s + s²/3) e^(-s), s = √5 r
 kind(::ArdMatern32) = Int32(7)   # DSMGP_KIND_ARD_MATERN32: as 5 with one ℓ_d per dimension
 kind(::ArdMatern52) = Int32(8)   # DSMGP_KIND_ARD_MATERN52: as 6 with one ℓ_d per dimension
+kind(::IsoRQ) = Int32(9)         # DSMGP_KIND_ISO_RQ: σ² (1 + w)^(-α), w = r² / (2 α); not kernels of the reference
+kind(::ArdRQ) = Int32(10)        # DSMGP_KIND_ARD_RQ: as 9 with one ℓ_d per dimension
 # hyper-vector of one kernel id on the reference's log scale, [logℓ..., logσ, logNoise] (src/gaussianprocess.jl:141-161)
 loghyp(k::IsoSE, ln) = Float64[k.logℓ, k.logσ, ln]
 loghyp(k::ArdSE, ln) = Float64[k.logℓ..., k.logσ, ln]
@@ -145,6 +186,8 @@ loghyp(k::ArdLinear, ln) = Float64[k.logℓ..., 0.0, ln]          # ... here too
 loghyp(k::ArdSEProduct, ln) = Float64[k.logℓ..., k.logσ, ln]    # the layout of ArdSE
 loghyp(k::IsoMatern, ln) = Float64[k.logℓ, k.logσ, ln]          # the layout of IsoSE
 loghyp(k::ArdMatern, ln) = Float64[k.logℓ..., k.logσ, ln]       # the layout of ArdSE
+loghyp(k::IsoRQ, ln) = Float64[k.logℓ, getfield(k, :logα), k.logσ, ln]      # the shape sits between the length-scales and logσ
+loghyp(k::ArdRQ, ln) = Float64[k.logℓ..., getfield(k, :logα), k.logσ, ln]
 
 # ---------------------------------------------------------------------------------------------- session
 "One device context + the leaf table of one model (or of one stand-alone GaussianProcess)."
@@ -628,11 +671,17 @@ function fetchgradients!(s::Session)
     GC.@preserve g chk(s, ccall(sym(:dsmgp_gradients), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32), s.h, g, Int32(s.stride)))
     for (l, gp) in enumerate(s.gps)
         k = gp.kernel
-        nl = k isa Union{ArdSE,ArdLinear} || k isa ArdSEProduct || k isa ArdMatern ? length(k.logℓ) : 1
-        if k isa Union{ArdSE,ArdLinear} || k isa ArdSEProduct || k isa ArdMatern
+        nl = k isa Union{ArdSE,ArdLinear} || k isa ArdSEProduct || k isa ArdMatern || k isa ArdRQ ? length(k.logℓ) : 1
+        if k isa Union{ArdSE,ArdLinear} || k isa ArdSEProduct || k isa ArdMatern || k isa ArdRQ
             k.∂ℓ[:] = g[1:nl, l]        # ArdLinear: written in place, never through getgradients (src/kernels.jl:247 cannot run)
         else
             k.∂ℓ = g[1, l]
+        end
+        if k isa RQ                      # rational quadratic: [∂ℓ..., ∂α, ∂σ, ∂ϵ]
+            setfield!(k, :∂α, g[nl + 1, l])     # a field of this binding's own types, not of a reference struct
+            k.∂σ = g[nl + 2, l]
+            gp.∂ϵ.value = g[nl + 3, l]
+            continue
         end
         k isa Union{IsoLinear,ArdLinear} || (k.∂σ = g[nl + 1, l])
         gp.∂ϵ.value = g[nl + 2, l]
