@@ -7,6 +7,7 @@
 #endif
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
+#include "kernels_targets.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -601,6 +602,22 @@ struct dsmgp_ctx {
     bool predicted = false;
     int64_t route_total = 0;
 
+    // several target columns on the current factors (dsmgp_solve_targets / dsmgp_predict_targets, kernels_targets.hpp): allocated on
+    // first use, not part of bytes_needed, dropped with the plan (free_targets); what depends on the test set goes with it (free_test)
+    double* arenaT = nullptr;       // per leaf Yc | Z, npad x Qpad each (grow-only, from the pool when there is one)
+    size_t cap_T = 0;
+    int tg_Q = 0, tg_qpad = 0;      // columns of the resident Z; the Qpad the lists below were built for
+    bool tg_lists = false;          // toff / tfwd point into the current arenaT and the current plan's factors
+    bool tg_valid = false;          // Z holds L^-1 (Y - mean) for the CURRENT fit (cleared by a fit)
+    std::vector<size_t> toff;       // per leaf: offset of its Yc in arenaT
+    DevBuf<long long> d_toff;
+    DevBuf<double> d_tY, d_tmean, d_tmll;       // Y (N x Q), mean and mll (L x Q)
+    DevBuf<TargetsFwdTask> tfwd;    // the sweep's tasks, lane after lane: lane q's launch s is entry q * tfwd_steps + s of tfwd_off
+    std::vector<int> tfwd_off;      //   (launch 0: Z_0 of every leaf; launch s: block column s - 1)
+    int tfwd_steps = 0, tfwd_lanes = 1;
+    DevBuf<TargetsMuTask> tmu;      // test tiles, rebuilt per call
+    DevBuf<double> d_tmu;           // mu, route_total x Q (ld = route_total)
+
     // aggregation of the leaf moments per test row + scores (dsmgp_aggregate*, dsmgp_scores)
     DevBuf<int64_t> d_row_ptr;      // n_t + 1: entries of every test row (built by set_test)
     DevBuf<int32_t> d_row_ent;      // entry positions, ascending per row
@@ -927,6 +944,22 @@ void free_grad(dsmgp_ctx* c) {
     c->d_lgpart.release();
 }
 
+// the resident target columns (dsmgp_solve_targets): they go with the plan -- a new leaf table, new training data, dsmgp_release --
+// and, under a reserved pool, with whatever resets the pool's stack below them
+void free_targets(dsmgp_ctx* c) {
+    arena_put(c, c->arenaT);
+    c->cap_T = 0;
+    c->tg_lists = c->tg_valid = false;
+    c->tg_Q = c->tg_qpad = 0;
+    c->d_toff.release();
+    c->d_tY.release();
+    c->d_tmean.release();
+    c->d_tmll.release();
+    c->tfwd.release();
+    c->tmu.release();
+    c->d_tmu.release();
+}
+
 void free_tree(dsmgp_ctx* c) {
     c->rtree = RouteTree{};
     c->rt_kind.release();
@@ -966,6 +999,7 @@ void free_plan(dsmgp_ctx* c) {
     c->dinvc_fwd.release();
     c->dinvc_all.release();
     free_grad(c);
+    free_targets(c);
     c->plan_ready = false;
     c->phase_ready = false;
     c->fitted = false;
@@ -977,6 +1011,7 @@ void free_test(dsmgp_ctx* c, bool keep) {
     drop_graphs(c);
     if (c->pool_base) {      // the gradient arenas sit above (or would be clobbered below) the test arenas
         free_grad(c);
+        free_targets(c);
         c->pool_top = c->pool_mark_plan;
         keep = false;
     }
@@ -1014,6 +1049,8 @@ void free_test(dsmgp_ctx* c, bool keep) {
     c->pgfin.drop(keep);
     c->d_pgpart.drop(keep);
     c->d_pgout.drop(keep);
+    c->tmu.drop(keep);
+    c->d_tmu.drop(keep);
     for (auto& lane : c->phaseJ)
         for (auto& ph : lane) ph.drop(keep);
     for (auto& sl : c->slabJ) arena_put(c, sl);
@@ -2587,6 +2624,7 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
     c->vt_valid = false;
     c->alpha_valid = false;
     c->xinv_all = false;
+    c->tg_valid = false;            // Z of dsmgp_solve_targets belongs to the factors this fit replaces
     // Replay the sequence as a graph while nothing inside it records events (profile 0); capture it on first use
     const int gk = joint ? 1 : 0;
     if (c->use_graph && c->profile == 0) {
@@ -4064,6 +4102,198 @@ int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int
     if (dvar_out)
         HIPCHK(c, hipMemcpy2D(dvar_out, (size_t)ld * sizeof(double), c->d_pgout.p + nr * (size_t)D, nr * sizeof(double),
                               nr * sizeof(double), (size_t)D, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Several target columns on the current factors (kernels_targets.hpp).  Z = L^-1 (Y[obs] - mean) for every leaf by a
+// right-looking block sweep on the matrix cores, one launch per block column and lane, every factor tile read once; then the
+// per-(leaf, column) log-marginals.  Writes its own arena only: z, alpha and everything else a fit left stay as they are
+// (ensure_dinv completes Dinv as every other reader of it does).
+namespace {
+static int build_targets_plan(dsmgp_ctx* c, int qpad) {      // (static: inside extern "C" an unnamed namespace alone still exports the name)
+    const int L = c->L;
+    c->tg_lists = c->tg_valid = false;
+    c->toff.assign((size_t)L, 0);
+    size_t tot = 0;
+    int maxnb = 0;
+    for (int l = 0; l < L; ++l) {
+        c->toff[(size_t)l] = tot;
+        tot += 2 * (size_t)c->leaves[l].npad * (size_t)qpad;
+        maxnb = std::max(maxnb, c->leaves[l].nb);
+    }
+    if (int rc = slab_grow(c, c->arenaT, c->cap_T, tot)) {
+        (void)hipGetLastError();
+        return rc;
+    }
+    std::vector<long long> ho((size_t)L);
+    for (int l = 0; l < L; ++l) ho[(size_t)l] = (long long)c->toff[(size_t)l];
+    if (int rc = dev_upload(c, c->d_toff, ho)) return rc;
+    // launch 0: Z_0 = Dinv_0 Yc_0 of every leaf; launch s >= 1: block column k = s - 1, the tasks of blocks i = k + 1 .. nb - 1,
+    // that of i = k + 1 going on to Z_i.  A COPY leaf reads its source's factor (h_leaves: F / Dinv alias) and has blocks of its own.
+    const int nl = c->nlanes, ns = maxnb;
+    std::vector<TargetsFwdTask> tasks;
+    c->tfwd_off.assign((size_t)nl * ns + 1, 0);
+    for (int q = 0; q < nl; ++q)
+        for (int s = 0; s < ns; ++s) {
+            c->tfwd_off[(size_t)q * ns + s] = (int)tasks.size();
+            for (int l = 0; l < L; ++l) {
+                const LeafHost& lf = c->leaves[l];
+                if ((nl > 1 && c->leaf_lane[l] != q) || lf.nb <= s) continue;
+                const LeafDev& d = c->h_leaves[l];
+                double* yc = c->arenaT + c->toff[(size_t)l];
+                double* z = yc + (size_t)lf.npad * qpad;
+                TargetsFwdTask t{};
+                t.ldt = t.ldz = lf.npad;
+                t.qpad = qpad;
+                if (s == 0) {
+                    t.src = yc;
+                    t.dst = z;
+                    t.Dinv = d.Dinv;
+                    t.nrows = std::min(TB, lf.n);
+                    tasks.push_back(t);
+                    continue;
+                }
+                const int k = s - 1;
+                for (int i = k + 1; i < lf.nb; ++i) {
+                    t.T = d.F + (size_t)i * TB + (size_t)k * TB * lf.npad;
+                    t.Zk = z + (size_t)k * TB;
+                    t.src = (k == 0 ? yc : z) + (size_t)i * TB;
+                    t.dst = z + (size_t)i * TB;
+                    t.Dinv = i == k + 1 ? d.Dinv + (size_t)i * TB * TB : nullptr;
+                    t.nrows = std::min(TB, lf.n - i * TB);
+                    tasks.push_back(t);
+                }
+            }
+        }
+    c->tfwd_off[(size_t)nl * ns] = (int)tasks.size();
+    if (int rc = dev_upload(c, c->tfwd, tasks)) return rc;
+    c->tfwd_steps = ns;
+    c->tfwd_lanes = nl;
+    c->tg_qpad = qpad;
+    c->tg_lists = true;
+    return 0;
+}
+}  // namespace
+
+int dsmgp_solve_targets(dsmgp_ctx* c, const double* Y, int64_t N, int32_t Q, int64_t ldy, const double* mean, double* mll_out,
+                        double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->fitted) return fail(c, DSMGP_E_STATE, "solve_targets before fit");
+    if (!Y || N != c->N || Q < 1 || Q > 65535 || ldy < N)
+        return fail(c, DSMGP_E_ARG, "solve_targets: Y is NULL, N is not the N of set_train, Q outside 1 .. 65535 or ldy < N");
+    const int L = c->L;
+    for (int32_t j = 0; j < Q; ++j)
+        for (int64_t i = 0; i < N; ++i)
+            if (!std::isfinite(Y[i + (size_t)j * ldy])) return fail(c, DSMGP_E_ARG, "solve_targets: non-finite value in Y");
+    if (mean)
+        for (size_t i = 0; i < (size_t)L * Q; ++i)
+            if (!std::isfinite(mean[i])) return fail(c, DSMGP_E_ARG, "solve_targets: non-finite value in mean");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int qpad = round_up(Q, TQ);
+    if (!c->tg_lists || c->tg_qpad != qpad)
+        if (int rc = build_targets_plan(c, qpad)) return rc;
+    c->tg_valid = false;
+    if (int rc = c->d_tY.grow(c, (size_t)N * Q)) return rc;
+    if (int rc = c->d_tmean.grow(c, (size_t)L * Q)) return rc;
+    if (int rc = c->d_tmll.grow(c, (size_t)L * Q)) return rc;
+    HIPCHK(c, hipMemcpy2D(c->d_tY.p, (size_t)N * sizeof(double), Y, (size_t)ldy * sizeof(double), (size_t)N * sizeof(double),
+                          (size_t)Q, hipMemcpyHostToDevice));
+    if (mean) HIPCHK(c, hipMemcpy(c->d_tmean.p, mean, (size_t)L * Q * sizeof(double), hipMemcpyHostToDevice));
+    else HIPCHK(c, hipMemset(c->d_tmean.p, 0, (size_t)L * Q * sizeof(double)));
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    if (int rc = ensure_dinv(c)) return rc;       // the diagonal solves multiply with the whole Dinv_k
+    {
+        int maxpad = 0;
+        for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
+        for (int l0 = 0; l0 < L; l0 += 32768) {
+            const int cnt = std::min(32768, L - l0);
+            targets_gather_kernel<<<dim3((maxpad + 255) / 256, cnt), 256, 0, c->stream>>>(
+                c->d_leaves.p, c->d_obs_ptr.p, c->d_obs_idx.p, c->d_tY.p, N, Q, qpad, c->d_tmean.p, L, c->arenaT, c->d_toff.p, l0);
+        }
+    }
+    if (int rc = fork_lanes(c, c->tfwd_lanes)) return rc;
+    for (int s = 0; s < c->tfwd_steps; ++s)
+        for (int lane = 0; lane < c->tfwd_lanes; ++lane) {
+            const int v = lane * c->tfwd_steps + s;
+            const int nt = c->tfwd_off[(size_t)v + 1] - c->tfwd_off[(size_t)v];
+            if (nt > 0) targets_fwd_kernel<<<nt, 256, 0, c->lane_stream[lane]>>>(c->tfwd.p + c->tfwd_off[(size_t)v]);
+        }
+    if (int rc = join_lanes(c, c->tfwd_lanes)) return rc;
+    targets_mll_kernel<<<dim3(L, Q), 256, 0, c->stream>>>(c->d_leaves.p, c->arenaT, c->d_toff.p, qpad, L, c->d_tmll.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = ms * 1e-3;
+    c->tg_Q = Q;
+    c->tg_valid = true;
+    if (mll_out) HIPCHK(c, hipMemcpy(mll_out, c->d_tmll.p, (size_t)L * Q * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int dsmgp_predict_targets(dsmgp_ctx* c, double* mu_out, int64_t ld, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "predict_targets before solve_targets on the current fit");
+    if (!c->predicted) return fail(c, DSMGP_E_STATE, "predict_targets before predict_run on the current fit");
+    const size_t nr = (size_t)c->route_total;
+    if (nr == 0) return 0;          // (no routed rows: there is no sweep that would have set vt_valid)
+    if (!c->vt_valid) return fail(c, DSMGP_E_STATE, "predict_targets before predict_run on the current fit");
+    if (!mu_out || ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_targets: mu_out is NULL or ld < route_total");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int L = c->L, Q = c->tg_Q, qpad = c->tg_qpad;
+    if (int rc = c->d_tmu.grow(c, nr * (size_t)Q)) return rc;
+    std::vector<TargetsMuTask> tasks;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.nt == 0) continue;
+        const LeafDev& d = c->h_leaves[l];
+        for (int i = 0; i < lf.ntpad / TB; ++i) {
+            TargetsMuTask t{};
+            t.Vt = d.Vt + (size_t)i * TB;
+            t.Z = c->arenaT + c->toff[(size_t)l] + (size_t)lf.npad * qpad;
+            t.out = c->d_tmu.p + (size_t)lf.route_off + (size_t)i * TB;
+            t.info = d.info;
+            t.ldo = (long long)nr;
+            t.ldv = lf.ntpad;
+            t.ldz = lf.npad;
+            t.n = lf.n;
+            t.nrows = std::min(TB, lf.nt - i * TB);
+            t.leaf = l;
+            tasks.push_back(t);
+        }
+    }
+    c->stage_top = 0;       // (the stream is idle: every entry point synchronises before it returns)
+    if (int rc = stage_upload_list(c, c->tmu, tasks)) return rc;
+    if (int rc = stage_done(c)) return rc;
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    targets_mu_kernel<<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->tmu.p, c->d_tmean.p, L, Q, qpad);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = ms * 1e-3;
+    HIPCHK(c, hipMemcpy2D(mu_out, (size_t)ld * sizeof(double), c->d_tmu.p, nr * sizeof(double), nr * sizeof(double), (size_t)Q,
+                          hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int dsmgp_targets_fetch(dsmgp_ctx* c, int32_t leaf, double* Z_out) {
+    if (!c) return DSMGP_E_ARG;
+    if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "targets_fetch before solve_targets on the current fit");
+    if (leaf < 0 || leaf >= c->L || !Z_out) return fail(c, DSMGP_E_ARG, "targets_fetch: leaf out of range or Z_out is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    const LeafHost& lf = c->leaves[leaf];
+    const double* z = c->arenaT + c->toff[(size_t)leaf] + (size_t)lf.npad * c->tg_qpad;
+    HIPCHK(c, hipMemcpy2D(Z_out, (size_t)lf.n * sizeof(double), z, (size_t)lf.npad * sizeof(double), (size_t)lf.n * sizeof(double),
+                          (size_t)c->tg_Q, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,0 +1,234 @@
+// Several target columns on one factorisation (dsmgp_solve_targets / dsmgp_predict_targets): gather, multi-column forward
+// substitution, per-(leaf, column) log-marginal and predictive means.  Nothing here writes what another entry point reads.
+//
+// Layout: every leaf has two npad x Qpad column-major blocks (ld = npad), Yc = Y[obs, :] - mean and Z = L^-1 Yc; Qpad = Q
+// rounded up to 16, the N width of v_mfma_f64_16x16x4_f64.  Padding rows and padding columns are zero.
+//
+// Both tile kernels form their products as C^T = B^T A^T: the MFMA's first operand is the 16-column chunk of the targets
+// (lane: column l15, k = l4), its second the factor / Vt rows (lane: row l15, k = l4), and register r of the result is
+// (column l4 + 4 r, row l15) -- 16 consecutive rows per store.  An output column is a sum over its own target column only, in
+// the k order of the instruction sequence: column j's bits do not depend on Q or on what the other columns hold.
+#pragma once
+#include "kernels.hpp"
+
+namespace dsmgp {
+
+constexpr int TQ = 16;          // target columns per MFMA chunk
+constexpr int TLW = TB + 4;     // LDS leading dimension of the 16 x 128 block of W handed to the diagonal solve
+
+// Yc[l] = Y[obs(l), :] - mean[l, :], zero in the padding rows and columns; one thread per row, columns in a loop
+__global__ __launch_bounds__(256) void targets_gather_kernel(const LeafDev* __restrict__ leaves, const int64_t* __restrict__ obs_ptr,
+                                                             const int64_t* __restrict__ obs_idx, const double* __restrict__ Y,
+                                                             int64_t N, int Q, int qpad, const double* __restrict__ mean, int L,
+                                                             double* __restrict__ arena, const long long* __restrict__ toff,
+                                                             int leaf0) {
+    const int l = leaf0 + blockIdx.y;
+    const LeafDev lf = leaves[l];
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= lf.npad) return;
+    const bool valid = r < lf.n;
+    const int64_t g = valid ? obs_idx[obs_ptr[l] + r] : 0;
+    double* yc = arena + toff[l];
+    for (int q = 0; q < qpad; ++q)
+        yc[r + (size_t)q * lf.npad] = (valid && q < Q) ? Y[g + (size_t)q * N] - mean[l + (size_t)q * L] : 0.0;
+}
+
+// One task of the right-looking sweep Z = L^-1 Yc, block step k of a leaf:
+//   T != null:  W_i = src_i - L[i, k] Z_k   (src = Yc in step 0, Z afterwards: block i is read and written by this task alone)
+//   Dinv != null (the task of i = k + 1, whose block is final after this update; and the leaf's first task, T == null, i = 0):
+//               Z_i = Dinv_i W_i, lower triangle of Dinv_i only, instead of W_i
+// so a launch per block step reads every factor tile of its block column once and the next launch finds Z_{k+1} ready.  The
+// sums of a block run over k ascending, one task per (leaf, block, step): fixed order, no atomics, nothing depends on what
+// else is in the launch.  Right-looking, not left-looking: step k of one leaf is nb - k - 1 independent tasks instead of one
+// workgroup that walks a whole block row of the factor.
+// Rows >= nrows of block i (padding of the leaf's last block) are masked on load -- factor rows, Dinv rows and columns -- and
+// come out as zeros whatever the arenas hold there.
+struct TargetsFwdTask {
+    const double* T;        // L[i, k], ld = ldt; null: no update
+    const double* Zk;       // Z block k (128 x qpad, ld = ldz)
+    const double* src;      // block i of Yc or Z
+    double* dst;            // block i of Z
+    const double* Dinv;     // Dinv_i (ld 128) or null
+    int ldt, ldz, qpad, nrows;
+};
+
+__global__ __launch_bounds__(256) void targets_fwd_kernel(const TargetsFwdTask* __restrict__ tasks) {
+    __shared__ double sW[TQ * TLW];
+    const TargetsFwdTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const bool upd = tk.T != nullptr, solve = tk.Dinv != nullptr;
+    // this wave's rows of the factor tile: (row = 32 w + 16 rn + l15, k = 4 kk + l4), read once for all column chunks
+    double ft[2][32];
+    if (upd) {
+#pragma unroll
+        for (int rn = 0; rn < 2; ++rn) {
+            const int row = 32 * w + 16 * rn + l15;
+            const double* p = tk.T + row + (size_t)l4 * tk.ldt;
+#pragma unroll
+            for (int kk = 0; kk < 32; ++kk) ft[rn][kk] = row < tk.nrows ? p[(size_t)(4 * kk) * tk.ldt] : 0.0;
+        }
+    }
+    for (int q0 = 0; q0 < tk.qpad; q0 += TQ) {
+        d4 acc[2];
+        acc[0] = (d4){0.0, 0.0, 0.0, 0.0};
+        acc[1] = (d4){0.0, 0.0, 0.0, 0.0};
+        if (upd) {
+            const double* pz = tk.Zk + l4 + (size_t)(q0 + l15) * tk.ldz;      // (k = 4 kk + l4, column q0 + l15)
+#pragma unroll
+            for (int kk = 0; kk < 32; ++kk) {
+                const double fz = pz[4 * kk];
+                acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fz, ft[0][kk], acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fz, ft[1][kk], acc[1], 0, 0, 0);
+            }
+        }
+        // register r of acc[rn]: (column q0 + l4 + 4 r, row 32 w + 16 rn + l15)
+        double wv[2][4];
+#pragma unroll
+        for (int rn = 0; rn < 2; ++rn) {
+            const int row = 32 * w + 16 * rn + l15;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const size_t at = (size_t)row + (size_t)(q0 + l4 + 4 * r) * tk.ldz;
+                wv[rn][r] = row < tk.nrows ? tk.src[at] - acc[rn][r] : 0.0;
+            }
+        }
+        if (!solve) {
+#pragma unroll
+            for (int rn = 0; rn < 2; ++rn)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    tk.dst[(size_t)(32 * w + 16 * rn + l15) + (size_t)(q0 + l4 + 4 * r) * tk.ldz] = wv[rn][r];
+            continue;
+        }
+        // Z_i = Dinv_i W_i: the 16 x 128 block of W meets in LDS, wave w multiplies rows 32 w .. 32 w + 31 of Dinv_i over
+        // k < 32 (w + 1) -- beyond that the triangle is empty
+        __syncthreads();        // the block of the chunk before has been read
+#pragma unroll
+        for (int rn = 0; rn < 2; ++rn)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sW[(l4 + 4 * r) * TLW + 32 * w + 16 * rn + l15] = wv[rn][r];
+        __syncthreads();
+        d4 zz[2];
+        zz[0] = (d4){0.0, 0.0, 0.0, 0.0};
+        zz[1] = (d4){0.0, 0.0, 0.0, 0.0};
+        const int kend = 8 * (w + 1);
+        for (int kk = 0; kk < kend; ++kk) {
+            const int k = 4 * kk + l4;
+            const double fw = sW[l15 * TLW + k];
+            double fd[2];
+#pragma unroll
+            for (int rn = 0; rn < 2; ++rn) {
+                const int row = 32 * w + 16 * rn + l15;
+                fd[rn] = (k <= row && row < tk.nrows) ? tk.Dinv[row + (size_t)k * TB] : 0.0;
+            }
+            zz[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fw, fd[0], zz[0], 0, 0, 0);
+            zz[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fw, fd[1], zz[1], 0, 0, 0);
+        }
+#pragma unroll
+        for (int rn = 0; rn < 2; ++rn)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                tk.dst[(size_t)(32 * w + 16 * rn + l15) + (size_t)(q0 + l4 + 4 * r) * tk.ldz] = zz[rn][r];
+    }
+}
+
+// mll[l + j L] = -(|Z[:, j]|^2 + 2 sum log L_ii + n log 2pi) / 2, the sums and the tree of mll_kernel per (leaf, column);
+// NaN for a leaf whose fit reported info != 0.  Grid (L, Q).
+__global__ __launch_bounds__(256) void targets_mll_kernel(const LeafDev* __restrict__ leaves, const double* __restrict__ arena,
+                                                          const long long* __restrict__ toff, int qpad, int L,
+                                                          double* __restrict__ mll_out) {
+    __shared__ double red[256];
+    __shared__ double red2[256];
+    const int l = blockIdx.x, j = blockIdx.y;
+    const LeafDev lf = leaves[l];
+    const double* z = arena + toff[l] + (size_t)lf.npad * qpad + (size_t)j * lf.npad;
+    const int t = threadIdx.x;
+    double s = 0.0, ld = 0.0;
+    for (int i = t; i < lf.n; i += 256) {
+        s = fma(z[i], z[i], s);
+        ld += log(lf.F[i + (size_t)i * lf.npad]);
+    }
+    red[t] = s;
+    red2[t] = ld;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            red[t] += red[t + o];
+            red2[t] += red2[t + o];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const double log2pi = 1.8378770664093454835606594728112;
+        const double v = -(red[0] + 2.0 * red2[0] + log2pi * (double)lf.n) / 2.0;
+        mll_out[l + (size_t)j * L] = *lf.info != 0 ? __builtin_nan("") : v;
+    }
+}
+
+// mu[e, j] = mean[l, j] + sum_{c < n} Vt[e, c] Z[c, j] for a 128-row test tile of one leaf: wave w holds rows 32 w .. 32 w + 31
+// and up to TMU_CH column chunks at a time, so Vt is read once per TMU_CH * 16 columns.
+// The K_tn arena is not cleared: columns c >= n of Vt (and its rows >= nt) may hold anything, NaN included.  Columns c >= n are
+// MASKED ON LOAD here (the operand is 0.0 there, and Z's padding rows are zeros), so they never reach a sum; rows >= nt do
+// produce garbage, in their own output rows only, which are not stored.
+constexpr int TMU_CH = 4;
+struct TargetsMuTask {
+    const double* Vt;       // row tile of Vt, ld = ldv
+    const double* Z;        // npad x qpad, ld = ldz
+    double* out;            // mu of this tile's first row, column 0 (ld = ldo)
+    const int* info;
+    long long ldo;
+    int ldv, ldz, n, nrows, leaf, pad;
+};
+
+__global__ __launch_bounds__(256) void targets_mu_kernel(const TargetsMuTask* __restrict__ tasks, const double* __restrict__ mean,
+                                                         int L, int Q, int qpad) {
+    const TargetsMuTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const bool failed = *tk.info != 0;
+    const int nk = (tk.n + 3) / 4;
+    for (int q0 = 0; q0 < qpad; q0 += TMU_CH * TQ) {
+        const int nch = min(TMU_CH, (qpad - q0) / TQ);
+        d4 acc[TMU_CH][2];
+#pragma unroll
+        for (int ch = 0; ch < TMU_CH; ++ch) {
+            acc[ch][0] = (d4){0.0, 0.0, 0.0, 0.0};
+            acc[ch][1] = (d4){0.0, 0.0, 0.0, 0.0};
+        }
+        const double* pv = tk.Vt + 32 * w + l15;
+        const double* pz = tk.Z + (size_t)(q0 + l15) * tk.ldz;
+        for (int kk = 0; kk < nk; ++kk) {
+            const int c = 4 * kk + l4;
+            const bool in = c < tk.n;
+            const double v0 = in ? pv[(size_t)c * tk.ldv] : 0.0;
+            const double v1 = in ? pv[(size_t)c * tk.ldv + 16] : 0.0;
+#pragma unroll
+            for (int ch = 0; ch < TMU_CH; ++ch) {
+                if (ch >= nch) continue;
+                const double fz = in ? pz[c + (size_t)(ch * TQ) * tk.ldz] : 0.0;
+                acc[ch][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fz, v0, acc[ch][0], 0, 0, 0);
+                acc[ch][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fz, v1, acc[ch][1], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int ch = 0; ch < TMU_CH; ++ch) {
+            if (ch >= nch) continue;
+#pragma unroll
+            for (int rn = 0; rn < 2; ++rn) {
+                const int row = 32 * w + 16 * rn + l15;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int q = q0 + ch * TQ + l4 + 4 * r;
+                    if (row < tk.nrows && q < Q)
+                        tk.out[(size_t)row + (size_t)q * tk.ldo] =
+                            failed ? __builtin_nan("") : mean[tk.leaf + (size_t)q * L] + acc[ch][rn][r];
+                }
+            }
+        }
+    }
+}
+
+}  // namespace dsmgp

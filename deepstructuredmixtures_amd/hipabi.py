@@ -53,6 +53,9 @@ SIGNATURES = {
     "dsmgp_predict_leaves": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, _lp, _lp, _dp, _dp]),
     "dsmgp_predict_cov": (C.c_int, [_ctx, C.c_int32, C.c_int32, _dp, C.c_int64, _dp]),
     "dsmgp_predict_gradients": (C.c_int, [_ctx, _dp, _dp, C.c_int64, _dp]),
+    "dsmgp_solve_targets": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp, _dp]),
+    "dsmgp_predict_targets": (C.c_int, [_ctx, _dp, C.c_int64, _dp]),
+    "dsmgp_targets_fetch": (C.c_int, [_ctx, C.c_int32, _dp]),
     "dsmgp_gradients": (C.c_int, [_ctx, _dp, C.c_int32]),
     "dsmgp_loo": (C.c_int, [_ctx, _dp, _dp, _dp, _dp]),
     "dsmgp_loo_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp]),
@@ -193,6 +196,8 @@ class Context:
         self.D = 0
         self.route_total = 0
         self.n_t = 0
+        self.leaf_n = np.zeros(0, dtype=np.int64)
+        self.targets_Q = 0      # columns of the last solve_targets
 
     def _chk(self, rc):
         if rc != 0:
@@ -230,6 +235,7 @@ class Context:
         self._chk(self.lib.dsmgp_set_leaves(self.h, L, p0, p1, p2, p3))
         self.L = L
         self.n_obs = int(obs_ptr[-1])
+        self.leaf_n = np.diff(obs_ptr)      # rows of every leaf: the shape of targets_fetch
 
     def set_sharing(self, op, src, plen):
         if op is None:
@@ -390,6 +396,54 @@ class Context:
         self._chk(self.lib.dsmgp_loo_gradients(self.h, g.ctypes.data_as(_dp), int(stride), lpd.ctypes.data_as(_dp), C.byref(sec)))
         self.loo_gradients_seconds = sec.value
         return g, lpd
+
+    def solve_targets(self, Y, mean=None):
+        """Several target columns on the current fit (dsmgp_solve_targets): `Y` is `(N, Q)` over the rows of `set_train` (a
+        vector counts as one column), `mean` `(L, Q)` with the constant mean of every leaf and column (None: the ABI's zeros).
+        Leaves `Z = L^-1 (Y[obs] - mean)` of every leaf resident for `predict_targets` / `targets_fetch` and returns
+        `(mll[L, Q], device_seconds)`: the log marginal likelihood of every leaf under every column.  Leaves with `info != 0`
+        have NaN rows.  Nothing a fit left is touched."""
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y[:, None]
+        if Y.ndim != 2:
+            raise ValueError(f"targets of shape {Y.shape}: expected (N, Q)")
+        Y, py = _f64_fortran(Y)
+        N, Q = Y.shape
+        pm = None
+        if mean is not None:
+            mean = np.asarray(mean, dtype=np.float64)
+            if mean.ndim == 1:
+                mean = mean[:, None]
+            if mean.shape != (self.L, Q):
+                raise ValueError(f"mean of shape {mean.shape}: expected ({self.L}, {Q})")
+            mean, pm = _f64_fortran(mean)
+        mll = np.empty((self.L, Q), dtype=np.float64, order="F")
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_solve_targets(self.h, py, N, Q, max(1, N), pm, mll.ctypes.data_as(_dp), C.byref(sec)))
+        self.targets_Q = Q
+        self.targets_seconds = sec.value
+        return mll, sec.value
+
+    def predict_targets(self):
+        """`mu[route_total, Q]` (Fortran order): the predictive mean of every (leaf, routed test row) entry of `predict_fetch`
+        under every column of the last `solve_targets` (dsmgp_predict_targets; needs `solve_targets` and `predict_run` on the
+        current fit).  The variance does not depend on the targets: it is `predict_fetch`'s for every column.  The device time
+        of the call is left in `self.predict_targets_seconds`."""
+        n = int(self.route_total)
+        mu = np.empty((n, self.targets_Q), dtype=np.float64, order="F")
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_predict_targets(self.h, mu.ctypes.data_as(_dp), max(1, n), C.byref(sec)))
+        self.predict_targets_seconds = sec.value
+        return mu
+
+    def targets_fetch(self, leaf):
+        """`Z[n, Q] = L^-1 (Y[obs] - mean)` of one leaf as the last `solve_targets` left it (inspection)."""
+        leaf = int(leaf)
+        n = int(self.leaf_n[leaf]) if 0 <= leaf < self.L else 1
+        Z = np.empty((n, self.targets_Q), dtype=np.float64, order="F")
+        self._chk(self.lib.dsmgp_targets_fetch(self.h, leaf, Z.ctypes.data_as(_dp)))
+        return Z
 
     # ---- predict(model, x) aggregation + scores on the device (src/common.jl:134-302, src/scorefunctions.jl) ----
     def _agg_args(self, family, leaf_coef, leaf_group):

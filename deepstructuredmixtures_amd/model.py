@@ -1241,6 +1241,97 @@ def predict_gradients(model, xtest):
     return mu, var, dmu, dvar
 
 
+def _targets_matrix(model, Y):
+    """`Y` as an (N, Q) float64 matrix over the model's training rows; a vector counts as one column."""
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim == 1:
+        Y = Y[:, None]
+    if Y.ndim != 2 or Y.shape[0] != model.x.shape[0] or Y.shape[1] < 1:
+        raise ValueError(f"targets of shape {Y.shape}: expected ({model.x.shape[0]}, Q) with Q >= 1")
+    return Y
+
+
+def targets_leaf_means(model, Y):
+    """`mean[L, Q]`: for every leaf the mean of each column of `Y` over the leaf's own observations, `mean(Y[obs], axis=0)` --
+    the ConstMean of a leaf built without a mean function (`src/treeStructure.jl:253`), column by column."""
+    target = model.model if isinstance(model, GaussianProcess) else model
+    Y = _targets_matrix(target, Y)
+    return np.stack([np.mean(Y[lf.obs], axis=0) for lf in target.leaves])
+
+
+def _targets_model(model, what):
+    target = model.model if isinstance(model, GaussianProcess) else model
+    if target.shard.world > 1:
+        raise NotImplementedError(f"{what}: the model is sharded over several ranks; every rank solves its own leaves "
+                                  "(Context.solve_targets), the exchange is out of scope")
+    if not hasattr(_ctx_type(target), "solve_targets"):
+        raise NotImplementedError(f"{what}: {_ctx_type(target).__name__} has no solve_targets")
+    return target
+
+
+def fit_targets(model, Y, mean=None):
+    """Several target columns over the model's inputs on its CURRENT fit (no reference counterpart): `Y` is `(N, Q)`, one
+    column per output -- joint torques, sensor channels, bootstrap or permuted targets.  Every leaf GP keeps its
+    factorisation; the device solves `Z = L^-1 (Y[obs] - mean)` per leaf (`Context.solve_targets`: 2 n^2 flops per leaf and
+    column instead of a refit's n^3 / 3).  Returns the `(L, Q)` table of log marginal likelihoods, `mll[l, j]` = that of leaf
+    `l` with column `j` as its targets -- what a caller needs to re-weigh the sum nodes per column.
+    Runs `fit(model)` first if the model has no fit.  `mean` is `(L, Q)`; `None` gives every leaf the mean of each column over
+    its own observations (`targets_leaf_means`), the ConstMean of a leaf built without a mean function.  A `GaussianProcess`
+    works too.  The model's own `y`, its fit and its weights are left as they are."""
+    target = _targets_model(model, "fit_targets")
+    Y = _targets_matrix(target, Y)
+    mean = targets_leaf_means(target, Y) if mean is None else np.asarray(mean, dtype=np.float64).reshape(target.L, Y.shape[1])
+    if not target._uploaded or np.all(np.isnan(target.leaf_mll)):
+        fit(target)
+    try:
+        mll, sec = target.ctx.solve_targets(Y, mean)
+    except hipabi.DsmgpError as e:
+        if e.code != hipabi.E_STATE:
+            raise
+        fit(target)             # the hyper-parameters moved since the last fit
+        mll, sec = target.ctx.solve_targets(Y, mean)
+    target.last_targets_seconds = sec
+    return np.ascontiguousarray(mll)
+
+
+def _aggregate_host(model, xt, rc, mu, var):
+    """`predict`'s aggregation of one set of per-(leaf, row) moments on the host, by the model's own rule."""
+    if model.family == "dsmgp":
+        if model.root.kind != "gp" and not model.tindex.weights_normalised():
+            return _aggregate_dsmgp(model, xt, rc["ptr"], mu, var)      # the literal recursion with its mu_min - 1 shift
+        return _aggregate_dsmgp_flat(model, xt.shape[0], rc, mu, var)
+    return _aggregate_poe(model, xt, rc["ptr"], mu, var)
+
+
+def predict_targets(model, xtest):
+    """`(mu, var)`, both `(n_t, Q)`: `predict(model, xtest)` for every target column of the last `fit_targets` (no reference
+    counterpart).  The per-(leaf, row) means of all columns come from the device (`Context.predict_targets`, on the `K_tn L^-T`
+    of `predict`'s own sweep); the leaf variances do not depend on the targets.  The aggregation runs on the host, column by
+    column, with the model's own rule (DSMGP mixture, PoE, gPoE, rBCM, single GP) and the clamps and the `mu_min - 1` shift
+    rule of `predict`.  The sum-node weights are the ones the model holds -- those of its own `y`: this function does NOT
+    re-weigh per column (the `mll` table of `fit_targets` is there for callers who want to).  The mixture variance depends on
+    the column through `sum W mu^2 - mu^2`; the product-of-experts variances are the same in every column."""
+    target = _targets_model(model, "predict_targets")
+    xt = _test_matrix(target, xtest)
+    Q = int(getattr(target.ctx, "targets_Q", 0))
+    if Q < 1:
+        raise hipabi.DsmgpError(hipabi.E_STATE, "predict_targets before fit_targets")
+    n_t = xt.shape[0]
+    if n_t == 0:
+        return np.zeros((0, Q)), np.zeros((0, Q))
+    rc = _routing(target, xt)
+    _, var_l = _leaf_moments(target, xt, rc)
+    mu_l = target.ctx.predict_targets()
+    mu = np.empty((n_t, Q))
+    var = np.empty((n_t, Q))
+    for j in range(Q):
+        if isinstance(model, GaussianProcess):
+            mu[:, j], var[:, j] = mu_l[:, j], np.where(var_l <= 0, EPS, var_l)
+        else:
+            mu[:, j], var[:, j] = _aggregate_host(target, xt, rc, np.ascontiguousarray(mu_l[:, j]), var_l)
+    return mu, var
+
+
 def _ctx_type(model):
     """Type of the model's device context without creating it (a rank that owns no leaves never does)."""
     if model._ctx is not None:

@@ -191,6 +191,44 @@ int dsmgp_predict_cov(dsmgp_ctx* ctx, int32_t leaf, int32_t with_noise, double* 
 int dsmgp_predict_gradients(dsmgp_ctx* ctx, double* dmu_out, double* dvar_out /* route_total x D, column-major, ld */,
                             int64_t ld, double* seconds);
 
+/* Several target columns over the same inputs on ONE factorisation (not a call of the reference): the seven joint torques of a
+ * robot arm, sensor channels, bootstrap or permuted targets.  After dsmgp_fit the factor, the inverted diagonal blocks and (after
+ * dsmgp_predict_run) K_tn L^-T do not depend on y; only z = L^-1 (y - m) does.  With K_y = L L^T the matrix the fit factorised:
+ *   dsmgp_solve_targets    Z[l] = L^-1 (Y[obs(l), :] - mean[l, :]) for every leaf, resident in HBM, and
+ *                          mll_out[l + j L] = -(|Z[l][:, j]|^2 + 2 sum_i log L_ii + n log 2pi) / 2   (dsmgp_fit's formula per column),
+ *   dsmgp_predict_targets  mu_out[e + j ld] = mean[l, j] + sum_{c < n} (K_tn L^-T)[e, c] Z[l][c, j] for every (leaf, routed test row)
+ *                          entry e of dsmgp_predict_fetch, in its order,
+ *   dsmgp_targets_fetch    Z[l] of one leaf (n x Q, column-major, ld = n): inspection, like dsmgp_download_factor.
+ * The predictive variance does not depend on the targets: it is dsmgp_predict_fetch's var_out for every column.
+ * Cost: 2 n^2 flops per leaf and column instead of a refit's n^3 / 3: a right-looking block sweep on the f64 matrix cores, one
+ * launch per 128-column block step and leaf lane, every factor tile read once per call whatever Q is; the means are one tile
+ * product per 128 routed rows.  Sums are added in a fixed order, no atomics: the same bits from call to call, with one lane
+ * and with two, and column j's results are the same bits whatever Q is and whatever the other columns hold.
+ * A COPY leaf reads its source's factor and has targets and a mean of its own; a PREFIX leaf has its own factor.  Leaves whose
+ * fit reported info != 0 get NaN in their mll row and their mu entries; the others are unaffected.
+ * dsmgp_solve_targets: Y is N x Q column-major with leading dimension ldy; mean is L x Q column-major (ld = L), NULL = zeros;
+ *   mll_out (L x Q, ld = L) and seconds (device time of the call) may be NULL.  Needs a fit on the current leaf table
+ *   (DSMGP_E_STATE otherwise).  DSMGP_E_ARG: N is not the N of dsmgp_set_train, Q < 1 (or > 65535), ldy < N, Y NULL, a non-finite
+ *   value in Y or mean.  The data of dsmgp_set_train, z and alpha are not touched: dsmgp_fit's outputs, dsmgp_predict_fetch,
+ *   dsmgp_predict_cov, dsmgp_gradients, dsmgp_loo* and dsmgp_predict_gradients return the same bits before and after.
+ * dsmgp_predict_targets: mu_out is route_total x Q (the Q of the last dsmgp_solve_targets), column-major, ld >= route_total
+ *   (DSMGP_E_ARG otherwise).  Needs BOTH dsmgp_solve_targets and dsmgp_predict_run on the CURRENT fit, on either route to
+ *   K_tn L^-T (rows that rode through the fit, or the standalone sweep); missing either: DSMGP_E_STATE.  A later dsmgp_fit makes
+ *   the resident Z stale: dsmgp_predict_targets and dsmgp_targets_fetch return DSMGP_E_STATE until dsmgp_solve_targets is called
+ *   again.  No routed rows at all: success, nothing written.  The K_tn arena is never cleared; its columns >= n are masked on load.
+ * Memory: Yc and Z take 2 npad Qpad doubles per leaf (Qpad = Q rounded up to 16, the width of the f64 MFMA tile), plus Y, mean,
+ *   mll, mu and the task lists: allocated on first use (the arena from the reserved pool when there is one; DSMGP_E_NOMEM with a
+ *   usable context when it does not fit), re-used while Q does not grow, NOT counted by dsmgp_estimate_bytes / dsmgp_memory,
+ *   dropped with the leaf table, new training data and dsmgp_release (under a reserved pool also with a new test set: the pool
+ *   is a stack).
+ * Out of scope: gradients of sum_j mll_j, LOO and input gradients for the extra columns, the multi-GPU exchange (each rank solves
+ *   its own leaves, the mll table is per rank), and the streaming context. */
+int dsmgp_solve_targets(dsmgp_ctx* ctx, const double* Y /* N x Q column-major */, int64_t N, int32_t Q, int64_t ldy,
+                        const double* mean /* L x Q column-major, ld = L; NULL = zeros */,
+                        double* mll_out /* L x Q column-major, ld = L; may be NULL */, double* seconds /* may be NULL */);
+int dsmgp_predict_targets(dsmgp_ctx* ctx, double* mu_out /* route_total x Q column-major */, int64_t ld, double* seconds);
+int dsmgp_targets_fetch(dsmgp_ctx* ctx, int32_t leaf, double* Z_out /* n x Q column-major, ld = n */);
+
 /* ---- predict(model, x): sum/product aggregation of the leaf moments over the leaves every test row visits, on the
  *      moments the last dsmgp_predict_run left in HBM (replaces the host recursions of src/common.jl:134-149,198-302).
  *      family  DSMGP_AGG_MIXTURE  DSMGP (_predict / _minpredict, :134-143,151-196,275-302): leaf_coef[l] = W_l, the product of the

@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, predict_cov, predict_gradients, loo, loo_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
+export attach!, detach!, census, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, targets_fetch, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -204,6 +204,7 @@ mutable struct Session
     testptr::Vector{Int64}
     census::Dict{Symbol,Any}
     fitted::Bool
+    targets::Int                           # columns of the last solve_targets (0: none)
 end
 
 const SESSIONS = IdDict{Any,Session}()     # root node (or GaussianProcess) -> session
@@ -217,7 +218,7 @@ function newsession(device::Integer)
     rc = ccall(sym(:dsmgp_create), Cint, (Int32, Ref{Ptr{Cvoid}}), Int32(device), r)
     rc == 0 || error("dsmgp_create: " * lasterror(C_NULL))        # no GPU: the path has no CPU fallback
     s = Session(r[], GPNode[], GaussianProcess[], IdDict{Any,Int}(), Float64[], Int32[], zeros(0, 0), 0, UInt(0), Int64[],
-                Dict{Symbol,Any}(), false)
+                Dict{Symbol,Any}(), false, 0)
     finalizer(x -> (x.h != C_NULL && ccall(sym(:dsmgp_destroy), Cint, (Ptr{Cvoid},), x.h); x.h = C_NULL), s)
     return s
 end
@@ -534,6 +535,49 @@ function loo_gradients(s::Session)
     GC.@preserve g lpd chk(s, ccall(sym(:dsmgp_loo_gradients), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ref{Float64}),
                                     s.h, g, Int32(s.stride), lpd, sec))
     return g, lpd
+end
+
+"solve_targets(s, Y; mean=nothing): several target columns over the same inputs on the current fit (dsmgp_solve_targets).  `Y` is
+`N × Q` over the rows of the training data, `mean` `L × Q` with the constant mean of every leaf (the order of `s.leaves`) and
+column (`nothing`: zeros).  Leaves Z = L⁻¹ (Y[obs, :] − mean) of every leaf resident on the device and returns the `L × Q` table of
+log marginal likelihoods.  Nothing the fit left is touched; leaves whose fit reported info ≠ 0 have NaN rows."
+function solve_targets(s::Session, Y::AbstractMatrix; mean::Union{Nothing,AbstractMatrix}=nothing)
+    Yc = Matrix{Float64}(Y)
+    N, Q = size(Yc)
+    L = length(s.leaves)
+    M = mean === nothing ? nothing : Matrix{Float64}(mean)
+    M === nothing || size(M) == (L, Q) || throw(DimensionMismatch("mean must be L × Q"))
+    out = Matrix{Float64}(undef, L, Q)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve Yc M out chk(s, ccall(sym(:dsmgp_solve_targets), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+        s.h, Yc, Int64(N), Int32(Q), Int64(max(N, 1)), M === nothing ? Ptr{Float64}(C_NULL) : pointer(M), out, sec))
+    s.targets = Q
+    return out
+end
+
+"predict_targets(s): the predictive mean of every (leaf, routed test row) entry of the last prediction under every column of the
+last solve_targets (dsmgp_predict_targets; needs both on the current fit): `route_total × Q`, in the entry order of the per-leaf
+moments.  The predictive variance does not depend on the targets: it is the one of the prediction for every column."
+function predict_targets(s::Session)
+    ptr = Vector{Int64}(undef, length(s.leaves) + 1)
+    GC.@preserve ptr chk(s, ccall(sym(:dsmgp_routes), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), s.h, ptr, C_NULL))
+    nr = Int(ptr[end])
+    Q = s.targets
+    μ = Matrix{Float64}(undef, nr, Q)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve μ chk(s, ccall(sym(:dsmgp_predict_targets), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}),
+                            s.h, μ, Int64(max(nr, 1)), sec))
+    return μ
+end
+
+"targets_fetch(s, leaf): Z = L⁻¹ (Y[obs, :] − mean) of leaf `leaf` (1-based, the order of `s.leaves`) as the last solve_targets left
+it, `n × Q` (dsmgp_targets_fetch; inspection)."
+function targets_fetch(s::Session, leaf::Integer)
+    n = length(s.leaves[leaf].obs)
+    Z = Matrix{Float64}(undef, n, s.targets)
+    GC.@preserve Z chk(s, ccall(sym(:dsmgp_targets_fetch), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.h, Int32(leaf - 1), Z))
+    return Z
 end
 
 # ---------------------------------------------------------------------------------------------- predict
