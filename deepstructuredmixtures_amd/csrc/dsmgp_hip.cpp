@@ -617,6 +617,16 @@ struct dsmgp_ctx {
     int tfwd_steps = 0, tfwd_lanes = 1;
     DevBuf<TargetsMuTask> tmu;      // test tiles, rebuilt per call
     DevBuf<double> d_tmu;           // mu, route_total x Q (ld = route_total)
+    // dsmgp_mll_columns_gradients: A = L^-T Z per leaf, npad x Qpad at offset toff / 2 of an arena of its own (allocated on first use, from
+    // the pool when there is one, not part of bytes_needed, dropped where arenaT is); its task lists are rebuilt per call
+    double* arenaA = nullptr;
+    size_t cap_A = 0;
+    DevBuf<TargetsATask> tga;
+    DevBuf<GradTaskTg> tgdot;
+    DevBuf<FrobTask> tgfrob;
+    DevBuf<ArdLinTask> tgquad;
+    DevBuf<TargetsArdLinTask> tgardlin;
+    DevBuf<double> d_tgw, d_tgpart; // the weights (L x Q); frob | contraction x gstride | 2 L | ArdLinear 2 D per column group | D per leaf
 
     // aggregation of the leaf moments per test row + scores (dsmgp_aggregate*, dsmgp_scores)
     DevBuf<int64_t> d_row_ptr;      // n_t + 1: entries of every test row (built by set_test)
@@ -958,6 +968,15 @@ void free_targets(dsmgp_ctx* c) {
     c->tfwd.release();
     c->tmu.release();
     c->d_tmu.release();
+    arena_put(c, c->arenaA);
+    c->cap_A = 0;
+    c->tga.release();
+    c->tgdot.release();
+    c->tgfrob.release();
+    c->tgquad.release();
+    c->tgardlin.release();
+    c->d_tgw.release();
+    c->d_tgpart.release();
 }
 
 void free_tree(dsmgp_ctx* c) {
@@ -3675,6 +3694,64 @@ int build_grad_plan(dsmgp_ctx* c) {
 
 }  // namespace
 
+namespace {
+// The per-kind assembly of one leaf's gradient row from the sums of the device passes: S1 / Sd / Sa the contractions of the
+// weight matrix with K P, dK / dlog l_d and dK / dlog alpha, Sl the ArdLinear forms, trK = s tr K_y^-1, ya = sum w (y - m) . alpha,
+// aa = sum w alpha . alpha, ns = n s -- s = 1 and one column for dsmgp_gradients, s = sum_q w_q for dsmgp_mll_columns_gradients.
+struct GradSums {
+    double S1;
+    const double* Sd;       // D sums, or null when no per-dimension sums were taken
+    double Sa;
+    const double* Sl;       // D sums
+    double trK, ya, aa, ns;
+};
+void assemble_gradient(const dsmgp_ctx* c, const HyperHost& h, const GradSums& q, double* g) {
+    const int nl = n_lengthscales(h.kind, h.loghyp.size());
+    const int ns = nl + KINDS[h.kind].n_shape;               // the slot of logs; logNoise behind it
+    const double noise = std::exp(2.0 * h.loghyp[ns + 1]);
+    const double cc = noise + 1e-8;
+    const double ya = q.ya, aa = q.aa;
+    const double n = q.ns;
+    // tr(precomp K) with K = K_y - c I:  (y.alpha - c alpha.alpha) - (n - c tr K_y^-1)
+    const double trPK = (ya - cc * aa) - (n - cc * q.trK);
+    if (h.kind == DSMGP_KIND_ISO_SE) {
+        const double sigma = std::exp(h.loghyp[1]);
+        const double ell2 = std::exp(2.0 * h.loghyp[0]);
+        g[0] = 0.5 * sigma * q.S1 / ell2;                 // src/kernels.jl:95-97
+        g[1] = sigma * trPK;                              // src/kernels.jl:90-93
+    } else if (h.kind == DSMGP_KIND_ARD_SE) {
+        const double sigma = std::exp(h.loghyp[nl]);
+        for (int d = 0; d < nl; ++d)                      // src/kernels.jl:161: identically zero unless the
+            g[d] = (c->ard_true_gradient && q.Sd) ? 0.5 * q.Sd[d] : 0.0;   // true gradient is asked for
+        g[nl] = sigma * trPK;                             // src/kernels.jl:157
+    } else if (h.kind == DSMGP_KIND_ISO_LINEAR) {
+        g[0] = -trPK;                                     // src/kernels.jl:198
+        g[1] = 0.0;                                       // src/kernels.jl:201
+    } else if (h.kind == DSMGP_KIND_ARD_LINEAR) {
+        // the true derivative -S_d / l_d^2 (src/kernels.jl:234-246 is the same trace with kappa = z / l_d and does not run;
+        // DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT is about ArdSE only); no variance gradient (the slot is a dummy, :216-218)
+        for (int d = 0; d < nl; ++d) g[d] = -q.Sl[d] / std::exp(2.0 * h.loghyp[d]);
+        g[nl] = 0.0;
+    } else if (h.kind == DSMGP_KIND_ARD_SE_PRODUCT) {
+        // the true derivatives: 0.5 tr(W dK / dlog l_d) from the per-dimension sums, 0.5 tr(W 2K) = tr(W K) (no SURVEY F7 factor)
+        for (int d = 0; d < nl; ++d) g[d] = 0.5 * q.Sd[d];
+        g[nl] = trPK;
+    } else if (KINDS[h.kind].matern || KINDS[h.kind].rq) {
+        // the true derivatives as for ArdSEProduct; an iso kind's dl is the sum over the dimensions, added in ascending d
+        if (KINDS[h.kind].iso_matern) {
+            double sl = 0.0;
+            for (int d = 0; d < c->D; ++d) sl += q.Sd[d];
+            g[0] = 0.5 * sl;
+        } else {
+            for (int d = 0; d < nl; ++d) g[d] = 0.5 * q.Sd[d];
+        }
+        if (KINDS[h.kind].rq) g[nl] = 0.5 * q.Sa;         // da = 0.5 tr(W dK / dlog alpha)
+        g[ns] = trPK;
+    }
+    g[ns + 1] = noise * (aa - q.trK);                     // src/gaussianprocess.jl:176
+}
+}  // namespace
+
 int dsmgp_set_gradient_leaves(dsmgp_ctx* c, const int32_t* active) {
     if (!c) return DSMGP_E_ARG;
     if (c->L == 0) return fail(c, DSMGP_E_STATE, "set_gradient_leaves before set_leaves");
@@ -3731,15 +3808,15 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     const size_t nm0 = c->gdot_mat0;      // tasks [nm0, nr0): Matern leaves
     const size_t nr0 = c->gdot_rq0;       // tasks [nr0, count): rational quadratic leaves
     if (np0)
-        tile_graddot_kernel<false><<<(int)np0, 256, 0, c->stream>>>(c->gdot.p, c->d_kp.p, c->D, pdot, c->gstride);
+        tile_graddot_kernel<GD_MLL><<<(int)np0, 256, 0, c->stream>>>(c->gdot.p, c->d_kp.p, c->D, pdot, c->gstride);
     if (nm0 > np0)
-        tile_graddot_prod_kernel<false><<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->gdot.p + np0, c->d_kp.p, c->D,
+        tile_graddot_prod_kernel<GD_MLL><<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->gdot.p + np0, c->d_kp.p, c->D,
                                                                                pdot + (size_t)c->gstride * np0, c->gstride);
     if (nr0 > nm0)
-        tile_graddot_matern_kernel<false><<<(int)(nr0 - nm0), 256, 0, c->stream>>>(c->gdot.p + nm0, c->d_kp.p, c->D,
+        tile_graddot_matern_kernel<GD_MLL><<<(int)(nr0 - nm0), 256, 0, c->stream>>>(c->gdot.p + nm0, c->d_kp.p, c->D,
                                                                                  pdot + (size_t)c->gstride * nm0, c->gstride);
     if (c->gdot.count > nr0)
-        tile_graddot_rq_kernel<false><<<(int)(c->gdot.count - nr0), 256, 0, c->stream>>>(c->gdot.p + nr0, c->d_kp.p, c->D,
+        tile_graddot_rq_kernel<GD_MLL><<<(int)(c->gdot.count - nr0), 256, 0, c->stream>>>(c->gdot.p + nr0, c->d_kp.p, c->D,
                                                                                        pdot + (size_t)c->gstride * nr0, c->gstride);
     HIPCHK(c, hipEventRecord(e_dot.a, c->stream));
     if (c->gfrob.count) frob_kernel<<<(int)c->gfrob.count, 256, 0, c->stream>>>(c->gfrob.p, pfrob);
@@ -3811,53 +3888,19 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     }
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
-        const HyperHost& h = c->hyper[lf.kid];
-        const int nl = n_lengthscales(h.kind, h.loghyp.size());
-        const int ns = nl + KINDS[h.kind].n_shape;               // the slot of logs; logNoise behind it
-        const double noise = std::exp(2.0 * h.loghyp[ns + 1]);
-        const double cc = noise + 1e-8;
-        const double ya = pl[2 * l], aa = pl[2 * l + 1];
-        const double n = (double)lf.n;
-        // tr(precomp K) with K = K_y - c I:  (y.alpha - c alpha.alpha) - (n - c tr K_y^-1)
-        const double trPK = (ya - cc * aa) - (n - cc * trK[l]);
         double* g = grad_out + (size_t)l * stride;
         for (int j = 0; j < stride; ++j) g[j] = 0.0;
         if (!c->grad_active.empty() && !c->grad_active[l]) continue;      // not asked for (dsmgp_set_gradient_leaves): zeros
-        if (h.kind == DSMGP_KIND_ISO_SE) {
-            const double sigma = std::exp(h.loghyp[1]);
-            const double ell2 = std::exp(2.0 * h.loghyp[0]);
-            g[0] = 0.5 * sigma * S1[l] / ell2;                // src/kernels.jl:95-97
-            g[1] = sigma * trPK;                              // src/kernels.jl:90-93
-        } else if (h.kind == DSMGP_KIND_ARD_SE) {
-            const double sigma = std::exp(h.loghyp[nl]);
-            for (int d = 0; d < nl; ++d)                      // src/kernels.jl:161: identically zero unless the
-                g[d] = (c->ard_true_gradient && gs > 2) ? 0.5 * Sd[(size_t)l * c->D + d] : 0.0;   // true gradient is asked for
-            g[nl] = sigma * trPK;                             // src/kernels.jl:157
-        } else if (h.kind == DSMGP_KIND_ISO_LINEAR) {
-            g[0] = -trPK;                                     // src/kernels.jl:198
-            g[1] = 0.0;                                       // src/kernels.jl:201
-        } else if (h.kind == DSMGP_KIND_ARD_LINEAR) {
-            // the true derivative -S_d / l_d^2 (src/kernels.jl:234-246 is the same trace with kappa = z / l_d and does not run;
-            // DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT is about ArdSE only); no variance gradient (the slot is a dummy, :216-218)
-            for (int d = 0; d < nl; ++d) g[d] = -Sl[(size_t)l * c->D + d] / std::exp(2.0 * h.loghyp[d]);
-            g[nl] = 0.0;
-        } else if (h.kind == DSMGP_KIND_ARD_SE_PRODUCT) {
-            // the true derivatives: 0.5 tr(W dK / dlog l_d) from the per-dimension sums, 0.5 tr(W 2K) = tr(W K) (no SURVEY F7 factor)
-            for (int d = 0; d < nl; ++d) g[d] = 0.5 * Sd[(size_t)l * c->D + d];
-            g[nl] = trPK;
-        } else if (KINDS[h.kind].matern || KINDS[h.kind].rq) {
-            // the true derivatives as for ArdSEProduct; an iso kind's dl is the sum over the dimensions, added in ascending d
-            if (KINDS[h.kind].iso_matern) {
-                double sl = 0.0;
-                for (int d = 0; d < c->D; ++d) sl += Sd[(size_t)l * c->D + d];
-                g[0] = 0.5 * sl;
-            } else {
-                for (int d = 0; d < nl; ++d) g[d] = 0.5 * Sd[(size_t)l * c->D + d];
-            }
-            if (KINDS[h.kind].rq) g[nl] = 0.5 * Sa[l];        // da = 0.5 tr(W dK / dlog alpha)
-            g[ns] = trPK;
-        }
-        g[ns + 1] = noise * (aa - trK[l]);                    // src/gaussianprocess.jl:176
+        GradSums q{};
+        q.S1 = S1[l];
+        q.Sd = gs > 2 ? Sd.data() + (size_t)l * c->D : nullptr;
+        q.Sa = Sa[l];
+        q.Sl = Sl.data() + (size_t)l * c->D;
+        q.trK = trK[l];
+        q.ya = pl[2 * l];
+        q.aa = pl[2 * l + 1];
+        q.ns = (double)lf.n;
+        assemble_gradient(c, c->hyper[lf.kid], q, g);
     }
     return 0;
 }
@@ -4297,6 +4340,273 @@ int dsmgp_targets_fetch(dsmgp_ctx* c, int32_t leaf, double* Z_out) {
     return 0;
 }
 
+// Hyper-parameter gradients of sum_q w_lq mll_lq over the resident target columns (kernels_targets.hpp at targets_a_kernel):
+// one inversion -- or none, when the arena holds L^-T of this fit (dsmgp_loo's rule) -- and one contraction per leaf whatever Q is,
+// plus O(n^2 Q) for A = L^-T Z and the rank-Q term.  Every leaf has tasks of its own (a COPY leaf reads its source's L^-T with its
+// own A); the lists are rebuilt per call and live in buffers of this entry point, as do A, the weights and the partial sums:
+// nothing another entry point reads is written, and the mask of dsmgp_set_gradient_leaves neither applies nor changes.
+int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, const double* col_weight, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "targets_gradients before solve_targets on the current fit");
+    if (!grad_out) return fail(c, DSMGP_E_ARG, "targets_gradients: grad_out is NULL");
+    const int L = c->L, Q = c->tg_Q, qpad = c->tg_qpad, D = c->D;
+    bool any_ard = false, any_prod = false;
+    for (int l = 0; l < L; ++l) {
+        const HyperHost& h = c->hyper[c->leaves[l].kid];
+        if ((int)h.loghyp.size() > stride) return fail(c, DSMGP_E_ARG, "targets_gradients: stride smaller than the hyper-vector");
+        any_ard = any_ard || (h.kind == DSMGP_KIND_ARD_SE && c->ard_true_gradient);
+        any_prod = any_prod || h.kind == DSMGP_KIND_ARD_SE_PRODUCT || KINDS[h.kind].matern || KINDS[h.kind].rq;
+    }
+    if (any_ard && D > GRADDOT_STAGE_D)
+        return fail(c, DSMGP_E_ARG, "ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
+    std::vector<double> W((size_t)L * Q, 1.0), sw((size_t)L, 0.0);
+    if (col_weight)
+        for (size_t i = 0; i < W.size(); ++i) {
+            if (!std::isfinite(col_weight[i])) return fail(c, DSMGP_E_ARG, "targets_gradients: non-finite value in col_weight");
+            W[i] = col_weight[i];
+        }
+    for (int l = 0; l < L; ++l)
+        for (int q = 0; q < Q; ++q) sw[(size_t)l] += W[(size_t)l + (size_t)q * L];
+    HIPCHK(c, hipSetDevice(c->device));
+    // L^-T of every factor owner (xinv_lists / xinv_fill); lists of the call's own are dropped again on every way out
+    OwnGradLists own_lists{c};
+    if (int rc = xinv_lists(c, own_lists)) return rc;
+    size_t atot = 0;
+    for (int l = 0; l < L; ++l) atot += (size_t)c->leaves[l].npad * (size_t)qpad;
+    if (int rc = slab_grow(c, c->arenaA, c->cap_A, atot)) {
+        (void)hipGetLastError();
+        return rc == DSMGP_E_NOMEM ? rc : fail(c, DSMGP_E_NOMEM, "targets_gradients: no room for A = L^-T Z (" + std::to_string((atot * 8) >> 20) + " MiB)");
+    }
+    const int gs = any_rq(c) ? 3 + D : (any_ard || any_prod) ? 2 + D : 2;
+    auto Xt = [&](int l) { return c->arenaX + c->gxoff[(size_t)c->leaves[l].owner]; };
+    auto Al = [&](int l) { return c->arenaA + c->toff[(size_t)l] / 2; };
+    std::vector<TargetsATask> ta;
+    std::vector<FrobTask> frob;
+    std::vector<int> frob_leaf;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        const int ldt = c->leaves[lf.owner].npad;
+        for (int i = 0; i < lf.nb; ++i) {
+            TargetsATask t{};
+            t.Xt = Xt(l) + (size_t)i * TB;
+            t.Z = c->arenaT + c->toff[(size_t)l] + (size_t)lf.npad * qpad;
+            t.A = Al(l) + (size_t)i * TB;
+            t.ldt = ldt;
+            t.ldz = lf.npad;
+            t.k0 = i * TB;
+            t.n = lf.n;
+            t.nrows = std::max(0, std::min(TB, lf.n - i * TB));
+            ta.push_back(t);
+            if (lf.owner != l) continue;
+            FrobTask f{};
+            f.X = Xt(l) + (size_t)i * TB;
+            f.ld = lf.npad;
+            f.col0 = i * TB;
+            f.col1 = lf.npad;
+            f.nrows = t.nrows;
+            f.n = lf.n;
+            frob.push_back(f);
+            frob_leaf.push_back(l);
+        }
+    }
+    // contraction tiles in the order of build_grad_plan: IsoSE / ArdSE | ArdSEProduct | Matern | rational quadratic, super-tiles of
+    // GS x GS tiles per leaf, dealt to the XCDs by work
+    constexpr int GS = 4;
+    std::vector<GradTaskTg> gd;
+    std::vector<int> gd_leaf;
+    std::vector<size_t> gblock;
+    size_t first[5] = {0, 0, 0, 0, 0};
+    for (int pass = 0; pass < 4; ++pass) {
+        first[pass] = gd.size();
+        const size_t begin = gd.size();
+        gblock.clear();
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            const int kind_l = c->hyper[lf.kid].kind;
+            const bool ard = kind_l == DSMGP_KIND_ARD_SE && c->ard_true_gradient;
+            if (!KINDS[kind_l].contraction && !ard) continue;
+            if ((kind_l == DSMGP_KIND_ARD_SE_PRODUCT ? 1 : KINDS[kind_l].matern ? 2 : KINDS[kind_l].rq ? 3 : 0) != pass) continue;
+            const LeafDev& d = c->h_leaves[l];
+            const int ldt = c->leaves[lf.owner].npad;
+            for (int ib = 0; ib < lf.nb; ib += GS) {
+                gblock.push_back(gd.size() - begin);
+                for (int jb = 0; jb <= ib; jb += GS)
+                    for (int i = ib; i < std::min(ib + GS, lf.nb); ++i)
+                        for (int j = jb; j < std::min(jb + GS, i + 1); ++j) {
+                            GradTaskTg g{};
+                            g.gemm.A = Xt(l) + (size_t)i * TB;
+                            g.gemm.B = Xt(l) + (size_t)j * TB;
+                            g.gemm.C = nullptr;
+                            g.gemm.lda = g.gemm.ldb = ldt;
+                            g.gemm.ldc = TB;
+                            g.gemm.k0 = i * TB;
+                            g.gemm.k1 = lf.npad;
+                            g.gemm.update = 0;
+                            g.xa = d.Xg + (size_t)i * TB;
+                            g.xb = d.Xg + (size_t)j * TB;
+                            g.alpha_a = d.alpha + (size_t)i * TB;
+                            g.alpha_b = d.alpha + (size_t)j * TB;
+                            g.ldx = lf.npad;
+                            g.na = std::max(0, std::min(TB, lf.n - i * TB));
+                            g.nb = std::max(0, std::min(TB, lf.n - j * TB));
+                            g.diag = (i == j);
+                            g.kid = lf.kid;
+                            g.Aa = Al(l) + (size_t)i * TB;
+                            g.Ab = Al(l) + (size_t)j * TB;
+                            g.wq = c->d_tgw.p;      // + l once the buffer is there (below)
+                            g.sw = sw[(size_t)l];
+                            g.lda_t = lf.npad;
+                            g.ldw = L;
+                            g.Q = Q;
+                            g.qpad = qpad;
+                            gd.push_back(g);
+                            gd_leaf.push_back(l);
+                        }
+            }
+        }
+        gblock.push_back(gd.size() - begin);
+        std::vector<double> work(gd.size() - begin);
+        for (size_t i = 0; i < work.size(); ++i) work[i] = (double)(gd[begin + i].gemm.k1 - gd[begin + i].gemm.k0) + 64.0 + qpad;
+        xcd_deal_by_work(gd, gd_leaf, begin, gd.size(), gblock, work, c->xcd_order);
+    }
+    first[4] = gd.size();
+    // ArdLinear leaves: |L^-1 x_d|^2 by ardlin_quad_kernel (its alpha sums are not used: any vector of the leaf serves), and the
+    // weighted squares of a_q . x_d
+    std::vector<ArdLinTask> quad;
+    std::vector<int> quad_leaf;
+    std::vector<TargetsArdLinTask> al;
+    std::vector<int> al_leaf;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR) continue;
+        const LeafDev& d = c->h_leaves[l];
+        for (int c0 = 0; c0 < lf.n; c0 += ARDLIN_COLS) {
+            ArdLinTask a{};
+            a.Xt = Xt(l);
+            a.x = d.Xg;
+            a.alpha = d.Xg;
+            a.ldt = c->leaves[lf.owner].npad;
+            a.ldx = lf.npad;
+            a.c0 = c0;
+            a.n = lf.n;
+            quad.push_back(a);
+            quad_leaf.push_back(l);
+        }
+        TargetsArdLinTask t{};
+        t.A = Al(l);
+        t.x = d.Xg;
+        t.wq = nullptr;
+        t.ld = lf.npad;
+        t.ldw = L;
+        t.n = lf.n;
+        t.Q = Q;
+        al.push_back(t);
+        al_leaf.push_back(l);
+    }
+    if (int rc = c->d_tgw.grow(c, W.size())) return rc;
+    for (size_t i = 0; i < gd.size(); ++i) gd[i].wq = c->d_tgw.p + gd_leaf[i];
+    for (size_t i = 0; i < al.size(); ++i) al[i].wq = c->d_tgw.p + al_leaf[i];
+    HIPCHK(c, hipMemcpy(c->d_tgw.p, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = dev_upload(c, c->tga, ta)) return rc;
+    if (int rc = dev_upload(c, c->tgfrob, frob)) return rc;
+    if (int rc = dev_upload(c, c->tgdot, gd)) return rc;
+    if (int rc = dev_upload(c, c->tgquad, quad)) return rc;
+    if (int rc = dev_upload(c, c->tgardlin, al)) return rc;
+    const size_t npart = frob.size() + (size_t)gs * gd.size() + 2 * (size_t)L + 2 * (size_t)D * quad.size() + (size_t)D * al.size();
+    if (int rc = c->d_tgpart.grow(c, std::max<size_t>(1, npart))) return rc;
+    double* pfrob = c->d_tgpart.p;
+    double* pdot = pfrob + frob.size();
+    double* pleaf = pdot + (size_t)gs * gd.size();
+    double* pquad = pleaf + 2 * (size_t)L;
+    double* pal = pquad + 2 * (size_t)D * quad.size();
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    if (int rc = ensure_dinv(c)) return rc;
+    if (int rc = xinv_fill(c)) return rc;
+    if (!ta.empty()) targets_a_kernel<<<(unsigned)ta.size(), 256, 0, c->stream>>>(c->tga.p, qpad);
+    if (first[1] > first[0])
+        tile_graddot_kernel<GD_TARGETS><<<(unsigned)(first[1] - first[0]), 256, 0, c->stream>>>(c->tgdot.p + first[0], c->d_kp.p, D,
+                                                                                              pdot + (size_t)gs * first[0], gs);
+    if (first[2] > first[1])
+        tile_graddot_prod_kernel<GD_TARGETS><<<(unsigned)(first[2] - first[1]), 256, 0, c->stream>>>(c->tgdot.p + first[1], c->d_kp.p, D,
+                                                                                                   pdot + (size_t)gs * first[1], gs);
+    if (first[3] > first[2])
+        tile_graddot_matern_kernel<GD_TARGETS><<<(unsigned)(first[3] - first[2]), 256, 0, c->stream>>>(c->tgdot.p + first[2], c->d_kp.p, D,
+                                                                                                     pdot + (size_t)gs * first[2], gs);
+    if (first[4] > first[3])
+        tile_graddot_rq_kernel<GD_TARGETS><<<(unsigned)(first[4] - first[3]), 256, 0, c->stream>>>(c->tgdot.p + first[3], c->d_kp.p, D,
+                                                                                                 pdot + (size_t)gs * first[3], gs);
+    if (!frob.empty()) frob_kernel<<<(unsigned)frob.size(), 256, 0, c->stream>>>(c->tgfrob.p, pfrob);
+    targets_wsums_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->arenaT, c->d_toff.p, c->arenaA, c->d_tgw.p, L, Q, qpad, pleaf);
+    if (!quad.empty())
+        ardlin_quad_kernel<false><<<dim3((unsigned)quad.size(), (unsigned)((D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
+            c->tgquad.p, D, pquad);
+    if (!al.empty()) targets_ardlin_kernel<<<dim3((unsigned)al.size(), (unsigned)D), 256, 0, c->stream>>>(c->tgardlin.p, D, pal);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->xinv_all = true;
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = ms * 1e-3;
+    std::vector<double> part(std::max<size_t>(1, npart));
+    HIPCHK(c, hipMemcpy(part.data(), c->d_tgpart.p, npart * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<int> info((size_t)L);
+    HIPCHK(c, hipMemcpy(info.data(), c->d_info.p, (size_t)L * sizeof(int), hipMemcpyDeviceToHost));
+    // host assembly, every sum in list order
+    std::vector<double> trG((size_t)L, 0.0), S1((size_t)L, 0.0), Sa((size_t)L, 0.0), Sd, Sl((size_t)L * D, 0.0);
+    for (size_t i = 0; i < frob.size(); ++i) trG[(size_t)frob_leaf[i]] += part[i];
+    for (int l = 0; l < L; ++l)
+        if (c->leaves[l].owner != l) trG[(size_t)l] = trG[(size_t)c->leaves[l].owner];
+    if (gs > 2) Sd.assign((size_t)L * D, 0.0);
+    const double* pd = part.data() + frob.size();
+    for (size_t i = 0; i < gd.size(); ++i) {
+        const size_t l = (size_t)gd_leaf[i];
+        const KindInfo& ki = KINDS[c->hyper[c->leaves[l].kid].kind];
+        if (ki.per_dim_grad) {
+            for (int d = 0; d < D; ++d) Sd[l * D + d] += pd[(size_t)gs * i + 2 + d];
+            if (ki.rq) Sa[l] += pd[(size_t)gs * i + 2 + D];
+        } else {
+            S1[l] += pd[(size_t)gs * i];
+        }
+    }
+    const double* pl = pd + (size_t)gs * gd.size();
+    const double* pq = pl + 2 * (size_t)L;
+    const double* pa = pq + 2 * (size_t)D * quad.size();
+    {
+        std::vector<double> Qf((size_t)L * D, 0.0);
+        for (size_t i = 0; i < quad.size(); ++i)
+            for (int d = 0; d < D; ++d) Qf[(size_t)quad_leaf[i] * D + d] += pq[2 * (size_t)D * i + D + d];
+        for (size_t i = 0; i < al.size(); ++i) {
+            const size_t l = (size_t)al_leaf[i];
+            for (int d = 0; d < D; ++d) Sl[l * D + d] = pa[i * D + d] - sw[l] * Qf[l * D + d];
+        }
+    }
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        double* g = grad_out + (size_t)l * stride;
+        for (int j = 0; j < stride; ++j) g[j] = 0.0;
+        if (info[(size_t)lf.owner] != 0) {
+            for (int j = 0; j < stride; ++j) g[j] = qnan;
+            continue;
+        }
+        GradSums q{};
+        q.S1 = S1[(size_t)l];
+        q.Sd = gs > 2 ? Sd.data() + (size_t)l * D : nullptr;
+        q.Sa = Sa[(size_t)l];
+        q.Sl = Sl.data() + (size_t)l * D;
+        q.trK = sw[(size_t)l] * trG[(size_t)l];
+        q.ya = pl[2 * l];
+        q.aa = pl[2 * l + 1];
+        q.ns = (double)lf.n * sw[(size_t)l];
+        assemble_gradient(c, c->hyper[lf.kid], q, g);
+    }
+    return 0;
+}
+
 // Hyper-parameter gradients of the LOO log predictive density (GPML eq. 5.13; the kernels and the formulas: kernels.hpp at
 // loo_weights_kernel).  dsmgp_loo itself runs first -- L^-T of every owner, the row sums, lpd -- so lpd_out is its lpd_out to
 // the bit and everything that call promises about dsmgp_gradients and the mask holds here too; then the passes of this call's
@@ -4501,13 +4811,13 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
     if (c->lginv.count) tile_ginv_kernel<<<(unsigned)c->lginv.count, 256, 0, c->stream>>>(c->lginv.p);
     if (c->lghvec.count) loo_hvec_kernel<<<(unsigned)c->lghvec.count, 256, 0, c->stream>>>(c->lghvec.p, ph);
     const size_t np0 = c->lgdot_prod0, nm0 = c->lgdot_mat0, nr0 = c->lgdot_rq0, nd = c->lgdot.count;
-    if (np0) tile_graddot_kernel<true><<<(int)np0, 256, 0, c->stream>>>(c->lgdot.p, c->d_kp.p, D, pdot, gs);
+    if (np0) tile_graddot_kernel<GD_LOO><<<(int)np0, 256, 0, c->stream>>>(c->lgdot.p, c->d_kp.p, D, pdot, gs);
     if (nm0 > np0)
-        tile_graddot_prod_kernel<true><<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->lgdot.p + np0, c->d_kp.p, D, pdot + (size_t)gs * np0, gs);
+        tile_graddot_prod_kernel<GD_LOO><<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->lgdot.p + np0, c->d_kp.p, D, pdot + (size_t)gs * np0, gs);
     if (nr0 > nm0)
-        tile_graddot_matern_kernel<true><<<(int)(nr0 - nm0), 256, 0, c->stream>>>(c->lgdot.p + nm0, c->d_kp.p, D, pdot + (size_t)gs * nm0, gs);
+        tile_graddot_matern_kernel<GD_LOO><<<(int)(nr0 - nm0), 256, 0, c->stream>>>(c->lgdot.p + nm0, c->d_kp.p, D, pdot + (size_t)gs * nm0, gs);
     if (nd > nr0)
-        tile_graddot_rq_kernel<true><<<(int)(nd - nr0), 256, 0, c->stream>>>(c->lgdot.p + nr0, c->d_kp.p, D, pdot + (size_t)gs * nr0, gs);
+        tile_graddot_rq_kernel<GD_LOO><<<(int)(nd - nr0), 256, 0, c->stream>>>(c->lgdot.p + nr0, c->d_kp.p, D, pdot + (size_t)gs * nr0, gs);
     if (c->lgardlin.count)
         ardlin_quad_kernel<true><<<dim3((unsigned)c->lgardlin.count, (unsigned)((D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
             c->lgardlin.p, D, pal);

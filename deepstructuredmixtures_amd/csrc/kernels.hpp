@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "route_walk.hpp"
 
 namespace dsmgp {
@@ -1236,15 +1237,92 @@ struct GradTask {
     int na, nb;             // valid rows / cols
     int diag;               // tile on the block diagonal
     int kid;
-    int uoff;               // LOO contraction (template argument LOO): u of the rows / columns = alpha_a / alpha_b + uoff; else unused
+    int uoff;               // LOO contraction (MODE == GD_LOO): u of the rows / columns = alpha_a / alpha_b + uoff; else unused
 };
+
+// The three objectives the contraction kernels serve (their template argument MODE).
+constexpr int GD_MLL = 0;       // log marginal likelihood of the context's y (dsmgp_gradients)
+constexpr int GD_LOO = 1;       // leave-one-out density (dsmgp_loo_gradients)
+constexpr int GD_TARGETS = 2;   // weighted sum of the log marginal likelihoods of the target columns (dsmgp_mll_columns_gradients)
+
+// A task of the targets mode: the contraction task of the leaf's tile plus the two row blocks of A = L^-T Z = K_y^-1 (Y - m)
+// and the leaf's row of column weights.  The alpha pointers of the base are staged but never enter a weight.
+struct GradTaskTg : GradTask {
+    const double* Aa;       // rows of tile i of A (128 x qpad, ld = lda_t)
+    const double* Ab;       // rows of tile j
+    const double* wq;       // weight of column q at wq[q * ldw]
+    double sw;              // s_l = sum_q w_lq
+    int lda_t, ldw, Q, qpad;
+};
+template <int MODE>
+using graddot_task_t = std::conditional_t<MODE == GD_TARGETS, GradTaskTg, GradTask>;
 
 // The weight an accumulator element G_rc is contracted with.  Marginal likelihood: alpha_r alpha_c - G_rc with G = K_y^-1.
 // Leave-one-out density (dsmgp_loo_gradients, GPML eq. 5.13): (u_r alpha_c + alpha_r u_c) / 2 - G_rc with G = H H^T.
-template <bool LOO>
+// Targets: the accumulators already hold s G - A_i diag(w) A_j^T (graddot_targets_acc), and the weight is their negative.
+template <int MODE>
 __device__ __forceinline__ double graddot_weight(double ar, double ac, double ur, double uc, double acc) {
-    if constexpr (LOO) return 0.5 * fma(ur, ac, ar * uc) - acc;
+    if constexpr (MODE == GD_LOO) return 0.5 * fma(ur, ac, ar * uc) - acc;
+    else if constexpr (MODE == GD_TARGETS) return -acc;
     else return ar * ac - acc;
+}
+
+// Targets mode, right after gemm_mainloop_v2 (the ring is free): tr = trace of G on a diagonal tile, taken from the
+// accumulators first; then acc <- s acc - A_i diag(w) A_j^T by Qpad / 4 MFMA k-steps.  The two 128 x 16 chunks of A go through
+// the first two slots of the ring's halves (k-major, ld = LDP: the operand layout of the main loop), -w_q folded into the
+// column operand while staging, chunks in ascending q: an element's sum runs over q in a fixed order.  Rows past the tile's
+// valid rows / columns and columns q >= Q are staged as zeros.  Ends on a barrier: the ring is free again.
+__device__ __forceinline__ void graddot_targets_acc(const GradTaskTg& g, d4 (&acc)[4][4], double* smem, double& tr) {
+    const int t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+#pragma unroll
+    for (int rn = 0; rn < 4; ++rn) {
+        const int r = wr * 64 + 16 * rn + l15;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
+            if (g.diag && r == c && r < g.na) tr += acc[i >> 2][rn][i & 3];
+        }
+    }
+#pragma unroll
+    for (int cm = 0; cm < 4; ++cm)
+#pragma unroll
+        for (int rn = 0; rn < 4; ++rn)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[cm][rn][q] *= g.sw;
+    double* sa = smem;                          // rows:    sa[q * LDP + r]
+    double* sb = smem + NRING * KC2 * LDP;      // columns: sb[q * LDP + c], times -w_q
+    static_assert(16 <= 2 * KC2, "a chunk of 16 columns of A fits two slots of the ring");
+    for (int q0 = 0; q0 < g.qpad; q0 += 16) {
+        if (q0) __syncthreads();                // the chunk before has been read
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int e = t + 256 * m, q = e >> 7, r = e & 127;
+            const bool qv = q0 + q < g.Q;
+            const double wv = qv ? -g.wq[(size_t)(q0 + q) * g.ldw] : 0.0;
+            sa[q * LDP + r] = (qv && r < g.na) ? g.Aa[r + (size_t)(q0 + q) * g.lda_t] : 0.0;
+            sb[q * LDP + r] = (qv && r < g.nb) ? wv * g.Ab[r + (size_t)(q0 + q) * g.lda_t] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int G = 0; G < 4; ++G) {
+            double fa[4], fb[4];
+            const double* pa = sb + (G * 4 + l4) * LDP + wc * 64 + l15;
+            const double* pb = sa + (G * 4 + l4) * LDP + wr * 64 + l15;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                fa[i] = pa[16 * i];
+                fb[i] = pb[16 * i];
+            }
+#pragma unroll
+            for (int cm = 0; cm < 4; ++cm)
+#pragma unroll
+                for (int rn = 0; rn < 4; ++rn)
+                    acc[cm][rn] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[cm], fb[rn], acc[cm][rn], 0, 0, 0);
+        }
+    }
+    __syncthreads();
 }
 
 // The epilogue is a Gram tile of its own (squared distance + exp per element): the coordinates of the tile's 128 rows
@@ -1255,17 +1333,17 @@ constexpr int GRADDOT_STAGE_D = 35;
 // asked for (dsmgp_set_option DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT): out[2 + d] = sum_rc (alpha_r alpha_c - G_rc) *
 // sigma^2 exp(-u_d^2 / 2 l_d^2) * u_d^2 / l_d^2, u_d = x_rd - x_cd -- the contraction with dK / dlog l_d.  2 + D too when an
 // ArdSEProduct or Matern leaf has tasks: out[2 + d] = sum_rc (alpha_r alpha_c - G_rc) dK_rc / dlog l_d.
-// LOO (all three kernels): the weight is graddot_weight<true>, u staged next to alpha in 256 doubles of LDS of its own, and
+// GD_LOO (all four kernels): the weight is graddot_weight<GD_LOO>, u staged next to alpha in 256 doubles of LDS of its own, and
 // out[1] = sum_rc weight_rc K_rc (counted like out[0]) in place of the trace, which that pass does not need.
-template <bool LOO>
-__global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __restrict__ tasks,
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const graddot_task_t<MODE>* __restrict__ tasks,
                                                               const KParam* __restrict__ kp, int D,
                                                               double* __restrict__ out, int ostride) {
     __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
     __shared__ double red[2][4];
     double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
     double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
-    const GradTask g = tasks[blockIdx.x];
+    const graddot_task_t<MODE> g = tasks[blockIdx.x];
     const KParam p = kp[g.kid];
     d4 acc[4][4];
     gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);      // ends on a barrier: the ring is free
@@ -1273,7 +1351,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
     const int lane = t & 63, w = t >> 6;
     const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
     double* ul = nullptr;
-    if constexpr (LOO) {
+    if constexpr (MODE == GD_LOO) {
         __shared__ double ul_s[2 * TB];
         ul = ul_s;
         ul[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[g.uoff + t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[g.uoff + t - TB] : 0.0);
@@ -1281,6 +1359,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
     }
     const double nh = p.nh0;
     double s = 0.0, tr = 0.0;
+    if constexpr (MODE == GD_TARGETS) graddot_targets_acc(g, acc, smem, tr);
     if (p.kind == 1) {
         // additive ArdSE (needs D <= GRADDOT_STAGE_D, checked by the host): one dimension at a time
         double* xs = smem;
@@ -1301,15 +1380,15 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
                 const int r = wr * 64 + 16 * rn + l15;
                 const bool rv = r < g.na;
                 const double ar = al[r], a = xs[d * 256 + r];
-                const double ur = LOO ? ul[r] : 0.0;
+                const double ur = MODE == GD_LOO ? ul[r] : 0.0;
                 const double* xb = xs + d * 256 + TB + wc * 64 + l4;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
                     const double u = a - xb[16 * (i >> 2) + 4 * (i & 3)];
                     const double q = u * u;
-                    const double pre = graddot_weight<LOO>(ar, al[TB + c], ur, LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
-                    if constexpr (LOO) {
+                    const double pre = graddot_weight<MODE>(ar, al[TB + c], ur, MODE == GD_LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
+                    if constexpr (MODE == GD_LOO) {
                         if (rv && c < g.nb) {
                             const double pe = pre * exp_nonpos(q * nhd);
                             sd = fma(pe, q, sd);
@@ -1327,9 +1406,9 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
             if (t == 0)   // u^2 / l_d^2 = -2 nh_d u^2
                 out[(size_t)ostride * blockIdx.x + 2 + d] = wgt * p.sigma2 * (-2.0 * nhd) * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
         }
-        if constexpr (LOO) {
+        if constexpr (MODE == GD_LOO) {
             tr *= p.sigma2;      // sum_rc weight_rc K_rc, K = sigma^2 sum_d exp(...)
-        } else {
+        } else if constexpr (MODE == GD_MLL) {
 #pragma unroll
             for (int rn = 0; rn < 4; ++rn) {
                 const int r = wr * 64 + 16 * rn + l15;
@@ -1357,7 +1436,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
             const int r = wr * 64 + 16 * rn + l15;
             const bool rv = r < g.na;
             const double ar = al[r];
-            const double ur = LOO ? ul[r] : 0.0;
+            const double ur = MODE == GD_LOO ? ul[r] : 0.0;
             double z[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) z[i] = 0.0;
@@ -1375,10 +1454,12 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
                 const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
                 if (rv && c < g.nb) {
                     const double kv = p.sigma2 * exp_nonpos(z[i] * nh);
-                    const double pre = graddot_weight<LOO>(ar, al[TB + c], ur, LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
+                    const double pre = graddot_weight<MODE>(ar, al[TB + c], ur, MODE == GD_LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
                     s = fma(pre * kv, z[i], s);
-                    if constexpr (LOO) tr += pre * kv;
-                    else if (g.diag && r == c) tr += acc[i >> 2][rn][i & 3];
+                    if constexpr (MODE == GD_LOO) tr += pre * kv;
+                    else if constexpr (MODE == GD_MLL) {
+                        if (g.diag && r == c) tr += acc[i >> 2][rn][i & 3];
+                    }
                 }
             }
         }
@@ -1400,10 +1481,12 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
                             z = fma(u, u, z);
                         }
                         const double kv = p.sigma2 * exp_nonpos(z * nh);
-                        const double pre = graddot_weight<LOO>(ar, g.alpha_b[c], LOO ? ul[r] : 0.0, LOO ? ul[TB + c] : 0.0, acc[cm][rn][q]);
+                        const double pre = graddot_weight<MODE>(ar, g.alpha_b[c], MODE == GD_LOO ? ul[r] : 0.0, MODE == GD_LOO ? ul[TB + c] : 0.0, acc[cm][rn][q]);
                         s = fma(pre * kv, z, s);
-                        if constexpr (LOO) tr += pre * kv;
-                        else if (g.diag && r == c) tr += acc[cm][rn][q];
+                        if constexpr (MODE == GD_LOO) tr += pre * kv;
+                        else if constexpr (MODE == GD_MLL) {
+                            if (g.diag && r == c) tr += acc[cm][rn][q];
+                        }
                     }
                 }
         }
@@ -1420,7 +1503,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
     if (threadIdx.x == 0) {
         const double wgt = g.diag ? 1.0 : 2.0;
         out[(size_t)ostride * blockIdx.x] = wgt * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
-        out[(size_t)ostride * blockIdx.x + 1] = (LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        out[(size_t)ostride * blockIdx.x + 1] = (MODE == GD_LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 
@@ -1431,8 +1514,8 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const GradTask* __
 // gram_accumulate<4>), with the coordinates staged GRADDOT_STAGE_D dimensions at a time (one stage for all four row groups
 // when D fits at once); the trace is taken from acc first, then acc <- (alpha_r alpha_c - G_rc) K_rc, and each dimension
 // costs one fma per entry.
-template <bool LOO>
-__global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTask* __restrict__ tasks,
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const graddot_task_t<MODE>* __restrict__ tasks,
                                                                    const KParam* __restrict__ kp, int D,
                                                                    double* __restrict__ out, int ostride) {
     __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
@@ -1440,7 +1523,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTas
     static_assert((GRADDOT_STAGE_D + 1) * 256 <= 2 * NRING * KC2 * LDP, "a chunk of coordinates and the alphas fit the ring");
     double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
     double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
-    const GradTask g = tasks[blockIdx.x];
+    const graddot_task_t<MODE> g = tasks[blockIdx.x];
     const KParam p = kp[g.kid];
     d4 acc[4][4];
     gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);      // ends on a barrier: the ring is free
@@ -1448,19 +1531,20 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTas
     const int lane = t & 63, w = t >> 6;
     const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
     double* ul = nullptr;
-    if constexpr (LOO) {
+    if constexpr (MODE == GD_LOO) {
         __shared__ double ul_s[2 * TB];
         ul = ul_s;
         ul[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[g.uoff + t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[g.uoff + t - TB] : 0.0);
         __syncthreads();
     }
     double tr = 0.0;
+    if constexpr (MODE == GD_TARGETS) graddot_targets_acc(g, acc, smem, tr);
     constexpr int CH = GRADDOT_STAGE_D;
     double* xs = smem;
     double* al = smem + (size_t)CH * 256;
     const int nch = (D + CH - 1) / CH;
     const double wgt = g.diag ? 1.0 : 2.0;
-    if constexpr (!LOO) {
+    if constexpr (MODE == GD_MLL) {
 #pragma unroll
         for (int rn = 0; rn < 4; ++rn) {
             const int r = wr * 64 + 16 * rn + l15;
@@ -1502,13 +1586,13 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTas
             }
         }
         const double ar = al[r];
-        const double ur = LOO ? ul[r] : 0.0;
+        const double ur = MODE == GD_LOO ? ul[r] : 0.0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
-            const double pre = graddot_weight<LOO>(ar, al[TB + c], ur, LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
+            const double pre = graddot_weight<MODE>(ar, al[TB + c], ur, MODE == GD_LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
             acc[i >> 2][rn][i & 3] = (rv && c < g.nb) ? pre * (p.sigma2 * exp_nonpos(z[i])) : 0.0;
-            if constexpr (LOO) tr += acc[i >> 2][rn][i & 3];
+            if constexpr (MODE == GD_LOO) tr += acc[i >> 2][rn][i & 3];
         }
     }
     for (int ch = 0; ch < nch; ++ch) {
@@ -1549,7 +1633,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTas
     __syncthreads();
     if (threadIdx.x == 0) {
         out[(size_t)ostride * blockIdx.x] = 0.0;
-        out[(size_t)ostride * blockIdx.x + 1] = (LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        out[(size_t)ostride * blockIdx.x + 1] = (MODE == GD_LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 
@@ -1558,8 +1642,8 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const GradTas
 // sigma^2 exp(-s) c(s) u_d^2 nh_d, finite at s = 0.  Launched over the last part of the tail.  A copy, not a template of that
 // kernel: as a template instantiation, or with the body shared through a template <bool> device function, the ArdSEProduct
 // kernel went from 240 VGPRs to 256 and 684 bytes of scratch per lane.
-template <bool LOO>
-__global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradTask* __restrict__ tasks,
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const graddot_task_t<MODE>* __restrict__ tasks,
                                                                      const KParam* __restrict__ kp, int D,
                                                                      double* __restrict__ out, int ostride) {
     __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
@@ -1567,7 +1651,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
     static_assert((GRADDOT_STAGE_D + 1) * 256 <= 2 * NRING * KC2 * LDP, "a chunk of coordinates and the alphas fit the ring");
     double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
     double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
-    const GradTask g = tasks[blockIdx.x];
+    const graddot_task_t<MODE> g = tasks[blockIdx.x];
     const KParam p = kp[g.kid];
     d4 acc[4][4];
     gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);      // ends on a barrier: the ring is free
@@ -1575,13 +1659,14 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
     const int lane = t & 63, w = t >> 6;
     const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
     double* ul = nullptr;
-    if constexpr (LOO) {
+    if constexpr (MODE == GD_LOO) {
         __shared__ double ul_s[2 * TB];
         ul = ul_s;
         ul[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[g.uoff + t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[g.uoff + t - TB] : 0.0);
         __syncthreads();
     }
     double tr = 0.0;
+    if constexpr (MODE == GD_TARGETS) graddot_targets_acc(g, acc, smem, tr);
     constexpr int CH = GRADDOT_STAGE_D;
     double* xs = smem;
     double* al = smem + (size_t)CH * 256;
@@ -1590,7 +1675,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
     // c(s) = c1 + c2 s: (1, 0) for nu = 3/2, (1/3, 1/3) for nu = 5/2
     const double c2 = matern_c2(p);
     const double c1 = (c2 != 0.0) ? c2 : 1.0;
-    if constexpr (!LOO) {
+    if constexpr (MODE == GD_MLL) {
 #pragma unroll
         for (int rn = 0; rn < 4; ++rn) {
             const int r = wr * 64 + 16 * rn + l15;
@@ -1632,15 +1717,15 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
             }
         }
         const double ar = al[r];
-        const double ur = LOO ? ul[r] : 0.0;
+        const double ur = MODE == GD_LOO ? ul[r] : 0.0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
-            const double pre = graddot_weight<LOO>(ar, al[TB + c], ur, LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
+            const double pre = graddot_weight<MODE>(ar, al[TB + c], ur, MODE == GD_LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
             const double s = sqrt(z[i]);
             const double wk = p.sigma2 * exp_nonpos(-s) * fma(c2, s, c1);
             acc[i >> 2][rn][i & 3] = (rv && c < g.nb) ? pre * wk : 0.0;
-            if constexpr (LOO)        // the kernel value from the weight: K = wk (1 + s + c2 s^2) / c(s), c(s) >= 1/3
+            if constexpr (MODE == GD_LOO)        // the kernel value from the weight: K = wk (1 + s + c2 s^2) / c(s), c(s) >= 1/3
                 tr = fma(acc[i >> 2][rn][i & 3], fma(fma(c2, s, 1.0), s, 1.0) / fma(c2, s, c1), tr);
         }
     }
@@ -1682,7 +1767,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
     __syncthreads();
     if (threadIdx.x == 0) {
         out[(size_t)ostride * blockIdx.x] = 0.0;
-        out[(size_t)ostride * blockIdx.x + 1] = (LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        out[(size_t)ostride * blockIdx.x + 1] = (MODE == GD_LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 
@@ -1691,8 +1776,8 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const GradT
 // 2 alpha nh_d = 1 / l_d^2: dK / dlog l_d = k / (1 + w) u_d^2 / l_d^2.  One more output, out[2 + D] (ostride >= 3 + D): the
 // contraction with dK / dlog alpha = k alpha (w / (1 + w) - log1p(w)), evaluated as written (<= 0; the cancellation at small w
 // costs absolute error of order eps k alpha w).  A copy for the reason given there.
-template <bool LOO>
-__global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const GradTask* __restrict__ tasks,
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const graddot_task_t<MODE>* __restrict__ tasks,
                                                                      const KParam* __restrict__ kp, int D,
                                                                      double* __restrict__ out, int ostride) {
     __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
@@ -1700,7 +1785,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const GradTask*
     static_assert((GRADDOT_STAGE_D + 1) * 256 <= 2 * NRING * KC2 * LDP, "a chunk of coordinates and the alphas fit the ring");
     double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
     double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
-    const GradTask g = tasks[blockIdx.x];
+    const graddot_task_t<MODE> g = tasks[blockIdx.x];
     const KParam p = kp[g.kid];
     d4 acc[4][4];
     gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);      // ends on a barrier: the ring is free
@@ -1708,13 +1793,14 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const GradTask*
     const int lane = t & 63, w = t >> 6;
     const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
     double* ul = nullptr;
-    if constexpr (LOO) {
+    if constexpr (MODE == GD_LOO) {
         __shared__ double ul_s[2 * TB];
         ul = ul_s;
         ul[t] = (t < TB) ? ((t < g.na) ? g.alpha_a[g.uoff + t] : 0.0) : ((t - TB < g.nb) ? g.alpha_b[g.uoff + t - TB] : 0.0);
         __syncthreads();
     }
     double tr = 0.0;
+    if constexpr (MODE == GD_TARGETS) graddot_targets_acc(g, acc, smem, tr);
     constexpr int CH = GRADDOT_STAGE_D;
     double* xs = smem;
     double* al = smem + (size_t)CH * 256;
@@ -1722,7 +1808,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const GradTask*
     const double wgt = g.diag ? 1.0 : 2.0;
     const double alpha = rq_alpha(p);
     double sa = 0.0;            // sum_rc weight_rc k_rc (w / (1 + w) - log1p(w)): the contraction with dK / dlog alpha, over alpha
-    if constexpr (!LOO) {
+    if constexpr (MODE == GD_MLL) {
 #pragma unroll
         for (int rn = 0; rn < 4; ++rn) {
             const int r = wr * 64 + 16 * rn + l15;
@@ -1764,17 +1850,17 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const GradTask*
             }
         }
         const double ar = al[r];
-        const double ur = LOO ? ul[r] : 0.0;
+        const double ur = MODE == GD_LOO ? ul[r] : 0.0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
-            const double pre = graddot_weight<LOO>(ar, al[TB + c], ur, LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
+            const double pre = graddot_weight<MODE>(ar, al[TB + c], ur, MODE == GD_LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
             const double lw = log1p(z[i]);
             const double q = 1.0 / (1.0 + z[i]);
             const double pk = (rv && c < g.nb) ? pre * (p.sigma2 * exp_nonpos(-alpha * lw)) : 0.0;
             sa = fma(pk, z[i] * q - lw, sa);
             acc[i >> 2][rn][i & 3] = pk * q;
-            if constexpr (LOO) tr += pk;
+            if constexpr (MODE == GD_LOO) tr += pk;
         }
     }
     for (int ch = 0; ch < nch; ++ch) {
@@ -1819,7 +1905,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const GradTask*
     __syncthreads();
     if (threadIdx.x == 0) {
         out[(size_t)ostride * blockIdx.x] = 0.0;
-        out[(size_t)ostride * blockIdx.x + 1] = (LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        out[(size_t)ostride * blockIdx.x + 1] = (MODE == GD_LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 

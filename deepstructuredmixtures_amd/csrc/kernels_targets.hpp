@@ -231,4 +231,136 @@ __global__ __launch_bounds__(256) void targets_mu_kernel(const TargetsMuTask* __
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Hyper-parameter gradients of sum_q w_lq mll_lq (dsmgp_mll_columns_gradients).  With A = L^-T Z = K_y^-1 (Y - m), G = K_y^-1 and
+// s_l = sum_q w_lq:   sum_q w_lq dmll_lq / dtheta = 1/2 sum_rc (sum_q w_lq a_rq a_cq - s_l G_rc) (dK_y / dtheta)_rc.
+//   targets_a_kernel        A of every leaf into an arena of its own (npad x Qpad per leaf, ld = npad)
+//   tile_graddot_*<GD_TARGETS>   the contraction, G never stored and the rank-Q term added to the accumulators (kernels.hpp)
+//   targets_wsums_kernel    sum_q w_lq |z_q|^2 and sum_q w_lq |a_q|^2 per leaf (the trace identity and dnoise)
+//   targets_ardlin_kernel   ArdLinear leaves: sum_q w_lq (a_q . x_d)^2
+
+// A_i = sum_{k >= i} Xt[i, k] Z_k for one 128-row block i of a leaf, Xt = L^-T of the leaf's factor owner: row tile i of the
+// arena from column 128 i on (the blocks left of the diagonal are never written and never read here).  Operands as in
+// targets_mu_kernel: column j of A is a sum over column j of Z only, in ascending k.  Columns c >= n of Xt are masked on load
+// and rows >= nrows are stored as zeros, whatever the arena's padding holds; all Qpad columns are written.
+struct TargetsATask {
+    const double* Xt;       // row tile i of the owner's L^-T, ld = ldt
+    const double* Z;        // the leaf's Z (npad x qpad, ld = ldz)
+    double* A;              // block i of the leaf's A (ld = ldz)
+    int ldt, ldz, k0, n, nrows, pad;
+};
+
+__global__ __launch_bounds__(256) void targets_a_kernel(const TargetsATask* __restrict__ tasks, int qpad) {
+    const TargetsATask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int nk = (tk.n - tk.k0 + 3) / 4;
+    for (int q0 = 0; q0 < qpad; q0 += TMU_CH * TQ) {
+        const int nch = min(TMU_CH, (qpad - q0) / TQ);
+        d4 acc[TMU_CH][2];
+#pragma unroll
+        for (int ch = 0; ch < TMU_CH; ++ch) {
+            acc[ch][0] = (d4){0.0, 0.0, 0.0, 0.0};
+            acc[ch][1] = (d4){0.0, 0.0, 0.0, 0.0};
+        }
+        const double* pv = tk.Xt + 32 * w + l15;
+        const double* pz = tk.Z + (size_t)(q0 + l15) * tk.ldz;
+        for (int kk = 0; kk < nk; ++kk) {
+            const int c = tk.k0 + 4 * kk + l4;
+            const bool in = c < tk.n;
+            const int r0 = tk.k0 + 32 * w + l15;        // L^-T is upper triangular: (row, c) enters for row <= c only
+            const double v0 = (in && r0 <= c) ? pv[(size_t)c * tk.ldt] : 0.0;
+            const double v1 = (in && r0 + 16 <= c) ? pv[(size_t)c * tk.ldt + 16] : 0.0;
+#pragma unroll
+            for (int ch = 0; ch < TMU_CH; ++ch) {
+                if (ch >= nch) continue;
+                const double fz = in ? pz[c + (size_t)(ch * TQ) * tk.ldz] : 0.0;
+                acc[ch][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fz, v0, acc[ch][0], 0, 0, 0);
+                acc[ch][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fz, v1, acc[ch][1], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int ch = 0; ch < TMU_CH; ++ch) {
+            if (ch >= nch) continue;
+#pragma unroll
+            for (int rn = 0; rn < 2; ++rn) {
+                const int row = 32 * w + 16 * rn + l15;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int q = q0 + ch * TQ + l4 + 4 * r;
+                    tk.A[(size_t)row + (size_t)q * tk.ldz] = row < tk.nrows ? acc[ch][rn][r] : 0.0;
+                }
+            }
+        }
+    }
+}
+
+// out[2 l] = sum_q w_lq |z_q|^2, out[2 l + 1] = sum_q w_lq |a_q|^2: thread t adds the rows t, t + 256, ..., each row's columns in
+// ascending q, then the tree of mll_kernel -- a fixed order.  One workgroup per leaf.
+__global__ __launch_bounds__(256) void targets_wsums_kernel(const LeafDev* __restrict__ leaves, const double* __restrict__ arenaT,
+                                                            const long long* __restrict__ toff, const double* __restrict__ arenaA,
+                                                            const double* __restrict__ wq, int L, int Q, int qpad,
+                                                            double* __restrict__ out) {
+    __shared__ double r1[256], r2[256];
+    const int l = blockIdx.x;
+    const LeafDev lf = leaves[l];
+    const double* z = arenaT + toff[l] + (size_t)lf.npad * qpad;
+    const double* a = arenaA + toff[l] / 2;
+    const int t = threadIdx.x;
+    double sz = 0.0, sa = 0.0;
+    for (int i = t; i < lf.n; i += 256)
+        for (int q = 0; q < Q; ++q) {
+            const double wv = wq[l + (size_t)q * L];
+            const double zv = z[i + (size_t)q * lf.npad], av = a[i + (size_t)q * lf.npad];
+            sz = fma(wv * zv, zv, sz);
+            sa = fma(wv * av, av, sa);
+        }
+    r1[t] = sz;
+    r2[t] = sa;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            r1[t] += r1[t + o];
+            r2[t] += r2[t + o];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[2 * l] = r1[0];
+        out[2 * l + 1] = r2[0];
+    }
+}
+
+// ArdLinear leaves: out[task * D + d] = sum_q w_q (a_q . x_d)^2, one workgroup per (task, d).  Wave w takes the columns
+// q = w, w + 4, ...: the dot product over the lanes (fixed butterfly), the columns of a wave added in ascending q, the four
+// waves in order.
+struct TargetsArdLinTask {
+    const double* A;        // the leaf's A (ld = ld)
+    const double* x;        // the leaf's inputs (ld = ld)
+    const double* wq;       // weight of column q at wq[q * ldw]
+    int ld, ldw, n, Q;
+};
+
+__global__ __launch_bounds__(256) void targets_ardlin_kernel(const TargetsArdLinTask* __restrict__ tasks, int D,
+                                                             double* __restrict__ out) {
+    __shared__ double red[4];
+    const TargetsArdLinTask tk = tasks[blockIdx.x];
+    const int d = blockIdx.y;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const double* x = tk.x + (size_t)d * tk.ld;
+    double s = 0.0;
+    for (int q = w; q < tk.Q; q += 4) {
+        const double* a = tk.A + (size_t)q * tk.ld;
+        double dot = 0.0;
+        for (int i = lane; i < tk.n; i += 64) dot = fma(a[i], x[i], dot);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+        s = fma(tk.wq[(size_t)q * tk.ldw] * dot, dot, s);
+    }
+    if (lane == 0) red[w] = s;
+    __syncthreads();
+    if (t == 0) out[(size_t)blockIdx.x * D + d] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 }  // namespace dsmgp

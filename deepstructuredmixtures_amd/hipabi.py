@@ -56,6 +56,7 @@ SIGNATURES = {
     "dsmgp_solve_targets": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp, _dp]),
     "dsmgp_predict_targets": (C.c_int, [_ctx, _dp, C.c_int64, _dp]),
     "dsmgp_targets_fetch": (C.c_int, [_ctx, C.c_int32, _dp]),
+    "dsmgp_mll_columns_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp]),
     "dsmgp_gradients": (C.c_int, [_ctx, _dp, C.c_int32]),
     "dsmgp_loo": (C.c_int, [_ctx, _dp, _dp, _dp, _dp]),
     "dsmgp_loo_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp]),
@@ -444,6 +445,26 @@ class Context:
         Z = np.empty((n, self.targets_Q), dtype=np.float64, order="F")
         self._chk(self.lib.dsmgp_targets_fetch(self.h, leaf, Z.ctypes.data_as(_dp)))
         return Z
+
+    def targets_gradients(self, stride, col_weight=None):
+        """`grad[L, stride]`: `grad[l, j] = sum_q col_weight[l, q] * d mll[l, q] / d theta_j` over the columns of the last
+        `solve_targets`, `mll` its table, in the layout and with the conventions of `gradients` (dsmgp_mll_columns_gradients).
+        `col_weight` is `(L, Q)` (a vector counts as one column), any sign, zero columns allowed; None: ones.  Needs
+        `solve_targets` on the current fit.  Leaves with `info != 0` come back as NaN rows.  The mask of `set_gradient_leaves`
+        does not apply.  The device time of the call is left in `self.targets_gradients_seconds`."""
+        pw = None
+        if col_weight is not None:
+            w = np.asarray(col_weight, dtype=np.float64)
+            if w.ndim == 1:
+                w = w[:, None]
+            if w.shape != (self.L, self.targets_Q):
+                raise ValueError(f"col_weight of shape {w.shape}: expected ({self.L}, {self.targets_Q})")
+            w, pw = _f64_fortran(w)
+        g = np.zeros((self.L, stride))
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_mll_columns_gradients(self.h, g.ctypes.data_as(_dp), int(stride), pw, C.byref(sec)))
+        self.targets_gradients_seconds = sec.value
+        return g
 
     # ---- predict(model, x) aggregation + scores on the device (src/common.jl:134-302, src/scorefunctions.jl) ----
     def _agg_args(self, family, leaf_coef, leaf_group):

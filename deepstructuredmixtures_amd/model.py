@@ -726,33 +726,97 @@ def _grad_tree(model, tab, leaf_weights, rho=True):
     """`∇mll!` over a table of node values `tab` and the per-leaf gradients `model.leaf_grad` (shared by grad_mll and grad_loo).
     `rho=False`: every sum node of K children weighs a child by exp(-log K + child - node) and nothing else -- without the
     reference's `+ log K` (`src/optimize.jl:70-73`) and with the `-log K` it leaves out under a sum over GPs (`:76-89`): the true
-    derivative of the root value."""
+    derivative of the root value.  Two parts: the scalar weight of every leaf (`_tree_leaf_weights`), then the scatter of the
+    weighted leaf rows into the hyper-vector (`_scatter_leaf_rows`)."""
+    visits = _tree_leaf_weights(model, tab, leaf_weights, rho)
+    return _scatter_leaf_rows(model, model.leaf_grad, visits)
+
+
+def _tree_leaf_weights(model, tab, leaf_weights=None, rho=True):
+    """The scalar weight of every leaf in `∇mll!` over the node values `tab`: a list of `(leaf, weight, offset, size)` in the
+    order the recursion visits the leaves, `offset` / `size` the slice of the hyper-vector the leaf's row is added to."""
     logS = tab[model.root.id]
     n_hyp = getparams(model).size
-    grad = np.zeros(n_hyp)
+    visits = []
 
-    def rec(node, dparent, lrho, g):
+    def rec(node, dparent, lrho, off, size):
         if node.kind == "gp":
             w = np.exp(-logS + lrho + tab[node.id] + dparent)                 # :48
             if leaf_weights is not None:
                 w = w * leaf_weights[node.leaf]                               # :101
-            g += model.leaf_grad[node.leaf][: g.size] * w                     # :49
+            visits.append((node.leaf, w, off, size))
         elif node.kind == "split":
             for c in node.children:
-                rec(c, dparent + (tab[node.id] - tab[c.id]), lrho, g)         # :58-61
+                rec(c, dparent + (tab[node.id] - tab[c.id]), lrho, off, size)  # :58-61
         elif node.of_gps:
             c0 = 0
             for c in node.children:                                           # :76-89
                 nn = c.kernel.nparams() + 1
-                rec(c, dparent if rho else dparent - np.log(len(node.children)), lrho, g[c0:c0 + nn])
+                lo = min(off + c0, off + size)
+                rec(c, dparent if rho else dparent - np.log(len(node.children)), lrho, lo, min(off + c0 + nn, off + size) - lo)
                 c0 += nn
         else:
             K = len(node.children)
             for c in node.children:
-                rec(c, -np.log(K) + dparent, np.log(K) + lrho if rho else lrho, g)   # :70-73
+                rec(c, -np.log(K) + dparent, np.log(K) + lrho if rho else lrho, off, size)   # :70-73
 
-    rec(model.root, 0.0, 0.0, grad)
+    rec(model.root, 0.0, 0.0, 0, n_hyp)
+    return visits
+
+
+def _scatter_leaf_rows(model, rows, visits):
+    """`grad[offset : offset + size] += rows[leaf][:size] * weight` for every visit, in order (`src/optimize.jl:49`)."""
+    grad = np.zeros(getparams(model).size)
+    for leaf, w, off, size in visits:
+        g = grad[off:off + size]
+        g += rows[leaf][: g.size] * w                                         # :49
     return grad
+
+
+def targets_objective(model):
+    """`sum_q` of the tree recursion of `mll(model)` over column `q` of the `(L, Q)` table the last `fit_targets` returned:
+    `sum_q log p_tree(Y[:, q])`; for a `GaussianProcess` the sum of its row."""
+    target = model.model if isinstance(model, GaussianProcess) else model
+    tab = getattr(target, "targets_mll", None)
+    if tab is None:
+        raise hipabi.DsmgpError(hipabi.E_STATE, "targets_objective before fit_targets")
+    if isinstance(model, GaussianProcess):
+        return float(np.sum(tab[0]))
+    return float(sum(_value_table(model, tab[:, q])[model.root.id] for q in range(tab.shape[1])))
+
+
+def targets_weight_table(model):
+    """The `(L, Q)` table of `grad_targets`: entry `[l, q]` is the weight `∇mll!` gives leaf `l` when column `q` of the last
+    `fit_targets` table stands for the leaf log marginals."""
+    target = model.model if isinstance(model, GaussianProcess) else model
+    tab = target.targets_mll
+    if isinstance(model, GaussianProcess):
+        return np.ones_like(tab), [(0, 1.0, 0, model.node.kernel.nparams() + 1)]
+    W = np.zeros_like(tab)
+    visits = []
+    for q in range(tab.shape[1]):
+        visits = _tree_leaf_weights(model, _value_table(model, tab[:, q]))
+        for leaf, w, _, _ in visits:
+            W[leaf, q] += w
+    return W, visits
+
+
+def grad_targets(model):
+    """Gradient of `targets_objective(model)` w.r.t. the shared hyper-vector in `grad_mll`'s convention (the reference's
+    `∇mll!`, column by column): with `Y = y[:, None]` it equals `grad_mll(model)`.  The weight of every (leaf, column) comes from
+    the tree recursion on that column's table; ONE device call returns `sum_q W[l, q] dmll[l, q] / dtheta` per leaf
+    (`Context.targets_gradients`: one inversion and one contraction per leaf whatever Q is), and the rows are scattered into
+    the hyper-vector with weight 1.  Needs `fit_targets` on the current fit."""
+    target = _targets_model(model, "grad_targets")
+    if getattr(target, "targets_mll", None) is None:
+        raise hipabi.DsmgpError(hipabi.E_STATE, "grad_targets before fit_targets")
+    W, visits = targets_weight_table(model)
+    stride = max(lf.kernel.nparams() + 1 for lf in target.leaves)
+    rows = target.ctx.targets_gradients(stride, W)
+    target.targets_leaf_grad = rows
+    if isinstance(model, GaussianProcess):
+        return rows[0][: model.node.kernel.nparams() + 1].copy()
+    return _scatter_leaf_rows(model, rows, [(leaf, 1.0, off, size) for leaf, _, off, size in visits])
 
 
 class ADAM:
@@ -794,7 +858,7 @@ class RMSProp:
         return g * (self.eta / (np.sqrt(self.acc) + self.eps))
 
 
-def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="mll"):
+def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="mll", targets=None):
     """`train!(gp::GaussianProcess; iterations, optim, λ)` (`src/optimisers.jl:89-145`): ascent on one GP's log
     marginal; a NaN log marginal (or a factorisation that fails: LAPACK info > 0, which the reference's potrf! call
     ignores and which then shows up as NaN) rolls back to the previous hyper-vector and returns; early stop when the
@@ -815,6 +879,9 @@ def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="ml
         if objective == "loo" and not np.isnan(ell):      # value and gradient from one call, outside the try: an error of the
             updategradients(gp, objective="loo")          # LOO pass itself (memory, ArdSE with D > 35) is an error, as for the
             ell = loo_objective(gp, lpd=gp.model.leaf_lpd)    # marginal-likelihood gradients below
+        if targets is not None and not np.isnan(ell):     # sum_q mll of the target columns on this factorisation
+            fit_targets(gp, targets)
+            ell = targets_objective(gp)
         hist.append(ell)
         if np.isnan(ell):                                                     # :115-119
             setparams(target, old)
@@ -827,6 +894,8 @@ def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="ml
             return gp, np.array(hist)
         if objective == "loo":
             g = grad_loo(gp)
+        elif targets is not None:
+            g = grad_targets(gp)
         else:
             updategradients(gp)
             g = grad_mll(gp)
@@ -838,18 +907,25 @@ def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="ml
 
 
 def train(model, optim=None, *, iterations=10_000, lam=None, randinit=True, earlystop=10, seed=0, tau=0.05, verbose=False,
-          objective="mll"):
+          objective="mll", targets=None):
     """`train!(model, optim; iterations, λ, randinit, earlystop)` (`src/optimisers.jl:4-87`): gradient ASCENT
     on the tree log marginal over one shared hyper-vector.  Returns (model, history of root mll).
     For a single `GaussianProcess` it is `train!(gp; iterations, optim, λ)` (`src/optimisers.jl:89-145`:
     RMSProp, λ = 0.1, rollback on a NaN log marginal).
     `objective="loo"`: the same loops on `loo_objective(model)` -- history and early stop on it, ascent on `grad_loo` (no
-    counterpart in the reference); a streaming model refuses (`DsmgpError`, E_STATE)."""
+    counterpart in the reference); a streaming model refuses (`DsmgpError`, E_STATE).
+    `targets=Y` (`(N, Q)`, default None: nothing changes): the same loops on `targets_objective(model)`, one kernel trained on all
+    Q columns -- per iteration `setparams`, `fit`, `fit_targets`, `grad_targets`, optimiser step.  Not together with
+    `objective="loo"`; streaming and multi-rank models refuse as `fit_targets` does."""
     from .datagen import normal
     _check_objective(objective)
+    if targets is not None:
+        if objective == "loo":
+            raise ValueError("train: targets go with the marginal likelihood objective, not with objective='loo'")
+        _targets_model(model, "train(targets=...)")
     if isinstance(model, GaussianProcess):
         return _train_gp(model, RMSProp() if optim is None else optim, iterations, 0.1 if lam is None else lam, randinit, seed,
-                         verbose, objective)
+                         verbose, objective, targets)
     has_leaves = len(model.shard.local) > 0
     # factor-and-discard context: a pass over the leaf groups cannot be revisited, so the loop's fit! asks for the
     # gradients of the same pass up front (one pass per iteration instead of a fit pass plus a fit + gradient pass)
@@ -869,7 +945,7 @@ def train(model, optim=None, *, iterations=10_000, lam=None, randinit=True, earl
         model.ctx.want_gradients = max(lf.kernel.nparams() + 1 for lf in model.leaves)
         model.ctx.groups = None
     try:
-        return _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming, objective)
+        return _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming, objective, targets)
     finally:
         if streaming:                  # also after an error inside the loop: later passes must not collect gradients
             model.ctx.want_gradients = 0
@@ -878,7 +954,8 @@ def train(model, optim=None, *, iterations=10_000, lam=None, randinit=True, earl
             model.ctx.set_joint(True)
 
 
-def _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming=False, objective="mll"):
+def _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming=False, objective="mll",
+                targets=None):
     def plain_fits():
         if streaming:                  # the fits after the loop need no gradients: smaller groups, fewer passes
             model.ctx.want_gradients = 0
@@ -890,6 +967,9 @@ def _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, ver
         if objective == "loo":          # value and gradient from one call
             updategradients(model, objective="loo")
             ell = loo_objective(model, lpd=model.leaf_lpd)
+        elif targets is not None:
+            fit_targets(model, targets)
+            ell = targets_objective(model)
         else:
             ell = mll(model)
         hist.append(ell)
@@ -902,6 +982,8 @@ def _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, ver
             return model, np.array(hist)
         if objective == "loo":
             g = grad_loo(model)
+        elif targets is not None:
+            g = grad_targets(model)
         else:
             updategradients(model)
             g = grad_mll(model)
@@ -1291,7 +1373,8 @@ def fit_targets(model, Y, mean=None):
         fit(target)             # the hyper-parameters moved since the last fit
         mll, sec = target.ctx.solve_targets(Y, mean)
     target.last_targets_seconds = sec
-    return np.ascontiguousarray(mll)
+    target.targets_mll = np.ascontiguousarray(mll)      # what targets_objective / grad_targets read
+    return target.targets_mll.copy()
 
 
 def _aggregate_host(model, xt, rc, mu, var):

@@ -221,13 +221,44 @@ int dsmgp_predict_gradients(dsmgp_ctx* ctx, double* dmu_out, double* dvar_out /*
  *   usable context when it does not fit), re-used while Q does not grow, NOT counted by dsmgp_estimate_bytes / dsmgp_memory,
  *   dropped with the leaf table, new training data and dsmgp_release (under a reserved pool also with a new test set: the pool
  *   is a stack).
- * Out of scope: gradients of sum_j mll_j, LOO and input gradients for the extra columns, the multi-GPU exchange (each rank solves
- *   its own leaves, the mll table is per rank), and the streaming context. */
+ * Out of scope: LOO and input gradients for the extra columns, the multi-GPU exchange (each rank solves its own leaves, the mll
+ *   table is per rank), and the streaming context.  Gradients of sum_j mll_j: dsmgp_mll_columns_gradients below. */
 int dsmgp_solve_targets(dsmgp_ctx* ctx, const double* Y /* N x Q column-major */, int64_t N, int32_t Q, int64_t ldy,
                         const double* mean /* L x Q column-major, ld = L; NULL = zeros */,
                         double* mll_out /* L x Q column-major, ld = L; may be NULL */, double* seconds /* may be NULL */);
 int dsmgp_predict_targets(dsmgp_ctx* ctx, double* mu_out /* route_total x Q column-major */, int64_t ld, double* seconds);
 int dsmgp_targets_fetch(dsmgp_ctx* ctx, int32_t leaf, double* Z_out /* n x Q column-major, ld = n */);
+
+/* Hyper-parameter gradients of the weighted sum of the per-column log marginal likelihoods of dsmgp_solve_targets:
+ *   grad_out[l * stride + j] = sum_q col_weight[l + q L] * d mll_out[l + q L] / d theta_j ,
+ * in the layout and with every convention of dsmgp_gradients ([dl..., ds, dnoise], [dl..., da, ds, dnoise] for the rational
+ * quadratic kinds; the reference's factor sigma for IsoSE; ArdSE dl zero unless DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT = 1; the dummy
+ * variance slot of the linear kinds; zeros past the hyper-vector).  With Q = 1, Y = y, mean = the leaf means and weight 1 it is
+ * dsmgp_gradients to rounding.  With A = L^-T Z = K_y^-1 (Y - m), G = K_y^-1 and s_l = sum_q w_lq,
+ *   sum_q w_lq d mll_lq / d theta = 1/2 sum_rc ( sum_q w_lq a_rq a_cq - s_l G_rc ) (dK_y / d theta)_rc :
+ * one inversion (none when the arena already holds L^-T of this fit, dsmgp_loo's rule) and one contraction per leaf whatever Q
+ * is, plus O(n^2 Q) for A (a tile product on the f64 matrix cores) and for the rank-Q term, which the contraction kernels add to
+ * their accumulators before their epilogue.  The weights may have any sign and zero columns; NULL = ones.  They are per leaf AND
+ * per column because the back-propagation of sum_q log p_tree(Y[:, q]) weighs a leaf differently for every column.
+ * Needs a fit and a dsmgp_solve_targets on the CURRENT fit (DSMGP_E_STATE otherwise).  DSMGP_E_ARG: grad_out NULL, stride smaller
+ * than a hyper-vector, a non-finite weight, and where dsmgp_gradients refuses (ArdSE with the option on and D > 35).
+ * The mask of dsmgp_set_gradient_leaves does not apply and is left as it is.  Leaves whose fit reported info != 0 get a NaN row.
+ * Nothing another entry point reads is written: dsmgp_fit's outputs, dsmgp_gradients, dsmgp_loo*, dsmgp_predict_*,
+ * dsmgp_targets_fetch and dsmgp_predict_targets return the same bits before and after.  Sums run in a fixed order, no atomics: the
+ * same bits from call to call, and with one lane and with two wherever both fits leave the same factor bits.
+ * Memory: A takes npad Qpad doubles per leaf in an arena of its own, allocated on first use (from the reserved pool when there is
+ *   one; DSMGP_E_NOMEM with a usable context when it does not fit), NOT counted by dsmgp_estimate_bytes / dsmgp_memory, dropped
+ *   where the arena of dsmgp_solve_targets is dropped.  seconds: device time of the call. */
+int dsmgp_mll_columns_gradients(dsmgp_ctx* ctx, double* grad_out /* L x stride */, int32_t stride,
+                            const double* col_weight /* L x Q column-major, ld = L; NULL = ones */,
+                            double* seconds /* may be NULL */);
+/* The same call under the name of the feature, for C and C++ callers (an inline alias, not a symbol of the library: the library
+ * exports exactly three symbols with the word of the feature in their name, the three above, and bindings that resolve symbols
+ * at run time -- Python, Julia -- use dsmgp_mll_columns_gradients). */
+static inline int dsmgp_targets_gradients(dsmgp_ctx* ctx, double* grad_out, int32_t stride, const double* col_weight,
+                                          double* seconds) {
+    return dsmgp_mll_columns_gradients(ctx, grad_out, stride, col_weight, seconds);
+}
 
 /* ---- predict(model, x): sum/product aggregation of the leaf moments over the leaves every test row visits, on the
  *      moments the last dsmgp_predict_run left in HBM (replaces the host recursions of src/common.jl:134-149,198-302).

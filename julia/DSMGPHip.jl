@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, targets_fetch, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
+export attach!, detach!, census, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, targets_fetch, targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -578,6 +578,23 @@ function targets_fetch(s::Session, leaf::Integer)
     Z = Matrix{Float64}(undef, n, s.targets)
     GC.@preserve Z chk(s, ccall(sym(:dsmgp_targets_fetch), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.h, Int32(leaf - 1), Z))
     return Z
+end
+
+"targets_gradients(s; col_weight=nothing): hyper-parameter gradients of the weighted sum of the per-column log marginal likelihoods
+of the last solve_targets (dsmgp_mll_columns_gradients): `g[:, l] = Σ_q col_weight[l, q] ∂mll[l, q]/∂θ` in the layout and with the
+conventions of updategradients! ([∂ℓ…, ∂σ, ∂ϵ]; zeros past the leaf's hyper-vector).  `col_weight` is `L × Q` (the order of
+`s.leaves`), any sign, zero columns allowed; `nothing`: ones.  One inversion and one contraction per leaf whatever Q is.  Needs
+solve_targets on the current fit; leaves whose fit reported info ≠ 0 come back as NaN.  Nothing is written to the kernels'
+gradient fields."
+function targets_gradients(s::Session; col_weight::Union{Nothing,AbstractMatrix}=nothing)
+    L = length(s.leaves)
+    W = col_weight === nothing ? nothing : Matrix{Float64}(col_weight)
+    W === nothing || size(W) == (L, s.targets) || throw(DimensionMismatch("col_weight must be L × Q"))
+    g = Matrix{Float64}(undef, s.stride, L)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve g W chk(s, ccall(sym(:dsmgp_mll_columns_gradients), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ref{Float64}),
+                                  s.h, g, Int32(s.stride), W === nothing ? Ptr{Float64}(C_NULL) : pointer(W), sec))
+    return g
 end
 
 # ---------------------------------------------------------------------------------------------- predict
