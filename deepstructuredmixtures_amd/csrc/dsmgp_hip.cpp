@@ -2693,6 +2693,14 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
         std::vector<int> owner_info(L);
         HIPCHK(c, hipMemcpy(owner_info.data(), c->d_info.p, L * sizeof(int), hipMemcpyDeviceToHost));
         for (int l = 0; l < L; ++l) info_out[l] = owner_info[c->leaves[l].owner];
+        // A PREFIX leaf whose source failed inside the rows it copied meets the damage at its first own pivot (row kb * TB + 1);
+        // its first bad leading minor is the source's, and that is what LAPACK would report for the leaf
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            if (lf.op != DSMGP_SHARE_PREFIX) continue;
+            const int si = owner_info[lf.src];
+            if (si != 0 && si <= lf.kb * TB && info_out[l] != 0) info_out[l] = si;
+        }
     }
     c->fitted = true;
     c->predicted = false;

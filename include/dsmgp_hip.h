@@ -123,6 +123,13 @@ int dsmgp_set_hyper(dsmgp_ctx* ctx, int32_t kernel_id, int32_t kind, const doubl
  *      mll_out[l]  = -(y.alpha + logdet + n log 2pi)/2, with y.alpha evaluated as |L^-1 y|^2; gp.alpha itself is
  *                    materialised on first use (dsmgp_gradients, dsmgp_download_factor), not by fit
  *      info_out[l] = 0, or k>0 if the leading minor of order k is not positive definite (LAPACK potrf)
+ *                    A COPY leaf reports its source's value.  A PREFIX leaf whose source failed inside the rows it copies
+ *                    (k <= 128 floor(prefix_len / 128)) has the same first bad minor and reports the same k: on the device it
+ *                    meets the damage at its first own pivot, so it is flagged as failed there too and gets NaN wherever a
+ *                    failed leaf does (dsmgp_solve_targets, dsmgp_predict_targets, dsmgp_loo*, dsmgp_predict_gradients, ...).
+ *                    Where the source fails later, in a block the PREFIX leaf recomputes, the leaf finds its own k.  Every
+ *                    other leaf, the other PREFIX and COPY leaves of other sources included, keeps its bits.
+ *                    (dsmgp_fit_exchange ships the device's flag: nonzero for such a leaf, row 128 floor(prefix_len / 128) + 1.)
  *      seconds     = device time of the call (hipEvents), like the @elapsed value fit! returns */
 int dsmgp_fit(dsmgp_ctx* ctx, double* mll_out /* L */, int32_t* info_out /* L */, double* seconds);
 
