@@ -627,6 +627,19 @@ struct dsmgp_ctx {
     DevBuf<ArdLinTask> tgquad;
     DevBuf<TargetsArdLinTask> tgardlin;
     DevBuf<double> d_tgw, d_tgpart; // the weights (L x Q); frob | contraction x gstride | 2 L | ArdLinear 2 D per column group | D per leaf
+    // dsmgp_loo_columns / dsmgp_loo_columns_gradients: H = K_y^-1 diag(sqrt W), npad^2 per leaf, and U = K_y^-1 (A / d), npad x Qpad
+    // at offset toff / 2, in arenas of their own (the rule of arenaA); the lists are rebuilt per call
+    double* arenaHc = nullptr;
+    double* arenaU = nullptr;
+    size_t cap_Hc = 0, cap_U = 0;
+    DevBuf<LooColsTask> lcleaf;
+    DevBuf<GinvTask> lcginv;
+    DevBuf<LooColsUTask> lcu;
+    DevBuf<LooColsRowTask> lcrow;
+    DevBuf<GradTaskLc> lcdot;
+    DevBuf<ArdLinTask> lcquad;
+    DevBuf<LooColsArdLinTask> lcardlin;
+    DevBuf<double> d_lcw, d_lcvec, d_lcpart, d_lcout;   // weights (L x Q); [d | sqrt W | 1 / (d sqrt W)] per leaf; partial sums; mu | var | lpd
 
     // aggregation of the leaf moments per test row + scores (dsmgp_aggregate*, dsmgp_scores)
     DevBuf<int64_t> d_row_ptr;      // n_t + 1: entries of every test row (built by set_test)
@@ -977,6 +990,20 @@ void free_targets(dsmgp_ctx* c) {
     c->tgardlin.release();
     c->d_tgw.release();
     c->d_tgpart.release();
+    arena_put(c, c->arenaHc);
+    arena_put(c, c->arenaU);
+    c->cap_Hc = c->cap_U = 0;
+    c->lcleaf.release();
+    c->lcginv.release();
+    c->lcu.release();
+    c->lcrow.release();
+    c->lcdot.release();
+    c->lcquad.release();
+    c->lcardlin.release();
+    c->d_lcw.release();
+    c->d_lcvec.release();
+    c->d_lcpart.release();
+    c->d_lcout.release();
 }
 
 void free_tree(dsmgp_ctx* c) {
@@ -4348,6 +4375,40 @@ int dsmgp_targets_fetch(dsmgp_ctx* c, int32_t leaf, double* Z_out) {
     return 0;
 }
 
+namespace {
+// An arena of npad x Qpad doubles per leaf at offset toff / 2 (A, U): grown on first use, from the pool when there is one
+// (static, like build_targets_plan: inside extern "C" an unnamed namespace alone still exports the name)
+static int targets_slab(dsmgp_ctx* c, double*& p, size_t& cap, const char* what) {
+    size_t tot = 0;
+    for (int l = 0; l < c->L; ++l) tot += (size_t)c->leaves[l].npad * (size_t)c->tg_qpad;
+    if (int rc = slab_grow(c, p, cap, tot)) {
+        (void)hipGetLastError();
+        return rc == DSMGP_E_NOMEM ? rc : fail(c, DSMGP_E_NOMEM, std::string(what) + " (" + std::to_string((tot * 8) >> 20) + " MiB)");
+    }
+    return 0;
+}
+// The tasks of A = L^-T Z (targets_a_kernel), one per 128-row block of every leaf; arenaA must be there
+static void targets_a_tasks(const dsmgp_ctx* c, std::vector<TargetsATask>& ta) {
+    ta.clear();
+    for (int l = 0; l < c->L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        const double* Xt = c->arenaX + c->gxoff[(size_t)lf.owner];
+        for (int i = 0; i < lf.nb; ++i) {
+            TargetsATask t{};
+            t.Xt = Xt + (size_t)i * TB;
+            t.Z = c->arenaT + c->toff[(size_t)l] + (size_t)lf.npad * c->tg_qpad;
+            t.A = c->arenaA + c->toff[(size_t)l] / 2 + (size_t)i * TB;
+            t.ldt = c->leaves[lf.owner].npad;
+            t.ldz = lf.npad;
+            t.k0 = i * TB;
+            t.n = lf.n;
+            t.nrows = std::max(0, std::min(TB, lf.n - i * TB));
+            ta.push_back(t);
+        }
+    }
+}
+}  // namespace
+
 // Hyper-parameter gradients of sum_q w_lq mll_lq over the resident target columns (kernels_targets.hpp at targets_a_kernel):
 // one inversion -- or none, when the arena holds L^-T of this fit (dsmgp_loo's rule) -- and one contraction per leaf whatever Q is,
 // plus O(n^2 Q) for A = L^-T Z and the rank-Q term.  Every leaf has tasks of its own (a COPY leaf reads its source's L^-T with its
@@ -4380,39 +4441,24 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     // L^-T of every factor owner (xinv_lists / xinv_fill); lists of the call's own are dropped again on every way out
     OwnGradLists own_lists{c};
     if (int rc = xinv_lists(c, own_lists)) return rc;
-    size_t atot = 0;
-    for (int l = 0; l < L; ++l) atot += (size_t)c->leaves[l].npad * (size_t)qpad;
-    if (int rc = slab_grow(c, c->arenaA, c->cap_A, atot)) {
-        (void)hipGetLastError();
-        return rc == DSMGP_E_NOMEM ? rc : fail(c, DSMGP_E_NOMEM, "targets_gradients: no room for A = L^-T Z (" + std::to_string((atot * 8) >> 20) + " MiB)");
-    }
+    if (int rc = targets_slab(c, c->arenaA, c->cap_A, "targets_gradients: no room for A = L^-T Z")) return rc;
     const int gs = any_rq(c) ? 3 + D : (any_ard || any_prod) ? 2 + D : 2;
     auto Xt = [&](int l) { return c->arenaX + c->gxoff[(size_t)c->leaves[l].owner]; };
     auto Al = [&](int l) { return c->arenaA + c->toff[(size_t)l] / 2; };
     std::vector<TargetsATask> ta;
+    targets_a_tasks(c, ta);
     std::vector<FrobTask> frob;
     std::vector<int> frob_leaf;
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
-        const int ldt = c->leaves[lf.owner].npad;
+        if (lf.owner != l) continue;
         for (int i = 0; i < lf.nb; ++i) {
-            TargetsATask t{};
-            t.Xt = Xt(l) + (size_t)i * TB;
-            t.Z = c->arenaT + c->toff[(size_t)l] + (size_t)lf.npad * qpad;
-            t.A = Al(l) + (size_t)i * TB;
-            t.ldt = ldt;
-            t.ldz = lf.npad;
-            t.k0 = i * TB;
-            t.n = lf.n;
-            t.nrows = std::max(0, std::min(TB, lf.n - i * TB));
-            ta.push_back(t);
-            if (lf.owner != l) continue;
             FrobTask f{};
             f.X = Xt(l) + (size_t)i * TB;
             f.ld = lf.npad;
             f.col0 = i * TB;
             f.col1 = lf.npad;
-            f.nrows = t.nrows;
+            f.nrows = std::max(0, std::min(TB, lf.n - i * TB));
             f.n = lf.n;
             frob.push_back(f);
             frob_leaf.push_back(l);
@@ -4620,6 +4666,30 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
 // the bit and everything that call promises about dsmgp_gradients and the mask holds here too; then the passes of this call's
 // own lists over an arena of their own.  Nothing the gradient pass or dsmgp_loo reads is written.
 namespace {
+// The lower tiles (i, j) of a leaf in the super-tile order of build_grad_plan (GS x GS tiles per super-tile), the start of every
+// block of GS tile rows marked in `gblock`; and the XCD dealing of the tasks listed that way, by the length of their K range.
+constexpr int LOO_GS = 4;
+extern "C++" {      // (templates cannot have C linkage)
+template <class SizeNow, class Emit>
+void each_lower_tile(const LeafHost& lf, std::vector<size_t>& gblock, size_t begin, SizeNow&& size_now, Emit&& emit) {
+    constexpr int GS = LOO_GS;
+    for (int ib = 0; ib < lf.nb; ib += GS) {
+        gblock.push_back(size_now() - begin);
+        for (int jb = 0; jb <= ib; jb += GS)
+            for (int i = ib; i < std::min(ib + GS, lf.nb); ++i)
+                for (int j = jb; j < std::min(jb + GS, i + 1); ++j)
+                    emit(i, j, std::max(0, std::min(TB, lf.n - i * TB)), std::max(0, std::min(TB, lf.n - j * TB)));
+    }
+}
+template <class Tasks>
+void deal_tiles(dsmgp_ctx* c, Tasks& tasks, std::vector<int>& leaf_of, size_t begin, std::vector<size_t>& gblock) {
+    gblock.push_back(tasks.size() - begin);
+    std::vector<double> work(tasks.size() - begin);
+    for (size_t i = 0; i < work.size(); ++i) work[i] = (double)(tasks[begin + i].gemm.k1 - tasks[begin + i].gemm.k0) + 64.0;
+    xcd_deal_by_work(tasks, leaf_of, begin, tasks.size(), gblock, work, c->xcd_order);
+}
+}  // extern "C++"
+
 int build_loo_grad_plan(dsmgp_ctx* c) {
     const int L = c->L;
     const int D = c->D;
@@ -4670,31 +4740,14 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
             c->lghvec_leaf.push_back(l);
         }
     }
-    // tiles of G, then of the contraction: the super-tile order and the XCD dealing of build_grad_plan.  `each_tile` lists the
-    // lower tiles (i, j) of a leaf in that order and marks the start of every block of GS tile rows.
-    constexpr int GS = 4;
-    auto each_tile = [&](const LeafHost& lf, std::vector<size_t>& gblock, size_t begin, auto&& size_now, auto&& emit) {
-        for (int ib = 0; ib < lf.nb; ib += GS) {
-            gblock.push_back(size_now() - begin);
-            for (int jb = 0; jb <= ib; jb += GS)
-                for (int i = ib; i < std::min(ib + GS, lf.nb); ++i)
-                    for (int j = jb; j < std::min(jb + GS, i + 1); ++j)
-                        emit(i, j, std::max(0, std::min(TB, lf.n - i * TB)), std::max(0, std::min(TB, lf.n - j * TB)));
-        }
-    };
-    auto deal = [&](auto& tasks, std::vector<int>& leaf_of, size_t begin, std::vector<size_t>& gblock) {
-        gblock.push_back(tasks.size() - begin);
-        std::vector<double> work(tasks.size() - begin);
-        for (size_t i = 0; i < work.size(); ++i) work[i] = (double)(tasks[begin + i].gemm.k1 - tasks[begin + i].gemm.k0) + 64.0;
-        xcd_deal_by_work(tasks, leaf_of, begin, tasks.size(), gblock, work, c->xcd_order);
-    };
+    // tiles of G, then of the contraction: the super-tile order and the XCD dealing of build_grad_plan
     std::vector<size_t> gblock;
     std::vector<GinvTask> gi;
     std::vector<int> gi_leaf;
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
         if (c->grad_src[l] >= 0) continue;
-        each_tile(lf, gblock, 0, [&] { return gi.size(); }, [&](int i, int j, int na, int nb) {
+        each_lower_tile(lf, gblock, 0, [&] { return gi.size(); }, [&](int i, int j, int na, int nb) {
             GinvTask g{};
             g.gemm.A = Xt(l) + (size_t)i * TB;
             g.gemm.B = Xt(l) + (size_t)j * TB;
@@ -4712,7 +4765,7 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
             gi_leaf.push_back(l);
         });
     }
-    deal(gi, gi_leaf, 0, gblock);
+    deal_tiles(c, gi, gi_leaf, 0, gblock);
     // the contraction, as gdot: IsoSE and ArdSE leaves (pass 0), ArdSEProduct (1), Matern (2), rational quadratic (3), each run
     // by its own kernel
     std::vector<GradTask> gd;
@@ -4730,7 +4783,7 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
             if (!KINDS[kind_l].contraction && kind_l != DSMGP_KIND_ARD_SE) continue;
             if ((kind_l == DSMGP_KIND_ARD_SE_PRODUCT ? 1 : KINDS[kind_l].matern ? 2 : KINDS[kind_l].rq ? 3 : 0) != pass) continue;
             const LeafDev& d = c->h_leaves[l];
-            each_tile(lf, gblock, begin, [&] { return gd.size(); }, [&](int i, int j, int na, int nb) {
+            each_lower_tile(lf, gblock, begin, [&] { return gd.size(); }, [&](int i, int j, int na, int nb) {
                 GradTask g{};
                 g.gemm.A = H(l) + (size_t)i * TB;
                 g.gemm.B = H(l) + (size_t)j * TB;
@@ -4753,7 +4806,7 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
                 c->lgdot_leaf.push_back(l);
             });
         }
-        deal(gd, c->lgdot_leaf, begin, gblock);
+        deal_tiles(c, gd, c->lgdot_leaf, begin, gblock);
     }
     std::vector<ArdLinTask> al;
     c->lgardlin_leaf.clear();
@@ -4784,6 +4837,43 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
     for (const HyperHost& h : c->hyper) c->lg_kinds.push_back(h.kind);
     c->lg_ready = true;
     return 0;
+}
+
+// The per-kind assembly of one leaf's row from the sums of the LOO passes (dsmgp_loo_gradients, dsmgp_loo_columns_gradients):
+// every slot the true derivative sum_rc M_rc (dK_y / dtheta)_rc.  S1 / SK / Sd / Sa: M contracted with K r^2, K, dK / dlog l_d and
+// dK / dlog alpha; xMx the ArdLinear forms x_d^T M x_d; trM and trMKy = tr(M K_y) from their identities.
+struct LooSums {
+    double S1, SK, Sa, trM, trMKy;
+    const double* Sd;       // D sums
+    const double* xMx;      // D forms, or null when the leaf is not ArdLinear
+};
+static void assemble_loo_gradient(const dsmgp_ctx* c, const HyperHost& h, const LooSums& q, double* g) {
+    const int D = c->D;
+    const int nl = n_lengthscales(h.kind, h.loghyp.size());
+    const int ns = nl + KINDS[h.kind].n_shape;                // the slot of logs; logNoise behind it
+    const double noise = std::exp(2.0 * h.loghyp[ns + 1]);
+    const double cc = noise + 1e-8;
+    if (h.kind == DSMGP_KIND_ISO_SE) {
+        g[0] = q.S1 / std::exp(2.0 * h.loghyp[0]);            // dK / dlog l = K r^2 / l^2
+        g[1] = 2.0 * q.SK;                                    // dK / dlog sigma = 2 K, contracted directly
+    } else if (h.kind == DSMGP_KIND_ISO_LINEAR) {
+        g[0] = -2.0 * (q.trMKy - cc * q.trM);                 // dK / dlog l = -2 K; sum M K = tr(M K_y) - c tr M
+        g[1] = 0.0;
+    } else if (h.kind == DSMGP_KIND_ARD_LINEAR) {
+        for (int d = 0; d < nl; ++d) g[d] = -2.0 * q.xMx[d] / std::exp(2.0 * h.loghyp[d]);
+        g[nl] = 0.0;
+    } else {                                                  // ArdSE, ArdSEProduct, Matern, rational quadratic: per-dimension sums
+        if (KINDS[h.kind].iso_matern) {
+            double sl = 0.0;
+            for (int d = 0; d < D; ++d) sl += q.Sd[d];
+            g[0] = sl;
+        } else {
+            for (int d = 0; d < nl; ++d) g[d] = q.Sd[d];
+        }
+        if (KINDS[h.kind].rq) g[nl] = q.Sa;                   // sum M dK / dlog alpha
+        g[ns] = 2.0 * q.SK;
+    }
+    g[ns + 1] = 2.0 * noise * q.trM;
 }
 }  // namespace
 
@@ -4870,46 +4960,404 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
             }
         }
     }
+    std::vector<double> xMx((size_t)D, 0.0);
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
         const HyperHost& h = c->hyper[lf.kid];
         const size_t s = (size_t)(c->grad_src[l] >= 0 ? c->grad_src[l] : l);      // a COPY leaf with its source's mean: the source's
-        const int nl = n_lengthscales(h.kind, h.loghyp.size());
-        const int ns = nl + KINDS[h.kind].n_shape;                // the slot of logs; logNoise behind it
-        const double noise = std::exp(2.0 * h.loghyp[ns + 1]);
-        const double cc = noise + 1e-8;
         double* g = grad_out + (size_t)l * stride;
         for (int j = 0; j < stride; ++j) g[j] = 0.0;
         if (std::isnan(lpd[l])) {       // the fit of this leaf failed (info != 0)
-            for (int j = 0; j < ns + 2; ++j) g[j] = std::nan("");
+            for (size_t j = 0; j < h.loghyp.size(); ++j) g[j] = std::nan("");
             continue;
         }
-        const double trM = ua[s] - frob[s];                       // tr M = u . alpha - |H|_F^2
-        const double trMKy = hw[2 * s] - hw[2 * s + 1];           // tr(M K_y) = sum alpha_i^2 / d_i - sum w_i d_i
-        if (h.kind == DSMGP_KIND_ISO_SE) {
-            g[0] = S1[s] / std::exp(2.0 * h.loghyp[0]);           // dK / dlog l = K r^2 / l^2
-            g[1] = 2.0 * SK[s];                                   // dK / dlog sigma = 2 K, contracted directly
-        } else if (h.kind == DSMGP_KIND_ISO_LINEAR) {
-            g[0] = -2.0 * (trMKy - cc * trM);                     // dK / dlog l = -2 K; sum M K = tr(M K_y) - c tr M
-            g[1] = 0.0;
-        } else if (h.kind == DSMGP_KIND_ARD_LINEAR) {
-            for (int d = 0; d < nl; ++d)                          // x_d^T M x_d = (x_d . u)(x_d . alpha) - |H^T x_d|^2
-                g[d] = -2.0 * (U[s * D + d] * A[s * D + d] - Q[s * D + d]) / std::exp(2.0 * h.loghyp[d]);
-            g[nl] = 0.0;
-        } else {                                                  // ArdSE, ArdSEProduct, Matern, rational quadratic: per-dimension sums
-            if (KINDS[h.kind].iso_matern) {
-                double sl = 0.0;
-                for (int d = 0; d < D; ++d) sl += Sd[s * D + d];
-                g[0] = sl;
-            } else {
-                for (int d = 0; d < nl; ++d) g[d] = Sd[s * D + d];
-            }
-            if (KINDS[h.kind].rq) g[nl] = Sa[s];                  // sum M dK / dlog alpha
-            g[ns] = 2.0 * SK[s];
+        LooSums q{};
+        q.S1 = S1[s];
+        q.SK = SK[s];
+        q.Sa = Sa[s];
+        q.Sd = Sd.data() + s * D;
+        q.trM = ua[s] - frob[s];                                  // tr M = u . alpha - |H|_F^2
+        q.trMKy = hw[2 * s] - hw[2 * s + 1];                      // tr(M K_y) = sum alpha_i^2 / d_i - sum w_i d_i
+        if (h.kind == DSMGP_KIND_ARD_LINEAR) {
+            for (int d = 0; d < D; ++d)                           // x_d^T M x_d = (x_d . u)(x_d . alpha) - |H^T x_d|^2
+                xMx[d] = U[s * D + d] * A[s * D + d] - Q[s * D + d];
+            q.xMx = xMx.data();
         }
-        g[ns + 1] = 2.0 * noise * trM;
+        assemble_loo_gradient(c, h, q, g);
     }
     if (lpd_out) std::memcpy(lpd_out, lpd.data(), (size_t)L * sizeof(double));
+    return 0;
+}
+
+// Leave-one-out moments and gradients of the resident target columns (the kernels and the formulas: kernels_targets.hpp at
+// LooColsTask).  d and L^-T come by dsmgp_loo's rule (xinv_lists / xinv_fill, the row sums by rownorm_kernel over that call's own
+// lists), A by the kernel and the tasks of dsmgp_mll_columns_gradients.  Every leaf has tasks of its own: a COPY leaf reads its
+// source's d and L^-T with its own A, mean and weights.  H, U, the vectors, the lists and the sums live in buffers of these two
+// entry points: nothing another entry point reads is written, and the mask of dsmgp_set_gradient_leaves neither applies nor changes.
+namespace {
+// What both calls need before their own kernels: the lists of the inversion and of the row sums, A's arena and its tasks
+static int loo_columns_prepare(dsmgp_ctx* c, OwnGradLists& own) {
+    if (int rc = xinv_lists(c, own)) return rc;
+    if (!c->loo_ready)
+        if (int rc = build_loo_plan(c)) return rc;
+    if (int rc = targets_slab(c, c->arenaA, c->cap_A, "loo_columns: no room for A = L^-T Z")) return rc;
+    std::vector<TargetsATask> ta;
+    targets_a_tasks(c, ta);
+    return dev_upload(c, c->tga, ta);
+}
+// ... and queues: L^-T (when the arena does not hold this fit's), the row sums of diag K_y^-1, A
+static int loo_columns_front(dsmgp_ctx* c) {
+    if (int rc = ensure_dinv(c)) return rc;
+    if (int rc = xinv_fill(c)) return rc;
+    if (c->lrow.count) rownorm_kernel<<<(unsigned)c->lrow.count, 256, 0, c->stream>>>(c->lrow.p);
+    if (c->tga.count) targets_a_kernel<<<(unsigned)c->tga.count, 256, 0, c->stream>>>(c->tga.p, c->tg_qpad);
+    return 0;
+}
+}  // namespace
+
+int dsmgp_loo_columns(dsmgp_ctx* c, double* mu_out, int64_t ld, double* var_out, double* lpd_out, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "loo_columns before solve_targets on the current fit");
+    const int L = c->L, Q = c->tg_Q;
+    const size_t nobs = (size_t)c->obs_ptr[L];
+    if (mu_out && ld < (int64_t)nobs) return fail(c, DSMGP_E_ARG, "loo_columns: ld < obs_ptr[L]");
+    HIPCHK(c, hipSetDevice(c->device));
+    OwnGradLists own_lists{c};
+    if (int rc = loo_columns_prepare(c, own_lists)) return rc;
+    std::vector<LooColsTask> lt((size_t)L);
+    for (int l = 0; l < L; ++l) {
+        lt[(size_t)l].A = c->arenaA + c->toff[(size_t)l] / 2;
+        lt[(size_t)l].npad = c->leaves[l].npad;
+        lt[(size_t)l].Q = Q;
+    }
+    if (int rc = dev_upload(c, c->lcleaf, lt)) return rc;
+    if (int rc = c->d_lcout.grow(c, nobs * (size_t)Q + nobs + (size_t)L * Q)) return rc;
+    double* dmu = c->d_lcout.p;
+    double* dvar = dmu + nobs * (size_t)Q;
+    double* dlpd = dvar + nobs;
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    if (int rc = loo_columns_front(c)) return rc;
+    loo_columns_moments_kernel<<<dim3((unsigned)L, (unsigned)Q), 256, 0, c->stream>>>(
+        c->d_leaves.p, c->lleaf.p, c->lcleaf.p, c->d_obs_idx.p, c->d_tY.p, c->N, L, dmu, (long long)nobs, dvar, dlpd);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->xinv_all = true;
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = ms * 1e-3;
+    if (mu_out && nobs)
+        HIPCHK(c, hipMemcpy2D(mu_out, (size_t)ld * sizeof(double), dmu, nobs * sizeof(double), nobs * sizeof(double), (size_t)Q,
+                              hipMemcpyDeviceToHost));
+    if (var_out) HIPCHK(c, hipMemcpy(var_out, dvar, nobs * sizeof(double), hipMemcpyDeviceToHost));
+    if (lpd_out) HIPCHK(c, hipMemcpy(lpd_out, dlpd, (size_t)L * Q * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, const double* col_weight, double* lpd_out,
+                                double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "loo_columns_gradients before solve_targets on the current fit");
+    if (!grad_out) return fail(c, DSMGP_E_ARG, "loo_columns_gradients: grad_out is NULL");
+    const int L = c->L, Q = c->tg_Q, qpad = c->tg_qpad, D = c->D;
+    bool any_ardse = false;
+    for (int l = 0; l < L; ++l) {
+        const HyperHost& h = c->hyper[c->leaves[l].kid];
+        if ((int)h.loghyp.size() > stride) return fail(c, DSMGP_E_ARG, "loo_columns_gradients: stride smaller than the hyper-vector");
+        any_ardse = any_ardse || h.kind == DSMGP_KIND_ARD_SE;
+    }
+    if (any_ardse && D > GRADDOT_STAGE_D)
+        return fail(c, DSMGP_E_ARG, "loo_columns_gradients: ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
+    std::vector<double> W((size_t)L * Q, 1.0), sw((size_t)L, 0.0);
+    if (col_weight)
+        for (size_t i = 0; i < W.size(); ++i) {
+            if (!std::isfinite(col_weight[i]) || col_weight[i] < 0.0)
+                return fail(c, DSMGP_E_ARG, "loo_columns_gradients: non-finite or negative value in col_weight");
+            W[i] = col_weight[i];
+        }
+    for (int l = 0; l < L; ++l)
+        for (int q = 0; q < Q; ++q) sw[(size_t)l] += W[(size_t)l + (size_t)q * L];
+    auto active = [&](int l) { return sw[(size_t)l] > 0.0; };      // a row of zero weights: a row of zeros and no tasks
+    HIPCHK(c, hipSetDevice(c->device));
+    OwnGradLists own_lists{c};
+    if (int rc = loo_columns_prepare(c, own_lists)) return rc;
+    if (int rc = targets_slab(c, c->arenaU, c->cap_U, "loo_columns_gradients: no room for U = K_y^-1 (A / d)")) return rc;
+    std::vector<size_t> hoff((size_t)L, 0), voff((size_t)L, 0);
+    size_t hTot = 0, vTot = 0;
+    for (int l = 0; l < L; ++l) {
+        hoff[(size_t)l] = hTot;
+        voff[(size_t)l] = vTot;
+        hTot += (size_t)c->leaves[l].npad * c->leaves[l].npad;
+        vTot += 3 * (size_t)c->leaves[l].npad;
+    }
+    if (int rc = slab_grow(c, c->arenaHc, c->cap_Hc, hTot)) {
+        (void)hipGetLastError();
+        return rc == DSMGP_E_NOMEM ? rc : fail(c, DSMGP_E_NOMEM, "loo_columns_gradients: no room for K_y^-1 (" + std::to_string((hTot * 8) >> 20) + " MiB)");
+    }
+    if (int rc = c->d_lcvec.grow(c, std::max<size_t>(1, vTot))) return rc;
+    if (int rc = c->d_lcw.grow(c, W.size())) return rc;
+    auto H = [&](int l) { return c->arenaHc + hoff[(size_t)l]; };
+    auto V = [&](int l) { return c->d_lcvec.p + voff[(size_t)l]; };
+    auto Al = [&](int l) { return c->arenaA + c->toff[(size_t)l] / 2; };
+    auto Ul = [&](int l) { return c->arenaU + c->toff[(size_t)l] / 2; };
+    auto Xt = [&](int l) { return c->arenaX + c->gxoff[(size_t)c->leaves[l].owner]; };
+    const double* wdev = c->d_lcw.p;
+
+    std::vector<LooColsTask> lt((size_t)L);
+    std::vector<LooColsUTask> ut;
+    std::vector<LooColsRowTask> rt;
+    std::vector<int> rt_leaf;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        LooColsTask& t = lt[(size_t)l];
+        t.A = Al(l);
+        t.vec = active(l) ? V(l) : nullptr;
+        t.wq = wdev + l;
+        t.s = sw[(size_t)l];
+        t.npad = lf.npad;
+        t.ldw = L;
+        t.Q = Q;
+        if (!active(l)) continue;
+        for (int i = 0; i * TB < lf.n; ++i) {
+            const int nrows = std::min(TB, lf.n - i * TB);
+            LooColsUTask u{};
+            u.H = H(l) + (size_t)i * TB;
+            u.A = Al(l);
+            u.tq = V(l) + 2 * (size_t)lf.npad;
+            u.U = Ul(l) + (size_t)i * TB;
+            u.ld = lf.npad;
+            u.n = lf.n;
+            u.nrows = nrows;
+            ut.push_back(u);
+            LooColsRowTask r{};
+            r.H = H(l);
+            r.A = Al(l);
+            r.U = Ul(l);
+            r.wq = wdev + l;
+            r.ld = lf.npad;
+            r.ldw = L;
+            r.n = lf.n;
+            r.Q = Q;
+            r.row0 = i * TB;
+            r.nrows = nrows;
+            rt.push_back(r);
+            rt_leaf.push_back(l);
+        }
+    }
+    // tiles of H, then of the contraction, in the order and the dealing of dsmgp_loo_gradients
+    std::vector<size_t> gblock;
+    std::vector<GinvTask> gi;
+    std::vector<int> gi_leaf;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (!active(l)) continue;
+        const int ldt = c->leaves[lf.owner].npad;
+        each_lower_tile(lf, gblock, 0, [&] { return gi.size(); }, [&](int i, int j, int na, int nb) {
+            GinvTask g{};
+            g.gemm.A = Xt(l) + (size_t)i * TB;
+            g.gemm.B = Xt(l) + (size_t)j * TB;
+            g.gemm.C = H(l) + (size_t)i * TB + (size_t)j * TB * lf.npad;
+            g.Ct = H(l) + (size_t)j * TB + (size_t)i * TB * lf.npad;
+            g.gemm.lda = g.gemm.ldb = ldt;
+            g.gemm.ldc = lf.npad;
+            g.gemm.k0 = i * TB;
+            g.gemm.k1 = lf.npad;
+            g.sw_a = V(l) + (size_t)lf.npad + (size_t)i * TB;
+            g.sw_b = V(l) + (size_t)lf.npad + (size_t)j * TB;
+            g.na = na;
+            g.nb = nb;
+            g.diag = (i == j);
+            gi.push_back(g);
+            gi_leaf.push_back(l);
+        });
+    }
+    deal_tiles(c, gi, gi_leaf, 0, gblock);
+    std::vector<GradTaskLc> gd;
+    std::vector<int> gd_leaf;
+    size_t first[5] = {0, 0, 0, 0, 0};
+    for (int pass = 0; pass < 4; ++pass) {
+        first[pass] = gd.size();
+        const size_t begin = gd.size();
+        gblock.clear();
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            if (!active(l)) continue;
+            const int kind_l = c->hyper[lf.kid].kind;
+            if (!KINDS[kind_l].contraction && kind_l != DSMGP_KIND_ARD_SE) continue;
+            if ((kind_l == DSMGP_KIND_ARD_SE_PRODUCT ? 1 : KINDS[kind_l].matern ? 2 : KINDS[kind_l].rq ? 3 : 0) != pass) continue;
+            const LeafDev& d = c->h_leaves[l];
+            each_lower_tile(lf, gblock, begin, [&] { return gd.size(); }, [&](int i, int j, int na, int nb) {
+                GradTaskLc g{};
+                g.gemm.A = H(l) + (size_t)i * TB;
+                g.gemm.B = H(l) + (size_t)j * TB;
+                g.gemm.C = nullptr;
+                g.gemm.lda = g.gemm.ldb = lf.npad;
+                g.gemm.ldc = TB;
+                g.gemm.k0 = 0;
+                g.gemm.k1 = lf.npad;
+                g.xa = d.Xg + (size_t)i * TB;
+                g.xb = d.Xg + (size_t)j * TB;
+                g.alpha_a = V(l) + (size_t)i * TB;      // staged by the epilogues, never in a weight: any vector of the leaf serves
+                g.alpha_b = V(l) + (size_t)j * TB;
+                g.ldx = lf.npad;
+                g.na = na;
+                g.nb = nb;
+                g.diag = (i == j);
+                g.kid = lf.kid;
+                g.Aa = Al(l) + (size_t)i * TB;
+                g.Ab = Al(l) + (size_t)j * TB;
+                g.Ua = Ul(l) + (size_t)i * TB;
+                g.Ub = Ul(l) + (size_t)j * TB;
+                g.wq = wdev + l;
+                g.lda_t = lf.npad;
+                g.ldw = L;
+                g.Q = Q;
+                g.qpad = qpad;
+                gd.push_back(g);
+                gd_leaf.push_back(l);
+            });
+        }
+        deal_tiles(c, gd, gd_leaf, begin, gblock);
+    }
+    first[4] = gd.size();
+    // ArdLinear leaves: |H^T x_d|^2 by ardlin_quad_kernel<true> (its two vector sums are not used: any block of the leaf serves) and
+    // the weighted products of x_d . u_q and x_d . a_q
+    std::vector<ArdLinTask> quad;
+    std::vector<int> quad_leaf;
+    std::vector<LooColsArdLinTask> al;
+    std::vector<int> al_leaf;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR || !active(l)) continue;
+        const LeafDev& d = c->h_leaves[l];
+        for (int c0 = 0; c0 < lf.n; c0 += ARDLIN_COLS) {
+            ArdLinTask a{};
+            a.Xt = H(l);
+            a.x = d.Xg;
+            a.alpha = V(l);
+            a.ldt = lf.npad;
+            a.ldx = lf.npad;
+            a.c0 = c0;
+            a.n = lf.n;
+            quad.push_back(a);
+            quad_leaf.push_back(l);
+        }
+        LooColsArdLinTask t{};
+        t.A = Al(l);
+        t.U = Ul(l);
+        t.x = d.Xg;
+        t.wq = wdev + l;
+        t.ld = lf.npad;
+        t.ldw = L;
+        t.n = lf.n;
+        t.Q = Q;
+        al.push_back(t);
+        al_leaf.push_back(l);
+    }
+    HIPCHK(c, hipMemcpy(c->d_lcw.p, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = dev_upload(c, c->lcleaf, lt)) return rc;
+    if (int rc = dev_upload(c, c->lcginv, gi)) return rc;
+    if (int rc = dev_upload(c, c->lcu, ut)) return rc;
+    if (int rc = dev_upload(c, c->lcrow, rt)) return rc;
+    if (int rc = dev_upload(c, c->lcdot, gd)) return rc;
+    if (int rc = dev_upload(c, c->lcquad, quad)) return rc;
+    if (int rc = dev_upload(c, c->lcardlin, al)) return rc;
+    const int gs = 2 + D + (any_rq(c) ? 1 : 0);
+    const size_t npart = 2 * (size_t)L + 2 * rt.size() + (size_t)gs * gd.size() + 3 * (size_t)D * quad.size() + (size_t)D * al.size();
+    if (int rc = c->d_lcpart.grow(c, npart)) return rc;
+    if (int rc = c->d_lcout.grow(c, (size_t)L * Q)) return rc;
+    double* pw = c->d_lcpart.p;
+    double* prow = pw + 2 * (size_t)L;
+    double* pdot = prow + 2 * rt.size();
+    double* pquad = pdot + (size_t)gs * gd.size();
+    double* pal = pquad + 3 * (size_t)D * quad.size();
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    if (int rc = loo_columns_front(c)) return rc;
+    loo_columns_moments_kernel<<<dim3((unsigned)L, (unsigned)Q), 256, 0, c->stream>>>(
+        c->d_leaves.p, c->lleaf.p, c->lcleaf.p, c->d_obs_idx.p, c->d_tY.p, c->N, L, nullptr, 0, nullptr, c->d_lcout.p);
+    loo_columns_weights_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->lleaf.p, c->lcleaf.p, pw);
+    if (!gi.empty()) tile_ginv_kernel<<<(unsigned)gi.size(), 256, 0, c->stream>>>(c->lcginv.p);
+    if (!ut.empty()) loo_columns_u_kernel<<<(unsigned)ut.size(), 256, 0, c->stream>>>(c->lcu.p, qpad);
+    if (!rt.empty()) loo_columns_rowsums_kernel<<<(unsigned)rt.size(), 256, 0, c->stream>>>(c->lcrow.p, prow);
+    if (first[1] > first[0])
+        tile_graddot_kernel<GD_LOO_COLUMNS><<<(unsigned)(first[1] - first[0]), 256, 0, c->stream>>>(c->lcdot.p + first[0], c->d_kp.p, D,
+                                                                                                  pdot + (size_t)gs * first[0], gs);
+    if (first[2] > first[1])
+        tile_graddot_prod_kernel<GD_LOO_COLUMNS><<<(unsigned)(first[2] - first[1]), 256, 0, c->stream>>>(c->lcdot.p + first[1], c->d_kp.p, D,
+                                                                                                       pdot + (size_t)gs * first[1], gs);
+    if (first[3] > first[2])
+        tile_graddot_matern_kernel<GD_LOO_COLUMNS><<<(unsigned)(first[3] - first[2]), 256, 0, c->stream>>>(c->lcdot.p + first[2], c->d_kp.p, D,
+                                                                                                         pdot + (size_t)gs * first[2], gs);
+    if (first[4] > first[3])
+        tile_graddot_rq_kernel<GD_LOO_COLUMNS><<<(unsigned)(first[4] - first[3]), 256, 0, c->stream>>>(c->lcdot.p + first[3], c->d_kp.p, D,
+                                                                                                     pdot + (size_t)gs * first[3], gs);
+    if (!quad.empty())
+        ardlin_quad_kernel<true><<<dim3((unsigned)quad.size(), (unsigned)((D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
+            c->lcquad.p, D, pquad);
+    if (!al.empty()) loo_columns_ardlin_kernel<<<dim3((unsigned)al.size(), (unsigned)D), 256, 0, c->stream>>>(c->lcardlin.p, D, pal);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->xinv_all = true;
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = ms * 1e-3;
+    std::vector<double> part(std::max<size_t>(1, npart));
+    HIPCHK(c, hipMemcpy(part.data(), c->d_lcpart.p, npart * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<int> info((size_t)L);
+    HIPCHK(c, hipMemcpy(info.data(), c->d_info.p, (size_t)L * sizeof(int), hipMemcpyDeviceToHost));
+    // host assembly: the task sums of a leaf are added in list order (fixed: bit-reproducible)
+    const double* hw = part.data();
+    const double* hr = hw + 2 * (size_t)L;
+    const double* hd = hr + 2 * rt.size();
+    const double* hq = hd + (size_t)gs * gd.size();
+    const double* ha = hq + 3 * (size_t)D * quad.size();
+    std::vector<double> frob((size_t)L, 0.0), ua((size_t)L, 0.0), S1((size_t)L, 0.0), SK((size_t)L, 0.0), Sd((size_t)L * D, 0.0),
+        Sa((size_t)L, 0.0), xMx((size_t)L * D, 0.0);
+    for (size_t i = 0; i < rt.size(); ++i) {
+        frob[(size_t)rt_leaf[i]] += hr[2 * i];
+        ua[(size_t)rt_leaf[i]] += hr[2 * i + 1];
+    }
+    for (size_t i = 0; i < gd.size(); ++i) {
+        const size_t l = (size_t)gd_leaf[i];
+        S1[l] += hd[gs * i];
+        SK[l] += hd[gs * i + 1];
+        const int kind_l = c->hyper[c->leaves[l].kid].kind;      // IsoSE tasks write no per-dimension sums
+        if (kind_l == DSMGP_KIND_ARD_SE || KINDS[kind_l].per_dim_grad)
+            for (int d = 0; d < D; ++d) Sd[l * D + d] += hd[gs * i + 2 + d];
+        if (KINDS[kind_l].rq) Sa[l] += hd[gs * i + 2 + D];
+    }
+    for (size_t i = 0; i < al.size(); ++i)
+        for (int d = 0; d < D; ++d) xMx[(size_t)al_leaf[i] * D + d] = ha[i * D + d];
+    for (size_t i = 0; i < quad.size(); ++i)                      // x_d^T M x_d = sum_q c_q (x_d . u_q)(x_d . a_q) - |H^T x_d|^2
+        for (int d = 0; d < D; ++d) xMx[(size_t)quad_leaf[i] * D + d] -= hq[3 * (size_t)D * i + D + d];
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        const HyperHost& h = c->hyper[lf.kid];
+        double* g = grad_out + (size_t)l * stride;
+        for (int j = 0; j < stride; ++j) g[j] = 0.0;
+        if (info[(size_t)lf.owner] != 0) {
+            for (size_t j = 0; j < h.loghyp.size(); ++j) g[j] = std::nan("");
+            continue;
+        }
+        if (!active(l)) continue;
+        LooSums q{};
+        q.S1 = S1[(size_t)l];
+        q.SK = SK[(size_t)l];
+        q.Sa = Sa[(size_t)l];
+        q.Sd = Sd.data() + (size_t)l * D;
+        q.xMx = xMx.data() + (size_t)l * D;
+        q.trM = ua[(size_t)l] - frob[(size_t)l];                  // tr M = sum_q c_q u_q . a_q - |H|_F^2
+        q.trMKy = hw[2 * l] - hw[2 * l + 1];                      // tr(M K_y) = sum_q c_q sum_i a_iq^2 / d_i - sum_i W_i d_i
+        assemble_loo_gradient(c, h, q, g);
+    }
+    if (lpd_out) HIPCHK(c, hipMemcpy(lpd_out, c->d_lcout.p, (size_t)L * Q * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1240,7 +1240,7 @@ struct GradTask {
     int uoff;               // LOO contraction (MODE == GD_LOO): u of the rows / columns = alpha_a / alpha_b + uoff; else unused
 };
 
-// The three objectives the contraction kernels serve (their template argument MODE).
+// The objectives the contraction kernels serve (their template argument MODE); the fourth, GD_LOO_COLUMNS, is defined with its task below.
 constexpr int GD_MLL = 0;       // log marginal likelihood of the context's y (dsmgp_gradients)
 constexpr int GD_LOO = 1;       // leave-one-out density (dsmgp_loo_gradients)
 constexpr int GD_TARGETS = 2;   // weighted sum of the log marginal likelihoods of the target columns (dsmgp_mll_columns_gradients)
@@ -1254,16 +1254,31 @@ struct GradTaskTg : GradTask {
     double sw;              // s_l = sum_q w_lq
     int lda_t, ldw, Q, qpad;
 };
+// Weighted sum of the leave-one-out densities of the target columns (dsmgp_loo_columns_gradients): the LOO contraction of the
+// leaf's H tiles plus the row blocks of A and of U = K_y^-1 (A / d) and the leaf's row of column weights.
+constexpr int GD_LOO_COLUMNS = 3;
+struct GradTaskLc : GradTask {
+    const double* Aa;       // rows of tile i of A (128 x qpad, ld = lda_t)
+    const double* Ab;       // rows of tile j
+    const double* Ua;       // rows of tile i of U (same layout)
+    const double* Ub;
+    const double* wq;       // weight of column q at wq[q * ldw]
+    int lda_t, ldw, Q, qpad;
+};
 template <int MODE>
-using graddot_task_t = std::conditional_t<MODE == GD_TARGETS, GradTaskTg, GradTask>;
+using graddot_task_t = std::conditional_t<MODE == GD_TARGETS, GradTaskTg, std::conditional_t<MODE == GD_LOO_COLUMNS, GradTaskLc, GradTask>>;
+// The modes whose weight matrix M contracts with dK itself: true derivatives in every slot, out[1] = sum_rc weight_rc K_rc with
+// the kernel value recovered from the weight, off-diagonal tiles counted twice there too.
+constexpr bool gd_loo_density(int mode) { return mode == GD_LOO || mode == GD_LOO_COLUMNS; }
 
 // The weight an accumulator element G_rc is contracted with.  Marginal likelihood: alpha_r alpha_c - G_rc with G = K_y^-1.
 // Leave-one-out density (dsmgp_loo_gradients, GPML eq. 5.13): (u_r alpha_c + alpha_r u_c) / 2 - G_rc with G = H H^T.
 // Targets: the accumulators already hold s G - A_i diag(w) A_j^T (graddot_targets_acc), and the weight is their negative.
+// LOO of the columns: they hold H H^T - (U_i diag(c) A_j^T + A_i diag(c) U_j^T) / 2 (graddot_loo_columns_acc), negated likewise.
 template <int MODE>
 __device__ __forceinline__ double graddot_weight(double ar, double ac, double ur, double uc, double acc) {
     if constexpr (MODE == GD_LOO) return 0.5 * fma(ur, ac, ar * uc) - acc;
-    else if constexpr (MODE == GD_TARGETS) return -acc;
+    else if constexpr (MODE == GD_TARGETS || MODE == GD_LOO_COLUMNS) return -acc;
     else return ar * ac - acc;
 }
 
@@ -1325,6 +1340,53 @@ __device__ __forceinline__ void graddot_targets_acc(const GradTaskTg& g, d4 (&ac
     __syncthreads();
 }
 
+// LOO-of-the-columns mode, right after gemm_mainloop_v2 over H (the ring is free): acc <- acc - (U_i diag(c) A_j^T +
+// A_i diag(c) U_j^T) / 2 by 2 Qpad / 4 MFMA k-steps -- graddot_targets_acc with two operand pairs.  Per chunk of 16 columns the
+// row operands U_i | A_i fill the 32 k-rows of the ring's first half and the column operands A_j | U_j, times -c_q / 2 while
+// staging, those of the second: k-rows 0..15 pair U_i with A_j, 16..31 A_i with U_j.  Chunks in ascending q; rows past the
+// tile's valid rows / columns and columns q >= Q are staged as zeros.  Ends on a barrier: the ring is free again.
+__device__ __forceinline__ void graddot_loo_columns_acc(const GradTaskLc& g, d4 (&acc)[4][4], double* smem) {
+    const int t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
+    double* sa = smem;                          // rows:    sa[k * LDP + r]
+    double* sb = smem + NRING * KC2 * LDP;      // columns: sb[k * LDP + c]
+    static_assert(32 <= NRING * KC2, "two chunks of 16 columns fit one half of the ring");
+    for (int q0 = 0; q0 < g.qpad; q0 += 16) {
+        if (q0) __syncthreads();                // the chunk before has been read
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int e = t + 256 * m, q = e >> 7, r = e & 127;
+            const bool qv = q0 + q < g.Q;
+            const double wv = qv ? -0.5 * g.wq[(size_t)(q0 + q) * g.ldw] : 0.0;
+            const size_t at = r + (size_t)(q0 + q) * g.lda_t;
+            const bool va = qv && r < g.na, vb = qv && r < g.nb;
+            sa[q * LDP + r] = va ? g.Ua[at] : 0.0;
+            sa[(16 + q) * LDP + r] = va ? g.Aa[at] : 0.0;
+            sb[q * LDP + r] = vb ? wv * g.Ab[at] : 0.0;
+            sb[(16 + q) * LDP + r] = vb ? wv * g.Ub[at] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int G = 0; G < 8; ++G) {
+            double fa[4], fb[4];
+            const double* pa = sb + (G * 4 + l4) * LDP + wc * 64 + l15;
+            const double* pb = sa + (G * 4 + l4) * LDP + wr * 64 + l15;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                fa[i] = pa[16 * i];
+                fb[i] = pb[16 * i];
+            }
+#pragma unroll
+            for (int cm = 0; cm < 4; ++cm)
+#pragma unroll
+                for (int rn = 0; rn < 4; ++rn)
+                    acc[cm][rn] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[cm], fb[rn], acc[cm][rn], 0, 0, 0);
+        }
+    }
+    __syncthreads();
+}
+
 // The epilogue is a Gram tile of its own (squared distance + exp per element): the coordinates of the tile's 128 rows
 // and 128 columns and the two alpha blocks are staged once through the LDS the main loop no longer needs (D <= 35;
 // wider inputs read them from global memory, element by element).
@@ -1334,7 +1396,8 @@ constexpr int GRADDOT_STAGE_D = 35;
 // sigma^2 exp(-u_d^2 / 2 l_d^2) * u_d^2 / l_d^2, u_d = x_rd - x_cd -- the contraction with dK / dlog l_d.  2 + D too when an
 // ArdSEProduct or Matern leaf has tasks: out[2 + d] = sum_rc (alpha_r alpha_c - G_rc) dK_rc / dlog l_d.
 // GD_LOO (all four kernels): the weight is graddot_weight<GD_LOO>, u staged next to alpha in 256 doubles of LDS of its own, and
-// out[1] = sum_rc weight_rc K_rc (counted like out[0]) in place of the trace, which that pass does not need.
+// out[1] = sum_rc weight_rc K_rc (counted like out[0]) in place of the trace, which that pass does not need.  GD_LOO_COLUMNS:
+// the same epilogue (gd_loo_density) on the accumulators of graddot_loo_columns_acc; no u is staged.
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const graddot_task_t<MODE>* __restrict__ tasks,
                                                               const KParam* __restrict__ kp, int D,
@@ -1360,6 +1423,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const graddot_task
     const double nh = p.nh0;
     double s = 0.0, tr = 0.0;
     if constexpr (MODE == GD_TARGETS) graddot_targets_acc(g, acc, smem, tr);
+    if constexpr (MODE == GD_LOO_COLUMNS) graddot_loo_columns_acc(g, acc, smem);
     if (p.kind == 1) {
         // additive ArdSE (needs D <= GRADDOT_STAGE_D, checked by the host): one dimension at a time
         double* xs = smem;
@@ -1388,7 +1452,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const graddot_task
                     const double u = a - xb[16 * (i >> 2) + 4 * (i & 3)];
                     const double q = u * u;
                     const double pre = graddot_weight<MODE>(ar, al[TB + c], ur, MODE == GD_LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
-                    if constexpr (MODE == GD_LOO) {
+                    if constexpr (gd_loo_density(MODE)) {
                         if (rv && c < g.nb) {
                             const double pe = pre * exp_nonpos(q * nhd);
                             sd = fma(pe, q, sd);
@@ -1406,7 +1470,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const graddot_task
             if (t == 0)   // u^2 / l_d^2 = -2 nh_d u^2
                 out[(size_t)ostride * blockIdx.x + 2 + d] = wgt * p.sigma2 * (-2.0 * nhd) * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
         }
-        if constexpr (MODE == GD_LOO) {
+        if constexpr (gd_loo_density(MODE)) {
             tr *= p.sigma2;      // sum_rc weight_rc K_rc, K = sigma^2 sum_d exp(...)
         } else if constexpr (MODE == GD_MLL) {
 #pragma unroll
@@ -1456,7 +1520,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const graddot_task
                     const double kv = p.sigma2 * exp_nonpos(z[i] * nh);
                     const double pre = graddot_weight<MODE>(ar, al[TB + c], ur, MODE == GD_LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
                     s = fma(pre * kv, z[i], s);
-                    if constexpr (MODE == GD_LOO) tr += pre * kv;
+                    if constexpr (gd_loo_density(MODE)) tr += pre * kv;
                     else if constexpr (MODE == GD_MLL) {
                         if (g.diag && r == c) tr += acc[i >> 2][rn][i & 3];
                     }
@@ -1483,7 +1547,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const graddot_task
                         const double kv = p.sigma2 * exp_nonpos(z * nh);
                         const double pre = graddot_weight<MODE>(ar, g.alpha_b[c], MODE == GD_LOO ? ul[r] : 0.0, MODE == GD_LOO ? ul[TB + c] : 0.0, acc[cm][rn][q]);
                         s = fma(pre * kv, z, s);
-                        if constexpr (MODE == GD_LOO) tr += pre * kv;
+                        if constexpr (gd_loo_density(MODE)) tr += pre * kv;
                         else if constexpr (MODE == GD_MLL) {
                             if (g.diag && r == c) tr += acc[cm][rn][q];
                         }
@@ -1503,7 +1567,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_kernel(const graddot_task
     if (threadIdx.x == 0) {
         const double wgt = g.diag ? 1.0 : 2.0;
         out[(size_t)ostride * blockIdx.x] = wgt * (red[0][0] + red[0][1] + red[0][2] + red[0][3]);
-        out[(size_t)ostride * blockIdx.x + 1] = (MODE == GD_LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        out[(size_t)ostride * blockIdx.x + 1] = (gd_loo_density(MODE) ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 
@@ -1539,6 +1603,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const graddot
     }
     double tr = 0.0;
     if constexpr (MODE == GD_TARGETS) graddot_targets_acc(g, acc, smem, tr);
+    if constexpr (MODE == GD_LOO_COLUMNS) graddot_loo_columns_acc(g, acc, smem);
     constexpr int CH = GRADDOT_STAGE_D;
     double* xs = smem;
     double* al = smem + (size_t)CH * 256;
@@ -1592,7 +1657,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const graddot
             const int c = wc * 64 + 16 * (i >> 2) + l4 + 4 * (i & 3);
             const double pre = graddot_weight<MODE>(ar, al[TB + c], ur, MODE == GD_LOO ? ul[TB + c] : 0.0, acc[i >> 2][rn][i & 3]);
             acc[i >> 2][rn][i & 3] = (rv && c < g.nb) ? pre * (p.sigma2 * exp_nonpos(z[i])) : 0.0;
-            if constexpr (MODE == GD_LOO) tr += acc[i >> 2][rn][i & 3];
+            if constexpr (gd_loo_density(MODE)) tr += acc[i >> 2][rn][i & 3];
         }
     }
     for (int ch = 0; ch < nch; ++ch) {
@@ -1633,7 +1698,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_prod_kernel(const graddot
     __syncthreads();
     if (threadIdx.x == 0) {
         out[(size_t)ostride * blockIdx.x] = 0.0;
-        out[(size_t)ostride * blockIdx.x + 1] = (MODE == GD_LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        out[(size_t)ostride * blockIdx.x + 1] = (gd_loo_density(MODE) ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 
@@ -1667,6 +1732,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const gradd
     }
     double tr = 0.0;
     if constexpr (MODE == GD_TARGETS) graddot_targets_acc(g, acc, smem, tr);
+    if constexpr (MODE == GD_LOO_COLUMNS) graddot_loo_columns_acc(g, acc, smem);
     constexpr int CH = GRADDOT_STAGE_D;
     double* xs = smem;
     double* al = smem + (size_t)CH * 256;
@@ -1725,7 +1791,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const gradd
             const double s = sqrt(z[i]);
             const double wk = p.sigma2 * exp_nonpos(-s) * fma(c2, s, c1);
             acc[i >> 2][rn][i & 3] = (rv && c < g.nb) ? pre * wk : 0.0;
-            if constexpr (MODE == GD_LOO)        // the kernel value from the weight: K = wk (1 + s + c2 s^2) / c(s), c(s) >= 1/3
+            if constexpr (gd_loo_density(MODE))        // the kernel value from the weight: K = wk (1 + s + c2 s^2) / c(s), c(s) >= 1/3
                 tr = fma(acc[i >> 2][rn][i & 3], fma(fma(c2, s, 1.0), s, 1.0) / fma(c2, s, c1), tr);
         }
     }
@@ -1767,7 +1833,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_matern_kernel(const gradd
     __syncthreads();
     if (threadIdx.x == 0) {
         out[(size_t)ostride * blockIdx.x] = 0.0;
-        out[(size_t)ostride * blockIdx.x + 1] = (MODE == GD_LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        out[(size_t)ostride * blockIdx.x + 1] = (gd_loo_density(MODE) ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 
@@ -1801,6 +1867,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const graddot_t
     }
     double tr = 0.0;
     if constexpr (MODE == GD_TARGETS) graddot_targets_acc(g, acc, smem, tr);
+    if constexpr (MODE == GD_LOO_COLUMNS) graddot_loo_columns_acc(g, acc, smem);
     constexpr int CH = GRADDOT_STAGE_D;
     double* xs = smem;
     double* al = smem + (size_t)CH * 256;
@@ -1860,7 +1927,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const graddot_t
             const double pk = (rv && c < g.nb) ? pre * (p.sigma2 * exp_nonpos(-alpha * lw)) : 0.0;
             sa = fma(pk, z[i] * q - lw, sa);
             acc[i >> 2][rn][i & 3] = pk * q;
-            if constexpr (MODE == GD_LOO) tr += pk;
+            if constexpr (gd_loo_density(MODE)) tr += pk;
         }
     }
     for (int ch = 0; ch < nch; ++ch) {
@@ -1905,7 +1972,7 @@ __global__ __launch_bounds__(256, 2) void tile_graddot_rq_kernel(const graddot_t
     __syncthreads();
     if (threadIdx.x == 0) {
         out[(size_t)ostride * blockIdx.x] = 0.0;
-        out[(size_t)ostride * blockIdx.x + 1] = (MODE == GD_LOO ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        out[(size_t)ostride * blockIdx.x + 1] = (gd_loo_density(MODE) ? wgt : 1.0) * (red[1][0] + red[1][1] + red[1][2] + red[1][3]);
     }
 }
 

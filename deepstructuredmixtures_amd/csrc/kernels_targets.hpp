@@ -363,4 +363,259 @@ __global__ __launch_bounds__(256) void targets_ardlin_kernel(const TargetsArdLin
     if (t == 0) out[(size_t)blockIdx.x * D + d] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Leave-one-out moments and gradients of the target columns (dsmgp_loo_columns, dsmgp_loo_columns_gradients; GPML eqs. 5.10-5.13
+// per column, summed with weights c_q >= 0).  With G = K_y^-1, d = diag G (the row sums of dsmgp_loo), a_q column q of A:
+//   mu_iq = y_iq - a_iq / d_i,  var_i = 1 / d_i,  lpd_q = sum_i -(log 2pi - log d_i + a_iq^2 / d_i) / 2
+//   sum_q c_q dlpd_q / dtheta = sum_rc M_rc (dK_y / dtheta)_rc,  M = sum_q c_q (u_q a_q^T + a_q u_q^T) / 2 - H H^T,
+//   u_q = G (a_q / d),  H = G diag(sqrt W),  W_i = (s + sum_q c_q a_iq^2 / d_i) / (2 d_i),  s = sum_q c_q:
+// the diagonal weight of G diag(w_q) G is linear in the column, so ONE H serves every column.
+//   loo_columns_moments_kernel   the moments and the lpd table, one workgroup per (leaf, column)
+//   loo_columns_weights_kernel   per leaf [d | sqrt W | 1 / (d sqrt W)] and the two sums of tr(M K_y)
+//   tile_ginv_kernel             H, as dsmgp_loo_gradients forms it, with sqrt W in place of sqrt w
+//   loo_columns_u_kernel         U = H (A / (d sqrt W)) per 128-row tile on the f64 MFMA
+//   loo_columns_rowsums_kernel   |H|_F^2 and sum_q c_q u_q . a_q per row tile (tr M)
+//   tile_graddot_*<GD_LOO_COLUMNS>   the contraction (kernels.hpp)
+//   loo_columns_ardlin_kernel, ardlin_quad_kernel<true>   ArdLinear: sum_q c_q (x_d . u_q)(x_d . a_q) and |H^T x_d|^2
+// The row sums of the factor owner and the leaf's place in obs_idx come from dsmgp_loo's own list (LooTask: P, ldp, off).
+struct LooColsTask {
+    const double* A;        // the leaf's A (npad x qpad, ld = npad)
+    double* vec;            // [d | sqrt W | 1 / (d sqrt W)], 3 npad doubles, zero from row n on; null: no gradient work for this leaf
+    const double* wq;       // weight of column q at wq[q * ldw]
+    double s;               // sum_q c_q
+    int npad, ldw, Q, pad;
+};
+
+// d_i as loo_moments_kernel adds it: the slices of the row in ascending column order
+__device__ __forceinline__ double loo_columns_d(const LooTask& tk, int n, int i) {
+    const int nparts = (n - (i & ~(TB - 1)) + ROWNORM_COLS - 1) / ROWNORM_COLS;
+    double d = 0.0;
+    for (int k = 0; k < nparts; ++k) d += tk.P[(size_t)k * tk.ldp + i];
+    return d;
+}
+
+// Grid (L, Q).  mu (may be null) is nobs x Q with leading dimension ldmu, var (may be null) nobs long and written by column 0;
+// lpd[l + q L].  The sum of a column: thread t adds rows t, t + 256, ..., then the tree of mll_kernel.  A column's results read
+// that column of A and Y only.  NaN for a leaf whose fit failed.
+__global__ __launch_bounds__(256) void loo_columns_moments_kernel(const LeafDev* __restrict__ leaves, const LooTask* __restrict__ loo,
+                                                                  const LooColsTask* __restrict__ tasks,
+                                                                  const int64_t* __restrict__ obs_idx, const double* __restrict__ Y,
+                                                                  int64_t N, int L, double* __restrict__ mu, long long ldmu,
+                                                                  double* __restrict__ var, double* __restrict__ lpd) {
+    __shared__ double red[256];
+    const int l = blockIdx.x, q = blockIdx.y;
+    const LeafDev lf = leaves[l];
+    const LooColsTask tk = tasks[l];
+    const LooTask lt = loo[l];
+    const int t = threadIdx.x;
+    const bool bad = *lf.info != 0;
+    const double log2pi = 1.8378770664093454835606594728112;
+    const double qnan = __builtin_nan("");
+    const double* a_q = tk.A + (size_t)q * tk.npad;
+    double s = 0.0;
+    for (int i = t; i < lf.n; i += 256) {
+        const double d = loo_columns_d(lt, lf.n, i);
+        const double a = a_q[i];
+        const double r = a / d;
+        if (mu) mu[lt.off + i + (size_t)q * ldmu] = bad ? qnan : Y[obs_idx[lt.off + i] + (size_t)q * N] - r;
+        if (var && q == 0) var[lt.off + i] = bad ? qnan : 1.0 / d;
+        s += -0.5 * ((log2pi - log(d)) + a * r);
+    }
+    red[t] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+    if (t == 0) lpd[l + (size_t)q * L] = bad ? qnan : red[0];
+}
+
+// out[2 l] = sum_i sum_q c_q a_iq^2 / d_i, out[2 l + 1] = sum_i W_i d_i: a row's columns in ascending q, thread t adds rows
+// t, t + 256, ..., then a fixed tree.  One workgroup per leaf.
+__global__ __launch_bounds__(256) void loo_columns_weights_kernel(const LeafDev* __restrict__ leaves, const LooTask* __restrict__ loo,
+                                                                  const LooColsTask* __restrict__ tasks, double* __restrict__ out) {
+    __shared__ double r1[256], r2[256];
+    const LooColsTask tk = tasks[blockIdx.x];
+    if (!tk.vec) return;
+    const LooTask lt = loo[blockIdx.x];
+    const LeafDev lf = leaves[blockIdx.x];
+    const int t = threadIdx.x;
+    const size_t np = (size_t)tk.npad;
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = t; i < tk.npad; i += 256) {
+        double d = 0.0, sw = 0.0, tq = 0.0;
+        if (i < lf.n) {
+            d = loo_columns_d(lt, lf.n, i);
+            double S = 0.0;
+            for (int q = 0; q < tk.Q; ++q) {
+                const double a = tk.A[i + (size_t)q * np];
+                S = fma(tk.wq[(size_t)q * tk.ldw] * a, a / d, S);
+            }
+            const double W = (tk.s + S) / (2.0 * d);
+            sw = sqrt(W);
+            tq = 1.0 / (d * sw);
+            s1 += S;
+            s2 = fma(W, d, s2);
+        }
+        tk.vec[i] = d;
+        tk.vec[np + i] = sw;
+        tk.vec[2 * np + i] = tq;
+    }
+    r1[t] = s1;
+    r2[t] = s2;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            r1[t] += r1[t + o];
+            r2[t] += r2[t + o];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[2 * blockIdx.x] = r1[0];
+        out[2 * blockIdx.x + 1] = r2[0];
+    }
+}
+
+// U_i = sum_{c < n} H[i, c] (A[c, :] tq_c) for one 128-row block i of a leaf: targets_a_kernel on a full square (H is stored
+// whole, nothing is triangular) with the scale 1 / (d_c sqrt W_c) folded into the column operand on load, so A / (d sqrt W) is
+// never stored.  Columns c >= n are masked on load and rows >= nrows stored as zeros; all Qpad columns are written.
+struct LooColsUTask {
+    const double* H;        // row tile i of the leaf's H, ld = ld
+    const double* A;        // the leaf's A (ld = ld)
+    const double* tq;       // 1 / (d sqrt W), n entries
+    double* U;              // block i of the leaf's U (ld = ld)
+    int ld, n, nrows, pad;
+};
+
+__global__ __launch_bounds__(256) void loo_columns_u_kernel(const LooColsUTask* __restrict__ tasks, int qpad) {
+    const LooColsUTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int nk = (tk.n + 3) / 4;
+    for (int q0 = 0; q0 < qpad; q0 += TMU_CH * TQ) {
+        const int nch = min(TMU_CH, (qpad - q0) / TQ);
+        d4 acc[TMU_CH][2];
+#pragma unroll
+        for (int ch = 0; ch < TMU_CH; ++ch) {
+            acc[ch][0] = (d4){0.0, 0.0, 0.0, 0.0};
+            acc[ch][1] = (d4){0.0, 0.0, 0.0, 0.0};
+        }
+        const double* pv = tk.H + 32 * w + l15;
+        const double* pz = tk.A + (size_t)(q0 + l15) * tk.ld;
+        for (int kk = 0; kk < nk; ++kk) {
+            const int c = 4 * kk + l4;
+            const bool in = c < tk.n;
+            const double v0 = in ? pv[(size_t)c * tk.ld] : 0.0;
+            const double v1 = in ? pv[(size_t)c * tk.ld + 16] : 0.0;
+            const double sc = in ? tk.tq[c] : 0.0;
+#pragma unroll
+            for (int ch = 0; ch < TMU_CH; ++ch) {
+                if (ch >= nch) continue;
+                const double fz = in ? pz[c + (size_t)(ch * TQ) * tk.ld] * sc : 0.0;
+                acc[ch][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fz, v0, acc[ch][0], 0, 0, 0);
+                acc[ch][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fz, v1, acc[ch][1], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int ch = 0; ch < TMU_CH; ++ch) {
+            if (ch >= nch) continue;
+#pragma unroll
+            for (int rn = 0; rn < 2; ++rn) {
+                const int row = 32 * w + 16 * rn + l15;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int q = q0 + ch * TQ + l4 + 4 * r;
+                    tk.U[(size_t)row + (size_t)q * tk.ld] = row < tk.nrows ? acc[ch][rn][r] : 0.0;
+                }
+            }
+        }
+    }
+}
+
+// One 128-row tile of a leaf: out[2 task] = sum_r sum_{c < n} H(r, c)^2 (the column halves and partial sums of loo_hvec_kernel),
+// out[2 task + 1] = sum_r sum_q c_q U(r, q) A(r, q) (half h of the workgroup takes q = h, h + 2, ...), both through a fixed tree.
+struct LooColsRowTask {
+    const double* H;        // the leaf's H (ld = ld)
+    const double* A;        // the leaf's A and U (ld = ld)
+    const double* U;
+    const double* wq;
+    int ld, ldw, n, Q, row0, nrows;
+};
+
+__global__ __launch_bounds__(256) void loo_columns_rowsums_kernel(const LooColsRowTask* __restrict__ tasks, double* __restrict__ out) {
+    __shared__ double ru[256], rf[256];
+    const LooColsRowTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x, r = t & 127, h = t >> 7;
+    double su = 0.0, sf[4] = {0.0, 0.0, 0.0, 0.0};
+    if (r < tk.nrows) {
+        const double* Hr = tk.H + tk.row0 + r;
+        for (int c = h; c < tk.n; c += 8) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (c + 2 * j < tk.n) {
+                    const double v = Hr[(size_t)(c + 2 * j) * tk.ld];
+                    sf[j] = fma(v, v, sf[j]);
+                }
+        }
+        for (int q = h; q < tk.Q; q += 2) {
+            const size_t at = (size_t)tk.row0 + r + (size_t)q * tk.ld;
+            su = fma(tk.wq[(size_t)q * tk.ldw] * tk.U[at], tk.A[at], su);
+        }
+    }
+    ru[t] = su;
+    rf[t] = (sf[0] + sf[1]) + (sf[2] + sf[3]);
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            ru[t] += ru[t + o];
+            rf[t] += rf[t + o];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[2 * blockIdx.x] = rf[0];
+        out[2 * blockIdx.x + 1] = ru[0];
+    }
+}
+
+// ArdLinear leaves: out[task * D + d] = sum_q c_q (u_q . x_d)(a_q . x_d), one workgroup per (task, d), the order of
+// targets_ardlin_kernel: wave w takes q = w, w + 4, ..., dot products over the lanes by a fixed butterfly, the waves in order.
+struct LooColsArdLinTask {
+    const double* A;        // the leaf's A and U (ld = ld)
+    const double* U;
+    const double* x;        // the leaf's inputs (ld = ld)
+    const double* wq;
+    int ld, ldw, n, Q;
+};
+
+__global__ __launch_bounds__(256) void loo_columns_ardlin_kernel(const LooColsArdLinTask* __restrict__ tasks, int D,
+                                                                 double* __restrict__ out) {
+    __shared__ double red[4];
+    const LooColsArdLinTask tk = tasks[blockIdx.x];
+    const int d = blockIdx.y;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const double* x = tk.x + (size_t)d * tk.ld;
+    double s = 0.0;
+    for (int q = w; q < tk.Q; q += 4) {
+        const double* a = tk.A + (size_t)q * tk.ld;
+        const double* u = tk.U + (size_t)q * tk.ld;
+        double da = 0.0, du = 0.0;
+        for (int i = lane; i < tk.n; i += 64) {
+            da = fma(a[i], x[i], da);
+            du = fma(u[i], x[i], du);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            da += __shfl_xor(da, o, 64);
+            du += __shfl_xor(du, o, 64);
+        }
+        s = fma(tk.wq[(size_t)q * tk.ldw] * du, da, s);
+    }
+    if (lane == 0) red[w] = s;
+    __syncthreads();
+    if (t == 0) out[(size_t)blockIdx.x * D + d] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 }  // namespace dsmgp

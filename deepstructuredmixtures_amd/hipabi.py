@@ -57,6 +57,8 @@ SIGNATURES = {
     "dsmgp_predict_targets": (C.c_int, [_ctx, _dp, C.c_int64, _dp]),
     "dsmgp_targets_fetch": (C.c_int, [_ctx, C.c_int32, _dp]),
     "dsmgp_mll_columns_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp]),
+    "dsmgp_loo_columns": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp]),
+    "dsmgp_loo_columns_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp, _dp]),
     "dsmgp_gradients": (C.c_int, [_ctx, _dp, C.c_int32]),
     "dsmgp_loo": (C.c_int, [_ctx, _dp, _dp, _dp, _dp]),
     "dsmgp_loo_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp]),
@@ -454,17 +456,53 @@ class Context:
         does not apply.  The device time of the call is left in `self.targets_gradients_seconds`."""
         pw = None
         if col_weight is not None:
-            w = np.asarray(col_weight, dtype=np.float64)
-            if w.ndim == 1:
-                w = w[:, None]
-            if w.shape != (self.L, self.targets_Q):
-                raise ValueError(f"col_weight of shape {w.shape}: expected ({self.L}, {self.targets_Q})")
-            w, pw = _f64_fortran(w)
+            w, pw = self._col_weight(col_weight)
         g = np.zeros((self.L, stride))
         sec = C.c_double(0.0)
         self._chk(self.lib.dsmgp_mll_columns_gradients(self.h, g.ctypes.data_as(_dp), int(stride), pw, C.byref(sec)))
         self.targets_gradients_seconds = sec.value
         return g
+
+    def _col_weight(self, col_weight):
+        w = np.asarray(col_weight, dtype=np.float64)
+        if w.ndim == 1:
+            w = w[:, None]
+        if w.shape != (self.L, self.targets_Q):
+            raise ValueError(f"col_weight of shape {w.shape}: expected ({self.L}, {self.targets_Q})")
+        return _f64_fortran(w)
+
+    def loo_targets(self):
+        """Leave-one-out moments of every leaf under every column of the last `solve_targets` (dsmgp_loo_columns; GPML eqs.
+        5.10-5.12 per column, means and hyper-parameters held fixed): `(mu[n_obs, Q], var[n_obs], lpd[L, Q])`, rows in the order
+        of `obs_idx` as for `loo()`.  `var` does not depend on the column: it is `loo()`'s, to the bit.  Leaves with `info != 0`
+        come back as NaN.  Needs `solve_targets` on the current fit.  The device time is left in `self.loo_targets_seconds`."""
+        n = int(self.n_obs)
+        mu = np.empty((n, self.targets_Q), dtype=np.float64, order="F")
+        var = np.empty(n)
+        lpd = np.empty((self.L, self.targets_Q), dtype=np.float64, order="F")
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_loo_columns(self.h, mu.ctypes.data_as(_dp), max(1, n), var.ctypes.data_as(_dp),
+                                             lpd.ctypes.data_as(_dp), C.byref(sec)))
+        self.loo_targets_seconds = sec.value
+        return mu, var, lpd
+
+    def loo_targets_gradients(self, stride, col_weight=None):
+        """`(grad[L, stride], lpd[L, Q])`: `grad[l, j] = sum_q col_weight[l, q] * d lpd[l, q] / d theta_j`, every component the
+        true derivative in the layout of `gradients`, as `loo_gradients` defines them (dsmgp_loo_columns_gradients; GPML eq. 5.13
+        summed over the columns: one inverse and one contraction per leaf whatever Q is).  `col_weight` is `(L, Q)` (a vector
+        counts as one column), finite and >= 0; None: ones; a leaf whose weights are all zero gets a row of zeros.  `lpd` is the
+        table of `loo_targets()`, same bits.  Needs `solve_targets` on the current fit.  Leaves with `info != 0` come back as
+        NaN.  The device time is left in `self.loo_targets_gradients_seconds`."""
+        pw = None
+        if col_weight is not None:
+            w, pw = self._col_weight(col_weight)
+        g = np.zeros((self.L, stride))
+        lpd = np.empty((self.L, self.targets_Q), dtype=np.float64, order="F")
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_loo_columns_gradients(self.h, g.ctypes.data_as(_dp), int(stride), pw, lpd.ctypes.data_as(_dp),
+                                                       C.byref(sec)))
+        self.loo_targets_gradients_seconds = sec.value
+        return g, lpd
 
     # ---- predict(model, x) aggregation + scores on the device (src/common.jl:134-302, src/scorefunctions.jl) ----
     def _agg_args(self, family, leaf_coef, leaf_group):

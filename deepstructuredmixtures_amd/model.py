@@ -819,6 +819,64 @@ def grad_targets(model):
     return _scatter_leaf_rows(model, rows, [(leaf, 1.0, off, size) for leaf, _, off, size in visits])
 
 
+def loo_targets(model):
+    """Leave-one-out cross-validation of every leaf GP under every column of the last `fit_targets` (`dsmgp_loo_columns`), on the
+    one factorisation: dict(obs, mu, var, lpd) like `loo(model)`, with `mu[l]` of shape `(n_l, Q)`, `var[l]` of length `n_l` (the
+    same for every column) and `lpd` of shape `(L, Q)`, which is also stored in `targets_lpd`.  Needs `fit_targets` on the
+    current fit; streaming and multi-rank models refuse as `fit_targets` does."""
+    target = _targets_model(model, "loo_targets")
+    if getattr(target, "targets_mll", None) is None:
+        raise hipabi.DsmgpError(hipabi.E_STATE, "loo_targets before fit_targets")
+    mu, var, lpd = target.ctx.loo_targets()
+    target.targets_lpd = np.ascontiguousarray(lpd)
+    ptr, idx = obs_table(target.leaves)
+    return dict(obs=[np.asarray(idx[ptr[l]:ptr[l + 1]], dtype=np.int64) for l in range(target.L)],
+                mu=[mu[ptr[l]:ptr[l + 1]] for l in range(target.L)],
+                var=[var[ptr[l]:ptr[l + 1]] for l in range(target.L)], lpd=target.targets_lpd.copy())
+
+
+def loo_targets_objective(model, lpd=None):
+    """`sum_q` of the recursion of `loo_objective` on column `q` of the `(L, Q)` table of LOO densities: default the table of
+    the current fit from the device (`loo_targets`), which is also stored in `targets_lpd`; for a `GaussianProcess` the sum of
+    its row."""
+    target = model.model if isinstance(model, GaussianProcess) else model
+    if lpd is None:
+        lpd = loo_targets(model)["lpd"]
+    lpd = np.asarray(lpd, dtype=np.float64)
+    if isinstance(model, GaussianProcess):
+        return float(np.sum(lpd[0]))
+    return float(sum(_value_table(target, lpd[:, q])[target.root.id] for q in range(lpd.shape[1])))
+
+
+def grad_loo_targets(model):
+    """The true gradient of `loo_targets_objective(model)` w.r.t. the shared hyper-vector; with `Y = y[:, None]` it is
+    `grad_loo(model)`.  The weight of every (leaf, column) comes from `_tree_leaf_weights(..., rho=False)` on that column of the
+    table of LOO densities (exponentials: non-negative, as the device call requires); ONE device call returns
+    `sum_q W[l, q] dlpd[l, q] / dtheta` per leaf (`Context.loo_targets_gradients`: one inverse and one contraction per leaf
+    whatever Q is), and the rows are scattered into the hyper-vector with weight 1.  The table the call returns is stored in
+    `targets_lpd`.  Needs `fit_targets` on the current fit."""
+    target = _targets_model(model, "grad_loo_targets")
+    if getattr(target, "targets_mll", None) is None:
+        raise hipabi.DsmgpError(hipabi.E_STATE, "grad_loo_targets before fit_targets")
+    stride = max(lf.kernel.nparams() + 1 for lf in target.leaves)
+    if isinstance(model, GaussianProcess):
+        rows, lpd = target.ctx.loo_targets_gradients(stride)
+        target.targets_lpd = np.ascontiguousarray(lpd)
+        return rows[0][: model.node.kernel.nparams() + 1].copy()
+    tab = getattr(target, "targets_lpd", None)
+    if tab is None:
+        tab = loo_targets(model)["lpd"]
+    W = np.zeros_like(tab)
+    visits = []
+    for q in range(tab.shape[1]):
+        visits = _tree_leaf_weights(target, _value_table(target, tab[:, q]), None, rho=False)
+        for leaf, w, _, _ in visits:
+            W[leaf, q] += w
+    rows, lpd = target.ctx.loo_targets_gradients(stride, W)
+    target.targets_lpd = np.ascontiguousarray(lpd)
+    return _scatter_leaf_rows(target, rows, [(leaf, 1.0, off, size) for leaf, _, off, size in visits])
+
+
 class ADAM:
     """Flux.Optimise.ADAM stand-in for `train!`.  With stateful=False (default) the moment estimates are
     reset every step, which is what the reference effectively runs: `hyp += grad` rebinds `hyp`, so Flux's
@@ -858,7 +916,7 @@ class RMSProp:
         return g * (self.eta / (np.sqrt(self.acc) + self.eps))
 
 
-def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="mll", targets=None):
+def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="mll", targets=None, targets_objective_kind="mll"):
     """`train!(gp::GaussianProcess; iterations, optim, λ)` (`src/optimisers.jl:89-145`): ascent on one GP's log
     marginal; a NaN log marginal (or a factorisation that fails: LAPACK info > 0, which the reference's potrf! call
     ignores and which then shows up as NaN) rolls back to the previous hyper-vector and returns; early stop when the
@@ -881,7 +939,7 @@ def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="ml
             ell = loo_objective(gp, lpd=gp.model.leaf_lpd)    # marginal-likelihood gradients below
         if targets is not None and not np.isnan(ell):     # sum_q mll of the target columns on this factorisation
             fit_targets(gp, targets)
-            ell = targets_objective(gp)
+            ell = loo_targets_objective(gp) if targets_objective_kind == "loo" else targets_objective(gp)
         hist.append(ell)
         if np.isnan(ell):                                                     # :115-119
             setparams(target, old)
@@ -895,7 +953,7 @@ def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="ml
         if objective == "loo":
             g = grad_loo(gp)
         elif targets is not None:
-            g = grad_targets(gp)
+            g = grad_loo_targets(gp) if targets_objective_kind == "loo" else grad_targets(gp)
         else:
             updategradients(gp)
             g = grad_mll(gp)
@@ -907,7 +965,7 @@ def _train_gp(gp, optim, iterations, lam, randinit, seed, verbose, objective="ml
 
 
 def train(model, optim=None, *, iterations=10_000, lam=None, randinit=True, earlystop=10, seed=0, tau=0.05, verbose=False,
-          objective="mll", targets=None):
+          objective="mll", targets=None, targets_objective="mll"):
     """`train!(model, optim; iterations, λ, randinit, earlystop)` (`src/optimisers.jl:4-87`): gradient ASCENT
     on the tree log marginal over one shared hyper-vector.  Returns (model, history of root mll).
     For a single `GaussianProcess` it is `train!(gp; iterations, optim, λ)` (`src/optimisers.jl:89-145`:
@@ -916,16 +974,21 @@ def train(model, optim=None, *, iterations=10_000, lam=None, randinit=True, earl
     counterpart in the reference); a streaming model refuses (`DsmgpError`, E_STATE).
     `targets=Y` (`(N, Q)`, default None: nothing changes): the same loops on `targets_objective(model)`, one kernel trained on all
     Q columns -- per iteration `setparams`, `fit`, `fit_targets`, `grad_targets`, optimiser step.  Not together with
-    `objective="loo"`; streaming and multi-rank models refuse as `fit_targets` does."""
+    `objective="loo"`; streaming and multi-rank models refuse as `fit_targets` does.
+    `targets_objective="loo"` (with `targets=Y`; default "mll": nothing changes): the loops run on `loo_targets_objective(model)`
+    instead, the summed leave-one-out densities of the columns, with `grad_loo_targets` as the gradient.  Any other value raises
+    `ValueError`."""
     from .datagen import normal
     _check_objective(objective)
+    if targets_objective not in ("mll", "loo"):
+        raise ValueError(f"targets_objective must be 'mll' or 'loo', not {targets_objective!r}")
     if targets is not None:
         if objective == "loo":
             raise ValueError("train: targets go with the marginal likelihood objective, not with objective='loo'")
         _targets_model(model, "train(targets=...)")
     if isinstance(model, GaussianProcess):
         return _train_gp(model, RMSProp() if optim is None else optim, iterations, 0.1 if lam is None else lam, randinit, seed,
-                         verbose, objective, targets)
+                         verbose, objective, targets, targets_objective)
     has_leaves = len(model.shard.local) > 0
     # factor-and-discard context: a pass over the leaf groups cannot be revisited, so the loop's fit! asks for the
     # gradients of the same pass up front (one pass per iteration instead of a fit pass plus a fit + gradient pass)
@@ -945,7 +1008,8 @@ def train(model, optim=None, *, iterations=10_000, lam=None, randinit=True, earl
         model.ctx.want_gradients = max(lf.kernel.nparams() + 1 for lf in model.leaves)
         model.ctx.groups = None
     try:
-        return _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming, objective, targets)
+        return _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming, objective, targets,
+                           targets_objective)
     finally:
         if streaming:                  # also after an error inside the loop: later passes must not collect gradients
             model.ctx.want_gradients = 0
@@ -955,7 +1019,7 @@ def train(model, optim=None, *, iterations=10_000, lam=None, randinit=True, earl
 
 
 def _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, verbose, streaming=False, objective="mll",
-                targets=None):
+                targets=None, targets_objective_kind="mll"):
     def plain_fits():
         if streaming:                  # the fits after the loop need no gradients: smaller groups, fewer passes
             model.ctx.want_gradients = 0
@@ -969,7 +1033,7 @@ def _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, ver
             ell = loo_objective(model, lpd=model.leaf_lpd)
         elif targets is not None:
             fit_targets(model, targets)
-            ell = targets_objective(model)
+            ell = loo_targets_objective(model) if targets_objective_kind == "loo" else targets_objective(model)
         else:
             ell = mll(model)
         hist.append(ell)
@@ -983,7 +1047,7 @@ def _train_loop(model, optim, hyp, hist, c, iterations, lam, earlystop, tau, ver
         if objective == "loo":
             g = grad_loo(model)
         elif targets is not None:
-            g = grad_targets(model)
+            g = grad_loo_targets(model) if targets_objective_kind == "loo" else grad_targets(model)
         else:
             updategradients(model)
             g = grad_mll(model)
@@ -1374,6 +1438,7 @@ def fit_targets(model, Y, mean=None):
         mll, sec = target.ctx.solve_targets(Y, mean)
     target.last_targets_seconds = sec
     target.targets_mll = np.ascontiguousarray(mll)      # what targets_objective / grad_targets read
+    target.targets_lpd = None                           # the LOO table of the columns belongs to the targets it was taken on
     return target.targets_mll.copy()
 
 

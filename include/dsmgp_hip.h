@@ -228,8 +228,9 @@ int dsmgp_predict_gradients(dsmgp_ctx* ctx, double* dmu_out, double* dvar_out /*
  *   usable context when it does not fit), re-used while Q does not grow, NOT counted by dsmgp_estimate_bytes / dsmgp_memory,
  *   dropped with the leaf table, new training data and dsmgp_release (under a reserved pool also with a new test set: the pool
  *   is a stack).
- * Out of scope: LOO and input gradients for the extra columns, the multi-GPU exchange (each rank solves its own leaves, the mll
- *   table is per rank), and the streaming context.  Gradients of sum_j mll_j: dsmgp_mll_columns_gradients below. */
+ * Out of scope: input gradients for the extra columns, the multi-GPU exchange (each rank solves its own leaves, the mll
+ *   table is per rank), and the streaming context.  Gradients of sum_j mll_j: dsmgp_mll_columns_gradients below; leave-one-out
+ *   moments and gradients of the columns: dsmgp_loo_columns and dsmgp_loo_columns_gradients below. */
 int dsmgp_solve_targets(dsmgp_ctx* ctx, const double* Y /* N x Q column-major */, int64_t N, int32_t Q, int64_t ldy,
                         const double* mean /* L x Q column-major, ld = L; NULL = zeros */,
                         double* mll_out /* L x Q column-major, ld = L; may be NULL */, double* seconds /* may be NULL */);
@@ -266,6 +267,43 @@ static inline int dsmgp_targets_gradients(dsmgp_ctx* ctx, double* grad_out, int3
                                           double* seconds) {
     return dsmgp_mll_columns_gradients(ctx, grad_out, stride, col_weight, seconds);
 }
+
+/* Leave-one-out cross-validation of the columns of dsmgp_solve_targets on the one factorisation (GPML eqs. 5.10-5.13 per column,
+ * the mean and the hyper-parameters held fixed).  With K_y the matrix the fit factorised, G = K_y^-1, d = diag G and a_q =
+ * G (y_q - m_q) (column q of A, the arena of dsmgp_mll_columns_gradients, same kernel and same bits):
+ *   mu_iq = y_iq - a_iq / d_i,   var_i = 1 / d_i (the same for every column: dsmgp_loo's var_out to the bit),
+ *   lpd_q = sum_i -(log 2pi - log d_i + a_iq^2 / d_i) / 2 .
+ * dsmgp_loo_columns: mu_out is obs_ptr[L] x Q column-major with leading dimension ld >= obs_ptr[L], rows in obs_idx order as for
+ *   dsmgp_loo; var_out obs_ptr[L]; lpd_out L x Q (ld = L).  Any of the three may be NULL.  Column q of mu_out and lpd_out is the
+ *   same bits whatever Q is and whatever the other columns hold.
+ * dsmgp_loo_columns_gradients: grad_out[l * stride + j] = sum_q col_weight[l + q L] d lpd_out[l + q L] / d theta_j in the layout
+ *   of dsmgp_gradients, EVERY component the true derivative as dsmgp_loo_gradients defines them for all eleven kinds (no factor
+ *   sigma for IsoSE; true ArdSE dl whatever DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT says, refused above 35 dimensions; an iso Matern's
+ *   dl summed over d; the rational quadratic da slot; 0 in the dummy slot of the linear kinds; dnoise = 2 exp(2 logNoise) tr M;
+ *   zeros past the hyper-vector).  With s = sum_q c_q,
+ *     sum_q c_q dlpd_q / dtheta = sum_rc M_rc (dK_y / dtheta)_rc,   M = 1/2 sum_q c_q (u_q a_q^T + a_q u_q^T) - H H^T,
+ *     u_q = G (a_q / d),   H = G diag(sqrt W),   W_i = (s + sum_q c_q a_iq^2 / d_i) / (2 d_i) :
+ *   the diagonal weight is linear in the column, so ONE G and ONE H H^T contraction serve every column, plus a rank-2Q term the
+ *   contraction kernels add to their accumulators and O(n^2 Q) for U = [u_q].  The weights must be finite and >= 0 (sqrt W has to
+ *   exist; the tree back-propagation produces such weights); NULL = ones.  A leaf whose weights are all zero gets a row of zeros.
+ *   lpd_out (L x Q, may be NULL): dsmgp_loo_columns' table, the same bits.
+ * Both need a fit and a dsmgp_solve_targets on the CURRENT fit (DSMGP_E_STATE otherwise).  DSMGP_E_ARG: grad_out NULL, a stride
+ * smaller than a hyper-vector, ld < obs_ptr[L], a non-finite or negative weight.  d and L^-T come by dsmgp_loo's rule (read when
+ * the arena holds this fit's, filled otherwise; what that call says about dsmgp_gradients and the mask holds here).  Leaves
+ * whose fit reported info != 0 get NaN rows and NaN lpd / mu / var, the others are unaffected.  A COPY leaf reads its source's d
+ * and L^-T and has targets, mean and weights of its own.
+ * Nothing another entry point reads is written: dsmgp_fit's outputs, dsmgp_gradients, dsmgp_loo*, dsmgp_predict_*,
+ * dsmgp_targets_fetch, dsmgp_predict_targets and dsmgp_mll_columns_gradients return the same bits before and after.  Sums run in a
+ * fixed order, no atomics: the same bits from call to call, and with one lane and with two wherever both fits leave the same
+ * factor bits.
+ * Memory (gradients): H takes npad^2 doubles per leaf and U npad Qpad, in arenas of their own, allocated on first use (from the
+ *   reserved pool when there is one; DSMGP_E_NOMEM with a usable context when they do not fit), NOT counted by
+ *   dsmgp_estimate_bytes / dsmgp_memory, dropped where the arena of dsmgp_solve_targets is dropped.  seconds: device time. */
+int dsmgp_loo_columns(dsmgp_ctx* ctx, double* mu_out /* obs_ptr[L] x Q column-major */, int64_t ld,
+                      double* var_out /* obs_ptr[L] */, double* lpd_out /* L x Q, ld = L */, double* seconds /* may be NULL */);
+int dsmgp_loo_columns_gradients(dsmgp_ctx* ctx, double* grad_out /* L x stride */, int32_t stride,
+                                const double* col_weight /* L x Q column-major, ld = L, >= 0; NULL = ones */,
+                                double* lpd_out /* L x Q, ld = L; may be NULL */, double* seconds /* may be NULL */);
 
 /* ---- predict(model, x): sum/product aggregation of the leaf moments over the leaves every test row visits, on the
  *      moments the last dsmgp_predict_run left in HBM (replaces the host recursions of src/common.jl:134-149,198-302).

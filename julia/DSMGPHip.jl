@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, targets_fetch, targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
+export attach!, detach!, census, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -595,6 +595,42 @@ function targets_gradients(s::Session; col_weight::Union{Nothing,AbstractMatrix}
     GC.@preserve g W chk(s, ccall(sym(:dsmgp_mll_columns_gradients), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ref{Float64}),
                                   s.h, g, Int32(s.stride), W === nothing ? Ptr{Float64}(C_NULL) : pointer(W), sec))
     return g
+end
+
+"loo_targets(s): leave-one-out moments of every leaf under every column of the last solve_targets, on the one factorisation
+(dsmgp_loo_columns; GPML §5.4.2, eqs. 5.10-5.12 per column).  Returns (μ, σ², lpd): `μ[l]` is `n_l × Q` and `σ²[l]` of length `n_l`
+(the same for every column: that of `loo(s)`, same bits), aligned with `s.leaves[l].obs`; `lpd` is `L × Q`.  Needs solve_targets on
+the current fit; leaves whose fit reported info ≠ 0 come back as NaN."
+function loo_targets(s::Session)
+    L = length(s.leaves)
+    Q = s.targets
+    off = cumsum([0; [length(lf.obs) for lf in s.leaves]])
+    n = off[end]
+    μ = Matrix{Float64}(undef, n, Q)
+    σ² = Vector{Float64}(undef, n)
+    lpd = Matrix{Float64}(undef, L, Q)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve μ σ² lpd chk(s, ccall(sym(:dsmgp_loo_columns), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Float64}), s.h, μ, Int64(max(n, 1)), σ², lpd, sec))
+    return [μ[off[l]+1:off[l+1], :] for l in 1:L], [σ²[off[l]+1:off[l+1]] for l in 1:L], lpd
+end
+
+"loo_targets_gradients(s; col_weight=nothing): `g[:, l] = Σ_q col_weight[l, q] ∂lpd[l, q]/∂θ`, every component the true derivative
+as loo_gradients defines them (dsmgp_loo_columns_gradients; GPML eq. 5.13 summed over the columns: one inverse and one contraction
+per leaf whatever Q is).  `col_weight` is `L × Q` (the order of `s.leaves`), finite and ≥ 0; `nothing`: ones; a leaf whose weights
+are all zero gets a column of zeros.  Returns (g, lpd), `lpd` the `L × Q` table of loo_targets, same bits.  Needs solve_targets on
+the current fit; leaves whose fit reported info ≠ 0 come back as NaN.  Nothing is written to the kernels' gradient fields."
+function loo_targets_gradients(s::Session; col_weight::Union{Nothing,AbstractMatrix}=nothing)
+    L = length(s.leaves)
+    W = col_weight === nothing ? nothing : Matrix{Float64}(col_weight)
+    W === nothing || size(W) == (L, s.targets) || throw(DimensionMismatch("col_weight must be L × Q"))
+    g = Matrix{Float64}(undef, s.stride, L)
+    lpd = Matrix{Float64}(undef, L, s.targets)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve g W lpd chk(s, ccall(sym(:dsmgp_loo_columns_gradients), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+        s.h, g, Int32(s.stride), W === nothing ? Ptr{Float64}(C_NULL) : pointer(W), lpd, sec))
+    return g, lpd
 end
 
 # ---------------------------------------------------------------------------------------------- predict
