@@ -458,6 +458,14 @@ struct SweepLane {
 
 }  // namespace
 
+// A contraction list of the gradient passes (build_dot_list): tasks [first[p], first[p + 1]) belong to the kinds of KindInfo::dot_pass == p and are run by that pass's
+// kernel; leaf_of[i] is the leaf of task i.
+struct DotRanges {
+    size_t first[5] = {0, 0, 0, 0, 0};
+    std::vector<int> leaf_of;
+    size_t count() const { return first[4]; }
+};
+
 struct dsmgp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -663,10 +671,7 @@ struct dsmgp_ctx {
     DevBuf<FrobTask> gfrob;
     std::vector<int> gfrob_leaf;    // owner leaf of each frob task
     DevBuf<GradTask> gdot;
-    size_t gdot_prod0 = 0;          // first task of an ArdSEProduct leaf in gdot (they and the Matern leaves form its tail)
-    size_t gdot_mat0 = 0;           // first task of a Matern leaf in gdot
-    size_t gdot_rq0 = 0;            // first task of a rational quadratic leaf in gdot (the end of the list)
-    std::vector<int> gdot_leaf;     // leaf of each graddot task
+    DotRanges gdot_ranges;          // its four kernel ranges and the leaf of each task
     DevBuf<ArdLinTask> gardlin;     // ArdLinear leaves: column groups of L^-T (ardlin_quad_kernel)
     std::vector<int> gardlin_leaf;  // leaf of each of them
     bool ard_true_gradient = false; // DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT
@@ -695,10 +700,9 @@ struct dsmgp_ctx {
     DevBuf<GinvTask> lginv;
     DevBuf<LooHvecTask> lghvec;
     std::vector<int> lghvec_leaf;
-    DevBuf<GradTask> lgdot;         // as gdot: IsoSE / ArdSE | ArdSEProduct | Matern
-    size_t lgdot_prod0 = 0, lgdot_mat0 = 0, lgdot_rq0 = 0;
+    DevBuf<GradTask> lgdot;         // as gdot: IsoSE / ArdSE | ArdSEProduct | Matern | rational quadratic
+    DotRanges lgdot_ranges;
     int lgstride = 2;               // doubles per contraction task in d_lgpart: 2 + D, one more with a rational quadratic id
-    std::vector<int> lgdot_leaf;
     DevBuf<ArdLinTask> lgardlin;
     std::vector<int> lgardlin_leaf;
     DevBuf<double> d_lgpart;        // weights 2 L | hvec pairs | graddot x (2 + D) | ArdLinear 3 D per task
@@ -1128,21 +1132,22 @@ struct KindInfo {
     bool contraction;   // the gradient always contracts (alpha alpha^T - K_y^-1) with dK on the device (tile_graddot*); ArdSE
                         //   with ard_true_gradient only
     bool set_checked;   // dsmgp_set_hyper refuses a wrong number of length-scales itself (the reference kinds: check_hyper, at fit)
+    int dot_pass;       // the contraction kernel of the kind's tiles (launch_graddot): 0 tile_graddot_kernel, 1 _prod, 2 _matern, 3 _rq
 };
 constexpr KindInfo KINDS[] = {
-    //  name           ard    iso_m  matern rq     n_shape linear nh_num per_dim contr. set_checked
-    {"IsoSE",          false, false, false, false, 0,      false, -0.5,  false,  true,  false},
-    {"ArdSE",          true,  false, false, false, 0,      false, -0.5,  true,   false, false},
-    {"IsoLinear",      false, false, false, false, 0,      true,  -0.5,  false,  false, false},
-    {"ArdLinear",      true,  false, false, false, 0,      true,  1.0,   false,  false, false},
-    {"ArdSEProduct",   true,  false, false, false, 0,      false, -0.5,  true,   true,  true},
-    {"IsoMatern32",    false, true,  true,  false, 0,      false, 3.0,   true,   true,  true},
-    {"IsoMatern52",    false, true,  true,  false, 0,      false, 5.0,   true,   true,  true},
-    {"ArdMatern32",    true,  false, true,  false, 0,      false, 3.0,   true,   true,  true},
-    {"ArdMatern52",    true,  false, true,  false, 0,      false, 5.0,   true,   true,  true},
+    //  name           ard    iso_m  matern rq     n_shape linear nh_num per_dim contr. set_checked dot_pass
+    {"IsoSE",          false, false, false, false, 0,      false, -0.5,  false,  true,  false, 0},
+    {"ArdSE",          true,  false, false, false, 0,      false, -0.5,  true,   false, false, 0},
+    {"IsoLinear",      false, false, false, false, 0,      true,  -0.5,  false,  false, false, 0},
+    {"ArdLinear",      true,  false, false, false, 0,      true,  1.0,   false,  false, false, 0},
+    {"ArdSEProduct",   true,  false, false, false, 0,      false, -0.5,  true,   true,  true,  1},
+    {"IsoMatern32",    false, true,  true,  false, 0,      false, 3.0,   true,   true,  true,  2},
+    {"IsoMatern52",    false, true,  true,  false, 0,      false, 5.0,   true,   true,  true,  2},
+    {"ArdMatern32",    true,  false, true,  false, 0,      false, 3.0,   true,   true,  true,  2},
+    {"ArdMatern52",    true,  false, true,  false, 0,      false, 5.0,   true,   true,  true,  2},
     // rational quadratic: iso_m = D equal slots for the iso kind; nh_num is 0.5 / alpha, made in upload_hyper
-    {"IsoRQ",          false, true,  false, true,  1,      false, 0.0,   true,   true,  true},
-    {"ArdRQ",          true,  false, false, true,  1,      false, 0.0,   true,   true,  true},
+    {"IsoRQ",          false, true,  false, true,  1,      false, 0.0,   true,   true,  true,  3},
+    {"ArdRQ",          true,  false, false, true,  1,      false, 0.0,   true,   true,  true,  3},
 };
 static_assert(sizeof(KINDS) / sizeof(KINDS[0]) == DSMGP_KIND_ARD_RQ + 1, "one row per DSMGP_KIND_*");
 // length-scales of a hyper-vector of n values: [logl..., shape..., logs, logNoise]
@@ -3490,6 +3495,217 @@ int dsmgp_scores(dsmgp_ctx* c, const double* y_test, double* out) {
 
 namespace {
 
+// ---- What the four hyper-parameter gradient passes share (dsmgp_gradients, dsmgp_loo_gradients, dsmgp_mll_columns_gradients,
+// dsmgp_loo_columns_gradients): one builder of the contraction list, one launcher, one reducer of its sums.
+//
+// Order of a tile list.  A 128x128 tile task moves 2 x 128 x K operand doubles for 2 x 128^2 x K flops: 8 flop/B, below the
+// ridge of the chip unless operands are shared through L2.  Tasks that are adjacent in the list run at the same time on one
+// XCD, so the lower tiles (i, j) of a leaf are listed in super-tiles of GS x GS tiles: the GS^2 tasks of a super-tile read GS
+// row panels and GS column panels between them (measured: tiles listed row by row 55 TFLOP/s; sorted by depth across leaves,
+// i.e. no sharing at all, 26).  each_lower_tile lists them, marking the start of every block of GS tile rows in `gblock`
+// (these tasks share their A panels); deal_tiles deals the blocks listed since `begin` to the XCDs by work = the length of a
+// task's K range + `overhead` per task (neighbours in the list sit 8 apart in the launch: they run on one XCD and share its L2;
+// the XCD slots get equal work).
+constexpr int GS = 4;
+extern "C++" {      // (templates cannot have C linkage, nor can the helpers below that return or take C++ types by value)
+template <class SizeNow, class Emit>
+void each_lower_tile(const LeafHost& lf, std::vector<size_t>& gblock, size_t begin, SizeNow&& size_now, Emit&& emit) {
+    for (int ib = 0; ib < lf.nb; ib += GS) {
+        gblock.push_back(size_now() - begin);
+        for (int jb = 0; jb <= ib; jb += GS)
+            for (int i = ib; i < std::min(ib + GS, lf.nb); ++i)
+                for (int j = jb; j < std::min(jb + GS, i + 1); ++j)
+                    emit(i, j, std::max(0, std::min(TB, lf.n - i * TB)), std::max(0, std::min(TB, lf.n - j * TB)));
+    }
+}
+template <class Tasks>
+void deal_tiles(dsmgp_ctx* c, Tasks& tasks, std::vector<int>& leaf_of, size_t begin, std::vector<size_t>& gblock, double overhead) {
+    gblock.push_back(tasks.size() - begin);
+    std::vector<double> work(tasks.size() - begin);
+    for (size_t i = 0; i < work.size(); ++i) work[i] = (double)(tasks[begin + i].gemm.k1 - tasks[begin + i].gemm.k0) + overhead;
+    xcd_deal_by_work(tasks, leaf_of, begin, tasks.size(), gblock, work, c->xcd_order);
+}
+
+// What a contraction task of one leaf reads: G = the matrix whose row tiles are multiplied (ld = ldg) -- L^-T, of which row tile
+// i is zero left of column 128 i (tri: the K range starts there), or the full square H -- and the leaf's vector block.
+struct DotOperand {
+    const double* G;
+    int ldg;
+    bool tri;
+    const double* vec;
+};
+// The contraction list of a pass: the four ranges in turn, in each the leaves of that range's kinds in leaf order, their lower
+// tiles by each_lower_tile, dealt by deal_tiles.  has(l, kind): the leaf has tasks (an IsoLinear or ArdLinear leaf never has;
+// whether an ArdSE leaf has is the caller's to say); operand(l): its DotOperand; fill(task, l, i, j): the mode's own fields.
+template <class Task, class Has, class Operand, class Fill>
+std::vector<Task> build_dot_list(dsmgp_ctx* c, DotRanges& r, double overhead, Has&& has, Operand&& operand, Fill&& fill) {
+    std::vector<Task> gd;
+    std::vector<size_t> gblock;
+    r.leaf_of.clear();
+    for (int pass = 0; pass < 4; ++pass) {
+        const size_t begin = r.first[pass] = gd.size();
+        gblock.clear();
+        for (int l = 0; l < c->L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            const int kind = c->hyper[lf.kid].kind;
+            if (!KINDS[kind].contraction && kind != DSMGP_KIND_ARD_SE) continue;
+            if (KINDS[kind].dot_pass != pass || !has(l, kind)) continue;
+            const LeafDev& d = c->h_leaves[l];
+            const DotOperand o = operand(l);
+            each_lower_tile(lf, gblock, begin, [&] { return gd.size(); }, [&](int i, int j, int na, int nb) {
+                Task g{};
+                g.gemm.A = o.G + (size_t)i * TB;
+                g.gemm.B = o.G + (size_t)j * TB;
+                g.gemm.C = nullptr;
+                g.gemm.lda = g.gemm.ldb = o.ldg;
+                g.gemm.ldc = TB;
+                g.gemm.k0 = o.tri ? i * TB : 0;
+                g.gemm.k1 = lf.npad;
+                g.gemm.update = 0;
+                g.xa = d.Xg + (size_t)i * TB;
+                g.xb = d.Xg + (size_t)j * TB;
+                g.alpha_a = o.vec + (size_t)i * TB;
+                g.alpha_b = o.vec + (size_t)j * TB;
+                g.ldx = lf.npad;
+                g.na = na;
+                g.nb = nb;
+                g.diag = (i == j);
+                g.kid = lf.kid;
+                fill(g, l, i, j);
+                gd.push_back(g);
+                r.leaf_of.push_back(l);
+            });
+        }
+        deal_tiles(c, gd, r.leaf_of, begin, gblock, overhead);
+    }
+    r.first[4] = gd.size();
+    return gd;
+}
+// The up to four launches over a contraction list on the device: range p by the kernel of pass p, its sums at pdot + gs * first[p]
+template <int MODE>
+void launch_graddot(dsmgp_ctx* c, const graddot_task_t<MODE>* tasks, const DotRanges& r, double* pdot, int gs) {
+    const size_t* f = r.first;
+    auto grid = [&](int p) { return (unsigned)(f[p + 1] - f[p]); };
+    auto out = [&](int p) { return pdot + (size_t)gs * f[p]; };
+    if (grid(0)) tile_graddot_kernel<MODE><<<grid(0), 256, 0, c->stream>>>(tasks + f[0], c->d_kp.p, c->D, out(0), gs);
+    if (grid(1)) tile_graddot_prod_kernel<MODE><<<grid(1), 256, 0, c->stream>>>(tasks + f[1], c->d_kp.p, c->D, out(1), gs);
+    if (grid(2)) tile_graddot_matern_kernel<MODE><<<grid(2), 256, 0, c->stream>>>(tasks + f[2], c->d_kp.p, c->D, out(2), gs);
+    if (grid(3)) tile_graddot_rq_kernel<MODE><<<grid(3), 256, 0, c->stream>>>(tasks + f[3], c->d_kp.p, c->D, out(3), gs);
+}
+// The tiles of H = K_y^-1 diag(sqrt w) of the LOO passes (tile_ginv_kernel): the leaves with has(l) in leaf order, one deal.
+// place(l): what a leaf's tasks read and write.
+struct GinvPlace {
+    const double* Xt;       // L^-T of the leaf's factor owner (ld = ldt)
+    int ldt;
+    double* H;              // npad x npad
+    const double* sw;       // sqrt w of the leaf's rows
+};
+template <class Has, class Place>
+std::vector<GinvTask> build_ginv_list(dsmgp_ctx* c, Has&& has, Place&& place) {
+    std::vector<GinvTask> gi;
+    std::vector<int> gi_leaf;
+    std::vector<size_t> gblock;
+    for (int l = 0; l < c->L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (!has(l)) continue;
+        const GinvPlace o = place(l);
+        each_lower_tile(lf, gblock, 0, [&] { return gi.size(); }, [&](int i, int j, int na, int nb) {
+            GinvTask g{};
+            g.gemm.A = o.Xt + (size_t)i * TB;
+            g.gemm.B = o.Xt + (size_t)j * TB;
+            g.gemm.C = o.H + (size_t)i * TB + (size_t)j * TB * lf.npad;
+            g.Ct = o.H + (size_t)j * TB + (size_t)i * TB * lf.npad;
+            g.gemm.lda = g.gemm.ldb = o.ldt;
+            g.gemm.ldc = lf.npad;
+            g.gemm.k0 = i * TB;
+            g.gemm.k1 = lf.npad;
+            g.sw_a = o.sw + (size_t)i * TB;
+            g.sw_b = o.sw + (size_t)j * TB;
+            g.na = na;
+            g.nb = nb;
+            g.diag = (i == j);
+            gi.push_back(g);
+            gi_leaf.push_back(l);
+        });
+    }
+    deal_tiles(c, gi, gi_leaf, 0, gblock, 64.0);
+    return gi;
+}
+
+// The sums of a contraction list per leaf, the tasks of a leaf added in list order (fixed: bit-reproducible).  A task's slots:
+// [0] weight . K r^2, [1] weight . K (LOO modes), [2 .. 2 + D) weight . dK / dlog l_d, [2 + D] weight . dK / dlog alpha (rational
+// quadratic).  The LOO modes read slots 0 and 1 of every task; the marginal-likelihood modes read slot 0 of the kinds without
+// per-dimension sums only.  Sd is empty when the tasks have no per-dimension slots (gs == 2).
+struct DotSums {
+    std::vector<double> S1, SK, Sd, Sa;
+};
+DotSums reduce_dot_sums(const dsmgp_ctx* c, const DotRanges& r, const double* pd, size_t gs, bool loo) {
+    const size_t L = (size_t)c->L, D = (size_t)c->D;
+    DotSums s;
+    s.S1.assign(L, 0.0);
+    s.Sa.assign(L, 0.0);
+    if (loo) s.SK.assign(L, 0.0);
+    if (gs > 2) s.Sd.assign(L * D, 0.0);
+    for (size_t i = 0; i < r.count(); ++i) {
+        const size_t l = (size_t)r.leaf_of[i];
+        const KindInfo& ki = KINDS[c->hyper[c->leaves[l].kid].kind];
+        const double* t = pd + gs * i;
+        if (loo) {
+            s.S1[l] += t[0];
+            s.SK[l] += t[1];
+        } else if (!ki.per_dim_grad) {
+            s.S1[l] += t[0];
+        }
+        if (ki.per_dim_grad) {
+            for (size_t d = 0; d < D; ++d) s.Sd[l * D + d] += t[2 + d];
+            if (ki.rq) s.Sa[l] += t[2 + D];
+        }
+    }
+    return s;
+}
+// The ardlin_quad_kernel tasks of an ArdLinear leaf, ARDLIN_COLS columns of M (ld = ldm: L^-T of the factor owner, or the leaf's H)
+// each, with the leaf's inputs x and its vector block
+void ardlin_tasks(std::vector<ArdLinTask>& tasks, std::vector<int>& leaf_of, int l, const LeafHost& lf, const double* M, int ldm,
+                  const double* x, const double* vec) {
+    for (int c0 = 0; c0 < lf.n; c0 += ARDLIN_COLS) {
+        ArdLinTask a{};
+        a.Xt = M;
+        a.x = x;
+        a.alpha = vec;
+        a.ldt = ldm;
+        a.ldx = lf.npad;      // FULL (the LOO passes): also the distance from alpha to u in the vector block
+        a.c0 = c0;
+        a.n = lf.n;
+        tasks.push_back(a);
+        leaf_of.push_back(l);
+    }
+}
+// What the entry points check of their arguments alike
+int check_stride(dsmgp_ctx* c, const char* who, int stride) {
+    for (int l = 0; l < c->L; ++l)
+        if ((int)c->hyper[c->leaves[l].kid].loghyp.size() > stride)
+            return fail(c, DSMGP_E_ARG, std::string(who) + ": stride smaller than the hyper-vector");
+    return 0;
+}
+// W[L x Q] = the caller's column weights (NULL: ones), sw[l] = their sum over the columns in ascending q
+int column_weights(dsmgp_ctx* c, const char* who, const double* col_weight, bool refuse_negative, std::vector<double>& W,
+                   std::vector<double>& sw) {
+    const size_t L = (size_t)c->L, Q = (size_t)c->tg_Q;
+    W.assign(L * Q, 1.0);
+    sw.assign(L, 0.0);
+    if (col_weight)
+        for (size_t i = 0; i < W.size(); ++i) {
+            if (!std::isfinite(col_weight[i]) || (refuse_negative && col_weight[i] < 0.0))
+                return fail(c, DSMGP_E_ARG, std::string(who) + (refuse_negative ? ": non-finite or negative value in col_weight"
+                                                                               : ": non-finite value in col_weight"));
+            W[i] = col_weight[i];
+        }
+    for (size_t l = 0; l < L; ++l)
+        for (size_t q = 0; q < Q; ++q) sw[l] += W[l + q * L];
+    return 0;
+}
+}  // extern "C++"
+
 // Task lists of the gradient pass: Xt = L^-T by a blocked triangular inversion on the same tile kernels
 // (row tile t of Xt is e_t^T L^-T: zero left of block t, Dinv_t^T on the diagonal, then a left-looking sweep
 // whose K range starts at column 128 t), then the contraction tiles of tile_graddot_kernel.
@@ -3606,76 +3822,21 @@ int build_grad_plan(dsmgp_ctx* c) {
         }
     }
 
-    // contraction tiles: every IsoSE, ArdSEProduct and Matern leaf (COPY leaves too: their alpha is their own)
-    // Order.  A 128x128 tile task moves 2 x 128 x K operand doubles for 2 x 128^2 x K flops: 8 flop/B, below the
-    // ridge of the chip unless operands are shared through L2.  Tasks that are adjacent in this list run at the same
-    // time on one XCD (xcd_permute below), so the lower tiles of a leaf are listed in super-tiles of GS x GS tiles:
-    // the GS^2 tasks of a super-tile read GS row panels and GS column panels of L^-T between them (measured: tiles
-    // listed row by row 55 TFLOP/s; sorted by depth across leaves, i.e. no sharing at all, 26).
-    constexpr int GS = 4;
-    std::vector<GradTask> gd;
-    std::vector<size_t> gblock;
-    c->gdot_leaf.clear();
-    // The tasks of ArdSEProduct leaves (pass 1), then those of Matern leaves (pass 2), then those of rational quadratic leaves
-    // (pass 3) form the tail of the list, run by tile_graddot_prod_kernel, tile_graddot_matern_kernel and tile_graddot_rq_kernel.
+    // contraction tiles (build_dot_list): every IsoSE, ArdSEProduct, Matern and rational quadratic leaf, and the ArdSE leaves when
+    // the true length-scale gradient is asked for (COPY leaves too: their alpha is their own).
+    // Shared gradients (the idea of src/fit.jl:313-395: a leaf whose observation set equals its main leaf's takes that leaf's
+    // gradients, `copygradients`): a COPY leaf has its source's factor and kernel id; with the same ConstMean its alpha is the
+    // source's too, so its contraction is the source's and is not computed again.
     bool any_ard = false, any_prod = false;
-    for (int pass = 0; pass < 4; ++pass) {
-        if (pass == 1) c->gdot_prod0 = gd.size();
-        if (pass == 2) c->gdot_mat0 = gd.size();
-        if (pass == 3) c->gdot_rq0 = gd.size();
-        const size_t begin = gd.size();
-        gblock.clear();
-        for (int l = 0; l < L; ++l) {
-            const LeafHost& lf = c->leaves[l];
-            const int kind_l = c->hyper[lf.kid].kind;
-            const bool ard = kind_l == DSMGP_KIND_ARD_SE && c->ard_true_gradient;
-            const bool prod = kind_l == DSMGP_KIND_ARD_SE_PRODUCT;
-            const bool mat = KINDS[kind_l].matern, rq = KINDS[kind_l].rq;
-            if (!KINDS[kind_l].contraction && !ard) continue;
-            if ((prod ? 1 : mat ? 2 : rq ? 3 : 0) != pass) continue;
-            any_ard = any_ard || ard;
-            any_prod = any_prod || prod || mat || rq;
-            // Shared gradients (the idea of src/fit.jl:313-395: a leaf whose observation set equals its main leaf's takes
-            // that leaf's gradients, `copygradients`): a COPY leaf has its source's factor and kernel id; with the same
-            // ConstMean its alpha is the source's too, so its contraction is the source's and is not computed again.
-            if (c->grad_src[l] >= 0 || !needC[l]) continue;
-            const LeafDev& d = c->h_leaves[l];
-            for (int ib = 0; ib < lf.nb; ib += GS) {
-                gblock.push_back(gd.size() - begin);   // one block per (leaf, GS tile rows): these tasks share their A panels
-                for (int jb = 0; jb <= ib; jb += GS)
-                    for (int i = ib; i < std::min(ib + GS, lf.nb); ++i)
-                        for (int j = jb; j < std::min(jb + GS, i + 1); ++j) {
-                            GradTask g{};
-                            g.gemm.A = Xt(l) + (size_t)i * TB;
-                            g.gemm.B = Xt(l) + (size_t)j * TB;
-                            g.gemm.C = nullptr;
-                            g.gemm.lda = g.gemm.ldb = lf.npad;
-                            g.gemm.ldc = TB;
-                            g.gemm.k0 = i * TB;
-                            g.gemm.k1 = lf.npad;
-                            g.gemm.update = 0;
-                            g.xa = d.Xg + (size_t)i * TB;
-                            g.xb = d.Xg + (size_t)j * TB;
-                            g.alpha_a = d.alpha + (size_t)i * TB;
-                            g.alpha_b = d.alpha + (size_t)j * TB;
-                            g.ldx = lf.npad;
-                            g.na = std::max(0, std::min(TB, lf.n - i * TB));
-                            g.nb = std::max(0, std::min(TB, lf.n - j * TB));
-                            g.diag = (i == j);
-                            g.kid = lf.kid;
-                            gd.push_back(g);
-                            c->gdot_leaf.push_back(l);
-                        }
-            }
-        }
-        // neighbours in the list sit 8 apart in the launch: they run on one XCD and share its L2; the XCD slots get equal work
-        {
-            gblock.push_back(gd.size() - begin);
-            std::vector<double> work(gd.size() - begin);
-            for (size_t i = 0; i < work.size(); ++i) work[i] = (double)(gd[begin + i].gemm.k1 - gd[begin + i].gemm.k0) + 64.0;   // + per-task overhead
-            xcd_deal_by_work(gd, c->gdot_leaf, begin, gd.size(), gblock, work, c->xcd_order);
-        }
+    for (int l = 0; l < L; ++l) {
+        const int kind_l = c->hyper[c->leaves[l].kid].kind;
+        any_ard = any_ard || (kind_l == DSMGP_KIND_ARD_SE && c->ard_true_gradient);
+        any_prod = any_prod || KINDS[kind_l].dot_pass != 0;
     }
+    const std::vector<GradTask> gd = build_dot_list<GradTask>(
+        c, c->gdot_ranges, 64.0,
+        [&](int l, int kind) { return (kind != DSMGP_KIND_ARD_SE || c->ard_true_gradient) && c->grad_src[l] < 0 && needC[l]; },
+        [&](int l) { return DotOperand{Xt(l), c->leaves[l].npad, true, c->h_leaves[l].alpha}; }, [](GradTask&, int, int, int) {});
     if (int rc = dev_upload(c, c->gtrans, trans)) return rc;
     if (int rc = dev_upload(c, c->gfrob, frob)) return rc;
     if (int rc = pack_sweep(c, c->ginv, lanes, copy_upload)) return rc;
@@ -3693,19 +3854,7 @@ int build_grad_plan(dsmgp_ctx* c) {
         const LeafHost& lf = c->leaves[l];
         if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR) continue;
         if (c->grad_src[l] >= 0 || !needC[l]) continue;
-        const LeafDev& d = c->h_leaves[l];
-        for (int c0 = 0; c0 < lf.n; c0 += ARDLIN_COLS) {
-            ArdLinTask a{};
-            a.Xt = Xt(l);
-            a.x = d.Xg;
-            a.alpha = d.alpha;
-            a.ldt = c->leaves[lf.owner].npad;
-            a.ldx = lf.npad;
-            a.c0 = c0;
-            a.n = lf.n;
-            al.push_back(a);
-            c->gardlin_leaf.push_back(l);
-        }
+        ardlin_tasks(al, c->gardlin_leaf, l, lf, Xt(l), c->leaves[lf.owner].npad, c->h_leaves[l].Xg, c->h_leaves[l].alpha);
     }
     {
         std::vector<size_t> ord(al.size());
@@ -3814,10 +3963,7 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     if (!grad_out) return fail(c, DSMGP_E_ARG, "grad_out is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     const int L = c->L;
-    for (int l = 0; l < L; ++l) {
-        const HyperHost& h = c->hyper[c->leaves[l].kid];
-        if ((int)h.loghyp.size() > stride) return fail(c, DSMGP_E_ARG, "gradients: stride smaller than the hyper-vector");
-    }
+    if (int rc = check_stride(c, "gradients", stride)) return rc;
     if (!c->grad_ready)
         if (int rc = build_grad_plan(c)) return rc;
     if (int rc = ensure_dinv(c)) return rc;
@@ -3839,20 +3985,7 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     double* pfrob = c->d_gpart.p;
     double* pdot = pfrob + c->gfrob.count;
     double* pleaf = pdot + (size_t)c->gstride * c->gdot.count;
-    const size_t np0 = c->gdot_prod0;     // tasks [np0, nm0): ArdSEProduct leaves
-    const size_t nm0 = c->gdot_mat0;      // tasks [nm0, nr0): Matern leaves
-    const size_t nr0 = c->gdot_rq0;       // tasks [nr0, count): rational quadratic leaves
-    if (np0)
-        tile_graddot_kernel<GD_MLL><<<(int)np0, 256, 0, c->stream>>>(c->gdot.p, c->d_kp.p, c->D, pdot, c->gstride);
-    if (nm0 > np0)
-        tile_graddot_prod_kernel<GD_MLL><<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->gdot.p + np0, c->d_kp.p, c->D,
-                                                                               pdot + (size_t)c->gstride * np0, c->gstride);
-    if (nr0 > nm0)
-        tile_graddot_matern_kernel<GD_MLL><<<(int)(nr0 - nm0), 256, 0, c->stream>>>(c->gdot.p + nm0, c->d_kp.p, c->D,
-                                                                                 pdot + (size_t)c->gstride * nm0, c->gstride);
-    if (c->gdot.count > nr0)
-        tile_graddot_rq_kernel<GD_MLL><<<(int)(c->gdot.count - nr0), 256, 0, c->stream>>>(c->gdot.p + nr0, c->d_kp.p, c->D,
-                                                                                       pdot + (size_t)c->gstride * nr0, c->gstride);
+    launch_graddot<GD_MLL>(c, c->gdot.p, c->gdot_ranges, pdot, c->gstride);
     HIPCHK(c, hipEventRecord(e_dot.a, c->stream));
     if (c->gfrob.count) frob_kernel<<<(int)c->gfrob.count, 256, 0, c->stream>>>(c->gfrob.p, pfrob);
     dots_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, pleaf);
@@ -3877,30 +4010,19 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     std::vector<double> part(c->gpart_count);
     HIPCHK(c, hipMemcpy(part.data(), c->d_gpart.p, c->gpart_count * sizeof(double), hipMemcpyDeviceToHost));
     // host assembly (fixed summation order -> reproducible)
-    std::vector<double> trK(L, 0.0), S1(L, 0.0);
+    std::vector<double> trK(L, 0.0);
     for (size_t i = 0; i < c->gfrob.count; ++i) trK[c->gfrob_leaf[i]] += part[i];
     for (int l = 0; l < L; ++l)
         if (c->leaves[l].owner != l) trK[l] = trK[c->leaves[l].owner];
     const double* pd = part.data() + c->gfrob.count;
     const size_t gs = (size_t)c->gstride;
-    std::vector<double> Sd;           // per leaf and dimension: contraction with dK / dlog l_d (ArdSE option, ArdSEProduct, Matern)
-    if (gs > 2) Sd.assign((size_t)L * c->D, 0.0);
-    std::vector<double> Sa(L, 0.0);   // per leaf: contraction with dK / dlog alpha (rational quadratic)
-    for (size_t i = 0; i < c->gdot.count; ++i) {
-        const int l = c->gdot_leaf[i];
-        if (KINDS[c->hyper[c->leaves[l].kid].kind].per_dim_grad) {
-            for (int d = 0; d < c->D; ++d) Sd[(size_t)l * c->D + d] += pd[gs * i + 2 + d];
-            if (KINDS[c->hyper[c->leaves[l].kid].kind].rq) Sa[l] += pd[gs * i + 2 + c->D];
-        } else {
-            S1[l] += pd[gs * i];
-        }
-    }
+    DotSums sums = reduce_dot_sums(c, c->gdot_ranges, pd, gs, false);
     for (int l = 0; l < L; ++l)
         if (c->grad_src[l] >= 0) {   // copygradients (src/fit.jl:352-356)
-            S1[l] = S1[c->grad_src[l]];
-            Sa[l] = Sa[c->grad_src[l]];
+            sums.S1[l] = sums.S1[c->grad_src[l]];
+            sums.Sa[l] = sums.Sa[c->grad_src[l]];
             if (gs > 2)
-                for (int d = 0; d < c->D; ++d) Sd[(size_t)l * c->D + d] = Sd[(size_t)c->grad_src[l] * c->D + d];
+                for (int d = 0; d < c->D; ++d) sums.Sd[(size_t)l * c->D + d] = sums.Sd[(size_t)c->grad_src[l] * c->D + d];
         }
     const double* pl = pd + gs * c->gdot.count;
     // ArdLinear: S_d = (alpha . x_d)^2 - |L^-1 x_d|^2 per leaf, the task sums added in list order
@@ -3927,9 +4049,9 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
         for (int j = 0; j < stride; ++j) g[j] = 0.0;
         if (!c->grad_active.empty() && !c->grad_active[l]) continue;      // not asked for (dsmgp_set_gradient_leaves): zeros
         GradSums q{};
-        q.S1 = S1[l];
-        q.Sd = gs > 2 ? Sd.data() + (size_t)l * c->D : nullptr;
-        q.Sa = Sa[l];
+        q.S1 = sums.S1[l];
+        q.Sd = gs > 2 ? sums.Sd.data() + (size_t)l * c->D : nullptr;
+        q.Sa = sums.Sa[l];
         q.Sl = Sl.data() + (size_t)l * c->D;
         q.trK = trK[l];
         q.ya = pl[2 * l];
@@ -4420,23 +4542,17 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "targets_gradients before solve_targets on the current fit");
     if (!grad_out) return fail(c, DSMGP_E_ARG, "targets_gradients: grad_out is NULL");
     const int L = c->L, Q = c->tg_Q, qpad = c->tg_qpad, D = c->D;
+    if (int rc = check_stride(c, "targets_gradients", stride)) return rc;
     bool any_ard = false, any_prod = false;
     for (int l = 0; l < L; ++l) {
-        const HyperHost& h = c->hyper[c->leaves[l].kid];
-        if ((int)h.loghyp.size() > stride) return fail(c, DSMGP_E_ARG, "targets_gradients: stride smaller than the hyper-vector");
-        any_ard = any_ard || (h.kind == DSMGP_KIND_ARD_SE && c->ard_true_gradient);
-        any_prod = any_prod || h.kind == DSMGP_KIND_ARD_SE_PRODUCT || KINDS[h.kind].matern || KINDS[h.kind].rq;
+        const int kind_l = c->hyper[c->leaves[l].kid].kind;
+        any_ard = any_ard || (kind_l == DSMGP_KIND_ARD_SE && c->ard_true_gradient);
+        any_prod = any_prod || KINDS[kind_l].dot_pass != 0;
     }
     if (any_ard && D > GRADDOT_STAGE_D)
         return fail(c, DSMGP_E_ARG, "ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
-    std::vector<double> W((size_t)L * Q, 1.0), sw((size_t)L, 0.0);
-    if (col_weight)
-        for (size_t i = 0; i < W.size(); ++i) {
-            if (!std::isfinite(col_weight[i])) return fail(c, DSMGP_E_ARG, "targets_gradients: non-finite value in col_weight");
-            W[i] = col_weight[i];
-        }
-    for (int l = 0; l < L; ++l)
-        for (int q = 0; q < Q; ++q) sw[(size_t)l] += W[(size_t)l + (size_t)q * L];
+    std::vector<double> W, sw;
+    if (int rc = column_weights(c, "targets_gradients", col_weight, false, W, sw)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     // L^-T of every factor owner (xinv_lists / xinv_fill); lists of the call's own are dropped again on every way out
     OwnGradLists own_lists{c};
@@ -4464,67 +4580,22 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
             frob_leaf.push_back(l);
         }
     }
-    // contraction tiles in the order of build_grad_plan: IsoSE / ArdSE | ArdSEProduct | Matern | rational quadratic, super-tiles of
-    // GS x GS tiles per leaf, dealt to the XCDs by work
-    constexpr int GS = 4;
-    std::vector<GradTaskTg> gd;
-    std::vector<int> gd_leaf;
-    std::vector<size_t> gblock;
-    size_t first[5] = {0, 0, 0, 0, 0};
-    for (int pass = 0; pass < 4; ++pass) {
-        first[pass] = gd.size();
-        const size_t begin = gd.size();
-        gblock.clear();
-        for (int l = 0; l < L; ++l) {
-            const LeafHost& lf = c->leaves[l];
-            const int kind_l = c->hyper[lf.kid].kind;
-            const bool ard = kind_l == DSMGP_KIND_ARD_SE && c->ard_true_gradient;
-            if (!KINDS[kind_l].contraction && !ard) continue;
-            if ((kind_l == DSMGP_KIND_ARD_SE_PRODUCT ? 1 : KINDS[kind_l].matern ? 2 : KINDS[kind_l].rq ? 3 : 0) != pass) continue;
-            const LeafDev& d = c->h_leaves[l];
-            const int ldt = c->leaves[lf.owner].npad;
-            for (int ib = 0; ib < lf.nb; ib += GS) {
-                gblock.push_back(gd.size() - begin);
-                for (int jb = 0; jb <= ib; jb += GS)
-                    for (int i = ib; i < std::min(ib + GS, lf.nb); ++i)
-                        for (int j = jb; j < std::min(jb + GS, i + 1); ++j) {
-                            GradTaskTg g{};
-                            g.gemm.A = Xt(l) + (size_t)i * TB;
-                            g.gemm.B = Xt(l) + (size_t)j * TB;
-                            g.gemm.C = nullptr;
-                            g.gemm.lda = g.gemm.ldb = ldt;
-                            g.gemm.ldc = TB;
-                            g.gemm.k0 = i * TB;
-                            g.gemm.k1 = lf.npad;
-                            g.gemm.update = 0;
-                            g.xa = d.Xg + (size_t)i * TB;
-                            g.xb = d.Xg + (size_t)j * TB;
-                            g.alpha_a = d.alpha + (size_t)i * TB;
-                            g.alpha_b = d.alpha + (size_t)j * TB;
-                            g.ldx = lf.npad;
-                            g.na = std::max(0, std::min(TB, lf.n - i * TB));
-                            g.nb = std::max(0, std::min(TB, lf.n - j * TB));
-                            g.diag = (i == j);
-                            g.kid = lf.kid;
-                            g.Aa = Al(l) + (size_t)i * TB;
-                            g.Ab = Al(l) + (size_t)j * TB;
-                            g.wq = c->d_tgw.p;      // + l once the buffer is there (below)
-                            g.sw = sw[(size_t)l];
-                            g.lda_t = lf.npad;
-                            g.ldw = L;
-                            g.Q = Q;
-                            g.qpad = qpad;
-                            gd.push_back(g);
-                            gd_leaf.push_back(l);
-                        }
-            }
-        }
-        gblock.push_back(gd.size() - begin);
-        std::vector<double> work(gd.size() - begin);
-        for (size_t i = 0; i < work.size(); ++i) work[i] = (double)(gd[begin + i].gemm.k1 - gd[begin + i].gemm.k0) + 64.0 + qpad;
-        xcd_deal_by_work(gd, gd_leaf, begin, gd.size(), gblock, work, c->xcd_order);
-    }
-    first[4] = gd.size();
+    // contraction tiles (build_dot_list), as dsmgp_gradients lists them but for every leaf; the columns add qpad to a task's cost
+    DotRanges ranges;
+    std::vector<GradTaskTg> gd = build_dot_list<GradTaskTg>(
+        c, ranges, 64.0 + qpad, [&](int, int kind) { return kind != DSMGP_KIND_ARD_SE || c->ard_true_gradient; },
+        [&](int l) { return DotOperand{Xt(l), c->leaves[c->leaves[l].owner].npad, true, c->h_leaves[l].alpha}; },
+        [&](GradTaskTg& g, int l, int i, int j) {
+            g.Aa = Al(l) + (size_t)i * TB;
+            g.Ab = Al(l) + (size_t)j * TB;
+            g.wq = c->d_tgw.p;      // + l once the buffer is there (below)
+            g.sw = sw[(size_t)l];
+            g.lda_t = c->leaves[l].npad;
+            g.ldw = L;
+            g.Q = Q;
+            g.qpad = qpad;
+        });
+    const std::vector<int>& gd_leaf = ranges.leaf_of;
     // ArdLinear leaves: |L^-1 x_d|^2 by ardlin_quad_kernel (its alpha sums are not used: any vector of the leaf serves), and the
     // weighted squares of a_q . x_d
     std::vector<ArdLinTask> quad;
@@ -4535,18 +4606,7 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
         const LeafHost& lf = c->leaves[l];
         if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR) continue;
         const LeafDev& d = c->h_leaves[l];
-        for (int c0 = 0; c0 < lf.n; c0 += ARDLIN_COLS) {
-            ArdLinTask a{};
-            a.Xt = Xt(l);
-            a.x = d.Xg;
-            a.alpha = d.Xg;
-            a.ldt = c->leaves[lf.owner].npad;
-            a.ldx = lf.npad;
-            a.c0 = c0;
-            a.n = lf.n;
-            quad.push_back(a);
-            quad_leaf.push_back(l);
-        }
+        ardlin_tasks(quad, quad_leaf, l, lf, Xt(l), c->leaves[lf.owner].npad, d.Xg, d.Xg);
         TargetsArdLinTask t{};
         t.A = Al(l);
         t.x = d.Xg;
@@ -4580,18 +4640,7 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     if (int rc = ensure_dinv(c)) return rc;
     if (int rc = xinv_fill(c)) return rc;
     if (!ta.empty()) targets_a_kernel<<<(unsigned)ta.size(), 256, 0, c->stream>>>(c->tga.p, qpad);
-    if (first[1] > first[0])
-        tile_graddot_kernel<GD_TARGETS><<<(unsigned)(first[1] - first[0]), 256, 0, c->stream>>>(c->tgdot.p + first[0], c->d_kp.p, D,
-                                                                                              pdot + (size_t)gs * first[0], gs);
-    if (first[2] > first[1])
-        tile_graddot_prod_kernel<GD_TARGETS><<<(unsigned)(first[2] - first[1]), 256, 0, c->stream>>>(c->tgdot.p + first[1], c->d_kp.p, D,
-                                                                                                   pdot + (size_t)gs * first[1], gs);
-    if (first[3] > first[2])
-        tile_graddot_matern_kernel<GD_TARGETS><<<(unsigned)(first[3] - first[2]), 256, 0, c->stream>>>(c->tgdot.p + first[2], c->d_kp.p, D,
-                                                                                                     pdot + (size_t)gs * first[2], gs);
-    if (first[4] > first[3])
-        tile_graddot_rq_kernel<GD_TARGETS><<<(unsigned)(first[4] - first[3]), 256, 0, c->stream>>>(c->tgdot.p + first[3], c->d_kp.p, D,
-                                                                                                 pdot + (size_t)gs * first[3], gs);
+    launch_graddot<GD_TARGETS>(c, c->tgdot.p, ranges, pdot, gs);
     if (!frob.empty()) frob_kernel<<<(unsigned)frob.size(), 256, 0, c->stream>>>(c->tgfrob.p, pfrob);
     targets_wsums_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->arenaT, c->d_toff.p, c->arenaA, c->d_tgw.p, L, Q, qpad, pleaf);
     if (!quad.empty())
@@ -4610,22 +4659,12 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     std::vector<int> info((size_t)L);
     HIPCHK(c, hipMemcpy(info.data(), c->d_info.p, (size_t)L * sizeof(int), hipMemcpyDeviceToHost));
     // host assembly, every sum in list order
-    std::vector<double> trG((size_t)L, 0.0), S1((size_t)L, 0.0), Sa((size_t)L, 0.0), Sd, Sl((size_t)L * D, 0.0);
+    std::vector<double> trG((size_t)L, 0.0), Sl((size_t)L * D, 0.0);
     for (size_t i = 0; i < frob.size(); ++i) trG[(size_t)frob_leaf[i]] += part[i];
     for (int l = 0; l < L; ++l)
         if (c->leaves[l].owner != l) trG[(size_t)l] = trG[(size_t)c->leaves[l].owner];
-    if (gs > 2) Sd.assign((size_t)L * D, 0.0);
     const double* pd = part.data() + frob.size();
-    for (size_t i = 0; i < gd.size(); ++i) {
-        const size_t l = (size_t)gd_leaf[i];
-        const KindInfo& ki = KINDS[c->hyper[c->leaves[l].kid].kind];
-        if (ki.per_dim_grad) {
-            for (int d = 0; d < D; ++d) Sd[l * D + d] += pd[(size_t)gs * i + 2 + d];
-            if (ki.rq) Sa[l] += pd[(size_t)gs * i + 2 + D];
-        } else {
-            S1[l] += pd[(size_t)gs * i];
-        }
-    }
+    const DotSums sums = reduce_dot_sums(c, ranges, pd, (size_t)gs, false);
     const double* pl = pd + (size_t)gs * gd.size();
     const double* pq = pl + 2 * (size_t)L;
     const double* pa = pq + 2 * (size_t)D * quad.size();
@@ -4648,9 +4687,9 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
             continue;
         }
         GradSums q{};
-        q.S1 = S1[(size_t)l];
-        q.Sd = gs > 2 ? Sd.data() + (size_t)l * D : nullptr;
-        q.Sa = Sa[(size_t)l];
+        q.S1 = sums.S1[(size_t)l];
+        q.Sd = gs > 2 ? sums.Sd.data() + (size_t)l * D : nullptr;
+        q.Sa = sums.Sa[(size_t)l];
         q.Sl = Sl.data() + (size_t)l * D;
         q.trK = sw[(size_t)l] * trG[(size_t)l];
         q.ya = pl[2 * l];
@@ -4666,30 +4705,6 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
 // the bit and everything that call promises about dsmgp_gradients and the mask holds here too; then the passes of this call's
 // own lists over an arena of their own.  Nothing the gradient pass or dsmgp_loo reads is written.
 namespace {
-// The lower tiles (i, j) of a leaf in the super-tile order of build_grad_plan (GS x GS tiles per super-tile), the start of every
-// block of GS tile rows marked in `gblock`; and the XCD dealing of the tasks listed that way, by the length of their K range.
-constexpr int LOO_GS = 4;
-extern "C++" {      // (templates cannot have C linkage)
-template <class SizeNow, class Emit>
-void each_lower_tile(const LeafHost& lf, std::vector<size_t>& gblock, size_t begin, SizeNow&& size_now, Emit&& emit) {
-    constexpr int GS = LOO_GS;
-    for (int ib = 0; ib < lf.nb; ib += GS) {
-        gblock.push_back(size_now() - begin);
-        for (int jb = 0; jb <= ib; jb += GS)
-            for (int i = ib; i < std::min(ib + GS, lf.nb); ++i)
-                for (int j = jb; j < std::min(jb + GS, i + 1); ++j)
-                    emit(i, j, std::max(0, std::min(TB, lf.n - i * TB)), std::max(0, std::min(TB, lf.n - j * TB)));
-    }
-}
-template <class Tasks>
-void deal_tiles(dsmgp_ctx* c, Tasks& tasks, std::vector<int>& leaf_of, size_t begin, std::vector<size_t>& gblock) {
-    gblock.push_back(tasks.size() - begin);
-    std::vector<double> work(tasks.size() - begin);
-    for (size_t i = 0; i < work.size(); ++i) work[i] = (double)(tasks[begin + i].gemm.k1 - tasks[begin + i].gemm.k0) + 64.0;
-    xcd_deal_by_work(tasks, leaf_of, begin, tasks.size(), gblock, work, c->xcd_order);
-}
-}  // extern "C++"
-
 int build_loo_grad_plan(dsmgp_ctx* c) {
     const int L = c->L;
     const int D = c->D;
@@ -4740,91 +4755,21 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
             c->lghvec_leaf.push_back(l);
         }
     }
-    // tiles of G, then of the contraction: the super-tile order and the XCD dealing of build_grad_plan
-    std::vector<size_t> gblock;
-    std::vector<GinvTask> gi;
-    std::vector<int> gi_leaf;
-    for (int l = 0; l < L; ++l) {
-        const LeafHost& lf = c->leaves[l];
-        if (c->grad_src[l] >= 0) continue;
-        each_lower_tile(lf, gblock, 0, [&] { return gi.size(); }, [&](int i, int j, int na, int nb) {
-            GinvTask g{};
-            g.gemm.A = Xt(l) + (size_t)i * TB;
-            g.gemm.B = Xt(l) + (size_t)j * TB;
-            g.gemm.C = H(l) + (size_t)i * TB + (size_t)j * TB * lf.npad;
-            g.Ct = H(l) + (size_t)j * TB + (size_t)i * TB * lf.npad;
-            g.gemm.lda = g.gemm.ldb = g.gemm.ldc = lf.npad;
-            g.gemm.k0 = i * TB;
-            g.gemm.k1 = lf.npad;
-            g.sw_a = V(l) + 2 * (size_t)lf.npad + (size_t)i * TB;
-            g.sw_b = V(l) + 2 * (size_t)lf.npad + (size_t)j * TB;
-            g.na = na;
-            g.nb = nb;
-            g.diag = (i == j);
-            gi.push_back(g);
-            gi_leaf.push_back(l);
-        });
-    }
-    deal_tiles(c, gi, gi_leaf, 0, gblock);
-    // the contraction, as gdot: IsoSE and ArdSE leaves (pass 0), ArdSEProduct (1), Matern (2), rational quadratic (3), each run
-    // by its own kernel
-    std::vector<GradTask> gd;
-    c->lgdot_leaf.clear();
-    for (int pass = 0; pass < 4; ++pass) {
-        if (pass == 1) c->lgdot_prod0 = gd.size();
-        if (pass == 2) c->lgdot_mat0 = gd.size();
-        if (pass == 3) c->lgdot_rq0 = gd.size();
-        const size_t begin = gd.size();
-        gblock.clear();
-        for (int l = 0; l < L; ++l) {
-            const LeafHost& lf = c->leaves[l];
-            if (c->grad_src[l] >= 0) continue;
-            const int kind_l = c->hyper[lf.kid].kind;
-            if (!KINDS[kind_l].contraction && kind_l != DSMGP_KIND_ARD_SE) continue;
-            if ((kind_l == DSMGP_KIND_ARD_SE_PRODUCT ? 1 : KINDS[kind_l].matern ? 2 : KINDS[kind_l].rq ? 3 : 0) != pass) continue;
-            const LeafDev& d = c->h_leaves[l];
-            each_lower_tile(lf, gblock, begin, [&] { return gd.size(); }, [&](int i, int j, int na, int nb) {
-                GradTask g{};
-                g.gemm.A = H(l) + (size_t)i * TB;
-                g.gemm.B = H(l) + (size_t)j * TB;
-                g.gemm.C = nullptr;
-                g.gemm.lda = g.gemm.ldb = lf.npad;
-                g.gemm.ldc = TB;
-                g.gemm.k0 = 0;
-                g.gemm.k1 = lf.npad;
-                g.xa = d.Xg + (size_t)i * TB;
-                g.xb = d.Xg + (size_t)j * TB;
-                g.alpha_a = V(l) + (size_t)i * TB;
-                g.alpha_b = V(l) + (size_t)j * TB;
-                g.uoff = lf.npad;
-                g.ldx = lf.npad;
-                g.na = na;
-                g.nb = nb;
-                g.diag = (i == j);
-                g.kid = lf.kid;
-                gd.push_back(g);
-                c->lgdot_leaf.push_back(l);
-            });
-        }
-        deal_tiles(c, gd, c->lgdot_leaf, begin, gblock);
-    }
+    // tiles of H (build_ginv_list), then of the contraction (build_dot_list): ArdSE leaves always have tasks here
+    auto computes = [&](int l) { return c->grad_src[l] < 0; };
+    const std::vector<GinvTask> gi = build_ginv_list(c, computes, [&](int l) {
+        return GinvPlace{Xt(l), c->leaves[l].npad, H(l), V(l) + 2 * (size_t)c->leaves[l].npad};
+    });
+    const std::vector<GradTask> gd = build_dot_list<GradTask>(
+        c, c->lgdot_ranges, 64.0, [&](int l, int) { return computes(l); },
+        [&](int l) { return DotOperand{H(l), c->leaves[l].npad, false, V(l)}; },
+        [&](GradTask& g, int l, int, int) { g.uoff = c->leaves[l].npad; });
     std::vector<ArdLinTask> al;
     c->lgardlin_leaf.clear();
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
-        if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR || c->grad_src[l] >= 0) continue;
-        for (int c0 = 0; c0 < lf.n; c0 += ARDLIN_COLS) {
-            ArdLinTask a{};
-            a.Xt = H(l);
-            a.x = c->h_leaves[l].Xg;
-            a.alpha = V(l);
-            a.ldt = lf.npad;
-            a.ldx = lf.npad;      // also the distance from alpha to u in the vector block (ardlin_quad_kernel<true>)
-            a.c0 = c0;
-            a.n = lf.n;
-            al.push_back(a);
-            c->lgardlin_leaf.push_back(l);
-        }
+        if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR || !computes(l)) continue;
+        ardlin_tasks(al, c->lgardlin_leaf, l, lf, H(l), lf.npad, c->h_leaves[l].Xg, V(l));
     }
     if (int rc = dev_upload(c, c->lgvec, vt)) return rc;
     if (int rc = dev_upload(c, c->lghvec, hv)) return rc;
@@ -4884,9 +4829,7 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
     if (!grad_out) return fail(c, DSMGP_E_ARG, "grad_out is NULL");
     const int L = c->L;
     const int D = c->D;
-    for (int l = 0; l < L; ++l)
-        if ((int)c->hyper[c->leaves[l].kid].loghyp.size() > stride)
-            return fail(c, DSMGP_E_ARG, "loo_gradients: stride smaller than the hyper-vector");
+    if (int rc = check_stride(c, "loo_gradients", stride)) return rc;
     std::vector<double> lpd((size_t)L);
     double sec_loo = 0.0;
     if (int rc = dsmgp_loo(c, nullptr, nullptr, lpd.data(), &sec_loo)) return rc;
@@ -4908,14 +4851,7 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
     loo_weights_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->lleaf.p, c->lgvec.p, pw);
     if (c->lginv.count) tile_ginv_kernel<<<(unsigned)c->lginv.count, 256, 0, c->stream>>>(c->lginv.p);
     if (c->lghvec.count) loo_hvec_kernel<<<(unsigned)c->lghvec.count, 256, 0, c->stream>>>(c->lghvec.p, ph);
-    const size_t np0 = c->lgdot_prod0, nm0 = c->lgdot_mat0, nr0 = c->lgdot_rq0, nd = c->lgdot.count;
-    if (np0) tile_graddot_kernel<GD_LOO><<<(int)np0, 256, 0, c->stream>>>(c->lgdot.p, c->d_kp.p, D, pdot, gs);
-    if (nm0 > np0)
-        tile_graddot_prod_kernel<GD_LOO><<<(int)(nm0 - np0), 256, 0, c->stream>>>(c->lgdot.p + np0, c->d_kp.p, D, pdot + (size_t)gs * np0, gs);
-    if (nr0 > nm0)
-        tile_graddot_matern_kernel<GD_LOO><<<(int)(nr0 - nm0), 256, 0, c->stream>>>(c->lgdot.p + nm0, c->d_kp.p, D, pdot + (size_t)gs * nm0, gs);
-    if (nd > nr0)
-        tile_graddot_rq_kernel<GD_LOO><<<(int)(nd - nr0), 256, 0, c->stream>>>(c->lgdot.p + nr0, c->d_kp.p, D, pdot + (size_t)gs * nr0, gs);
+    launch_graddot<GD_LOO>(c, c->lgdot.p, c->lgdot_ranges, pdot, gs);
     if (c->lgardlin.count)
         ardlin_quad_kernel<true><<<dim3((unsigned)c->lgardlin.count, (unsigned)((D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
             c->lgardlin.p, D, pal);
@@ -4931,21 +4867,13 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
     const double* hw = part.data();
     const double* hh = hw + 2 * (size_t)L;
     const double* hd = hh + 2 * c->lghvec.count;
-    const double* ha = hd + (size_t)gs * nd;
-    std::vector<double> frob(L, 0.0), ua(L, 0.0), S1(L, 0.0), SK(L, 0.0), Sd((size_t)L * D, 0.0), Sa(L, 0.0);
+    const double* ha = hd + (size_t)gs * c->lgdot.count;
+    std::vector<double> frob(L, 0.0), ua(L, 0.0);
     for (size_t i = 0; i < c->lghvec.count; ++i) {
         frob[c->lghvec_leaf[i]] += hh[2 * i];
         ua[c->lghvec_leaf[i]] += hh[2 * i + 1];
     }
-    for (size_t i = 0; i < nd; ++i) {
-        const size_t l = (size_t)c->lgdot_leaf[i];
-        S1[l] += hd[gs * i];
-        SK[l] += hd[gs * i + 1];
-        const int kind_l = c->hyper[c->leaves[l].kid].kind;      // IsoSE tasks write no per-dimension sums
-        if (kind_l == DSMGP_KIND_ARD_SE || KINDS[kind_l].per_dim_grad)
-            for (int d = 0; d < D; ++d) Sd[l * D + d] += hd[gs * i + 2 + d];
-        if (KINDS[kind_l].rq) Sa[l] += hd[gs * i + 2 + D];
-    }
+    const DotSums sums = reduce_dot_sums(c, c->lgdot_ranges, hd, (size_t)gs, true);
     std::vector<double> A, U, Q;
     if (c->lgardlin.count) {
         A.assign((size_t)L * D, 0.0);
@@ -4972,10 +4900,10 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
             continue;
         }
         LooSums q{};
-        q.S1 = S1[s];
-        q.SK = SK[s];
-        q.Sa = Sa[s];
-        q.Sd = Sd.data() + s * D;
+        q.S1 = sums.S1[s];
+        q.SK = sums.SK[s];
+        q.Sa = sums.Sa[s];
+        q.Sd = sums.Sd.data() + s * D;
         q.trM = ua[s] - frob[s];                                  // tr M = u . alpha - |H|_F^2
         q.trMKy = hw[2 * s] - hw[2 * s + 1];                      // tr(M K_y) = sum alpha_i^2 / d_i - sum w_i d_i
         if (h.kind == DSMGP_KIND_ARD_LINEAR) {
@@ -5064,23 +4992,13 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "loo_columns_gradients before solve_targets on the current fit");
     if (!grad_out) return fail(c, DSMGP_E_ARG, "loo_columns_gradients: grad_out is NULL");
     const int L = c->L, Q = c->tg_Q, qpad = c->tg_qpad, D = c->D;
+    if (int rc = check_stride(c, "loo_columns_gradients", stride)) return rc;
     bool any_ardse = false;
-    for (int l = 0; l < L; ++l) {
-        const HyperHost& h = c->hyper[c->leaves[l].kid];
-        if ((int)h.loghyp.size() > stride) return fail(c, DSMGP_E_ARG, "loo_columns_gradients: stride smaller than the hyper-vector");
-        any_ardse = any_ardse || h.kind == DSMGP_KIND_ARD_SE;
-    }
+    for (int l = 0; l < L; ++l) any_ardse = any_ardse || c->hyper[c->leaves[l].kid].kind == DSMGP_KIND_ARD_SE;
     if (any_ardse && D > GRADDOT_STAGE_D)
         return fail(c, DSMGP_E_ARG, "loo_columns_gradients: ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
-    std::vector<double> W((size_t)L * Q, 1.0), sw((size_t)L, 0.0);
-    if (col_weight)
-        for (size_t i = 0; i < W.size(); ++i) {
-            if (!std::isfinite(col_weight[i]) || col_weight[i] < 0.0)
-                return fail(c, DSMGP_E_ARG, "loo_columns_gradients: non-finite or negative value in col_weight");
-            W[i] = col_weight[i];
-        }
-    for (int l = 0; l < L; ++l)
-        for (int q = 0; q < Q; ++q) sw[(size_t)l] += W[(size_t)l + (size_t)q * L];
+    std::vector<double> W, sw;
+    if (int rc = column_weights(c, "loo_columns_gradients", col_weight, true, W, sw)) return rc;
     auto active = [&](int l) { return sw[(size_t)l] > 0.0; };      // a row of zero weights: a row of zeros and no tasks
     HIPCHK(c, hipSetDevice(c->device));
     OwnGradLists own_lists{c};
@@ -5148,82 +5066,27 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
             rt_leaf.push_back(l);
         }
     }
-    // tiles of H, then of the contraction, in the order and the dealing of dsmgp_loo_gradients
-    std::vector<size_t> gblock;
-    std::vector<GinvTask> gi;
-    std::vector<int> gi_leaf;
-    for (int l = 0; l < L; ++l) {
-        const LeafHost& lf = c->leaves[l];
-        if (!active(l)) continue;
-        const int ldt = c->leaves[lf.owner].npad;
-        each_lower_tile(lf, gblock, 0, [&] { return gi.size(); }, [&](int i, int j, int na, int nb) {
-            GinvTask g{};
-            g.gemm.A = Xt(l) + (size_t)i * TB;
-            g.gemm.B = Xt(l) + (size_t)j * TB;
-            g.gemm.C = H(l) + (size_t)i * TB + (size_t)j * TB * lf.npad;
-            g.Ct = H(l) + (size_t)j * TB + (size_t)i * TB * lf.npad;
-            g.gemm.lda = g.gemm.ldb = ldt;
-            g.gemm.ldc = lf.npad;
-            g.gemm.k0 = i * TB;
-            g.gemm.k1 = lf.npad;
-            g.sw_a = V(l) + (size_t)lf.npad + (size_t)i * TB;
-            g.sw_b = V(l) + (size_t)lf.npad + (size_t)j * TB;
-            g.na = na;
-            g.nb = nb;
-            g.diag = (i == j);
-            gi.push_back(g);
-            gi_leaf.push_back(l);
+    // tiles of H (build_ginv_list), then of the contraction (build_dot_list), as dsmgp_loo_gradients lists them but for every
+    // leaf with weight
+    const std::vector<GinvTask> gi = build_ginv_list(c, active, [&](int l) {
+        return GinvPlace{Xt(l), c->leaves[c->leaves[l].owner].npad, H(l), V(l) + (size_t)c->leaves[l].npad};
+    });
+    DotRanges ranges;
+    const std::vector<GradTaskLc> gd = build_dot_list<GradTaskLc>(
+        c, ranges, 64.0, [&](int l, int) { return active(l); },
+        // (the vector block is staged by the epilogues, never in a weight: any vector of the leaf serves)
+        [&](int l) { return DotOperand{H(l), c->leaves[l].npad, false, V(l)}; },
+        [&](GradTaskLc& g, int l, int i, int j) {
+            g.Aa = Al(l) + (size_t)i * TB;
+            g.Ab = Al(l) + (size_t)j * TB;
+            g.Ua = Ul(l) + (size_t)i * TB;
+            g.Ub = Ul(l) + (size_t)j * TB;
+            g.wq = wdev + l;
+            g.lda_t = c->leaves[l].npad;
+            g.ldw = L;
+            g.Q = Q;
+            g.qpad = qpad;
         });
-    }
-    deal_tiles(c, gi, gi_leaf, 0, gblock);
-    std::vector<GradTaskLc> gd;
-    std::vector<int> gd_leaf;
-    size_t first[5] = {0, 0, 0, 0, 0};
-    for (int pass = 0; pass < 4; ++pass) {
-        first[pass] = gd.size();
-        const size_t begin = gd.size();
-        gblock.clear();
-        for (int l = 0; l < L; ++l) {
-            const LeafHost& lf = c->leaves[l];
-            if (!active(l)) continue;
-            const int kind_l = c->hyper[lf.kid].kind;
-            if (!KINDS[kind_l].contraction && kind_l != DSMGP_KIND_ARD_SE) continue;
-            if ((kind_l == DSMGP_KIND_ARD_SE_PRODUCT ? 1 : KINDS[kind_l].matern ? 2 : KINDS[kind_l].rq ? 3 : 0) != pass) continue;
-            const LeafDev& d = c->h_leaves[l];
-            each_lower_tile(lf, gblock, begin, [&] { return gd.size(); }, [&](int i, int j, int na, int nb) {
-                GradTaskLc g{};
-                g.gemm.A = H(l) + (size_t)i * TB;
-                g.gemm.B = H(l) + (size_t)j * TB;
-                g.gemm.C = nullptr;
-                g.gemm.lda = g.gemm.ldb = lf.npad;
-                g.gemm.ldc = TB;
-                g.gemm.k0 = 0;
-                g.gemm.k1 = lf.npad;
-                g.xa = d.Xg + (size_t)i * TB;
-                g.xb = d.Xg + (size_t)j * TB;
-                g.alpha_a = V(l) + (size_t)i * TB;      // staged by the epilogues, never in a weight: any vector of the leaf serves
-                g.alpha_b = V(l) + (size_t)j * TB;
-                g.ldx = lf.npad;
-                g.na = na;
-                g.nb = nb;
-                g.diag = (i == j);
-                g.kid = lf.kid;
-                g.Aa = Al(l) + (size_t)i * TB;
-                g.Ab = Al(l) + (size_t)j * TB;
-                g.Ua = Ul(l) + (size_t)i * TB;
-                g.Ub = Ul(l) + (size_t)j * TB;
-                g.wq = wdev + l;
-                g.lda_t = lf.npad;
-                g.ldw = L;
-                g.Q = Q;
-                g.qpad = qpad;
-                gd.push_back(g);
-                gd_leaf.push_back(l);
-            });
-        }
-        deal_tiles(c, gd, gd_leaf, begin, gblock);
-    }
-    first[4] = gd.size();
     // ArdLinear leaves: |H^T x_d|^2 by ardlin_quad_kernel<true> (its two vector sums are not used: any block of the leaf serves) and
     // the weighted products of x_d . u_q and x_d . a_q
     std::vector<ArdLinTask> quad;
@@ -5234,18 +5097,7 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
         const LeafHost& lf = c->leaves[l];
         if (c->hyper[lf.kid].kind != DSMGP_KIND_ARD_LINEAR || !active(l)) continue;
         const LeafDev& d = c->h_leaves[l];
-        for (int c0 = 0; c0 < lf.n; c0 += ARDLIN_COLS) {
-            ArdLinTask a{};
-            a.Xt = H(l);
-            a.x = d.Xg;
-            a.alpha = V(l);
-            a.ldt = lf.npad;
-            a.ldx = lf.npad;
-            a.c0 = c0;
-            a.n = lf.n;
-            quad.push_back(a);
-            quad_leaf.push_back(l);
-        }
+        ardlin_tasks(quad, quad_leaf, l, lf, H(l), lf.npad, d.Xg, V(l));
         LooColsArdLinTask t{};
         t.A = Al(l);
         t.U = Ul(l);
@@ -5285,18 +5137,7 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     if (!gi.empty()) tile_ginv_kernel<<<(unsigned)gi.size(), 256, 0, c->stream>>>(c->lcginv.p);
     if (!ut.empty()) loo_columns_u_kernel<<<(unsigned)ut.size(), 256, 0, c->stream>>>(c->lcu.p, qpad);
     if (!rt.empty()) loo_columns_rowsums_kernel<<<(unsigned)rt.size(), 256, 0, c->stream>>>(c->lcrow.p, prow);
-    if (first[1] > first[0])
-        tile_graddot_kernel<GD_LOO_COLUMNS><<<(unsigned)(first[1] - first[0]), 256, 0, c->stream>>>(c->lcdot.p + first[0], c->d_kp.p, D,
-                                                                                                  pdot + (size_t)gs * first[0], gs);
-    if (first[2] > first[1])
-        tile_graddot_prod_kernel<GD_LOO_COLUMNS><<<(unsigned)(first[2] - first[1]), 256, 0, c->stream>>>(c->lcdot.p + first[1], c->d_kp.p, D,
-                                                                                                       pdot + (size_t)gs * first[1], gs);
-    if (first[3] > first[2])
-        tile_graddot_matern_kernel<GD_LOO_COLUMNS><<<(unsigned)(first[3] - first[2]), 256, 0, c->stream>>>(c->lcdot.p + first[2], c->d_kp.p, D,
-                                                                                                         pdot + (size_t)gs * first[2], gs);
-    if (first[4] > first[3])
-        tile_graddot_rq_kernel<GD_LOO_COLUMNS><<<(unsigned)(first[4] - first[3]), 256, 0, c->stream>>>(c->lcdot.p + first[3], c->d_kp.p, D,
-                                                                                                     pdot + (size_t)gs * first[3], gs);
+    launch_graddot<GD_LOO_COLUMNS>(c, c->lcdot.p, ranges, pdot, gs);
     if (!quad.empty())
         ardlin_quad_kernel<true><<<dim3((unsigned)quad.size(), (unsigned)((D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
             c->lcquad.p, D, pquad);
@@ -5318,21 +5159,12 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     const double* hd = hr + 2 * rt.size();
     const double* hq = hd + (size_t)gs * gd.size();
     const double* ha = hq + 3 * (size_t)D * quad.size();
-    std::vector<double> frob((size_t)L, 0.0), ua((size_t)L, 0.0), S1((size_t)L, 0.0), SK((size_t)L, 0.0), Sd((size_t)L * D, 0.0),
-        Sa((size_t)L, 0.0), xMx((size_t)L * D, 0.0);
+    std::vector<double> frob((size_t)L, 0.0), ua((size_t)L, 0.0), xMx((size_t)L * D, 0.0);
     for (size_t i = 0; i < rt.size(); ++i) {
         frob[(size_t)rt_leaf[i]] += hr[2 * i];
         ua[(size_t)rt_leaf[i]] += hr[2 * i + 1];
     }
-    for (size_t i = 0; i < gd.size(); ++i) {
-        const size_t l = (size_t)gd_leaf[i];
-        S1[l] += hd[gs * i];
-        SK[l] += hd[gs * i + 1];
-        const int kind_l = c->hyper[c->leaves[l].kid].kind;      // IsoSE tasks write no per-dimension sums
-        if (kind_l == DSMGP_KIND_ARD_SE || KINDS[kind_l].per_dim_grad)
-            for (int d = 0; d < D; ++d) Sd[l * D + d] += hd[gs * i + 2 + d];
-        if (KINDS[kind_l].rq) Sa[l] += hd[gs * i + 2 + D];
-    }
+    const DotSums sums = reduce_dot_sums(c, ranges, hd, (size_t)gs, true);
     for (size_t i = 0; i < al.size(); ++i)
         for (int d = 0; d < D; ++d) xMx[(size_t)al_leaf[i] * D + d] = ha[i * D + d];
     for (size_t i = 0; i < quad.size(); ++i)                      // x_d^T M x_d = sum_q c_q (x_d . u_q)(x_d . a_q) - |H^T x_d|^2
@@ -5348,10 +5180,10 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
         }
         if (!active(l)) continue;
         LooSums q{};
-        q.S1 = S1[(size_t)l];
-        q.SK = SK[(size_t)l];
-        q.Sa = Sa[(size_t)l];
-        q.Sd = Sd.data() + (size_t)l * D;
+        q.S1 = sums.S1[(size_t)l];
+        q.SK = sums.SK[(size_t)l];
+        q.Sa = sums.Sa[(size_t)l];
+        q.Sd = sums.Sd.data() + (size_t)l * D;
         q.xMx = xMx.data() + (size_t)l * D;
         q.trM = ua[(size_t)l] - frob[(size_t)l];                  // tr M = sum_q c_q u_q . a_q - |H|_F^2
         q.trMKy = hw[2 * l] - hw[2 * l + 1];                      // tr(M K_y) = sum_q c_q sum_i a_iq^2 / d_i - sum_i W_i d_i
