@@ -542,6 +542,7 @@ struct dsmgp_ctx {
     bool joint = true;              // fit advances the resident test rows too
     bool joint_ready = false;
     bool vt_valid = false;          // Vt holds K_tn L^-T for the current factor
+    bool vt_from_fit = false;       // ... because the rows rode through the fit (else: the standalone sweep of predict_run made it)
     bool last_fit_joint = false;
     int ncu = 256;
     bool xcd_order = true;          // XCD-aware task order (speed only)
@@ -2581,6 +2582,9 @@ int dsmgp_set_hyper(dsmgp_ctx* c, int32_t kernel_id, int32_t kind, const double*
     if (any_matern(c) != had_matern || any_rq(c) != had_rq) drop_graphs(c);
     c->fitted = false;
     c->predicted = false;
+    // the partial sums and the aggregated moments belong to the prediction that just fell; the rBCM finish would also read the
+    // prior variance from the NEXT KParam table (upload_hyper overwrites it)
+    c->agg_partial_ready = c->agg_done = c->agg_total = false;
     c->vt_valid = false;
     return 0;
 }
@@ -2736,7 +2740,9 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
     }
     c->fitted = true;
     c->predicted = false;
+    c->agg_partial_ready = c->agg_done = c->agg_total = false;   // they fall with the prediction they were summed from
     c->vt_valid = joint;
+    c->vt_from_fit = joint;
     c->last_fit_joint = joint;
     c->dinv_complete = c->dinvc_all.count == 0;
     return 0;
@@ -3269,17 +3275,22 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
             // V^T = K_tn L^-T, block column by block column (src/gaussianprocess.jl:120), lane by lane on the lanes' streams
             if (int rc = run_sweep(c, c->psweep, &pt)) return rc;
             c->vt_valid = true;
+            c->vt_from_fit = false;
         }
         // mu = m + V^T z (= m + K_tn alpha), var = diag(Ktt - V'V) + noise   (src/gaussianprocess.jl:117-126):
         // both sums were accumulated by the panel-solve epilogues of the sweep; leaves whose z did not exist yet
         // while their rows rode through the factorisation (COPY / PREFIX) are finished from the stored rows
         pt.begin(9);
         pred_finish_kernel<<<(int)c->ptasks.count, 128, 0, c->stream>>>(c->d_leaves.p, c->ptasks.p, c->d_kp.p, c->D);
-        if (!standalone && c->ptasks_slow.count) {
+        // (only where the rows rode through the fit: a repeated call after the standalone sweep finds the sweep's sums of EVERY
+        // leaf in the accumulators, and finishing COPY / PREFIX leaves from the stored rows instead would change their bits)
+        if (!standalone && c->vt_from_fit && c->ptasks_slow.count) {
             pred_mu_kernel<<<(int)c->ptasks_slow.count, 256, 0, c->stream>>>(c->d_leaves.p, c->ptasks_slow.p);
             pred_var_kernel<<<(int)c->ptasks_slow.count, 256, 0, c->stream>>>(c->d_leaves.p, c->ptasks_slow.p, c->d_kp.p, c->D);
         }
         pt.end();
+    } else {
+        c->vt_valid = true;         // no routed rows at all: K_tn L^-T is empty, and current (predict_cov / predict_gradients: nothing written)
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(t1, c->stream));

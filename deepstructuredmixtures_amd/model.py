@@ -464,6 +464,7 @@ _RANK_FAILED = -(1 << 30)      # info value of every leaf of a rank whose fit ra
 
 def _fit(model, tau):
     model._upload(tau)
+    model._scores_on_device = False     # the aggregated prediction on the device belongs to the fit this one replaces
     if model.shard.world > 1 and _ctx_type(model) is hipabi.Context:
         _ = model.ctx          # every rank, also one without leaves, joins the set-up of the device exchange (collective)
     failure = None
@@ -1561,7 +1562,9 @@ def _predict_device(model, xt, rc):
 
 def scores(model, y_test, mu=None, var=None):
     """dict(mse, sse, mae, sae, nlpd) (`src/scorefunctions.jl:6-16`) of the last `predict(model, x)`: computed on the
-    device from the aggregated prediction still resident there when one context holds the model, else from (mu, var)."""
+    device from the aggregated prediction still resident there when one context holds the model, else from (mu, var).
+    A later `fit` drops the resident prediction (the context refuses `dsmgp_scores` on the sums of an earlier fit): call
+    `predict` again, or pass the (mu, var) it returned."""
     y_test = np.ascontiguousarray(y_test, dtype=np.float64)
     if getattr(model, "_scores_on_device", False) and mu is None:
         return model.ctx.scores(y_test)

@@ -156,7 +156,10 @@ int dsmgp_set_tree(dsmgp_ctx* ctx, int64_t n_nodes, const int8_t* kind, const in
                    const int64_t* split_dim, const double* thr, int64_t thr_ld, const int64_t* leaf_id);
 int dsmgp_set_test_routed(dsmgp_ctx* ctx, const double* Xt /* n_t x D column-major */, int64_t n_t, int32_t D);
 int dsmgp_routes(dsmgp_ctx* ctx, int64_t* route_ptr /* L+1 */, int64_t* route_idx /* or NULL */);
-int dsmgp_predict_run(dsmgp_ctx* ctx, double* seconds);   /* device work only, inputs resident */
+/* dsmgp_predict_run: device work only, inputs resident.  A repeated call on the same fit and test set leaves the same bits (the
+ * sweep is not run again; the moments are finished from the same sums).  A test set without routed rows is a valid one: the call
+ * succeeds and dsmgp_predict_cov / dsmgp_predict_gradients / dsmgp_predict_targets answer "nothing written". */
+int dsmgp_predict_run(dsmgp_ctx* ctx, double* seconds);
 int dsmgp_predict_fetch(dsmgp_ctx* ctx, double* mu_out, double* var_out);
 int dsmgp_predict_leaves(dsmgp_ctx* ctx, const double* Xt, int64_t n_t, int32_t D, const int64_t* route_ptr,
                          const int64_t* route_idx, double* mu_out, double* var_out);
@@ -317,7 +320,11 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* ctx, double* grad_out /* L x stride *
  *      dsmgp_aggregate = partial + finish on one context.  With leaves spread over ranks or contexts every holder
  *      calls dsmgp_aggregate_partial (partial_out: W x n_t sums, W = 3 mixture / 2 PoE, gPoE / 2 n_groups rBCM), the
  *      caller adds the partial sums (the multi-GPU exchange: one all-gather of W n_t doubles per rank) and hands the
- *      total to dsmgp_aggregate_finish.  mu_out / var_out (n_t each) may be NULL: results stay resident for dsmgp_scores. */
+ *      total to dsmgp_aggregate_finish.  mu_out / var_out (n_t each) may be NULL: results stay resident for dsmgp_scores.
+ *      The partial sums, the total and the aggregated moments belong to the dsmgp_predict_run they were made from.
+ *      A later dsmgp_fit or dsmgp_set_hyper makes them stale, like the moments themselves (the rBCM finish would also read
+ *      the prior variance of the NEW hyper-parameters): dsmgp_aggregate_finish, dsmgp_aggregate_exchange and dsmgp_scores then
+ *      return DSMGP_E_STATE until dsmgp_predict_run and dsmgp_aggregate_partial (or dsmgp_aggregate) have run on the current fit. */
 #define DSMGP_AGG_MIXTURE 0
 #define DSMGP_AGG_POE     1
 #define DSMGP_AGG_GPOE    2
