@@ -8,6 +8,7 @@
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
 #include "kernels_targets.hpp"
+#include "ctx_state.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -24,6 +25,7 @@
 #include <vector>
 
 using namespace dsmgp;
+using namespace ctx_state;
 
 namespace {
 
@@ -466,7 +468,14 @@ struct DotRanges {
     size_t count() const { return first[4]; }
 };
 
-struct dsmgp_ctx {
+struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).  HOW a product was made is a plain member:
+    bool vt_from_fit = false;       // P_VT: the rows rode through the fit (else: the standalone sweep of predict_run made it)
+    bool last_fit_joint = false;    // P_FIT: it carried the resident test rows
+    bool grad_lists_all = false;    // P_GRAD_LISTS: they invert every factor owner (build_grad_plan)
+    bool grad_all_owners = false;   // P_GRAD_LISTS while build_grad_plan runs: every owner whatever the mask says (xinv_lists)
+    int tg_qpad = 0;                // P_TG_LISTS: the Qpad they were built for
+    bool use_graph = false;         // P_FIT is replayed from a captured graph: opt-in (DSMGP_OPT_FIT_GRAPH), config 2 2.50 -> 2.47 ms, nothing
+                                    // elsewhere; capture does not mix with several contexts driven from concurrent host threads (MultiContext)
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -481,7 +490,6 @@ struct dsmgp_ctx {
     std::vector<LeafHost> leaves;
     std::vector<int64_t> obs_ptr, obs_idx;
     DevBuf<int64_t> d_obs_ptr, d_obs_idx;
-    bool plan_ready = false;
 
     std::vector<HyperHost> hyper;
     DevBuf<KParam> d_kp;
@@ -499,9 +507,9 @@ struct dsmgp_ctx {
     size_t bytes_needed = 0;
 
     DevBuf<GramTask> gram;          // Gram launch of fit!: every lower tile, or (fused) the tiles no update task writes
-    bool fuse_gram = true;          // update tasks of fit! evaluate the Gram values of their tile themselves (TileTask.gram)
-    bool fuse_steps = true;         // block steps with more diagonal blocks than CUs run as two fused launches (kernels_fused.hpp)
-    bool diag_in_update = true;     // classic steps: the diagonal tile's update runs one step ahead and its factorisation rides in
+    int fuse_gram = 1;              // update tasks of fit! evaluate the Gram values of their tile themselves (TileTask.gram)
+    int fuse_steps = 1;             // block steps with more diagonal blocks than CUs run as two fused launches (kernels_fused.hpp)
+    int diag_in_update = 1;         // classic steps: the diagonal tile's update runs one step ahead and its factorisation rides in
                                     // the update launch (DiagFinishTask, kernels_fused.hpp)
     // per phase and block step (decided by build_plan):
     //   STEP_CLASSIC    update (all tiles, split-K) / reduce / diagonal block / panel solve launches, one after the other
@@ -540,10 +548,6 @@ struct dsmgp_ctx {
     double* slabJ[MAX_LANES] = {};
     double alg_flops_joint = 0.0;
     bool joint = true;              // fit advances the resident test rows too
-    bool joint_ready = false;
-    bool vt_valid = false;          // Vt holds K_tn L^-T for the current factor
-    bool vt_from_fit = false;       // ... because the rows rode through the fit (else: the standalone sweep of predict_run made it)
-    bool last_fit_joint = false;
     int ncu = 256;
     bool xcd_order = true;          // XCD-aware task order (speed only)
     int tail_split = DSMGP_TAIL_SPLIT_DEFAULT, tail_rounds = DSMGP_TAIL_ROUNDS_DEFAULT;          // plans with one lane
@@ -552,19 +556,13 @@ struct dsmgp_ctx {
     std::vector<int> fwd_off, bwd_off;
     DevBuf<SolveTask> fwd, bwd;
     int solve_steps = 0;
-    bool fitted = false;
     // The launch sequence of fit! as a captured hipGraph (one per variant: fit alone / with the resident test rows), replayed
     // while per-launch timing is off (dsmgp_set_profile 0): every kernel argument is a pointer into the plan's task lists or
     // arenas, which live as long as the plan, and the hyper-parameters go through d_kp's CONTENTS -- so a graph stays valid
     // until the plan, the test set or the KParam table's allocation changes (drop_graphs).  What it buys is the host-side
     // launch cost between dependent kernels of a latency-bound chain (config 2: 32 steps x 3 launches).
-    bool use_graph = false;         // opt-in (DSMGP_OPT_FIT_GRAPH): config 2 2.50 -> 2.47 ms, nothing elsewhere; capture does not mix with
-                                    // several contexts driven from concurrent host threads (hipabi.MultiContext)
     hipGraphExec_t fit_graph[2] = {nullptr, nullptr};
     int graph_launches[2][2] = {{0, 0}, {0, 0}};
-    bool alpha_valid = false;       // alpha = L^-T z has been computed for the current factors (ensure_alpha)
-    bool dinv_complete = false;     // every Dinv_k holds the whole inverse for the current factors (ensure_dinv); a fit leaves the
-                                    // blocks of its fused steps with their 16x16 diagonal inverses only
     DevBuf<DiagTask> dinvc_prefix;  // copied blocks of PREFIX leaves whose source factorised them in a fused step: completed right
                                     // after the copy (the classic steps of the PREFIX phase solve against Dinv_k)
     DevBuf<DiagTask> dinvc_fwd;     // blocks of the leaves whose z comes from the forward sweep (COPY, PREFIX): completed before it
@@ -607,17 +605,13 @@ struct dsmgp_ctx {
     DevBuf<PredGradFinTask> pgfin;  // test tiles
     DevBuf<double> d_pgpart;        // the slabs' sums
     DevBuf<double> d_pgout;         // dmu | dvar (absent in a mean-only call), route_total x D each (ld = route_total)
-    bool test_ready = false;
-    bool predicted = false;
     int64_t route_total = 0;
 
     // several target columns on the current factors (dsmgp_solve_targets / dsmgp_predict_targets, kernels_targets.hpp): allocated on
     // first use, not part of bytes_needed, dropped with the plan (free_targets); what depends on the test set goes with it (free_test)
     double* arenaT = nullptr;       // per leaf Yc | Z, npad x Qpad each (grow-only, from the pool when there is one)
     size_t cap_T = 0;
-    int tg_Q = 0, tg_qpad = 0;      // columns of the resident Z; the Qpad the lists below were built for
-    bool tg_lists = false;          // toff / tfwd point into the current arenaT and the current plan's factors
-    bool tg_valid = false;          // Z holds L^-1 (Y - mean) for the CURRENT fit (cleared by a fit)
+    int tg_Q = 0;                   // columns of the resident Z
     std::vector<size_t> toff;       // per leaf: offset of its Yc in arenaT
     DevBuf<long long> d_toff;
     DevBuf<double> d_tY, d_tmean, d_tmll;       // Y (N x Q), mean and mll (L x Q)
@@ -659,11 +653,8 @@ struct dsmgp_ctx {
     DevBuf<int32_t> d_agg_group;    // L
     DevBuf<double> d_agg_out;       // mu | var (n_t each) | y_test (n_t) | score block sums
     int agg_family = -1, agg_G = 0, agg_W = 0;
-    bool agg_partial_ready = false, agg_done = false;
-    bool agg_total = false;         // d_agg_part holds the sum over ranks (dsmgp_aggregate_exchange ran on these partial sums)
 
     // gradients (built on first use)
-    bool grad_ready = false;
     std::vector<char> grad_active;  // dsmgp_set_gradient_leaves: leaves whose gradients are wanted (empty = all)
     double* arenaX = nullptr;       // Xt = L^-T per factor owner, npad x npad
     size_t arenaX_count = 0;
@@ -681,20 +672,12 @@ struct dsmgp_ctx {
     DevBuf<double> d_gpart;         // partial results: frob | graddot pairs | per-leaf dots | ArdLinear quadratic forms (2 D per task)
     size_t gpart_count = 0;
     // leave-one-out (dsmgp_loo): reads the same L^-T arena
-    bool xinv_all = false;          // arenaX holds L^-T of the CURRENT fit for EVERY factor owner: set by a sweep over lists that invert
-                                    // every owner (dsmgp_loo's; dsmgp_gradients' when no mask leaves an owner out), cleared by a fit, by
-                                    // a sweep over fewer owners, a new leaf table and dsmgp_release.  The arena outlives the lists.
-    bool grad_lists_all = false;    // the current lists invert every factor owner (build_grad_plan)
-    bool grad_all_owners = false;   // build_grad_plan: invert every owner whatever the mask says (set by dsmgp_loo around its own build)
     std::vector<size_t> gxoff;      // per owner leaf: its offset in arenaX (build_grad_plan)
-    bool loo_ready = false;         // the two lists below point into the current arenaX / scratch (they depend on the leaf table only)
     DevBuf<RowNormTask> lrow;
     DevBuf<LooTask> lleaf;
     DevBuf<double> d_loo;           // row-sum planes of every owner | mu | var (obs_ptr[L] each) | lpd (L).  Allocated on first use,
                                     // dropped with the leaf table (free_grad); not part of bytes_needed
     // gradients of the LOO density (dsmgp_loo_gradients): lists and arena built on first use, dropped with the leaf table (free_grad)
-    bool lg_ready = false;
-    std::vector<int> lg_kinds;      // kind of every kernel id the lists were built for (a change of kind rebuilds them)
     double* arenaH = nullptr;       // H = K_y^-1 diag(sqrt w) per computing leaf, npad x npad
     DevBuf<double> d_lgvec;         // [alpha | u | sqrt w | alpha / (d sqrt w)] per computing leaf, npad each
     DevBuf<LooVecTask> lgvec;
@@ -719,7 +702,6 @@ struct dsmgp_ctx {
     DevBuf<double> rt_thr;
     int64_t rtree_nodes = 0;
     int rtree_max_leaf = -1;        // largest local leaf index a region names (checked against the leaf table at routing time)
-    bool rtree_ready = false;
     // routing workspace, kept across registrations: row counts | leaf counts | outside flag, bitmap, word prefixes
     DevBuf<int32_t> rws_counts;
     DevBuf<uint32_t> rws_bits;
@@ -731,7 +713,6 @@ struct dsmgp_ctx {
     double alg_flops_update = 0.0;  // algorithmic flops of the Cholesky update launches
     double alg_flops_fused = 0.0, alg_flops_fused_joint = 0.0;   // ... of the fused tile launches (update + solve), fit alone / joint
     int n_fused_launches = 0;
-    bool phase_ready = false;       // `phase` (fit! without resident test rows) has been built for the current plan
     int n_update_launches = 0;
 };
 
@@ -944,7 +925,7 @@ void free_grad_lists(dsmgp_ctx* c) {
     c->gfrob.clear();
     c->gdot.clear();
     c->gardlin.clear();
-    c->grad_ready = false;
+    c->invalidate(P_GRAD_LISTS);
 }
 
 void free_grad(dsmgp_ctx* c) {
@@ -955,13 +936,10 @@ void free_grad(dsmgp_ctx* c) {
     c->gdot.release();
     c->gardlin.release();
     c->d_gpart.release();
-    c->grad_ready = false;
-    c->xinv_all = false;
-    c->loo_ready = false;
     c->lrow.release();
     c->lleaf.release();
     c->d_loo.release();
-    c->lg_ready = false;
+    c->invalidate(P_GRAD_LISTS | P_XINV | P_LOO_LISTS | P_LG_LISTS);
     arena_put(c, c->arenaH);
     c->d_lgvec.release();
     c->lgvec.release();
@@ -977,7 +955,7 @@ void free_grad(dsmgp_ctx* c) {
 void free_targets(dsmgp_ctx* c) {
     arena_put(c, c->arenaT);
     c->cap_T = 0;
-    c->tg_lists = c->tg_valid = false;
+    c->invalidate(P_TG_LISTS);
     c->tg_Q = c->tg_qpad = 0;
     c->d_toff.release();
     c->d_tY.release();
@@ -1019,7 +997,7 @@ void free_tree(dsmgp_ctx* c) {
     c->rt_sdim.release();
     c->rt_leaf.release();
     c->rt_thr.release();
-    c->rtree_ready = false;
+    c->invalidate(P_RTREE);
     c->rtree_nodes = 0;
     c->rtree_max_leaf = -1;
 }
@@ -1051,9 +1029,7 @@ void free_plan(dsmgp_ctx* c) {
     c->dinvc_all.release();
     free_grad(c);
     free_targets(c);
-    c->plan_ready = false;
-    c->phase_ready = false;
-    c->fitted = false;
+    c->invalidate(P_PLAN);
 }
 
 // keep: a registration that replaces another -- every buffer of the old test set stays allocated for the new one (they are
@@ -1076,7 +1052,6 @@ void free_test(dsmgp_ctx* c, bool keep) {
     c->d_agg_coef.drop(keep);
     c->d_agg_group.drop(keep);
     c->d_agg_out.drop(keep);
-    c->agg_partial_ready = c->agg_done = c->agg_total = false;
     if (!keep) {
         arena_put(c, c->arenaVt);
         c->arenaVt_count = 0;
@@ -1105,10 +1080,12 @@ void free_test(dsmgp_ctx* c, bool keep) {
     for (auto& lane : c->phaseJ)
         for (auto& ph : lane) ph.drop(keep);
     for (auto& sl : c->slabJ) arena_put(c, sl);
-    c->joint_ready = false;
-    c->vt_valid = false;
-    c->test_ready = false;
-    c->predicted = false;
+    c->invalidate(P_TEST);
+}
+
+void free_plan_and_test(dsmgp_ctx* c) {       // new training data, leaf table, sharing schedule, plan option or pool
+    free_plan(c);
+    free_test(c);     // the task lists of a resident test set point into the plan's arenas: they go with it
 }
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -1669,8 +1646,9 @@ int build_factor_steps(dsmgp_ctx* c, int lane, bool with_test, StepLists (&phase
     return 0;
 }
 
-// Build arenas, the LeafDev table and every task list for the current leaf table + sharing schedule.
+// Build arenas, the LeafDev table and every task list for the current leaf table + sharing schedule, unless they are current.
 int build_plan(dsmgp_ctx* c) {
+    if (c->has(P_PLAN)) return 0;
     HostLog hl_total("build_plan");
     {
         HostLog hl("build_plan: free_plan");
@@ -1955,7 +1933,6 @@ int build_plan(dsmgp_ctx* c) {
     // The step lists of the factorisation are built on first use: those for the train rows alone by the first fit! without a
     // resident test set (ensure_phase), those with the test rows riding along by dsmgp_set_test -- a context that only ever
     // fits with its test set resident (the streaming mode: 20 million tile tasks over the groups of config 5) builds one set.
-    c->phase_ready = false;
 
     // solve sweeps.  Forward: only leaves whose factor came from elsewhere (COPY, PREFIX) -- leaves factorised
     // in full get z = L^-1 y from the factorisation itself (chol_diag_packed_kernel + the panel-solve epilogue).
@@ -2030,7 +2007,7 @@ int build_plan(dsmgp_ctx* c) {
         if (int rc = dev_upload(c, c->bwd, bwd)) return rc;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->plan_ready = true;
+    c->mark(P_PLAN);
     c->pool_mark_plan = c->pool_top;
     return 0;
 }
@@ -2038,7 +2015,7 @@ int build_plan(dsmgp_ctx* c) {
 // Step lists of a fit! without resident test rows.  Built after the plan, possibly after the test arenas: with a device pool
 // its split-K workspace is allocated outside the pool (the pool is a stack: plan < test < gradients).
 int ensure_phase(dsmgp_ctx* c) {
-    if (c->phase_ready) return 0;
+    if (c->has(P_PHASE)) return 0;
     HostLog hl("ensure_phase: factor steps");
     c->alg_flops_update = c->alg_flops_fused = 0.0;
     for (int lane = 0; lane < c->nlanes; ++lane) {
@@ -2048,13 +2025,13 @@ int ensure_phase(dsmgp_ctx* c) {
         c->alg_flops_fused += ff;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->phase_ready = true;
+    c->mark(P_PHASE);
     return 0;
 }
 
 // Step lists of a fit! with the registered test rows riding along: built on first use (see dsmgp_set_test).
 int ensure_joint(dsmgp_ctx* c) {
-    if (c->joint_ready) return 0;
+    if (c->has(P_JOINT)) return 0;
     HostLog hl("ensure_joint: joint factor steps");
     c->alg_flops_joint = c->alg_flops_fused_joint = 0.0;
     for (int lane = 0; lane < c->nlanes; ++lane) {
@@ -2064,7 +2041,7 @@ int ensure_joint(dsmgp_ctx* c) {
         c->alg_flops_fused_joint += ff;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->joint_ready = true;
+    c->mark(P_JOINT);
     return 0;
 }
 
@@ -2270,17 +2247,17 @@ int run_lanes(dsmgp_ctx* c, StepLists (*lists)[2], int ph, PhaseTimer& pt, bool 
 // The whole inverse of every diagonal block (the fused steps of a fit leave L_kk and its 16x16 diagonal inverses only): what the
 // standalone prediction sweep, the gradients and the sweeps for alpha multiply with.  Queued on the context's stream.
 int ensure_dinv(dsmgp_ctx* c) {
-    if (c->dinv_complete) return 0;
+    if (c->has(P_DINV)) return 0;
     if (c->dinvc_all.count)
         dinv_complete_kernel<<<(int)c->dinvc_all.count, 256, DIAGP_LDS_BYTES, c->stream>>>(c->dinvc_all.p);
     HIPCHK(c, hipGetLastError());
-    c->dinv_complete = true;
+    c->mark(P_DINV);
     return 0;
 }
 
 // alpha = L^-T z by the backward block sweep on w = copy of z (z stays: the predictive mean is m + V^T z).
 int ensure_alpha(dsmgp_ctx* c) {
-    if (c->alpha_valid) return 0;
+    if (c->has(P_ALPHA)) return 0;
     if (int rc = ensure_dinv(c)) return rc;
     EventPair ev;
     HIPCHK(c, ev.init());
@@ -2298,7 +2275,7 @@ int ensure_alpha(dsmgp_ctx* c) {
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     c->timings[14] = ms * 1e-3;
-    c->alpha_valid = true;
+    c->mark(P_ALPHA);
     return 0;
 }
 
@@ -2355,8 +2332,7 @@ int dsmgp_create(int32_t device_id, dsmgp_ctx** out) {
 int dsmgp_destroy(dsmgp_ctx* c) {
     if (!c) return DSMGP_E_ARG;
     (void)hipSetDevice(c->device);
-    free_plan(c);
-    free_test(c);
+    free_plan_and_test(c);
     if (c->pool_base) (void)hipFree(c->pool_base);
     c->pool_base = nullptr;
     (void)dsmgp_comm_destroy(c);
@@ -2404,49 +2380,26 @@ int dsmgp_set_option(dsmgp_ctx* c, int32_t option, int32_t value) {
         c->ard_true_gradient = value != 0;
         return 0;
     }
-    if (option == DSMGP_OPT_FUSED_GRAM) {
-        if ((value != 0) != c->fuse_gram) {
-            HIPCHK(c, hipSetDevice(c->device));
-            free_plan(c);     // task lists of fit! (and, through the plan, of the resident test set) depend on it
-            free_test(c);
-        }
-        c->fuse_gram = value != 0;
-        return 0;
-    }
-    if (option == DSMGP_OPT_FUSED_STEPS) {
-        if ((value != 0) != c->fuse_steps) {
-            HIPCHK(c, hipSetDevice(c->device));
-            free_plan(c);
-            free_test(c);
-        }
-        c->fuse_steps = value != 0;
-        return 0;
-    }
     if (option == DSMGP_OPT_FIT_GRAPH) {
         if (value == 0) drop_graphs(c);
         c->use_graph = value != 0;
         return 0;
     }
-    if (option == DSMGP_OPT_LANES) {
+    // PLAN_OPTIONS: the task lists of fit! (and, through the plan, of the resident test set) depend on them
+    int* const opt = option == DSMGP_OPT_FUSED_GRAM ? &c->fuse_gram : option == DSMGP_OPT_FUSED_STEPS ? &c->fuse_steps :
+                     option == DSMGP_OPT_DIAG_IN_UPDATE ? &c->diag_in_update : option == DSMGP_OPT_LANES ? &c->lanes_opt : nullptr;
+    if (!opt) return fail(c, DSMGP_E_ARG, "set_option: unknown option");
+    if (opt == &c->lanes_opt) {
         if (value < 0 || value > MAX_LANES) return fail(c, DSMGP_E_ARG, "set_option: lanes must be 0 (automatic) or 1 .. 4");
-        if (value != c->lanes_opt) {
-            HIPCHK(c, hipSetDevice(c->device));
-            free_plan(c);
-            free_test(c);
-        }
-        c->lanes_opt = value;
-        return 0;
+    } else {
+        value = value != 0;
     }
-    if (option == DSMGP_OPT_DIAG_IN_UPDATE) {
-        if ((value != 0) != c->diag_in_update) {
-            HIPCHK(c, hipSetDevice(c->device));
-            free_plan(c);
-            free_test(c);
-        }
-        c->diag_in_update = value != 0;
-        return 0;
+    if (value != *opt) {
+        HIPCHK(c, hipSetDevice(c->device));
+        free_plan_and_test(c);
     }
-    return fail(c, DSMGP_E_ARG, "set_option: unknown option");
+    *opt = value;
+    return 0;
 }
 
 int dsmgp_set_profile(dsmgp_ctx* c, int32_t on) {
@@ -2460,8 +2413,7 @@ int dsmgp_set_train(dsmgp_ctx* c, const double* X, const double* y, int64_t N, i
     if (!c) return DSMGP_E_ARG;
     if (!X || !y || N <= 0 || D <= 0) return fail(c, DSMGP_E_ARG, "set_train: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    free_plan(c);
-    free_test(c);
+    free_plan_and_test(c);
     free_tree(c);
     c->dX.release();
     c->dy.release();
@@ -2482,8 +2434,7 @@ int dsmgp_set_leaves(dsmgp_ctx* c, int32_t L, const int64_t* obs_ptr, const int6
     if (!c->dX.p) return fail(c, DSMGP_E_STATE, "set_leaves before set_train");
     if (L <= 0 || !obs_ptr || !obs_idx || !kernel_id || !mean) return fail(c, DSMGP_E_ARG, "set_leaves: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    free_plan(c);
-    free_test(c);
+    free_plan_and_test(c);
     free_tree(c);           // its regions name indices of the OLD leaf table
     if (obs_ptr[0] != 0) return fail(c, DSMGP_E_ARG, "obs_ptr[0] must be 0");
     c->leaves.assign(L, LeafHost{});
@@ -2549,8 +2500,7 @@ int dsmgp_set_sharing(dsmgp_ctx* c, const int32_t* op, const int32_t* src, const
         }
     }
     HIPCHK(c, hipSetDevice(c->device));
-    free_plan(c);
-    free_test(c);     // the task lists of a resident test set point into the plan's arenas: they go with it
+    free_plan_and_test(c);
     for (int l = 0; l < L; ++l) {
         c->leaves[l].op = sh[l].op;
         c->leaves[l].src = sh[l].src;
@@ -2580,12 +2530,7 @@ int dsmgp_set_hyper(dsmgp_ctx* c, int32_t kernel_id, int32_t kind, const double*
     c->hyper[kernel_id].loghyp.assign(loghyp, loghyp + n);
     // a captured fit launches diag_fused_reg_matern_kernel / diag_fused_reg_rq_kernel or not
     if (any_matern(c) != had_matern || any_rq(c) != had_rq) drop_graphs(c);
-    c->fitted = false;
-    c->predicted = false;
-    // the partial sums and the aggregated moments belong to the prediction that just fell; the rBCM finish would also read the
-    // prior variance from the NEXT KParam table (upload_hyper overwrites it)
-    c->agg_partial_ready = c->agg_done = c->agg_total = false;
-    c->vt_valid = false;
+    c->invalidate(P_FIT);   // (the aggregation's sums fall too: the rBCM finish would read its prior variance from the NEXT KParam table)
     return 0;
 }
 
@@ -2594,11 +2539,10 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
     if (c->L == 0) return fail(c, DSMGP_E_STATE, "fit before set_leaves");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = check_hyper(c)) return rc;
-    if (!c->plan_ready)
-        if (int rc = build_plan(c)) return rc;
+    if (int rc = build_plan(c)) return rc;
     if (int rc = upload_hyper(c)) return rc;
     // With a resident test set the rows of K_tn ride through the same launches (build_factor_steps).
-    const bool joint = c->joint && c->test_ready;
+    const bool joint = c->joint && c->has(P_TEST);
     if (joint) {
         if (int rc = ensure_joint(c)) return rc;
     } else if (int rc = ensure_phase(c)) {
@@ -2676,10 +2620,7 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
         pt.end();
         return 0;
     };
-    c->vt_valid = false;
-    c->alpha_valid = false;
-    c->xinv_all = false;
-    c->tg_valid = false;            // Z of dsmgp_solve_targets belongs to the factors this fit replaces
+    c->invalidate(P_FIT);           // the factors are rewritten from here on
     // Replay the sequence as a graph while nothing inside it records events (profile 0); capture it on first use
     const int gk = joint ? 1 : 0;
     if (c->use_graph && c->profile == 0) {
@@ -2738,13 +2679,10 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
             if (si != 0 && si <= lf.kb * TB && info_out[l] != 0) info_out[l] = si;
         }
     }
-    c->fitted = true;
-    c->predicted = false;
-    c->agg_partial_ready = c->agg_done = c->agg_total = false;   // they fall with the prediction they were summed from
-    c->vt_valid = joint;
+    c->mark(P_FIT);
+    if (joint) c->mark(P_VT);
     c->vt_from_fit = joint;
     c->last_fit_joint = joint;
-    c->dinv_complete = c->dinvc_all.count == 0;
     return 0;
 }
 
@@ -3017,14 +2955,12 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
     // here; otherwise by the first fit that wants them (ensure_joint) -- predict(model, x) on rows the model has not seen
     // registers them and runs its own sweep, and should not wait for task lists only a later fit! would use (0.067 s of the
     // 0.088 s this call took at the headline model).
-    c->joint_ready = false;
-    if (c->pool_base)
-        if (int rc = ensure_joint(c)) return rc;
+    c->mark(P_TEST);
+    int rc = c->pool_base ? ensure_joint(c) : 0;
     hl.lap("set_test: final sync");
-    if (int rc = stage_done(c)) return rc;
-    c->test_ready = true;
-    c->vt_valid = false;
-    return 0;
+    if (rc == 0) rc = stage_done(c);
+    if (rc != 0) c->invalidate(P_TEST);
+    return rc;
 }
 }  // namespace
 
@@ -3037,8 +2973,7 @@ int dsmgp_set_test(dsmgp_ctx* c, const double* Xt, int64_t n_t, int32_t D, const
     if (D != c->D) return fail(c, DSMGP_E_ARG, "set_test: the test matrix has " + std::to_string(D) + " columns, the training data " + std::to_string(c->D));
     HIPCHK(c, hipSetDevice(c->device));
     HostLog hl_total("set_test");
-    if (!c->plan_ready)
-        if (int rc = build_plan(c)) return rc;
+    if (int rc = build_plan(c)) return rc;
     HostLog hl("set_test: free old");
     free_test(c, true);     // every buffer of the set this one replaces is kept for it
     c->stage_top = 0;       // (the stream is idle: every entry point synchronises before it returns)
@@ -3131,20 +3066,19 @@ int dsmgp_set_tree(dsmgp_ctx* c, int64_t n_nodes, const int8_t* kind, const int6
     c->rtree = RouteTree{c->rt_kind.p, c->rt_first.p, c->rt_nchild.p, c->rt_sdim.p, c->rt_leaf.p, c->rt_thr.p, (int)thr_ld};
     c->rtree_nodes = n_nodes;
     c->rtree_max_leaf = max_leaf;
-    c->rtree_ready = true;
+    c->mark(P_RTREE);
     return 0;
 }
 
 int dsmgp_set_test_routed(dsmgp_ctx* c, const double* Xt, int64_t n_t, int32_t D) {
     if (!c) return DSMGP_E_ARG;
     if (c->L == 0) return fail(c, DSMGP_E_STATE, "set_test before set_leaves");
-    if (!c->rtree_ready) return fail(c, DSMGP_E_STATE, "set_test_routed before set_tree");
+    if (!c->has(P_RTREE)) return fail(c, DSMGP_E_STATE, "set_test_routed before set_tree");
     if (!Xt || n_t <= 0) return fail(c, DSMGP_E_ARG, "set_test_routed: bad arguments");
     if (D != c->D) return fail(c, DSMGP_E_ARG, "set_test_routed: the test matrix has " + std::to_string(D) + " columns, the training data " + std::to_string(c->D));
     HIPCHK(c, hipSetDevice(c->device));
     HostLog hl_total("set_test_routed");
-    if (!c->plan_ready)
-        if (int rc = build_plan(c)) return rc;
+    if (int rc = build_plan(c)) return rc;
     HostLog hl("set_test: free old");
     free_test(c, true);
     c->stage_top = 0;
@@ -3201,7 +3135,7 @@ int dsmgp_set_test_routed(dsmgp_ctx* c, const double* Xt, int64_t n_t, int32_t D
 
 int dsmgp_routes(dsmgp_ctx* c, int64_t* route_ptr, int64_t* route_idx) {
     if (!c) return DSMGP_E_ARG;
-    if (!c->test_ready) return fail(c, DSMGP_E_STATE, "routes before set_test");
+    if (!c->has(P_TEST)) return fail(c, DSMGP_E_STATE, "routes before set_test");
     HIPCHK(c, hipSetDevice(c->device));
     if (route_ptr) std::memcpy(route_ptr, c->route_ptr.data(), ((size_t)c->L + 1) * sizeof(int64_t));
     if (route_idx && c->route_total)
@@ -3249,8 +3183,8 @@ extern "C" {
 
 int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
     if (!c) return DSMGP_E_ARG;
-    if (!c->fitted) return fail(c, DSMGP_E_STATE, "predict before fit");
-    if (!c->test_ready) return fail(c, DSMGP_E_STATE, "predict before set_test");
+    if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "predict before fit");
+    if (!c->has(P_TEST)) return fail(c, DSMGP_E_STATE, "predict before set_test");
     HIPCHK(c, hipSetDevice(c->device));
     for (int i = 6; i < 10; ++i) c->timings[i] = 0.0;
     c->timings[12] = 0.0;
@@ -3262,7 +3196,7 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
     HIPCHK(c, hipEventRecord(t0, c->stream));
     hl.lap("predict_run: enqueue");
     if (c->ptasks.count) {
-        const bool standalone = !c->vt_valid;
+        const bool standalone = !c->has(P_VT);
         if (standalone) {
             if (int rc = ensure_dinv(c)) return rc;       // the panel solves of the sweep multiply with Dinv_k
             HIPCHK(c, hipMemsetAsync(c->arenaPV + c->acc_off, 0, c->acc_count * sizeof(double), c->stream));
@@ -3274,7 +3208,7 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
             }
             // V^T = K_tn L^-T, block column by block column (src/gaussianprocess.jl:120), lane by lane on the lanes' streams
             if (int rc = run_sweep(c, c->psweep, &pt)) return rc;
-            c->vt_valid = true;
+            c->mark(P_VT);
             c->vt_from_fit = false;
         }
         // mu = m + V^T z (= m + K_tn alpha), var = diag(Ktt - V'V) + noise   (src/gaussianprocess.jl:117-126):
@@ -3290,7 +3224,7 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
         }
         pt.end();
     } else {
-        c->vt_valid = true;         // no routed rows at all: K_tn L^-T is empty, and current (predict_cov / predict_gradients: nothing written)
+        c->mark(P_VT);              // no routed rows at all: K_tn L^-T is empty, and current (predict_cov / predict_gradients: nothing written)
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(t1, c->stream));
@@ -3302,14 +3236,14 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
     pt.collect();
     c->timings[12] = ms * 1e-3;
     if (seconds) *seconds = ms * 1e-3;
-    c->predicted = true;
-    c->agg_partial_ready = c->agg_done = c->agg_total = false;
+    c->invalidate(P_PRED);
+    c->mark(P_PRED);
     return 0;
 }
 
 int dsmgp_predict_fetch(dsmgp_ctx* c, double* mu_out, double* var_out) {
     if (!c) return DSMGP_E_ARG;
-    if (!c->predicted) return fail(c, DSMGP_E_STATE, "predict_fetch before predict_run");
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_fetch before predict_run");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->route_total;
     if (n && mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->arenaPV, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -3333,7 +3267,7 @@ int dsmgp_predict_leaves(dsmgp_ctx* c, const double* Xt, int64_t n_t, int32_t D,
 int dsmgp_predict_cov(dsmgp_ctx* c, int32_t leaf, int32_t with_noise, double* Sigma_out, int64_t ld, double* seconds) {
     if (!c) return DSMGP_E_ARG;
     if (seconds) *seconds = 0.0;
-    if (!c->predicted || !c->vt_valid) return fail(c, DSMGP_E_STATE, "predict_cov before predict_run on the current fit");
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_cov before predict_run on the current fit");
     if (leaf < 0 || leaf >= c->L) return fail(c, DSMGP_E_ARG, "predict_cov: leaf out of range");
     const LeafHost& lf = c->leaves[leaf];
     if (lf.nt == 0) return 0;
@@ -3392,7 +3326,7 @@ int agg_width(int family, int G) { return family == AGG_MIXTURE ? 3 : (family ==
 int dsmgp_aggregate_partial(dsmgp_ctx* c, int32_t family, const double* leaf_coef, const int32_t* leaf_group,
                             int32_t n_groups, double* partial_out) {
     if (!c) return DSMGP_E_ARG;
-    if (!c->predicted) return fail(c, DSMGP_E_STATE, "aggregate before predict_run");
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "aggregate before predict_run");
     if (family < AGG_MIXTURE || family > AGG_RBCM) return fail(c, DSMGP_E_ARG, "aggregate: unknown family");
     if (family == AGG_RBCM) {
         if (!leaf_group || n_groups <= 0 || n_groups > 4096) return fail(c, DSMGP_E_ARG, "aggregate: rBCM needs leaf groups");
@@ -3431,16 +3365,15 @@ int dsmgp_aggregate_partial(dsmgp_ctx* c, int32_t family, const double* leaf_coe
     c->agg_family = family;
     c->agg_G = G;
     c->agg_W = W;
-    c->agg_partial_ready = true;
-    c->agg_total = false;
-    c->agg_done = false;
+    c->invalidate(P_PARTIAL);
+    c->mark(P_PARTIAL);
     return 0;
 }
 
 int dsmgp_aggregate_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain, int32_t prior_kernel_id,
                            double* mu_out, double* var_out) {
     if (!c) return DSMGP_E_ARG;
-    if (!c->agg_partial_ready) return fail(c, DSMGP_E_STATE, "aggregate_finish before aggregate_partial");
+    if (!c->has(P_PARTIAL)) return fail(c, DSMGP_E_STATE, "aggregate_finish before aggregate_partial");
     if (c->agg_family == AGG_RBCM &&
         (prior_kernel_id < 0 || prior_kernel_id >= (int)c->hyper.size() || c->hyper[prior_kernel_id].kind < 0))
         return fail(c, DSMGP_E_ARG, "aggregate_finish: rBCM needs the kernel id of the model's first leaf");
@@ -3460,7 +3393,7 @@ int dsmgp_aggregate_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain
     if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->d_agg_out.p, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->d_agg_out.p + nt, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->agg_done = true;
+    c->mark(P_DONE);
     return 0;
 }
 
@@ -3472,7 +3405,7 @@ int dsmgp_aggregate(dsmgp_ctx* c, int32_t family, const double* leaf_coef, const
 
 int dsmgp_scores(dsmgp_ctx* c, const double* y_test, double* out) {
     if (!c) return DSMGP_E_ARG;
-    if (!c->agg_done) return fail(c, DSMGP_E_STATE, "scores before aggregate");
+    if (!c->has(P_DONE)) return fail(c, DSMGP_E_STATE, "scores before aggregate");
     if (!y_test || !out) return fail(c, DSMGP_E_ARG, "scores: NULL argument");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nt = (size_t)c->n_t;
@@ -3883,7 +3816,7 @@ int build_grad_plan(dsmgp_ctx* c) {
     if (int rc = dev_upload(c, c->gardlin, al)) return rc;
     c->gpart_count = frob.size() + (size_t)c->gstride * gd.size() + 2 * (size_t)L + 2 * (size_t)c->D * al.size();
     if (int rc = c->d_gpart.grow(c, c->gpart_count)) return rc;
-    c->grad_ready = true;
+    c->mark(P_GRAD_LISTS);
     return 0;
 }
 
@@ -3970,12 +3903,12 @@ int dsmgp_set_gradient_leaves(dsmgp_ctx* c, const int32_t* active) {
 
 int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     if (!c) return DSMGP_E_ARG;
-    if (!c->fitted) return fail(c, DSMGP_E_STATE, "gradients before fit");
+    if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "gradients before fit");
     if (!grad_out) return fail(c, DSMGP_E_ARG, "grad_out is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     const int L = c->L;
     if (int rc = check_stride(c, "gradients", stride)) return rc;
-    if (!c->grad_ready)
+    if (!c->has(P_GRAD_LISTS))
         if (int rc = build_grad_plan(c)) return rc;
     if (int rc = ensure_dinv(c)) return rc;
     if (int rc = ensure_alpha(c)) return rc;
@@ -3989,7 +3922,7 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     HIPCHK(c, e_inv.init());
     HIPCHK(c, e_dot.init());
     // Xt = L^-T (blocks left of the diagonal are never written and never read)
-    c->xinv_all = false;
+    c->invalidate(P_XINV);
     if (c->gtrans.count) transpose_tile_kernel<<<(int)c->gtrans.count * 16, 256, 0, c->stream>>>(c->gtrans.p);
     if (int rc = run_sweep(c, c->ginv, nullptr)) return rc;     // the lanes' streams wait for the transposes
     HIPCHK(c, hipEventRecord(e_inv.a, c->stream));
@@ -4007,8 +3940,8 @@ int dsmgp_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride) {
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(t1, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->xinv_all = c->grad_lists_all;    // dsmgp_loo on this fit reads the arena as it is (this pass itself inverts on every call, as it
-                                        // always did); under a mask that leaves owners out, theirs is stale or rewritten by other lists
+    if (c->grad_lists_all) c->mark(P_XINV);     // dsmgp_loo on this fit reads the arena as it is (this pass itself inverts on every call, as
+                                                // it always did); under a mask that leaves owners out, theirs is stale or rewritten by other lists
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, t0, t1));
     c->timings[10] = ms * 1e-3;
@@ -4082,7 +4015,7 @@ namespace {
 // (dsmgp_set_gradient_leaves) leave out the owners no active leaf needs: then the sweep runs over lists of the call's own, built
 // for every owner and dropped again when `own` goes out of scope (on every way out, the failing ones too), so that the next
 // dsmgp_gradients builds the mask's lists as it would have without the call -- same launches, same bits.
-// xinv_fill: queues the transposes and the sweep when they are needed; the caller sets xinv_all once the stream is through.
+// xinv_fill: queues the transposes and the sweep when they are needed; the caller marks P_XINV once the stream is through.
 struct OwnGradLists {
     dsmgp_ctx* c;
     bool on = false;
@@ -4091,9 +4024,9 @@ struct OwnGradLists {
     }
 };
 int xinv_lists(dsmgp_ctx* c, OwnGradLists& own) {
-    if (c->xinv_all) return 0;
-    if (c->grad_ready && !c->grad_lists_all) free_grad_lists(c);
-    if (!c->grad_ready) {
+    if (c->has(P_XINV)) return 0;
+    if (c->has(P_GRAD_LISTS) && !c->grad_lists_all) free_grad_lists(c);
+    if (!c->has(P_GRAD_LISTS)) {
         own.on = !c->grad_active.empty();
         c->grad_all_owners = true;
         const int rc = build_grad_plan(c);
@@ -4103,7 +4036,7 @@ int xinv_lists(dsmgp_ctx* c, OwnGradLists& own) {
     return 0;
 }
 int xinv_fill(dsmgp_ctx* c) {
-    if (c->xinv_all) return 0;
+    if (c->has(P_XINV)) return 0;
     if (c->gtrans.count) transpose_tile_kernel<<<(int)c->gtrans.count * 16, 256, 0, c->stream>>>(c->gtrans.p);
     return run_sweep(c, c->ginv, nullptr);
 }
@@ -4144,7 +4077,7 @@ int build_loo_plan(dsmgp_ctx* c) {
     }
     if (int rc = dev_upload(c, c->lrow, rows)) return rc;
     if (int rc = dev_upload(c, c->lleaf, lt)) return rc;
-    c->loo_ready = true;
+    c->mark(P_LOO_LISTS);
     return 0;
 }
 }  // namespace
@@ -4152,13 +4085,13 @@ int build_loo_plan(dsmgp_ctx* c) {
 int dsmgp_loo(dsmgp_ctx* c, double* mu_out, double* var_out, double* lpd_out, double* seconds) {
     if (!c) return DSMGP_E_ARG;
     if (seconds) *seconds = 0.0;
-    if (!c->fitted) return fail(c, DSMGP_E_STATE, "loo before fit");
+    if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "loo before fit");
     HIPCHK(c, hipSetDevice(c->device));
     const int L = c->L;
     // L^-T of every factor owner (xinv_lists / xinv_fill)
     OwnGradLists own_lists{c};
     if (int rc = xinv_lists(c, own_lists)) return rc;
-    if (!c->loo_ready)
+    if (!c->has(P_LOO_LISTS))
         if (int rc = build_loo_plan(c)) return rc;
     EventPair ev;           // the device work of the call: what is left to complete of Dinv and alpha after this fit, the sweep, the two kernels
     HIPCHK(c, ev.init());
@@ -4175,7 +4108,7 @@ int dsmgp_loo(dsmgp_ctx* c, double* mu_out, double* var_out, double* lpd_out, do
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev.b, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->xinv_all = true;
+    c->mark(P_XINV);
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     if (seconds) *seconds = ms * 1e-3;
@@ -4192,7 +4125,7 @@ int dsmgp_loo(dsmgp_ctx* c, double* mu_out, double* var_out, double* lpd_out, do
 int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int64_t ld, double* seconds) {
     if (!c) return DSMGP_E_ARG;
     if (seconds) *seconds = 0.0;
-    if (!c->predicted || !c->vt_valid) return fail(c, DSMGP_E_STATE, "predict_gradients before predict_run on the current fit");
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_gradients before predict_run on the current fit");
     const size_t nr = (size_t)c->route_total;
     if (nr == 0) return 0;
     if (ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_gradients: ld < route_total");
@@ -4303,7 +4236,7 @@ int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev.b, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (var) c->xinv_all = true;
+    if (var) c->mark(P_XINV);
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     if (seconds) *seconds = ms * 1e-3;
@@ -4323,7 +4256,7 @@ int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int
 namespace {
 static int build_targets_plan(dsmgp_ctx* c, int qpad) {      // (static: inside extern "C" an unnamed namespace alone still exports the name)
     const int L = c->L;
-    c->tg_lists = c->tg_valid = false;
+    c->invalidate(P_TG_LISTS);
     c->toff.assign((size_t)L, 0);
     size_t tot = 0;
     int maxnb = 0;
@@ -4381,7 +4314,7 @@ static int build_targets_plan(dsmgp_ctx* c, int qpad) {      // (static: inside 
     c->tfwd_steps = ns;
     c->tfwd_lanes = nl;
     c->tg_qpad = qpad;
-    c->tg_lists = true;
+    c->mark(P_TG_LISTS);
     return 0;
 }
 }  // namespace
@@ -4390,7 +4323,7 @@ int dsmgp_solve_targets(dsmgp_ctx* c, const double* Y, int64_t N, int32_t Q, int
                         double* seconds) {
     if (!c) return DSMGP_E_ARG;
     if (seconds) *seconds = 0.0;
-    if (!c->fitted) return fail(c, DSMGP_E_STATE, "solve_targets before fit");
+    if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "solve_targets before fit");
     if (!Y || N != c->N || Q < 1 || Q > 65535 || ldy < N)
         return fail(c, DSMGP_E_ARG, "solve_targets: Y is NULL, N is not the N of set_train, Q outside 1 .. 65535 or ldy < N");
     const int L = c->L;
@@ -4402,9 +4335,9 @@ int dsmgp_solve_targets(dsmgp_ctx* c, const double* Y, int64_t N, int32_t Q, int
             if (!std::isfinite(mean[i])) return fail(c, DSMGP_E_ARG, "solve_targets: non-finite value in mean");
     HIPCHK(c, hipSetDevice(c->device));
     const int qpad = round_up(Q, TQ);
-    if (!c->tg_lists || c->tg_qpad != qpad)
+    if (!c->has(P_TG_LISTS) || c->tg_qpad != qpad)
         if (int rc = build_targets_plan(c, qpad)) return rc;
-    c->tg_valid = false;
+    c->invalidate(P_Z);
     if (int rc = c->d_tY.grow(c, (size_t)N * Q)) return rc;
     if (int rc = c->d_tmean.grow(c, (size_t)L * Q)) return rc;
     if (int rc = c->d_tmll.grow(c, (size_t)L * Q)) return rc;
@@ -4441,7 +4374,7 @@ int dsmgp_solve_targets(dsmgp_ctx* c, const double* Y, int64_t N, int32_t Q, int
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     if (seconds) *seconds = ms * 1e-3;
     c->tg_Q = Q;
-    c->tg_valid = true;
+    c->mark(P_Z);
     if (mll_out) HIPCHK(c, hipMemcpy(mll_out, c->d_tmll.p, (size_t)L * Q * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -4449,11 +4382,10 @@ int dsmgp_solve_targets(dsmgp_ctx* c, const double* Y, int64_t N, int32_t Q, int
 int dsmgp_predict_targets(dsmgp_ctx* c, double* mu_out, int64_t ld, double* seconds) {
     if (!c) return DSMGP_E_ARG;
     if (seconds) *seconds = 0.0;
-    if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "predict_targets before solve_targets on the current fit");
-    if (!c->predicted) return fail(c, DSMGP_E_STATE, "predict_targets before predict_run on the current fit");
+    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "predict_targets before solve_targets on the current fit");
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_targets before predict_run on the current fit");
     const size_t nr = (size_t)c->route_total;
-    if (nr == 0) return 0;          // (no routed rows: there is no sweep that would have set vt_valid)
-    if (!c->vt_valid) return fail(c, DSMGP_E_STATE, "predict_targets before predict_run on the current fit");
+    if (nr == 0) return 0;
     if (!mu_out || ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_targets: mu_out is NULL or ld < route_total");
     HIPCHK(c, hipSetDevice(c->device));
     const int L = c->L, Q = c->tg_Q, qpad = c->tg_qpad;
@@ -4498,7 +4430,7 @@ int dsmgp_predict_targets(dsmgp_ctx* c, double* mu_out, int64_t ld, double* seco
 
 int dsmgp_targets_fetch(dsmgp_ctx* c, int32_t leaf, double* Z_out) {
     if (!c) return DSMGP_E_ARG;
-    if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "targets_fetch before solve_targets on the current fit");
+    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "targets_fetch before solve_targets on the current fit");
     if (leaf < 0 || leaf >= c->L || !Z_out) return fail(c, DSMGP_E_ARG, "targets_fetch: leaf out of range or Z_out is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     const LeafHost& lf = c->leaves[leaf];
@@ -4550,7 +4482,7 @@ static void targets_a_tasks(const dsmgp_ctx* c, std::vector<TargetsATask>& ta) {
 int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, const double* col_weight, double* seconds) {
     if (!c) return DSMGP_E_ARG;
     if (seconds) *seconds = 0.0;
-    if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "targets_gradients before solve_targets on the current fit");
+    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "targets_gradients before solve_targets on the current fit");
     if (!grad_out) return fail(c, DSMGP_E_ARG, "targets_gradients: grad_out is NULL");
     const int L = c->L, Q = c->tg_Q, qpad = c->tg_qpad, D = c->D;
     if (int rc = check_stride(c, "targets_gradients", stride)) return rc;
@@ -4661,7 +4593,7 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev.b, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->xinv_all = true;
+    c->mark(P_XINV);
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     if (seconds) *seconds = ms * 1e-3;
@@ -4789,9 +4721,7 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
     if (int rc = dev_upload(c, c->lgardlin, al)) return rc;
     c->lgstride = 2 + D + (any_rq(c) ? 1 : 0);      // one more slot behind the dimensions: the sum for dK / dlog alpha
     if (int rc = c->d_lgpart.grow(c, 2 * (size_t)L + 2 * hv.size() + (size_t)c->lgstride * gd.size() + 3 * (size_t)D * al.size())) return rc;
-    c->lg_kinds.clear();
-    for (const HyperHost& h : c->hyper) c->lg_kinds.push_back(h.kind);
-    c->lg_ready = true;
+    c->mark(P_LG_LISTS);
     return 0;
 }
 
@@ -4836,7 +4766,7 @@ static void assemble_loo_gradient(const dsmgp_ctx* c, const HyperHost& h, const 
 int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* lpd_out, double* seconds) {
     if (!c) return DSMGP_E_ARG;
     if (seconds) *seconds = 0.0;
-    if (!c->fitted) return fail(c, DSMGP_E_STATE, "loo_gradients before fit");
+    if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "loo_gradients before fit");
     if (!grad_out) return fail(c, DSMGP_E_ARG, "grad_out is NULL");
     const int L = c->L;
     const int D = c->D;
@@ -4844,12 +4774,7 @@ int dsmgp_loo_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, double* 
     std::vector<double> lpd((size_t)L);
     double sec_loo = 0.0;
     if (int rc = dsmgp_loo(c, nullptr, nullptr, lpd.data(), &sec_loo)) return rc;
-    if (c->lg_ready) {
-        bool same = c->lg_kinds.size() == c->hyper.size();
-        for (size_t k = 0; same && k < c->hyper.size(); ++k) same = c->lg_kinds[k] == c->hyper[k].kind;
-        c->lg_ready = same;
-    }
-    if (!c->lg_ready)
+    if (!c->has(P_LG_LISTS))        // (built for the kernel kinds of now: a change of kind drops them, free_grad in dsmgp_set_hyper)
         if (int rc = build_loo_grad_plan(c)) return rc;
     const int gs = c->lgstride;
     double* pw = c->d_lgpart.p;
@@ -4937,7 +4862,7 @@ namespace {
 // What both calls need before their own kernels: the lists of the inversion and of the row sums, A's arena and its tasks
 static int loo_columns_prepare(dsmgp_ctx* c, OwnGradLists& own) {
     if (int rc = xinv_lists(c, own)) return rc;
-    if (!c->loo_ready)
+    if (!c->has(P_LOO_LISTS))
         if (int rc = build_loo_plan(c)) return rc;
     if (int rc = targets_slab(c, c->arenaA, c->cap_A, "loo_columns: no room for A = L^-T Z")) return rc;
     std::vector<TargetsATask> ta;
@@ -4957,7 +4882,7 @@ static int loo_columns_front(dsmgp_ctx* c) {
 int dsmgp_loo_columns(dsmgp_ctx* c, double* mu_out, int64_t ld, double* var_out, double* lpd_out, double* seconds) {
     if (!c) return DSMGP_E_ARG;
     if (seconds) *seconds = 0.0;
-    if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "loo_columns before solve_targets on the current fit");
+    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "loo_columns before solve_targets on the current fit");
     const int L = c->L, Q = c->tg_Q;
     const size_t nobs = (size_t)c->obs_ptr[L];
     if (mu_out && ld < (int64_t)nobs) return fail(c, DSMGP_E_ARG, "loo_columns: ld < obs_ptr[L]");
@@ -4984,7 +4909,7 @@ int dsmgp_loo_columns(dsmgp_ctx* c, double* mu_out, int64_t ld, double* var_out,
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev.b, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->xinv_all = true;
+    c->mark(P_XINV);
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     if (seconds) *seconds = ms * 1e-3;
@@ -5000,7 +4925,7 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
                                 double* seconds) {
     if (!c) return DSMGP_E_ARG;
     if (seconds) *seconds = 0.0;
-    if (!c->fitted || !c->tg_valid) return fail(c, DSMGP_E_STATE, "loo_columns_gradients before solve_targets on the current fit");
+    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "loo_columns_gradients before solve_targets on the current fit");
     if (!grad_out) return fail(c, DSMGP_E_ARG, "loo_columns_gradients: grad_out is NULL");
     const int L = c->L, Q = c->tg_Q, qpad = c->tg_qpad, D = c->D;
     if (int rc = check_stride(c, "loo_columns_gradients", stride)) return rc;
@@ -5156,7 +5081,7 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev.b, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->xinv_all = true;
+    c->mark(P_XINV);
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     if (seconds) *seconds = ms * 1e-3;
@@ -5251,7 +5176,7 @@ int dsmgp_kernel_matrix(dsmgp_ctx* c, int32_t kernel_id, const double* x1, int64
 
 int dsmgp_download_factor(dsmgp_ctx* c, int32_t leaf, double* F, double* alpha) {
     if (!c) return DSMGP_E_ARG;
-    if (!c->fitted) return fail(c, DSMGP_E_STATE, "download_factor before fit");
+    if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "download_factor before fit");
     if (leaf < 0 || leaf >= c->L) return fail(c, DSMGP_E_ARG, "leaf out of range");
     HIPCHK(c, hipSetDevice(c->device));
     const LeafHost& lf = c->leaves[leaf];
@@ -5302,7 +5227,7 @@ int dsmgp_work(dsmgp_ctx* c, double* alg_flops_update, int32_t* n_update_launche
 
 int dsmgp_lanes(dsmgp_ctx* c, int32_t* lanes) {
     if (!c || !lanes) return DSMGP_E_ARG;
-    *lanes = c->plan_ready ? c->nlanes : 0;
+    *lanes = c->has(P_PLAN) ? c->nlanes : 0;
     return 0;
 }
 
@@ -5320,8 +5245,7 @@ int dsmgp_reserve(dsmgp_ctx* c, int64_t bytes) {
     if (!c || bytes < 0) return DSMGP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_plan(c);
-    free_test(c);
+    free_plan_and_test(c);
     if (c->pool_base) (void)hipFree(c->pool_base);
     c->pool_base = nullptr;
     c->pool_cap = c->pool_top = c->pool_mark_plan = 0;
@@ -5341,8 +5265,7 @@ int dsmgp_release(dsmgp_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HostLog hl("release");
-    free_plan(c);
-    free_test(c);
+    free_plan_and_test(c);
     return 0;
 }
 
@@ -5969,7 +5892,7 @@ int dsmgp_fit_exchange(dsmgp_ctx* c, int64_t count, double* out) {
     if (!c) return DSMGP_E_ARG;
     if (!c->comm) return fail(c, DSMGP_E_STATE, "fit_exchange before comm_init");
     if (!out || count <= 0 || count < c->L) return fail(c, DSMGP_E_ARG, "fit_exchange: count must cover this rank's leaves");
-    if (c->L > 0 && !c->fitted) return fail(c, DSMGP_E_STATE, "fit_exchange before fit");
+    if (c->L > 0 && !c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "fit_exchange before fit");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = 2 * (size_t)count;
     if (int rc = xchg_reserve(c, n)) return rc;
@@ -5989,8 +5912,8 @@ int dsmgp_fit_exchange(dsmgp_ctx* c, int64_t count, double* out) {
 int dsmgp_aggregate_exchange(dsmgp_ctx* c, double* total_out) {
     if (!c) return DSMGP_E_ARG;
     if (!c->comm) return fail(c, DSMGP_E_STATE, "aggregate_exchange before comm_init");
-    if (!c->agg_partial_ready) return fail(c, DSMGP_E_STATE, "aggregate_exchange before aggregate_partial");
-    if (c->agg_total) return fail(c, DSMGP_E_STATE, "aggregate_exchange: these partial sums already hold the total over ranks");
+    if (!c->has(P_PARTIAL)) return fail(c, DSMGP_E_STATE, "aggregate_exchange before aggregate_partial");
+    if (c->has(P_TOTAL)) return fail(c, DSMGP_E_STATE, "aggregate_exchange: these partial sums already hold the total over ranks");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->agg_W * (size_t)c->n_t;
     if (int rc = xchg_reserve(c, n)) return rc;
@@ -6000,7 +5923,7 @@ int dsmgp_aggregate_exchange(dsmgp_ctx* c, double* total_out) {
     HIPCHK(c, hipGetLastError());
     if (total_out) HIPCHK(c, hipMemcpyAsync(total_out, c->d_agg_part.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->agg_total = true;
+    c->mark(P_TOTAL);
     return 0;
 }
 

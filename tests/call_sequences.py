@@ -242,18 +242,18 @@ NEEDS = {"fit": ("leaves", "hyper"), "download_factor": ("fit",), "predict_fetch
 # (dsmgp_routes and dsmgp_kernel_matrix keep answering after set_hyper / fit because neither is among their inputs.)
 EXCEPTIONS = {}
 
-# Readers that share an arena or a flag, from the comments of struct dsmgp_ctx (csrc/dsmgp_hip.cpp): every ordered pair inside a
+# Readers that share an arena or a product, from struct dsmgp_ctx (csrc/dsmgp_hip.cpp) and csrc/ctx_state.hpp: every ordered pair inside a
 # group must appear back to back in some sequence.
 SHARING = {
-    "arenaX / xinv_all (L^-T of every factor owner)": ("gradients", "loo", "loo_gradients", "predict_gradients.var",
+    "arenaX / P_XINV (L^-T of every factor owner)": ("gradients", "loo", "loo_gradients", "predict_gradients.var",
                                                        "targets_gradients", "loo_targets", "loo_targets_gradients"),
-    "alpha_valid / dinv_complete (ensure_alpha, ensure_dinv)": ("download_factor", "gradients", "loo", "loo_gradients",
+    "P_ALPHA / P_DINV (ensure_alpha, ensure_dinv)": ("download_factor", "gradients", "loo", "loo_gradients",
                                                                 "predict_gradients.mean", "solve_targets"),
-    "arenaVt / vt_valid, arenaCov, arenaB (K_tn L^-T and what is made from it)": ("predict_fetch", "predict_cov",
+    "arenaVt / P_VT, arenaCov, arenaB (K_tn L^-T and what is made from it)": ("predict_fetch", "predict_cov",
                                                                                  "predict_gradients.var", "predict_targets"),
-    "arenaPV, d_agg_part, d_agg_out, agg_* flags": ("predict_fetch", "aggregate.mixture", "aggregate.rbcm",
+    "arenaPV, d_agg_part, d_agg_out / P_PRED, P_PARTIAL, P_TOTAL, P_DONE": ("predict_fetch", "aggregate.mixture", "aggregate.rbcm",
                                                     "aggregate_partial.poe", "aggregate_finish", "scores"),
-    "arenaT, arenaA, arenaHc, arenaU / tg_valid, tg_lists": ("solve_targets", "targets_fetch", "predict_targets", "targets_gradients",
+    "arenaT, arenaA, arenaHc, arenaU / P_Z, P_TG_LISTS": ("solve_targets", "targets_fetch", "predict_targets", "targets_gradients",
                                                              "loo_targets", "loo_targets_gradients"),
     "d_kp (the KParam table)": ("kernel_matrix", "fit", "aggregate.rbcm"),
 }

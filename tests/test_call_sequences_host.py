@@ -144,6 +144,60 @@ def test_the_route_is_the_shortest_and_reproduces_the_path():
             m.apply(op, arg)
 
 
+# What each writer class does to the products of csrc/ctx_state.hpp: (invalidated, marked), read off the entry point in
+# csrc/dsmgp_hip.cpp and the free_* functions it calls.  No row: refused (argument checks only) and the poison pair (a set_hyper).
+_FREE_GRAD = ("grad_lists", "xinv", "loo_lists", "lg_lists")
+_NEW_PLAN = (("plan",), ())                                     # free_plan_and_test
+CTX_WRITES = {"set_train": (("plan", "routing_tree"), ()), "set_leaves": (("plan", "routing_tree"), ()), "set_sharing": _NEW_PLAN,
+              "set_hyper_values": (("fit",), ()), "set_hyper_kind": (_FREE_GRAD + ("fit",), ()),
+              "set_test": (("test",), ("test",)), "set_test_routed": (("test",), ("routing_tree", "test")),
+              "set_joint": ((), ()), "opt_ard": (_FREE_GRAD, ()), "opt_fused_gram": _NEW_PLAN, "opt_fused_steps": _NEW_PLAN,
+              "opt_lanes": _NEW_PLAN, "opt_diag_in_update": _NEW_PLAN, "opt_fit_graph": ((), ()),
+              "set_gradient_leaves": (("grad_lists",), ()), "reserve": _NEW_PLAN, "release": _NEW_PLAN,
+              "fit": (("fit",), ("fit",)), "predict_run": (("prediction",), ("vt", "prediction")),
+              "solve_targets": (("targets",), ("targets",))}
+CTX_WORD = {"fit": "fit", "test": "test", "pred": "prediction", "targets": "targets", "partial": "partial", "done": "done"}
+CTX_POOL_STACK = _FREE_GRAD + ("target_lists",)     # free_test under a reserved pool: what is carved above the test arenas goes too
+
+
+def test_the_context_s_dependency_table_is_the_model_s(tmp_path):
+    """csrc/ctx_state.hpp, printed by tests/ctx_state_dump.cpp, against Model.apply: from a context where everything is current,
+    with and without a reserved pool, one instance of every writer class fells a has() word of the model if and only if the
+    word's product falls with what the writer invalidates (and is not marked again by it); a product is only marked while its
+    parents are current; and every product is a root or falls with another."""
+    exe = str(tmp_path / "ctx_state_dump")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "deepstructuredmixtures_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "ctx_state_dump.cpp"), "-o", exe], check=True)
+    import json
+    table = json.loads(subprocess.run([exe], check=True, capture_output=True, text=True).stdout)
+    assert set(CTX_WORD.values()) | set(CTX_POOL_STACK) <= set(table)
+    assert all(set(inv) | set(mk) <= set(table) for inv, mk in CTX_WRITES.values())
+    assert set(CTX_WRITES) == set(cs.WRITERS) - {"refused", "poison_then_healthy"}
+    fallen = set().union(*(set(r["falls"]) for r in table.values()))
+    assert not [p for p, r in table.items() if r["parents"] and p not in fallen]
+    wrong = []
+    for reserved in (False, True):
+        for w, (inv, marks) in CTX_WRITES.items():
+            s = cs._Seq("x")
+            s.base()
+            if reserved:
+                s.do("reserve", 1)
+            s.full()
+            assert all(s.m.has(word) for word in CTX_WORD)
+            for op, arg in cs._writer_instances(s, w, 0):
+                assert s.do(op, arg) is None
+            if reserved and "test" in inv:
+                inv = inv + CTX_POOL_STACK
+            valid = set(table)
+            for p in inv:
+                valid -= {p} | set(table[p]["falls"])
+            for p in marks:
+                assert set(table[p]["parents"]) <= valid, (w, p)
+                valid.add(p)
+            wrong += [(w, reserved, word) for word, p in CTX_WORD.items() if s.m.has(word) != (p in valid)]
+    assert not wrong, wrong
+
+
 @pytest.fixture(scope="module")
 def oracle_run():
     """Every committed sequence on the dense chain, once: [(sequence id, index, call, before, [(ref, tol)])], the conds, the infos."""
