@@ -1,10 +1,10 @@
 """The dense float64 chain the call sequences of tests/call_sequences.py are checked against: LooColumnsOracleContext
 (tests/loo_columns_context.py) with the readers it lacks, and for every reader the reference value together with its tolerance.
 
-Every leaf is fitted densely (SciPy's Cholesky of K + (noise + 1e-8) I), for all kernel kinds, so that a leaf that is not
+Every leaf is fitted densely (tests/dense_gp.py), for all kernel kinds, so that a leaf that is not
 positive definite is reported (info != 0) and gets NaN wherever the device gives NaN.  The readers the chain lacks come from the
-dense modules: loo_columns_dense with one column for loo / loo_gradients, the formulas of predgrad_dense (with the rational
-quadratic derivative beside them) for predict_gradients, K_tt - V'V for predict_cov as tests/test_predcov_host.py restates it,
+dense modules: loo_columns_dense with one column for loo / loo_gradients, the kernel table of dense_kernels under the formulas
+of predgrad_dense for predict_gradients, K_tt - V'V for predict_cov as tests/test_predcov_host.py restates it,
 pred_tolerance.aggregate for the four families, targets_dense / targets_grad_dense for the target columns.
 
 No tolerance is new.  `SeqOracleContext.reference(m, reader)` returns [(value, tolerance)] with the tolerance the named helper
@@ -16,149 +16,36 @@ import numpy as np
 import scipy.linalg as sla
 
 import call_sequences as cs
+import dense_kernels as dk
 import loo_columns_dense as lcd
 import loo_dense as ld
 import loo_grad_dense as lgd
 import targets_dense as td
 import targets_grad_dense as tgd
+from dense_gp import DenseGP
 from loo_columns_context import LooColumnsOracleContext
 from oracle_context import OraclePartialContext
 from pred_tolerance import ATOL, EPS, LOG2PI, RTOL, Prop, agg_tol, aggregate, alpha_tol, mll_tol, moment_tol, row_entries, score_tol
 
-LINEAR = (2, 3)
 
-
-def il2_of(kind, h, D):
-    """1 / l_d^2 per input dimension (an iso kind: D equal values); h without the noise."""
-    nl = D if kind in tgd.ARD_KINDS else 1
-    return np.exp(-2.0 * np.asarray(h[:nl], dtype=np.float64)) * np.ones(D)
-
-
-def signal_of(kind, h, D):
-    if kind in LINEAR:
-        return 1.0
-    nl = D if kind in tgd.ARD_KINDS else 1
-    return float(np.exp(2.0 * h[nl + (1 if kind in tgd.RQ_KINDS else 0)]))
-
-
-def cross(kind, h, A, B):
-    """k(a_r, b_c) for every kind of include/dsmgp_hip.h (the formulas of predgrad_dense.kernelmatrix and rq_dense.kernelmatrix)."""
-    A, B = np.atleast_2d(A), np.atleast_2d(B)
-    D = A.shape[1]
-    il2, s2 = il2_of(kind, h, D), signal_of(kind, h, D)
-    if kind in LINEAR:
-        return (A * il2) @ B.T
-    d = A[:, None, :] - B[None, :, :]
-    if kind == 1:
-        return s2 * np.sum(np.exp(-0.5 * d * d * il2), axis=2)
-    r2 = np.sum(d * d * il2, axis=2)
-    if kind in (0, 4):
-        return s2 * np.exp(-0.5 * r2)
-    if kind in tgd.RQ_KINDS:
-        al = float(np.exp(h[D if kind == 10 else 1]))
-        return s2 * np.exp(-al * np.log1p(r2 / (2.0 * al)))
-    nu2 = 3.0 if kind in (5, 7) else 5.0
-    s = np.sqrt(nu2 * r2)
-    return s2 * np.exp(-s) * (1.0 + s + (s * s / 3.0 if nu2 == 5.0 else 0.0))
-
-
-def cross_dx(kind, h, Xt, X):
-    """G[t, i, d] = dk(x_t, x_i) / dx_{t,d} (predgrad_dense.kernel_dx; rational quadratic: -k / (1 + w) D_d / l_d^2)."""
-    Xt, X = np.atleast_2d(Xt), np.atleast_2d(X)
-    D = X.shape[1]
-    il2, s2 = il2_of(kind, h, D), signal_of(kind, h, D)
-    if kind in LINEAR:
-        return np.broadcast_to((X * il2)[None, :, :], (Xt.shape[0],) + X.shape).copy()
-    d = Xt[:, None, :] - X[None, :, :]
-    if kind == 1:
-        return -s2 * np.exp(-0.5 * d * d * il2) * d * il2
-    r2 = np.sum(d * d * il2, axis=2)
-    if kind in (0, 4):
-        return -(s2 * np.exp(-0.5 * r2))[:, :, None] * d * il2
-    if kind in tgd.RQ_KINDS:
-        al = float(np.exp(h[D if kind == 10 else 1]))
-        w = r2 / (2.0 * al)
-        return -(s2 * np.exp(-al * np.log1p(w)) / (1.0 + w))[:, :, None] * d * il2
-    nu2 = 3.0 if kind in (5, 7) else 5.0
-    s = np.sqrt(nu2 * r2)
-    c = 1.0 if nu2 == 3.0 else (1.0 + s) / 3.0
-    return -(s2 * np.exp(-s) * c)[:, :, None] * (nu2 * il2) * d
-
-
-def prior_diag(kind, h, Xt):
-    Xt = np.atleast_2d(Xt)
-    il2, s2 = il2_of(kind, h, Xt.shape[1]), signal_of(kind, h, Xt.shape[1])
-    if kind in LINEAR:
-        return (Xt * Xt) @ il2
-    return np.full(Xt.shape[0], s2 * (Xt.shape[1] if kind == 1 else 1.0))
-
-
-def prior_dx(kind, h, Xt):
-    Xt = np.atleast_2d(Xt)
-    return 2.0 * Xt * il2_of(kind, h, Xt.shape[1]) if kind in LINEAR else np.zeros(Xt.shape)
-
-
-def grad_scale(kind, h, X, Xt):
-    """predgrad_dense.grad_scale for every kind."""
-    il2 = il2_of(kind, h, X.shape[1])
-    if kind not in LINEAR:
-        return np.broadcast_to(np.sqrt(il2)[None, :], Xt.shape)
-    big = np.maximum(np.maximum(1.0, np.max(np.abs(X), axis=0))[None, :], np.abs(Xt))
-    return big * il2[None, :] / np.maximum(1.0, prior_diag(kind, h, Xt))[:, None]
-
-
-class Leaf:
-    """One leaf fitted densely: what OracleContext and its subclasses read of a leaf (L(), mll(), info, grad()), and K, cond."""
+class Leaf(DenseGP):
+    """A DenseGP kept by its inputs, with the ArdSE option the context's gradients() reads."""
     _cache = {}
 
     def __init__(self, kind, hyp, X, y, mean, ard_true=False):
-        self.kind, self.hyp, self.x, self.y, self.mean, self.ard_true = int(kind), np.asarray(hyp, dtype=np.float64), X, y, float(mean), ard_true
-        n = X.shape[0]
-        self.noise = float(np.exp(2.0 * self.hyp[-1]))
-        self.K = cross(self.kind, self.hyp[:-1], X, X)
-        Ky = self.K + (self.noise + 1e-8) * np.eye(n)
-        self.info = 0
-        try:
-            self.F = sla.cholesky(Ky, lower=True)
-            ev = np.linalg.eigvalsh(Ky)
-            self.cond = float(ev[-1] / ev[0])
-            self.z = sla.solve_triangular(self.F, y - self.mean, lower=True)
-            self.alpha = sla.solve_triangular(self.F, self.z, lower=True, trans="T")
-        except (sla.LinAlgError, ValueError):
-            self.F, self.info, self.cond = np.eye(n), 1, float("inf")
-            self.z = self.alpha = np.full(n, np.nan)
-
-    def L(self):
-        return self.F
-
-    def mll(self):
-        if self.info:
-            return float("nan")
-        return float(-(self.z @ self.z + 2.0 * np.sum(np.log(np.diag(self.F))) + LOG2PI * self.x.shape[0]) / 2.0)
+        super().__init__(kind, hyp, X, y, mean)
+        self.ard_true = ard_true
 
     def grad(self):
-        return tgd.column_gradients(self.kind, self.hyp, self.x, self.y[:, None], [self.mean], ard_true=self.ard_true)[0][0]
+        return mll_gradients(self, self.y, [self.mean], self.ard_true)[0]
 
 
 def mll_gradients(g, Y, mean, ard_true):
-    """targets_grad_dense.column_gradients on a fitted Leaf (its factor and cond_2(K_y) instead of a factorisation and an
-    eigenvalue decomposition per call): G[Q, len(hyp)], every column's gradient row in the library's convention."""
-    n, D = g.x.shape
+    """targets_grad_dense.column_gradients on a fitted leaf (its factor instead of a factorisation per call): G[Q, len(hyp)],
+    every column's gradient row in the library's convention."""
     Y = Y[:, None] if Y.ndim == 1 else Y
     mean = np.broadcast_to(np.asarray(mean, dtype=np.float64), (Y.shape[1],))
-    _, dK = tgd.kernel_and_derivatives(g.kind, g.hyp[:-1], g.x)
-    Kinv = sla.cho_solve((g.F, True), np.eye(n))
-    Kinv = 0.5 * (Kinv + Kinv.T)
-    A = Kinv @ (Y - mean[None, :])
-    G = np.zeros((Y.shape[1], g.hyp.size))
-    for j in range(Y.shape[1]):
-        P = np.outer(A[:, j], A[:, j]) - Kinv
-        for t, M in enumerate(dK):
-            G[j, t] = 0.5 * np.sum(P * M)
-        G[j, -1] = g.noise * np.trace(P)
-    if g.kind == 1 and not ard_true:
-        G[:, :D] = 0.0
-    return G
+    return tgd.gradients_from_factor(g.kind, g.hyp, g.x, g.F, Y, mean, ard_true)[0]
 
 
 class SeqOracleContext(LooColumnsOracleContext):
@@ -218,11 +105,11 @@ class SeqOracleContext(LooColumnsOracleContext):
             rows = self._rows(i)
             if not rows.size:
                 continue
-            Ktn = cross(g.kind, g.hyp[:-1], self.Xt[rows], g.x)
+            Ktn = dk.value(g.kind, g.hyp[:-1], self.Xt[rows], g.x)
             V = sla.solve_triangular(g.F, Ktn.T, lower=True)
             self._V[i] = (Ktn, V)
             m = g.mean + Ktn @ g.alpha
-            v = prior_diag(g.kind, g.hyp[:-1], self.Xt[rows]) - np.sum(V * V, axis=0) + g.noise
+            v = dk.prior_diag(g.kind, g.hyp[:-1], self.Xt[rows]) - np.sum(V * V, axis=0) + g.noise
             mu.append(m if not g.info else np.full(rows.size, np.nan))
             var.append(v if not g.info else np.full(rows.size, np.nan))
         self._mu = np.concatenate(mu) if mu else np.zeros(0)
@@ -252,7 +139,7 @@ class SeqOracleContext(LooColumnsOracleContext):
         g0 = self.hyper[0]
         kw = dict(coef=coef, group=group, G=G, plain=False)
         if family == 3:
-            kw.update(kss_prior=prior_diag(g0[0], g0[1][:-1], self.Xt), noise_prior=float(np.exp(2.0 * g0[1][-1])))
+            kw.update(kss_prior=dk.prior_diag(g0[0], g0[1][:-1], self.Xt), noise_prior=float(np.exp(2.0 * g0[1][-1])))
         with np.errstate(all="ignore"):
             m, v = aggregate(family, list(self._mu), list(self._var), ent, log=np.log, **kw)
         self._amu, self._avar = np.array(m, dtype=np.float64), np.array(v, dtype=np.float64)
@@ -285,7 +172,7 @@ class SeqOracleContext(LooColumnsOracleContext):
         kss, noise = [], []
         for i, g in enumerate(self.gps):
             rows = self._rows(i)
-            kss.append(prior_diag(g.kind, g.hyp[:-1], self.Xt[rows]) if rows.size else np.zeros(0))
+            kss.append(dk.prior_diag(g.kind, g.hyp[:-1], self.Xt[rows]) if rows.size else np.zeros(0))
             noise.append(np.full(rows.size, g.noise))
         kss, noise = np.concatenate(kss), np.concatenate(noise)
         tm, tv = moment_tol(self._mu, self._var, kss, noise, max(1.0, float(np.max(np.abs(self.y)))))
@@ -304,7 +191,7 @@ class SeqOracleContext(LooColumnsOracleContext):
             S1 = np.array([sum(coef[l] * self._mu[e] ** 2 for l, e in er) for er in ent])
         if family == "rbcm":
             g0 = self.hyper[0]
-            kw.update(kss_prior=prior_diag(g0[0], g0[1][:-1], self.Xt), noise_prior=float(np.exp(2.0 * g0[1][-1])))
+            kw.update(kss_prior=dk.prior_diag(g0[0], g0[1][:-1], self.Xt), noise_prior=float(np.exp(2.0 * g0[1][-1])))
         with np.errstate(all="ignore"):
             tm, tv = agg_tol(cs.FAMILY[family], np.nan_to_num(self._mu), np.nan_to_num(self._var, nan=1.0), tm_e / 2.0, tv_e / 2.0, ent,
                              S1=S1, **kw)
@@ -362,9 +249,9 @@ class SeqOracleContext(LooColumnsOracleContext):
         if name == "predict_cov":
             l = int(np.argmax(np.diff(self.rptr)))
             g, rows = gps[l], self._rows(l)
-            kss = prior_diag(g.kind, g.hyp[:-1], self.Xt[rows])
+            kss = dk.prior_diag(g.kind, g.hyp[:-1], self.Xt[rows])
             V = self._V[l][1]
-            S = cross(g.kind, g.hyp[:-1], self.Xt[rows], self.Xt[rows]) - V.T @ V + g.noise * np.eye(rows.size)
+            S = dk.value(g.kind, g.hyp[:-1], self.Xt[rows], self.Xt[rows]) - V.T @ V + g.noise * np.eye(rows.size)
             # tests/test_predcov_gpu.py entry_tol, doubled
             return [(S, 2.0 * (RTOL * np.abs(S) + ATOL * np.maximum(1.0, np.maximum(kss[:, None], kss[None, :]) + g.noise)))]
         if name == "predict_gradients":
@@ -375,12 +262,12 @@ class SeqOracleContext(LooColumnsOracleContext):
                 if not rows.size:
                     continue
                 Xr, h = self.Xt[rows], g.hyp[:-1]
-                Gd = cross_dx(g.kind, h, Xr, g.x)
+                Gd = dk.d_input(g.kind, h, Xr, g.x)
                 beta = sla.solve_triangular(g.F, self._V[i][1], lower=True, trans="T").T
                 a = np.einsum("i,tid->td", np.nan_to_num(g.alpha), Gd)
-                b = prior_dx(g.kind, h, Xr) - 2.0 * np.einsum("ti,tid->td", beta, Gd)
-                gs = grad_scale(g.kind, h, g.x, Xr)
-                vscale = np.maximum(1.0, prior_diag(g.kind, h, Xr) + g.noise)[:, None]
+                b = dk.prior_dx(g.kind, h, Xr) - 2.0 * np.einsum("ti,tid->td", beta, Gd)
+                gs = dk.grad_scale(g.kind, h, g.x, Xr)
+                vscale = np.maximum(1.0, dk.prior_diag(g.kind, h, Xr) + g.noise)[:, None]
                 nan = np.nan if g.info else 0.0             # predgrad_dense.tolerances, doubled
                 dmu.append(a + nan)
                 dvar.append(b + nan)
@@ -504,7 +391,7 @@ class SeqOracleContext(LooColumnsOracleContext):
             out = []
             for k in sorted(m.hyper):
                 kind, h = self.hyper[k]
-                K = cross(kind, h[:-1], X[:130], X[130:263])
+                K = dk.value(kind, h[:-1], X[:130], X[130:263])
                 out.append((K, np.full(K.shape, 1e-13 * max(1.0, float(np.max(np.abs(K)))))))     # tests/test_gpu_parity.py
             return out
         raise KeyError(reader)

@@ -13,12 +13,12 @@ tolerance metadata).  The n = 1 and n = 2 cases must agree with their closed for
 mpmath only (the data come from numpy's PCG64 generator).  Run from the repo root:
     python tests/golden/make_ardse_product_golden.py        (a minute or two; the output is byte-reproducible)
 """
-import io
 import os
-import zipfile
 
 import mpmath as mp
 import numpy as np
+
+from mp_kernels import savez_reproducible, spread_logl as _logl, value
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 mp.mp.dps = 50
@@ -34,7 +34,7 @@ def mp_case(X, y, mean, logl, logs, logNoise, Xt):
     c = noise + mp.mpf("1e-8")
 
     def k(a, b):
-        return s2 * mp.e ** (-sum((a[d] - b[d]) ** 2 * il2[d] for d in range(D)) / 2)
+        return value(4, a, b, il2, None, s2)
 
     K = [[k(x[i], x[j]) for j in range(i + 1)] for i in range(n)]
     full = lambda A, i, j: A[i][j] if j <= i else A[j][i]      # noqa: E731
@@ -109,10 +109,6 @@ def closed_form(X, y, mean, logl, logs, logNoise):
     return [P01 * b * q[d] for d in range(D)] + [(P00 + P11) * s2 + 2 * P01 * b, noise * (P00 + P11), mll]
 
 
-def _logl(D, lo=0.7, hi=1.4):
-    return np.log(0.35 * np.sqrt(D) * np.linspace(lo, hi, D)) if D > 1 else np.log([0.35])
-
-
 # name, n, D, logl, logs, logNoise, target offset (the leaf's mean stays 0: the kernel carries it)
 SPECS = [
     ("n1_d3", 1, 3, _logl(3), 0.1, np.log(0.2), 0.0),
@@ -126,18 +122,6 @@ SPECS = [
     ("spread_d8", 129, 8, np.log(np.geomspace(0.05, 20.0, 8)), 0.0, np.log(0.2), 0.0),
     ("offset_d3", 128, 3, _logl(3), 0.5, np.log(0.2), 3.0),
 ]
-
-
-def savez_reproducible(path, arrays):
-    """np.savez_compressed with fixed member timestamps, so that a rerun writes the same bytes."""
-    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
-        for key in sorted(arrays):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.asarray(arrays[key]), allow_pickle=False)
-            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            info.external_attr = 0o600 << 16
-            z.writestr(info, buf.getvalue())
 
 
 def main():

@@ -11,8 +11,8 @@ the device uses.  The components are stored in the library's convention (src/gau
   ArdLinear  the true d/dlog l_d, 0 in the variance slot (include/dsmgp_hip.h, DSMGP_KIND_ARD_LINEAR)
 
 together with the log-marginal, cond_2(K_y) and, for the tolerance of the weak-signal cases, n and c tr K_y^-1.  Before
-anything is stored the oracle (oracle.gp, tests/ard_linear_dense.DenseGP for ArdLinear) must agree with the 50-digit values,
-and the n = 1 and n = 2 cases must agree with their closed forms.  Imports: oracle/, datagen and tests/ard_linear_dense.py
+anything is stored the oracle (oracle.gp, tests/dense_gp.DenseGP for ArdLinear) must agree with the 50-digit values,
+and the n = 1 and n = 2 cases must agree with their closed forms.  Imports: oracle/, datagen and tests/dense_gp.py
 only.  Run from the repo root:  python tests/golden/make_grad_golden.py   (about a minute; the output is byte-reproducible)
 """
 import importlib.util
@@ -29,7 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import gp as ogp  # noqa: E402
-from ard_linear_dense import DenseGP  # noqa: E402
+from dense_gp import DenseGP  # noqa: E402
 
 # the data generator alone, loaded from its file: importing it through the package would run the product's model and tree code
 _spec = importlib.util.spec_from_file_location("datagen", os.path.join(ROOT, "deepstructuredmixtures_amd", "datagen.py"))
@@ -195,7 +195,7 @@ SPECS = [
 
 def oracle_grad(kind, loghyp, logNoise, X, y, mean):
     if kind == 3:
-        g = DenseGP(X, y, mean, loghyp[:-1], logNoise)
+        g = DenseGP(3, np.append(loghyp, logNoise), X, y, mean)
         return g, g.grad()
     g = ogp.GaussianProcess(X, y, mean, ogp.make_kernel(kind, loghyp), logNoise, exact_dist=True).update_cholesky()
     return g, g.grad()

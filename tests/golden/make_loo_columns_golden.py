@@ -30,23 +30,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, HERE)
 
 from make_pred_golden import uniform, normal  # noqa: E402
-from make_predcov_golden import savez_reproducible  # noqa: E402
-from make_targets_grad_golden import entry  # noqa: E402
+import mp_kernels as mpk  # noqa: E402
 import loo_columns_dense as lcd  # noqa: E402
 
 mp.mp.dps = 50
 JIT = mp.mpf("1e-8")
-
-
-def true_entry(kind, h, a, b):
-    """(k, [true dk / dtheta per slot before logNoise]): `entry` without the reference's factors sigma."""
-    k, dk = entry(kind, h, a, b)
-    if kind == 0:
-        sigma = mp.e ** h[1]
-        dk = [dk[0] / sigma, 2 * k]
-    elif kind == 1:
-        dk = dk[:-1] + [2 * k]
-    return k, dk
 
 
 def inverse_parts(kind, hmp, x, noise_log):
@@ -54,11 +42,12 @@ def inverse_parts(kind, hmp, x, noise_log):
     n = len(x)
     nt = len(hmp)
     noise = mp.e ** (2 * noise_log)
+    par = mpk.unpack(kind, hmp, len(x[0]))
     K = mp.zeros(n, n)
     dK = [mp.zeros(n, n) for _ in range(nt + 1)]
     for i in range(n):
         for j in range(i + 1):
-            k, dk = true_entry(kind, hmp, x[i], x[j])
+            k, dk = mpk.d_hyper(kind, x[i], x[j], *par)
             K[i, j] = K[j, i] = k
             for t in range(nt):
                 dK[t][i, j] = dK[t][j, i] = dk[t]
@@ -194,7 +183,7 @@ def main():
         for k, v in rec.items():
             flat[f"{name}/{k}"] = np.asarray(v)
     out = os.path.join(HERE, "gp_loo_columns.npz")
-    savez_reproducible(out, flat)
+    mpk.savez_reproducible(out, flat, compresslevel=9)
     print(f"{out}: {os.path.getsize(out)} bytes")
 
 

@@ -32,68 +32,25 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, HERE)
 
+import dense_kernels  # noqa: E402
 import loo_grad_dense as lgd  # noqa: E402
 from make_pred_golden import uniform, normal  # noqa: E402
-from make_predcov_golden import savez_reproducible  # noqa: E402
+import mp_kernels as mpk  # noqa: E402
 
 mp.mp.dps = 50
 JIT = mp.mpf("1e-8")
 
 
-def hyper(kind, h, D):
-    """(il2 per dimension, sigma^2) from the mp hyper-vector without the noise."""
-    ard = kind in (1, 3, 4, 7, 8)
-    nl = D if ard else 1
-    il2 = [1 / mp.e ** (2 * v) for v in h[:nl]]
-    return (il2 if ard else il2 * D), (mp.mpf(1) if kind in (2, 3) else mp.e ** (2 * h[nl]))
-
-
-def kval(kind, a, b, il2, s2):
-    if kind == 1:
-        return s2 * mp.fsum(mp.e ** (-((p - q) ** 2) * il / 2) for p, q, il in zip(a, b, il2))
-    if kind in (2, 3):
-        return mp.fsum(p * q * il for p, q, il in zip(a, b, il2))
-    r2 = mp.fsum((p - q) ** 2 * il for p, q, il in zip(a, b, il2))
-    if kind in (0, 4):
-        return s2 * mp.e ** (-r2 / 2)
-    nu2 = 3 if kind in (5, 7) else 5
-    s = mp.sqrt(nu2 * r2)
-    return s2 * mp.e ** (-s) * (1 + s + (s * s / 3 if nu2 == 5 else 0))
-
-
-def kder(kind, a, b, il2, s2, D):
-    """[dk/dtheta_j] of one entry over [logl..., logs]."""
-    ard = kind in (1, 3, 4, 7, 8)
-    q = [(p - r) ** 2 * il for p, r, il in zip(a, b, il2)]
-    if kind in (2, 3):
-        per = [-2 * p * r * il for p, r, il in zip(a, b, il2)]
-        return (per if ard else [mp.fsum(per)]) + [mp.mpf(0)]
-    if kind == 1:
-        e = [s2 * mp.e ** (-qd / 2) for qd in q]
-        return [ed * qd for ed, qd in zip(e, q)] + [2 * mp.fsum(e)]
-    r2 = mp.fsum(q)
-    if kind in (0, 4):
-        k = s2 * mp.e ** (-r2 / 2)
-        per = [k * qd for qd in q]
-    else:
-        nu2 = 3 if kind in (5, 7) else 5
-        s = mp.sqrt(nu2 * r2)
-        k = s2 * mp.e ** (-s) * (1 + s + (s * s / 3 if nu2 == 5 else 0))
-        cs = mp.mpf(1) if nu2 == 3 else (1 + s) / 3
-        per = [s2 * mp.e ** (-s) * cs * nu2 * qd for qd in q]
-    return (per if ard else [mp.fsum(per)]) + [2 * k]
-
-
 def chol(kind, x, h, logNoise):
     n, D = len(x), len(x[0])
-    il2, s2 = hyper(kind, h, D)
+    par = mpk.unpack(kind, h, D)
     c = mp.e ** (2 * logNoise) + JIT
     L = []
     for i in range(n):
         row = []
         for j in range(i):
-            row.append((kval(kind, x[i], x[j], il2, s2) - mp.fdot(row[:j], L[j][:j])) / L[j][j])
-        row.append(mp.sqrt(kval(kind, x[i], x[i], il2, s2) + c - mp.fdot(row, row)))
+            row.append((mpk.value(kind, x[i], x[j], *par) - mp.fdot(row[:j], L[j][:j])) / L[j][j])
+        row.append(mp.sqrt(mpk.value(kind, x[i], x[i], *par) + c - mp.fdot(row, row)))
         L.append(row)
     return L
 
@@ -128,7 +85,7 @@ def lpd_of(kind, x, yc, h, logNoise):
 def literal_513(kind, x, yc, h, logNoise):
     """(gradient over [logl..., logs, logNoise], lpd) from G = K_y^-1, eq. 5.13 as printed."""
     n, D = len(x), len(x[0])
-    il2, s2 = hyper(kind, h, D)
+    par = mpk.unpack(kind, h, D)
     L = chol(kind, x, h, logNoise)
     cols = linv_columns(L)
     # G = L^-T L^-1: G[i][j] = sum_k Linv[k][i] Linv[k][j], k >= max(i, j); column i of L^-1 holds rows i ..
@@ -141,7 +98,7 @@ def literal_513(kind, x, yc, h, logNoise):
     log2pi = mp.log(2 * mp.pi)
     lpd = mp.fsum(-(log2pi - mp.log(d[i]) + alpha[i] ** 2 / d[i]) / 2 for i in range(n))
     nh = len(h)
-    dk = [[kder(kind, x[i], x[j], il2, s2, D) for j in range(n)] for i in range(n)]
+    dk = [[mpk.d_hyper(kind, x[i], x[j], *par)[1] for j in range(n)] for i in range(n)]
     grad = []
     noise2 = 2 * mp.e ** (2 * logNoise)
     for p in range(nh + 1):
@@ -210,12 +167,12 @@ def run_case(args):
         assert dev <= mp.mpf("1e-24"), (name, p, fd, g_mp[p])
     grad = np.array([float(v) for v in g_mp])
     noise = float(np.exp(2.0 * logNoise))
-    K = lgd.kernel_matrix(kind, loghyp, X, X)
+    K = dense_kernels.value(kind, loghyp, X, X)
     ev = np.linalg.eigvalsh(K + (noise + lgd.JITTER) * np.eye(n))
     cond = float(f"{ev[-1] / ev[0]:.4g}")
     assert cond <= 1e6, (name, cond)
     case = dict(kind=kind, cond=cond, weak=bool(weak), logNoise=logNoise, y=y, mean=mean)
-    dense = lgd.loo_grad_dense(K, lgd.kernel_derivatives(kind, loghyp, X), noise, y, mean)
+    dense = lgd.loo_grad_dense(K, dense_kernels.d_hyper(kind, loghyp, X)[1], noise, y, mean)
     ratio = float(np.max(np.abs(dense - grad) / lgd.tolerance(case, grad, K)))
     line = (f"{name:24s} kind {kind} n {n:3d} D {D:2d}  cond {cond:9.4g}  max|y| {np.max(np.abs(y)):8.3g}  |g|inf {np.max(np.abs(grad)):9.3g}  "
             f"fd dev {float(worst):.1e}  dense err / tol {ratio:.2g}")
@@ -234,7 +191,7 @@ def main():
         for k, v in rec.items():
             flat[f"{name}/{k}"] = np.asarray(v)
     out = os.path.join(HERE, "gp_loo_grad.npz")
-    savez_reproducible(out, flat)
+    mpk.savez_reproducible(out, flat, compresslevel=9)
     print(f"{out}: {os.path.getsize(out)} bytes")
 
 

@@ -15,16 +15,16 @@ tolerance metadata).  The n = 1 and n = 2 cases must agree with their closed for
 numerical derivatives of the closed-form log-marginal, independent of the formula above -- before anything is written.  Cases
 include duplicate training points (s = 0 off the diagonal) and length-scales spread over two decades.  The largest leaf has 300
 rows: 50-digit Cholesky factors above 1,300 rows would take hours, so tests/test_matern_gpu.py checks those sizes against the dense
-restatement (tests/matern_dense.py), which tests/test_matern_host.py pins to these references.  Imports numpy and mpmath only
+restatement (tests/dense_gp.py), which tests/test_matern_host.py pins to these references.  Imports numpy and mpmath only
 (the data come from numpy's PCG64 generator).  Run from the repo root:
     python tests/golden/make_matern_golden.py        (a few minutes; the output is byte-reproducible)
 """
-import io
 import os
-import zipfile
 
 import mpmath as mp
 import numpy as np
+
+from mp_kernels import d_hyper, iso_logl as _iso, savez_reproducible, spread_logl as _logl, unpack, value
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 mp.mp.dps = 50
@@ -40,23 +40,9 @@ def _ard(kind):
 
 
 def _kfun(kind, logl, logs, D):
-    """k(a, b) and dk/dlog l_d (all d) at 50 digits."""
-    nu2 = _nu2(kind)
-    ll = [mp.mpf(float(v)) for v in logl]
-    il2 = [1 / mp.e ** (2 * (ll[d] if _ard(kind) else ll[0])) for d in range(D)]
-    s2 = mp.e ** (2 * mp.mpf(float(logs)))
-
-    def k(a, b):
-        s = mp.sqrt(nu2 * sum((a[d] - b[d]) ** 2 * il2[d] for d in range(D)))
-        p = 1 + s if nu2 == 3 else 1 + s + s * s / 3
-        return s2 * p * mp.e ** (-s)
-
-    def dk(a, b):
-        s = mp.sqrt(nu2 * sum((a[d] - b[d]) ** 2 * il2[d] for d in range(D)))
-        c = 1 if nu2 == 3 else (1 + s) / 3
-        return [s2 * mp.e ** (-s) * c * nu2 * (a[d] - b[d]) ** 2 * il2[d] for d in range(D)]
-
-    return k, dk, s2
+    """k(a, b) and dk/dlog l (one entry for an iso kind, D for an ARD kind) at 50 digits."""
+    par = unpack(kind, [mp.mpf(float(v)) for v in logl] + [mp.mpf(float(logs))], D)
+    return (lambda a, b: value(kind, a, b, *par)), (lambda a, b: d_hyper(kind, a, b, *par)[1][:-1]), par[2]
 
 
 def mp_case(kind, X, y, mean, logl, logs, logNoise, Xt):
@@ -87,7 +73,7 @@ def mp_case(kind, X, y, mean, logl, logs, logNoise, Xt):
     alpha = [mp.fdot([full(Kinv, i, j) for j in range(n)], yc) for i in range(n)]
     mll = -(mp.fdot(yc, alpha) + 2 * sum(mp.log(L[i][i]) for i in range(n)) + n * mp.log(2 * mp.pi)) / 2
     # gradients: W = alpha alpha^T - K_y^-1 contracted entry by entry (off-diagonal entries twice)
-    gl = [mp.mpf(0)] * D
+    gl = [mp.mpf(0)] * (D if _ard(kind) else 1)
     gs = mp.mpf(0)
     trW = mp.mpf(0)
     for i in range(n):
@@ -99,11 +85,9 @@ def mp_case(kind, X, y, mean, logl, logs, logNoise, Xt):
                 trW += w
                 continue
             dki = dk(x[i], x[j])
-            for d in range(D):
+            for d in range(len(gl)):
                 gl[d] += f * w * dki[d]
     gl = [v / 2 for v in gl]
-    if not _ard(kind):
-        gl = [mp.fsum(gl)]
     grad = gl + [gs, noise * trW]
     # predictive moments
     mu, var = [], []
@@ -159,14 +143,6 @@ def closed_form(kind, X, y, mean, logl, logs, logNoise):
     return grads + [f(*th)]
 
 
-def _logl(D, lo=0.7, hi=1.4):
-    return np.log(0.35 * np.sqrt(D) * np.linspace(lo, hi, D)) if D > 1 else np.log([0.35])
-
-
-def _iso(D):
-    return np.log([0.35 * np.sqrt(D)])
-
-
 # name, kind, n, D, logl, logs, logNoise, target offset (the leaf's mean stays 0: the kernel carries it), duplicated rows
 SPECS = [
     ("n1_iso32_d3", ISO32, 1, 3, _iso(3), 0.1, np.log(0.2), 0.0, 0),
@@ -189,18 +165,6 @@ SPECS = [
     ("dup_ard32_d3", ARD32, 140, 3, _logl(3), 0.0, np.log(0.3), 0.0, 24),
     ("offset_iso32_d3", ISO32, 128, 3, _iso(3), 0.5, np.log(0.2), 3.0, 0),
 ]
-
-
-def savez_reproducible(path, arrays):
-    """np.savez_compressed with fixed member timestamps, so that a rerun writes the same bytes."""
-    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
-        for key in sorted(arrays):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.asarray(arrays[key]), allow_pickle=False)
-            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            info.external_attr = 0o600 << 16
-            z.writestr(info, buf.getvalue())
 
 
 def main():

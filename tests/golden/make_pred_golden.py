@@ -20,8 +20,8 @@ mu = mean + k*.alpha and sigma^2 = k(x*, x*) - |L^-1 k*|^2 + noise (src/gaussian
                   (src/common.jl:134-143,275-302), both at 50 digits, and the scores.
 
 Before anything is stored, every value is checked against the float64 oracle (oracle.gp, oracle.spn, oracle.scores;
-tests/ard_linear_dense.DenseGP for ArdLinear) and the n = 1 cases against their closed forms.  Imports: oracle/, datagen,
-tests/ard_linear_dense.py and tests/pred_tolerance.py (the aggregation formula, run here at 50 digits) only.  Run from the repo root:  python tests/golden/make_pred_golden.py  (a few minutes;
+tests/dense_gp.DenseGP for ArdLinear) and the n = 1 cases against their closed forms.  Imports: oracle/, datagen,
+tests/dense_gp.py and tests/pred_tolerance.py (the aggregation formula, run here at 50 digits) only.  Run from the repo root:  python tests/golden/make_pred_golden.py  (a few minutes;
 the output is byte-reproducible)
 """
 import importlib.util
@@ -38,7 +38,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import gp as ogp, spn as ospn, scores as oscores, tree as otree  # noqa: E402
-from ard_linear_dense import DenseGP  # noqa: E402
+from dense_gp import DenseGP  # noqa: E402
 from pred_tolerance import Prop, aggregate, row_entries  # noqa: E402
 
 # the data generator alone, loaded from its file: importing it through the package would run the product's model and tree code
@@ -138,7 +138,7 @@ class MPLeaf:
 def oracle_leaf(kind, loghyp, logNoise, X, y, mean):
     """The float64 oracle of one leaf (DenseGP for ArdLinear)."""
     if kind == 3:
-        return DenseGP(X, y, mean, loghyp[:-1], logNoise)
+        return DenseGP(3, np.append(loghyp, logNoise), X, y, mean)
     return ogp.GaussianProcess(X, y, mean, ogp.make_kernel(kind, loghyp), logNoise, exact_dist=True).update_cholesky()
 
 

@@ -14,7 +14,7 @@ away, far rows, one row listed twice):
   incompressible doubles, and the file stays below the largest fixture committed before it (gp_pred.npz).
 
 Before anything is stored every case is checked against the float64 oracle -- oracle.gp prediction(full_cov=True) for kinds
-0-2, the dense helpers of tests/ (ard_linear_dense, ardse_product_dense, matern_dense) for the others -- to the variance
+0-2, the dense GP of tests/dense_gp.py for the others -- to the variance
 tolerance of tests/pred_tolerance.moment_tol applied per entry:  RTOL |Sigma_rc| + ATOL max(1, max(kss_r, kss_c) + noise).
 Run from the repo root:  python tests/golden/make_predcov_golden.py   (a few minutes; the output is byte-reproducible)
 """
@@ -23,7 +23,6 @@ import sys
 
 import mpmath as mp
 import numpy as np
-import scipy.linalg as sla
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -32,9 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, HERE)
 
 from oracle import gp as ogp  # noqa: E402
-import ard_linear_dense  # noqa: E402
-import ardse_product_dense  # noqa: E402
-import matern_dense  # noqa: E402
+from dense_gp import DenseGP  # noqa: E402
 from pred_tolerance import RTOL, ATOL  # noqa: E402
 import io  # noqa: E402
 import zipfile  # noqa: E402
@@ -137,7 +134,6 @@ class MPCov:
 
 def oracle_cov(kind, loghyp, logNoise, X, y, mean, Xt):
     """Sigma without noise from the float64 oracle of the kind."""
-    nl = len(loghyp) - 1
     if kind <= 2:
         g = ogp.GaussianProcess(X, y, mean, ogp.make_kernel(kind, loghyp), logNoise, exact_dist=True).update_cholesky()
         assert g.info == 0
@@ -145,18 +141,9 @@ def oracle_cov(kind, loghyp, logNoise, X, y, mean, Xt):
         S = S.copy()
         S[np.diag_indices(Xt.shape[0])] -= g.getnoise()
         return S
-    if kind == 3:
-        g = ard_linear_dense.DenseGP(X, y, mean, loghyp[:nl], logNoise)
-        km = lambda a, b: ard_linear_dense.kernelmatrix(loghyp[:nl], a, b)                          # noqa: E731
-    elif kind == 4:
-        g = ardse_product_dense.DenseGP(X, y, mean, loghyp[:nl], loghyp[nl], logNoise)
-        km = lambda a, b: ardse_product_dense.kernelmatrix(loghyp[:nl], loghyp[nl], a, b)           # noqa: E731
-    else:
-        g = matern_dense.DenseGP(X, y, mean, kind, loghyp[:nl], loghyp[nl], logNoise)
-        km = lambda a, b: matern_dense.kernelmatrix(kind, loghyp[:nl], loghyp[nl], a, b)            # noqa: E731
+    g = DenseGP(kind, np.append(loghyp, logNoise), X, y, mean)
     assert g.info == 0
-    V = sla.solve_triangular(g.L(), km(X, Xt), lower=True)
-    return km(Xt, Xt) - V.T @ V
+    return g.prediction_cov(Xt, with_noise=False)
 
 
 # name, kind, n, routed rows, D, loghyp (library hyper-vector without the noise), logNoise

@@ -34,6 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, HERE)
 
 from deepstructuredmixtures_amd import datagen  # noqa: E402
+import dense_kernels as dk  # noqa: E402
 import predgrad_dense as pgd  # noqa: E402
 from pred_tolerance import aggregate, row_entries  # noqa: E402
 from make_predcov_golden import savez_reproducible  # noqa: E402
@@ -47,10 +48,10 @@ AGG_ROWS = 120
 def loghyp_of(kind, D):
     """Hyper-vector without the noise; length-scales grow with sqrt(D) so that cond(K_y) stays below 1e6."""
     ls = np.array([0.35, 0.5, 0.42])[:D] * np.sqrt(D) if D <= 3 else np.full(D, 0.3 * np.sqrt(D))
-    if kind in pgd.LINEAR:
+    if kind in dk.LINEAR:
         ls = ls + 0.5
-    nl = D if kind in pgd.ARD else 1
-    return np.concatenate([np.log(ls[:nl]), [0.0 if kind in pgd.LINEAR else 0.1]])
+    nl = D if kind in dk.ARD else 1
+    return np.concatenate([np.log(ls[:nl]), [0.0 if kind in dk.LINEAR else 0.1]])
 
 
 def inputs(n, nt, D):
@@ -77,10 +78,10 @@ class MPGrad:
         n, D = X.shape
         h = [mp.mpf(float(v)) for v in loghyp]
         self.noise = mp.e ** (2 * mp.mpf(float(logNoise)))
-        nl = D if kind in pgd.ARD else 1
+        nl = D if kind in dk.ARD else 1
         il2 = [1 / mp.e ** (2 * v) for v in h[:nl]]
-        self.il2 = il2 if kind in pgd.ARD else il2 * D
-        self.s2 = mp.mpf(1) if kind in pgd.LINEAR else mp.e ** (2 * h[nl])
+        self.il2 = il2 if kind in dk.ARD else il2 * D
+        self.s2 = mp.mpf(1) if kind in dk.LINEAR else mp.e ** (2 * h[nl])
         self.nu2 = 3 if kind in (5, 7) else 5
         self.x = [[mp.mpf(float(v)) for v in r] for r in X]
         self.mean = mp.mpf(float(mean))
@@ -118,7 +119,7 @@ class MPGrad:
         kind = self.kind
         if kind == 1:
             return self.s2 * mp.fsum(mp.e ** (-((p - q) ** 2) * il / 2) for p, q, il in zip(a, b, self.il2))
-        if kind in pgd.LINEAR:
+        if kind in dk.LINEAR:
             return mp.fsum(p * q * il for p, q, il in zip(a, b, self.il2))
         r2 = mp.fsum((p - q) ** 2 * il for p, q, il in zip(a, b, self.il2))
         if kind in (0, 4):
@@ -129,7 +130,7 @@ class MPGrad:
     def dk(self, t, xi):
         """[dk(t, xi) / dt_d for d]: the formulas of the issue, literally."""
         kind = self.kind
-        if kind in pgd.LINEAR:
+        if kind in dk.LINEAR:
             return [q * il for q, il in zip(xi, self.il2)]
         if kind == 1:
             return [-self.s2 * mp.e ** (-((p - q) ** 2) * il / 2) * (p - q) * il for p, q, il in zip(t, xi, self.il2)]
@@ -153,7 +154,7 @@ class MPGrad:
         D = len(t)
         beta = self.bwd(self.fwd([self.k(xi, t) for xi in self.x]))
         G = [self.dk(t, xi) for xi in self.x]
-        self_term = [2 * p * il for p, il in zip(t, self.il2)] if self.kind in pgd.LINEAR else [mp.mpf(0)] * D
+        self_term = [2 * p * il for p, il in zip(t, self.il2)] if self.kind in dk.LINEAR else [mp.mpf(0)] * D
         dmu = [mp.fdot(self.alpha, [g[d] for g in G]) for d in range(D)]
         dvar = [self_term[d] - 2 * mp.fdot(beta, [g[d] for g in G]) for d in range(D)]
         return dmu, dvar
@@ -164,7 +165,7 @@ def run_case(spec):
     name, kind, n, nt, D = spec
     X, y, Xt, dup = inputs(n, nt, D)
     Xt = Xt.copy()
-    if kind not in pgd.LINEAR and nt > 4:
+    if kind not in dk.LINEAR and nt > 4:
         Xt[2], Xt[3] = 1e3, -1e3
     loghyp = loghyp_of(kind, D)
     logNoise = float(np.log(0.1))
@@ -232,8 +233,8 @@ def aggregates(flat):
     pk = int(T["prior_kid"])
     phyp = T["hyp"][pk][:T["hyp_len"][pk]]
     pkind = int(T["kinds"][pk])
-    kss = M(pgd.prior_diag(pkind, phyp[:-1], Xt))
-    dkss = [M(r) for r in pgd.prior_dx(pkind, phyp[:-1], Xt)]
+    kss = M(dk.prior_diag(pkind, phyp[:-1], Xt))
+    dkss = [M(r) for r in dk.prior_dx(pkind, phyp[:-1], Xt)]
     pnoise = mp.e ** (2 * mp.mpf(float(phyp[-1])))
     fams = dict(mixture=(0, dict(coef=T["w_mix"])), plain=(0, dict(coef=T["w_mix"], plain=True)), poe=(1, dict(coef=np.ones(41))),
                 gpoe=(2, dict(coef=T["beta"])),

@@ -23,13 +23,13 @@ alpha in {0.3, 2, 50}, D in {1, 3, 8}, the largest leaf at 300 rows.  Imports nu
 PCG64 generator).  Run from the repo root:
     python tests/golden/make_rq_golden.py        (the cases run in parallel processes; a few minutes; byte-reproducible)
 """
-import io
 import os
-import zipfile
 from multiprocessing import Pool
 
 import mpmath as mp
 import numpy as np
+
+from mp_kernels import d_hyper, d_input, iso_logl as _iso, savez_reproducible, spread_logl as _logl, unpack, value
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 mp.mp.dps = 50
@@ -37,44 +37,16 @@ ISO, ARD = 9, 10
 JIT = mp.mpf("1e-8")
 
 
-def _unpack(kind, th, D):
-    """(1 / l_d^2 per dimension, alpha, sigma^2) from th = [logl..., loga, logs, ...]."""
-    nl = D if kind == ARD else 1
-    il2 = [1 / mp.e ** (2 * th[d if kind == ARD else 0]) for d in range(D)]
-    return il2, mp.e ** th[nl], mp.e ** (2 * th[nl + 1])
-
-
-def kval(a, b, il2, al, s2):
-    w = mp.fsum((p - q) ** 2 * il for p, q, il in zip(a, b, il2)) / (2 * al)
-    return s2 * mp.e ** (-al * mp.log(1 + w))
-
-
-def kder(kind, a, b, il2, al, s2):
-    """[dk/dlog l..., dk/dlog alpha, dk/dlog sigma] of one entry."""
-    q = [(p - r) ** 2 * il for p, r, il in zip(a, b, il2)]
-    w = mp.fsum(q) / (2 * al)
-    k = s2 * mp.e ** (-al * mp.log(1 + w))
-    per = [k / (1 + w) * qd for qd in q]
-    return (per if kind == ARD else [mp.fsum(per)]) + [k * al * (w / (1 + w) - mp.log(1 + w)), 2 * k]
-
-
-def kdx(xt, xi, il2, al, s2):
-    """dk(x_t, x_i) / dx_{t,d} for every d."""
-    w = mp.fsum((p - q) ** 2 * il for p, q, il in zip(xt, xi, il2)) / (2 * al)
-    k = s2 * mp.e ** (-al * mp.log(1 + w))
-    return [-k / (1 + w) * (p - q) * il for p, q, il in zip(xt, xi, il2)]
-
-
 def chol(kind, x, th):
     n, D = len(x), len(x[0])
-    il2, al, s2 = _unpack(kind, th, D)
+    par = unpack(kind, th, D)
     c = mp.e ** (2 * th[-1]) + JIT
     L = []
     for i in range(n):
         row = []
         for j in range(i):
-            row.append((kval(x[i], x[j], il2, al, s2) - mp.fdot(row[:j], L[j][:j])) / L[j][j])
-        row.append(mp.sqrt(kval(x[i], x[i], il2, al, s2) + c - mp.fdot(row, row)))
+            row.append((value(kind, x[i], x[j], *par) - mp.fdot(row[:j], L[j][:j])) / L[j][j])
+        row.append(mp.sqrt(value(kind, x[i], x[i], *par) + c - mp.fdot(row, row)))
         L.append(row)
     return L
 
@@ -112,7 +84,8 @@ def mp_case(kind, X, y, mean, th, Xt):
     n, D = X.shape
     x = [[mp.mpf(float(v)) for v in row] for row in X]
     xt = [[mp.mpf(float(v)) for v in row] for row in Xt]
-    il2, al, s2 = _unpack(kind, th, D)
+    par = unpack(kind, th, D)
+    s2 = par[2]
     noise = mp.e ** (2 * th[-1])
     m = mp.mpf(float(mean))
     yc = [mp.mpf(float(v)) - m for v in y]
@@ -146,7 +119,7 @@ def mp_case(kind, X, y, mean, th, Xt):
             if i == j:
                 trW += Wij
                 trM += Mij
-            dk = kder(kind, x[i], x[j], il2, al, s2)
+            dk = d_hyper(kind, x[i], x[j], *par)[1]
             for p in range(nh):
                 gm[p] += f * Wij * dk[p] / 2
                 gl[p] += f * Mij * dk[p]
@@ -155,20 +128,20 @@ def mp_case(kind, X, y, mean, th, Xt):
     # predictive moments and their input gradients
     mu, var, dmu, dvar = [], [], [], []
     for t in range(len(xt)):
-        ks = [kval(x[i], xt[t], il2, al, s2) for i in range(n)]
+        ks = [value(kind, x[i], xt[t], *par) for i in range(n)]
         v = []
         for i in range(n):
             v.append((ks[i] - mp.fdot(L[i][:i], v)) / L[i][i])
         mu.append(m + mp.fdot(ks, alpha))
         var.append(s2 - mp.fdot(v, v) + noise)
         beta = [mp.fdot(G[i], ks) for i in range(n)]
-        dk = [kdx(xt[t], x[i], il2, al, s2) for i in range(n)]
+        dk = [d_input(kind, xt[t], x[i], *par) for i in range(n)]
         dmu.append([mp.fdot(alpha, [dk[i][dd] for i in range(n)]) for dd in range(D)])
         dvar.append([-2 * mp.fdot(beta, [dk[i][dd] for i in range(n)]) for dd in range(D)])
     c = min(n, 8)
-    Kc = np.array([[float(kval(x[i], x[j], il2, al, s2)) for j in range(c)] for i in range(c)])
-    Kt = np.array([[float(kval(x[i], xt[t], il2, al, s2)) for t in range(len(xt))] for i in range(c)])
-    Ky = np.array([[float(kval(x[i], x[j], il2, al, s2)) for j in range(n)] for i in range(n)]) + float(noise + JIT) * np.eye(n)
+    Kc = np.array([[float(value(kind, x[i], x[j], *par)) for j in range(c)] for i in range(c)])
+    Kt = np.array([[float(value(kind, x[i], xt[t], *par)) for t in range(len(xt))] for i in range(c)])
+    Ky = np.array([[float(value(kind, x[i], x[j], *par)) for j in range(n)] for i in range(n)]) + float(noise + JIT) * np.eye(n)
     return dict(x=x, xt=xt, yc=yc, grad=grad, loo_grad=loo_grad, mll=mll, mu=mu, var=var, dmu=dmu, dvar=dvar, loo_mu=loo_mu,
                 loo_var=loo_var, lpd=lpd, Kc=Kc, Kt=Kt, Ky=Ky)
 
@@ -176,20 +149,21 @@ def mp_case(kind, X, y, mean, th, Xt):
 def _small(kind, x, yc, m, th, xt=None):
     """n = 1 and n = 2 by hand (2 x 2 inverse written out): (mll, lpd sum), or (mu, var) at the test point xt."""
     D = len(x[0])
-    il2, al, s2 = _unpack(kind, th, D)
+    par = unpack(kind, th, D)
+    s2 = par[2]
     noise = mp.e ** (2 * th[-1])
     a = s2 + noise + JIT
     log2pi = mp.log(2 * mp.pi)
     if len(x) == 1:
         if xt is not None:
-            k0 = kval(x[0], xt, il2, al, s2)
+            k0 = value(kind, x[0], xt, *par)
             return m + k0 * yc[0] / a, s2 - k0 * k0 / a + noise
         v = -(yc[0] ** 2 / a + mp.log(a) + log2pi) / 2
         return v, v                                               # one point: the LOO density is the prior's
-    b = kval(x[0], x[1], il2, al, s2)
+    b = value(kind, x[0], x[1], *par)
     det = a * a - b * b
     if xt is not None:
-        k0, k1 = kval(x[0], xt, il2, al, s2), kval(x[1], xt, il2, al, s2)
+        k0, k1 = value(kind, x[0], xt, *par), value(kind, x[1], xt, *par)
         mu = m + (k0 * (a * yc[0] - b * yc[1]) + k1 * (a * yc[1] - b * yc[0])) / det
         return mu, s2 - (a * k0 * k0 - 2 * b * k0 * k1 + a * k1 * k1) / det + noise
     mll = -((a * yc[0] ** 2 - 2 * b * yc[0] * yc[1] + a * yc[1] ** 2) / det + mp.log(det) + 2 * log2pi) / 2
@@ -243,14 +217,6 @@ def self_check(name, kind, r, m, th):
             _close(r["loo_grad"][j], (fp[1] - fm[1]) / (2 * step), "1e-24", f"{name} loo_grad[{j}] vs differences")
 
 
-def _logl(D, lo=0.7, hi=1.4):
-    return np.log(0.35 * np.sqrt(D) * np.linspace(lo, hi, D)) if D > 1 else np.log([0.35])
-
-
-def _iso(D):
-    return np.log([0.35 * np.sqrt(D)])
-
-
 # name, kind, n, D, logl, alpha, logs, logNoise, target offset (then the leaf's mean stays 0), duplicated rows
 SPECS = [
     ("n1_iso_d3", ISO, 1, 3, _iso(3), 2.0, 0.1, np.log(0.2), 0.0, 0),
@@ -270,18 +236,6 @@ SPECS = [
     ("dup_ard_d3", ARD, 140, 3, _logl(3), 0.3, 0.0, np.log(0.3), 0.0, 24),
     ("offset_iso_d3", ISO, 128, 3, _iso(3), 2.0, 0.5, np.log(0.2), 3.0, 0),
 ]
-
-
-def savez_reproducible(path, arrays):
-    """np.savez_compressed with fixed member timestamps, so that a rerun writes the same bytes."""
-    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
-        for key in sorted(arrays):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.asarray(arrays[key]), allow_pickle=False)
-            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            info.external_attr = 0o600 << 16
-            z.writestr(info, buf.getvalue())
 
 
 def run_case(args):

@@ -33,50 +33,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, HERE)
 
 from make_pred_golden import uniform, normal  # noqa: E402
-from make_predcov_golden import savez_reproducible  # noqa: E402
+import mp_kernels as mpk  # noqa: E402
 import targets_grad_dense as tgd  # noqa: E402
 
 mp.mp.dps = 50
 JIT = mp.mpf("1e-8")
-ARD, RQ = tgd.ARD_KINDS, tgd.RQ_KINDS
-
-
-def entry(kind, h, a, b):
-    """(k, [dk / dtheta per slot before logNoise, library convention; ArdSE: the true length-scale derivatives]) of one pair."""
-    D = len(a)
-    ard = kind in ARD
-    nl = D if ard else 1
-    il2 = [1 / mp.e ** (2 * h[d if ard else 0]) for d in range(D)]
-    if kind in (2, 3):
-        k = mp.fsum(p * q * il for p, q, il in zip(a, b, il2))
-        if kind == 2:
-            return k, [-2 * k, mp.mpf(0)]
-        return k, [-2 * a[d] * b[d] * il2[d] for d in range(D)] + [mp.mpf(0)]
-    q = [(p - r) ** 2 * il for p, r, il in zip(a, b, il2)]
-    if kind in RQ:
-        al, s2 = mp.e ** h[nl], mp.e ** (2 * h[nl + 1])
-        w = mp.fsum(q) / (2 * al)
-        k = s2 * mp.e ** (-al * mp.log(1 + w))
-        per = [k / (1 + w) * qd for qd in q]
-        return k, (per if ard else [mp.fsum(per)]) + [k * al * (w / (1 + w) - mp.log(1 + w)), 2 * k]
-    s2, sigma = mp.e ** (2 * h[nl]), mp.e ** h[nl]
-    if kind == 1:
-        e = [s2 * mp.e ** (-qd / 2) for qd in q]
-        k = mp.fsum(e)
-        return k, [ed * qd for ed, qd in zip(e, q)] + [sigma * 2 * k]
-    r2 = mp.fsum(q)
-    if kind == 0:
-        k = s2 * mp.e ** (-r2 / 2)
-        return k, [sigma * k * r2, sigma * 2 * k]
-    if kind == 4:
-        k = s2 * mp.e ** (-r2 / 2)
-        return k, [k * qd for qd in q] + [2 * k]
-    nu2 = 3 if kind in (5, 7) else 5
-    s = mp.sqrt(nu2 * r2)
-    k = s2 * mp.e ** (-s) * (1 + s + (s * s / 3 if nu2 == 5 else 0))
-    c = 1 if nu2 == 3 else (1 + s) / 3
-    per = [s2 * mp.e ** (-s) * c * nu2 * qd for qd in q]
-    return k, (per if ard else [mp.fsum(per)]) + [2 * k]
 
 
 def mp_case(kind, hyp, X, Y, mean):
@@ -88,12 +49,14 @@ def mp_case(kind, hyp, X, Y, mean):
     noise = mp.e ** (2 * mp.mpf(float(hyp[-1])))
     c = noise + JIT
     nt = len(hyp) - 1
+    par = mpk.unpack(kind, h, D)
     K = []
     dK = [[] for _ in range(nt)]
     for i in range(n):
         row, drow = [], [[] for _ in range(nt)]
         for j in range(i + 1):
-            k, dk = entry(kind, h, x[i], x[j])
+            k, dk = mpk.d_hyper(kind, x[i], x[j], *par)
+            dk = mpk.mll_convention(kind, h, dk)
             row.append(k)
             for t in range(nt):
                 drow[t].append(dk[t])
@@ -228,7 +191,7 @@ def main():
         for k, v in rec.items():
             flat[f"{name}/{k}"] = np.asarray(v)
     out = os.path.join(HERE, "gp_targets_grad.npz")
-    savez_reproducible(out, flat)
+    mpk.savez_reproducible(out, flat, compresslevel=9)
     print(f"{out}: {os.path.getsize(out)} bytes")
 
 

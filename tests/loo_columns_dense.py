@@ -11,33 +11,28 @@ With K_y = K + (exp(2 logNoise) + 1e-8) I, G = K_y^-1, d = diag G and a_q = G (y
                                  W_i = (sum_q c_q + sum_q c_q a_iq^2 / d_i) / (2 d_i)
 
 Every gradient component is the TRUE derivative for all eleven kinds of include/dsmgp_hip.h, as dsmgp_loo_gradients defines
-them (`true_derivatives`: no factor sigma anywhere; the dummy variance slot of the linear kinds is zero).  `hyp` is the library
+them (dense_kernels.d_hyper: no factor sigma anywhere; the dummy variance slot of the linear kinds is zero).  `hyp` is the library
 hyper-vector INCLUDING logNoise; gradients come back as [dl..., (da,) ds, dnoise].
 
 Tolerances, the project's own rules and no new constants: the moments of column q get loo_dense.loo_tol of that column; the
 weighted gradient gets loo_grad_dense.tolerance per column carried through the weighted sum, sum_q c_q tol_q, as
 targets_grad_dense.tolerance does, including the weak-signal IsoLinear floor.  Against the 50-digit fixture they are used as
 they are; where both sides are float64 the tests double them."""
-import os
-
 import numpy as np
 import scipy.linalg as sla
 
+import dense_gp
+import dense_kernels as dk
 import loo_dense as ld
 import loo_grad_dense as lgd
 import targets_grad_dense as tgd
 
 EPS = np.finfo(np.float64).eps
-JITTER = ld.JITTER
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+JITTER = dk.JITTER
 
 
 def load_cases():
-    z = np.load(os.path.join(GOLDEN, "gp_loo_columns.npz"))
-    cases = {}
-    for key in z.files:
-        name, field = key.split("/", 1)
-        cases.setdefault(name, {})[field] = z[key]
+    cases = dk.load_cases("gp_loo_columns.npz")
     for c in cases.values():
         for f in ("kind", "n"):
             c[f] = int(c[f])
@@ -46,28 +41,16 @@ def load_cases():
     return cases
 
 
-def true_derivatives(kind, h, X):
-    """(K, [dK / dtheta over the slots before logNoise]), every slot the true derivative; `h` without the noise."""
-    K, dK = tgd.kernel_and_derivatives(kind, h, X)
-    nl = np.asarray(X).shape[1] if kind in tgd.ARD_KINDS else 1
-    if kind == 0:
-        sigma = np.exp(h[1])
-        dK = [dK[0] / sigma, 2.0 * K]
-    elif kind == 1:
-        dK = dK[:nl] + [2.0 * K]
-    return K, dK
-
-
 def _parts(kind, hyp, X, Y, mean):
+    """K, dK_y/dtheta over all of hyp, noise, G = K_y^-1 formed explicitly, d, A = G (Y - mean), Y."""
     hyp = np.asarray(hyp, dtype=np.float64)
     Y = np.asarray(Y, dtype=np.float64)
     Y = Y[:, None] if Y.ndim == 1 else Y
     n = Y.shape[0]
     mean = np.broadcast_to(np.asarray(mean, dtype=np.float64), (Y.shape[1],))
-    K, dK = true_derivatives(kind, hyp[:-1], X)
+    K, dK = dk.d_hyper(kind, hyp[:-1], X)
     noise = float(np.exp(2.0 * hyp[-1]))
-    Ky = K + (noise + JITTER) * np.eye(n)
-    G = sla.cho_solve(sla.cho_factor(Ky, lower=True), np.eye(n))
+    G = sla.cho_solve((dense_gp.factor(K, noise), True), np.eye(n))
     G = 0.5 * (G + G.T)
     return K, dK + [2.0 * noise * np.eye(n)], noise, G, np.diag(G).copy(), G @ (Y - mean[None, :]), Y
 
@@ -123,7 +106,7 @@ def moment_tolerances(case, q):
 def gradient_tolerance(case, Gc, c, K=None):
     """sum_q c_q loo_grad_dense.tolerance(column q): `Gc` the per-column reference gradients, `c` the weights."""
     if K is None:
-        K = true_derivatives(case["kind"], case["hyp"][:-1], case["X"])[0]
+        K = dk.d_hyper(case["kind"], case["hyp"][:-1], case["X"])[0]
     tol = np.zeros(Gc.shape[1])
     for q in range(Gc.shape[0]):
         col = dict(kind=case["kind"], cond=case["cond"], weak=case["weak"], logNoise=float(case["hyp"][-1]), y=case["Y"][:, q],

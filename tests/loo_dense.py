@@ -8,58 +8,30 @@ alpha = K_y^-1 (y - m), the mean m and the hyper-parameters held fixed:
     var_loo_i = 1 / d_i
     lpd_i     = -(log 2pi + log var_loo_i + (y_i - mu_loo_i)^2 / var_loo_i) / 2
 
-`loo_from_factor` evaluates exactly that from a Cholesky factor (scipy), `loo_brute` is the definition: refit without row i
+`loo_from_factor` evaluates exactly that from a Cholesky factor (dense_gp.factor, or a device's), `loo_brute` is the definition: refit without row i
 (same mean, same hyper-parameters, same jitter) and predict at x_i.  var_loo_i is that fit's k(x_i, x_i) - |v|^2 + noise plus
 the 1e-8 jitter; mu_loo_i is its mean.
 
 Tolerances (`loo_tol`): LOO moments are predictive moments, so pred_tolerance.moment_tol applies as it stands --
 RTOL |mu| + ATOL max(1, max|y|) and RTOL |var| + ATOL max(1, k(x_i, x_i) + noise); lpd_i gets both carried through its formula
 (pred_tolerance.Prop), the leaf sum their sum plus (8 + n / 256) eps times the mean |lpd_i| for the rounding of the sum itself."""
-import os
-
 import numpy as np
 import scipy.linalg as sla
 
+import dense_gp
+import dense_kernels as dk
+from dense_kernels import JITTER  # noqa: F401  (the tests read it from here)
 from pred_tolerance import EPS, LOG2PI, Prop, moment_tol
-
-JITTER = 1e-8
 
 
 def load_cases():
     """The cases of tests/golden/gp_loo.npz by name: X, y, loghyp, the 50-digit mu / var / lpd (per row) and kss, and the
     scalars of `meta` (kind, mean, logNoise, cond_2(K_y), the 50-digit sum of lpd)."""
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gp_loo.npz"))
-    cases = {}
-    for key in z.files:
-        name, field = key.split("/")
-        cases.setdefault(name, {})[field] = z[key]
+    cases = dk.load_cases("gp_loo.npz")
     for c in cases.values():
         m = c.pop("meta")
         c.update(kind=int(m[0]), mean=float(m[1]), logNoise=float(m[2]), cond=float(m[3]), lpd_sum=float(m[4]))
     return cases
-
-
-def kernel_matrix(kind, loghyp, x1, x2):
-    """k(x1, x2) of the kinds of include/dsmgp_hip.h (0-8) in float64; loghyp = the library hyper-vector without the noise."""
-    x1 = np.asarray(x1, dtype=np.float64)
-    x2 = np.asarray(x2, dtype=np.float64)
-    h = np.asarray(loghyp, dtype=np.float64)
-    D = x1.shape[1]
-    ard = kind in (1, 3, 4, 7, 8)
-    nl = D if ard else 1
-    il2 = np.broadcast_to(np.exp(-2.0 * h[:nl]), (D,))
-    s2 = 1.0 if kind in (2, 3) else np.exp(2.0 * h[nl])
-    if kind in (2, 3):
-        return (x1 * il2) @ x2.T
-    diff2 = (x1[:, None, :] - x2[None, :, :]) ** 2 * il2
-    if kind == 1:
-        return s2 * np.sum(np.exp(-0.5 * diff2), axis=2)
-    r2 = np.sum(diff2, axis=2)
-    if kind in (0, 4):
-        return s2 * np.exp(-0.5 * r2)
-    nu2 = 3.0 if kind in (5, 7) else 5.0
-    s = np.sqrt(nu2 * r2)
-    return s2 * np.exp(-s) * (1.0 + s + (s * s / 3.0 if nu2 == 5.0 else 0.0))
 
 
 def lpd_terms(y, mu, var):
@@ -84,8 +56,7 @@ def loo_from_factor(Lf, y, mean):
 
 def loo_dense(K, noise, y, mean):
     """The same from the kernel matrix K (without noise) and noise = exp(2 logNoise)."""
-    Ky = np.asarray(K, dtype=np.float64) + (noise + JITTER) * np.eye(len(y))
-    return loo_from_factor(sla.cholesky(Ky, lower=True), y, mean)
+    return loo_from_factor(dense_gp.factor(K, noise), y, mean)
 
 
 def loo_brute(K, noise, y, mean):
@@ -101,7 +72,7 @@ def loo_brute(K, noise, y, mean):
         if n == 1:
             mu[i], var[i] = mean, K[i, i] + noise
             continue
-        cf = sla.cho_factor(K[np.ix_(keep, keep)] + (noise + JITTER) * np.eye(n - 1), lower=True)
+        cf = (dense_gp.factor(K[np.ix_(keep, keep)], noise), True)
         ki = K[keep, i]
         mu[i] = mean + ki @ sla.cho_solve(cf, y[keep] - mean)
         var[i] = K[i, i] - ki @ sla.cho_solve(cf, ki) + noise

@@ -8,9 +8,8 @@ lpd = sum_i -(log 2pi - log d_i + alpha_i^2 / d_i) / 2 (loo_dense.loo_dense, sum
     M form:          dlpd/dtheta = sum_rc M_rc (dK_y/dtheta)_rc,   M = (u alpha' + alpha u') / 2 - G diag(w) G,
                      u = G (alpha / d),   w_i = (1 + alpha_i^2 / d_i) / (2 d_i)
 
-`kernel_derivatives` gives dK/dtheta_j for every entry of the library hyper-vector without the noise ([logl..., logs]; the
-dummy variance slot of the linear kinds: zeros), `loo_grad_dense` the M form, `loo_grad_literal` the literal one; both return
-the vector [dl..., ds, dnoise] of dsmgp_loo_gradients.
+`dKs` are the true derivatives dK/dtheta_j of dense_kernels.d_hyper; `loo_grad_dense` is the M form, `loo_grad_literal` the
+literal one, both from G formed explicitly; both return the vector [dl..., (da,) ds, dnoise] of dsmgp_loo_gradients.
 
 Tolerance (`tolerance`): the project's gradient rule as tests/test_gradients_gpu.py::_tolerance states it, per component
 max(1e-13, 64 cond_2(K_y) eps max(1, |g_ref|_inf)).  dsmgp_loo_gradients contracts the signal variance and the SE / Matern
@@ -18,12 +17,11 @@ length-scales with M directly; only IsoLinear's dl = -2 (tr(M K_y) - c tr M) goe
 cancel when the signal is weak against c.  For a weak-signal IsoLinear case that component also gets the floor of the same
 construction as there: 8 eps x the size of the cancelling halves,
 sum alpha_i^2/d_i + sum w_i d_i + c (|u . alpha| + |H|_F^2), H = G diag(sqrt w)."""
-import os
-
 import numpy as np
 import scipy.linalg as sla
 
-from loo_dense import JITTER, kernel_matrix  # noqa: F401  (kernel_matrix: re-exported for the tests)
+import dense_gp
+from dense_kernels import JITTER, load_cases as _load
 
 EPS = np.finfo(np.float64).eps
 
@@ -31,52 +29,16 @@ EPS = np.finfo(np.float64).eps
 def load_cases():
     """The cases of tests/golden/gp_loo_grad.npz by name: X, y, loghyp (without the noise), grad (50 digits, [dl..., ds,
     dnoise]) and the scalars of `meta`: kind, mean, logNoise, cond_2(K_y), lpd (50 digits), weak (1: sigma^2 / c = 1e-8)."""
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gp_loo_grad.npz"))
-    cases = {}
-    for key in z.files:
-        name, field = key.split("/")
-        cases.setdefault(name, {})[field] = z[key]
+    cases = _load("gp_loo_grad.npz")
     for c in cases.values():
         m = c.pop("meta")
         c.update(kind=int(m[0]), mean=float(m[1]), logNoise=float(m[2]), cond=float(m[3]), lpd=float(m[4]), weak=bool(m[5]))
     return cases
 
 
-def kernel_derivatives(kind, loghyp, X):
-    """[dK/dtheta_j] over the hyper-vector without the noise, kinds 0-8 of include/dsmgp_hip.h, float64."""
-    X = np.asarray(X, dtype=np.float64)
-    h = np.asarray(loghyp, dtype=np.float64)
-    n, D = X.shape
-    ard = kind in (1, 3, 4, 7, 8)
-    nl = D if ard else 1
-    il2 = np.broadcast_to(np.exp(-2.0 * h[:nl]), (D,))
-    if kind in (2, 3):
-        per_dim = [-2.0 * il2[d] * np.outer(X[:, d], X[:, d]) for d in range(D)]
-        dl = per_dim if ard else [sum(per_dim)]
-        return dl + [np.zeros((n, n))]
-    s2 = np.exp(2.0 * h[nl])
-    q = (X[:, None, :] - X[None, :, :]) ** 2 * il2        # u_d^2 / l_d^2
-    if kind == 1:
-        e = s2 * np.exp(-0.5 * q)
-        return [e[:, :, d] * q[:, :, d] for d in range(D)] + [2.0 * np.sum(e, axis=2)]
-    r2 = np.sum(q, axis=2)
-    if kind in (0, 4):
-        K = s2 * np.exp(-0.5 * r2)
-        per_dim = [K * q[:, :, d] for d in range(D)]
-    else:
-        nu2 = 3.0 if kind in (5, 7) else 5.0
-        s = np.sqrt(nu2 * r2)
-        K = s2 * np.exp(-s) * (1.0 + s + (s * s / 3.0 if nu2 == 5.0 else 0.0))
-        cs = 1.0 if nu2 == 3.0 else (1.0 + s) / 3.0      # dK/dlog l_d = sigma^2 exp(-s) c(s) nu2 u_d^2 / l_d^2
-        per_dim = [s2 * np.exp(-s) * cs * nu2 * q[:, :, d] for d in range(D)]
-    dl = per_dim if ard else [sum(per_dim)]
-    return dl + [2.0 * K]
-
-
 def _parts(K, noise, y, mean):
-    n = len(y)
-    Ky = np.asarray(K, dtype=np.float64) + (noise + JITTER) * np.eye(n)
-    G = sla.cho_solve(sla.cho_factor(Ky, lower=True), np.eye(n))
+    """(G, d, alpha) with G = K_y^-1 formed explicitly."""
+    G = sla.cho_solve((dense_gp.factor(K, noise), True), np.eye(len(y)))
     G = 0.5 * (G + G.T)
     alpha = G @ (np.asarray(y, dtype=np.float64) - mean)
     return G, np.diag(G).copy(), alpha

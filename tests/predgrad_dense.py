@@ -4,106 +4,20 @@ For one leaf with training inputs X, K_y = K + (noise + 1e-8) I (the matrix the 
 per test row t, k_t = k(X, x_t), beta_t = K_y^-1 k_t:
     mu = m + k_t . alpha                      dmu[t, d]  = sum_i alpha_i dk(x_t, x_i) / dx_{t,d}
     var = k(x_t, x_t) - k_t . beta_t + noise  dvar[t, d] = dk(x_t, x_t) / dx_{t,d} - 2 sum_i beta_{t,i} dk(x_t, x_i) / dx_{t,d}
-with the kernel derivatives of include/dsmgp_hip.h (dsmgp_predict_gradients), every kind 0-8.  `loghyp` is the library's
-hyper-vector without the noise: [logl..., logs] (the variance slot of the linear kinds is a dummy)."""
+with the kernel derivatives of dense_kernels.d_input, every kind.  `loghyp` is the library hyper-vector without the noise:
+[logl..., (loga,) logs] (the variance slot of the linear kinds is a dummy)."""
 import numpy as np
-import scipy.linalg as sla
 
+from dense_gp import DenseGP
+from dense_kernels import LINEAR, grad_scale, prior_diag
 from pred_tolerance import RTOL, ATOL
-
-ARD = (1, 3, 4, 7, 8)
-LINEAR = (2, 3)
-JITTER = 1e-8
-
-
-def _params(kind, loghyp, D):
-    loghyp = np.asarray(loghyp, dtype=np.float64)
-    nl = D if kind in ARD else 1
-    il2 = np.exp(-2.0 * loghyp[:nl]) * np.ones(D)
-    s2 = 1.0 if kind in LINEAR else float(np.exp(2.0 * loghyp[nl]))
-    return il2, s2
-
-
-def kernelmatrix(kind, loghyp, A, B):
-    """k(a_r, b_c), (len(A), len(B))."""
-    A, B = np.atleast_2d(A), np.atleast_2d(B)
-    il2, s2 = _params(kind, loghyp, A.shape[1])
-    if kind in LINEAR:
-        return (A * il2) @ B.T
-    d = A[:, None, :] - B[None, :, :]
-    if kind == 1:
-        return s2 * np.sum(np.exp(-0.5 * d * d * il2), axis=2)
-    r2 = np.sum(d * d * il2, axis=2)
-    if kind in (0, 4):
-        return s2 * np.exp(-0.5 * r2)
-    nu2 = 3.0 if kind in (5, 7) else 5.0
-    s = np.sqrt(nu2 * r2)
-    return s2 * np.exp(-s) * (1.0 + s + (s * s / 3.0 if nu2 == 5.0 else 0.0))
-
-
-def kernel_dx(kind, loghyp, Xt, X):
-    """G[t, i, d] = dk(x_t, x_i) / dx_{t,d}: true derivatives, finite at x_t = x_i."""
-    Xt, X = np.atleast_2d(Xt), np.atleast_2d(X)
-    il2, s2 = _params(kind, loghyp, X.shape[1])
-    if kind in LINEAR:
-        return np.broadcast_to((X * il2)[None, :, :], (Xt.shape[0],) + X.shape).copy()
-    d = Xt[:, None, :] - X[None, :, :]
-    if kind == 1:
-        return -s2 * np.exp(-0.5 * d * d * il2) * d * il2
-    r2 = np.sum(d * d * il2, axis=2)
-    if kind in (0, 4):
-        return -(s2 * np.exp(-0.5 * r2))[:, :, None] * d * il2
-    nu2 = 3.0 if kind in (5, 7) else 5.0
-    s = np.sqrt(nu2 * r2)
-    c = 1.0 if nu2 == 3.0 else (1.0 + s) / 3.0
-    return -(s2 * np.exp(-s) * c)[:, :, None] * (nu2 * il2) * d
-
-
-def prior_dx(kind, loghyp, Xt):
-    """dk(x, x) / dx_d at the rows of Xt: 2 x_d / l_d^2 for the linear kinds, 0 for the stationary ones."""
-    Xt = np.atleast_2d(Xt)
-    il2, _ = _params(kind, loghyp, Xt.shape[1])
-    return 2.0 * Xt * il2 if kind in LINEAR else np.zeros(Xt.shape)
-
-
-def prior_diag(kind, loghyp, Xt):
-    Xt = np.atleast_2d(Xt)
-    il2, s2 = _params(kind, loghyp, Xt.shape[1])
-    if kind in LINEAR:
-        return (Xt * Xt) @ il2
-    return np.full(Xt.shape[0], s2 * (Xt.shape[1] if kind == 1 else 1.0))
 
 
 def moments(kind, loghyp, logNoise, X, y, mean, Xt, L=None, alpha=None):
     """(mu, var, dmu, dvar) of one leaf in dense float64.  `L` (lower factor of K_y) and `alpha` may be given (the device's own,
-    `Context.download_factor`); else they come from scipy's Cholesky of K + (noise + 1e-8) I."""
-    X, Xt = np.atleast_2d(X), np.atleast_2d(Xt)
-    noise = float(np.exp(2.0 * logNoise))
-    if L is None:
-        Ky = kernelmatrix(kind, loghyp, X, X) + (noise + JITTER) * np.eye(X.shape[0])
-        L = np.linalg.cholesky(Ky)
-    if alpha is None:
-        alpha = sla.cho_solve((L, True), np.asarray(y, dtype=np.float64) - mean)
-    Ktn = kernelmatrix(kind, loghyp, Xt, X)
-    V = sla.solve_triangular(L, Ktn.T, lower=True)                  # n x nt
-    beta = sla.solve_triangular(L, V, lower=True, trans="T").T      # nt x n
-    G = kernel_dx(kind, loghyp, Xt, X)
-    mu = mean + Ktn @ alpha
-    var = prior_diag(kind, loghyp, Xt) - np.sum(V * V, axis=0) + noise
-    dmu = np.einsum("i,tid->td", alpha, G)
-    dvar = prior_dx(kind, loghyp, Xt) - 2.0 * np.einsum("ti,tid->td", beta, G)
-    return mu, var, dmu, dvar
-
-
-def grad_scale(kind, loghyp, X, Xt):
-    """g_d per (test row, dimension): the size of d/dx_d relative to the kernel's own scale -- 1 / l_d for the stationary kinds,
-    max(1, max_i |x_{i,d}|, |x_{t,d}|) / l_d^2 relative to max(1, k**) for the linear ones."""
-    X, Xt = np.atleast_2d(X), np.atleast_2d(Xt)
-    il2, _ = _params(kind, loghyp, X.shape[1])
-    if kind not in LINEAR:
-        return np.broadcast_to(np.sqrt(il2)[None, :], Xt.shape)
-    big = np.maximum(np.maximum(1.0, np.max(np.abs(X), axis=0))[None, :], np.abs(Xt))
-    return big * il2[None, :] / np.maximum(1.0, prior_diag(kind, loghyp, Xt))[:, None]
+    `Context.download_factor`); else they are DenseGP's."""
+    g = DenseGP(kind, np.append(loghyp, logNoise), np.atleast_2d(X), y, mean, F=L, alpha=alpha)
+    return g.prediction(Xt) + g.input_gradients(Xt)
 
 
 def tolerances(kind, loghyp, logNoise, X, y, Xt, dmu, dvar):

@@ -39,9 +39,8 @@ import os
 import numpy as np
 
 from oracle import gp as ogp
-import ard_linear_dense
-import matern_dense
-import rq_dense
+import dense_kernels as dk
+from dense_gp import DenseGP
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _spec = importlib.util.spec_from_file_location("_sharing_datagen", os.path.join(_ROOT, "deepstructuredmixtures_amd", "datagen.py"))
@@ -101,26 +100,16 @@ def hyper(kid, D):
 
 
 def oracle_leaf(kind, hyp, X, y, mean):
-    """The float64 oracle of one leaf: oracle.gp for IsoSE, the dense restatements of tests/ for the kinds oracle/ lacks.
+    """The float64 oracle of one leaf: oracle.gp for IsoSE, tests/dense_gp.py for the kinds oracle/ lacks.
     hyp = the library hyper-vector with logNoise.  All answer info, mll(), prediction(Xt) and L()."""
-    D = X.shape[1]
     if kind == 0:
         return ogp.GaussianProcess(X, y, mean, ogp.make_kernel(0, hyp[:-1]), hyp[-1], exact_dist=True).update_cholesky()
-    if kind == 3:
-        return ard_linear_dense.DenseGP(X, y, mean, hyp[:D], hyp[-1])
-    if kind == 8:
-        return matern_dense.DenseGP(X, y, mean, kind, hyp[:D], hyp[D], hyp[-1])
-    assert kind == 10, kind
-    return rq_dense.DenseGP(X, y, mean, kind, hyp[:D], hyp[D], hyp[D + 1], hyp[-1])
+    return DenseGP(kind, hyp, X, y, mean)
 
 
 def prior_diag(kind, hyp, Xt):
     """k(x*, x*) per row."""
-    D = Xt.shape[1]
-    if kind == 3:
-        return ard_linear_dense.prior_diag(hyp[:D], Xt)
-    logs = hyp[{0: 1, 8: D, 10: D + 1}[kind]]
-    return np.full(Xt.shape[0], np.exp(2.0 * logs))
+    return dk.prior_diag(kind, hyp[:-1], Xt)
 
 
 class Data:

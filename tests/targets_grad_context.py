@@ -1,41 +1,14 @@
 """TargetsOracleContext (tests/targets_context.py) that also answers targets_gradients, and fits every kernel kind: kinds the
-CPU oracle does not have (ArdLinear, ArdSEProduct, Matern, rational quadratic) get a float64 dense leaf from
-tests/targets_grad_dense.py.  targets_gradients is that module's textbook contraction per (leaf, column), weighted and added in
+CPU oracle does not have (ArdLinear, ArdSEProduct, Matern, rational quadratic) get a float64 dense leaf
+(tests/dense_gp.py).  targets_gradients is targets_grad_dense's textbook contraction per (leaf, column), weighted and added in
 ascending column order.  Lets the CPU suite drive model.targets_objective / model.grad_targets / model.train(targets=...) end to
 end without a GPU.  Also holds `default_path_results`, the values of the untouched default paths (train, grad_mll, grad_loo)
 that tests/golden/targets_grad_parent.json records from the parent commit.  Test infrastructure only."""
 import numpy as np
-import scipy.linalg as sla
 
 import targets_grad_dense as tgd
+from dense_gp import DenseGP
 from targets_context import TargetsOracleContext
-
-LOG2PI = float(np.log(2.0 * np.pi))
-
-
-class DenseLeaf:
-    """What OracleContext / TargetsOracleContext read of a leaf: L(), mll(), info, grad()."""
-
-    def __init__(self, kind, hyp, X, y, mean):
-        self.kind, self.hyp, self.x, self.y, self.mean = kind, np.asarray(hyp, dtype=np.float64), X, y, float(mean)
-        K, _ = tgd.kernel_and_derivatives(kind, self.hyp[:-1], X)
-        self.info = 0
-        try:
-            self.F = sla.cholesky(K + (np.exp(2.0 * self.hyp[-1]) + 1e-8) * np.eye(X.shape[0]), lower=True)
-        except (sla.LinAlgError, ValueError):
-            self.F, self.info = np.eye(X.shape[0]), 1
-
-    def L(self):
-        return self.F
-
-    def mll(self):
-        if self.info:
-            return float("nan")
-        z = sla.solve_triangular(self.F, self.y - self.mean, lower=True)
-        return float(-(z @ z + 2.0 * np.sum(np.log(np.diag(self.F))) + LOG2PI * self.x.shape[0]) / 2.0)
-
-    def grad(self):
-        return tgd.column_gradients(self.kind, self.hyp, self.x, self.y[:, None], [self.mean])[0][0]
 
 
 class TargetsGradOracleContext(TargetsOracleContext):
@@ -44,7 +17,7 @@ class TargetsGradOracleContext(TargetsOracleContext):
         if all(self.hyper[k][0] <= 2 for k in self.kid):
             mll, info, sec = super().fit()
         else:
-            self.gps = [DenseLeaf(*self.hyper[self.kid[i]], self.X[self.obs[i]], self.y[self.obs[i]], self.mean[i])
+            self.gps = [DenseGP(*self.hyper[self.kid[i]], self.X[self.obs[i]], self.y[self.obs[i]], self.mean[i])
                         for i in range(self.L)]
             mll = np.array([g.mll() for g in self.gps])
             info = np.array([g.info for g in self.gps], dtype=np.int32)

@@ -1,5 +1,5 @@
 """GPU suite for the ArdLinear kernel (DSMGP_KIND_ARD_LINEAR): Gram tiles of every path, single leaves, gradients by the new
-quadratic-form kernel, and whole models -- against the dense restatement of tests/ard_linear_dense.py and through the
+quadratic-form kernel, and whole models -- against the dense restatement of tests/dense_gp.py and through the
 oracle-checked IsoLinear path (equal length-scales, rescaled inputs)."""
 import itertools
 
@@ -10,7 +10,8 @@ import deepstructuredmixtures_amd as dsm
 from deepstructuredmixtures_amd import hipabi, tree as ptree
 from deepstructuredmixtures_amd.datagen import uniform, normal, regression_data
 from oracle import spn as ospn
-from ard_linear_dense import DenseGP, kernelmatrix as dense_K
+import dense_kernels as dk
+from dense_gp import DenseGP
 
 pytestmark = pytest.mark.gpu
 
@@ -56,7 +57,7 @@ def test_kernel_matrix_against_the_dense_formula(ctx, D):
     K = ctx.kernel_matrix(0, x1, x2)
     s = 1.0 / np.exp(ll) ** 2
     scale = np.abs(x1) @ np.diag(s) @ np.abs(x2).T              # sum_d |a_d b_d| / l_d^2 per entry
-    assert np.all(np.abs(K - dense_K(ll, x1, x2)) <= 1e-14 * scale)
+    assert np.all(np.abs(K - dk.value(3, dk.pack(3, ll), x1, x2)) <= 1e-14 * scale)
     Ks = ctx.kernel_matrix(0, x1, x1)
     assert np.array_equal(Ks, Ks.T)                            # bit-symmetric
 
@@ -65,7 +66,7 @@ def test_kernel_matrix_against_the_dense_formula(ctx, D):
 def test_single_leaf_against_the_dense_restatement_under_every_schedule(ctx, n, D):
     X, y, Xt = _data(700 + n, n, D)
     ll, ln, mean = _logl(D), np.log(0.2), float(np.mean(y))
-    g = DenseGP(X, y, mean, ll, ln)
+    g = DenseGP(3, dk.pack(3, ll, logNoise=ln), X, y, mean)
     assert g.info == 0
     ref = None
     try:
@@ -105,7 +106,7 @@ def test_equal_lengthscales_are_iso_linear_and_scaled_inputs_are_unit_lengthscal
     gi = ctx.gradients(3)[0]
     assert abs(ma - mi) <= 1e-11 * abs(mi)
     assert np.allclose(mua, mui, rtol=1e-11, atol=0) and np.allclose(vara, vari, rtol=1e-11, atol=0)
-    A, Q = DenseGP(X, y, mean, np.full(D, l0), ln).quad_terms()
+    A, Q = DenseGP(3, dk.pack(3, np.full(D, l0), logNoise=ln), X, y, mean).quad_terms()
     scale = max(abs(gi[0]), np.sum(A + Q) / np.exp(2 * l0))      # magnitude of the terms whose difference dl is
     assert abs(np.sum(ga[:D]) - gi[0]) <= 1e-11 * scale, (np.sum(ga[:D]), gi[0])
     assert ga[D] == 0.0 and abs(ga[D + 1] - gi[2]) <= 1e-11 * abs(gi[2])
@@ -127,7 +128,7 @@ def test_gradients_closed_form_finite_differences_and_the_ardse_option(ctx, n, D
     h = np.append(ll, 0.0)
     _single(ctx, X, y, mean, KIND, h, ln)
     g = ctx.gradients(D + 2)[0]
-    go = DenseGP(X, y, mean, ll, ln).grad()
+    go = DenseGP(3, dk.pack(3, ll, logNoise=ln), X, y, mean).grad()
     assert np.max(np.abs(g - go)) <= 1e-8 * np.max(np.abs(go)), (g, go)
     assert g[D] == 0.0
     ctx.set_option(hipabi.OPT_ARD_LENGTHSCALE_GRADIENT, 1)
@@ -162,7 +163,7 @@ def test_gradients_on_copy_and_prefix_leaves_and_under_a_leaf_mask(ctx):
     assert np.all(info == 0)
     g = ctx.gradients(D + 2)
     for l in range(4):
-        r = DenseGP(X[rows[l]], y[rows[l]], means[l], ll, ln)
+        r = DenseGP(3, dk.pack(3, ll, logNoise=ln), X[rows[l]], y[rows[l]], means[l])
         assert abs(mll[l] - r.mll()) <= RTOL * abs(r.mll())
         go = r.grad()
         assert np.max(np.abs(g[l] - go)) <= 1e-8 * np.max(np.abs(go)), (l, g[l], go)
@@ -203,7 +204,7 @@ def test_lengthscale_count_and_unknown_kinds_are_refused(ctx):
 
 
 def _dense_leaves(m, X, y):
-    return [DenseGP(X[lf.obs], y[lf.obs], lf.mean.m, lf.kernel.logl, lf.logNoise) for lf in ptree.get_leaves(m.root)]
+    return [DenseGP(3, dk.pack(3, lf.kernel.logl, logNoise=lf.logNoise), X[lf.obs], y[lf.obs], lf.mean.m) for lf in ptree.get_leaves(m.root)]
 
 
 def test_model_fit_predict_scores_gradients_and_the_iso_linear_identity():
@@ -258,7 +259,7 @@ def test_deep_tree_runs_the_fused_small_leaf_kernels_on_ard_linear():
     leaves = ptree.get_leaves(m.root)
     for l in sample:
         lf = leaves[l]
-        r = DenseGP(X[lf.obs], y[lf.obs], lf.mean.m, ll, lf.logNoise)
+        r = DenseGP(3, dk.pack(3, ll, logNoise=lf.logNoise), X[lf.obs], y[lf.obs], lf.mean.m)
         assert abs(m.leaf_mll[l] - r.mll()) <= RTOL * max(1.0, abs(r.mll())), l
     gps = _dense_leaves(m, X, y)
     mu, var = dsm.predict(m, Xt)

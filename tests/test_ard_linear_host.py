@@ -75,9 +75,10 @@ def test_julia_glue_maps_ard_linear():
 
 
 def test_dense_restatement_with_equal_lengthscales_is_the_oracle_iso_linear():
-    """The dense ArdLinear restatement the GPU tests compare against (tests/ard_linear_dense.py), tied to the reviewed oracle:
+    """The dense ArdLinear restatement the GPU tests compare against (tests/dense_gp.py, kind 3), tied to the reviewed oracle:
     with every l_d = l it is oracle.gp's IsoLinear(l) in K, log-marginal, predictive moments and sum_d dl_d = dl."""
-    from ard_linear_dense import DenseGP, kernelmatrix
+    import dense_kernels as dk
+    from dense_gp import DenseGP
     from oracle import gp as ogp
     from deepstructuredmixtures_amd.datagen import uniform, normal
     n, D = 300, 3
@@ -85,10 +86,10 @@ def test_dense_restatement_with_equal_lengthscales_is_the_oracle_iso_linear():
     y = X @ np.array([0.5, -1.0, 2.0]) + 0.1 * normal(8, 0, n)
     Xt = uniform(9, 0, 40 * D).reshape((40, D), order="F")
     ll, ln, m = np.log(0.7), np.log(0.3), float(np.mean(y))
-    g = DenseGP(X, y, m, np.full(D, ll), ln)
+    g = DenseGP(3, dk.pack(3, np.full(D, ll), logNoise=ln), X, y, m)
     o = ogp.GaussianProcess(X, y, m, ogp.IsoLinear(ll), ln).update_cholesky()
     Ko = ogp.kernelmatrix(ogp.IsoLinear(ll), X, Xt)
-    assert np.max(np.abs(kernelmatrix(np.full(D, ll), X, Xt) - Ko)) <= 1e-14 * np.max(np.abs(Ko))
+    assert np.max(np.abs(dk.value(3, dk.pack(3, np.full(D, ll)), X, Xt) - Ko)) <= 1e-14 * np.max(np.abs(Ko))
     assert abs(g.mll() - o.mll()) <= 1e-11 * abs(o.mll())
     mu, var = g.prediction(Xt)
     mo, vo = o.prediction(Xt)

@@ -1,6 +1,6 @@
 """GPU suite for the ArdSEProduct kernel (DSMGP_KIND_ARD_SE_PRODUCT): Gram tiles, single leaves and gradients against the
 50-digit references of tests/golden/gp_ardse_product.npz, the IsoSE identity at equal length-scales, gradients by central
-differences at D up to 48, mixed kernel vectors, whole models against the dense restatement of tests/ardse_product_dense.py,
+differences at D up to 48, mixed kernel vectors, whole models against the dense restatement of tests/dense_gp.py,
 train! and the refusals.  Tolerances come from tests/pred_tolerance.py (mll_tol, moment_tol) and the gradient fixture's rule
 64 cond_2(K_y) eps max(1, |g|_inf) (tests/test_gradients_gpu.py)."""
 import itertools
@@ -13,10 +13,17 @@ import deepstructuredmixtures_amd as dsm
 from deepstructuredmixtures_amd import hipabi, tree as ptree
 from deepstructuredmixtures_amd.datagen import uniform, normal, regression_data
 from oracle import spn as ospn
-from ardse_product_dense import DenseGP, kernelmatrix as dense_K, exponent as dense_z
+import dense_kernels as dk
+from dense_gp import DenseGP
 from pred_tolerance import EPS, mll_tol, moment_tol
 
 pytestmark = pytest.mark.gpu
+
+
+def dense_z(logl, x1, x2):
+    """The exponent z = -sum_d (a_d - b_d)^2 / (2 l_d^2)."""
+    return -0.5 * dk.scaled_sqdist(4, dk.pack(4, logl), x1, x2)
+
 
 KIND = dsm.kernels.KIND_ARD_SE_PRODUCT
 GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gp_ardse_product.npz"))
@@ -66,7 +73,7 @@ def _single(ctx, X, y, mean, kind, loghyp, logNoise):
 
 
 def _cond(g):
-    ev = np.linalg.eigvalsh(g.Lf @ g.Lf.T)
+    ev = np.linalg.eigvalsh(g.F @ g.F.T)
     return ev[-1] / ev[0]
 
 
@@ -79,7 +86,7 @@ def test_kernel_matrix_against_the_dense_formula(ctx, D):
     ctx.set_train(x1, np.zeros(n1))
     ctx.set_hyper(0, KIND, list(ll) + [ls, 0.0])
     K = ctx.kernel_matrix(0, x1, x2)
-    Kd = dense_K(ll, ls, x1, x2)
+    Kd = dk.value(4, dk.pack(4, ll, ls), x1, x2)
     # both sides round z = sum_d u_d^2 nh_d in D steps (|dz| <= (D + 2) eps |z|), then exp and the sigma^2 product
     tol = Kd * (2 * (D + 2) * EPS * np.abs(dense_z(ll, x1, x2)) + 8 * EPS) + 1e-300
     _ratio("gram", np.abs(K - Kd), tol)
@@ -144,7 +151,7 @@ def test_equal_lengthscales_are_iso_se(ctx, n, D):
     mi = _single(ctx, X, y, mean, 0, np.array([l0, ls]), ln)[0][0]
     mui, vari = ctx.predict_leaves(Xt, [0, Xt.shape[0]], np.arange(Xt.shape[0]))
     gi = ctx.gradients(3)[0]
-    g = DenseGP(X, y, mean, np.full(D, l0), ls, ln)
+    g = DenseGP(4, dk.pack(4, np.full(D, l0), ls, logNoise=ln), X, y, mean)
     cond = _cond(g)
     assert abs(ma - mi) <= mll_tol(mi, cond)
     _ratio("iso identity", abs(ma - mi), mll_tol(mi, cond))
@@ -165,7 +172,7 @@ def test_gradients_against_the_dense_trace_and_finite_differences(ctx, D):
     h = np.append(ll, ls)
     _single(ctx, X, y, mean, KIND, h, ln)
     g = ctx.gradients(D + 2)[0]
-    dg = DenseGP(X, y, mean, ll, ls, ln)
+    dg = DenseGP(4, dk.pack(4, ll, ls, logNoise=ln), X, y, mean)
     go = dg.grad()
     tg = grad_tol(_cond(dg), go)
     _ratio("gradients dense", np.abs(g - go), tg)
@@ -207,7 +214,7 @@ def test_gradients_on_copy_and_prefix_leaves_and_under_a_leaf_mask(ctx):
     assert np.all(info == 0)
     g = ctx.gradients(D + 2)
     for l in range(4):
-        r = DenseGP(X[rows[l]], y[rows[l]], means[l], ll, ls, ln)
+        r = DenseGP(4, dk.pack(4, ll, ls, logNoise=ln), X[rows[l]], y[rows[l]], means[l])
         cond = _cond(r)
         assert abs(mll[l] - r.mll()) <= mll_tol(r.mll(), cond)
         go = r.grad()
@@ -240,7 +247,7 @@ def test_refusals_leave_a_usable_context(ctx):
     ctx.set_hyper(0, KIND, [0.1, 0.2, 0.3, 0.0, np.log(0.3)])
     mll, info, _ = ctx.fit()
     assert info[0] == 0
-    r = DenseGP(X, y, 0.0, [0.1, 0.2, 0.3], 0.0, np.log(0.3))
+    r = DenseGP(4, dk.pack(4, [0.1, 0.2, 0.3], 0.0, logNoise=np.log(0.3)), X, y, 0.0)
     assert abs(mll[0] - r.mll()) <= mll_tol(r.mll(), _cond(r))
 
 
@@ -270,7 +277,7 @@ def test_one_context_with_every_kind_equals_each_leaf_alone(ctx):
 
 
 def _dense_leaves(m, X, y):
-    return [DenseGP(X[lf.obs], y[lf.obs], lf.mean.m, lf.kernel.logl, lf.kernel.logs, lf.logNoise) for lf in ptree.get_leaves(m.root)]
+    return [DenseGP(4, dk.pack(4, lf.kernel.logl, lf.kernel.logs, logNoise=lf.logNoise), X[lf.obs], y[lf.obs], lf.mean.m) for lf in ptree.get_leaves(m.root)]
 
 
 def _rbcm(root, gps, x, s):

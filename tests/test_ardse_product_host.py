@@ -1,5 +1,5 @@
 """ArdSEProduct without a GPU: the parameter object, the kind number shared with the C header, the dense restatement the GPU
-tests compare against (tests/ardse_product_dense.py) against the 50-digit references and the oracle's IsoSE, and the Julia
+tests compare against (tests/dense_gp.py on tests/dense_kernels.py) against the 50-digit references and the oracle's IsoSE, and the Julia
 glue's methods for it (julia/DSMGPHip.jl cannot be executed here: its text is checked)."""
 import os
 import re
@@ -66,12 +66,13 @@ def _golden():
 
 @pytest.mark.parametrize("name,c", _golden(), ids=[n for n, _ in _golden()])
 def test_dense_restatement_against_50_digit_references(name, c):
-    from ardse_product_dense import DenseGP, kernelmatrix
-    g = DenseGP(c["X"], c["y"], float(c["mean"]), c["logl"], float(c["logs"]), float(c["logNoise"]))
+    import dense_kernels as dk
+    from dense_gp import DenseGP
+    g = DenseGP(4, dk.pack(4, c["logl"], c["logs"], logNoise=c["logNoise"]), c["X"], c["y"], float(c["mean"]))
     assert g.info == 0
     cond = float(c["cond"])
     m = c["Kc"].shape[0]
-    assert np.allclose(kernelmatrix(c["logl"], float(c["logs"]), c["X"][:m], c["X"][:m]), c["Kc"], rtol=1e-13, atol=0)
+    assert np.allclose(dk.value(4, dk.pack(4, c["logl"], c["logs"]), c["X"][:m], c["X"][:m]), c["Kc"], rtol=1e-13, atol=0)
     assert abs(g.mll() - float(c["mll"])) <= mll_tol(float(c["mll"]), cond)
     mu, var = g.prediction(c["Xt"])
     tol = 64 * cond * EPS * max(1.0, float(np.max(np.abs(c["y"]))))
@@ -83,7 +84,8 @@ def test_dense_restatement_against_50_digit_references(name, c):
 def test_dense_restatement_with_equal_lengthscales_is_the_oracle_iso_se():
     """With every l_d = l: the oracle's IsoSE(l, s) in K, log-marginal and moments; sum_d dl_d * sigma = IsoSE's dl and
     ds * sigma = IsoSE's ds (the reference's factor sigma)."""
-    from ardse_product_dense import DenseGP, kernelmatrix
+    import dense_kernels as dk
+    from dense_gp import DenseGP
     from oracle import gp as ogp
     from deepstructuredmixtures_amd.datagen import uniform, normal
     n, D = 300, 3
@@ -91,11 +93,11 @@ def test_dense_restatement_with_equal_lengthscales_is_the_oracle_iso_se():
     y = np.sin(3 * X[:, 0]) + 0.1 * normal(8, 0, n)
     Xt = uniform(9, 0, 40 * D).reshape((40, D), order="F")
     ll, ls, ln, m = np.log(0.5), 0.2, np.log(0.3), float(np.mean(y))
-    g = DenseGP(X, y, m, np.full(D, ll), ls, ln)
+    g = DenseGP(4, dk.pack(4, np.full(D, ll), ls, logNoise=ln), X, y, m)
     k = ogp.make_kernel(0, np.array([ll, ls]))
     o = ogp.GaussianProcess(X, y, m, k, ln, exact_dist=True).update_cholesky()
     Ko = ogp.kernelmatrix(k, X, Xt)
-    assert np.max(np.abs(kernelmatrix(np.full(D, ll), ls, X, Xt) - Ko)) <= 1e-14 * np.max(np.abs(Ko))
+    assert np.max(np.abs(dk.value(4, dk.pack(4, np.full(D, ll), ls), X, Xt) - Ko)) <= 1e-14 * np.max(np.abs(Ko))
     assert abs(g.mll() - o.mll()) <= 1e-11 * abs(o.mll())
     mu, var = g.prediction(Xt)
     mo, vo = o.prediction(Xt)

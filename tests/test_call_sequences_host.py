@@ -244,10 +244,12 @@ def test_the_references_alone_are_finite_and_well_conditioned(oracle_run):
 
 
 def test_the_oracle_s_kernels_are_the_dense_modules():
-    """call_sequences_oracle.cross / cross_dx against predgrad_dense (kinds 0-8), matern_dense and rq_dense; its gradient rows
-    against targets_grad_dense.column_gradients."""
+    """call_sequences_oracle's gradient rows against targets_grad_dense.column_gradients, and its kernel -- the one table of
+    tests/dense_kernels.py -- against itself: the input derivative of every kind against central differences of the value."""
     import call_sequences_oracle as co
+    import dense_kernels as dk
     import targets_grad_dense as tgd
+    assert co.dk is dk
     Xa, ya = cs.train("A")
     for cls in cs.KIND:
         kind, hyp = cs.hyper(cls, "a", 2)
@@ -256,26 +258,15 @@ def test_the_oracle_s_kernels_are_the_dense_modules():
         for ard in (False, True):
             G, _, cond = tgd.column_gradients(kind, hyp, Xa[:60], Y, [0.1, 0.2], ard_true=ard)
             assert np.allclose(co.mll_gradients(g, Y, [0.1, 0.2], ard), G, rtol=1e-9, atol=1e-9) and abs(g.cond / cond - 1.0) < 1e-6
-    import matern_dense
-    import predgrad_dense
-    import rq_dense
     X, _ = cs.train("B")
     A, B = X[:9], X[20:31]
     for cls in cs.KIND:
         kind, hyp = cs.hyper(cls, "b", 5)
         h = hyp[:-1]
-        K = co.cross(kind, h, A, B)
-        if kind <= 8:
-            assert np.allclose(K, predgrad_dense.kernelmatrix(kind, h, A, B), rtol=1e-14, atol=0)
-            assert np.allclose(co.cross_dx(kind, h, A, B), predgrad_dense.kernel_dx(kind, h, A, B), rtol=1e-13, atol=1e-300)
-        if kind in matern_dense.KINDS:
-            assert np.allclose(K, matern_dense.kernelmatrix(kind, h[:-1], h[-1], A, B), rtol=1e-14, atol=0)
-        if kind in rq_dense.KINDS:
-            assert np.allclose(K, rq_dense.kernelmatrix(kind, h[:-2], h[-2], h[-1], A, B), rtol=1e-14, atol=0)
-            e = 1e-6                                    # the rational quadratic derivative: central differences
-            for d in range(5):
-                P, M = A.copy(), A.copy()
-                P[:, d] += e
-                M[:, d] -= e
-                fd = (co.cross(kind, h, P, B) - co.cross(kind, h, M, B)) / (2 * e)
-                assert np.allclose(co.cross_dx(kind, h, A, B)[:, :, d], fd, rtol=1e-6, atol=1e-9)
+        e = 1e-6
+        for d in range(5):
+            P, M = A.copy(), A.copy()
+            P[:, d] += e
+            M[:, d] -= e
+            fd = (dk.value(kind, h, P, B) - dk.value(kind, h, M, B)) / (2 * e)
+            assert np.allclose(dk.d_input(kind, h, A, B)[:, :, d], fd, rtol=1e-6, atol=1e-9)

@@ -13,7 +13,7 @@ import scipy.linalg as sla
 from deepstructuredmixtures_amd import hipabi
 from deepstructuredmixtures_amd.datagen import uniform, normal, regression_data
 from oracle import gp as ogp
-from ard_linear_dense import DenseGP
+from dense_gp import DenseGP
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +43,7 @@ def _oracle(X, y, mean, kind, hyp):
     """f64 oracle of one leaf (DenseGP for ArdLinear)."""
     hyp = np.asarray(hyp, dtype=np.float64)
     if kind == 3:
-        return DenseGP(X, y, mean, hyp[:-2], hyp[-1])
+        return DenseGP(3, hyp, X, y, mean)
     return ogp.GaussianProcess(X, y, mean, ogp.make_kernel(kind, hyp[:-1]), hyp[-1], exact_dist=True).update_cholesky()
 
 

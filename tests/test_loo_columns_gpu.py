@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import dense_kernels as dk
 import loo_columns_dense as lcd
 from deepstructuredmixtures_amd import hipabi
 
@@ -86,7 +87,7 @@ def test_fixture_cases_against_50_digit_references(ctx, name, fused_gram):
         _single(ctx, c["X"], Y[:, 0], c["mean"][0], kind, hyp)
         ctx.solve_targets(Y, c["mean"][None, :])
         worst = _check_moments(name, c, ctx.loo_targets())
-        K = lcd.true_derivatives(kind, hyp[:-1], c["X"])[0]
+        K = dk.d_hyper(kind, hyp[:-1], c["X"])[0]
         g, lpd = ctx.loo_targets_gradients(hyp.size, w[None, :])
         assert _same_bits(lpd, ctx.loo_targets()[2])
         worst = max(worst, _check(f"{name} weighted", g[0], c["wsum"], lcd.gradient_tolerance(c, c["grad"], w, K)))
@@ -114,7 +115,7 @@ def _columns(seed, X, Q):
 def _dense_case(kind, hyp, X, Y, mean):
     """A case in the fixture's layout with float64 references from the dense module (the literal form per column)."""
     mu, var, lpd = lcd.moments(kind, hyp, X, Y, mean)
-    K = lcd.true_derivatives(kind, hyp[:-1], X)[0]
+    K = dk.d_hyper(kind, hyp[:-1], X)[0]
     ev = np.linalg.eigvalsh(K + (np.exp(2.0 * hyp[-1]) + lcd.JITTER) * np.eye(X.shape[0]))
     return dict(kind=kind, X=X, Y=Y, mean=np.asarray(mean, dtype=np.float64), hyp=hyp, mu=mu, var=var, lpd=lpd, kss=np.diag(K).copy(),
                 cond=float(ev[-1] / ev[0]), weak=False, grad=lcd.column_gradients_literal(kind, hyp, X, Y, mean)), K

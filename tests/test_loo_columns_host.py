@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import deepstructuredmixtures_amd as dsm
+import dense_kernels as dk
 import loo_columns_dense as lcd
 from deepstructuredmixtures_amd import hipabi
 from loo_columns_context import LooColumnsOracleContext
@@ -107,7 +108,7 @@ def test_dense_moments_against_brute_force_refits():
     mean = np.array([0.1, 2.4, 0.0])
     hyp = np.array([np.log(0.5), 0.1, np.log(0.2)])
     mu, var, _ = lcd.moments(0, hyp, X, Y, mean)
-    K = lcd.true_derivatives(0, hyp[:-1], X)[0]
+    K = dk.d_hyper(0, hyp[:-1], X)[0]
     for q in range(3):
         mb, vb = ld.loo_brute(K, np.exp(2.0 * hyp[-1]), Y[:, q], mean[q])
         assert np.allclose(mu[:, q], mb, rtol=1e-9, atol=1e-10) and np.allclose(var, vb + ld.JITTER, rtol=1e-9, atol=1e-12)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import deepstructuredmixtures_amd as dsm
+import dense_kernels as dk
 import loo_dense
 from deepstructuredmixtures_amd import hipabi
 from deepstructuredmixtures_amd import model as dmodel
@@ -407,7 +408,7 @@ def test_failed_leaf_gets_nan_and_the_others_are_unaffected(ctx):
     assert info[0] != 0 and info[1] == 0
     mu, var, lpd = ctx.loo()
     assert np.all(np.isnan(mu[:n0])) and np.all(np.isnan(var[:n0])) and np.isnan(lpd[0])
-    K = loo_dense.kernel_matrix(0, hyp1, X[n0:], X[n0:])
+    K = dk.value(0, hyp1, X[n0:], X[n0:])
     rm, rv, rl = loo_dense.loo_dense(K, lib_noise(np.log(0.1)), y[n0:], 0.2)
     tm, tv, _, ts = loo_dense.loo_tol(y[n0:], rm, rv, np.diag(K), lib_noise(np.log(0.1)))
     _check("good leaf mu", mu[n0:], rm, 2.0 * tm)

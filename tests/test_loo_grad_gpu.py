@@ -13,6 +13,7 @@ import pytest
 
 from deepstructuredmixtures_amd import hipabi
 from deepstructuredmixtures_amd.datagen import uniform, normal
+import dense_kernels as dk
 import loo_grad_dense as lgd
 
 pytestmark = pytest.mark.gpu
@@ -53,7 +54,7 @@ def test_fixture_cases_against_50_digit_references(ctx, name):
     _single(ctx, c["X"], c["y"], c["mean"], c["kind"], hyp)
     g, lpd = ctx.loo_gradients(hyp.size)
     assert g.shape == (1, hyp.size) and lpd.shape == (1,)
-    K = lgd.kernel_matrix(c["kind"], c["loghyp"], c["X"], c["X"])
+    K = dk.value(c["kind"], c["loghyp"], c["X"], c["X"])
     tol = lgd.tolerance(c, c["grad"], K)
     err = np.abs(g[0] - c["grad"])
     print(f"\n{name}: cond {c['cond']:.3g} |g|inf {np.max(np.abs(c['grad'])):.3g} max err {np.max(err):.3g}, worst err/tol {np.max(err / tol):.3g}")
@@ -91,7 +92,7 @@ def _table_check(ctx, tag, mean, g, factor=2.0):
         F, _ = ctx.download_factor(l, b - a)
         F = np.tril(F)
         Xl = np.asfortranarray(T["X"][rows])
-        ref = lgd.loo_grad_from_factor(F, lgd.kernel_derivatives(kind, hyp[:-1], Xl), noise, T["y"][rows], float(mean[l]))
+        ref = lgd.loo_grad_from_factor(F, dk.d_hyper(kind, hyp[:-1], Xl)[1], noise, T["y"][rows], float(mean[l]))
         sv = np.linalg.svd(F, compute_uv=False)
         case = dict(kind=kind, cond=float((sv[0] / sv[-1]) ** 2), weak=False, logNoise=float(hyp[-1]))
         tol = factor * lgd.tolerance(case, ref)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import deepstructuredmixtures_amd as dsm
+import dense_kernels as dk
 import loo_grad_dense as lgd
 from deepstructuredmixtures_amd import hipabi
 from deepstructuredmixtures_amd import model as dmodel
@@ -42,8 +43,8 @@ def test_dense_helper_against_50_digits(name):
     agrees with the 50-digit one."""
     c = CASES[name]
     noise = float(np.exp(2.0 * c["logNoise"]))
-    K = lgd.kernel_matrix(c["kind"], c["loghyp"], c["X"], c["X"])
-    g = lgd.loo_grad_dense(K, lgd.kernel_derivatives(c["kind"], c["loghyp"], c["X"]), noise, c["y"], c["mean"])
+    K = dk.value(c["kind"], c["loghyp"], c["X"], c["X"])
+    g = lgd.loo_grad_dense(K, dk.d_hyper(c["kind"], c["loghyp"], c["X"])[1], noise, c["y"], c["mean"])
     assert g.shape == c["grad"].shape
     r = float(np.max(np.abs(g - c["grad"]) / lgd.tolerance(c, c["grad"], K)))
     print(f"\n{name}: cond {c['cond']:.3g}, dense err/tol {r:.3g}")
@@ -67,12 +68,12 @@ def test_dense_helper_against_central_differences_and_the_literal_form(kind):
     X, y, mean, loghyp, logNoise = _random_case(kind, 40 + 3 * kind, 1 + kind % 3, 100 + kind)
 
     def lpd(h):
-        return lgd.lpd_sum(lgd.kernel_matrix(kind, h[:-1], X, X), float(np.exp(2.0 * h[-1])), y, mean)
+        return lgd.lpd_sum(dk.value(kind, h[:-1], X, X), float(np.exp(2.0 * h[-1])), y, mean)
 
     h0 = np.concatenate([loghyp, [logNoise]])
     noise = float(np.exp(2.0 * logNoise))
-    K = lgd.kernel_matrix(kind, loghyp, X, X)
-    dKs = lgd.kernel_derivatives(kind, loghyp, X)
+    K = dk.value(kind, loghyp, X, X)
+    dKs = dk.d_hyper(kind, loghyp, X)[1]
     g = lgd.loo_grad_dense(K, dKs, noise, y, mean)
     lit = lgd.loo_grad_literal(K, dKs, noise, y, mean)
     assert np.max(np.abs(g - lit)) <= 1e-10 * max(1.0, float(np.max(np.abs(lit))))

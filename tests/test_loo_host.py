@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import dense_kernels as dk
 import loo_dense
 from deepstructuredmixtures_amd import hipabi
 from deepstructuredmixtures_amd import model as dmodel
@@ -32,7 +33,7 @@ def test_fixture_covers_the_cases_the_feature_names():
 def test_dense_helper_against_50_digits(name):
     c = CASES[name]
     noise = math.exp(2.0 * c["logNoise"])
-    K = loo_dense.kernel_matrix(c["kind"], c["loghyp"], c["X"], c["X"])
+    K = dk.value(c["kind"], c["loghyp"], c["X"], c["X"])
     assert np.all(np.abs(np.diag(K) - c["kss"]) <= 1e-13 * np.maximum(1.0, c["kss"]))
     mu, var, lpd = loo_dense.loo_dense(K, noise, c["y"], c["mean"])
     tm, tv, tl, ts = loo_dense.loo_tol(c["y"], c["mu"], c["var"], c["kss"], noise)
@@ -52,7 +53,7 @@ def test_dense_helper_against_brute_force(kind, n, D):
     ard = kind in (1, 3, 8)
     loghyp = np.concatenate([np.log(np.full(D if ard else 1, 0.6)), [0.1]])
     noise = 0.1 ** 2
-    K = loo_dense.kernel_matrix(kind, loghyp, X, X)
+    K = dk.value(kind, loghyp, X, X)
     mean = 0.25
     mu, var, _ = loo_dense.loo_dense(K, noise, y, mean)
     mu_b, var_b = loo_dense.loo_brute(K, noise, y, mean)

@@ -1,5 +1,5 @@
 """GPU suite for the Matern kernels (DSMGP kinds 5-8): Gram tiles, single leaves and gradients against the 50-digit references of
-tests/golden/gp_matern.npz and the dense restatement of tests/matern_dense.py, the iso kind as the ARD kind with equal
+tests/golden/gp_matern.npz and the dense restatement of tests/dense_gp.py, the iso kind as the ARD kind with equal
 length-scales (bit for bit), gradients by central differences at D up to 48 with duplicate training points, COPY / PREFIX
 leaves and masks, all nine kinds in one context, whole models, mixed kernel vectors with resident test rows and n_sub = 2,
 train! and the refusals.  Tolerances come from tests/pred_tolerance.py (mll_tol, moment_tol) and the gradient rule
@@ -14,10 +14,18 @@ import deepstructuredmixtures_amd as dsm
 from deepstructuredmixtures_amd import hipabi, tree as ptree
 from deepstructuredmixtures_amd.datagen import uniform, normal, regression_data
 from oracle import spn as ospn
-from matern_dense import DenseGP, KINDS, NAMES, is_ard, kernelmatrix as dense_K, s2 as dense_s2
+import dense_kernels as dk
+from dense_gp import DenseGP
 from pred_tolerance import EPS, mll_tol, moment_tol
 
 pytestmark = pytest.mark.gpu
+
+KINDS = dk.MATERN
+
+
+def is_ard(kind):
+    return kind in dk.ARD
+
 
 GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gp_matern.npz"))
 CASES = sorted({k.split("/")[0] for k in GOLD.files})
@@ -44,7 +52,7 @@ def gram_tol(kind, logl, x1, x2, Kd):
     """Both sides round s^2 in D steps (|dz| <= (D + 2) eps z), then sqrt, exp(-s) and the polynomial: |dK| / K <= about
     (D / 2 + 3) eps s + 8 eps per side."""
     D = x1.shape[1]
-    s = np.sqrt(dense_s2(kind, logl, x1, x2))
+    s = np.sqrt(dk.two_nu(kind) * dk.scaled_sqdist(kind, dk.pack(kind, logl), x1, x2))
     return np.abs(Kd) * ((D + 6) * EPS * s + 16 * EPS) + 1e-300
 
 
@@ -79,7 +87,7 @@ def _single(ctx, X, y, mean, kind, loghyp, logNoise):
 
 
 def _cond(g):
-    ev = np.linalg.eigvalsh(g.Lf @ g.Lf.T)
+    ev = np.linalg.eigvalsh(g.F @ g.F.T)
     return ev[-1] / ev[0]
 
 
@@ -96,7 +104,7 @@ def test_kernel_matrix_against_the_dense_formula(ctx, kind, D):
     ctx.set_train(x1, np.zeros(n1))
     ctx.set_hyper(0, kind, list(ll) + [ls, 0.0])
     K = ctx.kernel_matrix(0, x1, x2)
-    Kd = dense_K(kind, ll, ls, x1, x2)
+    Kd = dk.value(kind, dk.pack(kind, ll, ls), x1, x2)
     tol = gram_tol(kind, ll, x1, x2, Kd)
     _ratio("gram", np.abs(K - Kd), tol)
     assert np.all(np.abs(K - Kd) <= tol)
@@ -154,7 +162,7 @@ def test_large_leaves_against_the_dense_restatement(ctx, kind, n, D):
     X, y, Xt = _data(700 + n + kind, n, D, dup=7)
     ll, ls, ln, mean = _logl(kind, D), 0.1, np.log(0.25), float(np.mean(y))
     h = np.append(ll, ls)
-    r = DenseGP(X, y, mean, kind, ll, ls, ln)
+    r = DenseGP(kind, dk.pack(kind, ll, ls, logNoise=ln), X, y, mean)
     cond = _cond(r)
     mo, vo = r.prediction(Xt)
     go = r.grad()
@@ -211,7 +219,7 @@ def test_gradients_against_the_dense_trace_and_finite_differences(ctx, kind, D):
     _single(ctx, X, y, mean, kind, h, ln)
     ng = _ng(kind, D)
     g = ctx.gradients(ng)[0]
-    dg = DenseGP(X, y, mean, kind, ll, ls, ln)
+    dg = DenseGP(kind, dk.pack(kind, ll, ls, logNoise=ln), X, y, mean)
     go = dg.grad()
     assert np.all(np.isfinite(g))
     tg = grad_tol(_cond(dg), go)
@@ -256,7 +264,7 @@ def test_gradients_on_copy_and_prefix_leaves_and_under_a_leaf_mask(ctx, kind):
     assert np.all(info == 0)
     g = ctx.gradients(ng)
     for l in range(4):
-        r = DenseGP(X[rows[l]], y[rows[l]], means[l], kind, ll, ls, ln)
+        r = DenseGP(kind, dk.pack(kind, ll, ls, logNoise=ln), X[rows[l]], y[rows[l]], means[l])
         cond = _cond(r)
         assert abs(mll[l] - r.mll()) <= mll_tol(r.mll(), cond)
         go = r.grad()
@@ -295,7 +303,7 @@ def test_refusals_leave_a_usable_context(ctx, kind):
     ctx.set_hyper(0, kind, ll + [0.0, np.log(0.3)])
     mll, info, _ = ctx.fit()
     assert info[0] == 0
-    r = DenseGP(X, y, 0.0, kind, ll, 0.0, np.log(0.3))
+    r = DenseGP(kind, dk.pack(kind, ll, 0.0, logNoise=np.log(0.3)), X, y, 0.0)
     assert abs(mll[0] - r.mll()) <= mll_tol(r.mll(), _cond(r))
 
 
@@ -327,7 +335,7 @@ def test_one_context_with_every_kind_equals_each_leaf_alone(ctx):
             assert abs(mll[l] - ml) <= 1e-12 * max(1.0, abs(ml)), l
             assert np.allclose(g[l], gl, rtol=1e-12, atol=1e-13 * max(1.0, np.max(np.abs(gl)))), l
             if kind >= 5:
-                r = DenseGP(X[rows[l]], y[rows[l]], means[l], kind, h[:-1], h[-1], ln)
+                r = DenseGP(kind, dk.pack(kind, h[:-1], h[-1], logNoise=ln), X[rows[l]], y[rows[l]], means[l])
                 go = r.grad()
                 _ratio("nine kinds", np.abs(g[l][:go.size] - go), grad_tol(_cond(r), go))
                 assert np.all(np.abs(g[l][:go.size] - go) <= grad_tol(_cond(r), go)), (l, g[l], go)
@@ -336,7 +344,7 @@ def test_one_context_with_every_kind_equals_each_leaf_alone(ctx):
 
 
 def _dense_leaves(m, X, y):
-    return [DenseGP(X[lf.obs], y[lf.obs], lf.mean.m, lf.kernel.kind, lf.kernel.logl, lf.kernel.logs, lf.logNoise)
+    return [DenseGP(lf.kernel.kind, dk.pack(lf.kernel.kind, lf.kernel.logl, lf.kernel.logs, logNoise=lf.logNoise), X[lf.obs], y[lf.obs], lf.mean.m)
             for lf in ptree.get_leaves(m.root)]
 
 
@@ -522,7 +530,7 @@ def test_a_pooled_context_takes_its_kinds_after_set_test(order):
             for l in (0, 1, L - 2, L - 1):
                 kind, h = hyp[kid[l]]
                 if kind >= 5:
-                    r = DenseGP(X[rows[l]], y[rows[l]], means[l], kind, h[:-1], h[-1], ln)
+                    r = DenseGP(kind, dk.pack(kind, h[:-1], h[-1], logNoise=ln), X[rows[l]], y[rows[l]], means[l])
                     _ratio("pooled set_test", abs(mll[l] - r.mll()), mll_tol(r.mll(), _cond(r)))
                     assert abs(mll[l] - r.mll()) <= mll_tol(r.mll(), _cond(r)), l
     finally:

@@ -1,5 +1,5 @@
 """The Matern kernels without a GPU: the parameter objects, the kind numbers shared with the C header, the dense restatement the
-GPU tests compare against (tests/matern_dense.py) against the 50-digit references and the closed forms at r = 0 and r -> inf,
+GPU tests compare against (tests/dense_gp.py on tests/dense_kernels.py) against the 50-digit references and the closed forms at r = 0 and r -> inf,
 the model-side host paths (gradient rows, the rBCM prior), and the Julia glue's methods for them (julia/DSMGPHip.jl cannot be
 executed here: its text is checked)."""
 import os
@@ -88,14 +88,15 @@ def test_golden_covers_every_kind_duplicates_and_spread_lengthscales():
 
 @pytest.mark.parametrize("name,c", _golden(), ids=[n for n, _ in _golden()])
 def test_dense_restatement_against_50_digit_references(name, c):
-    from matern_dense import DenseGP, kernelmatrix
+    import dense_kernels as dk
+    from dense_gp import DenseGP
     kind = int(c["kind"])
-    g = DenseGP(c["X"], c["y"], float(c["mean"]), kind, c["logl"], float(c["logs"]), float(c["logNoise"]))
+    g = DenseGP(kind, dk.pack(kind, c["logl"], c["logs"], logNoise=c["logNoise"]), c["X"], c["y"], float(c["mean"]))
     assert g.info == 0
     cond = float(c["cond"])
     m = c["Kc"].shape[0]
-    assert np.allclose(kernelmatrix(kind, c["logl"], float(c["logs"]), c["X"][:m], c["X"][:m]), c["Kc"], rtol=1e-13, atol=0)
-    assert np.allclose(kernelmatrix(kind, c["logl"], float(c["logs"]), c["X"][:m], c["Xt"]), c["Kt"], rtol=1e-13, atol=0)
+    assert np.allclose(dk.value(kind, dk.pack(kind, c["logl"], c["logs"]), c["X"][:m], c["X"][:m]), c["Kc"], rtol=1e-13, atol=0)
+    assert np.allclose(dk.value(kind, dk.pack(kind, c["logl"], c["logs"]), c["X"][:m], c["Xt"]), c["Kt"], rtol=1e-13, atol=0)
     assert abs(g.mll() - float(c["mll"])) <= mll_tol(float(c["mll"]), cond)
     mu, var = g.prediction(c["Xt"])
     tol = 64 * cond * EPS * max(1.0, float(np.max(np.abs(c["y"]))))
@@ -109,45 +110,51 @@ def test_dense_restatement_against_50_digit_references(name, c):
 def test_closed_forms_at_r_zero_and_r_to_infinity(kind):
     """k(x, x) = sigma^2 exactly; far apart k -> 0 with the nu-specific tail; at one s the textbook polynomial; the iso kind
     is the ARD kind with equal length-scales."""
-    from matern_dense import kernelmatrix, two_nu, is_ard
+    import dense_kernels as dk
+    from dense_kernels import two_nu
+
+    def is_ard(kind):
+        return kind in dk.ARD
     D, ls = 3, 0.4
     ll = np.log([0.7] * (D if is_ard(kind) else 1))
     x = np.array([[0.1, 0.2, 0.3]])
-    assert kernelmatrix(kind, ll, ls, x, x)[0, 0] == np.exp(2 * ls)
+    assert dk.value(kind, dk.pack(kind, ll, ls), x, x)[0, 0] == np.exp(2 * ls)
     far = x + 1e3
-    assert kernelmatrix(kind, ll, ls, x, far)[0, 0] == 0.0
+    assert dk.value(kind, dk.pack(kind, ll, ls), x, far)[0, 0] == 0.0
     # s = sqrt(2 nu) r with r = |a - b| / l
     b = x + np.array([[0.3, -0.1, 0.2]])
     r = np.sqrt(np.sum((x - b) ** 2)) / 0.7
     s = np.sqrt(two_nu(kind)) * r
     p = 1 + s if two_nu(kind) == 3.0 else 1 + s + s * s / 3
-    assert abs(kernelmatrix(kind, ll, ls, x, b)[0, 0] - np.exp(2 * ls) * p * np.exp(-s)) <= 1e-15
+    assert abs(dk.value(kind, dk.pack(kind, ll, ls), x, b)[0, 0] - np.exp(2 * ls) * p * np.exp(-s)) <= 1e-15
     # tail: k / sigma^2 = e^-s (1 + s [+ s^2 / 3]) at s = 30
     b30 = x + np.array([[30.0 * 0.7 / np.sqrt(two_nu(kind)), 0.0, 0.0]])
     tail = (31.0 if two_nu(kind) == 3.0 else 1 + 30 + 300.0) * np.exp(-30.0)
-    assert abs(kernelmatrix(kind, ll, 0.0, x, b30)[0, 0] - tail) <= 1e-12 * tail
+    assert abs(dk.value(kind, dk.pack(kind, ll, 0.0), x, b30)[0, 0] - tail) <= 1e-12 * tail
     if not is_ard(kind):
-        assert np.array_equal(kernelmatrix(kind, ll, ls, x, b), kernelmatrix(kind + 2, np.full(D, ll[0]), ls, x, b))
+        assert np.array_equal(dk.value(kind, dk.pack(kind, ll, ls), x, b),
+                              dk.value(kind + 2, dk.pack(kind + 2, np.full(D, ll[0]), ls), x, b))
 
 
 @pytest.mark.parametrize("kind", [5, 6, 7, 8])
 def test_dense_gradients_are_finite_at_duplicate_points_and_match_finite_differences(kind):
-    from matern_dense import DenseGP, is_ard
+    import dense_kernels as dk
+    from dense_gp import DenseGP
     from deepstructuredmixtures_amd.datagen import uniform, normal
     n, D = 60, 2
     X = uniform(31, 0, n * D).reshape((n, D), order="F")
     X[50:] = X[:10]                                             # s = 0 off the diagonal
     y = np.sin(3 * X[:, 0]) + 0.1 * normal(32, 0, n)
-    ll = np.log([0.4, 0.9]) if is_ard(kind) else np.log([0.6])
+    ll = np.log([0.4, 0.9]) if kind in dk.ARD else np.log([0.6])
     h = np.concatenate([ll, [0.1, np.log(0.3)]])
-    g = DenseGP(X, y, 0.0, kind, h[:-2], h[-2], h[-1]).grad()
+    g = DenseGP(kind, h, X, y, 0.0).grad()
     assert np.all(np.isfinite(g))
     e = 1e-6
     for j in range(h.size):
         hp, hm = h.copy(), h.copy()
         hp[j] += e
         hm[j] -= e
-        fd = (DenseGP(X, y, 0.0, kind, hp[:-2], hp[-2], hp[-1]).mll() - DenseGP(X, y, 0.0, kind, hm[:-2], hm[-2], hm[-1]).mll()) / (2 * e)
+        fd = (DenseGP(kind, hp, X, y, 0.0).mll() - DenseGP(kind, hm, X, y, 0.0).mll()) / (2 * e)
         assert abs(fd - g[j]) <= 1e-6 * max(1.0, abs(fd)), (j, fd, g[j])
 
 

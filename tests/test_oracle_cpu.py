@@ -234,7 +234,7 @@ def test_oracle_gradients_match_the_50_digit_references(golden_dir):
     """tests/golden/gp_grad.npz (make_grad_golden.py): gradients contracted directly at 50 digits, in the library's
     convention.  oracle.gp (DenseGP for ArdLinear) within 16 cond_2(K_y) eps max(1, |g|_inf) of every component; the ArdSE
     length-scale slots are the reference's zeros.  Leaf sizes 1, 2, 127..129, 160; D up to 48; the weak-signal cases too."""
-    from ard_linear_dense import DenseGP
+    from dense_gp import DenseGP
 
     z = np.load(os.path.join(golden_dir, "gp_grad.npz"))
     cases = {}
@@ -246,7 +246,7 @@ def test_oracle_gradients_match_the_50_digit_references(golden_dir):
     for name, c in cases.items():
         kind, h, ln = int(c["kind"]), c["loghyp"], float(c["logNoise"])
         if kind == 3:
-            g = DenseGP(c["X"], c["y"], float(c["mean"]), h[:-1], ln)
+            g = DenseGP(3, np.append(h, ln), c["X"], c["y"], float(c["mean"]))
         else:
             g = ogp.GaussianProcess(c["X"], c["y"], float(c["mean"]), ogp.make_kernel(kind, h), ln, True).update_cholesky()
         assert g.info == 0
@@ -267,7 +267,8 @@ def test_oracle_prediction_aggregation_and_scores_match_the_50_digit_references(
     through oracle/spn.py's update! and literal predict recursion on the tree of oracle/tree.py, within those per-entry bounds
     carried through the formula (pred_tolerance.agg_tol / score_tol)."""
     import math
-    from ard_linear_dense import DenseGP, prior_diag as ardlin_diag
+    import dense_kernels as dk
+    from dense_gp import DenseGP
     from oracle import scores as oscores, tree as otree
     from pred_tolerance import agg_tol, aggregate, row_entries, score_tol
 
@@ -284,7 +285,7 @@ def test_oracle_prediction_aggregation_and_scores_match_the_50_digit_references(
 
     def leaf(kind, hyp, X, y, mean):
         if kind == 3:
-            return DenseGP(X, y, mean, hyp[:-2], hyp[-1])
+            return DenseGP(3, hyp, X, y, mean)
         return ogp.GaussianProcess(X, y, mean, ogp.make_kernel(kind, hyp[:-1]), hyp[-1], True).update_cholesky()
 
     def moments_tol(cond, kss, noise, yscale):
@@ -325,7 +326,7 @@ def test_oracle_prediction_aggregation_and_scores_match_the_50_digit_references(
     # aggregations in float64 from the oracle's moments, and the oracle's scores of them
     ent = row_entries(rp, T["route_idx"], nt)
     pk = int(T["prior_kid"])
-    kss_prior = ardlin_diag(T["hyp"][pk][:T["Xt"].shape[1]], T["Xt"])
+    kss_prior = dk.prior_diag(3, T["hyp"][pk][:T["hyp_len"][pk] - 1], T["Xt"])
     noise_prior = float(np.exp(2.0 * T["hyp"][pk][T["hyp_len"][pk] - 1]))
     fams = dict(mixture=(0, T["w_mix"], False), mixture_plain=(0, T["w_mix"], True), poe=(1, np.ones(L), False),
                 gpoe=(2, T["beta"], False), rbcm=(3, None, False), mixture_off=(0, T["w_mix"], False))

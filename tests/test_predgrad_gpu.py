@@ -13,6 +13,7 @@ import pytest
 import deepstructuredmixtures_amd as dsm
 from deepstructuredmixtures_amd import hipabi
 from deepstructuredmixtures_amd import datagen
+import dense_kernels as dk
 import predgrad_dense as pgd
 from test_predcov_gpu import TABLE, _same_bits, _table_setup, lib_noise
 
@@ -31,7 +32,7 @@ def loghyp_of(kind, D):
     ls = np.array([0.35, 0.5, 0.42])[:D] * np.sqrt(D) if D <= 3 else np.full(D, 0.3 * np.sqrt(D))
     if kind in (2, 3):
         ls = ls + 0.5
-    nl = D if kind in pgd.ARD else 1
+    nl = D if kind in dk.ARD else 1
     return np.concatenate([np.log(ls[:nl]), [0.0 if kind in (2, 3) else 0.1]])
 
 

@@ -9,6 +9,7 @@ import pytest
 
 import deepstructuredmixtures_amd as dsm
 from deepstructuredmixtures_amd import datagen, hipabi
+import dense_kernels as dk
 import predgrad_dense as pgd
 from pred_tolerance import EPS, Prop, aggregate, moment_tol, row_entries
 
@@ -40,7 +41,7 @@ def test_fixture_covers_the_cases_the_feature_names():
         a, b = c["dup"]
         assert np.array_equal(c["Xt"][a], c["Xt"][b]) and (a != b or nt == 1) and a // 128 == b // 128
         assert np.array_equal(c["dmu"][a], c["dmu"][b]) and np.array_equal(c["dvar"][a], c["dvar"][b])
-        if c["kind"] not in pgd.LINEAR and nt > 4:                                      # k* underflows: exactly 0
+        if c["kind"] not in dk.LINEAR and nt > 4:                                      # k* underflows: exactly 0
             assert c["far"] == [2, 3] and np.all(c["Xt"][2] == 1e3) and np.all(c["Xt"][3] == -1e3)
             assert np.all(c["dmu"][2:4] == 0.0) and np.all(c["dvar"][2:4] == 0.0)
         else:
@@ -94,8 +95,8 @@ def _agg_case(fname):
         kw["coef"] = T["beta"]
     else:
         Xt = T["Xt"][:R]
-        kw.update(group=T["group"], G=int(T["G"]), kss_prior=pgd.prior_diag(int(T["kinds"][pk]), phyp[:-1], Xt),
-                  noise_prior=float(np.exp(2 * phyp[-1])), dkss_prior=pgd.prior_dx(int(T["kinds"][pk]), phyp[:-1], Xt))
+        kw.update(group=T["group"], G=int(T["G"]), kss_prior=dk.prior_diag(int(T["kinds"][pk]), phyp[:-1], Xt),
+                  noise_prior=float(np.exp(2 * phyp[-1])), dkss_prior=dk.prior_dx(int(T["kinds"][pk]), phyp[:-1], Xt))
     d = Z["agg/dleaf"]
     return fam, T["mu"][sel], T["var"][sel], d[:, :D], d[:, D:], ent, kw, sel, leaf
 
@@ -128,7 +129,7 @@ def _case(kind, n, nt, D, seed):
     Xt = datagen.uniform(seed + 2, 0, nt * D).reshape((nt, D), order="F") * 1.2 - 0.1
     Xt[0] = X[n - 1]                    # Delta = 0
     ls = np.array([0.35, 0.5, 0.42])[:D] * np.sqrt(D) + (0.5 if kind in (2, 3) else 0.0)
-    nl = D if kind in pgd.ARD else 1
+    nl = D if kind in dk.ARD else 1
     loghyp = np.concatenate([np.log(ls[:nl]), [0.0 if kind in (2, 3) else 0.1]])
     return X, y, Xt, loghyp, float(np.log(0.1)), float(np.mean(y)) + 0.25
 
@@ -145,9 +146,9 @@ def test_dense_helper_against_central_differences(kind, D):
     1e-4 of the same scale."""
     X, y, Xt, loghyp, logNoise, mean = _case(kind, 40, 7, D, seed=7000 + 10 * kind + D)
     mu, var, dmu, dvar = pgd.moments(kind, loghyp, logNoise, X, y, mean, Xt)
-    il2, _ = pgd._params(kind, loghyp, D)
+    il2 = dk.unpack(kind, loghyp, D)[0]
     yscale = max(1.0, float(np.max(np.abs(y))))
-    vscale = np.maximum(1.0, pgd.prior_diag(kind, loghyp, Xt) + np.exp(2 * logNoise))
+    vscale = np.maximum(1.0, dk.prior_diag(kind, loghyp, Xt) + np.exp(2 * logNoise))
     worst = 0.0
     for d in range(D):
         ld = 1.0 / np.sqrt(il2[d])

@@ -1,5 +1,5 @@
 """GPU suite for the rational quadratic kernels (DSMGP kinds 9 and 10): Gram tiles, single leaves, log-marginal and LOO gradients
-(the shape's da included), input gradients and the predictive covariance against the dense restatement of tests/rq_dense.py,
+(the shape's da included), input gradients and the predictive covariance against the dense restatement of tests/dense_gp.py,
 the iso kind as the ARD kind with equal length-scales (bit for bit), gradients by central differences of the device's own
 log-marginal and LOO density at D up to 48 with duplicate training points, COPY / PREFIX leaves and masks, all eleven kinds in
 one context, a pooled context, whole models, a mixed kernel vector, train! and the refusals.  Tolerances come from
@@ -14,7 +14,9 @@ import deepstructuredmixtures_amd as dsm
 from deepstructuredmixtures_amd import hipabi, tree as ptree
 from deepstructuredmixtures_amd.datagen import uniform, normal, regression_data
 from oracle import spn as ospn
-from rq_dense import DenseGP, KINDS, ISO_RQ, ARD_RQ, is_ard, kernelmatrix as dense_K, load_cases, wsum as dense_w
+import dense_kernels as dk
+from dense_gp import DenseGP
+from test_rq_host import KINDS, ISO_RQ, ARD_RQ, is_ard, load_cases
 from pred_tolerance import EPS, mll_tol, moment_tol
 from loo_dense import loo_tol
 import predgrad_dense as pgd
@@ -41,7 +43,7 @@ def gram_tol(kind, logl, loga, x1, x2, Kd):
     (|dw| <= (D + 2) eps w, so |d log1p(w)| <= (D + 2) eps w / (1 + w) <= (D + 2) eps log1p(w) (1 + ...)), then log1p, the
     product with alpha and exp: |dK| / K <= about (D / 2 + 3) eps alpha log1p(w) + 8 eps per side."""
     D = x1.shape[1]
-    s = np.exp(loga) * np.log1p(dense_w(kind, logl, loga, x1, x2))
+    s = np.exp(loga) * np.log1p(dk.scaled_sqdist(kind, dk.pack(kind, logl, loga=loga), x1, x2) / (2.0 * np.exp(loga)))
     return np.abs(Kd) * ((D + 6) * EPS * s + 16 * EPS) + 1e-300
 
 
@@ -76,7 +78,7 @@ def _single(ctx, X, y, mean, kind, loghyp, logNoise):
 
 
 def _cond(g):
-    ev = np.linalg.eigvalsh(g.Lf @ g.Lf.T)
+    ev = np.linalg.eigvalsh(g.F @ g.F.T)
     return ev[-1] / ev[0]
 
 
@@ -85,7 +87,7 @@ def _ng(kind, D):
 
 
 def _dense(X, y, mean, kind, h, ln):
-    return DenseGP(X, y, mean, kind, h[:-2], h[-2], h[-1], ln)
+    return DenseGP(kind, np.append(h, ln), X, y, mean)
 
 
 @pytest.mark.parametrize("kind,D", list(itertools.product(KINDS, [1, 3, 8, 32, 33, 48])))
@@ -98,7 +100,7 @@ def test_kernel_matrix_against_the_dense_formula(ctx, kind, D):
         ctx.set_train(x1, np.zeros(n1))
         ctx.set_hyper(0, kind, list(ll) + [la, ls, 0.0])
         K = ctx.kernel_matrix(0, x1, x2)
-        Kd = dense_K(kind, ll, la, ls, x1, x2)
+        Kd = dk.value(kind, dk.pack(kind, ll, ls, la), x1, x2)
         tol = gram_tol(kind, ll, la, x1, x2, Kd)
         _ratio("gram", np.abs(K - Kd), tol)
         assert np.all(np.abs(K - Kd) <= tol)
@@ -118,7 +120,7 @@ def test_large_alpha_bound_on_device_values(ctx):
     ctx.set_hyper(0, ARD_RQ, list(ll) + [la, ls, 0.0])
     ctx.set_hyper(1, 4, list(ll) + [ls, 0.0])
     Kr, Ks = ctx.kernel_matrix(0, x, x), ctx.kernel_matrix(1, x, x)
-    r2 = 2.0 * 1e6 * dense_w(ARD_RQ, ll, la, x, x)
+    r2 = dk.scaled_sqdist(ARD_RQ, dk.pack(ARD_RQ, ll, loga=la), x, x)
     slack = Ks * ((D + 6) * EPS * r2 + 32 * EPS)
     assert np.all(Kr - Ks >= -slack)
     assert np.all(Kr - Ks <= Ks * np.expm1(r2 * r2 / 8e6) + slack)
@@ -443,7 +445,7 @@ def test_one_context_with_every_kind_equals_each_leaf_alone(ctx):
 
 
 def _dense_leaves(m, X, y):
-    return [DenseGP(X[lf.obs], y[lf.obs], lf.mean.m, lf.kernel.kind, lf.kernel.logl, lf.kernel.loga, lf.kernel.logs, lf.logNoise)
+    return [DenseGP(lf.kernel.kind, dk.pack(lf.kernel.kind, lf.kernel.logl, lf.kernel.logs, lf.kernel.loga, lf.logNoise), X[lf.obs], y[lf.obs], lf.mean.m)
             for lf in ptree.get_leaves(m.root)]
 
 

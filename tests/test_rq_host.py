@@ -1,5 +1,5 @@
 """Host-side tests of the rational quadratic kernels (kinds 9 and 10), no GPU: the kernel classes and their hyper-vector layout,
-getparams / setparams, the kind constants against the header, and the dense restatement of tests/rq_dense.py -- the reference of
+getparams / setparams, the kind constants against the header, and the dense restatement of tests/dense_gp.py -- the reference of
 tests/test_rq_gpu.py -- against the 50-digit references of tests/golden/gp_rq.npz, closed forms, central differences of its own log-marginal, LOO density and predictions, and the
 large-alpha bound against the product-form squared exponential."""
 import os
@@ -11,13 +11,24 @@ import pytest
 import deepstructuredmixtures_amd as dsm
 from deepstructuredmixtures_amd import kernels
 from deepstructuredmixtures_amd import model as M
+import dense_kernels as dk
 import loo_dense
 import loo_grad_dense as lgd
 import predgrad_dense as pgd
-from rq_dense import DenseGP, KINDS, ISO_RQ, ARD_RQ, is_ard, kernelmatrix, load_cases, wsum
+from dense_gp import DenseGP
 from pred_tolerance import EPS, mll_tol
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ISO_RQ, ARD_RQ = KINDS = dk.RQ
+
+
+def is_ard(kind):
+    return kind in dk.ARD
+
+
+def load_cases():
+    """The cases of tests/golden/gp_rq.npz (tests/golden/make_rq_golden.py), name -> dict of arrays and Python scalars."""
+    return {name: {f: v if v.ndim else v.item() for f, v in c.items()} for name, c in dk.load_cases("gp_rq.npz").items()}
 
 
 def test_hyper_vector_layout_and_round_trip():
@@ -102,11 +113,11 @@ def test_dense_restatement_against_50_digit_references(name):
     squared exponential at the same length-scales and sigma: |dk/dx_d| <= k |x_d - x'_d| / l_d^2 there and here)."""
     c = CASES[name]
     kind, cond, D = c["kind"], c["cond"], c["X"].shape[1]
-    g = DenseGP(c["X"], c["y"], c["mean"], kind, c["logl"], c["loga"], c["logs"], c["logNoise"])
+    g = DenseGP(kind, dk.pack(kind, c["logl"], c["logs"], c["loga"], c["logNoise"]), c["X"], c["y"], c["mean"])
     assert g.info == 0
     m = c["Kc"].shape[0]
-    assert np.allclose(kernelmatrix(kind, c["logl"], c["loga"], c["logs"], c["X"][:m], c["X"][:m]), c["Kc"], rtol=1e-13, atol=0)
-    assert np.allclose(kernelmatrix(kind, c["logl"], c["loga"], c["logs"], c["X"][:m], c["Xt"]), c["Kt"], rtol=1e-13, atol=0)
+    assert np.allclose(dk.value(kind, dk.pack(kind, c["logl"], c["logs"], c["loga"]), c["X"][:m], c["X"][:m]), c["Kc"], rtol=1e-13, atol=0)
+    assert np.allclose(dk.value(kind, dk.pack(kind, c["logl"], c["logs"], c["loga"]), c["X"][:m], c["Xt"]), c["Kt"], rtol=1e-13, atol=0)
     assert abs(g.mll() - c["mll"]) <= mll_tol(c["mll"], cond)
     mu, var = g.prediction(c["Xt"])
     tol = 64 * cond * EPS * max(1.0, float(np.max(np.abs(c["y"]))))
@@ -152,7 +163,7 @@ def test_closed_forms(kind):
     ls, la, ln = 0.2, np.log(0.3), np.log(0.5)
     x = np.array([[0.3, 0.7]])
     logl = np.log([0.4, 0.9]) if is_ard(kind) else np.log([0.4])
-    g = DenseGP(x, [1.5], 0.5, kind, logl, la, ls, ln)
+    g = DenseGP(kind, dk.pack(kind, logl, ls, la, ln), x, [1.5], 0.5)
     c = np.exp(2 * ls) + np.exp(2 * ln) + 1e-8
     assert g.K[0, 0] == np.exp(2 * ls)
     assert abs(g.mll() - (-(1.0 / c + np.log(c) + np.log(2 * np.pi)) / 2)) <= 4 * EPS * abs(g.mll())
@@ -160,18 +171,18 @@ def test_closed_forms(kind):
     assert np.allclose(g.grad(), ref, rtol=1e-14, atol=1e-16)
     a = np.array([[0.0], [0.1]])
     b = np.array([[0.5], [0.1], [2.0]])
-    K = kernelmatrix(kind, [np.log(0.4)], la, ls, a, b)
+    K = dk.value(kind, dk.pack(kind, [np.log(0.4)], ls, la), a, b)
     ref = np.exp(2 * ls) * (1.0 + (a - b.T) ** 2 / (2 * 0.3 * 0.16)) ** -0.3
     assert np.allclose(K, ref, rtol=1e-14, atol=0) and K[1, 1] == np.exp(2 * ls)
     X, _, logl = _case(kind, 40, 3, 5)
-    Ks = kernelmatrix(kind, logl, la, ls, X, X)
+    Ks = dk.value(kind, dk.pack(kind, logl, ls, la), X, X)
     assert np.array_equal(Ks, Ks.T) and np.all(np.diag(Ks) == np.exp(2 * ls))
 
 
 def test_iso_is_ard_with_equal_lengthscales_to_the_bit():
     X, y, _ = _case(ISO_RQ, 50, 4, 6)
-    a = DenseGP(X, y, 0.1, ARD_RQ, np.full(4, np.log(0.6)), 0.4, 0.1, -1.0)
-    i = DenseGP(X, y, 0.1, ISO_RQ, [np.log(0.6)], 0.4, 0.1, -1.0)
+    a = DenseGP(ARD_RQ, dk.pack(ARD_RQ, np.full(4, np.log(0.6)), 0.1, 0.4, -1.0), X, y, 0.1)
+    i = DenseGP(ISO_RQ, dk.pack(ISO_RQ, [np.log(0.6)], 0.1, 0.4, -1.0), X, y, 0.1)
     assert np.array_equal(a.K, i.K) and a.mll() == i.mll()
     ga, gi = a.grad(), i.grad()
     assert np.allclose(np.sum(ga[:4]), gi[0], rtol=1e-12) and np.array_equal(ga[4:], gi[1:])
@@ -186,7 +197,7 @@ def test_dense_gradients_are_finite_at_duplicate_points_and_match_central_differ
     h = np.concatenate([logl, [np.log(alpha), 0.1, np.log(0.3)]])
 
     def gp(v):
-        return DenseGP(X, y, 0.2, kind, v[:-3], v[-3], v[-2], v[-1])
+        return DenseGP(kind, v, X, y, 0.2)
 
     g0 = gp(h)
     ga, la = g0.grad(), g0.loo_grad()
@@ -216,10 +227,10 @@ def test_dense_gradients_are_finite_at_duplicate_points_and_match_central_differ
 def test_shape_derivative_is_nonpositive_and_quadratic_at_small_w():
     """dK/dlog alpha = k alpha (w / (1 + w) - log1p(w)) <= 0, and -k alpha w^2 / 2 to first order at small w."""
     X = np.array([[0.0], [1e-3], [0.5], [3.0]])
-    g = DenseGP(X, np.zeros(4), 0.0, ISO_RQ, [0.0], np.log(2.0), 0.0, -1.0)
-    dA = g.kernel_derivatives()[1]
+    g = DenseGP(ISO_RQ, dk.pack(ISO_RQ, [0.0], 0.0, np.log(2.0), -1.0), X, np.zeros(4), 0.0)
+    dA = dk.d_hyper(ISO_RQ, g.h, X)[1][1]
     assert np.all(dA <= 0.0) and dA[0, 0] == 0.0
-    w = wsum(ISO_RQ, [0.0], np.log(2.0), X[:1], X[1:2])[0, 0]
+    w = dk.scaled_sqdist(ISO_RQ, g.h, X[:1], X[1:2])[0, 0] / (2.0 * 2.0)
     assert abs(dA[0, 1] - (-g.K[0, 1] * 2.0 * w * w / 2)) <= 2 * w * abs(dA[0, 1]) + EPS * g.K[0, 1] * 2.0 * w
 
 
@@ -229,7 +240,7 @@ def test_large_alpha_limit_is_the_squared_exponential():
     rng = np.random.default_rng(9)
     X = rng.uniform(size=(80, 3))
     logl, ls, alpha = np.log([0.4, 0.6, 0.9]), 0.1, 1e6
-    Kr = kernelmatrix(ARD_RQ, logl, np.log(alpha), ls, X, X)
+    Kr = dk.value(ARD_RQ, dk.pack(ARD_RQ, logl, ls, np.log(alpha)), X, X)
     r2 = np.sum((X[:, None, :] - X[None, :, :]) ** 2 / np.exp(2 * logl), axis=2)
     Ks = np.exp(2 * ls) * np.exp(-0.5 * r2)
     slack = Ks * (16 * EPS * (1.0 + r2))

@@ -9,10 +9,11 @@ import pytest
 
 import scipy.linalg as sla
 
+import dense_gp
+import dense_kernels as dk
 import loo_dense
 import loo_grad_dense as lgd
 import predgrad_dense as pgd
-import rq_dense
 import sharing_tables as st
 import targets_dense as td
 import targets_grad_dense as tgd
@@ -247,14 +248,6 @@ def _targets(t):
     return np.asfortranarray(Y), mean, W
 
 
-def _cross_kernel(kind, h, A, B):
-    """k(a_r, b_c) in float64 for the four kinds of the tables; h without the noise."""
-    D = A.shape[1]
-    if kind == 10:
-        return rq_dense.kernelmatrix(kind, h[:D], h[D], h[D + 1], A, B)
-    return pgd.kernelmatrix(kind, h, A, B)
-
-
 def _dense(t, l, Y, mean, W):
     """The float64 dense restatement of every downstream call for leaf l, from SciPy's factor of K + (noise + 1e-8) I of the
     leaf's own rows, own targets and own mean: computed once per set and shared by the cells."""
@@ -275,37 +268,28 @@ def _dense(t, l, Y, mean, W):
     r["grad"] = (G[0], 2.0 * tgd.tolerance(G[:1], [1.0], cond))
     r["tgrad"] = (tgd.weighted(G, W[l]), 2.0 * tgd.tolerance(G, W[l], cond))
     # leave-one-out moments and density: tests/loo_dense.py
-    K, _ = tgd.kernel_and_derivatives(kind, h, Xl)
+    K, dKs = dk.d_hyper(kind, h, Xl)
     lmu, lvar, lpd = loo_dense.loo_dense(K, noise, yl, m)
     tm, tv, _, tsum = loo_dense.loo_tol(yl, lmu, lvar, np.diag(K), noise)
     r["loo"] = (lmu, 2.0 * tm, lvar, 2.0 * tv, float(np.sum(lpd)), 2.0 * tsum)
-    # LOO gradients: tests/loo_grad_dense.py on the true kernel derivatives (rq_dense's for ArdRQ)
-    if kind == 10:
-        dKs = rq_dense.DenseGP(Xl, yl, m, kind, h[:D], h[D], h[D + 1], logNoise).kernel_derivatives()
-    else:
-        dKs = lgd.kernel_derivatives(kind, h, Xl)
+    # LOO gradients: tests/loo_grad_dense.py on the true kernel derivatives
     lg = lgd.loo_grad_dense(K, dKs, noise, yl, m)
     r["loograd"] = (lg, 2.0 * lgd.tolerance(dict(kind=kind, cond=cond, weak=False, logNoise=logNoise), lg))
     # targets: tests/targets_dense.py on the dense factor
-    F = sla.cholesky(K + (noise + 1e-8) * np.eye(n), lower=True)
-    Ktn = _cross_kernel(kind, h, Xr, Xl) if Xr.shape[0] else None
+    F = dense_gp.factor(K, noise)
+    Ktn = dk.value(kind, h, Xr, Xl) if Xr.shape[0] else None
     Z, tmll, tmu = td.reference(F, Yl, mean[l], Ktn)
     r["targets"] = (Z, 2.0 * td.z_tol(Z, cond), tmll, 2.0 * td.mll_tol(Z, F, cond), tmu,
                     None if tmu is None else 2.0 * td.mu_tol(tmu, Yl))
     if Xr.shape[0]:
         # full predictive covariance: as tests/test_predcov_gpu.py
         V = sla.solve_triangular(F, Ktn.T, lower=True)
-        S = _cross_kernel(kind, h, Xr, Xr) - V.T @ V
+        S = dk.value(kind, h, Xr, Xr) - V.T @ V
         kss = st.prior_diag(kind, hyp, Xr)
         r["cov"] = (S, 2.0 * entry_tol(S, kss, noise), noise)
-        # input gradients: tests/predgrad_dense.py (rq_dense's for ArdRQ, with the scales of an ARD stationary kind: 1 / l_d)
-        if kind == 10:
-            dmu, dvar = rq_dense.DenseGP(Xl, yl, m, kind, h[:D], h[D], h[D + 1], logNoise).input_gradients(Xr)
-            tk, th = 8, np.concatenate([h[:D], [h[D + 1]]])
-        else:
-            _, _, dmu, dvar = pgd.moments(kind, h, logNoise, Xl, yl, m, Xr)
-            tk, th = kind, h
-        tdm, tdv = pgd.tolerances(tk, th, logNoise, Xl, yl, Xr, dmu, dvar)
+        # input gradients: tests/predgrad_dense.py
+        _, _, dmu, dvar = pgd.moments(kind, h, logNoise, Xl, yl, m, Xr)
+        tdm, tdv = pgd.tolerances(kind, h, logNoise, Xl, yl, Xr, dmu, dvar)
         r["pgrad"] = (dmu, 2.0 * tdm, dvar, 2.0 * tdv)
     _DENSE[key] = r
     return r

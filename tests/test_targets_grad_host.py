@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import deepstructuredmixtures_amd as dsm
+import dense_kernels as dk
 import targets_grad_context as tgc
 import targets_grad_dense as tgd
 from deepstructuredmixtures_amd import hipabi
@@ -64,7 +65,7 @@ def test_fixture_covers_the_cases_the_feature_names():
     for c in CASES.values():
         Q = c["Y"].shape[1]
         assert c["grad"].shape == (Q, c["hyp"].size) and np.array_equal(c["w"], tgd.signed_weights(Q))
-        assert c["hyp"].size == tgd.n_hyper(int(c["kind"]), c["X"].shape[1])
+        assert c["hyp"].size == dk.n_hyper(int(c["kind"]), c["X"].shape[1])
     assert os.path.getsize(os.path.join(GOLDEN, "gp_targets_grad.npz")) < (1 << 20)
 
 

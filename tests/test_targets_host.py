@@ -9,9 +9,10 @@ import subprocess
 
 import numpy as np
 import pytest
-import scipy.linalg as sla
 
 import deepstructuredmixtures_amd as dsm
+import dense_gp
+import dense_kernels as dk
 import targets_dense as td
 from deepstructuredmixtures_amd import hipabi
 from oracle import gp as ogp
@@ -110,24 +111,17 @@ def test_fixture_covers_the_cases_the_feature_names():
 
 
 def _kernel_matrix(c, A, B):
-    """The kernel of a fixture case in float64 (kinds 0, 2 through the oracle, ArdMatern52 written out)."""
+    """The kernel of a fixture case in float64 (kinds 0, 2 through the oracle, ArdMatern52 from tests/dense_kernels.py)."""
     h = c["loghyp"]
     if c["kind"] in (0, 2):
         return ogp.kernelmatrix(ogp.make_kernel(c["kind"], h), A, B, True)
-    D = A.shape[1]
-    il = np.exp(-h[:D])
-    d = (A[:, None, :] - B[None, :, :]) * il[None, None, :]
-    s = np.sqrt(5.0 * np.sum(d * d, axis=2))
-    return math.exp(2.0 * h[D]) * (1.0 + s + s * s / 3.0) * np.exp(-s)
+    return dk.value(c["kind"], h, A, B)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_dense_helper_against_50_digits(name):
     c = CASES[name]
-    n = c["X"].shape[0]
-    Ky = _kernel_matrix(c, c["X"], c["X"])
-    Ky[np.diag_indices(n)] += math.exp(2.0 * c["logNoise"]) + 1e-8
-    F = sla.cholesky(Ky, lower=True)
+    F = dense_gp.factor(_kernel_matrix(c, c["X"], c["X"]), math.exp(2.0 * c["logNoise"]))
     cond = td.factor_cond(F)
     assert 0.5 <= cond / c["cond"] <= 2.0
     Z, mll, mu = td.reference(F, c["Y"], c["mean"], _kernel_matrix(c, c["Xt"], c["X"]))
