@@ -711,6 +711,8 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     double timings[DSMGP_N_TIMINGS] = {0};
     std::vector<hipEvent_t> event_pool;   // PhaseTimer's events, reused across calls
     double alg_flops_update = 0.0;  // algorithmic flops of the Cholesky update launches
+    int64_t append_stats[DSMGP_N_APPEND_STATS] = {0, 0, 0, 0, 0, 0};
+    bool have_append_stats = false;
     double alg_flops_fused = 0.0, alg_flops_fused_joint = 0.0;   // ... of the fused tile launches (update + solve), fit alone / joint
     int n_fused_launches = 0;
     int n_update_launches = 0;
@@ -1646,17 +1648,11 @@ int build_factor_steps(dsmgp_ctx* c, int lane, bool with_test, StepLists (&phase
     return 0;
 }
 
-// Build arenas, the LeafDev table and every task list for the current leaf table + sharing schedule, unless they are current.
-int build_plan(dsmgp_ctx* c) {
-    if (c->has(P_PLAN)) return 0;
-    HostLog hl_total("build_plan");
-    {
-        HostLog hl("build_plan: free_plan");
-        free_plan(c);
-    }
+int build_schedule(dsmgp_ctx* c);
+// Who owns which factor, how many leading blocks a PREFIX leaf keeps, and where every leaf's buffers sit in the plan's arenas
+void plan_layout(dsmgp_ctx* c, size_t& fTot, size_t& dTot, size_t& vTot, size_t& xTot) {
     const int L = c->L;
-    if (L == 0) return fail(c, DSMGP_E_STATE, "no leaves set");
-    size_t fTot = 0, dTot = 0, vTot = 0, xTot = 0;
+    fTot = dTot = vTot = xTot = 0;
     for (int l = 0; l < L; ++l) {
         LeafHost& lf = c->leaves[l];
         lf.owner = (lf.op == DSMGP_SHARE_COPY) ? lf.src : l;
@@ -1686,18 +1682,41 @@ int build_plan(dsmgp_ctx* c) {
             lf.dinv_off = c->leaves[lf.owner].dinv_off;
         }
     }
+}
+
+// Build arenas, the LeafDev table and every task list for the current leaf table + sharing schedule, unless they are current.
+// adoptF / adoptDinv (dsmgp_append_rows in place): the factor and Dinv arenas of the previous plan, whose layout is this plan's; they
+// become c->arenaF / c->arenaDinv instead of new allocations -- the context owns them from that assignment on, the caller until then.
+int build_plan(dsmgp_ctx* c, double* adoptF = nullptr, double* adoptDinv = nullptr) {
+    if (c->has(P_PLAN)) return 0;
+    HostLog hl_total("build_plan");
+    {
+        HostLog hl("build_plan: free_plan");
+        free_plan(c);
+    }
+    const int L = c->L;
+    if (L == 0) return fail(c, DSMGP_E_STATE, "no leaves set");
+    size_t fTot = 0, dTot = 0, vTot = 0, xTot = 0;
+    plan_layout(c, fTot, dTot, vTot, xTot);
     c->bytes_needed = (fTot + dTot + vTot + xTot) * sizeof(double);
     size_t freeB = 0, totalB = 0;
     HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
-    if (!c->pool_base && c->bytes_needed + (size_t(1) << 30) > freeB)
+    // (dsmgp_append_rows in place: the factor and Dinv arenas of the previous plan are taken over, they are allocated already)
+    const bool adopt = adoptF != nullptr && adoptDinv != nullptr;
+    if (!c->pool_base && c->bytes_needed - (adopt ? (fTot + dTot) * sizeof(double) : 0) + (size_t(1) << 30) > freeB)
         return fail(c, DSMGP_E_NOMEM, "leaf table needs " + std::to_string(c->bytes_needed >> 20) + " MiB, device has " +
                                           std::to_string(freeB >> 20) + " MiB free");
     {
         HostLog hl("build_plan: arenas");
-        if (int rc = arena_get(c, c->arenaF, fTot)) return rc;
-        if (int rc = arena_get(c, c->arenaDinv, dTot)) return rc;
-        // the diagonal-block kernel writes the lower blocks of Dinv_k only: the blocks above the diagonal are zero from here on
-        HIPCHK(c, hipMemsetAsync(c->arenaDinv, 0, std::max<size_t>(1, dTot) * sizeof(double), c->stream));
+        if (adopt) {
+            c->arenaF = adoptF;
+            c->arenaDinv = adoptDinv;
+        } else {
+            if (int rc = arena_get(c, c->arenaF, fTot)) return rc;
+            if (int rc = arena_get(c, c->arenaDinv, dTot)) return rc;
+            // the diagonal-block kernel writes the lower blocks of Dinv_k only: the blocks above the diagonal are zero from here on
+            HIPCHK(c, hipMemsetAsync(c->arenaDinv, 0, std::max<size_t>(1, dTot) * sizeof(double), c->stream));
+        }
         if (int rc = arena_get(c, c->arenaVec, vTot)) return rc;
         if (int rc = arena_get(c, c->arenaXg, xTot)) return rc;
     }
@@ -1785,6 +1804,18 @@ int build_plan(dsmgp_ctx* c) {
         HIPCHK(c, e2);
     }
 
+    if (int rc = build_schedule(c)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mark(P_PLAN);
+    c->pool_mark_plan = c->pool_top;
+    return 0;
+}
+
+// The part of the plan that depends on the sharing schedule alone, not on where the arenas are: phases, lanes, how every block step
+// runs, the Gram list, the Dinv completions and the solve sweeps.  dsmgp_append_rows builds it twice over the same arenas: once with
+// its one-shot continuation marks, once with the schedule it leaves behind.
+int build_schedule(dsmgp_ctx* c) {
+    const int L = c->L;
     // Phases: PREFIX leaves run after their sources (phase 1), everything else in phase 0 (COPY leaves ride with their source).
     // (Round 3 also built a split of the phase-0 leaves into two groups whose fused steps ran merged -- one launch carrying the
     // diagonal blocks of one group next to the tiles of the other, so that a CU mostly holds one latency-bound and one
@@ -1869,8 +1900,11 @@ int build_plan(dsmgp_ctx* c) {
             if (fused && !fs.empty() && fs[0] != STEP_CLASSIC) continue;
         }
         const LeafDev& d = c->h_leaves[l];
+        // (a leaf that continues from its OWN kept blocks -- dsmgp_append_rows, src == l -- may hold them in place: no tile of the
+        // kept square is written; a PREFIX leaf proper gets its copy after this launch)
+        const bool keeps_own = lf.op == DSMGP_SHARE_PREFIX && lf.src == l;
         for (int j = 0; j < (fused ? 1 : lf.nb); ++j)
-            for (int i = (fused ? std::max(j, lf.kb) : j); i < lf.nb; ++i) {
+            for (int i = ((fused || keeps_own) ? std::max(j, lf.kb) : j); i < lf.nb; ++i) {
                 GramTask g{};
                 g.xa = d.Xg + (size_t)i * TB;
                 g.xb = d.Xg + (size_t)j * TB;
@@ -2006,9 +2040,6 @@ int build_plan(dsmgp_ctx* c) {
         if (int rc = dev_upload(c, c->fwd, fwd)) return rc;
         if (int rc = dev_upload(c, c->bwd, bwd)) return rc;
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->mark(P_PLAN);
-    c->pool_mark_plan = c->pool_top;
     return 0;
 }
 
@@ -2683,6 +2714,305 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
     if (joint) c->mark(P_VT);
     c->vt_from_fit = joint;
     c->last_fit_joint = joint;
+    return 0;
+}
+
+// Append training rows to the fitted model: every factor owner keeps the leading blocks of the factor it had and continues
+// from them, through the PREFIX phase of the fit with the leaf's OWN old factor as the source (include/dsmgp_hip.h).
+int dsmgp_append_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int64_t m, int32_t D, const int64_t* add_ptr,
+                      const int64_t* add_idx, const double* mean, double* mll_out, int32_t* info_out, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "append_rows needs a current fit");
+    if (c->pool_base) return fail(c, DSMGP_E_STATE, "append_rows under a reserved pool");
+    if (!X_new || !y_new || !add_ptr || !add_idx || m < 1) return fail(c, DSMGP_E_ARG, "append_rows: bad arguments");
+    if (D != c->D) return fail(c, DSMGP_E_ARG, "append_rows: D is not the D of set_train");
+    const int L = c->L;
+    const int64_t N0 = c->N;
+    if (add_ptr[0] != 0) return fail(c, DSMGP_E_ARG, "append_rows: add_ptr[0] must be 0");
+    for (int l = 0; l < L; ++l) {
+        const int64_t a = add_ptr[l], b = add_ptr[l + 1];
+        if (b < a) return fail(c, DSMGP_E_ARG, "append_rows: add_ptr must not descend");
+        if (b - a > m) return fail(c, DSMGP_E_ARG, "append_rows: a list that is not strictly ascending");
+        if ((int64_t)c->leaves[l].n + (b - a) > (int64_t)1 << 20) return fail(c, DSMGP_E_ARG, "append_rows: leaf too large");
+        for (int64_t i = a; i < b; ++i) {
+            if (add_idx[i] < 0 || add_idx[i] >= m) return fail(c, DSMGP_E_ARG, "append_rows: position out of range");
+            if (i > a && add_idx[i] <= add_idx[i - 1]) return fail(c, DSMGP_E_ARG, "append_rows: lists must be strictly ascending");
+        }
+    }
+    for (int64_t i = 0; i < m * (int64_t)D; ++i)
+        if (!std::isfinite(X_new[i])) return fail(c, DSMGP_E_ARG, "append_rows: non-finite value in X_new");
+    for (int64_t i = 0; i < m; ++i)
+        if (!std::isfinite(y_new[i])) return fail(c, DSMGP_E_ARG, "append_rows: non-finite value in y_new");
+    if (mean)
+        for (int l = 0; l < L; ++l)
+            if (!std::isfinite(mean[l])) return fail(c, DSMGP_E_ARG, "append_rows: non-finite mean");
+    HIPCHK(c, hipSetDevice(c->device));
+
+    // 1. what the kept blocks need before they are read again: every Dinv_k whole (the fused steps of the fit left the 16x16
+    //    inverses only), and who failed (their kept blocks are damaged: factorised from block 0)
+    if (int rc = ensure_dinv(c)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int> old_info((size_t)L);
+    HIPCHK(c, hipMemcpy(old_info.data(), c->d_info.p, (size_t)L * sizeof(int), hipMemcpyDeviceToHost));
+
+    // 2. the grown data beside the old: nothing of the context has changed if it does not fit
+    DevBuf<double> nX, ny;
+    {
+        DevBuf<double> aX, ay;
+        // (the message says so: a caller that mirrors the table's sizes -- hipabi.Context -- tells this DSMGP_E_NOMEM from the later one)
+        auto unchanged = [&](int rc) { return fail(c, rc, "append_rows: the grown data do not fit, the context is unchanged (" + c->err + ")"); };
+        if (int rc = aX.alloc(c, (size_t)m * D)) return unchanged(rc);
+        if (int rc = ay.alloc(c, (size_t)m)) return unchanged(rc);
+        if (int rc = nX.alloc(c, (size_t)(N0 + m) * D)) return unchanged(rc);
+        if (int rc = ny.alloc(c, (size_t)(N0 + m))) return unchanged(rc);
+        HIPCHK(c, hipMemcpy(aX.p, X_new, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(ay.p, y_new, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+        const long long total = (long long)(N0 + m) * D;
+        const int grid = (int)std::min<long long>((total + 255) / 256, 65536);
+        append_rows_kernel<<<grid, 256, 0, c->stream>>>(c->dX.p, aX.p, nX.p, (long long)N0, (long long)m, D);
+        append_rows_kernel<<<grid, 256, 0, c->stream>>>(c->dy.p, ay.p, ny.p, (long long)N0, (long long)m, 1);
+        const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
+        HIPCHK(c, e1);
+        HIPCHK(c, e2);
+    }
+
+    // 3. the previous plan: where every factor sits, and the arenas themselves (taken out of the context: free_plan leaves them)
+    struct Old { size_t f_off, dinv_off; int n, npad, nb, owner, op, src; double mean; };
+    std::vector<Old> old((size_t)L);
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        old[(size_t)l] = Old{lf.f_off, lf.dinv_off, lf.n, lf.npad, lf.nb, lf.owner, lf.op, lf.src, lf.mean};
+    }
+    double* oldF = c->arenaF;
+    double* oldDinv = c->arenaDinv;
+    c->arenaF = c->arenaDinv = nullptr;
+    free_plan_and_test(c);          // (the routing tree stays: leaf indices do not change)
+    c->grad_active.clear();
+
+    // 4. the grown leaf table and the schedule it keeps: COPY where source and leaf got the same rows, FULL elsewhere
+    auto adds_of = [&](int l) { return add_ptr[l + 1] - add_ptr[l]; };
+    auto same_adds = [&](int a, int b) {
+        return adds_of(a) == adds_of(b) &&
+               (adds_of(a) == 0 || std::memcmp(add_idx + add_ptr[a], add_idx + add_ptr[b], sizeof(int64_t) * (size_t)adds_of(a)) == 0);
+    };
+    {
+        std::vector<int64_t> ptr((size_t)L + 1, 0), idx;
+        idx.reserve(c->obs_idx.size() + (size_t)add_ptr[L]);
+        for (int l = 0; l < L; ++l) {
+            LeafHost& lf = c->leaves[l];
+            idx.insert(idx.end(), c->obs_idx.begin() + lf.obs_off, c->obs_idx.begin() + lf.obs_off + lf.n);
+            for (int64_t i = add_ptr[l]; i < add_ptr[l + 1]; ++i) idx.push_back(N0 + add_idx[i]);
+            ptr[(size_t)l + 1] = (int64_t)idx.size();
+        }
+        for (int l = 0; l < L; ++l) {
+            LeafHost& lf = c->leaves[l];
+            lf.obs_off = ptr[(size_t)l];
+            lf.n = (int)(ptr[(size_t)l + 1] - ptr[(size_t)l]);
+            lf.npad = round_up(lf.n, TB);
+            lf.nb = lf.npad / TB;
+            if (mean) lf.mean = mean[l];
+        }
+        c->obs_ptr.swap(ptr);
+        c->obs_idx.swap(idx);
+    }
+    c->dX = std::move(nX);
+    c->dy = std::move(ny);
+    c->N = N0 + m;
+    int64_t st[DSMGP_N_APPEND_STATS] = {0, 0, 0, 0, 0, 0};
+    std::vector<char> stays_copy((size_t)L, 0);
+    for (int l = 0; l < L; ++l)
+        if (old[(size_t)l].op == DSMGP_SHARE_COPY) {
+            stays_copy[(size_t)l] = same_adds(l, old[(size_t)l].src) ? 1 : 0;
+            if (!stays_copy[(size_t)l]) st[5]++;
+        }
+    auto final_schedule = [&]() {       // what later fits run under
+        for (int l = 0; l < (int)c->leaves.size(); ++l) {
+            LeafHost& lf = c->leaves[l];
+            lf.op = stays_copy[(size_t)l] ? DSMGP_SHARE_COPY : DSMGP_SHARE_FULL;
+            lf.src = stays_copy[(size_t)l] ? old[(size_t)l].src : -1;
+            lf.prefix = 0;
+        }
+    };
+    // whatever goes wrong from here on: the grown data and leaf table, no plan, no fit -- as after dsmgp_set_leaves
+    auto give_up = [&](int rc) {
+        const std::string msg = c->err;
+        if (oldF && c->arenaF == oldF) oldF = oldDinv = nullptr;    // build_plan took them over (in place): free_plan puts them back
+        (void)hipStreamSynchronize(c->stream);
+        free_plan_and_test(c);
+        if (oldF) (void)hipFree(oldF);
+        if (oldDinv) (void)hipFree(oldDinv);
+        final_schedule();
+        c->err = msg;
+        return rc;
+    };
+    // ... except where the device copy of the grown leaf table itself cannot be made: a plan must never gather through a missing
+    // or stale copy, so the leaf table goes (the grown data stay; dsmgp_set_leaves is the next call, anything else: DSMGP_E_STATE)
+    auto without_table = [&](int rc) {
+        give_up(rc);
+        c->L = 0;
+        c->leaves.clear();
+        c->obs_ptr.clear();
+        c->obs_idx.clear();
+        c->d_obs_ptr.release();
+        c->d_obs_idx.release();
+        return rc;
+    };
+    c->d_obs_ptr.release();
+    c->d_obs_idx.release();
+    if (int rc = c->d_obs_ptr.alloc(c, (size_t)L + 1)) return without_table(rc);
+    if (int rc = c->d_obs_idx.grow(c, c->obs_idx.size(), std::max<size_t>(1, c->obs_idx.size()))) return without_table(rc);
+    if (hipMemcpy(c->d_obs_ptr.p, c->obs_ptr.data(), ((size_t)L + 1) * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_obs_idx.p, c->obs_idx.data(), c->obs_idx.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess)
+        return without_table(fail(c, DSMGP_E_HIP, "append_rows: upload of the leaf table failed"));
+
+    // 5. this call's one-shot marks: an owner that keeps blocks is a PREFIX leaf whose source is its own old factor (phase 1, z
+    //    from the forward sweep); kb = every block for a leaf without additions, floor(n_old / 128) otherwise
+    final_schedule();
+    for (int l = 0; l < L; ++l) {
+        LeafHost& lf = c->leaves[l];
+        if (lf.op != DSMGP_SHARE_FULL) continue;
+        const Old& mine = old[(size_t)l];
+        const Old& from = old[(size_t)mine.owner];
+        const int keep = old_info[(size_t)mine.owner] != 0 ? 0 : (adds_of(l) == 0 ? from.nb : from.n / TB);
+        if (keep > 0) {
+            lf.op = DSMGP_SHARE_PREFIX;
+            lf.src = l;
+            lf.prefix = (int64_t)keep * TB;
+        }
+        if (keep == 0) st[4]++;
+        else if (keep < lf.nb) st[0]++;
+        st[3] += lf.nb - keep;
+    }
+    bool in_place = true;
+    {
+        size_t a = 0, b = 0, v = 0, x = 0;
+        plan_layout(c, a, b, v, x);
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            const Old& o = old[(size_t)l];
+            if (lf.owner != o.owner || lf.npad != o.npad || lf.f_off != o.f_off || lf.dinv_off != o.dinv_off) in_place = false;
+        }
+    }
+    // (the lane deal of this plan weighs every owner by n^3 as a fit would, although a continuing owner costs O(n 128 n) and an
+    // untouched one nothing: the lanes of this one call may be unevenly loaded -- speed only, and the lists are rebuilt below)
+    if (int rc = in_place ? build_plan(c, oldF, oldDinv) : build_plan(c)) return give_up(rc);
+    if (int rc = upload_hyper(c)) return give_up(rc);
+    if (int rc = ensure_phase(c)) return give_up(rc);      // this call's step lists: dropped below
+
+    // 6. the kept blocks of every continuing owner, old arenas -> new ones: one task list, one launch
+    DevBuf<RelocTask> reloc;
+    if (!in_place) {
+        std::vector<RelocTask> rt;
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            if (lf.op != DSMGP_SHARE_PREFIX) continue;
+            const Old& from = old[(size_t)old[(size_t)l].owner];
+            const LeafDev& d = c->h_leaves[l];
+            for (int j = 0; j < lf.kb; ++j) {
+                for (int i = 0; i < lf.kb; ++i)
+                    rt.push_back(RelocTask{oldF + from.f_off + (size_t)i * TB + (size_t)j * TB * from.npad,
+                                           d.F + (size_t)i * TB + (size_t)j * TB * lf.npad, from.npad, lf.npad});
+                rt.push_back(RelocTask{oldDinv + from.dinv_off + (size_t)j * TB * TB, d.Dinv + (size_t)j * TB * TB, TB, TB});
+            }
+        }
+        st[2] = (int64_t)rt.size() * TB * TB * (int64_t)sizeof(double);
+        if (int rc = dev_upload(c, reloc, rt)) return give_up(rc);
+    } else {
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            const int o = lf.owner;
+            if (adds_of(l) == 0 && adds_of(o) == 0 && lf.mean == old[(size_t)l].mean && old_info[(size_t)old[(size_t)l].owner] == 0) st[1]++;
+        }
+    }
+
+    // 7. the launches of a fit, the relocation between its phases
+    for (int i = 0; i < 6; ++i) c->timings[i] = 0.0;
+    c->timings[11] = c->timings[13] = c->timings[14] = 0.0;
+    c->timings[18] = c->timings[19] = c->timings[20] = 0.0;
+    c->n_update_launches = 0;
+    c->n_fused_launches = 0;
+    PhaseTimer pt(c);
+    EventPair ev;
+    if (ev.init() != hipSuccess) return give_up(fail(c, DSMGP_E_HIP, "append_rows: hipEventCreate failed"));
+    auto enqueue = [&]() -> int {
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_info.p, 0, (size_t)L * sizeof(int), c->stream));
+        pt.begin(0);
+        if (c->gram.count) gram_tile_kernel<<<2 * (int)c->gram.count, 256, 0, c->stream>>>(c->gram.p, c->d_kp.p, c->D);
+        pt.end();
+        int maxpad = 0;
+        for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
+        copy_vec_kernel<<<dim3((maxpad + 255) / 256, L), 256, 0, c->stream>>>(c->d_leaves.p);
+        if (int rc = run_lanes(c, c->phase, 0, pt, true)) return rc;      // owners without kept blocks (may be empty)
+        if (reloc.count) relocate_tiles_kernel<<<(unsigned)reloc.count, 256, 0, c->stream>>>(reloc.p);
+        if (int rc = run_lanes(c, c->phase, 1, pt, true)) return rc;      // the continuations
+        pt.begin(4);
+        if (c->dinvc_fwd.count)
+            dinv_complete_kernel<<<(int)c->dinvc_fwd.count, 256, DIAGP_LDS_BYTES, c->stream>>>(c->dinvc_fwd.p);
+        for (int k = 0; k < c->solve_steps; ++k) {
+            const int n = c->fwd_off[k + 1] - c->fwd_off[k];
+            if (n > 0) solve_fwd_kernel<<<n, 256, 0, c->stream>>>(c->fwd.p + c->fwd_off[k]);
+        }
+        pt.end();
+        pt.begin(5);
+        mll_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->d_mll.p);
+        pt.end();
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return 0;
+    };
+    if (int rc = enqueue()) {
+        pt.collect();
+        return give_up(rc);
+    }
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+    pt.collect(ev.a);
+    c->timings[11] = ms * 1e-3;
+    if (seconds) *seconds = ms * 1e-3;
+    if (!in_place) {        // the old factors have been read for the last time
+        (void)hipFree(oldF);
+        (void)hipFree(oldDinv);
+    }
+    oldF = oldDinv = nullptr;
+    // (a failure from here on still goes through give_up: the one-shot marks never outlive the call)
+    auto hip_failed = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess) return false;
+        c->err = std::string(what) + ": " + hipGetErrorString(e);
+        return true;
+    };
+    if (mll_out && hip_failed(hipMemcpy(mll_out, c->d_mll.p, (size_t)L * sizeof(double), hipMemcpyDeviceToHost), "append_rows: mll"))
+        return give_up(DSMGP_E_HIP);
+    if (info_out) {
+        std::vector<int> owner_info((size_t)L);
+        if (hip_failed(hipMemcpy(owner_info.data(), c->d_info.p, (size_t)L * sizeof(int), hipMemcpyDeviceToHost), "append_rows: info"))
+            return give_up(DSMGP_E_HIP);
+        for (int l = 0; l < L; ++l) info_out[l] = owner_info[(size_t)c->leaves[l].owner];
+    }
+    c->mark(P_FIT);
+    c->vt_from_fit = false;
+    c->last_fit_joint = false;
+    // 8. the marks go: the blocks this call's fused steps left without their whole inverse are completed under ITS lists, then
+    //    the schedule lists are rebuilt as the next fit needs them (COPY where kept, FULL elsewhere) and the step lists dropped
+    if (int rc = ensure_dinv(c)) return give_up(rc);
+    if (hip_failed(hipStreamSynchronize(c->stream), "append_rows: hipStreamSynchronize")) return give_up(DSMGP_E_HIP);
+    final_schedule();
+    {
+        size_t a = 0, b = 0, v = 0, x = 0;
+        plan_layout(c, a, b, v, x);
+    }
+    if (int rc = build_schedule(c)) return give_up(rc);
+    c->invalidate(P_PHASE);
+    for (int i = 0; i < DSMGP_N_APPEND_STATS; ++i) c->append_stats[i] = st[i];
+    c->have_append_stats = true;
+    return 0;
+}
+
+int dsmgp_append_stats(dsmgp_ctx* c, int64_t* out) {
+    if (!c || !out) return DSMGP_E_ARG;
+    if (!c->have_append_stats) return fail(c, DSMGP_E_STATE, "append_stats before append_rows");
+    for (int i = 0; i < DSMGP_N_APPEND_STATS; ++i) out[i] = c->append_stats[i];
     return 0;
 }
 
@@ -5768,6 +6098,65 @@ int dsmgp_probe_diag_fused(dsmgp_ctx* c, int32_t ntiles, int32_t K, int32_t reps
     int bad = 0;
     HIPCHK(c, hipMemcpy(&bad, info.p, sizeof(int), hipMemcpyDeviceToHost));
     if (bad != 0) return fail(c, DSMGP_E_STATE, "probe block was not positive definite");
+    return 0;
+}
+
+// diagnostic: the kept blocks of `nleaves` leaves of kb x kb blocks each, from factors of leading dimension ld_old into factors of
+// leading dimension ld_new (and their kb Dinv blocks), three ways: out[0] = seconds of the ONE relocate_tiles_kernel launch of
+// dsmgp_append_rows, out[1] = of one device-to-device hipMemcpy of the same byte count (contiguous: the ceiling), out[2] = of the
+// hipMemcpy2DAsync + hipMemcpyAsync pair per leaf the PREFIX phase of dsmgp_fit issues, out[3] = bytes moved.  Best of `reps`.
+int dsmgp_bench_relocate(dsmgp_ctx* c, int32_t nleaves, int32_t kb, int32_t ld_old, int32_t ld_new, int32_t reps, double* out) {
+    if (!c || !out || nleaves < 1 || kb < 1 || reps < 1 || ld_old < kb * TB || ld_new < kb * TB || ld_old % TB || ld_new % TB)
+        return DSMGP_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t fo = (size_t)ld_old * ld_old, fn = (size_t)ld_new * ld_new, dv = (size_t)kb * TB * TB;
+    DevBuf<double> Fo, Fn, Do, Dn;
+    if (int rc = Fo.alloc(c, fo * nleaves)) return rc;
+    if (int rc = Fn.alloc(c, fn * nleaves)) return rc;
+    if (int rc = Do.alloc(c, dv * nleaves)) return rc;
+    if (int rc = Dn.alloc(c, dv * nleaves)) return rc;
+    HIPCHK(c, hipMemset(Fo.p, 0, fo * nleaves * sizeof(double)));
+    HIPCHK(c, hipMemset(Do.p, 0, dv * nleaves * sizeof(double)));
+    std::vector<RelocTask> rt;
+    for (int l = 0; l < nleaves; ++l)
+        for (int j = 0; j < kb; ++j) {
+            for (int i = 0; i < kb; ++i)
+                rt.push_back(RelocTask{Fo.p + l * fo + (size_t)i * TB + (size_t)j * TB * ld_old,
+                                       Fn.p + l * fn + (size_t)i * TB + (size_t)j * TB * ld_new, ld_old, ld_new});
+            rt.push_back(RelocTask{Do.p + l * dv + (size_t)j * TB * TB, Dn.p + l * dv + (size_t)j * TB * TB, TB, TB});
+        }
+    DevBuf<RelocTask> tasks;
+    if (int rc = dev_upload(c, tasks, rt)) return rc;
+    const size_t bytes = rt.size() * TB * TB * sizeof(double);
+    DevBuf<double> flat_a, flat_b;
+    if (int rc = flat_a.alloc(c, bytes / sizeof(double))) return rc;
+    if (int rc = flat_b.alloc(c, bytes / sizeof(double))) return rc;
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    const size_t rows = (size_t)kb * TB;
+    out[0] = out[1] = out[2] = 1e30;
+    for (int r = 0; r <= reps; ++r)         // (pass 0 warms up)
+        for (int way = 0; way < 3; ++way) {
+            HIPCHK(c, hipEventRecord(ev.a, c->stream));
+            if (way == 0) {
+                relocate_tiles_kernel<<<(unsigned)tasks.count, 256, 0, c->stream>>>(tasks.p);
+            } else if (way == 1) {
+                HIPCHK(c, hipMemcpyAsync(flat_b.p, flat_a.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+            } else {
+                for (int l = 0; l < nleaves; ++l) {
+                    HIPCHK(c, hipMemcpy2DAsync(Fn.p + l * fn, (size_t)ld_new * sizeof(double), Fo.p + l * fo, (size_t)ld_old * sizeof(double),
+                                               rows * sizeof(double), rows, hipMemcpyDeviceToDevice, c->stream));
+                    HIPCHK(c, hipMemcpyAsync(Dn.p + l * dv, Do.p + l * dv, dv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+                }
+            }
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(ev.b, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            float ms = 0.f;
+            HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+            if (r > 0) out[way] = std::min(out[way], (double)ms * 1e-3);
+        }
+    out[3] = (double)bytes;
     return 0;
 }
 

@@ -3367,6 +3367,38 @@ __global__ void copy_vec_kernel(const LeafDev* __restrict__ leaves) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// dsmgp_append_rows
+// One 128 x 128 block of a kept factor -- between the leading dimension it had and the one it gets -- or one Dinv_k block
+// (lds = ldd = 128): every kept block of every leaf of a call is one task of ONE launch, one workgroup each.  A thread moves
+// 16 bytes at a time and the 64 threads of a wave 1 KB of a column; blocks start at multiples of 128 doubles and leading
+// dimensions are multiples of 128, so every access is 16-byte aligned.  src and dst never overlap (old and new arenas).
+struct RelocTask {
+    const double* src;
+    double* dst;
+    int lds, ldd;
+};
+__global__ __launch_bounds__(256) void relocate_tiles_kernel(const RelocTask* __restrict__ tasks) {
+    const RelocTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x;
+#pragma unroll 8
+    for (int it = 0; it < TB * TB / 2 / 256; ++it) {
+        const int e = it * 256 + t, col = e >> 6, r = 2 * (e & 63);
+        const d2 v = *AS_GLOBAL_D2(tk.src + (size_t)col * (size_t)tk.lds + r);
+        *reinterpret_cast<d2*>(tk.dst + (size_t)col * (size_t)tk.ldd + r) = v;
+    }
+}
+
+// Column-major N x D (ld = N) with m new rows (m x D, ld = m) appended below: out is (N + m) x D with ld = N + m
+__global__ __launch_bounds__(256) void append_rows_kernel(const double* __restrict__ old_, const double* __restrict__ add,
+                                                          double* __restrict__ out, long long N, long long m, int D) {
+    const long long ld = N + m, total = ld * (long long)D;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long d = i / ld, r = i - d * ld;
+        out[i] = r < N ? old_[r + d * N] : add[(r - N) + d * m];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // prediction helpers (src/gaussianprocess.jl:117-126), one workgroup per (leaf, 128-row test tile)
 struct PredTask {
     int leaf;

@@ -44,6 +44,8 @@ SIGNATURES = {
     "dsmgp_set_sharing": (C.c_int, [_ctx, _ip, _ip, _lp]),
     "dsmgp_set_hyper": (C.c_int, [_ctx, C.c_int32, C.c_int32, _dp, C.c_int32]),
     "dsmgp_fit": (C.c_int, [_ctx, _dp, _ip, _dp]),
+    "dsmgp_append_rows": (C.c_int, [_ctx, _dp, _dp, C.c_int64, C.c_int32, _lp, _lp, _dp, _dp, _ip, _dp]),
+    "dsmgp_append_stats": (C.c_int, [_ctx, _lp]),
     "dsmgp_set_test": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, _lp, _lp]),
     "dsmgp_set_tree": (C.c_int, [_ctx, C.c_int64, C.POINTER(C.c_int8), _lp, _lp, _lp, _dp, C.c_int64, _lp]),
     "dsmgp_set_test_routed": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32]),
@@ -110,6 +112,7 @@ DIAG_SIGNATURES = {
     "dsmgp_probe_diag": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]),
     "dsmgp_bench_fused8": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]),
     "dsmgp_probe_diag_fused": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, _dp]),
+    "dsmgp_bench_relocate": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]),
 }
 DIAG_LIB_PATH = os.path.join(_HERE, "libdsmgp_hip_diag.so")
 
@@ -260,6 +263,52 @@ class Context:
         sec = C.c_double(0.0)
         self._chk(self.lib.dsmgp_fit(self.h, mll.ctypes.data_as(_dp), info.ctypes.data_as(_ip), C.byref(sec)))
         return mll, info, sec.value
+
+    def append_rows(self, X_new, y_new, add_ptr, add_idx, mean=None):
+        """Append training rows to the fitted model (dsmgp_append_rows): leaf l takes the rows X_new[add_idx[add_ptr[l]:add_ptr[l + 1]]]
+        behind its list; mean: the leaves' means from now on (None = unchanged).  Every factor owner keeps the leading blocks of
+        its factor and factorises the rest.  Returns (mll[L], info[L], device_seconds) like fit.  On DSMGP_E_NOMEM the context
+        holds the grown table without a fit (`fit()` refits it in full) unless the message says the context is unchanged."""
+        X_new, px = _f64_fortran(np.atleast_2d(np.asarray(X_new, dtype=np.float64)))
+        y_new, py = _f64(np.atleast_1d(y_new))
+        if X_new.ndim != 2 or X_new.shape[1] != self.D or y_new.shape != (X_new.shape[0],):
+            raise ValueError(f"new rows of shape {X_new.shape} / {y_new.shape}: the model was trained on D = {self.D} columns")
+        add_ptr, p0 = _i64(add_ptr)
+        add_idx, p1 = _i64(add_idx)
+        if add_ptr.shape != (self.L + 1,) or add_idx.ndim != 1 or len(add_idx) < int(add_ptr[-1]):
+            raise ValueError("add_ptr needs L + 1 entries and add_idx add_ptr[L]")
+        if len(add_idx) == 0:
+            add_idx, p1 = _i64(np.zeros(1, dtype=np.int64))      # a valid pointer for the library's NULL check
+        pm = None
+        if mean is not None:
+            mean, pm = _f64(mean)
+            if mean.shape != (self.L,):
+                raise ValueError("mean needs one value per leaf")
+        mll = np.empty(self.L)
+        info = np.empty(self.L, dtype=np.int32)
+        sec = C.c_double(0.0)
+        rc = self.lib.dsmgp_append_rows(self.h, px, py, X_new.shape[0], X_new.shape[1], p0, p1, pm, mll.ctypes.data_as(_dp),
+                                        info.ctypes.data_as(_ip), C.byref(sec))
+        msg = self.lib.dsmgp_last_error(self.h).decode() if rc != 0 else ""
+        if rc == 0 or (rc == E_NOMEM and "the context is unchanged" not in msg):
+            # DSMGP_E_NOMEM from the new arenas: the library holds the grown data and leaf table already (and no fit), and the
+            # shapes follow it, so that fit / loo / targets_fetch of a caller that goes on with this context have the right lengths
+            self.leaf_n = self.leaf_n + np.diff(add_ptr)
+            self.n_obs = int(self.leaf_n.sum())
+            self.route_total = 0
+            self.n_t = 0
+            self.targets_Q = 0
+        self._chk(rc)
+        return mll, info, sec.value
+
+    APPEND_STAT_NAMES = ("owners_continued", "leaves_untouched", "bytes_relocated", "block_columns_factorised", "owners_restarted",
+                         "copies_dissolved")
+
+    def append_stats(self):
+        """What the last append_rows did (dsmgp_append_stats): a dict over APPEND_STAT_NAMES; bytes_relocated == 0: it ran in place."""
+        out = np.zeros(len(self.APPEND_STAT_NAMES), dtype=np.int64)
+        self._chk(self.lib.dsmgp_append_stats(self.h, out.ctypes.data_as(_lp)))
+        return {k: int(v) for k, v in zip(self.APPEND_STAT_NAMES, out)}
 
     def _test_matrix(self, Xt):
         """The test rows as the ABI reads them (n_t x D doubles, column-major); a matrix of another width is refused HERE,
@@ -697,6 +746,12 @@ class Context:
         s = C.c_double(0.0)
         self._chk(self.lib.dsmgp_bench_tile(self.h, int(ntiles), int(K), int(mode), int(group), int(reps), C.byref(s)))
         return 2.0 * 128 * 128 * K * ntiles / s.value / 1e12
+
+    def bench_relocate(self, nleaves, kb, ld_old, ld_new, reps=5):
+        """Diagnostic build: dict(kernel_s, memcpy_s, per_leaf_copies_s, bytes) of moving the kept blocks of `nleaves` leaves."""
+        out = np.zeros(4)
+        self._chk(self.lib.dsmgp_bench_relocate(self.h, int(nleaves), int(kb), int(ld_old), int(ld_new), int(reps), out.ctypes.data_as(_dp)))
+        return dict(kernel_s=float(out[0]), memcpy_s=float(out[1]), per_leaf_copies_s=float(out[2]), bytes=int(out[3]))
 
     def bench_fused8(self, ntasks, K, group=16, reps=3):
         """seconds per launch of the eight-wave fused tile task on a uniform batch (diagnostic)."""

@@ -289,8 +289,12 @@ class ArdRQ(KernelFunction):
 class ConstMean:
     """Constant mean function (`src/means.jl:7-18`)."""
 
-    def __init__(self, m):
+    default = False      # True: the builder's own mean(y[obs]) of the leaf (no meanFun given); add_data lets it follow the grown list
+
+    def __init__(self, m, default=False):
         self.m = float(m)
+        if default:
+            self.default = True
 
     def __repr__(self):
         return f"ConstMean({self.m})"

@@ -358,7 +358,7 @@ class GaussianProcess:
         if x.ndim == 1:
             x = x.reshape(-1, 1)
         y = np.asarray(y, dtype=np.float64)
-        mean = ConstMean(float(np.mean(y))) if mean is None else mean
+        mean = ConstMean(float(np.mean(y)), default=True) if mean is None else mean
         kernel = IsoSE(0.0, 0.0) if kernel is None else kernel
         N, D = x.shape
         leaf = GPNode(np.arange(N), np.full(D, -np.inf), np.full(D, np.inf), kernel, 0, mean, logNoise)
@@ -519,6 +519,101 @@ def fit(model, tau=0.05):
     target = model.model if isinstance(model, GaussianProcess) else model
     out = FitSeconds(_fit(target, tau))
     out.census = target.fit_census
+    return out
+
+
+class AppendSeconds(float):
+    """What `add_data` returns: the device seconds of the call.  `.fallback`: the new factors did not fit beside the old ones
+    (DSMGP_E_NOMEM) and the grown table was fitted from scratch instead; `.stats`: `Context.append_stats()` of the call (None
+    after a fallback)."""
+    fallback = False
+    stats = None
+
+
+def add_data(model, x_new, y_new, tau=0.05):
+    """Observe new rows and add them to a fitted model without refactorising it (`dsmgp_append_rows`): the step after an
+    acquisition.  The rows are routed through the model's own tree (region membership (lb, ub] per split, the rule of `route`; a
+    sum node sends a row to every child, a kernel vector to every GP of the region; a row beyond a split node's last threshold
+    raises `DsmgpDomainError`, as `predict` does, and changes nothing), `model.x`, `model.y` and every leaf's `obs` / `nobs`
+    grow, a leaf whose mean is the builder's default `ConstMean(mean(y[obs]))` gets the mean of its grown list (a user-supplied
+    `meanFun` is kept), the overlap matrix is recomputed, and every leaf that received rows continues its factorisation from the
+    blocks it keeps.  Sum-node weights stay as they are: `update(model)` is the caller's next step, as after `fit`.  The next
+    `fit(model, tau)` re-derives the sharing decisions and uploads the leaf table, not the data.  Returns `AppendSeconds`;
+    raises `LinAlgError` like `fit`.  `tau`: the sharing threshold of the fallback fit."""
+    gp = model if isinstance(model, GaussianProcess) else None
+    target = model.model if gp is not None else model
+    if target.shard.world > 1:
+        raise NotImplementedError("add_data on a sharded model: the multi-GPU exchange is out of scope")
+    if not target._uploaded:
+        raise hipabi.DsmgpError(hipabi.E_STATE, "add_data on a model that has never been fitted")
+    ctx = target.ctx
+    if not hasattr(ctx, "append_rows"):
+        raise NotImplementedError(f"{type(ctx).__name__} has no append_rows")
+    xn = np.asarray(x_new, dtype=np.float64)
+    if xn.ndim == 1:
+        xn = xn.reshape(1, -1) if target.x.shape[1] > 1 else xn.reshape(-1, 1)
+    yn = np.atleast_1d(np.asarray(y_new, dtype=np.float64))
+    if xn.ndim != 2 or xn.shape[1] != target.x.shape[1] or yn.shape != (xn.shape[0],) or xn.shape[0] < 1:
+        raise ValueError(f"new rows of shape {xn.shape} / {yn.shape}: the model holds D = {target.x.shape[1]} columns")
+    if not np.all(np.isfinite(yn)):
+        raise ValueError("non-finite value in y_new")
+    m, N0 = xn.shape[0], target.x.shape[0]
+    if target.root.kind == "gp":
+        if not np.all(np.isfinite(xn)):
+            raise ValueError("non-finite value in x_new")
+        ptr, idx = np.array([0, m], dtype=np.int64), np.arange(m, dtype=np.int64)
+    else:
+        try:
+            ptr, idx = route(target.root, xn)
+        except ValueError as e:
+            if "outside the region" in str(e):
+                raise hipabi.DsmgpDomainError(hipabi.E_DOMAIN, str(e)) from None
+            raise
+    y_all = np.concatenate([target.y, yn])
+    grown, means = [], []
+    for l, lf in enumerate(target.leaves):
+        add = idx[ptr[l]:ptr[l + 1]]
+        obs = np.concatenate([lf.obs, N0 + add]).astype(np.int64) if add.size else lf.obs
+        grown.append(obs)
+        default = getattr(lf.mean, "default", False) and add.size
+        means.append(float(np.mean(y_all[obs])) if default else float(lf.mean.m))
+
+    def commit():
+        target.x = np.asfortranarray(np.vstack([target.x, xn]))
+        target.y = y_all
+        for lf, obs, mu in zip(target.leaves, grown, means):
+            if obs is not lf.obs:
+                lf.obs, lf.nobs = obs, int(obs.size)
+                if getattr(lf.mean, "default", False):
+                    lf.mean = ConstMean(mu, default=True)
+        if target.D is not None:
+            target.D = get_overlap(target.root, target.L)
+        if gp is not None:
+            gp.N = int(target.x.shape[0])
+        target._route_cache = None
+        target._scores_on_device = False
+        target._schedule = None          # the next fit re-derives the sharing decisions and uploads the leaf table (not the data)
+
+    try:
+        mll_, info, sec = ctx.append_rows(xn, yn, ptr, idx, means)
+    except hipabi.DsmgpError as e:
+        if e.code != hipabi.E_NOMEM:
+            raise
+        commit()
+        target._uploaded = False         # whatever the context still holds: the fallback uploads everything again
+        out = AppendSeconds(_fit(target, tau))
+        out.fallback = True
+        return out
+    commit()
+    target.leaf_mll = np.ascontiguousarray(mll_, dtype=np.float64)
+    target.leaf_info = np.asarray(info, dtype=np.int32)
+    target.last_fit_seconds = sec
+    out = AppendSeconds(sec)
+    out.stats = ctx.append_stats() if hasattr(ctx, "append_stats") else None
+    bad = np.flatnonzero(target.leaf_info != 0)
+    if bad.size:
+        raise np.linalg.LinAlgError(f"leaf {int(bad[0])}: leading minor of order {int(target.leaf_info[bad[0]])} "
+                                    "is not positive definite")
     return out
 
 

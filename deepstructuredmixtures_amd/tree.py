@@ -166,7 +166,7 @@ def _get_splits(xd, lower, upper, minData, eps, K, rng, depth=1):
 def _build_gp(X, y, lb, ub, config, observations):
     """`src/treeStructure.jl:245-307`."""
     ym = float(np.mean(y)) if y.size else 0.0
-    mfun = ConstMean(ym) if config.meanFun is None else config.meanFun
+    mfun = ConstMean(ym, default=True) if config.meanFun is None else config.meanFun
     if isinstance(config.kernels, (list, tuple)):
         w = config._rng.dirichlet1(len(config.kernels))
         node = GPSumNode(of_gps=True)
@@ -283,6 +283,7 @@ def _nodes_from_table(config, tab, nodes, leaves, kvec, nk):
             else:
                 mfun = new(mean_cls)
                 mfun.m = means[region] if o1 > o0 else 0.0
+                mfun.default = True
             if kvec:
                 u = tab["dir_u"][region * nk:(region + 1) * nk]
                 e = -np.log(1.0 - u)                     # Stream.dirichlet1 on the uniforms the builder drew

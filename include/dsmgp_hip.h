@@ -133,6 +133,54 @@ int dsmgp_set_hyper(dsmgp_ctx* ctx, int32_t kernel_id, int32_t kind, const doubl
  *      seconds     = device time of the call (hipEvents), like the @elapsed value fit! returns */
 int dsmgp_fit(dsmgp_ctx* ctx, double* mll_out /* L */, int32_t* info_out /* L */, double* seconds);
 
+/* ---- append training rows to a fitted model without refactorising it (not a call of the reference): the step after an
+ *      acquisition, "observe the chosen point and add it".  Equivalent, with the hyper-parameters of the current fit, to
+ *        dsmgp_set_train([X; X_new], [y; y_new]);
+ *        dsmgp_set_leaves with every leaf's list grown by N_old + add_idx[add_ptr[l] .. add_ptr[l + 1]), the same kernel ids, `mean`;
+ *        the sharing schedule below;  dsmgp_fit
+ *      except that every factor owner keeps the leading kb = floor(n_old / 128) block rows and columns of the factor it had (the
+ *      Cholesky factor of a matrix with rows appended has the old factor as its leading block) and only the block columns from
+ *      kb on are factorised: the continuation the PREFIX phase of dsmgp_fit runs (chol_continue!, src/AdvancedCholeskey.jl:152-174),
+ *      with the leaf's own old factor as the source.  O(n 128 n) flops per leaf that receives rows instead of n^3 / 3, nothing for
+ *      the others.  mll_out, info_out, seconds: dsmgp_fit's, with its conventions; a first bad minor inside the new blocks is
+ *      reported with its absolute order.  A new row that no leaf takes is allowed and is stored with the data.
+ *      Needs a current fit and no reserved pool (DSMGP_E_STATE: after dsmgp_set_hyper, before the first fit, under dsmgp_reserve).
+ *      DSMGP_E_ARG, the context exactly as before: m < 1, D not the D of dsmgp_set_train, a NULL among X_new, y_new, add_ptr,
+ *      add_idx, a non-finite value (X_new, y_new, mean), add_ptr[0] != 0 or descending, a position outside 0 .. m-1, a list
+ *      that is not strictly ascending, a leaf beyond the size limit of dsmgp_set_leaves.
+ *      Sharing after the call: a COPY leaf stays a COPY of its source if and only if both receive identical additions (decided
+ *      here); every other leaf owns its factor from now on -- a former PREFIX leaf continues from its own factor, a COPY leaf
+ *      whose additions differ from its source's gets a factor of its own, continued from the source's old one.  Later
+ *      dsmgp_fit calls run under exactly this schedule (COPY where kept, FULL elsewhere) and factorise in full: the
+ *      continuation is one-shot.  dsmgp_set_sharing works as always.  Owners whose fit reported info != 0 are factorised from
+ *      block 0 (their kept blocks are damaged).
+ *      State after the call: the plan and the fit are current; the routing tree of dsmgp_set_tree stays registered (leaf
+ *      indices do not change); everything else that falls with a new leaf table falls -- the resident test set, the gradient,
+ *      LOO and target lists and arenas, L^-T, the mask of dsmgp_set_gradient_leaves -- and captured fit graphs are dropped (the
+ *      call itself never runs as a graph).
+ *      Storage: IN PLACE when no owner's padded size (n rounded up to 128) changes and the ownership map is unchanged: the
+ *      factor and Dinv arenas stay where they are and no kept byte moves; the partial block row kb is rewritten tile by tile
+ *      before it is read.  Otherwise RELOCATE: new arenas are allocated while the old ones are alive, the kept blocks move in
+ *      one launch, the old arenas are freed: PEAK MEMORY IS THE OLD FACTORS PLUS THE NEW ONES.  If the new arenas do not fit:
+ *      DSMGP_E_NOMEM, and the context holds the grown data and leaf table and no fit, as after dsmgp_set_leaves (the next
+ *      dsmgp_fit factorises in full).  (If not even the grown copy of the data fits, DSMGP_E_NOMEM leaves the context as before;
+ *      if the device copy of the grown leaf table cannot be made, the context keeps the grown data and NO leaf table: dsmgp_set_leaves next.)
+ *      Guarantees: for every owner with info == 0 before and after, the leading 128 kb square of its factor is the same bits as
+ *      before the call; a leaf without additions keeps every factor bit (z and the log-marginal are recomputed from them);
+ *      same inputs on the same state give the same bits (no atomics).  dsmgp_timings, dsmgp_work and dsmgp_work_fused
+ *      describe the call as they would a fit.
+ *      dsmgp_append_stats (of the last dsmgp_append_rows; DSMGP_E_STATE before the first): [0] owners continued (kept blocks
+ *      and factorised the rest), [1] leaves untouched (no additions, same mean, factor not moved: 0 on the relocate path),
+ *      [2] bytes of factor and Dinv relocated (0 = the in-place path ran), [3] block columns factorised, summed over the
+ *      owners, [4] owners restarted from block 0, [5] COPY relations dissolved. */
+int dsmgp_append_rows(dsmgp_ctx* ctx, const double* X_new /* m x D column-major, ld = m */, const double* y_new /* m */,
+                      int64_t m, int32_t D, const int64_t* add_ptr /* L+1 */,
+                      const int64_t* add_idx /* positions 0..m-1 in X_new, strictly ascending per leaf */,
+                      const double* mean /* L: the leaves' means from now on; NULL = unchanged */,
+                      double* mll_out /* L, may be NULL */, int32_t* info_out /* L, may be NULL */, double* seconds /* may be NULL */);
+#define DSMGP_N_APPEND_STATS 6
+int dsmgp_append_stats(dsmgp_ctx* ctx, int64_t* out /* DSMGP_N_APPEND_STATS, of the last dsmgp_append_rows */);
+
 /* ---- prediction(gp, xtest) for every (leaf, routed test row): src/gaussianprocess.jl:110-137
  *      mu  = m + Knt' alpha ; var = k(x*,x*) - |L^-1 k_n*|^2 + exp(2 logNoise)   (diag only; no clamp,
  *      the caller applies src/common.jl:137).  route_ptr/route_idx: per leaf, which rows of Xt.

@@ -31,6 +31,11 @@ int dsmgp_probe_diag(dsmgp_ctx* ctx, int32_t ntiles, int32_t ld, int32_t reps, d
  * depth K (a multiple of 128; 0 = the first block step): us per launch.  256 / 512 / 768 blocks = one / two / three tasks per CU */
 int dsmgp_probe_diag_fused(dsmgp_ctx* ctx, int32_t ntiles, int32_t K, int32_t reps, double* kernel_us);
 
+/* diagnostic: the kept blocks of nleaves leaves (kb x kb blocks of 128, leading dimension ld_old -> ld_new, and kb Dinv blocks each)
+ * moved three ways: out[4] = { seconds of the one relocate_tiles_kernel launch of dsmgp_append_rows, of one contiguous device-to-device
+ * hipMemcpy of the same byte count, of the hipMemcpy2DAsync + hipMemcpyAsync pair per leaf of the PREFIX phase, bytes moved } */
+int dsmgp_bench_relocate(dsmgp_ctx* ctx, int32_t nleaves, int32_t kb, int32_t ld_old, int32_t ld_new, int32_t reps, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
+export attach!, detach!, census, append_rows!, append_stats, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -578,6 +578,47 @@ function targets_fetch(s::Session, leaf::Integer)
     Z = Matrix{Float64}(undef, n, s.targets)
     GC.@preserve Z chk(s, ccall(sym(:dsmgp_targets_fetch), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.h, Int32(leaf - 1), Z))
     return Z
+end
+
+"append_rows!(s, Xnew, ynew, add_ptr, add_idx; mean=nothing): append training rows to the fitted session without refactorising it
+(dsmgp_append_rows).  `Xnew` is `m × D`, `ynew` has `m` entries; leaf `l` (the order of `s.leaves`) takes the rows
+`Xnew[add_idx[add_ptr[l]+1:add_ptr[l+1]], :]` behind its list: `add_ptr` has `L + 1` entries starting at 0, `add_idx` holds 1-based
+row numbers of `Xnew`, strictly ascending per leaf.  `mean`: the constant mean of every leaf from now on (`nothing`: unchanged).
+Every factor owner keeps the leading ⌊n/128⌋ blocks of its factor and only the rest is factorised; a COPY leaf stays a COPY only
+where it received the rows of its source; the registered test set, the resident targets and the gradient lists are dropped.  Needs
+a current fit.  The node objects of the reference are not touched: the caller grows them.  Returns the device seconds."
+function append_rows!(s::Session, Xnew::AbstractMatrix, ynew::AbstractVector, add_ptr::AbstractVector{<:Integer},
+                      add_idx::AbstractVector{<:Integer}; mean::Union{Nothing,AbstractVector}=nothing)
+    X = Matrix{Float64}(Xnew)
+    y = Vector{Float64}(ynew)
+    m, Dm = size(X)
+    L = length(s.gps)
+    length(y) == m || throw(DimensionMismatch("ynew needs one entry per row of Xnew"))
+    length(add_ptr) == L + 1 || throw(DimensionMismatch("add_ptr needs L + 1 entries"))
+    ptr = Vector{Int64}(add_ptr)
+    idx = isempty(add_idx) ? Int64[0] : Vector{Int64}(add_idx) .- 1        # 1-based in Julia, 0-based in the ABI
+    M = mean === nothing ? nothing : Vector{Float64}(mean)
+    M === nothing || length(M) == L || throw(DimensionMismatch("mean needs one entry per leaf"))
+    sec = Ref{Float64}(0.0)
+    mllv, info = s.leafmll, s.info
+    GC.@preserve X y ptr idx M mllv info chk(s, ccall(sym(:dsmgp_append_rows), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{Float64}),
+        s.h, X, y, Int64(m), Int32(Dm), ptr, idx, M === nothing ? Ptr{Float64}(C_NULL) : pointer(M), mllv, info, sec))
+    s.testkey = UInt(0)
+    s.targets = 0
+    bad = findfirst(!=(0), info)
+    bad === nothing || throw(PosDefException(Int(info[bad])))
+    return sec[]
+end
+
+"append_stats(s): what the last append_rows! did (dsmgp_append_stats), as a named tuple: owners continued, leaves untouched,
+bytes of factor and Dinv relocated (0: the call ran in place), block columns factorised, owners restarted from block 0, COPY
+relations dissolved."
+function append_stats(s::Session)
+    out = zeros(Int64, 6)
+    GC.@preserve out chk(s, ccall(sym(:dsmgp_append_stats), Cint, (Ptr{Cvoid}, Ptr{Int64}), s.h, out))
+    return (owners_continued = out[1], leaves_untouched = out[2], bytes_relocated = out[3], block_columns_factorised = out[4],
+            owners_restarted = out[5], copies_dissolved = out[6])
 end
 
 "targets_gradients(s; col_weight=nothing): hyper-parameter gradients of the weighted sum of the per-column log marginal likelihoods
