@@ -713,6 +713,18 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     double alg_flops_update = 0.0;  // algorithmic flops of the Cholesky update launches
     int64_t append_stats[DSMGP_N_APPEND_STATS] = {0, 0, 0, 0, 0, 0};
     bool have_append_stats = false;
+    // dsmgp_add_rows_keep_test: plain per-leaf data beside the validity table.  vt_first[l] leading block columns of leaf l's part of
+    // arenaVt hold K_tn L^-T of the CURRENT fit although P_VT is not current: it means something only while P_TEST is current,
+    // P_VT is not and resume_armed says that the fit is still the one the call made (dsmgp_fit and the predict_run that uses it
+    // clear it; so does whatever drops or replaces the test set: free_test)
+    std::vector<int> vt_first;
+    bool resume_armed = false;
+    bool sweep_resumed = false;     // psweep / pgram skip block steps (built from vt_first): rebuilt from block 0 when next needed
+    DevBuf<KeptSumTask> kept_tasks; // the moment sums of the kept columns (kept_sums_kernel), their partial sums and finish tasks
+    DevBuf<KeptFinTask> kept_fin;
+    DevBuf<double> d_kept_part;
+    int64_t resume_stats[DSMGP_N_RESUME_STATS] = {0, 0, 0, -1, 0, 0};
+    bool have_resume_stats = false;
     double alg_flops_fused = 0.0, alg_flops_fused_joint = 0.0;   // ... of the fused tile launches (update + solve), fit alone / joint
     int n_fused_launches = 0;
     int n_update_launches = 0;
@@ -1067,6 +1079,10 @@ void free_test(dsmgp_ctx* c, bool keep) {
     c->ptasks_slow.drop(keep);
     c->psweep.drop(c, keep);
     c->psegs.drop(keep);
+    c->kept_tasks.drop(keep);
+    c->kept_fin.drop(keep);
+    c->d_kept_part.drop(keep);
+    c->resume_armed = c->sweep_resumed = false;
     arena_put(c, c->arenaCov);
     c->cap_Cov = 0;
     c->pcov.drop(keep);
@@ -1649,6 +1665,8 @@ int build_factor_steps(dsmgp_ctx* c, int lane, bool with_test, StepLists (&phase
 }
 
 int build_schedule(dsmgp_ctx* c);
+int register_test(dsmgp_ctx* c, HostLog& hl, const std::vector<int>* first = nullptr);
+int full_sweep_lists(dsmgp_ctx* c);
 // Who owns which factor, how many leading blocks a PREFIX leaf keeps, and where every leaf's buffers sit in the plan's arenas
 void plan_layout(dsmgp_ctx* c, size_t& fTot, size_t& dTot, size_t& vTot, size_t& xTot) {
     const int L = c->L;
@@ -2574,7 +2592,9 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
     if (int rc = upload_hyper(c)) return rc;
     // With a resident test set the rows of K_tn ride through the same launches (build_factor_steps).
     const bool joint = c->joint && c->has(P_TEST);
+    c->resume_armed = false;        // the factor changes: what dsmgp_add_rows_keep_test kept of K_tn L^-T is stale from here on
     if (joint) {
+        if (int rc = full_sweep_lists(c)) return rc;      // (the joint fit launches pgram where the Gram is not fused)
         if (int rc = ensure_joint(c)) return rc;
     } else if (int rc = ensure_phase(c)) {
         return rc;
@@ -2719,8 +2739,91 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
 
 // Append training rows to the fitted model: every factor owner keeps the leading blocks of the factor it had and continues
 // from them, through the PREFIX phase of the fit with the leaf's OWN old factor as the source (include/dsmgp_hip.h).
-int dsmgp_append_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int64_t m, int32_t D, const int64_t* add_ptr,
-                      const int64_t* add_idx, const double* mean, double* mll_out, int32_t* info_out, double* seconds) {
+// What dsmgp_add_rows_keep_test carries of the resident test set across the rebuild of the plan
+struct KeptTest {
+    struct Leaf {
+        size_t vt_off;
+        int ntpad, npad;
+        int have;                   // leading block columns of the leaf's K_tn L^-T that were current when the call began
+    };
+    bool resident = false;
+    std::vector<Leaf> old;
+    double* arena = nullptr;        // the previous arenaVt: owned here until the context adopts it again or it is freed
+    size_t arena_count = 0;
+};
+
+// The test set again on the grown plan (the fit is done, the old factors are gone).  A leaf keeps the block columns that were
+// current and belong to kept blocks of the factor it reads -- its owner's, so a COPY leaf its source's.  IN PLACE where no leaf's
+// offset or size in the arena moves; else RELOCATE: a new arena beside the old, the kept column runs (contiguous: 128 x 128
+// tiles with lds = ldd = ntpad) in one launch, then the old one is freed -- never a move inside one arena, whose source and
+// destination would overlap.  rs: dsmgp_resume_stats.  An error leaves the set half built: the caller drops it.
+static int keep_test_set(dsmgp_ctx* c, KeptTest& kt, const std::vector<int>& factor_keep, int64_t* rs) {
+    const int L = c->L;
+    std::vector<int> first((size_t)L, 0);
+    std::vector<size_t> off((size_t)L, 0);
+    size_t vTot = 0;
+    bool same = true, any = false;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        const KeptTest::Leaf& o = kt.old[(size_t)l];
+        off[(size_t)l] = vTot;
+        vTot += (size_t)o.ntpad * lf.npad;      // (register_test's layout: the routes, and with them ntpad, are what they were)
+        if (off[(size_t)l] != o.vt_off || lf.npad != o.npad) same = false;
+        if (c->route_ptr[(size_t)l + 1] == c->route_ptr[(size_t)l]) continue;
+        first[(size_t)l] = std::min(std::min(o.have, factor_keep[(size_t)lf.owner]), lf.nb);
+        if (first[(size_t)l] > 0) {
+            any = true;
+            rs[0]++;
+            rs[1] += first[(size_t)l];
+        } else {
+            rs[4]++;
+        }
+    }
+    if (same || !any) {     // in place -- or nothing to keep: register_test takes the arena over while it fits
+        c->arenaVt = kt.arena;
+        c->arenaVt_count = kt.arena_count;
+        kt.arena = nullptr;
+    } else {
+        const size_t want = vTot + vTot / 8;
+        size_t freeB = 0, totalB = 0;
+        HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
+        if (want * sizeof(double) + (size_t(1) << 30) > freeB)
+            return fail(c, DSMGP_E_NOMEM, "add_rows_keep_test: no room for the new K_tn arena beside the old one");
+        if (int rc = arena_get(c, c->arenaVt, want)) return rc;
+        c->arenaVt_count = want;
+        std::vector<RelocTask> rt;
+        for (int l = 0; l < L; ++l) {
+            const KeptTest::Leaf& o = kt.old[(size_t)l];
+            for (int j = 0; j < first[(size_t)l]; ++j)
+                for (int i = 0; i < o.ntpad / TB; ++i) {
+                    const size_t at = (size_t)i * TB + (size_t)j * TB * (size_t)o.ntpad;
+                    rt.push_back(RelocTask{kt.arena + o.vt_off + at, c->arenaVt + off[(size_t)l] + at, o.ntpad, o.ntpad});
+                }
+        }
+        DevBuf<RelocTask> reloc;
+        if (int rc = dev_upload(c, reloc, rt)) return rc;
+        relocate_tiles_kernel<<<(unsigned)rt.size(), 256, 0, c->stream>>>(reloc.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(kt.arena);
+        kt.arena = nullptr;
+        rs[2] = (int64_t)rt.size() * TB * TB * (int64_t)sizeof(double);
+    }
+    const double* const arena = c->arenaVt;
+    c->stage_top = 0;       // (the stream is idle)
+    HostLog hl("add_rows_keep_test: sizes");
+    if (int rc = register_test(c, hl, &first)) return rc;
+    if (any && c->arenaVt != arena) return fail(c, DSMGP_E_STATE, "add_rows_keep_test: the K_tn arena was replaced");
+    c->vt_first = first;
+    c->resume_armed = true;
+    return 0;
+}
+
+// keep_test (dsmgp_add_rows_keep_test): a resident test set stays resident -- its rows, routes and entry index as they are, the second
+// half of its registration again on the grown plan -- and, where dsmgp_predict_run had run on the fit the call finds, every leaf
+// keeps the leading block columns of K_tn L^-T that belong to the kept blocks of the factor it reads (keep_test_set, below).
+static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int64_t m, int32_t D, const int64_t* add_ptr,
+                     const int64_t* add_idx, const double* mean, double* mll_out, int32_t* info_out, double* seconds, bool keep_test) {
     if (!c) return DSMGP_E_ARG;
     if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "append_rows needs a current fit");
     if (c->pool_base) return fail(c, DSMGP_E_STATE, "append_rows under a reserved pool");
@@ -2786,7 +2889,33 @@ int dsmgp_append_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, in
     double* oldF = c->arenaF;
     double* oldDinv = c->arenaDinv;
     c->arenaF = c->arenaDinv = nullptr;
-    free_plan_and_test(c);          // (the routing tree stays: leaf indices do not change)
+    // ... and, for a test set that stays, where every leaf's K_tn L^-T sits, how much of it is current, and the arena itself
+    KeptTest kt;
+    kt.resident = keep_test && c->has(P_TEST);
+    if (kt.resident) {
+        const bool swept = c->has(P_PRED), pending = !c->has(P_VT) && c->resume_armed;
+        kt.old.resize((size_t)L);
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            kt.old[(size_t)l] = KeptTest::Leaf{lf.vt_off, lf.ntpad, lf.npad, swept ? lf.nb : (pending ? c->vt_first[(size_t)l] : 0)};
+        }
+        kt.arena = c->arenaVt;
+        kt.arena_count = c->arenaVt_count;
+        c->arenaVt = nullptr;
+        c->arenaVt_count = 0;
+        const size_t counts[6] = {c->dXt.count,     c->d_route_ptr.count, c->d_route_idx.count,
+                                  c->d_row_ptr.count, c->d_row_ent.count,   c->d_ent_leaf.count};
+        free_plan(c);
+        free_test(c, true);         // the rows, the CSR and the entry index stay as they are: emptied lists, the same bytes
+        c->dXt.count = counts[0];
+        c->d_route_ptr.count = counts[1];
+        c->d_route_idx.count = counts[2];
+        c->d_row_ptr.count = counts[3];
+        c->d_row_ent.count = counts[4];
+        c->d_ent_leaf.count = counts[5];
+    } else {
+        free_plan_and_test(c);      // (the routing tree stays: leaf indices do not change)
+    }
     c->grad_active.clear();
 
     // 4. the grown leaf table and the schedule it keeps: COPY where source and leaf got the same rows, FULL elsewhere
@@ -2841,6 +2970,8 @@ int dsmgp_append_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, in
         free_plan_and_test(c);
         if (oldF) (void)hipFree(oldF);
         if (oldDinv) (void)hipFree(oldDinv);
+        if (kt.arena) (void)hipFree(kt.arena);      // (the test set has gone with free_plan_and_test)
+        kt.arena = nullptr;
         final_schedule();
         c->err = msg;
         return rc;
@@ -2868,6 +2999,7 @@ int dsmgp_append_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, in
     // 5. this call's one-shot marks: an owner that keeps blocks is a PREFIX leaf whose source is its own old factor (phase 1, z
     //    from the forward sweep); kb = every block for a leaf without additions, floor(n_old / 128) otherwise
     final_schedule();
+    std::vector<int> factor_keep((size_t)L, 0);         // per factor owner: the leading blocks it keeps
     for (int l = 0; l < L; ++l) {
         LeafHost& lf = c->leaves[l];
         if (lf.op != DSMGP_SHARE_FULL) continue;
@@ -2879,6 +3011,7 @@ int dsmgp_append_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, in
             lf.src = l;
             lf.prefix = (int64_t)keep * TB;
         }
+        factor_keep[(size_t)l] = keep;
         if (keep == 0) st[4]++;
         else if (keep < lf.nb) st[0]++;
         st[3] += lf.nb - keep;
@@ -3006,6 +3139,39 @@ int dsmgp_append_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, in
     c->invalidate(P_PHASE);
     for (int i = 0; i < DSMGP_N_APPEND_STATS; ++i) c->append_stats[i] = st[i];
     c->have_append_stats = true;
+    // 9. the test set that stays: after the old factors have gone, so that the call's peak is the larger of "old + new factors +
+    //    old K_tn L^-T" and "new factors + old + new K_tn L^-T".  The fit is good whatever happens here: a set that cannot be
+    //    kept is dropped, as dsmgp_append_rows drops it, and the stats say so.
+    if (keep_test) {
+        int64_t rs[DSMGP_N_RESUME_STATS] = {0, 0, 0, -1, 0, 0};
+        if (kt.resident && keep_test_set(c, kt, factor_keep, rs) != 0) {
+            (void)hipStreamSynchronize(c->stream);
+            free_test(c);
+            const int64_t dropped[DSMGP_N_RESUME_STATS] = {0, 0, 0, -1, 0, 1};
+            for (int i = 0; i < DSMGP_N_RESUME_STATS; ++i) rs[i] = dropped[i];
+        }
+        if (kt.arena) (void)hipFree(kt.arena);
+        kt.arena = nullptr;
+        for (int i = 0; i < DSMGP_N_RESUME_STATS; ++i) c->resume_stats[i] = rs[i];
+        c->have_resume_stats = true;
+    }
+    return 0;
+}
+
+int dsmgp_append_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int64_t m, int32_t D, const int64_t* add_ptr,
+                      const int64_t* add_idx, const double* mean, double* mll_out, int32_t* info_out, double* seconds) {
+    return grow_rows(c, X_new, y_new, m, D, add_ptr, add_idx, mean, mll_out, info_out, seconds, false);
+}
+
+int dsmgp_add_rows_keep_test(dsmgp_ctx* c, const double* X_new, const double* y_new, int64_t m, int32_t D, const int64_t* add_ptr,
+                             const int64_t* add_idx, const double* mean, double* mll_out, int32_t* info_out, double* seconds) {
+    return grow_rows(c, X_new, y_new, m, D, add_ptr, add_idx, mean, mll_out, info_out, seconds, true);
+}
+
+int dsmgp_resume_stats(dsmgp_ctx* c, int64_t* out) {
+    if (!c || !out) return DSMGP_E_ARG;
+    if (!c->have_resume_stats) return fail(c, DSMGP_E_STATE, "resume_stats before add_rows_keep_test");
+    for (int i = 0; i < DSMGP_N_RESUME_STATS; ++i) out[i] = c->resume_stats[i];
     return 0;
 }
 
@@ -3024,7 +3190,8 @@ namespace {
 // made on the device): per-leaf sizes from c->route_ptr, the K_tn arena, the gathered test rows, the task lists of the sweep.
 // The first half has put the rows (dXt), the CSR (d_route_ptr / d_route_idx) and the per-row entry index (d_row_ptr / d_row_ent /
 // d_ent_leaf) into HBM and the per-leaf row offsets into c->route_ptr.
-int register_test(dsmgp_ctx* c, HostLog& hl) {
+int build_sweep_lists(dsmgp_ctx* c, HostLog& hl, const std::vector<int>& first);
+int register_test(dsmgp_ctx* c, HostLog& hl, const std::vector<int>* first) {
     const int L = c->L;
     const int64_t n_t = c->n_t, total = c->route_total;
     const int64_t* rp = c->route_ptr.data();
@@ -3095,6 +3262,29 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
         }
         HIPCHK(c, hipGetLastError());
     }
+    {
+        const std::vector<int> zero((size_t)L, 0);
+        if (int rc = build_sweep_lists(c, hl, first ? *first : zero)) return rc;
+    }
+    // The same test rows as riders of the factorisation launches (used by fit while this test set is resident).  With a device
+    // pool (the streaming context: the pool is a stack, plan < test < gradients, and a fit follows at once) the lists are built
+    // here; otherwise by the first fit that wants them (ensure_joint) -- predict(model, x) on rows the model has not seen
+    // registers them and runs its own sweep, and should not wait for task lists only a later fit! would use (0.067 s of the
+    // 0.088 s this call took at the headline model).
+    c->mark(P_TEST);
+    int rc = c->pool_base ? ensure_joint(c) : 0;
+    hl.lap("set_test: final sync");
+    if (rc == 0) rc = stage_done(c);
+    if (rc != 0) c->invalidate(P_TEST);
+    return rc;
+}
+
+// The task lists of the standalone sweep over the registered rows.  first[l]: the block step leaf l's sweep begins at -- zeros for
+// a registration; what dsmgp_add_rows_keep_test kept of the leaf's K_tn L^-T otherwise: steps k < first[l] have no task of any
+// kind (no K_tn tile either: block columns below first[l] are never written), block column first[l] is written whole like every
+// later one, and the moment sums over the columns the sweep does not visit come from kept_sums_kernel (dsmgp_predict_run).
+int build_sweep_lists(dsmgp_ctx* c, HostLog& hl, const std::vector<int>& first) {
+    const int L = c->L;
     hl.lap("set_test: task lists (host)");
     // task lists
     // In the block steps that a fit runs fused (many leaves, or shallow: build_plan) the sweep does too: one tile_fused8_kernel
@@ -3132,7 +3322,7 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
                 g.sym = 0;
                 g.diag = 0;
                 g.kid = lf.kid;
-                pg.push_back(g);
+                if (j >= first[(size_t)l]) pg.push_back(g);
                 if (j == 0) pg0.push_back(g);
             }
         }
@@ -3155,7 +3345,7 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
             if (lf.nt == 0) continue;
             const int nt8 = ((lf.nt + 15) / 16 + 7) / 8;
             const size_t v0 = (size_t)c->leaf_lane[l] * (size_t)nsteps;
-            for (int k = 0; k < lf.nb; ++k) {
+            for (int k = first[(size_t)l]; k < lf.nb; ++k) {
                 if (fused_at(l, k)) cnt8[v0 + (size_t)k] += nt8;
                 else classic[v0 + (size_t)k].push_back(l);
             }
@@ -3173,7 +3363,7 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
             if (lf.nt == 0) continue;
             const int nt8 = ((lf.nt + 15) / 16 + 7) / 8;
             const size_t v0 = (size_t)c->leaf_lane[l] * (size_t)nsteps;
-            for (int k = 0; k < lf.nb; ++k)
+            for (int k = first[(size_t)l]; k < lf.nb; ++k)
                 if (fused_at(l, k)) {
                     SweepSeg sg{};
                     sg.leaf = l;
@@ -3280,17 +3470,45 @@ int register_test(dsmgp_ctx* c, HostLog& hl) {
     if (int rc = stage_upload_list(c, c->pgram0, pg0)) return rc;
     if (int rc = stage_upload_list(c, c->ptasks, ptk)) return rc;
     if (int rc = stage_upload_list(c, c->ptasks_slow, ptk_slow)) return rc;
-    // The same test rows as riders of the factorisation launches (used by fit while this test set is resident).  With a device
-    // pool (the streaming context: the pool is a stack, plan < test < gradients, and a fit follows at once) the lists are built
-    // here; otherwise by the first fit that wants them (ensure_joint) -- predict(model, x) on rows the model has not seen
-    // registers them and runs its own sweep, and should not wait for task lists only a later fit! would use (0.067 s of the
-    // 0.088 s this call took at the headline model).
-    c->mark(P_TEST);
-    int rc = c->pool_base ? ensure_joint(c) : 0;
-    hl.lap("set_test: final sync");
-    if (rc == 0) rc = stage_done(c);
-    if (rc != 0) c->invalidate(P_TEST);
-    return rc;
+    // the sums over the kept columns: per (leaf, row tile) chunks of KEPT_CHUNK_BLOCKS block columns, real columns only (a leaf
+    // without additions keeps its last, partial block column)
+    std::vector<KeptSumTask> ks;
+    std::vector<KeptFinTask> kf;
+    const int chunk = KEPT_CHUNK_BLOCKS * TB;
+    auto kept_cols = [&](int l) { return c->leaves[l].nt == 0 ? 0 : std::min(first[(size_t)l] * TB, c->leaves[l].n); };
+    size_t nchunk = 0;
+    for (int l = 0; l < L; ++l) nchunk += (size_t)(c->leaves[l].ntpad / TB) * (size_t)((kept_cols(l) + chunk - 1) / chunk);
+    if (int rc = dev_reserve(c, c->d_kept_part, nchunk * 2 * TB)) return rc;
+    bool any = false;
+    for (int l = 0; l < L; ++l) {
+        const int ncols = kept_cols(l);
+        if (ncols == 0) continue;
+        any = true;
+        const LeafHost& lf = c->leaves[l];
+        const LeafDev& d = c->h_leaves[l];
+        for (int ti = 0; ti < lf.ntpad / TB; ++ti) {
+            double* part = c->d_kept_part.p + ks.size() * 2 * TB;
+            kf.push_back(KeptFinTask{part, d.macc + (size_t)ti * TB, d.sacc + (size_t)ti * TB, (ncols + chunk - 1) / chunk, 0});
+            for (int c0 = 0; c0 < ncols; c0 += chunk, part += 2 * TB)
+                ks.push_back(KeptSumTask{d.Vt + (size_t)ti * TB + (size_t)c0 * (size_t)lf.ntpad, d.z + c0, part, lf.ntpad,
+                                         std::min(chunk, ncols - c0), std::max(0, std::min(TB, lf.nt - ti * TB)), 0});
+        }
+    }
+    if (int rc = stage_upload_list(c, c->kept_tasks, ks)) return rc;
+    if (int rc = stage_upload_list(c, c->kept_fin, kf)) return rc;
+    c->sweep_resumed = any;
+    return 0;
+}
+
+// The sweep's lists from block 0 again, where the resident ones skip what dsmgp_add_rows_keep_test had kept
+int full_sweep_lists(dsmgp_ctx* c) {
+    if (!c->sweep_resumed) return 0;
+    drop_graphs(c);
+    c->stage_top = 0;       // (the stream is idle: every entry point synchronises before it returns)
+    HostLog hl("sweep lists from block 0");
+    const std::vector<int> zero((size_t)c->L, 0);
+    if (int rc = build_sweep_lists(c, hl, zero)) return rc;
+    return stage_done(c);
 }
 }  // namespace
 
@@ -3528,8 +3746,25 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
     if (c->ptasks.count) {
         const bool standalone = !c->has(P_VT);
         if (standalone) {
+            // after dsmgp_add_rows_keep_test the sweep resumes where the kept block columns end, once; any other sweep begins at 0
+            const bool resume = c->resume_armed;
+            if (!resume)
+                if (int rc = full_sweep_lists(c)) return rc;
             if (int rc = ensure_dinv(c)) return rc;       // the panel solves of the sweep multiply with Dinv_k
             HIPCHK(c, hipMemsetAsync(c->arenaPV + c->acc_off, 0, c->acc_count * sizeof(double), c->stream));
+            if (resume && c->kept_tasks.count) {          // ... and the sums of the columns it skips are stored over the zeros
+                pt.begin(9);
+                kept_sums_kernel<<<(unsigned)c->kept_tasks.count, 256, 0, c->stream>>>(c->kept_tasks.p);
+                kept_sums_finish_kernel<<<(unsigned)c->kept_fin.count, 128, 0, c->stream>>>(c->kept_fin.p);
+                pt.end();
+            }
+            if (resume) {
+                int64_t swept = 0;
+                for (int l = 0; l < c->L; ++l)
+                    if (c->leaves[l].nt > 0) swept += c->leaves[l].nb - c->vt_first[(size_t)l];
+                c->resume_stats[3] = swept;
+                c->resume_armed = false;
+            }
             // K_tn tiles of the classic steps                (src/gaussianprocess.jl:133)
             if (c->pgram.count) {
                 pt.begin(6);
@@ -3579,6 +3814,20 @@ int dsmgp_predict_fetch(dsmgp_ctx* c, double* mu_out, double* var_out) {
     if (n && mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->arenaPV, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (n && var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->arenaPV + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// Inspection: K_tn L^-T of one leaf over its routed rows and its n real columns, as the sweep left it
+int dsmgp_download_vt(dsmgp_ctx* c, int32_t leaf, double* V_out, int64_t ld) {
+    if (!c) return DSMGP_E_ARG;
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "download_vt before predict_run on the current fit");
+    if (leaf < 0 || leaf >= c->L) return fail(c, DSMGP_E_ARG, "download_vt: leaf out of range");
+    const LeafHost& lf = c->leaves[leaf];
+    if (lf.nt == 0) return 0;
+    if (!V_out || ld < lf.nt) return fail(c, DSMGP_E_ARG, "download_vt: V_out is NULL or ld < nt");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy2D(V_out, (size_t)ld * sizeof(double), c->h_leaves[leaf].Vt, (size_t)lf.ntpad * sizeof(double),
+                          (size_t)lf.nt * sizeof(double), (size_t)lf.n, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -3478,6 +3478,83 @@ __global__ __launch_bounds__(256) void pred_var_kernel(const LeafDev* __restrict
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// dsmgp_add_rows_keep_test: the moment sums of the block columns of V = K_tn L^-T that a resumed sweep does not visit.
+// The sweep adds sum_c V(r,c) z(c) and sum_c V(r,c)^2 to macc / sacc in the epilogue of every panel solve; a sweep that begins at
+// block column `first` finds them STORED here over columns [0, 128 first) against the CURRENT z.  One workgroup per (leaf, 128-row
+// tile, chunk of KEPT_CHUNK_BLOCKS block columns): the chunk size is a constant, so which columns meet in one partial sum -- and
+// with that a leaf's bits -- does not depend on what else the launch holds.  A lane owns two consecutive rows (one 16-byte load
+// per column; tiles start at multiples of 128 doubles and ld is one: always aligned), a wave the 128 rows of a column (1 KB,
+// contiguous), the four waves every fourth column; a wave sums its columns ascending, then waves 0..3 are added in that order.
+// V is read once for both sums.  Rows from `nrows` on are padding: the arena is never cleared, they hold whatever was there, so
+// they are never added (a select, not a product with zero: they may be NaN) and their sums are written as zeros.
+constexpr int KEPT_CHUNK_BLOCKS = 4;
+struct KeptSumTask {
+    const double* V;      // row 0 of the tile, column 0 of the chunk (ld = ntpad)
+    const double* z;      // z of the chunk's first column
+    double* part;         // 2 x 128: the chunk's sums, V z | V^2
+    int ld, ncols, nrows, pad;
+};
+__global__ __launch_bounds__(256) void kept_sums_kernel(const KeptSumTask* __restrict__ tasks) {
+    __shared__ double red[3][4][64];
+    const KeptSumTask tk = tasks[blockIdx.x];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, r = 2 * lane;
+    const bool ok0 = r < tk.nrows, ok1 = r + 1 < tk.nrows;
+    double m0 = 0.0, m1 = 0.0, s0 = 0.0, s1 = 0.0;
+    if (ok0) {
+        const double* col = tk.V + r + (size_t)w * (size_t)tk.ld;
+#pragma unroll 4
+        for (int c = w; c < tk.ncols; c += 4, col += 4 * (size_t)tk.ld) {
+            const d2 v = *AS_GLOBAL_D2(col);
+            const double z = tk.z[c];
+            m0 = fma(v.x, z, m0);
+            s0 = fma(v.x, v.x, s0);
+            m1 = ok1 ? fma(v.y, z, m1) : 0.0;
+            s1 = ok1 ? fma(v.y, v.y, s1) : 0.0;
+        }
+    }
+    if (w > 0) {
+        red[w - 1][0][lane] = m0;
+        red[w - 1][1][lane] = m1;
+        red[w - 1][2][lane] = s0;
+        red[w - 1][3][lane] = s1;
+    }
+    __syncthreads();
+    if (w == 0) {
+        for (int q = 0; q < 3; ++q) {
+            m0 += red[q][0][lane];
+            m1 += red[q][1][lane];
+            s0 += red[q][2][lane];
+            s1 += red[q][3][lane];
+        }
+        d2 m, s;
+        m.x = m0;
+        m.y = m1;
+        s.x = s0;
+        s.y = s1;
+        *reinterpret_cast<d2*>(tk.part + r) = m;
+        *reinterpret_cast<d2*>(tk.part + TB + r) = s;
+    }
+}
+// ... and the chunks of one (leaf, tile) added in ascending order: macc / sacc are stored, not added to
+struct KeptFinTask {
+    const double* part;   // nchunks x 2 x 128
+    double* macc;
+    double* sacc;
+    int nchunks, pad;
+};
+__global__ __launch_bounds__(128) void kept_sums_finish_kernel(const KeptFinTask* __restrict__ tasks) {
+    const KeptFinTask tk = tasks[blockIdx.x];
+    const int r = threadIdx.x;
+    double m = 0.0, s = 0.0;
+    for (int q = 0; q < tk.nchunks; ++q) {
+        m += tk.part[(size_t)q * 2 * TB + r];
+        s += tk.part[(size_t)q * 2 * TB + TB + r];
+    }
+    tk.macc[r] = m;
+    tk.sacc[r] = s;
+}
+
 // per leaf: y.alpha and alpha.alpha (inputs of the gradient assembly)
 __global__ __launch_bounds__(256) void dots_kernel(const LeafDev* __restrict__ leaves, double* __restrict__ out) {
     __shared__ double r1[256], r2[256];

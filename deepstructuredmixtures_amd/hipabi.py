@@ -46,6 +46,9 @@ SIGNATURES = {
     "dsmgp_fit": (C.c_int, [_ctx, _dp, _ip, _dp]),
     "dsmgp_append_rows": (C.c_int, [_ctx, _dp, _dp, C.c_int64, C.c_int32, _lp, _lp, _dp, _dp, _ip, _dp]),
     "dsmgp_append_stats": (C.c_int, [_ctx, _lp]),
+    "dsmgp_add_rows_keep_test": (C.c_int, [_ctx, _dp, _dp, C.c_int64, C.c_int32, _lp, _lp, _dp, _dp, _ip, _dp]),
+    "dsmgp_resume_stats": (C.c_int, [_ctx, _lp]),
+    "dsmgp_download_vt": (C.c_int, [_ctx, C.c_int32, _dp, C.c_int64]),
     "dsmgp_set_test": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, _lp, _lp]),
     "dsmgp_set_tree": (C.c_int, [_ctx, C.c_int64, C.POINTER(C.c_int8), _lp, _lp, _lp, _dp, C.c_int64, _lp]),
     "dsmgp_set_test_routed": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32]),
@@ -264,11 +267,13 @@ class Context:
         self._chk(self.lib.dsmgp_fit(self.h, mll.ctypes.data_as(_dp), info.ctypes.data_as(_ip), C.byref(sec)))
         return mll, info, sec.value
 
-    def append_rows(self, X_new, y_new, add_ptr, add_idx, mean=None):
+    def append_rows(self, X_new, y_new, add_ptr, add_idx, mean=None, keep_test=False):
         """Append training rows to the fitted model (dsmgp_append_rows): leaf l takes the rows X_new[add_idx[add_ptr[l]:add_ptr[l + 1]]]
         behind its list; mean: the leaves' means from now on (None = unchanged).  Every factor owner keeps the leading blocks of
         its factor and factorises the rest.  Returns (mll[L], info[L], device_seconds) like fit.  On DSMGP_E_NOMEM the context
-        holds the grown table without a fit (`fit()` refits it in full) unless the message says the context is unchanged."""
+        holds the grown table without a fit (`fit()` refits it in full) unless the message says the context is unchanged.
+        keep_test=True (dsmgp_add_rows_keep_test): a resident test set stays resident and the next predict_run resumes K_tn L^-T
+        from the block columns the call kept (resume_stats); the set is dropped only where its new arena does not fit."""
         X_new, px = _f64_fortran(np.atleast_2d(np.asarray(X_new, dtype=np.float64)))
         y_new, py = _f64(np.atleast_1d(y_new))
         if X_new.ndim != 2 or X_new.shape[1] != self.D or y_new.shape != (X_new.shape[0],):
@@ -287,16 +292,20 @@ class Context:
         mll = np.empty(self.L)
         info = np.empty(self.L, dtype=np.int32)
         sec = C.c_double(0.0)
-        rc = self.lib.dsmgp_append_rows(self.h, px, py, X_new.shape[0], X_new.shape[1], p0, p1, pm, mll.ctypes.data_as(_dp),
-                                        info.ctypes.data_as(_ip), C.byref(sec))
+        call = self.lib.dsmgp_add_rows_keep_test if keep_test else self.lib.dsmgp_append_rows
+        rc = call(self.h, px, py, X_new.shape[0], X_new.shape[1], p0, p1, pm, mll.ctypes.data_as(_dp), info.ctypes.data_as(_ip),
+                  C.byref(sec))
         msg = self.lib.dsmgp_last_error(self.h).decode() if rc != 0 else ""
         if rc == 0 or (rc == E_NOMEM and "the context is unchanged" not in msg):
             # DSMGP_E_NOMEM from the new arenas: the library holds the grown data and leaf table already (and no fit), and the
             # shapes follow it, so that fit / loo / targets_fetch of a caller that goes on with this context have the right lengths
             self.leaf_n = self.leaf_n + np.diff(add_ptr)
             self.n_obs = int(self.leaf_n.sum())
-            self.route_total = 0
-            self.n_t = 0
+            # keep_test: the mirror of the resident test set stays, unless the library had none or had to drop it
+            if not (keep_test and rc == 0 and not self.resume_stats()["test_set_dropped"]
+                    and self.lib.dsmgp_routes(self.h, None, None) == 0):
+                self.route_total = 0
+                self.n_t = 0
             self.targets_Q = 0
         self._chk(rc)
         return mll, info, sec.value
@@ -309,6 +318,23 @@ class Context:
         out = np.zeros(len(self.APPEND_STAT_NAMES), dtype=np.int64)
         self._chk(self.lib.dsmgp_append_stats(self.h, out.ctypes.data_as(_lp)))
         return {k: int(v) for k, v in zip(self.APPEND_STAT_NAMES, out)}
+
+    RESUME_STAT_NAMES = ("leaves_kept", "block_columns_kept", "bytes_relocated", "block_columns_swept", "leaves_from_block_0",
+                         "test_set_dropped")
+
+    def resume_stats(self):
+        """What the last append_rows(keep_test=True) kept of the resident test set and what the predict_run after it swept
+        (dsmgp_resume_stats): a dict over RESUME_STAT_NAMES; block_columns_swept is -1 until that predict_run has run."""
+        out = np.zeros(len(self.RESUME_STAT_NAMES), dtype=np.int64)
+        self._chk(self.lib.dsmgp_resume_stats(self.h, out.ctypes.data_as(_lp)))
+        return {k: int(v) for k, v in zip(self.RESUME_STAT_NAMES, out)}
+
+    def download_vt(self, leaf, nt, n):
+        """K_tn L^-T of one leaf over its nt routed rows and its n training rows, (nt, n) in Fortran order (dsmgp_download_vt);
+        needs predict_run on the current fit."""
+        V = np.empty((int(nt), int(n)), order="F")
+        self._chk(self.lib.dsmgp_download_vt(self.h, int(leaf), V.ctypes.data_as(_dp), max(1, int(nt))))
+        return V
 
     def _test_matrix(self, Xt):
         """The test rows as the ABI reads them (n_t x D doubles, column-major); a matrix of another width is refused HERE,

@@ -9,6 +9,8 @@ All per-leaf numerics (Gram, Cholesky, alpha, mll, predictive moments, gradients
 libdsmgp_hip.so through `hipabi.Context`; this module only holds the tree logic the reference keeps in
 scalar Julia code (routing, log-domain mixture aggregation, weights), plus leaf sharding across ranks.
 """
+import inspect
+
 import numpy as np
 
 try:
@@ -525,12 +527,14 @@ def fit(model, tau=0.05):
 class AppendSeconds(float):
     """What `add_data` returns: the device seconds of the call.  `.fallback`: the new factors did not fit beside the old ones
     (DSMGP_E_NOMEM) and the grown table was fitted from scratch instead; `.stats`: `Context.append_stats()` of the call (None
-    after a fallback)."""
+    after a fallback); `.resume_stats`: `Context.resume_stats()` where the call kept the resident test set (`keep_test=True`),
+    else None."""
     fallback = False
     stats = None
+    resume_stats = None
 
 
-def add_data(model, x_new, y_new, tau=0.05):
+def add_data(model, x_new, y_new, tau=0.05, keep_test=False):
     """Observe new rows and add them to a fitted model without refactorising it (`dsmgp_append_rows`): the step after an
     acquisition.  The rows are routed through the model's own tree (region membership (lb, ub] per split, the rule of `route`; a
     sum node sends a row to every child, a kernel vector to every GP of the region; a row beyond a split node's last threshold
@@ -539,7 +543,10 @@ def add_data(model, x_new, y_new, tau=0.05):
     `meanFun` is kept), the overlap matrix is recomputed, and every leaf that received rows continues its factorisation from the
     blocks it keeps.  Sum-node weights stay as they are: `update(model)` is the caller's next step, as after `fit`.  The next
     `fit(model, tau)` re-derives the sharing decisions and uploads the leaf table, not the data.  Returns `AppendSeconds`;
-    raises `LinAlgError` like `fit`.  `tau`: the sharing threshold of the fallback fit."""
+    raises `LinAlgError` like `fit`.  `tau`: the sharing threshold of the fallback fit.
+    `keep_test=True` (`dsmgp_add_rows_keep_test`, where the context's `append_rows` takes the keyword): the test set the context
+    holds stays resident, so the next `predict` / `predict_gradients` / `prediction(..., full_cov=True)` on the same `xtest` goes
+    straight to `predict_run`, which resumes `K_tn L^-T` from the block columns the call kept."""
     gp = model if isinstance(model, GaussianProcess) else None
     target = model.model if gp is not None else model
     if target.shard.world > 1:
@@ -578,7 +585,9 @@ def add_data(model, x_new, y_new, tau=0.05):
         default = getattr(lf.mean, "default", False) and add.size
         means.append(float(np.mean(y_all[obs])) if default else float(lf.mean.m))
 
-    def commit():
+    keeps = bool(keep_test) and "keep_test" in inspect.signature(ctx.append_rows).parameters
+
+    def commit(keep_routes=False):
         target.x = np.asfortranarray(np.vstack([target.x, xn]))
         target.y = y_all
         for lf, obs, mu in zip(target.leaves, grown, means):
@@ -590,12 +599,13 @@ def add_data(model, x_new, y_new, tau=0.05):
             target.D = get_overlap(target.root, target.L)
         if gp is not None:
             gp.N = int(target.x.shape[0])
-        target._route_cache = None
+        if not keep_routes:
+            target._route_cache = None
         target._scores_on_device = False
         target._schedule = None          # the next fit re-derives the sharing decisions and uploads the leaf table (not the data)
 
     try:
-        mll_, info, sec = ctx.append_rows(xn, yn, ptr, idx, means)
+        mll_, info, sec = ctx.append_rows(xn, yn, ptr, idx, means, keep_test=True) if keeps else ctx.append_rows(xn, yn, ptr, idx, means)
     except hipabi.DsmgpError as e:
         if e.code != hipabi.E_NOMEM:
             raise
@@ -604,12 +614,17 @@ def add_data(model, x_new, y_new, tau=0.05):
         out = AppendSeconds(_fit(target, tau))
         out.fallback = True
         return out
-    commit()
+    commit(keep_routes=keeps)
     target.leaf_mll = np.ascontiguousarray(mll_, dtype=np.float64)
     target.leaf_info = np.asarray(info, dtype=np.int32)
     target.last_fit_seconds = sec
     out = AppendSeconds(sec)
     out.stats = ctx.append_stats() if hasattr(ctx, "append_stats") else None
+    if keeps:
+        # the routes of the test rows are what they were (the tree did not change); `uploaded` as the context left it
+        out.resume_stats = ctx.resume_stats()
+        if target._route_cache is not None and out.resume_stats["test_set_dropped"]:
+            target._route_cache["uploaded"] = False
     bad = np.flatnonzero(target.leaf_info != 0)
     if bad.size:
         raise np.linalg.LinAlgError(f"leaf {int(bad[0])}: leading minor of order {int(target.leaf_info[bad[0]])} "

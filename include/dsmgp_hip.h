@@ -181,6 +181,57 @@ int dsmgp_append_rows(dsmgp_ctx* ctx, const double* X_new /* m x D column-major,
 #define DSMGP_N_APPEND_STATS 6
 int dsmgp_append_stats(dsmgp_ctx* ctx, int64_t* out /* DSMGP_N_APPEND_STATS, of the last dsmgp_append_rows */);
 
+/* ---- the same, for the loop acquire -> add the observed point -> predict again ON THE SAME CANDIDATES: the resident test set
+ *      stays resident and dsmgp_predict_run resumes K_tn L^-T instead of sweeping it from block column 0.
+ *      Arguments, results, refusals, guarantees, factor storage paths and dsmgp_append_stats: those of dsmgp_append_rows (one
+ *      body).  Without a resident test set the call IS dsmgp_append_rows.  With one:
+ *      The test set: appended training rows change neither the tree nor the leaf indices, so the routes are the same: the test
+ *      rows, the CSR and the per-row entry index stay as they are (dsmgp_routes returns the same arrays before and after), and
+ *      the second half of the registration runs again on the grown plan (per-leaf sizes, arenas, gathered rows, task lists).
+ *      Dropped and rebuilt on demand as after any registration: the buffers of dsmgp_predict_gradients, dsmgp_predict_cov,
+ *      dsmgp_predict_targets, dsmgp_aggregate* and the lists of a joint fit.
+ *      Kept columns: where dsmgp_predict_run had run on the fit the call found, every leaf with routed rows keeps the leading
+ *      128 keep columns of its K_tn L^-T, keep = the leading blocks kept of the factor it reads: floor(n_old / 128) for an owner
+ *      that receives rows, every block for a leaf without additions, 0 where the old fit reported info != 0; a COPY leaf,
+ *      whether it stays one or gets a factor of its own, the kept blocks of the factor it reads.  Without such a run keep = 0
+ *      everywhere: the test set is still kept, only the sweep is full.  A second call before any dsmgp_predict_run: a leaf's
+ *      count can only shrink (the minimum of what it had and what this call keeps).
+ *      Storage of K_tn L^-T (ntpad x npad per leaf, column-major, ld = ntpad: a grown leaf gains columns at the end and its kept
+ *      columns stay one contiguous run): in place when no leaf's offset or padded sizes change -- the arena stays and no byte
+ *      of it moves; otherwise a new arena is allocated while the old one is alive, the kept runs move in one launch and the old
+ *      arena is freed (never a move inside one arena).  This happens after the old factors have been freed: the peak of the
+ *      call is the larger of "old + new factors + old K_tn L^-T" and "new factors + old + new K_tn L^-T".  If the new arena does
+ *      not fit, the call still returns 0 (the fit is good), the test set is dropped, dsmgp_resume_stats says so and the next
+ *      dsmgp_predict_run returns DSMGP_E_STATE, as after dsmgp_append_rows.  The failure paths of the append itself drop the
+ *      test set as dsmgp_append_rows does.
+ *      dsmgp_predict_run after the call: for every leaf the block steps k < keep are not run; steps keep .. nb-1 run through
+ *      the sweep's own kernels and write their block columns whole (block column keep is the partial old block: stale).  The
+ *      moment sums over the kept columns, which the sweep's epilogues would have added, are formed first against the current
+ *      z, each kept tile read once for both sums, in chunks of a constant number of block columns added in ascending order.
+ *      One-shot: it applies to the fit the call made; dsmgp_fit and the dsmgp_predict_run that used it end it, and a
+ *      dsmgp_predict_run after a later dsmgp_fit returns exactly what it returns after a fresh dsmgp_set_test of the same rows.
+ *      After the resumed run every reader of K_tn L^-T and of the moments works on the grown model (dsmgp_predict_fetch,
+ *      dsmgp_predict_cov, dsmgp_predict_gradients, dsmgp_predict_targets, dsmgp_aggregate*, dsmgp_download_vt).  A repeated
+ *      dsmgp_predict_run leaves the same bits; same inputs on the same state give the same bits (fixed summation order, no
+ *      atomics).  NOT promised: that mu / var of a leaf without additions keep their bits (their sums are formed again), or
+ *      that the results equal a sweep from block 0 to the bit.
+ *      dsmgp_resume_stats (of the last dsmgp_add_rows_keep_test and the dsmgp_predict_run that used it; DSMGP_E_STATE before the
+ *      first): [0] leaves with routed rows that kept columns, [1] block columns of K_tn L^-T kept, summed over those leaves,
+ *      [2] bytes of K_tn L^-T relocated (0 = in place), [3] block columns swept by the resumed dsmgp_predict_run, summed over the
+ *      leaves with routed rows (-1 until it has run), [4] leaves swept from block 0, [5] 1 if the test set had to be dropped
+ *      for lack of memory. */
+int dsmgp_add_rows_keep_test(dsmgp_ctx* ctx, const double* X_new /* m x D column-major, ld = m */, const double* y_new /* m */,
+                             int64_t m, int32_t D, const int64_t* add_ptr /* L+1 */,
+                             const int64_t* add_idx /* positions 0..m-1 in X_new, strictly ascending per leaf */,
+                             const double* mean /* L: the leaves' means from now on; NULL = unchanged */,
+                             double* mll_out /* L, may be NULL */, int32_t* info_out /* L, may be NULL */, double* seconds /* may be NULL */);
+#define DSMGP_N_RESUME_STATS 6
+int dsmgp_resume_stats(dsmgp_ctx* ctx, int64_t* out /* DSMGP_N_RESUME_STATS */);
+/*      Inspection, like dsmgp_download_factor: K_tn L^-T of one leaf over its routed rows and its n real columns.  Needs
+ *      dsmgp_predict_run on the current fit (DSMGP_E_STATE).  DSMGP_E_ARG: leaf out of range, ld < nt.  A leaf without routed
+ *      rows: success, nothing written. */
+int dsmgp_download_vt(dsmgp_ctx* ctx, int32_t leaf, double* V_out /* nt x n column-major */, int64_t ld);
+
 /* ---- prediction(gp, xtest) for every (leaf, routed test row): src/gaussianprocess.jl:110-137
  *      mu  = m + Knt' alpha ; var = k(x*,x*) - |L^-1 k_n*|^2 + exp(2 logNoise)   (diag only; no clamp,
  *      the caller applies src/common.jl:137).  route_ptr/route_idx: per leaf, which rows of Xt.

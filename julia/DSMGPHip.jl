@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, append_rows!, append_stats, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
+export attach!, detach!, census, append_rows!, append_stats, resume_stats, download_vt, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -586,9 +586,12 @@ end
 row numbers of `Xnew`, strictly ascending per leaf.  `mean`: the constant mean of every leaf from now on (`nothing`: unchanged).
 Every factor owner keeps the leading ⌊n/128⌋ blocks of its factor and only the rest is factorised; a COPY leaf stays a COPY only
 where it received the rows of its source; the registered test set, the resident targets and the gradient lists are dropped.  Needs
-a current fit.  The node objects of the reference are not touched: the caller grows them.  Returns the device seconds."
+a current fit.  The node objects of the reference are not touched: the caller grows them.  Returns the device seconds.
+`keep_test=true` (dsmgp_add_rows_keep_test): the registered test set stays registered -- the routes of its rows do not change -- and
+the next prediction on the same rows resumes K_tn L⁻ᵀ from the block columns the call kept instead of sweeping it from block 0
+(`resume_stats`); the set is dropped only where its new arena does not fit."
 function append_rows!(s::Session, Xnew::AbstractMatrix, ynew::AbstractVector, add_ptr::AbstractVector{<:Integer},
-                      add_idx::AbstractVector{<:Integer}; mean::Union{Nothing,AbstractVector}=nothing)
+                      add_idx::AbstractVector{<:Integer}; mean::Union{Nothing,AbstractVector}=nothing, keep_test::Bool=false)
     X = Matrix{Float64}(Xnew)
     y = Vector{Float64}(ynew)
     m, Dm = size(X)
@@ -601,10 +604,17 @@ function append_rows!(s::Session, Xnew::AbstractMatrix, ynew::AbstractVector, ad
     M === nothing || length(M) == L || throw(DimensionMismatch("mean needs one entry per leaf"))
     sec = Ref{Float64}(0.0)
     mllv, info = s.leafmll, s.info
-    GC.@preserve X y ptr idx M mllv info chk(s, ccall(sym(:dsmgp_append_rows), Cint,
-        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{Float64}),
-        s.h, X, y, Int64(m), Int32(Dm), ptr, idx, M === nothing ? Ptr{Float64}(C_NULL) : pointer(M), mllv, info, sec))
-    s.testkey = UInt(0)
+    if keep_test
+        GC.@preserve X y ptr idx M mllv info chk(s, ccall(sym(:dsmgp_add_rows_keep_test), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{Float64}),
+            s.h, X, y, Int64(m), Int32(Dm), ptr, idx, M === nothing ? Ptr{Float64}(C_NULL) : pointer(M), mllv, info, sec))
+        resume_stats(s).test_set_dropped == 0 || (s.testkey = UInt(0))
+    else
+        GC.@preserve X y ptr idx M mllv info chk(s, ccall(sym(:dsmgp_append_rows), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{Float64}),
+            s.h, X, y, Int64(m), Int32(Dm), ptr, idx, M === nothing ? Ptr{Float64}(C_NULL) : pointer(M), mllv, info, sec))
+        s.testkey = UInt(0)
+    end
     s.targets = 0
     bad = findfirst(!=(0), info)
     bad === nothing || throw(PosDefException(Int(info[bad])))
@@ -619,6 +629,27 @@ function append_stats(s::Session)
     GC.@preserve out chk(s, ccall(sym(:dsmgp_append_stats), Cint, (Ptr{Cvoid}, Ptr{Int64}), s.h, out))
     return (owners_continued = out[1], leaves_untouched = out[2], bytes_relocated = out[3], block_columns_factorised = out[4],
             owners_restarted = out[5], copies_dissolved = out[6])
+end
+
+"resume_stats(s): what the last append_rows!(…; keep_test=true) kept of the registered test set and what the prediction after it
+swept (dsmgp_resume_stats), as a named tuple: leaves that kept columns of K_tn L⁻ᵀ, block columns kept, bytes relocated (0: in
+place), block columns swept by the resumed prediction (-1 until it has run), leaves swept from block 0, 1 if the test set had to be
+dropped for lack of memory."
+function resume_stats(s::Session)
+    out = zeros(Int64, 6)
+    GC.@preserve out chk(s, ccall(sym(:dsmgp_resume_stats), Cint, (Ptr{Cvoid}, Ptr{Int64}), s.h, out))
+    return (leaves_kept = out[1], block_columns_kept = out[2], bytes_relocated = out[3], block_columns_swept = out[4],
+            leaves_from_block_0 = out[5], test_set_dropped = out[6])
+end
+
+"download_vt(s, leaf): K_tn L⁻ᵀ of leaf `leaf` (1-based, the order of `s.leaves`) over its routed test rows and its training rows,
+`nt × n` (dsmgp_download_vt; inspection).  Needs a prediction on the current fit."
+function download_vt(s::Session, leaf::Integer)
+    nt = Int(s.testptr[leaf + 1] - s.testptr[leaf])
+    n = length(s.leaves[leaf].obs)
+    V = Matrix{Float64}(undef, nt, n)
+    GC.@preserve V chk(s, ccall(sym(:dsmgp_download_vt), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64), s.h, Int32(leaf - 1), V, Int64(max(nt, 1))))
+    return V
 end
 
 "targets_gradients(s; col_weight=nothing): hyper-parameter gradients of the weighted sum of the per-column log marginal likelihoods
