@@ -9,6 +9,7 @@
 #include "kernels_fused.hpp"
 #include "kernels_targets.hpp"
 #include "ctx_state.hpp"
+#include "dev_owner.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -51,8 +52,18 @@ struct LeafHost {
     int64_t route_off = 0;
 };
 
-// The one owner of a device array: every device allocation of the library outside the pool's arenas lives in one of these
-// and is freed by it.  `cap` is assigned in one place only, after a successful allocation (grow).
+// The large arenas and the reserved pool they may be carved from (dev_owner.hpp), on hipMalloc / hipFree.  A status of theirs
+// becomes an error code and a message in arena_status.
+struct HipMem {
+    static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void free(void* p) { (void)hipFree(p); }
+};
+using DevPool = dev_owner::Pool<HipMem>;
+using DevArena = dev_owner::Arena<HipMem>;
+
+// The one owner of a device array: every device allocation of the library that is not an arena or the pool (DevArena, DevPool)
+// lives in one of these and is freed by it -- nothing is outside an owner.  `cap` is assigned in one place only, after a
+// successful allocation (grow).
 template <class T>
 struct DevBuf {
     T* p = nullptr;
@@ -199,8 +210,7 @@ struct SweepLists {
     DevBuf<ReduceTask> red;
     std::vector<int> f8_off;                       // fused 8-block tasks per (lane, step), made on the device (build_sweep8_kernel);
     DevBuf<FusedTask8> f8;                         // empty where the sweep has none (the gradient pass)
-    double* slab = nullptr;                        // split-K workspace of all lanes (slab_grow)
-    size_t slab_cap = 0;                           // doubles
+    DevArena slab;                                 // split-K workspace of all lanes (grow-only)
 
     void clear() {           // empty lists; the allocations and the slab stay for the lists that replace them
         nsteps = 0;
@@ -209,8 +219,15 @@ struct SweepLists {
         red.clear();
         f8.clear();
     }
-    void release(dsmgp_ctx* c);
-    void drop(dsmgp_ctx* c, bool keep) { keep ? clear() : release(c); }
+    void release() {
+        nsteps = 0;
+        upd.release();
+        trsm.release();
+        red.release();
+        f8.release();
+        slab.put();
+    }
+    void drop(bool keep) { keep ? clear() : release(); }
 };
 
 // Collects the update tiles of one block step and splits their K range over several workgroups when
@@ -495,10 +512,10 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     DevBuf<KParam> d_kp;
     DevBuf<double> d_l2;
 
-    double* arenaF = nullptr;
-    double* arenaDinv = nullptr;
-    double* arenaVec = nullptr;     // per leaf: yc, w, z, alpha (4 x npad)
-    double* arenaXg = nullptr;
+    // the large arenas: each owns its doubles or knows that they are a piece of the pool (dev_owner.hpp)
+    DevArena arenaF, arenaDinv;
+    DevArena arenaVec;              // per leaf: yc, w, z, alpha (4 x npad)
+    DevArena arenaXg;
     DevBuf<int> d_info;
     DevBuf<int> d_owner;            // per leaf: the leaf whose factor (and info slot) it uses (dsmgp_fit_exchange packs info per owner)
     DevBuf<double> d_mll;
@@ -541,11 +558,10 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     // Optional device pool (dsmgp_reserve): the large arenas are carved out of one allocation made once, in stack
     // order plan < test < gradients, instead of hipMalloc/hipFree per leaf table -- the driver clears memory on
     // allocation (5 s per 230 GB group measured), which dominated the streaming mode's wall time.
-    char* pool_base = nullptr;
-    size_t pool_cap = 0, pool_top = 0, pool_mark_plan = 0;
-    double* slabF[MAX_LANES] = {};  // split-K workspace of the factorisation, per lane
+    DevPool pool;
+    DevArena slabF[MAX_LANES];      // split-K workspace of the factorisation, per lane
     StepLists phaseJ[MAX_LANES][2]; // the same with the resident test rows riding along (built by set_test)
-    double* slabJ[MAX_LANES] = {};
+    DevArena slabJ[MAX_LANES];
     double alg_flops_joint = 0.0;
     bool joint = true;              // fit advances the resident test rows too
     int ncu = 256;
@@ -576,30 +592,28 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     int64_t n_t = 0;
     DevBuf<int64_t> d_route_ptr, d_route_idx;
     std::vector<int64_t> route_ptr;
-    double* arenaVt = nullptr;
-    size_t arenaVt_count = 0;       // doubles allocated for the K_tn arena: a test set that replaces another takes it over while it
-                                    // fits (releasing ~10 GB and asking the driver for them again took up to 0.6 s of a 0.06 s predict)
-    // capacities of the test set's pool-carved arenas (arena_fit: kept across registrations, freed with the plan)
-    size_t cap_Xt = 0, cap_PV = 0;
+    DevArena arenaVt;               // K_tn: a test set that replaces another takes the arenas of the old one over while it fits
+                                    // (DevArena::fit; releasing ~10 GB and asking the driver for them again took up to 0.6 s of a
+                                    // 0.06 s predict)
     // pinned host staging for the uploads of a registration (stage_upload): the lists of a test set are ~10 MB at the headline
     // model; through hipMemcpy from pageable vectors they took 9 ms of a 25 ms registration and left the runtime busy behind them
     char* stage = nullptr;
     size_t stage_cap = 0, stage_top = 0;
     DevBuf<SweepSeg> psegs;         // (leaf, block step) pairs of the sweep's fused steps: build_sweep8_kernel makes the tasks
-    double* arenaXt = nullptr;
-    double* arenaPV = nullptr;      // mu | var (route order, unpadded) | macc | sacc (padded accumulators of the sweep)
+    DevArena arenaXt;
+    DevArena arenaPV;               // mu | var (route order, unpadded) | macc | sacc (padded accumulators of the sweep)
     size_t acc_off = 0, acc_count = 0;
     DevBuf<PredTask> ptasks_slow;   // test tiles of leaves whose z is not produced during the factorisation
     DevBuf<GramTask> pgram;         // K_tn tiles the standalone sweep reads from memory (all of them only when D > 32)
     DevBuf<GramTask> pgram0;        // ... of the joint fit when the Gram is fused: block column 0 only
     DevBuf<PredTask> ptasks;
     SweepLists psweep;              // V^T = K_tn L^-T; in the block steps that run fused: update + solve of eight 16-row blocks per task
-    double* arenaCov = nullptr;     // ntpad x ntpad of the leaf dsmgp_predict_cov was last asked for (grow-only, allocated on first use,
-    size_t cap_Cov = 0;             //   from the pool when there is one; goes with the test set: free_test).  Not part of bytes_needed.
+    DevArena arenaCov;              // ntpad x ntpad of the leaf dsmgp_predict_cov was last asked for (grow-only, allocated on first use,
+                                    //   from the pool when there is one; goes with the test set: free_test).  Not part of bytes_needed.
     DevBuf<PredCovTask> pcov;       // its lower tiles, rebuilt per call
     // input gradients of the predictive moments (dsmgp_predict_gradients): lists rebuilt per call, buffers allocated on first use
-    double* arenaB = nullptr;       // B = Vt L^-1 (rows K_y^-1 k_t), ntpad x npad per leaf with routed rows, laid out like arenaVt (grow-only,
-    size_t cap_B = 0;               //   from the pool when there is one; goes with the test set: free_test).  Not part of bytes_needed.
+    DevArena arenaB;                // B = Vt L^-1 (rows K_y^-1 k_t), ntpad x npad per leaf with routed rows, laid out like arenaVt (grow-only,
+                                    //   from the pool when there is one; goes with the test set: free_test).  Not part of bytes_needed.
     DevBuf<PredBetaTask> pgbeta;    // the tiles of B
     DevBuf<PredGradTask> pgtasks;   // (test tile, slab of training rows) pairs
     DevBuf<PredGradFinTask> pgfin;  // test tiles
@@ -609,8 +623,7 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
 
     // several target columns on the current factors (dsmgp_solve_targets / dsmgp_predict_targets, kernels_targets.hpp): allocated on
     // first use, not part of bytes_needed, dropped with the plan (free_targets); what depends on the test set goes with it (free_test)
-    double* arenaT = nullptr;       // per leaf Yc | Z, npad x Qpad each (grow-only, from the pool when there is one)
-    size_t cap_T = 0;
+    DevArena arenaT;                // per leaf Yc | Z, npad x Qpad each (grow-only, from the pool when there is one)
     int tg_Q = 0;                   // columns of the resident Z
     std::vector<size_t> toff;       // per leaf: offset of its Yc in arenaT
     DevBuf<long long> d_toff;
@@ -622,8 +635,7 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     DevBuf<double> d_tmu;           // mu, route_total x Q (ld = route_total)
     // dsmgp_mll_columns_gradients: A = L^-T Z per leaf, npad x Qpad at offset toff / 2 of an arena of its own (allocated on first use, from
     // the pool when there is one, not part of bytes_needed, dropped where arenaT is); its task lists are rebuilt per call
-    double* arenaA = nullptr;
-    size_t cap_A = 0;
+    DevArena arenaA;
     DevBuf<TargetsATask> tga;
     DevBuf<GradTaskTg> tgdot;
     DevBuf<FrobTask> tgfrob;
@@ -632,9 +644,7 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     DevBuf<double> d_tgw, d_tgpart; // the weights (L x Q); frob | contraction x gstride | 2 L | ArdLinear 2 D per column group | D per leaf
     // dsmgp_loo_columns / dsmgp_loo_columns_gradients: H = K_y^-1 diag(sqrt W), npad^2 per leaf, and U = K_y^-1 (A / d), npad x Qpad
     // at offset toff / 2, in arenas of their own (the rule of arenaA); the lists are rebuilt per call
-    double* arenaHc = nullptr;
-    double* arenaU = nullptr;
-    size_t cap_Hc = 0, cap_U = 0;
+    DevArena arenaHc, arenaU;
     DevBuf<LooColsTask> lcleaf;
     DevBuf<GinvTask> lcginv;
     DevBuf<LooColsUTask> lcu;
@@ -656,8 +666,7 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
 
     // gradients (built on first use)
     std::vector<char> grad_active;  // dsmgp_set_gradient_leaves: leaves whose gradients are wanted (empty = all)
-    double* arenaX = nullptr;       // Xt = L^-T per factor owner, npad x npad
-    size_t arenaX_count = 0;
+    DevArena arenaX;                // Xt = L^-T per factor owner, npad x npad (kept only while the total is exactly the same)
     DevBuf<TransTask> gtrans;
     SweepLists ginv;                // Xt = L^-T (no fused tasks)
     DevBuf<FrobTask> gfrob;
@@ -678,7 +687,7 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     DevBuf<double> d_loo;           // row-sum planes of every owner | mu | var (obs_ptr[L] each) | lpd (L).  Allocated on first use,
                                     // dropped with the leaf table (free_grad); not part of bytes_needed
     // gradients of the LOO density (dsmgp_loo_gradients): lists and arena built on first use, dropped with the leaf table (free_grad)
-    double* arenaH = nullptr;       // H = K_y^-1 diag(sqrt w) per computing leaf, npad x npad
+    DevArena arenaH;                // H = K_y^-1 diag(sqrt w) per computing leaf, npad x npad
     DevBuf<double> d_lgvec;         // [alpha | u | sqrt w | alpha / (d sqrt w)] per computing leaf, npad each
     DevBuf<LooVecTask> lgvec;
     DevBuf<GinvTask> lginv;
@@ -778,9 +787,6 @@ int dev_upload(dsmgp_ctx* ctx, DevBuf<T>& buf, const std::vector<T>& host) {
     return copy_upload(ctx, buf.p, host.data(), host.size() * sizeof(T));
 }
 
-bool in_pool(const dsmgp_ctx* c, const void* p) {
-    return c->pool_base && (const char*)p >= c->pool_base && (const char*)p < c->pool_base + c->pool_cap;
-}
 // `bytes` from host memory to the device through the context's PINNED staging buffer, asynchronously on the context's stream: the
 // caller's memory is free again on return, the copy is done once the stream is synchronised (stage_done, which every user calls
 // before it returns).  Grows on demand; growing waits for the copies in flight.
@@ -814,44 +820,16 @@ int stage_upload_list(dsmgp_ctx* c, DevBuf<T>& buf, const std::vector<T>& host) 
     return stage_upload(c, buf.p, host.data(), host.size() * sizeof(T));
 }
 
-// `count` doubles for one of the large arenas: from the pool when there is one, else its own allocation
-int arena_get(dsmgp_ctx* c, double*& p, size_t count) {
-    const size_t bytes = std::max<size_t>(1, count) * sizeof(double);
-    if (c->pool_base) {
-        const size_t off = (c->pool_top + 255) & ~size_t(255);
-        if (off + bytes > c->pool_cap)
-            return fail(c, DSMGP_E_NOMEM, "reserved device pool too small: need " + std::to_string((off + bytes) >> 20) +
-                                              " MiB, pool has " + std::to_string(c->pool_cap >> 20) + " MiB");
-        p = reinterpret_cast<double*>(c->pool_base + off);
-        c->pool_top = off + bytes;
-        return 0;
-    }
-    HIPCHK(c, hipMalloc(&p, bytes));
-    return 0;
-}
-void arena_put(dsmgp_ctx* c, double*& p) {
-    if (p && !in_pool(c, p)) (void)hipFree(p);
-    p = nullptr;
-}
-// A grow-only workspace of `count` doubles: kept while it holds them, else put back before the new one is asked for.  `cap` is
-// set only once the new one is there: on failure the workspace is empty (p null, cap 0).
-int slab_grow(dsmgp_ctx* c, double*& p, size_t& cap, size_t count) {
-    if (count == 0 || (p && cap >= count)) return 0;
-    arena_put(c, p);
-    cap = 0;
-    if (int rc = arena_get(c, p, count)) return rc;
-    cap = count;
-    return 0;
-}
-
-void SweepLists::release(dsmgp_ctx* c) {
-    nsteps = 0;
-    upd.release();
-    trsm.release();
-    red.release();
-    f8.release();
-    arena_put(c, slab);
-    slab_cap = 0;
+// Where the large arenas come from: the reserved pool when there is one, else (null) allocations of their own
+DevPool* arena_pool(dsmgp_ctx* c) { return c->pool.active() ? &c->pool : nullptr; }
+// What DevArena::get / grow / fit / exact answered, as the library's error code with the text in c->err
+int arena_status(dsmgp_ctx* c, int status) {
+    if (status == 0) return 0;
+    if (status == dev_owner::POOL_FULL)
+        return fail(c, DSMGP_E_NOMEM, "reserved device pool too small: need " + std::to_string(c->pool.need >> 20) +
+                                          " MiB, pool has " + std::to_string(c->pool.cap >> 20) + " MiB");
+    const hipError_t e = (hipError_t)status;
+    return fail(c, e == hipErrorOutOfMemory ? DSMGP_E_NOMEM : DSMGP_E_HIP, std::string("hipMalloc of an arena: ") + hipGetErrorString(e));
 }
 
 // An UpdateSplitter with the context's scheduling settings for a plan of `nl` lanes
@@ -888,7 +866,7 @@ int pack_sweep(dsmgp_ctx* c, SweepLists& S, std::vector<SweepLane>& lanes, int (
         nr += q.U.red.size();
         nt += q.trsm.size();
     }
-    if (int rc = slab_grow(c, S.slab, S.slab_cap, slabs * TB * TB)) return rc;
+    if (int rc = arena_status(c, S.slab.grow(arena_pool(c), slabs * TB * TB))) return rc;
     if (int rc = dev_reserve(c, S.upd, nu)) return rc;
     if (int rc = dev_reserve(c, S.red, nr)) return rc;
     if (int rc = dev_reserve(c, S.trsm, nt)) return rc;
@@ -901,7 +879,7 @@ int pack_sweep(dsmgp_ctx* c, SweepLists& S, std::vector<SweepLane>& lanes, int (
     int bu = 0, br = 0, bt = 0;
     for (int q = 0; q < nl; ++q) {
         SweepLane& ln = lanes[(size_t)q];
-        ln.U.bind(S.slab + bs * TB * TB);
+        ln.U.bind(S.slab.p + bs * TB * TB);
         for (int k = 0; k < nsteps; ++k) {
             const size_t v = (size_t)q * (size_t)nsteps + (size_t)k;
             S.upd_off[v] = bu + ln.upd_at[(size_t)k];
@@ -943,8 +921,8 @@ void free_grad_lists(dsmgp_ctx* c) {
 }
 
 void free_grad(dsmgp_ctx* c) {
-    c->ginv.release(c);
-    arena_put(c, c->arenaX);
+    c->ginv.release();
+    c->arenaX.put();
     c->gtrans.release();
     c->gfrob.release();
     c->gdot.release();
@@ -954,7 +932,7 @@ void free_grad(dsmgp_ctx* c) {
     c->lleaf.release();
     c->d_loo.release();
     c->invalidate(P_GRAD_LISTS | P_XINV | P_LOO_LISTS | P_LG_LISTS);
-    arena_put(c, c->arenaH);
+    c->arenaH.put();
     c->d_lgvec.release();
     c->lgvec.release();
     c->lginv.release();
@@ -967,8 +945,7 @@ void free_grad(dsmgp_ctx* c) {
 // the resident target columns (dsmgp_solve_targets): they go with the plan -- a new leaf table, new training data, dsmgp_release --
 // and, under a reserved pool, with whatever resets the pool's stack below them
 void free_targets(dsmgp_ctx* c) {
-    arena_put(c, c->arenaT);
-    c->cap_T = 0;
+    c->arenaT.put();
     c->invalidate(P_TG_LISTS);
     c->tg_Q = c->tg_qpad = 0;
     c->d_toff.release();
@@ -978,8 +955,7 @@ void free_targets(dsmgp_ctx* c) {
     c->tfwd.release();
     c->tmu.release();
     c->d_tmu.release();
-    arena_put(c, c->arenaA);
-    c->cap_A = 0;
+    c->arenaA.put();
     c->tga.release();
     c->tgdot.release();
     c->tgfrob.release();
@@ -987,9 +963,8 @@ void free_targets(dsmgp_ctx* c) {
     c->tgardlin.release();
     c->d_tgw.release();
     c->d_tgpart.release();
-    arena_put(c, c->arenaHc);
-    arena_put(c, c->arenaU);
-    c->cap_Hc = c->cap_U = 0;
+    c->arenaHc.put();
+    c->arenaU.put();
     c->lcleaf.release();
     c->lcginv.release();
     c->lcu.release();
@@ -1019,15 +994,14 @@ void free_tree(dsmgp_ctx* c) {
 void free_test(dsmgp_ctx* c, bool keep = false);
 void free_plan(dsmgp_ctx* c) {
     drop_graphs(c);
-    if (c->pool_base) {      // stack order: everything above the plan goes with it
+    if (c->pool.active()) {  // stack order: everything above the plan goes with it
         free_test(c);
-        c->pool_top = 0;
-        c->pool_mark_plan = 0;
+        c->pool.reset();
     }
-    arena_put(c, c->arenaF);
-    arena_put(c, c->arenaDinv);
-    arena_put(c, c->arenaVec);
-    arena_put(c, c->arenaXg);
+    c->arenaF.put();
+    c->arenaDinv.put();
+    c->arenaVec.put();
+    c->arenaXg.put();
     c->d_info.release();
     c->d_owner.release();
     c->d_mll.release();
@@ -1035,7 +1009,7 @@ void free_plan(dsmgp_ctx* c) {
     c->gram.release();
     for (auto& lane : c->phase)
         for (auto& ph : lane) ph.drop(false);
-    for (auto& sl : c->slabF) arena_put(c, sl);
+    for (auto& sl : c->slabF) sl.put();
     c->fwd.release();
     c->bwd.release();
     c->dinvc_prefix.release();
@@ -1046,48 +1020,40 @@ void free_plan(dsmgp_ctx* c) {
     c->invalidate(P_PLAN);
 }
 
-// keep: a registration that replaces another -- every buffer of the old test set stays allocated for the new one (they are
-// emptied, not freed).  With a device pool the arenas are carved out of the pool's stack and go with its top.
-void free_test(dsmgp_ctx* c, bool keep) {
+// What was made from a registered test set -- its arenas, the sweep's, the joint fit's and the prediction's lists, the aggregation
+// buffers -- without the set's inputs (free_test).  keep: every buffer stays allocated for what replaces it (emptied, not freed).
+// With a device pool the arenas are carved out of the pool's stack and go with its top, so nothing is kept: the answer is the
+// `keep` that held.
+bool free_test_products(dsmgp_ctx* c, bool keep) {
     drop_graphs(c);
-    if (c->pool_base) {      // the gradient arenas sit above (or would be clobbered below) the test arenas
+    if (c->pool.active()) {  // the gradient arenas sit above (or would be clobbered below) the test arenas
         free_grad(c);
         free_targets(c);
-        c->pool_top = c->pool_mark_plan;
+        c->pool.reset_to_mark();
         keep = false;
     }
-    c->dXt.drop(keep);
-    c->d_route_ptr.drop(keep);
-    c->d_route_idx.drop(keep);
-    c->d_row_ptr.drop(keep);
-    c->d_row_ent.drop(keep);
-    c->d_ent_leaf.drop(keep);
     c->d_agg_part.drop(keep);
     c->d_agg_coef.drop(keep);
     c->d_agg_group.drop(keep);
     c->d_agg_out.drop(keep);
     if (!keep) {
-        arena_put(c, c->arenaVt);
-        c->arenaVt_count = 0;
-        arena_put(c, c->arenaXt);
-        arena_put(c, c->arenaPV);
-        c->cap_Xt = c->cap_PV = 0;
+        c->arenaVt.put();
+        c->arenaXt.put();
+        c->arenaPV.put();
     }
     c->pgram.drop(keep);
     c->pgram0.drop(keep);
     c->ptasks.drop(keep);
     c->ptasks_slow.drop(keep);
-    c->psweep.drop(c, keep);
+    c->psweep.drop(keep);
     c->psegs.drop(keep);
     c->kept_tasks.drop(keep);
     c->kept_fin.drop(keep);
     c->d_kept_part.drop(keep);
     c->resume_armed = c->sweep_resumed = false;
-    arena_put(c, c->arenaCov);
-    c->cap_Cov = 0;
+    c->arenaCov.put();
     c->pcov.drop(keep);
-    arena_put(c, c->arenaB);
-    c->cap_B = 0;
+    c->arenaB.put();
     c->pgbeta.drop(keep);
     c->pgtasks.drop(keep);
     c->pgfin.drop(keep);
@@ -1097,8 +1063,21 @@ void free_test(dsmgp_ctx* c, bool keep) {
     c->d_tmu.drop(keep);
     for (auto& lane : c->phaseJ)
         for (auto& ph : lane) ph.drop(keep);
-    for (auto& sl : c->slabJ) arena_put(c, sl);
+    for (auto& sl : c->slabJ) sl.put();
     c->invalidate(P_TEST);
+    return keep;
+}
+
+// The registered test set: what was made from it, and its inputs -- the rows, the route CSR, the row / entry index.  keep: a
+// registration that replaces another.
+void free_test(dsmgp_ctx* c, bool keep) {
+    keep = free_test_products(c, keep);
+    c->dXt.drop(keep);
+    c->d_route_ptr.drop(keep);
+    c->d_route_idx.drop(keep);
+    c->d_row_ptr.drop(keep);
+    c->d_row_ent.drop(keep);
+    c->d_ent_leaf.drop(keep);
 }
 
 void free_plan_and_test(dsmgp_ctx* c) {       // new training data, leaf table, sharing schedule, plan option or pool
@@ -1304,7 +1283,7 @@ void push_fused8_tasks(std::vector<FusedTask8>& out, std::vector<RowBlock>& bloc
 // with_test: the rows of K_tn (Vt) of every leaf are appended below its factor and advance through the same
 // update / panel-solve launches -- prediction's triangular solves (src/gaussianprocess.jl:120) cost no launches
 // of their own when the test set is resident at fit time.
-int build_factor_steps(dsmgp_ctx* c, int lane, bool with_test, StepLists (&phase)[2], double*& slab_ws, double& alg_flops,
+int build_factor_steps(dsmgp_ctx* c, int lane, bool with_test, StepLists (&phase)[2], DevArena& slab_ws, double& alg_flops,
                        double& alg_flops_fused, bool slab_outside_pool = false) {
     const int L = c->L;
     alg_flops = 0.0;
@@ -1615,13 +1594,11 @@ int build_factor_steps(dsmgp_ctx* c, int lane, bool with_test, StepLists (&phase
     }
     {
         const size_t slabs = std::max(split[0].max_slabs, split[1].max_slabs);
-        arena_put(c, slab_ws);
-        if (slabs) {
-            if (slab_outside_pool && c->pool_base) HIPCHK(c, hipMalloc(&slab_ws, slabs * TB * TB * sizeof(double)));
-            else if (int rc = arena_get(c, slab_ws, slabs * TB * TB)) return rc;
-        }
+        slab_ws.put();
+        if (slabs)
+            if (int rc = arena_status(c, slab_ws.get(slab_outside_pool ? nullptr : arena_pool(c), slabs * TB * TB))) return rc;
         for (int ph = 0; ph < 2; ++ph) {
-            split[ph].bind(slab_ws);
+            split[ph].bind(slab_ws.p);
             if (int rc = dev_upload(c, phase[ph].upd, split[ph].upd)) return rc;
             if (int rc = dev_upload(c, phase[ph].red, split[ph].red)) return rc;
         }
@@ -1704,8 +1681,8 @@ void plan_layout(dsmgp_ctx* c, size_t& fTot, size_t& dTot, size_t& vTot, size_t&
 
 // Build arenas, the LeafDev table and every task list for the current leaf table + sharing schedule, unless they are current.
 // adoptF / adoptDinv (dsmgp_append_rows in place): the factor and Dinv arenas of the previous plan, whose layout is this plan's; they
-// become c->arenaF / c->arenaDinv instead of new allocations -- the context owns them from that assignment on, the caller until then.
-int build_plan(dsmgp_ctx* c, double* adoptF = nullptr, double* adoptDinv = nullptr) {
+// are moved into c->arenaF / c->arenaDinv instead of new allocations -- the caller's are empty from then on, and its own until then.
+int build_plan(dsmgp_ctx* c, DevArena&& adoptF = DevArena(), DevArena&& adoptDinv = DevArena()) {
     if (c->has(P_PLAN)) return 0;
     HostLog hl_total("build_plan");
     {
@@ -1720,23 +1697,23 @@ int build_plan(dsmgp_ctx* c, double* adoptF = nullptr, double* adoptDinv = nullp
     size_t freeB = 0, totalB = 0;
     HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
     // (dsmgp_append_rows in place: the factor and Dinv arenas of the previous plan are taken over, they are allocated already)
-    const bool adopt = adoptF != nullptr && adoptDinv != nullptr;
-    if (!c->pool_base && c->bytes_needed - (adopt ? (fTot + dTot) * sizeof(double) : 0) + (size_t(1) << 30) > freeB)
+    const bool adopt = adoptF.p != nullptr && adoptDinv.p != nullptr;
+    if (!c->pool.active() && c->bytes_needed - (adopt ? (fTot + dTot) * sizeof(double) : 0) + (size_t(1) << 30) > freeB)
         return fail(c, DSMGP_E_NOMEM, "leaf table needs " + std::to_string(c->bytes_needed >> 20) + " MiB, device has " +
                                           std::to_string(freeB >> 20) + " MiB free");
     {
         HostLog hl("build_plan: arenas");
         if (adopt) {
-            c->arenaF = adoptF;
-            c->arenaDinv = adoptDinv;
+            c->arenaF = std::move(adoptF);
+            c->arenaDinv = std::move(adoptDinv);
         } else {
-            if (int rc = arena_get(c, c->arenaF, fTot)) return rc;
-            if (int rc = arena_get(c, c->arenaDinv, dTot)) return rc;
+            if (int rc = arena_status(c, c->arenaF.get(arena_pool(c), fTot))) return rc;
+            if (int rc = arena_status(c, c->arenaDinv.get(arena_pool(c), dTot))) return rc;
             // the diagonal-block kernel writes the lower blocks of Dinv_k only: the blocks above the diagonal are zero from here on
-            HIPCHK(c, hipMemsetAsync(c->arenaDinv, 0, std::max<size_t>(1, dTot) * sizeof(double), c->stream));
+            HIPCHK(c, hipMemsetAsync(c->arenaDinv.p, 0, std::max<size_t>(1, dTot) * sizeof(double), c->stream));
         }
-        if (int rc = arena_get(c, c->arenaVec, vTot)) return rc;
-        if (int rc = arena_get(c, c->arenaXg, xTot)) return rc;
+        if (int rc = arena_status(c, c->arenaVec.get(arena_pool(c), vTot))) return rc;
+        if (int rc = arena_status(c, c->arenaXg.get(arena_pool(c), xTot))) return rc;
     }
     if (int rc = c->d_info.alloc(c, L)) return rc;
     if (int rc = c->d_owner.alloc(c, L)) return rc;
@@ -1752,10 +1729,10 @@ int build_plan(dsmgp_ctx* c, double* adoptF = nullptr, double* adoptDinv = nullp
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
         LeafDev& d = c->h_leaves[l];
-        d.F = c->arenaF + lf.f_off;
-        d.Dinv = c->arenaDinv + lf.dinv_off;
-        d.Xg = c->arenaXg + lf.xg_off;
-        d.yc = c->arenaVec + lf.vec_off;
+        d.F = c->arenaF.p + lf.f_off;
+        d.Dinv = c->arenaDinv.p + lf.dinv_off;
+        d.Xg = c->arenaXg.p + lf.xg_off;
+        d.yc = c->arenaVec.p + lf.vec_off;
         d.w = d.yc + lf.npad;
         d.z = d.w + lf.npad;
         d.alpha = d.z + lf.npad;
@@ -1825,7 +1802,7 @@ int build_plan(dsmgp_ctx* c, double* adoptF = nullptr, double* adoptDinv = nullp
     if (int rc = build_schedule(c)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->mark(P_PLAN);
-    c->pool_mark_plan = c->pool_top;
+    c->pool.mark();
     return 0;
 }
 
@@ -1854,7 +1831,7 @@ int build_schedule(dsmgp_ctx* c) {
         int nunits = 0;
         for (int l = 0; l < L; ++l) nunits += unit[l] == l ? 1 : 0;
         // (also under a reserved pool -- the streaming context -- since round 6: every lane's split-K workspace is one more
-        // arena_get on the pool's stack, lane after lane; config 5 at full size 111.4 -> 110.3 s with two lanes in every group)
+        // arena carved from the pool's stack, lane after lane; config 5 at full size 111.4 -> 110.3 s with two lanes in every group)
         c->nlanes = c->lanes_opt > 0 ? c->lanes_opt : (nunits >= LANES_AUTO_MIN_LEAVES ? 2 : 1);
         c->nlanes = std::max(1, std::min(c->nlanes, nunits));
         c->leaf_lane.assign(L, 0);
@@ -2328,6 +2305,84 @@ int ensure_alpha(dsmgp_ctx* c) {
     return 0;
 }
 
+// The timing slots and launch counters that the launches of a fit fill
+void reset_fit_timings(dsmgp_ctx* c) {
+    for (int i = 0; i < 6; ++i) c->timings[i] = 0.0;
+    c->timings[11] = c->timings[13] = c->timings[14] = 0.0;
+    c->timings[18] = c->timings[19] = c->timings[20] = 0.0;
+    c->n_update_launches = 0;
+    c->n_fused_launches = 0;
+}
+
+// The launches of a fit over the step lists `phases` (c->phase, or c->phaseJ with the resident test rows riding along: joint), on
+// the context's stream and the lanes'.  between(): what the caller queues between the two phases -- dsmgp_fit the copies of the
+// PREFIX leaves' leading blocks, dsmgp_append_rows the relocation of the kept blocks.  Nothing here synchronises or records the
+// call's own events: dsmgp_fit captures this sequence into a graph.
+template <class Between>
+int enqueue_fit(dsmgp_ctx* c, StepLists (*phases)[2], bool joint, PhaseTimer& pt, Between&& between) {
+    const int L = c->L;
+    HIPCHK(c, hipMemsetAsync(c->d_info.p, 0, (size_t)L * sizeof(int), c->stream));
+    if (joint && c->acc_count) HIPCHK(c, hipMemsetAsync(c->arenaPV.p + c->acc_off, 0, c->acc_count * sizeof(double), c->stream));
+    // 1. kernel matrices K + (noise + eps) I, lower tiles   (src/gaussianprocess.jl:83-98) [+ K_tn tiles]
+    //    (fused into the update tasks: only the tiles of block column 0 are written here)
+    {
+        const DevBuf<GramTask>& tg = (joint && gram_fused(c)) ? c->pgram0 : c->pgram;
+        pt.begin(0);
+        if (c->gram.count) gram_tile_kernel<<<2 * (int)c->gram.count, 256, 0, c->stream>>>(c->gram.p, c->d_kp.p, c->D);
+        if (joint && tg.count) gram_tile_kernel<<<2 * (int)tg.count, 256, 0, c->stream>>>(tg.p, c->d_kp.p, c->D);
+        pt.end();
+    }
+    // 2. factorisation, full leaves first                    (src/gaussianprocess.jl:101); w = y - m rides along
+    {
+        int maxpad = 0;
+        for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
+        copy_vec_kernel<<<dim3((maxpad + 255) / 256, L), 256, 0, c->stream>>>(c->d_leaves.p);
+    }
+    if (int rc = run_lanes(c, phases, 0, pt, true)) return rc;
+    // 3. prefix leaves: their leading blocks from where they are, continue (src/fit.jl:276-278).  (A table without a PREFIX
+    //    leaf has no step in phase 1: run_lanes queues nothing, not even the fork.)
+    if (int rc = between()) return rc;
+    if (int rc = run_lanes(c, phases, 1, pt, true)) return rc;
+    // 4. z = L^-1 (y - m) for the leaves whose factor came from another leaf (COPY, PREFIX); leaves factorised in
+    //    full produced z during the factorisation.  alpha = L^-T z (src/gaussianprocess.jl:105) is NOT computed here:
+    //    neither the log-marginal (z.z) nor the prediction (V^T z) needs it -- ensure_alpha() runs the backward sweep
+    //    on first use (gradients, dsmgp_download_factor).
+    {
+        pt.begin(4);
+        if (c->dinvc_fwd.count)
+            dinv_complete_kernel<<<(int)c->dinvc_fwd.count, 256, DIAGP_LDS_BYTES, c->stream>>>(c->dinvc_fwd.p);
+        for (int k = 0; k < c->solve_steps; ++k) {
+            const int n = c->fwd_off[k + 1] - c->fwd_off[k];
+            if (n > 0) solve_fwd_kernel<<<n, 256, 0, c->stream>>>(c->fwd.p + c->fwd_off[k]);
+        }
+        pt.end();
+    }
+    // 5. log marginal likelihood                              (src/gaussianprocess.jl:163)
+    pt.begin(5);
+    mll_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->d_mll.p);
+    pt.end();
+    return 0;
+}
+
+// mll and info of the fit that has just run, per leaf (either may be null).  info lives per factor owner.
+int fetch_fit_results(dsmgp_ctx* c, double* mll_out, int32_t* info_out) {
+    const int L = c->L;
+    if (mll_out) HIPCHK(c, hipMemcpy(mll_out, c->d_mll.p, (size_t)L * sizeof(double), hipMemcpyDeviceToHost));
+    if (!info_out) return 0;
+    std::vector<int> owner_info((size_t)L);
+    HIPCHK(c, hipMemcpy(owner_info.data(), c->d_info.p, (size_t)L * sizeof(int), hipMemcpyDeviceToHost));
+    for (int l = 0; l < L; ++l) info_out[l] = owner_info[(size_t)c->leaves[l].owner];
+    // A PREFIX leaf whose source failed inside the rows it copied meets the damage at its first own pivot (row kb * TB + 1);
+    // its first bad leading minor is the source's, and that is what LAPACK would report for the leaf
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.op != DSMGP_SHARE_PREFIX) continue;
+        const int si = owner_info[(size_t)lf.src];
+        if (si != 0 && si <= lf.kb * TB && info_out[l] != 0) info_out[l] = si;
+    }
+    return 0;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -2382,8 +2437,7 @@ int dsmgp_destroy(dsmgp_ctx* c) {
     if (!c) return DSMGP_E_ARG;
     (void)hipSetDevice(c->device);
     free_plan_and_test(c);
-    if (c->pool_base) (void)hipFree(c->pool_base);
-    c->pool_base = nullptr;
+    c->pool.release();
     (void)dsmgp_comm_destroy(c);
     drop_graphs(c);
     if (c->side) {
@@ -2600,40 +2654,15 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
         return rc;
     }
     const int L = c->L;
-    for (int i = 0; i < 6; ++i) c->timings[i] = 0.0;
-    c->timings[11] = 0.0;
-    c->timings[13] = 0.0;
-    c->timings[14] = 0.0;
-    c->timings[18] = c->timings[19] = c->timings[20] = 0.0;
-    c->n_update_launches = 0;
-    c->n_fused_launches = 0;
+    reset_fit_timings(c);
     PhaseTimer pt(c);
     EventPair ev;
     HIPCHK(c, ev.init());
     const hipEvent_t t0 = ev.a, t1 = ev.b;
     HIPCHK(c, hipEventRecord(t0, c->stream));
 
-    StepLists (*phases)[2] = joint ? c->phaseJ : c->phase;
-    auto enqueue = [&]() -> int {
-        HIPCHK(c, hipMemsetAsync(c->d_info.p, 0, L * sizeof(int), c->stream));
-        if (joint && c->acc_count) HIPCHK(c, hipMemsetAsync(c->arenaPV + c->acc_off, 0, c->acc_count * sizeof(double), c->stream));
-        // 1. kernel matrices K + (noise + eps) I, lower tiles   (src/gaussianprocess.jl:83-98) [+ K_tn tiles]
-        //    (fused into the update tasks: only the tiles of block column 0 are written here)
-        {
-            const DevBuf<GramTask>& tg = (joint && gram_fused(c)) ? c->pgram0 : c->pgram;
-            pt.begin(0);
-            if (c->gram.count) gram_tile_kernel<<<2 * (int)c->gram.count, 256, 0, c->stream>>>(c->gram.p, c->d_kp.p, c->D);
-            if (joint && tg.count) gram_tile_kernel<<<2 * (int)tg.count, 256, 0, c->stream>>>(tg.p, c->d_kp.p, c->D);
-            pt.end();
-        }
-        // 2. factorisation, full leaves first                    (src/gaussianprocess.jl:101); w = y - m rides along
-        {
-            int maxpad = 0;
-            for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
-            copy_vec_kernel<<<dim3((maxpad + 255) / 256, L), 256, 0, c->stream>>>(c->d_leaves.p);
-        }
-        if (int rc = run_lanes(c, phases, 0, pt, true)) return rc;
-        // 3. prefix leaves: copy the leading blocks of the source factor, continue (src/fit.jl:276-278)
+    // between the phases: the leading blocks of every PREFIX leaf, copied from its source's factor
+    auto prefix_copies = [&]() -> int {
         bool any_prefix = false;
         for (int l = 0; l < L; ++l) {
             const LeafHost& lf = c->leaves[l];
@@ -2646,31 +2675,11 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
                                        rows * sizeof(double), rows, hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(d.Dinv, s.Dinv, rows * TB * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         }
-        if (any_prefix) {
-            if (c->dinvc_prefix.count)      // copied blocks that a fused step factorised: their whole inverse, for the classic steps below
-                dinv_complete_kernel<<<(int)c->dinvc_prefix.count, 256, DIAGP_LDS_BYTES, c->stream>>>(c->dinvc_prefix.p);
-            if (int rc = run_lanes(c, phases, 1, pt, true)) return rc;
-        }
-        // 4. z = L^-1 (y - m) for the leaves whose factor came from another leaf (COPY, PREFIX); leaves factorised in
-        //    full produced z during the factorisation.  alpha = L^-T z (src/gaussianprocess.jl:105) is NOT computed here:
-        //    neither the log-marginal (z.z) nor the prediction (V^T z) needs it -- ensure_alpha() runs the backward sweep
-        //    on first use (gradients, dsmgp_download_factor).
-        {
-            pt.begin(4);
-            if (c->dinvc_fwd.count)
-                dinv_complete_kernel<<<(int)c->dinvc_fwd.count, 256, DIAGP_LDS_BYTES, c->stream>>>(c->dinvc_fwd.p);
-            for (int k = 0; k < c->solve_steps; ++k) {
-                const int n = c->fwd_off[k + 1] - c->fwd_off[k];
-                if (n > 0) solve_fwd_kernel<<<n, 256, 0, c->stream>>>(c->fwd.p + c->fwd_off[k]);
-            }
-            pt.end();
-        }
-        // 5. log marginal likelihood                              (src/gaussianprocess.jl:163)
-        pt.begin(5);
-        mll_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->d_mll.p);
-        pt.end();
+        if (any_prefix && c->dinvc_prefix.count)    // copied blocks that a fused step factorised: their whole inverse, for the classic steps of phase 1
+            dinv_complete_kernel<<<(int)c->dinvc_prefix.count, 256, DIAGP_LDS_BYTES, c->stream>>>(c->dinvc_prefix.p);
         return 0;
     };
+    auto enqueue = [&]() -> int { return enqueue_fit(c, joint ? c->phaseJ : c->phase, joint, pt, prefix_copies); };
     c->invalidate(P_FIT);           // the factors are rewritten from here on
     // Replay the sequence as a graph while nothing inside it records events (profile 0); capture it on first use
     const int gk = joint ? 1 : 0;
@@ -2715,21 +2724,7 @@ int dsmgp_fit(dsmgp_ctx* c, double* mll_out, int32_t* info_out, double* seconds)
     pt.collect(t0);
     c->timings[11] = ms * 1e-3;
     if (seconds) *seconds = ms * 1e-3;
-    if (mll_out) HIPCHK(c, hipMemcpy(mll_out, c->d_mll.p, L * sizeof(double), hipMemcpyDeviceToHost));
-    if (info_out) {
-        // info lives per factor owner
-        std::vector<int> owner_info(L);
-        HIPCHK(c, hipMemcpy(owner_info.data(), c->d_info.p, L * sizeof(int), hipMemcpyDeviceToHost));
-        for (int l = 0; l < L; ++l) info_out[l] = owner_info[c->leaves[l].owner];
-        // A PREFIX leaf whose source failed inside the rows it copied meets the damage at its first own pivot (row kb * TB + 1);
-        // its first bad leading minor is the source's, and that is what LAPACK would report for the leaf
-        for (int l = 0; l < L; ++l) {
-            const LeafHost& lf = c->leaves[l];
-            if (lf.op != DSMGP_SHARE_PREFIX) continue;
-            const int si = owner_info[lf.src];
-            if (si != 0 && si <= lf.kb * TB && info_out[l] != 0) info_out[l] = si;
-        }
-    }
+    if (int rc = fetch_fit_results(c, mll_out, info_out)) return rc;
     c->mark(P_FIT);
     if (joint) c->mark(P_VT);
     c->vt_from_fit = joint;
@@ -2748,14 +2743,13 @@ struct KeptTest {
     };
     bool resident = false;
     std::vector<Leaf> old;
-    double* arena = nullptr;        // the previous arenaVt: owned here until the context adopts it again or it is freed
-    size_t arena_count = 0;
+    DevArena arena;                 // the previous arenaVt: owned here until the context takes it back or it is put
 };
 
 // The test set again on the grown plan (the fit is done, the old factors are gone).  A leaf keeps the block columns that were
 // current and belong to kept blocks of the factor it reads -- its owner's, so a COPY leaf its source's.  IN PLACE where no leaf's
 // offset or size in the arena moves; else RELOCATE: a new arena beside the old, the kept column runs (contiguous: 128 x 128
-// tiles with lds = ldd = ntpad) in one launch, then the old one is freed -- never a move inside one arena, whose source and
+// tiles with lds = ldd = ntpad) in one launch, then the old one is put -- never a move inside one arena, whose source and
 // destination would overlap.  rs: dsmgp_resume_stats.  An error leaves the set half built: the caller drops it.
 static int keep_test_set(dsmgp_ctx* c, KeptTest& kt, const std::vector<int>& factor_keep, int64_t* rs) {
     const int L = c->L;
@@ -2780,24 +2774,21 @@ static int keep_test_set(dsmgp_ctx* c, KeptTest& kt, const std::vector<int>& fac
         }
     }
     if (same || !any) {     // in place -- or nothing to keep: register_test takes the arena over while it fits
-        c->arenaVt = kt.arena;
-        c->arenaVt_count = kt.arena_count;
-        kt.arena = nullptr;
+        c->arenaVt = std::move(kt.arena);
     } else {
         const size_t want = vTot + vTot / 8;
         size_t freeB = 0, totalB = 0;
         HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
         if (want * sizeof(double) + (size_t(1) << 30) > freeB)
             return fail(c, DSMGP_E_NOMEM, "add_rows_keep_test: no room for the new K_tn arena beside the old one");
-        if (int rc = arena_get(c, c->arenaVt, want)) return rc;
-        c->arenaVt_count = want;
+        if (int rc = arena_status(c, c->arenaVt.get(arena_pool(c), want))) return rc;
         std::vector<RelocTask> rt;
         for (int l = 0; l < L; ++l) {
             const KeptTest::Leaf& o = kt.old[(size_t)l];
             for (int j = 0; j < first[(size_t)l]; ++j)
                 for (int i = 0; i < o.ntpad / TB; ++i) {
                     const size_t at = (size_t)i * TB + (size_t)j * TB * (size_t)o.ntpad;
-                    rt.push_back(RelocTask{kt.arena + o.vt_off + at, c->arenaVt + off[(size_t)l] + at, o.ntpad, o.ntpad});
+                    rt.push_back(RelocTask{kt.arena.p + o.vt_off + at, c->arenaVt.p + off[(size_t)l] + at, o.ntpad, o.ntpad});
                 }
         }
         DevBuf<RelocTask> reloc;
@@ -2805,32 +2796,23 @@ static int keep_test_set(dsmgp_ctx* c, KeptTest& kt, const std::vector<int>& fac
         relocate_tiles_kernel<<<(unsigned)rt.size(), 256, 0, c->stream>>>(reloc.p);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(kt.arena);
-        kt.arena = nullptr;
+        kt.arena.put();
         rs[2] = (int64_t)rt.size() * TB * TB * (int64_t)sizeof(double);
     }
-    const double* const arena = c->arenaVt;
+    const double* const arena = c->arenaVt.p;
     c->stage_top = 0;       // (the stream is idle)
     HostLog hl("add_rows_keep_test: sizes");
     if (int rc = register_test(c, hl, &first)) return rc;
-    if (any && c->arenaVt != arena) return fail(c, DSMGP_E_STATE, "add_rows_keep_test: the K_tn arena was replaced");
+    if (any && c->arenaVt.p != arena) return fail(c, DSMGP_E_STATE, "add_rows_keep_test: the K_tn arena was replaced");
     c->vt_first = first;
     c->resume_armed = true;
     return 0;
 }
 
-// keep_test (dsmgp_add_rows_keep_test): a resident test set stays resident -- its rows, routes and entry index as they are, the second
-// half of its registration again on the grown plan -- and, where dsmgp_predict_run had run on the fit the call finds, every leaf
-// keeps the leading block columns of K_tn L^-T that belong to the kept blocks of the factor it reads (keep_test_set, below).
-static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int64_t m, int32_t D, const int64_t* add_ptr,
-                     const int64_t* add_idx, const double* mean, double* mll_out, int32_t* info_out, double* seconds, bool keep_test) {
-    if (!c) return DSMGP_E_ARG;
-    if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "append_rows needs a current fit");
-    if (c->pool_base) return fail(c, DSMGP_E_STATE, "append_rows under a reserved pool");
-    if (!X_new || !y_new || !add_ptr || !add_idx || m < 1) return fail(c, DSMGP_E_ARG, "append_rows: bad arguments");
-    if (D != c->D) return fail(c, DSMGP_E_ARG, "append_rows: D is not the D of set_train");
+// The argument checks of grow_rows that read nothing but the arguments and the leaf table's sizes
+static int check_added_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int64_t m, int32_t D, const int64_t* add_ptr,
+                            const int64_t* add_idx, const double* mean) {
     const int L = c->L;
-    const int64_t N0 = c->N;
     if (add_ptr[0] != 0) return fail(c, DSMGP_E_ARG, "append_rows: add_ptr[0] must be 0");
     for (int l = 0; l < L; ++l) {
         const int64_t a = add_ptr[l], b = add_ptr[l + 1];
@@ -2849,6 +2831,22 @@ static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int
     if (mean)
         for (int l = 0; l < L; ++l)
             if (!std::isfinite(mean[l])) return fail(c, DSMGP_E_ARG, "append_rows: non-finite mean");
+    return 0;
+}
+
+// keep_test (dsmgp_add_rows_keep_test): a resident test set stays resident -- its rows, routes and entry index as they are, the second
+// half of its registration again on the grown plan -- and, where dsmgp_predict_run had run on the fit the call finds, every leaf
+// keeps the leading block columns of K_tn L^-T that belong to the kept blocks of the factor it reads (keep_test_set, above).
+static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int64_t m, int32_t D, const int64_t* add_ptr,
+                     const int64_t* add_idx, const double* mean, double* mll_out, int32_t* info_out, double* seconds, bool keep_test) {
+    if (!c) return DSMGP_E_ARG;
+    if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "append_rows needs a current fit");
+    if (c->pool.active()) return fail(c, DSMGP_E_STATE, "append_rows under a reserved pool");
+    if (!X_new || !y_new || !add_ptr || !add_idx || m < 1) return fail(c, DSMGP_E_ARG, "append_rows: bad arguments");
+    if (D != c->D) return fail(c, DSMGP_E_ARG, "append_rows: D is not the D of set_train");
+    if (int rc = check_added_rows(c, X_new, y_new, m, D, add_ptr, add_idx, mean)) return rc;
+    const int L = c->L;
+    const int64_t N0 = c->N;
     HIPCHK(c, hipSetDevice(c->device));
 
     // 1. what the kept blocks need before they are read again: every Dinv_k whole (the fused steps of the fit left the 16x16
@@ -2879,16 +2877,15 @@ static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int
         HIPCHK(c, e2);
     }
 
-    // 3. the previous plan: where every factor sits, and the arenas themselves (taken out of the context: free_plan leaves them)
+    // 3. the previous plan: where every factor sits, and the arenas themselves, moved out of the context -- free_plan finds nothing
+    //    there, and whatever this call does not hand back (build_plan in place, keep_test_set) goes when the call returns
     struct Old { size_t f_off, dinv_off; int n, npad, nb, owner, op, src; double mean; };
     std::vector<Old> old((size_t)L);
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
         old[(size_t)l] = Old{lf.f_off, lf.dinv_off, lf.n, lf.npad, lf.nb, lf.owner, lf.op, lf.src, lf.mean};
     }
-    double* oldF = c->arenaF;
-    double* oldDinv = c->arenaDinv;
-    c->arenaF = c->arenaDinv = nullptr;
+    DevArena oldF = std::move(c->arenaF), oldDinv = std::move(c->arenaDinv);
     // ... and, for a test set that stays, where every leaf's K_tn L^-T sits, how much of it is current, and the arena itself
     KeptTest kt;
     kt.resident = keep_test && c->has(P_TEST);
@@ -2899,20 +2896,9 @@ static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int
             const LeafHost& lf = c->leaves[l];
             kt.old[(size_t)l] = KeptTest::Leaf{lf.vt_off, lf.ntpad, lf.npad, swept ? lf.nb : (pending ? c->vt_first[(size_t)l] : 0)};
         }
-        kt.arena = c->arenaVt;
-        kt.arena_count = c->arenaVt_count;
-        c->arenaVt = nullptr;
-        c->arenaVt_count = 0;
-        const size_t counts[6] = {c->dXt.count,     c->d_route_ptr.count, c->d_route_idx.count,
-                                  c->d_row_ptr.count, c->d_row_ent.count,   c->d_ent_leaf.count};
+        kt.arena = std::move(c->arenaVt);
         free_plan(c);
-        free_test(c, true);         // the rows, the CSR and the entry index stay as they are: emptied lists, the same bytes
-        c->dXt.count = counts[0];
-        c->d_route_ptr.count = counts[1];
-        c->d_route_idx.count = counts[2];
-        c->d_row_ptr.count = counts[3];
-        c->d_row_ent.count = counts[4];
-        c->d_ent_leaf.count = counts[5];
+        free_test_products(c, true);    // the rows, the CSR and the entry index stay as they are
     } else {
         free_plan_and_test(c);      // (the routing tree stays: leaf indices do not change)
     }
@@ -2962,16 +2948,12 @@ static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int
             lf.prefix = 0;
         }
     };
-    // whatever goes wrong from here on: the grown data and leaf table, no plan, no fit -- as after dsmgp_set_leaves
+    // whatever goes wrong from here on: the grown data and leaf table, no plan, no fit -- as after dsmgp_set_leaves.  (The old
+    // arenas go with their owners: the context's with free_plan_and_test, those still held here when the call returns.)
     auto give_up = [&](int rc) {
         const std::string msg = c->err;
-        if (oldF && c->arenaF == oldF) oldF = oldDinv = nullptr;    // build_plan took them over (in place): free_plan puts them back
         (void)hipStreamSynchronize(c->stream);
         free_plan_and_test(c);
-        if (oldF) (void)hipFree(oldF);
-        if (oldDinv) (void)hipFree(oldDinv);
-        if (kt.arena) (void)hipFree(kt.arena);      // (the test set has gone with free_plan_and_test)
-        kt.arena = nullptr;
         final_schedule();
         c->err = msg;
         return rc;
@@ -3028,7 +3010,7 @@ static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int
     }
     // (the lane deal of this plan weighs every owner by n^3 as a fit would, although a continuing owner costs O(n 128 n) and an
     // untouched one nothing: the lanes of this one call may be unevenly loaded -- speed only, and the lists are rebuilt below)
-    if (int rc = in_place ? build_plan(c, oldF, oldDinv) : build_plan(c)) return give_up(rc);
+    if (int rc = in_place ? build_plan(c, std::move(oldF), std::move(oldDinv)) : build_plan(c)) return give_up(rc);
     if (int rc = upload_hyper(c)) return give_up(rc);
     if (int rc = ensure_phase(c)) return give_up(rc);      // this call's step lists: dropped below
 
@@ -3043,9 +3025,9 @@ static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int
             const LeafDev& d = c->h_leaves[l];
             for (int j = 0; j < lf.kb; ++j) {
                 for (int i = 0; i < lf.kb; ++i)
-                    rt.push_back(RelocTask{oldF + from.f_off + (size_t)i * TB + (size_t)j * TB * from.npad,
+                    rt.push_back(RelocTask{oldF.p + from.f_off + (size_t)i * TB + (size_t)j * TB * from.npad,
                                            d.F + (size_t)i * TB + (size_t)j * TB * lf.npad, from.npad, lf.npad});
-                rt.push_back(RelocTask{oldDinv + from.dinv_off + (size_t)j * TB * TB, d.Dinv + (size_t)j * TB * TB, TB, TB});
+                rt.push_back(RelocTask{oldDinv.p + from.dinv_off + (size_t)j * TB * TB, d.Dinv + (size_t)j * TB * TB, TB, TB});
             }
         }
         st[2] = (int64_t)rt.size() * TB * TB * (int64_t)sizeof(double);
@@ -3058,44 +3040,25 @@ static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int
         }
     }
 
-    // 7. the launches of a fit, the relocation between its phases
-    for (int i = 0; i < 6; ++i) c->timings[i] = 0.0;
-    c->timings[11] = c->timings[13] = c->timings[14] = 0.0;
-    c->timings[18] = c->timings[19] = c->timings[20] = 0.0;
-    c->n_update_launches = 0;
-    c->n_fused_launches = 0;
+    // 7. the launches of a fit, the relocation between its phases: the owners without kept blocks (there may be none) in phase
+    //    0, the continuations in phase 1
+    reset_fit_timings(c);
     PhaseTimer pt(c);
     EventPair ev;
     if (ev.init() != hipSuccess) return give_up(fail(c, DSMGP_E_HIP, "append_rows: hipEventCreate failed"));
-    auto enqueue = [&]() -> int {
-        HIPCHK(c, hipEventRecord(ev.a, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_info.p, 0, (size_t)L * sizeof(int), c->stream));
-        pt.begin(0);
-        if (c->gram.count) gram_tile_kernel<<<2 * (int)c->gram.count, 256, 0, c->stream>>>(c->gram.p, c->d_kp.p, c->D);
-        pt.end();
-        int maxpad = 0;
-        for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
-        copy_vec_kernel<<<dim3((maxpad + 255) / 256, L), 256, 0, c->stream>>>(c->d_leaves.p);
-        if (int rc = run_lanes(c, c->phase, 0, pt, true)) return rc;      // owners without kept blocks (may be empty)
+    auto relocate = [&]() -> int {
         if (reloc.count) relocate_tiles_kernel<<<(unsigned)reloc.count, 256, 0, c->stream>>>(reloc.p);
-        if (int rc = run_lanes(c, c->phase, 1, pt, true)) return rc;      // the continuations
-        pt.begin(4);
-        if (c->dinvc_fwd.count)
-            dinv_complete_kernel<<<(int)c->dinvc_fwd.count, 256, DIAGP_LDS_BYTES, c->stream>>>(c->dinvc_fwd.p);
-        for (int k = 0; k < c->solve_steps; ++k) {
-            const int n = c->fwd_off[k + 1] - c->fwd_off[k];
-            if (n > 0) solve_fwd_kernel<<<n, 256, 0, c->stream>>>(c->fwd.p + c->fwd_off[k]);
-        }
-        pt.end();
-        pt.begin(5);
-        mll_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->d_mll.p);
-        pt.end();
+        return 0;
+    };
+    auto run_fit = [&]() -> int {
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        if (int rc = enqueue_fit(c, c->phase, false, pt, relocate)) return rc;
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(ev.b, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return 0;
     };
-    if (int rc = enqueue()) {
+    if (int rc = run_fit()) {
         pt.collect();
         return give_up(rc);
     }
@@ -3104,32 +3067,18 @@ static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int
     pt.collect(ev.a);
     c->timings[11] = ms * 1e-3;
     if (seconds) *seconds = ms * 1e-3;
-    if (!in_place) {        // the old factors have been read for the last time
-        (void)hipFree(oldF);
-        (void)hipFree(oldDinv);
-    }
-    oldF = oldDinv = nullptr;
-    // (a failure from here on still goes through give_up: the one-shot marks never outlive the call)
-    auto hip_failed = [&](hipError_t e, const char* what) {
-        if (e == hipSuccess) return false;
-        c->err = std::string(what) + ": " + hipGetErrorString(e);
-        return true;
-    };
-    if (mll_out && hip_failed(hipMemcpy(mll_out, c->d_mll.p, (size_t)L * sizeof(double), hipMemcpyDeviceToHost), "append_rows: mll"))
-        return give_up(DSMGP_E_HIP);
-    if (info_out) {
-        std::vector<int> owner_info((size_t)L);
-        if (hip_failed(hipMemcpy(owner_info.data(), c->d_info.p, (size_t)L * sizeof(int), hipMemcpyDeviceToHost), "append_rows: info"))
-            return give_up(DSMGP_E_HIP);
-        for (int l = 0; l < L; ++l) info_out[l] = owner_info[(size_t)c->leaves[l].owner];
-    }
+    oldF.put();             // the old factors have been read for the last time (in place: the context has them)
+    oldDinv.put();
+    // (a failure from here on still goes through give_up: the one-shot marks never outlive the call.)  The read-back comes before
+    // final_schedule() takes the marks away; its PREFIX correction changes nothing here, where a PREFIX leaf's source is itself.
+    if (int rc = fetch_fit_results(c, mll_out, info_out)) return give_up(rc);
     c->mark(P_FIT);
     c->vt_from_fit = false;
     c->last_fit_joint = false;
     // 8. the marks go: the blocks this call's fused steps left without their whole inverse are completed under ITS lists, then
     //    the schedule lists are rebuilt as the next fit needs them (COPY where kept, FULL elsewhere) and the step lists dropped
     if (int rc = ensure_dinv(c)) return give_up(rc);
-    if (hip_failed(hipStreamSynchronize(c->stream), "append_rows: hipStreamSynchronize")) return give_up(DSMGP_E_HIP);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return give_up(fail(c, DSMGP_E_HIP, "append_rows: hipStreamSynchronize failed"));
     final_schedule();
     {
         size_t a = 0, b = 0, v = 0, x = 0;
@@ -3150,8 +3099,7 @@ static int grow_rows(dsmgp_ctx* c, const double* X_new, const double* y_new, int
             const int64_t dropped[DSMGP_N_RESUME_STATS] = {0, 0, 0, -1, 0, 1};
             for (int i = 0; i < DSMGP_N_RESUME_STATS; ++i) rs[i] = dropped[i];
         }
-        if (kt.arena) (void)hipFree(kt.arena);
-        kt.arena = nullptr;
+        kt.arena.put();
         for (int i = 0; i < DSMGP_N_RESUME_STATS; ++i) c->resume_stats[i] = rs[i];
         c->have_resume_stats = true;
     }
@@ -3214,26 +3162,16 @@ int register_test(dsmgp_ctx* c, HostLog& hl, const std::vector<int>* first) {
     size_t freeB = 0, totalB = 0;
     HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
     const size_t need = (vTot + xTot + pTot) * sizeof(double) + (size_t)n_t * c->D * sizeof(double);
-    if (!c->pool_base) freeB += (c->arenaVt_count + c->cap_Xt + c->cap_PV) * sizeof(double);   // taken over or released first (arena_fit)
-    if (!c->pool_base && need + (size_t(1) << 30) > freeB)
+    if (!c->pool.active()) freeB += (c->arenaVt.cap + c->arenaXt.cap + c->arenaPV.cap) * sizeof(double);   // taken over or released first (DevArena::fit)
+    if (!c->pool.active() && need + (size_t(1) << 30) > freeB)
         return fail(c, DSMGP_E_NOMEM, "test set needs " + std::to_string(need >> 20) + " MiB, device has " +
                                           std::to_string(freeB >> 20) + " MiB free");
     hl.lap("set_test: arenas");
     // every arena of the test set this one replaces is taken over while it fits (and is not wastefully large: at most twice what
     // is needed); with a device pool they are carved out of the pool's stack
-    auto arena_fit = [&](double*& p, size_t& cap, size_t need_) -> int {
-        if (c->pool_base) return arena_get(c, p, need_);
-        if (p && cap >= need_ && cap <= 2 * need_ + (size_t(1) << 20)) return 0;
-        arena_put(c, p);
-        cap = 0;
-        const size_t want = need_ + need_ / 8;
-        if (int rc = arena_get(c, p, want)) return rc;
-        cap = want;
-        return 0;
-    };
-    if (int rc = arena_fit(c->arenaVt, c->arenaVt_count, vTot)) return rc;
-    if (int rc = arena_fit(c->arenaXt, c->cap_Xt, xTot)) return rc;
-    if (int rc = arena_fit(c->arenaPV, c->cap_PV, pTot)) return rc;
+    if (int rc = arena_status(c, c->arenaVt.fit(arena_pool(c), vTot))) return rc;
+    if (int rc = arena_status(c, c->arenaXt.fit(arena_pool(c), xTot))) return rc;
+    if (int rc = arena_status(c, c->arenaPV.fit(arena_pool(c), pTot))) return rc;
     int maxpad = 0;
     size_t accOff = 0;
     c->acc_off = 2 * (size_t)total;
@@ -3241,11 +3179,11 @@ int register_test(dsmgp_ctx* c, HostLog& hl, const std::vector<int>* first) {
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
         LeafDev& d = c->h_leaves[l];
-        d.Vt = c->arenaVt + lf.vt_off;
-        d.Xtg = c->arenaXt + lf.xt_off;
-        d.mu = c->arenaPV + lf.pv_off;
-        d.var = c->arenaPV + (size_t)total + lf.pv_off;
-        d.macc = c->arenaPV + 2 * (size_t)total + accOff;
+        d.Vt = c->arenaVt.p + lf.vt_off;
+        d.Xtg = c->arenaXt.p + lf.xt_off;
+        d.mu = c->arenaPV.p + lf.pv_off;
+        d.var = c->arenaPV.p + (size_t)total + lf.pv_off;
+        d.macc = c->arenaPV.p + 2 * (size_t)total + accOff;
         d.sacc = d.macc + accTot;
         d.zfused = (lf.owner == l && lf.op == DSMGP_SHARE_FULL) ? 1 : 0;
         accOff += (size_t)lf.ntpad;
@@ -3272,7 +3210,7 @@ int register_test(dsmgp_ctx* c, HostLog& hl, const std::vector<int>* first) {
     // registers them and runs its own sweep, and should not wait for task lists only a later fit! would use (0.067 s of the
     // 0.088 s this call took at the headline model).
     c->mark(P_TEST);
-    int rc = c->pool_base ? ensure_joint(c) : 0;
+    int rc = c->pool.active() ? ensure_joint(c) : 0;
     hl.lap("set_test: final sync");
     if (rc == 0) rc = stage_done(c);
     if (rc != 0) c->invalidate(P_TEST);
@@ -3751,7 +3689,7 @@ int dsmgp_predict_run(dsmgp_ctx* c, double* seconds) {
             if (!resume)
                 if (int rc = full_sweep_lists(c)) return rc;
             if (int rc = ensure_dinv(c)) return rc;       // the panel solves of the sweep multiply with Dinv_k
-            HIPCHK(c, hipMemsetAsync(c->arenaPV + c->acc_off, 0, c->acc_count * sizeof(double), c->stream));
+            HIPCHK(c, hipMemsetAsync(c->arenaPV.p + c->acc_off, 0, c->acc_count * sizeof(double), c->stream));
             if (resume && c->kept_tasks.count) {          // ... and the sums of the columns it skips are stored over the zeros
                 pt.begin(9);
                 kept_sums_kernel<<<(unsigned)c->kept_tasks.count, 256, 0, c->stream>>>(c->kept_tasks.p);
@@ -3811,8 +3749,8 @@ int dsmgp_predict_fetch(dsmgp_ctx* c, double* mu_out, double* var_out) {
     if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_fetch before predict_run");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->route_total;
-    if (n && mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->arenaPV, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (n && var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->arenaPV + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n && mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->arenaPV.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n && var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->arenaPV.p + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -3854,7 +3792,7 @@ int dsmgp_predict_cov(dsmgp_ctx* c, int32_t leaf, int32_t with_noise, double* Si
     HIPCHK(c, hipSetDevice(c->device));
     const LeafDev& d = c->h_leaves[leaf];
     const int ntp = lf.ntpad, nbt = ntp / TB;
-    if (int rc = slab_grow(c, c->arenaCov, c->cap_Cov, (size_t)ntp * ntp)) return rc;
+    if (int rc = arena_status(c, c->arenaCov.grow(arena_pool(c), (size_t)ntp * ntp))) return rc;
     std::vector<PredCovTask> tasks;
     tasks.reserve((size_t)nbt * (nbt + 1) / 2);
     // row tile by row tile, the tiles of one row next to each other: they share their A panel
@@ -3863,11 +3801,11 @@ int dsmgp_predict_cov(dsmgp_ctx* c, int32_t leaf, int32_t with_noise, double* Si
             PredCovTask g{};
             g.gemm.A = d.Vt + (size_t)i * TB;
             g.gemm.B = d.Vt + (size_t)j * TB;
-            g.gemm.C = c->arenaCov + (size_t)i * TB + (size_t)j * TB * ntp;
+            g.gemm.C = c->arenaCov.p + (size_t)i * TB + (size_t)j * TB * ntp;
             g.gemm.lda = g.gemm.ldb = g.gemm.ldc = ntp;
             g.gemm.k0 = 0;
             g.gemm.k1 = lf.n - lf.n % KC2;
-            g.Ct = c->arenaCov + (size_t)j * TB + (size_t)i * TB * ntp;
+            g.Ct = c->arenaCov.p + (size_t)j * TB + (size_t)i * TB * ntp;
             g.xa = d.Xtg + (size_t)i * TB;
             g.xb = d.Xtg + (size_t)j * TB;
             g.ldx = ntp;
@@ -3887,7 +3825,7 @@ int dsmgp_predict_cov(dsmgp_ctx* c, int32_t leaf, int32_t with_noise, double* Si
     tile_predcov_kernel<<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->pcov.p, c->d_kp.p, c->D);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev.b, c->stream));
-    HIPCHK(c, hipMemcpy2DAsync(Sigma_out, (size_t)ld * sizeof(double), c->arenaCov, (size_t)ntp * sizeof(double),
+    HIPCHK(c, hipMemcpy2DAsync(Sigma_out, (size_t)ld * sizeof(double), c->arenaCov.p, (size_t)ntp * sizeof(double),
                                (size_t)lf.nt * sizeof(double), (size_t)lf.nt, hipMemcpyDeviceToHost, c->stream));
     if (int rc = stage_done(c)) return rc;
     float ms = 0.f;
@@ -3929,8 +3867,8 @@ int dsmgp_aggregate_partial(dsmgp_ctx* c, int32_t family, const double* leaf_coe
     a.row_ptr = c->d_row_ptr.p;
     a.row_ent = c->d_row_ent.p;
     a.ent_leaf = c->d_ent_leaf.p;
-    a.mu = c->arenaPV;
-    a.var = c->arenaPV + (size_t)c->route_total;
+    a.mu = c->arenaPV.p;
+    a.var = c->arenaPV.p + (size_t)c->route_total;
     a.coef = c->d_agg_coef.p;
     a.group = c->d_agg_group.p;
     a.part = c->d_agg_part.p;
@@ -4243,16 +4181,13 @@ int build_grad_plan(dsmgp_ctx* c) {
         }
     size_t freeB = 0, totalB = 0;
     HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
-    if (!c->pool_base && xTot * sizeof(double) + (size_t(2) << 30) > freeB)
+    if (!c->pool.active() && xTot * sizeof(double) + (size_t(2) << 30) > freeB)
         return fail(c, DSMGP_E_NOMEM, "gradients need " + std::to_string((xTot * 8) >> 20) + " MiB for L^-1, device has " +
                                           std::to_string(freeB >> 20) + " MiB free");
-    if (!c->arenaX || c->arenaX_count != xTot) {      // kept across changes of the active set (dsmgp_set_gradient_leaves)
-        arena_put(c, c->arenaX);
-        if (int rc = arena_get(c, c->arenaX, xTot)) return rc;
-        c->arenaX_count = xTot;
-    }
+    // kept across changes of the active set (dsmgp_set_gradient_leaves)
+    if (int rc = arena_status(c, c->arenaX.exact(arena_pool(c), xTot))) return rc;
     c->gxoff = xoff;
-    auto Xt = [&](int l) { return c->arenaX + xoff[c->leaves[l].owner]; };
+    auto Xt = [&](int l) { return c->arenaX.p + xoff[c->leaves[l].owner]; };
     // Active leaves (dsmgp_set_gradient_leaves; default all).  A leaf's gradient needs tr K_y^-1 = |L^-1|_F^2 of its factor
     // owner and, for the kernels with a length-scale term, the contraction tiles -- its own, or its source's where a COPY leaf
     // shares them (grad_src): needC = leaves whose contraction is computed, needX = owners whose L^-T is built.
@@ -4645,7 +4580,7 @@ int build_loo_plan(dsmgp_ctx* c) {
         for (int t = 0; t * TB < lf.n; ++t)
             for (int c0 = t * TB, k = 0; c0 < lf.n; c0 += ROWNORM_COLS, ++k) {
                 RowNormTask r{};
-                r.X = c->arenaX + c->gxoff[l] + (size_t)t * TB;
+                r.X = c->arenaX.p + c->gxoff[l] + (size_t)t * TB;
                 r.out = c->d_loo.p + poff[l] + (size_t)k * lf.npad + (size_t)t * TB;
                 r.ld = lf.npad;
                 r.col0 = c0;
@@ -4722,7 +4657,7 @@ int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int
             boff[l] = bTot;
             bTot += (size_t)lf.ntpad * lf.npad;
         }
-        if (int rc = slab_grow(c, c->arenaB, c->cap_B, bTot)) return rc;
+        if (int rc = arena_status(c, c->arenaB.grow(arena_pool(c), bTot))) return rc;
     }
     // task lists: the tiles of B; per test tile its slabs of training rows, next to each other in the list and in d_pgpart
     const size_t planes = (var ? 2 : 1) * (size_t)D * TB;
@@ -4749,7 +4684,7 @@ int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int
         if (lf.nt == 0) continue;
         const LeafDev& d = c->h_leaves[l];
         const int nslab = (lf.n + PGRAD_SLAB - 1) / PGRAD_SLAB;
-        double* Bl = var ? c->arenaB + boff[l] : nullptr;
+        double* Bl = var ? c->arenaB.p + boff[l] : nullptr;
         for (int i = 0; i < lf.ntpad / TB; ++i) {
             PredGradFinTask& f = fin[fi++];
             f.part = c->d_pgpart.p + ti * planes;
@@ -4781,7 +4716,7 @@ int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int
             for (int j = 0; j * TB < lf.n; ++j) {
                 PredBetaTask b{};
                 b.gemm.A = d.Vt + (size_t)i * TB;
-                b.gemm.B = c->arenaX + c->gxoff[lf.owner] + (size_t)j * TB;
+                b.gemm.B = c->arenaX.p + c->gxoff[lf.owner] + (size_t)j * TB;
                 b.gemm.C = Bl + (size_t)i * TB + (size_t)j * TB * lf.ntpad;
                 b.gemm.lda = b.gemm.ldc = lf.ntpad;
                 b.gemm.ldb = ow.npad;
@@ -4844,7 +4779,7 @@ static int build_targets_plan(dsmgp_ctx* c, int qpad) {      // (static: inside 
         tot += 2 * (size_t)c->leaves[l].npad * (size_t)qpad;
         maxnb = std::max(maxnb, c->leaves[l].nb);
     }
-    if (int rc = slab_grow(c, c->arenaT, c->cap_T, tot)) {
+    if (int rc = arena_status(c, c->arenaT.grow(arena_pool(c), tot))) {
         (void)hipGetLastError();
         return rc;
     }
@@ -4863,7 +4798,7 @@ static int build_targets_plan(dsmgp_ctx* c, int qpad) {      // (static: inside 
                 const LeafHost& lf = c->leaves[l];
                 if ((nl > 1 && c->leaf_lane[l] != q) || lf.nb <= s) continue;
                 const LeafDev& d = c->h_leaves[l];
-                double* yc = c->arenaT + c->toff[(size_t)l];
+                double* yc = c->arenaT.p + c->toff[(size_t)l];
                 double* z = yc + (size_t)lf.npad * qpad;
                 TargetsFwdTask t{};
                 t.ldt = t.ldz = lf.npad;
@@ -4934,7 +4869,7 @@ int dsmgp_solve_targets(dsmgp_ctx* c, const double* Y, int64_t N, int32_t Q, int
         for (int l0 = 0; l0 < L; l0 += 32768) {
             const int cnt = std::min(32768, L - l0);
             targets_gather_kernel<<<dim3((maxpad + 255) / 256, cnt), 256, 0, c->stream>>>(
-                c->d_leaves.p, c->d_obs_ptr.p, c->d_obs_idx.p, c->d_tY.p, N, Q, qpad, c->d_tmean.p, L, c->arenaT, c->d_toff.p, l0);
+                c->d_leaves.p, c->d_obs_ptr.p, c->d_obs_idx.p, c->d_tY.p, N, Q, qpad, c->d_tmean.p, L, c->arenaT.p, c->d_toff.p, l0);
         }
     }
     if (int rc = fork_lanes(c, c->tfwd_lanes)) return rc;
@@ -4945,7 +4880,7 @@ int dsmgp_solve_targets(dsmgp_ctx* c, const double* Y, int64_t N, int32_t Q, int
             if (nt > 0) targets_fwd_kernel<<<nt, 256, 0, c->lane_stream[lane]>>>(c->tfwd.p + c->tfwd_off[(size_t)v]);
         }
     if (int rc = join_lanes(c, c->tfwd_lanes)) return rc;
-    targets_mll_kernel<<<dim3(L, Q), 256, 0, c->stream>>>(c->d_leaves.p, c->arenaT, c->d_toff.p, qpad, L, c->d_tmll.p);
+    targets_mll_kernel<<<dim3(L, Q), 256, 0, c->stream>>>(c->d_leaves.p, c->arenaT.p, c->d_toff.p, qpad, L, c->d_tmll.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev.b, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4977,7 +4912,7 @@ int dsmgp_predict_targets(dsmgp_ctx* c, double* mu_out, int64_t ld, double* seco
         for (int i = 0; i < lf.ntpad / TB; ++i) {
             TargetsMuTask t{};
             t.Vt = d.Vt + (size_t)i * TB;
-            t.Z = c->arenaT + c->toff[(size_t)l] + (size_t)lf.npad * qpad;
+            t.Z = c->arenaT.p + c->toff[(size_t)l] + (size_t)lf.npad * qpad;
             t.out = c->d_tmu.p + (size_t)lf.route_off + (size_t)i * TB;
             t.info = d.info;
             t.ldo = (long long)nr;
@@ -5013,7 +4948,7 @@ int dsmgp_targets_fetch(dsmgp_ctx* c, int32_t leaf, double* Z_out) {
     if (leaf < 0 || leaf >= c->L || !Z_out) return fail(c, DSMGP_E_ARG, "targets_fetch: leaf out of range or Z_out is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     const LeafHost& lf = c->leaves[leaf];
-    const double* z = c->arenaT + c->toff[(size_t)leaf] + (size_t)lf.npad * c->tg_qpad;
+    const double* z = c->arenaT.p + c->toff[(size_t)leaf] + (size_t)lf.npad * c->tg_qpad;
     HIPCHK(c, hipMemcpy2D(Z_out, (size_t)lf.n * sizeof(double), z, (size_t)lf.npad * sizeof(double), (size_t)lf.n * sizeof(double),
                           (size_t)c->tg_Q, hipMemcpyDeviceToHost));
     return 0;
@@ -5022,10 +4957,10 @@ int dsmgp_targets_fetch(dsmgp_ctx* c, int32_t leaf, double* Z_out) {
 namespace {
 // An arena of npad x Qpad doubles per leaf at offset toff / 2 (A, U): grown on first use, from the pool when there is one
 // (static, like build_targets_plan: inside extern "C" an unnamed namespace alone still exports the name)
-static int targets_slab(dsmgp_ctx* c, double*& p, size_t& cap, const char* what) {
+static int targets_slab(dsmgp_ctx* c, DevArena& a, const char* what) {
     size_t tot = 0;
     for (int l = 0; l < c->L; ++l) tot += (size_t)c->leaves[l].npad * (size_t)c->tg_qpad;
-    if (int rc = slab_grow(c, p, cap, tot)) {
+    if (int rc = arena_status(c, a.grow(arena_pool(c), tot))) {
         (void)hipGetLastError();
         return rc == DSMGP_E_NOMEM ? rc : fail(c, DSMGP_E_NOMEM, std::string(what) + " (" + std::to_string((tot * 8) >> 20) + " MiB)");
     }
@@ -5036,12 +4971,12 @@ static void targets_a_tasks(const dsmgp_ctx* c, std::vector<TargetsATask>& ta) {
     ta.clear();
     for (int l = 0; l < c->L; ++l) {
         const LeafHost& lf = c->leaves[l];
-        const double* Xt = c->arenaX + c->gxoff[(size_t)lf.owner];
+        const double* Xt = c->arenaX.p + c->gxoff[(size_t)lf.owner];
         for (int i = 0; i < lf.nb; ++i) {
             TargetsATask t{};
             t.Xt = Xt + (size_t)i * TB;
-            t.Z = c->arenaT + c->toff[(size_t)l] + (size_t)lf.npad * c->tg_qpad;
-            t.A = c->arenaA + c->toff[(size_t)l] / 2 + (size_t)i * TB;
+            t.Z = c->arenaT.p + c->toff[(size_t)l] + (size_t)lf.npad * c->tg_qpad;
+            t.A = c->arenaA.p + c->toff[(size_t)l] / 2 + (size_t)i * TB;
             t.ldt = c->leaves[lf.owner].npad;
             t.ldz = lf.npad;
             t.k0 = i * TB;
@@ -5079,10 +5014,10 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     // L^-T of every factor owner (xinv_lists / xinv_fill); lists of the call's own are dropped again on every way out
     OwnGradLists own_lists{c};
     if (int rc = xinv_lists(c, own_lists)) return rc;
-    if (int rc = targets_slab(c, c->arenaA, c->cap_A, "targets_gradients: no room for A = L^-T Z")) return rc;
+    if (int rc = targets_slab(c, c->arenaA, "targets_gradients: no room for A = L^-T Z")) return rc;
     const int gs = any_rq(c) ? 3 + D : (any_ard || any_prod) ? 2 + D : 2;
-    auto Xt = [&](int l) { return c->arenaX + c->gxoff[(size_t)c->leaves[l].owner]; };
-    auto Al = [&](int l) { return c->arenaA + c->toff[(size_t)l] / 2; };
+    auto Xt = [&](int l) { return c->arenaX.p + c->gxoff[(size_t)c->leaves[l].owner]; };
+    auto Al = [&](int l) { return c->arenaA.p + c->toff[(size_t)l] / 2; };
     std::vector<TargetsATask> ta;
     targets_a_tasks(c, ta);
     std::vector<FrobTask> frob;
@@ -5164,7 +5099,7 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     if (!ta.empty()) targets_a_kernel<<<(unsigned)ta.size(), 256, 0, c->stream>>>(c->tga.p, qpad);
     launch_graddot<GD_TARGETS>(c, c->tgdot.p, ranges, pdot, gs);
     if (!frob.empty()) frob_kernel<<<(unsigned)frob.size(), 256, 0, c->stream>>>(c->tgfrob.p, pfrob);
-    targets_wsums_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->arenaT, c->d_toff.p, c->arenaA, c->d_tgw.p, L, Q, qpad, pleaf);
+    targets_wsums_kernel<<<L, 256, 0, c->stream>>>(c->d_leaves.p, c->arenaT.p, c->d_toff.p, c->arenaA.p, c->d_tgw.p, L, Q, qpad, pleaf);
     if (!quad.empty())
         ardlin_quad_kernel<false><<<dim3((unsigned)quad.size(), (unsigned)((D + ARDLIN_DC - 1) / ARDLIN_DC)), 256, 0, c->stream>>>(
             c->tgquad.p, D, pquad);
@@ -5244,18 +5179,18 @@ int build_loo_grad_plan(dsmgp_ctx* c) {
     }
     if (any_ardse && D > GRADDOT_STAGE_D)
         return fail(c, DSMGP_E_ARG, "loo_gradients: ArdSE length-scale gradients need D <= " + std::to_string(GRADDOT_STAGE_D));
-    if (!c->arenaH) {
+    if (!c->arenaH.p) {
         size_t freeB = 0, totalB = 0;
         HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
-        if (!c->pool_base && hTot * sizeof(double) + (size_t(2) << 30) > freeB)
+        if (!c->pool.active() && hTot * sizeof(double) + (size_t(2) << 30) > freeB)
             return fail(c, DSMGP_E_NOMEM, "loo_gradients need " + std::to_string((hTot * 8) >> 20) + " MiB for K_y^-1, device has " +
                                               std::to_string(freeB >> 20) + " MiB free");
-        if (int rc = arena_get(c, c->arenaH, hTot)) return rc;
+        if (int rc = arena_status(c, c->arenaH.get(arena_pool(c), hTot))) return rc;
     }
     if (int rc = c->d_lgvec.alloc(c, vTot)) return rc;
-    auto H = [&](int l) { return c->arenaH + hoff[l]; };
+    auto H = [&](int l) { return c->arenaH.p + hoff[l]; };
     auto V = [&](int l) { return c->d_lgvec.p + voff[l]; };
-    auto Xt = [&](int l) { return c->arenaX + c->gxoff[c->leaves[l].owner]; };
+    auto Xt = [&](int l) { return c->arenaX.p + c->gxoff[c->leaves[l].owner]; };
 
     std::vector<LooVecTask> vt((size_t)L);
     std::vector<LooHvecTask> hv;
@@ -5443,7 +5378,7 @@ static int loo_columns_prepare(dsmgp_ctx* c, OwnGradLists& own) {
     if (int rc = xinv_lists(c, own)) return rc;
     if (!c->has(P_LOO_LISTS))
         if (int rc = build_loo_plan(c)) return rc;
-    if (int rc = targets_slab(c, c->arenaA, c->cap_A, "loo_columns: no room for A = L^-T Z")) return rc;
+    if (int rc = targets_slab(c, c->arenaA, "loo_columns: no room for A = L^-T Z")) return rc;
     std::vector<TargetsATask> ta;
     targets_a_tasks(c, ta);
     return dev_upload(c, c->tga, ta);
@@ -5470,7 +5405,7 @@ int dsmgp_loo_columns(dsmgp_ctx* c, double* mu_out, int64_t ld, double* var_out,
     if (int rc = loo_columns_prepare(c, own_lists)) return rc;
     std::vector<LooColsTask> lt((size_t)L);
     for (int l = 0; l < L; ++l) {
-        lt[(size_t)l].A = c->arenaA + c->toff[(size_t)l] / 2;
+        lt[(size_t)l].A = c->arenaA.p + c->toff[(size_t)l] / 2;
         lt[(size_t)l].npad = c->leaves[l].npad;
         lt[(size_t)l].Q = Q;
     }
@@ -5518,7 +5453,7 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
     HIPCHK(c, hipSetDevice(c->device));
     OwnGradLists own_lists{c};
     if (int rc = loo_columns_prepare(c, own_lists)) return rc;
-    if (int rc = targets_slab(c, c->arenaU, c->cap_U, "loo_columns_gradients: no room for U = K_y^-1 (A / d)")) return rc;
+    if (int rc = targets_slab(c, c->arenaU, "loo_columns_gradients: no room for U = K_y^-1 (A / d)")) return rc;
     std::vector<size_t> hoff((size_t)L, 0), voff((size_t)L, 0);
     size_t hTot = 0, vTot = 0;
     for (int l = 0; l < L; ++l) {
@@ -5527,17 +5462,17 @@ int dsmgp_loo_columns_gradients(dsmgp_ctx* c, double* grad_out, int32_t stride, 
         hTot += (size_t)c->leaves[l].npad * c->leaves[l].npad;
         vTot += 3 * (size_t)c->leaves[l].npad;
     }
-    if (int rc = slab_grow(c, c->arenaHc, c->cap_Hc, hTot)) {
+    if (int rc = arena_status(c, c->arenaHc.grow(arena_pool(c), hTot))) {
         (void)hipGetLastError();
         return rc == DSMGP_E_NOMEM ? rc : fail(c, DSMGP_E_NOMEM, "loo_columns_gradients: no room for K_y^-1 (" + std::to_string((hTot * 8) >> 20) + " MiB)");
     }
     if (int rc = c->d_lcvec.grow(c, std::max<size_t>(1, vTot))) return rc;
     if (int rc = c->d_lcw.grow(c, W.size())) return rc;
-    auto H = [&](int l) { return c->arenaHc + hoff[(size_t)l]; };
+    auto H = [&](int l) { return c->arenaHc.p + hoff[(size_t)l]; };
     auto V = [&](int l) { return c->d_lcvec.p + voff[(size_t)l]; };
-    auto Al = [&](int l) { return c->arenaA + c->toff[(size_t)l] / 2; };
-    auto Ul = [&](int l) { return c->arenaU + c->toff[(size_t)l] / 2; };
-    auto Xt = [&](int l) { return c->arenaX + c->gxoff[(size_t)c->leaves[l].owner]; };
+    auto Al = [&](int l) { return c->arenaA.p + c->toff[(size_t)l] / 2; };
+    auto Ul = [&](int l) { return c->arenaU.p + c->toff[(size_t)l] / 2; };
+    auto Xt = [&](int l) { return c->arenaX.p + c->gxoff[(size_t)c->leaves[l].owner]; };
     const double* wdev = c->d_lcw.p;
 
     std::vector<LooColsTask> lt((size_t)L);
@@ -5825,17 +5760,12 @@ int dsmgp_reserve(dsmgp_ctx* c, int64_t bytes) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_plan_and_test(c);
-    if (c->pool_base) (void)hipFree(c->pool_base);
-    c->pool_base = nullptr;
-    c->pool_cap = c->pool_top = c->pool_mark_plan = 0;
+    c->pool.release();
     if (bytes == 0) return 0;
-    void* p = nullptr;
-    if (hipMalloc(&p, (size_t)bytes) != hipSuccess) {
+    if (c->pool.reserve((size_t)bytes) != 0) {
         (void)hipGetLastError();
         return fail(c, DSMGP_E_NOMEM, "cannot reserve " + std::to_string(bytes >> 20) + " MiB of device memory");
     }
-    c->pool_base = static_cast<char*>(p);
-    c->pool_cap = (size_t)bytes;
     return 0;
 }
 

@@ -39,7 +39,12 @@ def _compare_with_scratch(tag, a, b, T, mll_a, info_a, mll_b, info_b):
     """Context a (old fit + append_rows) against context b (from scratch on the grown table): info, mll, factor and alpha of
     every leaf.  Prints every figure before it asserts.  Returns the factors of a."""
     sizes = [len(o) for o in T.grown()[2]]
-    Fa, Fb = at.factors(a, sizes), at.factors(b, sizes)
+    return _compare_downloads(tag, at.factors(a, sizes), at.factors(b, sizes), T, mll_a, info_a, mll_b, info_b)
+
+
+def _compare_downloads(tag, Fa, Fb, T, mll_a, info_a, mll_b, info_b):
+    """_compare_with_scratch on factors downloaded already (a context that has moved on since)."""
+    sizes = [len(o) for o in T.grown()[2]]
     assert np.array_equal(info_a, info_b), (tag, info_a, info_b)
     for l in range(T.L):
         (F, al), (G, bl) = Fa[l], Fb[l]
@@ -487,6 +492,126 @@ def test_two_contexts_through_the_same_sequence_agree_bitwise():
             assert np.array_equal(F, G) and np.array_equal(al, bl)
     finally:
         _close(*ctxs)
+
+
+def _transition_tables():
+    """Leaves of 100, 130 and 260 rows (padded 128, 256, 384: the smallest table in which an appended row can and cannot move a
+    padded size) and a COPY of the 260-row leaf; D = 2.  T1 adds rows that leave every padded size as it is; T2, on top of it,
+    takes the 100-row leaf (110 by then) past 128 and gives the 130-row leaf nothing.  24 routed test rows."""
+    X, y, Xn1, yn1 = at._data("iso", 490, 23, 4711)
+    _, _, Xn2, yn2 = at._data("iso", 1, 28, 4712)
+    lists = [np.arange(0, 100), np.arange(100, 230), np.arange(230, 490), np.arange(230, 490)]
+    op, src = [at.SHARE_FULL] * 3 + [at.SHARE_COPY], [-1, -1, -1, 2]
+    mean = [0.5, 0.4, 0.6, 0.45]
+    adds1 = [np.arange(0, 10), np.arange(10, 15), np.arange(15, 23), np.arange(15, 23)]
+    T1 = at.Table("iso", X, y, lists, op, src, [0] * 4, mean, Xn1, yn1, adds1, None)
+    Xg, yg, lists1, op1, src1, mean1 = T1.grown()
+    adds2 = [np.arange(0, 25), np.zeros(0, np.int64), np.arange(25, 28), np.arange(25, 28)]
+    T2 = at.Table("iso", Xg, yg, lists1, op1, src1, [0] * 4, mean1, Xn2, yn2, adds2, [0.52, 0.4, 0.61, 0.44])
+    assert [-(-len(o) // at.TB) for o in lists] == [-(-len(o) // at.TB) for o in lists1] == [1, 2, 3, 3]
+    assert [-(-len(o) // at.TB) for o in T2.grown()[2]] == [2, 2, 3, 3] and T2.grown()[3] == op
+    c = [10, 6, 5, 3]
+    Xt = np.asfortranarray(np.random.default_rng(8).uniform(size=(max(c), 2)))
+    rptr = np.concatenate([[0], np.cumsum(c)]).astype(np.int64)
+    assert rptr[-1] == 24
+    return T1, T2, (Xt, rptr, np.concatenate([np.arange(k) for k in c]).astype(np.int64), c)
+
+
+def _walk_the_transitions(a, T1, T2, test):
+    """The sequence of test_one_context_through_every_ownership_transition on context a.  Returns every output in order and,
+    per append, what the comparison with a fresh context needs."""
+    Xt, rptr, ridx, c = test
+    out, calls = [], []
+
+    def registered_and_predicted():
+        a.set_test(Xt, rptr, ridx)
+        a.predict_run()
+        out.extend(a.predict_fetch())
+
+    out.extend(at.fit_old(a, T1)[:2])
+    registered_and_predicted()
+    out.append(a.gradients(3))
+    for pool in (256 << 20, 0):                                         # every arena carved from the pool, then its own again
+        a.reserve(pool)
+        out.extend(a.fit()[:2])
+        registered_and_predicted()
+    for T in (T1, T2):
+        n_old, n_new = [len(o) for o in T.lists], [len(o) for o in T.grown()[2]]
+        before = at.factors(a, n_old)
+        V0 = [a.download_vt(l, c[l], n_old[l]) for l in range(T.L)]
+        ptr, idx = T.add_csr()
+        mll, info, _ = a.append_rows(T.Xn, T.yn, ptr, idx, T.mean_new, keep_test=True)
+        a.predict_run()
+        mu, var = a.predict_fetch()
+        after = at.factors(a, n_new)
+        V1 = [a.download_vt(l, c[l], n_new[l]) for l in range(T.L)]
+        calls.append(dict(mll=mll, info=info, before=before, after=after, V0=V0, V1=V1, mu=mu, var=var,
+                          append_stats=a.append_stats(), resume_stats=a.resume_stats()))
+        out.extend([mll, info, mu, var] + [x for F, al in after for x in (F, al)] + V1)
+    grads = a.gradients(3)
+    loo = a.loo()
+    out.extend([grads, *loo])
+    return out, calls, grads, loo
+
+
+def test_one_context_through_every_ownership_transition():
+    """fit, set_test, predict_run, gradients; the same under a reserved pool and again without it; an append that keeps the test
+    set in place, predict_run; one that relocates, predict_run, gradients, loo.  After each append a fresh context b on the grown
+    table: factors, mll and alpha as test_table_against_from_scratch_and_the_oracle compares them, the moments within
+    pred_tolerance.moment_tol; the kept blocks and the kept columns of K_tn L^-T are the bits a had before the call.  A second
+    context through the same sequence gives the same bits everywhere."""
+    T1, T2, test = _transition_tables()
+    Xt, rptr, ridx, c = test
+    a, a2 = _contexts(2)
+    try:
+        out, calls, grads, loo = _walk_the_transitions(a, T1, T2, test)
+        out2 = _walk_the_transitions(a2, T1, T2, test)[0]
+        assert len(out) == len(out2)
+        for i, (x, y) in enumerate(zip(out, out2)):
+            assert np.array_equal(x, y), f"output {i} of the two contexts differs"
+        for T, r, tag in ((T1, calls[0], "transitions: in place"), (T2, calls[1], "transitions: relocate")):
+            Xg, yg, lists, _, _, mean = T.grown()
+            (b,) = _contexts(1)
+            try:
+                mll_b, info_b, _ = at.fit_grown(b, T)
+                assert np.all(r["info"] == 0)
+                sizes = [len(o) for o in lists]
+                _compare_downloads(tag, r["after"], at.factors(b, sizes), T, r["mll"], r["info"], mll_b, info_b)
+                ref, Lo, ao = _oracle(T)
+                assert np.all(np.abs(r["mll"] - ref) <= RTOL * np.abs(ref)), tag
+                assert max(np.max(np.abs(r["after"][l][0] - Lo[l])) / np.max(np.abs(Lo[l])) for l in range(T.L)) <= RTOL, tag
+                assert max(np.max(np.abs(r["after"][l][1] - ao[l])) / np.max(np.abs(ao[l])) for l in range(T.L)) <= RTOL, tag
+                b.set_test(Xt, rptr, ridx)
+                b.predict_run()
+                mb, vb = b.predict_fetch()
+                noise = float(np.exp(2.0 * T.hyp[-1]))
+                tm, tv = moment_tol(mb, vb, np.ones(mb.size), noise, max(1.0, float(np.max(np.abs(yg)))))
+                _check(f"{tag} mu", r["mu"], mb, tm)
+                _check(f"{tag} var", r["var"], vb, tv)
+                if T is T2:
+                    gb = b.gradients(3)
+                    _check(f"{tag} gradients", grads, gb, 1e-9 * max(1.0, float(np.max(np.abs(gb)))))
+                    mlb, vlb, llb = b.loo()
+                    ptr = np.concatenate([[0], np.cumsum(sizes)])
+                    for l, o in enumerate(lists):
+                        s = slice(ptr[l], ptr[l + 1])
+                        tmu, tvar, _, ts = loo_dense.loo_tol(yg[o], mlb[s], vlb[s], np.ones(len(o)), noise)
+                        _check(f"{tag} loo mu leaf {l}", loo[0][s], mlb[s], tmu)
+                        _check(f"{tag} loo var leaf {l}", loo[1][s], vlb[s], tvar)
+                        _check(f"{tag} loo lpd leaf {l}", loo[2][l], llb[l], ts)
+            finally:
+                _close(b)
+            _assert_kept_bits(tag, T, r["before"], r["after"], None)
+            kb = T.kept_blocks(None)
+            for l in range(T.L):                                        # a COPY leaf reads its source's factor
+                k = min((kb[T.src[l]] if T.op[l] == at.SHARE_COPY else kb[l]) * at.TB, len(T.lists[l]))
+                assert k == 0 or np.array_equal(r["V0"][l][:, :k], r["V1"][l][:, :k]), (tag, l, k)
+            print(f"\n{tag}: {r['append_stats']} {r['resume_stats']}")
+            assert r["resume_stats"]["test_set_dropped"] == 0 and r["resume_stats"]["leaves_kept"] > 0
+        assert calls[0]["append_stats"]["bytes_relocated"] == 0 and calls[0]["resume_stats"]["bytes_relocated"] == 0
+        assert calls[1]["append_stats"]["bytes_relocated"] > 0 and calls[1]["resume_stats"]["bytes_relocated"] > 0
+    finally:
+        _close(a, a2)
 
 
 def test_add_data_on_a_small_dsmgp_against_the_hand_grown_copy():

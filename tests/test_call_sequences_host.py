@@ -198,6 +198,18 @@ def test_the_context_s_dependency_table_is_the_model_s(tmp_path):
     assert not wrong, wrong
 
 
+def test_the_arena_and_pool_owners_free_each_block_once(tmp_path):
+    """csrc/dev_owner.hpp on the counting host allocator of tests/dev_owner_check.cpp: moves, the adoption sequence of an append,
+    pool carving and the three growth policies at their boundaries.  The program aborts on a free of a block that is not live
+    and fails when a block is live at exit."""
+    exe = str(tmp_path / "dev_owner_check")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "deepstructuredmixtures_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "dev_owner_check.cpp"), "-o", exe], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and "FAILED" not in run.stdout, run.stdout + run.stderr
+    assert run.stdout.count("case: ") == 8 and run.stdout.rstrip().endswith("all cases passed"), run.stdout
+
+
 @pytest.fixture(scope="module")
 def oracle_run():
     """Every committed sequence on the dense chain, once: [(sequence id, index, call, before, [(ref, tol)])], the conds, the infos."""

@@ -10,6 +10,8 @@ trap 'rm -rf "$out"' EXIT
 cd "$here/micro"
 $cxx -O1 -g -std=c++17 -ffp-contract=off -pthread -fsanitize=address,undefined -fno-omit-frame-pointer host_sanitize.cpp -o "$out/asan"
 "$out/asan"
+$cxx -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -I"$here/../deepstructuredmixtures_amd/csrc" "$here/../tests/dev_owner_check.cpp" -o "$out/owners"
+"$out/owners"
 $cxx -O1 -g -std=c++17 -ffp-contract=off -pthread -fsanitize=thread host_sanitize.cpp -o "$out/tsan"
 "$out/tsan"
 echo "host code: clean under ASan+UBSan and TSan"
