@@ -9,6 +9,8 @@ tests) or when that path cannot be set up, through `torch.distributed` from host
 """
 import numpy as np
 
+from .leafset import LeafSubset, csr_ptr, share_roots
+
 
 # The process group the exchanges of the path travel over: None = the default group.  A launcher may keep a host-side (gloo)
 # default group for agreement and bookkeeping and hand the data path a second group of its own -- bench.py does: its RCCL group
@@ -36,7 +38,10 @@ class Shard:
         self.owner = np.asarray(owner, dtype=np.int64)
         self.rank = int(rank)
         self.world = int(world)
-        self.local = np.flatnonzero(self.owner == self.rank)
+        self.subsets = [LeafSubset(np.flatnonzero(self.owner == r), self.owner.size) for r in range(self.world)]
+        self.subset = self.subsets[self.rank]      # this rank's leaves: what its context holds as a table of its own
+        self.local = self.subset.loc
+        self.max_leaves = max(sub.loc.size for sub in self.subsets)      # slots per rank of a padded per-leaf exchange
         self.comm_ctx = None          # hipabi.Context whose RCCL communicator carries the exchanges (device_comm)
         self.exchange_seconds = 0.0   # wall time this rank has spent inside the exchange collectives (waiting for the slowest
         self.exchanges = 0            # rank included): bench.py prints it per rank, so an N-GPU line explains its own efficiency
@@ -146,15 +151,11 @@ class Shard:
         With more than one rank the FIRST exchange of a communicator is cross-checked against the torch.distributed
         gather of `local_cols` (this rank's (n_local, 2) results); a mismatch on any rank drops the device path on all."""
         import time
-        counts = np.bincount(self.owner, minlength=self.world)
         t0 = time.perf_counter()
-        both = np.asarray(ctx.fit_exchange(int(max(1, counts.max()))))
+        both = np.asarray(ctx.fit_exchange(max(1, self.max_leaves)))
         self.exchange_seconds += time.perf_counter() - t0
         self.exchanges += 1
-        out = np.empty((self.owner.size, 2))
-        for r in range(self.world):
-            idx = np.flatnonzero(self.owner == r)
-            out[idx] = both[r, : idx.size]
+        out = self._put_leaves(np.empty((self.owner.size, 2)), both)
         if self.world > 1 and not getattr(self, "verified", True) and local_cols is not None:
             ref = self.gather_leaf_columns(local_cols)
             same = int(np.array_equal(ref, out))
@@ -184,20 +185,12 @@ class Shard:
         nt = np.zeros(L) if n_test is None else np.asarray(n_test, dtype=np.float64)
         cost = nobs ** 3 / 3.0 + nobs ** 2 * nt
         steps = np.ceil(nobs / 128.0)
-        group = np.arange(L)
-        for j in range(L):
-            if op[j] != 0 and src[j] >= 0:
-                group[j] = src[j]
-        for j in range(L):          # resolve one level of chaining
-            group[j] = group[group[j]]
-        gcost = np.zeros(L)
-        for j in range(L):
-            gcost[group[j]] += cost[j] if op[j] == 0 else 2.0 * nobs[j] ** 2
+        group = share_roots(op, src, L)
+        gcost = np.bincount(group, weights=np.where(np.asarray(op) == 0, cost, 2.0 * nobs ** 2), minlength=L)
         roots = [g for g in range(L) if group[g] == g]
         roots.sort(key=lambda g: (-gcost[g], g))
         gsteps = np.zeros(L)
-        for j in range(L):
-            gsteps[group[j]] = max(gsteps[group[j]], steps[j])
+        np.maximum.at(gsteps, group, steps)
         load = np.zeros(world)
         maxsteps = np.zeros(world)
         owner_of_root = {}
@@ -247,19 +240,18 @@ class Shard:
             tot += p
         return tot.reshape(local.shape)
 
+    def _put_leaves(self, out, parts):
+        """out[leaves of rank r] = the first rows of parts[r] (the rest is padding), for every rank."""
+        for sub, part in zip(self.subsets, parts):
+            sub.put_leaves(out, part[: sub.loc.size])
+        return out
+
     def gather_leaf_values(self, local_vals):
         """local_vals[i] belongs to leaf self.local[i]; returns the value of every leaf."""
-        L = self.owner.size
         local_vals = np.asarray(local_vals, dtype=np.float64)
         if self.world == 1:
             return local_vals.copy()
-        counts = np.bincount(self.owner, minlength=self.world)
-        parts = self._all_gather_padded(local_vals, int(counts.max()))
-        out = np.empty(L)
-        for r in range(self.world):
-            idx = np.flatnonzero(self.owner == r)
-            out[idx] = parts[r][: idx.size]
-        return out
+        return self._put_leaves(np.empty(self.owner.size), self._all_gather_padded(local_vals, self.max_leaves))
 
     def gather_leaf_columns(self, local_cols):
         """Several per-leaf quantities in ONE collective: local_cols is (n_local_leaves, k); returns (L, k)."""
@@ -267,13 +259,8 @@ class Shard:
         k = local_cols.shape[1]
         if self.world == 1:
             return local_cols.copy()
-        counts = np.bincount(self.owner, minlength=self.world)
-        parts = self._all_gather_padded(local_cols.reshape(-1), int(counts.max()) * k)
-        out = np.empty((self.owner.size, k))
-        for r in range(self.world):
-            idx = np.flatnonzero(self.owner == r)
-            out[idx] = parts[r][: idx.size * k].reshape(idx.size, k)
-        return out
+        parts = self._all_gather_padded(local_cols.reshape(-1), self.max_leaves * k)
+        return self._put_leaves(np.empty((self.owner.size, k)), [p.reshape(-1, k) for p in parts])
 
     def gather_ragged_pair(self, a_flat, b_flat, counts):
         """gather_ragged of two vectors with the same ragged layout (mu and var) in ONE collective."""
@@ -290,14 +277,10 @@ class Shard:
         local_flat = np.asarray(local_flat, dtype=np.float64)
         if self.world == 1:
             return local_flat.copy()
-        per_rank = np.array([counts[self.owner == r].sum() for r in range(self.world)])
+        per_rank = np.array([counts[sub.loc].sum() for sub in self.subsets])
         parts = self._all_gather_padded(local_flat, int(per_rank.max()))
-        ptr = np.concatenate([[0], np.cumsum(counts)])
+        ptr = csr_ptr(counts)
         out = np.empty(int(ptr[-1]))
-        for r in range(self.world):
-            pos = 0
-            for g in np.flatnonzero(self.owner == r):
-                c = int(counts[g])
-                out[ptr[g]:ptr[g] + c] = parts[r][pos:pos + c]
-                pos += c
+        for sub, part, n in zip(self.subsets, parts, per_rank):
+            sub.put_entries(out, ptr, part[:n])
         return out

@@ -7,6 +7,8 @@ import os
 import sys
 import numpy as np
 
+from .leafset import LeafSubset, share_roots
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdsmgp_hip.so")
 
@@ -798,9 +800,9 @@ class MultiContext:
     chip.  Leaves are independent, so results are exactly those of the single-context run per leaf.  Used for the
     per-rank shard of multi-GPU runs, where launches are too small to fill the GPU on their own."""
 
-    def __init__(self, device=0, n=2):
+    def __init__(self, device=0, n=2, make_context=Context):
         from concurrent.futures import ThreadPoolExecutor
-        self.subs = [Context(device) for _ in range(n)]
+        self.subs = [make_context(device) for _ in range(n)]
         self.pool = ThreadPoolExecutor(max_workers=n)
         self.L = 0
         self.route_total = 0
@@ -810,6 +812,7 @@ class MultiContext:
         self._test = None
         self._test_dirty = False
         self.part = None
+        self.subsets = None           # one LeafSubset per entry of part: every slice and scatter below goes through it
         self.act = self.subs          # contexts that hold leaves (all of them unless there are fewer leaf groups)
 
     def close(self):
@@ -862,11 +865,7 @@ class MultiContext:
         ptr = self._leaves[0]
         n = np.diff(ptr).astype(np.float64)
         op, src, _ = self._sharing
-        group = np.arange(self.L)
-        if op is not None:
-            for j in range(self.L):
-                if op[j] != 0 and src[j] >= 0:
-                    group[j] = src[j]
+        group = share_roots(op, src, self.L)
         cost = np.zeros(self.L)
         for j in range(self.L):
             cost[group[j]] += n[j] ** 3 if (op is None or op[j] == 0) else n[j] ** 2
@@ -883,19 +882,13 @@ class MultiContext:
         if not self._dirty:
             return
         ptr, idx, kid, mean = self._leaves
-        op, src, plen = self._sharing
         parts = self._partition()
         self.act = [s for s, loc in zip(self.subs, parts) if len(loc)]
         self.part = [loc for loc in parts if len(loc)]
-        for s, loc in zip(self.act, self.part):
-            lptr = np.concatenate([[0], np.cumsum(ptr[loc + 1] - ptr[loc])])
-            lidx = np.concatenate([idx[ptr[g]:ptr[g + 1]] for g in loc]) if len(loc) else np.zeros(0, np.int64)
-            s.set_leaves(lptr, lidx, kid[loc], mean[loc])
-            if op is None:
-                s.set_sharing(None, None, None)
-            else:
-                g2l = {int(g): i for i, g in enumerate(loc)}
-                s.set_sharing(op[loc], np.array([g2l.get(int(src[g]), -1) for g in loc], dtype=np.int32), plen[loc])
+        self.subsets = [LeafSubset(loc, self.L) for loc in self.part]
+        for s, sub in zip(self.act, self.subsets):
+            s.set_leaves(*sub.take_csr(ptr, idx), kid[sub.loc], mean[sub.loc])
+            s.set_sharing(*sub.take_sharing(*self._sharing))
         self._dirty = False
         self._test_dirty = self._test is not None
 
@@ -903,10 +896,8 @@ class MultiContext:
         if not self._test_dirty:
             return
         Xt, rptr, ridx = self._test
-        for s, loc in zip(self.act, self.part):
-            lptr = np.concatenate([[0], np.cumsum(rptr[loc + 1] - rptr[loc])])
-            lidx = np.concatenate([ridx[rptr[g]:rptr[g + 1]] for g in loc]) if len(loc) else np.zeros(0, np.int64)
-            s.set_test(Xt, lptr, lidx)
+        for s, sub in zip(self.act, self.subsets):
+            s.set_test(Xt, *sub.take_csr(rptr, ridx))
         self._test_dirty = False
 
     def fit(self):
@@ -915,9 +906,9 @@ class MultiContext:
         res = self._each(lambda s: s.fit())
         mll = np.empty(self.L)
         info = np.empty(self.L, dtype=np.int32)
-        for (m, i, _), loc in zip(res, self.part):
-            mll[loc] = m
-            info[loc] = i
+        for (m, i, _), sub in zip(res, self.subsets):
+            sub.put_leaves(mll, m)
+            sub.put_leaves(info, i)
         return mll, info, max(r[2] for r in res)
 
     def set_test(self, Xt, route_ptr, route_idx):
@@ -937,14 +928,10 @@ class MultiContext:
         _, rptr, _ = self._test
         mu = np.empty(self.route_total)
         var = np.empty(self.route_total)
-        for s, loc in zip(self.act, self.part):
+        for s, sub in zip(self.act, self.subsets):
             m, v = s.predict_fetch()
-            pos = 0
-            for g in loc:
-                c = int(rptr[g + 1] - rptr[g])
-                mu[rptr[g]:rptr[g + 1]] = m[pos:pos + c]
-                var[rptr[g]:rptr[g + 1]] = v[pos:pos + c]
-                pos += c
+            sub.put_entries(mu, rptr, m)
+            sub.put_entries(var, rptr, v)
         return mu, var
 
     def predict_leaves(self, Xt, route_ptr, route_idx):
@@ -964,14 +951,10 @@ class MultiContext:
         D = self.act[0].D
         dmu = np.empty((self.route_total, D), dtype=np.float64, order="F")
         dvar = np.empty((self.route_total, D), dtype=np.float64, order="F") if want_var else None
-        for (m, v), loc in zip(res, self.part):
-            pos = 0
-            for g in loc:
-                c = int(rptr[g + 1] - rptr[g])
-                dmu[rptr[g]:rptr[g + 1]] = m[pos:pos + c]
-                if want_var:
-                    dvar[rptr[g]:rptr[g + 1]] = v[pos:pos + c]
-                pos += c
+        for (m, v), sub in zip(res, self.subsets):
+            sub.put_entries(dmu, rptr, m)
+            if want_var:
+                sub.put_entries(dvar, rptr, v)
         self.grad_seconds = max(s.grad_seconds for s in self.act)
         return dmu, dvar
 
@@ -980,23 +963,23 @@ class MultiContext:
         coef = None if leaf_coef is None else np.asarray(leaf_coef, dtype=np.float64)
         grp = None if leaf_group is None else np.asarray(leaf_group, dtype=np.int32)
         tot = None
-        for s, loc in zip(self.act, self.part):
-            p = s.aggregate_partial(family, None if coef is None else coef[loc], None if grp is None else grp[loc], n_groups)
+        for s, sub in zip(self.act, self.subsets):
+            p = s.aggregate_partial(family, None if coef is None else coef[sub.loc], None if grp is None else grp[sub.loc], n_groups)
             tot = p if tot is None else tot + p
         return tot
 
     def set_gradient_leaves(self, active=None):
         self._upload()
         a = None if active is None else np.asarray(active) != 0
-        for s, loc in zip(self.act, self.part):
-            s.set_gradient_leaves(None if a is None else a[loc])
+        for s, sub in zip(self.act, self.subsets):
+            s.set_gradient_leaves(None if a is None else a[sub.loc])
 
     def gradients(self, stride):
         self._upload()
         res = self._each(lambda s: s.gradients(stride))
         g = np.zeros((self.L, stride))
-        for r, loc in zip(res, self.part):
-            g[loc] = r
+        for r, sub in zip(res, self.subsets):
+            sub.put_leaves(g, r)
         return g
 
     def loo_gradients(self, stride):
@@ -1006,9 +989,9 @@ class MultiContext:
         res = self._each(lambda s: s.loo_gradients(stride))
         g = np.zeros((self.L, stride))
         lpd = np.empty(self.L)
-        for (r, d), loc in zip(res, self.part):
-            g[loc] = r
-            lpd[loc] = d
+        for (r, d), sub in zip(res, self.subsets):
+            sub.put_leaves(g, r)
+            sub.put_leaves(lpd, d)
         self.loo_gradients_seconds = max(s.loo_gradients_seconds for s in self.act)
         return g, lpd
 
@@ -1021,14 +1004,10 @@ class MultiContext:
         mu = np.empty(int(ptr[-1]))
         var = np.empty_like(mu)
         lpd = np.empty(self.L)
-        for (m, v, d), loc in zip(res, self.part):
-            pos = 0
-            for g in loc:
-                c = int(ptr[g + 1] - ptr[g])
-                mu[ptr[g]:ptr[g + 1]] = m[pos:pos + c]
-                var[ptr[g]:ptr[g + 1]] = v[pos:pos + c]
-                pos += c
-            lpd[loc] = d
+        for (m, v, d), sub in zip(res, self.subsets):
+            sub.put_entries(mu, ptr, m)
+            sub.put_entries(var, ptr, v)
+            sub.put_leaves(lpd, d)
         self.loo_seconds = max(s.loo_seconds for s in self.act)
         return mu, var, lpd
 
@@ -1150,8 +1129,8 @@ class StreamingContext:
     recomputed by the next pass, which is what `train!` does anyway (every iteration changes the hyper-parameters).
     Interface of `Context`; results per leaf are those of the resident run."""
 
-    def __init__(self, device=0, budget_bytes=None, headroom=0.85):
-        self.ctx = Context(device)
+    def __init__(self, device=0, budget_bytes=None, headroom=0.85, make_context=Context):
+        self.ctx = make_context(device)
         self.budget = budget_bytes
         self.headroom = headroom
         self.L = 0
@@ -1221,11 +1200,7 @@ class StreamingContext:
         n = np.diff(ptr)
         nt = np.diff(self._test[1]) if self._test is not None else np.zeros(self.L, dtype=np.int64)
         op, src, _ = self._sharing
-        unit = np.arange(self.L)
-        if op is not None:
-            for j in range(self.L):
-                if op[j] != 0 and src[j] >= 0:
-                    unit[j] = src[j]           # leaves sharing a factor travel together
+        unit = share_roots(op, src, self.L)        # leaves sharing a factor travel together
         budget = self.budget
         if budget is None:
             if self._pool_bytes:               # the pool holds the memory: keep the budget it was sized for
@@ -1271,7 +1246,6 @@ class StreamingContext:
         if self.groups is None:
             self._make_groups()
         ptr, idx, kid, mean = self._leaves
-        op, src, plen = self._sharing
         mll = np.empty(self.L)
         info = np.zeros(self.L, dtype=np.int32)
         mu = np.empty(self.route_total)
@@ -1297,36 +1271,25 @@ class StreamingContext:
                 print(f"# streaming pass {self.passes + 1}: group {gi + 1}/{len(self.groups)} ({len(loc)} leaves) at "
                       f"{_time.perf_counter() - t_pass:.1f} s", file=sys.stderr, flush=True)
             c = self.ctx
-            lptr = np.concatenate([[0], np.cumsum(ptr[loc + 1] - ptr[loc])])
-            timed("set_leaves", c.set_leaves, lptr, np.concatenate([idx[ptr[g]:ptr[g + 1]] for g in loc]), kid[loc], mean[loc])
-            if op is None:
-                timed("set_sharing", c.set_sharing, None, None, None)
-            else:
-                g2l = {int(g): i for i, g in enumerate(loc)}
-                timed("set_sharing", c.set_sharing, op[loc],
-                      np.array([g2l.get(int(src[g]), -1) for g in loc], dtype=np.int32), plen[loc])
+            sub = LeafSubset(loc, self.L)
+            timed("set_leaves", c.set_leaves, *sub.take_csr(ptr, idx), kid[loc], mean[loc])
+            timed("set_sharing", c.set_sharing, *sub.take_sharing(*self._sharing))
             if self._test is not None:
                 Xt, rptr, ridx = self._test
-                tptr = np.concatenate([[0], np.cumsum(rptr[loc + 1] - rptr[loc])])
-                timed("set_test", c.set_test, Xt, tptr, np.concatenate([ridx[rptr[g]:rptr[g + 1]] for g in loc]))
+                timed("set_test", c.set_test, Xt, *sub.take_csr(rptr, ridx))
             m, i, s = timed("fit", c.fit)
-            mll[loc], info[loc] = m, i
+            sub.put_leaves(mll, m)
+            sub.put_leaves(info, i)
             seconds += s
             if self._test is not None:
                 tpred += c.predict_run()
                 gm, gv = c.predict_fetch()
-                pos = 0
-                for g in loc:
-                    k = int(rptr[g + 1] - rptr[g])
-                    mu[rptr[g]:rptr[g + 1]] = gm[pos:pos + k]
-                    var[rptr[g]:rptr[g + 1]] = gv[pos:pos + k]
-                    pos += k
+                sub.put_entries(mu, rptr, gm)
+                sub.put_entries(var, rptr, gv)
             if self.want_gradients:
-                grads[loc] = c.gradients(self.want_gradients)
-            for g in self.keep_alpha:
-                li = np.flatnonzero(loc == g)
-                if li.size:
-                    alphas[int(g)] = c.download_factor(int(li[0]), int(ptr[g + 1] - ptr[g]), factor=False)[1]
+                sub.put_leaves(grads, c.gradients(self.want_gradients))
+            for g in np.intersect1d(loc, self.keep_alpha):
+                alphas[int(g)] = c.download_factor(int(sub.global_to_local()[g]), int(ptr[g + 1] - ptr[g]), factor=False)[1]
             for k_, v_ in c.timings().items():
                 tsum[k_] = tsum.get(k_, 0.0) + v_
             f_, n_ = c.work()

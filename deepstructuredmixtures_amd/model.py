@@ -259,23 +259,16 @@ class Model:
         self.ctx.set_leaves(ptr, idx, [lf.kernelid for lf in lv], [lf.mean.m for lf in lv])
         if self.D is not None and tau is not None:
             op, src, plen, _ = self._set_decisions(share_decisions(self.leaves, self.D, tau))
-            g2l = {g: i for i, g in enumerate(loc)}
-            lop = np.zeros(len(lv), dtype=np.int32)
-            lsrc = np.full(len(lv), -1, dtype=np.int32)
-            lpl = np.zeros(len(lv), dtype=np.int64)
-            for i, g in enumerate(loc):
-                if op[g] != SHARE_FULL and int(src[g]) in g2l:   # source must live on the same rank
-                    lop[i], lsrc[i], lpl[i] = op[g], g2l[int(src[g])], plen[g]
-            self.ctx.set_sharing(lop, lsrc, lpl)
+            self.ctx.set_sharing(*self.shard.subset.take_sharing(op, src, plen))   # (a source must live on the same rank)
         else:
             self._set_decisions(None)
             self.ctx.set_sharing(None, None, None)
         self._uploaded = True
         self._schedule = key
         self._route_cache = None      # set_leaves dropped the device-side test set
-        self._register_tree(loc)
+        self._register_tree()
 
-    def _register_tree(self, loc):
+    def _register_tree(self):
         """The routing of `predict` (`src/common.jl:101-122,181-196,275-292`) on the device: hand the context the tree as flat
         arrays, with every region's index in THIS rank's leaf table (-1: held elsewhere).  DSMGP models on a plain context;
         anything else (and a tree deeper than the device walk's stack) keeps routing on the host."""
@@ -283,9 +276,7 @@ class Model:
         if self.family != "dsmgp" or self.root.kind == "gp" or not hasattr(self.ctx, "set_tree"):
             return
         ri = route_index(self.root)
-        g2l = np.full(self.L, -1, dtype=np.int64)
-        g2l[np.asarray(loc, dtype=np.int64)] = np.arange(len(loc))
-        leaf_local = np.where(ri.leaf >= 0, g2l[np.maximum(ri.leaf, 0)], -1)
+        leaf_local = np.where(ri.leaf >= 0, self.shard.subset.global_to_local()[np.maximum(ri.leaf, 0)], -1)
         try:
             self.ctx.set_tree(ri.kind, ri.first, ri.nchild, ri.sdim, ri.thr, leaf_local)
             self._device_routing = True
@@ -421,8 +412,7 @@ def leaf_covariance(model, xtest, leaf, with_noise=True):
     leaf = int(leaf)
     if not 0 <= leaf < model.L:
         raise ValueError(f"leaf {leaf}: the model has {model.L} leaves")
-    local = [int(g) for g in model.shard.local]
-    if model.shard.world > 1 and leaf not in local:
+    if model.shard.world > 1 and leaf not in model.shard.local:
         raise NotImplementedError(f"leaf {leaf} is held by another rank: leaf_covariance serves this rank's leaves only")
     xt = _test_matrix(model, xtest)
     rc = _routing(model, xt)
@@ -433,7 +423,7 @@ def leaf_covariance(model, xtest, leaf, with_noise=True):
         model.ctx.set_test(xt, rc["lptr"], rc["lidx"])      # (host lists: the rows come back in THIS order)
         rc["uploaded"] = True
     model.last_predict_seconds = model.ctx.predict_run()
-    return rows, model.ctx.predict_cov(local.index(leaf), rows.size, with_noise)
+    return rows, model.ctx.predict_cov(int(model.shard.subset.global_to_local()[leaf]), rows.size, with_noise)
 
 
 def posterior_sample(gp, xtest, n_samples, seed=0, with_noise=False):
@@ -1266,14 +1256,7 @@ def _routing(model, xt, host_routes=True):
         rc = model._route_cache = dict(key=key, ptr=None, idx=None, lptr=None, lidx=None, masks={}, uploaded=False)
     if host_routes and rc["ptr"] is None:
         ptr, idx = route(model.root, xt) if model.family == "dsmgp" else route_all(model.root, xt.shape[0])
-        loc = np.asarray(model.shard.local, dtype=np.int64)
-        if loc.size == ptr.size - 1 and np.array_equal(loc, np.arange(loc.size)):
-            lptr, lidx = ptr, idx                          # this rank holds every leaf, in order
-        else:                                              # the segments of this rank's leaves, one after the other (no loop
-            cnt = (ptr[1:] - ptr[:-1])[loc]                # over leaves: 18k of them at depth 4)
-            lptr = np.zeros(loc.size + 1, dtype=np.int64)
-            np.cumsum(cnt, out=lptr[1:])
-            lidx = idx[np.repeat(ptr[loc] - lptr[:-1], cnt) + np.arange(lptr[-1])] if loc.size else np.zeros(0, np.int64)
+        lptr, lidx = model.shard.subset.take_csr(ptr, idx)     # (ptr, idx themselves where this rank holds every leaf)
         rc.update(ptr=ptr, idx=idx, lptr=lptr, lidx=lidx)
     return rc
 
