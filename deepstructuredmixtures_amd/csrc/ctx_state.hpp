@@ -12,28 +12,30 @@ enum Product : uint32_t {
 };
 struct Row { Product product; const char* name; uint32_t parents; };
 
-// The chains: each product, its DIRECT parents (what it is made from or points into) and the storage it stands for.  The hyper-
-// parameters, the options and the mask are inputs: their setters invalidate what was made from them (dsmgp_set_hyper the fit).
+// The chains: each product, its DIRECT parents (what it is made from or points into) and the lifetime group of dsmgp_ctx that
+// holds its storage (csrc/dsmgp_hip.cpp: the group's declarations are the list of what falls; a CONTENT product names the group
+// whose arenas it fills).  The hyper-parameters, the options and the mask are inputs: their setters invalidate what was made
+// from them (dsmgp_set_hyper the fit).
 constexpr Row TABLE[] = {
-    {P_PLAN,       "plan",         0},                   // factor / Dinv / vector arenas, d_leaves, the solve lists (build_plan)
-    {P_PHASE,      "phase_lists",  P_PLAN},              // phase, slabF: the steps of a fit without resident test rows
-    {P_TEST,       "test",         P_PLAN},              // dXt, the CSR, arenaVt / Xt / PV, the sweep's lists: they point into the plan's arenas
-    {P_JOINT,      "joint_lists",  P_PLAN | P_TEST},     // phaseJ, slabJ: the steps of a fit with the test rows riding along
-    {P_FIT,        "fit",          P_PLAN},              // L, z, mll, info for the current hyper-parameters
-    {P_ALPHA,      "alpha",        P_FIT},               // alpha = L^-T z (ensure_alpha)
-    {P_DINV,       "dinv",         P_FIT},               // every Dinv_k whole: a fit's fused steps leave the 16x16 diagonal inverses only (ensure_dinv)
-    {P_VT,         "vt",           P_FIT | P_TEST},      // arenaVt = K_tn L^-T, from the fit the rows rode through or from predict_run's sweep
-    {P_PRED,       "prediction",   P_FIT | P_TEST},      // arenaPV: mu | var of every routed row
-    {P_PARTIAL,    "partial",      P_PRED},              // d_agg_part: this context's sums (agg_family / agg_G / agg_W describe them)
+    {P_PLAN,       "plan",         0},                   // PlanStore, as build_plan makes it
+    {P_PHASE,      "phase_lists",  P_PLAN},              // PlanStore: the steps of a fit without resident test rows (ensure_phase)
+    {P_TEST,       "test",         P_PLAN},              // TestInputs and TestProducts: the lists point into the plan's arenas
+    {P_JOINT,      "joint_lists",  P_PLAN | P_TEST},     // TestProducts: the steps of a fit with the test rows riding along (ensure_joint)
+    {P_FIT,        "fit",          P_PLAN},              // content of PlanStore: L, z, mll, info for the current hyper-parameters
+    {P_ALPHA,      "alpha",        P_FIT},               // content of PlanStore: alpha = L^-T z (ensure_alpha)
+    {P_DINV,       "dinv",         P_FIT},               // content of PlanStore: every Dinv_k whole: a fit's fused steps leave the 16x16 diagonal inverses only (ensure_dinv)
+    {P_VT,         "vt",           P_FIT | P_TEST},      // content of TestProducts: K_tn L^-T, from the fit the rows rode through or from predict_run's sweep
+    {P_PRED,       "prediction",   P_FIT | P_TEST},      // content of TestProducts: mu | var of every routed row
+    {P_PARTIAL,    "partial",      P_PRED},              // content of TestProducts: this context's sums (agg_family / agg_G / agg_W describe them)
     {P_TOTAL,      "total",        P_PARTIAL},           // ... summed over the ranks (dsmgp_aggregate_exchange ran on them)
-    {P_DONE,       "done",         P_PARTIAL},           // d_agg_out: the aggregated moments
-    {P_GRAD_LISTS, "grad_lists",   P_PLAN},              // gtrans, ginv, gfrob, gdot, gardlin: the gradient pass under the current mask
-    {P_XINV,       "xinv",         P_FIT | P_PLAN},      // arenaX = L^-T of EVERY factor owner.  The leaf table's arena, not the lists': it outlives them
-    {P_LOO_LISTS,  "loo_lists",    P_PLAN},              // lrow, lleaf, d_loo: they point into arenaX
-    {P_LG_LISTS,   "lg_lists",     P_PLAN},              // arenaH and the lists of dsmgp_loo_gradients
-    {P_TG_LISTS,   "target_lists", P_PLAN},              // toff, tfwd over arenaT for tg_qpad columns
-    {P_Z,          "targets",      P_FIT | P_TG_LISTS},  // arenaT: Z = L^-1 (Y - mean)
-    {P_RTREE,      "routing_tree", 0},                   // rt_*: the model's tree (dsmgp_set_tree)
+    {P_DONE,       "done",         P_PARTIAL},           // content of TestProducts: the aggregated moments
+    {P_GRAD_LISTS, "grad_lists",   P_PLAN},              // GradLists: the gradient pass under the current mask
+    {P_XINV,       "xinv",         P_FIT | P_PLAN},      // content of GradStore: L^-T of EVERY factor owner.  The leaf table's arena, not the lists': it outlives them
+    {P_LOO_LISTS,  "loo_lists",    P_PLAN},              // GradStore: the lists of dsmgp_loo, they point into its L^-T arena
+    {P_LG_LISTS,   "lg_lists",     P_PLAN},              // GradStore: the arena and the lists of dsmgp_loo_gradients
+    {P_TG_LISTS,   "target_lists", P_PLAN},              // TargetsStore: the sweep's lists for tg_qpad columns
+    {P_Z,          "targets",      P_FIT | P_TG_LISTS},  // content of TargetsStore: Z = L^-1 (Y - mean)
+    {P_RTREE,      "routing_tree", 0},                   // RouteTreeStore: the model's tree (dsmgp_set_tree)
 };
 constexpr int N_PRODUCTS = (int)(sizeof(TABLE) / sizeof(TABLE[0]));
 

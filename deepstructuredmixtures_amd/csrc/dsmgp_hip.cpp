@@ -19,6 +19,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <array>
 #include <chrono>
 #include <dlfcn.h>
@@ -212,22 +213,14 @@ struct SweepLists {
     DevBuf<FusedTask8> f8;                         // empty where the sweep has none (the gradient pass)
     DevArena slab;                                 // split-K workspace of all lanes (grow-only)
 
-    void clear() {           // empty lists; the allocations and the slab stay for the lists that replace them
+    void drop(bool keep) {   // keep: empty lists; the allocations and the slab stay for the lists that replace them
         nsteps = 0;
-        upd.clear();
-        trsm.clear();
-        red.clear();
-        f8.clear();
+        upd.drop(keep);
+        trsm.drop(keep);
+        red.drop(keep);
+        f8.drop(keep);
+        if (!keep) slab.put();
     }
-    void release() {
-        nsteps = 0;
-        upd.release();
-        trsm.release();
-        red.release();
-        f8.release();
-        slab.put();
-    }
-    void drop(bool keep) { keep ? clear() : release(); }
 };
 
 // Collects the update tiles of one block step and splits their K range over several workgroups when
@@ -485,12 +478,253 @@ struct DotRanges {
     size_t count() const { return first[4]; }
 };
 
-struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).  HOW a product was made is a plain member:
+// The context's storage, one struct per LIFETIME: each is a base of dsmgp_ctx, and what it declares falls together, in one place.
+// A group that is only ever released falls by assignment from a default-constructed value (reset<G>): the owners release or put
+// on move-assignment and the default member initialisers are the resets, so a member added to such a group needs no further line.
+// A group that is sometimes emptied and kept has one drop(bool keep) under its declarations.
+
+// PlanStore.  Built by build_plan (arenas, leaf table, build_schedule's lists) and ensure_phase (phase, slabF); stands behind
+// P_PLAN and P_PHASE; falls in free_plan: new training data, leaf table, sharing schedule, plan option, pool or dsmgp_release.
+struct PlanStore {
+    // the large arenas: each owns its doubles or knows that they are a piece of the pool (dev_owner.hpp)
+    DevArena arenaF, arenaDinv;
+    DevArena arenaVec;              // per leaf: yc, w, z, alpha (4 x npad)
+    DevArena arenaXg;
+    DevBuf<int> d_info;
+    DevBuf<int> d_owner;            // per leaf: the leaf whose factor (and info slot) it uses (dsmgp_fit_exchange packs info per owner)
+    DevBuf<double> d_mll;
+    DevBuf<LeafDev> d_leaves;
+    DevBuf<GramTask> gram;          // Gram launch of fit!: every lower tile, or (fused) the tiles no update task writes
+    std::vector<char> fused_step[2];    // per phase and block step: STEP_* (build_schedule; see dsmgp_ctx::fuse_steps)
+    std::vector<char> leaf_lane;    // per leaf (COPY / PREFIX leaves: their source's)
+    StepLists phase[MAX_LANES][2];  // [lane][0: FULL leaves, 1: PREFIX leaves (need their source first)]
+    std::vector<char> leaf_group;   // per leaf: the phase it belongs to (COPY leaves ride with their source)
+    DevArena slabF[MAX_LANES];      // split-K workspace of the factorisation, per lane
+    std::vector<int> fwd_off, bwd_off;
+    DevBuf<SolveTask> fwd, bwd;
+    int solve_steps = 0;
+    DevBuf<DiagTask> dinvc_prefix;  // copied blocks of PREFIX leaves whose source factorised them in a fused step: completed right
+                                    // after the copy (the classic steps of the PREFIX phase solve against Dinv_k)
+    DevBuf<DiagTask> dinvc_fwd;     // blocks of the leaves whose z comes from the forward sweep (COPY, PREFIX): completed before it
+    DevBuf<DiagTask> dinvc_all;     // every diagonal block a fused step factorises WITHOUT its inverse (only L_kk and the 16x16 diagonal
+                                    // inverses exist after a fit): dinv_complete_kernel over this list produces the rest of Dinv_k for
+                                    // whoever needs it (ensure_dinv).  Owned by the PLAN -- the list is the same with and without test
+                                    // rows riding along, and must outlive a test set that is replaced between a fit and its first use
+};
+static_assert(std::is_nothrow_move_assignable_v<PlanStore>, "PlanStore falls by assignment (reset)");
+
+// TestInputs.  The registered test set as the caller gave it: the rows, the route CSR, the row / entry index.  Built by the
+// registration (dsmgp_set_test*); stands behind P_TEST; falls in free_test, NOT in free_test_products: dsmgp_add_rows_keep_test
+// keeps it across a rebuilt plan.  Its counts (n_t, route_ptr, route_total, vt_first) are plain members of the context.
+struct TestInputs {
+    DevBuf<double> dXt;
+    DevBuf<int64_t> d_route_ptr, d_route_idx;
+    // aggregation of the leaf moments per test row + scores (dsmgp_aggregate*, dsmgp_scores)
+    DevBuf<int64_t> d_row_ptr;      // n_t + 1: entries of every test row (built by set_test)
+    DevBuf<int32_t> d_row_ent;      // entry positions, ascending per row
+    DevBuf<int32_t> d_ent_leaf;     // leaf of every entry position
+
+    void drop(bool keep) {          // keep: a registration that replaces another
+        dXt.drop(keep);
+        d_route_ptr.drop(keep);
+        d_route_idx.drop(keep);
+        d_row_ptr.drop(keep);
+        d_row_ent.drop(keep);
+        d_ent_leaf.drop(keep);
+    }
+};
+
+// TestProducts.  What is made from a registered test set: built by register_test, ensure_joint and, on first use and not part of
+// bytes_needed, by the prediction entry points (predict_cov, predict_gradients, predict_targets, aggregate); stands behind P_TEST,
+// P_JOINT and what is below them; falls in free_test_products: the set is dropped or replaced, or the plan under it goes.
+struct TestProducts {
+    DevBuf<double> d_agg_part;      // W x n_t partial sums
+    DevBuf<double> d_agg_coef;      // L
+    DevBuf<int32_t> d_agg_group;    // L
+    DevBuf<double> d_agg_out;       // mu | var (n_t each) | y_test (n_t) | score block sums
+    DevArena arenaVt;               // K_tn: a test set that replaces another takes the arenas of the old one over while it fits
+                                    // (DevArena::fit; releasing ~10 GB and asking the driver for them again took up to 0.6 s of a
+                                    // 0.06 s predict)
+    DevArena arenaXt;
+    DevArena arenaPV;               // mu | var (route order, unpadded) | macc | sacc (padded accumulators of the sweep)
+    DevBuf<GramTask> pgram;         // K_tn tiles the standalone sweep reads from memory (all of them only when D > 32)
+    DevBuf<GramTask> pgram0;        // ... of the joint fit when the Gram is fused: block column 0 only
+    DevBuf<PredTask> ptasks;
+    DevBuf<PredTask> ptasks_slow;   // test tiles of leaves whose z is not produced during the factorisation
+    SweepLists psweep;              // V^T = K_tn L^-T; in the block steps that run fused: update + solve of eight 16-row blocks per task
+    DevBuf<SweepSeg> psegs;         // (leaf, block step) pairs of the sweep's fused steps: build_sweep8_kernel makes the tasks
+    // dsmgp_add_rows_keep_test (see dsmgp_ctx::vt_first)
+    DevBuf<KeptSumTask> kept_tasks; // the moment sums of the kept columns (kept_sums_kernel), their partial sums and finish tasks
+    DevBuf<KeptFinTask> kept_fin;
+    DevBuf<double> d_kept_part;
+    bool resume_armed = false;
+    bool sweep_resumed = false;     // psweep / pgram skip block steps (built from vt_first): rebuilt from block 0 when next needed
+    DevArena arenaCov;              // ntpad x ntpad of the leaf dsmgp_predict_cov was last asked for (grow-only, from the pool when there is one)
+    DevBuf<PredCovTask> pcov;       // its lower tiles, rebuilt per call
+    // input gradients of the predictive moments (dsmgp_predict_gradients): lists rebuilt per call
+    DevArena arenaB;                // B = Vt L^-1 (rows K_y^-1 k_t), ntpad x npad per leaf with routed rows, laid out like arenaVt (grow-only,
+                                    //   from the pool when there is one)
+    DevBuf<PredBetaTask> pgbeta;    // the tiles of B
+    DevBuf<PredGradTask> pgtasks;   // (test tile, slab of training rows) pairs
+    DevBuf<PredGradFinTask> pgfin;  // test tiles
+    DevBuf<double> d_pgpart;        // the slabs' sums
+    DevBuf<double> d_pgout;         // dmu | dvar (absent in a mean-only call), route_total x D each (ld = route_total)
+    // dsmgp_predict_targets.  They depend on the resident columns as well: free_targets releases these two by name
+    DevBuf<TargetsMuTask> tmu;      // test tiles, rebuilt per call
+    DevBuf<double> d_tmu;           // mu, route_total x Q (ld = route_total)
+    StepLists phaseJ[MAX_LANES][2]; // PlanStore::phase with the resident test rows riding along (ensure_joint)
+    DevArena slabJ[MAX_LANES];
+
+    // keep: every buffer stays allocated for what replaces it (emptied, not freed).  Two asymmetries, on purpose: the three big
+    // arenas (Vt, Xt, PV) stay under `keep` as they are -- DevArena::fit takes them over or replaces them -- and arenaCov, arenaB
+    // and slabJ are put back either way.
+    void drop(bool keep) {
+        d_agg_part.drop(keep);
+        d_agg_coef.drop(keep);
+        d_agg_group.drop(keep);
+        d_agg_out.drop(keep);
+        if (!keep) {
+            arenaVt.put();
+            arenaXt.put();
+            arenaPV.put();
+        }
+        pgram.drop(keep);
+        pgram0.drop(keep);
+        ptasks.drop(keep);
+        ptasks_slow.drop(keep);
+        psweep.drop(keep);
+        psegs.drop(keep);
+        kept_tasks.drop(keep);
+        kept_fin.drop(keep);
+        d_kept_part.drop(keep);
+        resume_armed = sweep_resumed = false;
+        arenaCov.put();
+        pcov.drop(keep);
+        arenaB.put();
+        pgbeta.drop(keep);
+        pgtasks.drop(keep);
+        pgfin.drop(keep);
+        d_pgpart.drop(keep);
+        d_pgout.drop(keep);
+        tmu.drop(keep);
+        d_tmu.drop(keep);
+        for (auto& lane : phaseJ)
+            for (auto& ph : lane) ph.drop(keep);
+        for (auto& sl : slabJ) sl.put();
+    }
+};
+
+// GradLists.  The task lists of the gradient pass under the current mask, and what describes them.  Built by build_grad_plan;
+// stand behind P_GRAD_LISTS; emptied in free_grad_lists (the mask changes: finetune! changes it L times per iteration,
+// src/finetuning.jl:34-57, and the lists that replace these fit into the same buffers), released in free_grad.
+struct GradLists {
+    DevBuf<TransTask> gtrans;
+    SweepLists ginv;                // Xt = L^-T (no fused tasks)
+    DevBuf<FrobTask> gfrob;
+    std::vector<int> gfrob_leaf;    // owner leaf of each frob task
+    DevBuf<GradTask> gdot;
+    DotRanges gdot_ranges;          // its four kernel ranges and the leaf of each task
+    DevBuf<ArdLinTask> gardlin;     // ArdLinear leaves: column groups of L^-T (ardlin_quad_kernel)
+    std::vector<int> gardlin_leaf;  // leaf of each of them
+    int gstride = 2;                // doubles per contraction task in d_gpart
+    size_t gpart_count = 0;         // doubles of d_gpart (GradStore) these lists write
+
+    void drop(bool keep) {          // keep: the allocations and the sweep's slab stay
+        gtrans.drop(keep);
+        ginv.drop(keep);
+        gfrob.drop(keep);
+        gfrob_leaf.clear();
+        gdot.drop(keep);
+        gdot_ranges = DotRanges{};
+        gardlin.drop(keep);
+        gardlin_leaf.clear();
+        gstride = 2;
+        gpart_count = 0;
+    }
+};
+
+// GradStore.  What the gradient pass, dsmgp_loo and dsmgp_loo_gradients keep beside GradLists: built on first use (build_grad_plan,
+// build_loo_plan, the lists of dsmgp_loo_gradients), not part of bytes_needed; stands behind P_XINV, P_LOO_LISTS and P_LG_LISTS;
+// falls in free_grad: with the plan, with a change of kernel kind or of the ARD gradient option, and with whatever moves the pool's
+// stack below it.
+struct GradStore {
+    DevArena arenaX;                // Xt = L^-T per factor owner, npad x npad (kept only while the total is exactly the same)
+    DevBuf<double> d_gpart;         // partial results: frob | graddot pairs | per-leaf dots | ArdLinear quadratic forms (2 D per task)
+    // leave-one-out (dsmgp_loo): reads the same L^-T arena
+    DevBuf<RowNormTask> lrow;
+    DevBuf<LooTask> lleaf;
+    DevBuf<double> d_loo;           // row-sum planes of every owner | mu | var (obs_ptr[L] each) | lpd (L)
+    // gradients of the LOO density (dsmgp_loo_gradients)
+    DevArena arenaH;                // H = K_y^-1 diag(sqrt w) per computing leaf, npad x npad
+    DevBuf<double> d_lgvec;         // [alpha | u | sqrt w | alpha / (d sqrt w)] per computing leaf, npad each
+    DevBuf<LooVecTask> lgvec;
+    DevBuf<GinvTask> lginv;
+    DevBuf<LooHvecTask> lghvec;
+    std::vector<int> lghvec_leaf;
+    DevBuf<GradTask> lgdot;         // as gdot: IsoSE / ArdSE | ArdSEProduct | Matern | rational quadratic
+    DotRanges lgdot_ranges;
+    int lgstride = 2;               // doubles per contraction task in d_lgpart: 2 + D, one more with a rational quadratic id
+    DevBuf<ArdLinTask> lgardlin;
+    std::vector<int> lgardlin_leaf;
+    DevBuf<double> d_lgpart;        // weights 2 L | hvec pairs | graddot x (2 + D) | ArdLinear 3 D per task
+};
+static_assert(std::is_nothrow_move_assignable_v<GradStore>, "GradStore falls by assignment (reset)");
+
+// TargetsStore.  Several target columns on the current factors (dsmgp_solve_targets and what reads its Z, kernels_targets.hpp):
+// built on first use, not part of bytes_needed, the arenas from the pool when there is one; stands behind P_TG_LISTS and P_Z;
+// falls in free_targets: with the plan, and with whatever moves the pool's stack below it.
+struct TargetsStore {
+    DevArena arenaT;                // per leaf Yc | Z, npad x Qpad each (grow-only)
+    int tg_Q = 0;                   // columns of the resident Z
+    int tg_qpad = 0;                // P_TG_LISTS: the Qpad they were built for
+    std::vector<size_t> toff;       // per leaf: offset of its Yc in arenaT
+    DevBuf<long long> d_toff;
+    DevBuf<double> d_tY, d_tmean, d_tmll;       // Y (N x Q), mean and mll (L x Q)
+    DevBuf<TargetsFwdTask> tfwd;    // the sweep's tasks, lane after lane: lane q's launch s is entry q * tfwd_steps + s of tfwd_off
+    std::vector<int> tfwd_off;      //   (launch 0: Z_0 of every leaf; launch s: block column s - 1)
+    int tfwd_steps = 0, tfwd_lanes = 1;
+    // dsmgp_mll_columns_gradients: A = L^-T Z per leaf, npad x Qpad at offset toff / 2 of an arena of its own; its task lists are
+    // rebuilt per call
+    DevArena arenaA;
+    DevBuf<TargetsATask> tga;
+    DevBuf<GradTaskTg> tgdot;
+    DevBuf<FrobTask> tgfrob;
+    DevBuf<ArdLinTask> tgquad;
+    DevBuf<TargetsArdLinTask> tgardlin;
+    DevBuf<double> d_tgw, d_tgpart; // the weights (L x Q); frob | contraction x gstride | 2 L | ArdLinear 2 D per column group | D per leaf
+    // dsmgp_loo_columns / dsmgp_loo_columns_gradients: H = K_y^-1 diag(sqrt W), npad^2 per leaf, and U = K_y^-1 (A / d), npad x Qpad
+    // at offset toff / 2, in arenas of their own (the rule of arenaA); the lists are rebuilt per call
+    DevArena arenaHc, arenaU;
+    DevBuf<LooColsTask> lcleaf;
+    DevBuf<GinvTask> lcginv;
+    DevBuf<LooColsUTask> lcu;
+    DevBuf<LooColsRowTask> lcrow;
+    DevBuf<GradTaskLc> lcdot;
+    DevBuf<ArdLinTask> lcquad;
+    DevBuf<LooColsArdLinTask> lcardlin;
+    DevBuf<double> d_lcw, d_lcvec, d_lcpart, d_lcout;   // weights (L x Q); [d | sqrt W | 1 / (d sqrt W)] per leaf; partial sums; mu | var | lpd
+};
+static_assert(std::is_nothrow_move_assignable_v<TargetsStore>, "TargetsStore falls by assignment (reset)");
+
+// RouteTreeStore.  The model's tree as flat arrays in HBM: the routing of predict runs on the device (dsmgp_set_test_routed).
+// Built by dsmgp_set_tree; stands behind P_RTREE; falls in free_tree: a new tree, new training data or a new leaf table.
+struct RouteTreeStore {
+    RouteTree rtree{};              // the kernel's by-value view of the arrays below
+    DevBuf<int8_t> rt_kind;
+    DevBuf<int32_t> rt_first, rt_nchild, rt_sdim, rt_leaf;
+    DevBuf<double> rt_thr;
+    int64_t rtree_nodes = 0;
+    int rtree_max_leaf = -1;        // largest local leaf index a region names (checked against the leaf table at routing time)
+};
+static_assert(std::is_nothrow_move_assignable_v<RouteTreeStore>, "RouteTreeStore falls by assignment (reset)");
+
+// What lives as long as the context, and the plain numbers that describe a group without falling with it
+struct dsmgp_ctx : Validity, PlanStore, TestInputs, TestProducts, GradLists, GradStore, TargetsStore, RouteTreeStore {
+    // `valid`: what is current (ctx_state.hpp).  HOW a product was made is a plain member:
     bool vt_from_fit = false;       // P_VT: the rows rode through the fit (else: the standalone sweep of predict_run made it)
     bool last_fit_joint = false;    // P_FIT: it carried the resident test rows
     bool grad_lists_all = false;    // P_GRAD_LISTS: they invert every factor owner (build_grad_plan)
     bool grad_all_owners = false;   // P_GRAD_LISTS while build_grad_plan runs: every owner whatever the mask says (xinv_lists)
-    int tg_qpad = 0;                // P_TG_LISTS: the Qpad they were built for
     bool use_graph = false;         // P_FIT is replayed from a captured graph: opt-in (DSMGP_OPT_FIT_GRAPH), config 2 2.50 -> 2.47 ms, nothing
                                     // elsewhere; capture does not mix with several contexts driven from concurrent host threads (MultiContext)
     int device = 0;
@@ -512,23 +746,14 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     DevBuf<KParam> d_kp;
     DevBuf<double> d_l2;
 
-    // the large arenas: each owns its doubles or knows that they are a piece of the pool (dev_owner.hpp)
-    DevArena arenaF, arenaDinv;
-    DevArena arenaVec;              // per leaf: yc, w, z, alpha (4 x npad)
-    DevArena arenaXg;
-    DevBuf<int> d_info;
-    DevBuf<int> d_owner;            // per leaf: the leaf whose factor (and info slot) it uses (dsmgp_fit_exchange packs info per owner)
-    DevBuf<double> d_mll;
-    DevBuf<LeafDev> d_leaves;
-    std::vector<LeafDev> h_leaves;
+    std::vector<LeafDev> h_leaves;  // the host's copy of PlanStore::d_leaves
     size_t bytes_needed = 0;
 
-    DevBuf<GramTask> gram;          // Gram launch of fit!: every lower tile, or (fused) the tiles no update task writes
     int fuse_gram = 1;              // update tasks of fit! evaluate the Gram values of their tile themselves (TileTask.gram)
     int fuse_steps = 1;             // block steps with more diagonal blocks than CUs run as two fused launches (kernels_fused.hpp)
     int diag_in_update = 1;         // classic steps: the diagonal tile's update runs one step ahead and its factorisation rides in
                                     // the update launch (DiagFinishTask, kernels_fused.hpp)
-    // per phase and block step (decided by build_plan):
+    // per phase and block step (PlanStore::fused_step, decided by build_plan):
     //   STEP_CLASSIC    update (all tiles, split-K) / reduce / diagonal block / panel solve launches, one after the other
     //   STEP_FUSED      many leaves: diag_fused_reg_kernel, then tile_fused8_kernel, from the kernel function (kernels_fused.hpp)
     // (A third, lookahead schedule -- the update of step k cut at its last block column, the bulk on this stream, the rank-128
@@ -542,7 +767,6 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     // 0.3947 -> 0.4096 s, 8-rank shard 0.0562 -> 0.0645, config 2 2.51 -> 4.40 ms (profiles/r04_one_launch_ab.log): the last
     // piece to arrive sums up to 46 slabs alone where the reduce launch spreads a tile over 8 workgroups, and the row-split
     // main loop the in-register solve needs runs 5-10 % behind the 2 x 2 one at K >= 2000.  Removed again.)
-    std::vector<char> fused_step[2];
     // Leaf lanes (round 5, DSMGP_OPT_LANES): the leaves of a table are dealt to one or two LANES (longest-processing-time on n^3,
     // sharing groups together); every lane has step lists and a split-K workspace of its own and runs them on a stream of its
     // own, joined at the end of fit!.  One lane's latency-bound launches (diagonal blocks, panel solves, split-K reduces) then
@@ -552,16 +776,10 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     int nlanes = 1;                 // lanes of the current plan
     hipStream_t lane_stream[MAX_LANES] = {};           // [0] = stream
     hipEvent_t ev_fork = nullptr, ev_join[MAX_LANES] = {};
-    std::vector<char> leaf_lane;    // per leaf (COPY / PREFIX leaves: their source's)
-    StepLists phase[MAX_LANES][2];  // [lane][0: FULL leaves, 1: PREFIX leaves (need their source first)]
-    std::vector<char> leaf_group;   // per leaf: the phase it belongs to (COPY leaves ride with their source)
     // Optional device pool (dsmgp_reserve): the large arenas are carved out of one allocation made once, in stack
     // order plan < test < gradients, instead of hipMalloc/hipFree per leaf table -- the driver clears memory on
     // allocation (5 s per 230 GB group measured), which dominated the streaming mode's wall time.
     DevPool pool;
-    DevArena slabF[MAX_LANES];      // split-K workspace of the factorisation, per lane
-    StepLists phaseJ[MAX_LANES][2]; // the same with the resident test rows riding along (built by set_test)
-    DevArena slabJ[MAX_LANES];
     double alg_flops_joint = 0.0;
     bool joint = true;              // fit advances the resident test rows too
     int ncu = 256;
@@ -569,9 +787,6 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     int tail_split = DSMGP_TAIL_SPLIT_DEFAULT, tail_rounds = DSMGP_TAIL_ROUNDS_DEFAULT;          // plans with one lane
     int tail_split_lanes = DSMGP_TAIL_SPLIT_LANES, tail_rounds_lanes = DSMGP_TAIL_ROUNDS_LANES;  // plans with two or more
     int ragged_rounds = 2, ragged_div = 4;   // UpdateSplitter::add_step_ragged (launches of the gradient pass)
-    std::vector<int> fwd_off, bwd_off;
-    DevBuf<SolveTask> fwd, bwd;
-    int solve_steps = 0;
     // The launch sequence of fit! as a captured hipGraph (one per variant: fit alone / with the resident test rows), replayed
     // while per-launch timing is off (dsmgp_set_profile 0): every kernel argument is a pointer into the plan's task lists or
     // arenas, which live as long as the plan, and the hyper-parameters go through d_kp's CONTENTS -- so a graph stays valid
@@ -579,138 +794,30 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     // launch cost between dependent kernels of a latency-bound chain (config 2: 32 steps x 3 launches).
     hipGraphExec_t fit_graph[2] = {nullptr, nullptr};
     int graph_launches[2][2] = {{0, 0}, {0, 0}};
-    DevBuf<DiagTask> dinvc_prefix;  // copied blocks of PREFIX leaves whose source factorised them in a fused step: completed right
-                                    // after the copy (the classic steps of the PREFIX phase solve against Dinv_k)
-    DevBuf<DiagTask> dinvc_fwd;     // blocks of the leaves whose z comes from the forward sweep (COPY, PREFIX): completed before it
-    DevBuf<DiagTask> dinvc_all;     // every diagonal block a fused step factorises WITHOUT its inverse (only L_kk and the 16x16 diagonal
-                                    // inverses exist after a fit): dinv_complete_kernel over this list produces the rest of Dinv_k for
-                                    // whoever needs it (ensure_dinv).  Owned by the PLAN -- the list is the same with and without test
-                                    // rows riding along, and must outlive a test set that is replaced between a fit and its first use
 
-    // prediction
-    DevBuf<double> dXt;
+    // prediction: the counts of the registered test set (TestInputs, TestProducts).  They stay when free_test_products(c, true)
+    // empties what was made from the set: dsmgp_add_rows_keep_test registers the same set again on the grown plan
     int64_t n_t = 0;
-    DevBuf<int64_t> d_route_ptr, d_route_idx;
     std::vector<int64_t> route_ptr;
-    DevArena arenaVt;               // K_tn: a test set that replaces another takes the arenas of the old one over while it fits
-                                    // (DevArena::fit; releasing ~10 GB and asking the driver for them again took up to 0.6 s of a
-                                    // 0.06 s predict)
+    int64_t route_total = 0;
+    size_t acc_off = 0, acc_count = 0;      // the accumulators' part of arenaPV (register_test)
+    int agg_family = -1, agg_G = 0, agg_W = 0;      // P_PARTIAL: what d_agg_part holds (dsmgp_aggregate_partial)
     // pinned host staging for the uploads of a registration (stage_upload): the lists of a test set are ~10 MB at the headline
     // model; through hipMemcpy from pageable vectors they took 9 ms of a 25 ms registration and left the runtime busy behind them
     char* stage = nullptr;
     size_t stage_cap = 0, stage_top = 0;
-    DevBuf<SweepSeg> psegs;         // (leaf, block step) pairs of the sweep's fused steps: build_sweep8_kernel makes the tasks
-    DevArena arenaXt;
-    DevArena arenaPV;               // mu | var (route order, unpadded) | macc | sacc (padded accumulators of the sweep)
-    size_t acc_off = 0, acc_count = 0;
-    DevBuf<PredTask> ptasks_slow;   // test tiles of leaves whose z is not produced during the factorisation
-    DevBuf<GramTask> pgram;         // K_tn tiles the standalone sweep reads from memory (all of them only when D > 32)
-    DevBuf<GramTask> pgram0;        // ... of the joint fit when the Gram is fused: block column 0 only
-    DevBuf<PredTask> ptasks;
-    SweepLists psweep;              // V^T = K_tn L^-T; in the block steps that run fused: update + solve of eight 16-row blocks per task
-    DevArena arenaCov;              // ntpad x ntpad of the leaf dsmgp_predict_cov was last asked for (grow-only, allocated on first use,
-                                    //   from the pool when there is one; goes with the test set: free_test).  Not part of bytes_needed.
-    DevBuf<PredCovTask> pcov;       // its lower tiles, rebuilt per call
-    // input gradients of the predictive moments (dsmgp_predict_gradients): lists rebuilt per call, buffers allocated on first use
-    DevArena arenaB;                // B = Vt L^-1 (rows K_y^-1 k_t), ntpad x npad per leaf with routed rows, laid out like arenaVt (grow-only,
-                                    //   from the pool when there is one; goes with the test set: free_test).  Not part of bytes_needed.
-    DevBuf<PredBetaTask> pgbeta;    // the tiles of B
-    DevBuf<PredGradTask> pgtasks;   // (test tile, slab of training rows) pairs
-    DevBuf<PredGradFinTask> pgfin;  // test tiles
-    DevBuf<double> d_pgpart;        // the slabs' sums
-    DevBuf<double> d_pgout;         // dmu | dvar (absent in a mean-only call), route_total x D each (ld = route_total)
-    int64_t route_total = 0;
 
-    // several target columns on the current factors (dsmgp_solve_targets / dsmgp_predict_targets, kernels_targets.hpp): allocated on
-    // first use, not part of bytes_needed, dropped with the plan (free_targets); what depends on the test set goes with it (free_test)
-    DevArena arenaT;                // per leaf Yc | Z, npad x Qpad each (grow-only, from the pool when there is one)
-    int tg_Q = 0;                   // columns of the resident Z
-    std::vector<size_t> toff;       // per leaf: offset of its Yc in arenaT
-    DevBuf<long long> d_toff;
-    DevBuf<double> d_tY, d_tmean, d_tmll;       // Y (N x Q), mean and mll (L x Q)
-    DevBuf<TargetsFwdTask> tfwd;    // the sweep's tasks, lane after lane: lane q's launch s is entry q * tfwd_steps + s of tfwd_off
-    std::vector<int> tfwd_off;      //   (launch 0: Z_0 of every leaf; launch s: block column s - 1)
-    int tfwd_steps = 0, tfwd_lanes = 1;
-    DevBuf<TargetsMuTask> tmu;      // test tiles, rebuilt per call
-    DevBuf<double> d_tmu;           // mu, route_total x Q (ld = route_total)
-    // dsmgp_mll_columns_gradients: A = L^-T Z per leaf, npad x Qpad at offset toff / 2 of an arena of its own (allocated on first use, from
-    // the pool when there is one, not part of bytes_needed, dropped where arenaT is); its task lists are rebuilt per call
-    DevArena arenaA;
-    DevBuf<TargetsATask> tga;
-    DevBuf<GradTaskTg> tgdot;
-    DevBuf<FrobTask> tgfrob;
-    DevBuf<ArdLinTask> tgquad;
-    DevBuf<TargetsArdLinTask> tgardlin;
-    DevBuf<double> d_tgw, d_tgpart; // the weights (L x Q); frob | contraction x gstride | 2 L | ArdLinear 2 D per column group | D per leaf
-    // dsmgp_loo_columns / dsmgp_loo_columns_gradients: H = K_y^-1 diag(sqrt W), npad^2 per leaf, and U = K_y^-1 (A / d), npad x Qpad
-    // at offset toff / 2, in arenas of their own (the rule of arenaA); the lists are rebuilt per call
-    DevArena arenaHc, arenaU;
-    DevBuf<LooColsTask> lcleaf;
-    DevBuf<GinvTask> lcginv;
-    DevBuf<LooColsUTask> lcu;
-    DevBuf<LooColsRowTask> lcrow;
-    DevBuf<GradTaskLc> lcdot;
-    DevBuf<ArdLinTask> lcquad;
-    DevBuf<LooColsArdLinTask> lcardlin;
-    DevBuf<double> d_lcw, d_lcvec, d_lcpart, d_lcout;   // weights (L x Q); [d | sqrt W | 1 / (d sqrt W)] per leaf; partial sums; mu | var | lpd
-
-    // aggregation of the leaf moments per test row + scores (dsmgp_aggregate*, dsmgp_scores)
-    DevBuf<int64_t> d_row_ptr;      // n_t + 1: entries of every test row (built by set_test)
-    DevBuf<int32_t> d_row_ent;      // entry positions, ascending per row
-    DevBuf<int32_t> d_ent_leaf;     // leaf of every entry position
-    DevBuf<double> d_agg_part;      // W x n_t partial sums
-    DevBuf<double> d_agg_coef;      // L
-    DevBuf<int32_t> d_agg_group;    // L
-    DevBuf<double> d_agg_out;       // mu | var (n_t each) | y_test (n_t) | score block sums
-    int agg_family = -1, agg_G = 0, agg_W = 0;
-
-    // gradients (built on first use)
+    // gradients: the inputs, and what build_grad_plan writes for other readers than its own pass (dsmgp_loo, dsmgp_loo_gradients and
+    // the column passes read both as well: they do not fall with GradLists)
     std::vector<char> grad_active;  // dsmgp_set_gradient_leaves: leaves whose gradients are wanted (empty = all)
-    DevArena arenaX;                // Xt = L^-T per factor owner, npad x npad (kept only while the total is exactly the same)
-    DevBuf<TransTask> gtrans;
-    SweepLists ginv;                // Xt = L^-T (no fused tasks)
-    DevBuf<FrobTask> gfrob;
-    std::vector<int> gfrob_leaf;    // owner leaf of each frob task
-    DevBuf<GradTask> gdot;
-    DotRanges gdot_ranges;          // its four kernel ranges and the leaf of each task
-    DevBuf<ArdLinTask> gardlin;     // ArdLinear leaves: column groups of L^-T (ardlin_quad_kernel)
-    std::vector<int> gardlin_leaf;  // leaf of each of them
     bool ard_true_gradient = false; // DSMGP_OPT_ARD_LENGTHSCALE_GRADIENT
-    int gstride = 2;                // doubles per contraction task in d_gpart
     std::vector<int> grad_src;      // per leaf: the leaf whose contraction it shares (COPY leaf with the same mean), or -1
-    DevBuf<double> d_gpart;         // partial results: frob | graddot pairs | per-leaf dots | ArdLinear quadratic forms (2 D per task)
-    size_t gpart_count = 0;
-    // leave-one-out (dsmgp_loo): reads the same L^-T arena
     std::vector<size_t> gxoff;      // per owner leaf: its offset in arenaX (build_grad_plan)
-    DevBuf<RowNormTask> lrow;
-    DevBuf<LooTask> lleaf;
-    DevBuf<double> d_loo;           // row-sum planes of every owner | mu | var (obs_ptr[L] each) | lpd (L).  Allocated on first use,
-                                    // dropped with the leaf table (free_grad); not part of bytes_needed
-    // gradients of the LOO density (dsmgp_loo_gradients): lists and arena built on first use, dropped with the leaf table (free_grad)
-    DevArena arenaH;                // H = K_y^-1 diag(sqrt w) per computing leaf, npad x npad
-    DevBuf<double> d_lgvec;         // [alpha | u | sqrt w | alpha / (d sqrt w)] per computing leaf, npad each
-    DevBuf<LooVecTask> lgvec;
-    DevBuf<GinvTask> lginv;
-    DevBuf<LooHvecTask> lghvec;
-    std::vector<int> lghvec_leaf;
-    DevBuf<GradTask> lgdot;         // as gdot: IsoSE / ArdSE | ArdSEProduct | Matern | rational quadratic
-    DotRanges lgdot_ranges;
-    int lgstride = 2;               // doubles per contraction task in d_lgpart: 2 + D, one more with a rational quadratic id
-    DevBuf<ArdLinTask> lgardlin;
-    std::vector<int> lgardlin_leaf;
-    DevBuf<double> d_lgpart;        // weights 2 L | hvec pairs | graddot x (2 + D) | ArdLinear 3 D per task
 
     // multi-GPU exchange over RCCL (dsmgp_comm_*, dsmgp_allgather): librccl.so is loaded on first use
     void* comm = nullptr;           // ncclComm_t
     int comm_rank = 0, comm_world = 1;
     DevBuf<double> d_xchg;          // send | recv staging
-    // the model's tree as flat arrays in HBM (dsmgp_set_tree): the routing of predict runs on the device (dsmgp_set_test_routed)
-    RouteTree rtree{};              // the kernel's by-value view of the arrays below
-    DevBuf<int8_t> rt_kind;
-    DevBuf<int32_t> rt_first, rt_nchild, rt_sdim, rt_leaf;
-    DevBuf<double> rt_thr;
-    int64_t rtree_nodes = 0;
-    int rtree_max_leaf = -1;        // largest local leaf index a region names (checked against the leaf table at routing time)
     // routing workspace, kept across registrations: row counts | leaf counts | outside flag, bitmap, word prefixes
     DevBuf<int32_t> rws_counts;
     DevBuf<uint32_t> rws_bits;
@@ -724,14 +831,9 @@ struct dsmgp_ctx : Validity {       // `valid`: what is current (ctx_state.hpp).
     bool have_append_stats = false;
     // dsmgp_add_rows_keep_test: plain per-leaf data beside the validity table.  vt_first[l] leading block columns of leaf l's part of
     // arenaVt hold K_tn L^-T of the CURRENT fit although P_VT is not current: it means something only while P_TEST is current,
-    // P_VT is not and resume_armed says that the fit is still the one the call made (dsmgp_fit and the predict_run that uses it
-    // clear it; so does whatever drops or replaces the test set: free_test)
+    // P_VT is not and TestProducts::resume_armed says that the fit is still the one the call made (dsmgp_fit and the predict_run
+    // that uses it clear it; so does whatever drops or replaces the test set)
     std::vector<int> vt_first;
-    bool resume_armed = false;
-    bool sweep_resumed = false;     // psweep / pgram skip block steps (built from vt_first): rebuilt from block 0 when next needed
-    DevBuf<KeptSumTask> kept_tasks; // the moment sums of the kept columns (kept_sums_kernel), their partial sums and finish tasks
-    DevBuf<KeptFinTask> kept_fin;
-    DevBuf<double> d_kept_part;
     int64_t resume_stats[DSMGP_N_RESUME_STATS] = {0, 0, 0, -1, 0, 0};
     bool have_resume_stats = false;
     double alg_flops_fused = 0.0, alg_flops_fused_joint = 0.0;   // ... of the fused tile launches (update + solve), fit alone / joint
@@ -908,87 +1010,36 @@ void drop_graphs(dsmgp_ctx* c) {
         }
 }
 
-// the task lists of the gradient pass (they depend on the set of active leaves): emptied, their allocations and the L^-T arena
-// stay -- finetune! changes the mask L times per iteration (src/finetuning.jl:34-57), and the lists that replace these fit into
-// the same buffers (dev_upload) instead of a hipFree + hipMalloc per list and pass
+// The named transitions: each lets its lifetime groups fall (reset<G>, or the group's drop), invalidates the products that stood
+// for them and, under a reserved pool, keeps the stack order.  Under a pool put() on a carved arena only forgets it: the stack's
+// top moves by pool.reset / reset_to_mark, after everything carved above the new top has been forgotten.
+template <class G>
+void reset(dsmgp_ctx* c) { static_cast<G&>(*c) = G{}; }
+
+// the task lists of the gradient pass (they depend on the set of active leaves): emptied, their allocations and the L^-T arena stay
 void free_grad_lists(dsmgp_ctx* c) {
-    c->gtrans.clear();
-    c->ginv.clear();
-    c->gfrob.clear();
-    c->gdot.clear();
-    c->gardlin.clear();
+    c->GradLists::drop(true);
     c->invalidate(P_GRAD_LISTS);
 }
 
 void free_grad(dsmgp_ctx* c) {
-    c->ginv.release();
-    c->arenaX.put();
-    c->gtrans.release();
-    c->gfrob.release();
-    c->gdot.release();
-    c->gardlin.release();
-    c->d_gpart.release();
-    c->lrow.release();
-    c->lleaf.release();
-    c->d_loo.release();
+    c->GradLists::drop(false);
+    reset<GradStore>(c);
     c->invalidate(P_GRAD_LISTS | P_XINV | P_LOO_LISTS | P_LG_LISTS);
-    c->arenaH.put();
-    c->d_lgvec.release();
-    c->lgvec.release();
-    c->lginv.release();
-    c->lghvec.release();
-    c->lgdot.release();
-    c->lgardlin.release();
-    c->d_lgpart.release();
 }
 
 // the resident target columns (dsmgp_solve_targets): they go with the plan -- a new leaf table, new training data, dsmgp_release --
 // and, under a reserved pool, with whatever resets the pool's stack below them
 void free_targets(dsmgp_ctx* c) {
-    c->arenaT.put();
+    reset<TargetsStore>(c);
     c->invalidate(P_TG_LISTS);
-    c->tg_Q = c->tg_qpad = 0;
-    c->d_toff.release();
-    c->d_tY.release();
-    c->d_tmean.release();
-    c->d_tmll.release();
-    c->tfwd.release();
-    c->tmu.release();
-    c->d_tmu.release();
-    c->arenaA.put();
-    c->tga.release();
-    c->tgdot.release();
-    c->tgfrob.release();
-    c->tgquad.release();
-    c->tgardlin.release();
-    c->d_tgw.release();
-    c->d_tgpart.release();
-    c->arenaHc.put();
-    c->arenaU.put();
-    c->lcleaf.release();
-    c->lcginv.release();
-    c->lcu.release();
-    c->lcrow.release();
-    c->lcdot.release();
-    c->lcquad.release();
-    c->lcardlin.release();
-    c->d_lcw.release();
-    c->d_lcvec.release();
-    c->d_lcpart.release();
-    c->d_lcout.release();
+    c->tmu.release();       // members of TestProducts, which drops them as well: predict_targets' lists are made from the
+    c->d_tmu.release();     // resident columns AND the test set, and go with whichever goes first
 }
 
 void free_tree(dsmgp_ctx* c) {
-    c->rtree = RouteTree{};
-    c->rt_kind.release();
-    c->rt_first.release();
-    c->rt_nchild.release();
-    c->rt_sdim.release();
-    c->rt_leaf.release();
-    c->rt_thr.release();
+    reset<RouteTreeStore>(c);
     c->invalidate(P_RTREE);
-    c->rtree_nodes = 0;
-    c->rtree_max_leaf = -1;
 }
 
 void free_test(dsmgp_ctx* c, bool keep = false);
@@ -998,23 +1049,7 @@ void free_plan(dsmgp_ctx* c) {
         free_test(c);
         c->pool.reset();
     }
-    c->arenaF.put();
-    c->arenaDinv.put();
-    c->arenaVec.put();
-    c->arenaXg.put();
-    c->d_info.release();
-    c->d_owner.release();
-    c->d_mll.release();
-    c->d_leaves.release();
-    c->gram.release();
-    for (auto& lane : c->phase)
-        for (auto& ph : lane) ph.drop(false);
-    for (auto& sl : c->slabF) sl.put();
-    c->fwd.release();
-    c->bwd.release();
-    c->dinvc_prefix.release();
-    c->dinvc_fwd.release();
-    c->dinvc_all.release();
+    reset<PlanStore>(c);
     free_grad(c);
     free_targets(c);
     c->invalidate(P_PLAN);
@@ -1032,38 +1067,7 @@ bool free_test_products(dsmgp_ctx* c, bool keep) {
         c->pool.reset_to_mark();
         keep = false;
     }
-    c->d_agg_part.drop(keep);
-    c->d_agg_coef.drop(keep);
-    c->d_agg_group.drop(keep);
-    c->d_agg_out.drop(keep);
-    if (!keep) {
-        c->arenaVt.put();
-        c->arenaXt.put();
-        c->arenaPV.put();
-    }
-    c->pgram.drop(keep);
-    c->pgram0.drop(keep);
-    c->ptasks.drop(keep);
-    c->ptasks_slow.drop(keep);
-    c->psweep.drop(keep);
-    c->psegs.drop(keep);
-    c->kept_tasks.drop(keep);
-    c->kept_fin.drop(keep);
-    c->d_kept_part.drop(keep);
-    c->resume_armed = c->sweep_resumed = false;
-    c->arenaCov.put();
-    c->pcov.drop(keep);
-    c->arenaB.put();
-    c->pgbeta.drop(keep);
-    c->pgtasks.drop(keep);
-    c->pgfin.drop(keep);
-    c->d_pgpart.drop(keep);
-    c->d_pgout.drop(keep);
-    c->tmu.drop(keep);
-    c->d_tmu.drop(keep);
-    for (auto& lane : c->phaseJ)
-        for (auto& ph : lane) ph.drop(keep);
-    for (auto& sl : c->slabJ) sl.put();
+    c->TestProducts::drop(keep);
     c->invalidate(P_TEST);
     return keep;
 }
@@ -1072,12 +1076,7 @@ bool free_test_products(dsmgp_ctx* c, bool keep) {
 // registration that replaces another.
 void free_test(dsmgp_ctx* c, bool keep) {
     keep = free_test_products(c, keep);
-    c->dXt.drop(keep);
-    c->d_route_ptr.drop(keep);
-    c->d_route_idx.drop(keep);
-    c->d_row_ptr.drop(keep);
-    c->d_row_ent.drop(keep);
-    c->d_ent_leaf.drop(keep);
+    c->TestInputs::drop(keep);
 }
 
 void free_plan_and_test(dsmgp_ctx* c) {       // new training data, leaf table, sharing schedule, plan option or pool
