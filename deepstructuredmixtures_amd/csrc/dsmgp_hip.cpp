@@ -572,6 +572,11 @@ struct TestProducts {
     // dsmgp_predict_targets.  They depend on the resident columns as well: free_targets releases these two by name
     DevBuf<TargetsMuTask> tmu;      // test tiles, rebuilt per call
     DevBuf<double> d_tmu;           // mu, route_total x Q (ld = route_total)
+    // dsmgp_predict_columns_gradients: a group of its own (nothing of dsmgp_predict_gradients is written), lists rebuilt per call
+    DevBuf<TargetsInputGradTask> tigtasks;      // (test tile, slab of training rows) pairs
+    DevBuf<TargetsInputGradFinTask> tigfin;     // test tiles
+    DevBuf<double> d_tigpart;       // the slabs' sums: D x Qpad planes of 128 rows per task
+    DevBuf<double> d_tigout;        // dmu, route_total x D x Q (ld = route_total)
     StepLists phaseJ[MAX_LANES][2]; // PlanStore::phase with the resident test rows riding along (ensure_joint)
     DevArena slabJ[MAX_LANES];
 
@@ -608,6 +613,10 @@ struct TestProducts {
         d_pgout.drop(keep);
         tmu.drop(keep);
         d_tmu.drop(keep);
+        tigtasks.drop(keep);
+        tigfin.drop(keep);
+        d_tigpart.drop(keep);
+        d_tigout.drop(keep);
         for (auto& lane : phaseJ)
             for (auto& ph : lane) ph.drop(keep);
         for (auto& sl : slabJ) sl.put();
@@ -4986,6 +4995,99 @@ static void targets_a_tasks(const dsmgp_ctx* c, std::vector<TargetsATask>& ta) {
     }
 }
 }  // namespace
+
+// Input gradients of the predictive means of the resident target columns (kernels_targets.hpp at targets_inputgrad_kernel): A as
+// dsmgp_mll_columns_gradients obtains it (L^-T by dsmgp_loo's rule, targets_a_kernel into arenaA), then one matrix product per
+// dimension with the kernel derivatives made in registers.  A COPY leaf reads its source's L^-T with its own Z.  The lists are
+// rebuilt per call; the partial sums and the output live in buffers of this entry point (TestProducts): nothing another entry point
+// reads is written, and the mask of dsmgp_set_gradient_leaves neither applies nor changes.
+int dsmgp_predict_columns_gradients(dsmgp_ctx* c, double* dmu_out, int64_t ld, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "predict_targets_gradients before solve_targets on the current fit");
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_targets_gradients before predict_run on the current fit");
+    const size_t nr = (size_t)c->route_total;
+    if (nr == 0) return 0;
+    if (!dmu_out || ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_targets_gradients: dmu_out is NULL or ld < route_total");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int L = c->L, D = c->D, Q = c->tg_Q, qpad = c->tg_qpad;
+    // L^-T of every factor owner (xinv_lists / xinv_fill); lists of the call's own are dropped again on every way out
+    OwnGradLists own_lists{c};
+    if (int rc = xinv_lists(c, own_lists)) return rc;
+    if (int rc = targets_slab(c, c->arenaA, "predict_targets_gradients: no room for A = L^-T Z")) return rc;
+    std::vector<TargetsATask> ta;
+    targets_a_tasks(c, ta);
+    // per test tile its slabs of training rows, next to each other in the list and in d_tigpart
+    const size_t planes = (size_t)D * (size_t)qpad * TB;
+    std::vector<TargetsInputGradTask> tasks;
+    std::vector<TargetsInputGradFinTask> fin;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.nt == 0) continue;
+        const int nslab = (lf.n + TIG_SLAB - 1) / TIG_SLAB;
+        fin.resize(fin.size() + (size_t)(lf.ntpad / TB));
+        tasks.resize(tasks.size() + (size_t)(lf.ntpad / TB) * (size_t)nslab);
+    }
+    if (int rc = c->d_tigpart.grow(c, tasks.size() * planes)) return rc;
+    if (int rc = c->d_tigout.grow(c, nr * (size_t)D * (size_t)Q)) return rc;
+    size_t ti = 0, fi = 0;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.nt == 0) continue;
+        const LeafDev& d = c->h_leaves[l];
+        const int nslab = (lf.n + TIG_SLAB - 1) / TIG_SLAB;
+        for (int i = 0; i < lf.ntpad / TB; ++i) {
+            TargetsInputGradFinTask& f = fin[fi++];
+            f = TargetsInputGradFinTask{};
+            f.part = c->d_tigpart.p + ti * planes;
+            f.out = c->d_tigout.p + (size_t)lf.route_off + (size_t)i * TB;
+            f.info = d.info;
+            f.pstride = (long long)planes;
+            f.ldo = (long long)nr;
+            f.nslab = nslab;
+            f.nrows = std::min(TB, lf.nt - i * TB);
+            for (int s = 0; s < nslab; ++s) {
+                TargetsInputGradTask& g = tasks[ti];
+                g = TargetsInputGradTask{};
+                g.xt = d.Xtg + (size_t)i * TB;
+                g.xg = d.Xg;
+                g.A = c->arenaA.p + c->toff[(size_t)l] / 2;
+                g.part = c->d_tigpart.p + ti * planes;
+                g.ldt = lf.ntpad;
+                g.ldg = lf.npad;
+                g.nrows = f.nrows;
+                g.c0 = s * TIG_SLAB;
+                g.c1 = std::min(lf.n, g.c0 + TIG_SLAB);
+                g.kid = lf.kid;
+                ++ti;
+            }
+        }
+    }
+    if (int rc = dev_upload(c, c->tga, ta)) return rc;
+    c->stage_top = 0;       // (the stream is idle: every entry point synchronises before it returns)
+    if (int rc = stage_upload_list(c, c->tigtasks, tasks)) return rc;
+    if (int rc = stage_upload_list(c, c->tigfin, fin)) return rc;
+    if (int rc = stage_done(c)) return rc;
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    if (int rc = ensure_dinv(c)) return rc;
+    if (int rc = xinv_fill(c)) return rc;
+    if (!ta.empty()) targets_a_kernel<<<(unsigned)ta.size(), 256, 0, c->stream>>>(c->tga.p, qpad);
+    targets_inputgrad_kernel<<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->tigtasks.p, c->d_kp.p, D, qpad);
+    if (any_rq(c)) targets_inputgrad_rq_kernel<<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->tigtasks.p, c->d_kp.p, D, qpad);
+    targets_inputgrad_finish_kernel<<<dim3((unsigned)fin.size(), (unsigned)Q), 128, 0, c->stream>>>(c->tigfin.p, D, qpad);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mark(P_XINV);
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = ms * 1e-3;
+    HIPCHK(c, hipMemcpy2D(dmu_out, (size_t)ld * sizeof(double), c->d_tigout.p, nr * sizeof(double), nr * sizeof(double),
+                          (size_t)D * (size_t)Q, hipMemcpyDeviceToHost));
+    return 0;
+}
 
 // Hyper-parameter gradients of sum_q w_lq mll_lq over the resident target columns (kernels_targets.hpp at targets_a_kernel):
 // one inversion -- or none, when the arena holds L^-T of this fit (dsmgp_loo's rule) -- and one contraction per leaf whatever Q is,

@@ -618,4 +618,201 @@ __global__ __launch_bounds__(256) void loo_columns_ardlin_kernel(const LooColsAr
     if (t == 0) out[(size_t)blockIdx.x * D + d] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Input gradients of the predictive means of the target columns (dsmgp_predict_columns_gradients): for every (leaf, routed test
+// row t), dimension d and column q
+//   dmu[t, d, q] = sum_{i < n} A[i, q] g_d(t, i),   g_d(t, i) = dk(x_t, x_i) / dx_{t,d},   A = K_y^-1 (Y - m) (targets_a_kernel),
+// the per-kind derivatives of pred_inputgrad_kernel (kernels.hpp), built from the same helpers.  For Q columns this is the matrix
+// product G_d A per dimension, on the f64 matrix cores with the operands of targets_mu_kernel: the 16-column chunk of A is the
+// first operand (lane: column l15, k = l4), g_d(test row 32 w + l15 (+ 16), training row c0 + 4 kk + l4) the second, and the
+// lane that needs an entry of G_d computes it in registers -- G_d is never stored.  Within a wave every (test row, training row)
+// pair of a K-slice belongs to exactly one lane, so for the kinds whose derivative carries the kernel value (IsoSE, ArdSEProduct,
+// Matern, RQ) the pair factor -- the exponent summed over ALL D dimensions, then exp_nonpos / rq_value -- is evaluated once and
+// serves the TIG_DC dimensions of the chunk and the TIG_CH 16-column chunks held in accumulators (TIG_DC x TIG_CH x 2 MFMAs per
+// two factors).
+// One task = a 128-row test tile of one leaf x a slab of TIG_SLAB training rows; its sums go to planes of its own (plane
+// d * qpad + q, 128 rows), which targets_inputgrad_finish_kernel adds in ascending slab order: no atomics, and column q is a sum
+// over column q of A only, in an order that depends on constants alone -- the same bits whatever Q is and whatever the other
+// columns hold, and the same for a test row wherever it stands in a tile.
+// Training rows c >= c1 (<= n) are MASKED ON LOAD: both operands are 0.0 there, whatever the padding of Xg and A holds.  Rows
+// >= nrows of the test tile compute on zeros and are not stored.
+constexpr int TIG_SLAB = 1024;      // training rows per task
+constexpr int TIG_DC = PGRAD_DC;    // dimensions per chunk
+constexpr int TIG_CH = 2;           // 16-column chunks of A per pass: TIG_DC x TIG_CH x 2 accumulators of 4 doubles per lane
+
+struct TargetsInputGradTask {
+    const double* xt;       // gathered test inputs, offset to the tile's first row (ld = ldt)
+    const double* xg;       // gathered training inputs of the leaf (ld = ldg)
+    const double* A;        // the leaf's A (npad x qpad, ld = ldg)
+    double* part;           // this task's sums: plane d * qpad + q, 128 rows each
+    int ldt, ldg;
+    int nrows;              // valid test rows of the tile
+    int c0, c1;             // training rows [c0, c1), c1 <= n
+    int kid;
+};
+
+template <int KIND>
+__device__ __forceinline__ void targets_inputgrad_body(const TargetsInputGradTask& tk, const KParam& p, int D, int qpad) {
+    constexpr int DC = TIG_DC;
+    constexpr bool PAIR = (KIND == 0 || KIND == 4 || KIND == 5 || KIND == 6);   // the derivative carries the kernel value of the pair
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int r0 = 32 * w + l15, r1 = r0 + 16;
+    const bool live0 = r0 < tk.nrows, live1 = r1 < tk.nrows;
+    const double c2 = (KIND == 5) ? matern_c2(p) : 0.0;
+    const double c1 = (c2 != 0.0) ? c2 : 1.0;
+    const int nk = (tk.c1 - tk.c0 + 3) / 4;
+    const bool one_round = D <= DC;
+    // the pair factor from the exponent's sum
+    auto factor = [&](double f) {
+        if (KIND == 0) return -(p.sigma2 * exp_nonpos(f * p.nh0)) * p.il2;
+        if (KIND == 4) return p.sigma2 * exp_nonpos(f);
+        if (KIND == 6) return -(rq_value(f, p) / (1.0 + f)) * (2.0 * rq_alpha(p));
+        const double s = sqrt(f);
+        return -(p.sigma2 * exp_nonpos(-s) * fma(c2, s, c1));
+    };
+    for (int e0 = 0; e0 < D; e0 += DC) {
+        const int en = min(DC, D - e0);
+        double xa0[DC], xa1[DC], nhd[DC];
+#pragma unroll
+        for (int d = 0; d < DC; ++d) {
+            xa0[d] = (live0 && d < en) ? tk.xt[r0 + (size_t)(e0 + d) * tk.ldt] : 0.0;
+            xa1[d] = (live1 && d < en) ? tk.xt[r1 + (size_t)(e0 + d) * tk.ldt] : 0.0;
+            nhd[d] = (kind_reads_nh(KIND) && d < en) ? p.nh[e0 + d] : 0.0;
+        }
+        for (int q0 = 0; q0 < qpad; q0 += TIG_CH * TQ) {
+            const int nch = min(TIG_CH, (qpad - q0) / TQ);
+            d4 acc[DC][TIG_CH][2];
+#pragma unroll
+            for (int d = 0; d < DC; ++d)
+#pragma unroll
+                for (int ch = 0; ch < TIG_CH; ++ch) {
+                    acc[d][ch][0] = (d4){0.0, 0.0, 0.0, 0.0};
+                    acc[d][ch][1] = (d4){0.0, 0.0, 0.0, 0.0};
+                }
+            const double* pa = tk.A + (size_t)(q0 + l15) * tk.ldg;
+            for (int kk = 0; kk < nk; ++kk) {
+                const int c = tk.c0 + 4 * kk + l4;
+                const bool in = c < tk.c1;
+                double xc[DC], av[TIG_CH];
+#pragma unroll
+                for (int d = 0; d < DC; ++d) xc[d] = (in && d < en) ? tk.xg[c + (size_t)(e0 + d) * tk.ldg] : 0.0;
+#pragma unroll
+                for (int ch = 0; ch < TIG_CH; ++ch) av[ch] = (in && ch < nch) ? pa[c + (size_t)(ch * TQ) * tk.ldg] : 0.0;
+                double f0 = 0.0, f1 = 0.0;
+                if (PAIR) {
+                    if (one_round) {
+#pragma unroll
+                        for (int d = 0; d < DC; ++d)
+                            if (d < en) {
+                                const double u0 = xa0[d] - xc[d], u1 = xa1[d] - xc[d];
+                                f0 = (KIND == 0) ? fma(u0, u0, f0) : fma(u0 * u0, nhd[d], f0);
+                                f1 = (KIND == 0) ? fma(u1, u1, f1) : fma(u1 * u1, nhd[d], f1);
+                            }
+                    } else {
+                        for (int d = 0; d < D; ++d) {
+                            const double b = in ? tk.xg[c + (size_t)d * tk.ldg] : 0.0;
+                            const double u0 = (live0 ? tk.xt[r0 + (size_t)d * tk.ldt] : 0.0) - b;
+                            const double u1 = (live1 ? tk.xt[r1 + (size_t)d * tk.ldt] : 0.0) - b;
+                            const double h = (KIND == 0) ? 0.0 : p.nh[d];
+                            f0 = (KIND == 0) ? fma(u0, u0, f0) : fma(u0 * u0, h, f0);
+                            f1 = (KIND == 0) ? fma(u1, u1, f1) : fma(u1 * u1, h, f1);
+                        }
+                    }
+                    f0 = factor(f0);
+                    f1 = factor(f1);
+                }
+#pragma unroll
+                for (int d = 0; d < DC; ++d)
+                    if (d < en) {
+                        double g0, g1;
+                        if (KIND == 0) {
+                            g0 = f0 * (xa0[d] - xc[d]);
+                            g1 = f1 * (xa1[d] - xc[d]);
+                        } else if (KIND == 4) {
+                            g0 = f0 * ((xa0[d] - xc[d]) * (2.0 * nhd[d]));
+                            g1 = f1 * ((xa1[d] - xc[d]) * (2.0 * nhd[d]));
+                        } else if (KIND == 5 || KIND == 6) {
+                            g0 = f0 * ((xa0[d] - xc[d]) * nhd[d]);
+                            g1 = f1 * ((xa1[d] - xc[d]) * nhd[d]);
+                        } else if (KIND == 1) {
+                            const double u0 = xa0[d] - xc[d], u1 = xa1[d] - xc[d];
+                            g0 = (p.sigma2 * exp_nonpos((u0 * u0) * nhd[d])) * (u0 * (2.0 * nhd[d]));
+                            g1 = (p.sigma2 * exp_nonpos((u1 * u1) * nhd[d])) * (u1 * (2.0 * nhd[d]));
+                        } else if (KIND == 2) {
+                            g0 = g1 = xc[d] * p.il2;
+                        } else {
+                            g0 = g1 = xc[d] * nhd[d];
+                        }
+                        g0 = in ? g0 : 0.0;
+                        g1 = in ? g1 : 0.0;
+#pragma unroll
+                        for (int ch = 0; ch < TIG_CH; ++ch) {
+                            if (ch >= nch) continue;
+                            acc[d][ch][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ch], g0, acc[d][ch][0], 0, 0, 0);
+                            acc[d][ch][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ch], g1, acc[d][ch][1], 0, 0, 0);
+                        }
+                    }
+            }
+            // register r of acc[d][ch][rn]: (column q0 + 16 ch + l4 + 4 r, test row 32 w + 16 rn + l15)
+#pragma unroll
+            for (int d = 0; d < DC; ++d) {
+                if (d >= en) continue;
+#pragma unroll
+                for (int ch = 0; ch < TIG_CH; ++ch) {
+                    if (ch >= nch) continue;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        double* pp = tk.part + ((size_t)(e0 + d) * qpad + (size_t)(q0 + ch * TQ + l4 + 4 * r)) * TB;
+                        if (live0) pp[r0] = acc[d][ch][0][r];
+                        if (live1) pp[r1] = acc[d][ch][1][r];
+                    }
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void targets_inputgrad_kernel(const TargetsInputGradTask* __restrict__ tasks,
+                                                                const KParam* __restrict__ kp, int D, int qpad) {
+    const TargetsInputGradTask tk = tasks[blockIdx.x];
+    const KParam p = kp[tk.kid];
+    DSMGP_KIND_DISPATCH_NON_RQ(p.kind, K, targets_inputgrad_body<K>(tk, p, D, qpad));
+}
+
+// the tasks of rational quadratic leaves (kinds 9, 10), over the same list, as pred_inputgrad_rq_kernel: launched only while a
+// kernel id has such a kind; each of the two kernels leaves the other's tasks alone
+__global__ __launch_bounds__(256) void targets_inputgrad_rq_kernel(const TargetsInputGradTask* __restrict__ tasks,
+                                                                   const KParam* __restrict__ kp, int D, int qpad) {
+    const TargetsInputGradTask tk = tasks[blockIdx.x];
+    const KParam p = kp[tk.kid];
+    if (p.kind < 9) return;
+    targets_inputgrad_body<6>(tk, p, D, qpad);
+}
+
+// The slabs of a test tile in ascending order; NaN for a leaf whose factorisation failed.  Grid (tiles, Q), one thread per row:
+// only rows < nrows and columns < Q are written.
+struct TargetsInputGradFinTask {
+    const double* part;     // the tile's first slab; slab s at part + s * pstride
+    double* out;            // dmu of the tile's first entry: (d, q) at out + (d + q D) * ldo
+    const int* info;
+    long long pstride, ldo;
+    int nslab, nrows;
+};
+
+__global__ __launch_bounds__(128) void targets_inputgrad_finish_kernel(const TargetsInputGradFinTask* __restrict__ tasks, int D,
+                                                                       int qpad) {
+    const TargetsInputGradFinTask tk = tasks[blockIdx.x];
+    const int r = threadIdx.x, q = blockIdx.y;
+    if (r >= tk.nrows) return;
+    const bool bad = *tk.info != 0;
+    for (int d = 0; d < D; ++d) {
+        double s = 0.0;
+        if (!bad)
+            for (int k = 0; k < tk.nslab; ++k) s += tk.part[(size_t)k * tk.pstride + ((size_t)d * qpad + q) * TB + r];
+        tk.out[r + ((size_t)d + (size_t)q * D) * tk.ldo] = bad ? __builtin_nan("") : s;
+    }
+}
+
 }  // namespace dsmgp

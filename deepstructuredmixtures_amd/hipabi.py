@@ -64,6 +64,7 @@ SIGNATURES = {
     "dsmgp_predict_targets": (C.c_int, [_ctx, _dp, C.c_int64, _dp]),
     "dsmgp_targets_fetch": (C.c_int, [_ctx, C.c_int32, _dp]),
     "dsmgp_mll_columns_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp]),
+    "dsmgp_predict_columns_gradients": (C.c_int, [_ctx, _dp, C.c_int64, _dp]),
     "dsmgp_loo_columns": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp]),
     "dsmgp_loo_columns_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp, _dp]),
     "dsmgp_gradients": (C.c_int, [_ctx, _dp, C.c_int32]),
@@ -540,6 +541,20 @@ class Context:
         self.targets_gradients_seconds = sec.value
         return g
 
+    def predict_targets_gradients(self):
+        """`dmu[route_total, D, Q]` (Fortran order): the gradient of the predictive mean of every (leaf, routed test row) entry
+        of `predict_fetch` with respect to the test point, under every column of the last `solve_targets`
+        (dsmgp_predict_columns_gradients; needs `solve_targets` and `predict_run` on the current fit).  `dmu[:, :, q]` has the
+        layout of `predict_gradients`' `dmu`.  The gradient of the variance does not depend on the targets: it is
+        `predict_gradients`' `dvar` for every column.  Entries of leaves with `info != 0` come back as NaN.  The device time of
+        the call is left in `self.predict_targets_gradients_seconds`."""
+        n = int(self.route_total)
+        dmu = np.empty((n, self.D, self.targets_Q), dtype=np.float64, order="F")
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_predict_columns_gradients(self.h, dmu.ctypes.data_as(_dp), max(1, n), C.byref(sec)))
+        self.predict_targets_gradients_seconds = sec.value
+        return dmu
+
     def _col_weight(self, col_weight):
         w = np.asarray(col_weight, dtype=np.float64)
         if w.ndim == 1:
@@ -958,6 +973,19 @@ class MultiContext:
         self.grad_seconds = max(s.grad_seconds for s in self.act)
         return dmu, dvar
 
+    def predict_targets_gradients(self):
+        """`Context.predict_targets_gradients` per sub-context, put back into the entry order of the whole leaf table (every
+        sub-context must hold the same columns: `solve_targets` is a call of the sub-contexts, `self.act`);
+        `self.predict_targets_gradients_seconds` is the longest of the sub-contexts' device times."""
+        _, rptr, _ = self._test
+        res = self._each(lambda s: s.predict_targets_gradients())
+        D, Q = self.act[0].D, res[0].shape[2]
+        dmu = np.empty((self.route_total, D, Q), dtype=np.float64, order="F")
+        for m, sub in zip(res, self.subsets):
+            sub.put_entries(dmu, rptr, m)
+        self.predict_targets_gradients_seconds = max(s.predict_targets_gradients_seconds for s in self.act)
+        return dmu
+
     def aggregate_partial(self, family, leaf_coef=None, leaf_group=None, n_groups=0):
         """Partial sums of all sub-contexts added in context order (the sums are linear in the leaves)."""
         coef = None if leaf_coef is None else np.asarray(leaf_coef, dtype=np.float64)
@@ -1324,6 +1352,10 @@ class StreamingContext:
     def predict_gradients(self, want_var=True):
         raise DsmgpError(E_STATE, "predict_gradients: a streaming pass discards alpha, K_tn L^-T and L^-T with their leaf group; "
                                   "use a resident Context for the input gradients of the prediction")
+
+    def predict_targets_gradients(self):
+        raise DsmgpError(E_STATE, "predict_targets_gradients: a streaming pass discards K_tn L^-T and L^-T with their leaf group "
+                                  "and keeps no target columns; use a resident Context")
 
     def predict_leaves(self, Xt, route_ptr, route_idx):
         self.set_test(Xt, route_ptr, route_idx)

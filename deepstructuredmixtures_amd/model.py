@@ -1574,6 +1574,58 @@ def predict_targets(model, xtest):
     return mu, var
 
 
+def predict_targets_gradients(model, xtest):
+    """`(mu, var, dmu, dvar)`: `predict_targets(model, xtest)` -- `mu`, `var` of shape `(n_t, Q)` -- and the gradients of both
+    moments with respect to the test point for every target column of the last `fit_targets`, `dmu`, `dvar` of shape
+    `(n_t, Q, D)`: `dmu[t]` is the Jacobian of the vector-valued predictive mean at row t (no reference counterpart).  The
+    per-(leaf, row) gradients of the means of all columns come from the device in one call (`Context.predict_targets_gradients`:
+    a matrix product per dimension on the resident `A = K_y^-1 (Y - m)`), the leaf `dvar`, which does not depend on the targets,
+    from `Context.predict_gradients`; the aggregation runs on the host, column by column (`aggregate_input_gradients`).  The
+    mixture variance depends on the column through the means, so `dvar` differs per column for a DSMGP; it is the same in every
+    column for PoE, gPoE, rBCM and a single GaussianProcess.  Refused: what `predict_gradients` and `predict_targets` refuse."""
+    target = _targets_model(model, "predict_targets_gradients")
+    if target.family == "dsmgp" and target.root.kind != "gp" and not target.tindex.weights_normalised():
+        raise ValueError("predict_targets_gradients: the sum weights are not normalised; predict then shifts the means by "
+                         "mu_min - 1, which is not differentiable")
+    if not hasattr(_ctx_type(target), "predict_targets_gradients"):
+        raise NotImplementedError(f"predict_targets_gradients: {_ctx_type(target).__name__} has no predict_targets_gradients")
+    if issubclass(_ctx_type(target), hipabi.StreamingContext):
+        raise hipabi.DsmgpError(hipabi.E_STATE, "predict_targets_gradients: a streaming context discards what the input gradients read")
+    xt = _test_matrix(target, xtest)
+    n_t, D = xt.shape
+    Q = int(getattr(target.ctx, "targets_Q", 0))
+    if Q < 1:
+        raise hipabi.DsmgpError(hipabi.E_STATE, "predict_targets_gradients before fit_targets")
+    if n_t == 0:
+        return np.zeros((0, Q)), np.zeros((0, Q)), np.zeros((0, Q, D)), np.zeros((0, Q, D))
+    mu, var = predict_targets(model, xt)    # routes, registers and runs as predict does; K_tn L^-T stays on the device
+    rc = _routing(target, xt)
+    ptr, idx = rc["lptr"], rc["lidx"]
+    _, var_l = target.ctx.predict_fetch()
+    mu_l = target.ctx.predict_targets()
+    dmu_l = target.ctx.predict_targets_gradients()
+    _, dvar_l = target.ctx.predict_gradients()
+    dmu = np.empty((n_t, Q, D))
+    dvar = np.empty((n_t, Q, D))
+    if isinstance(model, GaussianProcess):
+        for j in range(Q):
+            dmu[:, j, :], dvar[:, j, :] = dmu_l[:, :, j], dvar_l
+        return mu, var, dmu, dvar
+    ent = [[] for _ in range(n_t)]
+    for l in range(len(ptr) - 1):
+        for k in range(int(ptr[l]), int(ptr[l + 1])):
+            ent[int(idx[k])].append((l, k))
+    family, coef, group, G, plain, prior = _aggregation_spec(target)
+    kw = {}
+    if family == hipabi.AGG_RBCM:
+        kw = dict(kss_prior=_prior_diag(prior, xt), noise_prior=np.exp(2 * prior.logNoise), dkss_prior=_prior_diag_grad(prior, xt))
+    for j in range(Q):
+        dmu[:, j, :], dvar[:, j, :] = aggregate_input_gradients(family, np.ascontiguousarray(mu_l[:, j]), var_l,
+                                                                np.ascontiguousarray(dmu_l[:, :, j]), dvar_l, ent, coef=coef,
+                                                                group=group, G=G, plain=plain, **kw)
+    return mu, var, dmu, dvar
+
+
 def _ctx_type(model):
     """Type of the model's device context without creating it (a rank that owns no leaves never does)."""
     if model._ctx is not None:

@@ -330,9 +330,10 @@ int dsmgp_predict_gradients(dsmgp_ctx* ctx, double* dmu_out, double* dvar_out /*
  *   usable context when it does not fit), re-used while Q does not grow, NOT counted by dsmgp_estimate_bytes / dsmgp_memory,
  *   dropped with the leaf table, new training data and dsmgp_release (under a reserved pool also with a new test set: the pool
  *   is a stack).
- * Out of scope: input gradients for the extra columns, the multi-GPU exchange (each rank solves its own leaves, the mll
- *   table is per rank), and the streaming context.  Gradients of sum_j mll_j: dsmgp_mll_columns_gradients below; leave-one-out
- *   moments and gradients of the columns: dsmgp_loo_columns and dsmgp_loo_columns_gradients below. */
+ * Out of scope: the multi-GPU exchange (each rank solves its own leaves, the mll table is per rank), and the streaming
+ *   context.  The input gradients of the columns' means: dsmgp_predict_columns_gradients below.  Gradients of sum_j mll_j:
+ *   dsmgp_mll_columns_gradients below; leave-one-out moments and gradients of the columns: dsmgp_loo_columns and
+ *   dsmgp_loo_columns_gradients below. */
 int dsmgp_solve_targets(dsmgp_ctx* ctx, const double* Y /* N x Q column-major */, int64_t N, int32_t Q, int64_t ldy,
                         const double* mean /* L x Q column-major, ld = L; NULL = zeros */,
                         double* mll_out /* L x Q column-major, ld = L; may be NULL */, double* seconds /* may be NULL */);
@@ -368,6 +369,37 @@ int dsmgp_mll_columns_gradients(dsmgp_ctx* ctx, double* grad_out /* L x stride *
 static inline int dsmgp_targets_gradients(dsmgp_ctx* ctx, double* grad_out, int32_t stride, const double* col_weight,
                                           double* seconds) {
     return dsmgp_mll_columns_gradients(ctx, grad_out, stride, col_weight, seconds);
+}
+
+/* Gradients of the predictive means of the columns of dsmgp_solve_targets with respect to the test point -- the Jacobian of the
+ * vector-valued predictive mean: for every (leaf, routed test row t) entry e of dsmgp_predict_fetch, in its order, every input
+ * dimension d and every column q,
+ *   dmu_out[e + d * ld + q * ld * D] = d mu_q / d x_{t,d} = sum_{i < n} A_iq g_d(t, i),   g_d(t, i) = dk(x_t, x_i) / dx_{t,d},
+ * A = K_y^-1 (Y - m) (column q of the arena of dsmgp_mll_columns_gradients, same kernel and same bits) and g_d exactly the per-kind
+ * derivatives documented at dsmgp_predict_gradients, for all eleven kinds and any D.  Slice q has the layout of
+ * dsmgp_predict_gradients' dmu_out; with Q = 1, Y = y and the leaf means it is that call's dmu_out to rounding (another kernel:
+ * for Q columns the sum is a matrix product per dimension on the f64 matrix cores, the derivatives made in registers).
+ * The variance does not depend on the targets: d var / d x is dsmgp_predict_gradients' dvar_out for every column, and this call
+ * does not compute it.
+ * Needs BOTH dsmgp_solve_targets and dsmgp_predict_run on the CURRENT fit, on either route to K_tn L^-T (DSMGP_E_STATE otherwise).
+ * dmu_out NULL or ld < route_total: DSMGP_E_ARG.  No routed rows at all: success, nothing written.  Leaves whose fit reported
+ * info != 0 get NaN in all their entries, the others are unaffected.  A COPY leaf uses its own A and its source's L^-T.
+ * A needs L^-T of every factor owner: read as it is or filled here, by the rule of dsmgp_loo, and what that call says about
+ * dsmgp_gradients and the mask of dsmgp_set_gradient_leaves holds here too (both are left exactly as they are; the mask does not
+ * apply).  Nothing another entry point reads is written: dsmgp_predict_fetch, dsmgp_predict_cov, dsmgp_predict_targets,
+ * dsmgp_targets_fetch, dsmgp_gradients, dsmgp_loo*, dsmgp_predict_gradients and dsmgp_mll_columns_gradients return the same bits
+ * before and after.  Sums run in a fixed order, no atomics: the same bits from call to call, column q is the same bits whatever Q
+ * is and whatever the other columns hold, and a test row listed twice gets identical rows.
+ * Memory: A as in dsmgp_mll_columns_gradients; the output (route_total x D x Q doubles) and the partial sums (128 D Qpad doubles per
+ *   128 routed rows of a leaf and per 1024 of its training rows) in buffers of this call's own, allocated on first use, NOT counted
+ *   by dsmgp_estimate_bytes / dsmgp_memory, dropped with the test set, the leaf table and dsmgp_release.
+ * seconds (may be NULL): device time of the call. */
+int dsmgp_predict_columns_gradients(dsmgp_ctx* ctx, double* dmu_out /* route_total x D x Q */, int64_t ld,
+                                    double* seconds /* may be NULL */);
+/* The same call under the name of the feature, for C and C++ callers (an inline alias, not a symbol of the library, like
+ * dsmgp_targets_gradients above). */
+static inline int dsmgp_predict_targets_gradients(dsmgp_ctx* ctx, double* dmu_out, int64_t ld, double* seconds) {
+    return dsmgp_predict_columns_gradients(ctx, dmu_out, ld, seconds);
 }
 
 /* Leave-one-out cross-validation of the columns of dsmgp_solve_targets on the one factorisation (GPML eqs. 5.10-5.13 per column,

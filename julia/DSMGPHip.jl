@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, append_rows!, append_stats, resume_stats, download_vt, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
+export attach!, detach!, census, append_rows!, append_stats, resume_stats, download_vt, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, predict_targets_gradients, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -569,6 +569,23 @@ function predict_targets(s::Session)
     GC.@preserve μ chk(s, ccall(sym(:dsmgp_predict_targets), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}),
                             s.h, μ, Int64(max(nr, 1)), sec))
     return μ
+end
+
+"predict_targets_gradients(s): the gradient of the predictive mean of every (leaf, routed test row) entry of the last prediction
+with respect to the test point, under every column of the last solve_targets (dsmgp_predict_columns_gradients; needs both on the
+current fit): `route_total × D × Q`, in the entry order of the per-leaf moments; slice `[:, :, q]` has the layout of
+predict_gradients' `dmu`.  The gradient of the variance does not depend on the targets: it is predict_gradients' `dvar` for
+every column.  Entries of leaves whose fit reported info ≠ 0 come back as NaN."
+function predict_targets_gradients(s::Session)
+    ptr = Vector{Int64}(undef, length(s.leaves) + 1)
+    GC.@preserve ptr chk(s, ccall(sym(:dsmgp_routes), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), s.h, ptr, C_NULL))
+    nr = Int(ptr[end])
+    D = size(s.gps[1].x, 2)
+    dmu = Array{Float64,3}(undef, nr, D, s.targets)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve dmu chk(s, ccall(sym(:dsmgp_predict_columns_gradients), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}),
+                              s.h, dmu, Int64(max(nr, 1)), sec))
+    return dmu
 end
 
 "targets_fetch(s, leaf): Z = L⁻¹ (Y[obs, :] − mean) of leaf `leaf` (1-based, the order of `s.leaves`) as the last solve_targets left
