@@ -542,6 +542,12 @@ struct TestProducts {
     DevBuf<double> d_agg_coef;      // L
     DevBuf<int32_t> d_agg_group;    // L
     DevBuf<double> d_agg_out;       // mu | var (n_t each) | y_test (n_t) | score block sums
+    DevBuf<double> d_agg_gpart;     // dsmgp_aggregate_gradients*: Wg x n_t gradient sums (agg_gradients_width)
+    DevBuf<double> d_agg_gout;      // dmu | dvar of the aggregated prediction, n_t x D each
+    DevBuf<double> d_col_coef;      // dsmgp_aggregate_columns*: L, a state of its own beside d_agg_*
+    DevBuf<int32_t> d_col_group;    // L
+    DevBuf<double> d_col_out;       // mu | var of every column, n_t x Q each
+    DevBuf<double> d_col_gout;      // dmu | dvar of every column, n_t x D x Q each
     DevArena arenaVt;               // K_tn: a test set that replaces another takes the arenas of the old one over while it fits
                                     // (DevArena::fit; releasing ~10 GB and asking the driver for them again took up to 0.6 s of a
                                     // 0.06 s predict)
@@ -588,6 +594,12 @@ struct TestProducts {
         d_agg_coef.drop(keep);
         d_agg_group.drop(keep);
         d_agg_out.drop(keep);
+        d_agg_gpart.drop(keep);
+        d_agg_gout.drop(keep);
+        d_col_coef.drop(keep);
+        d_col_group.drop(keep);
+        d_col_out.drop(keep);
+        d_col_gout.drop(keep);
         if (!keep) {
             arenaVt.put();
             arenaXt.put();
@@ -811,6 +823,7 @@ struct dsmgp_ctx : Validity, PlanStore, TestInputs, TestProducts, GradLists, Gra
     int64_t route_total = 0;
     size_t acc_off = 0, acc_count = 0;      // the accumulators' part of arenaPV (register_test)
     int agg_family = -1, agg_G = 0, agg_W = 0;      // P_PARTIAL: what d_agg_part holds (dsmgp_aggregate_partial)
+    int col_family = -1, col_G = 0;                 // P_CDONE: the family of the last dsmgp_aggregate_columns
     // pinned host staging for the uploads of a registration (stage_upload): the lists of a test set are ~10 MB at the headline
     // model; through hipMemcpy from pageable vectors they took 9 ms of a 25 ms registration and left the runtime busy behind them
     char* stage = nullptr;
@@ -3918,6 +3931,7 @@ int dsmgp_aggregate_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain
     if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->d_agg_out.p, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->d_agg_out.p + nt, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->invalidate(P_DONE);      // what was made from the moments of another total (the gradient sums) falls
     c->mark(P_DONE);
     return 0;
 }
@@ -4644,16 +4658,13 @@ int dsmgp_loo(dsmgp_ctx* c, double* mu_out, double* var_out, double* lpd_out, do
 // reads alpha and the gathered inputs only.  The variance half needs beta_t = K_y^-1 k_t for every routed row: B = Vt L^-1 by a
 // tile GEMM against the L^-T arena (dsmgp_loo's rule for filling it), into an arena of its own -- Vt stays for dsmgp_predict_cov.
 // Nothing any other entry point reads is written.
-int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int64_t ld, double* seconds) {
-    if (!c) return DSMGP_E_ARG;
-    if (seconds) *seconds = 0.0;
-    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_gradients before predict_run on the current fit");
+namespace {
+// The device part: dmu (and dvar with `var`) of every routed row into d_pgout, no host copy.  route_total > 0.
+static int predict_gradients_device(dsmgp_ctx* c, bool var, double* seconds) {
     const size_t nr = (size_t)c->route_total;
-    if (nr == 0) return 0;
-    if (ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_gradients: ld < route_total");
     HIPCHK(c, hipSetDevice(c->device));
     const int L = c->L, D = c->D;
-    const bool var = dvar_out != nullptr;
+    if (var) c->invalidate(P_PGRAD);    // until both halves are written again
     OwnGradLists own_lists{c};
     std::vector<size_t> boff((size_t)L, 0);
     if (var) {
@@ -4758,10 +4769,26 @@ int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev.b, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (var) c->mark(P_XINV);
+    if (var) {
+        c->mark(P_XINV);
+        c->mark(P_PGRAD);   // both halves are this prediction's (a mean-only call later writes the same dmu into the same place)
+    }
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     if (seconds) *seconds = ms * 1e-3;
+    return 0;
+}
+}  // namespace
+
+int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int64_t ld, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_gradients before predict_run on the current fit");
+    const size_t nr = (size_t)c->route_total;
+    if (nr == 0) return 0;
+    if (ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_gradients: ld < route_total");
+    const int D = c->D;
+    if (int rc = predict_gradients_device(c, dvar_out != nullptr, seconds)) return rc;
     if (dmu_out)
         HIPCHK(c, hipMemcpy2D(dmu_out, (size_t)ld * sizeof(double), c->d_pgout.p, nr * sizeof(double), nr * sizeof(double), (size_t)D,
                               hipMemcpyDeviceToHost));
@@ -4769,6 +4796,107 @@ int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int
         HIPCHK(c, hipMemcpy2D(dvar_out, (size_t)ld * sizeof(double), c->d_pgout.p + nr * (size_t)D, nr * sizeof(double),
                               nr * sizeof(double), (size_t)D, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// Input gradients of the aggregated prediction (the kernels and the layout of the sums: kernels.hpp at AggGradArgs).  Family,
+// coefficients and groups are those of the last dsmgp_aggregate_partial, resident since; the per-entry gradients are d_pgout,
+// made here (predict_gradients_device) unless both halves are this prediction's already.  Nothing another entry point reads is
+// written: the sums and the results have buffers of their own.
+namespace {
+int agg_gradients_width(int family, int G, int D) { return (family == AGG_MIXTURE ? 3 : (family == AGG_RBCM ? 2 * G : 2)) * D; }
+}  // namespace
+
+int dsmgp_aggregate_gradients_partial(dsmgp_ctx* c, double* partial_out, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->has(P_DONE)) return fail(c, DSMGP_E_STATE, "aggregate_gradients before aggregate on the current prediction");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nt = (size_t)c->n_t, nr = (size_t)c->route_total;
+    const int D = c->D;
+    const size_t need = (size_t)agg_gradients_width(c->agg_family, c->agg_G, D) * nt;
+    c->invalidate(P_GSUMS);
+    if (int rc = c->d_agg_gpart.grow(c, need)) return rc;
+    double prod_seconds = 0.0;
+    if (!c->has(P_PGRAD)) {
+        if (nr) {
+            if (int rc = predict_gradients_device(c, true, &prod_seconds)) return rc;
+        } else {
+            c->mark(P_PGRAD);       // no entry: nothing to make
+        }
+    }
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    AggGradArgs a{};
+    a.row_ptr = c->d_row_ptr.p;
+    a.row_ent = c->d_row_ent.p;
+    a.ent_leaf = c->d_ent_leaf.p;
+    a.mu = c->arenaPV.p;
+    a.var = c->arenaPV.p + nr;
+    a.dmu = c->d_pgout.p;
+    a.dvar = c->d_pgout.p + nr * (size_t)D;
+    a.coef = c->d_agg_coef.p;
+    a.group = c->d_agg_group.p;
+    a.agg_mu = c->d_agg_out.p;
+    a.part = c->d_agg_gpart.p;
+    a.n_t = c->n_t;
+    a.ld = c->route_total;
+    a.D = D;
+    a.family = c->agg_family;
+    a.G = c->agg_G;
+    agg_grad_partial_kernel<<<dim3((unsigned)((nt + 255) / 256), (unsigned)D), 256, 0, c->stream>>>(a);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    if (partial_out) HIPCHK(c, hipMemcpyAsync(partial_out, c->d_agg_gpart.p, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = prod_seconds + ms * 1e-3;
+    c->mark(P_GSUMS);
+    return 0;
+}
+
+int dsmgp_aggregate_gradients_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain, int32_t prior_kernel_id,
+                                     double* dmu_out, double* dvar_out, int64_t ld) {
+    if (!c) return DSMGP_E_ARG;
+    if (!c->has(P_GSUMS)) return fail(c, DSMGP_E_STATE, "aggregate_gradients_finish before aggregate_gradients_partial");
+    if (c->agg_family == AGG_RBCM &&
+        (prior_kernel_id < 0 || prior_kernel_id >= (int)c->hyper.size() || c->hyper[prior_kernel_id].kind < 0))
+        return fail(c, DSMGP_E_ARG, "aggregate_gradients_finish: rBCM needs the kernel id of the model's first leaf");
+    if (c->agg_family == AGG_RBCM && ard_linear_short(c, prior_kernel_id))
+        return fail(c, DSMGP_E_ARG, std::string("aggregate_gradients_finish: ") + KINDS[c->hyper[prior_kernel_id].kind].name +
+                                        " needs one lengthscale per input dimension");
+    if (ld < c->n_t) return fail(c, DSMGP_E_ARG, "aggregate_gradients_finish: ld < n_t");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nt = (size_t)c->n_t;
+    const int D = c->D;
+    if (int rc = c->d_agg_gout.grow(c, 2 * nt * (size_t)D)) return rc;
+    if (partial_in)     // sums over all contexts, added by the caller
+        HIPCHK(c, hipMemcpyAsync(c->d_agg_gpart.p, partial_in, (size_t)agg_gradients_width(c->agg_family, c->agg_G, D) * nt * sizeof(double),
+                                 hipMemcpyHostToDevice, c->stream));
+    double* gm = c->d_agg_gout.p;
+    double* gv = gm + nt * (size_t)D;
+    agg_grad_finish_kernel<<<dim3((unsigned)((nt + 255) / 256), (unsigned)D), 256, 0, c->stream>>>(
+        c->d_agg_gpart.p, c->d_agg_part.p, c->n_t, D, c->agg_family, c->agg_G, plain ? 1 : 0, c->d_kp.p,
+        c->agg_family == AGG_RBCM ? prior_kernel_id : 0, c->dXt.p, gm, gv);
+    HIPCHK(c, hipGetLastError());
+    if (dmu_out)
+        HIPCHK(c, hipMemcpy2DAsync(dmu_out, (size_t)ld * sizeof(double), gm, nt * sizeof(double), nt * sizeof(double), (size_t)D,
+                                   hipMemcpyDeviceToHost, c->stream));
+    if (dvar_out)
+        HIPCHK(c, hipMemcpy2DAsync(dvar_out, (size_t)ld * sizeof(double), gv, nt * sizeof(double), nt * sizeof(double), (size_t)D,
+                                   hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int dsmgp_aggregate_gradients(dsmgp_ctx* c, int32_t plain, int32_t prior_kernel_id, double* dmu_out, double* dvar_out, int64_t ld,
+                              double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (c->has(P_DONE) && ld < c->n_t) return fail(c, DSMGP_E_ARG, "aggregate_gradients: ld < n_t");    // before any device work
+    if (int rc = dsmgp_aggregate_gradients_partial(c, nullptr, seconds)) return rc;
+    return dsmgp_aggregate_gradients_finish(c, nullptr, plain, prior_kernel_id, dmu_out, dvar_out, ld);
 }
 
 // Several target columns on the current factors (kernels_targets.hpp).  Z = L^-1 (Y[obs] - mean) for every leaf by a
@@ -4901,16 +5029,13 @@ int dsmgp_solve_targets(dsmgp_ctx* c, const double* Y, int64_t N, int32_t Q, int
     return 0;
 }
 
-int dsmgp_predict_targets(dsmgp_ctx* c, double* mu_out, int64_t ld, double* seconds) {
-    if (!c) return DSMGP_E_ARG;
-    if (seconds) *seconds = 0.0;
-    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "predict_targets before solve_targets on the current fit");
-    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_targets before predict_run on the current fit");
+namespace {
+// The device part: the means of every resident column per routed row into d_tmu, no host copy.  route_total > 0.
+static int predict_targets_device(dsmgp_ctx* c, double* seconds) {
     const size_t nr = (size_t)c->route_total;
-    if (nr == 0) return 0;
-    if (!mu_out || ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_targets: mu_out is NULL or ld < route_total");
     HIPCHK(c, hipSetDevice(c->device));
     const int L = c->L, Q = c->tg_Q, qpad = c->tg_qpad;
+    c->invalidate(P_TMU);
     if (int rc = c->d_tmu.grow(c, nr * (size_t)Q)) return rc;
     std::vector<TargetsMuTask> tasks;
     for (int l = 0; l < L; ++l) {
@@ -4945,7 +5070,21 @@ int dsmgp_predict_targets(dsmgp_ctx* c, double* mu_out, int64_t ld, double* seco
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     if (seconds) *seconds = ms * 1e-3;
-    HIPCHK(c, hipMemcpy2D(mu_out, (size_t)ld * sizeof(double), c->d_tmu.p, nr * sizeof(double), nr * sizeof(double), (size_t)Q,
+    c->mark(P_TMU);
+    return 0;
+}
+}  // namespace
+
+int dsmgp_predict_targets(dsmgp_ctx* c, double* mu_out, int64_t ld, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "predict_targets before solve_targets on the current fit");
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_targets before predict_run on the current fit");
+    const size_t nr = (size_t)c->route_total;
+    if (nr == 0) return 0;
+    if (!mu_out || ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_targets: mu_out is NULL or ld < route_total");
+    if (int rc = predict_targets_device(c, seconds)) return rc;
+    HIPCHK(c, hipMemcpy2D(mu_out, (size_t)ld * sizeof(double), c->d_tmu.p, nr * sizeof(double), nr * sizeof(double), (size_t)c->tg_Q,
                           hipMemcpyDeviceToHost));
     return 0;
 }
@@ -5001,16 +5140,13 @@ static void targets_a_tasks(const dsmgp_ctx* c, std::vector<TargetsATask>& ta) {
 // dimension with the kernel derivatives made in registers.  A COPY leaf reads its source's L^-T with its own Z.  The lists are
 // rebuilt per call; the partial sums and the output live in buffers of this entry point (TestProducts): nothing another entry point
 // reads is written, and the mask of dsmgp_set_gradient_leaves neither applies nor changes.
-int dsmgp_predict_columns_gradients(dsmgp_ctx* c, double* dmu_out, int64_t ld, double* seconds) {
-    if (!c) return DSMGP_E_ARG;
-    if (seconds) *seconds = 0.0;
-    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "predict_targets_gradients before solve_targets on the current fit");
-    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_targets_gradients before predict_run on the current fit");
+namespace {
+// The device part: the input gradients of the columns' means into d_tigout, no host copy.  route_total > 0.
+static int predict_columns_gradients_device(dsmgp_ctx* c, double* seconds) {
     const size_t nr = (size_t)c->route_total;
-    if (nr == 0) return 0;
-    if (!dmu_out || ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_targets_gradients: dmu_out is NULL or ld < route_total");
     HIPCHK(c, hipSetDevice(c->device));
     const int L = c->L, D = c->D, Q = c->tg_Q, qpad = c->tg_qpad;
+    c->invalidate(P_TIG);
     // L^-T of every factor owner (xinv_lists / xinv_fill); lists of the call's own are dropped again on every way out
     OwnGradLists own_lists{c};
     if (int rc = xinv_lists(c, own_lists)) return rc;
@@ -5081,11 +5217,165 @@ int dsmgp_predict_columns_gradients(dsmgp_ctx* c, double* dmu_out, int64_t ld, d
     HIPCHK(c, hipEventRecord(ev.b, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->mark(P_XINV);
+    c->mark(P_TIG);
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     if (seconds) *seconds = ms * 1e-3;
+    return 0;
+}
+}  // namespace
+
+int dsmgp_predict_columns_gradients(dsmgp_ctx* c, double* dmu_out, int64_t ld, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "predict_targets_gradients before solve_targets on the current fit");
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_targets_gradients before predict_run on the current fit");
+    const size_t nr = (size_t)c->route_total;
+    if (nr == 0) return 0;
+    if (!dmu_out || ld < c->route_total) return fail(c, DSMGP_E_ARG, "predict_targets_gradients: dmu_out is NULL or ld < route_total");
+    if (int rc = predict_columns_gradients_device(c, seconds)) return rc;
     HIPCHK(c, hipMemcpy2D(dmu_out, (size_t)ld * sizeof(double), c->d_tigout.p, nr * sizeof(double), nr * sizeof(double),
-                          (size_t)D * (size_t)Q, hipMemcpyDeviceToHost));
+                          (size_t)c->D * (size_t)c->tg_Q, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// predict(model, x) and its input gradients for every resident target column (kernels.hpp at AggColsArgs).  A state of their own
+// beside the single-y aggregation (d_col_*, col_family): d_agg_* and what dsmgp_scores / dsmgp_aggregate_finish answer stay as
+// they are.  One context only: no partial / finish split.
+namespace {
+static void agg_columns_args(dsmgp_ctx* c, AggColsArgs& a, int plain, int prior_kernel_id) {
+    a.row_ptr = c->d_row_ptr.p;
+    a.row_ent = c->d_row_ent.p;
+    a.ent_leaf = c->d_ent_leaf.p;
+    a.tmu = c->d_tmu.p;
+    a.var = c->arenaPV.p + (size_t)c->route_total;
+    a.coef = c->d_col_coef.p;
+    a.group = c->d_col_group.p;
+    a.kp = c->d_kp.p;
+    a.Xt = c->dXt.p;
+    a.n_t = c->n_t;
+    a.ld = c->route_total;
+    a.D = c->D;
+    a.Q = c->tg_Q;
+    a.family = c->col_family;
+    a.G = c->col_G;
+    a.plain = plain ? 1 : 0;
+    a.prior_kid = c->col_family == AGG_RBCM ? prior_kernel_id : 0;
+}
+static int agg_prior_check(dsmgp_ctx* c, int family, int prior_kernel_id, const char* who) {
+    if (family != AGG_RBCM) return 0;
+    if (prior_kernel_id < 0 || prior_kernel_id >= (int)c->hyper.size() || c->hyper[prior_kernel_id].kind < 0)
+        return fail(c, DSMGP_E_ARG, std::string(who) + ": rBCM needs the kernel id of the model's first leaf");
+    if (ard_linear_short(c, prior_kernel_id))
+        return fail(c, DSMGP_E_ARG, std::string(who) + ": " + KINDS[c->hyper[prior_kernel_id].kind].name +
+                                        " needs one lengthscale per input dimension");
+    return 0;
+}
+}  // namespace
+
+int dsmgp_aggregate_columns(dsmgp_ctx* c, int32_t family, const double* leaf_coef, const int32_t* leaf_group, int32_t n_groups,
+                            int32_t plain, int32_t prior_kernel_id, double* mu_out, double* var_out, int64_t ld, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "aggregate_columns before solve_targets on the current fit");
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "aggregate_columns before predict_run on the current fit");
+    if (family < AGG_MIXTURE || family > AGG_RBCM) return fail(c, DSMGP_E_ARG, "aggregate_columns: unknown family");
+    if (family == AGG_RBCM) {
+        if (!leaf_group || n_groups <= 0 || n_groups > 4096) return fail(c, DSMGP_E_ARG, "aggregate_columns: rBCM needs leaf groups");
+        for (int l = 0; l < c->L; ++l)
+            if (leaf_group[l] < 0 || leaf_group[l] >= n_groups) return fail(c, DSMGP_E_ARG, "aggregate_columns: leaf group out of range");
+    } else if (!leaf_coef) {
+        return fail(c, DSMGP_E_ARG, "aggregate_columns: leaf_coef is NULL");
+    }
+    if (int rc = agg_prior_check(c, family, prior_kernel_id, "aggregate_columns")) return rc;
+    if (ld < c->n_t) return fail(c, DSMGP_E_ARG, "aggregate_columns: ld < n_t");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nt = (size_t)c->n_t, L = (size_t)c->L;
+    const int Q = c->tg_Q;
+    c->invalidate(P_CDONE);
+    if (int rc = c->d_col_coef.grow(c, L)) return rc;
+    if (int rc = c->d_col_group.grow(c, L)) return rc;
+    if (int rc = c->d_col_out.grow(c, 2 * nt * (size_t)Q)) return rc;
+    double prod_seconds = 0.0;
+    if (!c->has(P_TMU)) {
+        if (c->route_total) {
+            if (int rc = predict_targets_device(c, &prod_seconds)) return rc;
+        } else {
+            c->mark(P_TMU);         // no entry: nothing to make
+        }
+    }
+    if (leaf_coef) HIPCHK(c, hipMemcpyAsync(c->d_col_coef.p, leaf_coef, L * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (family == AGG_RBCM)
+        HIPCHK(c, hipMemcpyAsync(c->d_col_group.p, leaf_group, L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    c->col_family = family;
+    c->col_G = family == AGG_RBCM ? n_groups : 0;
+    AggColsArgs a{};
+    agg_columns_args(c, a, plain, prior_kernel_id);
+    a.out_m = c->d_col_out.p;
+    a.out_v = c->d_col_out.p + nt * (size_t)Q;
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    agg_columns_kernel<<<dim3((unsigned)((nt + 255) / 256), (unsigned)Q), 256, 0, c->stream>>>(a);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    if (mu_out)
+        HIPCHK(c, hipMemcpy2DAsync(mu_out, (size_t)ld * sizeof(double), a.out_m, nt * sizeof(double), nt * sizeof(double), (size_t)Q,
+                                   hipMemcpyDeviceToHost, c->stream));
+    if (var_out)
+        HIPCHK(c, hipMemcpy2DAsync(var_out, (size_t)ld * sizeof(double), a.out_v, nt * sizeof(double), nt * sizeof(double), (size_t)Q,
+                                   hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // leaf_coef / leaf_group are the caller's
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = prod_seconds + ms * 1e-3;
+    c->mark(P_CDONE);
+    return 0;
+}
+
+int dsmgp_aggregate_columns_gradients(dsmgp_ctx* c, int32_t plain, int32_t prior_kernel_id, double* dmu_out, double* dvar_out,
+                                      int64_t ld, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->has(P_CDONE)) return fail(c, DSMGP_E_STATE, "aggregate_columns_gradients before aggregate_columns on the current prediction and columns");
+    if (int rc = agg_prior_check(c, c->col_family, prior_kernel_id, "aggregate_columns_gradients")) return rc;
+    if (ld < c->n_t) return fail(c, DSMGP_E_ARG, "aggregate_columns_gradients: ld < n_t");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nt = (size_t)c->n_t, nr = (size_t)c->route_total;
+    const int D = c->D, Q = c->tg_Q;
+    if (int rc = c->d_col_gout.grow(c, 2 * nt * (size_t)D * (size_t)Q)) return rc;
+    double prod_seconds = 0.0, s1 = 0.0;
+    if (nr && !c->has(P_TIG)) {
+        if (int rc = predict_columns_gradients_device(c, &s1)) return rc;
+        prod_seconds += s1;
+    }
+    if (nr && !c->has(P_PGRAD)) {
+        if (int rc = predict_gradients_device(c, true, &s1)) return rc;
+        prod_seconds += s1;
+    }
+    AggColsArgs a{};
+    agg_columns_args(c, a, plain, prior_kernel_id);
+    a.tdmu = c->d_tigout.p;
+    a.dvar = c->d_pgout.p + nr * (size_t)D;
+    a.out_m = c->d_col_gout.p;
+    a.out_v = c->d_col_gout.p + nt * (size_t)D * (size_t)Q;
+    EventPair ev;
+    HIPCHK(c, ev.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    agg_columns_grad_kernel<<<dim3((unsigned)((nt + 255) / 256), (unsigned)Q), 256, 0, c->stream>>>(a);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    const size_t cols = (size_t)D * (size_t)Q;
+    if (dmu_out)
+        HIPCHK(c, hipMemcpy2DAsync(dmu_out, (size_t)ld * sizeof(double), a.out_m, nt * sizeof(double), nt * sizeof(double), cols,
+                                   hipMemcpyDeviceToHost, c->stream));
+    if (dvar_out)
+        HIPCHK(c, hipMemcpy2DAsync(dvar_out, (size_t)ld * sizeof(double), a.out_v, nt * sizeof(double), nt * sizeof(double), cols,
+                                   hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = prod_seconds + ms * 1e-3;
     return 0;
 }
 

@@ -3968,6 +3968,331 @@ __global__ __launch_bounds__(256) void agg_finish_kernel(const double* __restric
     }
 }
 
+// Input gradients of the aggregated prediction (dsmgp_aggregate_gradients*): the same gather-reduce over a row's entries, on
+// dmu | dvar of every entry (pred_inputgrad_finish_kernel: plane d at d * ld, ld = route_total).  One thread per (test row,
+// input dimension) -- blockIdx.y = d, lanes over consecutive rows as above -- walks the row's entries in ascending entry order:
+// fixed summation order, no atomics.  Partial sums in [k][row] planes, additive over contexts once every holder has the TOTAL
+// moments (agg_mu is the aggregated mean of the finish step; T, P of the products are read by the finish step only):
+//   mixture   k = d: sum W dmu_d;  D + d: sum W dvar'_d (dvar' = 0 where the moments clamp the leaf variance);
+//             2 D + d: sum W (mu_l - mu) dmu_d, centred on the aggregated mean so that a large offset of y cancels per term
+//   PoE/gPoE  k = d: dT_d = -sum beta dvar_d / sigma^4;  D + d: dP_d = sum beta (dmu_d / sigma^2 - mu_l dvar_d / sigma^4)
+//   rBCM      k = 2 g D + d: dT_gd;  (2 g + 1) D + d: dP_gd, with beta = 1, per root child g
+struct AggGradArgs {
+    const int64_t* row_ptr;     // as AggArgs
+    const int32_t* row_ent;
+    const int32_t* ent_leaf;
+    const double* mu;           // per (leaf, routed row), route order
+    const double* var;
+    const double* dmu;          // per entry and dimension: [pos + d * ld]
+    const double* dvar;
+    const double* coef;
+    const int32_t* group;
+    const double* agg_mu;       // n_t: the aggregated mean (mixture)
+    double* part;               // Wg x n_t
+    int64_t n_t;
+    int64_t ld;                 // route_total
+    int D;
+    int family;
+    int G;
+};
+
+__global__ __launch_bounds__(256) void agg_grad_partial_kernel(AggGradArgs a) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.n_t) return;
+    const int d = blockIdx.y, D = a.D;
+    const int64_t e0 = a.row_ptr[r], e1 = a.row_ptr[r + 1];
+    const double* dmu = a.dmu + (size_t)d * a.ld;
+    const double* dvar = a.dvar + (size_t)d * a.ld;
+    if (a.family == AGG_MIXTURE) {
+        const double mbar = a.agg_mu[r];
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int64_t e = e0; e < e1; ++e) {
+            const int pos = a.row_ent[e];
+            const double w = a.coef[a.ent_leaf[pos]];
+            const double dm = dmu[pos];
+            const double dv = a.var[pos] <= 0.0 ? 0.0 : dvar[pos];    // a clamped variance is a constant (a NaN one stays NaN)
+            s0 += w * dm;
+            s1 += w * dv;
+            s2 += w * ((a.mu[pos] - mbar) * dm);
+        }
+        a.part[(size_t)d * a.n_t + r] = s0;
+        a.part[(size_t)(D + d) * a.n_t + r] = s1;
+        a.part[(size_t)(2 * D + d) * a.n_t + r] = s2;
+    } else if (a.family == AGG_RBCM) {
+        for (int g = 0; g < a.G; ++g) {
+            a.part[((size_t)(2 * g) * D + d) * a.n_t + r] = 0.0;
+            a.part[((size_t)(2 * g + 1) * D + d) * a.n_t + r] = 0.0;
+        }
+        for (int64_t e = e0; e < e1; ++e) {
+            const int pos = a.row_ent[e];
+            const int g = a.group[a.ent_leaf[pos]];
+            const double v = a.var[pos];
+            const double t = 1.0 / v;
+            const double dv = dvar[pos];
+            a.part[((size_t)(2 * g) * D + d) * a.n_t + r] -= (t / v) * dv;
+            a.part[((size_t)(2 * g + 1) * D + d) * a.n_t + r] += t * dmu[pos] - (t * a.mu[pos] / v) * dv;
+        }
+    } else {
+        double s0 = 0.0, s1 = 0.0;
+        for (int64_t e = e0; e < e1; ++e) {
+            const int pos = a.row_ent[e];
+            const double v = a.var[pos];
+            const double t = a.coef[a.ent_leaf[pos]] / v;
+            const double dv = dvar[pos];
+            s0 -= (t / v) * dv;
+            s1 += t * dmu[pos] - (t * a.mu[pos] / v) * dv;
+        }
+        a.part[(size_t)d * a.n_t + r] = s0;
+        a.part[(size_t)(D + d) * a.n_t + r] = s1;
+    }
+}
+
+// Finish step on the (summed) gradient sums `gpart` and the total moment sums `part` of agg_finish_kernel (the formulas:
+// aggregate_input_gradients of the Python package, term by term).  One thread per (row, dimension); dmu_out / dvar_out are
+// n_t x D planes.  rBCM: ds/dx_d of the prior s = k(x*, x*) + noise is 2 x_d / l_d^2 for the linear kinds, 0 for the others.
+__global__ __launch_bounds__(256) void agg_grad_finish_kernel(const double* __restrict__ gpart, const double* __restrict__ part,
+                                                              int64_t n_t, int D, int family, int G, int plain,
+                                                              const KParam* __restrict__ kp, int prior_kid,
+                                                              const double* __restrict__ Xt, double* __restrict__ dmu_out,
+                                                              double* __restrict__ dvar_out) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_t) return;
+    const int d = blockIdx.y;
+    const size_t o = (size_t)d * n_t + r;
+    if (family == AGG_MIXTURE) {
+        const double sv = gpart[(size_t)(D + d) * n_t + r];
+        dmu_out[o] = gpart[o];
+        dvar_out[o] = plain ? sv : sv + 2.0 * gpart[(size_t)(2 * D + d) * n_t + r];
+    } else if (family == AGG_RBCM) {
+        const KParam p = kp[prior_kid];
+        const double s = prior_var(p, Xt, r, n_t, D) + p.noise;
+        const double x = Xt[o];
+        const double ds = p.kind == 2 ? 2.0 * x / p.l2[0] : (p.kind == 3 ? 2.0 * x * p.nh[d] : 0.0);
+        const double ds_s2 = ds / (s * s);
+        double C = 1.0 / s, dC = -ds_s2, m = 0.0, dm = 0.0;
+        for (int g = 0; g < G; ++g) {
+            const double T = part[(size_t)(2 * g + 1) * n_t + r];
+            if (T == 0.0) continue;                               // no leaf of this child saw the row
+            const double P = part[(size_t)(2 * g) * n_t + r];
+            const double dT = gpart[((size_t)(2 * g) * D + d) * n_t + r];
+            const double dP = gpart[((size_t)(2 * g + 1) * D + d) * n_t + r];
+            const double beta = 0.5 * (log(s) + log(T));
+            const double dbeta = 0.5 * (ds / s + dT / T);
+            C += beta * (T - 1.0 / s);
+            dC += dbeta * (T - 1.0 / s) + beta * (dT + ds_s2);
+            m += beta * P;
+            dm += dbeta * P + beta * dP;
+        }
+        const double mu = m / C;
+        dmu_out[o] = (dm - mu * dC) / C;
+        dvar_out[o] = -dC / (C * C);
+    } else {
+        const double P = part[r], T = part[n_t + r];
+        const double dT = gpart[o], dP = gpart[(size_t)(D + d) * n_t + r];
+        const double mu = P / T;
+        dmu_out[o] = (dP - mu * dT) / T;
+        dvar_out[o] = -dT / (T * T);
+    }
+}
+
+// The same aggregation for every resident target column (dsmgp_aggregate_columns, dsmgp_aggregate_columns_gradients): the means
+// are d_tmu [pos + q ld], their input gradients d_tigout [pos + d ld + q ld D]; the leaf variance and its gradient are shared by
+// the columns.  One thread per (test row, column), blockIdx.y = q, walks the row's entries in ascending entry order and
+// finishes in registers: no partial sums in memory, no atomics, and column q never reads another column, so it is the same bits
+// whatever Q is.  The operations are those of agg_partial_kernel / agg_finish_kernel and of the two gradient kernels above; an
+// rBCM row walks its entries once per group (the groups' sums in registers instead of G planes).
+struct AggColsArgs {
+    const int64_t* row_ptr;     // as AggArgs
+    const int32_t* row_ent;
+    const int32_t* ent_leaf;
+    const double* tmu;          // [pos + q * ld]
+    const double* var;          // [pos]
+    const double* tdmu;         // [pos + d * ld + q * ld * D]   (gradients only)
+    const double* dvar;         // [pos + d * ld]                (gradients only)
+    const double* coef;
+    const int32_t* group;
+    const KParam* kp;
+    const double* Xt;           // n_t x D (the rBCM prior)
+    double* out_m;              // moments: n_t x Q; gradients: [r + d * n_t + q * n_t * D]
+    double* out_v;
+    int64_t n_t;
+    int64_t ld;                 // route_total
+    int D, Q, family, G, plain, prior_kid;
+};
+
+__global__ __launch_bounds__(256) void agg_columns_kernel(AggColsArgs a) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.n_t) return;
+    const int q = blockIdx.y;
+    const int64_t e0 = a.row_ptr[r], e1 = a.row_ptr[r + 1];
+    const double* mu = a.tmu + (size_t)q * a.ld;
+    const size_t o = (size_t)q * a.n_t + r;
+    if (a.family == AGG_MIXTURE) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int64_t e = e0; e < e1; ++e) {
+            const int pos = a.row_ent[e];
+            const double w = a.coef[a.ent_leaf[pos]];
+            const double m = mu[pos];
+            double v = a.var[pos];
+            if (v <= 0.0) v = 1e-8;
+            s0 += w * m;
+            s1 += w * (m * m);
+            s2 += w * v;
+        }
+        a.out_m[o] = s0;
+        a.out_v[o] = a.plain ? s2 : s2 + (s1 - s0 * s0);
+    } else if (a.family == AGG_RBCM) {
+        const KParam p = a.kp[a.prior_kid];
+        const double s = prior_var(p, a.Xt, r, a.n_t, a.D) + p.noise;
+        double C = 1.0 / s, m = 0.0;
+        for (int g = 0; g < a.G; ++g) {
+            double S = 0.0, T = 0.0;
+            for (int64_t e = e0; e < e1; ++e) {
+                const int pos = a.row_ent[e];
+                if (a.group[a.ent_leaf[pos]] != g) continue;
+                const double t = 1.0 / a.var[pos];
+                S += t * mu[pos];
+                T += t;
+            }
+            if (T == 0.0) continue;
+            const double M = S / T;
+            const double beta = 0.5 * (log(s) - log(1.0 / T));
+            C += beta * T - beta / s;
+            m += M * (beta * T);
+        }
+        a.out_m[o] = m / C;
+        a.out_v[o] = 1.0 / C;
+    } else {
+        double s0 = 0.0, s1 = 0.0;
+        for (int64_t e = e0; e < e1; ++e) {
+            const int pos = a.row_ent[e];
+            const double bt = a.coef[a.ent_leaf[pos]] * (1.0 / a.var[pos]);
+            s0 += bt * mu[pos];
+            s1 += bt;
+        }
+        a.out_m[o] = s0 / s1;
+        a.out_v[o] = 1.0 / s1;
+    }
+}
+
+// Gradients: chunks of AGG_DC input dimensions in registers, so that an entry's indices, coefficient, mu and var are read once
+// per chunk and not once per dimension (once in all for D <= 8).
+constexpr int AGG_DC = 8;
+
+__global__ __launch_bounds__(256) void agg_columns_grad_kernel(AggColsArgs a) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.n_t) return;
+    const int q = blockIdx.y, D = a.D;
+    const int64_t e0 = a.row_ptr[r], e1 = a.row_ptr[r + 1];
+    const double* mu = a.tmu + (size_t)q * a.ld;
+    const double* dmq = a.tdmu + (size_t)q * a.ld * D;
+    double* om = a.out_m + (size_t)q * a.n_t * D + r;
+    double* ov = a.out_v + (size_t)q * a.n_t * D + r;
+    double mbar = 0.0;
+    if (a.family == AGG_MIXTURE)
+        for (int64_t e = e0; e < e1; ++e) {
+            const int pos = a.row_ent[e];
+            mbar += a.coef[a.ent_leaf[pos]] * mu[pos];
+        }
+    for (int d0 = 0; d0 < D; d0 += AGG_DC) {
+        const int nd = min(AGG_DC, D - d0);
+        if (a.family == AGG_MIXTURE) {
+            double s0[AGG_DC] = {}, s1[AGG_DC] = {}, s2[AGG_DC] = {};
+            for (int64_t e = e0; e < e1; ++e) {
+                const int pos = a.row_ent[e];
+                const double w = a.coef[a.ent_leaf[pos]];
+                const double c = mu[pos] - mbar;
+                const bool clamped = a.var[pos] <= 0.0;
+#pragma unroll
+                for (int k = 0; k < AGG_DC; ++k)
+                    if (k < nd) {
+                        const double dm = dmq[pos + (size_t)(d0 + k) * a.ld];
+                        const double dv = clamped ? 0.0 : a.dvar[pos + (size_t)(d0 + k) * a.ld];
+                        s0[k] += w * dm;
+                        s1[k] += w * dv;
+                        s2[k] += w * (c * dm);
+                    }
+            }
+#pragma unroll
+            for (int k = 0; k < AGG_DC; ++k)
+                if (k < nd) {
+                    om[(size_t)(d0 + k) * a.n_t] = s0[k];
+                    ov[(size_t)(d0 + k) * a.n_t] = a.plain ? s1[k] : s1[k] + 2.0 * s2[k];
+                }
+        } else if (a.family == AGG_RBCM) {
+            const KParam p = a.kp[a.prior_kid];
+            const double s = prior_var(p, a.Xt, r, a.n_t, D) + p.noise;
+            double C = 1.0 / s, m = 0.0, ds[AGG_DC], dC[AGG_DC], dm[AGG_DC];
+#pragma unroll
+            for (int k = 0; k < AGG_DC; ++k) {
+                double x = 0.0;
+                if (k < nd) x = a.Xt[r + (size_t)(d0 + k) * a.n_t];
+                ds[k] = k < nd ? (p.kind == 2 ? 2.0 * x / p.l2[0] : (p.kind == 3 ? 2.0 * x * p.nh[d0 + k] : 0.0)) : 0.0;
+                dC[k] = -(ds[k] / (s * s));
+                dm[k] = 0.0;
+            }
+            for (int g = 0; g < a.G; ++g) {
+                double T = 0.0, P = 0.0, dT[AGG_DC] = {}, dP[AGG_DC] = {};
+                for (int64_t e = e0; e < e1; ++e) {
+                    const int pos = a.row_ent[e];
+                    if (a.group[a.ent_leaf[pos]] != g) continue;
+                    const double v = a.var[pos], ml = mu[pos];
+                    const double t = 1.0 / v;
+                    P += t * ml;
+                    T += t;
+#pragma unroll
+                    for (int k = 0; k < AGG_DC; ++k)
+                        if (k < nd) {
+                            const double dv = a.dvar[pos + (size_t)(d0 + k) * a.ld];
+                            dT[k] -= (t / v) * dv;
+                            dP[k] += t * dmq[pos + (size_t)(d0 + k) * a.ld] - (t * ml / v) * dv;
+                        }
+                }
+                if (T == 0.0) continue;
+                const double beta = 0.5 * (log(s) + log(T));
+                C += beta * (T - 1.0 / s);
+                m += beta * P;
+#pragma unroll
+                for (int k = 0; k < AGG_DC; ++k) {
+                    const double dbeta = 0.5 * (ds[k] / s + dT[k] / T);
+                    dC[k] += dbeta * (T - 1.0 / s) + beta * (dT[k] + ds[k] / (s * s));
+                    dm[k] += dbeta * P + beta * dP[k];
+                }
+            }
+            const double mua = m / C;
+#pragma unroll
+            for (int k = 0; k < AGG_DC; ++k)
+                if (k < nd) {
+                    om[(size_t)(d0 + k) * a.n_t] = (dm[k] - mua * dC[k]) / C;
+                    ov[(size_t)(d0 + k) * a.n_t] = -dC[k] / (C * C);
+                }
+        } else {
+            double T = 0.0, P = 0.0, dT[AGG_DC] = {}, dP[AGG_DC] = {};
+            for (int64_t e = e0; e < e1; ++e) {
+                const int pos = a.row_ent[e];
+                const double v = a.var[pos], ml = mu[pos];
+                const double t = a.coef[a.ent_leaf[pos]] / v;
+                P += (a.coef[a.ent_leaf[pos]] * (1.0 / v)) * ml;
+                T += a.coef[a.ent_leaf[pos]] * (1.0 / v);
+#pragma unroll
+                for (int k = 0; k < AGG_DC; ++k)
+                    if (k < nd) {
+                        const double dv = a.dvar[pos + (size_t)(d0 + k) * a.ld];
+                        dT[k] -= (t / v) * dv;
+                        dP[k] += t * dmq[pos + (size_t)(d0 + k) * a.ld] - (t * ml / v) * dv;
+                    }
+            }
+            const double mua = P / T;
+#pragma unroll
+            for (int k = 0; k < AGG_DC; ++k)
+                if (k < nd) {
+                    om[(size_t)(d0 + k) * a.n_t] = (dP[k] - mua * dT[k]) / T;
+                    ov[(size_t)(d0 + k) * a.n_t] = -dT[k] / (T * T);
+                }
+        }
+    }
+}
+
 // Score sums (src/scorefunctions.jl:6-16) in two passes for the standard errors: pass 0 sums se, ae and the nlpd
 // terms; pass 1 sums (se - mean se)^2 and (ae - mean ae)^2.  Per-block tree reduction, blocks combined in block order
 // by the host: fixed summation order.

@@ -26,6 +26,14 @@ SCORE_NAMES = ("mse", "sse", "mae", "sae", "nlpd")
 def agg_width(family, n_groups=0):
     """Number of partial-sum vectors (of length n_t) the aggregation of a family exchanges."""
     return 3 if family == AGG_MIXTURE else (2 * int(n_groups) if family == AGG_RBCM else 2)
+
+
+def agg_gradients_width(family, n_groups, D):
+    """Number of gradient-sum vectors (of length n_t) `aggregate_gradients_partial` produces: D per moment sum of `agg_width`
+    (mixture: sum W dmu | sum W dvar' | sum W (mu_l - mu) dmu; PoE, gPoE: dT | dP; rBCM: dT_g | dP_g per group)."""
+    return agg_width(family, n_groups) * int(D)
+
+
 TIMING_NAMES = ("gram", "chol_update", "chol_diag", "chol_trsm", "solve", "mll", "predict_gram",
                 "predict_update", "predict_trsm", "predict_var", "gradients", "total_fit", "total_predict", "chol_reduce", "alpha",
                 "grad_inverse", "grad_contraction", "grad_traces", "chol_fused", "chol_update_union", "chol_fused_union")
@@ -76,6 +84,11 @@ SIGNATURES = {
     "dsmgp_aggregate": (C.c_int, [_ctx, C.c_int32, _dp, _ip, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]),
     "dsmgp_aggregate_partial": (C.c_int, [_ctx, C.c_int32, _dp, _ip, C.c_int32, _dp]),
     "dsmgp_aggregate_finish": (C.c_int, [_ctx, _dp, C.c_int32, C.c_int32, _dp, _dp]),
+    "dsmgp_aggregate_gradients_partial": (C.c_int, [_ctx, _dp, _dp]),
+    "dsmgp_aggregate_gradients_finish": (C.c_int, [_ctx, _dp, C.c_int32, C.c_int32, _dp, _dp, C.c_int64]),
+    "dsmgp_aggregate_gradients": (C.c_int, [_ctx, C.c_int32, C.c_int32, _dp, _dp, C.c_int64, _dp]),
+    "dsmgp_aggregate_columns": (C.c_int, [_ctx, C.c_int32, _dp, _ip, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_int64, _dp]),
+    "dsmgp_aggregate_columns_gradients": (C.c_int, [_ctx, C.c_int32, C.c_int32, _dp, _dp, C.c_int64, _dp]),
     "dsmgp_scores": (C.c_int, [_ctx, _dp, _dp]),
     "dsmgp_kernel_matrix": (C.c_int, [_ctx, C.c_int32, _dp, C.c_int64, _dp, C.c_int64, _dp]),
     "dsmgp_download_factor": (C.c_int, [_ctx, C.c_int32, _dp, _dp]),
@@ -210,6 +223,7 @@ class Context:
         self.n_t = 0
         self.leaf_n = np.zeros(0, dtype=np.int64)
         self.targets_Q = 0      # columns of the last solve_targets
+        self.agg_family, self.agg_groups = AGG_MIXTURE, 0      # of the last aggregate / aggregate_partial
 
     def _chk(self, rc):
         if rc != 0:
@@ -615,6 +629,7 @@ class Context:
         self._chk(self.lib.dsmgp_aggregate(self.h, int(family), pc, pg, int(n_groups), 1 if plain else 0, int(prior_kernel_id),
                                            mu.ctypes.data_as(_dp) if fetch else None,
                                            var.ctypes.data_as(_dp) if fetch else None))
+        self.agg_family, self.agg_groups = int(family), int(n_groups)
         return mu, var
 
     def aggregate_partial(self, family, leaf_coef=None, leaf_group=None, n_groups=0, fetch=True):
@@ -624,6 +639,7 @@ class Context:
         part = np.empty((agg_width(family, n_groups), self.n_t)) if fetch else None
         self._chk(self.lib.dsmgp_aggregate_partial(self.h, int(family), pc, pg, int(n_groups),
                                                    part.ctypes.data_as(_dp) if fetch else None))
+        self.agg_family, self.agg_groups = int(family), int(n_groups)
         return part
 
     def aggregate_finish(self, partial=None, plain=False, prior_kernel_id=0, fetch=True):
@@ -636,6 +652,74 @@ class Context:
                                                   mu.ctypes.data_as(_dp) if fetch else None,
                                                   var.ctypes.data_as(_dp) if fetch else None))
         return mu, var
+
+    # ---- input gradients of the aggregated prediction (dsmgp_aggregate_gradients*) ----
+    def aggregate_gradients(self, plain=False, prior_kernel_id=0, want_var=True):
+        """`(dmu, dvar)`, both `(n_t, D)` float64 in Fortran order: the gradients of the aggregated prediction of the last
+        `aggregate` / `aggregate_finish` with respect to the test point, reduced on the device from the per-entry gradients
+        (which are made first unless `predict_gradients()` left both halves for this prediction).  `want_var=False` returns
+        `(dmu, None)`, `dmu` the same bits.  The device time is left in `self.agg_gradients_seconds`."""
+        n = int(self.n_t)
+        dmu = np.empty((n, self.D), dtype=np.float64, order="F")
+        dvar = np.empty((n, self.D), dtype=np.float64, order="F") if want_var else None
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_aggregate_gradients(self.h, 1 if plain else 0, int(prior_kernel_id), dmu.ctypes.data_as(_dp),
+                                                     dvar.ctypes.data_as(_dp) if want_var else None, max(1, n), C.byref(sec)))
+        self.agg_gradients_seconds = sec.value
+        return dmu, dvar
+
+    def aggregate_gradients_partial(self, fetch=True):
+        """This context's gradient sums about the aggregated moments it holds, shape `(Wg, n_t)` (`agg_gradients_width`): what
+        contexts add once each of them has the total moments (`aggregate_finish(partial=total)`).  fetch=False: they stay on
+        the device."""
+        part = np.empty((agg_gradients_width(self.agg_family, self.agg_groups, self.D), self.n_t)) if fetch else None
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_aggregate_gradients_partial(self.h, part.ctypes.data_as(_dp) if fetch else None, C.byref(sec)))
+        self.agg_gradients_seconds = sec.value
+        return part
+
+    def aggregate_gradients_finish(self, partial=None, plain=False, prior_kernel_id=0, want_var=True):
+        """`(dmu, dvar)` from the context's own gradient sums, or from `partial`: the sums of all holders, added by the caller."""
+        pp = None
+        if partial is not None:
+            partial, pp = _f64(partial)
+            assert partial.size == agg_gradients_width(self.agg_family, self.agg_groups, self.D) * self.n_t
+        n = int(self.n_t)
+        dmu = np.empty((n, self.D), dtype=np.float64, order="F")
+        dvar = np.empty((n, self.D), dtype=np.float64, order="F") if want_var else None
+        self._chk(self.lib.dsmgp_aggregate_gradients_finish(self.h, pp, 1 if plain else 0, int(prior_kernel_id),
+                                                            dmu.ctypes.data_as(_dp),
+                                                            dvar.ctypes.data_as(_dp) if want_var else None, max(1, n)))
+        return dmu, dvar
+
+    # ---- the same for every column of the last solve_targets (dsmgp_aggregate_columns*) ----
+    def aggregate_columns(self, family, leaf_coef=None, leaf_group=None, n_groups=0, plain=False, prior_kernel_id=0):
+        """`(mu, var)`, both `(n_t, Q)` float64 in Fortran order: `aggregate` for every column of the last `solve_targets`
+        (needs `predict_run` and `solve_targets` on the current fit; the per-entry means are made on the device first unless
+        `predict_targets()` left them).  One coefficient per leaf serves all columns.  The device time is left in
+        `self.agg_columns_seconds`."""
+        coef, pc, grp, pg = self._agg_args(family, leaf_coef, leaf_group)
+        n, Q = int(self.n_t), int(self.targets_Q)
+        mu = np.empty((n, Q), dtype=np.float64, order="F")
+        var = np.empty((n, Q), dtype=np.float64, order="F")
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_aggregate_columns(self.h, int(family), pc, pg, int(n_groups), 1 if plain else 0, int(prior_kernel_id),
+                                                   mu.ctypes.data_as(_dp), var.ctypes.data_as(_dp), max(1, n), C.byref(sec)))
+        self.agg_columns_seconds = sec.value
+        return mu, var
+
+    def aggregate_columns_gradients(self, plain=False, prior_kernel_id=0):
+        """`(dmu, dvar)`, both `(n_t, D, Q)` float64 in Fortran order: `aggregate_gradients` for every column, with the family
+        and coefficients of the last `aggregate_columns` (needed first).  The device time is left in
+        `self.agg_columns_gradients_seconds`."""
+        n, Q = int(self.n_t), int(self.targets_Q)
+        dmu = np.empty((n, self.D, Q), dtype=np.float64, order="F")
+        dvar = np.empty((n, self.D, Q), dtype=np.float64, order="F")
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_aggregate_columns_gradients(self.h, 1 if plain else 0, int(prior_kernel_id), dmu.ctypes.data_as(_dp),
+                                                             dvar.ctypes.data_as(_dp), max(1, n), C.byref(sec)))
+        self.agg_columns_gradients_seconds = sec.value
+        return dmu, dvar
 
     def scores(self, y_test):
         """dict(mse, sse, mae, sae, nlpd) of the aggregated prediction still on the device."""
@@ -994,7 +1078,22 @@ class MultiContext:
         for s, sub in zip(self.act, self.subsets):
             p = s.aggregate_partial(family, None if coef is None else coef[sub.loc], None if grp is None else grp[sub.loc], n_groups)
             tot = p if tot is None else tot + p
+        self._agg_total = tot
         return tot
+
+    def aggregate_gradients(self, plain=False, prior_kernel_id=0):
+        """`(dmu, dvar)`, both `(n_t, D)`: `Context.aggregate_gradients` for leaves spread over the sub-contexts, after
+        `aggregate_partial`.  The total moment sums go to every sub-context (`aggregate_finish(partial=total)`), whose
+        gradient sums are then additive; they are added in context order and the first sub-context finishes the total."""
+        if getattr(self, "_agg_total", None) is None:
+            raise DsmgpError(E_STATE, "aggregate_gradients before aggregate_partial")
+        for s in self.act:
+            s.aggregate_finish(self._agg_total, plain=plain, prior_kernel_id=prior_kernel_id, fetch=False)
+        tot = None
+        for p in self._each(lambda s: s.aggregate_gradients_partial()):
+            tot = p if tot is None else tot + p
+        self.agg_gradients_seconds = max(s.agg_gradients_seconds for s in self.act)
+        return self.act[0].aggregate_gradients_finish(tot, plain=plain, prior_kernel_id=prior_kernel_id)
 
     def set_gradient_leaves(self, active=None):
         self._upload()

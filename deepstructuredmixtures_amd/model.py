@@ -1438,16 +1438,28 @@ def _prior_diag_grad(lf, xt):
     return np.zeros(xt.shape)
 
 
-def predict_gradients(model, xtest):
+def _check_aggregate(what, aggregate):
+    if aggregate not in ("host", "device"):
+        raise ValueError(f'{what}: aggregate must be "host" or "device", not {aggregate!r}')
+
+
+def predict_gradients(model, xtest, aggregate="host"):
     """(mu, var, dmu, dvar): `predict(model, xtest)` -- the same bits -- and the gradients of both moments with respect to
     the test point, `dmu`, `dvar` of shape (n_t, D), for a DSMGP, PoE, gPoE, rBCM or a single GaussianProcess (no reference
     counterpart).  The per-(leaf, row) gradients come from the device (`Context.predict_gradients`), the aggregation runs on
-    the host (`aggregate_input_gradients`).  The tree is piecewise constant in x -- which leaves a row reaches changes only
+    the host (`aggregate_input_gradients`) or, with `aggregate="device"`, on the device (`Context.aggregate_gradients`: no
+    per-entry array is fetched and no entry list is built; the result agrees with the host's to rounding, not to the bit).
+    The tree is piecewise constant in x -- which leaves a row reaches changes only
     at a split threshold, where the prediction itself jumps -- so the result is the gradient inside the row's region.
     Refused: a DSMGP whose sum weights are not normalised (ValueError: `predict` then shifts the means by mu_min - 1, which
     is not differentiable), a model sharded over several ranks (NotImplementedError), and contexts that do not keep what the
     device call reads (the streaming context: DsmgpError)."""
+    _check_aggregate("predict_gradients", aggregate)
     if isinstance(model, GaussianProcess):
+        if aggregate == "device":       # the one-leaf table as a plain mixture (a clamped variance is a constant: dvar = 0 there)
+            mu, var = predict(model, xtest)
+            _, _, dmu, dvar = predict_gradients(model.model, xtest, aggregate="device")
+            return mu, var, dmu, dvar
         mu, var, dmu, dvar = prediction(model, xtest, input_gradients=True)
         return mu, np.where(var <= 0, EPS, var), np.ascontiguousarray(dmu), np.ascontiguousarray(dvar)
     if model.shard.world > 1:
@@ -1464,7 +1476,14 @@ def predict_gradients(model, xtest):
     n_t, D = xt.shape
     if n_t == 0:
         return np.zeros(0), np.zeros(0), np.zeros((0, D)), np.zeros((0, D))
+    if aggregate == "device" and not hasattr(_ctx_type(model), "aggregate_gradients"):
+        raise NotImplementedError(f"predict_gradients: {_ctx_type(model).__name__} has no aggregate_gradients")
     mu, var = predict(model, xt)            # routes, registers and runs as predict does; the moments stay on the device
+    if aggregate == "device":               # ... and so do their sums: the gradients are reduced beside them
+        _, _, _, _, plain, prior = _aggregation_spec(model)
+        dmu, dvar = model.ctx.aggregate_gradients(plain=plain, prior_kernel_id=prior.kernelid if prior else 0)
+        model.last_agg_gradients_seconds = model.ctx.agg_gradients_seconds
+        return mu, var, np.ascontiguousarray(dmu), np.ascontiguousarray(dvar)
     rc = _routing(model, xt)                # the host's lists: entry by entry those of a context that routed the rows itself
     ptr, idx = rc["lptr"], rc["lidx"]
     mu_l, var_l = model.ctx.predict_fetch()
@@ -1545,7 +1564,19 @@ def _aggregate_host(model, xt, rc, mu, var):
     return _aggregate_poe(model, xt, rc["ptr"], mu, var)
 
 
-def predict_targets(model, xtest):
+def _columns_device(model, target, what):
+    """The context and the arguments of `Context.aggregate_columns` for `aggregate="device"`, after the refusals."""
+    if target.family == "dsmgp" and target.root.kind != "gp" and not target.tindex.weights_normalised():
+        raise ValueError(f"{what}: the sum weights are not normalised; the device aggregates the flat mixture only")
+    if issubclass(_ctx_type(target), hipabi.StreamingContext):
+        raise hipabi.DsmgpError(hipabi.E_STATE, f"{what}: a streaming context discards what the device aggregation reads")
+    if not hasattr(_ctx_type(target), "aggregate_columns"):
+        raise NotImplementedError(f"{what}: {_ctx_type(target).__name__} has no aggregate_columns (a single Context only)")
+    family, coef, group, G, plain, prior = _aggregation_spec(target)
+    return dict(family=family, leaf_coef=coef, leaf_group=group, n_groups=G, plain=plain, prior_kernel_id=prior.kernelid if prior else 0)
+
+
+def predict_targets(model, xtest, aggregate="host"):
     """`(mu, var)`, both `(n_t, Q)`: `predict(model, xtest)` for every target column of the last `fit_targets` (no reference
     counterpart).  The per-(leaf, row) means of all columns come from the device (`Context.predict_targets`, on the `K_tn L^-T`
     of `predict`'s own sweep); the leaf variances do not depend on the targets.  The aggregation runs on the host, column by
@@ -1553,14 +1584,20 @@ def predict_targets(model, xtest):
     rule of `predict`.  The sum-node weights are the ones the model holds -- those of its own `y`: this function does NOT
     re-weigh per column (the `mll` table of `fit_targets` is there for callers who want to).  The mixture variance depends on
     the column through `sum W mu^2 - mu^2`; the product-of-experts variances are the same in every column."""
+    _check_aggregate("predict_targets", aggregate)
     target = _targets_model(model, "predict_targets")
     xt = _test_matrix(target, xtest)
+    kw = _columns_device(model, target, "predict_targets") if aggregate == "device" else None
     Q = int(getattr(target.ctx, "targets_Q", 0))
     if Q < 1:
         raise hipabi.DsmgpError(hipabi.E_STATE, "predict_targets before fit_targets")
     n_t = xt.shape[0]
     if n_t == 0:
         return np.zeros((0, Q)), np.zeros((0, Q))
+    if kw is not None:      # with `aggregate="device"`: the moments of every column in one call, nothing per entry is fetched
+        predict(target, xt)         # routes, registers and runs as predict does
+        mu, var = target.ctx.aggregate_columns(**kw)
+        return np.ascontiguousarray(mu), np.ascontiguousarray(var)
     rc = _routing(target, xt)
     _, var_l = _leaf_moments(target, xt, rc)
     mu_l = target.ctx.predict_targets()
@@ -1574,7 +1611,7 @@ def predict_targets(model, xtest):
     return mu, var
 
 
-def predict_targets_gradients(model, xtest):
+def predict_targets_gradients(model, xtest, aggregate="host"):
     """`(mu, var, dmu, dvar)`: `predict_targets(model, xtest)` -- `mu`, `var` of shape `(n_t, Q)` -- and the gradients of both
     moments with respect to the test point for every target column of the last `fit_targets`, `dmu`, `dvar` of shape
     `(n_t, Q, D)`: `dmu[t]` is the Jacobian of the vector-valued predictive mean at row t (no reference counterpart).  The
@@ -1583,6 +1620,7 @@ def predict_targets_gradients(model, xtest):
     from `Context.predict_gradients`; the aggregation runs on the host, column by column (`aggregate_input_gradients`).  The
     mixture variance depends on the column through the means, so `dvar` differs per column for a DSMGP; it is the same in every
     column for PoE, gPoE, rBCM and a single GaussianProcess.  Refused: what `predict_gradients` and `predict_targets` refuse."""
+    _check_aggregate("predict_targets_gradients", aggregate)
     target = _targets_model(model, "predict_targets_gradients")
     if target.family == "dsmgp" and target.root.kind != "gp" and not target.tindex.weights_normalised():
         raise ValueError("predict_targets_gradients: the sum weights are not normalised; predict then shifts the means by "
@@ -1598,6 +1636,11 @@ def predict_targets_gradients(model, xtest):
         raise hipabi.DsmgpError(hipabi.E_STATE, "predict_targets_gradients before fit_targets")
     if n_t == 0:
         return np.zeros((0, Q)), np.zeros((0, Q)), np.zeros((0, Q, D)), np.zeros((0, Q, D))
+    if aggregate == "device":               # (n_t, D, Q) from the device -> (n_t, Q, D); no per-entry array, no entry list
+        kw = _columns_device(model, target, "predict_targets_gradients")
+        mu, var = predict_targets(model, xt, aggregate="device")
+        dmu, dvar = target.ctx.aggregate_columns_gradients(plain=kw["plain"], prior_kernel_id=kw["prior_kernel_id"])
+        return mu, var, np.ascontiguousarray(dmu.transpose(0, 2, 1)), np.ascontiguousarray(dvar.transpose(0, 2, 1))
     mu, var = predict_targets(model, xt)    # routes, registers and runs as predict does; K_tn L^-T stays on the device
     rc = _routing(target, xt)
     ptr, idx = rc["lptr"], rc["lidx"]

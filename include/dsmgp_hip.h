@@ -466,6 +466,61 @@ int dsmgp_aggregate_partial(dsmgp_ctx* ctx, int32_t family, const double* leaf_c
                             int32_t n_groups, double* partial_out /* W x n_t or NULL */);
 int dsmgp_aggregate_finish(dsmgp_ctx* ctx, const double* partial_in /* NULL: the context's own sums */, int32_t plain,
                            int32_t prior_kernel_id, double* mu_out, double* var_out);
+/* ---- Input gradients of the aggregated prediction: d mu / d x and d var / d x of predict(model, x) per test row, from the
+ *      per-entry gradients of dsmgp_predict_gradients without leaving HBM (no reference counterpart; the tree is piecewise
+ *      constant in x, so this is the gradient inside the row's region).  Family, leaf_coef and leaf_group are those of the last
+ *      dsmgp_aggregate_partial.  Needs the aggregated moments of the current prediction, dsmgp_aggregate or
+ *      dsmgp_aggregate_finish (DSMGP_E_STATE otherwise, and again after a later dsmgp_fit, dsmgp_set_hyper, dsmgp_predict_run,
+ *      dsmgp_aggregate_partial or dsmgp_aggregate_finish).  The per-entry gradients are read where both halves are this
+ *      prediction's already (a dsmgp_predict_gradients with dvar_out); otherwise the device part of that call runs first.
+ *      A dsmgp_predict_gradients with dvar_out writes them again: between dsmgp_aggregate_gradients_partial and _finish it
+ *      makes the sums stale (DSMGP_E_STATE from _finish until the partial call has run again).
+ *        mixture   dmu = sum W dmu_l, dvar = sum W dvar'_l + 2 sum W (mu_l - mu) dmu_l (plain: the first sum alone); dvar'_l = 0
+ *                  where the moments clamp the leaf variance (sigma2_l <= 0).  The second sum is centred on the aggregated mean.
+ *        PoE/gPoE  T = sum beta / sigma2_l, P = sum beta mu_l / sigma2_l; dT = -sum beta dvar_l / sigma2_l^2,
+ *                  dP = sum beta (dmu_l / sigma2_l - mu_l dvar_l / sigma2_l^2); dmu = (dP - mu dT) / T, dvar = -dT / T^2
+ *        rBCM      per group g that saw the row T_g, P_g, dT_g, dP_g with beta = 1; s = k(x, x) + noise of prior_kernel_id,
+ *                  ds/dx_d = 2 x_d / l_d^2 for the linear kinds and 0 for the others; beta_g = (log s + log T_g) / 2,
+ *                  dbeta_g = (ds / s + dT_g / T_g) / 2; C = 1 / s + sum_g beta_g (T_g - 1 / s), m = sum_g beta_g P_g,
+ *                  dC = -ds / s^2 + sum_g [dbeta_g (T_g - 1 / s) + beta_g (dT_g + ds / s^2)], dm = sum_g (dbeta_g P_g + beta_g dP_g);
+ *                  dmu = (dm - mu dC) / C, dvar = -dC / C^2
+ *      dsmgp_aggregate_gradients = partial + finish on one context.  The sums are Wg x n_t in [k][row] planes, Wg = 3 D
+ *      (mixture: sum W dmu_d | sum W dvar'_d | sum W (mu_l - mu) dmu_d), 2 D (PoE, gPoE: dT_d | dP_d) or 2 n_groups D (rBCM:
+ *      per group dT_gd | dP_gd).  With leaves spread over contexts the caller first hands the TOTAL moment sums to every holder
+ *      (dsmgp_aggregate_finish with partial_in); after that the holders' gradient sums are additive: the caller adds them and
+ *      hands the total to dsmgp_aggregate_gradients_finish of one holder.  dmu_out / dvar_out: n_t x D column-major, ld >= n_t
+ *      (DSMGP_E_ARG otherwise); either may be NULL, the other is the same bits.  A row's entries are added in ascending entry
+ *      order by one thread: the same bits from call to call.  A row that reaches a failed leaf gets NaN, the others are not
+ *      affected; a row without entries gets what the formulas give.  `seconds` (may be NULL): the device time of the
+ *      partial-sum kernel (the finish kernel is not timed), with that of the per-entry gradients where they had to be made.
+ *      partial_in is written over the context's own sums: a later finish with NULL on that holder finishes the same total.  The buffers are allocated on first use and are not part
+ *      of dsmgp_estimate_bytes / dsmgp_memory; DSMGP_E_NOMEM leaves the context usable.  dsmgp_predict_fetch,
+ *      dsmgp_predict_gradients, dsmgp_aggregate* and dsmgp_scores return the same bits before and after. */
+int dsmgp_aggregate_gradients_partial(dsmgp_ctx* ctx, double* partial_out /* Wg x n_t, may be NULL */, double* seconds);
+int dsmgp_aggregate_gradients_finish(dsmgp_ctx* ctx, const double* partial_in /* NULL: the context's own sums */, int32_t plain,
+                                     int32_t prior_kernel_id, double* dmu_out, double* dvar_out, int64_t ld);
+int dsmgp_aggregate_gradients(dsmgp_ctx* ctx, int32_t plain, int32_t prior_kernel_id, double* dmu_out, double* dvar_out,
+                              int64_t ld, double* seconds);
+/* ---- The same two aggregations for every column of the last dsmgp_solve_targets, on one context (no partial / finish split).
+ *      dsmgp_aggregate_columns is dsmgp_aggregate per column: mu_out / var_out are n_t x Q column-major, ld >= n_t (DSMGP_E_ARG
+ *      otherwise), either may be NULL.  Needs BOTH dsmgp_solve_targets and dsmgp_predict_run on the CURRENT fit (DSMGP_E_STATE
+ *      otherwise); the per-entry means of the columns are read where dsmgp_predict_targets left them for this prediction and
+ *      these columns, otherwise the device part of that call runs first.  One coefficient per leaf serves all columns; the leaf
+ *      variance is shared, so var_out differs per column only for the mixture.
+ *      dsmgp_aggregate_columns_gradients needs dsmgp_aggregate_columns on the current prediction and columns (DSMGP_E_STATE
+ *      otherwise) and uses its family, coefficients and groups; dmu_out / dvar_out hold element [r + d*ld + q*ld*D], ld >= n_t.
+ *      It reads dmu of dsmgp_predict_columns_gradients and dvar of dsmgp_predict_gradients, running either device part when it
+ *      is not current.  Formulas, clamps, skipped groups, NaN rows and rows without entries: as for the single y above.
+ *      One thread per (test row, column) adds the row's entries in ascending entry order and never reads another column: the
+ *      same bits from call to call, and column q is the same bits whatever Q is and whatever the other columns hold.  The state
+ *      of these calls is their own: dsmgp_aggregate_finish, dsmgp_aggregate_gradients* and dsmgp_scores answer as before (a
+ *      dsmgp_predict_gradients device part that had to run makes gradient SUMS stale, as said above).  Buffers: on first use,
+ *      not part of dsmgp_estimate_bytes / dsmgp_memory.  `seconds` (may be NULL): the aggregation kernel plus the device
+ *      parts that had to run. */
+int dsmgp_aggregate_columns(dsmgp_ctx* ctx, int32_t family, const double* leaf_coef, const int32_t* leaf_group, int32_t n_groups,
+                            int32_t plain, int32_t prior_kernel_id, double* mu_out, double* var_out, int64_t ld, double* seconds);
+int dsmgp_aggregate_columns_gradients(dsmgp_ctx* ctx, int32_t plain, int32_t prior_kernel_id, double* dmu_out, double* dvar_out,
+                                      int64_t ld, double* seconds);
 /* ---- score functions of src/scorefunctions.jl:6-16 on the aggregated prediction still in HBM:
  *      out[5] = { mse, sse (std(se)/sqrt(n)), mae, sae, nlpd } */
 int dsmgp_scores(dsmgp_ctx* ctx, const double* y_test /* n_t */, double* out /* 5 */);

@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, append_rows!, append_stats, resume_stats, download_vt, predict_cov, predict_gradients, loo, loo_gradients, solve_targets, predict_targets, predict_targets_gradients, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
+export attach!, detach!, census, append_rows!, append_stats, resume_stats, download_vt, predict_cov, predict_gradients, aggregate_gradients, aggregate_columns, aggregate_columns_gradients, loo, loo_gradients, solve_targets, predict_targets, predict_targets_gradients, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -205,6 +205,7 @@ mutable struct Session
     census::Dict{Symbol,Any}
     fitted::Bool
     targets::Int                           # columns of the last solve_targets (0: none)
+    testnt::Int                            # rows of the registered test set
 end
 
 const SESSIONS = IdDict{Any,Session}()     # root node (or GaussianProcess) -> session
@@ -218,7 +219,7 @@ function newsession(device::Integer)
     rc = ccall(sym(:dsmgp_create), Cint, (Int32, Ref{Ptr{Cvoid}}), Int32(device), r)
     rc == 0 || error("dsmgp_create: " * lasterror(C_NULL))        # no GPU: the path has no CPU fallback
     s = Session(r[], GPNode[], GaussianProcess[], IdDict{Any,Int}(), Float64[], Int32[], zeros(0, 0), 0, UInt(0), Int64[],
-                Dict{Symbol,Any}(), false, 0)
+                Dict{Symbol,Any}(), false, 0, 0)
     finalizer(x -> (x.h != C_NULL && ccall(sym(:dsmgp_destroy), Cint, (Ptr{Cvoid},), x.h); x.h = C_NULL), s)
     return s
 end
@@ -522,6 +523,53 @@ function predict_gradients(s::Session; want_var::Bool=true)
     return dmu, dvar
 end
 
+"aggregate_gradients(s; plain=false, prior_kernel_id=0): the gradients of the aggregated prediction of the last `predict` with
+respect to the test point, reduced on the device over the leaves of every registered test row (dsmgp_aggregate_gradients; family,
+coefficients and groups are those of that prediction's dsmgp_aggregate).  Returns (dmu, dvar), both `n_t × D`.  `plain` is true for
+a model whose root is a single GP; `prior_kernel_id` is the zero-based kernel id of the first leaf of an rBCM.  The per-entry
+gradients are made on the device first unless `predict_gradients(s)` left them for this prediction."
+function aggregate_gradients(s::Session; plain::Bool=false, prior_kernel_id::Integer=0)
+    nt = s.testnt
+    D = size(s.gps[1].x, 2)
+    dmu = Matrix{Float64}(undef, nt, D)
+    dvar = Matrix{Float64}(undef, nt, D)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve dmu dvar chk(s, ccall(sym(:dsmgp_aggregate_gradients), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Float64}),
+        s.h, Int32(plain), Int32(prior_kernel_id), dmu, dvar, Int64(max(nt, 1)), sec))
+    return dmu, dvar
+end
+
+"aggregate_columns(s, family, coef, group, G; plain=false, prior_kernel_id=0): `dsmgp_aggregate` for every column of the last
+`solve_targets` on the prediction of the registered rows (dsmgp_aggregate_columns).  `coef` (length L, or `nothing` for an rBCM)
+and `group` (zero-based root child per leaf, or `nothing`) serve all columns.  Returns (mu, var), both `n_t × Q`."
+function aggregate_columns(s::Session, family::Integer, coef, group, G::Integer; plain::Bool=false, prior_kernel_id::Integer=0)
+    nt, Q = s.testnt, s.targets
+    μ = Matrix{Float64}(undef, nt, Q); σ² = similar(μ)
+    cf = coef === nothing ? nothing : Vector{Float64}(coef)
+    gr = group === nothing ? nothing : Vector{Int32}(group)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve cf gr μ σ² chk(s, ccall(sym(:dsmgp_aggregate_columns), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int32}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Float64}),
+        s.h, Int32(family), cf === nothing ? Ptr{Float64}(C_NULL) : pointer(cf), gr === nothing ? Ptr{Int32}(C_NULL) : pointer(gr),
+        Int32(G), Int32(plain), Int32(prior_kernel_id), μ, σ², Int64(max(nt, 1)), sec))
+    return μ, σ²
+end
+
+"aggregate_columns_gradients(s; plain=false, prior_kernel_id=0): the input gradients of `aggregate_columns`' moments, with its
+family and coefficients (dsmgp_aggregate_columns_gradients; `aggregate_columns` first).  Returns (dmu, dvar), both `n_t × D × Q`."
+function aggregate_columns_gradients(s::Session; plain::Bool=false, prior_kernel_id::Integer=0)
+    nt, Q = s.testnt, s.targets
+    D = size(s.gps[1].x, 2)
+    dmu = Array{Float64,3}(undef, nt, D, Q)
+    dvar = Array{Float64,3}(undef, nt, D, Q)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve dmu dvar chk(s, ccall(sym(:dsmgp_aggregate_columns_gradients), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Float64}),
+        s.h, Int32(plain), Int32(prior_kernel_id), dmu, dvar, Int64(max(nt, 1)), sec))
+    return dmu, dvar
+end
+
 "loo_gradients(s): the true derivatives of every leaf's LOO log predictive density with respect to its log-scale hyper-vector
 (GPML §5.4.2, eq. 5.13; dsmgp_loo_gradients), mean held fixed.  Returns (g, lpd): `g[:, l]` in the order [∂ℓ…, ∂σ, ∂ϵ] of
 updategradients! for leaf `l` of `s.leaves` (every component the true derivative: no factor σ for IsoSE, true length-scale
@@ -768,6 +816,7 @@ function settest!(s::Session, x::Matrix{Float64}, rows::Dict{Symbol,Vector{Int}}
                                         s.h, x, size(x, 1), size(x, 2), ptr, idx))
     s.testkey = key
     s.testptr = ptr
+    s.testnt = size(x, 1)
 end
 
 "Register the test rows of a DSMGP and let the device route them (dsmgp_set_test_routed: one thread per row walks the tree
@@ -780,6 +829,7 @@ function settestrouted!(s::Session, x::Matrix{Float64})
     GC.@preserve ptr chk(s, ccall(sym(:dsmgp_routes), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), s.h, ptr, C_NULL))
     s.testkey = key
     s.testptr = ptr
+    s.testnt = size(x, 1)
 end
 
 function aggregate(s::Session, family::Int32, coef, group, G::Integer, plain::Bool, priorkid::Integer, nt::Integer)
