@@ -9,7 +9,7 @@ enum Product : uint32_t {
     P_PLAN = 1u << 0, P_PHASE = 1u << 1, P_TEST = 1u << 2, P_JOINT = 1u << 3, P_FIT = 1u << 4, P_ALPHA = 1u << 5, P_DINV = 1u << 6,
     P_VT = 1u << 7, P_PRED = 1u << 8, P_PARTIAL = 1u << 9, P_TOTAL = 1u << 10, P_DONE = 1u << 11, P_GRAD_LISTS = 1u << 12,
     P_XINV = 1u << 13, P_LOO_LISTS = 1u << 14, P_LG_LISTS = 1u << 15, P_TG_LISTS = 1u << 16, P_Z = 1u << 17, P_RTREE = 1u << 18,
-    P_PGRAD = 1u << 19, P_GSUMS = 1u << 20, P_TMU = 1u << 21, P_TIG = 1u << 22, P_CDONE = 1u << 23,
+    P_PGRAD = 1u << 19, P_GSUMS = 1u << 20, P_TMU = 1u << 21, P_TIG = 1u << 22, P_CDONE = 1u << 23, P_SAMPLE = 1u << 24,
 };
 struct Row { Product product; const char* name; uint32_t parents; };
 
@@ -42,6 +42,7 @@ constexpr Row TABLE[] = {
     {P_TMU,        "column_means", P_PRED | P_Z},        // content of TestProducts: the means of every resident column per routed row (d_tmu)
     {P_TIG,        "column_mean_gradients", P_PRED | P_Z},   // content of TestProducts: their input gradients (d_tigout)
     {P_CDONE,      "column_moments", P_TMU},             // content of TestProducts: the aggregated moments of the columns (col_family / col_G describe them)
+    {P_SAMPLE,     "sample_factors", P_PRED},            // content of TestProducts: chol(Sigma_l + jitter I) of every leaf (sample_noise / sample_jitter tag them)
 };
 constexpr int N_PRODUCTS = (int)(sizeof(TABLE) / sizeof(TABLE[0]));
 

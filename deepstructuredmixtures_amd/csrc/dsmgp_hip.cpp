@@ -8,6 +8,7 @@
 #include "kernels.hpp"
 #include "kernels_fused.hpp"
 #include "kernels_targets.hpp"
+#include "kernels_sample.hpp"
 #include "ctx_state.hpp"
 #include "dev_owner.hpp"
 
@@ -567,6 +568,22 @@ struct TestProducts {
     bool sweep_resumed = false;     // psweep / pgram skip block steps (built from vt_first): rebuilt from block 0 when next needed
     DevArena arenaCov;              // ntpad x ntpad of the leaf dsmgp_predict_cov was last asked for (grow-only, from the pool when there is one)
     DevBuf<PredCovTask> pcov;       // its lower tiles, rebuilt per call
+    // joint draws (dsmgp_predict_sample, kernels_sample.hpp).  P_SAMPLE: arenaSample holds chol(Sigma_l + jitter I) of every leaf with
+    // routed rows for the tag (sample_noise, sample_jitter); the lists are rebuilt per factorisation, the draw's per call
+    DevArena arenaSample;           // ntpad x ntpad per leaf with routed rows, at sample_off (grow-only, from the pool when there is one)
+    DevArena arenaSampleDinv;       // the inverted diagonal blocks of the block steps, ntpad x 128 per leaf (scratch of the factorisation)
+    std::vector<size_t> sample_off; // per leaf: offset of its factor in arenaSample
+    std::vector<int32_t> sample_info;       // per leaf: 0, the first bad minor, or -1 (the flags of the current factors)
+    int sample_noise = 0;
+    double sample_jitter = 0.0;
+    double sample_seconds[3] = {0.0, 0.0, 0.0};     // device seconds of the last call: Sigma, factorisation (0, 0: the factors were current), draws
+    DevBuf<PredCovTask> scov;       // the lower tiles of every Sigma_l
+    DevBuf<TileTask> supd, strsm;   // the block steps: step k's tasks are [s*_off[k], s*_off[k + 1])
+    DevBuf<TileTask> sres, strsm2, sadd;    // the refinement of a step's panel solves, task for task beside strsm
+    DevBuf<DiagTask> sdiag;
+    DevBuf<int> d_sinfo;            // L flags
+    DevBuf<SampleDrawTask> sdraw;   // (row tile, 16 columns) pairs
+    DevBuf<double> d_seps, d_sout;  // the staged normals and the draws, route_total x S rounded up to 16 (ld = route_total)
     // input gradients of the predictive moments (dsmgp_predict_gradients): lists rebuilt per call
     DevArena arenaB;                // B = Vt L^-1 (rows K_y^-1 k_t), ntpad x npad per leaf with routed rows, laid out like arenaVt (grow-only,
                                     //   from the pool when there is one)
@@ -617,6 +634,21 @@ struct TestProducts {
         resume_armed = sweep_resumed = false;
         arenaCov.put();
         pcov.drop(keep);
+        arenaSample.put();
+        arenaSampleDinv.put();
+        sample_off.clear();
+        sample_info.clear();
+        scov.drop(keep);
+        supd.drop(keep);
+        strsm.drop(keep);
+        sres.drop(keep);
+        strsm2.drop(keep);
+        sadd.drop(keep);
+        sdiag.drop(keep);
+        d_sinfo.drop(keep);
+        sdraw.drop(keep);
+        d_seps.drop(keep);
+        d_sout.drop(keep);
         arenaB.put();
         pgbeta.drop(keep);
         pgtasks.drop(keep);
@@ -3852,6 +3884,284 @@ int dsmgp_predict_cov(dsmgp_ctx* c, int32_t leaf, int32_t with_noise, double* Si
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
     if (seconds) *seconds = ms * 1e-3;
+    return 0;
+}
+
+// Joint draws of every leaf over its routed rows (kernels_sample.hpp): out = mu + chol(Sigma_l + jitter I) eps_l.
+namespace {
+// The factors of every leaf with routed rows for (with_noise, jitter): Sigma in one launch, then one round of launches per block
+// step for all leaves that still have it.  Leaves whose fit failed get the flag -1 and no task.  Marks P_SAMPLE.
+int sample_factorise(dsmgp_ctx* c, int with_noise, double jitter, hipEvent_t after_sigma) {
+    c->invalidate(P_SAMPLE);
+    const int L = c->L;
+    std::vector<int32_t> finfo((size_t)L);
+    if (int rc = fetch_fit_results(c, nullptr, finfo.data())) return rc;
+    c->sample_off.assign((size_t)L, 0);
+    std::vector<size_t> doff((size_t)L, 0);
+    size_t ftot = 0, dtot = 0;
+    int maxnb = 0;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.nt == 0) continue;
+        c->sample_off[(size_t)l] = ftot;
+        doff[(size_t)l] = dtot;
+        ftot += (size_t)lf.ntpad * lf.ntpad;
+        dtot += (size_t)lf.ntpad * TB;
+        maxnb = std::max(maxnb, lf.ntpad / TB);
+    }
+    // behind the inverted diagonal blocks: -I, and one scratch tile per panel solve of the widest step (step 0)
+    size_t nsolve0 = 0;
+    for (int l = 0; l < L; ++l)
+        if (c->leaves[l].nt > 0) nsolve0 += (size_t)(c->leaves[l].ntpad / TB - 1);
+    const size_t negi_off = dtot, scratch_off = dtot + (size_t)TB * TB;
+    const size_t wtot = scratch_off + nsolve0 * TB * TB;
+    if (int rc = arena_status(c, c->arenaSample.grow(arena_pool(c), ftot))) return rc;
+    if (int rc = arena_status(c, c->arenaSampleDinv.grow(arena_pool(c), wtot))) return rc;
+    if (int rc = c->d_sinfo.grow(c, (size_t)L)) return rc;
+    std::vector<int> flags((size_t)L, 0);
+    std::vector<PredCovTask> cov;
+    std::vector<TileTask> upd, trsm, res, trsm2, add;
+    std::vector<DiagTask> diag;
+    std::vector<int> upd_off((size_t)maxnb + 1, 0), trsm_off((size_t)maxnb + 1, 0), diag_off((size_t)maxnb + 1, 0);
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.nt == 0) continue;
+        if (finfo[(size_t)l] != 0) {
+            flags[(size_t)l] = -1;
+            continue;
+        }
+        const LeafDev& d = c->h_leaves[l];
+        const int ntp = lf.ntpad, nbt = ntp / TB;
+        double* F = c->arenaSample.p + c->sample_off[(size_t)l];
+        for (int i = 0; i < nbt; ++i)
+            for (int j = 0; j <= i; ++j) {      // dsmgp_predict_cov's tasks, into the leaf's part of the factor arena
+                PredCovTask g{};
+                g.gemm.A = d.Vt + (size_t)i * TB;
+                g.gemm.B = d.Vt + (size_t)j * TB;
+                g.gemm.C = F + (size_t)i * TB + (size_t)j * TB * ntp;
+                g.gemm.lda = g.gemm.ldb = g.gemm.ldc = ntp;
+                g.gemm.k0 = 0;
+                g.gemm.k1 = lf.n - lf.n % KC2;
+                g.Ct = g.gemm.C;
+                g.xa = d.Xtg + (size_t)i * TB;
+                g.xb = d.Xtg + (size_t)j * TB;
+                g.ldx = ntp;
+                g.na = std::min(TB, lf.nt - i * TB);
+                g.nb = std::min(TB, lf.nt - j * TB);
+                g.diag = (i == j);
+                g.kid = lf.kid;
+                g.n = lf.n;
+                g.with_noise = with_noise ? 1 : 0;
+                cov.push_back(g);
+            }
+    }
+    for (int k = 0; k < maxnb; ++k) {
+        for (int l = 0; l < L; ++l) {
+            const LeafHost& lf = c->leaves[l];
+            const int ntp = lf.ntpad, nbt = ntp / TB;
+            if (lf.nt == 0 || flags[(size_t)l] != 0 || k >= nbt) continue;
+            double* F = c->arenaSample.p + c->sample_off[(size_t)l];
+            double* Dk = c->arenaSampleDinv.p + doff[(size_t)l] + (size_t)k * TB * TB;
+            if (k > 0)
+                for (int i = k; i < nbt; ++i) {     // F[i, k] -= F[i, 0:k] F[k, 0:k]^T, the whole K range in one task
+                    TileTask t{};
+                    t.A = F + (size_t)i * TB;
+                    t.B = F + (size_t)k * TB;
+                    t.C = F + (size_t)i * TB + (size_t)k * TB * ntp;
+                    t.lda = t.ldb = t.ldc = ntp;
+                    t.k0 = 0;
+                    t.k1 = k * TB;
+                    t.update = 1;
+                    t.sym = (i == k) ? 1 : 0;
+                    upd.push_back(t);
+                }
+            DiagTask dt{};
+            dt.T = F + (size_t)k * TB + (size_t)k * TB * ntp;
+            dt.Dinv = Dk;
+            dt.info = c->d_sinfo.p + l;
+            dt.ld = ntp;
+            dt.nvalid = std::min(TB, lf.nt - k * TB);
+            dt.row0 = k * TB;
+            diag.push_back(dt);
+            // The panel solve X = B L_kk^-T of tile B = F[i, k] multiplies with the explicit inverse, whose error grows with the
+            // condition of L_kk (Sigma + 1e-8 I without noise: 4e-15 of ||A|| where a substitution leaves 3e-16), so it takes one
+            // step of refinement, each a launch of the existing kernels over the step's tiles:
+            //   S = B Dinv_k^T;   B <- B - S L_kk^T (the residual);   B <- B Dinv_k^T (the correction);   B <- B + S (as B - S (-I)^T)
+            for (int i = k + 1; i < nbt; ++i) {
+                double* tile = F + (size_t)i * TB + (size_t)k * TB * ntp;
+                double* S = c->arenaSampleDinv.p + scratch_off + (trsm.size() - (size_t)trsm_off[(size_t)k]) * TB * TB;
+                TileTask t{};
+                t.A = tile;
+                t.B = Dk;
+                t.C = S;
+                t.lda = ntp;
+                t.ldb = t.ldc = TB;
+                t.k0 = 0;
+                t.k1 = TB;
+                trsm.push_back(t);
+                TileTask r{};
+                r.A = S;
+                r.B = F + (size_t)k * TB + (size_t)k * TB * ntp;
+                r.C = tile;
+                r.lda = TB;
+                r.ldb = r.ldc = ntp;
+                r.k0 = 0;
+                r.k1 = TB;
+                r.update = 1;
+                res.push_back(r);
+                TileTask t2 = t;
+                t2.C = tile;
+                t2.ldc = ntp;
+                trsm2.push_back(t2);
+                TileTask a = r;
+                a.B = c->arenaSampleDinv.p + negi_off;
+                a.ldb = TB;
+                add.push_back(a);
+            }
+        }
+        upd_off[(size_t)k + 1] = (int)upd.size();
+        trsm_off[(size_t)k + 1] = (int)trsm.size();
+        diag_off[(size_t)k + 1] = (int)diag.size();
+    }
+    c->stage_top = 0;       // (the stream is idle: every entry point synchronises before it returns)
+    if (int rc = stage_upload_list(c, c->scov, cov)) return rc;
+    if (int rc = stage_upload_list(c, c->supd, upd)) return rc;
+    if (int rc = stage_upload_list(c, c->strsm, trsm)) return rc;
+    if (int rc = stage_upload_list(c, c->sres, res)) return rc;
+    if (int rc = stage_upload_list(c, c->strsm2, trsm2)) return rc;
+    if (int rc = stage_upload_list(c, c->sadd, add)) return rc;
+    if (int rc = stage_upload_list(c, c->sdiag, diag)) return rc;
+    if (int rc = stage_upload(c, c->d_sinfo.p, flags.data(), (size_t)L * sizeof(int))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->arenaSample.p, 0, std::max<size_t>(1, ftot) * sizeof(double), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->arenaSampleDinv.p, 0, std::max<size_t>(1, dtot) * sizeof(double), c->stream));
+    if (!trsm.empty()) {
+        std::vector<double> negi((size_t)TB * TB, 0.0);
+        for (int i = 0; i < TB; ++i) negi[(size_t)i * TB + i] = -1.0;
+        if (int rc = stage_upload(c, c->arenaSampleDinv.p + negi_off, negi.data(), negi.size() * sizeof(double))) return rc;
+    }
+    if (!cov.empty()) predsample_sigma_kernel<<<(unsigned)cov.size(), 256, 0, c->stream>>>(c->scov.p, c->d_kp.p, c->D, jitter);
+    HIPCHK(c, hipEventRecord(after_sigma, c->stream));
+    for (int k = 0; k < maxnb; ++k) {
+        const int nu = upd_off[(size_t)k + 1] - upd_off[(size_t)k], nd = diag_off[(size_t)k + 1] - diag_off[(size_t)k];
+        const int ns = trsm_off[(size_t)k + 1] - trsm_off[(size_t)k];
+        if (nu) launch_tiles(c, c->supd.p + upd_off[(size_t)k], nu);
+        if (nd) chol_diag_packed_kernel<<<nd, 256, DIAGP_LDS_BYTES, c->stream>>>(c->sdiag.p + diag_off[(size_t)k]);
+        if (ns) {
+            launch_tiles(c, c->strsm.p + trsm_off[(size_t)k], ns, 1);
+            launch_tiles(c, c->sres.p + trsm_off[(size_t)k], ns);
+            launch_tiles(c, c->strsm2.p + trsm_off[(size_t)k], ns, 1);
+            launch_tiles(c, c->sadd.p + trsm_off[(size_t)k], ns);
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    c->sample_info.assign((size_t)L, 0);
+    static_assert(sizeof(int) == sizeof(int32_t), "the flags are read back as int32_t");
+    HIPCHK(c, hipMemcpyAsync(c->sample_info.data(), c->d_sinfo.p, (size_t)L * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = stage_done(c)) return rc;
+    c->sample_noise = with_noise ? 1 : 0;
+    c->sample_jitter = jitter;
+    c->mark(P_SAMPLE);
+    return 0;
+}
+}  // namespace
+
+int dsmgp_predict_sample(dsmgp_ctx* c, int32_t with_noise, double jitter, const double* eps, int64_t ld_eps, int32_t S,
+                         double* out, int64_t ld_out, int32_t* info_out, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "predict_sample before predict_run on the current fit");
+    if (S < 1 || S > 65535) return fail(c, DSMGP_E_ARG, "predict_sample: S must be 1 .. 65535");
+    if (!std::isfinite(jitter) || jitter < 0.0) return fail(c, DSMGP_E_ARG, "predict_sample: jitter must be finite and >= 0");
+    const int L = c->L;
+    const int64_t R = c->route_total;
+    if (R == 0) {       // no routed rows at all: nothing to draw
+        if (info_out) std::fill(info_out, info_out + L, 0);
+        return 0;
+    }
+    if (!eps || !out) return fail(c, DSMGP_E_ARG, "predict_sample: eps or out is NULL");
+    if (ld_eps < R || ld_out < R) return fail(c, DSMGP_E_ARG, "predict_sample: ld_eps or ld_out < route_total");
+    for (int s = 0; s < S; ++s)
+        for (int64_t e = 0; e < R; ++e)
+            if (!std::isfinite(eps[e + (size_t)s * ld_eps])) return fail(c, DSMGP_E_ARG, "predict_sample: eps is not finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int wn = with_noise ? 1 : 0;
+    EventPair ev, evf;      // ev.a .. evf.a Sigma (after the lists' uploads), evf.a .. evf.b the block steps, evf.b .. ev.b the draws
+    HIPCHK(c, ev.init());
+    HIPCHK(c, evf.init());
+    HIPCHK(c, hipEventRecord(ev.a, c->stream));
+    const bool factorise = !c->has(P_SAMPLE) || c->sample_noise != wn || c->sample_jitter != jitter;
+    if (factorise)
+        if (int rc = sample_factorise(c, wn, jitter, evf.a)) return rc;
+    HIPCHK(c, hipEventRecord(evf.b, c->stream));
+    const int ngrp = (S + SAMPLE_COLS - 1) / SAMPLE_COLS;
+    const size_t S16 = (size_t)ngrp * SAMPLE_COLS;
+    if (int rc = c->d_seps.grow(c, (size_t)R * S16)) return rc;
+    if (int rc = c->d_sout.grow(c, (size_t)R * S16)) return rc;
+    std::vector<SampleDrawTask> tasks;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (lf.nt == 0) continue;
+        for (int i = lf.ntpad / TB - 1; i >= 0; --i)        // the long rows first
+            for (int g = 0; g < ngrp; ++g) {
+                SampleDrawTask t{};
+                t.C = c->arenaSample.p + c->sample_off[(size_t)l];
+                t.eps = c->d_seps.p + (size_t)lf.route_off + (size_t)g * SAMPLE_COLS * (size_t)R;
+                t.out = c->d_sout.p + (size_t)lf.route_off + (size_t)g * SAMPLE_COLS * (size_t)R;
+                t.mu = c->h_leaves[l].mu;
+                t.info = c->d_sinfo.p + l;
+                t.lde = (long long)R;
+                t.ntpad = lf.ntpad;
+                t.nt = lf.nt;
+                t.ti = i;
+                tasks.push_back(t);
+            }
+    }
+    c->stage_top = 0;
+    if (int rc = stage_upload_list(c, c->sdraw, tasks)) return rc;
+    // the caller's S columns, and zeros in the columns that round S up to 16
+    if (S16 > (size_t)S)
+        HIPCHK(c, hipMemsetAsync(c->d_seps.p + (size_t)R * (size_t)S, 0, (size_t)R * (S16 - (size_t)S) * sizeof(double), c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(c->d_seps.p, (size_t)R * sizeof(double), eps, (size_t)ld_eps * sizeof(double), (size_t)R * sizeof(double),
+                               (size_t)S, hipMemcpyHostToDevice, c->stream));
+    predsample_draw_kernel<<<(unsigned)tasks.size(), 256, 0, c->stream>>>(c->sdraw.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev.b, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(out, (size_t)ld_out * sizeof(double), c->d_sout.p, (size_t)R * sizeof(double), (size_t)R * sizeof(double),
+                               (size_t)S, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = stage_done(c)) return rc;
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (seconds) *seconds = ms * 1e-3;
+    c->sample_seconds[0] = c->sample_seconds[1] = 0.0;
+    if (factorise) {
+        HIPCHK(c, hipEventElapsedTime(&ms, ev.a, evf.a));
+        c->sample_seconds[0] = ms * 1e-3;
+        HIPCHK(c, hipEventElapsedTime(&ms, evf.a, evf.b));
+        c->sample_seconds[1] = ms * 1e-3;
+    }
+    HIPCHK(c, hipEventElapsedTime(&ms, evf.b, ev.b));
+    c->sample_seconds[2] = ms * 1e-3;
+    if (info_out) std::copy(c->sample_info.begin(), c->sample_info.end(), info_out);
+    return 0;
+}
+
+int dsmgp_predict_sample_seconds(dsmgp_ctx* c, double* out) {
+    if (!c || !out) return DSMGP_E_ARG;
+    for (int i = 0; i < 3; ++i) out[i] = c->sample_seconds[i];
+    return 0;
+}
+
+// Inspection: the factor of one leaf as the last dsmgp_predict_sample left it
+int dsmgp_predict_cov_factor(dsmgp_ctx* c, int32_t leaf, double* Lc_out, int64_t ld) {
+    if (!c) return DSMGP_E_ARG;
+    if (!c->has(P_SAMPLE)) return fail(c, DSMGP_E_STATE, "predict_cov_factor without a current factor (dsmgp_predict_sample)");
+    if (leaf < 0 || leaf >= c->L) return fail(c, DSMGP_E_ARG, "predict_cov_factor: leaf out of range");
+    const LeafHost& lf = c->leaves[leaf];
+    if (lf.nt == 0) return 0;
+    if (!Lc_out || ld < lf.nt) return fail(c, DSMGP_E_ARG, "predict_cov_factor: Lc_out is NULL or ld < nt");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy2D(Lc_out, (size_t)ld * sizeof(double), c->arenaSample.p + c->sample_off[(size_t)leaf],
+                          (size_t)lf.ntpad * sizeof(double), (size_t)lf.nt * sizeof(double), (size_t)lf.nt, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -2002,8 +2002,12 @@ struct PredCovTask {
     int pad;
 };
 
-template <int KIND>
-__device__ __forceinline__ void predcov_epilogue(const PredCovTask& g, const KParam& p, int D, d4 (&acc)[4][4], double* xs) {
+// FACTOR (predsample_sigma_kernel, kernels_sample.hpp): the tile is the start of a Cholesky factorisation in an arena that was
+// cleared -- the same values, `jitter` more on the real diagonal, ones on the padded diagonal, and no mirror of the tiles below
+// the block diagonal (the strict upper block triangle stays zero).
+template <int KIND, bool FACTOR = false>
+__device__ __forceinline__ void predcov_epilogue(const PredCovTask& g, const KParam& p, int D, d4 (&acc)[4][4], double* xs,
+                                                 double jitter = 0.0) {
     const int t = threadIdx.x;
     const int lane = t & 63, w = t >> 6;
     const int wr = w & 1, wc = w >> 1, l15 = lane & 15, l4 = lane >> 4;
@@ -2045,20 +2049,23 @@ __device__ __forceinline__ void predcov_epilogue(const PredCovTask& g, const KPa
             if (r < g.na && c < g.nb && low) {
                 double v = gram_finish<KIND, false>(z[0][i], p, r, c, g.na, g.nb, false) - acc[i >> 2][rn][i & 3];
                 if (g.diag && r == c) v += dadd;
+                if (FACTOR && g.diag && r == c) v += jitter;
                 AS_GLOBAL_F64(g.gemm.C)[r + (size_t)c * ldc] = v;
-                if (!g.diag || r != c) AS_GLOBAL_F64(g.Ct)[c + (size_t)r * ldc] = v;
+                if (FACTOR ? (g.diag && r != c) : (!g.diag || r != c)) AS_GLOBAL_F64(g.Ct)[c + (size_t)r * ldc] = v;
+            } else if (FACTOR && g.diag && r == c) {
+                AS_GLOBAL_F64(g.gemm.C)[r + (size_t)c * ldc] = 1.0;
             }
         }
     }
 }
 
-__global__ __launch_bounds__(256, 2) void tile_predcov_kernel(const PredCovTask* __restrict__ tasks,
-                                                              const KParam* __restrict__ kp, int D) {
-    __shared__ __attribute__((aligned(16))) double smem[2 * NRING * KC2 * LDP];
-    static_assert(GRADDOT_STAGE_D * 256 <= 2 * NRING * KC2 * LDP, "a round of coordinates fits the ring");
+constexpr int PREDCOV_LDS_DOUBLES = 2 * NRING * KC2 * LDP;
+template <bool FACTOR>
+__device__ __forceinline__ void predcov_tile_body(const PredCovTask& g, const KParam* __restrict__ kp, int D, double* smem,
+                                                  double jitter) {
+    static_assert(GRADDOT_STAGE_D * 256 <= PREDCOV_LDS_DOUBLES, "a round of coordinates fits the ring");
     double (*sA)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem);
     double (*sB)[KC2 * LDP] = reinterpret_cast<double (*)[KC2 * LDP]>(smem + NRING * KC2 * LDP);
-    const PredCovTask g = tasks[blockIdx.x];
     const KParam p = kp[g.kid];
     d4 acc[4][4];
     gemm_mainloop_v2<false>(g.gemm, acc, sA, sB, nullptr);      // ends on a barrier: the ring is free
@@ -2079,7 +2086,14 @@ __global__ __launch_bounds__(256, 2) void tile_predcov_kernel(const PredCovTask*
                 for (int i = 0; i < 16; ++i) acc[i >> 2][rn][i & 3] = fma(a[rn], b[i], acc[i >> 2][rn][i & 3]);
         }
     }
-    DSMGP_KIND_DISPATCH(p.kind, K, predcov_epilogue<K>(g, p, D, acc, smem));
+    DSMGP_KIND_DISPATCH(p.kind, K, (predcov_epilogue<K, FACTOR>(g, p, D, acc, smem, jitter)));
+}
+
+__global__ __launch_bounds__(256, 2) void tile_predcov_kernel(const PredCovTask* __restrict__ tasks,
+                                                              const KParam* __restrict__ kp, int D) {
+    __shared__ __attribute__((aligned(16))) double smem[PREDCOV_LDS_DOUBLES];
+    const PredCovTask g = tasks[blockIdx.x];
+    predcov_tile_body<false>(g, kp, D, smem, 0.0);
 }
 
 // ---------------------------------------------------------------------------------------------

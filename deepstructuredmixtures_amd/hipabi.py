@@ -21,6 +21,7 @@ OPT_DIAG_IN_UPDATE = 4
 OPT_FIT_GRAPH = 5
 OPT_LANES = 6
 SCORE_NAMES = ("mse", "sse", "mae", "sae", "nlpd")
+SAMPLE_JITTER = 1e-8    # predict_sample without noise: model.EPS (`const ϵ` of src/DeepStructuredMixtures.jl:27)
 
 
 def agg_width(family, n_groups=0):
@@ -67,6 +68,10 @@ SIGNATURES = {
     "dsmgp_predict_fetch": (C.c_int, [_ctx, _dp, _dp]),
     "dsmgp_predict_leaves": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, _lp, _lp, _dp, _dp]),
     "dsmgp_predict_cov": (C.c_int, [_ctx, C.c_int32, C.c_int32, _dp, C.c_int64, _dp]),
+    "dsmgp_predict_sample": (C.c_int, [_ctx, C.c_int32, C.c_double, _dp, C.c_int64, C.c_int32, _dp, C.c_int64,
+                                       C.POINTER(C.c_int32), _dp]),
+    "dsmgp_predict_cov_factor": (C.c_int, [_ctx, C.c_int32, _dp, C.c_int64]),
+    "dsmgp_predict_sample_seconds": (C.c_int, [_ctx, _dp]),
     "dsmgp_predict_gradients": (C.c_int, [_ctx, _dp, _dp, C.c_int64, _dp]),
     "dsmgp_solve_targets": (C.c_int, [_ctx, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp, _dp]),
     "dsmgp_predict_targets": (C.c_int, [_ctx, _dp, C.c_int64, _dp]),
@@ -426,6 +431,45 @@ class Context:
         self._chk(self.lib.dsmgp_predict_cov(self.h, int(leaf), 1 if with_noise else 0, S.ctypes.data_as(_dp), nt, C.byref(sec)))
         self.cov_seconds = sec.value
         return S
+
+    def predict_sample(self, eps, with_noise=False, jitter=None):
+        """Joint posterior draws of every leaf over its routed rows from the caller's standard normals (dsmgp_predict_sample; needs
+        `predict_run` on the current fit): `eps` is `(route_total, S)` (a vector is one draw), entry order of `predict_fetch`;
+        returns `(draws, info)`, draws `(route_total, S)` float64 in Fortran order, column s = mu + chol(Sigma_l + jitter I) eps_l[:, s]
+        per leaf, and info `(L,)` int32: 0, the order of the first leading minor that is not positive definite, or -1 for a leaf
+        whose fit failed (NaN entries either way).  `jitter` defaults to SAMPLE_JITTER (the model's EPS) without noise and 0 with
+        it.  The factors stay on the device for the next call with the same `(with_noise, jitter)`.  The device time of the call
+        is left in `self.sample_seconds`, its split (sigma, factor, draws; the first two 0 on current factors) in
+        `self.sample_split_seconds`."""
+        eps = np.asarray(eps, dtype=np.float64)
+        if eps.ndim == 1:
+            eps = eps[:, None]
+        n = int(self.route_total)
+        if eps.ndim != 2 or eps.shape[0] != n:
+            raise ValueError(f"predict_sample: eps must be (route_total = {n}, S), got {eps.shape}")
+        eps = np.asfortranarray(eps)
+        S = int(eps.shape[1])
+        if jitter is None:
+            jitter = 0.0 if with_noise else SAMPLE_JITTER
+        out = np.empty((n, S), dtype=np.float64, order="F")
+        info = np.zeros(self.L, dtype=np.int32)
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_predict_sample(self.h, 1 if with_noise else 0, float(jitter), eps.ctypes.data_as(_dp), max(1, n), S,
+                                                out.ctypes.data_as(_dp), max(1, n), info.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                C.byref(sec)))
+        self.sample_seconds = sec.value
+        split = np.zeros(3)
+        self._chk(self.lib.dsmgp_predict_sample_seconds(self.h, split.ctypes.data_as(_dp)))
+        self.sample_split_seconds = dict(sigma=float(split[0]), factor=float(split[1]), draws=float(split[2]))
+        return out, info
+
+    def predict_cov_factor(self, leaf, nt):
+        """The lower Cholesky factor of leaf `leaf` the last `predict_sample` made, `(nt, nt)` float64 in Fortran order with a
+        strict upper triangle of exact zeros (inspection; E_STATE when no current factor exists)."""
+        nt = int(nt)
+        Lc = np.zeros((nt, nt), dtype=np.float64, order="F")
+        self._chk(self.lib.dsmgp_predict_cov_factor(self.h, int(leaf), Lc.ctypes.data_as(_dp), max(1, nt)))
+        return Lc
 
     def predict_gradients(self, want_var=True):
         """`(dmu, dvar)`: the gradients of the predictive mean and variance of every (leaf, routed test row) entry of
@@ -1038,6 +1082,12 @@ class MultiContext:
         self.predict_run()
         return self.predict_fetch()
 
+    def predict_sample(self, eps, with_noise=False, jitter=None):
+        raise NotImplementedError("predict_sample: joint draws are served by a single Context only")
+
+    def predict_cov_factor(self, leaf, nt):
+        raise NotImplementedError("predict_cov_factor: joint draws are served by a single Context only")
+
     def predict_cov(self, leaf, nt, with_noise=True):
         raise DsmgpError(E_STATE, "predict_cov: the full covariance of a leaf is served by a single Context only "
                                   "(MultiContext spreads the leaf table over several devices)")
@@ -1443,6 +1493,12 @@ class StreamingContext:
 
     def predict_fetch(self):
         return self._res["mu"], self._res["var"]
+
+    def predict_sample(self, eps, with_noise=False, jitter=None):
+        raise NotImplementedError("predict_sample: a streaming pass discards K_tn L^-T with its leaf group")
+
+    def predict_cov_factor(self, leaf, nt):
+        raise NotImplementedError("predict_cov_factor: a streaming pass keeps no factor of a test covariance")
 
     def predict_cov(self, leaf, nt, with_noise=True):
         raise DsmgpError(E_STATE, "predict_cov: a streaming pass discards K_tn L^-T with its leaf group; "

@@ -426,11 +426,13 @@ def leaf_covariance(model, xtest, leaf, with_noise=True):
     return rows, model.ctx.predict_cov(int(model.shard.subset.global_to_local()[leaf]), rows.size, with_noise)
 
 
-def posterior_sample(gp, xtest, n_samples, seed=0, with_noise=False):
+def posterior_sample(gp, xtest, n_samples, seed=0, with_noise=False, device=False):
     """`n_samples` joint draws of a GaussianProcess at the rows of `xtest`: mu + chol(Sigma) eps, an (n_samples, n_t) array.
     Sigma comes from the device (`Context.predict_cov`), the factorisation and the draws run on the host; eps is the
     project's counter stream (`datagen.normal(seed, 0, n_t * n_samples)`, one column of n_t per sample).  Without noise the
-    module's EPS is added to the diagonal; np.linalg.LinAlgError if the Cholesky still fails."""
+    module's EPS is added to the diagonal; np.linalg.LinAlgError if the Cholesky still fails.
+    `device=True`: the same eps through `Context.predict_sample` -- Sigma, its factorisation and the product stay on the device,
+    nothing of size n_t^2 is downloaded; the same law, the bits of another Cholesky."""
     if not isinstance(gp, GaussianProcess):
         raise TypeError("posterior_sample takes a GaussianProcess (the joint law of a mixture is not Gaussian)")
     n_samples = int(n_samples)
@@ -440,6 +442,14 @@ def posterior_sample(gp, xtest, n_samples, seed=0, with_noise=False):
     nt = mu.size
     if nt == 0:
         return np.zeros((n_samples, 0))
+    if device:
+        if n_samples == 0:
+            return np.zeros((0, nt))
+        eps = _datagen.normal(int(seed), 0, nt * n_samples).reshape((nt, n_samples), order="F")
+        draws, info = gp.model.ctx.predict_sample(eps, with_noise=with_noise)
+        if info[0] != 0:
+            raise np.linalg.LinAlgError(f"posterior_sample: the covariance is not positive definite (info = {int(info[0])})")
+        return draws.T
     S = gp.model.ctx.predict_cov(0, nt, with_noise)
     if not with_noise:
         d = np.arange(nt)
@@ -447,6 +457,111 @@ def posterior_sample(gp, xtest, n_samples, seed=0, with_noise=False):
     Lc = np.linalg.cholesky(S)
     eps = _datagen.normal(int(seed), 0, nt * n_samples).reshape((nt, n_samples), order="F")
     return (mu[:, None] + Lc @ eps).T
+
+
+def leaf_samples(model, xtest, n_samples, seed=0, with_noise=False):
+    """Joint draws of EVERY leaf GP at its routed rows, on the device (`Context.predict_sample`): returns
+    `(route_ptr, route_idx, draws, info)` -- the routes of `xtest` as CSR over the leaves, draws `(route_total, n_samples)` in
+    entry order (column s is one joint draw of every leaf; leaves are independent of each other) and the per-leaf info of the
+    factorisations (a leaf with info != 0 has NaN entries).  eps = `datagen.normal(seed, 0, route_total * n_samples)` in entry
+    order, one column per draw.  Without noise the module's EPS is added to the diagonals.  For DSMGP, PoE, gPoE, rBCM models
+    and a GaussianProcess; single rank (`shard.world > 1` raises NotImplementedError, as `leaf_covariance` does for a leaf held
+    elsewhere).  Draws of the target columns of `fit_targets` differ from these by the mean only and are not offered."""
+    if isinstance(model, GaussianProcess):
+        model = model.model
+    n_samples = int(n_samples)
+    if n_samples < 0:
+        raise ValueError("n_samples must not be negative")
+    if model.shard.world > 1:
+        raise NotImplementedError("leaf_samples runs on a single rank")
+    xt = _test_matrix(model, xtest)
+    rc = _routing(model, xt)
+    ptr, idx = rc["ptr"], rc["idx"]
+    total = int(ptr[-1])
+    if total == 0 or n_samples == 0:
+        return ptr, idx, np.zeros((total, n_samples), order="F"), np.zeros(model.L, dtype=np.int32)
+    if not rc["uploaded"]:
+        model.ctx.set_test(xt, rc["lptr"], rc["lidx"])      # (host lists: the entries come back in THIS order)
+        rc["uploaded"] = True
+    model.last_predict_seconds = model.ctx.predict_run()
+    eps = _datagen.normal(int(seed), 0, total * n_samples).reshape((total, n_samples), order="F")
+    draws, info = model.ctx.predict_sample(eps, with_noise=with_noise)
+    return ptr, idx, draws, info
+
+
+_SELECTION_SEED_XOR = 0x5DEECE66D
+
+
+def _sum_nodes(root):
+    """The sum nodes of a tree in creation order (the counter of their ids)."""
+    out, stack = [], [root]
+    while stack:
+        nd = stack.pop()
+        if nd.kind == "sum":
+            out.append(nd)
+        stack.extend(nd.children)
+    return sorted(out, key=lambda nd: int(nd.id.split("#")[1]))
+
+
+def _mixture_choices(root, n_samples, seed):
+    """(n_samples, number of sum nodes) child indices: per draw, one child of every sum node (creation order) with probability
+    exp(logweights) normalised, from `datagen.Stream((seed XOR 0x5DEECE66D) mod 2^63)` -- draw after draw, node after node, one
+    uniform each."""
+    nodes = _sum_nodes(root)
+    stream = _datagen.Stream((int(seed) ^ _SELECTION_SEED_XOR) & ((1 << 63) - 1))
+    probs = [np.exp(nd.logweights - _logsumexp(nd.logweights)) for nd in nodes]
+    out = np.zeros((int(n_samples), len(nodes)), dtype=np.int64)
+    for s in range(int(n_samples)):
+        for j, p in enumerate(probs):
+            out[s, j] = stream.categorical(p)
+    return nodes, out
+
+
+def _mixture_leaf_of_rows(root, xt, nodes, choice):
+    """The leaf every row of `xt` falls into when sum node nodes[j] keeps child choice[j] only (split nodes keep all children):
+    the chosen leaves partition the input space."""
+    pick = {id(nd): int(k) for nd, k in zip(nodes, choice)}
+    leaf = np.full(xt.shape[0], -1, dtype=np.int64)
+
+    def rec(node, rows):
+        if rows.size == 0:
+            return
+        if node.kind == "gp":
+            leaf[rows] = node.leaf
+        elif node.kind == "sum":
+            rec(node.children[pick[id(node)]], rows)
+        else:
+            ch = get_child(node, xt[rows])
+            for k, c in enumerate(node.children):
+                rec(c, rows[ch == k])
+
+    rec(root, np.arange(xt.shape[0], dtype=np.int64))
+    return leaf
+
+
+def mixture_sample(model, xtest, n_samples, seed=0, with_noise=False):
+    """`n_samples` draws of a DSMGP at the rows of `xtest`, an (n_samples, n_t) array: per draw one child of every sum node is
+    chosen with probability exp(logweights) (normalised; `_mixture_choices` documents the stream), split nodes keep all their
+    children, so the chosen leaves partition the input space; row r of draw s is column s of `leaf_samples(model, xtest,
+    n_samples, seed, with_noise)` at the entry of r under its chosen leaf.  Host composition of the device's leaf draws: rows
+    under different leaves are independent given the choice.  A GaussianProcess: `posterior_sample(..., device=True)`.  PoE, gPoE
+    and rBCM raise TypeError (the reference defines no joint law for them)."""
+    if isinstance(model, GaussianProcess):
+        return posterior_sample(model, xtest, n_samples, seed=seed, with_noise=with_noise, device=True)
+    if not isinstance(model, Model) or model.family != "dsmgp":
+        raise TypeError("mixture_sample takes a DSMGP or a GaussianProcess: product-of-experts models have no joint law here")
+    ptr, idx, draws, info = leaf_samples(model, xtest, n_samples, seed=seed, with_noise=with_noise)
+    xt = _test_matrix(model, xtest)
+    n_samples = int(n_samples)
+    out = np.empty((n_samples, xt.shape[0]))
+    nodes, choices = _mixture_choices(model.root, n_samples, seed)
+    for s in range(n_samples):
+        leaf = _mixture_leaf_of_rows(model.root, xt, nodes, choices[s])
+        for l in np.unique(leaf):
+            rows = np.nonzero(leaf == l)[0]
+            seg = idx[ptr[l]:ptr[l + 1]]            # the leaf's routed rows, ascending
+            out[s, rows] = draws[ptr[l] + np.searchsorted(seg, rows), s]
+    return out
 
 
 # ------------------------------------------------------------------------------------ fit

@@ -271,6 +271,45 @@ int dsmgp_predict_leaves(dsmgp_ctx* ctx, const double* Xt, int64_t n_t, int32_t 
  * one -- and is NOT counted by dsmgp_estimate_bytes / dsmgp_memory; it is dropped with the test set, the leaf table and
  * dsmgp_release. */
 int dsmgp_predict_cov(dsmgp_ctx* ctx, int32_t leaf, int32_t with_noise, double* Sigma_out, int64_t ld, double* seconds);
+/* Joint posterior draws of every leaf GP over its routed test rows (not a call of the reference: Thompson sampling, batch
+ * selection by sampled maxima, Monte-Carlo acquisition values).  The caller supplies the standard normals; no random number is
+ * made on the device.  For every leaf l with routed rows, over its segment e0 .. e0 + nt - 1 of the entries of
+ * dsmgp_predict_fetch, in that order:
+ *   A_l = Sigma_l + jitter I, Sigma_l exactly what dsmgp_predict_cov(leaf = l, with_noise) returns (same kernel, same bits),
+ *   C_l = chol(A_l), lower,
+ *   out[e0 + i + s * ld_out] = mu[e0 + i] + sum_{j <= i} C_l[i, j] eps[e0 + j + s * ld_eps].
+ * Column s is one joint draw of every leaf; leaves are independent of each other.  eps and out are route_total x S, column-major.
+ * info_out (L, may be NULL): 0 = success; k > 0 = the leading minor of order k of A_l is not positive definite (LAPACK potrf's
+ * convention, as dsmgp_fit reports it); -1 = a leaf whose fit reported info != 0.  A leaf with info_out[l] != 0 gets NaN in all
+ * its entries, every other leaf is unaffected; a leaf without routed rows reports 0 and writes nothing.
+ * Needs dsmgp_predict_run on the current fit (DSMGP_E_STATE otherwise), on either route to K_tn L^-T: rows that rode through the
+ * fit, or the standalone sweep; one lane or two.  DSMGP_E_ARG: S < 1 or S > 65535, a NULL eps or out, ld_eps or ld_out below
+ * route_total, a jitter that is negative or not finite, a non-finite value in eps.  No routed rows at all: success, nothing
+ * written.  Runs on the context's stream and synchronises before it returns.  seconds (may be NULL): device time of the call.
+ * Sums run in a fixed order and there are no atomics: the same bits from call to call, and column s is the same bits whatever S
+ * is and whatever the other columns hold.  dsmgp_predict_fetch, dsmgp_predict_cov, dsmgp_predict_gradients,
+ * dsmgp_predict_targets, dsmgp_aggregate*, dsmgp_scores and dsmgp_fit's outputs return the same bits before and after this call.
+ * The factors are kept, tagged with (with_noise, jitter): a second call with the same tag and new eps skips the factorisation
+ * (Thompson loops draw repeatedly); whatever fells the prediction fells them (a new fit, new hyper-parameters, a new test set,
+ * dsmgp_predict_run, dsmgp_add_rows_keep_test -- after it and the resumed dsmgp_predict_run the call works on the grown model).
+ * Memory: dsmgp_predict_cov keeps its own scratch; the factors live in an arena of their own, ntpad^2 doubles per leaf with routed
+ * rows (nt rounded up to 128), plus 128 ntpad for the inverted diagonal blocks and two staging buffers of route_total x S rounded
+ * up to 16: allocated on first use (the arenas from the reserved pool when there is one; DSMGP_E_NOMEM with a usable context when
+ * they do not fit), NOT counted by dsmgp_estimate_bytes / dsmgp_memory, dropped with the test set, the leaf table and
+ * dsmgp_release.  Cost: the n nt^2 flops of Sigma_l, nt^3 / 3 of its factorisation, nt^2 S of the draws, all on the f64 matrix
+ * cores.  Draws of the target columns of dsmgp_solve_targets differ from these by the mean only and are not offered. */
+int dsmgp_predict_sample(dsmgp_ctx* ctx, int32_t with_noise, double jitter,
+                         const double* eps /* route_total x S, column-major */, int64_t ld_eps, int32_t S,
+                         double* out /* route_total x S, column-major */, int64_t ld_out,
+                         int32_t* info_out /* L, may be NULL */, double* seconds /* may be NULL */);
+/* Device seconds of the last successful dsmgp_predict_sample, split: out[0] forming Sigma (with the uploads of the task lists),
+ * out[1] the factorisation, out[2] the staging of eps and the draws; out[0] = out[1] = 0 when the call found its factors current. */
+int dsmgp_predict_sample_seconds(dsmgp_ctx* ctx, double* out /* 3 */);
+/* Inspection, like dsmgp_download_factor: C_l of the last dsmgp_predict_sample, nt x nt column-major with leading dimension
+ * ld >= nt: the lower triangle, the strict upper triangle exactly 0.  DSMGP_E_STATE when no current factor exists; leaf out of
+ * range, a NULL Lc_out or ld < nt: DSMGP_E_ARG; a leaf without routed rows: success, nothing written.  The factor of a leaf whose
+ * flag is not 0 holds no meaning. */
+int dsmgp_predict_cov_factor(dsmgp_ctx* ctx, int32_t leaf, double* Lc_out /* nt x nt column-major */, int64_t ld);
 /* Gradients of the predictive mean and variance with respect to the test point (not a call of the reference): for every
  * (leaf, routed test row t) -- the entries of dsmgp_predict_fetch, in its order -- and every input dimension d,
  *   dmu_out[e + d * ld]  = d mu / d x_{t,d}  = sum_i alpha_i dk(x_t, x_i) / dx_{t,d},

@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, append_rows!, append_stats, resume_stats, download_vt, predict_cov, predict_gradients, aggregate_gradients, aggregate_columns, aggregate_columns_gradients, loo, loo_gradients, solve_targets, predict_targets, predict_targets_gradients, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
+export attach!, detach!, census, append_rows!, append_stats, resume_stats, download_vt, predict_cov, predict_sample, predict_cov_factor, predict_gradients, aggregate_gradients, aggregate_columns, aggregate_columns_gradients, loo, loo_gradients, solve_targets, predict_targets, predict_targets_gradients, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -485,6 +485,44 @@ function predict_cov(s::Session, leaf::Integer; with_noise::Bool=true)
     GC.@preserve Σ chk(s, ccall(sym(:dsmgp_predict_cov), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int64, Ref{Float64}),
                            s.h, Int32(leaf - 1), Int32(with_noise), Σ, nt, sec))
     return Σ
+end
+
+"predict_sample(s, eps; with_noise=false, jitter=nothing): joint posterior draws of every leaf GP over its routed rows of the
+registered test set from the caller's standard normals (dsmgp_predict_sample; needs a prediction on the current fit).  `eps` is
+`route_total × S` in the entry order of the per-leaf moments; returns (draws, info): draws `route_total × S`, column s =
+μ + chol(Σ_l + jitter·I) eps_l[:, s] per leaf (leaves are independent of each other), and info per leaf: 0, the order of the first
+leading minor that is not positive definite, or −1 for a leaf whose fit failed (NaN entries either way).  `jitter` defaults to the
+reference's ϵ = 1e-8 without noise and to 0 with it.  The factors stay on the device for the next call with the same
+(with_noise, jitter).  (The scalar `jitter` goes by value: the call is written with @ccall.)"
+function predict_sample(s::Session, eps::AbstractMatrix{<:Real}; with_noise::Bool=false, jitter::Union{Nothing,Real}=nothing)
+    ptr = Vector{Int64}(undef, length(s.leaves) + 1)
+    GC.@preserve ptr chk(s, ccall(sym(:dsmgp_routes), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), s.h, ptr, C_NULL))
+    nr = Int(ptr[end])
+    size(eps, 1) == nr || throw(ArgumentError("predict_sample: eps must have route_total = $nr rows"))
+    E = Matrix{Float64}(eps)
+    S = size(E, 2)
+    jit = Float64(jitter === nothing ? (with_noise ? 0.0 : 1e-8) : jitter)
+    out = Matrix{Float64}(undef, nr, S)
+    info = zeros(Int32, length(s.leaves))
+    sec = Ref{Float64}(0.0)
+    fptr = sym(:dsmgp_predict_sample)
+    GC.@preserve E out info chk(s, @ccall $fptr(s.h::Ptr{Cvoid}, Int32(with_noise)::Int32, jit::Float64, pointer(E)::Ptr{Float64},
+                                                max(1, nr)::Int64, Int32(S)::Int32, pointer(out)::Ptr{Float64}, max(1, nr)::Int64,
+                                                pointer(info)::Ptr{Int32}, sec::Ref{Float64})::Cint)
+    return out, info
+end
+
+"predict_cov_factor(s, leaf): the lower Cholesky factor of leaf `leaf` (1-based) the last predict_sample made, over its routed rows
+(dsmgp_predict_cov_factor; inspection): the strict upper triangle is exactly 0.  A leaf without routed rows gives a 0×0 matrix."
+function predict_cov_factor(s::Session, leaf::Integer)
+    ptr = Vector{Int64}(undef, length(s.leaves) + 1)
+    GC.@preserve ptr chk(s, ccall(sym(:dsmgp_routes), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), s.h, ptr, C_NULL))
+    nt = Int(ptr[leaf + 1] - ptr[leaf])
+    Lc = zeros(Float64, nt, nt)
+    nt == 0 && return Lc
+    GC.@preserve Lc chk(s, ccall(sym(:dsmgp_predict_cov_factor), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64),
+                            s.h, Int32(leaf - 1), Lc, nt))
+    return Lc
 end
 
 "loo(s): leave-one-out cross-validation of every leaf GP on the current fit (GPML §5.4.2, eqs. 5.10–5.12; dsmgp_loo), mean and
