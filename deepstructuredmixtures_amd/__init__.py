@@ -9,6 +9,7 @@ from .model import (DSMGP, PoE, gPoE, rBCM, GaussianProcess, build, buildDSMGP, 
                     fit_naive, predict, prediction, update_cholesky, update, infer, mll, mll_table,
                     reset_weights, getparams, setparams, mse, sse, mae, sae, nlpd, scores, updategradients, grad_mll, train, ADAM, RMSProp,
                     resident_test, finetune, leaf_covariance, posterior_sample, leaf_samples, mixture_sample, loo, loo_predict, loo_scores, loo_objective, grad_loo,
+                    kfold, kfold_predict, kfold_scores, make_folds,
                     predict_gradients, aggregate_input_gradients, fit_targets, predict_targets, predict_targets_gradients,
                     targets_leaf_means,
                     targets_objective, grad_targets, loo_targets, loo_targets_objective, grad_loo_targets, add_data, AppendSeconds)

@@ -9,6 +9,8 @@
 #include "kernels_fused.hpp"
 #include "kernels_targets.hpp"
 #include "kernels_sample.hpp"
+#include "kernels_kfold.hpp"
+#include "kfold_plan.hpp"
 #include "ctx_state.hpp"
 #include "dev_owner.hpp"
 
@@ -759,6 +761,29 @@ struct TargetsStore {
 };
 static_assert(std::is_nothrow_move_assignable_v<TargetsStore>, "TargetsStore falls by assignment (reset)");
 
+// KfoldStore.  dsmgp_kfold (kernels_kfold.hpp): arenas and lists of the last call, grow-only, the arenas from the pool when there is
+// one; built per call, not part of bytes_needed, behind no product (labels arrive per call, nothing is cached: no row in
+// ctx_state.hpp); falls in free_kfold: with the plan, and with whatever moves the pool's stack below it.
+struct KfoldStore {
+    DevArena arenaKP;               // the packed panels of one label round: mpad x npad per block, the largest round's total
+    DevArena arenaKF;               // G_FF, then its factor, mpad^2 per block
+    DevArena arenaKD;               // the inverted diagonal blocks, mpad x 128 per block | -I | the panel solves' scratch tiles
+    DevArena arenaKX;               // C^-T, mpad^2 per block: only a call that returns variances asks for it
+    DevBuf<int32_t> d_kpos;         // the positions of every block
+    DevBuf<int> d_kinfo;            // one flag per block
+    DevBuf<double> d_kwork;         // w | v of every (leaf, label) task
+    DevBuf<double> d_kout;          // mu | var (obs_ptr[L] each) | lpd (L x K)
+    DevBuf<KfoldPackTask> kpack;
+    DevBuf<KfoldGffTask> kgff;
+    DevBuf<KfoldMomTask> kmom;
+    DevBuf<TileTask> kupd, ktrsm, kres, ktrsm2, kadd;   // the block steps of the factorisation (chol_blocks)
+    DevBuf<DiagTask> kdiag;
+    DevBuf<TransTask> kxtrans;      // C^-T: the diagonal tiles, then the sweep's steps
+    DevBuf<TileTask> kxupd, kxtrsm;
+    double kfold_seconds[4] = {0.0, 0.0, 0.0, 0.0};     // device seconds of the last successful call: L^-T, pack + G_FF, factorisation, moments
+};
+static_assert(std::is_nothrow_move_assignable_v<KfoldStore>, "KfoldStore falls by assignment (reset)");
+
 // RouteTreeStore.  The model's tree as flat arrays in HBM: the routing of predict runs on the device (dsmgp_set_test_routed).
 // Built by dsmgp_set_tree; stands behind P_RTREE; falls in free_tree: a new tree, new training data or a new leaf table.
 struct RouteTreeStore {
@@ -772,7 +797,7 @@ struct RouteTreeStore {
 static_assert(std::is_nothrow_move_assignable_v<RouteTreeStore>, "RouteTreeStore falls by assignment (reset)");
 
 // What lives as long as the context, and the plain numbers that describe a group without falling with it
-struct dsmgp_ctx : Validity, PlanStore, TestInputs, TestProducts, GradLists, GradStore, TargetsStore, RouteTreeStore {
+struct dsmgp_ctx : Validity, PlanStore, TestInputs, TestProducts, GradLists, GradStore, TargetsStore, KfoldStore, RouteTreeStore {
     // `valid`: what is current (ctx_state.hpp).  HOW a product was made is a plain member:
     bool vt_from_fit = false;       // P_VT: the rows rode through the fit (else: the standalone sweep of predict_run made it)
     bool last_fit_joint = false;    // P_FIT: it carried the resident test rows
@@ -1091,6 +1116,9 @@ void free_targets(dsmgp_ctx* c) {
     c->d_tmu.release();     // resident columns AND the test set, and go with whichever goes first
 }
 
+// the arenas and lists of dsmgp_kfold: they go where the resident target columns go
+void free_kfold(dsmgp_ctx* c) { reset<KfoldStore>(c); }
+
 void free_tree(dsmgp_ctx* c) {
     reset<RouteTreeStore>(c);
     c->invalidate(P_RTREE);
@@ -1106,6 +1134,7 @@ void free_plan(dsmgp_ctx* c) {
     reset<PlanStore>(c);
     free_grad(c);
     free_targets(c);
+    free_kfold(c);
     c->invalidate(P_PLAN);
 }
 
@@ -1118,6 +1147,7 @@ bool free_test_products(dsmgp_ctx* c, bool keep) {
     if (c->pool.active()) {  // the gradient arenas sit above (or would be clobbered below) the test arenas
         free_grad(c);
         free_targets(c);
+        free_kfold(c);
         c->pool.reset_to_mark();
         keep = false;
     }
@@ -3889,6 +3919,137 @@ int dsmgp_predict_cov(dsmgp_ctx* c, int32_t leaf, int32_t with_noise, double* Si
 
 // Joint draws of every leaf over its routed rows (kernels_sample.hpp): out = mu + chol(Sigma_l + jitter I) eps_l.
 namespace {
+// The blocked Cholesky of a list of symmetric matrices whose lower tiles are in place (mpad x mpad, ld = mpad, identity padding
+// behind the m valid rows), one round of launches per 128-column block step for all matrices that still have that step, left
+// looking: tile_gemm_kernel_v2 (block column k minus the product of the finished columns, the whole K range in one task: a fixed
+// order), chol_diag_packed_kernel with nvalid (the diagonal tile, its inverse into Dinv, the first bad pivot with its absolute
+// order into the matrix's flag), tile_trsm_kernel.  Shared by dsmgp_predict_sample and dsmgp_kfold.
+struct CholBlock {
+    double* F;          // the matrix, overwritten by its factor
+    int m, mpad;
+    double* Dinv;       // mpad x 128 of its own: the inverted diagonal blocks (zeroed by the caller)
+    int* info;          // its flag on the device (zeroed by the caller)
+};
+struct CholSteps {
+    std::vector<TileTask> upd, trsm, res, trsm2, add;
+    std::vector<DiagTask> diag;
+    std::vector<int> upd_off, trsm_off, diag_off;      // step k's tasks are [*_off[k], *_off[k + 1])
+    int nsteps = 0;
+};
+struct CholLists {
+    DevBuf<TileTask>&upd, &trsm, &res, &trsm2, &add;
+    DevBuf<DiagTask>& diag;
+};
+// scratch tiles (128 x 128 doubles each) the panel solves of the widest step need: one per tile below the first diagonal block
+size_t chol_blocks_scratch_tiles(const std::vector<CholBlock>& mats) {
+    size_t n = 0;
+    for (const CholBlock& b : mats) n += (size_t)(b.mpad / TB - 1);
+    return n;
+}
+// negi: 128 x 128 doubles that chol_blocks_negi fills with -I; scratch: chol_blocks_scratch_tiles(mats) tiles
+void chol_blocks_plan(const std::vector<CholBlock>& mats, double* negi, double* scratch, CholSteps& S) {
+    S = CholSteps{};
+    for (const CholBlock& b : mats) S.nsteps = std::max(S.nsteps, b.mpad / TB);
+    S.upd_off.assign((size_t)S.nsteps + 1, 0);
+    S.trsm_off.assign((size_t)S.nsteps + 1, 0);
+    S.diag_off.assign((size_t)S.nsteps + 1, 0);
+    for (int k = 0; k < S.nsteps; ++k) {
+        for (const CholBlock& b : mats) {
+            const int ntp = b.mpad, nbt = ntp / TB;
+            if (k >= nbt) continue;
+            double* F = b.F;
+            double* Dk = b.Dinv + (size_t)k * TB * TB;
+            if (k > 0)
+                for (int i = k; i < nbt; ++i) {     // F[i, k] -= F[i, 0:k] F[k, 0:k]^T, the whole K range in one task
+                    TileTask t{};
+                    t.A = F + (size_t)i * TB;
+                    t.B = F + (size_t)k * TB;
+                    t.C = F + (size_t)i * TB + (size_t)k * TB * ntp;
+                    t.lda = t.ldb = t.ldc = ntp;
+                    t.k0 = 0;
+                    t.k1 = k * TB;
+                    t.update = 1;
+                    t.sym = (i == k) ? 1 : 0;
+                    S.upd.push_back(t);
+                }
+            DiagTask dt{};
+            dt.T = F + (size_t)k * TB + (size_t)k * TB * ntp;
+            dt.Dinv = Dk;
+            dt.info = b.info;
+            dt.ld = ntp;
+            dt.nvalid = std::min(TB, b.m - k * TB);
+            dt.row0 = k * TB;
+            S.diag.push_back(dt);
+            // The panel solve X = B L_kk^-T of tile B = F[i, k] multiplies with the explicit inverse, whose error grows with the
+            // condition of L_kk (Sigma + 1e-8 I without noise: 4e-15 of ||A|| where a substitution leaves 3e-16), so it takes one
+            // step of refinement, each a launch of the existing kernels over the step's tiles:
+            //   S = B Dinv_k^T;   B <- B - S L_kk^T (the residual);   B <- B Dinv_k^T (the correction);   B <- B + S (as B - S (-I)^T)
+            for (int i = k + 1; i < nbt; ++i) {
+                double* tile = F + (size_t)i * TB + (size_t)k * TB * ntp;
+                double* Sc = scratch + (S.trsm.size() - (size_t)S.trsm_off[(size_t)k]) * TB * TB;
+                TileTask t{};
+                t.A = tile;
+                t.B = Dk;
+                t.C = Sc;
+                t.lda = ntp;
+                t.ldb = t.ldc = TB;
+                t.k0 = 0;
+                t.k1 = TB;
+                S.trsm.push_back(t);
+                TileTask r{};
+                r.A = Sc;
+                r.B = F + (size_t)k * TB + (size_t)k * TB * ntp;
+                r.C = tile;
+                r.lda = TB;
+                r.ldb = r.ldc = ntp;
+                r.k0 = 0;
+                r.k1 = TB;
+                r.update = 1;
+                S.res.push_back(r);
+                TileTask t2 = t;
+                t2.C = tile;
+                t2.ldc = ntp;
+                S.trsm2.push_back(t2);
+                TileTask a = r;
+                a.B = negi;
+                a.ldb = TB;
+                S.add.push_back(a);
+            }
+        }
+        S.upd_off[(size_t)k + 1] = (int)S.upd.size();
+        S.trsm_off[(size_t)k + 1] = (int)S.trsm.size();
+        S.diag_off[(size_t)k + 1] = (int)S.diag.size();
+    }
+}
+int chol_blocks_upload(dsmgp_ctx* c, const CholSteps& S, CholLists& Ls) {
+    if (int rc = stage_upload_list(c, Ls.upd, S.upd)) return rc;
+    if (int rc = stage_upload_list(c, Ls.trsm, S.trsm)) return rc;
+    if (int rc = stage_upload_list(c, Ls.res, S.res)) return rc;
+    if (int rc = stage_upload_list(c, Ls.trsm2, S.trsm2)) return rc;
+    if (int rc = stage_upload_list(c, Ls.add, S.add)) return rc;
+    return stage_upload_list(c, Ls.diag, S.diag);
+}
+int chol_blocks_negi(dsmgp_ctx* c, const CholSteps& S, double* negi) {
+    if (S.trsm.empty()) return 0;
+    std::vector<double> h((size_t)TB * TB, 0.0);
+    for (int i = 0; i < TB; ++i) h[(size_t)i * TB + i] = -1.0;
+    return stage_upload(c, negi, h.data(), h.size() * sizeof(double));
+}
+void chol_blocks_run(dsmgp_ctx* c, const CholSteps& S, CholLists& Ls) {
+    for (int k = 0; k < S.nsteps; ++k) {
+        const int nu = S.upd_off[(size_t)k + 1] - S.upd_off[(size_t)k], nd = S.diag_off[(size_t)k + 1] - S.diag_off[(size_t)k];
+        const int ns = S.trsm_off[(size_t)k + 1] - S.trsm_off[(size_t)k];
+        if (nu) launch_tiles(c, Ls.upd.p + S.upd_off[(size_t)k], nu);
+        if (nd) chol_diag_packed_kernel<<<nd, 256, DIAGP_LDS_BYTES, c->stream>>>(Ls.diag.p + S.diag_off[(size_t)k]);
+        if (ns) {
+            launch_tiles(c, Ls.trsm.p + S.trsm_off[(size_t)k], ns, 1);
+            launch_tiles(c, Ls.res.p + S.trsm_off[(size_t)k], ns);
+            launch_tiles(c, Ls.trsm2.p + S.trsm_off[(size_t)k], ns, 1);
+            launch_tiles(c, Ls.add.p + S.trsm_off[(size_t)k], ns);
+        }
+    }
+}
+
 // The factors of every leaf with routed rows for (with_noise, jitter): Sigma in one launch, then one round of launches per block
 // step for all leaves that still have it.  Leaves whose fit failed get the flag -1 and no task.  Marks P_SAMPLE.
 int sample_factorise(dsmgp_ctx* c, int with_noise, double jitter, hipEvent_t after_sigma) {
@@ -3899,7 +4060,6 @@ int sample_factorise(dsmgp_ctx* c, int with_noise, double jitter, hipEvent_t aft
     c->sample_off.assign((size_t)L, 0);
     std::vector<size_t> doff((size_t)L, 0);
     size_t ftot = 0, dtot = 0;
-    int maxnb = 0;
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
         if (lf.nt == 0) continue;
@@ -3907,7 +4067,6 @@ int sample_factorise(dsmgp_ctx* c, int with_noise, double jitter, hipEvent_t aft
         doff[(size_t)l] = dtot;
         ftot += (size_t)lf.ntpad * lf.ntpad;
         dtot += (size_t)lf.ntpad * TB;
-        maxnb = std::max(maxnb, lf.ntpad / TB);
     }
     // behind the inverted diagonal blocks: -I, and one scratch tile per panel solve of the widest step (step 0)
     size_t nsolve0 = 0;
@@ -3920,9 +4079,7 @@ int sample_factorise(dsmgp_ctx* c, int with_noise, double jitter, hipEvent_t aft
     if (int rc = c->d_sinfo.grow(c, (size_t)L)) return rc;
     std::vector<int> flags((size_t)L, 0);
     std::vector<PredCovTask> cov;
-    std::vector<TileTask> upd, trsm, res, trsm2, add;
-    std::vector<DiagTask> diag;
-    std::vector<int> upd_off((size_t)maxnb + 1, 0), trsm_off((size_t)maxnb + 1, 0), diag_off((size_t)maxnb + 1, 0);
+    std::vector<CholBlock> mats;
     for (int l = 0; l < L; ++l) {
         const LeafHost& lf = c->leaves[l];
         if (lf.nt == 0) continue;
@@ -3954,105 +4111,21 @@ int sample_factorise(dsmgp_ctx* c, int with_noise, double jitter, hipEvent_t aft
                 g.with_noise = with_noise ? 1 : 0;
                 cov.push_back(g);
             }
+        mats.push_back(CholBlock{F, lf.nt, ntp, c->arenaSampleDinv.p + doff[(size_t)l], c->d_sinfo.p + l});
     }
-    for (int k = 0; k < maxnb; ++k) {
-        for (int l = 0; l < L; ++l) {
-            const LeafHost& lf = c->leaves[l];
-            const int ntp = lf.ntpad, nbt = ntp / TB;
-            if (lf.nt == 0 || flags[(size_t)l] != 0 || k >= nbt) continue;
-            double* F = c->arenaSample.p + c->sample_off[(size_t)l];
-            double* Dk = c->arenaSampleDinv.p + doff[(size_t)l] + (size_t)k * TB * TB;
-            if (k > 0)
-                for (int i = k; i < nbt; ++i) {     // F[i, k] -= F[i, 0:k] F[k, 0:k]^T, the whole K range in one task
-                    TileTask t{};
-                    t.A = F + (size_t)i * TB;
-                    t.B = F + (size_t)k * TB;
-                    t.C = F + (size_t)i * TB + (size_t)k * TB * ntp;
-                    t.lda = t.ldb = t.ldc = ntp;
-                    t.k0 = 0;
-                    t.k1 = k * TB;
-                    t.update = 1;
-                    t.sym = (i == k) ? 1 : 0;
-                    upd.push_back(t);
-                }
-            DiagTask dt{};
-            dt.T = F + (size_t)k * TB + (size_t)k * TB * ntp;
-            dt.Dinv = Dk;
-            dt.info = c->d_sinfo.p + l;
-            dt.ld = ntp;
-            dt.nvalid = std::min(TB, lf.nt - k * TB);
-            dt.row0 = k * TB;
-            diag.push_back(dt);
-            // The panel solve X = B L_kk^-T of tile B = F[i, k] multiplies with the explicit inverse, whose error grows with the
-            // condition of L_kk (Sigma + 1e-8 I without noise: 4e-15 of ||A|| where a substitution leaves 3e-16), so it takes one
-            // step of refinement, each a launch of the existing kernels over the step's tiles:
-            //   S = B Dinv_k^T;   B <- B - S L_kk^T (the residual);   B <- B Dinv_k^T (the correction);   B <- B + S (as B - S (-I)^T)
-            for (int i = k + 1; i < nbt; ++i) {
-                double* tile = F + (size_t)i * TB + (size_t)k * TB * ntp;
-                double* S = c->arenaSampleDinv.p + scratch_off + (trsm.size() - (size_t)trsm_off[(size_t)k]) * TB * TB;
-                TileTask t{};
-                t.A = tile;
-                t.B = Dk;
-                t.C = S;
-                t.lda = ntp;
-                t.ldb = t.ldc = TB;
-                t.k0 = 0;
-                t.k1 = TB;
-                trsm.push_back(t);
-                TileTask r{};
-                r.A = S;
-                r.B = F + (size_t)k * TB + (size_t)k * TB * ntp;
-                r.C = tile;
-                r.lda = TB;
-                r.ldb = r.ldc = ntp;
-                r.k0 = 0;
-                r.k1 = TB;
-                r.update = 1;
-                res.push_back(r);
-                TileTask t2 = t;
-                t2.C = tile;
-                t2.ldc = ntp;
-                trsm2.push_back(t2);
-                TileTask a = r;
-                a.B = c->arenaSampleDinv.p + negi_off;
-                a.ldb = TB;
-                add.push_back(a);
-            }
-        }
-        upd_off[(size_t)k + 1] = (int)upd.size();
-        trsm_off[(size_t)k + 1] = (int)trsm.size();
-        diag_off[(size_t)k + 1] = (int)diag.size();
-    }
+    CholSteps steps;
+    chol_blocks_plan(mats, c->arenaSampleDinv.p + negi_off, c->arenaSampleDinv.p + scratch_off, steps);
     c->stage_top = 0;       // (the stream is idle: every entry point synchronises before it returns)
     if (int rc = stage_upload_list(c, c->scov, cov)) return rc;
-    if (int rc = stage_upload_list(c, c->supd, upd)) return rc;
-    if (int rc = stage_upload_list(c, c->strsm, trsm)) return rc;
-    if (int rc = stage_upload_list(c, c->sres, res)) return rc;
-    if (int rc = stage_upload_list(c, c->strsm2, trsm2)) return rc;
-    if (int rc = stage_upload_list(c, c->sadd, add)) return rc;
-    if (int rc = stage_upload_list(c, c->sdiag, diag)) return rc;
+    CholLists lists{c->supd, c->strsm, c->sres, c->strsm2, c->sadd, c->sdiag};
+    if (int rc = chol_blocks_upload(c, steps, lists)) return rc;
     if (int rc = stage_upload(c, c->d_sinfo.p, flags.data(), (size_t)L * sizeof(int))) return rc;
     HIPCHK(c, hipMemsetAsync(c->arenaSample.p, 0, std::max<size_t>(1, ftot) * sizeof(double), c->stream));
     HIPCHK(c, hipMemsetAsync(c->arenaSampleDinv.p, 0, std::max<size_t>(1, dtot) * sizeof(double), c->stream));
-    if (!trsm.empty()) {
-        std::vector<double> negi((size_t)TB * TB, 0.0);
-        for (int i = 0; i < TB; ++i) negi[(size_t)i * TB + i] = -1.0;
-        if (int rc = stage_upload(c, c->arenaSampleDinv.p + negi_off, negi.data(), negi.size() * sizeof(double))) return rc;
-    }
+    if (int rc = chol_blocks_negi(c, steps, c->arenaSampleDinv.p + negi_off)) return rc;
     if (!cov.empty()) predsample_sigma_kernel<<<(unsigned)cov.size(), 256, 0, c->stream>>>(c->scov.p, c->d_kp.p, c->D, jitter);
     HIPCHK(c, hipEventRecord(after_sigma, c->stream));
-    for (int k = 0; k < maxnb; ++k) {
-        const int nu = upd_off[(size_t)k + 1] - upd_off[(size_t)k], nd = diag_off[(size_t)k + 1] - diag_off[(size_t)k];
-        const int ns = trsm_off[(size_t)k + 1] - trsm_off[(size_t)k];
-        if (nu) launch_tiles(c, c->supd.p + upd_off[(size_t)k], nu);
-        if (nd) chol_diag_packed_kernel<<<nd, 256, DIAGP_LDS_BYTES, c->stream>>>(c->sdiag.p + diag_off[(size_t)k]);
-        if (ns) {
-            launch_tiles(c, c->strsm.p + trsm_off[(size_t)k], ns, 1);
-            launch_tiles(c, c->sres.p + trsm_off[(size_t)k], ns);
-            launch_tiles(c, c->strsm2.p + trsm_off[(size_t)k], ns, 1);
-            launch_tiles(c, c->sadd.p + trsm_off[(size_t)k], ns);
-        }
-    }
+    chol_blocks_run(c, steps, lists);
     HIPCHK(c, hipGetLastError());
     c->sample_info.assign((size_t)L, 0);
     static_assert(sizeof(int) == sizeof(int32_t), "the flags are read back as int32_t");
@@ -4961,6 +5034,313 @@ int dsmgp_loo(dsmgp_ctx* c, double* mu_out, double* var_out, double* lpd_out, do
     if (mu_out) HIPCHK(c, hipMemcpy(mu_out, dmu, nobs * sizeof(double), hipMemcpyDeviceToHost));
     if (var_out) HIPCHK(c, hipMemcpy(var_out, dvar, nobs * sizeof(double), hipMemcpyDeviceToHost));
     if (lpd_out) HIPCHK(c, hipMemcpy(lpd_out, dlpd, (size_t)L * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+namespace {
+// C^-T of every factorised block of dsmgp_kfold into `X` (block b at xoff[b], ld = mpad): the recipe of build_grad_plan's
+// inversion -- the diagonal tiles are the transposed inverted diagonal blocks, then per block step k one update launch
+// (tile (t, k) = -X[t, 128 t : 128 k] C[k, 128 t : 128 k]^T, nothing read: update = 2) and one panel solve against Dinv_k.
+struct KfoldInverseTasks {
+    std::vector<TransTask> trans;
+    std::vector<TileTask> upd, trsm;        // task for task beside each other
+    std::vector<size_t> step_off{0};        // step k's tasks are [step_off[k - 1], step_off[k])
+};
+static void kfold_inverse_tasks(const std::vector<CholBlock>& mats, double* X, const std::vector<size_t>& xoff, int nsteps,
+                         KfoldInverseTasks& out) {
+    for (size_t b = 0; b < mats.size(); ++b)
+        for (int t = 0; t < mats[b].mpad / TB; ++t) {
+            TransTask tt{};
+            tt.src = mats[b].Dinv + (size_t)t * TB * TB;
+            tt.dst = X + xoff[b] + (size_t)t * TB + (size_t)t * TB * mats[b].mpad;
+            tt.ldd = mats[b].mpad;
+            out.trans.push_back(tt);
+        }
+    for (int k = 1; k < nsteps; ++k) {
+        for (size_t b = 0; b < mats.size(); ++b) {
+            const int mp = mats[b].mpad;
+            if (mp / TB <= k) continue;
+            double* Xc = X + xoff[b];
+            for (int t = 0; t < k; ++t) {
+                double* tile = Xc + (size_t)t * TB + (size_t)k * TB * mp;
+                TileTask u{};
+                u.A = Xc + (size_t)t * TB;
+                u.B = mats[b].F + (size_t)k * TB;
+                u.C = tile;
+                u.lda = u.ldb = u.ldc = mp;
+                u.k0 = t * TB;
+                u.k1 = k * TB;
+                u.update = 2;
+                u.rev = 1;
+                out.upd.push_back(u);
+                TileTask sv{};
+                sv.A = tile;
+                sv.B = mats[b].Dinv + (size_t)k * TB * TB;
+                sv.C = tile;
+                sv.lda = mp;
+                sv.ldb = TB;
+                sv.ldc = mp;
+                sv.k0 = 0;
+                sv.k1 = TB;
+                out.trsm.push_back(sv);
+            }
+        }
+        out.step_off.push_back(out.upd.size());
+    }
+}
+}  // namespace
+
+// k-fold cross-validation of every leaf GP from the current fit (the kernels and the formulas: kernels_kfold.hpp).  The blocks come
+// from kfold_plan.hpp, once per factor owner -- a COPY leaf applies its source's factors to its own alpha, y and mean.  L^-T comes
+// by dsmgp_loo's rule (xinv_lists / xinv_fill).  The labels are packed round by round (label k of every owner, then that round's
+// G_FF tiles), so the panel arena has the largest round's size; the factorisation, the inversion and the moments run over all
+// blocks together.  Nothing another entry point reads is written, and nothing is kept but the allocations.
+int dsmgp_kfold(dsmgp_ctx* c, const int32_t* fold, int32_t K, double* mu_out, double* var_out, double* lpd_out, int32_t* info_out,
+                double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->has(P_FIT)) return fail(c, DSMGP_E_STATE, "kfold before fit");
+    if (!fold) return fail(c, DSMGP_E_ARG, "kfold: fold is NULL");
+    if (K < 1 || K > 65535) return fail(c, DSMGP_E_ARG, "kfold: K must be 1 .. 65535");
+    // every one of the N labels is checked, held by a leaf or not: what the call accepts does not depend on the leaf table or on
+    // which fits succeeded (kfold_plan::build guards itself once more; after this loop it cannot refuse)
+    for (int64_t i = 0; i < c->N; ++i)
+        if (fold[i] < -1 || fold[i] >= K) return fail(c, DSMGP_E_ARG, "kfold: a label outside -1 .. K - 1");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int L = c->L;
+    const size_t nobs = (size_t)c->obs_ptr[L];
+    const bool want_var = var_out != nullptr;
+    std::vector<int32_t> finfo((size_t)L);
+    if (int rc = fetch_fit_results(c, nullptr, finfo.data())) return rc;
+    // L^-T of every factor owner (xinv_lists / xinv_fill); lists of the call's own are dropped again on every way out
+    const bool had_xinv = c->has(P_XINV);
+    OwnGradLists own_lists{c};
+    if (int rc = xinv_lists(c, own_lists)) return rc;
+
+    // the blocks, once per factor owner whose fit succeeded
+    std::vector<kfold_plan::Owner> owners;
+    std::vector<int> owner_at((size_t)L, -1);
+    for (int l = 0; l < L; ++l)
+        if (c->leaves[l].owner == l && finfo[(size_t)l] == 0) {
+            owner_at[(size_t)l] = (int)owners.size();
+            owners.push_back(kfold_plan::Owner{l, c->leaves[l].n, c->obs_ptr[l]});
+        }
+    kfold_plan::Plan plan;
+    if (kfold_plan::build(owners, c->obs_idx.data(), fold, K, plan) != 0) return fail(c, DSMGP_E_ARG, "kfold: a label outside -1 .. K - 1");
+    const size_t nblk = plan.blocks.size();
+    std::vector<size_t> foff(nblk, 0), doff(nblk, 0), poff(nblk, 0);
+    size_t ftot = 0, dtot = 0, pmax = 0;
+    for (int32_t k = 0; k < K; ++k) {
+        size_t pk = 0;
+        for (int64_t b = plan.label_first[(size_t)k]; b < plan.label_first[(size_t)k + 1]; ++b) {
+            const kfold_plan::Block& B = plan.blocks[(size_t)b];
+            foff[(size_t)b] = ftot;
+            doff[(size_t)b] = dtot;
+            poff[(size_t)b] = pk;
+            ftot += (size_t)B.mpad * B.mpad;
+            dtot += (size_t)B.mpad * TB;
+            pk += (size_t)B.mpad * c->leaves[owners[(size_t)B.owner].id].npad;
+        }
+        pmax = std::max(pmax, pk);
+    }
+    if (int rc = arena_status(c, c->arenaKP.grow(arena_pool(c), pmax))) return rc;
+    if (int rc = arena_status(c, c->arenaKF.grow(arena_pool(c), ftot))) return rc;
+    if (want_var)
+        if (int rc = arena_status(c, c->arenaKX.grow(arena_pool(c), ftot))) return rc;
+    if (int rc = c->d_kinfo.grow(c, std::max<size_t>(1, nblk))) return rc;
+    if (int rc = c->d_kout.grow(c, 2 * nobs + (size_t)L * (size_t)K)) return rc;
+    double* dmu = c->d_kout.p;
+    double* dvar = dmu + nobs;
+    double* dlpd = dvar + nobs;
+
+    // rounds: panels and G_FF tiles of label k
+    std::vector<KfoldPackTask> pack;
+    std::vector<KfoldGffTask> gff;
+    std::vector<size_t> pack_off((size_t)K + 1, 0), gff_off((size_t)K + 1, 0);
+    std::vector<CholBlock> mats;
+    mats.reserve(nblk);
+    if (int rc = c->d_kpos.grow(c, std::max<size_t>(1, plan.pos.size()))) return rc;
+    for (int32_t k = 0; k < K; ++k) {
+        for (int64_t b = plan.label_first[(size_t)k]; b < plan.label_first[(size_t)k + 1]; ++b) {
+            const kfold_plan::Block& B = plan.blocks[(size_t)b];
+            const int ol = owners[(size_t)B.owner].id;
+            const int npad = c->leaves[ol].npad, nbt = B.mpad / TB;
+            const double* Xt = c->arenaX.p + c->gxoff[(size_t)ol];
+            double* P = c->arenaKP.p + poff[(size_t)b];
+            double* F = c->arenaKF.p + foff[(size_t)b];
+            for (int i = 0; i < nbt; ++i) {
+                const int kstart = plan.tile_first[(size_t)B.tile_off + (size_t)i] / TB * TB;
+                for (int c0 = kstart; c0 < npad; c0 += 2 * TB) {
+                    KfoldPackTask t{};
+                    t.X = Xt;
+                    t.P = P + (size_t)i * TB;
+                    t.pos = c->d_kpos.p + B.pos_off + (size_t)i * TB;
+                    t.ldx = npad;
+                    t.ldp = B.mpad;
+                    t.nrows = std::min(TB, B.m - i * TB);
+                    t.col0 = c0;
+                    t.col1 = std::min(c0 + 2 * TB, npad);
+                    pack.push_back(t);
+                }
+                for (int j = 0; j <= i; ++j) {
+                    KfoldGffTask g{};
+                    g.gemm.A = P + (size_t)i * TB;
+                    g.gemm.B = P + (size_t)j * TB;
+                    g.gemm.C = F + (size_t)i * TB + (size_t)j * TB * B.mpad;
+                    g.gemm.lda = g.gemm.ldb = g.gemm.ldc = B.mpad;
+                    g.gemm.k0 = kstart;
+                    g.gemm.k1 = npad;
+                    g.na = std::min(TB, B.m - i * TB);
+                    g.nb = std::min(TB, B.m - j * TB);
+                    g.diag = (i == j);
+                    gff.push_back(g);
+                }
+            }
+        }
+        pack_off[(size_t)k + 1] = pack.size();
+        gff_off[(size_t)k + 1] = gff.size();
+    }
+    // behind the inverted diagonal blocks: -I, and the scratch tiles of the panel solves
+    const size_t negi_off = dtot, scratch_off = dtot + (size_t)TB * TB;
+    for (size_t b = 0; b < nblk; ++b) mats.push_back(CholBlock{nullptr, plan.blocks[b].m, plan.blocks[b].mpad, nullptr, nullptr});
+    if (int rc = arena_status(c, c->arenaKD.grow(arena_pool(c), scratch_off + chol_blocks_scratch_tiles(mats) * TB * TB))) return rc;
+    for (size_t b = 0; b < nblk; ++b) {
+        mats[b].F = c->arenaKF.p + foff[b];
+        mats[b].Dinv = c->arenaKD.p + doff[b];
+        mats[b].info = c->d_kinfo.p + b;
+    }
+    CholSteps steps;
+    chol_blocks_plan(mats, c->arenaKD.p + negi_off, c->arenaKD.p + scratch_off, steps);
+
+    // C^-T of every block, and one task per (leaf, label) with rows
+    KfoldInverseTasks inv;
+    if (want_var) kfold_inverse_tasks(mats, c->arenaKX.p, foff, steps.nsteps, inv);
+    std::vector<KfoldMomTask> mom;
+    std::vector<size_t> work_off;           // per task: its w | v in d_kwork
+    size_t wtot = 0;
+    for (int l = 0; l < L; ++l) {
+        const LeafHost& lf = c->leaves[l];
+        if (finfo[(size_t)l] != 0 || owner_at[(size_t)lf.owner] < 0) continue;
+        const int al = (lf.op == DSMGP_SHARE_COPY && lf.mean == c->leaves[lf.src].mean) ? lf.src : l;   // LooTask's rule
+        for (int32_t k = 0; k < K; ++k) {
+            const int32_t b = plan.find((size_t)owner_at[(size_t)lf.owner], k);
+            if (b < 0) continue;
+            const kfold_plan::Block& B = plan.blocks[(size_t)b];
+            KfoldMomTask t{};
+            t.C = mats[(size_t)b].F;
+            t.Xc = want_var ? c->arenaKX.p + foff[(size_t)b] : nullptr;
+            t.pos = c->d_kpos.p + B.pos_off;
+            t.alpha = c->h_leaves[al].alpha;
+            t.info = c->d_kinfo.p + b;
+            t.lpd = dlpd + (size_t)l + (size_t)k * (size_t)L;
+            t.off = (long long)c->obs_ptr[l];
+            t.m = B.m;
+            t.mpad = B.mpad;
+            mom.push_back(t);
+            work_off.push_back(wtot);
+            wtot += 2 * (size_t)B.mpad;
+        }
+    }
+    if (int rc = c->d_kwork.grow(c, std::max<size_t>(1, wtot))) return rc;
+    for (size_t i = 0; i < mom.size(); ++i) mom[i].work = c->d_kwork.p + work_off[i];
+
+    c->stage_top = 0;       // (the stream is idle: every entry point synchronises before it returns)
+    if (int rc = stage_upload_list(c, c->kpack, pack)) return rc;
+    if (int rc = stage_upload_list(c, c->kgff, gff)) return rc;
+    CholLists lists{c->kupd, c->ktrsm, c->kres, c->ktrsm2, c->kadd, c->kdiag};
+    if (int rc = chol_blocks_upload(c, steps, lists)) return rc;
+    if (int rc = stage_upload_list(c, c->kxtrans, inv.trans)) return rc;
+    if (int rc = stage_upload_list(c, c->kxupd, inv.upd)) return rc;
+    if (int rc = stage_upload_list(c, c->kxtrsm, inv.trsm)) return rc;
+    if (int rc = stage_upload_list(c, c->kmom, mom)) return rc;
+    if (int rc = stage_upload(c, c->d_kpos.p, plan.pos.data(), plan.pos.size() * sizeof(int32_t))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_kinfo.p, 0, std::max<size_t>(1, nblk) * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->arenaKD.p, 0, std::max<size_t>(1, dtot) * sizeof(double), c->stream));
+    if (int rc = chol_blocks_negi(c, steps, c->arenaKD.p + negi_off)) return rc;
+    HIPCHK(c, hipMemsetAsync(dmu, 0xff, std::max<size_t>(1, 2 * nobs) * sizeof(double), c->stream));   // NaN: rows no block holds
+    HIPCHK(c, hipMemsetAsync(dlpd, 0, (size_t)L * (size_t)K * sizeof(double), c->stream));             // empty blocks
+
+    EventPair e01, e23, e4;     // e01.a .. e01.b L^-T, .. e23.a pack and G_FF, .. e23.b factorisation, .. e4.a inversion and moments
+    HIPCHK(c, e01.init());
+    HIPCHK(c, e23.init());
+    HIPCHK(c, e4.init());
+    HIPCHK(c, hipEventRecord(e01.a, c->stream));
+    if (int rc = ensure_dinv(c)) return rc;
+    if (int rc = ensure_alpha(c)) return rc;
+    if (int rc = xinv_fill(c)) return rc;
+    HIPCHK(c, hipEventRecord(e01.b, c->stream));
+    for (int32_t k = 0; k < K; ++k) {
+        const size_t np = pack_off[(size_t)k + 1] - pack_off[(size_t)k], ng = gff_off[(size_t)k + 1] - gff_off[(size_t)k];
+        if (np) kfold_pack_kernel<<<(unsigned)np, 256, 0, c->stream>>>(c->kpack.p + pack_off[(size_t)k]);
+        if (ng) kfold_gff_kernel<<<(unsigned)ng, 256, 0, c->stream>>>(c->kgff.p + gff_off[(size_t)k]);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(e23.a, c->stream));
+    chol_blocks_run(c, steps, lists);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(e23.b, c->stream));
+    if (want_var) {
+        if (!inv.trans.empty()) transpose_tile_kernel<<<(unsigned)inv.trans.size() * 16, 256, 0, c->stream>>>(c->kxtrans.p);
+        for (size_t s = 0; s + 1 < inv.step_off.size(); ++s) {
+            const int n = (int)(inv.step_off[s + 1] - inv.step_off[s]);
+            if (n == 0) continue;
+            launch_tiles(c, c->kxupd.p + inv.step_off[s], n);
+            launch_tiles(c, c->kxtrsm.p + inv.step_off[s], n, 1);
+        }
+    }
+    if (!mom.empty())
+        kfold_moments_kernel<<<(unsigned)mom.size(), 256, 0, c->stream>>>(c->kmom.p, c->d_obs_idx.p, c->dy.p, dmu, dvar);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(e4.a, c->stream));
+    std::vector<int> binfo(std::max<size_t>(1, nblk), 0);
+    HIPCHK(c, hipMemcpyAsync(binfo.data(), c->d_kinfo.p, std::max<size_t>(1, nblk) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = stage_done(c)) return rc;
+    c->mark(P_XINV);
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, e01.a, e4.a));
+    if (seconds) *seconds = ms * 1e-3;
+    // the four parts add up to the call's time: with L^-T current part [0] is 0 by definition, and what was left to complete of
+    // the diagonal-block inverses and alpha (e01.a .. e01.b then) counts with part [1]
+    HIPCHK(c, hipEventElapsedTime(&ms, e01.a, e01.b));
+    c->kfold_seconds[0] = had_xinv ? 0.0 : ms * 1e-3;
+    HIPCHK(c, hipEventElapsedTime(&ms, had_xinv ? e01.a : e01.b, e23.a));
+    c->kfold_seconds[1] = ms * 1e-3;
+    HIPCHK(c, hipEventElapsedTime(&ms, e23.a, e23.b));
+    c->kfold_seconds[2] = ms * 1e-3;
+    HIPCHK(c, hipEventElapsedTime(&ms, e23.b, e4.a));
+    c->kfold_seconds[3] = ms * 1e-3;
+    if (mu_out) HIPCHK(c, hipMemcpy(mu_out, dmu, nobs * sizeof(double), hipMemcpyDeviceToHost));
+    if (var_out) HIPCHK(c, hipMemcpy(var_out, dvar, nobs * sizeof(double), hipMemcpyDeviceToHost));
+    if (lpd_out) HIPCHK(c, hipMemcpy(lpd_out, dlpd, (size_t)L * (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
+    // per (leaf, label): -1 and NaN where the leaf's fit failed, else the block's flag (0 for an empty block)
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    for (int l = 0; l < L; ++l) {
+        const bool failed = finfo[(size_t)l] != 0;
+        const int oa = owner_at[(size_t)c->leaves[l].owner];
+        for (int32_t k = 0; k < K; ++k) {
+            const size_t at = (size_t)l + (size_t)k * (size_t)L;
+            if (failed) {
+                if (lpd_out) lpd_out[at] = qnan;
+                if (info_out) info_out[at] = -1;
+                continue;
+            }
+            const int32_t b = oa >= 0 ? plan.find((size_t)oa, k) : -1;
+            if (info_out) info_out[at] = b >= 0 ? binfo[(size_t)b] : 0;
+        }
+    }
+    return 0;
+}
+
+int dsmgp_kfold_stats(dsmgp_ctx* c, int64_t* out) {
+    if (!c || !out) return DSMGP_E_ARG;
+    const DevArena* a[4] = {&c->arenaKP, &c->arenaKF, &c->arenaKD, &c->arenaKX};
+    for (int i = 0; i < 4; ++i) out[i] = (int64_t)(a[i]->p ? a[i]->cap * sizeof(double) : 0);
+    return 0;
+}
+
+int dsmgp_kfold_seconds(dsmgp_ctx* c, double* out) {
+    if (!c || !out) return DSMGP_E_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = c->kfold_seconds[i];
     return 0;
 }
 

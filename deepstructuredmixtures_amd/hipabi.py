@@ -83,6 +83,9 @@ SIGNATURES = {
     "dsmgp_gradients": (C.c_int, [_ctx, _dp, C.c_int32]),
     "dsmgp_loo": (C.c_int, [_ctx, _dp, _dp, _dp, _dp]),
     "dsmgp_loo_gradients": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp]),
+    "dsmgp_kfold": (C.c_int, [_ctx, _ip, C.c_int32, _dp, _dp, _dp, _ip, _dp]),
+    "dsmgp_kfold_seconds": (C.c_int, [_ctx, _dp]),
+    "dsmgp_kfold_stats": (C.c_int, [_ctx, _lp]),
     "dsmgp_set_gradient_leaves": (C.c_int, [_ctx, _ip]),
     "dsmgp_set_option": (C.c_int, [_ctx, C.c_int32, C.c_int32]),
     "dsmgp_lanes": (C.c_int, [_ctx, _ip]),
@@ -223,6 +226,7 @@ class Context:
             raise DsmgpError(rc, msg)
         self.L = 0
         self.n_obs = 0          # obs_ptr[L] of the leaf table (set_leaves): the length of loo's outputs
+        self.N = 0              # rows of the training set (set_train, append_rows): the length of kfold's labels
         self.D = 0
         self.route_total = 0
         self.n_t = 0
@@ -256,6 +260,7 @@ class Context:
         assert X.ndim == 2 and y.shape == (X.shape[0],)
         self._chk(self.lib.dsmgp_set_train(self.h, px, py, X.shape[0], X.shape[1]))
         self.D = X.shape[1]
+        self.N = X.shape[0]     # rows of the training set: the length of kfold's labels
 
     def set_leaves(self, obs_ptr, obs_idx, kernel_id, mean):
         obs_ptr, p0 = _i64(obs_ptr)
@@ -323,6 +328,7 @@ class Context:
             # shapes follow it, so that fit / loo / targets_fetch of a caller that goes on with this context have the right lengths
             self.leaf_n = self.leaf_n + np.diff(add_ptr)
             self.n_obs = int(self.leaf_n.sum())
+            self.N += int(X_new.shape[0])
             # keep_test: the mirror of the resident test set stays, unless the library had none or had to drop it
             if not (keep_test and rc == 0 and not self.resume_stats()["test_set_dropped"]
                     and self.lib.dsmgp_routes(self.h, None, None) == 0):
@@ -523,6 +529,41 @@ class Context:
         self._chk(self.lib.dsmgp_loo(self.h, mu.ctypes.data_as(_dp), var.ctypes.data_as(_dp), lpd.ctypes.data_as(_dp), C.byref(sec)))
         self.loo_seconds = sec.value
         return mu, var, lpd
+
+    def kfold(self, fold, K=None, want_var=True):
+        """k-fold cross-validation of every leaf on the current fit (dsmgp_kfold; the multiple-fold residual formulas, mean and
+        hyper-parameters held fixed): `fold[r]` is the label of training row r, -1 .. K - 1 (`K` defaults to `max(fold) + 1`);
+        rows labelled -1 are never held out.  Returns `(mu, var, lpd, info)`: `mu`, `var` of length `obs_ptr[L]` in the layout
+        of `loo` (the joint held-out mean and the diagonal of the held-out covariance of the row's block; NaN for rows with
+        label -1; `var` is None with `want_var=False`, and none of the work behind it runs), `lpd[l, k]` the joint log
+        predictive density of leaf l's rows with label k (0 for an empty block) and `info[l, k]` (0, -1 for a leaf whose fit
+        failed, j > 0 for a block that is not positive definite).  The device time of the call is left in `self.kfold_seconds`,
+        its split (L^-T, pack + G_FF, factorisation, moments) in `self.kfold_split_seconds`."""
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        if fold.shape != (self.N,):
+            raise ValueError(f"kfold: fold must hold one label per training row ({self.N}), got shape {fold.shape}")
+        if K is None:
+            K = int(fold.max()) + 1 if fold.size else 1
+        K = int(K)
+        mu = np.empty(self.n_obs)
+        var = np.empty_like(mu) if want_var else None
+        lpd = np.empty((self.L, max(K, 0)), order="F")
+        info = np.empty((self.L, max(K, 0)), dtype=np.int32, order="F")
+        sec = C.c_double(0.0)
+        self._chk(self.lib.dsmgp_kfold(self.h, fold.ctypes.data_as(_ip), K, mu.ctypes.data_as(_dp),
+                                       var.ctypes.data_as(_dp) if want_var else None, lpd.ctypes.data_as(_dp),
+                                       info.ctypes.data_as(_ip), C.byref(sec)))
+        self.kfold_seconds = sec.value
+        split = np.zeros(4)
+        self._chk(self.lib.dsmgp_kfold_seconds(self.h, split.ctypes.data_as(_dp)))
+        self.kfold_split_seconds = split
+        return mu, var, lpd, info
+
+    def kfold_stats(self):
+        """Bytes held for `kfold` right now (dsmgp_kfold_stats): dict(packed, factors, diag_inverses, inverse_factors)."""
+        out = np.zeros(4, dtype=np.int64)
+        self._chk(self.lib.dsmgp_kfold_stats(self.h, out.ctypes.data_as(_lp)))
+        return dict(zip(("packed", "factors", "diag_inverses", "inverse_factors"), (int(v) for v in out)))
 
     def loo_gradients(self, stride):
         """`(grad, lpd)`: the true derivatives of every leaf's LOO log predictive density `lpd[l]` (the `lpd` of `loo()`, same
@@ -1188,6 +1229,29 @@ class MultiContext:
         self.loo_seconds = max(s.loo_seconds for s in self.act)
         return mu, var, lpd
 
+    def kfold(self, fold, K=None, want_var=True):
+        """`Context.kfold` per sub-context, put back into the order of the whole leaf table (leaves are independent);
+        `self.kfold_seconds` is the longest of the sub-contexts' device times, `self.kfold_split_seconds` the longest per part."""
+        self._upload()
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        if K is None:
+            K = int(fold.max()) + 1 if fold.size else 1
+        res = self._each(lambda s: s.kfold(fold, K, want_var))
+        ptr = self._leaves[0]
+        mu = np.empty(int(ptr[-1]))
+        var = np.empty_like(mu) if want_var else None
+        lpd = np.empty((self.L, K))
+        info = np.empty((self.L, K), dtype=np.int32)
+        for (m, v, d, i), sub in zip(res, self.subsets):
+            sub.put_entries(mu, ptr, m)
+            if want_var:
+                sub.put_entries(var, ptr, v)
+            sub.put_leaves(lpd, d)
+            sub.put_leaves(info, i)
+        self.kfold_seconds = max(s.kfold_seconds for s in self.act)
+        self.kfold_split_seconds = np.max([s.kfold_split_seconds for s in self.act], axis=0)
+        return mu, var, lpd, info
+
     def timings(self):
         ts = [s.timings() for s in self.act]
         return {k: max(t[k] for t in ts) for k in ts[0]}
@@ -1531,6 +1595,10 @@ class StreamingContext:
     def loo(self):
         raise DsmgpError(E_STATE, "loo: a streaming pass discards the factors and L^-T with their leaf group; "
                                   "use a resident Context for leave-one-out moments")
+
+    def kfold(self, fold, K=None, want_var=True):
+        raise DsmgpError(E_STATE, "kfold: a streaming pass discards the factors and L^-T with their leaf group; "
+                                  "use a resident Context for k-fold moments")
 
     def loo_gradients(self, stride):
         raise DsmgpError(E_STATE, "loo_gradients: a streaming pass discards the factors and L^-T with their leaf group; "

@@ -1941,6 +1941,92 @@ def loo_scores(model):
     return dict(mse=mse(y, mu), sse=sse(y, mu), mae=mae(y, mu), sae=sae(y, mu), nlpd=nlpd(y, mu, var))
 
 
+# ------------------------------------------------------------------------------------ k-fold
+
+def make_folds(n, K, seed=0, groups=None):
+    """int32 fold labels 0 .. K - 1 for `n` rows, balanced (sizes differ by at most one) and shuffled with the portable counter
+    stream of `datagen` (two machines draw the same folds).  With `groups` (one value per row) the units that are shuffled and
+    dealt are the distinct groups, in the order of their first row: rows of one group share a label, and the labels are balanced
+    in groups."""
+    from .datagen import uniform
+    n, K = int(n), int(K)
+    if K < 1:
+        raise ValueError("make_folds: K must be at least 1")
+    if groups is None:
+        unit = np.arange(n, dtype=np.int64)
+        n_units = n
+    else:
+        groups = np.asarray(groups)
+        if groups.shape != (n,):
+            raise ValueError("make_folds: groups must have one value per row")
+        _, first, inv = np.unique(groups, return_index=True, return_inverse=True)
+        rank = np.empty(first.size, dtype=np.int64)
+        rank[np.argsort(first, kind="stable")] = np.arange(first.size)     # groups numbered by their first row
+        unit = rank[inv.reshape(-1)]
+        n_units = first.size
+    order = np.argsort(uniform(int(seed), 0, n_units), kind="stable")       # a permutation: unit order[j] is dealt j-th
+    label = np.empty(n_units, dtype=np.int32)
+    label[order] = (np.arange(n_units) % K).astype(np.int32)
+    return np.ascontiguousarray(label[unit], dtype=np.int32)
+
+
+def kfold(model, fold):
+    """k-fold cross-validation of every leaf GP on the current fit (`dsmgp_kfold`; the multiple-fold residual formulas), the
+    mean and the hyper-parameters held fixed: `fold[r]` is the label of training row r, -1 (never held out) .. K - 1 with
+    K = max(fold) + 1.  dict(obs, mu, var, lpd, info) per leaf in the model's leaf order, in the shape of `loo(model)`:
+    `mu[l]` / `var[l]` the moments at the leaf's rows of the leaf's GP fitted without the rows that share the row's label (NaN
+    for label -1), `lpd` `(L, K)` the joint log predictive density of every (leaf, label) block and `info` `(L, K)` its flag.
+    Works on a `GaussianProcess` too.  Single rank only, as `loo`."""
+    target = model.model if isinstance(model, GaussianProcess) else model
+    if target.shard.world > 1:
+        raise NotImplementedError("kfold: k-fold moments are served on a single rank only")
+    fold = np.ascontiguousarray(fold, dtype=np.int32)
+    if fold.shape != (target.x.shape[0],):
+        raise ValueError("kfold: fold must have one label per training row")
+    mu, var, lpd, info = target.ctx.kfold(fold)
+    ptr, idx = obs_table(target.leaves)
+    return dict(obs=[np.asarray(idx[ptr[l]:ptr[l + 1]], dtype=np.int64) for l in range(target.L)],
+                mu=[mu[ptr[l]:ptr[l + 1]] for l in range(target.L)],
+                var=[var[ptr[l]:ptr[l + 1]] for l in range(target.L)], lpd=np.asarray(lpd), info=np.asarray(info))
+
+
+def _kfold_held(obs, mu, var, fold):
+    """The per-leaf tables of `kfold` without the rows that are never held out (label -1): what `_loo_substitute` takes."""
+    keep = [np.asarray(fold)[np.asarray(o, dtype=np.int64)] >= 0 for o in obs]
+    return ([np.asarray(o)[k] for o, k in zip(obs, keep)], [np.asarray(m)[k] for m, k in zip(mu, keep)],
+            [np.asarray(v)[k] for v, k in zip(var, keep)])
+
+
+def kfold_predict(model, fold):
+    """(mu, var) per training row: `loo_predict`'s construction with the held-out moments of `kfold(model, fold)` substituted --
+    for every leaf that holds the row among its observations, that leaf's moments fitted without the row's fold; leaves that
+    never saw the row, and rows with label -1, keep their ordinary prediction.  The entries are aggregated by the model's own
+    family rule on the host.  Single rank only."""
+    res = kfold(model, fold)
+    if isinstance(model, GaussianProcess):
+        model = model.model
+    xt = model.x
+    rc = _routing(model, xt)
+    mu, var = _leaf_moments(model, xt, rc)
+    obs, mu_k, var_k = _kfold_held(res["obs"], res["mu"], res["var"], fold)
+    mu, var = _loo_substitute(rc["ptr"], rc["idx"], mu, var, obs, mu_k, var_k)
+    if model.family == "dsmgp":
+        if model.root.kind != "gp" and not model.tindex.weights_normalised():
+            return _aggregate_dsmgp(model, xt, rc["ptr"], mu, var)
+        return _aggregate_dsmgp_flat(model, xt.shape[0], rc, mu, var)
+    return _aggregate_poe(model, xt, rc["ptr"], mu, var)
+
+
+def kfold_scores(model, fold):
+    """dict(mse, sse, mae, sae, nlpd) of the training targets against `kfold_predict(model, fold)`, over the rows that were
+    held out (label >= 0)."""
+    mu, var = kfold_predict(model, fold)
+    y = (model.model if isinstance(model, GaussianProcess) else model).y
+    held = np.asarray(fold) >= 0
+    y, mu, var = y[held], mu[held], var[held]
+    return dict(mse=mse(y, mu), sse=sse(y, mu), mae=mae(y, mu), sae=sae(y, mu), nlpd=nlpd(y, mu, var))
+
+
 def _aggregate_dsmgp_flat(model, n_t, rc, mu, var):
     """The nested log-domain recursion of `_predict` (`src/common.jl:275-302`) is linear in the leaf quantities
     (mu - c, mu^2, sigma^2): unrolled, a test row's prediction is the flat mixture over the leaves it visits with

@@ -611,6 +611,54 @@ int dsmgp_set_gradient_leaves(dsmgp_ctx* ctx, const int32_t* active /* L flags, 
  * arena only; it is dropped with the leaf table and dsmgp_release. */
 int dsmgp_loo(dsmgp_ctx* ctx, double* mu_out, double* var_out /* obs_ptr[L] each, in obs_idx order; may be NULL */,
               double* lpd_out /* L; may be NULL */, double* seconds /* may be NULL */);
+/* k-fold cross-validation of every leaf GP from the current fit, the mean and the hyper-parameters held fixed: whole groups of
+ * rows held out at once, without refitting.  fold[r] is the label of training row r, -1 .. K - 1.  For leaf l and label k the
+ * block is F(l, k) = { i : fold[obs_idx[obs_ptr[l] + i]] == k }, positions ascending.  With G = K_y^-1 and alpha = G (y - m)
+ * (dsmgp_loo's K_y), the leaf fitted without the rows of F predicts them jointly as (the multiple-fold residuals, e.g.
+ * Ginsbourger & Schaerer 2021)
+ *   mu_F = y_F - G_FF^-1 alpha_F,   Sigma_F = G_FF^-1,
+ *   lpd_F = log N(y_F | mu_F, Sigma_F) = -1/2 alpha_F^T G_FF^-1 alpha_F + 1/2 log det G_FF - (|F| / 2) log 2 pi.
+ * mu_out[obs_ptr[l] + i] and var_out[obs_ptr[l] + i] for i in F(l, k) are mu_F and diag Sigma_F, in dsmgp_loo's layout and
+ * meaning (var carries the noise and the fit's 1e-8 jitter); lpd_out[l + k L] is the joint density.  Singleton blocks are
+ * dsmgp_loo's formulas; one block that holds the whole leaf gives mu = m, Sigma = K_y and lpd = the fit's mll.
+ * An empty block gives lpd = 0 and info = 0.  A row with label -1 is never held out: it belongs to no block, trains every fold, and
+ * its mu and var come back as NaN (K = 1 with labels 0 / -1 scores a validation subset from one full fit).  Rows that no leaf
+ * holds are ignored.  info_out[l + k L]: 0 = success; -1 = a leaf whose fit reported info != 0 (all of that leaf's outputs are
+ * NaN); j > 0 = the leading minor of order j of G_FF is not positive definite, LAPACK's convention (only that block is NaN;
+ * defensive: G_FF is a principal submatrix of an SPD matrix).  Other leaves and blocks are unaffected.  Any output may be NULL;
+ * with var_out = NULL the inverse factors behind the variances are neither computed nor allocated.
+ * A COPY leaf has its source's observation list: the blocks are formed and factorised once per factor owner and the COPY leaf
+ * applies them to its own alpha, y and mean.  A PREFIX leaf owns its factor.
+ * DSMGP_E_STATE: no fit on the current leaf table and hyper-parameters.  DSMGP_E_ARG: fold is NULL, K < 1 or K > 65535, a label
+ * outside -1 .. K - 1 on ANY of the N rows (a row that no leaf holds is ignored in every other respect, but its label must be a
+ * label: what the call accepts depends on neither the leaf table nor on which fits succeeded), or where dsmgp_loo refuses because the lists of the inversion cannot be built.  DSMGP_E_NOMEM: the arenas do
+ * not fit; the context stays usable.  L^-T follows dsmgp_loo's rule: read when the arena holds this fit's, filled otherwise; the
+ * mask of dsmgp_set_gradient_leaves does not apply and is left as it is, and dsmgp_gradients behaves exactly as before.  Nothing
+ * another entry point reads is written: dsmgp_fit's outputs, dsmgp_loo*, dsmgp_gradients, dsmgp_predict_*, dsmgp_targets_fetch
+ * and dsmgp_aggregate* return the same bits before and after.  Sums run in a fixed order with no atomics: the same bits from
+ * call to call, and a block's results depend on its row set only -- renumbering the labels, or changing the labels of rows
+ * outside the leaf, leaves mu, var and the block's lpd bit-identical.  The call keeps no product: labels arrive per call and
+ * nothing is cached but L^-T.
+ * Memory, per factor owner with blocks of m rows (mpad = m rounded up to 128): mpad^2 doubles per block for G_FF and its factor,
+ * as much again for the inverse factors when var_out is given, 128 mpad for the inverted diagonal blocks, the packed rows of one
+ * label at a time (mpad x npad per block, the largest label's total: about 1 / K of the L^-T arena for balanced folds), and
+ * 2 obs_ptr[L] + L K doubles of results (the host plans with one counter per label and one record per non-empty block, not with an
+ * L x K table; the caller's own lpd_out and info_out are L x K).  Grow-only, allocated on first use (the arenas from the reserved pool when there is
+ * one), NOT counted by dsmgp_estimate_bytes / dsmgp_memory, dropped with the leaf table and dsmgp_release.
+ * seconds (may be NULL): device time of the call. */
+int dsmgp_kfold(dsmgp_ctx* ctx, const int32_t* fold /* N: label of every training row, -1 .. K-1 */, int32_t K,
+                double* mu_out /* obs_ptr[L], may be NULL */, double* var_out /* obs_ptr[L], may be NULL */,
+                double* lpd_out /* L x K column-major, ld = L, may be NULL */,
+                int32_t* info_out /* L x K, ld = L, may be NULL */, double* seconds /* may be NULL */);
+/* Device seconds of the last successful dsmgp_kfold, split: out[0] the L^-T inversion with what was left to complete of the
+ * diagonal-block inverses and of alpha (0 when the arena was current: that completion then counts with out[1]), out[1] packing
+ * the held-out rows and forming G_FF, out[2] the factorisation, out[3] the inverse factors, solves and moments.  The four add up
+ * to the call's `seconds`. */
+int dsmgp_kfold_seconds(dsmgp_ctx* ctx, double* out /* 4 */);
+/* Bytes the context holds for dsmgp_kfold right now: out[0] the packed rows of one label, out[1] the block factors, out[2] the
+ * inverted diagonal blocks and the panel solves' scratch, out[3] the inverse factors (0 until a call with var_out asks for them).
+ * All 0 before the first call and after the leaf table or dsmgp_release dropped them. */
+int dsmgp_kfold_stats(dsmgp_ctx* ctx, int64_t* out /* 4 */);
 /* Gradients of the leaf's LOO log predictive density lpd_l (dsmgp_loo's lpd_out[l]) with respect to its log-scale
  * hyper-parameters (GPML 5.4.2, eq. 5.13), the mean held fixed: what makes leave-one-out a training objective.  With G = K_y^-1,
  * d = diag G, alpha = G (y - m):

@@ -35,7 +35,7 @@ import DeepStructuredMixtures: fit!, fit_naive!, update_cholesky!, prediction, m
 using DeepStructuredMixtures: GPNode, GPSumNode, GPSplitNode, DSMGP, PoE, gPoE, rBCM, BiDict, GaussianProcess,
                               IsoSE, ArdSE, IsoLinear, ArdLinear, ConstMean, getLeaves, getchild, children, logweights, getnoise
 
-export attach!, detach!, census, append_rows!, append_stats, resume_stats, download_vt, predict_cov, predict_sample, predict_cov_factor, predict_gradients, aggregate_gradients, aggregate_columns, aggregate_columns_gradients, loo, loo_gradients, solve_targets, predict_targets, predict_targets_gradients, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
+export attach!, detach!, census, append_rows!, append_stats, resume_stats, download_vt, predict_cov, predict_sample, predict_cov_factor, predict_gradients, aggregate_gradients, aggregate_columns, aggregate_columns_gradients, loo, loo_gradients, kfold, kfold_seconds, solve_targets, predict_targets, predict_targets_gradients, targets_fetch, targets_gradients, loo_targets, loo_targets_gradients, ArdSEProduct, IsoMatern32, IsoMatern52, ArdMatern32, ArdMatern52, IsoRQ, ArdRQ
 
 # ---------------------------------------------------------------------------------------------- ArdSEProduct
 """
@@ -542,6 +542,36 @@ function loo(s::Session)
                                        s.h, μ, σ², lpd, sec))
     off = cumsum(vcat(0, cnt))
     return [μ[off[l]+1:off[l+1]] for l in 1:L], [σ²[off[l]+1:off[l+1]] for l in 1:L], lpd
+end
+
+"kfold(s, fold, K; want_var=true): k-fold cross-validation of every leaf GP on the current fit (dsmgp_kfold; the multiple-fold
+residual formulas), mean and hyper-parameters held fixed.  `fold[r]` is the label of training row r in the ABI's numbering,
+-1 (never held out) and 0 … K-1.  Returns (μ, σ², lpd, info): per leaf, in the order of `s.leaves` and aligned with its observation
+list, the joint held-out moments of the row's block (NaN for label -1; `σ² === nothing` with `want_var=false`, and none of the
+work behind it runs), and the `L × K` tables of the blocks' joint log predictive densities and flags.  L⁻ᵀ is reused as by loo."
+function kfold(s::Session, fold::AbstractVector{<:Integer}, K::Integer; want_var::Bool=true)
+    L = length(s.leaves)
+    cnt = [length(lf.obs) for lf in s.leaves]
+    tot = sum(cnt)
+    f = Vector{Int32}(fold)
+    μ = Vector{Float64}(undef, tot)
+    σ² = Vector{Float64}(undef, want_var ? tot : 0)
+    lpd = Matrix{Float64}(undef, L, K)
+    info = Matrix{Int32}(undef, L, K)
+    sec = Ref{Float64}(0.0)
+    GC.@preserve f μ σ² lpd info chk(s, ccall(sym(:dsmgp_kfold), Cint,
+        (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{Float64}),
+        s.h, f, Int32(K), μ, want_var ? pointer(σ²) : Ptr{Float64}(C_NULL), lpd, info, sec))
+    off = cumsum(vcat(0, cnt))
+    return [μ[off[l]+1:off[l+1]] for l in 1:L], (want_var ? [σ²[off[l]+1:off[l+1]] for l in 1:L] : nothing), lpd, info
+end
+
+"kfold_seconds(s): device seconds of the last kfold, split into (L⁻ᵀ inversion — 0 when it was current, packing and G_FF,
+factorisation, solves and moments)."
+function kfold_seconds(s::Session)
+    out = zeros(Float64, 4)
+    GC.@preserve out chk(s, ccall(sym(:dsmgp_kfold_seconds), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.h, out))
+    return out
 end
 
 "predict_gradients(s; want_var=true): the gradients of the predictive mean and variance of every (leaf, routed test row) entry of
