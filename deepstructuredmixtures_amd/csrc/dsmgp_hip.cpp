@@ -6,6 +6,7 @@
 #include "../../include/dsmgp_hip_diag.h"
 #endif
 #include "kernels.hpp"
+#include "kernels_agg.hpp"
 #include "kernels_fused.hpp"
 #include "kernels_targets.hpp"
 #include "kernels_sample.hpp"
@@ -20,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -545,7 +547,7 @@ struct TestProducts {
     DevBuf<double> d_agg_coef;      // L
     DevBuf<int32_t> d_agg_group;    // L
     DevBuf<double> d_agg_out;       // mu | var (n_t each) | y_test (n_t) | score block sums
-    DevBuf<double> d_agg_gpart;     // dsmgp_aggregate_gradients*: Wg x n_t gradient sums (agg_gradients_width)
+    DevBuf<double> d_agg_gpart;     // dsmgp_aggregate_gradients*: Wg x n_t gradient sums (agg_width with D)
     DevBuf<double> d_agg_gout;      // dmu | dvar of the aggregated prediction, n_t x D each
     DevBuf<double> d_col_coef;      // dsmgp_aggregate_columns*: L, a state of its own beside d_agg_*
     DevBuf<int32_t> d_col_group;    // L
@@ -796,6 +798,11 @@ struct RouteTreeStore {
 };
 static_assert(std::is_nothrow_move_assignable_v<RouteTreeStore>, "RouteTreeStore falls by assignment (reset)");
 
+// A resident aggregation family (kernels_agg.hpp): the family, its number of rBCM groups and the number of its moment sums
+struct AggState {
+    int family = -1, G = 0, W = 0;
+};
+
 // What lives as long as the context, and the plain numbers that describe a group without falling with it
 struct dsmgp_ctx : Validity, PlanStore, TestInputs, TestProducts, GradLists, GradStore, TargetsStore, KfoldStore, RouteTreeStore {
     // `valid`: what is current (ctx_state.hpp).  HOW a product was made is a plain member:
@@ -879,8 +886,8 @@ struct dsmgp_ctx : Validity, PlanStore, TestInputs, TestProducts, GradLists, Gra
     std::vector<int64_t> route_ptr;
     int64_t route_total = 0;
     size_t acc_off = 0, acc_count = 0;      // the accumulators' part of arenaPV (register_test)
-    int agg_family = -1, agg_G = 0, agg_W = 0;      // P_PARTIAL: what d_agg_part holds (dsmgp_aggregate_partial)
-    int col_family = -1, col_G = 0;                 // P_CDONE: the family of the last dsmgp_aggregate_columns
+    AggState agg;       // P_PARTIAL: what d_agg_part holds (dsmgp_aggregate_partial)
+    AggState col;       // P_CDONE: the family of the last dsmgp_aggregate_columns
     // pinned host staging for the uploads of a registration (stage_upload): the lists of a test set are ~10 MB at the headline
     // model; through hipMemcpy from pageable vectors they took 9 ms of a 25 ms registration and left the runtime busy behind them
     char* stage = nullptr;
@@ -2178,6 +2185,23 @@ struct EventPair {
     hipError_t init() {
         hipError_t e = hipEventCreate(&a);
         return e != hipSuccess ? e : hipEventCreate(&b);
+    }
+    // init, then `launch()` between the two events on `st`; a launch error is returned
+    template <class Launch>
+    hipError_t timed(hipStream_t st, Launch&& launch) {
+        hipError_t e = init();
+        if (e == hipSuccess) e = hipEventRecord(a, st);
+        if (e != hipSuccess) return e;
+        launch();
+        e = hipGetLastError();
+        return e != hipSuccess ? e : hipEventRecord(b, st);
+    }
+    // after a synchronisation: the seconds between the two events, added to `seconds`
+    hipError_t add_seconds(double& seconds) const {
+        float ms = 0.f;
+        const hipError_t e = hipEventElapsedTime(&ms, a, b);
+        seconds += ms * 1e-3;
+        return e;
     }
     ~EventPair() {
         if (a) (void)hipEventDestroy(a);
@@ -4239,91 +4263,8 @@ int dsmgp_predict_cov_factor(dsmgp_ctx* c, int32_t leaf, double* Lc_out, int64_t
 }
 
 // -------------------------------------------------------------------------------------------------
-// predict(model, x): aggregation over the leaves of every test row, and the score functions, on the device
-namespace {
-int agg_width(int family, int G) { return family == AGG_MIXTURE ? 3 : (family == AGG_RBCM ? 2 * G : 2); }
-}  // namespace
-
-int dsmgp_aggregate_partial(dsmgp_ctx* c, int32_t family, const double* leaf_coef, const int32_t* leaf_group,
-                            int32_t n_groups, double* partial_out) {
-    if (!c) return DSMGP_E_ARG;
-    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "aggregate before predict_run");
-    if (family < AGG_MIXTURE || family > AGG_RBCM) return fail(c, DSMGP_E_ARG, "aggregate: unknown family");
-    if (family == AGG_RBCM) {
-        if (!leaf_group || n_groups <= 0 || n_groups > 4096) return fail(c, DSMGP_E_ARG, "aggregate: rBCM needs leaf groups");
-        for (int l = 0; l < c->L; ++l)
-            if (leaf_group[l] < 0 || leaf_group[l] >= n_groups) return fail(c, DSMGP_E_ARG, "aggregate: leaf group out of range");
-    } else if (!leaf_coef) {
-        return fail(c, DSMGP_E_ARG, "aggregate: leaf_coef is NULL");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const int L = c->L;
-    const int G = family == AGG_RBCM ? n_groups : 0;
-    const int W = agg_width(family, G);
-    const size_t need = (size_t)W * (size_t)c->n_t;
-    if (int rc = c->d_agg_part.grow(c, need)) return rc;
-    if (int rc = c->d_agg_coef.grow(c, (size_t)L)) return rc;
-    if (int rc = c->d_agg_group.grow(c, (size_t)L)) return rc;
-    if (leaf_coef) HIPCHK(c, hipMemcpyAsync(c->d_agg_coef.p, leaf_coef, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (family == AGG_RBCM)
-        HIPCHK(c, hipMemcpyAsync(c->d_agg_group.p, leaf_group, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    AggArgs a{};
-    a.row_ptr = c->d_row_ptr.p;
-    a.row_ent = c->d_row_ent.p;
-    a.ent_leaf = c->d_ent_leaf.p;
-    a.mu = c->arenaPV.p;
-    a.var = c->arenaPV.p + (size_t)c->route_total;
-    a.coef = c->d_agg_coef.p;
-    a.group = c->d_agg_group.p;
-    a.part = c->d_agg_part.p;
-    a.n_t = c->n_t;
-    a.family = family;
-    a.G = G;
-    agg_partial_kernel<<<(unsigned)((c->n_t + 255) / 256), 256, 0, c->stream>>>(a);
-    HIPCHK(c, hipGetLastError());
-    if (partial_out) HIPCHK(c, hipMemcpyAsync(partial_out, c->d_agg_part.p, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // leaf_coef / leaf_group are the caller's
-    c->agg_family = family;
-    c->agg_G = G;
-    c->agg_W = W;
-    c->invalidate(P_PARTIAL);
-    c->mark(P_PARTIAL);
-    return 0;
-}
-
-int dsmgp_aggregate_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain, int32_t prior_kernel_id,
-                           double* mu_out, double* var_out) {
-    if (!c) return DSMGP_E_ARG;
-    if (!c->has(P_PARTIAL)) return fail(c, DSMGP_E_STATE, "aggregate_finish before aggregate_partial");
-    if (c->agg_family == AGG_RBCM &&
-        (prior_kernel_id < 0 || prior_kernel_id >= (int)c->hyper.size() || c->hyper[prior_kernel_id].kind < 0))
-        return fail(c, DSMGP_E_ARG, "aggregate_finish: rBCM needs the kernel id of the model's first leaf");
-    if (c->agg_family == AGG_RBCM && ard_linear_short(c, prior_kernel_id))
-        return fail(c, DSMGP_E_ARG, std::string("aggregate_finish: ") + KINDS[c->hyper[prior_kernel_id].kind].name +
-                                        " needs one lengthscale per input dimension");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nt = (size_t)c->n_t;
-    const size_t nblk = (nt + 255) / 256;
-    if (int rc = c->d_agg_out.grow(c, 3 * nt + 3 * nblk + 8)) return rc;
-    if (partial_in)   // sums over all ranks / contexts, added by the caller
-        HIPCHK(c, hipMemcpyAsync(c->d_agg_part.p, partial_in, (size_t)c->agg_W * nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    agg_finish_kernel<<<(unsigned)nblk, 256, 0, c->stream>>>(c->d_agg_part.p, c->n_t, c->agg_family, c->agg_G, plain ? 1 : 0,
-                                                           c->d_kp.p, c->agg_family == AGG_RBCM ? prior_kernel_id : 0, c->dXt.p,
-                                                           c->D, c->d_agg_out.p, c->d_agg_out.p + nt);
-    HIPCHK(c, hipGetLastError());
-    if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->d_agg_out.p, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->d_agg_out.p + nt, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->invalidate(P_DONE);      // what was made from the moments of another total (the gradient sums) falls
-    c->mark(P_DONE);
-    return 0;
-}
-
-int dsmgp_aggregate(dsmgp_ctx* c, int32_t family, const double* leaf_coef, const int32_t* leaf_group, int32_t n_groups,
-                    int32_t plain, int32_t prior_kernel_id, double* mu_out, double* var_out) {
-    if (int rc = dsmgp_aggregate_partial(c, family, leaf_coef, leaf_group, n_groups, nullptr)) return rc;
-    return dsmgp_aggregate_finish(c, nullptr, plain, prior_kernel_id, mu_out, var_out);
-}
+// The score functions on the aggregated prediction (the aggregation itself: the section "predict(model, x): aggregation" below,
+// after the per-entry products it reads)
 
 int dsmgp_scores(dsmgp_ctx* c, const double* y_test, double* out) {
     if (!c) return DSMGP_E_ARG;
@@ -5488,107 +5429,6 @@ int dsmgp_predict_gradients(dsmgp_ctx* c, double* dmu_out, double* dvar_out, int
     return 0;
 }
 
-// Input gradients of the aggregated prediction (the kernels and the layout of the sums: kernels.hpp at AggGradArgs).  Family,
-// coefficients and groups are those of the last dsmgp_aggregate_partial, resident since; the per-entry gradients are d_pgout,
-// made here (predict_gradients_device) unless both halves are this prediction's already.  Nothing another entry point reads is
-// written: the sums and the results have buffers of their own.
-namespace {
-int agg_gradients_width(int family, int G, int D) { return (family == AGG_MIXTURE ? 3 : (family == AGG_RBCM ? 2 * G : 2)) * D; }
-}  // namespace
-
-int dsmgp_aggregate_gradients_partial(dsmgp_ctx* c, double* partial_out, double* seconds) {
-    if (!c) return DSMGP_E_ARG;
-    if (seconds) *seconds = 0.0;
-    if (!c->has(P_DONE)) return fail(c, DSMGP_E_STATE, "aggregate_gradients before aggregate on the current prediction");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nt = (size_t)c->n_t, nr = (size_t)c->route_total;
-    const int D = c->D;
-    const size_t need = (size_t)agg_gradients_width(c->agg_family, c->agg_G, D) * nt;
-    c->invalidate(P_GSUMS);
-    if (int rc = c->d_agg_gpart.grow(c, need)) return rc;
-    double prod_seconds = 0.0;
-    if (!c->has(P_PGRAD)) {
-        if (nr) {
-            if (int rc = predict_gradients_device(c, true, &prod_seconds)) return rc;
-        } else {
-            c->mark(P_PGRAD);       // no entry: nothing to make
-        }
-    }
-    EventPair ev;
-    HIPCHK(c, ev.init());
-    HIPCHK(c, hipEventRecord(ev.a, c->stream));
-    AggGradArgs a{};
-    a.row_ptr = c->d_row_ptr.p;
-    a.row_ent = c->d_row_ent.p;
-    a.ent_leaf = c->d_ent_leaf.p;
-    a.mu = c->arenaPV.p;
-    a.var = c->arenaPV.p + nr;
-    a.dmu = c->d_pgout.p;
-    a.dvar = c->d_pgout.p + nr * (size_t)D;
-    a.coef = c->d_agg_coef.p;
-    a.group = c->d_agg_group.p;
-    a.agg_mu = c->d_agg_out.p;
-    a.part = c->d_agg_gpart.p;
-    a.n_t = c->n_t;
-    a.ld = c->route_total;
-    a.D = D;
-    a.family = c->agg_family;
-    a.G = c->agg_G;
-    agg_grad_partial_kernel<<<dim3((unsigned)((nt + 255) / 256), (unsigned)D), 256, 0, c->stream>>>(a);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev.b, c->stream));
-    if (partial_out) HIPCHK(c, hipMemcpyAsync(partial_out, c->d_agg_gpart.p, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
-    if (seconds) *seconds = prod_seconds + ms * 1e-3;
-    c->mark(P_GSUMS);
-    return 0;
-}
-
-int dsmgp_aggregate_gradients_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain, int32_t prior_kernel_id,
-                                     double* dmu_out, double* dvar_out, int64_t ld) {
-    if (!c) return DSMGP_E_ARG;
-    if (!c->has(P_GSUMS)) return fail(c, DSMGP_E_STATE, "aggregate_gradients_finish before aggregate_gradients_partial");
-    if (c->agg_family == AGG_RBCM &&
-        (prior_kernel_id < 0 || prior_kernel_id >= (int)c->hyper.size() || c->hyper[prior_kernel_id].kind < 0))
-        return fail(c, DSMGP_E_ARG, "aggregate_gradients_finish: rBCM needs the kernel id of the model's first leaf");
-    if (c->agg_family == AGG_RBCM && ard_linear_short(c, prior_kernel_id))
-        return fail(c, DSMGP_E_ARG, std::string("aggregate_gradients_finish: ") + KINDS[c->hyper[prior_kernel_id].kind].name +
-                                        " needs one lengthscale per input dimension");
-    if (ld < c->n_t) return fail(c, DSMGP_E_ARG, "aggregate_gradients_finish: ld < n_t");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nt = (size_t)c->n_t;
-    const int D = c->D;
-    if (int rc = c->d_agg_gout.grow(c, 2 * nt * (size_t)D)) return rc;
-    if (partial_in)     // sums over all contexts, added by the caller
-        HIPCHK(c, hipMemcpyAsync(c->d_agg_gpart.p, partial_in, (size_t)agg_gradients_width(c->agg_family, c->agg_G, D) * nt * sizeof(double),
-                                 hipMemcpyHostToDevice, c->stream));
-    double* gm = c->d_agg_gout.p;
-    double* gv = gm + nt * (size_t)D;
-    agg_grad_finish_kernel<<<dim3((unsigned)((nt + 255) / 256), (unsigned)D), 256, 0, c->stream>>>(
-        c->d_agg_gpart.p, c->d_agg_part.p, c->n_t, D, c->agg_family, c->agg_G, plain ? 1 : 0, c->d_kp.p,
-        c->agg_family == AGG_RBCM ? prior_kernel_id : 0, c->dXt.p, gm, gv);
-    HIPCHK(c, hipGetLastError());
-    if (dmu_out)
-        HIPCHK(c, hipMemcpy2DAsync(dmu_out, (size_t)ld * sizeof(double), gm, nt * sizeof(double), nt * sizeof(double), (size_t)D,
-                                   hipMemcpyDeviceToHost, c->stream));
-    if (dvar_out)
-        HIPCHK(c, hipMemcpy2DAsync(dvar_out, (size_t)ld * sizeof(double), gv, nt * sizeof(double), nt * sizeof(double), (size_t)D,
-                                   hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int dsmgp_aggregate_gradients(dsmgp_ctx* c, int32_t plain, int32_t prior_kernel_id, double* dmu_out, double* dvar_out, int64_t ld,
-                              double* seconds) {
-    if (!c) return DSMGP_E_ARG;
-    if (seconds) *seconds = 0.0;
-    if (c->has(P_DONE) && ld < c->n_t) return fail(c, DSMGP_E_ARG, "aggregate_gradients: ld < n_t");    // before any device work
-    if (int rc = dsmgp_aggregate_gradients_partial(c, nullptr, seconds)) return rc;
-    return dsmgp_aggregate_gradients_finish(c, nullptr, plain, prior_kernel_id, dmu_out, dvar_out, ld);
-}
-
 // Several target columns on the current factors (kernels_targets.hpp).  Z = L^-1 (Y[obs] - mean) for every leaf by a
 // right-looking block sweep on the matrix cores, one launch per block column and lane, every factor tile read once; then the
 // per-(leaf, column) log-marginals.  Writes its own arena only: z, alpha and everything else a fit left stay as they are
@@ -5929,39 +5769,212 @@ int dsmgp_predict_columns_gradients(dsmgp_ctx* c, double* dmu_out, int64_t ld, d
     return 0;
 }
 
-// predict(model, x) and its input gradients for every resident target column (kernels.hpp at AggColsArgs).  A state of their own
-// beside the single-y aggregation (d_col_*, col_family): d_agg_* and what dsmgp_scores / dsmgp_aggregate_finish answer stay as
-// they are.  One context only: no partial / finish split.
+// -------------------------------------------------------------------------------------------------
+// predict(model, x): aggregation over the leaves of every test row on the device -- the moments, their input gradients, and both
+// for every resident target column.  The arithmetic of a family, the kernels and the layout of the sums: kernels_agg.hpp; this
+// section checks the arguments, keeps the resident family, makes the per-entry products a call reads, launches and downloads.
+//   single y    family, coefficients and groups are those of the last dsmgp_aggregate_partial (c->agg, d_agg_*), resident since;
+//               the gradient calls read the per-entry gradients d_pgout.  Sums and results have buffers of their own: nothing
+//               another entry point reads is written.
+//   columns     a state of their own beside it (c->col, d_col_*): d_agg_* and what dsmgp_scores / dsmgp_aggregate_finish answer
+//               stay as they are.  One context only: no partial / finish split.
 namespace {
-static void agg_columns_args(dsmgp_ctx* c, AggColsArgs& a, int plain, int prior_kernel_id) {
-    a.row_ptr = c->d_row_ptr.p;
-    a.row_ent = c->d_row_ent.p;
-    a.ent_leaf = c->d_ent_leaf.p;
-    a.tmu = c->d_tmu.p;
+int agg_width(int family, int G, int D = 1) { return (family == AGG_MIXTURE ? 3 : (family == AGG_RBCM ? 2 * G : 2)) * D; }
+
+static AggState agg_state(int family, int n_groups) {
+    const int G = family == AGG_RBCM ? n_groups : 0;
+    return AggState{family, G, agg_width(family, G)};
+}
+
+// The family, coefficient and group arguments of the two calls that take them
+static int agg_family_check(dsmgp_ctx* c, int family, const double* leaf_coef, const int32_t* leaf_group, int n_groups,
+                            const std::string& who) {
+    if (family < AGG_MIXTURE || family > AGG_RBCM) return fail(c, DSMGP_E_ARG, who + ": unknown family");
+    if (family == AGG_RBCM) {
+        if (!leaf_group || n_groups <= 0 || n_groups > 4096) return fail(c, DSMGP_E_ARG, who + ": rBCM needs leaf groups");
+        for (int l = 0; l < c->L; ++l)
+            if (leaf_group[l] < 0 || leaf_group[l] >= n_groups) return fail(c, DSMGP_E_ARG, who + ": leaf group out of range");
+    } else if (!leaf_coef) {
+        return fail(c, DSMGP_E_ARG, who + ": leaf_coef is NULL");
+    }
+    return 0;
+}
+
+// rBCM: the prior is the kernel id of the model's first leaf
+static int agg_prior_check(dsmgp_ctx* c, int family, int prior_kernel_id, const std::string& who) {
+    if (family != AGG_RBCM) return 0;
+    if (prior_kernel_id < 0 || prior_kernel_id >= (int)c->hyper.size() || c->hyper[prior_kernel_id].kind < 0)
+        return fail(c, DSMGP_E_ARG, who + ": rBCM needs the kernel id of the model's first leaf");
+    if (ard_linear_short(c, prior_kernel_id))
+        return fail(c, DSMGP_E_ARG, who + ": " + KINDS[c->hyper[prior_kernel_id].kind].name + " needs one lengthscale per input dimension");
+    return 0;
+}
+
+static int agg_upload(dsmgp_ctx* c, int family, const double* leaf_coef, const int32_t* leaf_group, double* d_coef, int32_t* d_group) {
+    const size_t L = (size_t)c->L;
+    if (leaf_coef) HIPCHK(c, hipMemcpyAsync(d_coef, leaf_coef, L * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (family == AGG_RBCM) HIPCHK(c, hipMemcpyAsync(d_group, leaf_group, L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// What every kernel that walks the entries reads, for the resident family `s` with its coefficients and groups; the caller adds
+// the arrays of its own (the columns: mu = d_tmu).
+static AggArgs agg_args(dsmgp_ctx* c, const AggState& s, const double* d_coef, const int32_t* d_group, int plain = 0,
+                        int prior_kernel_id = 0) {
+    AggArgs a{};
+    a.rows = AggRows{c->d_row_ptr.p, c->d_row_ent.p, c->d_ent_leaf.p};
+    a.mu = c->arenaPV.p;
     a.var = c->arenaPV.p + (size_t)c->route_total;
-    a.coef = c->d_col_coef.p;
-    a.group = c->d_col_group.p;
+    a.coef = d_coef;
+    a.group = d_group;
     a.kp = c->d_kp.p;
     a.Xt = c->dXt.p;
     a.n_t = c->n_t;
     a.ld = c->route_total;
     a.D = c->D;
     a.Q = c->tg_Q;
-    a.family = c->col_family;
-    a.G = c->col_G;
+    a.family = s.family;
+    a.G = s.G;
     a.plain = plain ? 1 : 0;
-    a.prior_kid = c->col_family == AGG_RBCM ? prior_kernel_id : 0;
+    a.prior_kid = s.family == AGG_RBCM ? prior_kernel_id : 0;
+    return a;
 }
-static int agg_prior_check(dsmgp_ctx* c, int family, int prior_kernel_id, const char* who) {
-    if (family != AGG_RBCM) return 0;
-    if (prior_kernel_id < 0 || prior_kernel_id >= (int)c->hyper.size() || c->hyper[prior_kernel_id].kind < 0)
-        return fail(c, DSMGP_E_ARG, std::string(who) + ": rBCM needs the kernel id of the model's first leaf");
-    if (ard_linear_short(c, prior_kernel_id))
-        return fail(c, DSMGP_E_ARG, std::string(who) + ": " + KINDS[c->hyper[prior_kernel_id].kind].name +
-                                        " needs one lengthscale per input dimension");
+
+// Make a per-entry product with `make(&its device seconds)` unless it is this prediction's already; the time is added to
+// `seconds`.  With no entry there is nothing to make: `mark_empty` then marks it current (the columns' gradient call never did).
+static int agg_ensure(dsmgp_ctx* c, Product p, bool mark_empty, double& seconds, const std::function<int(double*)>& make) {
+    if (c->has(p)) return 0;
+    if (!c->route_total) {
+        if (mark_empty) c->mark(p);
+        return 0;
+    }
+    double s = 0.0;
+    const int rc = make(&s);
+    seconds += s;
+    return rc;
+}
+
+// `cols` planes of n_t doubles to the caller's matrix of leading dimension ld; a NULL destination takes nothing
+static hipError_t agg_download(dsmgp_ctx* c, double* dst, int64_t ld, const double* d_src, size_t cols) {
+    if (!dst) return hipSuccess;
+    const size_t w = (size_t)c->n_t * sizeof(double);
+    return hipMemcpy2DAsync(dst, (size_t)ld * sizeof(double), d_src, w, w, cols, hipMemcpyDeviceToHost, c->stream);
+}
+
+static dim3 agg_grid(dsmgp_ctx* c, int ny = 1) { return dim3((unsigned)((c->n_t + 255) / 256), (unsigned)ny); }
+}  // namespace
+
+int dsmgp_aggregate_partial(dsmgp_ctx* c, int32_t family, const double* leaf_coef, const int32_t* leaf_group,
+                            int32_t n_groups, double* partial_out) {
+    if (!c) return DSMGP_E_ARG;
+    if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "aggregate before predict_run");
+    if (int rc = agg_family_check(c, family, leaf_coef, leaf_group, n_groups, "aggregate")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const AggState s = agg_state(family, n_groups);
+    const size_t need = (size_t)s.W * (size_t)c->n_t;
+    if (int rc = c->d_agg_part.grow(c, need)) return rc;
+    if (int rc = c->d_agg_coef.grow(c, (size_t)c->L)) return rc;
+    if (int rc = c->d_agg_group.grow(c, (size_t)c->L)) return rc;
+    if (int rc = agg_upload(c, family, leaf_coef, leaf_group, c->d_agg_coef.p, c->d_agg_group.p)) return rc;
+    AggArgs a = agg_args(c, s, c->d_agg_coef.p, c->d_agg_group.p);
+    a.out = c->d_agg_part.p;
+    agg_partial_kernel<<<agg_grid(c), 256, 0, c->stream>>>(a);
+    HIPCHK(c, hipGetLastError());
+    if (partial_out) HIPCHK(c, hipMemcpyAsync(partial_out, c->d_agg_part.p, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // leaf_coef / leaf_group are the caller's
+    c->agg = s;
+    c->invalidate(P_PARTIAL);
+    c->mark(P_PARTIAL);
     return 0;
 }
-}  // namespace
+
+int dsmgp_aggregate_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain, int32_t prior_kernel_id,
+                           double* mu_out, double* var_out) {
+    if (!c) return DSMGP_E_ARG;
+    if (!c->has(P_PARTIAL)) return fail(c, DSMGP_E_STATE, "aggregate_finish before aggregate_partial");
+    if (int rc = agg_prior_check(c, c->agg.family, prior_kernel_id, "aggregate_finish")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nt = (size_t)c->n_t;
+    const size_t nblk = (nt + 255) / 256;
+    if (int rc = c->d_agg_out.grow(c, 3 * nt + 3 * nblk + 8)) return rc;
+    if (partial_in)   // sums over all ranks / contexts, added by the caller
+        HIPCHK(c, hipMemcpyAsync(c->d_agg_part.p, partial_in, (size_t)c->agg.W * nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    agg_finish_kernel<<<agg_grid(c), 256, 0, c->stream>>>(c->d_agg_part.p, c->n_t, c->agg.family, c->agg.G, plain ? 1 : 0, c->d_kp.p,
+                                                        c->agg.family == AGG_RBCM ? prior_kernel_id : 0, c->dXt.p, c->D,
+                                                        c->d_agg_out.p, c->d_agg_out.p + nt);
+    HIPCHK(c, hipGetLastError());
+    if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->d_agg_out.p, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (var_out) HIPCHK(c, hipMemcpyAsync(var_out, c->d_agg_out.p + nt, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->invalidate(P_DONE);      // what was made from the moments of another total (the gradient sums) falls
+    c->mark(P_DONE);
+    return 0;
+}
+
+int dsmgp_aggregate(dsmgp_ctx* c, int32_t family, const double* leaf_coef, const int32_t* leaf_group, int32_t n_groups,
+                    int32_t plain, int32_t prior_kernel_id, double* mu_out, double* var_out) {
+    if (int rc = dsmgp_aggregate_partial(c, family, leaf_coef, leaf_group, n_groups, nullptr)) return rc;
+    return dsmgp_aggregate_finish(c, nullptr, plain, prior_kernel_id, mu_out, var_out);
+}
+
+int dsmgp_aggregate_gradients_partial(dsmgp_ctx* c, double* partial_out, double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (!c->has(P_DONE)) return fail(c, DSMGP_E_STATE, "aggregate_gradients before aggregate on the current prediction");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t need = (size_t)agg_width(c->agg.family, c->agg.G, c->D) * (size_t)c->n_t;
+    c->invalidate(P_GSUMS);
+    if (int rc = c->d_agg_gpart.grow(c, need)) return rc;
+    double sec = 0.0;
+    if (int rc = agg_ensure(c, P_PGRAD, true, sec, [&](double* s) { return predict_gradients_device(c, true, s); })) return rc;
+    AggArgs a = agg_args(c, c->agg, c->d_agg_coef.p, c->d_agg_group.p);
+    a.dmu = c->d_pgout.p;
+    a.dvar = c->d_pgout.p + (size_t)c->route_total * (size_t)c->D;
+    a.agg_mu = c->d_agg_out.p;
+    a.out = c->d_agg_gpart.p;
+    EventPair ev;
+    HIPCHK(c, ev.timed(c->stream, [&] { agg_grad_partial_kernel<<<agg_grid(c, c->D), 256, 0, c->stream>>>(a); }));
+    if (partial_out) HIPCHK(c, hipMemcpyAsync(partial_out, c->d_agg_gpart.p, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, ev.add_seconds(sec));
+    if (seconds) *seconds = sec;
+    c->mark(P_GSUMS);
+    return 0;
+}
+
+int dsmgp_aggregate_gradients_finish(dsmgp_ctx* c, const double* partial_in, int32_t plain, int32_t prior_kernel_id,
+                                     double* dmu_out, double* dvar_out, int64_t ld) {
+    if (!c) return DSMGP_E_ARG;
+    if (!c->has(P_GSUMS)) return fail(c, DSMGP_E_STATE, "aggregate_gradients_finish before aggregate_gradients_partial");
+    if (int rc = agg_prior_check(c, c->agg.family, prior_kernel_id, "aggregate_gradients_finish")) return rc;
+    if (ld < c->n_t) return fail(c, DSMGP_E_ARG, "aggregate_gradients_finish: ld < n_t");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nt = (size_t)c->n_t;
+    const int D = c->D;
+    if (int rc = c->d_agg_gout.grow(c, 2 * nt * (size_t)D)) return rc;
+    if (partial_in)     // sums over all contexts, added by the caller
+        HIPCHK(c, hipMemcpyAsync(c->d_agg_gpart.p, partial_in, (size_t)agg_width(c->agg.family, c->agg.G, D) * nt * sizeof(double),
+                                 hipMemcpyHostToDevice, c->stream));
+    double* gm = c->d_agg_gout.p;
+    double* gv = gm + nt * (size_t)D;
+    agg_grad_finish_kernel<<<agg_grid(c, D), 256, 0, c->stream>>>(c->d_agg_gpart.p, c->d_agg_part.p, c->n_t, D, c->agg.family, c->agg.G,
+                                                                plain ? 1 : 0, c->d_kp.p,
+                                                                c->agg.family == AGG_RBCM ? prior_kernel_id : 0, c->dXt.p, gm, gv);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, agg_download(c, dmu_out, ld, gm, (size_t)D));
+    HIPCHK(c, agg_download(c, dvar_out, ld, gv, (size_t)D));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int dsmgp_aggregate_gradients(dsmgp_ctx* c, int32_t plain, int32_t prior_kernel_id, double* dmu_out, double* dvar_out, int64_t ld,
+                              double* seconds) {
+    if (!c) return DSMGP_E_ARG;
+    if (seconds) *seconds = 0.0;
+    if (c->has(P_DONE) && ld < c->n_t) return fail(c, DSMGP_E_ARG, "aggregate_gradients: ld < n_t");    // before any device work
+    if (int rc = dsmgp_aggregate_gradients_partial(c, nullptr, seconds)) return rc;
+    return dsmgp_aggregate_gradients_finish(c, nullptr, plain, prior_kernel_id, dmu_out, dvar_out, ld);
+}
 
 int dsmgp_aggregate_columns(dsmgp_ctx* c, int32_t family, const double* leaf_coef, const int32_t* leaf_group, int32_t n_groups,
                             int32_t plain, int32_t prior_kernel_id, double* mu_out, double* var_out, int64_t ld, double* seconds) {
@@ -5969,14 +5982,7 @@ int dsmgp_aggregate_columns(dsmgp_ctx* c, int32_t family, const double* leaf_coe
     if (seconds) *seconds = 0.0;
     if (!c->has(P_Z)) return fail(c, DSMGP_E_STATE, "aggregate_columns before solve_targets on the current fit");
     if (!c->has(P_PRED)) return fail(c, DSMGP_E_STATE, "aggregate_columns before predict_run on the current fit");
-    if (family < AGG_MIXTURE || family > AGG_RBCM) return fail(c, DSMGP_E_ARG, "aggregate_columns: unknown family");
-    if (family == AGG_RBCM) {
-        if (!leaf_group || n_groups <= 0 || n_groups > 4096) return fail(c, DSMGP_E_ARG, "aggregate_columns: rBCM needs leaf groups");
-        for (int l = 0; l < c->L; ++l)
-            if (leaf_group[l] < 0 || leaf_group[l] >= n_groups) return fail(c, DSMGP_E_ARG, "aggregate_columns: leaf group out of range");
-    } else if (!leaf_coef) {
-        return fail(c, DSMGP_E_ARG, "aggregate_columns: leaf_coef is NULL");
-    }
+    if (int rc = agg_family_check(c, family, leaf_coef, leaf_group, n_groups, "aggregate_columns")) return rc;
     if (int rc = agg_prior_check(c, family, prior_kernel_id, "aggregate_columns")) return rc;
     if (ld < c->n_t) return fail(c, DSMGP_E_ARG, "aggregate_columns: ld < n_t");
     HIPCHK(c, hipSetDevice(c->device));
@@ -5986,39 +5992,21 @@ int dsmgp_aggregate_columns(dsmgp_ctx* c, int32_t family, const double* leaf_coe
     if (int rc = c->d_col_coef.grow(c, L)) return rc;
     if (int rc = c->d_col_group.grow(c, L)) return rc;
     if (int rc = c->d_col_out.grow(c, 2 * nt * (size_t)Q)) return rc;
-    double prod_seconds = 0.0;
-    if (!c->has(P_TMU)) {
-        if (c->route_total) {
-            if (int rc = predict_targets_device(c, &prod_seconds)) return rc;
-        } else {
-            c->mark(P_TMU);         // no entry: nothing to make
-        }
-    }
-    if (leaf_coef) HIPCHK(c, hipMemcpyAsync(c->d_col_coef.p, leaf_coef, L * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (family == AGG_RBCM)
-        HIPCHK(c, hipMemcpyAsync(c->d_col_group.p, leaf_group, L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    c->col_family = family;
-    c->col_G = family == AGG_RBCM ? n_groups : 0;
-    AggColsArgs a{};
-    agg_columns_args(c, a, plain, prior_kernel_id);
-    a.out_m = c->d_col_out.p;
+    double sec = 0.0;
+    if (int rc = agg_ensure(c, P_TMU, true, sec, [&](double* s) { return predict_targets_device(c, s); })) return rc;
+    if (int rc = agg_upload(c, family, leaf_coef, leaf_group, c->d_col_coef.p, c->d_col_group.p)) return rc;
+    c->col = agg_state(family, n_groups);
+    AggArgs a = agg_args(c, c->col, c->d_col_coef.p, c->d_col_group.p, plain, prior_kernel_id);
+    a.mu = c->d_tmu.p;
+    a.out = c->d_col_out.p;
     a.out_v = c->d_col_out.p + nt * (size_t)Q;
     EventPair ev;
-    HIPCHK(c, ev.init());
-    HIPCHK(c, hipEventRecord(ev.a, c->stream));
-    agg_columns_kernel<<<dim3((unsigned)((nt + 255) / 256), (unsigned)Q), 256, 0, c->stream>>>(a);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev.b, c->stream));
-    if (mu_out)
-        HIPCHK(c, hipMemcpy2DAsync(mu_out, (size_t)ld * sizeof(double), a.out_m, nt * sizeof(double), nt * sizeof(double), (size_t)Q,
-                                   hipMemcpyDeviceToHost, c->stream));
-    if (var_out)
-        HIPCHK(c, hipMemcpy2DAsync(var_out, (size_t)ld * sizeof(double), a.out_v, nt * sizeof(double), nt * sizeof(double), (size_t)Q,
-                                   hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, ev.timed(c->stream, [&] { agg_columns_kernel<<<agg_grid(c, Q), 256, 0, c->stream>>>(a); }));
+    HIPCHK(c, agg_download(c, mu_out, ld, a.out, (size_t)Q));
+    HIPCHK(c, agg_download(c, var_out, ld, a.out_v, (size_t)Q));
     HIPCHK(c, hipStreamSynchronize(c->stream));     // leaf_coef / leaf_group are the caller's
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
-    if (seconds) *seconds = prod_seconds + ms * 1e-3;
+    HIPCHK(c, ev.add_seconds(sec));
+    if (seconds) *seconds = sec;
     c->mark(P_CDONE);
     return 0;
 }
@@ -6028,44 +6016,27 @@ int dsmgp_aggregate_columns_gradients(dsmgp_ctx* c, int32_t plain, int32_t prior
     if (!c) return DSMGP_E_ARG;
     if (seconds) *seconds = 0.0;
     if (!c->has(P_CDONE)) return fail(c, DSMGP_E_STATE, "aggregate_columns_gradients before aggregate_columns on the current prediction and columns");
-    if (int rc = agg_prior_check(c, c->col_family, prior_kernel_id, "aggregate_columns_gradients")) return rc;
+    if (int rc = agg_prior_check(c, c->col.family, prior_kernel_id, "aggregate_columns_gradients")) return rc;
     if (ld < c->n_t) return fail(c, DSMGP_E_ARG, "aggregate_columns_gradients: ld < n_t");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t nt = (size_t)c->n_t, nr = (size_t)c->route_total;
-    const int D = c->D, Q = c->tg_Q;
-    if (int rc = c->d_col_gout.grow(c, 2 * nt * (size_t)D * (size_t)Q)) return rc;
-    double prod_seconds = 0.0, s1 = 0.0;
-    if (nr && !c->has(P_TIG)) {
-        if (int rc = predict_columns_gradients_device(c, &s1)) return rc;
-        prod_seconds += s1;
-    }
-    if (nr && !c->has(P_PGRAD)) {
-        if (int rc = predict_gradients_device(c, true, &s1)) return rc;
-        prod_seconds += s1;
-    }
-    AggColsArgs a{};
-    agg_columns_args(c, a, plain, prior_kernel_id);
-    a.tdmu = c->d_tigout.p;
-    a.dvar = c->d_pgout.p + nr * (size_t)D;
-    a.out_m = c->d_col_gout.p;
-    a.out_v = c->d_col_gout.p + nt * (size_t)D * (size_t)Q;
+    const size_t cols = (size_t)c->D * (size_t)c->tg_Q;
+    if (int rc = c->d_col_gout.grow(c, 2 * (size_t)c->n_t * cols)) return rc;
+    double sec = 0.0;
+    if (int rc = agg_ensure(c, P_TIG, false, sec, [&](double* s) { return predict_columns_gradients_device(c, s); })) return rc;
+    if (int rc = agg_ensure(c, P_PGRAD, false, sec, [&](double* s) { return predict_gradients_device(c, true, s); })) return rc;
+    AggArgs a = agg_args(c, c->col, c->d_col_coef.p, c->d_col_group.p, plain, prior_kernel_id);
+    a.mu = c->d_tmu.p;
+    a.dmu = c->d_tigout.p;
+    a.dvar = c->d_pgout.p + (size_t)c->route_total * (size_t)c->D;
+    a.out = c->d_col_gout.p;
+    a.out_v = c->d_col_gout.p + (size_t)c->n_t * cols;
     EventPair ev;
-    HIPCHK(c, ev.init());
-    HIPCHK(c, hipEventRecord(ev.a, c->stream));
-    agg_columns_grad_kernel<<<dim3((unsigned)((nt + 255) / 256), (unsigned)Q), 256, 0, c->stream>>>(a);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev.b, c->stream));
-    const size_t cols = (size_t)D * (size_t)Q;
-    if (dmu_out)
-        HIPCHK(c, hipMemcpy2DAsync(dmu_out, (size_t)ld * sizeof(double), a.out_m, nt * sizeof(double), nt * sizeof(double), cols,
-                                   hipMemcpyDeviceToHost, c->stream));
-    if (dvar_out)
-        HIPCHK(c, hipMemcpy2DAsync(dvar_out, (size_t)ld * sizeof(double), a.out_v, nt * sizeof(double), nt * sizeof(double), cols,
-                                   hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, ev.timed(c->stream, [&] { agg_columns_grad_kernel<<<agg_grid(c, c->tg_Q), 256, 0, c->stream>>>(a); }));
+    HIPCHK(c, agg_download(c, dmu_out, ld, a.out, cols));
+    HIPCHK(c, agg_download(c, dvar_out, ld, a.out_v, cols));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev.a, ev.b));
-    if (seconds) *seconds = prod_seconds + ms * 1e-3;
+    HIPCHK(c, ev.add_seconds(sec));
+    if (seconds) *seconds = sec;
     return 0;
 }
 
@@ -7564,7 +7535,7 @@ int dsmgp_aggregate_exchange(dsmgp_ctx* c, double* total_out) {
     if (!c->has(P_PARTIAL)) return fail(c, DSMGP_E_STATE, "aggregate_exchange before aggregate_partial");
     if (c->has(P_TOTAL)) return fail(c, DSMGP_E_STATE, "aggregate_exchange: these partial sums already hold the total over ranks");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)c->agg_W * (size_t)c->n_t;
+    const size_t n = (size_t)c->agg.W * (size_t)c->n_t;
     if (int rc = xchg_reserve(c, n)) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_xchg.p, c->d_agg_part.p, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     if (int rc = xchg_gather(c, n)) return rc;

@@ -12,7 +12,7 @@
 // a later column with the leading block copied, chol_continue! (src/AdvancedCholeskey.jl:152-174).
 // prediction() (src/gaussianprocess.jl:110-137) appends the test rows below the factor: V^T = K_tn L^-T
 // is the same two tile kernels run on the rows of K_tn.  Aggregation over the leaves of a test row and the score
-// functions (src/common.jl:134-302, src/scorefunctions.jl) are the agg_* kernels at the end of this file.
+// functions (src/common.jl:134-302, src/scorefunctions.jl) are the agg_* kernels of kernels_agg.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -3457,6 +3457,12 @@ __device__ __forceinline__ double prior_var(const KParam& p, const double* X, In
     return kss;
 }
 
+// d prior_var / d x_d at x = x_d: 2 x_d / l^2 for IsoLinear, 2 x_d nh_d for ArdLinear, 0 for the other kinds
+__device__ __forceinline__ double prior_var_dx(const KParam& p, double x, int d) {
+    const double x2 = 2.0 * x;
+    return p.kind == 2 ? x2 / p.l2[0] : (p.kind == 3 ? x2 * p.nh[d] : 0.0);
+}
+
 // mu = m + macc, var = k(x*,x*) + noise - sacc for the rows whose moments were accumulated by the sweep
 __global__ __launch_bounds__(128) void pred_finish_kernel(const LeafDev* __restrict__ leaves, const PredTask* __restrict__ tasks,
                                                           const KParam* __restrict__ kp, int D) {
@@ -3873,480 +3879,6 @@ __global__ __launch_bounds__(256) void loo_hvec_kernel(const LooHvecTask* __rest
     if (t == 0) {
         out[2 * blockIdx.x] = rf[0];
         out[2 * blockIdx.x + 1] = ru[0];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// predict(model, x): sum/product aggregation of the leaf moments over the leaves every test row visits
-// (src/common.jl:134-149,198-302) and the score functions (src/scorefunctions.jl:6-16), on the moments left in HBM
-// by pred_finish_kernel.  All four model families reduce to per-row sums over (leaf, row) entries:
-//   mixture (DSMGP, :275-302): the nested log-domain recursion is linear in (mu, mu^2, sigma^2) -- unrolled it is the
-//       flat mixture with weight W_l = product of the sum-node weights on leaf l's path: S0 = sum W mu,
-//       S1 = sum W mu^2, S2 = sum W sigma^2 (sigma^2 <= 0 -> 1e-8, :137); mu = S0, var = S2 + S1 - S0^2
-//   PoE / gPoE (:145-149,198-222): t = 1/sigma^2; S0 = sum beta t mu, S1 = sum beta t (beta = 1 resp. 1/#root children)
-//   rBCM (:224-241): per root child g the PoE sums (S_g0, S_g1) = (sum t mu, sum t); combined in agg_finish_kernel
-// Partial sums are stored [k][row] (W vectors of length n_t): with leaves sharded over ranks or contexts each one
-// produces its partial sums and they are added before the finish step.  One thread per test row walks that row's
-// entries in ascending entry order (= leaf order): fixed summation order, no atomics.
-constexpr int AGG_MIXTURE = 0, AGG_POE = 1, AGG_GPOE = 2, AGG_RBCM = 3;
-
-struct AggArgs {
-    const int64_t* row_ptr;     // n_t + 1: entries of every test row
-    const int32_t* row_ent;     // entry positions (index into mu / var), ascending per row
-    const int32_t* ent_leaf;    // leaf of every entry position
-    const double* mu;           // per (leaf, routed row), route order
-    const double* var;
-    const double* coef;         // per leaf: W_l (mixture) or beta_l (PoE / gPoE); unused for rBCM
-    const int32_t* group;       // per leaf: root child (rBCM); else unused
-    double* part;               // W x n_t
-    int64_t n_t;
-    int family;
-    int G;                      // rBCM: number of groups
-};
-
-__global__ __launch_bounds__(256) void agg_partial_kernel(AggArgs a) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= a.n_t) return;
-    const int64_t e0 = a.row_ptr[r], e1 = a.row_ptr[r + 1];
-    if (a.family == AGG_MIXTURE) {
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-        for (int64_t e = e0; e < e1; ++e) {
-            const int pos = a.row_ent[e];
-            const double w = a.coef[a.ent_leaf[pos]];
-            const double m = a.mu[pos];
-            double v = a.var[pos];
-            if (v <= 0.0) v = 1e-8;                               // src/common.jl:137
-            s0 += w * m;
-            s1 += w * (m * m);
-            s2 += w * v;
-        }
-        a.part[r] = s0;
-        a.part[a.n_t + r] = s1;
-        a.part[2 * a.n_t + r] = s2;
-    } else if (a.family == AGG_RBCM) {
-        for (int g = 0; g < a.G; ++g) {
-            a.part[(size_t)(2 * g) * a.n_t + r] = 0.0;
-            a.part[(size_t)(2 * g + 1) * a.n_t + r] = 0.0;
-        }
-        for (int64_t e = e0; e < e1; ++e) {
-            const int pos = a.row_ent[e];
-            const int g = a.group[a.ent_leaf[pos]];
-            const double t = 1.0 / a.var[pos];                    // src/common.jl:148
-            a.part[(size_t)(2 * g) * a.n_t + r] += t * a.mu[pos];
-            a.part[(size_t)(2 * g + 1) * a.n_t + r] += t;
-        }
-    } else {
-        double s0 = 0.0, s1 = 0.0;
-        for (int64_t e = e0; e < e1; ++e) {
-            const int pos = a.row_ent[e];
-            const double bt = a.coef[a.ent_leaf[pos]] * (1.0 / a.var[pos]);
-            s0 += bt * a.mu[pos];
-            s1 += bt;
-        }
-        a.part[r] = s0;
-        a.part[a.n_t + r] = s1;
-    }
-}
-
-// Finish step on the (summed) partial sums: mu / var of predict(model, x), left in HBM for agg_scores_kernel.
-// plain: the root is a single GP (predict(node::GPNode), src/common.jl:175-179): no mixture term.
-// rBCM: s = k(x*, x*) + noise of the model's first leaf (leftGP, :227-228).
-__global__ __launch_bounds__(256) void agg_finish_kernel(const double* __restrict__ part, int64_t n_t, int family, int G,
-                                                         int plain, const KParam* __restrict__ kp, int prior_kid,
-                                                         const double* __restrict__ Xt, int D,
-                                                         double* __restrict__ mu_out, double* __restrict__ var_out) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_t) return;
-    if (family == AGG_MIXTURE) {
-        const double m = part[r], m2 = part[n_t + r], sv = part[2 * n_t + r];
-        mu_out[r] = m;
-        var_out[r] = plain ? sv : sv + (m2 - m * m);              // src/common.jl:299-300
-    } else if (family == AGG_RBCM) {
-        const KParam p = kp[prior_kid];
-        const double s = prior_var(p, Xt, r, n_t, D) + p.noise;
-        double C = 1.0 / s, m = 0.0;
-        for (int g = 0; g < G; ++g) {
-            const double T = part[(size_t)(2 * g + 1) * n_t + r];
-            if (T == 0.0) continue;                               // no leaf of this child saw the row
-            const double M = part[(size_t)(2 * g) * n_t + r] / T; // mu_ of the child (:205)
-            const double beta = 0.5 * (log(s) - log(1.0 / T));    // :234-235
-            C += beta * T - beta / s;                             // :236
-            m += M * (beta * T);                                  // :237
-        }
-        mu_out[r] = m / C;
-        var_out[r] = 1.0 / C;
-    } else {
-        const double t = part[n_t + r];
-        mu_out[r] = part[r] / t;
-        var_out[r] = 1.0 / t;
-    }
-}
-
-// Input gradients of the aggregated prediction (dsmgp_aggregate_gradients*): the same gather-reduce over a row's entries, on
-// dmu | dvar of every entry (pred_inputgrad_finish_kernel: plane d at d * ld, ld = route_total).  One thread per (test row,
-// input dimension) -- blockIdx.y = d, lanes over consecutive rows as above -- walks the row's entries in ascending entry order:
-// fixed summation order, no atomics.  Partial sums in [k][row] planes, additive over contexts once every holder has the TOTAL
-// moments (agg_mu is the aggregated mean of the finish step; T, P of the products are read by the finish step only):
-//   mixture   k = d: sum W dmu_d;  D + d: sum W dvar'_d (dvar' = 0 where the moments clamp the leaf variance);
-//             2 D + d: sum W (mu_l - mu) dmu_d, centred on the aggregated mean so that a large offset of y cancels per term
-//   PoE/gPoE  k = d: dT_d = -sum beta dvar_d / sigma^4;  D + d: dP_d = sum beta (dmu_d / sigma^2 - mu_l dvar_d / sigma^4)
-//   rBCM      k = 2 g D + d: dT_gd;  (2 g + 1) D + d: dP_gd, with beta = 1, per root child g
-struct AggGradArgs {
-    const int64_t* row_ptr;     // as AggArgs
-    const int32_t* row_ent;
-    const int32_t* ent_leaf;
-    const double* mu;           // per (leaf, routed row), route order
-    const double* var;
-    const double* dmu;          // per entry and dimension: [pos + d * ld]
-    const double* dvar;
-    const double* coef;
-    const int32_t* group;
-    const double* agg_mu;       // n_t: the aggregated mean (mixture)
-    double* part;               // Wg x n_t
-    int64_t n_t;
-    int64_t ld;                 // route_total
-    int D;
-    int family;
-    int G;
-};
-
-__global__ __launch_bounds__(256) void agg_grad_partial_kernel(AggGradArgs a) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= a.n_t) return;
-    const int d = blockIdx.y, D = a.D;
-    const int64_t e0 = a.row_ptr[r], e1 = a.row_ptr[r + 1];
-    const double* dmu = a.dmu + (size_t)d * a.ld;
-    const double* dvar = a.dvar + (size_t)d * a.ld;
-    if (a.family == AGG_MIXTURE) {
-        const double mbar = a.agg_mu[r];
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-        for (int64_t e = e0; e < e1; ++e) {
-            const int pos = a.row_ent[e];
-            const double w = a.coef[a.ent_leaf[pos]];
-            const double dm = dmu[pos];
-            const double dv = a.var[pos] <= 0.0 ? 0.0 : dvar[pos];    // a clamped variance is a constant (a NaN one stays NaN)
-            s0 += w * dm;
-            s1 += w * dv;
-            s2 += w * ((a.mu[pos] - mbar) * dm);
-        }
-        a.part[(size_t)d * a.n_t + r] = s0;
-        a.part[(size_t)(D + d) * a.n_t + r] = s1;
-        a.part[(size_t)(2 * D + d) * a.n_t + r] = s2;
-    } else if (a.family == AGG_RBCM) {
-        for (int g = 0; g < a.G; ++g) {
-            a.part[((size_t)(2 * g) * D + d) * a.n_t + r] = 0.0;
-            a.part[((size_t)(2 * g + 1) * D + d) * a.n_t + r] = 0.0;
-        }
-        for (int64_t e = e0; e < e1; ++e) {
-            const int pos = a.row_ent[e];
-            const int g = a.group[a.ent_leaf[pos]];
-            const double v = a.var[pos];
-            const double t = 1.0 / v;
-            const double dv = dvar[pos];
-            a.part[((size_t)(2 * g) * D + d) * a.n_t + r] -= (t / v) * dv;
-            a.part[((size_t)(2 * g + 1) * D + d) * a.n_t + r] += t * dmu[pos] - (t * a.mu[pos] / v) * dv;
-        }
-    } else {
-        double s0 = 0.0, s1 = 0.0;
-        for (int64_t e = e0; e < e1; ++e) {
-            const int pos = a.row_ent[e];
-            const double v = a.var[pos];
-            const double t = a.coef[a.ent_leaf[pos]] / v;
-            const double dv = dvar[pos];
-            s0 -= (t / v) * dv;
-            s1 += t * dmu[pos] - (t * a.mu[pos] / v) * dv;
-        }
-        a.part[(size_t)d * a.n_t + r] = s0;
-        a.part[(size_t)(D + d) * a.n_t + r] = s1;
-    }
-}
-
-// Finish step on the (summed) gradient sums `gpart` and the total moment sums `part` of agg_finish_kernel (the formulas:
-// aggregate_input_gradients of the Python package, term by term).  One thread per (row, dimension); dmu_out / dvar_out are
-// n_t x D planes.  rBCM: ds/dx_d of the prior s = k(x*, x*) + noise is 2 x_d / l_d^2 for the linear kinds, 0 for the others.
-__global__ __launch_bounds__(256) void agg_grad_finish_kernel(const double* __restrict__ gpart, const double* __restrict__ part,
-                                                              int64_t n_t, int D, int family, int G, int plain,
-                                                              const KParam* __restrict__ kp, int prior_kid,
-                                                              const double* __restrict__ Xt, double* __restrict__ dmu_out,
-                                                              double* __restrict__ dvar_out) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_t) return;
-    const int d = blockIdx.y;
-    const size_t o = (size_t)d * n_t + r;
-    if (family == AGG_MIXTURE) {
-        const double sv = gpart[(size_t)(D + d) * n_t + r];
-        dmu_out[o] = gpart[o];
-        dvar_out[o] = plain ? sv : sv + 2.0 * gpart[(size_t)(2 * D + d) * n_t + r];
-    } else if (family == AGG_RBCM) {
-        const KParam p = kp[prior_kid];
-        const double s = prior_var(p, Xt, r, n_t, D) + p.noise;
-        const double x = Xt[o];
-        const double ds = p.kind == 2 ? 2.0 * x / p.l2[0] : (p.kind == 3 ? 2.0 * x * p.nh[d] : 0.0);
-        const double ds_s2 = ds / (s * s);
-        double C = 1.0 / s, dC = -ds_s2, m = 0.0, dm = 0.0;
-        for (int g = 0; g < G; ++g) {
-            const double T = part[(size_t)(2 * g + 1) * n_t + r];
-            if (T == 0.0) continue;                               // no leaf of this child saw the row
-            const double P = part[(size_t)(2 * g) * n_t + r];
-            const double dT = gpart[((size_t)(2 * g) * D + d) * n_t + r];
-            const double dP = gpart[((size_t)(2 * g + 1) * D + d) * n_t + r];
-            const double beta = 0.5 * (log(s) + log(T));
-            const double dbeta = 0.5 * (ds / s + dT / T);
-            C += beta * (T - 1.0 / s);
-            dC += dbeta * (T - 1.0 / s) + beta * (dT + ds_s2);
-            m += beta * P;
-            dm += dbeta * P + beta * dP;
-        }
-        const double mu = m / C;
-        dmu_out[o] = (dm - mu * dC) / C;
-        dvar_out[o] = -dC / (C * C);
-    } else {
-        const double P = part[r], T = part[n_t + r];
-        const double dT = gpart[o], dP = gpart[(size_t)(D + d) * n_t + r];
-        const double mu = P / T;
-        dmu_out[o] = (dP - mu * dT) / T;
-        dvar_out[o] = -dT / (T * T);
-    }
-}
-
-// The same aggregation for every resident target column (dsmgp_aggregate_columns, dsmgp_aggregate_columns_gradients): the means
-// are d_tmu [pos + q ld], their input gradients d_tigout [pos + d ld + q ld D]; the leaf variance and its gradient are shared by
-// the columns.  One thread per (test row, column), blockIdx.y = q, walks the row's entries in ascending entry order and
-// finishes in registers: no partial sums in memory, no atomics, and column q never reads another column, so it is the same bits
-// whatever Q is.  The operations are those of agg_partial_kernel / agg_finish_kernel and of the two gradient kernels above; an
-// rBCM row walks its entries once per group (the groups' sums in registers instead of G planes).
-struct AggColsArgs {
-    const int64_t* row_ptr;     // as AggArgs
-    const int32_t* row_ent;
-    const int32_t* ent_leaf;
-    const double* tmu;          // [pos + q * ld]
-    const double* var;          // [pos]
-    const double* tdmu;         // [pos + d * ld + q * ld * D]   (gradients only)
-    const double* dvar;         // [pos + d * ld]                (gradients only)
-    const double* coef;
-    const int32_t* group;
-    const KParam* kp;
-    const double* Xt;           // n_t x D (the rBCM prior)
-    double* out_m;              // moments: n_t x Q; gradients: [r + d * n_t + q * n_t * D]
-    double* out_v;
-    int64_t n_t;
-    int64_t ld;                 // route_total
-    int D, Q, family, G, plain, prior_kid;
-};
-
-__global__ __launch_bounds__(256) void agg_columns_kernel(AggColsArgs a) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= a.n_t) return;
-    const int q = blockIdx.y;
-    const int64_t e0 = a.row_ptr[r], e1 = a.row_ptr[r + 1];
-    const double* mu = a.tmu + (size_t)q * a.ld;
-    const size_t o = (size_t)q * a.n_t + r;
-    if (a.family == AGG_MIXTURE) {
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-        for (int64_t e = e0; e < e1; ++e) {
-            const int pos = a.row_ent[e];
-            const double w = a.coef[a.ent_leaf[pos]];
-            const double m = mu[pos];
-            double v = a.var[pos];
-            if (v <= 0.0) v = 1e-8;
-            s0 += w * m;
-            s1 += w * (m * m);
-            s2 += w * v;
-        }
-        a.out_m[o] = s0;
-        a.out_v[o] = a.plain ? s2 : s2 + (s1 - s0 * s0);
-    } else if (a.family == AGG_RBCM) {
-        const KParam p = a.kp[a.prior_kid];
-        const double s = prior_var(p, a.Xt, r, a.n_t, a.D) + p.noise;
-        double C = 1.0 / s, m = 0.0;
-        for (int g = 0; g < a.G; ++g) {
-            double S = 0.0, T = 0.0;
-            for (int64_t e = e0; e < e1; ++e) {
-                const int pos = a.row_ent[e];
-                if (a.group[a.ent_leaf[pos]] != g) continue;
-                const double t = 1.0 / a.var[pos];
-                S += t * mu[pos];
-                T += t;
-            }
-            if (T == 0.0) continue;
-            const double M = S / T;
-            const double beta = 0.5 * (log(s) - log(1.0 / T));
-            C += beta * T - beta / s;
-            m += M * (beta * T);
-        }
-        a.out_m[o] = m / C;
-        a.out_v[o] = 1.0 / C;
-    } else {
-        double s0 = 0.0, s1 = 0.0;
-        for (int64_t e = e0; e < e1; ++e) {
-            const int pos = a.row_ent[e];
-            const double bt = a.coef[a.ent_leaf[pos]] * (1.0 / a.var[pos]);
-            s0 += bt * mu[pos];
-            s1 += bt;
-        }
-        a.out_m[o] = s0 / s1;
-        a.out_v[o] = 1.0 / s1;
-    }
-}
-
-// Gradients: chunks of AGG_DC input dimensions in registers, so that an entry's indices, coefficient, mu and var are read once
-// per chunk and not once per dimension (once in all for D <= 8).
-constexpr int AGG_DC = 8;
-
-__global__ __launch_bounds__(256) void agg_columns_grad_kernel(AggColsArgs a) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= a.n_t) return;
-    const int q = blockIdx.y, D = a.D;
-    const int64_t e0 = a.row_ptr[r], e1 = a.row_ptr[r + 1];
-    const double* mu = a.tmu + (size_t)q * a.ld;
-    const double* dmq = a.tdmu + (size_t)q * a.ld * D;
-    double* om = a.out_m + (size_t)q * a.n_t * D + r;
-    double* ov = a.out_v + (size_t)q * a.n_t * D + r;
-    double mbar = 0.0;
-    if (a.family == AGG_MIXTURE)
-        for (int64_t e = e0; e < e1; ++e) {
-            const int pos = a.row_ent[e];
-            mbar += a.coef[a.ent_leaf[pos]] * mu[pos];
-        }
-    for (int d0 = 0; d0 < D; d0 += AGG_DC) {
-        const int nd = min(AGG_DC, D - d0);
-        if (a.family == AGG_MIXTURE) {
-            double s0[AGG_DC] = {}, s1[AGG_DC] = {}, s2[AGG_DC] = {};
-            for (int64_t e = e0; e < e1; ++e) {
-                const int pos = a.row_ent[e];
-                const double w = a.coef[a.ent_leaf[pos]];
-                const double c = mu[pos] - mbar;
-                const bool clamped = a.var[pos] <= 0.0;
-#pragma unroll
-                for (int k = 0; k < AGG_DC; ++k)
-                    if (k < nd) {
-                        const double dm = dmq[pos + (size_t)(d0 + k) * a.ld];
-                        const double dv = clamped ? 0.0 : a.dvar[pos + (size_t)(d0 + k) * a.ld];
-                        s0[k] += w * dm;
-                        s1[k] += w * dv;
-                        s2[k] += w * (c * dm);
-                    }
-            }
-#pragma unroll
-            for (int k = 0; k < AGG_DC; ++k)
-                if (k < nd) {
-                    om[(size_t)(d0 + k) * a.n_t] = s0[k];
-                    ov[(size_t)(d0 + k) * a.n_t] = a.plain ? s1[k] : s1[k] + 2.0 * s2[k];
-                }
-        } else if (a.family == AGG_RBCM) {
-            const KParam p = a.kp[a.prior_kid];
-            const double s = prior_var(p, a.Xt, r, a.n_t, D) + p.noise;
-            double C = 1.0 / s, m = 0.0, ds[AGG_DC], dC[AGG_DC], dm[AGG_DC];
-#pragma unroll
-            for (int k = 0; k < AGG_DC; ++k) {
-                double x = 0.0;
-                if (k < nd) x = a.Xt[r + (size_t)(d0 + k) * a.n_t];
-                ds[k] = k < nd ? (p.kind == 2 ? 2.0 * x / p.l2[0] : (p.kind == 3 ? 2.0 * x * p.nh[d0 + k] : 0.0)) : 0.0;
-                dC[k] = -(ds[k] / (s * s));
-                dm[k] = 0.0;
-            }
-            for (int g = 0; g < a.G; ++g) {
-                double T = 0.0, P = 0.0, dT[AGG_DC] = {}, dP[AGG_DC] = {};
-                for (int64_t e = e0; e < e1; ++e) {
-                    const int pos = a.row_ent[e];
-                    if (a.group[a.ent_leaf[pos]] != g) continue;
-                    const double v = a.var[pos], ml = mu[pos];
-                    const double t = 1.0 / v;
-                    P += t * ml;
-                    T += t;
-#pragma unroll
-                    for (int k = 0; k < AGG_DC; ++k)
-                        if (k < nd) {
-                            const double dv = a.dvar[pos + (size_t)(d0 + k) * a.ld];
-                            dT[k] -= (t / v) * dv;
-                            dP[k] += t * dmq[pos + (size_t)(d0 + k) * a.ld] - (t * ml / v) * dv;
-                        }
-                }
-                if (T == 0.0) continue;
-                const double beta = 0.5 * (log(s) + log(T));
-                C += beta * (T - 1.0 / s);
-                m += beta * P;
-#pragma unroll
-                for (int k = 0; k < AGG_DC; ++k) {
-                    const double dbeta = 0.5 * (ds[k] / s + dT[k] / T);
-                    dC[k] += dbeta * (T - 1.0 / s) + beta * (dT[k] + ds[k] / (s * s));
-                    dm[k] += dbeta * P + beta * dP[k];
-                }
-            }
-            const double mua = m / C;
-#pragma unroll
-            for (int k = 0; k < AGG_DC; ++k)
-                if (k < nd) {
-                    om[(size_t)(d0 + k) * a.n_t] = (dm[k] - mua * dC[k]) / C;
-                    ov[(size_t)(d0 + k) * a.n_t] = -dC[k] / (C * C);
-                }
-        } else {
-            double T = 0.0, P = 0.0, dT[AGG_DC] = {}, dP[AGG_DC] = {};
-            for (int64_t e = e0; e < e1; ++e) {
-                const int pos = a.row_ent[e];
-                const double v = a.var[pos], ml = mu[pos];
-                const double t = a.coef[a.ent_leaf[pos]] / v;
-                P += (a.coef[a.ent_leaf[pos]] * (1.0 / v)) * ml;
-                T += a.coef[a.ent_leaf[pos]] * (1.0 / v);
-#pragma unroll
-                for (int k = 0; k < AGG_DC; ++k)
-                    if (k < nd) {
-                        const double dv = a.dvar[pos + (size_t)(d0 + k) * a.ld];
-                        dT[k] -= (t / v) * dv;
-                        dP[k] += t * dmq[pos + (size_t)(d0 + k) * a.ld] - (t * ml / v) * dv;
-                    }
-            }
-            const double mua = P / T;
-#pragma unroll
-            for (int k = 0; k < AGG_DC; ++k)
-                if (k < nd) {
-                    om[(size_t)(d0 + k) * a.n_t] = (dP[k] - mua * dT[k]) / T;
-                    ov[(size_t)(d0 + k) * a.n_t] = -dT[k] / (T * T);
-                }
-        }
-    }
-}
-
-// Score sums (src/scorefunctions.jl:6-16) in two passes for the standard errors: pass 0 sums se, ae and the nlpd
-// terms; pass 1 sums (se - mean se)^2 and (ae - mean ae)^2.  Per-block tree reduction, blocks combined in block order
-// by the host: fixed summation order.
-__global__ __launch_bounds__(256) void agg_scores_kernel(const double* __restrict__ y, const double* __restrict__ mu,
-                                                         const double* __restrict__ var, int64_t n_t, int pass,
-                                                         double mean_se, double mean_ae, double* __restrict__ out) {
-    __shared__ double red[3][256];
-    const int t = threadIdx.x;
-    const int64_t r = (int64_t)blockIdx.x * 256 + t;
-    double a = 0.0, b = 0.0, c = 0.0;
-    if (r < n_t) {
-        const double d = y[r] - mu[r];
-        const double se = d * d, ae = fabs(d);
-        if (pass == 0) {
-            a = se;
-            b = ae;
-            const double sd = sqrt(var[r]);                       // Normal(mu, sqrt(var)), :16
-            const double zz = d / sd;
-            c = 0.5 * (zz * zz + 1.8378770664093454835606594728112) + log(sd);
-        } else {
-            a = (se - mean_se) * (se - mean_se);
-            b = (ae - mean_ae) * (ae - mean_ae);
-        }
-    }
-    red[0][t] = a;
-    red[1][t] = b;
-    red[2][t] = c;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) {
-            red[0][t] += red[0][t + o];
-            red[1][t] += red[1][t + o];
-            red[2][t] += red[2][t + o];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        out[3 * (size_t)blockIdx.x] = red[0][0];
-        out[3 * (size_t)blockIdx.x + 1] = red[1][0];
-        out[3 * (size_t)blockIdx.x + 2] = red[2][0];
     }
 }
 

@@ -11,8 +11,8 @@ mu = mean + k*.alpha and sigma^2 = k(x*, x*) - |L^-1 k*|^2 + noise (src/gaussian
   table/...       a leaf table of 41 leaves for the low-level ABI: 8 observation sets (n = 130 .. 512) repeated over 5
                   replicas, a COPY and a PREFIX leaf among them and one leaf without routed rows; four kernel ids.  Every
                   replica's leaves partition the 600 test rows, so each row has one entry per replica.  Per-entry moments,
-                  per-leaf mll, and the aggregations agg_partial_kernel / agg_finish_kernel evaluate (kernels.hpp, the
-                  comment above AggArgs) for mixture (plain off / on), PoE, gPoE and rBCM (a row-dependent prior kernel,
+                  per-leaf mll, and the aggregations agg_partial_kernel / agg_finish_kernel evaluate (kernels_agg.hpp, the
+                  comment at its head) for mixture (plain off / on), PoE, gPoE and rBCM (a row-dependent prior kernel,
                   rows that no leaf of group 2 sees), each with its five scores; the same table with the targets offset by
                   1000 for the mixture, where S1 - S0^2 cancels.
   config1/...     the README example (make_golden.config1) on the tree of oracle/tree.py: leaf mlls, update! (the

@@ -1,7 +1,7 @@
 """The aggregation formula of predict and the tolerances of tests/golden/gp_pred.npz, in one place.
 
-`aggregate` is what agg_partial_kernel and agg_finish_kernel evaluate (deepstructuredmixtures_amd/csrc/kernels.hpp, the
-comment above AggArgs), written once over any arithmetic: tests/golden/make_pred_golden.py runs it at 50 digits (mpmath),
+`aggregate` is what agg_partial_kernel and agg_finish_kernel evaluate (deepstructuredmixtures_amd/csrc/kernels_agg.hpp, the
+comment at its head and the agg_* rule functions), written once over any arithmetic: tests/golden/make_pred_golden.py runs it at 50 digits (mpmath),
 the tests run it on `Prop` values to carry the per-entry tolerances through the same operations.  Every tolerance the
 prediction tests use is a function below; each docstring says where it comes from."""
 import math
