@@ -3643,6 +3643,32 @@ int dsmgp_set_tree(dsmgp_ctx* c, int64_t n_nodes, const int8_t* kind, const int6
     if (stack_need > ROUTE_STACK)
         return fail(c, DSMGP_E_ARG, "set_tree: the tree needs " + std::to_string(stack_need) + " pending nodes per row, the walk holds " +
                                         std::to_string(ROUTE_STACK));
+    // The device path keeps one bit per (leaf, row) and writes a row's entries in the order its walk meets them, where the
+    // host registration orders them by leaf: the two agree only when the walk (depth-first, children in order) meets the held
+    // leaves in strictly ascending order.
+    {
+        std::vector<char> seen((size_t)c->L, 0);
+        std::vector<int32_t> pending(1, 0);
+        int last = -1;
+        int64_t met = 0;
+        while (!pending.empty()) {
+            const int32_t i = pending.back();
+            pending.pop_back();
+            if (++met > n_nodes) return fail(c, DSMGP_E_ARG, "set_tree: a node is the child of two parents");
+            if (kind[i] != 0) {
+                for (int32_t j = nch[(size_t)i] - 1; j >= 0; --j) pending.push_back(first[(size_t)i] + j);
+                continue;
+            }
+            const int l = leaf[(size_t)i];
+            if (l < 0) continue;
+            if (seen[(size_t)l]) return fail(c, DSMGP_E_ARG, "set_tree: leaf " + std::to_string(l) + " is named twice; the device routing holds a leaf once per row");
+            if (l < last)
+                return fail(c, DSMGP_E_ARG, "set_tree: the leaves are not numbered depth-first (leaf " + std::to_string(l) + " follows leaf " +
+                                                std::to_string(last) + "); the device routing needs them ascending along the walk");
+            seen[(size_t)l] = 1;
+            last = l;
+        }
+    }
     HIPCHK(c, hipSetDevice(c->device));
     free_tree(c);
     auto up = [&](auto& buf, const auto* src, size_t n) -> int {

@@ -246,7 +246,9 @@ int dsmgp_set_test(dsmgp_ctx* ctx, const double* Xt /* n_t x D column-major */, 
 /* predict(model, x) on rows the model has not seen (the reference's normal call, src/common.jl:304-307, src/plot.jl:40): the routing
  * of src/common.jl:101-122,181-196,275-292 on the device.  dsmgp_set_tree registers the model's tree once per leaf table (flat
  * arrays as dsmgp_tree_route takes them; leaf_id = index in THIS context's leaf table, -1 = a region another rank holds; a new
- * leaf table or new training data drop it).  dsmgp_set_test_routed(Xt, n_t, D) then is dsmgp_set_test with the routes made on the
+ * leaf table or new training data drop it).  The held leaves (leaf_id >= 0) must be numbered depth-first, children in order, each
+ * named by one region: DSMGP_E_ARG otherwise, since the device path keeps one bit per (leaf, row) and a row's entries in the
+ * order its walk meets them (dsmgp_tree_route builds lists for any tree).  dsmgp_set_test_routed(Xt, n_t, D) then is dsmgp_set_test with the routes made on the
  * device: one thread per row walks the tree, a bitmap per leaf turns the visits into the same CSR (rows ascending per leaf) and the
  * same per-row entry index the host path builds -- entry by entry -- and only the L + 1 per-leaf offsets come back to the host
  * (they size the K_tn arena and the sweep's task lists).  DSMGP_E_DOMAIN: a row outside the region of a split node (NaN included).
