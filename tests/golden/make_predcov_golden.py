@@ -37,6 +37,7 @@ import io  # noqa: E402
 import zipfile  # noqa: E402
 
 from make_pred_golden import single_rows, uniform, normal  # noqa: E402
+import mp_kernels as mpk  # noqa: E402
 
 mp.mp.dps = 50
 SQ = np.sqrt
@@ -68,7 +69,7 @@ def entry_tol(S, kss, noise):
 
 
 class MPCov:
-    """One leaf at 50 digits, any kernel kind of include/dsmgp_hip.h (0-8); loghyp = the library hyper-vector without the noise."""
+    """One leaf at 50 digits, any kernel kind of include/dsmgp_hip.h (0-10); loghyp = the library hyper-vector without the noise."""
 
     def __init__(self, kind, loghyp, logNoise, X):
         self.kind = kind
@@ -76,11 +77,13 @@ class MPCov:
         n, D = self.X.shape
         h = [mp.mpf(float(v)) for v in loghyp]
         self.noise = mp.e ** (2 * mp.mpf(float(logNoise)))
-        ard = kind in (1, 3, 4, 7, 8)
+        ard = kind in mpk.ARD
         nl = D if ard else 1
         il2 = [1 / mp.e ** (2 * v) for v in h[:nl]]
         self.il2 = il2 if ard else il2 * D
         self.s2 = mp.mpf(1) if kind in (2, 3) else mp.e ** (2 * h[nl])
+        if kind in mpk.RQ:          # [logl..., loga, logs]: the table of mp_kernels
+            self.il2, self.al, self.s2 = mpk.unpack(kind, h, D)
         self.x = [self.row(r) for r in self.X]
         c = self.noise + mp.mpf("1e-8")
         K = [[self.k(self.x[i], self.x[j]) for j in range(i + 1)] for i in range(n)]
@@ -102,6 +105,8 @@ class MPCov:
 
     def k(self, a, b):
         kind = self.kind
+        if kind in mpk.RQ:
+            return mpk.value(kind, a, b, self.il2, self.al, self.s2)
         if kind == 1:
             return self.s2 * mp.fsum(mp.e ** (-((p - q) ** 2) * il / 2) for p, q, il in zip(a, b, self.il2))
         if kind in (2, 3):

@@ -12,6 +12,8 @@ to rounding only), and -- stationary kinds, n_t > 4 -- rows 2 and 3 at +-1e3, wh
 values there are below 1e-300 and stored as the 0.0 they round to).  The targets of (130, 129, 3) are scaled to |y| > 500.
 Every case is checked here against mp.diff of the 50-digit mu(x), sigma^2(x) at three rows, and the float64 dense helper
 (tests/predgrad_dense.py) must stay within predgrad_dense.tolerances of the 50 digits; cond_2(K_y) <= 1e6 is stored.
+MPGrad and run_case also serve make_wide_golden.py (every kind, the rational quadratic ones through mp_kernels, at D = 8 .. 36 with
+distinct length-scales: gp_predgrad_wide.npz); this file's own cases and bytes do not depend on that.
 
 Aggregates.  On the first 120 test rows of the 41-leaf table of gp_pred.npz (loaded, not modified): per-entry gradients from the
 dense helper in float64 (stored: they are the INPUT of the aggregation, beside the table's own per-entry mu, var) and the
@@ -35,6 +37,7 @@ sys.path.insert(0, HERE)
 
 from deepstructuredmixtures_amd import datagen  # noqa: E402
 import dense_kernels as dk  # noqa: E402
+import mp_kernels as mpk  # noqa: E402
 import predgrad_dense as pgd  # noqa: E402
 from pred_tolerance import aggregate, row_entries  # noqa: E402
 from make_predcov_golden import savez_reproducible  # noqa: E402
@@ -83,6 +86,8 @@ class MPGrad:
         self.il2 = il2 if kind in dk.ARD else il2 * D
         self.s2 = mp.mpf(1) if kind in dk.LINEAR else mp.e ** (2 * h[nl])
         self.nu2 = 3 if kind in (5, 7) else 5
+        if kind in dk.RQ:           # [logl..., loga, logs]: the table of mp_kernels
+            self.il2, self.al, self.s2 = mpk.unpack(kind, h, D)
         self.x = [[mp.mpf(float(v)) for v in r] for r in X]
         self.mean = mp.mpf(float(mean))
         c = self.noise + mp.mpf("1e-8")
@@ -117,6 +122,8 @@ class MPGrad:
 
     def k(self, a, b):
         kind = self.kind
+        if kind in dk.RQ:
+            return mpk.value(kind, a, b, self.il2, self.al, self.s2)
         if kind == 1:
             return self.s2 * mp.fsum(mp.e ** (-((p - q) ** 2) * il / 2) for p, q, il in zip(a, b, self.il2))
         if kind in dk.LINEAR:
@@ -130,6 +137,8 @@ class MPGrad:
     def dk(self, t, xi):
         """[dk(t, xi) / dt_d for d]: the formulas of the issue, literally."""
         kind = self.kind
+        if kind in dk.RQ:
+            return mpk.d_input(kind, t, xi, self.il2, self.al, self.s2)
         if kind in dk.LINEAR:
             return [q * il for q, il in zip(xi, self.il2)]
         if kind == 1:
@@ -160,14 +169,16 @@ class MPGrad:
         return dmu, dvar
 
 
-def run_case(spec):
+def run_case(spec, loghyp=None, diff_dims=None):
+    """One case: (name, out = dmu | dvar, meta).  `loghyp` replaces loghyp_of's vector and `diff_dims` the dimensions mp.diff is
+    taken along (make_predgrad_wide_golden.py); the far rows are those of predgrad_dense.case_inputs."""
     mp.mp.dps = 50
     name, kind, n, nt, D = spec
     X, y, Xt, dup = inputs(n, nt, D)
     Xt = Xt.copy()
-    if kind not in dk.LINEAR and nt > 4:
+    if kind not in dk.LINEAR and kind not in dk.RQ and nt > 4:
         Xt[2], Xt[3] = 1e3, -1e3
-    loghyp = loghyp_of(kind, D)
+    loghyp = loghyp_of(kind, D) if loghyp is None else np.asarray(loghyp, dtype=np.float64)
     logNoise = float(np.log(0.1))
     mean = float(np.mean(y)) + 0.25
     g = MPGrad(kind, loghyp, logNoise, X, y, mean)
@@ -187,7 +198,7 @@ def run_case(spec):
     worst_diff = 0.0
     for r in sorted({0, dup[0], nt - 1}):
         t = [mp.mpf(float(v)) for v in Xt[r]]
-        for d in range(D if D <= 3 else 2):
+        for d in (range(D if D <= 3 else 2) if diff_dims is None else diff_dims):
             def at(u, d=d, t=t):
                 return t[:d] + [u] + t[d + 1:]
             dm = mp.diff(lambda u: g.mu(at(u)), t[d])

@@ -9,7 +9,7 @@ with the kernel derivatives of dense_kernels.d_input, every kind.  `loghyp` is t
 import numpy as np
 
 from dense_gp import DenseGP
-from dense_kernels import LINEAR, grad_scale, prior_diag
+from dense_kernels import LINEAR, RQ, grad_scale, prior_diag
 from pred_tolerance import RTOL, ATOL
 
 
@@ -33,14 +33,14 @@ def tolerances(kind, loghyp, logNoise, X, y, Xt, dmu, dvar):
 def case_inputs(z, name):
     """One single-leaf case of tests/golden/gp_predgrad.npz as the tests use it.  Cases of one (n, n_t, D) share the stored inputs
     `in_<n>_<nt>_<D>/{X, y, Xt}`; for the stationary kinds with n_t > 4 rows 2 and 3 of Xt are put at +-1e3 (the rule of
-    tests/golden/make_predgrad_golden.py).  meta = kind, n, n_t, D, mean, logNoise, cond, the pair of the row listed twice, then
+    tests/golden/make_predgrad_golden.py; not for the rational quadratic kinds, whose tails do not underflow).  meta = kind, n, n_t, D, mean, logNoise, cond, the pair of the row listed twice, then
     the hyper-vector without the noise; out = dmu | dvar (n_t x 2 D)."""
     m = z[name + "/meta"]
     kind, n, nt, D = (int(v) for v in m[:4])
     g = f"in_{n}_{nt}_{D}"
     Xt = np.array(z[g + "/Xt"], order="F")
     far = []
-    if kind not in LINEAR and nt > 4:
+    if kind not in LINEAR and kind not in RQ and nt > 4:
         Xt[2], Xt[3] = 1e3, -1e3
         far = [2, 3]
     out = z[name + "/out"]

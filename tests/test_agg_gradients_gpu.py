@@ -102,9 +102,10 @@ def test_leaf_table(ctx, name, path):
 # ------------------------------------------------------------------------------------------ shapes of the row kernel
 
 @pytest.mark.parametrize("name", ["mixture", "plain", "poe", "gpoe", "rbcm"])
-@pytest.mark.parametrize("n_t,D", [(1, 3), (255, 1), (257, 3), (257, 40)])
+@pytest.mark.parametrize("n_t,D", [(1, 3), (255, 1), (257, 3), (257, 40), (257, 8), (257, 9), (70, 17)])
 def test_shapes(ctx, n_t, D, name):
-    """n_t on both sides of the 256-thread block, D = 1, 3, 40; rows with no, one and up to six entries; G = 3 groups of which
+    """n_t on both sides of the 256-thread block, D = 1, 3, 40 and, around the chunk of 8 dimensions the kernels work in, D = 8
+    (exactly one chunk), 9 (a tail of one) and 17 (three rounds); rows with no, one and up to six entries; G = 3 groups of which
     some rows see one or two; the rBCM prior is the ArdLinear id.  A row without entries gets what the formulas give (NaN for
     the products, 0 and ds/dx for the others), as the host function does."""
     t = ac.small_table(n_t, D, 9100 + n_t + D)
@@ -444,14 +445,8 @@ def _device_columns(ctx, s):
     return mu, var, dmu, dvar
 
 
-@pytest.mark.parametrize("Q", [1, 3, 17])
-def test_columns_against_the_host(ctx, Q):
-    """Q = 1, 3, 17 (across Qpad = 16), every family, column by column: the moments within twice agg_tol of
-    pred_tolerance.aggregate, the gradients within tolerance of the host function, both on the context's own per-entry arrays;
-    rows without entries as dsmgp_aggregate gives them; a repeated call the same bits; and the single-y state (aggregate_finish,
-    aggregate_gradients_finish, scores) the same bits before and after."""
-    n_t, D = 70, 3
-    t = ac.small_table(n_t, D, 9600)
+def _columns_against_the_host(ctx, Q, n_t, D, seed):
+    t = ac.small_table(n_t, D, seed)
     Y, mean = _columns(t, Q)
     ac.small_predict(ctx, t)
     ctx.solve_targets(Y, mean)
@@ -479,6 +474,21 @@ def test_columns_against_the_host(ctx, Q):
         after = _bits(ctx.aggregate_finish(plain=s["plain"], prior_kernel_id=s["prior_kid"]),
                       ctx.aggregate_gradients(plain=s["plain"], prior_kernel_id=s["prior_kid"]), tuple(ctx.scores(yt).values()))
         assert _all_same(before, after), name
+
+
+@pytest.mark.parametrize("Q", [1, 3, 17])
+def test_columns_against_the_host(ctx, Q):
+    """Q = 1, 3, 17 (across Qpad = 16), every family, column by column: the moments within twice agg_tol of
+    pred_tolerance.aggregate, the gradients within tolerance of the host function, both on the context's own per-entry arrays;
+    rows without entries as dsmgp_aggregate gives them; a repeated call the same bits; and the single-y state (aggregate_finish,
+    aggregate_gradients_finish, scores) the same bits before and after."""
+    _columns_against_the_host(ctx, Q, 70, 3, 9600)
+
+
+def test_columns_against_the_host_past_one_chunk_of_dimensions(ctx):
+    """The same checks at D = 9, Q = 3: agg_columns_grad_kernel works in chunks of 8 dimensions, so a second round with a tail
+    of one."""
+    _columns_against_the_host(ctx, 3, 70, 9, 9650)
 
 
 def test_one_column_of_y_equals_the_single_y_calls(ctx):

@@ -114,8 +114,10 @@ def _check_case(ctx, c, path, tag):
 @pytest.mark.parametrize("path", ["standalone", "joint"])
 @pytest.mark.parametrize("kind", range(9))
 def test_fixture_cases_against_50_digits(ctx, kind, path):
-    """Every fixture case of the kind (five shapes, D = 1 and 3, D = 40 for IsoSE and ArdSEProduct) on both routes to K_tn L^-T,
-    against the 50 digits within the tolerance; then the exact properties on bits."""
+    """Every fixture case of the kind (five shapes, D = 1 and 3; D = 40 for IsoSE and ArdSEProduct, whose 40 length-scales are
+    EQUAL, so those two cases cannot tell one dimension's factor from another's) on both routes to K_tn L^-T, against the 50
+    digits within the tolerance; then the exact properties on bits.  Every kind past one chunk of 8 dimensions with distinct
+    length-scales: tests/test_wide_inputs_gpu.py."""
     names = [n for n in CASE_NAMES if n.startswith(KIND_NAMES[kind] + "_")]
     assert len(names) >= 10
     for name in names:
