@@ -12,6 +12,7 @@
 #include "kernels_sample.hpp"
 #include "kernels_kfold.hpp"
 #include "kfold_plan.hpp"
+#include "leaf_chunks.hpp"
 #include "ctx_state.hpp"
 #include "dev_owner.hpp"
 
@@ -33,6 +34,7 @@
 
 using namespace dsmgp;
 using namespace ctx_state;
+using leaf_chunks::for_leaf_chunks;
 
 namespace {
 
@@ -1840,12 +1842,11 @@ int build_plan(dsmgp_ctx* c, DevArena&& adoptF = DevArena(), DevArena&& adoptDin
     {
         int maxpad = 0;
         for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
-        for (int l0 = 0; l0 < L; l0 += 32768) {
-            const int cnt = std::min(32768, L - l0);
-            dim3 grid((maxpad + 255) / 256, cnt);
+        for_leaf_chunks((size_t)L, [&](size_t leaf0, size_t cnt) {
+            dim3 grid((maxpad + 255) / 256, (unsigned)cnt);
             gather_leaf_kernel<<<grid, 256, 0, c->stream>>>(c->d_leaves.p, c->d_obs_ptr.p, c->d_obs_idx.p, c->dX.p, c->dy.p,
-                                                            c->N, c->D, l0);
-        }
+                                                            c->N, c->D, (int)leaf0);
+        });
         HIPCHK(c, hipGetLastError());
     }
     // The eight-wave fused tile tasks write the 16-row blocks of a factor that hold data and nothing else: the rows below them
@@ -1880,10 +1881,9 @@ int build_plan(dsmgp_ctx* c, DevArena&& adoptF = DevArena(), DevArena&& adoptDin
         if (int rc = dev_upload(c, zrows, zr)) return rc;
         if (int rc = dev_upload(c, zupper, zu)) return rc;
         if (!zr.empty()) zero_pad_rows_kernel<<<(int)zr.size(), 256, 0, c->stream>>>(zrows.p);
-        for (size_t b0 = 0; b0 < zu.size(); b0 += 32768) {
-            const size_t cnt = std::min<size_t>(32768, zu.size() - b0);
+        for_leaf_chunks(zu.size(), [&](size_t b0, size_t cnt) {
             zero_upper_blocks_kernel<<<dim3((unsigned)cnt, (unsigned)std::min(maxnb, 64)), 256, 0, c->stream>>>(zupper.p + b0);
-        }
+        });
         const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
         HIPCHK(c, e1);
         HIPCHK(c, e2);
@@ -2397,7 +2397,9 @@ int ensure_alpha(dsmgp_ctx* c) {
     HIPCHK(c, hipEventRecord(ev.a, c->stream));
     int maxpad = 0;
     for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
-    copy_z_kernel<<<dim3((maxpad + 255) / 256, c->L), 256, 0, c->stream>>>(c->d_leaves.p);
+    for_leaf_chunks((size_t)c->L, [&](size_t leaf0, size_t cnt) {
+        copy_z_kernel<<<dim3((maxpad + 255) / 256, (unsigned)cnt), 256, 0, c->stream>>>(c->d_leaves.p, (int)leaf0);
+    });
     for (int s = 0; s < c->solve_steps; ++s) {
         const int n = c->bwd_off[s + 1] - c->bwd_off[s];
         if (n > 0) solve_bwd_kernel<<<n, 256, 0, c->stream>>>(c->bwd.p + c->bwd_off[s]);
@@ -2443,7 +2445,9 @@ int enqueue_fit(dsmgp_ctx* c, StepLists (*phases)[2], bool joint, PhaseTimer& pt
     {
         int maxpad = 0;
         for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
-        copy_vec_kernel<<<dim3((maxpad + 255) / 256, L), 256, 0, c->stream>>>(c->d_leaves.p);
+        for_leaf_chunks((size_t)L, [&](size_t leaf0, size_t cnt) {
+            copy_vec_kernel<<<dim3((maxpad + 255) / 256, (unsigned)cnt), 256, 0, c->stream>>>(c->d_leaves.p, (int)leaf0);
+        });
     }
     if (int rc = run_lanes(c, phases, 0, pt, true)) return rc;
     // 3. prefix leaves: their leading blocks from where they are, continue (src/fit.jl:276-278).  (A table without a PREFIX
@@ -3300,11 +3304,10 @@ int register_test(dsmgp_ctx* c, HostLog& hl, const std::vector<int>* first) {
     }
     if (int rc = stage_upload(c, c->d_leaves.p, c->h_leaves.data(), (size_t)L * sizeof(LeafDev))) return rc;
     if (maxpad > 0) {
-        for (int l0 = 0; l0 < L; l0 += 32768) {
-            const int cnt = std::min(32768, L - l0);
-            gather_test_kernel<<<dim3((maxpad + 255) / 256, cnt), 256, 0, c->stream>>>(
-                c->d_leaves.p, c->d_route_ptr.p, c->d_route_idx.p, c->dXt.p, n_t, c->D, l0);
-        }
+        for_leaf_chunks((size_t)L, [&](size_t leaf0, size_t cnt) {
+            gather_test_kernel<<<dim3((maxpad + 255) / 256, (unsigned)cnt), 256, 0, c->stream>>>(
+                c->d_leaves.p, c->d_route_ptr.p, c->d_route_idx.p, c->dXt.p, n_t, c->D, (int)leaf0);
+        });
         HIPCHK(c, hipGetLastError());
     }
     {
@@ -5558,11 +5561,11 @@ int dsmgp_solve_targets(dsmgp_ctx* c, const double* Y, int64_t N, int32_t Q, int
     {
         int maxpad = 0;
         for (auto& lf : c->leaves) maxpad = std::max(maxpad, lf.npad);
-        for (int l0 = 0; l0 < L; l0 += 32768) {
-            const int cnt = std::min(32768, L - l0);
-            targets_gather_kernel<<<dim3((maxpad + 255) / 256, cnt), 256, 0, c->stream>>>(
-                c->d_leaves.p, c->d_obs_ptr.p, c->d_obs_idx.p, c->d_tY.p, N, Q, qpad, c->d_tmean.p, L, c->arenaT.p, c->d_toff.p, l0);
-        }
+        for_leaf_chunks((size_t)L, [&](size_t leaf0, size_t cnt) {
+            targets_gather_kernel<<<dim3((maxpad + 255) / 256, (unsigned)cnt), 256, 0, c->stream>>>(
+                c->d_leaves.p, c->d_obs_ptr.p, c->d_obs_idx.p, c->d_tY.p, N, Q, qpad, c->d_tmean.p, L, c->arenaT.p, c->d_toff.p,
+                (int)leaf0);
+        });
     }
     if (int rc = fork_lanes(c, c->tfwd_lanes)) return rc;
     for (int s = 0; s < c->tfwd_steps; ++s)

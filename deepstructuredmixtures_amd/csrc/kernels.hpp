@@ -3367,15 +3367,15 @@ __global__ __launch_bounds__(256) void mll_kernel(const LeafDev* __restrict__ le
 }
 
 // w = z (start of the backward sweep; z itself stays for the predictive mean)
-__global__ void copy_z_kernel(const LeafDev* __restrict__ leaves) {
-    const LeafDev lf = leaves[blockIdx.y];
+__global__ void copy_z_kernel(const LeafDev* __restrict__ leaves, int leaf0) {
+    const LeafDev lf = leaves[leaf0 + blockIdx.y];
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r < lf.npad) lf.w[r] = lf.z[r];
 }
 
 // w = yc (start of the forward sweep)
-__global__ void copy_vec_kernel(const LeafDev* __restrict__ leaves) {
-    const LeafDev lf = leaves[blockIdx.y];
+__global__ void copy_vec_kernel(const LeafDev* __restrict__ leaves, int leaf0) {
+    const LeafDev lf = leaves[leaf0 + blockIdx.y];
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r < lf.npad) lf.w[r] = lf.yc[r];
 }

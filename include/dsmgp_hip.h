@@ -102,7 +102,13 @@ int dsmgp_set_train(dsmgp_ctx* ctx, const double* X /* N x D */, const double* y
                     int64_t N, int32_t D);
 
 /* leaf table = output of buildTree (src/treeStructure.jl:245-307): obs lists in CSR form
- * (ascending 0-based row indices), kernel id (0-based), ConstMean value per leaf (src/means.jl:7-14) */
+ * (ascending 0-based row indices), kernel id (0-based), ConstMean value per leaf (src/means.jl:7-14).
+ * The leaf count L of a context is bounded by device memory only: every launch with one grid row per leaf is cut into runs
+ * of 32,768 leaves, so no grid dimension grows with L beyond that.  Tables of 33,000 and 65,600 leaves are part of the test
+ * suite.  dsmgp_memory's `needed` covers the arenas of the fit only (factor, Dinv, four vectors and the gathered inputs of
+ * every leaf: about 268 KB per leaf of up to 128 rows, measured).  L^-T of a gradient, LOO or k-fold pass, the target columns
+ * and the k-fold arenas come ON TOP and are not in `needed`: by the code L^-T is another npad^2 doubles per factor owner, about
+ * 131 KB per leaf of up to 128 rows (not measured). */
 int dsmgp_set_leaves(dsmgp_ctx* ctx, int32_t L, const int64_t* obs_ptr /* L+1 */,
                      const int64_t* obs_idx, const int32_t* kernel_id, const double* mean /* L */);
 
